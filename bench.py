@@ -12,14 +12,21 @@ when N > 1).  Inputs (weights, initial noise, text embeddings) are resident in H
 region.  Weak scaling: 64 images per GPU.  Synthetic, seeded data: there is no network for the
 published checkpoint, so weights are the deterministic synthetic 101 M-parameter fill.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
-  roofline      the dominant kernel class (by HIP-event time inside the timed region) against the
-                2.5 PFLOP/s dense bf16 MFMA peak
-  cpu_baseline  the same module graph on the host cores, timed in this run on a bounded sample of the workload
-                (a full 35-step CFG sample of a small batch): the pure-PyTorch restatement (oracle/torch_ref.py:
-                the ATen CPU kernels the reference itself would run) as the headline value, and the fp32 C
-                restatement (oracle/tld_oracle.c) as a second line -- reported baselines, never part of the
-                measured path
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the K steps and
+prints the line: nothing else runs on the device or the host cores.
+
+  --dump-outputs DIR  after the timed steps, write what the last one returned (the final latents, all ranks' images)
+                      as DIR/latents.npy, float32; inputs are seeded, so two builds can be compared output for output
+  --full              also measure what the headline does not need, in the same line:
+      roofline      the dominant kernel class (by HIP-event time inside the timed region, after an untimed pass over
+                    every class) against the 2.5 PFLOP/s dense bf16 MFMA peak
+      power         socket power / shader clock on extra steps after the timed region (hwmon, best effort)
+      cpu_baseline  the same module graph on the host cores, timed in this run on a bounded sample of the workload
+                    (a full 35-step CFG sample of a small batch): the pure-PyTorch restatement (oracle/torch_ref.py:
+                    the ATen CPU kernels the reference itself would run) as the headline value, and the fp32 C
+                    restatement (oracle/tld_oracle.c) as a second line -- reported baselines, never part of the
+                    measured path
+                    (--no-profile / --no-power / --no-cpu-baseline drop one of them from a --full run)
 """
 import argparse
 import json
@@ -39,6 +46,18 @@ CFG = 6.0
 GFLOP_PER_SAMPLE_FWD = 46.163      # SURVEY.md Appendix B (N=256, d=768, L=12), reference op count
 GFLOP_BY_IMAGE_SIZE = {32: 46.163, 64: 213.466, 128: 1317.543}   # Appendix B, per sample-forward
 MFMA_PEAK_TFLOPS = 2500.0          # dense bf16, /opt/skills/guides/MI355X_MICROARCH.md
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(out_dir, latents):
+    """DIR/latents.npy: the [images, 4, S, S] latents a step returned, float32.  Above DUMP_LIMIT_BYTES a fixed, seeded
+    subset of whole images is kept, in batch order."""
+    a = latents.float().cpu().numpy()
+    if a.nbytes > DUMP_LIMIT_BYTES:
+        keep = np.random.default_rng(0).choice(a.shape[0], DUMP_LIMIT_BYTES // a[0].nbytes, replace=False)
+        a = a[np.sort(keep)]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "latents.npy"), np.ascontiguousarray(a))
 
 
 def class_flops(cls, M, d, ntok, n_layers, fused_attention=False):
@@ -265,6 +284,9 @@ def main():
                     help="latent size: 32 = C1/C2 (headline), 64 = C3 shape, 128 = C4 shape (bf16)")
     ap.add_argument("--gemm-dtype", default="bf16", choices=("bf16", "fp8"),
                     help="operand type of the QKV / MLP GEMMs: bf16 (headline) or fp8 (MX-fp8, BASELINE config C4)")
+    ap.add_argument("--full", action="store_true",
+                    help="also report the HIP-event roofline, power / clock on extra steps and the CPU baseline (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the latents of the last timed step as DIR/latents.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--with-vae", action="store_true",
                     help="after the timed region, also decode each rank's latents with the native VAE (SDXL-VAE geometry, random-init "
@@ -277,6 +299,11 @@ def main():
     ap.add_argument("--same-device", action="store_true",
                     help="plumbing test on a 1-GPU box: every rank uses cuda:0 (needs --backend gloo)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    profile = args.full and not args.no_profile
+    power_on = args.full and not args.no_power
+    cpu_base = args.full and not args.no_cpu_baseline
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -335,7 +362,7 @@ def main():
     # that class's events inside the timed region (each event pair costs ~1 us of stream time)
     warm_prof = {}
     dom_cls = "gemm_down"
-    if not args.no_profile:
+    if profile:
         model.set_profile(gemm_classes + extra_classes)
         out = one_step()
         fence()
@@ -356,11 +383,13 @@ def main():
     marks[args.steps].record()
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     # socket power and shader clock of the same workload, on a few MORE steps after the timed region: a hwmon read stalls the device for milliseconds (four reads per
     # second inside the timed region cost 2.5 % of the images/s, a hundred 4-7 %, and at 50 reads per second the reading itself drops from 1350 to 1135 W: same-box
     # A/B in profiles/r06_power_probe.txt), so the timed steps run unobserved and the observed ones are sampled five times a second
     power = None
-    if rank == 0 and world == 1 and not args.no_power:       # (one rank only: a step of the sharded path ends in a collective)
+    if rank == 0 and world == 1 and power_on:       # (one rank only: a step of the sharded path ends in a collective)
         poller = PowerPoller(dev.index, period=0.2)
         poller.start()
         t_obs = time.perf_counter()
@@ -391,7 +420,7 @@ def main():
         vdt = (time.perf_counter() - t1) / args.steps
         assert torch.isfinite(img).all()
         vae_cpu = None
-        if world == 1 and not args.no_cpu_baseline:             # cpu_baseline leg of the VAE stage: fp32 torch restatement, one image
+        if world == 1 and cpu_base:                             # cpu_baseline leg of the VAE stage: fp32 torch restatement, one image
             from oracle.vae_ref import TorchRefVaeDecoder
             ref = TorchRefVaeDecoder(VaeDecoderConfig(), vae.state_dict())
             zc = lat[:1].cpu()
@@ -406,7 +435,7 @@ def main():
                             "SDXL-VAE geometry with random-init weights (no checkpoint offline); not part of 'value'"}
 
     prof = {}
-    if not args.no_profile:
+    if profile:
         prof = dict(warm_prof)                       # untimed pass: all classes (context for the JSON)
         prof[dom_cls] = model.get_profile(dom_cls)   # timed region: the dominant class, live
         model.set_profile(())
@@ -469,7 +498,7 @@ def main():
             line["other_classes"] = {c: {"avg_ms": v[0] / max(v[1], 1), "launches": v[1]} for c, v in other_prof.items()}
         if vae_info:
             line["with_vae"] = vae_info
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and cpu_base:
             line["cpu_baseline"] = cpu_baseline(cfg, sd, S=S)
         print(json.dumps(line), flush=True)
     if world > 1:

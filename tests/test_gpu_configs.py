@@ -558,11 +558,12 @@ def test_rccl_single_rank_all_gather(tmp_path):
     assert r.returncode == 0 and "RCCL_OK" in r.stdout, (r.stdout[-1000:], r.stderr[-3000:])
 
 
-def test_bench_self_spawns_ranks():
+def test_bench_self_spawns_ranks(tmp_path):
     """`python bench.py --gpus 2` without a launcher re-executes itself under torch.distributed.run (here: both ranks on
-    the one GPU, gloo) and prints one JSON line for the 2-rank job."""
+    the one GPU, gloo) and prints one JSON line for the 2-rank job; --dump-outputs writes the gathered latents of both ranks."""
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-                        "--same-device", "--backend", "gloo", "--images-per-gpu", "8", "--no-cpu-baseline"],
+                        "--same-device", "--backend", "gloo", "--images-per-gpu", "8", "--full", "--no-cpu-baseline",
+                        "--dump-outputs", str(tmp_path)],
                        capture_output=True, text=True, timeout=900, env={k: v for k, v in os.environ.items()
                                                                            if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")})
     assert r.returncode == 0, r.stderr[-3000:]
@@ -570,3 +571,21 @@ def test_bench_self_spawns_ranks():
     assert len(lines) == 1, r.stdout[-2000:]
     j = json.loads(lines[0])
     assert j["n_gpus"] == 2 and j["config"]["global_batch"] == 16 and j["value"] > 0 and "roofline" in j
+    lat = np.load(tmp_path / "latents.npy")
+    assert lat.shape == (16, 4, 32, 32) and lat.dtype == np.float32 and np.isfinite(lat).all()
+
+
+def test_bench_plain_run_is_headline_only(tmp_path):
+    """A plain `bench.py` run times exactly --steps steps and prints the headline line without the --full extras
+    (roofline, power, cpu_baseline); --dump-outputs writes the last timed step's latents as float32."""
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--images-per-gpu", "4", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    j = json.loads(lines[0])
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(j), j
+    assert j["steps"] == 2 and j["value"] > 0 and j["ms_per_step"] > 0
+    assert not {"roofline", "power", "cpu_baseline"} & set(j), sorted(j)
+    lat = np.load(tmp_path / "latents.npy")
+    assert lat.shape == (4, 4, 32, 32) and lat.dtype == np.float32 and np.isfinite(lat).all()

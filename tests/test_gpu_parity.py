@@ -82,7 +82,7 @@ def _t(a):
                                    # more tiles than one round with a partly filled last round: its tiles are split by rows between two workgroups
                                    # (48 x 8 = 384 tiles: 16 of every XCD's 48; 36 x 9 = 324: 8 or 9 of 40 / 41; ragged M)
                                    (12288, 2048, 512), (9216, 2304, 768), (12200, 2048, 256)])
-def test_gemm_bf16_vs_fp32_matmul(M, N, K):
+def test_gemm_bf16_vs_fp32_matmul(M, N, K, tmp_path):
     import ctypes as C
     from transformer_latent_diffusion_amd import _lib
     g = torch.Generator().manual_seed(M + N + K)
@@ -100,14 +100,15 @@ def test_gemm_bf16_vs_fp32_matmul(M, N, K):
     if M * N >= 256 * 256 * 300:
         # the row-split tail of the last round accumulates every element exactly as a whole tile does: bitwise equal to the unsplit run
         import os, subprocess, sys
-        np.save("/tmp/_tld_gemm_tail.npy", c.cpu().numpy())
+        whole = str(tmp_path / "gemm_whole_tiles.npy")
+        np.save(whole, c.cpu().numpy())
         code = ("import sys, numpy as np, torch, ctypes as C; from transformer_latent_diffusion_amd import _lib\n"
-                f"M, N, K = {M}, {N}, {K}\n"
+                f"M, N, K, whole = {M}, {N}, {K}, {whole!r}\n"
                 "g = torch.Generator().manual_seed(M + N + K)\n"
                 "a = torch.randn(M, K, generator=g).to(torch.bfloat16).cuda(); w = (torch.randn(N, K, generator=g) * 0.1).to(torch.bfloat16).cuda()\n"
                 "c = torch.empty(M, N, device='cuda', dtype=torch.float32)\n"
                 "_lib.check(_lib.lib().tld_debug_gemm_bf16(a.data_ptr(), w.data_ptr(), c.data_ptr(), M, N, K, C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'gemm')\n"
-                "torch.cuda.synchronize(); assert np.array_equal(c.cpu().numpy(), np.load('/tmp/_tld_gemm_tail.npy')), 'half-tile tail changed the result'\n")
+                "torch.cuda.synchronize(); assert np.array_equal(c.cpu().numpy(), np.load(whole)), 'half-tile tail changed the result'\n")
         env = dict(os.environ, TLD_GEMM_HALFTAIL="0")
         r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
         assert r.returncode == 0, r.stderr[-2000:]

@@ -30,7 +30,7 @@ for rnd in range(a.rounds):
             for kv in parts[2].split(","):
                 k, v = kv.split("=", 1)
                 env[k] = v
-        cmd = [sys.executable, os.path.join(R, "bench.py"), "--steps", str(a.steps), "--warmup", "1", "--no-cpu-baseline"] + a.flags.split()
+        cmd = [sys.executable, os.path.join(R, "bench.py"), "--steps", str(a.steps), "--warmup", "1", "--full", "--no-cpu-baseline"] + a.flags.split()
         r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
         line = next((ln for ln in reversed(r.stdout.splitlines()) if ln.startswith("{")), None)
         if line is None:

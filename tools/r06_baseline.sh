@@ -5,10 +5,10 @@ T=${1:-r06_base}
 O=gpurun_out/$T
 mkdir -p $O
 R=$(pwd)
-timeout 300 python bench.py --steps 4 --warmup 1 --no-cpu-baseline > $O/bench_c1.json 2> $O/bench_c1.err; cut -c1-260 $O/bench_c1.json
-timeout 400 python bench.py --image-size 64 --images-per-gpu 16 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_c3.json 2> $O/bench_c3.err; cut -c1-260 $O/bench_c3.json
-timeout 400 python bench.py --image-size 128 --images-per-gpu 8 --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_c4_bf16.json 2> $O/bench_c4_bf16.err; cut -c1-260 $O/bench_c4_bf16.json
-timeout 400 python bench.py --image-size 128 --images-per-gpu 8 --steps 2 --warmup 1 --no-cpu-baseline --gemm-dtype fp8 > $O/bench_c4_fp8.json 2> $O/bench_c4_fp8.err; cut -c1-260 $O/bench_c4_fp8.json
+timeout 300 python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline > $O/bench_c1.json 2> $O/bench_c1.err; cut -c1-260 $O/bench_c1.json
+timeout 400 python bench.py --full --image-size 64 --images-per-gpu 16 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_c3.json 2> $O/bench_c3.err; cut -c1-260 $O/bench_c3.json
+timeout 400 python bench.py --full --image-size 128 --images-per-gpu 8 --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_c4_bf16.json 2> $O/bench_c4_bf16.err; cut -c1-260 $O/bench_c4_bf16.json
+timeout 400 python bench.py --full --image-size 128 --images-per-gpu 8 --steps 2 --warmup 1 --no-cpu-baseline --gemm-dtype fp8 > $O/bench_c4_fp8.json 2> $O/bench_c4_fp8.err; cut -c1-260 $O/bench_c4_fp8.json
 cd /tmp && export TMPDIR=/tmp
 for cfg in "c1:" "c3:--image-size 64 --images-per-gpu 16" "c4f:--image-size 128 --images-per-gpu 8 --gemm-dtype fp8" "c4b:--image-size 128 --images-per-gpu 8"; do
   tag=${cfg%%:*}; fl=${cfg#*:}

@@ -15,10 +15,10 @@ bash tools/pmc_traffic.sh $O/pmc_c4f --image-size 128 --images-per-gpu 8 --gemm-
 cp $O/pmc_c4f/traffic.json profiles/${P}_pmc_traffic_c4_fp8.json 2>/dev/null
 bash tools/pmc_traffic.sh $O/pmc_c4b --image-size 128 --images-per-gpu 8 > $O/pmc_c4b.log 2>&1; tail -7 $O/pmc_c4b.log
 cp $O/pmc_c4b/traffic.json profiles/${P}_pmc_traffic_c4_bf16.json 2>/dev/null
-timeout 900 python bench.py --steps 5 --warmup 2 --with-vae > $O/bench_c1.json 2> $O/bench_c1.err; cut -c1-300 $O/bench_c1.json; grep -o '"with_vae".*' $O/bench_c1.json | cut -c1-400
-timeout 600 python bench.py --image-size 64 --images-per-gpu 16 --steps 3 --warmup 1 > $O/bench_c3.json 2> $O/bench_c3.err; cut -c1-200 $O/bench_c3.json
-timeout 600 python bench.py --image-size 128 --images-per-gpu 8 --steps 2 --warmup 1 > $O/bench_c4_bf16.json 2> $O/bench_c4_bf16.err; cut -c1-200 $O/bench_c4_bf16.json
-timeout 300 python bench.py --image-size 128 --images-per-gpu 8 --steps 2 --warmup 1 --no-cpu-baseline --gemm-dtype fp8 > $O/bench_c4_fp8.json 2> $O/bench_c4_fp8.err; cut -c1-200 $O/bench_c4_fp8.json
+timeout 900 python bench.py --full --steps 5 --warmup 2 --with-vae > $O/bench_c1.json 2> $O/bench_c1.err; cut -c1-300 $O/bench_c1.json; grep -o '"with_vae".*' $O/bench_c1.json | cut -c1-400
+timeout 600 python bench.py --full --image-size 64 --images-per-gpu 16 --steps 3 --warmup 1 > $O/bench_c3.json 2> $O/bench_c3.err; cut -c1-200 $O/bench_c3.json
+timeout 600 python bench.py --full --image-size 128 --images-per-gpu 8 --steps 2 --warmup 1 > $O/bench_c4_bf16.json 2> $O/bench_c4_bf16.err; cut -c1-200 $O/bench_c4_bf16.json
+timeout 300 python bench.py --full --image-size 128 --images-per-gpu 8 --steps 2 --warmup 1 --no-cpu-baseline --gemm-dtype fp8 > $O/bench_c4_fp8.json 2> $O/bench_c4_fp8.err; cut -c1-200 $O/bench_c4_fp8.json
 R=$(pwd); cd /tmp && export TMPDIR=/tmp
 timeout 600 rocprofv3 --kernel-trace --stats -d $R/$O/prof_c1 -o p -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-profile > $R/$O/prof_c1.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --stats -d $R/$O/prof_c3 -o p -- python $R/bench.py --image-size 64 --images-per-gpu 16 --steps 1 --warmup 1 --no-cpu-baseline --no-profile > $R/$O/prof_c3.log 2>&1
