@@ -213,6 +213,55 @@ TLD_API int tld_debug_conv3x3(const void* in_bf16, const void* w_bf16, float* ou
 TLD_API int64_t tld_vae_weight_bytes(const tld_vae* v);
 TLD_API int tld_vae_destroy(tld_vae* v);
 
+/* ---- VAE encode: images -> latent moments (the reference's data pipeline, tld/data.py) --------------------------------
+ * Replaces `vae.encode(x, return_dict=False)[0]` of tld/data.py, with the same third-party AutoencoderKL as the decoder above.
+ * Restated: AutoencoderKL.encode of diffusers 0.2x -- Encoder (conv_in, DownEncoderBlock2D x n with Downsample2D(padding=0),
+ * UNetMidBlock2D with one single-head attention, GroupNorm + SiLU, conv_out -> 2 latent_channels) and quant_conv 1x1.  The
+ * DiagonalGaussianDistribution over the moments (mean | logvar) is evaluated by the caller.  Same numerics as the decoder. */
+typedef struct tld_vae_enc tld_vae_enc;
+
+typedef struct tld_vae_enc_config {
+    int32_t in_channels;            /* 3 (1..4) */
+    int32_t latent_channels;        /* 4 (<= 16): the moments have 2 latent_channels channels */
+    int32_t n_blocks;               /* entries of block_out_channels in use (<= 4) */
+    int32_t block_out_channels[4];  /* AutoencoderKL order, e.g. 128, 256, 512, 512; each in {64,128,256,512,1024} */
+    int32_t layers_per_block;       /* 2: every encoder down block has layers_per_block resnets */
+    int32_t norm_num_groups;        /* 32 */
+    int32_t mid_block_attention;    /* 1 */
+    int32_t use_quant_conv;         /* 1 */
+    int32_t image_size;             /* S = h = w of the input image: a multiple of 64 and of 8 * 2^(n_blocks-1), 64..2048 */
+    int32_t max_batch;              /* largest batch one tld_vae_enc_encode call will see (activation buffers < 4 GiB) */
+    int32_t device_id;
+} tld_vae_enc_config;
+
+TLD_API int tld_vae_enc_create(const tld_vae_enc_config* cfg, tld_vae_enc** out);
+/* AutoencoderKL.load_state_dict, one entry at a time (diffusers key names: "encoder.conv_in.weight",
+ * "encoder.down_blocks.<i>.resnets.<j>.*", "encoder.down_blocks.<i>.downsamplers.0.conv.*", "encoder.mid_block.*" with the
+ * pre-0.19 attention spellings accepted, "encoder.conv_norm_out.*", "encoder.conv_out.*", "quant_conv.*").  "decoder.*" and
+ * "post_quant_conv.*" entries are accepted and ignored.  Host fp32 data. */
+TLD_API int tld_vae_enc_load_tensor(tld_vae_enc* e, const char* key, const void* host_ptr, const int64_t* shape, int32_t ndim,
+                                    int32_t dtype);
+TLD_API int tld_vae_enc_finalize_weights(tld_vae_enc* e);
+/* AutoencoderKL.encode(x).latent_dist.parameters -- tld/data.py.
+ *   x        [batch, in_channels, S, S]                 device, io_dtype (already mapped to [-1, 1] by the caller)
+ *   moments  [batch, 2 latent_channels, S/2^(n-1), S/2^(n-1)]  device, fp32 (mean, then logvar before its clamp) */
+TLD_API int tld_vae_enc_encode(tld_vae_enc* e, const void* x, float* moments, int32_t batch, int32_t io_dtype, void* hip_stream);
+/* Test hook as tld_vae_set_debug / read_stage.  names: "conv_in", "down<i>.res<j>", "down<i>.downsample", "mid.res0", "mid.attn",
+ * "mid.res1", "norm_out" (after SiLU). */
+TLD_API int tld_vae_enc_set_debug(tld_vae_enc* e, int32_t enable);
+TLD_API int tld_vae_enc_read_stage(tld_vae_enc* e, const char* name, float* host_out, int64_t numel, int64_t* shape4);
+/* Live timing per kernel class, as tld_vae_set_profile: 0 conv3x3, 1 gemm (1x1 / attention), 2 groupnorm, 3 other (conv_in, tail) */
+TLD_API int tld_vae_enc_set_profile(tld_vae_enc* e, int32_t enable);
+TLD_API int tld_vae_enc_get_profile(tld_vae_enc* e, int32_t kclass, double* total_ms, int64_t* launches);
+TLD_API int64_t tld_vae_enc_weight_bytes(const tld_vae_enc* e);
+TLD_API int tld_vae_enc_destroy(tld_vae_enc* e);
+
+/* Test hook: the implicit-GEMM 3x3 convolution with stride 2 and padding (0, 1, 0, 1) (Downsample2D) alone.  H x W is the OUTPUT size.
+ *   in  bf16 channels-last [B, 2H, 2W, cin] (device);  w  bf16 [cout][3][3][cin] (device)
+ *   out fp32 [B*H*W][cout] (device).  cin % 64 == 0.  Synchronises the stream. */
+TLD_API int tld_debug_conv3x3_s2(const void* in_bf16, const void* w_bf16, float* out_f32, int32_t B, int32_t H, int32_t W,
+                                 int32_t cin, int32_t cout, void* hip_stream);
+
 /* ---- CLIP text tower: the front edge ---------------------------------------------------
  * Replaces `model.encode_text(text_tokens)` in encode_text, tld/diffusion.py:136-140, where `model` is OpenAI CLIP
  * "ViT-L/14" from `clip.load` (tld/diffusion.py:160, tld/configs.py:46-48; third-party, not in the reference checkout).

@@ -26,6 +26,9 @@ ABI_SYMBOLS = (
     "tld_vae_create", "tld_vae_load_tensor", "tld_vae_finalize_weights", "tld_vae_decode", "tld_vae_set_debug",
     "tld_vae_read_stage", "tld_vae_set_profile", "tld_vae_get_profile", "tld_debug_conv3x3", "tld_vae_weight_bytes",
     "tld_vae_destroy",
+    "tld_vae_enc_create", "tld_vae_enc_load_tensor", "tld_vae_enc_finalize_weights", "tld_vae_enc_encode", "tld_vae_enc_set_debug",
+    "tld_vae_enc_read_stage", "tld_vae_enc_set_profile", "tld_vae_enc_get_profile", "tld_vae_enc_weight_bytes", "tld_vae_enc_destroy",
+    "tld_debug_conv3x3_s2",
     "tld_clip_create", "tld_clip_load_tensor", "tld_clip_finalize_weights", "tld_clip_encode_text", "tld_clip_read_buffer", "tld_clip_weight_bytes",
     "tld_clip_destroy",
     "tld_train_create", "tld_train_param_count", "tld_train_tensor_count", "tld_train_param_layout", "tld_train_set_angular_speeds", "tld_train_bind",
@@ -50,6 +53,13 @@ class TldVaeConfig(C.Structure):
     _fields_ = [("latent_channels", C.c_int32), ("out_channels", C.c_int32), ("n_blocks", C.c_int32),
                 ("block_out_channels", C.c_int32 * 4), ("layers_per_block", C.c_int32), ("norm_num_groups", C.c_int32),
                 ("mid_block_attention", C.c_int32), ("use_post_quant_conv", C.c_int32), ("latent_size", C.c_int32),
+                ("max_batch", C.c_int32), ("device_id", C.c_int32)]
+
+
+class TldVaeEncConfig(C.Structure):
+    _fields_ = [("in_channels", C.c_int32), ("latent_channels", C.c_int32), ("n_blocks", C.c_int32),
+                ("block_out_channels", C.c_int32 * 4), ("layers_per_block", C.c_int32), ("norm_num_groups", C.c_int32),
+                ("mid_block_attention", C.c_int32), ("use_quant_conv", C.c_int32), ("image_size", C.c_int32),
                 ("max_batch", C.c_int32), ("device_id", C.c_int32)]
 
 
@@ -117,6 +127,19 @@ def lib() -> C.CDLL:
     L.tld_vae_weight_bytes.argtypes = [vp]
     L.tld_vae_weight_bytes.restype = C.c_int64
     L.tld_vae_destroy.argtypes = [vp]
+    if hasattr(L, "tld_vae_enc_create"):             # (absent from A/B builds that predate the encoder)
+        L.tld_vae_enc_create.argtypes = [C.POINTER(TldVaeEncConfig), C.POINTER(vp)]
+        L.tld_vae_enc_load_tensor.argtypes = [vp, C.c_char_p, vp, i64p, i32, i32]
+        L.tld_vae_enc_finalize_weights.argtypes = [vp]
+        L.tld_vae_enc_encode.argtypes = [vp, vp, vp, i32, i32, vp]
+        L.tld_vae_enc_set_debug.argtypes = [vp, i32]
+        L.tld_vae_enc_read_stage.argtypes = [vp, C.c_char_p, C.POINTER(C.c_float), C.c_int64, i64p]
+        L.tld_vae_enc_set_profile.argtypes = [vp, i32]
+        L.tld_vae_enc_get_profile.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+        L.tld_vae_enc_weight_bytes.argtypes = [vp]
+        L.tld_vae_enc_weight_bytes.restype = C.c_int64
+        L.tld_vae_enc_destroy.argtypes = [vp]
+        L.tld_debug_conv3x3_s2.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
     L.tld_clip_create.argtypes = [C.POINTER(TldClipConfig), C.POINTER(vp)]
     L.tld_clip_load_tensor.argtypes = [vp, C.c_char_p, vp, i64p, i32, i32]
     L.tld_clip_finalize_weights.argtypes = [vp]
@@ -146,7 +169,7 @@ def lib() -> C.CDLL:
     for name in ABI_SYMBOLS:
         if "TLD_LIB" in os.environ and not hasattr(L, name):     # an older A/B build: symbols added since are simply absent (tests/test_abi.py checks the real library)
             continue
-        if name not in ("tld_last_error", "tld_engine_weight_bytes", "tld_vae_weight_bytes", "tld_clip_weight_bytes", "tld_train_param_count",
+        if name not in ("tld_last_error", "tld_engine_weight_bytes", "tld_vae_weight_bytes", "tld_vae_enc_weight_bytes", "tld_clip_weight_bytes", "tld_train_param_count",
                         "tld_train_tensor_count"):
             getattr(L, name).restype = C.c_int
     _lib = L

@@ -395,6 +395,9 @@ struct GemmParams {
     int tn_ktotal;
     int half_tail;                // ring K loop: split the tiles of a partly filled last round by ROWS between two workgroups (set by the launcher)
     int dbg_epi;                  // experiment knob, builds with -DTLD_DBG_EPI only (TLD_EPI_DBG bit mask, see tld_gemm.hip)
+    int cv_down;                  // conv: stride-2 3x3 convolution with padding (0, 1, 0, 1) (diffusers Downsample2D, VAE encoder): output pixel (y, x)
+                                  //   and tap (ky, kx) read source pixel (2y + ky, 2x + kx) of a 2 cv_h x 2 cv_w image -- a tap is outside only on the
+                                  //   bottom / right pad, which reads the zero page.  Excludes cv_up (launch_gemm refuses both).
 };
 
 void launch_gemm(const GemmParams& p, int epilogue, hipStream_t s);

@@ -211,9 +211,11 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, int nblocks
     size_t tnA = 0, tnW = 0;                                  // TN: byte offset of k-row 0 of the tile the DMA is working on (its split), per operand
     auto conv_tap = [&](int tap) {                            // A-row offsets of one of the nine taps (uniform tap)
         if constexpr (CONV) {
+            // (cv_down: source pixel (2y + ky, 2x + kx) of a 2 cv_h x 2 cv_w image -- the doubled coordinates are kept in cpix)
             const int ky = tap / 3;
-            const int dy = ky - 1, dx = tap - ky * 3 - 1;
-            const int ws_ = p.cv_w >> p.cv_up;
+            const int dy = ky - 1 + p.cv_down, dx = tap - ky * 3 - 1 + p.cv_down;
+            const int ws_ = (p.cv_w >> p.cv_up) << p.cv_down;
+            const unsigned sh = (unsigned)(p.cv_h << p.cv_down), sw = (unsigned)(p.cv_w << p.cv_down);
             int ln = lane;
             asm volatile("" : "+v"(ln));
 #pragma unroll
@@ -221,7 +223,7 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, int nblocks
                 const int r = (wid * G::A_PIECES + q2) * 8 + (ln >> 3);
                 const unsigned c16 = (unsigned)(((ln & 7) ^ ((r >> 1) & 7)) * 16);
                 const int yy = (int)(cpix[q2] >> 16) + dy, xx = (int)(cpix[q2] & 0xffffu) + dx;
-                const bool inb = (unsigned)yy < (unsigned)p.cv_h && (unsigned)xx < (unsigned)p.cv_w;
+                const bool inb = (unsigned)yy < sh && (unsigned)xx < sw;
                 const unsigned sp = cbase[q2] + (unsigned)((yy >> p.cv_up) * ws_ + (xx >> p.cv_up));
                 unsigned v = inb ? p.cv_data_off + sp * (unsigned)(p.cv_cin * 2) + c16 : c16;     // outside: the zero page
                 asm volatile("" : "+v"(v));
@@ -254,7 +256,7 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, int nblocks
         }
         if constexpr (CONV) {
             const unsigned hw = (unsigned)(p.cv_h * p.cv_w);
-            const unsigned shw = (unsigned)((p.cv_h >> p.cv_up) * (p.cv_w >> p.cv_up));
+            const unsigned shw = (unsigned)((p.cv_h >> p.cv_up) * (p.cv_w >> p.cv_up)) << (2 * p.cv_down);
 #pragma unroll
             for (int q2 = 0; q2 < G::A_PIECES; ++q2) {
                 const int r = (wid * G::A_PIECES + q2) * 8 + (ln >> 3);
@@ -262,7 +264,7 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, int nblocks
                 gr = gr < p.M ? gr : p.M - 1;
                 const unsigned b = (unsigned)gr / hw, rem = (unsigned)gr - b * hw;
                 const unsigned y = rem / (unsigned)p.cv_w, x = rem - y * (unsigned)p.cv_w;
-                cpix[q2] = (y << 16) | x;
+                cpix[q2] = ((y << 16) | x) << p.cv_down;
                 cbase[q2] = b * shw;
             }
             conv_tap(0);
@@ -394,8 +396,9 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, int nblocks
     auto ring_conv_tap = [&](int tap) {
         if constexpr (RING && CONV) {
             const int ky = tap / 3;
-            const int dy = ky - 1, dx = tap - ky * 3 - 1;
-            const int ws_ = p.cv_w >> p.cv_up;
+            const int dy = ky - 1 + p.cv_down, dx = tap - ky * 3 - 1 + p.cv_down;     // (cv_down: as conv_tap)
+            const int ws_ = (p.cv_w >> p.cv_up) << p.cv_down;
+            const unsigned sh = (unsigned)(p.cv_h << p.cv_down), sw = (unsigned)(p.cv_w << p.cv_down);
             unsigned full = ~0u;
             asm volatile("" : "+s"(full));
             int ln = (int)__builtin_amdgcn_mbcnt_hi(full, __builtin_amdgcn_mbcnt_lo(full, 0u));
@@ -407,7 +410,7 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, int nblocks
                     const int r = (wid * 2 + q2) * 8 + (ln >> 3);
                     const unsigned c16 = (unsigned)(((ln & 7) ^ ((r >> 1) & 7)) * 16);
                     const int yy = (int)(rcpix[h * 2 + q2] >> 16) + dy, xx = (int)(rcpix[h * 2 + q2] & 0xffffu) + dx;
-                    const bool inb = (unsigned)yy < (unsigned)p.cv_h && (unsigned)xx < (unsigned)p.cv_w;
+                    const bool inb = (unsigned)yy < sh && (unsigned)xx < sw;
                     const unsigned sp = rcbase[h * 2 + q2] + (unsigned)((yy >> p.cv_up) * ws_ + (xx >> p.cv_up));
                     unsigned v = inb ? p.cv_data_off + sp * (unsigned)(p.cv_cin * 2) + c16 : c16;     // outside: the zero page
                     asm volatile("" : "+v"(v));
@@ -422,7 +425,7 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, int nblocks
             int ln = (int)__builtin_amdgcn_mbcnt_hi(full, __builtin_amdgcn_mbcnt_lo(full, 0u));
             asm volatile("" : "+v"(ln));
             const unsigned hw = (unsigned)(p.cv_h * p.cv_w);
-            const unsigned shw = (unsigned)((p.cv_h >> p.cv_up) * (p.cv_w >> p.cv_up));
+            const unsigned shw = (unsigned)((p.cv_h >> p.cv_up) * (p.cv_w >> p.cv_up)) << (2 * p.cv_down);
 #pragma unroll
             for (int h = 0; h < 2; ++h)
 #pragma unroll
@@ -433,7 +436,7 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, int nblocks
                     ga = ga < p.M ? ga : p.M - 1;
                     const unsigned bb = (unsigned)ga / hw, rem = (unsigned)ga - bb * hw;
                     const unsigned y = rem / (unsigned)p.cv_w, x = rem - y * (unsigned)p.cv_w;
-                    rcpix[h * 2 + q2] = (y << 16) | x;
+                    rcpix[h * 2 + q2] = ((y << 16) | x) << p.cv_down;
                     rcbase[h * 2 + q2] = bb * shw;
                     int gb = tn0 + (r >> 5) * 64 + h * 32 + (r & 31);
                     gb = gb < p.N ? gb : p.N - 1;
@@ -1690,6 +1693,10 @@ void launch_gemm(const GemmParams& p_in, int epilogue, hipStream_t s) {
         // 8-wave 192- / 384-wide kernels below).  TLD_DOWN_SMALL=0: A/B and test hook.
         static const bool dn_on = !(getenv("TLD_DOWN_SMALL") && atoi(getenv("TLD_DOWN_SMALL")) == 0);
         if (dn_on && down_pp_supported(p) && down_pp_fits(p)) { launch_down_pp(p, s); return; }
+    }
+    if (p.conv && p.cv_up && p.cv_down) {     // upsampling and stride 2 are exclusive addressing modes: launch nothing, report it to the caller
+        set_last_error("launch_gemm: conv with both cv_up and cv_down set");
+        return;
     }
     int bn = choose_bn(p.M, p.N, epilogue, p.K);
     if (p.conv) {           // 256-wide tiles when the width allows and they fill the chip, else 128

@@ -437,11 +437,12 @@ int group_norm(tld_vae* v, int src, int dst, const GnW& gn, int B, int HW, int C
 
 // 3x3 convolution of buffer `src` ([B, H >> up, W >> up, cin]) into an [B, H, W, cout] image
 //   epi EPI_BIAS_BF16: written to buffer dst;  EPI_BIAS_RESID: added to buffer dst in place;  EPI_F32: fp32 [M][cout] to c_f32
-int conv3x3(tld_vae* v, int src, int dst, const ConvW& cw, int B, int H, int W, int up, int epi, float* c_f32, hipStream_t s) {
+//   down = 1 (encoder Downsample2D): stride 2 with padding (0, 1, 0, 1) from a [B, 2H, 2W, cin] source instead (GemmParams::cv_down)
+int conv3x3(tld_vae* v, int src, int dst, const ConvW& cw, int B, int H, int W, int up, int epi, float* c_f32, hipStream_t s, int down = 0) {
     Timer t(v, VC_CONV, s);
     GemmParams p{};
     p.A = reinterpret_cast<const bf16*>(v->buf[src]);
-    p.conv = 1; p.cv_h = H; p.cv_w = W; p.cv_up = up; p.cv_cin = cw.cin; p.cv_data_off = kHdr;
+    p.conv = 1; p.cv_h = H; p.cv_w = W; p.cv_up = up; p.cv_down = down; p.cv_cin = cw.cin; p.cv_data_off = kHdr;
     p.lda = cw.cin;
     p.W = cw.w; p.ldw = 9 * cw.cin;
     p.M = B * H * W; p.N = cw.cout; p.K = 9 * cw.cin;
@@ -876,6 +877,408 @@ int tld_debug_conv3x3(const void* in_bf16, const void* w_bf16, float* out_f32, i
     HIP_TRY(hipStreamSynchronize(s));
     HIP_TRY(hipFree(buf));
     if (e != hipSuccess) return fail(TLD_ERR_HIP, "conv3x3 launch failed: %s", hipGetErrorString(e));
+    return TLD_OK;
+}
+
+}  // extern "C"
+
+// ======================================================================================================================
+// VAE encode (tld_vae_enc_*): AutoencoderKL.encode of diffusers 0.2x -- the reference's data pipeline turns images into
+// latents with it (tld/data.py: `vae.encode(img * 2 - 1, return_dict=False)[0].sample()`).  Restated (models/autoencoders/vae.py
+// Encoder, models/downsampling.py Downsample2D with padding = 0, models/autoencoders/vae.py DiagonalGaussianDistribution):
+//   conv_in 3x3 (3 -> C0) -> down blocks (layers_per_block resnets, stride-2 3x3 conv with padding (0, 1, 0, 1) except in the
+//   last) -> mid block (resnet, single-head attention, resnet) -> GroupNorm, SiLU, conv_out 3x3 (-> 2 zc) -> quant_conv 1x1.
+// Output: the fp32 moments [B, 2 zc, S / 2^(n-1), S / 2^(n-1)] (mean | logvar); the Gaussian is sampled on the Python side.
+// Everything between conv_in and conv_out is the decoder's machinery (resnet / attention / group_norm / conv3x3 on a tld_vae
+// workspace); the downsampler is the implicit-GEMM convolution with its stride-2 addressing (GemmParams::cv_down).
+
+namespace {
+
+// conv_in with 3 (<= 4) input channels, zero pad 1: NCHW image (fp32 / bf16 / fp16) -> channels-last bf16 [B, S, S, C0].
+// A thread owns 8 consecutive output channels of one pixel (one 16-byte store, coalesced across the C0 / 8 threads of a
+// pixel and the pixels of a workgroup); the 9 cin taps of the pixel come through the cache, the weights [9 cin][C0] fp32 and the
+// bias sit in LDS.  27 MACs per output: a memory-bound pass.
+__global__ __launch_bounds__(256) void vae_enc_conv_in_kernel(const void* __restrict__ x, int dtype, int cin, int S, const float* __restrict__ wt,
+                                                              const float* __restrict__ bias, bf16* __restrict__ out, int C0, int ppb, long npix) {
+    extern __shared__ float wsh[];                 // [9 cin][C0] then [C0]
+    const int nw = 9 * cin * C0;
+    for (int i = threadIdx.x; i < nw + C0; i += 256) wsh[i] = i < nw ? wt[i] : bias[i - nw];
+    __syncthreads();
+    const int TPP = C0 >> 3, PPI = 256 / TPP;
+    const int tp = threadIdx.x % TPP, slot = threadIdx.x / TPP;
+    const long p0 = (long)blockIdx.x * ppb;
+    const long p1 = p0 + ppb < npix ? p0 + ppb : npix;
+    const long HW = (long)S * S;
+    const float* bsh = wsh + nw + tp * 8;
+    for (long pix = p0 + slot; pix < p1; pix += PPI) {
+        const long b = pix / HW;
+        const int rem = (int)(pix - b * HW), y = rem / S, xq = rem - y * S;
+        float acc[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] = bsh[e];
+        for (int c = 0; c < cin; ++c) {
+            const long plane = (b * cin + c) * HW;
+#pragma unroll
+            for (int tap = 0; tap < 9; ++tap) {
+                const int yy = y + tap / 3 - 1, xx = xq + tap % 3 - 1;
+                float a = 0.f;
+                if ((unsigned)yy < (unsigned)S && (unsigned)xx < (unsigned)S) {
+                    const long i = plane + (long)yy * S + xx;
+                    a = dtype == TLD_DTYPE_F32 ? reinterpret_cast<const float*>(x)[i]
+                      : dtype == TLD_DTYPE_BF16 ? (float)reinterpret_cast<const bf16*>(x)[i] : (float)reinterpret_cast<const _Float16*>(x)[i];
+                }
+                const float* wr = wsh + (tap * cin + c) * C0 + tp * 8;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[e] = fmaf(a, wr[e], acc[e]);
+            }
+        }
+        bf16x8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (bf16)acc[e];
+        *reinterpret_cast<bf16x8*>(out + pix * C0 + tp * 8) = o;
+    }
+}
+
+// conv_out tail of the encoder: fp32 [B*HW][OC] (the GEMM's fp32 epilogue) + conv_out bias, then quant_conv (1x1, OC -> OC, fp32;
+// identity when qw is null) -> the moments, fp32 NCHW [B, OC, H, W].  OC <= 32.
+__global__ void vae_enc_out_kernel(const float* __restrict__ in, const float* __restrict__ bias, const float* __restrict__ qw,
+                                   const float* __restrict__ qb, float* __restrict__ out, int HW, int OC, long total) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;      // over B * HW pixels
+    if (i >= total) return;
+    const long b = i / HW, pix = i - b * HW;
+    float h[32];
+    for (int c = 0; c < OC; ++c) h[c] = in[(size_t)i * OC + c] + bias[c];
+    for (int o = 0; o < OC; ++o) {
+        float a = h[o];
+        if (qw) {
+            a = qb[o];
+            for (int c = 0; c < OC; ++c) a = fmaf(qw[o * OC + c], h[c], a);
+        }
+        out[((size_t)b * OC + o) * HW + pix] = a;
+    }
+}
+
+struct DownBlock { std::vector<Resnet> res; bool has_down = false; ConvW down; int cout = 0; };
+
+}  // namespace
+
+struct tld_vae_enc {
+    tld_vae_enc_config cfg{};
+    // workspace, GroupNorm / attention scratch, mid-block and output weights, stage snapshots and profile events: a decoder object
+    // used as the engine state that resnet() / attention() / group_norm() / conv3x3() work on (its decoder-only fields stay unused)
+    tld_vae core;
+    int S = 0, cin = 3, oc = 8;                  // image size, input channels, moments channels (2 zc)
+    float *cin_wt = nullptr, *cin_b = nullptr;   // conv_in fp32 [9 cin][C0], [C0]
+    std::vector<DownBlock> downs;
+    float *qc_w = nullptr, *qc_b = nullptr;      // quant_conv [oc][oc], [oc] (null: use_quant_conv = 0)
+};
+
+namespace {
+
+size_t enc_max_act_elems(const tld_vae_enc* e) {            // per sample, over all stages of the encoder
+    const tld_vae& v = e->core;
+    size_t H = (size_t)e->S, mx = H * H * v.boc[0];
+    int c = v.boc[0];
+    for (int i = 0; i < v.nb; ++i) {
+        const int cout = v.boc[i];
+        mx = std::max(mx, H * H * std::max(c, cout));
+        c = cout;
+        if (i != v.nb - 1) H /= 2;                            // (the downsampled image is smaller than its source)
+    }
+    mx = std::max(mx, H * H * c * 3);                        // attention q|k|v
+    return mx;
+}
+
+void enc_release(tld_vae_enc* e) {
+    tld_vae* v = &e->core;
+    clear_stages(v);
+    for (int k = 0; k < VC_COUNT; ++k)
+        for (auto& ev : v->ev[k]) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
+    for (void* p : v->allocs) (void)hipFree(p);
+    v->allocs.clear();
+}
+
+}  // namespace
+
+extern "C" {
+
+int tld_vae_enc_create(const tld_vae_enc_config* cfg, tld_vae_enc** out) {
+    if (!cfg || !out) return fail(TLD_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (cfg->in_channels < 1 || cfg->in_channels > 4) return fail(TLD_ERR_INVALID, "in_channels=%d: 1..4 supported", cfg->in_channels);
+    if (cfg->n_blocks < 1 || cfg->n_blocks > 4) return fail(TLD_ERR_INVALID, "n_blocks=%d: 1..4 supported", cfg->n_blocks);
+    for (int i = 0; i < cfg->n_blocks; ++i)
+        if (!chan_ok(cfg->block_out_channels[i]))
+            return fail(TLD_ERR_INVALID, "block_out_channels[%d]=%d: must be one of 64, 128, 256, 512, 1024", i, cfg->block_out_channels[i]);
+    if (cfg->latent_channels < 1 || cfg->latent_channels > 16) return fail(TLD_ERR_INVALID, "latent_channels=%d: 1..16 supported", cfg->latent_channels);
+    if (cfg->norm_num_groups < 1 || cfg->norm_num_groups > 64) return fail(TLD_ERR_INVALID, "norm_num_groups=%d: 1..64 supported", cfg->norm_num_groups);
+    for (int i = 0; i < cfg->n_blocks; ++i)
+        if (cfg->block_out_channels[i] % cfg->norm_num_groups)
+            return fail(TLD_ERR_INVALID, "block_out_channels[%d]=%d is not a multiple of norm_num_groups=%d", i, cfg->block_out_channels[i], cfg->norm_num_groups);
+    if (cfg->layers_per_block < 1 || cfg->layers_per_block > 8) return fail(TLD_ERR_INVALID, "layers_per_block=%d: 1..8 supported", cfg->layers_per_block);
+    const int down = 1 << (cfg->n_blocks - 1);
+    if (cfg->image_size < 64 || cfg->image_size > 2048 || cfg->image_size % 64 || cfg->image_size % (8 * down))
+        return fail(TLD_ERR_INVALID, "image_size=%d: a multiple of 64 and of 8 * 2^(n_blocks-1) = %d in 64..2048 (the mid-block attention needs "
+                    "a multiple of 8 per side)", cfg->image_size, 8 * down);
+    if (cfg->max_batch < 1) return fail(TLD_ERR_INVALID, "max_batch must be positive");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(TLD_ERR_HIP, "no HIP device available (the VAE encoder has no CPU path)");
+    if (cfg->device_id < 0 || cfg->device_id >= ndev) return fail(TLD_ERR_INVALID, "device_id=%d out of range (%d devices)", cfg->device_id, ndev);
+    DeviceGuard guard(cfg->device_id);
+
+    tld_vae_enc* e = new tld_vae_enc();
+    e->cfg = *cfg;
+    e->S = cfg->image_size; e->cin = cfg->in_channels; e->oc = 2 * cfg->latent_channels;
+    tld_vae* v = &e->core;
+    v->cfg.device_id = cfg->device_id; v->cfg.max_batch = cfg->max_batch; v->cfg.mid_block_attention = cfg->mid_block_attention;
+    v->G = cfg->norm_num_groups; v->zc = cfg->latent_channels; v->oc = e->oc; v->nb = cfg->n_blocks; v->hl = e->S / down;
+    v->boc.assign(cfg->block_out_channels, cfg->block_out_channels + cfg->n_blocks);
+    v->C0 = v->boc[v->nb - 1];                               // (the mid block's width, as in the decoder)
+    v->fuse_stats = true;
+    const size_t per = enc_max_act_elems(e);
+    v->buf_elems = per * (size_t)cfg->max_batch;
+    const size_t bytes = v->buf_elems * 2 + kHdr;
+    if (bytes >= (1ull << 32)) {
+        delete e;
+        return fail(TLD_ERR_INVALID, "max_batch=%d: an activation buffer (%zu bytes per sample) must stay below 4 GiB (32-bit DMA offsets); "
+                    "encode in chunks of at most %zu", cfg->max_batch, per * 2, (size_t)(((1ull << 32) - kHdr - 1) / (per * 2)));
+    }
+    auto bail = [&](int rc) { tld_vae_enc_destroy(e); return rc; };
+    for (int i = 0; i < 4; ++i) {
+        if (int rc = dev_alloc(v, &v->buf[i], bytes)) return bail(rc);
+        if (hipMemset(v->buf[i], 0, kHdr) != hipSuccess) return bail(fail(TLD_ERR_HIP, "hipMemset failed"));
+    }
+    v->gn_max_chunks = (e->S * e->S + 255) / 256;
+    if (int rc = dev_alloc(v, &v->gn_partial, (size_t)cfg->max_batch * v->gn_max_chunks * v->G)) return bail(rc);
+    if (int rc = dev_alloc(v, &v->gn_stats, (size_t)cfg->max_batch * v->G)) return bail(rc);
+    if (cfg->mid_block_attention) {
+        const size_t hw = (size_t)v->hl * v->hl;
+        const size_t fit = ((size_t)256 << 20) / (hw * hw * 4);             // samples whose fp32 scores fit in 256 MB
+        v->att_nb = (int)std::max<size_t>(1, std::min<size_t>(fit, (size_t)cfg->max_batch));
+        if (int rc = dev_alloc(v, &v->scores, (size_t)v->att_nb * hw * hw)) return bail(rc);
+        if (int rc = dev_alloc(v, &v->probs, (size_t)v->att_nb * hw * hw)) return bail(rc);
+        if (int rc = dev_alloc(v, &v->vt, (size_t)v->att_nb * hw * v->C0)) return bail(rc);
+    }
+    if (int rc = dev_alloc(v, &v->out_f32, (size_t)cfg->max_batch * v->hl * v->hl * e->oc)) return bail(rc);
+    *out = e;
+    return TLD_OK;
+}
+
+int tld_vae_enc_load_tensor(tld_vae_enc* e, const char* key, const void* host_ptr, const int64_t* shape, int32_t ndim, int32_t dtype) {
+    if (!e || !key || (!host_ptr && ndim > 0) || ndim < 0 || ndim > 8) return fail(TLD_ERR_INVALID, "bad argument");
+    tld_vae* v = &e->core;
+    if (v->finalized) return fail(TLD_ERR_STATE, "weights already finalized");
+    std::string k(key);
+    if (k.rfind("decoder.", 0) == 0 || k.rfind("post_quant_conv.", 0) == 0) return TLD_OK;      // the decoder half is not used by encode
+    if (k.rfind("encoder.", 0) != 0 && k.rfind("quant_conv.", 0) != 0) return fail(TLD_ERR_KEY, "unknown state_dict key '%s'", key);
+    if (dtype != TLD_DTYPE_F32) return fail(TLD_ERR_INVALID, "'%s': host tensors must be fp32", key);
+    static const char* const ren[][2] = {{".query.", ".to_q."}, {".key.", ".to_k."}, {".value.", ".to_v."}, {".proj_attn.", ".to_out.0."}};
+    for (auto& r : ren) {
+        const size_t pos = k.find(r[0]);
+        if (pos != std::string::npos && k.find(".attentions.") != std::string::npos) k.replace(pos, strlen(r[0]), r[1]);
+    }
+    HostTensor t;
+    int64_t n = 1;
+    for (int i = 0; i < ndim; ++i) { if (shape[i] < 0) return fail(TLD_ERR_SHAPE, "'%s': negative dimension", key); t.shape.push_back(shape[i]); n *= shape[i]; }
+    t.data.assign(reinterpret_cast<const float*>(host_ptr), reinterpret_cast<const float*>(host_ptr) + n);
+    v->host[k] = std::move(t);
+    return TLD_OK;
+}
+
+int tld_vae_enc_finalize_weights(tld_vae_enc* e) {
+    if (!e) return fail(TLD_ERR_INVALID, "null encoder");
+    tld_vae* v = &e->core;
+    if (v->finalized) return fail(TLD_ERR_STATE, "weights already finalized");
+    DeviceGuard guard(e->cfg.device_id);
+    const int c0 = v->boc[0], C = v->C0, cin = e->cin, oc = e->oc;
+    const HostTensor* t = nullptr;
+    {   // conv_in: [c0][cin][3][3] -> fp32 [tap][cin][c0]
+        if (int rc = need(v, "encoder.conv_in.weight", {c0, cin, 3, 3}, &t)) return rc;
+        std::vector<float> wt((size_t)9 * cin * c0);
+        for (int o = 0; o < c0; ++o)
+            for (int c = 0; c < cin; ++c)
+                for (int tap = 0; tap < 9; ++tap) wt[((size_t)tap * cin + c) * c0 + o] = t->data[((size_t)o * cin + c) * 9 + tap];
+        if (int rc = upload_f32(v, wt, &e->cin_wt)) return rc;
+        if (int rc = need(v, "encoder.conv_in.bias", {c0}, &t)) return rc;
+        if (int rc = upload_f32(v, t->data, &e->cin_b)) return rc;
+    }
+    e->downs.resize(v->nb);
+    int c = c0;
+    for (int i = 0; i < v->nb; ++i) {
+        DownBlock& db = e->downs[i];
+        db.cout = v->boc[i];
+        db.res.resize(e->cfg.layers_per_block);
+        const std::string pre = "encoder.down_blocks." + std::to_string(i);
+        for (int j = 0; j < e->cfg.layers_per_block; ++j)
+            if (int rc = pack_resnet(v, pre + ".resnets." + std::to_string(j), j == 0 ? c : db.cout, db.cout, &db.res[j])) return rc;
+        c = db.cout;
+        db.has_down = i != v->nb - 1;
+        if (db.has_down)
+            if (int rc = pack_conv(v, pre + ".downsamplers.0.conv", c, c, 3, &db.down)) return rc;
+    }
+    if (int rc = pack_resnet(v, "encoder.mid_block.resnets.0", C, C, &v->mid0)) return rc;
+    if (int rc = pack_resnet(v, "encoder.mid_block.resnets.1", C, C, &v->mid1)) return rc;
+    if (e->cfg.mid_block_attention) {
+        const std::string a = "encoder.mid_block.attentions.0";
+        if (int rc = pack_gn(v, a + ".group_norm", C, &v->attn_gn)) return rc;
+        std::vector<float> w((size_t)3 * C * C), b((size_t)3 * C);
+        const char* names[3] = {".to_q", ".to_k", ".to_v"};
+        for (int i = 0; i < 3; ++i) {
+            if (int rc = need(v, a + names[i] + ".weight", {C, C}, &t)) return rc;
+            memcpy(w.data() + (size_t)i * C * C, t->data.data(), (size_t)C * C * 4);
+            if (int rc = need(v, a + names[i] + ".bias", {C}, &t)) return rc;
+            memcpy(b.data() + (size_t)i * C, t->data.data(), (size_t)C * 4);
+        }
+        v->attn_qkv.cin = C; v->attn_qkv.cout = 3 * C; v->attn_qkv.k = 1;
+        if (int rc = upload_bf16(v, w, &v->attn_qkv.w)) return rc;
+        if (int rc = upload_f32(v, b, &v->attn_qkv.b)) return rc;
+        if (int rc = need(v, a + ".to_out.0.weight", {C, C}, &t)) return rc;
+        v->attn_out.cin = C; v->attn_out.cout = C; v->attn_out.k = 1;
+        if (int rc = upload_bf16(v, t->data, &v->attn_out.w)) return rc;
+        if (int rc = need(v, a + ".to_out.0.bias", {C}, &t)) return rc;
+        if (int rc = upload_f32(v, t->data, &v->attn_out.b)) return rc;
+    }
+    {
+        std::vector<float> z(1024, 0.f);
+        if (int rc = upload_f32(v, z, &v->zero_bias)) return rc;
+    }
+    if (int rc = pack_gn(v, "encoder.conv_norm_out", C, &v->norm_out)) return rc;
+    if (int rc = pack_conv(v, "encoder.conv_out", C, oc, 3, &v->conv_out)) return rc;      // bf16 [oc][9][C]; bias added by the tail kernel
+    if (e->cfg.use_quant_conv) {
+        if (int rc = need(v, "quant_conv.weight", {oc, oc, 1, 1}, &t)) return rc;
+        if (int rc = upload_f32(v, t->data, &e->qc_w)) return rc;
+        if (int rc = need(v, "quant_conv.bias", {oc}, &t)) return rc;
+        if (int rc = upload_f32(v, t->data, &e->qc_b)) return rc;
+    }
+    v->host.clear();
+    HIP_TRY(hipDeviceSynchronize());
+    v->finalized = true;
+    return TLD_OK;
+}
+
+int tld_vae_enc_encode(tld_vae_enc* e, const void* x, float* moments, int32_t batch, int32_t io_dtype, void* hip_stream) {
+    if (!e || !x || !moments) return fail(TLD_ERR_INVALID, "null argument");
+    tld_vae* v = &e->core;
+    if (!v->finalized) return fail(TLD_ERR_STATE, "weights not finalized");
+    if (batch < 1 || batch > e->cfg.max_batch) return fail(TLD_ERR_INVALID, "batch=%d outside 1..max_batch=%d", batch, e->cfg.max_batch);
+    if (io_dtype != TLD_DTYPE_F32 && io_dtype != TLD_DTYPE_BF16 && io_dtype != TLD_DTYPE_F16) return fail(TLD_ERR_INVALID, "io_dtype=%d", io_dtype);
+    DeviceGuard guard(e->cfg.device_id);
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    const int B = batch;
+    if (v->debug) clear_stages(v);
+    for (int k = 0; k < VC_COUNT; ++k) if (!v->profile) v->ev_used[k] = 0;
+
+    int H = e->S, W = e->S;
+    int C = v->boc[0];
+    v->have_partial = false;
+    {
+        Timer t(v, VC_OTHER, s);
+        const int ppb = 256;
+        const long npix = (long)B * H * W;
+        const size_t lds = ((size_t)9 * e->cin * C + C) * sizeof(float);          // <= 148 KiB (cin 4, C0 1024)
+        if (lds > 65536)
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(vae_enc_conv_in_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(vae_enc_conv_in_kernel, dim3((unsigned)((npix + ppb - 1) / ppb)), dim3(256), lds, s, x, io_dtype, e->cin, e->S,
+                           e->cin_wt, e->cin_b, v->data(0), C, ppb, npix);
+        if (int rc = check_launch("conv_in")) return rc;
+    }
+    int x0 = 0;
+    if (int rc = snapshot(v, "conv_in", x0, B, H, W, C, s)) return rc;
+    for (int i = 0; i < v->nb; ++i) {
+        const DownBlock& db = e->downs[i];
+        for (size_t j = 0; j < db.res.size(); ++j) {
+            if (int rc = resnet(v, db.res[j], &x0, B, H, W, s)) return rc;
+            C = db.cout;
+            const std::string nm = "down" + std::to_string(i) + ".res" + std::to_string(j);
+            if (int rc = snapshot(v, nm.c_str(), x0, B, H, W, C, s)) return rc;
+        }
+        if (db.has_down) {                    // Downsample2D: pad (0, 1, 0, 1), 3x3 conv with stride 2 -- one implicit GEMM over the small image
+            const int dst = (x0 + 1) & 3;
+            H /= 2; W /= 2;
+            if (int rc = conv3x3(v, x0, dst, db.down, B, H, W, 0, EPI_BIAS_BF16, nullptr, s, 1)) return rc;
+            x0 = dst;
+            const std::string nm = "down" + std::to_string(i) + ".downsample";
+            if (int rc = snapshot(v, nm.c_str(), x0, B, H, W, C, s)) return rc;
+        }
+    }
+    if (int rc = resnet(v, v->mid0, &x0, B, H, W, s)) return rc;
+    if (int rc = snapshot(v, "mid.res0", x0, B, H, W, C, s)) return rc;
+    if (e->cfg.mid_block_attention) {
+        if (int rc = attention(v, &x0, B, H, W, C, s)) return rc;
+        if (int rc = snapshot(v, "mid.attn", x0, B, H, W, C, s)) return rc;
+    }
+    if (int rc = resnet(v, v->mid1, &x0, B, H, W, s)) return rc;
+    if (int rc = snapshot(v, "mid.res1", x0, B, H, W, C, s)) return rc;
+    const int t = (x0 + 1) & 3;
+    if (int rc = group_norm(v, x0, t, v->norm_out, B, H * W, C, true, s)) return rc;
+    if (int rc = snapshot(v, "norm_out", t, B, H, W, C, s)) return rc;
+    if (int rc = conv3x3(v, t, -1, v->conv_out, B, H, W, 0, EPI_F32, v->out_f32, s)) return rc;
+    {
+        Timer tm(v, VC_OTHER, s);
+        const long total = (long)B * H * W;
+        hipLaunchKernelGGL(vae_enc_out_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, v->out_f32, v->conv_out.b, e->qc_w, e->qc_b,
+                           moments, H * W, e->oc, total);
+        if (int rc = check_launch("conv_out / quant_conv tail")) return rc;
+    }
+    return TLD_OK;
+}
+
+int tld_vae_enc_set_debug(tld_vae_enc* e, int32_t enable) {
+    if (!e) return fail(TLD_ERR_INVALID, "null encoder");
+    return tld_vae_set_debug(&e->core, enable);
+}
+
+int tld_vae_enc_read_stage(tld_vae_enc* e, const char* name, float* host_out, int64_t numel, int64_t* shape4) {
+    if (!e) return fail(TLD_ERR_INVALID, "null encoder");
+    return tld_vae_read_stage(&e->core, name, host_out, numel, shape4);
+}
+
+int tld_vae_enc_set_profile(tld_vae_enc* e, int32_t enable) {
+    if (!e) return fail(TLD_ERR_INVALID, "null encoder");
+    return tld_vae_set_profile(&e->core, enable);
+}
+
+int tld_vae_enc_get_profile(tld_vae_enc* e, int32_t kclass, double* total_ms, int64_t* launches) {
+    if (!e) return fail(TLD_ERR_INVALID, "null encoder");
+    return tld_vae_get_profile(&e->core, kclass, total_ms, launches);
+}
+
+int64_t tld_vae_enc_weight_bytes(const tld_vae_enc* e) { return e ? e->core.weight_bytes : 0; }
+
+int tld_vae_enc_destroy(tld_vae_enc* e) {
+    if (!e) return TLD_OK;
+    DeviceGuard guard(e->cfg.device_id);
+    enc_release(e);
+    delete e;
+    return TLD_OK;
+}
+
+// Test hook: the stride-2 implicit-GEMM 3x3 convolution alone (Downsample2D: pad (0, 1, 0, 1), stride 2).  H x W is the OUTPUT size.
+// in: bf16 channels-last [B, 2H, 2W, cin] (device); w: bf16 [cout][3][3][cin] (device); out: fp32 [B*H*W][cout] (device).
+int tld_debug_conv3x3_s2(const void* in_bf16, const void* w_bf16, float* out_f32, int32_t B, int32_t H, int32_t W, int32_t cin,
+                         int32_t cout, void* hip_stream) {
+    if (!in_bf16 || !w_bf16 || !out_f32) return fail(TLD_ERR_INVALID, "null argument");
+    if (cin % 64 || cin < 64) return fail(TLD_ERR_INVALID, "cin=%d must be a multiple of 64", cin);
+    if (B < 1 || H < 1 || W < 1 || cout < 1 || H > 8192 || W > 8192) return fail(TLD_ERR_INVALID, "bad shape");
+    PtrDeviceGuard guard(in_bf16);
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    const size_t n = (size_t)B * (2 * H) * (2 * W) * cin * 2;
+    if (n + kHdr >= (1ull << 32)) return fail(TLD_ERR_INVALID, "operands must be smaller than 4 GiB");
+    char* buf = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf), n + kHdr));
+    HIP_TRY(hipMemsetAsync(buf, 0, kHdr, s));
+    HIP_TRY(hipMemcpyAsync(buf + kHdr, in_bf16, n, hipMemcpyDeviceToDevice, s));
+    GemmParams p{};
+    p.A = reinterpret_cast<const bf16*>(buf);
+    p.conv = 1; p.cv_h = H; p.cv_w = W; p.cv_down = 1; p.cv_cin = cin; p.cv_data_off = kHdr; p.lda = cin;
+    p.W = reinterpret_cast<const bf16*>(w_bf16); p.ldw = 9 * cin;
+    p.M = B * H * W; p.N = cout; p.K = 9 * cin;
+    p.c_f32 = out_f32; p.ldc = cout;
+    launch_gemm(p, EPI_F32, s);
+    const hipError_t e = hipGetLastError();
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipFree(buf));
+    if (e != hipSuccess) return fail(TLD_ERR_HIP, "conv3x3_s2 launch failed: %s", hipGetErrorString(e));
     return TLD_OK;
 }
 
