@@ -119,7 +119,8 @@ TLD_API int tld_engine_set_debug(tld_engine* e, int32_t enable);
 TLD_API int tld_engine_read_stage(tld_engine* e, const char* name, float* host_out, int64_t numel);
 
 /* Test hook: C[M,N] = A[M,K] . W[N,K]^T with the engine's bf16 MFMA GEMM (fp32 accumulate), bf16
- * device inputs, fp32 device output.  K % 64 == 0. */
+ * device inputs, fp32 device output.  K % 64 == 0.  Refused (TLD_ERR_INVALID, nothing launched) when an operand row
+ * starts beyond the reach of the GEMM's 32-bit DMA offsets: (M - 1) K 2 + 128 > 2^32, or the same for N. */
 TLD_API int tld_debug_gemm_bf16(const void* a_bf16, const void* w_bf16, float* c_f32, int32_t M, int32_t N,
                         int32_t K, void* hip_stream);
 

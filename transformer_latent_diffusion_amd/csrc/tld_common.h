@@ -400,7 +400,9 @@ struct GemmParams {
                                   //   bottom / right pad, which reads the zero page.  Excludes cv_up (launch_gemm refuses both).
 };
 
-void launch_gemm(const GemmParams& p, int epilogue, hipStream_t s);
+// TLD_OK, or TLD_ERR_INVALID with the reason in tld_last_error() when nothing was launched: a plain launch whose operand rows lie beyond
+// the reach of the kernels' 32-bit DMA offsets, or a conv with both cv_up and cv_down
+int launch_gemm(const GemmParams& p, int epilogue, hipStream_t s);
 // EPI_UP_DWCONV2 on 256 x 128 tiles with 4-wave workgroups (tld_updw.hip): bitwise equal to the 8-wave kernel, taken by launch_gemm for launches of at most one tile per CU
 bool updw_pp_supported(const GemmParams& p);
 void launch_updw_pp(const GemmParams& p, hipStream_t s);

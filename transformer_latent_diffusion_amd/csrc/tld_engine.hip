@@ -961,12 +961,11 @@ int tld_sample(tld_engine* e, const void* x_T, const void* labels, const float* 
 int tld_debug_gemm_bf16(const void* a, const void* w, float* c, int32_t M, int32_t N, int32_t K, void* hip_stream) {
     if (!a || !w || !c) return fail(TLD_ERR_INVALID, "null argument");
     if (K % 64 || K <= 0 || M <= 0 || N <= 0) return fail(TLD_ERR_INVALID, "need K %% 64 == 0 and positive sizes");
-    if ((int64_t)M * K * 2 >= (int64_t)1 << 32 || (int64_t)N * K * 2 >= (int64_t)1 << 32)
-        return fail(TLD_ERR_INVALID, "operands must be smaller than 4 GiB");
     GemmParams g{};
     g.A = static_cast<const bf16*>(a); g.lda = K; g.W = static_cast<const bf16*>(w); g.ldw = K;
     g.M = M; g.N = N; g.K = K; g.c_f32 = c; g.ldc = N;
-    launch_gemm(g, EPI_F32, static_cast<hipStream_t>(hip_stream));
+    // the launch's own reach check decides: the last A row may start up to 4 GiB - 128 bytes into the operand
+    if (launch_gemm(g, EPI_F32, static_cast<hipStream_t>(hip_stream))) return TLD_ERR_INVALID;
     HIP_TRY(hipGetLastError());
     return TLD_OK;
 }
@@ -978,7 +977,7 @@ int tld_debug_gemm_splitk(const void* a, const void* w, float* c_slices, int32_t
     GemmParams g{};
     g.A = static_cast<const bf16*>(a); g.lda = K; g.W = static_cast<const bf16*>(w); g.ldw = K;
     g.M = M; g.N = N; g.K = K / ksplit; g.ksplit = ksplit; g.c_f32 = c_slices; g.ldc = N;
-    launch_gemm(g, EPI_F32, static_cast<hipStream_t>(hip_stream));
+    if (launch_gemm(g, EPI_F32, static_cast<hipStream_t>(hip_stream))) return TLD_ERR_INVALID;     // (refused: reason in tld_last_error)
     HIP_TRY(hipGetLastError());
     return TLD_OK;
 }
@@ -1098,7 +1097,7 @@ int tld_debug_gemm_mx8(const void* a_e4m3, const void* a_scale, const void* w_e4
     g.A = static_cast<const bf16*>(a_e4m3); g.lda = K; g.W = static_cast<const bf16*>(w_e4m3); g.ldw = K;
     g.a_scale = static_cast<const uint8_t*>(a_scale); g.w_scale = static_cast<const uint8_t*>(w_scale);
     g.M = M; g.N = N; g.K = K; g.c_f32 = c; g.ldc = N;
-    launch_gemm(g, EPI_F32, static_cast<hipStream_t>(hip_stream));
+    if (launch_gemm(g, EPI_F32, static_cast<hipStream_t>(hip_stream))) return TLD_ERR_INVALID;     // (refused: reason in tld_last_error)
     HIP_TRY(hipGetLastError());
     return TLD_OK;
 }

@@ -5,6 +5,7 @@
 //
 // One persistent workgroup per CU (8 waves) walks a static list of 256-row tiles; see the comment above
 // gemm256p_kernel for the pipeline and DESIGN.md 4.1 for the measurements that shaped it.
+#include "../../include/tld_hip.h"
 #include "tld_common.h"
 #include "tld_attn_core.h"
 #include <cstdlib>
@@ -204,7 +205,8 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, int nblocks
     const int nk = CONV ? 9 * (p.cv_cin >> 6) : p.K * ESZ / (G::BK * 2);   // 128-byte K-steps
     // DMA addressing: a uniform 64-bit base (operand + K offset, SGPRs) plus one 32-bit byte offset per piece and
     // lane (row clamp, row pitch and the source-side swizzle), recomputed once per tile -- per K-step and piece the
-    // only VALU work is the load itself.  (Operands are < 4 GiB: checked at launch.)
+    // only VALU work is the load itself.  (Every row offset fits the 32 bits: launch_gemm checks plain launches, the VAE's create
+    // functions size the conv buffers.)
     unsigned voffA[G::A_PIECES], voffB[G::B_PIECES];
     // CONV: output pixel (y << 16 | x) of every A row this lane brings in, and the first pixel of its sample in the source image
     unsigned cpix[G::A_PIECES], cbase[G::A_PIECES];
@@ -1655,7 +1657,9 @@ int choose_bn(long M, long N, int epilogue, long K) {
     if (bn == 192 && (epilogue != EPI_BIAS_RESID || N % 192)) bn = 128;
     // N = 768 with the plain bias epilogue (the training step's five per layer): one round of 256 x 384 tiles at the training batch instead of
     // three rounds of 256 x 128 (0.71 -> 1.0 PFLOP/s)
-    if (epilogue == EPI_BIAS_BF16 && N % 384 == 0 && N < 1536 && (ntm * (N / 384)) % 256 == 0) bn = 384;      // (callers with a LayerNorm-3 fold have N = 4 d >= 1536)
+    // (K >= 384: the shapes it was built and tested for.  The VAE's attention projection at 128 channels and 65 536 tokens -- N = 384, K = 128,
+    // 256 tile-rows -- met the other conditions and came out wrong in every row; it now takes the 128-wide tiles like every other K = 128 launch.)
+    if (epilogue == EPI_BIAS_BF16 && N % 384 == 0 && N < 1536 && K >= 384 && (ntm * (N / 384)) % 256 == 0) bn = 384;      // (callers with a LayerNorm-3 fold have N = 4 d >= 1536)
     if (bn == 384 && ((epilogue != EPI_BIAS_RESID && epilogue != EPI_BIAS_BF16) || N % 384)) bn = 128;
     if (bn != 256 && bn != 192 && bn != 384) bn = 128;
     return bn;
@@ -1666,7 +1670,25 @@ int gemm_resid_stat_slots(int N) {
     return (N % 192 == 0 && N / 96 <= kLnSlots) ? N / 96 : 0;
 }
 
-void launch_gemm(const GemmParams& p_in, int epilogue, hipStream_t s) {
+// The DMA of a plain (non-conv, non-TN) launch forms each operand row's address as a uniform 64-bit base plus a 32-bit
+// byte offset  row * pitch (__umul24: both factors < 2^24)  + the 16-byte piece inside the row's first 128 bytes (+ the
+// block-diagonal group's W offset).  The largest such offset must not wrap: (M - 1) lda ESZ + 128 <= 2^32 for A, and
+// (N - 1) ldw ESZ + 128 + the last group's offset for W.  Host arithmetic only; the kernels are unchanged.
+static int gemm_offsets_fit(const GemmParams& p) {
+    const uint64_t esz = p.f8 ? 1 : 2, lim = 1ull << 32;
+    const uint64_t pa = (uint64_t)p.lda * esz, pw = (uint64_t)p.ldw * esz;
+    if (p.M < 1 || p.N < 1 || p.M > (1 << 24) || p.N > (1 << 24) || pa >= (1u << 24) || pw >= (1u << 24)) return 0;
+    if ((uint64_t)(p.M - 1) * pa + 128 > lim) return 0;
+    const uint64_t wgrp = p.w_batch_rows ? (uint64_t)((p.M - 1) / p.w_batch_rows) * p.w_batch_stride_bytes : 0;
+    return (uint64_t)(p.N - 1) * pw + 128 + wgrp <= lim;
+}
+
+int launch_gemm(const GemmParams& p_in, int epilogue, hipStream_t s) {
+    if (!p_in.conv && !gemm_offsets_fit(p_in)) {      // launch nothing, report it to the caller
+        set_last_error("launch_gemm: an operand row lies beyond the 4 GiB reach of the 32-bit DMA offsets (row * pitch + 128 bytes must stay "
+                       "<= 2^32 for A and for W); split the launch by rows");
+        return TLD_ERR_INVALID;
+    }
 #ifdef TLD_DBG_EPI
     static const int dbg_epi_env = getenv("TLD_EPI_DBG") ? atoi(getenv("TLD_EPI_DBG")) : 0;
     GemmParams p = p_in;
@@ -1678,7 +1700,7 @@ void launch_gemm(const GemmParams& p_in, int epilogue, hipStream_t s) {
         // small batches (one to five images per call): one 256 x 128 tile per workgroup on twice as many CUs finishes sooner than one 256 x 256 tile (17.7 vs 28.6 us at one
         // image); results are bitwise those of the 8-wave kernel (tld_updw.hip), so the choice may follow the batch size.  TLD_UPDW_SMALL=0: A/B and test hook.
         static const bool small_on = !(getenv("TLD_UPDW_SMALL") && atoi(getenv("TLD_UPDW_SMALL")) == 0);
-        if (small_on && updw_pp_supported(p) && (long)(p.M / 256) * (p.N / 128) <= device_cu_count()) { launch_updw_pp(p, s); return; }
+        if (small_on && updw_pp_supported(p) && (long)(p.M / 256) * (p.N / 128) <= device_cu_count()) { launch_updw_pp(p, s); return TLD_OK; }
     }
     if (epilogue == EPI_F32 && p.ksplit > 1 && !p.f8 && !p.conv) {
         // the low-latency classes' split-K down projection: one 256 x 128 x (K / splits) item per 4-wave workgroup while the launch has at most two items per CU
@@ -1686,17 +1708,17 @@ void launch_gemm(const GemmParams& p_in, int epilogue, hipStream_t s) {
         static const bool sk_on = !(getenv("TLD_SPLITK_SMALL") && atoi(getenv("TLD_SPLITK_SMALL")) == 0);
         // (two such workgroups fit a CU and, K loops only, share it well: eight images in class 1 -- 384 items -- 58.3 -> 48.8 ms per generate; the fused up-projection's epilogue does
         // not: 288 - 480 tiles on two workgroups per CU measured 1 - 2 ms slower than the 8-wave kernel, hence one tile per CU there)
-        if (sk_on && splitk_pp_supported(p) && (long)(p.M / 256) * (p.N / 128) * p.ksplit <= 2L * device_cu_count()) { launch_splitk_pp(p, s); return; }
+        if (sk_on && splitk_pp_supported(p) && (long)(p.M / 256) * (p.N / 128) * p.ksplit <= 2L * device_cu_count()) { launch_splitk_pp(p, s); return TLD_OK; }
     }
     if (epilogue == EPI_BIAS_RESID && !p.f8 && !p.conv) {
         // the default class's down projection at small batch: 64 x 192 or 128 x 192 tiles on 4-wave workgroups while the launch has at most one tile per CU (tld_updw.hip; bitwise the
         // 8-wave 192- / 384-wide kernels below).  TLD_DOWN_SMALL=0: A/B and test hook.
         static const bool dn_on = !(getenv("TLD_DOWN_SMALL") && atoi(getenv("TLD_DOWN_SMALL")) == 0);
-        if (dn_on && down_pp_supported(p) && down_pp_fits(p)) { launch_down_pp(p, s); return; }
+        if (dn_on && down_pp_supported(p) && down_pp_fits(p)) { launch_down_pp(p, s); return TLD_OK; }
     }
     if (p.conv && p.cv_up && p.cv_down) {     // upsampling and stride 2 are exclusive addressing modes: launch nothing, report it to the caller
         set_last_error("launch_gemm: conv with both cv_up and cv_down set");
-        return;
+        return TLD_ERR_INVALID;
     }
     int bn = choose_bn(p.M, p.N, epilogue, p.K);
     if (p.conv) {           // 256-wide tiles when the width allows and they fill the chip, else 128
@@ -1719,6 +1741,7 @@ void launch_gemm(const GemmParams& p_in, int epilogue, hipStream_t s) {
     else if (bn == 192) launch256p<192>(p, epilogue, s);
     else if (bn == 128) launch256p<128>(p, epilogue, s);
     else launch256p<256>(p, epilogue, s);
+    return TLD_OK;
 }
 
 void launch_gemm_tn(const GemmParams& p, hipStream_t s) {

@@ -408,6 +408,13 @@ struct Timer {
     ~Timer() { if (on) (void)hipEventRecord(v->ev[kc][idx].second, s); }
 };
 
+// TLD_VAE_FUSE_STATS=0 (structural switch, read at create): every GroupNorm takes its statistics from the separate
+// vae_gn_stats_kernel instead of the producing conv's epilogue -- the test hook that pins both paths against one reference
+bool fuse_stats_enabled() {
+    const char* e = getenv("TLD_VAE_FUSE_STATS");
+    return !(e && atoi(e) == 0);
+}
+
 bool chan_ok(int c) { return c == 64 || c == 128 || c == 256 || c == 512 || c == 1024; }
 
 // ---- op sequencing ---------------------------------------------------------------------------------------------------
@@ -458,7 +465,7 @@ int conv3x3(tld_vae* v, int src, int dst, const ConvW& cw, int B, int H, int W, 
         p.gn_partial = v->gn_partial; p.gn_groups = v->G; p.gn_cpg = cpg; p.gn_hw = H * W;
         v->have_partial = true;
     }
-    launch_gemm(p, epi, s);
+    if (int rc = launch_gemm(p, epi, s)) return rc;         // (cv_up with cv_down: refused, nothing launched)
     return check_launch("conv3x3");
 }
 
@@ -468,11 +475,12 @@ int gemm(tld_vae* v, const bf16* A, int lda, const bf16* Wt, int ldw, int M, int
     Timer t(v, VC_GEMM, s);
     GemmParams p{};
     p.A = A; p.lda = lda; p.W = Wt; p.ldw = ldw; p.M = M; p.N = N; p.K = K; p.bias = bias;
+    if (w_batch_stride_bytes >= (1ull << 32)) return fail(TLD_ERR_INVALID, "gemm: a block-diagonal W stride beyond the 32-bit DMA offsets");
     p.w_batch_rows = w_batch_rows; p.w_batch_stride_bytes = (unsigned)w_batch_stride_bytes;
     if (epi == EPI_BIAS_BF16) { p.out_bf16 = out; p.ldo = ldo; }
     else if (epi == EPI_BIAS_RESID) { p.resid = reinterpret_cast<resid_t*>(out); p.ldr = ldo; }
     else { p.c_f32 = c_f32; p.ldc = ldo; }
-    launch_gemm(p, epi, s);
+    if (int rc = launch_gemm(p, epi, s)) return rc;         // (operand rows beyond the 32-bit DMA offsets: refused, nothing launched)
     return check_launch("gemm");
 }
 
@@ -523,6 +531,7 @@ int attention(tld_vae* v, int* xi, int B, int H, int W, int C, hipStream_t s) {
     if (int rc = group_norm(v, x, t, v->attn_gn, B, HW, C, false, s)) return rc;
     if (int rc = gemm(v, v->data(t), C, v->attn_qkv.w, C, M, 3 * C, C, EPI_BIAS_BF16, v->attn_qkv.b, v->data(qkv), 3 * C, nullptr, s)) return rc;
     const float scale = 1.0f / sqrtf((float)C);
+    const size_t pv_reach = (size_t)1 << 32;         // bytes a GEMM operand row offset can reach (launch_gemm)
     // groups of `step` samples per launch: all of att_nb when a 256-row tile cannot straddle two samples, else one by one
     const int step = HW % 256 == 0 ? v->att_nb : 1;
     for (int b0 = 0; b0 < B; b0 += step) {
@@ -537,8 +546,20 @@ int attention(tld_vae* v, int* xi, int B, int H, int W, int C, hipStream_t s) {
                                (size_t)HW * 3 * C, (size_t)C * HW);
         }
         // O_b = P_b V_b  (into the tokens of buffer t, which the projections no longer need)
-        if (int rc = gemm(v, v->probs, HW, v->vt, HW, n * HW, C, HW, EPI_BIAS_BF16, v->zero_bias, v->data(t) + (size_t)b0 * HW * C, C, nullptr, s,
-                          n > 1 ? HW : 0, (size_t)C * HW * 2)) return rc;
+        if ((size_t)(n * HW - 1) * HW * 2 + 128 <= pv_reach) {
+            if (int rc = gemm(v, v->probs, HW, v->vt, HW, n * HW, C, HW, EPI_BIAS_BF16, v->zero_bias, v->data(t) + (size_t)b0 * HW * C, C, nullptr, s,
+                              n > 1 ? HW : 0, (size_t)C * HW * 2)) return rc;
+        } else {
+            // one sample's probabilities reach past the 4 GiB of the GEMM's 32-bit row offsets (HW >= 46 341, latent side >= 216):
+            // query-row blocks of a multiple of 256 rows, each with its own A base, so that every row offset stays in reach
+            if (n != 1) return fail(TLD_ERR_INVALID, "attention: %d samples per launch at %d tokens", n, HW);
+            const int rb = (int)(((pv_reach - 128) / ((size_t)HW * 2) + 1) / 256 * 256);
+            for (int r0 = 0; r0 < HW; r0 += rb) {
+                const int rows = std::min(rb, HW - r0);
+                if (int rc = gemm(v, v->probs + (size_t)r0 * HW, HW, v->vt, HW, rows, C, HW, EPI_BIAS_BF16, v->zero_bias,
+                                  v->data(t) + ((size_t)b0 * HW + r0) * C, C, nullptr, s)) return rc;
+            }
+        }
     }
     if (int rc = gemm(v, v->data(t), C, v->attn_out.w, C, M, C, C, EPI_BIAS_RESID, v->attn_out.b, v->data(x), C, nullptr, s)) return rc;
     v->have_partial = false;               // x changed: the statistics a convolution left behind are stale
@@ -593,7 +614,7 @@ int tld_vae_create(const tld_vae_config* cfg, tld_vae** out) {
     v->G = cfg->norm_num_groups; v->zc = cfg->latent_channels; v->oc = cfg->out_channels; v->nb = cfg->n_blocks; v->hl = cfg->latent_size;
     v->boc.assign(cfg->block_out_channels, cfg->block_out_channels + cfg->n_blocks);
     v->C0 = v->boc[v->nb - 1];
-    v->fuse_stats = true;
+    v->fuse_stats = fuse_stats_enabled();
     v->buf_elems = max_act_elems(v) * (size_t)cfg->max_batch;
     const size_t bytes = v->buf_elems * 2 + kHdr;
     if (bytes >= (1ull << 32)) {
@@ -1034,7 +1055,7 @@ int tld_vae_enc_create(const tld_vae_enc_config* cfg, tld_vae_enc** out) {
     v->G = cfg->norm_num_groups; v->zc = cfg->latent_channels; v->oc = e->oc; v->nb = cfg->n_blocks; v->hl = e->S / down;
     v->boc.assign(cfg->block_out_channels, cfg->block_out_channels + cfg->n_blocks);
     v->C0 = v->boc[v->nb - 1];                               // (the mid block's width, as in the decoder)
-    v->fuse_stats = true;
+    v->fuse_stats = fuse_stats_enabled();
     const size_t per = enc_max_act_elems(e);
     v->buf_elems = per * (size_t)cfg->max_batch;
     const size_t bytes = v->buf_elems * 2 + kHdr;
