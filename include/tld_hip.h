@@ -304,7 +304,8 @@ TLD_API const char* tld_last_error(void);
  * caller, in the order of Denoiser.named_parameters() (tld/denoiser.py:85-114); tld_train_param_layout enumerates (key, offset,
  * numel).  The gradient all-reduce of the reference's accelerate/DDP wrapper (tld/train.py:114,168) is the caller's
  * torch.distributed all_reduce on the flat gradient vector between tld_train_forward_backward and tld_train_adam_ema.
- * cfg.max_batch = largest batch (NOT doubled); 256-token latents (image_size / patch_size == 16) only. */
+ * cfg.max_batch = largest batch (NOT doubled); square latent grids of G x G tokens, G = image_size / patch_size a multiple of 4 with
+ * 4 <= G <= 64 (16 .. 4096 tokens: the inference engine's grids up to 64 x 64; e.g. 576 tokens = 384 px at patch 2). */
 typedef struct tld_train tld_train;
 TLD_API int tld_train_create(const tld_config* cfg, tld_train** out);
 TLD_API int64_t tld_train_param_count(const tld_train* e);
@@ -336,7 +337,7 @@ TLD_API int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, co
  * ema may be NULL; grad_scale multiplies the gradient first (1 / world_size after a SUM all-reduce). */
 TLD_API int tld_train_adam_ema(tld_train* e, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t numel,
                                float lr, float beta1, float beta2, float eps, int32_t step, float ema_alpha, float grad_scale, void* hip_stream);
-/* Test hook: self-attention backward alone (head_dim 64; ntok = 64, 128 or a multiple of 256): qk [M, 2d] bf16 (q | k), vt [B, H, 64, ntok]
+/* Test hook: self-attention backward alone (head_dim 64; ntok a multiple of 16): qk [M, 2d] bf16 (q | k), vt [B, H, 64, ntok]
  * bf16, o [M, d] bf16 (forward output), g [M, d] fp32 (dL/dO) -> dqkv [M, 3d] bf16 (dq | dk | dv).  scratch: 2 * batch * heads * ntok floats
  * (row statistics between the two kernels of the ntok > 256 path; may be NULL otherwise).  Device pointers. */
 TLD_API int tld_debug_attention_bwd(const void* qk, const void* vt, const void* o, const float* g, void* dqkv, float* scratch, int32_t batch,

@@ -178,10 +178,10 @@ int tld_train_create(const tld_config* cfg, tld_train** out) {
     if (cfg->embed_dim % 64 || cfg->embed_dim > 1024 || cfg->embed_dim <= 0) return tfail(TLD_ERR_INVALID, "embed_dim must be a multiple of 64 (the head width), <= 1024");
     if (cfg->patch_size <= 0 || cfg->image_size % cfg->patch_size) return tfail(TLD_ERR_INVALID, "image_size must be a multiple of patch_size");
     const int G = cfg->image_size / cfg->patch_size;
-    // token counts the attention kernels are built for (forward: launch_attention; backward: tld_train_attn.hip); the reference trains at
-    // 256 tokens and fine-tunes at 1024 / 4096 (README.md:23)
-    if (!(G * G == 64 || (G * G) % 256 == 0) || G > 64)
-        return tfail(TLD_ERR_INVALID, "the training step supports 64 tokens or a multiple of 256 up to 4096 (image_size / patch_size = 8, 16, 32, 64); got %d", G * G);
+    // the inference engine's grids (square, side a multiple of 4: token counts that are multiples of 16, which the attention forward and
+    // backward take), up to 64 x 64; the reference trains at whatever image_size it is given (tld/train.py:83)
+    if (G % 4 || G < 4 || G > 64)
+        return tfail(TLD_ERR_INVALID, "the training step supports image_size / patch_size = G with G a multiple of 4, 4 <= G <= 64 (16 .. 4096 tokens); got G = %d", G);
     if (cfg->n_channels * cfg->patch_size * cfg->patch_size > 64) return tfail(TLD_ERR_INVALID, "patch_dim must be <= 64");
     if (cfg->noise_embed_dims % 2 || cfg->max_batch <= 0 || cfg->n_layers <= 0) return tfail(TLD_ERR_INVALID, "bad configuration");
     DevGuard dg(cfg->device_id);
@@ -505,6 +505,11 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
             if (bsk) { sk = bsk; ms = bms; }
         }
         if (e->tn_wgrad && wgrad_tn(dY, Nout, X, Kin, M, dW, e->splitk, e->splitk_floats, s)) return;
+        if (M % 64) {      // (token counts that are not multiples of 64, e.g. 144 x 3 rows): the GEMM's K loop takes whole 64-row steps, so the
+            ms = (M + 63) / 64 * 64;       // transposed operands get zero columns up to the next multiple of 64 (sk == 1 here)
+            hipMemsetAsync(e->T1, 0, (size_t)Nout * ms * 2, s);
+            hipMemsetAsync(e->T2, 0, (size_t)Kin * ms * 2, s);
+        }
         auto tr = [&](const bf16* src, int cols, bf16* dst) {
             if (M % 64 == 0 && cols % 64 == 0 && ms % 64 == 0)
                 hipLaunchKernelGGL(transpose_bf16_64, dim3(cols / 64, sk * ms / 64), blk, 0, s, src, cols, dst, ms, M, cols, sk);
@@ -513,7 +518,7 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
         };
         tr(dY, Nout, e->T1);
         tr(X, Kin, e->T2);
-        if (sk == 1) { gemm_f32(e->T1, M, e->T2, M, dW, Nout, Kin, M, s); return; }      // (ms == M here)
+        if (sk == 1) { gemm_f32(e->T1, ms, e->T2, ms, dW, Nout, Kin, ms, s); return; }      // (ms == M, or M rounded up to 64)
         GemmParams g{};
         g.A = e->T1; g.lda = ms; g.W = e->T2; g.ldw = ms; g.M = sk * Nout; g.N = Kin; g.K = ms; g.c_f32 = e->splitk; g.ldc = Kin;
         g.w_batch_rows = Nout; g.w_batch_stride_bytes = (unsigned)((size_t)Kin * ms * 2);
@@ -617,7 +622,7 @@ int tld_train_adam_ema(tld_train* e, float* params, const float* grads, float* e
     return TLD_OK;
 }
 
-/* Test hook: backward of softmax(Q K^T / 8) V for `batch` samples x `heads` heads over `ntok` tokens (64, 128 or a multiple of 256).
+/* Test hook: backward of softmax(Q K^T / 8) V for `batch` samples x `heads` heads over `ntok` tokens (a multiple of 16).
  * qk [M, 2 d] bf16 (q | k), vt [B, H, 64, ntok] bf16, o [M, d] bf16 (the forward output), g [M, d] fp32 (dL/dO); dqkv [M, 3 d] bf16 out
  * (dq | dk | dv); scratch: 2 * batch * heads * ntok floats (used when ntok > 256).  Device pointers. */
 int tld_debug_attention_bwd(const void* qk, const void* vt, const void* o, const float* g, void* dqkv, float* scratch, int32_t batch, int32_t ntok,

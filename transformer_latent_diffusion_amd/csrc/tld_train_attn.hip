@@ -14,10 +14,15 @@
 // from the one row-major image with gfx950's transposing LDS read (ds_read_b64_tr_b16: lane i of a 16-lane group receives
 // img[k0 + j][m0 + i], j = 0..3, from the 4 x 16 block whose rows the group's lanes address) -- nothing is transposed through memory,
 // and no image is kept twice.
-//   N = BT (64, 128, 256 tokens): one workgroup per (sample, head) runs both passes; L and delta stay in LDS.
-//   N = NB x 256:  kernel 1, one workgroup per (sample, head, query block): a first sweep over the key blocks for the row statistics,
+//   N <= 256: one workgroup per (sample, head) runs both passes (BT >= N); L and delta stay in LDS.
+//   N > 256:  kernel 1, one workgroup per (sample, head, query block): a first sweep over the key blocks for the row statistics,
 //           a second for dQ; L and delta go to a scratch vector.  Kernel 2, one workgroup per (sample, head, key block), sweeps the
 //           query blocks for dK and dV.
+// Any N that is a multiple of 16.  The block width is chosen per N (attn_bwd_block_waves); when N is not a multiple of BT the last query and
+// key blocks are partial (the MASKED kernels): rows past N are zero in LDS and never read from memory, keys past N leave the softmax
+// (score -inf in pass 1, P = dS = 0 in pass 2), and no dq / dk / dv row or statistic past N is stored.  N % 32 == 16 leaves one 32 x 32
+// tile half outside the sample; the masks then act per element, in the accumulator row order.  64, 128, 256 tokens and the multiples of
+// 256 keep the unmasked kernels at BT = N (<= 256) or 256.
 // Outputs are row-major bf16 [M, 3 d] (dq | dk | dv), the layout the weight- and input-gradient GEMMs consume.
 #include "tld_common.h"
 
@@ -92,7 +97,25 @@ __device__ __forceinline__ void store_tile(bf16* dst /* row of token l31, first 
         }
 }
 
-template <int NW, int MODE, typename TG>      // TG: dL/dO as fp32 (the test hook) or bf16 (the training step: the LayerNorm-2 backward leaves a bf16 copy of the residual gradient)
+// Waves per workgroup (block width BT = 32 nw tokens) of the attention backward at N tokens (N a multiple of 16).  N <= 256: one block
+// holds the sample, nw = ceil(N / 32) (64 / 128 / 256 tokens: 2 / 4 / 8, exact).  N > 256: the nw in 4 .. 8 with the least padded length
+// ceil(N / BT) BT, the wider on a tie (a multiple of 256: 8); 7 only where it leaves no padding -- the masked 7-wave dQ kernel spills.
+// Padded work (Np / N)^2 at the square grids: 16 tokens 4.0 (one 32-token tile), 144: 1.23, 400: 1.44, 784: 1.04, 1296: 1.08,
+// 1936: 1.12, 2704: 1.01, 3600: 1.03; 576, 1600, 3136 and the multiples of 256 none.
+int attn_bwd_block_waves(int ntok) {
+    if (ntok <= 256) return (ntok + 31) / 32;
+    int best = 8, pad = 1 << 30;
+    for (int nw = 8; nw >= 4; --nw) {
+        const int bt = 32 * nw, np = (ntok + bt - 1) / bt * bt;
+        if (nw == 7 && np != ntok) continue;
+        if (np < pad) { pad = np; best = nw; }
+    }
+    return best;
+}
+
+// TG: dL/dO as fp32 (the test hook) or bf16 (the training step: the LayerNorm-2 backward leaves a bf16 copy of the residual gradient).
+// MASKED: N is not a multiple of BT -- the last query / key block is partial (N a multiple of 16, so a 32-token tile is whole, half or empty).
+template <int NW, int MODE, typename TG, bool MASKED>
 __global__ __launch_bounds__(64 * NW) void attn_bwd_kernel(const bf16* __restrict__ qk, const bf16* __restrict__ vt, const bf16* __restrict__ o,
                                                           const TG* __restrict__ g, bf16* __restrict__ dqkv, float* __restrict__ stats, int H, int N) {
     using Ly = Lay<NW>;
@@ -101,7 +124,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_kernel(const bf16* __restric
     char* sQ = smem + Ly::Q; char* sK = smem + Ly::K; char* sG = smem + Ly::G; char* sV = smem + Ly::V;
     float* sL = reinterpret_cast<float*>(smem + Ly::L);
     float* sD = reinterpret_cast<float*>(smem + Ly::D);
-    const int NB = N / BT, d = H * 64;
+    const int NB = MASKED ? (N + BT - 1) / BT : N / BT, d = H * 64;
     int bid = blockIdx.x;
     const int blk = bid % NB; bid /= NB;
     const int h = bid % H, b = bid / H;
@@ -110,14 +133,26 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_kernel(const bf16* __restric
     float* Lg = stats + ((size_t)(b * H + h) * 2) * N;        // [L | delta] of this (sample, head): only the multi-block kernels touch it
     float* Dg = Lg + N;
 
-    // ---- staging: two threads per token row, four 16-byte chunks each
+    // ---- staging: two threads per token row, four 16-byte chunks each.  MASKED: rows past N are zero in LDS and never read from memory
+    // (the zero image keeps the transposing reads, which need every lane, inside the block)
     const int srow = tid >> 1, sc0 = (tid & 1) * 4;
     auto stage_rows = [&](char* img, const bf16* src, int ld, int tb) {
+        if (MASKED && tb * BT + srow >= N) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) *reinterpret_cast<u32x4*>(img + srow * kPitch + (sc0 + c) * 16) = u32x4{0u, 0u, 0u, 0u};
+            return;
+        }
         const u32x4* p = reinterpret_cast<const u32x4*>(src + (row0 + (size_t)tb * BT + srow) * ld) + sc0;
 #pragma unroll
         for (int c = 0; c < 4; ++c) *reinterpret_cast<u32x4*>(img + srow * kPitch + (sc0 + c) * 16) = p[c];
     };
     auto stage_g = [&](int qb, bool with_delta) {          // dO -> bf16 image; delta = dO . O per row
+        if (MASKED && qb * BT + srow >= N) {               // dO = 0, delta = 0 (the pair of threads of a row takes this branch together)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) *reinterpret_cast<u32x4*>(sG + srow * kPitch + (sc0 + c) * 16) = u32x4{0u, 0u, 0u, 0u};
+            if (with_delta && (tid & 1) == 0) sD[srow] = 0.f;
+            return;
+        }
         const size_t row = row0 + (size_t)qb * BT + srow;
         const u32x4* po = reinterpret_cast<const u32x4*>(o + row * d + h * 64) + sc0;
         float delta = 0.f;
@@ -157,7 +192,8 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_kernel(const bf16* __restric
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int idx = tid + j * 2 * BT, r = idx / CPR, c = idx % CPR;
-            *reinterpret_cast<u32x4*>(sV + r * PV + c * 16) = *reinterpret_cast<const u32x4*>(base + (size_t)r * N + c * 8);
+            if (MASKED && kb * BT + c * 8 >= N) *reinterpret_cast<u32x4*>(sV + r * PV + c * 16) = u32x4{0u, 0u, 0u, 0u};      // (N % 8 == 0: a chunk is whole or past N)
+            else *reinterpret_cast<u32x4*>(sV + r * PV + c * 16) = *reinterpret_cast<const u32x4*>(base + (size_t)r * N + c * 8);
         }
     };
     const bf16* qsrc = qk + h * 64;
@@ -187,6 +223,17 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_kernel(const bf16* __restric
                     st[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(sK, kt * 32 + l31, kc * 2 + hi), qf[kc], st[kt], 0, 0, 0);
             }
         };
+        // MASKED, last key block kb: scores of keys >= N become -inf before the row statistics, so P = 0 there.  (The dQ sweep needs no mask:
+        // a key past N has a zero K row, so its dS^T entry, finite, adds exactly nothing to dQ.)
+        auto mask_keys = [&](int kb) {
+#pragma unroll
+            for (int kt = 0; kt < NW; ++kt) {
+                const int lim = N - kb * BT - kt * 32 - 4 * hi;          // (r & 3) + 8 (r >> 2) is the key row of accumulator register r
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    if ((r & 3) + 8 * (r >> 2) >= lim) st[kt][r] = -__builtin_inff();
+            }
+        };
         f32x16 dq[2] = {zero16(), zero16()};
         auto dq_accum = [&]() {                             // st holds P^T of the staged key block
 #pragma unroll
@@ -208,6 +255,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_kernel(const bf16* __restric
         };
         if (MODE == ATTN_FUSED) {
             scores();
+            if (MASKED) mask_keys(0);
             float m = -3.0e38f;
 #pragma unroll
             for (int kt = 0; kt < NW; ++kt)
@@ -235,6 +283,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_kernel(const bf16* __restric
                 stage_rows(sK, ksrc, 2 * d, kb);
                 __syncthreads();
                 scores();
+                if (MASKED) mask_keys(kb);                   // (a no-op before the last block: there every lim >= 28)
                 float mb = -3.0e38f;
 #pragma unroll
                 for (int kt = 0; kt < NW; ++kt)
@@ -252,7 +301,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_kernel(const bf16* __restric
             }
             sum += __shfl_xor(sum, 32, 64);
             const float Lq = m + __builtin_amdgcn_logf(sum);
-            if (hi == 0) Lg[blk * BT + q0 + l31] = Lq;
+            if (hi == 0 && (!MASKED || blk * BT + q0 + l31 < N)) Lg[blk * BT + q0 + l31] = Lq;
             // sweep 2: dQ
             for (int kb = 0; kb < NB; ++kb) {
                 __syncthreads();
@@ -267,7 +316,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_kernel(const bf16* __restric
                 dq_accum();
             }
         }
-        if (!(TLD_AB_DBG & 8)) store_tile(dqkv + (row0 + (size_t)blk * BT + q0 + l31) * 3 * d + h * 64, dq, 0.125f, hi);
+        if (!(TLD_AB_DBG & 8) && (!MASKED || blk * BT + q0 + l31 < N)) store_tile(dqkv + (row0 + (size_t)blk * BT + q0 + l31) * 3 * d + h * 64, dq, 0.125f, hi);
         }
     }
     if (MODE == ATTN_DQ) return;
@@ -278,6 +327,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_kernel(const bf16* __restric
     __syncthreads();            // FUSED: every query's L is in LDS
     {
         const int k0 = 32 * wid;
+        const bool kval = !MASKED || blk * BT + k0 + l31 < N;           // this lane's key lies in the sample
         bf16x8 kf[4], vf[4];
 #pragma unroll
         for (int kc = 0; kc < 4; ++kc) { kf[kc] = frag(sK, k0 + l31, kc * 2 + hi); vf[kc] = tr_seq(sV, PV, 16 * kc, k0, lane); }
@@ -287,10 +337,13 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_kernel(const bf16* __restric
                 if (qb) __syncthreads();
                 stage_rows(sQ, qsrc, 2 * d, qb);
                 stage_g(qb, false);
-                if (tid < BT) { sL[tid] = Lg[qb * BT + tid]; sD[tid] = Dg[qb * BT + tid]; }
+                if (tid < BT) {
+                    if (!MASKED || qb * BT + tid < N) { sL[tid] = Lg[qb * BT + tid]; sD[tid] = Dg[qb * BT + tid]; }
+                    else { sL[tid] = 0.f; sD[tid] = 0.f; }      // queries past N: Q = dO = 0, so they add nothing to dK, dV
+                }
                 __syncthreads();
             }
-#pragma unroll 2
+#pragma unroll NW % 2 ? 1 : 2
             for (int qt = 0; qt < NW; ++qt) {
                 f32x16 s = zero16(), dp = zero16();
 #pragma unroll
@@ -302,8 +355,8 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_kernel(const bf16* __restric
                 for (int r = 0; r < 16; ++r) {
                     const int qi = qt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
                     const float p = __builtin_amdgcn_exp2f(s[r] * kC2 - sL[qi]);
-                    s[r] = p;                                   // P
-                    dp[r] = p * (dp[r] - sD[qi]);               // dS
+                    s[r] = kval ? p : 0.f;                      // P
+                    dp[r] = kval ? p * (dp[r] - sD[qi]) : 0.f;  // dS
                 }
 #pragma unroll
                 for (int sl = 0; sl < 2; ++sl) {
@@ -317,29 +370,58 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_kernel(const bf16* __restric
             }
         }
         bf16* dst = dqkv + (row0 + (size_t)blk * BT + k0 + l31) * 3 * d + h * 64;
-        if (!(TLD_AB_DBG & 8)) {
+        if (!(TLD_AB_DBG & 8) && kval) {
             store_tile(dst + d, dk, 0.125f, hi);
             store_tile(dst + 2 * d, dv, 1.0f, hi);
         }
     }
 }
 
-template <int NW, int MODE, typename TG>
+template <int NW, int MODE, typename TG, bool MASKED>
 void launch_one(const bf16* qk, const bf16* vt, const bf16* o, const TG* g, bf16* dqkv, float* stats, int batch, int ntok, int heads, hipStream_t s) {
     static PerDeviceOnce once;
-    once.run([&] { hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kernel<NW, MODE, TG>), hipFuncAttributeMaxDynamicSharedMemorySize, Lay<NW>::BYTES); });
-    hipLaunchKernelGGL((attn_bwd_kernel<NW, MODE, TG>), dim3(batch * heads * (ntok / (32 * NW))), dim3(64 * NW), Lay<NW>::BYTES, s, qk, vt, o, g, dqkv, stats, heads,
-                       ntok);
+    once.run([&] { hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kernel<NW, MODE, TG, MASKED>), hipFuncAttributeMaxDynamicSharedMemorySize, Lay<NW>::BYTES); });
+    constexpr int BT = 32 * NW;
+    hipLaunchKernelGGL((attn_bwd_kernel<NW, MODE, TG, MASKED>), dim3(batch * heads * ((ntok + BT - 1) / BT)), dim3(64 * NW), Lay<NW>::BYTES, s, qk, vt, o, g, dqkv,
+                       stats, heads, ntok);
+}
+
+// a block width chosen at run time: the masked kernel when N is not a multiple of BT = 32 nw
+template <int MODE, typename TG>
+void launch_nw(int nw, const bf16* qk, const bf16* vt, const bf16* o, const TG* g, bf16* dqkv, float* stats, int batch, int ntok, int heads, hipStream_t s) {
+    const bool masked = ntok % (32 * nw) != 0;
+#define TLD_ATTN_BWD_NW(W) \
+    case W: \
+        if (masked) launch_one<W, MODE, TG, true>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s); \
+        else launch_one<W, MODE, TG, false>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s); \
+        break;
+    if constexpr (MODE == ATTN_FUSED) {
+        switch (nw) { TLD_ATTN_BWD_NW(1) TLD_ATTN_BWD_NW(2) TLD_ATTN_BWD_NW(3) TLD_ATTN_BWD_NW(4) TLD_ATTN_BWD_NW(5) TLD_ATTN_BWD_NW(6) TLD_ATTN_BWD_NW(7)
+                      TLD_ATTN_BWD_NW(8) }
+    } else {
+        switch (nw) {
+            TLD_ATTN_BWD_NW(4) TLD_ATTN_BWD_NW(5) TLD_ATTN_BWD_NW(6) TLD_ATTN_BWD_NW(8)
+            case 7: launch_one<7, MODE, TG, false>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s); break;      // (exact only: see attn_bwd_block_waves)
+        }
+    }
+#undef TLD_ATTN_BWD_NW
 }
 
 template <typename TG>
 int launch_bwd(const bf16* qk, const bf16* vt, const bf16* o, const TG* g, bf16* dqkv, float* stats, int batch, int ntok, int heads, hipStream_t s) {
-    if (ntok == 256) launch_one<8, ATTN_FUSED>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
-    else if (ntok == 128) launch_one<4, ATTN_FUSED>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
-    else if (ntok == 64) launch_one<2, ATTN_FUSED>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
+    // the token counts of the first training engine keep their kernels (unmasked, same block widths)
+    if (ntok == 256) launch_one<8, ATTN_FUSED, TG, false>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
+    else if (ntok == 128) launch_one<4, ATTN_FUSED, TG, false>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
+    else if (ntok == 64) launch_one<2, ATTN_FUSED, TG, false>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
     else if (ntok > 256 && ntok % 256 == 0 && stats) {
-        launch_one<8, ATTN_DQ>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
-        launch_one<8, ATTN_DKV>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
+        launch_one<8, ATTN_DQ, TG, false>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
+        launch_one<8, ATTN_DKV, TG, false>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
+    } else if (ntok % 16 || ntok <= 0) return 1;
+    else if (ntok < 256) launch_nw<ATTN_FUSED>(attn_bwd_block_waves(ntok), qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
+    else if (stats) {
+        const int nw = attn_bwd_block_waves(ntok);
+        launch_nw<ATTN_DQ>(nw, qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
+        launch_nw<ATTN_DKV>(nw, qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
     } else return 1;
     return 0;
 }
@@ -347,7 +429,7 @@ int launch_bwd(const bf16* qk, const bf16* vt, const bf16* o, const TG* g, bf16*
 }  // namespace
 
 // qk [M, 2 d] (q | k) and vt [B, H, 64, N]: the forward's saved operands;  o [M, d]: the forward's output;  g [M, d]: dL/dO (fp32 or bf16);
-// dqkv [M, 3 d] bf16 out.  N = 64, 128 or a multiple of 256; `stats` = 2 B H N floats of scratch, touched only when N > 256.
+// dqkv [M, 3 d] bf16 out.  N a multiple of 16 (returns 1 otherwise); `stats` = 2 B H N floats of scratch, touched only when N > 256 (rows < N).
 int launch_attention_bwd(const bf16* qk, const bf16* vt, const bf16* o, const float* g, bf16* dqkv, float* stats, int batch, int ntok, int heads, hipStream_t s) {
     return launch_bwd<float>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
 }
