@@ -142,6 +142,19 @@ TLD_API int tld_debug_gemm_mx8(const void* a_e4m3, const void* a_scale, const vo
 TLD_API int tld_debug_gemm_bench(int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t ntok, int32_t iters,
                                  double* avg_ms);
 
+/* Test hook, host only (no GPU needed): which kernel, tile, K loop and grid a GEMM launch of the engine gets.  `queries` holds n rows of
+ * TLD_GEMM_PLAN_QUERY_INTS values --
+ *   0 M, 1 N, 2 K, 3 lda, 4 ldw, 5 ldo, 6 ldr, 7 epilogue, 8 f8, 9 conv, 10 cv_cin, 11 cv_up, 12 cv_down, 13 ksplit, 14 w_batch_rows,
+ *   15 / 16 / 17 whether bias / resid / c_f32 are present, 18 CU count of the device (> 0),
+ *   19 - 23 the switches TLD_F8_RING, TLD_GEMM_HALFTAIL, TLD_UPDW_SMALL, TLD_SPLITK_SMALL, TLD_DOWN_SMALL (1 = on, their default)
+ * -- and `plans` receives n rows of TLD_GEMM_PLAN_INTS values:
+ *   0 family (0 refused: nothing would be launched, 1 the 8-wave kernel, 2 / 3 / 4 the 4-wave small-batch forms of the fused up-projection, the split-K
+ *   slices and the residual-add down projection), 1 tile columns, 2 tile rows, 3 ring K loop, 4 xcd_ngroups, 5 half_tail, 6 workgroups, 7 threads per
+ *   workgroup, 8 reason of a refusal (1 conv with cv_up and cv_down, 2 no kernel is built for the combination). */
+#define TLD_GEMM_PLAN_QUERY_INTS 24
+#define TLD_GEMM_PLAN_INTS 9
+TLD_API int tld_debug_gemm_plan(const int32_t* queries, int32_t n, int32_t* plans);
+
 /* Live per-kernel-class timing with HIP events recorded on the launch stream around every launch
  * of the selected classes (bit k of class_mask).  Classes: 0 gemm_qkv, 1 gemm_up, 2 gemm_down,
  * 3 attention, 4 cross_row, 5 dwconv_gelu, 6 layernorm, 7 embed, 8 tail, 9 update, 10 conditioning.

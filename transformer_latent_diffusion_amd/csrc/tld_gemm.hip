@@ -21,10 +21,6 @@
 #define TLD_EPI_BIT(b) false
 #endif
 
-#ifndef TLD_KLOOP_RING
-#define TLD_KLOOP_RING 1      // counted-vmcnt half-tile ring K loop for 256 x 256 tiles (see kloop_ring); 0 = never instantiate it (the two-stage staggered loop everywhere)
-#endif
-
 namespace tld {
 
 namespace {
@@ -1534,140 +1530,96 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, int nblocks
     }
 }
 
-template <int BN>
-void launch256p(const GemmParams& p, int epilogue, hipStream_t s) {
+// Dynamic LDS of gemm256p_kernel<BN, EPI, F8>: the two stages, plus what the epilogue or the operand mode keeps behind them
+template <int BN, int EPI, bool F8>
+constexpr int main_lds_bytes() {
     using G = G256P<BN>;
-    const int ntn = (p.N + BN - 1) / BN, ntm = (p.M + G::BM - 1) / G::BM;
-    const int ncu = device_cu_count();
-    const int nsplit = (epilogue == EPI_F32 && !p.f8 && !p.conv && p.ksplit > 1) ? p.ksplit : 1;
-    const int nblocks = ntm * ntn * nsplit < ncu ? ntm * ntn * nsplit : ncu;
-    dim3 grid(nblocks), block(512);
-    // Up-projection (12 tile-columns at d = 768): two column groups x four tile-row blocks over the 8 XCDs keep each
-    // XCD's W working set at 2.4 MB (L2-resident across rounds; it was re-fetched every round, PMC fetch 296 MB vs
-    // 55 MB algorithmic) while A is fetched by two XCDs instead of one: 235 -> 228 us.  Measured and rejected:
-    // four groups for the up-projection (neutral), two / four groups for the down-projection (A is the 201 MB
-    // operand there: neutral / 175 -> 195 us).  Large launches only: every XCD cell needs workgroups of its own.
-    // half-tile ring K loop (256 x 256 tiles, bf16, no conv): an iteration is two K-tiles, so K must be a multiple of 128
-    const bool use_ring = nsplit > 1 ? false : p.conv ? (9 * (p.cv_cin >> 6)) % 2 == 0 : p.f8 ? (p.K >= 256 && p.K % 256 == 0)
-                                                                                        : (p.K >= 128 && p.K % 128 == 0);      // (an even number of 128-byte K-tiles; conv: K = 9 cv_cin)
-    (void)use_ring;
-    static const bool f8_ring = !(getenv("TLD_F8_RING") && atoi(getenv("TLD_F8_RING")) == 0);        // A/B hook: 0 = the two-stage loop under the fp8 GEMMs (round 2 - 5)
-    GemmParams pg = p;
-    static const bool half_tail = !(getenv("TLD_GEMM_HALFTAIL") && atoi(getenv("TLD_GEMM_HALFTAIL")) == 0);     // test hook: tests/test_gpu_parity.py holds the row-split tail bitwise equal to the unsplit run
-    pg.half_tail = half_tail ? 1 : 0;
-    if ((epilogue == EPI_UP_DWCONV2 || epilogue == EPI_UP_DWCONV32 || epilogue == EPI_BIAS_BF16) && ntn % 2 == 0 && ntm >= 8 && nblocks == ncu && ncu % 8 == 0)
-        pg.xcd_ngroups = 2;
-    // (EPI_QKV_ATTN, round 4: its PMC traffic is 2.6 x algorithmic -- an XCD's round of 32 items wants 2.7 samples' A tiles + all 12 heads' weights,
-    // 4.6 MB against 4 MB of L2 -- but two or four head groups over the XCDs left the kernel at 131.7 us: like the other GEMMs it is not fetch-bound)
-#define TLD_L256P_(E, F8) TLD_L256P__(E, F8, false)
-#define TLD_L256P_LAUNCH(E, F8, CV, RG)                                                               \
-    do {                                                                                              \
-        static PerDeviceOnce once;                                                                    \
-        once.run([&] { hipFuncSetAttribute(reinterpret_cast<const void*>(gemm256p_kernel<BN, E, F8, CV, RG>), \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds); });      \
-        hipLaunchKernelGGL((gemm256p_kernel<BN, E, F8, CV, RG>), grid, block, lds, s, pg, nblocks);   \
-    } while (0)
-#define TLD_L256P__(E, F8, CV)                                                                        \
-    do {                                                                                              \
-        constexpr int lds = (F8) ? G::LDS_BYTES + 4096                                                \
-                            : (((E) == EPI_UP_DWCONV2 || (E) == EPI_UP_DWCONV32) ? G::UPDW2_LDS                                   \
-                            : ((E) == EPI_QKV_ATTN ? G::ATTN_LDS                                      \
-                            : ((E) == EPI_QKV_LN ? G::QKVLN_LDS                                        \
-                            : ((E) == EPI_BIAS_BF16 && BN != 384 ? G::PLAINLN_LDS : G::LDS_BYTES))));  /* (384-wide: 160 KB of stages, no LayerNorm-3 fold) */ \
-        /* (fp8 + residual-add epilogue on the ring: 172 spilled registers, also with the lane-derived values re-materialised -- that one stays on the two-stage loop) */ \
-        constexpr bool ring_ok = TLD_KLOOP_RING && BN == 256 && !((F8) && ((CV) || (E) == EPI_BIAS_RESID)); \
-        if constexpr (ring_ok) {                                                                      \
-            if (use_ring && (!(F8) || f8_ring)) TLD_L256P_LAUNCH(E, F8, CV, true); else TLD_L256P_LAUNCH(E, F8, CV, false); \
-        } else {                                                                                      \
-            TLD_L256P_LAUNCH(E, F8, CV, false);                                                       \
-        }                                                                                             \
-    } while (0)
-#define TLD_L256P(E) TLD_L256P_(E, false)
-    if (p.conv) {           // implicit 3x3 convolution (VAE decoder): 256- or 128-wide tiles, three epilogues
-        if constexpr (BN == 256 || BN == 128) {
-            switch (epilogue) {
-                case EPI_F32: TLD_L256P__(EPI_F32, false, true); break;
-                case EPI_BIAS_BF16: TLD_L256P__(EPI_BIAS_BF16, false, true); break;
-                case EPI_BIAS_RESID: TLD_L256P__(EPI_BIAS_RESID, false, true); break;
-                default: break;
-            }
-        }
-    } else if (p.f8) {      // MX-fp8 operands: 256- or 128-wide tiles with four epilogues, 192-wide for the residual add
-        if constexpr (BN == 256 || BN == 128) {
-            switch (epilogue) {
-                case EPI_F32: TLD_L256P_(EPI_F32, true); break;
-                case EPI_QKV: TLD_L256P_(EPI_QKV, true); break;
-                case EPI_BIAS_BF16: TLD_L256P_(EPI_BIAS_BF16, true); break;
-                case EPI_BIAS_RESID: TLD_L256P_(EPI_BIAS_RESID, true); break;
-                default: break;
-            }
-        } else if constexpr (BN == 192) {
-            if (epilogue == EPI_BIAS_RESID) TLD_L256P_(EPI_BIAS_RESID, true);
-        }
-    } else if constexpr (BN == 384) {       // residual add (the down projection) and, for the training step's N = 768 linears, bias -> bf16
-        if (epilogue == EPI_BIAS_BF16) TLD_L256P(EPI_BIAS_BF16); else TLD_L256P(EPI_BIAS_RESID);
-    } else if constexpr (BN == 192) {
-        if (epilogue == EPI_QKV_ATTN) TLD_L256P(EPI_QKV_ATTN); else TLD_L256P(EPI_BIAS_RESID);
-    } else {
-        switch (epilogue) {
-            case EPI_F32: TLD_L256P(EPI_F32); break;
-            case EPI_QKV: TLD_L256P(EPI_QKV); break;
-            case EPI_QKV_LN: TLD_L256P(EPI_QKV_LN); break;
-            case EPI_BIAS_BF16: TLD_L256P(EPI_BIAS_BF16); break;
-            case EPI_BIAS_RESID: TLD_L256P(EPI_BIAS_RESID); break;
-            case EPI_UP_DWCONV2: if constexpr (BN == 256) { TLD_L256P(EPI_UP_DWCONV2); } break;
-            case EPI_UP_DWCONV32: if constexpr (BN == 256) { TLD_L256P(EPI_UP_DWCONV32); } break;
-            default: break;
-        }
+    if (F8) return G::LDS_BYTES + 4096;                                               // the scale strips of both stages
+    if (EPI == EPI_UP_DWCONV2 || EPI == EPI_UP_DWCONV32) return G::UPDW2_LDS;
+    if (EPI == EPI_QKV_ATTN) return G::ATTN_LDS;
+    if (EPI == EPI_QKV_LN) return G::QKVLN_LDS;
+    if (EPI == EPI_BIAS_BF16 && BN != 384) return G::PLAINLN_LDS;                      // (384-wide: 160 KB of stages, no LayerNorm-3 fold)
+    return G::LDS_BYTES;
+}
+
+template <int BN, int EPI, bool F8, bool CV, bool RG>
+void launch_main_kernel(const GemmParams& pg, const GemmPlan& plan, hipStream_t s) {
+    constexpr int lds = main_lds_bytes<BN, EPI, F8>();
+    static PerDeviceOnce once;
+    once.run([&] { hipFuncSetAttribute(reinterpret_cast<const void*>(gemm256p_kernel<BN, EPI, F8, CV, RG>), hipFuncAttributeMaxDynamicSharedMemorySize, lds); });
+    hipLaunchKernelGGL((gemm256p_kernel<BN, EPI, F8, CV, RG>), dim3(plan.nblocks), dim3(plan.block), lds, s, pg, plan.nblocks);
+}
+
+// one instantiation of the 8-wave kernel on the K loop the plan names
+template <int BN, int EPI, bool F8, bool CV>
+void launch_main(const GemmParams& pg, const GemmPlan& plan, hipStream_t s) {
+    static_assert(gemm_main_instantiated(BN, EPI, F8, CV), "plan_gemm does not know this instantiation (tld_gemm_plan.h)");
+    if constexpr (gemm_ring_instantiated(BN, EPI, F8, CV)) {
+        if (plan.ring) return launch_main_kernel<BN, EPI, F8, CV, true>(pg, plan, s);
     }
-#undef TLD_L256P__
-#undef TLD_L256P_LAUNCH
-#undef TLD_L256P_
-#undef TLD_L256P
+    launch_main_kernel<BN, EPI, F8, CV, false>(pg, plan, s);
+}
+
+constexpr int main_key(int bn, int epilogue, bool f8, bool conv) { return bn * 64 + epilogue * 4 + (f8 ? 2 : 0) + (conv ? 1 : 0); }
+
+// From a GEMM_MAIN plan to its instantiation: one case per combination gemm_main_instantiated accepts, <bn, epilogue, f8, conv>.  false: no such case (nothing launched).
+// (The compiler emits the kernels in the order of the cases, and the scalar code of one of them was seen to change with that order: new cases go at the end.)
+bool dispatch_main(const GemmParams& pg, int epilogue, const GemmPlan& plan, hipStream_t s) {
+    switch (main_key(plan.bn, epilogue, pg.f8 != 0, pg.conv != 0)) {
+        // 256 x 384 tiles
+        case main_key(384, EPI_BIAS_BF16, false, false): launch_main<384, EPI_BIAS_BF16, false, false>(pg, plan, s); return true;
+        case main_key(384, EPI_BIAS_RESID, false, false): launch_main<384, EPI_BIAS_RESID, false, false>(pg, plan, s); return true;
+        // 256 x 192
+        case main_key(192, EPI_BIAS_RESID, true, false): launch_main<192, EPI_BIAS_RESID, true, false>(pg, plan, s); return true;
+        case main_key(192, EPI_QKV_ATTN, false, false): launch_main<192, EPI_QKV_ATTN, false, false>(pg, plan, s); return true;
+        case main_key(192, EPI_BIAS_RESID, false, false): launch_main<192, EPI_BIAS_RESID, false, false>(pg, plan, s); return true;
+        // 256 x 128: implicit 3x3 convolution, MX-fp8 operands, bf16 operands
+        case main_key(128, EPI_F32, false, true): launch_main<128, EPI_F32, false, true>(pg, plan, s); return true;
+        case main_key(128, EPI_BIAS_BF16, false, true): launch_main<128, EPI_BIAS_BF16, false, true>(pg, plan, s); return true;
+        case main_key(128, EPI_BIAS_RESID, false, true): launch_main<128, EPI_BIAS_RESID, false, true>(pg, plan, s); return true;
+        case main_key(128, EPI_F32, true, false): launch_main<128, EPI_F32, true, false>(pg, plan, s); return true;
+        case main_key(128, EPI_QKV, true, false): launch_main<128, EPI_QKV, true, false>(pg, plan, s); return true;
+        case main_key(128, EPI_BIAS_BF16, true, false): launch_main<128, EPI_BIAS_BF16, true, false>(pg, plan, s); return true;
+        case main_key(128, EPI_BIAS_RESID, true, false): launch_main<128, EPI_BIAS_RESID, true, false>(pg, plan, s); return true;
+        case main_key(128, EPI_F32, false, false): launch_main<128, EPI_F32, false, false>(pg, plan, s); return true;
+        case main_key(128, EPI_QKV, false, false): launch_main<128, EPI_QKV, false, false>(pg, plan, s); return true;
+        case main_key(128, EPI_QKV_LN, false, false): launch_main<128, EPI_QKV_LN, false, false>(pg, plan, s); return true;
+        case main_key(128, EPI_BIAS_BF16, false, false): launch_main<128, EPI_BIAS_BF16, false, false>(pg, plan, s); return true;
+        case main_key(128, EPI_BIAS_RESID, false, false): launch_main<128, EPI_BIAS_RESID, false, false>(pg, plan, s); return true;
+        // 256 x 256, each also on the ring K loop (but fp8 + residual add)
+        case main_key(256, EPI_F32, false, true): launch_main<256, EPI_F32, false, true>(pg, plan, s); return true;
+        case main_key(256, EPI_BIAS_BF16, false, true): launch_main<256, EPI_BIAS_BF16, false, true>(pg, plan, s); return true;
+        case main_key(256, EPI_BIAS_RESID, false, true): launch_main<256, EPI_BIAS_RESID, false, true>(pg, plan, s); return true;
+        case main_key(256, EPI_F32, true, false): launch_main<256, EPI_F32, true, false>(pg, plan, s); return true;
+        case main_key(256, EPI_QKV, true, false): launch_main<256, EPI_QKV, true, false>(pg, plan, s); return true;
+        case main_key(256, EPI_BIAS_BF16, true, false): launch_main<256, EPI_BIAS_BF16, true, false>(pg, plan, s); return true;
+        case main_key(256, EPI_BIAS_RESID, true, false): launch_main<256, EPI_BIAS_RESID, true, false>(pg, plan, s); return true;
+        case main_key(256, EPI_F32, false, false): launch_main<256, EPI_F32, false, false>(pg, plan, s); return true;
+        case main_key(256, EPI_QKV, false, false): launch_main<256, EPI_QKV, false, false>(pg, plan, s); return true;
+        case main_key(256, EPI_QKV_LN, false, false): launch_main<256, EPI_QKV_LN, false, false>(pg, plan, s); return true;
+        case main_key(256, EPI_BIAS_BF16, false, false): launch_main<256, EPI_BIAS_BF16, false, false>(pg, plan, s); return true;
+        case main_key(256, EPI_BIAS_RESID, false, false): launch_main<256, EPI_BIAS_RESID, false, false>(pg, plan, s); return true;
+        case main_key(256, EPI_UP_DWCONV2, false, false): launch_main<256, EPI_UP_DWCONV2, false, false>(pg, plan, s); return true;
+        case main_key(256, EPI_UP_DWCONV32, false, false): launch_main<256, EPI_UP_DWCONV32, false, false>(pg, plan, s); return true;
+        default: return false;
+    }
 }
 
 }  // namespace
 
-namespace {
-// BN = 256 unless that leaves the last round of workgroups mostly empty on 256 CUs; then prefer the widest
-// tile whose workgroup count is a whole number of rounds (192 for the residual epilogue), else 128.
-int choose_bn(long M, long N, int epilogue, long K) {
-    const long ntm = (M + 255) / 256;
-    const long blocks256 = ntm * ((N + 255) / 256);
-    // (a last round that is at least 85 % full counts as whole: 252 tiles on 256 CUs are not a reason to halve the tile)
-    const long rounds256 = (blocks256 + 255) / 256;
-    bool narrow = (N % 256 != 0) || (blocks256 * 100 < rounds256 * 256 * 85 && blocks256 < 3 * 256);
-    // Round 6: a partly filled last round is cheap where the half-tile tail applies (gemm256p_kernel, HT_OK epilogues on the ring K loop): when the R
-    // left-over tiles of an XCD's 32 workgroups satisfy 2 R <= 32, two workgroups share each of them and the launch costs q + ~0.6 tile times instead of q + 1.
-    // 256-wide tiles then beat twice as many 128-wide ones (C3's block-0 QKV projection, 16 384 rows x 2304: 576 tiles = 2.25 rounds; 84 us as 1152 tiles of 128).
-    // Results do not depend on the tile width (every output element sees the same K order), so the choice may follow the batch size.
-    if (narrow && N % 256 == 0 && K >= 128 && K % 128 == 0 && (epilogue == EPI_F32 || epilogue == EPI_QKV || epilogue == EPI_QKV_LN || epilogue == EPI_BIAS_BF16) && blocks256 >= 256) {
-        const long per_xcd = blocks256 / 8, R = per_xcd % 32;
-        if (blocks256 % 8 == 0 && R > 0 && 2 * R <= 32) narrow = false;
-    }
-    int bn = narrow ? 128 : 256;
-    if (narrow && epilogue == EPI_BIAS_RESID && N % 192 == 0 && (ntm * (N / 192)) % 256 == 0) bn = 192;
-    // down projection at the bench size: 256 x 384 tiles make N = 768 ONE round of 256 workgroups (176 -> 155 us);
-    // any other batch size of that width uses 192-wide tiles, never 128 / 256: both 192 and 384 give 96-column wave
-    // tiles, which is what the LayerNorm-1 partial sums are defined on (results must not depend on the batch size)
-    if (epilogue == EPI_BIAS_RESID && N % 192 == 0) bn = 192;
-    if (epilogue == EPI_BIAS_RESID && N % 384 == 0 && (ntm * (N / 384)) % 256 == 0) bn = 384;
-    if (epilogue == EPI_UP_DWCONV2 || epilogue == EPI_UP_DWCONV32) bn = 256;          // caller guarantees N % 256 == 0 and one 16x16 image per 256 rows
-    if (epilogue == EPI_QKV_ATTN) return 192;       // one tile = one (sample, head): caller guarantees N = heads x 192, ntok == 256
-    if (bn == 192 && (epilogue != EPI_BIAS_RESID || N % 192)) bn = 128;
-    // N = 768 with the plain bias epilogue (the training step's five per layer): one round of 256 x 384 tiles at the training batch instead of
-    // three rounds of 256 x 128 (0.71 -> 1.0 PFLOP/s)
-    // (K >= 384: the shapes it was built and tested for.  The VAE's attention projection at 128 channels and 65 536 tokens -- N = 384, K = 128,
-    // 256 tile-rows -- met the other conditions and came out wrong in every row; it now takes the 128-wide tiles like every other K = 128 launch.)
-    if (epilogue == EPI_BIAS_BF16 && N % 384 == 0 && N < 1536 && K >= 384 && (ntm * (N / 384)) % 256 == 0) bn = 384;      // (callers with a LayerNorm-3 fold have N = 4 d >= 1536)
-    if (bn == 384 && ((epilogue != EPI_BIAS_RESID && epilogue != EPI_BIAS_BF16) || N % 384)) bn = 128;
-    if (bn != 256 && bn != 192 && bn != 384) bn = 128;
-    return bn;
-}
-}  // namespace
-
-int gemm_resid_stat_slots(int N) {
-    return (N % 192 == 0 && N / 96 <= kLnSlots) ? N / 96 : 0;
+// The five switches of GemmSwitches, read from the environment once per process
+static const GemmSwitches& gemm_switches() {
+    static const GemmSwitches sw = [] {
+        auto on = [](const char* name) { const char* v = getenv(name); return !(v && atoi(v) == 0); };
+        GemmSwitches g;
+        g.f8_ring = on("TLD_F8_RING");
+        g.half_tail = on("TLD_GEMM_HALFTAIL");
+        g.updw_small = on("TLD_UPDW_SMALL");
+        g.splitk_small = on("TLD_SPLITK_SMALL");
+        g.down_small = on("TLD_DOWN_SMALL");
+        return g;
+    }();
+    return sw;
 }
 
 // The DMA of a plain (non-conv, non-TN) launch forms each operand row's address as a uniform 64-bit base plus a 32-bit
@@ -1696,52 +1648,23 @@ int launch_gemm(const GemmParams& p_in, int epilogue, hipStream_t s) {
 #else
     const GemmParams& p = p_in;
 #endif
-    if (epilogue == EPI_UP_DWCONV2) {
-        // small batches (one to five images per call): one 256 x 128 tile per workgroup on twice as many CUs finishes sooner than one 256 x 256 tile (17.7 vs 28.6 us at one
-        // image); results are bitwise those of the 8-wave kernel (tld_updw.hip), so the choice may follow the batch size.  TLD_UPDW_SMALL=0: A/B and test hook.
-        static const bool small_on = !(getenv("TLD_UPDW_SMALL") && atoi(getenv("TLD_UPDW_SMALL")) == 0);
-        if (small_on && updw_pp_supported(p) && (long)(p.M / 256) * (p.N / 128) <= device_cu_count()) { launch_updw_pp(p, s); return TLD_OK; }
+    const GemmPlan plan = plan_gemm(p, epilogue, device_cu_count(), gemm_switches());
+    switch (plan.family) {
+        case GEMM_UPDW_PP: launch_updw_pp(p, plan, s); return TLD_OK;
+        case GEMM_SPLITK_PP: launch_splitk_pp(p, plan, s); return TLD_OK;
+        case GEMM_DOWN_PP: launch_down_pp(p, plan, s); return TLD_OK;
+        case GEMM_MAIN: {
+            GemmParams pg = p;
+            pg.half_tail = plan.half_tail;
+            pg.xcd_ngroups = plan.xcd_ngroups;
+            if (dispatch_main(pg, epilogue, plan, s)) return TLD_OK;
+            set_last_error(gemm_refusal_text(GEMM_REFUSED_NO_KERNEL));
+            return TLD_ERR_INVALID;
+        }
+        default:
+            set_last_error(gemm_refusal_text(plan.refusal));
+            return TLD_ERR_INVALID;
     }
-    if (epilogue == EPI_F32 && p.ksplit > 1 && !p.f8 && !p.conv) {
-        // the low-latency classes' split-K down projection: one 256 x 128 x (K / splits) item per 4-wave workgroup while the launch has at most two items per CU
-        // (tld_updw.hip; the slices are bitwise those of the 8-wave two-stage kernel below).  TLD_SPLITK_SMALL=0: A/B and test hook.
-        static const bool sk_on = !(getenv("TLD_SPLITK_SMALL") && atoi(getenv("TLD_SPLITK_SMALL")) == 0);
-        // (two such workgroups fit a CU and, K loops only, share it well: eight images in class 1 -- 384 items -- 58.3 -> 48.8 ms per generate; the fused up-projection's epilogue does
-        // not: 288 - 480 tiles on two workgroups per CU measured 1 - 2 ms slower than the 8-wave kernel, hence one tile per CU there)
-        if (sk_on && splitk_pp_supported(p) && (long)(p.M / 256) * (p.N / 128) * p.ksplit <= 2L * device_cu_count()) { launch_splitk_pp(p, s); return TLD_OK; }
-    }
-    if (epilogue == EPI_BIAS_RESID && !p.f8 && !p.conv) {
-        // the default class's down projection at small batch: 64 x 192 or 128 x 192 tiles on 4-wave workgroups while the launch has at most one tile per CU (tld_updw.hip; bitwise the
-        // 8-wave 192- / 384-wide kernels below).  TLD_DOWN_SMALL=0: A/B and test hook.
-        static const bool dn_on = !(getenv("TLD_DOWN_SMALL") && atoi(getenv("TLD_DOWN_SMALL")) == 0);
-        if (dn_on && down_pp_supported(p) && down_pp_fits(p)) { launch_down_pp(p, s); return TLD_OK; }
-    }
-    if (p.conv && p.cv_up && p.cv_down) {     // upsampling and stride 2 are exclusive addressing modes: launch nothing, report it to the caller
-        set_last_error("launch_gemm: conv with both cv_up and cv_down set");
-        return TLD_ERR_INVALID;
-    }
-    int bn = choose_bn(p.M, p.N, epilogue, p.K);
-    if (p.conv) {           // 256-wide tiles when the width allows and they fill the chip, else 128
-        const long ntm = (p.M + 255) / 256;
-        bn = (p.N % 256 == 0 && ntm * (p.N / 256) >= 192) ? 256 : 128;
-    }
-    if (p.f8) {             // the fp8 kernel is instantiated for 256 / 128 (all epilogues) and 192 (residual add: N = 768 in whole rounds)
-        const long ntm = (p.M + 255) / 256;
-        // (round 6: where 256-wide tiles fill whole rounds they beat the 192-wide ones -- the down projection at C4, 65 536 rows: 768 tiles in 3 rounds against 1024 in 4,
-        // 207.7 -> 174.8 us same-box; results do not depend on the tile width, the LayerNorm-1 partial sums are not taken in fp8 mode)
-        if (epilogue == EPI_BIAS_RESID && p.N % 256 == 0 && (ntm * (p.N / 256)) % 256 == 0) bn = 256;
-        else if (epilogue == EPI_BIAS_RESID && p.N % 192 == 0 && ((ntm * (p.N / 192)) % 256 == 0 || p.N % 256 != 0)) bn = 192;
-        else bn = (p.N % 256 == 0) ? 256 : 128;
-    }
-    if (epilogue == EPI_F32 && p.ksplit > 1 && !p.f8 && !p.conv) bn = 128;     // split-K: the narrow tile has no ring instantiation to fall into and gives the most work items
-    // (A column-split QKV launch -- 8 tile-columns of 256 as 4 whole rounds + the 9th as 128-wide tiles -- was
-    // measured: 109.8 + 27.8 us vs 134 us for the single 4.5-round launch; a one-round launch pays ~12 us of
-    // ramp/drain, so the half-empty fifth round is the cheaper tail.)
-    if (bn == 384) launch256p<384>(p, epilogue, s);
-    else if (bn == 192) launch256p<192>(p, epilogue, s);
-    else if (bn == 128) launch256p<128>(p, epilogue, s);
-    else launch256p<256>(p, epilogue, s);
-    return TLD_OK;
 }
 
 void launch_gemm_tn(const GemmParams& p, hipStream_t s) {
@@ -1756,3 +1679,26 @@ void launch_gemm_tn(const GemmParams& p, hipStream_t s) {
 }
 
 }  // namespace tld
+
+// Test hook (include/tld_hip.h): the plan of each query row, no device involved
+extern "C" TLD_API int tld_debug_gemm_plan(const int32_t* queries, int32_t n, int32_t* plans) {
+    if (!queries || !plans || n < 0) { tld::set_last_error("tld_debug_gemm_plan: null argument"); return TLD_ERR_INVALID; }
+    float f32_present = 0.0f;          // selection only asks whether bias / resid / c_f32 are there
+    tld::resid_t resid_present{};
+    for (int32_t i = 0; i < n; ++i) {
+        const int32_t* q = queries + (size_t)i * TLD_GEMM_PLAN_QUERY_INTS;
+        if (q[18] < 1) { tld::set_last_error("tld_debug_gemm_plan: the CU count must be positive"); return TLD_ERR_INVALID; }
+        tld::GemmParams p{};
+        p.M = q[0]; p.N = q[1]; p.K = q[2]; p.lda = q[3]; p.ldw = q[4]; p.ldo = q[5]; p.ldr = q[6];
+        p.f8 = q[8]; p.conv = q[9]; p.cv_cin = q[10]; p.cv_up = q[11]; p.cv_down = q[12]; p.ksplit = q[13]; p.w_batch_rows = q[14];
+        p.bias = q[15] ? &f32_present : nullptr;
+        p.resid = q[16] ? &resid_present : nullptr;
+        p.c_f32 = q[17] ? &f32_present : nullptr;
+        tld::GemmSwitches sw;
+        sw.f8_ring = q[19] != 0; sw.half_tail = q[20] != 0; sw.updw_small = q[21] != 0; sw.splitk_small = q[22] != 0; sw.down_small = q[23] != 0;
+        const tld::GemmPlan g = tld::plan_gemm(p, q[7], q[18], sw);
+        int32_t* o = plans + (size_t)i * TLD_GEMM_PLAN_INTS;
+        o[0] = g.family; o[1] = g.bn; o[2] = g.bm; o[3] = g.ring; o[4] = g.xcd_ngroups; o[5] = g.half_tail; o[6] = g.nblocks; o[7] = g.block; o[8] = g.refusal;
+    }
+    return TLD_OK;
+}

@@ -640,64 +640,31 @@ __global__ __launch_bounds__(256, 2) void down_pp_kernel(GemmParams p, int nbloc
 
 }  // namespace
 
-bool updw_pp_supported(const GemmParams& p) {
-    return !p.f8 && !p.conv && !p.w_batch_rows && p.M % 256 == 0 && p.N % 128 == 0 && p.K % 128 == 0 && p.K >= 256 && p.ldo % 4 == 0 &&
-           (size_t)p.M * p.lda * 2 < ((size_t)1 << 32) && (size_t)p.N * p.ldw * 2 < ((size_t)1 << 32) && (unsigned)p.lda * 2u < (1u << 24) && (unsigned)p.ldw * 2u < (1u << 24);
-}
-
-void launch_updw_pp(const GemmParams& p, hipStream_t s) {
+// Which launches come here, and with which grid, is plan_gemm's decision (tld_gemm_plan.h); its *_pp_supported predicates state the shapes these kernels are written for.
+void launch_updw_pp(const GemmParams& p, const GemmPlan& plan, hipStream_t s) {
     static PerDeviceOnce once;
     once.run([&] { hipFuncSetAttribute(reinterpret_cast<const void*>(updw_pp_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, PP::LDS); });
-    const int ntn = p.N / 128, ntm = p.M / 256;
-    const int ncu = device_cu_count();
-    const int ntiles = ntm * ntn;
-    const int nblocks = ntiles < 2 * ncu ? ntiles : 2 * ncu;           // (two workgroups fit a CU; launch_gemm only comes here with ntiles <= ncu)
     GemmParams pg = p;
-    pg.xcd_ngroups = (ntn % 2 == 0 && ntm >= 8 && nblocks == 2 * ncu && ncu % 8 == 0) ? 2 : 0;
-    hipLaunchKernelGGL(updw_pp_kernel<0>, dim3(nblocks), dim3(256), PP::LDS, s, pg, nblocks);
+    pg.xcd_ngroups = plan.xcd_ngroups;
+    hipLaunchKernelGGL(updw_pp_kernel<0>, dim3(plan.nblocks), dim3(plan.block), PP::LDS, s, pg, plan.nblocks);
 }
 
-// EPI_F32 with ksplit > 1 (the low-latency classes' down projection) on the same 4-wave K loop: K = the length of ONE split (a multiple of 128, >= 256)
-bool splitk_pp_supported(const GemmParams& p) {
-    return p.ksplit > 1 && p.c_f32 != nullptr && updw_pp_supported(p);
-}
-
-void launch_splitk_pp(const GemmParams& p, hipStream_t s) {
+void launch_splitk_pp(const GemmParams& p, const GemmPlan& plan, hipStream_t s) {
     static PerDeviceOnce once;
     once.run([&] { hipFuncSetAttribute(reinterpret_cast<const void*>(updw_pp_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, PP::RING_BYTES); });
-    const int ntiles = (p.N / 128) * (p.M / 256) * p.ksplit;
-    const int ncu = device_cu_count();
-    const int nblocks = ntiles < 2 * ncu ? ntiles : 2 * ncu;
     GemmParams pg = p;
-    pg.xcd_ngroups = 0;
-    hipLaunchKernelGGL(updw_pp_kernel<1>, dim3(nblocks), dim3(256), PP::RING_BYTES, s, pg, nblocks);
+    pg.xcd_ngroups = plan.xcd_ngroups;
+    hipLaunchKernelGGL(updw_pp_kernel<1>, dim3(plan.nblocks), dim3(plan.block), PP::RING_BYTES, s, pg, plan.nblocks);
 }
 
-// EPI_BIAS_RESID of the default class (bf16 operands, no conv) on 64 x 192 or 128 x 192 tiles: M % 64 == 0, N % 192 == 0, K % 64 == 0, K >= 192
-bool down_pp_supported(const GemmParams& p) {
-    return !p.f8 && !p.conv && !p.w_batch_rows && p.ksplit <= 1 && p.M % 64 == 0 && p.N % 192 == 0 && p.K % 64 == 0 && p.K >= 192 && p.ldr % 4 == 0 && p.bias && p.resid &&
-           (size_t)p.M * p.lda * 2 < ((size_t)1 << 32) && (size_t)p.N * p.ldw * 2 < ((size_t)1 << 32) && (unsigned)p.lda * 2u < (1u << 24) && (unsigned)p.ldw * 2u < (1u << 24);
-}
-
-// largest launch this form takes: one 128 x 192 tile per CU
-bool down_pp_fits(const GemmParams& p) {
-    const long ncu = device_cu_count();
-    return (long)(p.M / 64) * (p.N / 192) <= ncu || (p.M % 128 == 0 && (long)(p.M / 128) * (p.N / 192) <= ncu);
-}
-
-void launch_down_pp(const GemmParams& p, hipStream_t s) {
+void launch_down_pp(const GemmParams& p, const GemmPlan& plan, hipStream_t s) {
     static PerDeviceOnce once;
     once.run([&] {
         hipFuncSetAttribute(reinterpret_cast<const void*>(down_pp_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, DP::LDS);
         hipFuncSetAttribute(reinterpret_cast<const void*>(down_pp_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, DP::LDS);
     });
-    const int ncu = device_cu_count();
-    const int n64 = (p.M / 64) * (p.N / 192);
-    if (n64 <= ncu) hipLaunchKernelGGL(down_pp_kernel<1>, dim3(n64), dim3(256), DP::LDS, s, p, n64);       // 64-row tiles while they fit one per CU
-    else {
-        const int n128 = (p.M / 128) * (p.N / 192);
-        hipLaunchKernelGGL(down_pp_kernel<2>, dim3(n128 < ncu ? n128 : ncu), dim3(256), DP::LDS, s, p, n128 < ncu ? n128 : ncu);
-    }
+    if (plan.bm == 64) hipLaunchKernelGGL(down_pp_kernel<1>, dim3(plan.nblocks), dim3(plan.block), DP::LDS, s, p, plan.nblocks);
+    else hipLaunchKernelGGL(down_pp_kernel<2>, dim3(plan.nblocks), dim3(plan.block), DP::LDS, s, p, plan.nblocks);
 }
 
 }  // namespace tld
