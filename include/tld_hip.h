@@ -142,7 +142,34 @@ TLD_API int tld_debug_gemm_mx8(const void* a_e4m3, const void* a_scale, const vo
 TLD_API int tld_debug_gemm_bench(int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t ntok, int32_t iters,
                                  double* avg_ms);
 
-/* Test hook, host only (no GPU needed): which kernel, tile, K loop and grid a GEMM launch of the engine gets.  `queries` holds n rows of
+/* Test hook: ONE launch of the engine's GEMM with any of its non-conv epilogues on the caller's device buffers (tests/test_gpu_gemm_epilogues.py
+ * holds every kernel class against float64).  The fields are GemmParams' (csrc/tld_gemm_params.h); unused ones stay 0 / NULL.
+ *   epilogue 0: c_f32 [M][ldc] = A W^T.   2: out_bf16 [M][ldo] = bf16(A W^T + bias); with row_stats ([M] float2 (mean, rstd)) and ln_c1 [N] the folded
+ *   LayerNorm-3, bf16(rstd_m (acc - mean_m c1[n]) + bias[n]).   3: resid [M][ldr] (bf16) += A W^T + bias, and with stats_out ([M][8] float2) the (sum, sum of
+ *   squares) of the stored values per 96-column slot.   1: q | k -> out_bf16 [M][ldo >= 2 d], v -> vt [M / ntok][d][ntok].   5: epilogue 1 with LayerNorm-1
+ *   folded in: ln_stats [M][8] float2 partial sums of the A rows, ln_slots of them summed, rstd_m (acc - mean_m ln_c1[n]) + ln_b1[n], mean over K.
+ *   f8 != 0: A / W are e4m3 bytes with a_scale / w_scale as tld_debug_quant_mx8 lays them out (epilogues 0 - 3).
+ *   w_batch_rows != 0 (epilogues 0 and 2, bf16): rows [g w_batch_rows, (g + 1) w_batch_rows) multiply the W matrix at byte offset g w_batch_stride_bytes.
+ * Everything the kernels assume silently is checked first and refused with TLD_ERR_INVALID and the reason in tld_last_error(): operands the epilogue needs,
+ * K % 64 (fp8: K % 128, M % 4, N % 4), 16-byte rows and pointers, N % 8 for the bf16-storing epilogues (N % 4 for the residual add), pitches, the QKV
+ * geometry (N = 3 d, d % 64, ntok % 8, M % ntok), ln_slots even in 2 .. 8, an even M under row_stats, row_stats only without fp8 and where no 384-wide
+ * tile can be chosen, stats_out only at the widths that have slots (N % 192 == 0, N <= 768, bf16).  Convolution mode, the fused depthwise epilogues
+ * (4, 6) and fused attention (7) are refused: their layouts are engine-internal. */
+typedef struct tld_gemm_epilogue_args {
+    const void* A; const void* W;                    /* bf16 [M][lda] / [N][ldw], K contiguous (fp8: bytes) */
+    const void* a_scale; const void* w_scale;        /* fp8: E8M0 block scales [K / 128][rows][4] */
+    const float* bias;                               /* [N] */
+    void* out_bf16; void* vt; void* resid;
+    void* stats_out; const void* ln_stats; const float* ln_c1; const float* ln_b1; const void* row_stats;
+    float* c_f32;
+    int32_t M, N, K, lda, ldw;
+    int32_t epilogue, f8;
+    int32_t ldo, ntok, d, ldr, ln_slots, ldc;
+    int32_t w_batch_rows; uint32_t w_batch_stride_bytes;
+} tld_gemm_epilogue_args;
+TLD_API int tld_debug_gemm_epilogue(const tld_gemm_epilogue_args* args, void* hip_stream);
+
+/* Test hook, host only (no GPU needed): which kernel, tile, K loop and grid a GEMM launch of the engine gets. `queries` holds n rows of
  * TLD_GEMM_PLAN_QUERY_INTS values --
  *   0 M, 1 N, 2 K, 3 lda, 4 ldw, 5 ldo, 6 ldr, 7 epilogue, 8 f8, 9 conv, 10 cv_cin, 11 cv_up, 12 cv_down, 13 ksplit, 14 w_batch_rows,
  *   15 / 16 / 17 whether bias / resid / c_f32 are present, 18 CU count of the device (> 0),

@@ -21,7 +21,7 @@ KERNEL_CLASSES = ("gemm_qkv", "gemm_up", "gemm_down", "attention", "cross_row", 
 ABI_SYMBOLS = (
     "tld_engine_create", "tld_engine_load_tensor", "tld_engine_finalize_weights", "tld_denoiser_forward",
     "tld_sample", "tld_engine_set_gemm_dtype", "tld_engine_set_low_latency", "tld_debug_gemm_splitk", "tld_debug_quant_mx8", "tld_debug_quant_mx8_host", "tld_debug_gemm_mx8",
-    "tld_engine_set_debug", "tld_engine_read_stage", "tld_debug_gemm_bf16", "tld_debug_gemm_bench", "tld_debug_gemm_plan",
+    "tld_engine_set_debug", "tld_engine_read_stage", "tld_debug_gemm_bf16", "tld_debug_gemm_bench", "tld_debug_gemm_plan", "tld_debug_gemm_epilogue",
     "tld_engine_set_profile", "tld_engine_profile_reserve", "tld_engine_get_profile", "tld_engine_weight_bytes", "tld_engine_destroy",
     "tld_vae_create", "tld_vae_load_tensor", "tld_vae_finalize_weights", "tld_vae_decode", "tld_vae_set_debug",
     "tld_vae_read_stage", "tld_vae_set_profile", "tld_vae_get_profile", "tld_debug_conv3x3", "tld_vae_weight_bytes",
@@ -68,6 +68,14 @@ class TldClipConfig(C.Structure):
                                          "device_id")]
 
 
+class TldGemmEpilogueArgs(C.Structure):
+    """tld_gemm_epilogue_args (include/tld_hip.h): one GEMM launch with any non-conv epilogue, for tld_debug_gemm_epilogue."""
+    _fields_ = ([(n, C.c_void_p) for n in ("A", "W", "a_scale", "w_scale", "bias", "out_bf16", "vt", "resid", "stats_out", "ln_stats", "ln_c1", "ln_b1",
+                                           "row_stats", "c_f32")] +
+                [(n, C.c_int32) for n in ("M", "N", "K", "lda", "ldw", "epilogue", "f8", "ldo", "ntok", "d", "ldr", "ln_slots", "ldc", "w_batch_rows")] +
+                [("w_batch_stride_bytes", C.c_uint32)])
+
+
 _lib = None
 
 
@@ -111,6 +119,8 @@ def lib() -> C.CDLL:
     L.tld_debug_gemm_bench.argtypes = [i32, i32, i32, i32, i32, i32, C.POINTER(C.c_double)]
     if hasattr(L, "tld_debug_gemm_plan"):            # (absent from A/B builds that predate it)
         L.tld_debug_gemm_plan.argtypes = [vp, i32, vp]
+    if hasattr(L, "tld_debug_gemm_epilogue"):
+        L.tld_debug_gemm_epilogue.argtypes = [C.POINTER(TldGemmEpilogueArgs), vp]
     L.tld_engine_set_profile.argtypes = [vp, C.c_uint32]
     L.tld_engine_profile_reserve.argtypes = [vp, i32, C.c_int64]
     L.tld_engine_get_profile.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]

@@ -1102,6 +1102,79 @@ int tld_debug_gemm_mx8(const void* a_e4m3, const void* a_scale, const void* w_e4
     return TLD_OK;
 }
 
+// One launch_gemm call on the caller's buffers, any non-conv epilogue: what the kernels assume silently is checked here, nothing else is added.
+int tld_debug_gemm_epilogue(const tld_gemm_epilogue_args* a, void* hip_stream) {
+    if (!a) return fail(TLD_ERR_INVALID, "tld_debug_gemm_epilogue: null argument");
+    auto bad = [](const char* why) { return fail(TLD_ERR_INVALID, "tld_debug_gemm_epilogue: %s", why); };
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    const int epi = a->epilogue;
+    const bool f8 = a->f8 != 0;
+    if (epi != EPI_F32 && epi != EPI_QKV && epi != EPI_BIAS_BF16 && epi != EPI_BIAS_RESID && epi != EPI_QKV_LN)
+        return bad("epilogue must be 0 (fp32), 1 (QKV), 2 (bias -> bf16), 3 (bias + residual add) or 5 (QKV with LayerNorm-1); the fused depthwise and attention "
+                   "epilogues and convolution mode have engine-internal layouts and tests of their own");
+    if (f8 && epi == EPI_QKV_LN) return bad("the LayerNorm-1 fold has no fp8 form");
+    if (!a->A || !a->W || a->M <= 0 || a->N <= 0 || a->K <= 0) return bad("A, W and positive M, N, K are needed");
+    // operands: 128-byte K-steps, rows fetched in 16-byte pieces
+    const int esz = f8 ? 1 : 2;
+    if (a->K % (f8 ? 128 : 64)) return bad("K must be a multiple of 64 (fp8: 128)");
+    if (a->lda < a->K || a->ldw < a->K || (a->lda * esz) % 16 || (a->ldw * esz) % 16 || !al16(a->A) || !al16(a->W))
+        return bad("lda, ldw >= K, operand rows and pointers 16-byte aligned");
+    if (f8 && (!a->a_scale || !a->w_scale || a->M % 4 || a->N % 4 || !al16(a->a_scale) || !al16(a->w_scale)))
+        return bad("fp8 operands need both scale arrays (16-byte aligned), M % 4 == 0 and N % 4 == 0");
+    if (a->w_batch_rows) {
+        if (f8 || (epi != EPI_F32 && epi != EPI_BIAS_BF16) || a->w_batch_rows < 0 || a->w_batch_rows % 256 || a->w_batch_stride_bytes % 16)
+            return bad("w_batch_rows: bf16 operands, epilogues 0 and 2 only, a multiple of 256 rows, a 16-byte aligned stride");
+    }
+    if (epi == EPI_F32) {
+        if (!a->c_f32 || a->ldc < a->N) return bad("epilogue 0 needs c_f32 and ldc >= N");
+    } else if (epi == EPI_BIAS_RESID) {
+        // float4 of bias and four residual values (8 bytes) per lane, the column predicate on the first of the four
+        if (!a->bias || !a->resid || !al16(a->bias) || (reinterpret_cast<uintptr_t>(a->resid) & 7)) return bad("epilogue 3 needs bias (16-byte aligned) and resid (8-byte aligned)");
+        if (a->N % 4 || a->ldr % 4 || a->ldr < a->N) return bad("epilogue 3 needs N % 4 == 0, ldr % 4 == 0 and ldr >= N");
+        // partial sums are taken by the 96-column wave tiles only (192- / 384-wide tiles, the 4-wave form); any other launch would leave stats_out unwritten
+        if (a->stats_out && (f8 || gemm_resid_stat_slots(a->N) == 0)) return bad("stats_out: bf16 operands and N % 192 == 0, N <= 768 only (one slot per 96 columns, at most 8)");
+        if (a->stats_out && (reinterpret_cast<uintptr_t>(a->stats_out) & 7)) return bad("stats_out must be 8-byte aligned");
+    } else {
+        // bf16-storing epilogues: 16-byte groups of 8 columns, the column predicate on the first; bias / c1 / b1 as float4
+        if (!a->out_bf16 || !al16(a->out_bf16) || a->N % 8 || a->ldo % 8) return bad("epilogues 1, 2, 5 need out_bf16 (16-byte aligned), N % 8 == 0 and ldo % 8 == 0");
+        if (epi == EPI_BIAS_BF16) {
+            if (!a->bias || !al16(a->bias) || a->ldo < a->N) return bad("epilogue 2 needs bias (16-byte aligned) and ldo >= N");
+            if (a->row_stats) {
+                if (!a->ln_c1 || !al16(a->ln_c1) || !al16(a->row_stats)) return bad("row_stats needs ln_c1, both 16-byte aligned");
+                if (f8) return bad("row_stats: the LayerNorm-3 fold has no fp8 form");
+                if (a->M % 2) return bad("row_stats: M must be even (the statistics are fetched two rows at a time)");
+                if (a->N % 384 == 0 && a->N < 1536) return bad("row_stats: the 384-wide tile, which N % 384 == 0 below 1536 may get, has no LayerNorm-3 fold");
+            }
+        } else {
+            // one tile is q | k or v, never both: 2 d is a multiple of the tile width (256-wide tiles need N % 256 == 0, and then 2 d % 256 == 0 follows from
+            // d % 64 == 0); a V^T store is 8 tokens of one sample
+            if (!a->vt || !al16(a->vt) || a->d <= 0 || a->d % 64 || a->N != 3 * a->d) return bad("QKV epilogues need vt (16-byte aligned), d % 64 == 0 and N = 3 d");
+            if (a->ntok <= 0 || a->ntok % 8 || a->M % a->ntok) return bad("QKV epilogues need ntok % 8 == 0 and M % ntok == 0");
+            if (a->ldo < 2 * a->d) return bad("QKV epilogues need ldo >= 2 d");
+            if (epi == EPI_QKV_LN) {
+                if (!a->ln_stats || !a->ln_c1 || !a->ln_b1 || !al16(a->ln_stats) || !al16(a->ln_c1) || !al16(a->ln_b1)) return bad("epilogue 5 needs ln_stats, ln_c1 and ln_b1, 16-byte aligned");
+                if (a->ln_slots < 2 || a->ln_slots > kLnSlots || a->ln_slots % 2) return bad("ln_slots must be even, 2 .. 8");
+            }
+        }
+    }
+    PtrDeviceGuard guard(a->A);
+    GemmParams g{};
+    g.A = static_cast<const bf16*>(a->A); g.lda = a->lda; g.W = static_cast<const bf16*>(a->W); g.ldw = a->ldw;
+    g.M = a->M; g.N = a->N; g.K = a->K;
+    g.f8 = f8 ? 1 : 0; g.a_scale = static_cast<const uint8_t*>(a->a_scale); g.w_scale = static_cast<const uint8_t*>(a->w_scale);
+    g.bias = a->bias;
+    g.out_bf16 = static_cast<bf16*>(a->out_bf16); g.ldo = a->ldo;
+    g.vt = static_cast<bf16*>(a->vt); g.ntok = a->ntok; g.d = a->d;
+    g.resid = static_cast<resid_t*>(a->resid); g.ldr = a->ldr; g.stats_out = static_cast<float2*>(a->stats_out);
+    g.ln_stats = static_cast<const float2*>(a->ln_stats); g.ln_slots = a->ln_slots; g.ln_c1 = a->ln_c1; g.ln_b1 = a->ln_b1;
+    g.row_stats = static_cast<const float2*>(a->row_stats);
+    g.c_f32 = a->c_f32; g.ldc = a->ldc;
+    g.w_batch_rows = a->w_batch_rows; g.w_batch_stride_bytes = a->w_batch_stride_bytes;
+    if (launch_gemm(g, epi, static_cast<hipStream_t>(hip_stream))) return TLD_ERR_INVALID;     // (refused: reason in tld_last_error)
+    HIP_TRY(hipGetLastError());
+    return TLD_OK;
+}
+
 int tld_engine_set_profile(tld_engine* e, uint32_t class_mask) {
     if (!e) return fail(TLD_ERR_INVALID, "null engine");
     for (int k = 0; k < KC_COUNT; ++k) e->prof_used[k] = 0;       // recorded pairs are forgotten, the pool is kept

@@ -562,7 +562,7 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, int nblocks
                 }
             }
             if constexpr (EPI == EPI_BIAS_BF16) {      // folded LayerNorm-3 of the plain up-projection (grids other than 16 x 16)
-                if (p.row_stats && wid < 2) {
+                if (BN != 384 && p.row_stats && wid < 2) {                   // (384-wide: no fold and no LDS behind the stages to stage it in)
                     int r0s = m0 + wid * 128 + lane * 2;                     // 2 rows (16 B) per lane, clamped at the matrix end
                     r0s = r0s + 1 < p.M ? r0s : (p.M >= 2 ? p.M - 2 : 0);
                     const char* src = reinterpret_cast<const char*>(p.row_stats + r0s);
@@ -1367,6 +1367,38 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, int nblocks
                     }
                 }
                 // (the next tile's K loop opens with a barrier: every wave is out of the images before stage 1 is written again)
+            } else if constexpr (EPI == EPI_BIAS_BF16 && G::WCOLS == 96) {
+                // 256 x 384 tiles, bias -> bf16 (no LayerNorm-3 fold: all of LDS is operand stages).  The 64-column epilogue below moves one 32 x 64 slab
+                // per pass; a wave tile here is 96 columns wide, so it goes one 32 x 32 MFMA tile at a time: swapped accumulators (lane = token row, four
+                // consecutive columns per register quad) -> [32 rows][64 B] with an 80-byte pitch -> 16-byte groups of 8 columns.
+                // (Until this branch existed the instantiation had NO epilogue -- the chain went from the residual add straight to WCOLS == 64 -- and
+                // stored nothing: tests/test_gpu_gemm_epilogues.py.)
+                constexpr int P = 64 + 16;
+                int e_lane = lane, e_l31 = l31, e_hi = hi;
+                asm volatile("" : "+v"(e_lane), "+v"(e_l31), "+v"(e_hi));
+#pragma unroll
+                for (int i = 0; i < G::TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < G::TN; ++j) {
+#pragma unroll
+                        for (int rq = 0; rq < 4; ++rq) {
+                            const int cl = 8 * rq + 4 * e_hi;
+                            const int cg = col0 + j * 32 + cl < p.N ? col0 + j * 32 + cl : 0;
+                            const float4 bv = *reinterpret_cast<const float4*>(p.bias + cg);
+                            bf16x4 pk;
+                            pk[0] = (bf16)(acc[i][j][rq * 4 + 0] + bv.x); pk[1] = (bf16)(acc[i][j][rq * 4 + 1] + bv.y);
+                            pk[2] = (bf16)(acc[i][j][rq * 4 + 2] + bv.z); pk[3] = (bf16)(acc[i][j][rq * 4 + 3] + bv.w);
+                            *reinterpret_cast<bf16x4*>(ws + e_l31 * P + cl * 2) = pk;
+                        }
+#pragma unroll
+                        for (int itr = 0; itr < 2; ++itr) {
+                            const int idx = itr * 64 + e_lane;
+                            const int rl = idx >> 2, ch = idx & 3;
+                            const u32x4 v = *reinterpret_cast<const u32x4*>(ws + rl * P + ch * 16);
+                            const int row = row0 + i * 32 + rl, col = col0 + j * 32 + ch * 8;
+                            if (row < p.M && col < p.N) TLD_STORE(reinterpret_cast<u32x4*>(p.out_bf16 + (size_t)row * p.ldo + col), v);
+                        }
+                    }
             } else if constexpr (G::WCOLS == 64) {
                 // lane-derived values re-materialised per tile: otherwise every address expression of this epilogue is
                 // hoisted out of the tile loop and lives (or spills) across the K loops
@@ -1524,6 +1556,8 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, int nblocks
                             }
                         }
                 }
+            } else {
+                static_assert(BN < 0, "this (tile width, epilogue) has no epilogue code: the kernel would compute its tiles and store nothing");
             }
         }
         m0 = m0n; n0 = n0n; kb0 = kbn;

@@ -106,8 +106,14 @@ inline int bf16_tile_width(long M, long N, long K, int epilogue) {
     if (epilogue == EPI_BIAS_RESID && N % 192 == 0) return whole_rounds(384) ? 384 : 192;
     // N = 768 with the plain bias epilogue (the training step's five per layer): one round of 256 x 384 tiles at the training batch instead of three rounds of
     // 256 x 128 (0.71 -> 1.0 PFLOP/s).  N < 1536: callers with a LayerNorm-3 fold have N = 4 d >= 1536, and the 384-wide tile has no room for the fold.
-    // K >= 384: the shapes it was built and tested for.  The VAE's attention projection at 128 channels and 65 536 tokens -- N = 384, K = 128, 256 tile-rows --
+    // K >= 384: the shapes it was built for.  The VAE's attention projection at 128 channels and 65 536 tokens -- N = 384, K = 128, 256 tile-rows --
     // met the other conditions and came out wrong in every row; it takes the 128-wide tiles like every other K = 128 launch.
+    // The cause had nothing to do with K: gemm256p_kernel<384, EPI_BIAS_BF16> had no epilogue.  Its wave tiles are 96 columns wide, the bias -> bf16 store code was
+    // written under `WCOLS == 64`, and the if-constexpr chain of epilogues simply ended -- the kernel ran its K loop and stored nothing, at every K (the VAE saw it
+    // because its output buffer is read; the training step at batch 128, the shape this tile was built for, has no test at that size).  The 96-column epilogue exists
+    // now and tests/test_gpu_gemm_epilogues.py holds the tile against float64 at K = 384, 768 and 3072; the clause stays because those are the K it is tested at
+    // (and the frozen table records it).  The same tile under the residual add has no such clause and needs none: its epilogue handles 96-column wave tiles, and
+    // the same tests hold it at K = 64 .. 320.
     if (epilogue == EPI_BIAS_BF16 && N < 1536 && K >= 384 && whole_rounds(384)) return 384;
     // Everything else: 256 unless the width does not divide, or that leaves the last round of workgroups mostly empty; then 128.
     // (a last round that is at least 85 % full counts as whole: 252 tiles on 256 CUs are not a reason to halve the tile)
