@@ -399,6 +399,36 @@ TLD_API int tld_debug_attention_fwd(const void* qk, const void* vt, void* att, i
  * would pick for that grid (whole-image / tiled / row-streaming).  channels % 64 == 0; grid <= 16 or a multiple of 16. */
 TLD_API int tld_debug_dwconv_gelu(const void* in_bf16, const float* weight_host, const float* bias_host, void* out_bf16, int32_t batch,
                                   int32_t grid, int32_t channels, void* hip_stream);
+/* Test hook: stage capture of the training step (the training engine's tld_vae_set_debug / tld_vae_read_stage).  With debug on, one
+ * tld_train_forward_backward call
+ *   - first fills every engine-owned activation / statistics / scratch / partial-sum buffer and the bound gradient vector with 0xFF bytes
+ *     (NaN in bf16 and fp32), so that a kernel that stores nothing, or too few rows, shows as NaN instead of the previous call's values;
+ *   - keeps what the backward overwrites: device-to-device copies on the same stream, right after the kernel that completes the value.
+ *     Snapshot memory (for max_batch samples) is allocated by set_debug(1), which fails if it cannot be had, and freed by set_debug(0) / destroy;
+ *     create allocates none, a step allocates none;
+ *   - records which launch path every size-dependent dispatch took (tld_train_debug_paths).
+ * With debug off nothing is launched, copied or allocated for the hook.  A debug call on a capturing stream is refused (TLD_ERR_STATE).
+ * Each path bit is set inside the branch that launches the kernel (the attention bits by launch_attention_bwd itself).
+ *
+ * Stage names (i = block index; M = batch * tokens; every stage is read back as fp32 with its logical shape):
+ *   saved forward tensors, read in place:  blk<i>.{x1 a1 qk vt att x2 a2 qc cr x3 a3 h hc o} (bf16; hc = GELU'(pre-activation) as stored),
+ *     blk<i>.{st1 st2 st3} [M, 2] (mean, rstd), blk<i>.p0 [M, H], blk<i>.kvc [2 batch, 2 d], sinb h1 g1v ycat y yst, p16 p16n est1 e est2,
+ *     xfin, dout, row_loss; the bf16 GEMM operand copies blk<i>.{wqkv wq wup wdown} and their transposes blk<i>.{wqkv_t wq_t wup_t wdown_t};
+ *   copied:  blk<i>.gl (GELU output, before the backward reuses its buffer), gx.tail, gxb.tail, and per block
+ *     gx.in (= the gradient entering the block), dg, dhc (unfused depthwise backward only), dh, da3, gx.ln3, dqc, dkv, da2, gx.ln2,
+ *     dqkv, da1, gx.ln1, gxb.ln1 (blocks > 0), each under blk<i>.; then dy, de, dpn, dp16, dycat, dg1.
+ * Launch-path bits of tld_train_debug_paths (bit number : path):
+ *    0 resid_ln q4<1>   1 q4<2>   2 q4<3>   3 q4<4>   4 resid_ln generic        5 ln_bwd q4<1>   6 q4<2>   7 q4<3>   8 ln_bwd generic
+ *    9 embed LDS<1>    10 LDS<2>  11 LDS<3>  12 LDS<4>  13 embed plain           14 tail_dx4<16>  15 <32>   16 <64>   17 tail_dx generic
+ *   18 tall_dw_cols    19 tall_dw_partial             20 colsum4   21 colsum     22 depthwise backward fused   23 unfused
+ *   24 wgrad_tn        25 transposing wgrad, sk == 1  26 sk > 1    27 zero-padded (M % 64 != 0)
+ *   28 attention backward one kernel   29 two kernels   30 masked (token count not a multiple of the block) */
+#define TLD_TRAIN_PATH_BITS 31
+TLD_API int tld_train_set_debug(tld_train* e, int32_t enable);
+/* host_out fp32 [numel] (numel must match the stage); shape_out: 4 int64, unused trailing dimensions 1; may be NULL.  host_out NULL: only the shape. */
+TLD_API int tld_train_read_stage(tld_train* e, const char* name, float* host_out, int64_t numel, int64_t* shape_out);
+/* mask of the launch paths the last debug call took */
+TLD_API int tld_train_debug_paths(tld_train* e, uint64_t* mask);
 TLD_API int tld_train_destroy(tld_train* e);
 
 #ifdef __cplusplus

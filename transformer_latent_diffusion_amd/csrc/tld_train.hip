@@ -18,6 +18,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -25,8 +26,9 @@ using namespace tld;
 using namespace tld::train;
 
 namespace tld {
-int launch_attention_bwd(const bf16* qk, const bf16* vt, const bf16* o, const float* g, bf16* dqkv, float* stats, int batch, int ntok, int heads, hipStream_t s);
-int launch_attention_bwd(const bf16* qk, const bf16* vt, const bf16* o, const bf16* g, bf16* dqkv, float* stats, int batch, int ntok, int heads, hipStream_t s);
+// path_out (may be null): which kernels were launched -- 1 one kernel, 2 two kernels, | 4 the masked forms
+int launch_attention_bwd(const bf16* qk, const bf16* vt, const bf16* o, const float* g, bf16* dqkv, float* stats, int batch, int ntok, int heads, hipStream_t s, int* path_out = nullptr);
+int launch_attention_bwd(const bf16* qk, const bf16* vt, const bf16* o, const bf16* g, bf16* dqkv, float* stats, int batch, int ntok, int heads, hipStream_t s, int* path_out = nullptr);
 }
 
 namespace {
@@ -70,6 +72,16 @@ struct LayerB {          // engine-owned per-layer buffers
 
 inline dim3 g1(size_t n, int bs = 256) { return dim3((unsigned)((n + bs - 1) / bs)); }
 
+// stage hook (tld_train_set_debug): a named tensor, read in place (the engine's own buffer) or from a copy the hook owns
+enum { ST_F32 = 0, ST_BF16 = 1 };
+struct Stage { void* ptr = nullptr; int dtype = ST_F32; int64_t shape[4] = {1, 1, 1, 1}; bool owned = false; size_t cap = 0; bool live = false; };
+// launch-path bits (the table in include/tld_hip.h)
+enum : int {
+    PB_RESID_Q4 = 0, PB_RESID_GEN = 4, PB_LNB_Q4 = 5, PB_LNB_GEN = 8, PB_EMB_LDS = 9, PB_EMB_PLAIN = 13, PB_TAIL4_16 = 14, PB_TAIL4_32 = 15, PB_TAIL4_64 = 16,
+    PB_TAIL_GEN = 17, PB_TALL_COLS = 18, PB_TALL_PART = 19, PB_COLSUM4 = 20, PB_COLSUM = 21, PB_DW_FUSED = 22, PB_DW_UNFUSED = 23, PB_WG_TN = 24,
+    PB_WG_TR1 = 25, PB_WG_TRSK = 26, PB_WG_PAD = 27, PB_ATT_ONE = 28, PB_ATT_TWO = 29, PB_ATT_MASKED = 30
+};
+
 }  // namespace
 
 struct tld_train {
@@ -83,6 +95,10 @@ struct tld_train {
     std::vector<LayerB> lb;
     float *params = nullptr, *grads = nullptr;
     std::vector<void*> allocs;
+    std::vector<size_t> alloc_bytes;     // size of each entry of allocs (the stage hook poisons them)
+    bool debug = false;                  // stage hook (tld_train_set_debug)
+    uint64_t paths = 0;                  // launch paths of the last debug call
+    std::map<std::string, Stage> stages;
     float* angular = nullptr;            // sinusoid buffer (not a parameter; tld/transformer_blocks.py:11-15)
     float* zero_bias = nullptr;
     // conditioning path
@@ -121,6 +137,7 @@ int dalloc(tld_train* e, T** p, size_t n) {
     void* q = nullptr;
     if (hipMalloc(&q, n * sizeof(T)) != hipSuccess) return tfail(TLD_ERR_HIP, "hipMalloc of %zu bytes failed", n * sizeof(T));
     e->allocs.push_back(q);
+    e->alloc_bytes.push_back(n * sizeof(T));
     *p = reinterpret_cast<T*>(q);
     return 0;
 }
@@ -155,16 +172,116 @@ bool wgrad_tn(const bf16* dY, int Nout, const bf16* X, int Kin, int M, float* dW
     return true;
 }
 
-void gemm_f32(const bf16* A, int lda, const bf16* W, int ldw, float* C, int Mr, int Nc, int K, hipStream_t s) {
+int gemm_f32(const bf16* A, int lda, const bf16* W, int ldw, float* C, int Mr, int Nc, int K, hipStream_t s) {
     GemmParams g{};
     g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.M = Mr; g.N = Nc; g.K = K; g.c_f32 = C; g.ldc = Nc;
-    launch_gemm(g, EPI_F32, s);
+    return launch_gemm(g, EPI_F32, s);
 }
-void gemm_bf16(const bf16* A, int lda, const bf16* W, int ldw, const float* bias, bf16* out, int Mr, int Nc, int K, hipStream_t s) {
+int gemm_bf16(const bf16* A, int lda, const bf16* W, int ldw, const float* bias, bf16* out, int Mr, int Nc, int K, hipStream_t s) {
     GemmParams g{};
     g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.M = Mr; g.N = Nc; g.K = K; g.out_bf16 = out; g.ldo = Nc; g.bias = bias;
-    launch_gemm(g, EPI_BIAS_BF16, s);
+    return launch_gemm(g, EPI_BIAS_BF16, s);
 }
+// a refused GEMM plan launches nothing: the step fails with launch_gemm's text instead of going on with the previous call's buffers
+#define GEMM_TRY(expr)                                                                                                           \
+    do {                                                                                                                         \
+        if (int _g = (expr)) { const std::string _m = tld_last_error(); return tfail(_g, "training step: %s refused: %s", #expr, _m.c_str()); } \
+    } while (0)
+
+// ---- stage hook ---------------------------------------------------------------------------------------------------------------
+void free_stages(tld_train* e) {
+    for (auto& kv : e->stages) if (kv.second.owned && kv.second.ptr) hipFree(kv.second.ptr);
+    e->stages.clear();
+}
+Stage* stage_slot(tld_train* e, const std::string& name, int dtype, int64_t s0, int64_t s1, int64_t s2, int64_t s3) {
+    Stage& st = e->stages[name];
+    st.dtype = dtype; st.shape[0] = s0; st.shape[1] = s1; st.shape[2] = s2; st.shape[3] = s3; st.live = true;
+    return &st;
+}
+// the engine's own buffer under a name (nothing is copied)
+void stage_ref(tld_train* e, const std::string& name, const void* ptr, int dtype, int64_t s0, int64_t s1 = 1, int64_t s2 = 1, int64_t s3 = 1) {
+    if (!e->debug) return;
+    Stage* st = stage_slot(e, name, dtype, s0, s1, s2, s3);
+    if (st->owned && st->ptr) { hipFree(st->ptr); st->cap = 0; }
+    st->owned = false; st->ptr = const_cast<void*>(ptr);
+}
+// a device-to-device copy on the stream, taken right after the kernel that completed the value
+int stage_copy(tld_train* e, const std::string& name, const void* src, int dtype, hipStream_t s, int64_t s0, int64_t s1 = 1, int64_t s2 = 1, int64_t s3 = 1) {
+    if (!e->debug) return TLD_OK;
+    Stage* st = stage_slot(e, name, dtype, s0, s1, s2, s3);
+    const size_t bytes = (size_t)(s0 * s1 * s2 * s3) * (dtype == ST_BF16 ? 2 : 4);
+    if (!st->owned || st->cap < bytes) {      // (tld_train_set_debug reserved every snapshot at max_batch: a name it does not know is a bug here)
+        st->live = false;
+        return tfail(TLD_ERR_STATE, "stage hook: no snapshot memory reserved for '%s' (%zu bytes)", name.c_str(), bytes);
+    }
+    if (hipMemcpyAsync(st->ptr, src, bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) return tfail(TLD_ERR_HIP, "stage hook: copy of '%s' failed", name.c_str());
+    return TLD_OK;
+}
+// start of a debug call: poison what the kernels are to write, forget the last call's stages, name the saved forward tensors
+int debug_begin(tld_train* e, int B, hipStream_t s) {
+    const int d = e->d, hid = e->hid, pd = e->pd, N = e->N, H = e->H, M = B * N;
+    e->paths = 0;
+    for (auto& kv : e->stages) kv.second.live = false;
+    auto keep = [&](const void* p) {       // constants and the weight operand copies (refreshed before this point) stay
+        if (p == e->angular || p == e->zero_bias) return true;
+        for (const LayerB& b : e->lb)
+            if (p == b.wqkv || p == b.wqkv_t || p == b.wq || p == b.wq_t || p == b.wup || p == b.wup_t || p == b.wdown || p == b.wdown_t || p == b.dww_t) return true;
+        return false;
+    };
+    for (size_t i = 0; i < e->allocs.size(); ++i)
+        if (!keep(e->allocs[i])) HIP_TRY(hipMemsetAsync(e->allocs[i], 0xFF, e->alloc_bytes[i], s));
+    HIP_TRY(hipMemsetAsync(e->grads, 0xFF, (size_t)e->nparam * 4, s));
+    stage_ref(e, "sinb", e->sinb, ST_F32, B, e->ne); stage_ref(e, "h1", e->h1, ST_F32, B, d); stage_ref(e, "g1v", e->g1v, ST_F32, B, d);
+    stage_ref(e, "ycat", e->ycat, ST_F32, 2 * B, d); stage_ref(e, "y", e->y, ST_F32, 2 * B, d); stage_ref(e, "yst", e->yst, ST_F32, 2 * B, 2);
+    stage_ref(e, "p16", e->p16, ST_F32, M, pd); stage_ref(e, "p16n", e->p16n, ST_F32, M, pd); stage_ref(e, "est1", e->est1, ST_F32, M, 2);
+    stage_ref(e, "e", e->e, ST_F32, M, d); stage_ref(e, "est2", e->est2, ST_F32, M, 2); stage_ref(e, "xfin", e->xfin, ST_BF16, M, d);
+    stage_ref(e, "dout", e->dout, ST_F32, M, pd); stage_ref(e, "row_loss", e->row_loss, ST_F32, M);
+    for (int i = 0; i < e->L; ++i) {
+        const LayerB& b = e->lb[i];
+        const std::string p = "blk" + std::to_string(i) + ".";
+        const struct { const char* n; const bf16* q; int w; } acts[] = {{"x1", b.x1, d}, {"a1", b.a1, d}, {"qk", b.qk, 2 * d}, {"att", b.att, d}, {"x2", b.x2, d}, {"a2", b.a2, d},
+            {"qc", b.qc, d}, {"cr", b.cr, d}, {"x3", b.x3, d}, {"a3", b.a3, d}, {"h", b.h, hid}, {"hc", b.hc, hid}, {"o", b.o, d}};
+        for (const auto& a : acts) stage_ref(e, p + a.n, a.q, ST_BF16, M, a.w);
+        stage_ref(e, p + "vt", b.vt, ST_BF16, B, H, 64, N);
+        stage_ref(e, p + "st1", b.st1, ST_F32, M, 2); stage_ref(e, p + "st2", b.st2, ST_F32, M, 2); stage_ref(e, p + "st3", b.st3, ST_F32, M, 2);
+        stage_ref(e, p + "p0", b.p0, ST_F32, M, H); stage_ref(e, p + "kvc", b.kvc, ST_F32, 2 * B, 2 * d);
+        stage_ref(e, p + "wqkv", b.wqkv, ST_BF16, 3 * d, d); stage_ref(e, p + "wqkv_t", b.wqkv_t, ST_BF16, d, 3 * d);
+        stage_ref(e, p + "wq", b.wq, ST_BF16, d, d); stage_ref(e, p + "wq_t", b.wq_t, ST_BF16, d, d);
+        stage_ref(e, p + "wup", b.wup, ST_BF16, hid, d); stage_ref(e, p + "wup_t", b.wup_t, ST_BF16, d, hid);
+        stage_ref(e, p + "wdown", b.wdown, ST_BF16, d, hid); stage_ref(e, p + "wdown_t", b.wdown_t, ST_BF16, hid, d);
+    }
+    return TLD_OK;
+}
+// set_debug(1): memory for every snapshot a step of max_batch samples takes (the names of the SNAP calls in tld_train_forward_backward_cb)
+int reserve_snapshots(tld_train* e) {
+    const size_t M = (size_t)e->B * e->N, d = e->d, hid = e->hid, pd = e->pd, B2 = 2 * (size_t)e->B;
+    auto one = [&](const std::string& name, size_t bytes) -> int {
+        Stage& st = e->stages[name];
+        if (st.owned && st.cap >= bytes) return TLD_OK;
+        if (st.owned && st.ptr) hipFree(st.ptr);
+        st = Stage();
+        if (hipMalloc(&st.ptr, bytes) != hipSuccess) { st.ptr = nullptr; return tfail(TLD_ERR_HIP, "tld_train_set_debug: hipMalloc of %zu bytes for the snapshot '%s' failed", bytes, name.c_str()); }
+        st.owned = true; st.cap = bytes;
+        return TLD_OK;
+    };
+#define RES(name, bytes) do { if (int _r = one(name, bytes)) return _r; } while (0)
+    RES("gx.tail", M * d * 4); RES("gxb.tail", M * d * 2);
+    const bool dw_fused = e->G <= 16 && e->N >= 176 && e->hid % 64 == 0;
+    for (int i = 0; i < e->L; ++i) {
+        const std::string p = "blk" + std::to_string(i) + ".";
+        for (const char* n : {"gl", "dg", "dh"}) RES(p + n, M * hid * 2);
+        if (!dw_fused) RES(p + "dhc", M * hid * 2);
+        for (const char* n : {"gx.in", "gx.ln3", "gx.ln2", "gx.ln1"}) RES(p + n, M * d * 4);
+        for (const char* n : {"da3", "dqc", "da2", "da1"}) RES(p + n, M * d * 2);
+        RES(p + "dqkv", M * 3 * d * 2); RES(p + "dkv", B2 * 2 * d * 4);
+        if (i > 0) RES(p + "gxb.ln1", M * d * 2);
+    }
+    RES("dy", B2 * d * 4); RES("dycat", B2 * d * 4); RES("dg1", (size_t)e->B * d * 4); RES("de", M * d * 4); RES("dpn", M * pd * 4); RES("dp16", M * pd * 4);
+#undef RES
+    return TLD_OK;
+}
+#define PATH(b) do { if (e->debug) e->paths |= 1ull << (b); } while (0)
+#define SNAP(...) do { if (e->debug) { if (int _r = stage_copy(e, __VA_ARGS__)) return _r; } } while (0)
 
 }  // namespace
 
@@ -346,6 +463,12 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
         once.run([&] { hipFuncSetAttribute(reinterpret_cast<const void*>(dwconv_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
     }
     const float inv_numel = 1.0f / (float)((size_t)B * e->C * e->S * e->S);
+    if (e->debug) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)
+            return tfail(TLD_ERR_STATE, "a debug step (tld_train_set_debug) cannot be captured into a graph");
+        if (int rc = debug_begin(e, B, s)) return rc;
+    }
     // the three small fp32 products on the tiled kernel (see tld_train_kernels.h)
     auto lin_fwd = [&](const float* in, int ldi, const float* W, const float* bias, float* out, int ldo, int R, int Nn, int K, float* pre, int gelu) {
         hipLaunchKernelGGL(tiled_f32_kernel, dim3((Nn + 31) / 32, (R + 31) / 32), dim3(256), 0, s, in, (long)ldi, 1L, W, (long)K, 1L, bias, out, ldo, R, Nn, K, pre, gelu, 0);
@@ -377,23 +500,24 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
         const size_t lwb = (size_t)pd * d * 4;
         if (lwb <= 65536) {
             const int nwg = (M + 3) / 4 < 4 * device_cu_count() ? (M + 3) / 4 : 4 * device_cu_count();
-            if (d <= 256) hipLaunchKernelGGL((embed_fwd_lds_kernel<1>), dim3(nwg), blk, lwb, s, q);
-            else if (d <= 512) hipLaunchKernelGGL((embed_fwd_lds_kernel<2>), dim3(nwg), blk, lwb, s, q);
-            else if (d <= 768) hipLaunchKernelGGL((embed_fwd_lds_kernel<3>), dim3(nwg), blk, lwb, s, q);
-            else hipLaunchKernelGGL((embed_fwd_lds_kernel<4>), dim3(nwg), blk, lwb, s, q);
+            if (d <= 256) { PATH(PB_EMB_LDS); hipLaunchKernelGGL((embed_fwd_lds_kernel<1>), dim3(nwg), blk, lwb, s, q); }
+            else if (d <= 512) { PATH(PB_EMB_LDS + 1); hipLaunchKernelGGL((embed_fwd_lds_kernel<2>), dim3(nwg), blk, lwb, s, q); }
+            else if (d <= 768) { PATH(PB_EMB_LDS + 2); hipLaunchKernelGGL((embed_fwd_lds_kernel<3>), dim3(nwg), blk, lwb, s, q); }
+            else { PATH(PB_EMB_LDS + 3); hipLaunchKernelGGL((embed_fwd_lds_kernel<4>), dim3(nwg), blk, lwb, s, q); }
         } else {
+            PATH(PB_EMB_PLAIN);
             hipLaunchKernelGGL(embed_fwd_kernel, dim3((M + 3) / 4), blk, 0, s, q);
         }
     }
     // x_out = x_in + delta [; a_out = LN(x_out), stats]   (delta == nullptr: LayerNorm of x_in alone)
     auto resid_ln = [&](const bf16* x_in, const bf16* delta, bf16* x_out, const float* gamma, const float* beta, bf16* a_out, float2* st) {
         const dim3 grid((M + 3) / 4);
-        if (d == 768) hipLaunchKernelGGL((resid_add_ln_q4_kernel<3>), grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M);
-        else if (d == 512) hipLaunchKernelGGL((resid_add_ln_q4_kernel<2>), grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M);
-        else if (d == 256) hipLaunchKernelGGL((resid_add_ln_q4_kernel<1>), grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M);
-        else if (d == 1024) hipLaunchKernelGGL((resid_add_ln_q4_kernel<4>), grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M);
-        else if (delta) hipLaunchKernelGGL(resid_add_ln_kernel, grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M, d);
-        else hipLaunchKernelGGL((ln_fwd_kernel<bf16>), grid, blk, 0, s, x_in, gamma, beta, a_out, (float*)nullptr, st, (const float*)nullptr, 1, M, d);
+        if (d == 768) { PATH(PB_RESID_Q4 + 2); hipLaunchKernelGGL((resid_add_ln_q4_kernel<3>), grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M); }
+        else if (d == 512) { PATH(PB_RESID_Q4 + 1); hipLaunchKernelGGL((resid_add_ln_q4_kernel<2>), grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M); }
+        else if (d == 256) { PATH(PB_RESID_Q4); hipLaunchKernelGGL((resid_add_ln_q4_kernel<1>), grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M); }
+        else if (d == 1024) { PATH(PB_RESID_Q4 + 3); hipLaunchKernelGGL((resid_add_ln_q4_kernel<4>), grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M); }
+        else if (delta) { PATH(PB_RESID_GEN); hipLaunchKernelGGL(resid_add_ln_kernel, grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M, d); }
+        else { PATH(PB_RESID_GEN); hipLaunchKernelGGL((ln_fwd_kernel<bf16>), grid, blk, 0, s, x_in, gamma, beta, a_out, (float*)nullptr, st, (const float*)nullptr, 1, M, d); }
     };
     // (k | v) of the two conditioning tokens for every block in one launch (tld/transformer_blocks.py:66-68): the blocks' parameters are laid out
     // identically, so block i's kv_linear.weight sits i block-strides after block 0's
@@ -408,18 +532,18 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
         {
             GemmParams g{};
             g.A = b.a1; g.lda = d; g.W = b.wqkv; g.ldw = d; g.M = M; g.N = 3 * d; g.K = d; g.out_bf16 = b.qk; g.ldo = 2 * d; g.vt = b.vt; g.ntok = N; g.d = d;
-            launch_gemm(g, EPI_QKV, s);
+            GEMM_TRY(launch_gemm(g, EPI_QKV, s));
         }
         launch_attention(b.qk, b.vt, b.att, B, N, H, s);
         resid_ln(b.x1, b.att, b.x2, P + p.n2w, P + p.n2b, b.a2, b.st2);
         // x = x + CA(LN2 x, y)   (:62-72,137)
-        gemm_bf16(b.a2, d, b.wq, d, e->zero_bias, b.qc, M, d, d, s);
+        GEMM_TRY(gemm_bf16(b.a2, d, b.wq, d, e->zero_bias, b.qc, M, d, d, s));
         hipLaunchKernelGGL(cross_fwd_kernel, dim3(B * H), blk, 0, s, b.qc, b.kvc, b.cr, b.p0, N, d);
         resid_ln(b.x2, b.cr, b.x3, P + p.n3w, P + p.n3b, b.a3, b.st3);
         // x = x + MLPSepConv(LN3 x)   (:89-113,138)
-        gemm_bf16(b.a3, d, b.wup, d, P + p.up_b, b.h, M, hid, d, s);
+        GEMM_TRY(gemm_bf16(b.a3, d, b.wup, d, P + p.up_b, b.h, M, hid, d, s));
         hipLaunchKernelGGL(dwconv_kernel, dw_grid, blk, dw_lds, s, b.h, b.dww_t, P + p.dw_b, b.hc, b.gl, B, G, hid, 0, dw_rows);
-        gemm_bf16(b.gl, hid, b.wdown, hid, P + p.down_b, b.o, M, d, hid, s);
+        GEMM_TRY(gemm_bf16(b.gl, hid, b.wdown, hid, P + p.down_b, b.o, M, d, hid, s));
         bf16* xnext = i + 1 < e->L ? e->lb[i + 1].x1 : e->xfin;
         if (i + 1 < e->L) resid_ln(b.x3, b.o, xnext, P + e->lp[i + 1].n1w, P + e->lp[i + 1].n1b, e->lb[i + 1].a1, e->lb[i + 1].st1);      // + the next block's LN1
         else resid_ln(b.x3, b.o, xnext, (const float*)nullptr, (const float*)nullptr, (bf16*)nullptr, (float2*)nullptr);
@@ -430,6 +554,7 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
     hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), blk, 0, s, e->row_loss, M, inv_numel, loss_out);
 
     // ================================================ backward ===============================================
+    if (e->debug) for (int i = 0; i < e->L; ++i) SNAP("blk" + std::to_string(i) + ".gl", e->lb[i].gl, ST_BF16, s, M, hid);       // (the backward writes dh there)
     auto reduce = [&](int nparts, size_t stride, size_t part_off, float* dst, int n, int acc) {
         hipLaunchKernelGGL(reduce_partials, dim3((n + 15) / 16), dim3(1024), 0, s, e->part + part_off, nparts, stride, dst, n, acc);
     };
@@ -438,12 +563,14 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
         using TX = std::remove_cv_t<std::remove_pointer_t<decltype(xp)>>;
         const int nc64 = (M + 63) / 64;
         if ((Nn == 16 || Nn == 32 || Nn == 64) && (size_t)nc64 * Nn * K <= e->part_floats) {
+            PATH(PB_TALL_COLS);
             const dim3 grid((K + 255) / 256, nc64);
             if (Nn == 16) hipLaunchKernelGGL((tall_dw_cols_partial<TX, 16>), grid, blk, 0, s, dyp, xp, K, M, 64, e->part);
             else if (Nn == 32) hipLaunchKernelGGL((tall_dw_cols_partial<TX, 32>), grid, blk, 0, s, dyp, xp, K, M, 64, e->part);
             else hipLaunchKernelGGL((tall_dw_cols_partial<TX, 64>), grid, blk, 0, s, dyp, xp, K, M, 64, e->part);
             reduce(nc64, (size_t)Nn * K, 0, dst, Nn * K, 0);
         } else {
+            PATH(PB_TALL_PART);
             hipLaunchKernelGGL((tall_dw_partial<TX>), dim3((Nn * K + 255) / 256, nchunk), blk, 0, s, dyp, Nn, xp, K, M, 256, e->part);
             reduce(nchunk, (size_t)Nn * K, 0, dst, Nn * K, 0);
         }
@@ -453,10 +580,10 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
         using TDY = std::remove_cv_t<std::remove_pointer_t<decltype(dyp)>>;
         using TX = std::remove_cv_t<std::remove_pointer_t<decltype(xp)>>;
         const int nb = (rows + 31) / 32;                                  // 32 rows per workgroup: >= 1024 workgroups at the training batch
-        if (width == 768) hipLaunchKernelGGL((ln_bwd_q4_kernel<TDY, TX, 3>), dim3(nb), blk, 0, s, dyp, xp, st, gamma, dx, acc, e->part, 32, rows, dxb);
-        else if (width == 512) hipLaunchKernelGGL((ln_bwd_q4_kernel<TDY, TX, 2>), dim3(nb), blk, 0, s, dyp, xp, st, gamma, dx, acc, e->part, 32, rows, dxb);
-        else if (width == 256) hipLaunchKernelGGL((ln_bwd_q4_kernel<TDY, TX, 1>), dim3(nb), blk, 0, s, dyp, xp, st, gamma, dx, acc, e->part, 32, rows, dxb);
-        else hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX>), dim3(nb), blk, 0, s, dyp, xp, st, gamma, dx, acc, e->part, 32, rows, width, dxb);
+        if (width == 768) { PATH(PB_LNB_Q4 + 2); hipLaunchKernelGGL((ln_bwd_q4_kernel<TDY, TX, 3>), dim3(nb), blk, 0, s, dyp, xp, st, gamma, dx, acc, e->part, 32, rows, dxb); }
+        else if (width == 512) { PATH(PB_LNB_Q4 + 1); hipLaunchKernelGGL((ln_bwd_q4_kernel<TDY, TX, 2>), dim3(nb), blk, 0, s, dyp, xp, st, gamma, dx, acc, e->part, 32, rows, dxb); }
+        else if (width == 256) { PATH(PB_LNB_Q4); hipLaunchKernelGGL((ln_bwd_q4_kernel<TDY, TX, 1>), dim3(nb), blk, 0, s, dyp, xp, st, gamma, dx, acc, e->part, 32, rows, dxb); }
+        else { PATH(PB_LNB_GEN); hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX>), dim3(nb), blk, 0, s, dyp, xp, st, gamma, dx, acc, e->part, 32, rows, width, dxb); }
         if (dbeta == dgamma + width) reduce(nb, 2 * (size_t)width, 0, dgamma, 2 * width, 0);       // (weight, bias) are neighbours in the flat vector: one launch
         else {
             reduce(nb, 2 * (size_t)width, 0, dgamma, width, 0);
@@ -467,11 +594,13 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
         using T = std::remove_cv_t<std::remove_pointer_t<decltype(ap)>>;
         if (cols % 4 == 0 && rows >= 4096) {        // four columns per thread, 64-row chunks (the chunk count feeds the 64 part-lanes of the reduction)
             const int nb = (rows + 63) / 64;
+            PATH(PB_COLSUM4);
             hipLaunchKernelGGL((colsum4_partial<T>), dim3((cols / 4 + 255) / 256, nb), blk, 0, s, ap, rows, cols, 64, e->part);
             reduce(nb, (size_t)cols, 0, dst, cols, 0);
             return;
         }
         const int nb = (rows + 255) / 256;
+        PATH(PB_COLSUM);
         hipLaunchKernelGGL((colsum_partial<T>), dim3((cols + 255) / 256, nb), blk, 0, s, ap, rows, cols, 256, e->part);
         reduce(nb, (size_t)cols, 0, dst, cols, 0);
     };
@@ -483,7 +612,7 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
     // The output is small and the contraction long, so the rows are cut into `sk` runs (split-K): the transposes write the stacked
     // operands [split][Nout | Kin][M / sk], ONE GEMM launch multiplies every split with its own W block (GemmParams::w_batch_rows)
     // into fp32 partials [split][Nout][Kin], and a fixed-order sum finishes (bit-reproducible).
-    auto weight_grad = [&](const bf16* dY, int Nout, const bf16* X, int Kin, float* dW) {
+    auto weight_grad = [&](const bf16* dY, int Nout, const bf16* X, int Kin, float* dW) -> int {
         int sk = 1;
         if (Nout % 256 == 0) while (sk < 8 && (M / (sk * 2)) % 128 == 0 && M / (sk * 2) >= 1024) sk *= 2;
         int ms = M / sk;
@@ -504,9 +633,10 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
             }
             if (bsk) { sk = bsk; ms = bms; }
         }
-        if (e->tn_wgrad && wgrad_tn(dY, Nout, X, Kin, M, dW, e->splitk, e->splitk_floats, s)) return;
+        if (e->tn_wgrad && wgrad_tn(dY, Nout, X, Kin, M, dW, e->splitk, e->splitk_floats, s)) { PATH(PB_WG_TN); return 0; }
         if (M % 64) {      // (token counts that are not multiples of 64, e.g. 144 x 3 rows): the GEMM's K loop takes whole 64-row steps, so the
             ms = (M + 63) / 64 * 64;       // transposed operands get zero columns up to the next multiple of 64 (sk == 1 here)
+            PATH(PB_WG_PAD);
             hipMemsetAsync(e->T1, 0, (size_t)Nout * ms * 2, s);
             hipMemsetAsync(e->T2, 0, (size_t)Kin * ms * 2, s);
         }
@@ -518,58 +648,80 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
         };
         tr(dY, Nout, e->T1);
         tr(X, Kin, e->T2);
-        if (sk == 1) { gemm_f32(e->T1, ms, e->T2, ms, dW, Nout, Kin, ms, s); return; }      // (ms == M, or M rounded up to 64)
+        if (sk == 1) { if (M % 64 == 0) PATH(PB_WG_TR1); return gemm_f32(e->T1, ms, e->T2, ms, dW, Nout, Kin, ms, s); }      // (ms == M, or M rounded up to 64)
+        PATH(PB_WG_TRSK);
         GemmParams g{};
         g.A = e->T1; g.lda = ms; g.W = e->T2; g.ldw = ms; g.M = sk * Nout; g.N = Kin; g.K = ms; g.c_f32 = e->splitk; g.ldc = Kin;
         g.w_batch_rows = Nout; g.w_batch_stride_bytes = (unsigned)((size_t)Kin * ms * 2);
-        launch_gemm(g, EPI_F32, s);
+        if (int rc = launch_gemm(g, EPI_F32, s)) return rc;
         if ((Nout * Kin) % 4 == 0) hipLaunchKernelGGL(sum_slices, dim3((unsigned)(((size_t)Nout * Kin / 4 + 255) / 256)), blk, 0, s, e->splitk, sk, (size_t)Nout * Kin, dW, (size_t)Nout * Kin / 4);
         else hipLaunchKernelGGL(reduce_partials, dim3((Nout * Kin + 15) / 16), dim3(1024), 0, s, e->splitk, sk, (size_t)Nout * Kin, dW, Nout * Kin, 0);
+        return 0;
     };
 
     // out_proj: gx = dout Wout;  dWout = dout^T x_final;  dbout
     // gx and its bf16 copy (the top block's GEMM operand)
-    if (pd == 16) hipLaunchKernelGGL((tail_dx4_kernel<16>), g1((size_t)M * d / 4), blk, 0, s, e->dout, P + e->outw, e->gx, e->gxb, M, d);
-    else if (pd == 32) hipLaunchKernelGGL((tail_dx4_kernel<32>), g1((size_t)M * d / 4), blk, 0, s, e->dout, P + e->outw, e->gx, e->gxb, M, d);
-    else if (pd == 64) hipLaunchKernelGGL((tail_dx4_kernel<64>), g1((size_t)M * d / 4), blk, 0, s, e->dout, P + e->outw, e->gx, e->gxb, M, d);
-    else hipLaunchKernelGGL(tail_dx_kernel, g1((size_t)M * d), blk, 0, s, e->dout, P + e->outw, e->gx, e->gxb, M, pd, d);
+    if (pd == 16) { PATH(PB_TAIL4_16); hipLaunchKernelGGL((tail_dx4_kernel<16>), g1((size_t)M * d / 4), blk, 0, s, e->dout, P + e->outw, e->gx, e->gxb, M, d); }
+    else if (pd == 32) { PATH(PB_TAIL4_32); hipLaunchKernelGGL((tail_dx4_kernel<32>), g1((size_t)M * d / 4), blk, 0, s, e->dout, P + e->outw, e->gx, e->gxb, M, d); }
+    else if (pd == 64) { PATH(PB_TAIL4_64); hipLaunchKernelGGL((tail_dx4_kernel<64>), g1((size_t)M * d / 4), blk, 0, s, e->dout, P + e->outw, e->gx, e->gxb, M, d); }
+    else { PATH(PB_TAIL_GEN); hipLaunchKernelGGL(tail_dx_kernel, g1((size_t)M * d), blk, 0, s, e->dout, P + e->outw, e->gx, e->gxb, M, pd, d); }
+    SNAP("gx.tail", e->gx, ST_F32, s, M, d); SNAP("gxb.tail", e->gxb, ST_BF16, s, M, d);
     tall_dw(e->dout, pd, (const bf16*)e->xfin, d, Gd + e->outw);
     colsum(e->dout, M, pd, Gd + e->outb);
 
     for (int i = e->L - 1; i >= 0; --i) {
         LayerB& b = e->lb[i]; const LayerP& p = e->lp[i];
+        const std::string sn = e->debug ? "blk" + std::to_string(i) + "." : std::string();
+        SNAP(sn + "gx.in", e->gx, ST_F32, s, M, d);
         // ---- MLP: o = g Wdown^T + b;  g = GELU(hc);  hc = dwconv(h);  h = a3 Wup^T + b;  a3 = LN3(x3)
         // (e->gxb = bf16(e->gx): written by whoever completed gx -- tail_dx_kernel for the top block, the LayerNorm-1 backward of the block above otherwise)
         colsum(e->gxb, M, d, Gd + p.down_b);
-        weight_grad(e->gxb, d, b.gl, hid, Gd + p.down_w);
-        gemm_bf16(e->gxb, d, b.wdown_t, d, e->zero_bias, e->dbig, M, hid, d, s);                         // dg = go Wdown
+        GEMM_TRY(weight_grad(e->gxb, d, b.gl, hid, Gd + p.down_w));
+        GEMM_TRY(gemm_bf16(e->gxb, d, b.wdown_t, d, e->zero_bias, e->dbig, M, hid, d, s));                         // dg = go Wdown
+        SNAP(sn + "dg", e->dbig, ST_BF16, s, M, hid);
         const bool dw_fused = G <= 16 && N >= 176 && hid % 64 == 0;
-        if (dw_fused) {      // GELU' multiply, depthwise weight-gradient partials and input gradient in one pass (both images of a (sample, 64-channel chunk) in LDS)
+        if (dw_fused) {      PATH(PB_DW_FUSED);      // GELU' multiply, depthwise weight-gradient partials and input gradient in one pass (both images of a (sample, 64-channel chunk) in LDS)
             hipLaunchKernelGGL(dwconv_bwd_img_kernel, dim3(B * (hid / 64)), blk, (size_t)2 * N * 128, s, e->dbig, b.hc, b.h, b.dww_t, b.gl, e->part, G, hid);   // dh -> b.gl (its forward value is consumed)
             hipLaunchKernelGGL(dwconv_wgrad_reduce, dim3((hid * 11 + 63) / 64), dim3(1024), 0, s, e->part, Gd + p.dw_w, Gd + p.dw_b, B, hid, 11, Gd + p.up_b);   // + the up-projection's bias gradient
         } else {
+            PATH(PB_DW_UNFUSED);
             hipLaunchKernelGGL(gelu_bwd_kernel, g1((size_t)M * hid / 8), blk, 0, s, e->dbig, b.hc, e->dbig, (size_t)M * hid / 8);      // dhc (in place); b.hc = GELU'(pre-activation)
+            SNAP(sn + "dhc", e->dbig, ST_BF16, s, M, hid);
             hipLaunchKernelGGL(dwconv_wgrad_kernel, dim3((hid + 255) / 256, B * G), blk, 0, s, e->dbig, b.h, e->part, G, hid);
             hipLaunchKernelGGL(dwconv_wgrad_reduce, dim3((hid * 10 + 63) / 64), dim3(1024), 0, s, e->part, Gd + p.dw_w, Gd + p.dw_b, B * G, hid);
             hipLaunchKernelGGL(dwconv_kernel, dw_grid, blk, dw_lds, s, e->dbig, b.dww_t, (const float*)nullptr, b.gl, (bf16*)nullptr, B, G, hid, 1, dw_rows);   // dh -> b.gl
         }
+        SNAP(sn + "dh", b.gl, ST_BF16, s, M, hid);
         if (!dw_fused) colsum(b.gl, M, hid, Gd + p.up_b);
-        weight_grad(b.gl, hid, b.a3, d, Gd + p.up_w);
-        gemm_bf16(b.gl, hid, b.wup_t, hid, e->zero_bias, e->dsmall2, M, d, hid, s);                     // da3 = dh Wup
+        GEMM_TRY(weight_grad(b.gl, hid, b.a3, d, Gd + p.up_w));
+        GEMM_TRY(gemm_bf16(b.gl, hid, b.wup_t, hid, e->zero_bias, e->dsmall2, M, d, hid, s));                     // da3 = dh Wup
+        SNAP(sn + "da3", e->dsmall2, ST_BF16, s, M, d);
         ln_bwd_rows(e->dsmall2, b.x3, b.st3, P + p.n3w, e->gx, 1, Gd + p.n3w, Gd + p.n3b, M, d);
+        SNAP(sn + "gx.ln3", e->gx, ST_F32, s, M, d);
         // ---- cross-attention: cr = CA(qc, kv);  qc = a2 Wq^T;  kv = y Wkv^T;  a2 = LN2(x2)
         float* dkv = e->dkv_all + (size_t)i * kv_stride;
         hipLaunchKernelGGL(cross_bwd_kernel, dim3(B * H), blk, 0, s, e->gx, b.qc, b.kvc, b.p0, e->dsmall2, dkv, N, d);   // dqc -> dsmall2
+        SNAP(sn + "dqc", e->dsmall2, ST_BF16, s, M, d); SNAP(sn + "dkv", dkv, ST_F32, s, 2 * B, 2 * d);
         lin_dw(dkv, 2 * d, e->y, d, Gd + p.kv, nullptr, 2 * B, 2 * d, d);       // (per block: its gradient range must be complete at the grad_ready call below)
-        weight_grad(e->dsmall2, d, b.a2, d, Gd + p.q);
-        gemm_bf16(e->dsmall2, d, b.wq_t, d, e->zero_bias, e->dsmall, M, d, d, s);                       // da2 = dqc Wq
+        GEMM_TRY(weight_grad(e->dsmall2, d, b.a2, d, Gd + p.q));
+        GEMM_TRY(gemm_bf16(e->dsmall2, d, b.wq_t, d, e->zero_bias, e->dsmall, M, d, d, s));                       // da2 = dqc Wq
+        SNAP(sn + "da2", e->dsmall, ST_BF16, s, M, d);
         ln_bwd_rows(e->dsmall, b.x2, b.st2, P + p.n2w, e->gx, 1, Gd + p.n2w, Gd + p.n2b, M, d);
+        SNAP(sn + "gx.ln2", e->gx, ST_F32, s, M, d);
         // ---- self-attention: att = SDPA(q, k, v);  qkv = a1 Wqkv^T;  a1 = LN1(x1)
-        if (launch_attention_bwd(b.qk, b.vt, b.att, e->gx, e->dsmall, e->attn_stats, B, N, H, s)) return tfail(TLD_ERR_INVALID, "attention backward: unsupported token count %d", N);
+        int attn_path = 0;
+        if (launch_attention_bwd(b.qk, b.vt, b.att, e->gx, e->dsmall, e->attn_stats, B, N, H, s, &attn_path)) return tfail(TLD_ERR_INVALID, "attention backward: unsupported token count %d", N);
+        if (attn_path & 1) PATH(PB_ATT_ONE);
+        if (attn_path & 2) PATH(PB_ATT_TWO);
+        if (attn_path & 4) PATH(PB_ATT_MASKED);
+        SNAP(sn + "dqkv", e->dsmall, ST_BF16, s, M, 3 * d);
         // (dO as a bf16 copy from the LayerNorm-2 backward: 192 -> 189 us, but delta = dO . O from rounded dO moves the worst g15 gradient from 1.86e-2 to 1.92e-2 of a 2e-2 bound: not taken)
-        weight_grad(e->dsmall, 3 * d, b.a1, d, Gd + p.qkv);
-        gemm_bf16(e->dsmall, 3 * d, b.wqkv_t, 3 * d, e->zero_bias, e->dsmall2, M, d, 3 * d, s);         // da1 = dqkv Wqkv
+        GEMM_TRY(weight_grad(e->dsmall, 3 * d, b.a1, d, Gd + p.qkv));
+        GEMM_TRY(gemm_bf16(e->dsmall, 3 * d, b.wqkv_t, 3 * d, e->zero_bias, e->dsmall2, M, d, 3 * d, s));         // da1 = dqkv Wqkv
+        SNAP(sn + "da1", e->dsmall2, ST_BF16, s, M, d);
         ln_bwd_rows(e->dsmall2, b.x1, b.st1, P + p.n1w, e->gx, 1, Gd + p.n1w, Gd + p.n1b, M, d, i > 0 ? e->gxb : nullptr);
+        SNAP(sn + "gx.ln1", e->gx, ST_F32, s, M, d);
+        if (i > 0) SNAP(sn + "gxb.ln1", e->gxb, ST_BF16, s, M, d);
         // every gradient of this block is enqueued (its 15 tensors are one contiguous range of the flat vector): the data-parallel
         // reduction of that slice can start now, under the backward of the blocks below
         if (grad_ready) grad_ready(user, p.qkv, (p.n3b + d) - p.qkv);
@@ -579,13 +731,17 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
                        (const float*)nullptr, e->dy_parts, d, 2 * B, d, 2 * d, (float*)nullptr, 0, 0, kv_stride, blk_stride, (long)e->B * 2 * d);
     hipLaunchKernelGGL(reduce_partials, dim3((2 * B * d + 15) / 16), dim3(1024), 0, s, e->dy_parts, e->L, (size_t)e->B * 2 * d, e->dy, 2 * B * d, 0);
     // ---- patch embedding: x0 = LN2(e) + pos;  e = pn Wlin^T + b;  pn = LN1(p);  p = conv(x)     (tld/denoiser.py:34-45,75-77)
+    SNAP("dy", e->dy, ST_F32, s, 2 * B, d);
     hipLaunchKernelGGL(pos_grad_kernel, g1((size_t)N * d), blk, 0, s, e->gx, Gd + e->pos, B, N, d);
     ln_bwd_rows(e->gx, e->e, e->est2, P + e->l2w, e->de, 0, Gd + e->l2w, Gd + e->l2b, M, d);
+    SNAP("de", e->de, ST_F32, s, M, d);
     colsum(e->de, M, d, Gd + e->lib);
     lin_dx(e->de, d, P + e->liw, e->dpn, pd, M, d, pd, 0);               // dpn = de Wlin
+    SNAP("dpn", e->dpn, ST_F32, s, M, pd);
     tall_dw(e->p16n, pd, (const float*)e->de, d, e->scr);                                                                              // dWlin^T [pd, d]
     hipLaunchKernelGGL(transpose_f32_small, g1((size_t)pd * d), blk, 0, s, e->scr, Gd + e->liw, pd, d);
     hipLaunchKernelGGL(ln_small_bwd_kernel, dim3(nchunk), blk, 0, s, e->dpn, e->p16, e->est1, P + e->l1w, e->dp16, e->part, M, pd);
+    SNAP("dp16", e->dp16, ST_F32, s, M, pd);
     reduce(nchunk, 2 * (size_t)pd, 0, Gd + e->l1w, pd, 0);
     reduce(nchunk, 2 * (size_t)pd, pd, Gd + e->l1b, pd, 0);
     hipLaunchKernelGGL(patches_kernel, g1((size_t)M * pd), blk, 0, s, x_noisy, e->patches, B, e->C, e->S, e->cfg.patch_size, G);
@@ -593,10 +749,12 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
     colsum(e->dp16, M, pd, Gd + e->cvb);
     // ---- conditioning: y = LN(stack[nz, lb]);  nz = W3 GELU(W1 sin + b1) + b3;  lb = label_proj(label)     (tld/denoiser.py:105-122)
     ln_bwd_rows(e->dy, e->ycat, e->yst, P + e->nw, e->dycat, 0, Gd + e->nw, Gd + e->nb, 2 * B, d);
+    SNAP("dycat", e->dycat, ST_F32, s, 2 * B, d);
     lin_dw(e->dycat + d, 2 * d, label, e->text, Gd + e->lbw, Gd + e->lbb, B, d, e->text);
     lin_dw(e->dycat, 2 * d, e->g1v, d, Gd + e->ff3w, Gd + e->ff3b, B, d, d);
     lin_dx(e->dycat, 2 * d, P + e->ff3w, e->dg1, d, B, d, d, 0);
     hipLaunchKernelGGL(mul_gelu_grad, g1((size_t)B * d), blk, 0, s, e->dg1, e->h1, B * d);
+    SNAP("dg1", e->dg1, ST_F32, s, B, d);
     lin_dw(e->dg1, d, e->sinb, e->ne, Gd + e->ff1w, Gd + e->ff1b, B, d, e->ne);
     if (grad_ready) {       // the ranges around the blocks: conditioning MLP / patch embedding / position table; out_proj, norm, label_proj
         grad_ready(user, 0, e->lp[0].qkv);
@@ -648,9 +806,53 @@ int tld_debug_wgrad(const void* dy, const void* x, float* dw, float* slices, int
     return TLD_OK;
 }
 
+int tld_train_set_debug(tld_train* e, int32_t enable) {
+    if (!e) return tfail(TLD_ERR_INVALID, "null engine");
+    DevGuard dg(e->cfg.device_id);
+    e->paths = 0;
+    if (enable) {
+        if (int rc = reserve_snapshots(e)) { free_stages(e); e->debug = false; return rc; }
+        e->debug = true;
+    } else {
+        e->debug = false;
+        (void)hipDeviceSynchronize();
+        free_stages(e);
+    }
+    return TLD_OK;
+}
+
+int tld_train_read_stage(tld_train* e, const char* name, float* host_out, int64_t numel, int64_t* shape_out) {
+    if (!e || !name) return tfail(TLD_ERR_INVALID, "null argument");
+    DevGuard dg(e->cfg.device_id);
+    auto it = e->stages.find(name);
+    if (it == e->stages.end() || !it->second.live || !it->second.ptr)
+        return tfail(TLD_ERR_KEY, "no captured stage named '%s' (tld_train_set_debug before the step? a stage of the other depthwise form?)", name);
+    const Stage& st = it->second;
+    const int64_t n = st.shape[0] * st.shape[1] * st.shape[2] * st.shape[3];
+    if (shape_out) for (int k = 0; k < 4; ++k) shape_out[k] = st.shape[k];
+    if (!host_out) return TLD_OK;
+    if (numel != n) return tfail(TLD_ERR_SHAPE, "stage '%s' has %lld elements, caller gave %lld", name, (long long)n, (long long)numel);
+    HIP_TRY(hipDeviceSynchronize());
+    if (st.dtype == ST_F32) {
+        HIP_TRY(hipMemcpy(host_out, st.ptr, (size_t)n * 4, hipMemcpyDeviceToHost));
+    } else {       // bf16 -> fp32 on the host: the upper half of the word
+        std::vector<uint16_t> tmp((size_t)n);
+        HIP_TRY(hipMemcpy(tmp.data(), st.ptr, (size_t)n * 2, hipMemcpyDeviceToHost));
+        for (int64_t i = 0; i < n; ++i) { const uint32_t u = (uint32_t)tmp[(size_t)i] << 16; memcpy(host_out + i, &u, 4); }
+    }
+    return TLD_OK;
+}
+
+int tld_train_debug_paths(tld_train* e, uint64_t* mask) {
+    if (!e || !mask) return tfail(TLD_ERR_INVALID, "null argument");
+    *mask = e->paths;
+    return TLD_OK;
+}
+
 int tld_train_destroy(tld_train* e) {
     if (!e) return TLD_OK;
     DevGuard dg(e->cfg.device_id);
+    free_stages(e);
     for (void* p : e->allocs) hipFree(p);
     delete e;
     return TLD_OK;

@@ -388,7 +388,7 @@ void launch_one(const bf16* qk, const bf16* vt, const bf16* o, const TG* g, bf16
 
 // a block width chosen at run time: the masked kernel when N is not a multiple of BT = 32 nw
 template <int MODE, typename TG>
-void launch_nw(int nw, const bf16* qk, const bf16* vt, const bf16* o, const TG* g, bf16* dqkv, float* stats, int batch, int ntok, int heads, hipStream_t s) {
+int launch_nw(int nw, const bf16* qk, const bf16* vt, const bf16* o, const TG* g, bf16* dqkv, float* stats, int batch, int ntok, int heads, hipStream_t s) {
     const bool masked = ntok % (32 * nw) != 0;
 #define TLD_ATTN_BWD_NW(W) \
     case W: \
@@ -405,24 +405,28 @@ void launch_nw(int nw, const bf16* qk, const bf16* vt, const bf16* o, const TG* 
         }
     }
 #undef TLD_ATTN_BWD_NW
+    return masked ? 4 : 0;      // (MODE != ATTN_FUSED at 7 waves is exact only: attn_bwd_block_waves picks 7 only where masked is false)
 }
 
 template <typename TG>
-int launch_bwd(const bf16* qk, const bf16* vt, const bf16* o, const TG* g, bf16* dqkv, float* stats, int batch, int ntok, int heads, hipStream_t s) {
+int launch_bwd(const bf16* qk, const bf16* vt, const bf16* o, const TG* g, bf16* dqkv, float* stats, int batch, int ntok, int heads, hipStream_t s, int* path_out) {
+    int path = 0;      // for the stage hook of tld_train.hip: 1 one kernel, 2 two kernels, | 4 masked -- set in the branch that launches
     // the token counts of the first training engine keep their kernels (unmasked, same block widths)
-    if (ntok == 256) launch_one<8, ATTN_FUSED, TG, false>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
-    else if (ntok == 128) launch_one<4, ATTN_FUSED, TG, false>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
-    else if (ntok == 64) launch_one<2, ATTN_FUSED, TG, false>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
+    if (ntok == 256) { path = 1; launch_one<8, ATTN_FUSED, TG, false>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s); }
+    else if (ntok == 128) { path = 1; launch_one<4, ATTN_FUSED, TG, false>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s); }
+    else if (ntok == 64) { path = 1; launch_one<2, ATTN_FUSED, TG, false>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s); }
     else if (ntok > 256 && ntok % 256 == 0 && stats) {
+        path = 2;
         launch_one<8, ATTN_DQ, TG, false>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
         launch_one<8, ATTN_DKV, TG, false>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
     } else if (ntok % 16 || ntok <= 0) return 1;
-    else if (ntok < 256) launch_nw<ATTN_FUSED>(attn_bwd_block_waves(ntok), qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
+    else if (ntok < 256) path = 1 | launch_nw<ATTN_FUSED>(attn_bwd_block_waves(ntok), qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
     else if (stats) {
         const int nw = attn_bwd_block_waves(ntok);
-        launch_nw<ATTN_DQ>(nw, qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
+        path = 2 | launch_nw<ATTN_DQ>(nw, qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
         launch_nw<ATTN_DKV>(nw, qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
     } else return 1;
+    if (path_out) *path_out = path;
     return 0;
 }
 
@@ -430,11 +434,11 @@ int launch_bwd(const bf16* qk, const bf16* vt, const bf16* o, const TG* g, bf16*
 
 // qk [M, 2 d] (q | k) and vt [B, H, 64, N]: the forward's saved operands;  o [M, d]: the forward's output;  g [M, d]: dL/dO (fp32 or bf16);
 // dqkv [M, 3 d] bf16 out.  N a multiple of 16 (returns 1 otherwise); `stats` = 2 B H N floats of scratch, touched only when N > 256 (rows < N).
-int launch_attention_bwd(const bf16* qk, const bf16* vt, const bf16* o, const float* g, bf16* dqkv, float* stats, int batch, int ntok, int heads, hipStream_t s) {
-    return launch_bwd<float>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
+int launch_attention_bwd(const bf16* qk, const bf16* vt, const bf16* o, const float* g, bf16* dqkv, float* stats, int batch, int ntok, int heads, hipStream_t s, int* path_out) {
+    return launch_bwd<float>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s, path_out);
 }
-int launch_attention_bwd(const bf16* qk, const bf16* vt, const bf16* o, const bf16* g, bf16* dqkv, float* stats, int batch, int ntok, int heads, hipStream_t s) {
-    return launch_bwd<bf16>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
+int launch_attention_bwd(const bf16* qk, const bf16* vt, const bf16* o, const bf16* g, bf16* dqkv, float* stats, int batch, int ntok, int heads, hipStream_t s, int* path_out) {
+    return launch_bwd<bf16>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s, path_out);
 }
 
 }  // namespace tld

@@ -155,6 +155,7 @@ class Trainer:
         self._slices = []                 # (offset, numel) in the order they became ready (tests)
         self._graph = None
         self._graph_calls = 0
+        self._debug = False
         self._static = None
         # gradient accumulation over micro-batches (accelerator.accumulate(), tld/train.py:160)
         self._acc = None                  # flat fp32 sum of the gradients of the micro-batches folded so far
@@ -238,6 +239,40 @@ class Trainer:
             self.reset_accumulation()                             # gradients folded against the old weights mean nothing for the new ones
         return self
 
+    # ---- stage hook (tests) ---------------------------------------------------------------------------------------------------
+    # launch paths reported by debug_paths(), bit number = position (the table in include/tld_hip.h)
+    PATH_NAMES = ("resid_ln_q4<1>", "resid_ln_q4<2>", "resid_ln_q4<3>", "resid_ln_q4<4>", "resid_ln_generic", "ln_bwd_q4<1>", "ln_bwd_q4<2>", "ln_bwd_q4<3>",
+                  "ln_bwd_generic", "embed_lds<1>", "embed_lds<2>", "embed_lds<3>", "embed_lds<4>", "embed_plain", "tail_dx4<16>", "tail_dx4<32>", "tail_dx4<64>",
+                  "tail_dx_generic", "tall_dw_cols", "tall_dw_partial", "colsum4", "colsum", "dw_bwd_fused", "dw_bwd_unfused", "wgrad_tn", "wgrad_transposing_sk1",
+                  "wgrad_transposing_splitk", "wgrad_transposing_padded", "attn_bwd_one_kernel", "attn_bwd_two_kernels", "attn_bwd_masked")
+
+    def set_debug(self, enable: bool = True) -> "Trainer":
+        """Stage capture (``tld_train_set_debug``): the next ``forward_backward`` calls poison the engine's buffers first, keep every stage for
+        ``read_stage`` and record their launch paths; they run eagerly (never through the captured graph).  Off again: snapshots are freed."""
+        _lib.check(_lib.lib().tld_train_set_debug(self._h, 1 if enable else 0), "tld_train_set_debug")
+        self._debug = bool(enable)
+        return self
+
+    debug = property(lambda self: self._debug, lambda self, v: self.set_debug(v) and None)
+
+    def read_stage(self, name: str) -> torch.Tensor:
+        """A stage of the last debug step as a float32 host tensor with its logical shape (names: include/tld_hip.h)."""
+        L = _lib.lib()
+        shape = (C.c_int64 * 4)()
+        _lib.check(L.tld_train_read_stage(self._h, name.encode(), None, 0, shape), f"tld_train_read_stage({name})")
+        dims = [int(v) for v in shape]
+        while len(dims) > 1 and dims[-1] == 1:
+            dims.pop()
+        out = torch.empty(int(np.prod(dims)), dtype=torch.float32)
+        _lib.check(L.tld_train_read_stage(self._h, name.encode(), C.cast(out.data_ptr(), C.POINTER(C.c_float)), out.numel(), shape),
+                   f"tld_train_read_stage({name})")
+        return out.view(*dims)
+
+    def debug_paths(self) -> int:
+        m = C.c_uint64()
+        _lib.check(_lib.lib().tld_train_debug_paths(self._h, C.byref(m)), "tld_train_debug_paths")
+        return int(m.value)
+
     # ---- the step -------------------------------------------------------------------------------------------------------------
     def make_batch(self, x: torch.Tensor, y: torch.Tensor, np_rng: Optional[np.random.Generator] = None,
                    generator: Optional[torch.Generator] = None):
@@ -315,7 +350,7 @@ class Trainer:
                 _lib.check(_lib.lib().tld_train_forward_backward(self._h, C.c_void_p(xn_.data_ptr()), C.c_void_p(nl_.data_ptr()), C.c_void_p(lab_.data_ptr()),
                                                                  C.c_void_p(tgt_.data_ptr()), B, C.c_void_p(self._loss.data_ptr()), C.c_void_p(pred_.data_ptr()),
                                                                  C.c_void_p(stream)), "tld_train_forward_backward")
-        if self.use_graph and B == self.max_batch:
+        if self.use_graph and B == self.max_batch and not self._debug:      # (a debug step is never captured: the hook copies and allocates)
             self._graph_calls += 1
             if self._graph_calls >= 2:
                 if self._graph is None:      # second call: fixed buffers, capture (the first call ran eagerly: one-time attribute / cache set-up is done)
