@@ -111,6 +111,27 @@ TLD_API int tld_sample(tld_engine* e, const void* x_T, const void* labels, const
                float class_guidance, float sharp_f, float bright_f, void* out_latent, int32_t batch,
                void* trace_x0, void* trace_xt, void* hip_stream);
 
+/* Image-to-image and inpainting: tld_sample for a trajectory that starts from a latent instead of pure noise.  It replaces what a
+ * PyTorch user writes around the loop of tld/diffusion.py:59-92 -- noising an image with the forward process of the training loop
+ * (tld/train.py:130, x_s = s eps + (1 - s) x0) before the first step and re-imposing the known region after every step -- which cannot be done
+ * from outside here because the loop runs on the device.  The reference itself has no such entry point.
+ *   noise       [batch, C, S, S] fp32 device: eps (initialize_image, :105-120, done by caller)
+ *   init_latent [batch, C, S, S] fp32 device: z0 in model space (VAE latent / scale_factor, tld/train.py:122); may be NULL when mask is NULL
+ *               and start_mix is 1
+ *   mask        [batch, 1, S, S] fp32 device in [0, 1], broadcast over channels: 1 = regenerate, 0 = keep; NULL = no mask
+ *   start_mix   s0 in (0, 1]: x_start = s0 eps + (1 - s0) z0; exactly 1 = start from eps itself, as tld_sample does
+ *   labels, coeffs, n_levels, class_guidance, sharp_f, bright_f, out_latent, batch, trace_x0, trace_xt: as in tld_sample; coeffs holds the
+ *               REMAINING levels only (schedule.truncate_levels), so the first step is first-order
+ * Every step is tld_sample's (same kernels for the model; the elementwise step is its sibling kernel with the same arithmetic, one launch per
+ * step).  With a mask, after the update to level s_next:  x_t <- m x_t + (1 - m) (s_next eps + (1 - s_next) z0),  and on the final prediction
+ * x0 <- m x0 + (1 - m) z0 before the shifts; both are exact where m is 0 or 1.  x0 of the multistep history and trace_x0 stay unblended.
+ * Without a mask and with start_mix = 1 the result equals tld_sample's bit for bit.
+ * noise, init_latent and mask are read by every step: they must stay valid until the enqueued work has run.  Same rules as tld_sample otherwise:
+ * batch*2 <= max_batch, no stream synchronisation, everything is enqueued on hip_stream. */
+TLD_API int tld_sample_from(tld_engine* e, const void* noise, const void* init_latent, const void* mask, float start_mix, const void* labels,
+               const float* coeffs, int32_t n_levels, float class_guidance, float sharp_f, float bright_f, void* out_latent,
+               int32_t batch, void* trace_x0, void* trace_xt, void* hip_stream);
+
 /* Test hook: copy a named internal stage of the LAST forward to host fp32 (synchronises).
  * names: "cond_y" [T,d] (T = batch noise rows then batch label rows), "tokens0", "blk0_sa",
  * "blk0_ca", "blk0_mlp", "tokens_final" (each [batch*N, d]).  Stage capture must have been

@@ -2,7 +2,8 @@
 ``Denoiser`` / ``DiffusionGenerator`` / ``DiffusionTransformer`` hot path)."""
 from .configs import ClipConfig, DenoiserConfig, DenoiserLoad, LTDConfig, VaeConfig, config_100m  # noqa: F401
 from .denoiser import Denoiser  # noqa: F401
-from .diffusion import DiffusionGenerator, DiffusionTransformer, RequestBatcher  # noqa: F401
+from .diffusion import DiffusionGenerator, DiffusionTransformer, RequestBatcher, latent_mask  # noqa: F401
+from .sharded import generate_latents_from_sharded  # noqa: F401
 from .vae import AutoencoderKLDecoder, VaeDecoderConfig  # noqa: F401
 from .vae_encoder import AutoencoderKL, AutoencoderKLEncoder, DiagonalGaussianDistribution, VaeEncoderConfig, encode_image  # noqa: F401
 from .clip_text import ClipTextConfig, ClipTextEncoder  # noqa: F401
@@ -11,4 +12,5 @@ from .train import TrainConfig, Trainer  # noqa: F401
 
 __all__ = ["ClipConfig", "DenoiserConfig", "DenoiserLoad", "LTDConfig", "VaeConfig", "config_100m", "Denoiser",
            "DiffusionGenerator", "DiffusionTransformer", "RequestBatcher", "AutoencoderKLDecoder", "VaeDecoderConfig",
-           "AutoencoderKL", "AutoencoderKLEncoder", "DiagonalGaussianDistribution", "VaeEncoderConfig", "encode_image", "ClipTextConfig", "ClipTextEncoder", "ClipTokenizer", "TrainConfig", "Trainer"]
+           "AutoencoderKL", "AutoencoderKLEncoder", "DiagonalGaussianDistribution", "VaeEncoderConfig", "encode_image", "ClipTextConfig", "ClipTextEncoder", "ClipTokenizer", "TrainConfig", "Trainer",
+           "latent_mask", "generate_latents_from_sharded"]

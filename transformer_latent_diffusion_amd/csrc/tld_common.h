@@ -408,6 +408,18 @@ struct UpdateParams {
 };
 void launch_update(const UpdateParams& p, hipStream_t s);
 
+// the same step for a trajectory that starts from an image (tld_sample_from)
+struct UpdateFromParams {
+    UpdateParams u;
+    const float* noise;           // [B, img]  eps of the forward process             (read with a mask only)
+    const float* z0;              // [B, img]  initial latent = the known region      (read with a mask only)
+    const float* mask;            // [B, chan_stride] in [0,1], 1 = regenerate, broadcast over channels; null: no blend, update_kernel's arithmetic
+    float s_next;                 // noise level the updated x_t sits at (unused on the final step)
+};
+void launch_update_from(const UpdateFromParams& p, hipStream_t s);
+// x_t = s0 noise + (1 - s0) z0 over n elements
+void launch_start_mix(const float* noise, const float* z0, float s0, float* x_t, int n, hipStream_t s);
+
 // ---- conditioning path (fp32) ------------------------------------------------------------------
 // out[t, n] = act(sum_k in[t,k] W[n,k] + b[n]);  act: 0 none, 1 exact GELU
 void launch_linear_f32(const float* in, int ldi, const float* W, const float* b, float* out, int ldo,

@@ -486,6 +486,60 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
     return TLD_OK;
 }
 
+// What tld_sample and tld_sample_from share ahead of the loop: argument checks, the conditioning tables of the whole trajectory and the
+// token-row tables, through the engine's pinned staging buffer (no stream synchronisation).
+int sample_prepare(tld_engine* e, const void* labels, const float* coeffs, int n_levels, int batch, hipStream_t s, const int** label_row_out) {
+    if (!e->finalized) return fail(TLD_ERR_STATE, "weights not finalized");
+    if (batch <= 0 || 2 * batch > e->cfg.max_batch)
+        return fail(TLD_ERR_INVALID, "sampler batch %d needs max_batch >= %d (have %d)", batch, 2 * batch, e->cfg.max_batch);
+    if (n_levels < 2) return fail(TLD_ERR_INVALID, "need at least two noise levels");
+    const int B = batch, B2 = 2 * batch, T = n_levels + B + 1;
+    if (int rc = ensure_cond_capacity(e, T)) return rc;
+    if (int rc = ensure_rows_capacity(e, (int64_t)(n_levels + 1) * B2)) return rc;
+
+    // ---- conditioning tables for the whole trajectory, once
+    const size_t n_rows = (size_t)(n_levels + 1) * B2;
+    if (int rc = stage_acquire(e, (size_t)n_levels * sizeof(float) + n_rows * sizeof(int))) return rc;
+    float* sig = static_cast<float*>(e->stage_host);
+    int* rows = reinterpret_cast<int*>(sig + n_levels);
+    for (int i = 0; i < n_levels; ++i) sig[i] = coeffs[(size_t)i * 6 + 0];
+    HIP_TRY(hipMemcpyAsync(e->c_sigma, sig, (size_t)n_levels * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(e->c_label, labels, (size_t)B * e->text * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemsetAsync(e->c_label + (size_t)B * e->text, 0, e->text * sizeof(float), s));   // uncond = zeros (diffusion.py:61)
+    {
+        ProfScope ps(e, KC_COND, s);
+        cond_noise_rows(e, n_levels, s);
+        cond_label_rows(e, n_levels, B + 1, s);
+    }
+    if (int rc = cond_tables(e, T, s)) return rc;
+    // row tables: [step][B2] noise rows, then one [B2] label-row table
+    for (int i = 0; i < n_levels; ++i)
+        for (int b = 0; b < B2; ++b) rows[(size_t)i * B2 + b] = i;
+    for (int b = 0; b < B2; ++b) rows[(size_t)n_levels * B2 + b] = n_levels + (b < B ? b : B);
+    HIP_TRY(hipMemcpyAsync(e->rows_dev, rows, n_rows * sizeof(int), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(e->stage_ev, s));     // no stream sync: the staging buffer is the engine's, guarded by this event
+    *label_row_out = e->rows_dev + (size_t)n_levels * B2;
+    e->dbg_batch = B2; e->dbg_T = T;
+    return TLD_OK;
+}
+
+// one step's elementwise parameters (row i of the coefficient table)
+UpdateParams update_params(tld_engine* e, const float* coeffs, int n_levels, int i, float class_guidance, float sharp_f, float bright_f,
+                           void* out_latent, int B, void* trace_x0, void* trace_xt) {
+    const bool final_step = (i == n_levels - 1);
+    const size_t tot = (size_t)B * e->img;
+    UpdateParams up{};
+    const float* c = coeffs + (size_t)i * 6;
+    up.x0_2b = e->io_out; up.x_t = e->xt; up.x0_prev = e->x0_prev;
+    up.x0_out = final_step ? static_cast<float*>(out_latent) : e->x0_cfg;
+    up.trace_x0 = (!final_step && trace_x0) ? static_cast<float*>(trace_x0) + (size_t)i * tot : nullptr;
+    up.trace_xt = (!final_step && trace_xt) ? static_cast<float*>(trace_xt) + (size_t)i * tot : nullptr;
+    up.g = class_guidance; up.a = c[1]; up.b = c[2]; up.c = c[3]; up.c1 = c[4]; up.c2 = c[5];
+    up.sharp = sharp_f; up.bright = bright_f; up.final_step = final_step ? 1 : 0;
+    up.batch = B; up.img = e->img; up.chan_stride = e->cfg.image_size * e->cfg.image_size; up.C = e->cfg.n_channels;
+    return up;
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -900,59 +954,52 @@ int tld_sample(tld_engine* e, const void* x_T, const void* labels, const float* 
                float class_guidance, float sharp_f, float bright_f, void* out_latent, int32_t batch,
                void* trace_x0, void* trace_xt, void* hip_stream) {
     if (!e || !x_T || !labels || !coeffs || !out_latent) return fail(TLD_ERR_INVALID, "null argument");
-    if (!e->finalized) return fail(TLD_ERR_STATE, "weights not finalized");
-    if (batch <= 0 || 2 * batch > e->cfg.max_batch)
-        return fail(TLD_ERR_INVALID, "sampler batch %d needs max_batch >= %d (have %d)", batch, 2 * batch, e->cfg.max_batch);
-    if (n_levels < 2) return fail(TLD_ERR_INVALID, "need at least two noise levels");
     DeviceGuard dg(e->cfg.device_id);
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    const int B = batch, B2 = 2 * batch, T = n_levels + B + 1;
-    if (int rc = ensure_cond_capacity(e, T)) return rc;
-    if (int rc = ensure_rows_capacity(e, (int64_t)(n_levels + 1) * B2)) return rc;
-
-    // ---- conditioning tables for the whole trajectory, once
-    const size_t n_rows = (size_t)(n_levels + 1) * B2;
-    if (int rc = stage_acquire(e, (size_t)n_levels * sizeof(float) + n_rows * sizeof(int))) return rc;
-    float* sig = static_cast<float*>(e->stage_host);
-    int* rows = reinterpret_cast<int*>(sig + n_levels);
-    for (int i = 0; i < n_levels; ++i) sig[i] = coeffs[(size_t)i * 6 + 0];
-    HIP_TRY(hipMemcpyAsync(e->c_sigma, sig, (size_t)n_levels * sizeof(float), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(e->c_label, labels, (size_t)B * e->text * sizeof(float), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemsetAsync(e->c_label + (size_t)B * e->text, 0, e->text * sizeof(float), s));   // uncond = zeros (diffusion.py:61)
-    {
-        ProfScope ps(e, KC_COND, s);
-        cond_noise_rows(e, n_levels, s);
-        cond_label_rows(e, n_levels, B + 1, s);
-    }
-    if (int rc = cond_tables(e, T, s)) return rc;
-    // row tables: [step][B2] noise rows, then one [B2] label-row table
-    for (int i = 0; i < n_levels; ++i)
-        for (int b = 0; b < B2; ++b) rows[(size_t)i * B2 + b] = i;
-    for (int b = 0; b < B2; ++b) rows[(size_t)n_levels * B2 + b] = n_levels + (b < B ? b : B);
-    HIP_TRY(hipMemcpyAsync(e->rows_dev, rows, n_rows * sizeof(int), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipEventRecord(e->stage_ev, s));     // no stream sync: the staging buffer is the engine's, guarded by this event
-    const int* label_row = e->rows_dev + (size_t)n_levels * B2;
+    const int* label_row = nullptr;
+    if (int rc = sample_prepare(e, labels, coeffs, n_levels, batch, s, &label_row)) return rc;
+    const int B = batch, B2 = 2 * batch;
 
     const size_t tot = (size_t)B * e->img;
     HIP_TRY(hipMemcpyAsync(e->xt, x_T, tot * sizeof(float), hipMemcpyDeviceToDevice, s));
     HIP_TRY(hipMemsetAsync(e->x0_prev, 0, tot * sizeof(float), s));
-    e->dbg_batch = B2; e->dbg_T = T;
 
     for (int i = 0; i < n_levels; ++i) {
-        const bool final_step = (i == n_levels - 1);
         // pred_image: model(cat[x_t, x_t], sigma_i, [labels; 0])   (diffusion.py:94-101)
         if (int rc = run_body(e, e->xt, B, B2, e->rows_dev + (size_t)i * B2, label_row, e->io_out, s, true)) return rc;
         ProfScope ps(e, KC_UPDATE, s);
-        UpdateParams up{};
-        const float* c = coeffs + (size_t)i * 6;
-        up.x0_2b = e->io_out; up.x_t = e->xt; up.x0_prev = e->x0_prev;
-        up.x0_out = final_step ? static_cast<float*>(out_latent) : e->x0_cfg;
-        up.trace_x0 = (!final_step && trace_x0) ? static_cast<float*>(trace_x0) + (size_t)i * tot : nullptr;
-        up.trace_xt = (!final_step && trace_xt) ? static_cast<float*>(trace_xt) + (size_t)i * tot : nullptr;
-        up.g = class_guidance; up.a = c[1]; up.b = c[2]; up.c = c[3]; up.c1 = c[4]; up.c2 = c[5];
-        up.sharp = sharp_f; up.bright = bright_f; up.final_step = final_step ? 1 : 0;
-        up.batch = B; up.img = e->img; up.chan_stride = e->cfg.image_size * e->cfg.image_size; up.C = e->cfg.n_channels;
-        launch_update(up, s);
+        launch_update(update_params(e, coeffs, n_levels, i, class_guidance, sharp_f, bright_f, out_latent, B, trace_x0, trace_xt), s);
+    }
+    HIP_TRY(hipGetLastError());
+    return TLD_OK;
+}
+
+int tld_sample_from(tld_engine* e, const void* noise, const void* init_latent, const void* mask, float start_mix, const void* labels,
+                    const float* coeffs, int32_t n_levels, float class_guidance, float sharp_f, float bright_f, void* out_latent,
+                    int32_t batch, void* trace_x0, void* trace_xt, void* hip_stream) {
+    if (!e || !noise || !labels || !coeffs || !out_latent) return fail(TLD_ERR_INVALID, "null argument");
+    if (!(start_mix > 0.0f && start_mix <= 1.0f)) return fail(TLD_ERR_INVALID, "start_mix %g outside (0, 1]", (double)start_mix);
+    if (!init_latent && (mask || start_mix < 1.0f)) return fail(TLD_ERR_INVALID, "init_latent is required with a mask or with start_mix < 1");
+    DeviceGuard dg(e->cfg.device_id);
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    const int* label_row = nullptr;
+    if (int rc = sample_prepare(e, labels, coeffs, n_levels, batch, s, &label_row)) return rc;
+    const int B = batch, B2 = 2 * batch;
+
+    const size_t tot = (size_t)B * e->img;
+    // the start: pure noise at the schedule's first level (diffusion.py:52,59), else the forward process at the first remaining level (train.py:130)
+    if (start_mix == 1.0f) HIP_TRY(hipMemcpyAsync(e->xt, noise, tot * sizeof(float), hipMemcpyDeviceToDevice, s));
+    else launch_start_mix(static_cast<const float*>(noise), static_cast<const float*>(init_latent), start_mix, e->xt, (int)tot, s);
+    HIP_TRY(hipMemsetAsync(e->x0_prev, 0, tot * sizeof(float), s));
+
+    for (int i = 0; i < n_levels; ++i) {
+        if (int rc = run_body(e, e->xt, B, B2, e->rows_dev + (size_t)i * B2, label_row, e->io_out, s, true)) return rc;
+        ProfScope ps(e, KC_UPDATE, s);
+        UpdateFromParams uf{};
+        uf.u = update_params(e, coeffs, n_levels, i, class_guidance, sharp_f, bright_f, out_latent, B, trace_x0, trace_xt);
+        uf.noise = static_cast<const float*>(noise); uf.z0 = static_cast<const float*>(init_latent); uf.mask = static_cast<const float*>(mask);
+        uf.s_next = (i + 1 < n_levels) ? coeffs[(size_t)(i + 1) * 6 + 0] : 0.0f;
+        launch_update_from(uf, s);
     }
     HIP_TRY(hipGetLastError());
     return TLD_OK;

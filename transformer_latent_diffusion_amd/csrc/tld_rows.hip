@@ -5,6 +5,8 @@
 //   cross_row_kernel    SA residual add + whole cross-attention sub-block + LN3       tld/transformer_blocks.py:136-138, 62-72
 //   tail_kernel         out_proj Linear(d->pd) + unpatchify                           tld/denoiser.py:47-52,72,82
 //   update_kernel       CFG combine + DPM-Solver++(2M)/DDIM update + latent shifts    tld/diffusion.py:66-89,122-125
+//   update_from_kernel  the same step of a trajectory that starts from an image, + the inpainting blend
+//   start_mix_kernel    x_start = s0 eps + (1 - s0) z0, the forward process of tld/train.py:130
 //   dwconv_gelu_kernel  depthwise 3x3 + bias + exact GELU, channels-last              tld/transformer_blocks.py:96-103
 //
 // Row layout: a wave owns one token row of d features; lane l holds features {2l, 2l+1} + 128*j
@@ -1037,6 +1039,91 @@ __global__ __launch_bounds__(256) void update_kernel(UpdateParams p) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// update_kernel's sibling for tld_sample_from (image-to-image / inpainting).  A thread owns V consecutive elements (V = 4: one 16-byte access
+// per stream; they share a channel and a mask quad because chan_stride % 4 == 0) and runs update_kernel's arithmetic on each, so that without a
+// mask the two kernels write the same bits.  Which products of those expressions the compiler fuses depends on how it vectorises a kernel, so
+// contraction is switched off here and the roundings update_kernel performs are spelled out:
+//   x0 = fma(g, cond, (1 - g) unc)      D = fma(c1, x0, -(c2 x0_prev))      x_t = (a D + b x_t) / c   with both products rounded
+// (tests/test_gpu_img2img.py holds the two kernels to equal bits).  MASK adds, in the same launch:
+//   after the update   x_t <- m x_t + (1 - m) (s_next eps + (1 - s_next) z0)     the known region rides the forward process of the same eps
+//   on the final step  x0  <- m x0  + (1 - m) z0                                  before the latent shifts
+// x0_prev, x0_out of the inner steps and trace_x0 keep the unblended prediction.  The blend is written m a + (1 - m) b: m = 1 gives a and m = 0
+// gives b exactly, and with no contraction it rounds as the fp32 reference loop does.
+template <bool MASK, int V>
+__global__ __launch_bounds__(256) void update_from_kernel(UpdateFromParams q) {
+#pragma clang fp contract(off)
+    const UpdateParams& p = q.u;
+    const int i = (blockIdx.x * 256 + threadIdx.x) * V;
+    const int n = p.batch * p.img;
+    if (i >= n) return;
+    float cond[V], unc[V], prev[V], xin[V], eps[V], z[V], m[V], x0o[V], xto[V];
+    auto load = [&](float* dst, const float* src) {
+        if constexpr (V == 4) *reinterpret_cast<float4*>(dst) = *reinterpret_cast<const float4*>(src);
+        else dst[0] = src[0];
+    };
+    auto store = [&](float* dst, const float* src) {
+        if constexpr (V == 4) *reinterpret_cast<float4*>(dst) = *reinterpret_cast<const float4*>(src);
+        else dst[0] = src[0];
+    };
+    const int b = i / p.img, r = i - b * p.img;
+    const int ch = r / p.chan_stride;
+    load(cond, p.x0_2b + i);
+    load(unc, p.x0_2b + n + i);
+    if constexpr (MASK) {
+        load(m, q.mask + (size_t)b * p.chan_stride + (r - ch * p.chan_stride));
+        load(z, q.z0 + i);
+    }
+    if (p.final_step) {
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            float x0 = __builtin_fmaf(p.g, cond[v], (1.0f - p.g) * unc[v]);   // diffusion.py:124-125
+            if constexpr (MASK) x0 = m[v] * x0 + (1.0f - m[v]) * z[v];
+            if (ch == 3) x0 += p.sharp;                                   // diffusion.py:88
+            if (ch == 0) x0 += p.bright;                                  // diffusion.py:89
+            x0o[v] = x0;
+        }
+        store(p.x0_out + i, x0o);
+        return;
+    }
+    load(prev, p.x0_prev + i);
+    load(xin, p.x_t + i);
+    if constexpr (MASK) load(eps, q.noise + i);
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+        const float x0 = __builtin_fmaf(p.g, cond[v], (1.0f - p.g) * unc[v]);
+        const float D = __builtin_fmaf(p.c1, x0, -(p.c2 * prev[v]));      // diffusion.py:76 (c1=1,c2=0: :72/:79)
+        float xt = (p.a * D + p.b * xin[v]) / p.c;                        // diffusion.py:81
+        if constexpr (MASK) {
+            const float known = q.s_next * eps[v] + (1.0f - q.s_next) * z[v];
+            xt = m[v] * xt + (1.0f - m[v]) * known;
+        }
+        x0o[v] = x0;
+        xto[v] = xt;
+    }
+    store(p.x0_out + i, x0o);
+    if (p.trace_x0) store(p.trace_x0 + i, x0o);
+    store(p.x_t + i, xto);
+    store(p.x0_prev + i, x0o);
+    if (p.trace_xt) store(p.trace_xt + i, xto);
+}
+
+// x_start = s0 eps + (1 - s0) z0: the forward process at the first remaining level (tld/train.py:130)
+template <int V>
+__global__ __launch_bounds__(256) void start_mix_kernel(const float* __restrict__ noise, const float* __restrict__ z0, float s0,
+                                                        float* __restrict__ x_t, int n) {
+#pragma clang fp contract(off)
+    const int i = (blockIdx.x * 256 + threadIdx.x) * V;
+    if (i >= n) return;
+    if constexpr (V == 4) {
+        const float4 e = *reinterpret_cast<const float4*>(noise + i), z = *reinterpret_cast<const float4*>(z0 + i);
+        const float t = 1.0f - s0;
+        *reinterpret_cast<float4*>(x_t + i) = make_float4(s0 * e.x + t * z.x, s0 * e.y + t * z.y, s0 * e.z + t * z.z, s0 * e.w + t * z.w);
+    } else {
+        x_t[i] = s0 * noise[i] + (1.0f - s0) * z0[i];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Depthwise 3x3 + bias + exact GELU.  One workgroup = one sample x 64 channels: the whole g x g image
 // slab (g*g tokens x 128 B) is pulled into LDS once with 16-B coalesced loads, so HBM/L2 see every input
 // exactly once (the register-window version re-read each row three times through L2).  Thread (row i,
@@ -1411,6 +1498,34 @@ void launch_tail(const TailParams& p, hipStream_t s) {
 void launch_update(const UpdateParams& p, hipStream_t s) {
     const int n = p.batch * p.img;
     hipLaunchKernelGGL(update_kernel, dim3((n + 255) / 256), dim3(256), 0, s, p);
+}
+
+namespace {
+bool aligned16(const void* a) { return (reinterpret_cast<uintptr_t>(a) & 15) == 0; }
+}
+
+void launch_update_from(const UpdateFromParams& q, hipStream_t s) {
+    const UpdateParams& p = q.u;
+    const int n = p.batch * p.img;
+    // 16-byte accesses: four consecutive elements then share a sample, a channel and one aligned mask quad (null pointers count as aligned)
+    const bool vec = p.img % 4 == 0 && p.chan_stride % 4 == 0 && aligned16(p.x0_2b) && aligned16(p.x_t) && aligned16(p.x0_prev) && aligned16(p.x0_out) &&
+                     aligned16(p.trace_x0) && aligned16(p.trace_xt) && aligned16(q.noise) && aligned16(q.z0) && aligned16(q.mask);
+    const int threads = vec ? n / 4 : n;
+    const dim3 grid((threads + 255) / 256), block(256);
+    if (q.mask) {
+        if (vec) hipLaunchKernelGGL((update_from_kernel<true, 4>), grid, block, 0, s, q);
+        else hipLaunchKernelGGL((update_from_kernel<true, 1>), grid, block, 0, s, q);
+    } else {
+        if (vec) hipLaunchKernelGGL((update_from_kernel<false, 4>), grid, block, 0, s, q);
+        else hipLaunchKernelGGL((update_from_kernel<false, 1>), grid, block, 0, s, q);
+    }
+}
+
+void launch_start_mix(const float* noise, const float* z0, float s0, float* x_t, int n, hipStream_t s) {
+    if (n % 4 == 0 && aligned16(noise) && aligned16(z0) && aligned16(x_t))
+        hipLaunchKernelGGL((start_mix_kernel<4>), dim3((n / 4 + 255) / 256), dim3(256), 0, s, noise, z0, s0, x_t, n);
+    else
+        hipLaunchKernelGGL((start_mix_kernel<1>), dim3((n + 255) / 256), dim3(256), 0, s, noise, z0, s0, x_t, n);
 }
 
 // Streaming form of the same computation for grids that are a multiple of 32 wide (512 / 1024 px latents; round 3): one workgroup =

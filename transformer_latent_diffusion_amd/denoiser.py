@@ -254,6 +254,44 @@ class Denoiser:
                 C.c_void_p(stream)), "tld_sample")
         return (out, tx0, txt) if trace else out
 
+    @torch.no_grad()
+    def sample_latents_from(self, noise: torch.Tensor, init_latents: torch.Tensor, labels: torch.Tensor, coeffs: np.ndarray,
+                            class_guidance: float, start_mix: float, mask: Optional[torch.Tensor] = None, sharp_f: float = 0.0,
+                            bright_f: float = 0.0, trace: bool = False):
+        """On-device CFG sampler for image-to-image and inpainting (tld_sample_from): the trajectory starts at
+        ``start_mix * noise + (1 - start_mix) * init_latents`` (``start_mix = 1.0``: at ``noise`` itself) and runs the levels of ``coeffs``
+        (the remaining ones, ``schedule.truncate_levels``); with ``mask`` [B,1,S,S] in [0,1] (1 = regenerate) the kept region is re-imposed
+        after every step and on the final prediction.  Returns fp32 latent [B,C,S,S] (+ traces)."""
+        dev = self._resolve_device(noise)
+        B = noise.shape[0]
+        if tuple(init_latents.shape) != tuple(noise.shape):
+            raise ValueError(f"init_latents {tuple(init_latents.shape)} != noise {tuple(noise.shape)}")
+        if mask is not None and tuple(mask.shape) != (B, 1) + tuple(noise.shape[2:]):
+            raise ValueError(f"mask {tuple(mask.shape)}: expected {(B, 1) + tuple(noise.shape[2:])}")
+        if B == 0:
+            z = torch.empty_like(noise, dtype=torch.float32)
+            return (z, None, None) if trace else z
+        h = self._ensure_engine(2 * B, dev)
+        eps = noise.to(device=dev, dtype=torch.float32).contiguous()
+        z0 = init_latents.to(device=dev, dtype=torch.float32).contiguous()
+        m = mask.to(device=dev, dtype=torch.float32).contiguous() if mask is not None else None
+        lab = labels.to(device=dev, dtype=torch.float32).contiguous()
+        co = np.ascontiguousarray(coeffs, dtype=np.float32)
+        n_levels = co.shape[0]
+        out = torch.empty_like(eps)
+        tx0 = txt = None
+        if trace:
+            tx0 = torch.empty((n_levels - 1,) + tuple(eps.shape), device=dev, dtype=torch.float32)
+            txt = torch.empty_like(tx0)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().tld_sample_from(
+                h, eps.data_ptr(), z0.data_ptr(), C.c_void_p(m.data_ptr() if m is not None else None), float(start_mix), lab.data_ptr(),
+                co.ctypes.data_as(C.POINTER(C.c_float)), n_levels, float(class_guidance), float(sharp_f), float(bright_f), out.data_ptr(), B,
+                C.c_void_p(tx0.data_ptr() if trace else None), C.c_void_p(txt.data_ptr() if trace else None),
+                C.c_void_p(stream)), "tld_sample_from")
+        return (out, tx0, txt) if trace else out
+
     # ---- test / bench hooks -----------------------------------------------------------------------------
     def set_debug(self, enable: bool = True):
         _lib.check(_lib.lib().tld_engine_set_debug(self._engine, int(enable)), "tld_engine_set_debug")

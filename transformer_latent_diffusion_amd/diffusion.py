@@ -78,6 +78,63 @@ class DiffusionGenerator:
             return lat.to(self.model_dtype), tx0, txt
         return out.to(self.model_dtype)
 
+    @torch.no_grad()
+    def generate_from(self, init_latents: Tensor, labels: Tensor, strength: float = 0.6, mask: Optional[Tensor] = None, n_iter: int = 30,
+                      num_imgs: Optional[int] = None, class_guidance: float = 3, seed: int = 10, scale_factor: int = 8,
+                      img_size: Optional[int] = None, sharp_f: float = 0.1, bright_f: float = 0.1, exponent: float = 1,
+                      seeds: Optional[Tensor] = None, noise_levels=None, use_ddpm_plus: bool = True):
+        """``generate`` for image-to-image and inpainting (``generate_latents_from``); returns (decoded_images_on_cpu, latents)."""
+        latents = self.generate_latents_from(init_latents, labels, strength, mask, n_iter, num_imgs, class_guidance, seed, img_size,
+                                             sharp_f, bright_f, exponent, seeds, noise_levels, use_ddpm_plus)
+        if self.vae is None:
+            return None, latents
+        img = self.vae.decode((latents * scale_factor).to(self.model_dtype))[0].cpu()
+        return img, latents
+
+    @torch.no_grad()
+    def generate_latents_from(self, init_latents, labels, strength=0.6, mask=None, n_iter=30, num_imgs=None, class_guidance=3, seed=10,
+                              img_size=None, sharp_f=0.1, bright_f=0.1, exponent=1, seeds=None, noise_levels=None, use_ddpm_plus=True,
+                              trace=False):
+        """Reverse diffusion that starts from ``init_latents`` [B,C,S,S] (model space: VAE latent / scale_factor, tld/train.py:122)
+        instead of pure noise; the other arguments are ``generate_latents``' (``num_imgs`` / ``img_size`` default to the latents' own).
+
+        ``strength`` in (0, 1] picks the entry point of the schedule (``schedule.truncate_levels``): the latents are noised to the first
+        level ``<= strength`` with the training loop's forward process, ``s * eps + (1 - s) * z0`` (tld/train.py:130), ``eps`` being the
+        noise ``generate_latents`` would start from for the same ``seed`` / ``seeds``; 1.0 is the text-to-image trajectory, bit for bit.
+        ``mask`` [B,1,S,S] in [0,1] at latent resolution (1 = regenerate, 0 = keep): after every step the kept region is set to the same
+        forward process of ``init_latents`` at that step's level, and to ``init_latents`` itself in the final prediction (exactly, where
+        the mask is 0).  Shapes and ranges are checked on the host before anything is enqueued."""
+        if init_latents.dim() != 4:
+            raise ValueError(f"init_latents {tuple(init_latents.shape)}: expected [B,C,S,S]")
+        B, C_, S = init_latents.shape[0], init_latents.shape[1], init_latents.shape[-1]
+        num_imgs = B if num_imgs is None else num_imgs
+        img_size = S if img_size is None else img_size
+        want = (num_imgs, self.model.n_channels, img_size, img_size) if seeds is None else tuple(seeds.shape)
+        if tuple(init_latents.shape) != want:
+            raise ValueError(f"init_latents {tuple(init_latents.shape)} do not match the noise {want}")
+        if labels.size(0) != B:
+            raise ValueError(f"labels batch {labels.size(0)} != init_latents batch {B}")
+        if mask is not None:
+            if tuple(mask.shape) != (B, 1, img_size, img_size):
+                raise ValueError(f"mask {tuple(mask.shape)}: expected {(B, 1, img_size, img_size)} (latent resolution; see latent_mask)")
+            if mask.numel():
+                lo, hi = float(mask.min()), float(mask.max())
+                if not (lo >= 0.0 and hi <= 1.0):
+                    raise ValueError(f"mask values span [{lo}, {hi}]: expected [0, 1] (1 = regenerate, 0 = keep)")
+        full = schedule.noise_schedule(n_iter, exponent, noise_levels)
+        k, levels = schedule.truncate_levels(full, strength)
+        coeffs = schedule.step_coefficients(levels, use_ddpm_plus)
+        start_mix = float(np.float32(levels[0])) if k > 0 else 1.0      # k = 0: pure noise at the first level, as the reference feeds it (diffusion.py:52,59)
+        eps = self.initialize_image(seeds, num_imgs, img_size, seed)
+        self.model.eval()
+        out = self.model.sample_latents_from(eps, init_latents.to(self.device), labels.to(self.device), coeffs, class_guidance, start_mix,
+                                             mask=None if mask is None else mask.to(self.device), sharp_f=sharp_f, bright_f=bright_f,
+                                             trace=trace)
+        if trace:
+            lat, tx0, txt = out
+            return lat.to(self.model_dtype), tx0, txt
+        return out.to(self.model_dtype)
+
     def initialize_image(self, seeds, num_imgs, img_size, seed):
         """Initial noise (diffusion.py:105-120): the caller's ``seeds`` tensor, or ``torch.randn`` from a
         generator seeded with ``seed``.
@@ -119,6 +176,27 @@ def make_image_grid(images: Tensor, nrow: int, padding: int = 4) -> Tensor:
         y0, x0 = r * (h + padding) + padding, q * (w + padding) + padding
         grid[:, y0:y0 + h, x0:x0 + w] = images[k]
     return grid
+
+
+def latent_mask(mask, latent_size: int) -> Tensor:
+    """Pixel-resolution inpainting mask -> latent resolution by area averaging: a PIL "L" image (0..255) or a tensor [H,W] / [1,H,W] in
+    [0,1], square, with H a multiple of ``latent_size``; returns fp32 [1, latent_size, latent_size] in [0,1] (1 = regenerate).  A latent
+    cell is kept exactly (0) only where every pixel under it is 0."""
+    if not isinstance(mask, Tensor):
+        arr = np.array(mask.convert("L") if hasattr(mask, "convert") else mask)
+        mask = torch.from_numpy(arr).to(torch.float32) / (255.0 if arr.dtype == np.uint8 else 1.0)
+    m = mask.detach().to(torch.float32)
+    if m.dim() == 3 and m.shape[0] == 1:
+        m = m[0]
+    if m.dim() != 2 or m.shape[0] != m.shape[1]:
+        raise ValueError(f"mask {tuple(mask.shape)}: expected a square [H,W] or [1,H,W]")
+    H = m.shape[0]
+    if latent_size <= 0 or H % latent_size:
+        raise ValueError(f"mask side {H} is not a multiple of the latent size {latent_size}")
+    if m.numel() and not (float(m.min()) >= 0.0 and float(m.max()) <= 1.0):
+        raise ValueError(f"mask values span [{float(m.min())}, {float(m.max())}]: expected [0, 1]")
+    f = H // latent_size
+    return m.reshape(latent_size, f, latent_size, f).mean(dim=(1, 3)).clamp_(0.0, 1.0).unsqueeze(0)
 
 
 def to_pil(img: Tensor):
@@ -223,6 +301,46 @@ class DiffusionTransformer:
         return to_pil(make_image_grid((out + 1) / 2, nrow=nrow, padding=4).float().clip(0, 1))
 
 
+    @torch.no_grad()
+    def generate_image_from_image(self, image, prompt: str, strength=0.6, mask=None, class_guidance=6, seed=11, n_iter=15,
+                                  sample_posterior=False, return_latents=False):
+        """Image -> image: edit ``image`` towards ``prompt`` at ``strength``, or with ``mask`` regenerate only the masked region.
+
+        ``image``: a PIL image or a [3,H,W] tensor in [0,1] with H = W = 8 x the model's latent size (no resizing here).  It is encoded
+        with the pipeline's VAE (``vae.encode(2 x - 1).latent_dist``: ``.mode()``, or ``.sample()`` from a generator seeded with ``seed``
+        when ``sample_posterior``) and divided by 8 (tld/train.py:122).  ``mask``: PIL "L" image or tensor [H,W] / [1,H,W] at pixel
+        resolution, 1 = regenerate; it is area-averaged to the latent grid (``latent_mask``), so only latent cells whose 8 x 8 pixels are
+        all 0 are kept exactly.  Sampler settings as in ``generate_image_from_text``.  Returns a PIL image (with ``return_latents``:
+        (image, latents))."""
+        gen = self.diffuser
+        size = gen.model.image_size
+        if not isinstance(image, Tensor):
+            if not hasattr(image, "convert"):
+                raise ValueError("image: expected a PIL image or a [3,H,W] tensor in [0,1]")
+            image = torch.from_numpy(np.asarray(image.convert("RGB")).copy()).permute(2, 0, 1).to(torch.float32) / 255.0
+        if image.dim() != 3 or tuple(image.shape) != (3, 8 * size, 8 * size):
+            raise ValueError(f"image {tuple(image.shape)}: expected [3, {8 * size}, {8 * size}] (8 x the model's {size} x {size} latents)")
+        if image.numel() and not (float(image.min()) >= 0.0 and float(image.max()) <= 1.0):
+            raise ValueError("image values outside [0, 1]")
+        m = None
+        if mask is not None:
+            side = mask.size[0] if hasattr(mask, "convert") else mask.shape[-1]
+            if side != 8 * size:
+                raise ValueError(f"mask side {side}: expected the image's {8 * size}")
+            m = latent_mask(mask, size).unsqueeze(0)
+        labels = self.encode_text([prompt])
+        x = (image.to(self.device, torch.float32) * 2 - 1).unsqueeze(0)
+        x = x.to(getattr(gen.vae, "dtype", torch.float32))
+        dist_ = gen.vae.encode(x).latent_dist
+        if sample_posterior:
+            z = dist_.sample(generator=torch.Generator(device="cpu").manual_seed(int(seed)))
+        else:
+            z = dist_.mode()
+        z0 = z.to(torch.float32) / 8
+        out, latents = gen.generate_from(z0, labels, strength=strength, mask=m, n_iter=n_iter, class_guidance=class_guidance, seed=seed,
+                                         exponent=1, scale_factor=8, sharp_f=0, bright_f=0)
+        pic = to_pil(((out[0] + 1) / 2).float().clip(0, 1))
+        return (pic, latents) if return_latents else pic
 
 class RequestBatcher:
     """Groups text-to-image requests into batched sampler calls (serving-side batching; the reference's FastAPI

@@ -13,7 +13,7 @@ the tensor dtype when it meets the tensor; ``step_coefficients`` performs exactl
 from __future__ import annotations
 
 import math
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -85,6 +85,24 @@ def noise_schedule(n_iter: int, exponent: float = 1.0,
         levels = [float(v) for v in noise_levels]
     levels[0] = 0.99
     return levels
+
+
+def truncate_levels(levels: Sequence[float], strength: float) -> Tuple[int, List[float]]:
+    """Where an image-to-image trajectory enters the schedule: ``(k, levels[k:])`` with ``k`` the smallest index whose level is
+    ``<= strength``.  ``strength`` in (0, 1]: 1.0 keeps the whole schedule (``k = 0``, the text-to-image trajectory), a small value
+    keeps only its low-noise tail.  The initial latent is noised to ``levels[k]`` with the training loop's forward process
+    (tld/train.py:130) and the remaining steps run unchanged, the first of them first-order (``step_coefficients`` of the tail).
+
+    Raises ValueError for a strength outside (0, 1], below every level, or leaving fewer than the two levels a trajectory needs."""
+    s = float(strength)
+    if not (0.0 < s <= 1.0):
+        raise ValueError(f"strength {strength!r} outside (0, 1]")
+    lv = [float(v) for v in levels]
+    k = next((i for i, v in enumerate(lv) if v <= s), None)
+    if k is None or len(lv) - k < 2:
+        raise ValueError(f"strength {s} leaves {0 if k is None else len(lv) - k} of {len(lv)} noise levels; a trajectory needs two "
+                         f"(lowest levels: {lv[-2:]})")
+    return k, lv[k:]
 
 
 def multistep_ratios(noise_levels: Sequence[float]) -> List[float]:

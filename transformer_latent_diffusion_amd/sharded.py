@@ -13,7 +13,7 @@ capability behind the unchanged ``DiffusionGenerator`` contract.
 """
 from __future__ import annotations
 
-from typing import Callable, Optional, Tuple
+from typing import Callable, Optional, Sequence, Tuple
 
 import torch
 import torch.distributed as dist
@@ -26,19 +26,24 @@ def shard_bounds(total: int, world: int, rank: int) -> Tuple[int, int]:
     return lo, lo + base + (1 if rank < rem else 0)
 
 
-def sharded_sample(sample_fn: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], x_T: torch.Tensor,
-                   labels: torch.Tensor, group: Optional[dist.ProcessGroup] = None) -> torch.Tensor:
-    """Run ``sample_fn(x_T_shard, labels_shard) -> latents_shard`` on this rank's slice and all-gather.
+def sharded_sample(sample_fn: Callable[..., torch.Tensor], x_T: torch.Tensor,
+                   labels: torch.Tensor, group: Optional[dist.ProcessGroup] = None, extras: Sequence[Optional[torch.Tensor]] = ()) -> torch.Tensor:
+    """Run ``sample_fn(x_T_shard, labels_shard, *extras_shards) -> latents_shard`` on this rank's slice and all-gather.
 
-    ``x_T`` [B,C,S,S] and ``labels`` [B,text] are the FULL batch, identical on every rank.
+    ``x_T`` [B,C,S,S] and ``labels`` [B,text] are the FULL batch, identical on every rank; ``extras`` are further per-sample tensors
+    (leading dimension B: initial latents, masks) sliced with the same bounds -- a ``None`` entry is passed through as ``None``.
     Returns the full [B,C,S,S] latents on every rank.
     """
+    extras = tuple(extras)
+    for t in extras:
+        if t is not None and t.shape[0] != x_T.shape[0]:
+            raise ValueError(f"extras: a tensor of {t.shape[0]} samples beside x_T of {x_T.shape[0]}")
     if not (dist.is_available() and dist.is_initialized()):
-        return sample_fn(x_T, labels)
+        return sample_fn(x_T, labels, *extras)
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     B = x_T.shape[0]
     lo, hi = shard_bounds(B, world, rank)
-    mine = sample_fn(x_T[lo:hi], labels[lo:hi]) if hi > lo else x_T.new_zeros((0,) + tuple(x_T.shape[1:]))
+    mine = sample_fn(x_T[lo:hi], labels[lo:hi], *(None if t is None else t[lo:hi] for t in extras)) if hi > lo else x_T.new_zeros((0,) + tuple(x_T.shape[1:]))
     mine = mine.contiguous()
     home = mine.device
     if dist.get_backend(group) == "gloo" and mine.is_cuda:
@@ -75,3 +80,23 @@ def generate_latents_sharded(gen, labels: torch.Tensor, n_iter: int = 30, num_im
                                     use_ddpm_plus=use_ddpm_plus)
 
     return sharded_sample(one, x_T, labels.to(x_T.device), group)
+
+
+def generate_latents_from_sharded(gen, init_latents: torch.Tensor, labels: torch.Tensor, strength: float = 0.6,
+                                  mask: Optional[torch.Tensor] = None, n_iter: int = 30, num_imgs: Optional[int] = None,
+                                  class_guidance: float = 3, seed: int = 10, img_size: Optional[int] = None, sharp_f: float = 0.1,
+                                  bright_f: float = 0.1, exponent: float = 1, seeds: Optional[torch.Tensor] = None, noise_levels=None,
+                                  use_ddpm_plus: bool = True, group: Optional[dist.ProcessGroup] = None) -> torch.Tensor:
+    """``DiffusionGenerator.generate_latents_from`` over all ranks of ``group`` (same arguments): every sample's noise, initial latent
+    and mask travel to the rank that owns the sample."""
+    num_imgs = init_latents.shape[0] if num_imgs is None else num_imgs
+    img_size = init_latents.shape[-1] if img_size is None else img_size
+    eps = gen.initialize_image(seeds, num_imgs, img_size, seed)     # full batch, same on every rank
+
+    def one(eps_shard, lab_shard, z0_shard, mask_shard):
+        return gen.generate_latents_from(z0_shard, lab_shard, strength=strength, mask=mask_shard, n_iter=n_iter,
+                                         num_imgs=eps_shard.shape[0], class_guidance=class_guidance, seed=seed, img_size=img_size,
+                                         sharp_f=sharp_f, bright_f=bright_f, exponent=exponent, seeds=eps_shard,
+                                         noise_levels=noise_levels, use_ddpm_plus=use_ddpm_plus)
+
+    return sharded_sample(one, eps, labels.to(eps.device), group, extras=(init_latents, mask))
