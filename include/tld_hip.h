@@ -132,12 +132,53 @@ TLD_API int tld_sample_from(tld_engine* e, const void* noise, const void* init_l
                const float* coeffs, int32_t n_levels, float class_guidance, float sharp_f, float bright_f, void* out_latent,
                int32_t batch, void* trace_x0, void* trace_xt, void* hip_stream);
 
-/* Test hook: copy a named internal stage of the LAST forward to host fp32 (synchronises).
- * names: "cond_y" [T,d] (T = batch noise rows then batch label rows), "tokens0", "blk0_sa",
- * "blk0_ca", "blk0_mlp", "tokens_final" (each [batch*N, d]).  Stage capture must have been
- * enabled with tld_engine_set_debug(e, 1) before the forward. */
+/* Test hook: stage capture of the inference forward (what tld_train_set_debug is to the training step).  With debug on, a forward
+ * (tld_denoiser_forward, or every step of tld_sample / tld_sample_from)
+ *   - first fills every engine-owned activation, statistics, seam and split-K buffer -- and, once per call, the conditioning tables -- with 0xFF bytes
+ *     (NaN in bf16 and fp32), so that a kernel that stores nothing, or too few rows, shows as NaN instead of the previous call's values;
+ *   - keeps every stage of every block: device-to-device copies on the same stream, right after the kernel that completes the value, in the stored
+ *     type (bf16 or fp32; converted to fp32 on read).  Snapshot memory (for max_batch samples) is allocated by set_debug(1), which fails cleanly
+ *     (TLD_ERR_HIP, debug stays off) if it cannot be had, and freed by set_debug(0) / destroy; a forward allocates nothing.  Call set_debug(1) after
+ *     tld_engine_set_low_latency;
+ *   - records which launch path every size-dependent dispatch took (tld_engine_debug_paths).
+ * With debug off nothing is launched, copied or allocated for the hook, and the outputs are bitwise the same.  A debug call on a capturing stream is
+ * refused (TLD_ERR_STATE).  CFG layer-0 sharing stays on under debug: in a sampler step block 0's stages up to `att` hold the un-doubled batch.
+ *
+ * Stage names (i = block index; M = batch * tokens, Mi = the rows block i's first half runs on: src_batch * tokens for block 0 of a sampler step):
+ *   tokens0 [Mi, d]; blk<i>.x_in [Mi, d] (the residual stream entering the block), blk<i>.ln1 [Mi, 8, 2] (the (sum, sum of squares) partial sums the
+ *   LayerNorm-1 fold reads: the first 2 slots in block 0, d / 96 later; the others keep the poison) or blk<i>.xn1 [Mi, d] without the fold,
+ *   blk<i>.qk [Mi, 2 d] and blk<i>.vt [samples, d, tokens] on the two-kernel path, blk<i>.att [Mi, d], blk<i>.sa [M, d] (x + att, fp32), blk<i>.ca
+ *   [M, d], blk<i>.stats [M, 2] ((mean, rstd) of the stored row) or blk<i>.xn3 [M, d] without the LayerNorm-3 fold, blk<i>.hid_pre [M, hid] where
+ *   the up-projection's output exists in HBM, blk<i>.hid [M, hid], blk<i>.splitk [splits, M, d] in the low-latency classes, blk<i>.mlp [M, d];
+ *   out [batch, C S S] (the forward's output before any I/O cast); of a sampler's debug step: step.x_t, step.x0_prev (its inputs), step.out
+ *   [2 B, C S S], step.x0, step.x_next (absent at the last step);
+ *   conditioning, read in place: cond.sin [Tn, noise_embed_dims], cond.h1 [Tn, d] (the Tn noise rows: sinusoid features, GELU(ff1)), cond.pre, cond.y [T, d] (T token rows: noise rows, then label rows), cond.kv [L, T, 2 d], cond.wq [L, T, H, d],
+ *   cond.bwq [L, T, H];
+ *   operands as the engine holds them, read in place, in logical [N][K] order (the fused QKV -> attention kernel's row packing is undone on read):
+ *   blk<i>.wqkv [3 d, d], blk<i>.wup [hid, d] (gamma-scaled under the LayerNorm folds), blk<i>.wdown [d, hid], and the folds' vectors
+ *   blk<i>.qkv_c1, blk<i>.qkv_b1 [3 d], blk<i>.up_c1, blk<i>.up_b1 [hid].
+ *   The first hook's names stay as aliases: cond_y, tokens0, blk0_sa, blk0_ca, blk0_mlp, tokens_final, blk0_hid, blk0_hid_pre.
+ * Launch-path bits of tld_engine_debug_paths (bit number : path):
+ *    0 embed plain   1-4 embed_mfma<2 | 4 | 6 | 8>   5-8 layernorm q4<1..4>   9 layernorm generic   10 layernorm mx8 (fp8 mode)
+ *   11 QKV fused with attention   12 QKV with the LayerNorm-1 fold   13 QKV plain
+ *   14 attention 256 tokens   15 chunked (k 256 tokens)   17 64 tokens   19 masked (any other count)   (16, 18 unused: no square token grid has 128 / 32 tokens)
+ *   20-23 cross_row_mfma<1..4>   24 ... with one 16-row group per workgroup   25 ... with more   26 cross_row VALU   27 the x_in fan-out (layer-0 sharing)
+ *   28 up-projection fused with the depthwise conv, 16 x 16   29 ... 32 x 32 plus the seam kernel   30 ... 16 x 16, the 4-wave small-launch form
+ *   31 up-projection alone   32 depthwise whole image   33 tiled   34 streaming
+ *   35 down projection writing LayerNorm-1 partial sums   36 ... not writing them (last block, or no fold)   37 down projection, 8-wave kernel
+ *   38 4-wave form, 64-row tiles   39 4-wave form, 128-row tiles   40 split-K x 4   41 split-K x 8   42 split-K 4-wave form
+ *   43 split-K finisher <12> (d 768)   44 <6> (d 384)   45-48 tail_mfma<1..4>   49 tail plain
+ *   50 update   51 update_from without a mask   52 update_from with a mask   53 start_mix */
+#define TLD_ENGINE_PATH_BITS 54
 TLD_API int tld_engine_set_debug(tld_engine* e, int32_t enable);
+/* host_out fp32 [numel]; numel must match the stage (TLD_ERR_SHAPE otherwise).  Synchronises the device. */
 TLD_API int tld_engine_read_stage(tld_engine* e, const char* name, float* host_out, int64_t numel);
+/* logical shape of a captured stage: 4 int64, unused trailing dimensions 1 */
+TLD_API int tld_engine_stage_shape(tld_engine* e, const char* name, int64_t* shape4);
+/* sampler step (0-based) whose stages a debug tld_sample / tld_sample_from keeps; negative (the default): every step, so the last one remains */
+TLD_API int tld_engine_set_debug_step(tld_engine* e, int32_t step);
+/* mask of the launch paths the last debug call took */
+TLD_API int tld_engine_debug_paths(tld_engine* e, uint64_t* mask);
 
 /* Test hook: C[M,N] = A[M,K] . W[N,K]^T with the engine's bf16 MFMA GEMM (fp32 accumulate), bf16
  * device inputs, fp32 device output.  K % 64 == 0.  Refused (TLD_ERR_INVALID, nothing launched) when an operand row

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Dump the g5 forward and a 70-sample forward of the engine library selected by TLD_LIB (same-box A/B of builds: outputs of two builds that only re-order work
+"""Dump the g5 forward, a 70-sample forward and the g5 35-step CFG end latent of the engine library selected by TLD_LIB (same-box A/B of builds: outputs of two builds that only re-order work
 must be BITWISE equal).   TLD_LIB=<lib.so> python tools/lib_ab_check.py out.npy"""
 import os, sys
 from dataclasses import asdict
@@ -19,4 +19,9 @@ x = rng.standard_normal((70, 4, 32, 32)).astype(np.float32); s = rng.uniform(0.0
 lab = (rng.standard_normal((70, 768)) * 0.5).astype(np.float32)
 big = m(t(x), t(s), t(lab)).cpu().numpy()
 print(os.path.basename(os.environ.get("TLD_LIB", "default")), "g5 forward rel-rms", rel_rms(out, g["x0"]), "finite", bool(np.isfinite(big).all()))
-np.save(sys.argv[1], np.concatenate([out.reshape(-1), big.reshape(-1)]))
+from transformer_latent_diffusion_amd import DiffusionGenerator
+lat = DiffusionGenerator(m, None, dev, torch.float32).generate_latents(torch.from_numpy(g["traj_labels"]), n_iter=int(g["traj_n_iter"]), num_imgs=1,
+                                                                       class_guidance=float(g["traj_class_guidance"]), seeds=torch.from_numpy(g["traj_seeds"]),
+                                                                       img_size=32, sharp_f=0.0, bright_f=0.0).cpu().numpy()
+print("g5 35-step end latent rel-rms", rel_rms(lat, g["traj_latent"]))
+np.save(sys.argv[1], np.concatenate([out.reshape(-1), big.reshape(-1), lat.reshape(-1)]))

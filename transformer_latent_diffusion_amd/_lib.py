@@ -21,7 +21,7 @@ KERNEL_CLASSES = ("gemm_qkv", "gemm_up", "gemm_down", "attention", "cross_row", 
 ABI_SYMBOLS = (
     "tld_engine_create", "tld_engine_load_tensor", "tld_engine_finalize_weights", "tld_denoiser_forward",
     "tld_sample", "tld_sample_from", "tld_engine_set_gemm_dtype", "tld_engine_set_low_latency", "tld_debug_gemm_splitk", "tld_debug_quant_mx8", "tld_debug_quant_mx8_host", "tld_debug_gemm_mx8",
-    "tld_engine_set_debug", "tld_engine_read_stage", "tld_debug_gemm_bf16", "tld_debug_gemm_bench", "tld_debug_gemm_plan", "tld_debug_gemm_epilogue",
+    "tld_engine_set_debug", "tld_engine_read_stage", "tld_engine_stage_shape", "tld_engine_set_debug_step", "tld_engine_debug_paths", "tld_debug_gemm_bf16", "tld_debug_gemm_bench", "tld_debug_gemm_plan", "tld_debug_gemm_epilogue",
     "tld_engine_set_profile", "tld_engine_profile_reserve", "tld_engine_get_profile", "tld_engine_weight_bytes", "tld_engine_destroy",
     "tld_vae_create", "tld_vae_load_tensor", "tld_vae_finalize_weights", "tld_vae_decode", "tld_vae_set_debug",
     "tld_vae_read_stage", "tld_vae_set_profile", "tld_vae_get_profile", "tld_debug_conv3x3", "tld_vae_weight_bytes",
@@ -119,6 +119,10 @@ def lib() -> C.CDLL:
     L.tld_debug_gemm_mx8.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp]
     L.tld_engine_set_debug.argtypes = [vp, i32]
     L.tld_engine_read_stage.argtypes = [vp, C.c_char_p, C.POINTER(C.c_float), C.c_int64]
+    if hasattr(L, "tld_engine_stage_shape"):         # (absent from A/B builds that predate the per-block stage hook)
+        L.tld_engine_stage_shape.argtypes = [vp, C.c_char_p, i64p]
+        L.tld_engine_set_debug_step.argtypes = [vp, i32]
+        L.tld_engine_debug_paths.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.tld_debug_gemm_bf16.argtypes = [vp, vp, vp, i32, i32, i32, vp]
     L.tld_debug_gemm_bench.argtypes = [i32, i32, i32, i32, i32, i32, C.POINTER(C.c_double)]
     if hasattr(L, "tld_debug_gemm_plan"):            # (absent from A/B builds that predate it)

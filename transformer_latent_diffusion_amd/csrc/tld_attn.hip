@@ -843,12 +843,13 @@ void launch_attention(const bf16* qk, const bf16* vt, bf16* att, int batch, int 
     // 256 tokens: two unsynchronised 4-wave workgroups per CU, each staging its (sample, head)'s K / V^T once (attn1_kernel; the single
     // 8-wave workgroup it replaced took 60 us against 44 at C1).  512+ tokens: the chunked two-query-tile kernel (attn2_kernel).
     // (At the C1 shape the inference engine no longer comes here: its self-attention runs in the QKV GEMM's epilogue, EPI_QKV_ATTN.)
-    if (ntok == 256) launch_attn1<8, 4, 2, true>(qk, vt, att, batch, ntok, heads, s);
-    else if (ntok % 256 == 0) launch_attn2(qk, vt, att, batch, ntok, heads, s);
-    else if (ntok == 128) launch_kt<4, 4>(qk, vt, att, batch, ntok, heads, s);
-    else if (ntok == 64) launch_kt<2, 2>(qk, vt, att, batch, ntok, heads, s);
-    else if (ntok == 32) launch_kt<1, 1>(qk, vt, att, batch, ntok, heads, s);
-    else launch_masked(qk, vt, att, batch, ntok, heads, s);       // any other multiple of 8 (tld_engine_create checks)
+    // (128 and 32 tokens carry no launch-path bit: no square token grid has them, only tld_debug_attention_fwd comes here with those counts)
+    if (ntok == 256) { note_path(EP_ATT_256); launch_attn1<8, 4, 2, true>(qk, vt, att, batch, ntok, heads, s); }
+    else if (ntok % 256 == 0) { note_path(EP_ATT_CHUNKED); launch_attn2(qk, vt, att, batch, ntok, heads, s); }
+    else if (ntok == 128) { launch_kt<4, 4>(qk, vt, att, batch, ntok, heads, s); }
+    else if (ntok == 64) { note_path(EP_ATT_64); launch_kt<2, 2>(qk, vt, att, batch, ntok, heads, s); }
+    else if (ntok == 32) { launch_kt<1, 1>(qk, vt, att, batch, ntok, heads, s); }
+    else { note_path(EP_ATT_MASKED); launch_masked(qk, vt, att, batch, ntok, heads, s); }      // any other multiple of 8 (tld_engine_create checks)
 }
 
 }  // namespace tld

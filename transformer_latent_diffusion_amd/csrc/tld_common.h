@@ -301,6 +301,23 @@ inline int device_cu_count() {
     return c;
 }
 
+// ---- launch-path record of the engine's stage hook (tld_engine_debug_paths; the table in include/tld_hip.h) -------------------------------
+// Each bit is set inside the branch that launches the kernel.  The sink is null unless a debug forward of an engine runs on this thread: with
+// debug off a launch costs one thread-local load and a not-taken branch.
+enum : int {
+    EP_EMBED_PLAIN = 0, EP_EMBED_MFMA = 1 /* +0..3: TPW 2, 4, 6, 8 */, EP_LN_Q4 = 5 /* +0..3: q4<1..4> */, EP_LN_GENERIC = 9, EP_LN_MX8 = 10,
+    EP_QKV_ATTN = 11, EP_QKV_LN = 12, EP_QKV_PLAIN = 13,
+    EP_ATT_256 = 14, EP_ATT_CHUNKED = 15, EP_ATT_64 = 17 /* 16, 18: unused (128 / 32 tokens: no square grid) */, EP_ATT_MASKED = 19,
+    EP_CROSS_MFMA = 20 /* +0..3: NQ 1..4 */, EP_CROSS_GPW1 = 24, EP_CROSS_GPWN = 25, EP_CROSS_VALU = 26, EP_CROSS_FANOUT = 27,
+    EP_UP_FUSED16 = 28, EP_UP_FUSED32_SEAM = 29, EP_UP_FUSED16_SMALL = 30, EP_UP_PLAIN = 31, EP_DW_WHOLE = 32, EP_DW_TILED = 33, EP_DW_STREAM = 34,
+    EP_DOWN_STATS = 35, EP_DOWN_NOSTATS = 36, EP_DOWN_MAIN = 37, EP_DOWN_SMALL64 = 38, EP_DOWN_SMALL128 = 39,
+    EP_SPLITK4 = 40, EP_SPLITK8 = 41, EP_SPLITK_SMALL = 42, EP_SPLITK_FINISH12 = 43, EP_SPLITK_FINISH6 = 44,
+    EP_TAIL_MFMA = 45 /* +0..3: NT 1..4 */, EP_TAIL_PLAIN = 49, EP_UPDATE = 50, EP_UPDATE_FROM = 51, EP_UPDATE_FROM_MASK = 52, EP_START_MIX = 53,
+    EP_COUNT = 54
+};
+extern thread_local uint64_t* g_path_sink;
+inline void note_path(int bit) { if (g_path_sink) *g_path_sink |= 1ull << bit; }
+
 // Executes plan_gemm's answer (tld_gemm_plan.h) for this device and the process's switches.  TLD_OK, or TLD_ERR_INVALID with the reason in tld_last_error() when
 // nothing was launched: a plain launch whose operand rows lie beyond the reach of the kernels' 32-bit DMA offsets, or a refused plan
 int launch_gemm(const GemmParams& p, int epilogue, hipStream_t s);

@@ -33,6 +33,7 @@ int fail(int code, const char* fmt, ...) {
 }  // namespace
 namespace tld {
 void set_last_error(const char* msg) { snprintf(g_err, sizeof(g_err), "%s", msg); }
+thread_local uint64_t* g_path_sink = nullptr;
 }  // namespace tld
 namespace {
 
@@ -85,6 +86,16 @@ struct Layer {
     float *up_c1 = nullptr, *up_b1 = nullptr;             // [hid] column sums of up_wf; up_b + beta3 . Wup^T
     float *n1_w = nullptr, *n1_b = nullptr, *n2_w = nullptr, *n2_b = nullptr, *n3_w = nullptr, *n3_b = nullptr;
     float *kv_w = nullptr, *q_w = nullptr;   // fp32, conditioning path
+};
+
+// stage hook (tld_engine_set_debug): a named tensor in its stored type, read in place (the engine's own buffer) or from a copy the hook owns.
+// Tables with a per-layer pitch (the conditioning tables) are `outer` runs of shape[1..3] elements, `outer_stride` elements apart.
+enum { ST_F32 = 0, ST_BF16 = 1 };
+enum { UNPACK_NONE = 0, UNPACK_QKV_ROWS = 1 };      // rows stored in the fused QKV -> attention kernel's [head][feature half][q | k | v][32] order
+struct DbgStage {
+    void* ptr = nullptr; int dtype = ST_F32; int64_t shape[4] = {1, 1, 1, 1};
+    bool owned = false; size_t cap = 0; bool live = false;
+    int64_t outer_stride = 0; int unpack = UNPACK_NONE;
 };
 
 enum KClass { KC_GEMM_QKV = 0, KC_GEMM_UP, KC_GEMM_DOWN, KC_ATTN, KC_CROSS, KC_DWCONV, KC_LN, KC_EMBED,
@@ -145,10 +156,14 @@ struct tld_engine {
     float *c_wq = nullptr;             // [L][T][H][d]
     float *c_bwq = nullptr;            // [L][T][H]
 
-    // debug stage capture
+    // debug stage capture (tld_engine_set_debug)
     bool debug = false;
+    bool dbg_keep = false;             // the running body's stages are kept (debug on, and the sampler is at the debug step)
+    int dbg_step = -1;                 // sampler step whose stages are kept (tld_engine_set_debug_step); < 0: every step, so the last one remains
     int dbg_batch = 0, dbg_T = 0;
-    std::map<std::string, float*> stages;
+    uint64_t paths = 0;                // launch paths of the last debug call
+    std::map<std::string, DbgStage> stages;
+    std::vector<std::pair<void*, size_t>> poison;      // activation / statistics / seam / split-K buffers a debug forward fills with 0xFF first
 
     // per-class event profiling
     // (event pairs come from a per-class pool that set_profile / profile_reserve fill OUTSIDE any timed region;
@@ -261,24 +276,136 @@ struct ProfScope {
 constexpr int kLowLatMaxRows2 = 1024;
 constexpr int kLowLatMaxRows = 4096;        // capacity of the low-latency class (token rows = max_batch x tokens): beyond it the tiles fill the chip by themselves
 
-int capture_hidden(tld_engine* e, const char* name, const bf16* src, size_t count, hipStream_t s) {
-    if (!e->debug) return TLD_OK;
-    float*& buf = e->stages[name];
-    if (!buf) { if (int rc = dev_alloc(e, &buf, (size_t)e->cfg.max_batch * e->ntok * e->hid)) return rc; }
-    launch_cast_to_f32(src, TLD_DTYPE_BF16, buf, (int64_t)count, s);
+// ---- stage hook ---------------------------------------------------------------------------------------------------------------
+void free_stages(tld_engine* e) {
+    for (auto& kv : e->stages) if (kv.second.owned && kv.second.ptr) (void)hipFree(kv.second.ptr);
+    e->stages.clear();
+}
+DbgStage* stage_slot(tld_engine* e, const std::string& name, int dtype, int64_t s0, int64_t s1, int64_t s2, int64_t s3) {
+    DbgStage& st = e->stages[name];
+    st.dtype = dtype; st.shape[0] = s0; st.shape[1] = s1; st.shape[2] = s2; st.shape[3] = s3; st.live = true;
+    return &st;
+}
+// the engine's own buffer under a name (nothing is copied)
+void stage_ref(tld_engine* e, const std::string& name, const void* ptr, int dtype, int64_t s0, int64_t s1 = 1, int64_t s2 = 1, int64_t s3 = 1,
+               int64_t outer_stride = 0, int unpack = UNPACK_NONE) {
+    if (!e->debug || !ptr) return;
+    DbgStage* st = stage_slot(e, name, dtype, s0, s1, s2, s3);
+    st->owned = false; st->ptr = const_cast<void*>(ptr); st->outer_stride = outer_stride; st->unpack = unpack;
+}
+// a device-to-device copy on the stream, right after the kernel that completed the value, into memory tld_engine_set_debug(1) reserved
+int stage_copy(tld_engine* e, const std::string& name, const void* src, int dtype, hipStream_t s, int64_t s0, int64_t s1 = 1, int64_t s2 = 1, int64_t s3 = 1) {
+    if (!e->dbg_keep) return TLD_OK;
+    auto it = e->stages.find(name);
+    const size_t bytes = (size_t)(s0 * s1 * s2 * s3) * (dtype == ST_BF16 ? 2 : 4);
+    if (it == e->stages.end() || !it->second.owned || it->second.cap < bytes)
+        return fail(TLD_ERR_STATE, "stage hook: no snapshot memory reserved for '%s' (%zu bytes): call tld_engine_set_debug(1) after the engine's "
+                    "mode (tld_engine_set_low_latency) is chosen", name.c_str(), bytes);
+    stage_slot(e, name, dtype, s0, s1, s2, s3);
+    HIP_TRY(hipMemcpyAsync(it->second.ptr, src, bytes, hipMemcpyDeviceToDevice, s));
+    return TLD_OK;
+}
+// a snapshot a kernel writes itself (cross_row's x + att dump): *out is the reserved memory, or null when nothing is kept
+int stage_sink(tld_engine* e, const std::string& name, int64_t s0, int64_t s1, float** out) {
+    *out = nullptr;
+    if (!e->dbg_keep) return TLD_OK;
+    auto it = e->stages.find(name);
+    if (it == e->stages.end() || !it->second.owned || it->second.cap < (size_t)(s0 * s1) * 4)
+        return fail(TLD_ERR_STATE, "stage hook: no snapshot memory reserved for '%s' (%zu bytes)", name.c_str(), (size_t)(s0 * s1) * 4);
+    stage_slot(e, name, ST_F32, s0, s1, 1, 1);
+    *out = static_cast<float*>(it->second.ptr);
+    return TLD_OK;
+}
+#define SNAP(...) do { if (e->dbg_keep) { if (int _r = stage_copy(e, __VA_ARGS__)) return _r; } } while (0)
+inline std::string blk_name(int l, const char* n) { return "blk" + std::to_string(l) + "." + n; }
+
+// which of the forward's size-independent branches this engine takes (run_body and the snapshot reservation agree through these)
+inline bool eng_fused_qa(const tld_engine* e) { return e->fuse_qkv_attn && e->fold_ln1 && !e->fp8; }
+inline bool eng_fuse_dw(const tld_engine* e) { return e->fuse_dwconv && (e->grid == 16 || (e->grid == 32 && e->seam)) && e->hid % 256 == 0; }
+
+// set_debug(1): memory for every snapshot a forward of max_batch samples takes (the names of the SNAP calls in run_body and the samplers),
+// and the names of what is read in place: the conditioning tables and the GEMM operands as the engine holds them
+int reserve_snapshots(tld_engine* e) {
+    const size_t B = (size_t)e->cfg.max_batch, M = B * e->ntok, d = e->d, hid = e->hid;
+    auto one = [&](const std::string& name, size_t bytes) -> int {
+        DbgStage& st = e->stages[name];
+        if (st.owned && st.cap >= bytes) return TLD_OK;
+        if (st.owned && st.ptr) (void)hipFree(st.ptr);
+        st = DbgStage();
+        if (hipMalloc(&st.ptr, bytes) != hipSuccess) {
+            st.ptr = nullptr; (void)hipGetLastError();
+            return fail(TLD_ERR_HIP, "tld_engine_set_debug: hipMalloc of %zu bytes for the snapshot '%s' failed", bytes, name.c_str());
+        }
+        st.owned = true; st.cap = bytes;
+        return TLD_OK;
+    };
+#define RES(name, bytes) do { if (int _r = one(name, bytes)) return _r; } while (0)
+    const size_t rs = sizeof(resid_t);
+    RES("tokens0", M * d * rs); RES("out", B * e->img * 4);
+    for (const char* n : {"step.x_t", "step.x0_prev", "step.x0", "step.x_next"}) RES(n, B * e->img * 4);
+    RES("step.out", B * e->img * 4);
+    for (int l = 0; l < e->L; ++l) {
+        for (const char* n : {"x_in", "ca", "mlp"}) RES(blk_name(l, n), M * d * rs);
+        RES(blk_name(l, "att"), M * d * 2); RES(blk_name(l, "sa"), M * d * 4);
+        if (e->fold_ln1) RES(blk_name(l, "ln1"), M * kLnSlots * 8); else RES(blk_name(l, "xn1"), M * d * 2);
+        if (!eng_fused_qa(e)) { RES(blk_name(l, "qk"), M * 2 * d * 2); RES(blk_name(l, "vt"), M * d * 2); }
+        if (e->fold_ln3) RES(blk_name(l, "stats"), M * 8); else RES(blk_name(l, "xn3"), M * d * 2);
+        if (!eng_fuse_dw(e) && !e->fp8) RES(blk_name(l, "hid_pre"), M * hid * 2);
+        RES(blk_name(l, "hid"), M * hid * 2);
+        if (e->splitk) RES(blk_name(l, "splitk"), (size_t)e->ll_split * M * d * 4);
+    }
+#undef RES
+    for (int l = 0; l < e->L; ++l) {
+        const Layer& Ly = e->layers[l];
+        if (eng_fused_qa(e)) {
+            stage_ref(e, blk_name(l, "wqkv"), Ly.qkv_wp, ST_BF16, 3 * d, d, 1, 1, 0, UNPACK_QKV_ROWS);
+            stage_ref(e, blk_name(l, "qkv_c1"), Ly.qkv_c1p, ST_F32, 3 * d, 1, 1, 1, 0, UNPACK_QKV_ROWS);
+            stage_ref(e, blk_name(l, "qkv_b1"), Ly.qkv_b1p, ST_F32, 3 * d, 1, 1, 1, 0, UNPACK_QKV_ROWS);
+        } else {
+            stage_ref(e, blk_name(l, "wqkv"), e->fold_ln1 ? Ly.qkv_wf : Ly.qkv_w, ST_BF16, 3 * d, d);
+            stage_ref(e, blk_name(l, "qkv_c1"), Ly.qkv_c1, ST_F32, 3 * d); stage_ref(e, blk_name(l, "qkv_b1"), Ly.qkv_b1, ST_F32, 3 * d);
+        }
+        stage_ref(e, blk_name(l, "wup"), e->fold_ln3 ? Ly.up_wf : Ly.up_w, ST_BF16, hid, d);
+        stage_ref(e, blk_name(l, "up_c1"), Ly.up_c1, ST_F32, hid); stage_ref(e, blk_name(l, "up_b1"), Ly.up_b1, ST_F32, hid);
+        stage_ref(e, blk_name(l, "wdown"), Ly.down_w, ST_BF16, d, hid);
+    }
     return TLD_OK;
 }
 
-int capture(tld_engine* e, const char* name, const resid_t* src, size_t count, hipStream_t s) {
+// start of a debug forward: what its kernels are to write holds NaN (0xFF bytes), so a kernel that stores nothing, or too few rows, shows
+int debug_poison(tld_engine* e, hipStream_t s) {
     if (!e->debug) return TLD_OK;
-    float*& buf = e->stages[name];
-    if (!buf) {
-        const size_t cap = (size_t)std::max(e->cfg.max_batch * e->ntok, 4 * e->cfg.max_batch + 1024) * e->d;
-        if (int rc = dev_alloc(e, &buf, cap)) return rc;
-    }
-    launch_cast_to_f32(src, sizeof(resid_t) == 2 ? TLD_DTYPE_BF16 : TLD_DTYPE_F32, buf, (int64_t)count, s);
+    for (const auto& pb : e->poison) HIP_TRY(hipMemsetAsync(pb.first, 0xFF, pb.second, s));
+    const size_t M = (size_t)e->cfg.max_batch * e->ntok;
+    if (e->splitk) HIP_TRY(hipMemsetAsync(e->splitk, 0xFF, (size_t)e->ll_split * M * e->d * 4, s));
+    if (e->a8) { HIP_TRY(hipMemsetAsync(e->a8, 0xFF, M * e->hid, s)); HIP_TRY(hipMemsetAsync(e->as8, 0xFF, M * e->hid / 32 + 1024, s)); }
     return TLD_OK;
 }
+// ... and of a debug call: the conditioning tables too; the launch-path record starts empty; the tables get their names for this call's T rows
+int debug_begin(tld_engine* e, int T, int Tn, hipStream_t s) {
+    if (!e->debug) return TLD_OK;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+        return fail(TLD_ERR_STATE, "a debug forward (tld_engine_set_debug) cannot be captured into a graph");
+    e->paths = 0;
+    const size_t cap = (size_t)e->cond_cap, d = e->d, L = e->L, H = e->H;
+    for (float* p : {e->c_sin, e->c_h1, e->c_pre, e->c_y}) HIP_TRY(hipMemsetAsync(p, 0xFF, cap * (p == e->c_sin ? (size_t)e->ne : d) * 4, s));
+    HIP_TRY(hipMemsetAsync(e->c_kv, 0xFF, L * cap * 2 * d * 4, s));
+    HIP_TRY(hipMemsetAsync(e->c_wq, 0xFF, L * cap * H * d * 4, s));
+    HIP_TRY(hipMemsetAsync(e->c_bwq, 0xFF, L * cap * H * 4, s));
+    for (auto& kv : e->stages) if (kv.second.owned) kv.second.live = false;      // every snapshot of an earlier call is forgotten (the operand names stay)
+    stage_ref(e, "cond.sin", e->c_sin, ST_F32, Tn, e->ne); stage_ref(e, "cond.h1", e->c_h1, ST_F32, Tn, d);      // (noise rows only)
+    stage_ref(e, "cond.pre", e->c_pre, ST_F32, T, d); stage_ref(e, "cond.y", e->c_y, ST_F32, T, d);
+    stage_ref(e, "cond.kv", e->c_kv, ST_F32, L, T, 2 * d, 1, (int64_t)(cap * 2 * d));
+    stage_ref(e, "cond.wq", e->c_wq, ST_F32, L, T, H, d, (int64_t)(cap * H * d));
+    stage_ref(e, "cond.bwq", e->c_bwq, ST_F32, L, T, H, 1, (int64_t)(cap * H));
+    return TLD_OK;
+}
+struct PathScope {      // the launchers record their paths into this engine while one of its debug calls runs on this thread; no stage is kept after it, on any exit
+    tld_engine* e;
+    explicit PathScope(tld_engine* e_) : e(e_) { if (e->debug) g_path_sink = &e->paths; }
+    ~PathScope() { g_path_sink = nullptr; e->dbg_keep = false; }
+};
 
 // Conditioning tables for T token rows whose pre-LN vectors sit in c_pre[0..T): y = LN(pre), then per
 // layer K|V = y Wkv^T and the folded query vectors (denoiser.py:121-122, transformer_blocks.py:65-71).
@@ -314,7 +441,8 @@ void cond_label_rows(tld_engine* e, int row0, int Tl, hipStream_t s) {
 int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const int* noise_row,
              const int* label_row, float* out, hipStream_t s, bool share_l0 = false) {
     const int d = e->d, M = batch * e->ntok;
-    share_l0 = share_l0 && e->share_l0 && batch == 2 * src_batch && !e->debug;
+    share_l0 = share_l0 && e->share_l0 && batch == 2 * src_batch;
+    if (int rc = debug_poison(e, s)) return rc;
     const int b0 = share_l0 ? src_batch : batch;            // samples processed up to block 0's attention
     resid_t* xe = share_l0 ? e->x_half : e->x;
     const bool fold1 = e->fold_ln1;                          // LayerNorm-1 applied inside the QKV GEMM's epilogue
@@ -329,20 +457,23 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
         ep.ntok = e->ntok;
         launch_embed(ep, s);
     }
-    if (int rc = capture(e, "tokens0", e->x, (size_t)M * d, s)) return rc;
+    const int rdt = sizeof(resid_t) == 2 ? ST_BF16 : ST_F32;
+    SNAP("tokens0", xe, rdt, s, (int64_t)b0 * e->ntok, d);
     for (int l = 0; l < e->L; ++l) {
         const Layer& Ly = e->layers[l];
         const bool half = share_l0 && l == 0;
         const int bl = half ? b0 : batch, Ml = bl * e->ntok;
         const bool fuse8 = e->fp8 && e->fp8_fused;      // fp8 mode: producers write the MX-fp8 operand themselves
+        SNAP(blk_name(l, "x_in"), half ? xe : e->x, rdt, s, Ml, d);
+        if (fold1) SNAP(blk_name(l, "ln1"), e->ln_stats, ST_F32, s, Ml, kLnSlots, 2);
         if (!fold1) {   // xn = LN1(x)
             ProfScope ps(e, KC_LN, s);
             if (fuse8 && layernorm_mx8_supported(d)) launch_layernorm_mx8(half ? xe : e->x, Ly.n1_w, Ly.n1_b, e->a8, e->as8, Ml, d, s);
-            else launch_layernorm_bf16(half ? xe : e->x, Ly.n1_w, Ly.n1_b, e->xn, Ml, d, s);
+            else { launch_layernorm_bf16(half ? xe : e->x, Ly.n1_w, Ly.n1_b, e->xn, Ml, d, s); SNAP(blk_name(l, "xn1"), e->xn, ST_BF16, s, Ml, d); }
         }
         // 256-token grids with the LayerNorm-1 fold: the QKV projection and the whole self-attention of a (sample, head) are one 256 x 192
         // GEMM tile + epilogue; q | k, v^T never reach HBM and `att` is written directly.  (the fp8 mode keeps the two kernels)
-        const bool fused_qa = e->fuse_qkv_attn && fold1 && !e->fp8;
+        const bool fused_qa = eng_fused_qa(e);
         if (fused_qa) {
             ProfScope ps(e, KC_GEMM_QKV, s);
             GemmParams g{};
@@ -367,21 +498,18 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
             }
 #endif
             launch_gemm(g, fold1 ? EPI_QKV_LN : EPI_QKV, s);
+            SNAP(blk_name(l, "qk"), e->qk, ST_BF16, s, Ml, 2 * d); SNAP(blk_name(l, "vt"), e->vt, ST_BF16, s, bl, d, e->ntok);
         }
         if (!fused_qa) {
             ProfScope ps(e, KC_ATTN, s);
             launch_attention(e->qk, e->vt, e->att, bl, e->ntok, e->H, s);
         }
-        if (l == 0 && e->debug && !e->stages["blk0_sa"]) {
-            float* buf = nullptr;
-            if (int rc = dev_alloc(e, &buf, (size_t)e->cfg.max_batch * e->ntok * d)) return rc;
-            e->stages["blk0_sa"] = buf;
-        }
+        SNAP(blk_name(l, "att"), e->att, ST_BF16, s, Ml, d);
         // 256 px (16x16 tokens): one GEMM tile row-block is one image, so the depthwise conv + GELU run inside the
         // up-projection's epilogue and the pre-conv hidden never reaches HBM.  Other grids: separate kernels.
         // 512 px (32x32 tokens, round 4): a tile row-block is 8 image rows; the epilogue finishes the interior rows and a thin second kernel the two rows at
         // every tile seam from the hidden rows the epilogue leaves for it (half of the hidden tensor instead of a write + read of all of it).
-        const bool fuse_dw = e->fuse_dwconv && (e->grid == 16 || (e->grid == 32 && e->seam)) && e->hid % 256 == 0;
+        const bool fuse_dw = eng_fuse_dw(e);
         const bool fold3 = e->fold_ln3;                 // LN3 applied in the up-projection's epilogue: cross_row writes row statistics, not xn
         {   // x += att; x += CA(LN2 x, y); xn = LN3(x) (or its row statistics)
             ProfScope ps(e, KC_CROSS, s);
@@ -395,12 +523,14 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
             cp.noise_row = noise_row; cp.label_row = label_row;
             cp.ln2_w = Ly.n2_w; cp.ln2_b = Ly.n2_b; cp.ln3_w = Ly.n3_w; cp.ln3_b = Ly.n3_b;
             cp.xn3 = fold3 ? nullptr : e->xn; cp.ln3_stats = fold3 ? e->row_stats : nullptr; cp.batch = batch; cp.ntok = e->ntok; cp.d = d; cp.heads = e->H;
-            cp.sa_out = (l == 0 && e->debug) ? e->stages["blk0_sa"] : nullptr;
+            if (e->dbg_keep) { if (int rc = stage_sink(e, blk_name(l, "sa"), M, d, &cp.sa_out)) return rc; }
             const bool cross8 = fuse8 && cross_row_supports_ln3_stats(d);      // (= the 4-features-per-lane kernel is in use)
             if (cross8) { cp.xn3_f8 = e->a8; cp.xn3_s8 = e->as8; }
             launch_cross_row(cp, s);
+            if (!fold3 && !cross8) SNAP(blk_name(l, "xn3"), e->xn, ST_BF16, s, M, d);
         }
-        if (l == 0) if (int rc = capture(e, "blk0_ca", e->x, (size_t)M * d, s)) return rc;
+        SNAP(blk_name(l, "ca"), e->x, rdt, s, M, d);
+        if (fold3) SNAP(blk_name(l, "stats"), e->row_stats, ST_F32, s, M, 2);
         if (fuse_dw) {
             ProfScope ps(e, KC_GEMM_UP, s);
             GemmParams g{};
@@ -436,7 +566,7 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
 #endif
                 launch_gemm(g, EPI_BIAS_BF16, s);
             }
-            if (l == 0 && !e->fp8) if (int rc = capture_hidden(e, "blk0_hid_pre", e->hid1, (size_t)M * e->hid, s)) return rc;
+            if (!e->fp8) SNAP(blk_name(l, "hid_pre"), e->hid1, ST_BF16, s, M, e->hid);
             {
                 ProfScope ps(e, KC_DWCONV, s);
                 const bool dw8 = fuse8 && e->grid > 16;       // the tiled kernel writes the fp8 operand of the down projection itself
@@ -444,7 +574,7 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
                                    dw8 ? e->a8 : nullptr, dw8 ? e->as8 : nullptr);
             }
         }
-        if (l == 0) if (int rc = capture_hidden(e, "blk0_hid", e->hid2, (size_t)M * e->hid, s)) return rc;
+        SNAP(blk_name(l, "hid"), e->hid2, ST_BF16, s, M, e->hid);
         if (e->low_latency && !e->fp8) {
             // Low-latency class: a handful of samples are a handful of 256-row tiles, and the down projection's 48 K-steps per tile (K = 4 d) were
             // half of a layer's time however empty the chip was.  Four K-splits quadruple the work items (fp32 slices, summed in a fixed order by
@@ -456,6 +586,7 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
             g.A = e->hid2; g.lda = e->hid; g.W = Ly.down_w; g.ldw = e->hid; g.M = M; g.N = d; g.K = e->hid / e->ll_split; g.ksplit = e->ll_split;
             g.c_f32 = e->splitk; g.ldc = d;
             launch_gemm(g, EPI_F32, s);
+            SNAP(blk_name(l, "splitk"), e->splitk, ST_F32, s, e->ll_split, M, d);
             launch_splitk_resid(e->splitk, e->ll_split, (size_t)M * d, Ly.down_b, e->x, (fold1 && l + 1 < e->L) ? e->ln_stats : nullptr, M, d, s);
         } else
         {   // x += hid2 Wdown^T + b
@@ -471,9 +602,8 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
             }
             launch_gemm(g, EPI_BIAS_RESID, s);
         }
-        if (l == 0) if (int rc = capture(e, "blk0_mlp", e->x, (size_t)M * d, s)) return rc;
+        SNAP(blk_name(l, "mlp"), e->x, rdt, s, M, d);
     }
-    if (int rc = capture(e, "tokens_final", e->x, (size_t)M * d, s)) return rc;
     {
         ProfScope ps(e, KC_TAIL, s);
         TailParams tp{};
@@ -482,6 +612,7 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
         tp.pd = e->pd; tp.d = d; tp.ntok = e->ntok;
         launch_tail(tp, s);
     }
+    SNAP("out", out, ST_F32, s, batch, e->img);
     HIP_TRY(hipGetLastError());
     return TLD_OK;
 }
@@ -499,6 +630,7 @@ int sample_prepare(tld_engine* e, const void* labels, const float* coeffs, int n
 
     // ---- conditioning tables for the whole trajectory, once
     const size_t n_rows = (size_t)(n_levels + 1) * B2;
+    if (int rc = debug_begin(e, T, n_levels, s)) return rc;
     if (int rc = stage_acquire(e, (size_t)n_levels * sizeof(float) + n_rows * sizeof(int))) return rc;
     float* sig = static_cast<float*>(e->stage_host);
     int* rows = reinterpret_cast<int*>(sig + n_levels);
@@ -538,6 +670,20 @@ UpdateParams update_params(tld_engine* e, const float* coeffs, int n_levels, int
     up.sharp = sharp_f; up.bright = bright_f; up.final_step = final_step ? 1 : 0;
     up.batch = B; up.img = e->img; up.chan_stride = e->cfg.image_size * e->cfg.image_size; up.C = e->cfg.n_channels;
     return up;
+}
+
+// Stage hook around one sampler step: at the debug step (tld_engine_set_debug_step; every step when it is negative) the body's stages are kept, and so
+// are the step's inputs (x_t, x0_prev) and outputs (the 2B forward output, the x0 written, the next x_t).
+int step_begin(tld_engine* e, int i, int B, hipStream_t s) {
+    e->dbg_keep = e->debug && (e->dbg_step < 0 || e->dbg_step == i);
+    SNAP("step.x_t", e->xt, ST_F32, s, B, e->img); SNAP("step.x0_prev", e->x0_prev, ST_F32, s, B, e->img);
+    return TLD_OK;
+}
+int step_end(tld_engine* e, const UpdateParams& up, int B, hipStream_t s) {
+    SNAP("step.out", e->io_out, ST_F32, s, 2 * B, e->img); SNAP("step.x0", up.x0_out, ST_F32, s, B, e->img);
+    if (!up.final_step) SNAP("step.x_next", e->xt, ST_F32, s, B, e->img);
+    e->dbg_keep = false;
+    return TLD_OK;
 }
 
 }  // namespace
@@ -885,6 +1031,15 @@ int tld_engine_finalize_weights(tld_engine* e) {
         if (int rc = dev_alloc(e, &e->a8, M * hid)) return rc;
         if (int rc = dev_alloc(e, &e->as8, M * hid / 32 + 1024)) return rc;
     }
+    {   // what a debug forward poisons first: every activation / statistics / seam buffer above (the split-K slices and the fp8 operand: debug_poison)
+        auto& P = e->poison;
+        P.clear();
+        P.emplace_back(e->x, M * d * sizeof(resid_t)); P.emplace_back(e->x_half, (M + 1) / 2 * d * sizeof(resid_t)); P.emplace_back(e->xn, M * d * 2);
+        P.emplace_back(e->row_stats, (M + 256) * sizeof(float2)); P.emplace_back(e->ln_stats, (M + 256) * kLnSlots * sizeof(float2));
+        P.emplace_back(e->qk, M * 2 * d * 2); P.emplace_back(e->vt, M * d * 2); P.emplace_back(e->att, M * d * 2);
+        P.emplace_back(e->hid1, M * hid * 2); P.emplace_back(e->hid2, M * hid * 2);
+        if (e->seam) P.emplace_back(e->seam, M * hid / 4 * sizeof(uint32_t));
+    }
     if (int rc = dev_alloc(e, &e->io_x, B2 * e->img)) return rc;
     if (int rc = dev_alloc(e, &e->io_out, B2 * e->img)) return rc;
     if (int rc = dev_alloc(e, &e->io_sigma, B2)) return rc;
@@ -900,7 +1055,51 @@ int tld_engine_finalize_weights(tld_engine* e) {
 
 int tld_engine_set_debug(tld_engine* e, int32_t enable) {
     if (!e) return fail(TLD_ERR_INVALID, "null engine");
-    e->debug = enable != 0;
+    DeviceGuard dg(e->cfg.device_id);
+    if (enable) {
+        if (!e->finalized) return fail(TLD_ERR_STATE, "tld_engine_set_debug: weights not finalized");
+        e->debug = true;
+        if (int rc = reserve_snapshots(e)) { (void)hipDeviceSynchronize(); free_stages(e); e->debug = false; return rc; }
+    } else {
+        (void)hipDeviceSynchronize();
+        free_stages(e);
+        e->debug = false; e->dbg_keep = false;
+    }
+    return TLD_OK;
+}
+
+int tld_engine_set_debug_step(tld_engine* e, int32_t step) {
+    if (!e) return fail(TLD_ERR_INVALID, "null engine");
+    e->dbg_step = step;
+    return TLD_OK;
+}
+
+int tld_engine_debug_paths(tld_engine* e, uint64_t* mask) {
+    if (!e || !mask) return fail(TLD_ERR_INVALID, "null argument");
+    *mask = e->paths;
+    return TLD_OK;
+}
+
+namespace {
+// the six stage names of the first hook, and the two hidden-tensor ones
+std::string stage_alias(const tld_engine* e, const char* name) {
+    const struct { const char* old_name; const char* new_name; } al[] = {{"cond_y", "cond.y"}, {"blk0_sa", "blk0.sa"}, {"blk0_ca", "blk0.ca"},
+        {"blk0_mlp", "blk0.mlp"}, {"blk0_hid", "blk0.hid"}, {"blk0_hid_pre", "blk0.hid_pre"}};
+    for (const auto& a : al) if (!strcmp(name, a.old_name)) return a.new_name;
+    if (!strcmp(name, "tokens_final")) return blk_name(e->L - 1, "mlp");
+    return name;
+}
+const DbgStage* find_stage(tld_engine* e, const char* name) {
+    auto it = e->stages.find(stage_alias(e, name));
+    return (it != e->stages.end() && it->second.live && it->second.ptr) ? &it->second : nullptr;
+}
+}  // namespace
+
+int tld_engine_stage_shape(tld_engine* e, const char* name, int64_t* shape4) {
+    if (!e || !name || !shape4) return fail(TLD_ERR_INVALID, "null argument");
+    const DbgStage* st = find_stage(e, name);
+    if (!st) return fail(TLD_ERR_KEY, "no captured stage named %s (was debug enabled before the forward? a stage of another path?)", name);
+    for (int i = 0; i < 4; ++i) shape4[i] = st->shape[i];
     return TLD_OK;
 }
 
@@ -908,14 +1107,33 @@ int tld_engine_read_stage(tld_engine* e, const char* name, float* host_out, int6
     if (!e || !name || !host_out) return fail(TLD_ERR_INVALID, "null argument");
     DeviceGuard dg(e->cfg.device_id);
     HIP_TRY(hipDeviceSynchronize());
-    const float* src = nullptr;
-    if (!strcmp(name, "cond_y")) src = e->c_y;
-    else {
-        auto it = e->stages.find(name);
-        if (it != e->stages.end()) src = it->second;
+    const DbgStage* st = find_stage(e, name);
+    if (!st) return fail(TLD_ERR_KEY, "no captured stage named %s (was debug enabled before the forward? a stage of another path?)", name);
+    const int64_t outer = st->outer_stride ? st->shape[0] : 1;
+    const int64_t inner = (st->outer_stride ? 1 : st->shape[0]) * st->shape[1] * st->shape[2] * st->shape[3];
+    if (numel != outer * inner)
+        return fail(TLD_ERR_SHAPE, "stage %s has %lld elements [%lld, %lld, %lld, %lld], the caller's buffer %lld", name, (long long)(outer * inner),
+                    (long long)st->shape[0], (long long)st->shape[1], (long long)st->shape[2], (long long)st->shape[3], (long long)numel);
+    const size_t esz = st->dtype == ST_BF16 ? 2 : 4;
+    std::vector<uint16_t> half;
+    if (st->dtype == ST_BF16) half.resize((size_t)numel);
+    for (int64_t o = 0; o < outer; ++o) {
+        const char* src = static_cast<const char*>(st->ptr) + (size_t)o * st->outer_stride * esz;
+        void* dst = st->dtype == ST_BF16 ? static_cast<void*>(half.data() + o * inner) : static_cast<void*>(host_out + o * inner);
+        HIP_TRY(hipMemcpy(dst, src, (size_t)inner * esz, hipMemcpyDeviceToHost));
     }
-    if (!src) return fail(TLD_ERR_KEY, "no captured stage named %s (was debug enabled before the forward?)", name);
-    HIP_TRY(hipMemcpy(host_out, src, numel * sizeof(float), hipMemcpyDeviceToHost));
+    if (st->dtype == ST_BF16)
+        for (int64_t i = 0; i < numel; ++i) { const uint32_t u = (uint32_t)half[(size_t)i] << 16; memcpy(host_out + i, &u, 4); }
+    if (st->unpack == UNPACK_QKV_ROWS) {      // back to the logical [q; k; v] x [head][64] row order (the inverse of the packing in finalize_weights)
+        const int64_t d = e->d, row = st->shape[1];
+        std::vector<float> tmp(host_out, host_out + numel);
+        for (int64_t h = 0; h < e->H; ++h)
+            for (int part = 0; part < 3; ++part)
+                for (int64_t c = 0; c < 64; ++c) {
+                    const int64_t logical = part * d + h * 64 + c, packed = h * 192 + (c >> 5) * 96 + part * 32 + (c & 31);
+                    memcpy(host_out + logical * row, tmp.data() + packed * row, (size_t)row * 4);
+                }
+    }
     return TLD_OK;
 }
 
@@ -929,6 +1147,9 @@ int tld_denoiser_forward(tld_engine* e, const void* x, const void* noise, const 
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     const float* xin = static_cast<const float*>(x);
     float* o = static_cast<float*>(out);
+    PathScope paths(e);
+    if (int rc = debug_begin(e, 2 * batch, batch, s)) return rc;
+    e->dbg_keep = e->debug;
     if (io_dtype != TLD_DTYPE_F32) {
         launch_cast_to_f32(x, io_dtype, e->io_x, (int64_t)batch * e->img, s);
         xin = e->io_x; o = e->io_out;
@@ -957,6 +1178,7 @@ int tld_sample(tld_engine* e, const void* x_T, const void* labels, const float* 
     DeviceGuard dg(e->cfg.device_id);
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     const int* label_row = nullptr;
+    PathScope paths(e);
     if (int rc = sample_prepare(e, labels, coeffs, n_levels, batch, s, &label_row)) return rc;
     const int B = batch, B2 = 2 * batch;
 
@@ -966,9 +1188,14 @@ int tld_sample(tld_engine* e, const void* x_T, const void* labels, const float* 
 
     for (int i = 0; i < n_levels; ++i) {
         // pred_image: model(cat[x_t, x_t], sigma_i, [labels; 0])   (diffusion.py:94-101)
+        if (int rc = step_begin(e, i, B, s)) return rc;
         if (int rc = run_body(e, e->xt, B, B2, e->rows_dev + (size_t)i * B2, label_row, e->io_out, s, true)) return rc;
-        ProfScope ps(e, KC_UPDATE, s);
-        launch_update(update_params(e, coeffs, n_levels, i, class_guidance, sharp_f, bright_f, out_latent, B, trace_x0, trace_xt), s);
+        const UpdateParams up = update_params(e, coeffs, n_levels, i, class_guidance, sharp_f, bright_f, out_latent, B, trace_x0, trace_xt);
+        {
+            ProfScope ps(e, KC_UPDATE, s);
+            launch_update(up, s);
+        }
+        if (int rc = step_end(e, up, B, s)) return rc;
     }
     HIP_TRY(hipGetLastError());
     return TLD_OK;
@@ -983,6 +1210,7 @@ int tld_sample_from(tld_engine* e, const void* noise, const void* init_latent, c
     DeviceGuard dg(e->cfg.device_id);
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     const int* label_row = nullptr;
+    PathScope paths(e);
     if (int rc = sample_prepare(e, labels, coeffs, n_levels, batch, s, &label_row)) return rc;
     const int B = batch, B2 = 2 * batch;
 
@@ -993,13 +1221,17 @@ int tld_sample_from(tld_engine* e, const void* noise, const void* init_latent, c
     HIP_TRY(hipMemsetAsync(e->x0_prev, 0, tot * sizeof(float), s));
 
     for (int i = 0; i < n_levels; ++i) {
+        if (int rc = step_begin(e, i, B, s)) return rc;
         if (int rc = run_body(e, e->xt, B, B2, e->rows_dev + (size_t)i * B2, label_row, e->io_out, s, true)) return rc;
-        ProfScope ps(e, KC_UPDATE, s);
         UpdateFromParams uf{};
         uf.u = update_params(e, coeffs, n_levels, i, class_guidance, sharp_f, bright_f, out_latent, B, trace_x0, trace_xt);
         uf.noise = static_cast<const float*>(noise); uf.z0 = static_cast<const float*>(init_latent); uf.mask = static_cast<const float*>(mask);
         uf.s_next = (i + 1 < n_levels) ? coeffs[(size_t)(i + 1) * 6 + 0] : 0.0f;
-        launch_update_from(uf, s);
+        {
+            ProfScope ps(e, KC_UPDATE, s);
+            launch_update_from(uf, s);
+        }
+        if (int rc = step_end(e, uf.u, B, s)) return rc;
     }
     HIP_TRY(hipGetLastError());
     return TLD_OK;
@@ -1312,6 +1544,7 @@ int tld_engine_destroy(tld_engine* e) {
     (void)hipDeviceSynchronize();
     for (int k = 0; k < KC_COUNT; ++k)
         for (auto& ev : e->prof_ev[k]) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
+    free_stages(e);
     for (void* p : e->allocs) (void)hipFree(p);
     if (e->stage_host) (void)hipHostFree(e->stage_host);
     if (e->stage_ev) (void)hipEventDestroy(e->stage_ev);

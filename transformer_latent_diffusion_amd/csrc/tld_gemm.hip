@@ -1683,15 +1683,30 @@ int launch_gemm(const GemmParams& p_in, int epilogue, hipStream_t s) {
     const GemmParams& p = p_in;
 #endif
     const GemmPlan plan = plan_gemm(p, epilogue, device_cu_count(), gemm_switches());
+    auto note_main = [&]() {      // launch-path record of the engine's stage hook (the engine's epilogues only)
+        switch (epilogue) {
+            case EPI_QKV_ATTN: note_path(EP_QKV_ATTN); break;
+            case EPI_QKV_LN: note_path(EP_QKV_LN); break;
+            case EPI_QKV: note_path(EP_QKV_PLAIN); break;
+            case EPI_UP_DWCONV2: note_path(EP_UP_FUSED16); break;
+            case EPI_UP_DWCONV32: note_path(EP_UP_FUSED32_SEAM); break;
+            case EPI_BIAS_BF16: note_path(EP_UP_PLAIN); break;
+            case EPI_BIAS_RESID: note_path(EP_DOWN_MAIN); note_path(p.stats_out ? EP_DOWN_STATS : EP_DOWN_NOSTATS); break;
+            case EPI_F32: if (p.ksplit > 1) note_path(p.ksplit == 8 ? EP_SPLITK8 : EP_SPLITK4); break;
+            default: break;
+        }
+    };
     switch (plan.family) {
-        case GEMM_UPDW_PP: launch_updw_pp(p, plan, s); return TLD_OK;
-        case GEMM_SPLITK_PP: launch_splitk_pp(p, plan, s); return TLD_OK;
-        case GEMM_DOWN_PP: launch_down_pp(p, plan, s); return TLD_OK;
+        case GEMM_UPDW_PP: note_path(EP_UP_FUSED16_SMALL); launch_updw_pp(p, plan, s); return TLD_OK;
+        case GEMM_SPLITK_PP: note_path(EP_SPLITK_SMALL); note_path(p.ksplit == 8 ? EP_SPLITK8 : EP_SPLITK4); launch_splitk_pp(p, plan, s); return TLD_OK;
+        case GEMM_DOWN_PP:
+            note_path(plan.bm == 64 ? EP_DOWN_SMALL64 : EP_DOWN_SMALL128); note_path(p.stats_out ? EP_DOWN_STATS : EP_DOWN_NOSTATS);
+            launch_down_pp(p, plan, s); return TLD_OK;
         case GEMM_MAIN: {
             GemmParams pg = p;
             pg.half_tail = plan.half_tail;
             pg.xcd_ngroups = plan.xcd_ngroups;
-            if (dispatch_main(pg, epilogue, plan, s)) return TLD_OK;
+            if (dispatch_main(pg, epilogue, plan, s)) { note_main(); return TLD_OK; }
             set_last_error(gemm_refusal_text(GEMM_REFUSED_NO_KERNEL));
             return TLD_ERR_INVALID;
         }

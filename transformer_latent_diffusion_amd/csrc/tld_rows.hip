@@ -1270,6 +1270,13 @@ __global__ __launch_bounds__(256) void dwconv_gelu_tiled_kernel(const bf16* __re
     __syncthreads();                                       // ... everybody's
     if (gi >= g) return;
     auto col = [&](int lj, f32x2 (&c)[3][2]) {             // lj: halo-tile column index 0..17
+        // image columns >= g are zero padding, not the clamped copy the halo holds: the last tile of a grid that is not a multiple of 16 wide
+        // (24, 40 ...) is partial, and its right edge lies inside the tile
+        if (j0 + lj >= g) {
+#pragma unroll
+            for (int du = 0; du < 3; ++du) { c[du][0] = f32x2{0.f, 0.f}; c[du][1] = f32x2{0.f, 0.f}; }
+            return;
+        }
 #pragma unroll
         for (int du = 0; du < 3; ++du) {
             const bf16x4 v = *reinterpret_cast<const bf16x4*>(tile + ((li + du) * TP + lj) * 128 + cq * 8);
@@ -1278,7 +1285,7 @@ __global__ __launch_bounds__(256) void dwconv_gelu_tiled_kernel(const bf16* __re
         }
     };
     bf16* dst = out + ((size_t)b * g * g + (size_t)gi * g + (size_t)tx * T) * C + c0;
-    const int ncols = g - tx * T < T ? g - tx * T : T;     // (a multiple of the tile width for every supported grid)
+    const int ncols = g - tx * T < T ? g - tx * T : T;     // (8 in the last tile of a 24- or 40-wide grid)
     auto emit = [&](const f32x2 (&L)[3][2], const f32x2 (&Mc)[3][2], const f32x2 (&R)[3][2], int lj) {
         f32x2 a[2] = {bs[0], bs[1]};
 #pragma unroll
@@ -1357,6 +1364,7 @@ void launch_embed(const EmbedParams& p, hipStream_t s) {
         const int lds = 16 * 16 * 4 + 4 * 4 * 32 * 4 + 3 * p.d * 4 + 4 * 32 * 144;      // conv weight, row partials, bias / LayerNorm vectors, transpose patches
         dim3 grid((unsigned)((rows + 31) / 32));
 #define TLD_EM(TPW) do { TLD_LDS_OPT_IN((embed_mfma_kernel<TPW>), lds); hipLaunchKernelGGL((embed_mfma_kernel<TPW>), grid, dim3(256), lds, s, p, p.lin_w_hl); } while (0)
+        note_path(EP_EMBED_MFMA + p.d / 256 - 1);
         if (p.d == 256) TLD_EM(2); else if (p.d == 512) TLD_EM(4); else if (p.d == 768) TLD_EM(6); else TLD_EM(8);
 #undef TLD_EM
         return;
@@ -1364,11 +1372,13 @@ void launch_embed(const EmbedParams& p, hipStream_t s) {
 #endif
     const int rows = p.batch * p.ntok;
     const int lds = (p.pd * p.d + p.pd * p.C * p.p * p.p) * (int)sizeof(float);
+    note_path(EP_EMBED_PLAIN);
     TLD_DISPATCH_D(p.d, { TLD_LDS_OPT_IN((embed_kernel<NJ, HALF>), lds); hipLaunchKernelGGL((embed_kernel<NJ, HALF>), dim3((rows + 31) / 32), dim3(256), lds, s, p); });
 }
 
 void launch_layernorm_bf16(const resid_t* x, const float* g, const float* b, bf16* out, int M, int d,
                            hipStream_t s) {
+    if (d == 768 || d == 512 || d == 256 || d == 1024) note_path(EP_LN_Q4 + d / 256 - 1); else note_path(EP_LN_GENERIC);
     if (d == 768) { hipLaunchKernelGGL(layernorm_bf16_q4_kernel<3>, dim3((M + 3) / 4), dim3(256), 0, s, x, g, b, out, M, d); return; }
     if (d == 512) { hipLaunchKernelGGL(layernorm_bf16_q4_kernel<2>, dim3((M + 3) / 4), dim3(256), 0, s, x, g, b, out, M, d); return; }
     if (d == 256) { hipLaunchKernelGGL(layernorm_bf16_q4_kernel<1>, dim3((M + 3) / 4), dim3(256), 0, s, x, g, b, out, M, d); return; }
@@ -1381,6 +1391,7 @@ bool layernorm_mx8_supported(int d) { return d == 256 || d == 512 || d == 768; }
 void launch_layernorm_mx8(const resid_t* x, const float* g, const float* b, uint8_t* out8, uint8_t* scale8, int M, int d,
                           hipStream_t s) {
     const dim3 gr((M + 3) / 4), bl(256);
+    note_path(EP_LN_MX8);
     if (d == 768) hipLaunchKernelGGL(layernorm_mx8_kernel<3>, gr, bl, 0, s, x, g, b, out8, scale8, M, d);
     else if (d == 512) hipLaunchKernelGGL(layernorm_mx8_kernel<2>, gr, bl, 0, s, x, g, b, out8, scale8, M, d);
     else if (d == 256) hipLaunchKernelGGL(layernorm_mx8_kernel<1>, gr, bl, 0, s, x, g, b, out8, scale8, M, d);
@@ -1403,6 +1414,8 @@ void launch_cross_row(const CrossRowParams& p, hipStream_t s) {
         const int ldsm = 2 * 16 * p.d * 2 + 8 * 256 * 4 + 2 * p.d * 4;     // split-bf16 tile, partial logits, the two value rows
         dim3 gridm((unsigned)(p.batch * (gps / gpw)));
 #define TLD_CRM(NQ) do { TLD_LDS_OPT_IN((cross_row_mfma_kernel<NQ>), ldsm); hipLaunchKernelGGL((cross_row_mfma_kernel<NQ>), gridm, dim3(512), ldsm, s, p, gpw); } while (0)
+        note_path(EP_CROSS_MFMA + p.d / 256 - 1); note_path(gpw > 1 ? EP_CROSS_GPWN : EP_CROSS_GPW1);
+        if (p.x_in) note_path(EP_CROSS_FANOUT);
         if (p.d == 256) TLD_CRM(1); else if (p.d == 512) TLD_CRM(2); else if (p.d == 768) TLD_CRM(3); else TLD_CRM(4);
 #undef TLD_CRM
         return;
@@ -1419,6 +1432,8 @@ void launch_cross_row(const CrossRowParams& p, hipStream_t s) {
     if (cps < 1) cps = 1;
     const int lds = (p.heads * p.d + 2 * p.d + p.heads) * (int)sizeof(float);
     dim3 grid((unsigned)(p.batch * cps));
+    note_path(EP_CROSS_VALU);
+    if (p.x_in) note_path(EP_CROSS_FANOUT);
     TLD_DISPATCH_D(p.d, { TLD_LDS_OPT_IN((cross_row_kernel<NJ, HALF>), lds); hipLaunchKernelGGL((cross_row_kernel<NJ, HALF>), grid, dim3(256), lds, s, p, (int)cps); });
 }
 
@@ -1472,8 +1487,8 @@ bool splitk_resid_supported(int d) { return d == 768 || d == 384; }
 
 void launch_splitk_resid(const float* parts, int nsplit, size_t slice_stride, const float* bias, resid_t* x, float2* stats_out, int M, int d, hipStream_t s) {
     const dim3 grid((unsigned)((M + 3) / 4)), block(256);
-    if (d == 768) hipLaunchKernelGGL(splitk_resid_kernel<12>, grid, block, 0, s, parts, nsplit, slice_stride, bias, x, stats_out, M);
-    else if (d == 384) hipLaunchKernelGGL(splitk_resid_kernel<6>, grid, block, 0, s, parts, nsplit, slice_stride, bias, x, stats_out, M);
+    if (d == 768) { note_path(EP_SPLITK_FINISH12); hipLaunchKernelGGL(splitk_resid_kernel<12>, grid, block, 0, s, parts, nsplit, slice_stride, bias, x, stats_out, M); }
+    else if (d == 384) { note_path(EP_SPLITK_FINISH6); hipLaunchKernelGGL(splitk_resid_kernel<6>, grid, block, 0, s, parts, nsplit, slice_stride, bias, x, stats_out, M); }
 }
 
 void launch_tail(const TailParams& p, hipStream_t s) {
@@ -1484,6 +1499,7 @@ void launch_tail(const TailParams& p, hipStream_t s) {
         const int lds = 2 * nt * 16 * p.d * 2;
         dim3 grid((unsigned)((rows + 63) / 64));
 #define TLD_TM(NT) do { TLD_LDS_OPT_IN((tail_mfma_kernel<NT>), lds); hipLaunchKernelGGL((tail_mfma_kernel<NT>), grid, dim3(256), lds, s, p, p.w_hl); } while (0)
+        note_path(EP_TAIL_MFMA + (nt < 4 ? nt : 4) - 1);
         if (nt == 1) TLD_TM(1); else if (nt == 2) TLD_TM(2); else if (nt == 3) TLD_TM(3); else TLD_TM(4);
 #undef TLD_TM
         return;
@@ -1492,11 +1508,13 @@ void launch_tail(const TailParams& p, hipStream_t s) {
     const int rpb = 64;
     const int rows = p.batch * p.ntok;
     const int lds = p.pd * p.d * (int)sizeof(float);
+    note_path(EP_TAIL_PLAIN);
     TLD_DISPATCH_D(p.d, { TLD_LDS_OPT_IN((tail_kernel<NJ, HALF>), lds); hipLaunchKernelGGL((tail_kernel<NJ, HALF>), dim3((rows + rpb - 1) / rpb), dim3(256), lds, s, p, rpb); });
 }
 
 void launch_update(const UpdateParams& p, hipStream_t s) {
     const int n = p.batch * p.img;
+    note_path(EP_UPDATE);
     hipLaunchKernelGGL(update_kernel, dim3((n + 255) / 256), dim3(256), 0, s, p);
 }
 
@@ -1512,6 +1530,7 @@ void launch_update_from(const UpdateFromParams& q, hipStream_t s) {
                      aligned16(p.trace_x0) && aligned16(p.trace_xt) && aligned16(q.noise) && aligned16(q.z0) && aligned16(q.mask);
     const int threads = vec ? n / 4 : n;
     const dim3 grid((threads + 255) / 256), block(256);
+    note_path(q.mask ? EP_UPDATE_FROM_MASK : EP_UPDATE_FROM);
     if (q.mask) {
         if (vec) hipLaunchKernelGGL((update_from_kernel<true, 4>), grid, block, 0, s, q);
         else hipLaunchKernelGGL((update_from_kernel<true, 1>), grid, block, 0, s, q);
@@ -1522,6 +1541,7 @@ void launch_update_from(const UpdateFromParams& q, hipStream_t s) {
 }
 
 void launch_start_mix(const float* noise, const float* z0, float s0, float* x_t, int n, hipStream_t s) {
+    note_path(EP_START_MIX);
     if (n % 4 == 0 && aligned16(noise) && aligned16(z0) && aligned16(x_t))
         hipLaunchKernelGGL((start_mix_kernel<4>), dim3((n / 4 + 255) / 256), dim3(256), 0, s, noise, z0, s0, x_t, n);
     else
@@ -1755,6 +1775,7 @@ void launch_dwconv_gelu(const bf16* in, bf16* out, const float* w9c, const float
                         uint8_t* scale8) {
     if (grid > 16 && grid % 32 == 0) {       // row-streaming variant (ring of image rows in LDS, a DMA wave); halved tables
         const dim3 gr((unsigned)(batch * (grid / 32) * (channels / DW_CB)));
+        note_path(EP_DW_STREAM);
         if (out8) hipLaunchKernelGGL(dwconv_gelu_stream_kernel<true>, gr, dim3(320), 0, s, in, out, w9c_half, bias_half, batch, grid, channels, out8, scale8);
         else hipLaunchKernelGGL(dwconv_gelu_stream_kernel<false>, gr, dim3(320), 0, s, in, out, w9c_half, bias_half, batch, grid, channels, out8, scale8);
         return;
@@ -1762,6 +1783,7 @@ void launch_dwconv_gelu(const bf16* in, bf16* out, const float* w9c, const float
     if (grid > 16) {        // spatially tiled variant (halo in LDS); takes the halved tables
         const int tiles = (grid + 15) / 16;
         const dim3 gr((unsigned)(batch * tiles * tiles * (channels / DW_CB)));
+        note_path(EP_DW_TILED);
         if (out8) hipLaunchKernelGGL(dwconv_gelu_tiled_kernel<true>, gr, dim3(256), 0, s, in, out, w9c_half, bias_half, batch, grid,
                                      channels, out8, scale8);
         else hipLaunchKernelGGL(dwconv_gelu_tiled_kernel<false>, gr, dim3(256), 0, s, in, out, w9c_half, bias_half, batch, grid,
@@ -1769,6 +1791,7 @@ void launch_dwconv_gelu(const bf16* in, bf16* out, const float* w9c, const float
         return;
     }
     const int lds = grid * grid * 128;
+    note_path(EP_DW_WHOLE);
     hipLaunchKernelGGL(dwconv_gelu_kernel, dim3((unsigned)(batch * (channels / DW_CB))), dim3(256), lds, s, in, out,
                        w9c, bias, batch, grid, channels);
 }

@@ -293,11 +293,40 @@ class Denoiser:
         return (out, tx0, txt) if trace else out
 
     # ---- test / bench hooks -----------------------------------------------------------------------------
+    # launch paths of tld_engine_debug_paths, by bit number (include/tld_hip.h; None: unused bit)
+    PATH_NAMES = ("embed plain", "embed_mfma<2>", "embed_mfma<4>", "embed_mfma<6>", "embed_mfma<8>", "layernorm q4<1>", "layernorm q4<2>", "layernorm q4<3>",
+                  "layernorm q4<4>", "layernorm generic", "layernorm mx8", "QKV fused with attention", "QKV LayerNorm-1 fold", "QKV plain", "attention 256",
+                  "attention chunked", None, "attention 64", None, "attention masked", "cross_row_mfma<1>", "cross_row_mfma<2>",
+                  "cross_row_mfma<3>", "cross_row_mfma<4>", "cross_row gpw 1", "cross_row gpw > 1", "cross_row VALU", "cross_row x_in fan-out",
+                  "up fused 16", "up fused 32 + seam", "up fused 16 4-wave", "up alone", "depthwise whole image", "depthwise tiled", "depthwise streaming",
+                  "down with stats_out", "down without stats_out", "down 8-wave", "down 4-wave 64", "down 4-wave 128", "split-K x4", "split-K x8",
+                  "split-K 4-wave", "split-K finisher<12>", "split-K finisher<6>", "tail_mfma<1>", "tail_mfma<2>", "tail_mfma<3>", "tail_mfma<4>", "tail plain",
+                  "update", "update_from", "update_from masked", "start_mix")
+
     def set_debug(self, enable: bool = True):
+        """Stage capture of the forward (``tld_engine_set_debug``): allocates (frees) the snapshot memory of the current engine."""
         _lib.check(_lib.lib().tld_engine_set_debug(self._engine, int(enable)), "tld_engine_set_debug")
 
-    def read_stage(self, name: str, shape) -> np.ndarray:
-        out = np.empty(shape, dtype=np.float32)
+    def set_debug_step(self, step: int):
+        """Sampler step whose stages a debug ``sample_latents`` keeps (negative: every step, so the last one remains)."""
+        _lib.check(_lib.lib().tld_engine_set_debug_step(self._engine, int(step)), "tld_engine_set_debug_step")
+
+    def debug_paths(self) -> int:
+        m = C.c_uint64()
+        _lib.check(_lib.lib().tld_engine_debug_paths(self._engine, C.byref(m)), "tld_engine_debug_paths")
+        return int(m.value)
+
+    def stage_shape(self, name: str):
+        sh = (C.c_int64 * 4)()
+        _lib.check(_lib.lib().tld_engine_stage_shape(self._engine, name.encode(), sh), f"tld_engine_stage_shape({name})")
+        sh = list(sh)
+        while len(sh) > 1 and sh[-1] == 1:
+            sh.pop()
+        return tuple(sh)
+
+    def read_stage(self, name: str, shape=None) -> np.ndarray:
+        """A captured stage as fp32; ``shape`` defaults to the stage's logical shape, and a shape of another size is refused by the library."""
+        out = np.empty(self.stage_shape(name) if shape is None else shape, dtype=np.float32)
         _lib.check(_lib.lib().tld_engine_read_stage(self._engine, name.encode(),
                                                     out.ctypes.data_as(C.POINTER(C.c_float)), out.size),
                    f"tld_engine_read_stage({name})")
