@@ -157,6 +157,13 @@ TLD_API int tld_sample_from(tld_engine* e, const void* noise, const void* init_l
  *   operands as the engine holds them, read in place, in logical [N][K] order (the fused QKV -> attention kernel's row packing is undone on read):
  *   blk<i>.wqkv [3 d, d], blk<i>.wup [hid, d] (gamma-scaled under the LayerNorm folds), blk<i>.wdown [d, hid], and the folds' vectors
  *   blk<i>.qkv_c1, blk<i>.qkv_b1 [3 d], blk<i>.up_c1, blk<i>.up_b1 [hid].
+ *   fp8 GEMM mode (tld_engine_set_gemm_dtype; no folds, two-kernel QKV, up-projection alone): the three A operands as the GEMMs read them, copied after
+ *   the producer or quantisation pass and before the GEMM: blk<i>.a8_qkv [Mi, d], blk<i>.a8_up [M, d], blk<i>.a8_down [M, hid], each as two stages:
+ *   <name>.q, the e4m3 codes, and <name>.s [rows, K / 32], the E8M0 scale bytes in logical order (the GEMM's [K / 128][rows][4] layout, with the rows
+ *   of the call, is undone on read); both read as the byte values 0 ... 255.  blk<i>.hid_pre is kept; blk<i>.xn1, blk<i>.xn3 and blk<i>.hid exist
+ *   where a bf16 copy does (separate quantisation passes: TLD_FP8_FUSED=0, and the widths / grids whose producers do not quantise themselves) and
+ *   are "no such stage" (TLD_ERR_KEY) elsewhere.  blk<i>.wqkv, blk<i>.wup, blk<i>.wdown return the e4m3 weights as held, DEQUANTISED on the host
+ *   side of the read (code x 2^(scale - 127), exact in fp32).
  *   The first hook's names stay as aliases: cond_y, tokens0, blk0_sa, blk0_ca, blk0_mlp, tokens_final, blk0_hid, blk0_hid_pre.
  * Launch-path bits of tld_engine_debug_paths (bit number : path):
  *    0 embed plain   1-4 embed_mfma<2 | 4 | 6 | 8>   5-8 layernorm q4<1..4>   9 layernorm generic   10 layernorm mx8 (fp8 mode)
@@ -168,8 +175,10 @@ TLD_API int tld_sample_from(tld_engine* e, const void* noise, const void* init_l
  *   35 down projection writing LayerNorm-1 partial sums   36 ... not writing them (last block, or no fold)   37 down projection, 8-wave kernel
  *   38 4-wave form, 64-row tiles   39 4-wave form, 128-row tiles   40 split-K x 4   41 split-K x 8   42 split-K 4-wave form
  *   43 split-K finisher <12> (d 768)   44 <6> (d 384)   45-48 tail_mfma<1..4>   49 tail plain
- *   50 update   51 update_from without a mask   52 update_from with a mask   53 start_mix */
-#define TLD_ENGINE_PATH_BITS 54
+ *   50 update   51 update_from without a mask   52 update_from with a mask   53 start_mix
+ *   writers of the MX-fp8 A operand (with bit 10): 54 separate quantisation pass   55 cross_row_mfma writing e4m3   56 depthwise tiled writing e4m3
+ *   57 depthwise streaming writing e4m3 */
+#define TLD_ENGINE_PATH_BITS 58
 TLD_API int tld_engine_set_debug(tld_engine* e, int32_t enable);
 /* host_out fp32 [numel]; numel must match the stage (TLD_ERR_SHAPE otherwise).  Synchronises the device. */
 TLD_API int tld_engine_read_stage(tld_engine* e, const char* name, float* host_out, int64_t numel);

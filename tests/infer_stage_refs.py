@@ -175,6 +175,74 @@ def dw_gelu_model(h, dw_w, dw_b, G, taps_bf16):
     return gelu_poly_half(R.dwconv_fwd(h, wh, 0.5 * dw_b, G))
 
 
+# ---- MX-fp8 operands (the fp8 GEMM mode; tests/test_gpu_fp8_stages.py) ---------------------------------------------------------------------------
+def _pow2(k):
+    """2^k in float64 for an integer tensor k (|k| < 1023), built from the exponent field: exact on every device, where pow may round."""
+    return ((k.long() + 1023) << 52).view(torch.float64)
+
+
+def mx8_quantize(x):
+    """x [R, K] (K % 32 == 0) -> (e4m3 codes [R, K], E8M0 bytes [R, K / 32]) as float64 byte values 0 ... 255, the form read_stage returns.
+    OCP Microscaling v1.0 as tld_quant.hip states it: per 32-element block X = 2^(floor(log2 amax) - 8), q = e4m3_rne(clamp(v / X, -448, 448)).
+    Integer arithmetic on any device -- no float8 type; tests/test_infer_stage_refs_host.py holds it bit for bit against
+    mx8_emulation.mx8_quantize (which converts through torch.float8_e4m3fn)."""
+    R_, K = x.shape
+    xb = x.double().view(R_, K // 32, 32)
+    amax = xb.abs().amax(-1)
+    e = torch.frexp(amax)[1] - 1                                           # floor(log2 amax) for amax > 0
+    e8 = torch.where(amax > 0, (e + 119).clamp(min=0), torch.zeros_like(e))
+    v = (xb * _pow2(127 - e8)[..., None]).clamp(-448.0, 448.0)
+    a = v.abs()
+    ex = torch.where(a < 2.0 ** -6, torch.full_like(e8[..., None], -6), torch.frexp(a)[1] - 1)      # subnormals: multiples of 2^-9
+    q = torch.round(a * _pow2(3 - ex))                 # nearest even, in units of 2^(ex - 3): 8 ... 16 (normal), 0 ... 8 (subnormal)
+    code = (ex + 6) * 8 + q.long()                                         # ((ex + 7) << 3 | q - 8); q = 16 carries into the exponent by itself
+    code = code + 128 * torch.signbit(v).long()
+    return code.view(R_, K).double(), e8.double()
+
+
+def mx8_dequantize(q, s):
+    """Codes [R, K] and scale bytes [R, K / 32] (float byte values) -> float64 values."""
+    c = q.long()
+    ex, man = (c >> 3) & 15, c & 7
+    mag = torch.where(ex > 0, (8 + man).double() * _pow2(ex - 10), man.double() * 2.0 ** -9)
+    v = torch.where(c >= 128, -mag, mag)
+    return (v.view(q.shape[0], -1, 32) * _pow2(s.long() - 127)[..., None]).view(q.shape)
+
+
+def mx8_model(ref):
+    """What an exact producer followed by one bf16 rounding and the quantiser would hand the GEMM: the yardstick of the producers' MODELLED class."""
+    return mx8_dequantize(*mx8_quantize(bf16(ref)))
+
+
+def mx8_linear(aq, as_, w, bias=None, resid=None):
+    """The fp8 GEMM on the engine's operands: dequantised A [M, K] x dequantised weights as held w [N, K] (+ bias, + residual).  Exact in float64."""
+    y = mx8_dequantize(aq, as_) @ w.T
+    if bias is not None:
+        y = y + bias
+    return y if resid is None else y + resid
+
+
+def mx8_first_difference(q, s, q_ref, s_ref):
+    """(differing codes, differing scale bytes, description of the first differing (row, 32-block)) of two operands; ('', 0, 0) when bitwise equal."""
+    dq, ds = q != q_ref, s != s_ref
+    nq, ns = int(dq.sum()), int(ds.sum())
+    if nq + ns == 0:
+        return 0, 0, ""
+    blk = dq.view(q.shape[0], -1, 32).any(-1) | ds
+    r, b = (int(t[0]) for t in torch.nonzero(blk, as_tuple=True))
+    kind = "scale" if bool(ds[r, b]) else "byte"
+    return nq, ns, (f"first at (row {r}, block {b}): {kind} -- scale {int(s[r, b])} vs {int(s_ref[r, b])}, "
+                    f"{int(dq[r, b * 32:(b + 1) * 32].sum())} of 32 codes differ")
+
+
+def dw_partial_tile_mask(G):
+    """Pixels [G, G] of the partial last 16 x 16 tiles of the tiled depthwise kernel (grids that are not a multiple of 16 wide: 24, 40 ...), or None."""
+    if G % 16 == 0:
+        return None
+    yy, xx = torch.meshgrid(torch.arange(G), torch.arange(G), indexing="ij")
+    return (yy >= G - G % 16) | (xx >= G - G % 16)
+
+
 # ---- sampler ------------------------------------------------------------------------------------------------------------------------------------
 def cfg_combine(out2b, g):
     """[2 B, ...] (conditional half first) -> g cond + (1 - g) uncond -- tld/diffusion.py:124-125."""

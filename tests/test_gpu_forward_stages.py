@@ -110,7 +110,7 @@ CASES = {
     "FQ": (_cfg(768, 32, 2), (24,), 24, {"TLD_FUSE_QKV_ATTN": "0"}, 0),  # QKV with the LayerNorm-1 fold + attention 256; 6144 rows: the 4-wave down projection on 128-row tiles
 }
 IO_CASE = "W256"
-FP8_PATH_CASE = (_cfg(256, 128, 1), 1)        # reaches the fp8 mode's LayerNorm kernel for the launch-path record only (the fp8 GEMMs and producers have tests of their own)
+FP8_PATH_CASE = (_cfg(256, 128, 1), 1)        # reaches the fp8 mode's LayerNorm kernel for the launch-path record only: the fp8 mode is held stage by stage by tests/test_gpu_fp8_stages.py
 
 
 def _model(kw, seed=31):
@@ -661,6 +661,34 @@ def test_debug_runs_are_reproducible_and_debug_off_computes_the_same():
     for n in names:
         a, b2 = first[n], m.read_stage(n)
         assert np.array_equal(a.view(np.int32), b2.view(np.int32)), n
+    on_s = m.sample_latents(x, lab, co, 3.0).clone()
+    m.set_debug(False)
+    off2 = m(x, sigma, lab).clone()
+    assert torch.equal(off, on1) and torch.equal(on1, on2) and torch.equal(off, off2)
+    assert torch.equal(off_s, on_s)
+
+
+@pytest.mark.parametrize("fused", ["1", "0"])
+def test_fp8_debug_off_computes_the_same(fused):
+    """The same on an fp8 engine, quantising producers and separate passes: the operand snapshots, hid_pre and the poisoning of a8 / as8 change no output bit."""
+    from transformer_latent_diffusion_amd import schedule
+    kw = _cfg(768, 32, 2)
+    dev = _dev()
+    m = _model(kw)
+    m.set_gemm_dtype("fp8")
+    _with_env({"TLD_FP8_FUSED": fused}, lambda: m.reserve(16))
+    x, sigma, lab, _ = _inputs(kw, 8, 11)
+    x, sigma, lab = x.to(dev), sigma.to(dev), lab.to(dev)
+    co = schedule.step_coefficients(schedule.noise_schedule(6, 1), True)
+    off = m(x, sigma, lab).clone()
+    off_s = m.sample_latents(x, lab, co, 3.0).clone()
+    m.set_debug(True)
+    names = ["blk0.a8_qkv.q", "blk0.a8_up.s", "blk1.a8_down.q", "blk1.a8_down.s", "blk1.hid_pre", "blk1.mlp"]
+    on1 = m(x, sigma, lab).clone()
+    first = {n: m.read_stage(n) for n in names}
+    on2 = m(x, sigma, lab).clone()
+    for n in names:
+        assert np.isfinite(first[n]).all() and np.array_equal(first[n], m.read_stage(n)), n
     on_s = m.sample_latents(x, lab, co, 3.0).clone()
     m.set_debug(False)
     off2 = m(x, sigma, lab).clone()

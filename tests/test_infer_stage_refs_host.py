@@ -8,7 +8,10 @@ The GPU stage test compares the engine with these functions, so they are held he
   * the update functions against the g2 sampler traces: xt[i + 1] from xt[i], x0[i], x0[i - 1] and schedule.step_coefficients, DPM-Solver++(2M)
     and DDIM, and the CFG-free final prediction's shifts (fp32 traces: 2e-5 max|xt|; measured <= 1.4e-7);
   * the kernels' rounding models against their exact statements, at the size their comments give (the degree-6 GELU polynomial within 1.7e-4
-    absolute, tld_common.h; bf16 probabilities within 2^-8 relative).
+    absolute, tld_common.h; bf16 probabilities within 2^-8 relative);
+  * the MX-fp8 statements of the fp8 stage test (mx8_quantize, mx8_dequantize: integer arithmetic, any device) bit for bit against
+    tests/mx8_emulation.py (torch.float8_e4m3fn) on bf16 data of wide spread with zero blocks, negative zeros, ties, subnormals and saturation, and
+    against the library's host quantiser; mx8_linear against the plain product of the g5 chain's operands; the difference report and the tile mask.
 """
 import math
 
@@ -16,6 +19,7 @@ import numpy as np
 import torch
 
 import infer_stage_refs as F
+import mx8_emulation as E
 import train_stage_refs as R
 from conftest import cfg_from_arr, load_golden, synth_weights
 from transformer_latent_diffusion_amd import schedule
@@ -116,3 +120,74 @@ def test_rounding_models_stay_within_their_documented_size():
     for taps in (False, True):
         model = F.dw_gelu_model(h, dw, db, 8, taps)
         assert float((model - exact).abs().max()) <= 1.7e-4 + (2.0 ** -8 * 9 * 0.3 * 4 if taps else 0.0)
+
+
+def _mx8_inputs():
+    gen = torch.Generator().manual_seed(8)
+    x = (torch.randn(96, 768, generator=gen) * torch.exp(torch.randn(96, 24, generator=gen) * 3).repeat_interleave(32, 1)).bfloat16().float()
+    x[0, :64] = 0                                          # all-zero blocks
+    x[1, 3] = -0.0; x[1, 40:48] = -0.0                     # negative zeros keep their sign bit
+    x[2, 5] = 1e-30                                        # far below the block maximum
+    x[3, 7] = 3e20                                         # a huge element drags the block scale up
+    x[4, :32] = 448.0 * 2 ** -3                            # the representable maximum
+    x[5, :8] = torch.tensor([1.0625, 1.1875, 1.3125, 1.4375, 1.5625, 1.6875, 1.8125, 1.9375]) * 256      # ties of the 3-bit mantissa
+    x[6, :32] = torch.linspace(0, 31, 32) * 2.0 ** -9 * 4  # the subnormal grid and its ties, block maximum 2^-2 ... : codes 0 ... 8 and the first normals
+    x[7, :32] = 1.9921875 * 256                            # bf16 values above 448 X: saturate
+    x[8, :32] = 1e-40                                      # a block of fp32 subnormals: scale byte 0
+    return x
+
+
+def test_mx8_statements_match_the_emulation_bit_for_bit():
+    x = _mx8_inputs()
+    q_ref, e_ref = E.mx8_quantize(x)
+    q, e = F.mx8_quantize(x.double())
+    assert torch.equal(q, q_ref.double()) and torch.equal(e, e_ref.double())
+    assert 0.0 in q and 128.0 in q and 126.0 in q and 254.0 in q and any(float(v) in q for v in range(1, 8))        # zeros of both signs, saturation, subnormals
+    assert torch.equal(F.mx8_dequantize(q, e), E.mx8_dequantize(q_ref, e_ref))
+    # every code, through both dequantisers
+    codes = torch.arange(256).repeat(1, 1).view(8, 32).to(torch.uint8)
+    codes = codes[(codes & 0x7f) != 0x7f].view(-1)                    # (the two NaN codes are never stored: the quantiser saturates)
+    codes = torch.cat([codes, codes[:2]]).view(-1, 32)
+    sc = torch.full((codes.shape[0], 1), 127, dtype=torch.uint8)
+    assert torch.equal(F.mx8_dequantize(codes.double(), sc.double()), E.mx8_dequantize(codes, sc))
+    # the model of a producer is the emulation of its rounded output
+    ref = torch.randn(16, 256, generator=torch.Generator().manual_seed(9), dtype=torch.float64)
+    assert torch.equal(F.mx8_model(ref), E.mx8_dequantize(*E.mx8_quantize(ref.float().bfloat16().float())))
+    rel = float(((F.mx8_model(ref) - ref) ** 2).sum().sqrt() / (ref ** 2).sum().sqrt())
+    assert 1e-2 < rel < 2.0 ** -4, rel                               # three mantissa bits: half an ulp is at most 2^-4
+
+
+def test_mx8_statements_match_the_library_host_quantiser():
+    import ctypes as C
+    from transformer_latent_diffusion_amd import _lib
+    x = _mx8_inputs()
+    R_, K = x.shape
+    out, sc = np.zeros((R_, K), np.uint8), np.zeros((K // 128, R_, 4), np.uint8)
+    xa = np.ascontiguousarray(x.numpy(), dtype=np.float32)
+    _lib.check(_lib.lib().tld_debug_quant_mx8_host(xa.ctypes.data_as(C.POINTER(C.c_float)), R_, K, out.ctypes.data, sc.ctypes.data), "quant_mx8_host")
+    q, e = F.mx8_quantize(x.double())
+    assert np.array_equal(out, q.numpy().astype(np.uint8))
+    assert np.array_equal(sc, E.scales_to_gemm_layout(e.to(torch.uint8)).numpy())
+
+
+def test_mx8_linear_and_difference_report():
+    gen = torch.Generator().manual_seed(10)
+    a = F.bf16(torch.randn(48, 256, generator=gen, dtype=torch.float64))
+    w = torch.randn(64, 256, generator=gen, dtype=torch.float64) * 0.05
+    bias, resid = torch.randn(64, generator=gen, dtype=torch.float64), torch.randn(48, 64, generator=gen, dtype=torch.float64)
+    q, s = F.mx8_quantize(a)
+    wd = F.mx8_dequantize(*F.mx8_quantize(w))
+    ref = R.linear_fwd(E.mx8_dequantize(q.to(torch.uint8), s.to(torch.uint8)), wd, bias) + resid
+    assert torch.allclose(F.mx8_linear(q, s, wd, bias, resid), ref, rtol=0, atol=1e-13)
+    rel = float(((F.mx8_linear(q, s, wd) - a @ w.T) ** 2).sum().sqrt() / ((a @ w.T) ** 2).sum().sqrt())
+    assert rel < 6e-2, rel                                           # two e4m3 operands: a few percent by construction
+    assert F.mx8_first_difference(q, s, q, s) == (0, 0, "")
+    q2, s2 = q.clone(), s.clone()
+    s2[5, 3] += 1; q2[7, 40] = 1.0 if q2[7, 40] != 1.0 else 2.0
+    nq, ns, where = F.mx8_first_difference(q2, s2, q, s)
+    assert (nq, ns) == (1, 1) and where.startswith("first at (row 5, block 3): scale"), where
+    nq, ns, where = F.mx8_first_difference(q2, s, q, s)
+    assert (nq, ns) == (1, 0) and where.startswith("first at (row 7, block 1): byte"), where
+    assert F.dw_partial_tile_mask(32) is None
+    m = F.dw_partial_tile_mask(24)
+    assert m.shape == (24, 24) and int(m.sum()) == 24 * 24 - 16 * 16 and bool(m[23, 0]) and bool(m[0, 16]) and not bool(m[15, 15])

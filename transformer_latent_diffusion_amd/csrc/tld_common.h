@@ -313,7 +313,9 @@ enum : int {
     EP_DOWN_STATS = 35, EP_DOWN_NOSTATS = 36, EP_DOWN_MAIN = 37, EP_DOWN_SMALL64 = 38, EP_DOWN_SMALL128 = 39,
     EP_SPLITK4 = 40, EP_SPLITK8 = 41, EP_SPLITK_SMALL = 42, EP_SPLITK_FINISH12 = 43, EP_SPLITK_FINISH6 = 44,
     EP_TAIL_MFMA = 45 /* +0..3: NT 1..4 */, EP_TAIL_PLAIN = 49, EP_UPDATE = 50, EP_UPDATE_FROM = 51, EP_UPDATE_FROM_MASK = 52, EP_START_MIX = 53,
-    EP_COUNT = 54
+    // fp8 GEMM mode, the writers of the MX-fp8 A operand (bit 10 is the quantising LayerNorm)
+    EP_QUANT_MX8 = 54, EP_CROSS_F8 = 55, EP_DW_TILED_F8 = 56, EP_DW_STREAM_F8 = 57,
+    EP_COUNT = 58
 };
 extern thread_local uint64_t* g_path_sink;
 inline void note_path(int bit) { if (g_path_sink) *g_path_sink |= 1ull << bit; }

@@ -90,10 +90,13 @@ struct Layer {
 
 // stage hook (tld_engine_set_debug): a named tensor in its stored type, read in place (the engine's own buffer) or from a copy the hook owns.
 // Tables with a per-layer pitch (the conditioning tables) are `outer` runs of shape[1..3] elements, `outer_stride` elements apart.
-enum { ST_F32 = 0, ST_BF16 = 1 };
+// fp8 mode: ST_U8 = raw bytes (the e4m3 codes of an A operand), ST_MX8S = E8M0 scale bytes stored [K/128][rows][4], logical shape [rows, K/32] (the
+// layout is undone on read), ST_MX8W = an e4m3 weight [N, K] read in place with its scales (`aux`, [K/128][N][4]) and dequantised on the host
+enum { ST_F32 = 0, ST_BF16 = 1, ST_U8 = 2, ST_MX8S = 3, ST_MX8W = 4 };
+inline size_t st_bytes(int dtype) { return dtype == ST_F32 ? 4 : dtype == ST_BF16 ? 2 : 1; }
 enum { UNPACK_NONE = 0, UNPACK_QKV_ROWS = 1 };      // rows stored in the fused QKV -> attention kernel's [head][feature half][q | k | v][32] order
 struct DbgStage {
-    void* ptr = nullptr; int dtype = ST_F32; int64_t shape[4] = {1, 1, 1, 1};
+    void* ptr = nullptr; const void* aux = nullptr; int dtype = ST_F32; int64_t shape[4] = {1, 1, 1, 1};
     bool owned = false; size_t cap = 0; bool live = false;
     int64_t outer_stride = 0; int unpack = UNPACK_NONE;
 };
@@ -297,7 +300,7 @@ void stage_ref(tld_engine* e, const std::string& name, const void* ptr, int dtyp
 int stage_copy(tld_engine* e, const std::string& name, const void* src, int dtype, hipStream_t s, int64_t s0, int64_t s1 = 1, int64_t s2 = 1, int64_t s3 = 1) {
     if (!e->dbg_keep) return TLD_OK;
     auto it = e->stages.find(name);
-    const size_t bytes = (size_t)(s0 * s1 * s2 * s3) * (dtype == ST_BF16 ? 2 : 4);
+    const size_t bytes = (size_t)(s0 * s1 * s2 * s3) * st_bytes(dtype);
     if (it == e->stages.end() || !it->second.owned || it->second.cap < bytes)
         return fail(TLD_ERR_STATE, "stage hook: no snapshot memory reserved for '%s' (%zu bytes): call tld_engine_set_debug(1) after the engine's "
                     "mode (tld_engine_set_low_latency) is chosen", name.c_str(), bytes);
@@ -350,7 +353,12 @@ int reserve_snapshots(tld_engine* e) {
         if (e->fold_ln1) RES(blk_name(l, "ln1"), M * kLnSlots * 8); else RES(blk_name(l, "xn1"), M * d * 2);
         if (!eng_fused_qa(e)) { RES(blk_name(l, "qk"), M * 2 * d * 2); RES(blk_name(l, "vt"), M * d * 2); }
         if (e->fold_ln3) RES(blk_name(l, "stats"), M * 8); else RES(blk_name(l, "xn3"), M * d * 2);
-        if (!eng_fuse_dw(e) && !e->fp8) RES(blk_name(l, "hid_pre"), M * hid * 2);
+        if (!eng_fuse_dw(e)) RES(blk_name(l, "hid_pre"), M * hid * 2);
+        if (e->fp8) {   // the three A operands as the GEMMs read them: e4m3 codes, and the E8M0 scales of the call's rows
+            RES(blk_name(l, "a8_qkv.q"), M * d); RES(blk_name(l, "a8_qkv.s"), M * d / 32);
+            RES(blk_name(l, "a8_up.q"), M * d); RES(blk_name(l, "a8_up.s"), M * d / 32);
+            RES(blk_name(l, "a8_down.q"), M * hid); RES(blk_name(l, "a8_down.s"), M * hid / 32);
+        }
         RES(blk_name(l, "hid"), M * hid * 2);
         if (e->splitk) RES(blk_name(l, "splitk"), (size_t)e->ll_split * M * d * 4);
     }
@@ -368,6 +376,11 @@ int reserve_snapshots(tld_engine* e) {
         stage_ref(e, blk_name(l, "wup"), e->fold_ln3 ? Ly.up_wf : Ly.up_w, ST_BF16, hid, d);
         stage_ref(e, blk_name(l, "up_c1"), Ly.up_c1, ST_F32, hid); stage_ref(e, blk_name(l, "up_b1"), Ly.up_b1, ST_F32, hid);
         stage_ref(e, blk_name(l, "wdown"), Ly.down_w, ST_BF16, d, hid);
+        if (e->fp8) {   // the weights as held: e4m3 + E8M0, dequantised on read
+            stage_ref(e, blk_name(l, "wqkv"), Ly.qkv_w8, ST_MX8W, 3 * d, d); e->stages[blk_name(l, "wqkv")].aux = Ly.qkv_s8;
+            stage_ref(e, blk_name(l, "wup"), Ly.up_w8, ST_MX8W, hid, d); e->stages[blk_name(l, "wup")].aux = Ly.up_s8;
+            stage_ref(e, blk_name(l, "wdown"), Ly.down_w8, ST_MX8W, d, hid); e->stages[blk_name(l, "wdown")].aux = Ly.down_s8;
+        }
     }
     return TLD_OK;
 }
@@ -488,6 +501,7 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
             g.out_bf16 = e->qk; g.ldo = 2 * d; g.vt = e->vt; g.ntok = e->ntok; g.d = d;
             if (e->fp8) {   // MX-fp8: quantise LN1(x) (one pass over [M, d]; fused into the LayerNorm kernel when possible), then the e4m3 GEMM
                 if (!(fuse8 && layernorm_mx8_supported(d))) launch_quant_mx8(e->xn, e->a8, e->as8, Ml, d, s);
+                SNAP(blk_name(l, "a8_qkv.q"), e->a8, ST_U8, s, Ml, d); SNAP(blk_name(l, "a8_qkv.s"), e->as8, ST_MX8S, s, Ml, d / 32);
                 g.f8 = 1; g.A = reinterpret_cast<const bf16*>(e->a8); g.W = reinterpret_cast<const bf16*>(Ly.qkv_w8);
                 g.a_scale = e->as8; g.w_scale = Ly.qkv_s8;
             }
@@ -556,6 +570,7 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
                 g.out_bf16 = e->hid1; g.ldo = e->hid; g.bias = Ly.up_b;
                 if (e->fp8) {
                     if (!(fuse8 && cross_row_supports_ln3_stats(d))) launch_quant_mx8(e->xn, e->a8, e->as8, M, d, s);
+                    SNAP(blk_name(l, "a8_up.q"), e->a8, ST_U8, s, M, d); SNAP(blk_name(l, "a8_up.s"), e->as8, ST_MX8S, s, M, d / 32);
                     g.f8 = 1; g.A = reinterpret_cast<const bf16*>(e->a8); g.W = reinterpret_cast<const bf16*>(Ly.up_w8);
                     g.a_scale = e->as8; g.w_scale = Ly.up_s8;
                 }
@@ -566,7 +581,7 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
 #endif
                 launch_gemm(g, EPI_BIAS_BF16, s);
             }
-            if (!e->fp8) SNAP(blk_name(l, "hid_pre"), e->hid1, ST_BF16, s, M, e->hid);
+            SNAP(blk_name(l, "hid_pre"), e->hid1, ST_BF16, s, M, e->hid);
             {
                 ProfScope ps(e, KC_DWCONV, s);
                 const bool dw8 = fuse8 && e->grid > 16;       // the tiled kernel writes the fp8 operand of the down projection itself
@@ -574,7 +589,7 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
                                    dw8 ? e->a8 : nullptr, dw8 ? e->as8 : nullptr);
             }
         }
-        SNAP(blk_name(l, "hid"), e->hid2, ST_BF16, s, M, e->hid);
+        if (!(fuse8 && e->grid > 16)) SNAP(blk_name(l, "hid"), e->hid2, ST_BF16, s, M, e->hid);      // (the quantising depthwise kernels write no bf16 copy)
         if (e->low_latency && !e->fp8) {
             // Low-latency class: a handful of samples are a handful of 256-row tiles, and the down projection's 48 K-steps per tile (K = 4 d) were
             // half of a layer's time however empty the chip was.  Four K-splits quadruple the work items (fp32 slices, summed in a fixed order by
@@ -597,6 +612,7 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
             g.stats_out = (fold1 && l + 1 < e->L) ? e->ln_stats : nullptr;
             if (e->fp8) {
                 if (!(fuse8 && e->grid > 16)) launch_quant_mx8(e->hid2, e->a8, e->as8, M, e->hid, s);
+                SNAP(blk_name(l, "a8_down.q"), e->a8, ST_U8, s, M, e->hid); SNAP(blk_name(l, "a8_down.s"), e->as8, ST_MX8S, s, M, e->hid / 32);
                 g.f8 = 1; g.A = reinterpret_cast<const bf16*>(e->a8); g.W = reinterpret_cast<const bf16*>(Ly.down_w8);
                 g.a_scale = e->as8; g.w_scale = Ly.down_s8;
             }
@@ -1114,6 +1130,29 @@ int tld_engine_read_stage(tld_engine* e, const char* name, float* host_out, int6
     if (numel != outer * inner)
         return fail(TLD_ERR_SHAPE, "stage %s has %lld elements [%lld, %lld, %lld, %lld], the caller's buffer %lld", name, (long long)(outer * inner),
                     (long long)st->shape[0], (long long)st->shape[1], (long long)st->shape[2], (long long)st->shape[3], (long long)numel);
+    if (st->dtype == ST_U8 || st->dtype == ST_MX8S || st->dtype == ST_MX8W) {
+        const int64_t rows = st->shape[0], cols = st->shape[1];
+        std::vector<uint8_t> raw((size_t)numel);
+        HIP_TRY(hipMemcpy(raw.data(), st->ptr, (size_t)numel, hipMemcpyDeviceToHost));
+        if (st->dtype == ST_U8) {
+            for (int64_t i = 0; i < numel; ++i) host_out[i] = (float)raw[(size_t)i];
+        } else if (st->dtype == ST_MX8S) {      // [cols / 4][rows][4] -> [rows][cols]
+            for (int64_t r = 0; r < rows; ++r)
+                for (int64_t c = 0; c < cols; ++c) host_out[r * cols + c] = (float)raw[(size_t)(((c >> 2) * rows + r) * 4 + (c & 3))];
+        } else {                                // e4m3 code x 2^(E8M0 - 127), scales [cols / 128][rows][4]
+            std::vector<uint8_t> sc((size_t)(numel / 32));
+            HIP_TRY(hipMemcpy(sc.data(), st->aux, sc.size(), hipMemcpyDeviceToHost));
+            for (int64_t r = 0; r < rows; ++r)
+                for (int64_t c = 0; c < cols; ++c) {
+                    const uint8_t q = raw[(size_t)(r * cols + c)];
+                    const int ex = (q >> 3) & 15, man = q & 7;
+                    const float mag = ex ? ldexpf((float)(8 + man), ex - 10) : ldexpf((float)man, -9);      // (the quantiser saturates: no NaN code is stored)
+                    const int e8 = sc[(size_t)(((c >> 7) * rows + r) * 4 + ((c >> 5) & 3))];
+                    host_out[r * cols + c] = ldexpf((q & 0x80) ? -mag : mag, e8 - 127);
+                }
+        }
+        return TLD_OK;
+    }
     const size_t esz = st->dtype == ST_BF16 ? 2 : 4;
     std::vector<uint16_t> half;
     if (st->dtype == ST_BF16) half.resize((size_t)numel);

@@ -48,6 +48,7 @@ __global__ __launch_bounds__(256) void quant_mx8_kernel(const bf16* __restrict__
 
 void launch_quant_mx8(const bf16* in, uint8_t* out, uint8_t* scale, int M, int K, hipStream_t s) {
     const long groups = (long)M * (K >> 3);
+    note_path(EP_QUANT_MX8);
     hipLaunchKernelGGL(quant_mx8_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, s, in, out, scale, M, K);
 }
 

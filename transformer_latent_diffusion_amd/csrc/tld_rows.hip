@@ -1386,7 +1386,7 @@ void launch_layernorm_bf16(const resid_t* x, const float* g, const float* b, bf1
     TLD_DISPATCH_D(d, hipLaunchKernelGGL((layernorm_bf16_kernel<NJ, HALF>), dim3((M + 3) / 4), dim3(256), 0, s, x, g, b, out, M, d));
 }
 
-bool layernorm_mx8_supported(int d) { return d == 256 || d == 512 || d == 768; }      // (the engine's embed_dim limit is 896)
+bool layernorm_mx8_supported(int d) { return d == 256 || d == 512 || d == 768; }      // (the fp8 mode stops at embed_dim 896: d % 128 == 0 below the engine's 1024)
 
 void launch_layernorm_mx8(const resid_t* x, const float* g, const float* b, uint8_t* out8, uint8_t* scale8, int M, int d,
                           hipStream_t s) {
@@ -1395,7 +1395,6 @@ void launch_layernorm_mx8(const resid_t* x, const float* g, const float* b, uint
     if (d == 768) hipLaunchKernelGGL(layernorm_mx8_kernel<3>, gr, bl, 0, s, x, g, b, out8, scale8, M, d);
     else if (d == 512) hipLaunchKernelGGL(layernorm_mx8_kernel<2>, gr, bl, 0, s, x, g, b, out8, scale8, M, d);
     else if (d == 256) hipLaunchKernelGGL(layernorm_mx8_kernel<1>, gr, bl, 0, s, x, g, b, out8, scale8, M, d);
-    else if (d == 1024) hipLaunchKernelGGL(layernorm_mx8_kernel<4>, gr, bl, 0, s, x, g, b, out8, scale8, M, d);
 }
 
 // the LN3-statistics output (CrossRowParams::ln3_stats) exists in the matrix-pipe kernel only
@@ -1416,6 +1415,7 @@ void launch_cross_row(const CrossRowParams& p, hipStream_t s) {
 #define TLD_CRM(NQ) do { TLD_LDS_OPT_IN((cross_row_mfma_kernel<NQ>), ldsm); hipLaunchKernelGGL((cross_row_mfma_kernel<NQ>), gridm, dim3(512), ldsm, s, p, gpw); } while (0)
         note_path(EP_CROSS_MFMA + p.d / 256 - 1); note_path(gpw > 1 ? EP_CROSS_GPWN : EP_CROSS_GPW1);
         if (p.x_in) note_path(EP_CROSS_FANOUT);
+        if (p.xn3_f8) note_path(EP_CROSS_F8);
         if (p.d == 256) TLD_CRM(1); else if (p.d == 512) TLD_CRM(2); else if (p.d == 768) TLD_CRM(3); else TLD_CRM(4);
 #undef TLD_CRM
         return;
@@ -1776,6 +1776,7 @@ void launch_dwconv_gelu(const bf16* in, bf16* out, const float* w9c, const float
     if (grid > 16 && grid % 32 == 0) {       // row-streaming variant (ring of image rows in LDS, a DMA wave); halved tables
         const dim3 gr((unsigned)(batch * (grid / 32) * (channels / DW_CB)));
         note_path(EP_DW_STREAM);
+        if (out8) note_path(EP_DW_STREAM_F8);
         if (out8) hipLaunchKernelGGL(dwconv_gelu_stream_kernel<true>, gr, dim3(320), 0, s, in, out, w9c_half, bias_half, batch, grid, channels, out8, scale8);
         else hipLaunchKernelGGL(dwconv_gelu_stream_kernel<false>, gr, dim3(320), 0, s, in, out, w9c_half, bias_half, batch, grid, channels, out8, scale8);
         return;
@@ -1784,6 +1785,7 @@ void launch_dwconv_gelu(const bf16* in, bf16* out, const float* w9c, const float
         const int tiles = (grid + 15) / 16;
         const dim3 gr((unsigned)(batch * tiles * tiles * (channels / DW_CB)));
         note_path(EP_DW_TILED);
+        if (out8) note_path(EP_DW_TILED_F8);
         if (out8) hipLaunchKernelGGL(dwconv_gelu_tiled_kernel<true>, gr, dim3(256), 0, s, in, out, w9c_half, bias_half, batch, grid,
                                      channels, out8, scale8);
         else hipLaunchKernelGGL(dwconv_gelu_tiled_kernel<false>, gr, dim3(256), 0, s, in, out, w9c_half, bias_half, batch, grid,

@@ -302,6 +302,9 @@ class Denoiser:
                   "down with stats_out", "down without stats_out", "down 8-wave", "down 4-wave 64", "down 4-wave 128", "split-K x4", "split-K x8",
                   "split-K 4-wave", "split-K finisher<12>", "split-K finisher<6>", "tail_mfma<1>", "tail_mfma<2>", "tail_mfma<3>", "tail_mfma<4>", "tail plain",
                   "update", "update_from", "update_from masked", "start_mix")
+    # the writers of the MX-fp8 A operand, by bit number (bit 10 is in PATH_NAMES too): held by tests/test_gpu_fp8_stages.py
+    FP8_PATH_NAMES = {10: "layernorm mx8", 54: "fp8 separate quantisation pass", 55: "fp8 cross_row writer", 56: "fp8 depthwise tiled",
+                      57: "fp8 depthwise streaming"}
 
     def set_debug(self, enable: bool = True):
         """Stage capture of the forward (``tld_engine_set_debug``): allocates (frees) the snapshot memory of the current engine."""
