@@ -132,6 +132,41 @@ TLD_API int tld_sample_from(tld_engine* e, const void* noise, const void* init_l
                const float* coeffs, int32_t n_levels, float class_guidance, float sharp_f, float bright_f, void* out_latent,
                int32_t batch, void* trace_x0, void* trace_xt, void* hip_stream);
 
+/* B independent requests in ONE sampler call: every request brings its own guidance scale, its own schedule (levels and their number),
+ * an optional negative label in place of the zero "uncond" label of tld/diffusion.py:61, and its own image-to-image start.  It replaces what a serving
+ * loop around the reference does one call at a time (tld/app.py:48-65, one prompt, one guidance value, one n_iter per call) and cannot be done from
+ * outside here because the loop runs on the device.  Request b's result is bit for bit what tld_sample / tld_sample_from return for that request alone.
+ *   noise       [batch, C, S, S] fp32 device: eps of every request
+ *   init_latent [batch, C, S, S] fp32 device, or NULL when mask is NULL and every start_mix is 1
+ *   mask        [batch, 1, S, S] fp32 device in [0, 1] (1 = regenerate), or NULL.  A text-to-image request in a call that carries masks takes an
+ *               all-ones mask and any finite init_latent: the blends are then the identity, bit for bit
+ *   labels      [batch, text_emb] fp32 device;  neg_labels [batch, text_emb] fp32 device or NULL: row b is read when requests[b].has_negative
+ *   requests    HOST array of batch records, ordered by NON-INCREASING n_levels (TLD_ERR_INVALID otherwise; the Python layer sorts and un-sorts)
+ *   coeffs      [batch, n_max, 6] fp32 HOST: row b holds schedule.step_coefficients of request b (its REMAINING levels, as in tld_sample_from); entries
+ *               past requests[b].n_levels are ignored.  n_max = requests[0].n_levels
+ *   sharp_f, bright_f: per call, as in tld_sample
+ *   out_latent  [batch, C, S, S] fp32 device; trace_x0 / trace_xt: optional [n_max-1, batch, C, S, S] fp32 device.  Request b fills its first
+ *               n_levels[b] - 1 slots; the slots of a request that has already finished are left unwritten
+ * All requests start at step 0.  Step i runs the model on the requests with n_levels > i only (a prefix, by the ordering), CFG-doubled: a finished
+ * request is not computed again, so the call makes 2 x sum(n_levels) model-sample forwards.  Request b's final step, i = n_levels[b] - 1, writes
+ * out_latent[b] (mask blend with init_latent, then the shifts).  The elementwise step is one launch per step of update_from_kernel's sibling, which reads
+ * (g, a, b, c, c1, c2, s_next, final) per sample from a device table uploaded once per call.  Conditioning rows: one per DISTINCT float32 sigma of all
+ * (request, step) pairs -- requests that share a schedule share rows -- then batch label rows, one zero row and one row per request with has_negative;
+ * a call that needs more than 1024 of them is refused (TLD_ERR_INVALID, the count in the message).
+ * Same rules as tld_sample otherwise: batch*2 <= max_batch, no stream synchronisation (the host tables travel through the engine's pinned staging
+ * buffer), noise / init_latent / mask must stay valid until the enqueued work has run.  Under tld_engine_set_debug(1) the call records its launch paths
+ * (bits 58-60) but keeps NO stage; tld_engine_read_stage of a step.* or blk* name after it is "no such stage".  Every refusal happens before anything
+ * is enqueued. */
+typedef struct tld_sample_request {
+    int32_t n_levels;         /* >= 2 */
+    float class_guidance;     /* finite */
+    float start_mix;          /* in (0, 1]: x_start = s0 eps + (1 - s0) z0; exactly 1 = eps itself (copied, not mixed) */
+    int32_t has_negative;     /* != 0: the unconditional half of this request reads neg_labels[b] */
+} tld_sample_request;
+TLD_API int tld_sample_requests(tld_engine* e, const void* noise, const void* init_latent, const void* mask, const void* labels, const void* neg_labels,
+               const tld_sample_request* requests, const float* coeffs, int32_t n_max, float sharp_f, float bright_f, void* out_latent,
+               int32_t batch, void* trace_x0, void* trace_xt, void* hip_stream);
+
 /* Test hook: stage capture of the inference forward (what tld_train_set_debug is to the training step).  With debug on, a forward
  * (tld_denoiser_forward, or every step of tld_sample / tld_sample_from)
  *   - first fills every engine-owned activation, statistics, seam and split-K buffer -- and, once per call, the conditioning tables -- with 0xFF bytes
@@ -177,8 +212,9 @@ TLD_API int tld_sample_from(tld_engine* e, const void* noise, const void* init_l
  *   43 split-K finisher <12> (d 768)   44 <6> (d 384)   45-48 tail_mfma<1..4>   49 tail plain
  *   50 update   51 update_from without a mask   52 update_from with a mask   53 start_mix
  *   writers of the MX-fp8 A operand (with bit 10): 54 separate quantisation pass   55 cross_row_mfma writing e4m3   56 depthwise tiled writing e4m3
- *   57 depthwise streaming writing e4m3 */
-#define TLD_ENGINE_PATH_BITS 58
+ *   57 depthwise streaming writing e4m3
+ *   tld_sample_requests: 58 update_requests without a mask   59 update_requests with a mask   60 start_mix per request */
+#define TLD_ENGINE_PATH_BITS 61
 TLD_API int tld_engine_set_debug(tld_engine* e, int32_t enable);
 /* host_out fp32 [numel]; numel must match the stage (TLD_ERR_SHAPE otherwise).  Synchronises the device. */
 TLD_API int tld_engine_read_stage(tld_engine* e, const char* name, float* host_out, int64_t numel);

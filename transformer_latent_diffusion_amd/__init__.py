@@ -3,7 +3,7 @@
 from .configs import ClipConfig, DenoiserConfig, DenoiserLoad, LTDConfig, VaeConfig, config_100m  # noqa: F401
 from .denoiser import Denoiser  # noqa: F401
 from .diffusion import DiffusionGenerator, DiffusionTransformer, RequestBatcher, latent_mask  # noqa: F401
-from .sharded import generate_latents_from_sharded  # noqa: F401
+from .sharded import generate_latents_from_sharded, generate_latents_requests_sharded  # noqa: F401
 from .vae import AutoencoderKLDecoder, VaeDecoderConfig  # noqa: F401
 from .vae_encoder import AutoencoderKL, AutoencoderKLEncoder, DiagonalGaussianDistribution, VaeEncoderConfig, encode_image  # noqa: F401
 from .clip_text import ClipTextConfig, ClipTextEncoder  # noqa: F401
@@ -13,4 +13,4 @@ from .train import TrainConfig, Trainer  # noqa: F401
 __all__ = ["ClipConfig", "DenoiserConfig", "DenoiserLoad", "LTDConfig", "VaeConfig", "config_100m", "Denoiser",
            "DiffusionGenerator", "DiffusionTransformer", "RequestBatcher", "AutoencoderKLDecoder", "VaeDecoderConfig",
            "AutoencoderKL", "AutoencoderKLEncoder", "DiagonalGaussianDistribution", "VaeEncoderConfig", "encode_image", "ClipTextConfig", "ClipTextEncoder", "ClipTokenizer", "TrainConfig", "Trainer",
-           "latent_mask", "generate_latents_from_sharded"]
+           "latent_mask", "generate_latents_from_sharded", "generate_latents_requests_sharded"]

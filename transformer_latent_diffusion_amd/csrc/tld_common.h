@@ -315,7 +315,9 @@ enum : int {
     EP_TAIL_MFMA = 45 /* +0..3: NT 1..4 */, EP_TAIL_PLAIN = 49, EP_UPDATE = 50, EP_UPDATE_FROM = 51, EP_UPDATE_FROM_MASK = 52, EP_START_MIX = 53,
     // fp8 GEMM mode, the writers of the MX-fp8 A operand (bit 10 is the quantising LayerNorm)
     EP_QUANT_MX8 = 54, EP_CROSS_F8 = 55, EP_DW_TILED_F8 = 56, EP_DW_STREAM_F8 = 57,
-    EP_COUNT = 58
+    // tld_sample_requests
+    EP_UPDATE_REQ = 58, EP_UPDATE_REQ_MASK = 59, EP_START_MIX_REQ = 60,
+    EP_COUNT = 61
 };
 extern thread_local uint64_t* g_path_sink;
 inline void note_path(int bit) { if (g_path_sink) *g_path_sink |= 1ull << bit; }
@@ -438,6 +440,30 @@ struct UpdateFromParams {
 void launch_update_from(const UpdateFromParams& p, hipStream_t s);
 // x_t = s0 noise + (1 - s0) z0 over n elements
 void launch_start_mix(const float* noise, const float* z0, float s0, float* x_t, int n, hipStream_t s);
+
+// the same step for B independent requests in one call (tld_sample_requests): what UpdateParams / UpdateFromParams carry per call
+// is read per sample from a device table, one row per (step, request)
+struct UpdateRequestRow {
+    float g, a, b, c, c1, c2;     // class guidance and the step's coefficients of the request (schedule.py)
+    float s_next;                 // noise level the updated x_t sits at (unused on the request's final step)
+    int final_step;               // 1: the request's last level -- combine (+ mask blend, + shifts) into out_latent, no update
+};
+struct UpdateRequestsParams {
+    const float* x0_2b;           // [2 active, img] model output of the step: cond rows of the active prefix, then their uncond rows
+    float* x_t;                   // [B, img]  in/out
+    float* x0_prev;               // [B, img]  in/out
+    float* out_latent;            // [B, img]  written by a request's final step only
+    float* trace_x0; float* trace_xt;  // optional, this step's [B, img] slot
+    const float* noise;           // [B, img]  (read with a mask only)
+    const float* z0;              // [B, img]  (read with a mask only)
+    const float* mask;            // [B, chan_stride]; null: no blend
+    const UpdateRequestRow* rows; // [active] this step's rows of the device table
+    float sharp, bright;
+    int active, img, chan_stride; // requests still running at this step (a prefix: the records are ordered by non-increasing level count)
+};
+void launch_update_requests(const UpdateRequestsParams& p, hipStream_t s);
+// x_t[b] = s0[b] noise[b] + (1 - s0[b]) z0[b] with s0 read per sample from a device table; s0[b] == 1 copies noise[b] (z0 may then be null)
+void launch_start_mix_requests(const float* noise, const float* z0, const float* s0, float* x_t, int batch, int img, hipStream_t s);
 
 // ---- conditioning path (fp32) ------------------------------------------------------------------
 // out[t, n] = act(sum_k in[t,k] W[n,k] + b[n]);  act: 0 none, 1 exact GELU

@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <map>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 using namespace tld;
@@ -150,6 +151,8 @@ struct tld_engine {
     void* stage_host = nullptr;        // pinned staging for tld_sample's sigma / row tables
     size_t stage_cap = 0;
     hipEvent_t stage_ev = nullptr;     // recorded after the last copy out of stage_host
+    void* req_dev = nullptr;           // tld_sample_requests: the per-(step, request) update rows, then the per-request start mixes
+    size_t req_cap = 0;
 
     // conditioning tables (sized for cond_cap token rows)
     int cond_cap = 0;
@@ -236,6 +239,14 @@ int ensure_rows_capacity(tld_engine* e, int64_t n) {
     if (n <= e->rows_cap) return TLD_OK;
     if (int rc = dev_alloc(e, &e->rows_dev, (size_t)n)) return rc;
     e->rows_cap = n;
+    return TLD_OK;
+}
+
+int ensure_req_capacity(tld_engine* e, size_t bytes) {
+    if (bytes <= e->req_cap) return TLD_OK;
+    char* q = nullptr;
+    if (int rc = dev_alloc(e, &q, bytes)) return rc;      // grow-only, like the row tables
+    e->req_dev = q; e->req_cap = bytes;
     return TLD_OK;
 }
 
@@ -1271,6 +1282,154 @@ int tld_sample_from(tld_engine* e, const void* noise, const void* init_latent, c
             launch_update_from(uf, s);
         }
         if (int rc = step_end(e, uf.u, B, s)) return rc;
+    }
+    HIP_TRY(hipGetLastError());
+    return TLD_OK;
+}
+
+// the most conditioning token rows one tld_sample_requests call may need (distinct sigmas + label rows): at the 100 M width a row of cond.wq + cond.kv is
+// about 0.52 MB, so the grow-only tables stay near 0.5 GiB
+constexpr int kMaxRequestCondRows = 1024;
+
+int tld_sample_requests(tld_engine* e, const void* noise, const void* init_latent, const void* mask, const void* labels, const void* neg_labels,
+                        const tld_sample_request* requests, const float* coeffs, int32_t n_max, float sharp_f, float bright_f, void* out_latent,
+                        int32_t batch, void* trace_x0, void* trace_xt, void* hip_stream) {
+    // the records first: their checks need no engine and no device
+    if (!requests || !coeffs || batch <= 0) return fail(TLD_ERR_INVALID, "null argument");
+    if (mask && !init_latent) return fail(TLD_ERR_INVALID, "init_latent is required with a mask");
+    const int B = batch;
+    int n_neg = 0;
+    bool any_mix = false;
+    for (int b = 0; b < B; ++b) {
+        const tld_sample_request& r = requests[b];
+        if (r.n_levels < 2) return fail(TLD_ERR_INVALID, "request %d: need at least two noise levels (have %d)", b, r.n_levels);
+        if (r.n_levels > n_max) return fail(TLD_ERR_INVALID, "request %d: %d levels beside a coefficient table of n_max = %d", b, r.n_levels, n_max);
+        if (b > 0 && r.n_levels > requests[b - 1].n_levels)
+            return fail(TLD_ERR_INVALID, "request %d has %d levels after request %d with %d: the records must be ordered by non-increasing n_levels", b,
+                        r.n_levels, b - 1, requests[b - 1].n_levels);
+        if (!(r.start_mix > 0.0f && r.start_mix <= 1.0f)) return fail(TLD_ERR_INVALID, "request %d: start_mix %g outside (0, 1]", b, (double)r.start_mix);
+        if (!std::isfinite(r.class_guidance)) return fail(TLD_ERR_INVALID, "request %d: class_guidance is not finite", b);
+        if (r.start_mix < 1.0f) {
+            if (!init_latent) return fail(TLD_ERR_INVALID, "request %d: init_latent is required with start_mix < 1", b);
+            any_mix = true;
+        }
+        if (r.has_negative) {
+            if (!neg_labels) return fail(TLD_ERR_INVALID, "request %d: has_negative without neg_labels", b);
+            ++n_neg;
+        }
+    }
+    if (requests[0].n_levels != n_max) return fail(TLD_ERR_INVALID, "n_max = %d, but the longest request has %d levels", n_max, requests[0].n_levels);
+    if (!e || !noise || !labels || !out_latent) return fail(TLD_ERR_INVALID, "null argument");
+    if (!e->finalized) return fail(TLD_ERR_STATE, "weights not finalized");
+    if (2 * batch > e->cfg.max_batch)
+        return fail(TLD_ERR_INVALID, "sampler batch %d needs max_batch >= %d (have %d)", batch, 2 * batch, e->cfg.max_batch);
+
+    // ---- host tables: the distinct float32 sigmas of every (request, step), and the per-step token-row tables over the active prefix
+    std::vector<float> sig;                                   // distinct sigmas, in order of first use
+    std::unordered_map<uint32_t, int> sig_row;                // by bit pattern: requests that share a schedule share rows
+    std::vector<int> noise_idx((size_t)n_max * B, 0), active(n_max, 0);
+    size_t row_ints = 0;
+    for (int i = 0; i < n_max; ++i) {
+        int Bi = 0;
+        while (Bi < B && requests[Bi].n_levels > i) ++Bi;
+        active[i] = Bi;
+        row_ints += (size_t)4 * Bi;
+        for (int b = 0; b < Bi; ++b) {
+            const float sg = coeffs[((size_t)b * n_max + i) * 6 + 0];
+            uint32_t bits; memcpy(&bits, &sg, 4);
+            auto it = sig_row.find(bits);
+            if (it == sig_row.end()) { it = sig_row.emplace(bits, (int)sig.size()).first; sig.push_back(sg); }
+            noise_idx[(size_t)i * B + b] = it->second;
+        }
+    }
+    const int Tn = (int)sig.size(), T = Tn + B + 1 + n_neg;
+    if (T > kMaxRequestCondRows)
+        return fail(TLD_ERR_INVALID, "the call needs %d conditioning rows (%d distinct noise levels + %d labels + 1 + %d negative labels): at most %d", T, Tn,
+                    B, n_neg, kMaxRequestCondRows);
+    DeviceGuard dg(e->cfg.device_id);
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    PathScope paths(e);
+    if (int rc = ensure_cond_capacity(e, T)) return rc;
+    if (int rc = ensure_rows_capacity(e, (int64_t)row_ints)) return rc;
+    const size_t tab_bytes = (size_t)n_max * B * sizeof(UpdateRequestRow), mix_bytes = (size_t)B * sizeof(float);
+    if (int rc = ensure_req_capacity(e, tab_bytes + mix_bytes)) return rc;
+    if (int rc = debug_begin(e, T, Tn, s)) return rc;         // (debug: the launch paths are recorded; no stage of this entry is kept)
+    if (int rc = stage_acquire(e, tab_bytes + mix_bytes + (size_t)Tn * sizeof(float) + row_ints * sizeof(int))) return rc;
+    UpdateRequestRow* tab = static_cast<UpdateRequestRow*>(e->stage_host);
+    float* mix = reinterpret_cast<float*>(tab + (size_t)n_max * B);
+    float* sigs = mix + B;
+    int* rows = reinterpret_cast<int*>(sigs + Tn);
+    std::vector<int> neg_row(B, Tn + B);                      // the unconditional label row of each request: the zero row, or its own negative
+    for (int b = 0, k = 0; b < B; ++b) {
+        mix[b] = requests[b].start_mix;
+        if (requests[b].has_negative) neg_row[b] = Tn + B + 1 + k++;
+    }
+    memcpy(sigs, sig.data(), (size_t)Tn * sizeof(float));
+    std::vector<size_t> step_rows(n_max);                     // offset of step i's [noise rows 2 Bi | label rows 2 Bi] in the row table
+    for (size_t i = 0, at = 0; i < (size_t)n_max; ++i) {
+        const int Bi = active[i];
+        step_rows[i] = at;
+        int* nr = rows + at; int* lr = nr + 2 * Bi;
+        for (int b = 0; b < Bi; ++b) {
+            nr[b] = nr[Bi + b] = noise_idx[i * B + b];
+            lr[b] = Tn + b; lr[Bi + b] = neg_row[b];
+            const float* c = coeffs + ((size_t)b * n_max + i) * 6;
+            const int nl = requests[b].n_levels;
+            UpdateRequestRow& u = tab[i * B + b];
+            u.g = requests[b].class_guidance; u.a = c[1]; u.b = c[2]; u.c = c[3]; u.c1 = c[4]; u.c2 = c[5];
+            u.s_next = ((int)i + 1 < nl) ? c[6] : 0.0f;       // sigma of the request's next row
+            u.final_step = ((int)i == nl - 1) ? 1 : 0;
+        }
+        for (int b = Bi; b < B; ++b) tab[i * B + b] = UpdateRequestRow{};
+        at += (size_t)4 * Bi;
+    }
+
+    // ---- conditioning tables for every request's whole trajectory, once
+    const size_t text = e->text;
+    HIP_TRY(hipMemcpyAsync(e->c_sigma, sigs, (size_t)Tn * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(e->c_label, labels, (size_t)B * text * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemsetAsync(e->c_label + (size_t)B * text, 0, text * sizeof(float), s));     // uncond = zeros (diffusion.py:61)
+    for (int b = 0; b < B; ) {                                 // negative labels, compacted: one copy per run of consecutive requests that have one
+        if (!requests[b].has_negative) { ++b; continue; }
+        int b1 = b;
+        while (b1 < B && requests[b1].has_negative) ++b1;
+        HIP_TRY(hipMemcpyAsync(e->c_label + (size_t)(neg_row[b] - Tn) * text, static_cast<const float*>(neg_labels) + (size_t)b * text,
+                               (size_t)(b1 - b) * text * sizeof(float), hipMemcpyDeviceToDevice, s));
+        b = b1;
+    }
+    {
+        ProfScope ps(e, KC_COND, s);
+        cond_noise_rows(e, Tn, s);
+        cond_label_rows(e, Tn, B + 1 + n_neg, s);
+    }
+    if (int rc = cond_tables(e, T, s)) return rc;
+    HIP_TRY(hipMemcpyAsync(e->rows_dev, rows, row_ints * sizeof(int), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(e->req_dev, tab, tab_bytes + mix_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(e->stage_ev, s));     // no stream sync: the staging buffer is the engine's, guarded by this event
+    e->dbg_batch = 2 * B; e->dbg_T = T;
+    const UpdateRequestRow* tab_dev = static_cast<const UpdateRequestRow*>(e->req_dev);
+    const float* mix_dev = reinterpret_cast<const float*>(tab_dev + (size_t)n_max * B);
+
+    // ---- the start of every request, then the steps over the shrinking prefix of requests that still run
+    const size_t tot = (size_t)B * e->img;
+    if (!any_mix) HIP_TRY(hipMemcpyAsync(e->xt, noise, tot * sizeof(float), hipMemcpyDeviceToDevice, s));
+    else launch_start_mix_requests(static_cast<const float*>(noise), static_cast<const float*>(init_latent), mix_dev, e->xt, B, e->img, s);
+    HIP_TRY(hipMemsetAsync(e->x0_prev, 0, tot * sizeof(float), s));
+    for (int i = 0; i < n_max; ++i) {
+        const int Bi = active[i];
+        const int* nr = e->rows_dev + step_rows[i];
+        if (int rc = run_body(e, e->xt, Bi, 2 * Bi, nr, nr + 2 * Bi, e->io_out, s, true)) return rc;
+        UpdateRequestsParams up{};
+        up.x0_2b = e->io_out; up.x_t = e->xt; up.x0_prev = e->x0_prev; up.out_latent = static_cast<float*>(out_latent);
+        up.trace_x0 = (i < n_max - 1 && trace_x0) ? static_cast<float*>(trace_x0) + (size_t)i * tot : nullptr;
+        up.trace_xt = (i < n_max - 1 && trace_xt) ? static_cast<float*>(trace_xt) + (size_t)i * tot : nullptr;
+        up.noise = static_cast<const float*>(noise); up.z0 = static_cast<const float*>(init_latent); up.mask = static_cast<const float*>(mask);
+        up.rows = tab_dev + (size_t)i * B; up.sharp = sharp_f; up.bright = bright_f;
+        up.active = Bi; up.img = e->img; up.chan_stride = e->cfg.image_size * e->cfg.image_size;
+        {
+            ProfScope ps(e, KC_UPDATE, s);
+            launch_update_requests(up, s);
+        }
     }
     HIP_TRY(hipGetLastError());
     return TLD_OK;

@@ -7,6 +7,7 @@
 //   update_kernel       CFG combine + DPM-Solver++(2M)/DDIM update + latent shifts    tld/diffusion.py:66-89,122-125
 //   update_from_kernel  the same step of a trajectory that starts from an image, + the inpainting blend
 //   start_mix_kernel    x_start = s0 eps + (1 - s0) z0, the forward process of tld/train.py:130
+//   update_requests_kernel / start_mix_requests_kernel   the same two with per-sample scalars from a device table
 //   dwconv_gelu_kernel  depthwise 3x3 + bias + exact GELU, channels-last              tld/transformer_blocks.py:96-103
 //
 // Row layout: a wave owns one token row of d features; lane l holds features {2l, 2l+1} + 128*j
@@ -1124,6 +1125,88 @@ __global__ __launch_bounds__(256) void start_mix_kernel(const float* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------
+// update_from_kernel's sibling for tld_sample_requests: B independent requests in one launch, each with its own guidance,
+// coefficients and final step, read from rows[sample].  The arithmetic is update_from_kernel's, expression by expression (contraction off,
+// the same three spelled-out roundings, the same m a + (1 - m) b blends), so request b's elements carry the bits the batch-1 call of
+// update_kernel / update_from_kernel writes for it.  The launch covers the `active` requests still running at this step; the unconditional
+// operand of sample b sits `active` samples after its conditional one.  A thread's V elements share a sample (img % 4 == 0), hence a row.
+template <bool MASK, int V>
+__global__ __launch_bounds__(256) void update_requests_kernel(UpdateRequestsParams p) {
+#pragma clang fp contract(off)
+    const int i = (blockIdx.x * 256 + threadIdx.x) * V;
+    const int n = p.active * p.img;
+    if (i >= n) return;
+    float cond[V], unc[V], prev[V], xin[V], eps[V], z[V], m[V], x0o[V], xto[V];
+    auto load = [&](float* dst, const float* src) {
+        if constexpr (V == 4) *reinterpret_cast<float4*>(dst) = *reinterpret_cast<const float4*>(src);
+        else dst[0] = src[0];
+    };
+    auto store = [&](float* dst, const float* src) {
+        if constexpr (V == 4) *reinterpret_cast<float4*>(dst) = *reinterpret_cast<const float4*>(src);
+        else dst[0] = src[0];
+    };
+    const int b = i / p.img, r = i - b * p.img;
+    const int ch = r / p.chan_stride;
+    const UpdateRequestRow q = p.rows[b];
+    load(cond, p.x0_2b + i);
+    load(unc, p.x0_2b + n + i);
+    if constexpr (MASK) {
+        load(m, p.mask + (size_t)b * p.chan_stride + (r - ch * p.chan_stride));
+        load(z, p.z0 + i);
+    }
+    if (q.final_step) {
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            float x0 = __builtin_fmaf(q.g, cond[v], (1.0f - q.g) * unc[v]);   // diffusion.py:124-125
+            if constexpr (MASK) x0 = m[v] * x0 + (1.0f - m[v]) * z[v];
+            if (ch == 3) x0 += p.sharp;                                   // diffusion.py:88
+            if (ch == 0) x0 += p.bright;                                  // diffusion.py:89
+            x0o[v] = x0;
+        }
+        store(p.out_latent + i, x0o);
+        return;
+    }
+    load(prev, p.x0_prev + i);
+    load(xin, p.x_t + i);
+    if constexpr (MASK) load(eps, p.noise + i);
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+        const float x0 = __builtin_fmaf(q.g, cond[v], (1.0f - q.g) * unc[v]);
+        const float D = __builtin_fmaf(q.c1, x0, -(q.c2 * prev[v]));      // diffusion.py:76 (c1=1,c2=0: :72/:79)
+        float xt = (q.a * D + q.b * xin[v]) / q.c;                        // diffusion.py:81
+        if constexpr (MASK) {
+            const float known = q.s_next * eps[v] + (1.0f - q.s_next) * z[v];
+            xt = m[v] * xt + (1.0f - m[v]) * known;
+        }
+        x0o[v] = x0;
+        xto[v] = xt;
+    }
+    if (p.trace_x0) store(p.trace_x0 + i, x0o);
+    store(p.x_t + i, xto);
+    store(p.x0_prev + i, x0o);
+    if (p.trace_xt) store(p.trace_xt + i, xto);
+}
+
+// start_mix_kernel with the mix of each sample read from s0[sample]; a sample whose s0 is exactly 1 is copied, as tld_sample_from copies it
+template <int V>
+__global__ __launch_bounds__(256) void start_mix_requests_kernel(const float* __restrict__ noise, const float* __restrict__ z0,
+                                                                 const float* __restrict__ s0v, float* __restrict__ x_t, int n, int img) {
+#pragma clang fp contract(off)
+    const int i = (blockIdx.x * 256 + threadIdx.x) * V;
+    if (i >= n) return;
+    const float s0 = s0v[i / img];
+    if constexpr (V == 4) {
+        const float4 e = *reinterpret_cast<const float4*>(noise + i);
+        if (s0 == 1.0f) { *reinterpret_cast<float4*>(x_t + i) = e; return; }
+        const float4 z = *reinterpret_cast<const float4*>(z0 + i);
+        const float t = 1.0f - s0;
+        *reinterpret_cast<float4*>(x_t + i) = make_float4(s0 * e.x + t * z.x, s0 * e.y + t * z.y, s0 * e.z + t * z.z, s0 * e.w + t * z.w);
+    } else {
+        x_t[i] = s0 == 1.0f ? noise[i] : s0 * noise[i] + (1.0f - s0) * z0[i];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Depthwise 3x3 + bias + exact GELU.  One workgroup = one sample x 64 channels: the whole g x g image
 // slab (g*g tokens x 128 B) is pulled into LDS once with 16-B coalesced loads, so HBM/L2 see every input
 // exactly once (the register-window version re-read each row three times through L2).  Thread (row i,
@@ -1546,6 +1629,32 @@ void launch_start_mix(const float* noise, const float* z0, float s0, float* x_t,
         hipLaunchKernelGGL((start_mix_kernel<4>), dim3((n / 4 + 255) / 256), dim3(256), 0, s, noise, z0, s0, x_t, n);
     else
         hipLaunchKernelGGL((start_mix_kernel<1>), dim3((n + 255) / 256), dim3(256), 0, s, noise, z0, s0, x_t, n);
+}
+
+void launch_update_requests(const UpdateRequestsParams& p, hipStream_t s) {
+    const int n = p.active * p.img;
+    // as launch_update_from: 16-byte accesses need four consecutive elements in one sample, one channel and one aligned mask quad
+    const bool vec = p.img % 4 == 0 && p.chan_stride % 4 == 0 && aligned16(p.x0_2b) && aligned16(p.x_t) && aligned16(p.x0_prev) && aligned16(p.out_latent) &&
+                     aligned16(p.trace_x0) && aligned16(p.trace_xt) && aligned16(p.noise) && aligned16(p.z0) && aligned16(p.mask);
+    const int threads = vec ? n / 4 : n;
+    const dim3 grid((threads + 255) / 256), block(256);
+    note_path(p.mask ? EP_UPDATE_REQ_MASK : EP_UPDATE_REQ);
+    if (p.mask) {
+        if (vec) hipLaunchKernelGGL((update_requests_kernel<true, 4>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((update_requests_kernel<true, 1>), grid, block, 0, s, p);
+    } else {
+        if (vec) hipLaunchKernelGGL((update_requests_kernel<false, 4>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((update_requests_kernel<false, 1>), grid, block, 0, s, p);
+    }
+}
+
+void launch_start_mix_requests(const float* noise, const float* z0, const float* s0, float* x_t, int batch, int img, hipStream_t s) {
+    const int n = batch * img;
+    note_path(EP_START_MIX_REQ);
+    if (img % 4 == 0 && aligned16(noise) && aligned16(z0) && aligned16(x_t))
+        hipLaunchKernelGGL((start_mix_requests_kernel<4>), dim3((n / 4 + 255) / 256), dim3(256), 0, s, noise, z0, s0, x_t, n, img);
+    else
+        hipLaunchKernelGGL((start_mix_requests_kernel<1>), dim3((n + 255) / 256), dim3(256), 0, s, noise, z0, s0, x_t, n, img);
 }
 
 // Streaming form of the same computation for grids that are a multiple of 32 wide (512 / 1024 px latents; round 3): one workgroup =

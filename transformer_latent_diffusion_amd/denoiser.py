@@ -292,6 +292,96 @@ class Denoiser:
                 C.c_void_p(stream)), "tld_sample_from")
         return (out, tx0, txt) if trace else out
 
+    @torch.no_grad()
+    def sample_latents_requests(self, noise: torch.Tensor, labels: torch.Tensor, coeff_list, guidance, *, neg_labels=None, init_latents=None,
+                                start_mix=None, mask=None, sharp_f: float = 0.0, bright_f: float = 0.0, trace: bool = False):
+        """B independent requests in one on-device sampler call (tld_sample_requests).
+
+        ``noise`` [B,C,S,S], ``labels`` [B,text]; ``coeff_list``: B tables ``schedule.step_coefficients(...)`` (each request's own levels
+        and number of them); ``guidance``: B scales.  ``neg_labels``: None, a [B,text] tensor, or a length-B sequence of [text] tensors /
+        None (a request without one keeps the zero label).  ``init_latents`` [B,C,S,S] + ``start_mix`` (B values in (0, 1], default 1) +
+        ``mask`` [B,1,S,S] as in ``sample_latents_from``; a text-to-image request in a call that carries masks takes an all-ones mask.
+        Request b's result equals, bit for bit, ``sample_latents`` / ``sample_latents_from`` of that request alone.  Returns fp32 latents
+        [B,C,S,S] in the caller's order; with ``trace`` also [n_max-1,B,C,S,S] predictions and states, zero where a request had finished."""
+        from . import schedule
+        dev = self._resolve_device(noise)
+        B = noise.shape[0]
+        if noise.dim() != 4 or tuple(noise.shape[1:]) != (self.n_channels, self.image_size, self.image_size):
+            raise ValueError(f"noise {tuple(noise.shape)}: expected [B,{self.n_channels},{self.image_size},{self.image_size}]")
+        if tuple(labels.shape) != (B, self.text_emb_size):
+            raise ValueError(f"labels {tuple(labels.shape)}: expected {(B, self.text_emb_size)}")
+        tabs = [np.ascontiguousarray(c, dtype=np.float32) for c in coeff_list]
+        guid = [float(g) for g in guidance]
+        mix = [1.0] * B if start_mix is None else [float(v) for v in start_mix]
+        for what, seq in (("coeff_list", tabs), ("guidance", guid), ("start_mix", mix)):
+            if len(seq) != B:
+                raise ValueError(f"{what}: {len(seq)} entries for {B} requests")
+        for b, t in enumerate(tabs):
+            if t.ndim != 2 or t.shape[1] != 6 or t.shape[0] < 2:
+                raise ValueError(f"coeff_list[{b}] {t.shape}: expected [n_levels >= 2, 6]")
+            if not np.isfinite(guid[b]):
+                raise ValueError(f"guidance[{b}] = {guid[b]} is not finite")
+            if not (0.0 < mix[b] <= 1.0):
+                raise ValueError(f"start_mix[{b}] = {mix[b]} outside (0, 1]")
+        if init_latents is not None and tuple(init_latents.shape) != tuple(noise.shape):
+            raise ValueError(f"init_latents {tuple(init_latents.shape)} != noise {tuple(noise.shape)}")
+        if init_latents is None and (mask is not None or any(v < 1.0 for v in mix)):
+            raise ValueError("init_latents is required with a mask or with a start_mix < 1")
+        if mask is not None and tuple(mask.shape) != (B, 1) + tuple(noise.shape[2:]):
+            raise ValueError(f"mask {tuple(mask.shape)}: expected {(B, 1) + tuple(noise.shape[2:])}")
+        neg, has_neg = None, [False] * B
+        if neg_labels is not None:
+            if isinstance(neg_labels, torch.Tensor):
+                if tuple(neg_labels.shape) != (B, self.text_emb_size):
+                    raise ValueError(f"neg_labels {tuple(neg_labels.shape)}: expected {(B, self.text_emb_size)}")
+                neg, has_neg = neg_labels, [True] * B
+            else:
+                rows = list(neg_labels)
+                if len(rows) != B:
+                    raise ValueError(f"neg_labels: {len(rows)} entries for {B} requests")
+                for b, r in enumerate(rows):
+                    if r is not None and tuple(r.shape) != (self.text_emb_size,):
+                        raise ValueError(f"neg_labels[{b}] {tuple(r.shape)}: expected {(self.text_emb_size,)}")
+                has_neg = [r is not None for r in rows]
+                if any(has_neg):
+                    neg = torch.stack([torch.zeros(self.text_emb_size, device=dev) if r is None else r.detach().to(dev, torch.float32) for r in rows])
+        if B == 0:
+            z = torch.empty_like(noise, dtype=torch.float32)
+            return (z, None, None) if trace else z
+        counts = [t.shape[0] for t in tabs]
+        order = schedule.request_order(counts)                  # the engine wants non-increasing level counts: sort here, un-sort the results
+        n_max = counts[order[0]]
+        rows_needed = schedule.request_cond_rows([tabs[b] for b in order], sum(has_neg))
+        if rows_needed > schedule.REQUEST_ROW_CAP:
+            raise ValueError(f"the call needs {rows_needed} conditioning rows (distinct noise levels + labels): at most {schedule.REQUEST_ROW_CAP}")
+        table = np.zeros((B, n_max, 6), dtype=np.float32)
+        recs = (_lib.TldSampleRequest * B)()
+        for k, b in enumerate(order):
+            table[k, :counts[b]] = tabs[b]
+            recs[k] = _lib.TldSampleRequest(counts[b], guid[b], mix[b], int(has_neg[b]))
+        h = self._ensure_engine(2 * B, dev)
+        idx = torch.tensor(order, device=dev)
+
+        def take(t):
+            return None if t is None else t.to(device=dev, dtype=torch.float32)[idx].contiguous()
+
+        eps, lab, z0, m, ng = take(noise), take(labels), take(init_latents), take(mask), take(neg)
+        out = torch.empty_like(eps)
+        tx0 = txt = None
+        if trace:
+            tx0 = torch.zeros((n_max - 1,) + tuple(eps.shape), device=dev, dtype=torch.float32)
+            txt = torch.zeros_like(tx0)
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().tld_sample_requests(
+                h, ptr(eps), ptr(z0), ptr(m), ptr(lab), ptr(ng), recs, table.ctypes.data_as(C.POINTER(C.c_float)), n_max,
+                float(sharp_f), float(bright_f), ptr(out), B, ptr(tx0), ptr(txt), C.c_void_p(stream)), "tld_sample_requests")
+        inv = torch.empty_like(idx)
+        inv[idx] = torch.arange(B, device=dev)
+        out = out[inv]
+        return (out, tx0[:, inv], txt[:, inv]) if trace else out
+
     # ---- test / bench hooks -----------------------------------------------------------------------------
     # launch paths of tld_engine_debug_paths, by bit number (include/tld_hip.h; None: unused bit)
     PATH_NAMES = ("embed plain", "embed_mfma<2>", "embed_mfma<4>", "embed_mfma<6>", "embed_mfma<8>", "layernorm q4<1>", "layernorm q4<2>", "layernorm q4<3>",
@@ -305,6 +395,9 @@ class Denoiser:
     # the writers of the MX-fp8 A operand, by bit number (bit 10 is in PATH_NAMES too): held by tests/test_gpu_fp8_stages.py
     FP8_PATH_NAMES = {10: "layernorm mx8", 54: "fp8 separate quantisation pass", 55: "fp8 cross_row writer", 56: "fp8 depthwise tiled",
                       57: "fp8 depthwise streaming"}
+
+    # the launch paths of sample_latents_requests, by bit number
+    SAMPLER_PATH_NAMES = {58: "update_requests", 59: "update_requests masked", 60: "start_mix per request"}
 
     def set_debug(self, enable: bool = True):
         """Stage capture of the forward (``tld_engine_set_debug``): allocates (frees) the snapshot memory of the current engine."""

@@ -135,6 +135,95 @@ class DiffusionGenerator:
             return lat.to(self.model_dtype), tx0, txt
         return out.to(self.model_dtype)
 
+    @torch.no_grad()
+    def generate_latents_requests(self, labels, *, n_iter=30, class_guidance=3, negative_labels=None, seed=10, seeds=None, img_size=None,
+                                  sharp_f=0.1, bright_f=0.1, exponent=1, noise_levels=None, use_ddpm_plus=True, init_latents=None,
+                                  strength=None, mask=None, trace=False):
+        """B independent requests in ONE sampler call (``Denoiser.sample_latents_requests``): each of ``n_iter``,
+        ``class_guidance``, ``exponent``, ``strength`` and ``use_ddpm_plus`` is a scalar (for all) or a length-B sequence.  Request b's latent
+        is bit for bit what ``generate_latents`` / ``generate_latents_from`` return for that request alone with the same noise.
+
+        ``negative_labels``: None, a [B,text] tensor, or a length-B sequence of [text] tensors / None -- the label of the unconditional half
+        of the guidance pair instead of zeros (a negative prompt's embedding).  ``seeds``: the noise [B,C,S,S], or one int per request
+        (each request's own ``initialize_image(None, 1, size, seed)``, as ``generate_images_from_texts`` draws it); else ``seed`` draws the
+        whole batch as ``generate_latents`` does.  ``init_latents`` [B,C,S,S] with ``strength`` (an entry None or 1.0: the text-to-image
+        trajectory) and ``mask`` [B,1,S,S] as in ``generate_latents_from``; a sequence entry None stands for zeros (init) / all ones (mask).
+        Schedules are built per request with ``schedule.noise_schedule`` / ``truncate_levels`` / ``step_coefficients``, so the float64 scalars
+        are exactly those of the solo call.  Shapes and ranges are checked on the host before anything is enqueued."""
+        B = labels.size(0)
+        size = self.model.image_size if img_size is None else img_size
+
+        def per_request(v, what, scalar=(numbers.Number, bool, type(None))):
+            if isinstance(v, scalar) or (isinstance(v, Tensor) and v.dim() == 0):
+                return [v] * B
+            v = list(v)
+            if len(v) != B:
+                raise ValueError(f"{what}: {len(v)} entries for {B} requests")
+            return v
+
+        n_it, guid = per_request(n_iter, "n_iter"), per_request(class_guidance, "class_guidance")
+        expo, plus, stren = per_request(exponent, "exponent"), per_request(use_ddpm_plus, "use_ddpm_plus"), per_request(strength, "strength")
+        for b in range(B):
+            if not np.isfinite(float(guid[b])):
+                raise ValueError(f"class_guidance[{b}] = {guid[b]} is not finite")
+
+        def stacked(v, what, shape, fill):
+            if v is None or isinstance(v, Tensor):
+                if v is not None and tuple(v.shape) != (B,) + shape:
+                    raise ValueError(f"{what} {tuple(v.shape)}: expected {(B,) + shape}")
+                return v
+            v = per_request(v, what, scalar=())
+            if all(t is None for t in v):
+                return None
+            for b, t in enumerate(v):
+                if t is not None and tuple(t.shape) != shape:
+                    raise ValueError(f"{what}[{b}] {tuple(t.shape)}: expected {shape}")
+            return torch.stack([torch.full(shape, fill) if t is None else t.detach().to("cpu", torch.float32) for t in v])
+
+        C_ = self.model.n_channels
+        z0 = stacked(init_latents, "init_latents", (C_, size, size), 0.0)
+        m = stacked(mask, "mask", (1, size, size), 1.0)
+        if m is not None and m.numel() and not (float(m.min()) >= 0.0 and float(m.max()) <= 1.0):
+            raise ValueError(f"mask values span [{float(m.min())}, {float(m.max())}]: expected [0, 1] (1 = regenerate, 0 = keep)")
+        if z0 is None and (m is not None or any(v is not None and float(v) != 1.0 for v in stren)):
+            raise ValueError("init_latents is required with a mask or a strength below 1")
+        coeffs, mix = [], []
+        for b in range(B):
+            if int(n_it[b]) < 2 and noise_levels is None:
+                raise ValueError(f"n_iter[{b}] = {n_it[b]}: a trajectory needs at least two noise levels")
+            levels = schedule.noise_schedule(int(n_it[b]), expo[b], noise_levels)
+            k = 0
+            if stren[b] is not None:
+                k, levels = schedule.truncate_levels(levels, stren[b])
+            coeffs.append(schedule.step_coefficients(levels, bool(plus[b])))
+            mix.append(float(np.float32(levels[0])) if k > 0 else 1.0)
+        if seeds is None:
+            eps = self.initialize_image(None, B, size, seed)
+        elif isinstance(seeds, Tensor):
+            eps = self.initialize_image(seeds, B, size, seed)
+        else:
+            eps = torch.cat([self.initialize_image(None, 1, size, int(v)) for v in per_request(seeds, "seeds", scalar=())]) if B else \
+                self.initialize_image(None, 0, size, seed)
+        if eps.size(0) != B:
+            raise RuntimeError(f"labels batch {B} != noise batch {eps.size(0)}")
+        self.model.eval()
+        out = self.model.sample_latents_requests(eps, labels.to(self.device), coeffs, [float(g) for g in guid], neg_labels=negative_labels,
+                                                 init_latents=z0, start_mix=mix, mask=m, sharp_f=sharp_f, bright_f=bright_f, trace=trace)
+        if trace:
+            lat, tx0, txt = out
+            return lat.to(self.model_dtype), tx0, txt
+        return out.to(self.model_dtype)
+
+    @torch.no_grad()
+    def generate_requests(self, labels, *, scale_factor: int = 8, **kw):
+        """``generate_latents_requests`` plus the VAE decode; returns (decoded_images_on_cpu, latents)."""
+        kw.pop("trace", None)
+        latents = self.generate_latents_requests(labels, **kw)
+        if self.vae is None:
+            return None, latents
+        img = self.vae.decode((latents * scale_factor).to(self.model_dtype))[0].cpu()
+        return img, latents
+
     def initialize_image(self, seeds, num_imgs, img_size, seed):
         """Initial noise (diffusion.py:105-120): the caller's ``seeds`` tensor, or ``torch.randn`` from a
         generator seeded with ``seed``.
@@ -260,12 +349,15 @@ class DiffusionTransformer:
         return self.clip_model.encode_text(self.tokenize(prompts).to(self.device)).cpu()
 
     @torch.no_grad()
-    def generate_images_from_texts(self, prompts, class_guidance=6, seeds=11, n_iter=15):
+    def generate_images_from_texts(self, prompts, class_guidance=6, seeds=11, n_iter=15, negative_prompts=None):
         """Batched front edge (the reference serves one prompt per call, tld/app.py:48-65):
         one text-encoder call for all prompts, labels stay on the device, ONE sampler call (sample-sharded over the
         ranks of the default process group when torch.distributed is initialised), one VAE decode; returns one PIL image
         per prompt.  ``seeds``: an int (request i uses seeds + i) or one int per prompt.  Request i's picture is exactly
-        what ``generate_image_from_text(prompts[i], seed=seeds[i])`` returns: samples never interact."""
+        what ``generate_image_from_text(prompts[i], seed=seeds[i])`` returns: samples never interact.
+        ``class_guidance`` / ``n_iter`` may be one value per prompt and ``negative_prompts`` one string (or None) per prompt, or one string
+        for all: the call then goes through ``generate_latents_requests`` (still one sampler call), and a negative
+        prompt is encoded with the same text encoder in the same call as the prompts.  Scalars and no negatives take the path above."""
         from .sharded import sharded_sample
         prompts = list(prompts)
         n = len(prompts)
@@ -274,6 +366,8 @@ class DiffusionTransformer:
         seed_list = [int(seeds) + i for i in range(n)] if isinstance(seeds, numbers.Integral) else [int(v) for v in seeds]
         if len(seed_list) != n:
             raise ValueError(f"{len(seed_list)} seeds for {n} prompts")
+        if not (isinstance(class_guidance, numbers.Number) and isinstance(n_iter, numbers.Number) and negative_prompts is None):
+            return self._generate_images_requests(prompts, class_guidance, seed_list, n_iter, negative_prompts)
         if self._text_encoder is not None:
             labels = self._text_encoder(prompts)
         else:
@@ -290,8 +384,64 @@ class DiffusionTransformer:
         out = gen.vae.decode((latents * 8).to(gen.model_dtype))[0].cpu()                # scale_factor 8 (diffusion.py:180)
         return [to_pil(((out[i] + 1) / 2).float().clip(0, 1)) for i in range(n)]
 
-    def generate_image_from_text(self, prompt: str, class_guidance=6, seed=11, num_imgs=1, img_size=32, n_iter=15):
+    def _encode_with_negatives(self, prompts, negative_prompts):
+        """Labels of ``prompts`` and of the negative prompts that are not None, from ONE text-encoder call: (labels [n,text], list of n
+        [text] rows / None, or None when no request has a negative prompt)."""
+        n = len(prompts)
+        if negative_prompts is None or isinstance(negative_prompts, str):
+            negs = [negative_prompts] * n
+        else:
+            negs = list(negative_prompts)
+            if len(negs) != n:
+                raise ValueError(f"{len(negs)} negative prompts for {n} prompts")
+        texts = list(prompts) + [str(p) for p in negs if p is not None]
+        if self._text_encoder is not None:
+            emb = self._text_encoder(texts)
+        else:
+            emb = self.clip_model.encode_text(self.tokenize(texts).to(self.device))
+        emb = emb.to(self.device, torch.float32)
+        if len(texts) == n:
+            return emb, None
+        rows, k = [], n
+        for p in negs:
+            rows.append(None if p is None else emb[k])
+            k += p is not None
+        return emb[:n], rows
+
+    @torch.no_grad()
+    def _generate_images_requests(self, prompts, class_guidance, seed_list, n_iter, negative_prompts):
+        """``generate_images_from_texts`` with per-prompt sampler scalars and negative prompts: one encoder call, one sampler call."""
+        from .sharded import sharded_sample
+        n = len(prompts)
+
+        def per_prompt(v, what):
+            v = [v] * n if isinstance(v, numbers.Number) else list(v)
+            if len(v) != n:
+                raise ValueError(f"{len(v)} {what} values for {n} prompts")
+            return v
+
+        guid, n_it = [float(g) for g in per_prompt(class_guidance, "class_guidance")], [int(k) for k in per_prompt(n_iter, "n_iter")]
+        labels, neg_rows = self._encode_with_negatives(prompts, negative_prompts)
+        gen, size = self.diffuser, self.diffuser.model.image_size
+        x_T = torch.cat([gen.initialize_image(None, 1, size, s) for s in seed_list])     # each request's own noise
+
+        def one(xs, ls, which):               # the per-request scalars ride as the requests' indices, sliced like every per-sample tensor
+            w = [int(i) for i in which]
+            return gen.generate_latents_requests(ls, n_iter=[n_it[i] for i in w], class_guidance=[guid[i] for i in w],
+                                                 negative_labels=None if neg_rows is None else [neg_rows[i] for i in w], seeds=xs, img_size=size,
+                                                 sharp_f=0, bright_f=0, exponent=1)
+
+        latents = sharded_sample(one, x_T, labels, extras=(torch.arange(n),))
+        out = gen.vae.decode((latents * 8).to(gen.model_dtype))[0].cpu()                # scale_factor 8 (diffusion.py:180)
+        return [to_pil(((out[i] + 1) / 2).float().clip(0, 1)) for i in range(n)]
+
+    def generate_image_from_text(self, prompt: str, class_guidance=6, seed=11, num_imgs=1, img_size=32, n_iter=15, *, negative_prompt=None):
         nrow = int(np.sqrt(num_imgs))
+        if negative_prompt is not None:       # the unconditional half of the guidance pair reads the negative prompt's label instead of zeros
+            labels, neg = self._encode_with_negatives([prompt] * num_imgs, [negative_prompt] + [None] * (num_imgs - 1))
+            out, _ = self.diffuser.generate_requests(labels, negative_labels=[neg[0]] * num_imgs, n_iter=n_iter, class_guidance=class_guidance,
+                                                     seed=seed, exponent=1, scale_factor=8, sharp_f=0, bright_f=0)
+            return to_pil(make_image_grid((out + 1) / 2, nrow=nrow, padding=4).float().clip(0, 1))
         labels = self.encode_text([prompt] * num_imgs)
         # NOTE: like the reference, ``img_size`` is ignored in favour of the model's own size (:175)
         out, out_latent = self.diffuser.generate(
@@ -303,15 +453,15 @@ class DiffusionTransformer:
 
     @torch.no_grad()
     def generate_image_from_image(self, image, prompt: str, strength=0.6, mask=None, class_guidance=6, seed=11, n_iter=15,
-                                  sample_posterior=False, return_latents=False):
+                                  sample_posterior=False, return_latents=False, *, negative_prompt=None):
         """Image -> image: edit ``image`` towards ``prompt`` at ``strength``, or with ``mask`` regenerate only the masked region.
 
         ``image``: a PIL image or a [3,H,W] tensor in [0,1] with H = W = 8 x the model's latent size (no resizing here).  It is encoded
         with the pipeline's VAE (``vae.encode(2 x - 1).latent_dist``: ``.mode()``, or ``.sample()`` from a generator seeded with ``seed``
         when ``sample_posterior``) and divided by 8 (tld/train.py:122).  ``mask``: PIL "L" image or tensor [H,W] / [1,H,W] at pixel
         resolution, 1 = regenerate; it is area-averaged to the latent grid (``latent_mask``), so only latent cells whose 8 x 8 pixels are
-        all 0 are kept exactly.  Sampler settings as in ``generate_image_from_text``.  Returns a PIL image (with ``return_latents``:
-        (image, latents))."""
+        all 0 are kept exactly.  Sampler settings as in ``generate_image_from_text``; with ``negative_prompt`` the unconditional half of
+        the guidance pair reads that prompt's label (``generate_requests``).  Returns a PIL image (with ``return_latents``: (image, latents))."""
         gen = self.diffuser
         size = gen.model.image_size
         if not isinstance(image, Tensor):
@@ -328,7 +478,11 @@ class DiffusionTransformer:
             if side != 8 * size:
                 raise ValueError(f"mask side {side}: expected the image's {8 * size}")
             m = latent_mask(mask, size).unsqueeze(0)
-        labels = self.encode_text([prompt])
+        neg = None
+        if negative_prompt is None:
+            labels = self.encode_text([prompt])
+        else:
+            labels, neg = self._encode_with_negatives([prompt], [negative_prompt])
         x = (image.to(self.device, torch.float32) * 2 - 1).unsqueeze(0)
         x = x.to(getattr(gen.vae, "dtype", torch.float32))
         dist_ = gen.vae.encode(x).latent_dist
@@ -337,8 +491,12 @@ class DiffusionTransformer:
         else:
             z = dist_.mode()
         z0 = z.to(torch.float32) / 8
-        out, latents = gen.generate_from(z0, labels, strength=strength, mask=m, n_iter=n_iter, class_guidance=class_guidance, seed=seed,
-                                         exponent=1, scale_factor=8, sharp_f=0, bright_f=0)
+        if neg is not None:
+            out, latents = gen.generate_requests(labels, negative_labels=neg, init_latents=z0, strength=strength, mask=m, n_iter=n_iter,
+                                                 class_guidance=class_guidance, seed=seed, exponent=1, scale_factor=8, sharp_f=0, bright_f=0)
+        else:
+            out, latents = gen.generate_from(z0, labels, strength=strength, mask=m, n_iter=n_iter, class_guidance=class_guidance, seed=seed,
+                                             exponent=1, scale_factor=8, sharp_f=0, bright_f=0)
         pic = to_pil(((out[0] + 1) / 2).float().clip(0, 1))
         return (pic, latents) if return_latents else pic
 
@@ -349,27 +507,57 @@ class RequestBatcher:
     ``class_guidance`` and ``n_iter`` are per-call scalars of the sampler, so requests are grouped by that pair;
     inside a group every request keeps its own prompt and seed.  Synchronous by design: ``submit`` queues,
     ``flush`` runs the queued groups (largest first, at most ``max_batch`` requests per sampler call) and returns
-    ``{ticket: PIL.Image}``."""
+    ``{ticket: PIL.Image}``.
 
-    def __init__(self, pipeline: "DiffusionTransformer", max_batch: int = 64):
+    ``mixed=True``: a sampler call carries requests with different scalars (``generate_images_from_texts`` with one guidance value and
+    one ``n_iter`` per prompt), so calls are filled in submission order up to ``max_batch`` whatever the scalars
+    are, a request may bring a negative prompt, and a new call starts where the conditioning rows of one call (distinct noise levels +
+    label rows) would pass ``schedule.REQUEST_ROW_CAP``."""
+
+    def __init__(self, pipeline: "DiffusionTransformer", max_batch: int = 64, mixed: bool = False):
         self.pipeline = pipeline
         self.max_batch = int(max_batch)
+        self.mixed = bool(mixed)
         self._queue = []
         self._next = 0
 
-    def submit(self, prompt: str, class_guidance: float = 6, seed: int = 11, n_iter: int = 15) -> int:
+    def submit(self, prompt: str, class_guidance: float = 6, seed: int = 11, n_iter: int = 15, negative_prompt: Optional[str] = None) -> int:
+        if negative_prompt is not None and not self.mixed:
+            raise ValueError("a negative prompt needs RequestBatcher(mixed=True)")
         ticket = self._next
         self._next += 1
-        self._queue.append((ticket, str(prompt), float(class_guidance), int(seed), int(n_iter)))
+        self._queue.append((ticket, str(prompt), float(class_guidance), int(seed), int(n_iter), None if negative_prompt is None else str(negative_prompt)))
         return ticket
 
     def pending(self) -> int:
         return len(self._queue)
 
+    @staticmethod
+    def call_rows(requests) -> int:
+        """Conditioning rows one mixed call of ``requests`` (``(n_iter, has_negative)`` pairs) needs: the distinct float32 noise levels of
+        their schedules, one label row each, the zero row and one row per negative prompt (``tld_sample_requests``)."""
+        requests = list(requests)
+        sigmas = set()
+        for n, _ in requests:
+            sigmas.update(np.asarray(schedule.noise_schedule(int(n), 1), dtype=np.float32).tolist())
+        return len(sigmas) + len(requests) + 1 + sum(1 for _, neg in requests if neg)
+
     def plan(self):
-        """[(class_guidance, n_iter, [(ticket, prompt, seed), ...]), ...] -- the sampler calls ``flush`` will make."""
+        """[(class_guidance, n_iter, [(ticket, prompt, seed), ...]), ...] -- the sampler calls ``flush`` will make.
+        ``mixed=True``: [[(ticket, prompt, class_guidance, seed, n_iter, negative_prompt), ...], ...], in submission order."""
+        if self.mixed:
+            calls, cur = [], []
+            for q in self._queue:
+                if cur and (len(cur) == self.max_batch or
+                            self.call_rows([(r[4], r[5] is not None) for r in cur + [q]]) > schedule.REQUEST_ROW_CAP):
+                    calls.append(cur)
+                    cur = []
+                cur.append(q)
+            if cur:
+                calls.append(cur)
+            return calls
         groups = {}
-        for t, p, g, s, n in self._queue:
+        for t, p, g, s, n, _ in self._queue:
             groups.setdefault((g, n), []).append((t, p, s))
         calls = []
         for (g, n), reqs in sorted(groups.items(), key=lambda kv: -len(kv[1])):
@@ -382,6 +570,19 @@ class RequestBatcher:
         (bad prompt, out of memory) loses nothing that was already computed: the exception carries ``partial`` = the finished images,
         and a retry only repeats the groups that did not run."""
         out = {}
+        if self.mixed:
+            for reqs in self.plan():
+                kw = {"negative_prompts": [r[5] for r in reqs]} if any(r[5] is not None for r in reqs) else {}
+                try:
+                    imgs = self.pipeline.generate_images_from_texts([r[1] for r in reqs], class_guidance=[r[2] for r in reqs],
+                                                                    seeds=[r[3] for r in reqs], n_iter=[r[4] for r in reqs], **kw)
+                except Exception as exc:
+                    exc.partial = out
+                    raise
+                out.update({r[0]: im for r, im in zip(reqs, imgs)})
+                done = {r[0] for r in reqs}
+                self._queue = [q for q in self._queue if q[0] not in done]
+            return out
         for g, n, reqs in self.plan():
             try:
                 imgs = self.pipeline.generate_images_from_texts([p for _, p, _ in reqs], class_guidance=g,

@@ -138,3 +138,44 @@ def step_coefficients(noise_levels: Sequence[float], use_ddpm_plus: bool = True)
         tab[i] = (curr, curr - nxt, nxt, curr, c1, c2)
     tab[n - 1] = (nl[n - 1], 0.0, 0.0, 1.0, 1.0, 0.0)
     return tab.astype(np.float32)
+
+
+# ---- B requests in one sampler call (tld_sample_requests): the host planning the engine repeats in C ------------------
+REQUEST_ROW_CAP = 1024      # most conditioning rows one call may need: kMaxRequestCondRows in csrc/tld_engine.hip
+
+
+def request_order(level_counts: Sequence[int]) -> List[int]:
+    """Order in which the engine takes the requests: by descending level count, stable (equal counts keep the caller's order), so that the
+    requests still running at step i are a prefix.  ``order[k]`` is the caller's index of the k-th record."""
+    return sorted(range(len(level_counts)), key=lambda b: -int(level_counts[b]))
+
+
+def active_prefix(sorted_counts: Sequence[int]) -> List[int]:
+    """``B_i = #{b : n_levels[b] > i}`` for i = 0 .. n_max - 1 of counts in non-increasing order: the model runs ``2 B_i`` samples at step i."""
+    counts = [int(c) for c in sorted_counts]
+    if any(counts[k] < counts[k + 1] for k in range(len(counts) - 1)):
+        raise ValueError(f"level counts {counts} are not in non-increasing order")
+    return [sum(1 for c in counts if c > i) for i in range(counts[0] if counts else 0)]
+
+
+def distinct_sigma_rows(coeff_list: Sequence[np.ndarray]) -> Tuple[np.ndarray, List[List[int]]]:
+    """Noise rows of a call: the float32 sigmas of every (request, step) deduplicated BY VALUE (bit pattern), in order of first use walking
+    step by step over the requests as given -- the engine's order when they are sorted (``request_order``).  Returns ``(sigmas, rows)`` with
+    ``rows[b][i]`` the row of request b at step i; requests that share a schedule share rows."""
+    tabs = [np.ascontiguousarray(c, dtype=np.float32) for c in coeff_list]
+    seen, sigmas = {}, []
+    rows = [[0] * t.shape[0] for t in tabs]
+    for i in range(max((t.shape[0] for t in tabs), default=0)):
+        for b, t in enumerate(tabs):
+            if i < t.shape[0]:
+                key = t[i, 0].tobytes()
+                if key not in seen:
+                    seen[key] = len(sigmas)
+                    sigmas.append(t[i, 0])
+                rows[b][i] = seen[key]
+    return np.array(sigmas, dtype=np.float32), rows
+
+
+def request_cond_rows(coeff_list: Sequence[np.ndarray], n_negative: int = 0) -> int:
+    """Conditioning rows a call of these requests needs: distinct sigmas + one label row each + the zero row + one per negative label."""
+    return len(distinct_sigma_rows(coeff_list)[0]) + len(coeff_list) + 1 + int(n_negative)

@@ -100,3 +100,42 @@ def generate_latents_from_sharded(gen, init_latents: torch.Tensor, labels: torch
                                          noise_levels=noise_levels, use_ddpm_plus=use_ddpm_plus)
 
     return sharded_sample(one, eps, labels.to(eps.device), group, extras=(init_latents, mask))
+
+
+def generate_latents_requests_sharded(gen, labels: torch.Tensor, *, group: Optional[dist.ProcessGroup] = None, seed: int = 10,
+                                      seeds=None, img_size: Optional[int] = None, negative_labels=None, init_latents=None, mask=None,
+                                      **per_request) -> torch.Tensor:
+    """``DiffusionGenerator.generate_latents_requests`` over all ranks of ``group`` (same arguments, without ``trace``).  The noise,
+    labels, negative labels, initial latents and masks travel as per-sample tensors; the per-request sequences (``n_iter``,
+    ``class_guidance``, ``exponent``, ``strength``, ``use_ddpm_plus``) ride as the requests' indices, one more ``extras`` tensor sliced
+    with the same bounds, and every rank picks its own entries."""
+    B = labels.shape[0]
+    size = gen.model.image_size if img_size is None else img_size
+    if seeds is None or isinstance(seeds, torch.Tensor):
+        eps = gen.initialize_image(seeds, B, size, seed)            # full batch, same on every rank
+    else:
+        eps = torch.cat([gen.initialize_image(None, 1, size, int(v)) for v in seeds])
+
+    def tensor_of(v, shape, fill):                                   # a sequence with None entries -> one [B, ...] tensor
+        if v is None or isinstance(v, torch.Tensor):
+            return v
+        if all(t is None for t in v):
+            return None
+        return torch.stack([torch.full(shape, fill) if t is None else t.detach().to("cpu", torch.float32) for t in v])
+
+    has_neg = None
+    if negative_labels is not None and not isinstance(negative_labels, torch.Tensor):
+        has_neg = [t is not None for t in negative_labels]
+    neg = tensor_of(negative_labels, (labels.shape[1],), 0.0)
+    z0 = tensor_of(init_latents, tuple(eps.shape[1:]), 0.0)
+    m = tensor_of(mask, (1, size, size), 1.0)
+
+    def one(eps_shard, lab_shard, which, neg_shard, z0_shard, mask_shard):
+        w = [int(i) for i in which]
+        kw = {k: (v if not isinstance(v, (list, tuple)) else [v[i] for i in w]) for k, v in per_request.items()}
+        if neg_shard is not None and has_neg is not None:
+            neg_shard = [neg_shard[j] if has_neg[i] else None for j, i in enumerate(w)]
+        return gen.generate_latents_requests(lab_shard, negative_labels=neg_shard, seeds=eps_shard, img_size=size, init_latents=z0_shard,
+                                             mask=mask_shard, **kw)
+
+    return sharded_sample(one, eps, labels.to(eps.device), group, extras=(torch.arange(B), neg, z0, m))
