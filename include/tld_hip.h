@@ -122,8 +122,7 @@ TLD_API int tld_sample(tld_engine* e, const void* x_T, const void* labels, const
  *   start_mix   s0 in (0, 1]: x_start = s0 eps + (1 - s0) z0; exactly 1 = start from eps itself, as tld_sample does
  *   labels, coeffs, n_levels, class_guidance, sharp_f, bright_f, out_latent, batch, trace_x0, trace_xt: as in tld_sample; coeffs holds the
  *               REMAINING levels only (schedule.truncate_levels), so the first step is first-order
- * Every step is tld_sample's (same kernels for the model; the elementwise step is its sibling kernel with the same arithmetic, one launch per
- * step).  With a mask, after the update to level s_next:  x_t <- m x_t + (1 - m) (s_next eps + (1 - s_next) z0),  and on the final prediction
+ * Every step is tld_sample's (same kernels for the model, the same elementwise step kernel, one launch per step).  With a mask, after the update to level s_next:  x_t <- m x_t + (1 - m) (s_next eps + (1 - s_next) z0),  and on the final prediction
  * x0 <- m x0 + (1 - m) z0 before the shifts; both are exact where m is 0 or 1.  x0 of the multistep history and trace_x0 stay unblended.
  * Without a mask and with start_mix = 1 the result equals tld_sample's bit for bit.
  * noise, init_latent and mask are read by every step: they must stay valid until the enqueued work has run.  Same rules as tld_sample otherwise:
@@ -149,7 +148,7 @@ TLD_API int tld_sample_from(tld_engine* e, const void* noise, const void* init_l
  *               n_levels[b] - 1 slots; the slots of a request that has already finished are left unwritten
  * All requests start at step 0.  Step i runs the model on the requests with n_levels > i only (a prefix, by the ordering), CFG-doubled: a finished
  * request is not computed again, so the call makes 2 x sum(n_levels) model-sample forwards.  Request b's final step, i = n_levels[b] - 1, writes
- * out_latent[b] (mask blend with init_latent, then the shifts).  The elementwise step is one launch per step of update_from_kernel's sibling, which reads
+ * out_latent[b] (mask blend with init_latent, then the shifts).  The elementwise step is one launch per step of the kernel tld_sample runs; it reads
  * (g, a, b, c, c1, c2, s_next, final) per sample from a device table uploaded once per call.  Conditioning rows: one per DISTINCT float32 sigma of all
  * (request, step) pairs -- requests that share a schedule share rows -- then batch label rows, one zero row and one row per request with has_negative;
  * a call that needs more than 1024 of them is refused (TLD_ERR_INVALID, the count in the message).
@@ -210,7 +209,8 @@ TLD_API int tld_sample_requests(tld_engine* e, const void* noise, const void* in
  *   35 down projection writing LayerNorm-1 partial sums   36 ... not writing them (last block, or no fold)   37 down projection, 8-wave kernel
  *   38 4-wave form, 64-row tiles   39 4-wave form, 128-row tiles   40 split-K x 4   41 split-K x 8   42 split-K 4-wave form
  *   43 split-K finisher <12> (d 768)   44 <6> (d 384)   45-48 tail_mfma<1..4>   49 tail plain
- *   50 update   51 update_from without a mask   52 update_from with a mask   53 start_mix
+ *   the sampler's step and start kernels, named by the entry that launched them: tld_sample 50 update; tld_sample_from 51 update_from without a mask
+ *   52 update_from with a mask   53 start_mix
  *   writers of the MX-fp8 A operand (with bit 10): 54 separate quantisation pass   55 cross_row_mfma writing e4m3   56 depthwise tiled writing e4m3
  *   57 depthwise streaming writing e4m3
  *   tld_sample_requests: 58 update_requests without a mask   59 update_requests with a mask   60 start_mix per request */

@@ -124,6 +124,59 @@ def test_low_latency_class_2_full_strength_is_its_generate_latents():
     assert torch.isfinite(out).all() and not torch.equal(out, want)
 
 
+@pytest.mark.parametrize("entry", ["plain", "from"])
+def test_long_schedule_has_no_conditioning_row_cap(entry):
+    """1030 levels at batch 2 are 1030 + 2 + 1 > 1024 conditioning rows: the cap of tld_sample_requests (schedule.REQUEST_ROW_CAP) is that
+    entry's alone.  tld_sample and tld_sample_from take the call, return something finite, and repeat it bit for bit."""
+    from transformer_latent_diffusion_amd import schedule
+    cfg, sd, m, gen = _model(TINY)
+    eps, z0, labels = _inputs(2, seed=35)
+    n = 1030
+    assert n + 2 + 1 > schedule.REQUEST_ROW_CAP
+    kw = dict(n_iter=n, class_guidance=3.0, seeds=eps, sharp_f=0.1, bright_f=0.1)
+    if entry == "plain":
+        run = lambda: gen.generate_latents(labels, num_imgs=2, img_size=32, **kw)
+    else:
+        run = lambda: gen.generate_latents_from(z0, labels, strength=1.0, mask=_rect_masks(2), **kw)
+    a = run()
+    assert a.shape == eps.shape and torch.isfinite(a).all()
+    assert torch.equal(a, run()), "two identical calls differ"
+
+
+@pytest.mark.parametrize("entry", ["plain", "from", "from_mask"])
+def test_scalar_instantiation_through_an_odd_offset_view(entry):
+    """As in tests/test_gpu_requests.py: from Python only the 16-byte instantiation of the step kernel can be reached, so the scalar one is
+    reached by handing the C entry an out_latent and a trace_x0 that start 4 bytes into their buffers: same bits as the aligned call."""
+    import ctypes as C
+    from transformer_latent_diffusion_amd import _lib, schedule
+    cfg, sd, m, gen = _model(TINY)
+    eps, z0, labels = (t.to(_dev()).contiguous() for t in _inputs(2, seed=36))
+    mask = _rect_masks(2).to(_dev()).contiguous() if entry == "from_mask" else None
+    k, levels = schedule.truncate_levels(schedule.noise_schedule(8, 1), 1.0 if entry == "plain" else 0.65)
+    co = np.ascontiguousarray(schedule.step_coefficients(levels), dtype=np.float32)
+    nl, n = co.shape[0], eps.numel()
+    assert (k == 0) == (entry == "plain") and nl >= 3
+    h = m._ensure_engine(4, _dev())
+    vp = lambda t: C.c_void_p(None if t is None else t.data_ptr())
+    cop, stream = co.ctypes.data_as(C.POINTER(C.c_float)), C.c_void_p(torch.cuda.current_stream(_dev()).cuda_stream)
+
+    def call(out, tx0):
+        if entry == "plain":
+            return _lib.lib().tld_sample(h, vp(eps), vp(labels), cop, nl, 3.0, 0.1, 0.1, vp(out), 2, vp(tx0), None, stream)
+        return _lib.lib().tld_sample_from(h, vp(eps), vp(z0), vp(mask), float(np.float32(levels[0])), vp(labels), cop, nl, 3.0, 0.1, 0.1, vp(out), 2,
+                                          vp(tx0), None, stream)
+
+    out_a, tr_a = torch.empty_like(eps), torch.zeros((nl - 1,) + tuple(eps.shape), device=_dev())
+    buf_o, buf_t = torch.zeros(n + 4, device=_dev()), torch.zeros((nl - 1) * n + 4, device=_dev())
+    out_u, tr_u = buf_o[1:1 + n].view_as(eps), buf_t[1:1 + (nl - 1) * n].view(nl - 1, *eps.shape)
+    assert out_u.data_ptr() % 16 == 4 and tr_u.data_ptr() % 16 == 4
+    assert call(out_a, tr_a) == 0 and call(out_u, tr_u) == 0
+    torch.cuda.synchronize()
+    assert torch.isfinite(out_a).all() and tr_a.abs().sum() > 0
+    assert torch.equal(out_a, out_u) and torch.equal(tr_a, tr_u), "the scalar instantiation differs from the 16-byte one"
+    assert float(buf_o[0]) == 0.0 and float(buf_o[-3:].abs().max()) == 0.0 and float(buf_t[0]) == 0.0 and float(buf_t[-3:].abs().max()) == 0.0
+
+
 # ---- the known region --------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("plus", [True, False], ids=["dpm", "ddim"])
 def test_known_region_is_kept_exactly(plus):

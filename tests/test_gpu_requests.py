@@ -137,7 +137,7 @@ def _direct_call(m, eps, labels, coeffs, guid, out, tx0=None):
 
 def test_scalar_instantiation_through_an_odd_offset_view():
     """From Python every tensor is 16-byte aligned and C S S is a multiple of 16 (the token grid's side is a multiple of 4), so the
-    16-byte instantiation is the only one the public interface can reach.  The scalar one (update_requests_kernel<MASK, 1>) is reached
+    16-byte instantiation is the only one the public interface can reach.  The scalar one (sampler_step_kernel<MASK, 1>) is reached
     here by handing the C ABI an out_latent and a trace_x0 that start 4 bytes into their buffers: same bits as the aligned call."""
     from transformer_latent_diffusion_amd import schedule
     cfg, sd, m, gen = _model(TINY)

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Cost of image-to-image and inpainting beside plain text-to-image sampling at BASELINE config C1 (100 M model, 256 px = 32 x 32 latents,
 64 images, 35 noise levels, DPM-Solver++(2M), guidance 6), in one process:
-    plain      DiffusionGenerator.generate_latents                             35 steps, update_kernel
-    img2img    generate_latents_from at strength 0.6                           the levels <= 0.6 only, update_from_kernel without a mask
-    inpaint    generate_latents_from at strength 1.0 with a half-image mask    35 steps, update_from_kernel with the blend
+    plain      DiffusionGenerator.generate_latents                             35 steps
+    img2img    generate_latents_from at strength 0.6                           the levels <= 0.6 only, the step kernel without a mask
+    inpaint    generate_latents_from at strength 1.0 with a half-image mask    35 steps, the step kernel with the blend
 Reports the median ms per call and the `update` class time per launch (HIP events, Denoiser.get_profile); one JSON line at the end.
     python tools/img2img_bench.py [--batch 64] [--n-iter 35] [--iters 5] [--json out.json]"""
 import argparse

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Dump the g5 forward, a 70-sample forward and the g5 35-step CFG end latent of the engine library selected by TLD_LIB (same-box A/B of builds: outputs of two builds that only re-order work
-must be BITWISE equal).   TLD_LIB=<lib.so> python tools/lib_ab_check.py out.npy"""
-import os, sys
+"""Dump the g5 forward, a 70-sample forward, the g5 35-step CFG end latent and the tiny model's sampler outputs (end latent and both traces of a plain call, a
+strength-0.65 call, a masked call and the five-request call of tests/test_gpu_requests.py) of the engine library selected by TLD_LIB (same-box A/B of builds:
+outputs of two builds that only re-order work must be BITWISE equal).  One "part <name> <sha1>" line per tensor: equal lines are equal bits.
+    TLD_LIB=<lib.so> python tools/lib_ab_check.py out.npy"""
+import hashlib, os, sys
 from dataclasses import asdict
 import numpy as np, torch
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,4 +26,25 @@ lat = DiffusionGenerator(m, None, dev, torch.float32).generate_latents(torch.fro
                                                                        class_guidance=float(g["traj_class_guidance"]), seeds=torch.from_numpy(g["traj_seeds"]),
                                                                        img_size=32, sharp_f=0.0, bright_f=0.0).cpu().numpy()
 print("g5 35-step end latent rel-rms", rel_rms(lat, g["traj_latent"]))
-np.save(sys.argv[1], np.concatenate([out.reshape(-1), big.reshape(-1), lat.reshape(-1)]))
+parts = {"g5 forward": out, "70-sample forward": big, "g5 35-step end latent": lat}
+# the sampler entries on the tiny model (inputs, mask and requests as tests/test_gpu_requests.py builds them)
+gt = load_golden("g2_tiny32_sampler.npz")
+ct = cfg_from_arr(gt["cfg"]); sdt = synth_weights(ct, gt["weight_seed"], gt["weight_checksum"])
+mt = Denoiser(**asdict(ct)).to(dev); mt.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in sdt.items()})
+gent = DiffusionGenerator(mt, None, dev, torch.float32)
+rg = torch.Generator().manual_seed(61)
+eps = torch.randn(5, 4, 32, 32, generator=rg); z0 = torch.randn(5, 4, 32, 32, generator=rg) * 0.5; labels = torch.randn(5, 768, generator=rg) * 0.5
+mask = torch.zeros(5, 1, 32, 32); mask[:, :, 5:21, 3:17] = 1
+kw = dict(n_iter=8, class_guidance=3.0, sharp_f=0.1, bright_f=0.1, seeds=eps, trace=True)
+five = dict(class_guidance=[1.0, 3.0, 4.5, 6.0, 3.0], n_iter=[8, 5, 8, 3, 5], use_ddpm_plus=[True, True, False, True, True], exponent=[1, 1, 1, 1, 2])
+calls = {"tiny plain": lambda: gent.generate_latents(labels, num_imgs=5, img_size=32, **kw),
+         "tiny strength 0.65": lambda: gent.generate_latents_from(z0, labels, strength=0.65, **kw),
+         "tiny masked": lambda: gent.generate_latents_from(z0, labels, strength=0.65, mask=mask, **kw),
+         "tiny five requests": lambda: gent.generate_latents_requests(labels, seeds=eps, img_size=32, sharp_f=0.1, bright_f=0.1, trace=True, **five)}
+for name, call in calls.items():
+    for what, v in zip(("end latent", "trace_x0", "trace_xt"), call()):
+        parts[f"{name} {what}"] = v.cpu().numpy()
+for name, v in parts.items():
+    assert np.isfinite(v).all(), name
+    print("part", name, tuple(v.shape), hashlib.sha1(np.ascontiguousarray(v).tobytes()).hexdigest())
+np.save(sys.argv[1], np.concatenate([v.reshape(-1) for v in parts.values()]))

@@ -416,54 +416,31 @@ struct TailParams {
 };
 void launch_tail(const TailParams& p, hipStream_t s);
 
-// sampler elementwise: CFG combine + multistep update (see schedule.py)
-struct UpdateParams {
-    const float* x0_2b;           // [2B, img] model output (cond rows first, then uncond)
-    float* x_t;                   // [B, img]  in/out
-    float* x0_prev;               // [B, img]  in/out
-    float* x0_out;                // [B, img]  CFG-combined prediction (always written)
-    float* trace_x0; float* trace_xt;  // optional [B, img]
-    float g, a, b, c, c1, c2, sharp, bright;
-    int final_step;               // 1: only combine (+shifts on channels 3 and 0), no update
-    int batch, img, chan_stride, C;
-};
-void launch_update(const UpdateParams& p, hipStream_t s);
-
-// the same step for a trajectory that starts from an image (tld_sample_from)
-struct UpdateFromParams {
-    UpdateParams u;
-    const float* noise;           // [B, img]  eps of the forward process             (read with a mask only)
-    const float* z0;              // [B, img]  initial latent = the known region      (read with a mask only)
-    const float* mask;            // [B, chan_stride] in [0,1], 1 = regenerate, broadcast over channels; null: no blend, update_kernel's arithmetic
-    float s_next;                 // noise level the updated x_t sits at (unused on the final step)
-};
-void launch_update_from(const UpdateFromParams& p, hipStream_t s);
-// x_t = s0 noise + (1 - s0) z0 over n elements
-void launch_start_mix(const float* noise, const float* z0, float s0, float* x_t, int n, hipStream_t s);
-
-// the same step for B independent requests in one call (tld_sample_requests): what UpdateParams / UpdateFromParams carry per call
-// is read per sample from a device table, one row per (step, request)
-struct UpdateRequestRow {
+// sampler elementwise: CFG combine + multistep update (see schedule.py).  One kernel serves tld_sample, tld_sample_from and
+// tld_sample_requests: what differs per sample is read from a device table, one row per (step, request), or one per step shared by every sample
+struct SamplerStepRow {
     float g, a, b, c, c1, c2;     // class guidance and the step's coefficients of the request (schedule.py)
-    float s_next;                 // noise level the updated x_t sits at (unused on the request's final step)
-    int final_step;               // 1: the request's last level -- combine (+ mask blend, + shifts) into out_latent, no update
+    float s_next;                 // noise level the updated x_t sits at (read with a mask only; unused on the request's final step)
+    int final_step;               // 1: the request's last level -- combine (+ mask blend, + shifts on channels 3 and 0) into out_latent, no update
 };
-struct UpdateRequestsParams {
+struct SamplerStepParams {
     const float* x0_2b;           // [2 active, img] model output of the step: cond rows of the active prefix, then their uncond rows
     float* x_t;                   // [B, img]  in/out
-    float* x0_prev;               // [B, img]  in/out
+    float* x0_prev;               // [B, img]  in/out: after an inner step, the CFG-combined (unblended) prediction of that step
     float* out_latent;            // [B, img]  written by a request's final step only
     float* trace_x0; float* trace_xt;  // optional, this step's [B, img] slot
-    const float* noise;           // [B, img]  (read with a mask only)
-    const float* z0;              // [B, img]  (read with a mask only)
-    const float* mask;            // [B, chan_stride]; null: no blend
-    const UpdateRequestRow* rows; // [active] this step's rows of the device table
+    const float* noise;           // [B, img]  eps of the forward process           (read with a mask only)
+    const float* z0;              // [B, img]  initial latent = the known region    (read with a mask only)
+    const float* mask;            // [B, chan_stride] in [0,1], 1 = regenerate, broadcast over channels; null: no blend
+    const SamplerStepRow* rows;   // this step's rows of the device table: sample b reads rows[b * row_stride]
+    int row_stride;               // 1: a row per request; 0: one row for every sample
     float sharp, bright;
     int active, img, chan_stride; // requests still running at this step (a prefix: the records are ordered by non-increasing level count)
 };
-void launch_update_requests(const UpdateRequestsParams& p, hipStream_t s);
-// x_t[b] = s0[b] noise[b] + (1 - s0[b]) z0[b] with s0 read per sample from a device table; s0[b] == 1 copies noise[b] (z0 may then be null)
-void launch_start_mix_requests(const float* noise, const float* z0, const float* s0, float* x_t, int batch, int img, hipStream_t s);
+// path: the EP_UPDATE* bit that names the flavour of step the calling entry asked for
+void launch_sampler_step(const SamplerStepParams& p, int path, hipStream_t s);
+// x_t[b] = s0 noise[b] + (1 - s0) z0[b] with s0 = s0v[b * s0_stride] read from a device table; s0 == 1 copies noise[b] (z0 may then be null).  path: EP_START_MIX*
+void launch_start_mix(const float* noise, const float* z0, const float* s0v, int s0_stride, float* x_t, int batch, int img, int path, hipStream_t s);
 
 // ---- conditioning path (fp32) ------------------------------------------------------------------
 // out[t, n] = act(sum_k in[t,k] W[n,k] + b[n]);  act: 0 none, 1 exact GELU

@@ -145,13 +145,12 @@ struct tld_engine {
     bf16 *xn = nullptr, *qk = nullptr, *vt = nullptr, *att = nullptr, *hid1 = nullptr, *hid2 = nullptr;
     uint32_t* seam = nullptr;            // 32 x 32 grids: the seam rows of the hidden tensor between the fused up-projection and launch_dwconv_seam
     float *io_x = nullptr, *io_sigma = nullptr, *io_label = nullptr, *io_out = nullptr;
-    float *xt = nullptr, *x0_prev = nullptr, *x0_cfg = nullptr;
-    int* rows_dev = nullptr;           // noise_row / label_row tables
-    int64_t rows_cap = 0;
-    void* stage_host = nullptr;        // pinned staging for tld_sample's sigma / row tables
+    float *xt = nullptr, *x0_prev = nullptr;
+    int* rows_dev = nullptr;           // tld_denoiser_forward's noise_row / label_row tables [2 max_batch]
+    void* stage_host = nullptr;        // pinned staging for the samplers' host-built tables
     size_t stage_cap = 0;
     hipEvent_t stage_ev = nullptr;     // recorded after the last copy out of stage_host
-    void* req_dev = nullptr;           // tld_sample_requests: the per-(step, request) update rows, then the per-request start mixes
+    void* req_dev = nullptr;           // the samplers' tables of one call (run_sampler): step rows, start mixes, token-row indices
     size_t req_cap = 0;
 
     // conditioning tables (sized for cond_cap token rows)
@@ -235,17 +234,10 @@ int ensure_cond_capacity(tld_engine* e, int T) {
     return TLD_OK;
 }
 
-int ensure_rows_capacity(tld_engine* e, int64_t n) {
-    if (n <= e->rows_cap) return TLD_OK;
-    if (int rc = dev_alloc(e, &e->rows_dev, (size_t)n)) return rc;
-    e->rows_cap = n;
-    return TLD_OK;
-}
-
 int ensure_req_capacity(tld_engine* e, size_t bytes) {
     if (bytes <= e->req_cap) return TLD_OK;
     char* q = nullptr;
-    if (int rc = dev_alloc(e, &q, bytes)) return rc;      // grow-only, like the row tables
+    if (int rc = dev_alloc(e, &q, bytes)) return rc;      // grow-only, like the conditioning tables
     e->req_dev = q; e->req_cap = bytes;
     return TLD_OK;
 }
@@ -644,73 +636,149 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
     return TLD_OK;
 }
 
-// What tld_sample and tld_sample_from share ahead of the loop: argument checks, the conditioning tables of the whole trajectory and the
-// token-row tables, through the engine's pinned staging buffer (no stream synchronisation).
-int sample_prepare(tld_engine* e, const void* labels, const float* coeffs, int n_levels, int batch, hipStream_t s, const int** label_row_out) {
+// What a sampler entry asks of run_sampler, after its own argument checks.  Request b is requests[b * stride] with the coefficient table
+// coeffs + b * stride * n_max * 6: stride 1 for tld_sample_requests, 0 for the uniform entries (one record and one table for the whole batch, one
+// row per step in the device table).  The records are ordered by non-increasing n_levels, and requests[0].n_levels == n_max.
+struct SamplePlan {
+    int B, n_max, stride;
+    const tld_sample_request* requests;
+    const float* coeffs;                 // HOST [B or 1][n_max][6]: (sigma, a, b, c, c1, c2) per level
+    // conditioning noise rows: Tn sigmas and, per (step, request), the row of its sigma; null: row i is level i of the one table (the uniform entries)
+    int Tn; const float* sig; const int* noise_idx;       // sig [Tn], noise_idx [n_max][B]
+    const float *noise, *init_latent, *mask, *labels, *neg_labels;      // device; init_latent / mask / neg_labels optional
+    float sharp, bright;
+    float *out_latent, *trace_x0, *trace_xt;
+    int path_step, path_start;           // the EP_UPDATE* / EP_START_MIX* bits of the calling entry
+    bool keep_stages;                    // step.* and the body's stages are kept at the debug step (the uniform entries)
+};
+
+// The one sampler loop: conditioning tables of every request's whole trajectory, the start, then per step the model on the requests that still run
+// (a shrinking prefix, CFG-doubled, layer-0 sharing) and the elementwise step.  Host-built tables travel through the engine's pinned staging buffer
+// in two uploads behind stage_ev: no stream synchronisation.  Conditioning rows: Tn noise rows, B label rows, the zero row, one row per negative label.
+int run_sampler(tld_engine* e, const SamplePlan& p, hipStream_t s) {
+    const int B = p.B, n_max = p.n_max, Tn = p.Tn, tabB = p.stride ? B : 1;
+    auto req = [&](int b) -> const tld_sample_request& { return p.requests[(size_t)b * p.stride]; };
+    int n_neg = 0;
+    size_t row_ints = 0;                                      // per step [noise rows 2 Bi | label rows 2 Bi] over the Bi requests still running
+    for (int b = 0; b < B; ++b) { n_neg += req(b).has_negative ? 1 : 0; row_ints += (size_t)4 * req(b).n_levels; }
+    const int T = Tn + B + 1 + n_neg;
+    const size_t tab_bytes = (size_t)n_max * tabB * sizeof(SamplerStepRow), mix_bytes = (size_t)tabB * sizeof(float);
+    const size_t up_bytes = tab_bytes + mix_bytes + row_ints * sizeof(int);
+    if (int rc = ensure_cond_capacity(e, T)) return rc;
+    if (int rc = ensure_req_capacity(e, up_bytes)) return rc;
+    if (int rc = debug_begin(e, T, Tn, s)) return rc;
+    if (int rc = stage_acquire(e, up_bytes + (size_t)Tn * sizeof(float))) return rc;
+    SamplerStepRow* tab = static_cast<SamplerStepRow*>(e->stage_host);
+    float* mix = reinterpret_cast<float*>(tab + (size_t)n_max * tabB);
+    int* rows = reinterpret_cast<int*>(mix + tabB);
+    float* sigs = reinterpret_cast<float*>(rows + row_ints);
+    bool any_mix = false;
+    for (int b = 0; b < tabB; ++b) {
+        const tld_sample_request& r = req(b);
+        const float* c = p.coeffs + (size_t)b * n_max * 6;
+        mix[b] = r.start_mix;
+        any_mix |= r.start_mix < 1.0f;
+        for (int i = 0; i < n_max; ++i, c += 6) {
+            SamplerStepRow& u = tab[(size_t)i * tabB + b];
+            if (i >= r.n_levels) { u = SamplerStepRow{}; continue; }
+            u.g = r.class_guidance; u.a = c[1]; u.b = c[2]; u.c = c[3]; u.c1 = c[4]; u.c2 = c[5];
+            u.s_next = (i + 1 < r.n_levels) ? c[6] : 0.0f;    // sigma of the request's next row
+            u.final_step = (i == r.n_levels - 1) ? 1 : 0;
+        }
+    }
+    for (int t = 0; t < Tn; ++t) sigs[t] = p.sig ? p.sig[t] : p.coeffs[(size_t)t * 6];
+    {
+        int* nr = rows;
+        for (int i = 0, Bi = B; i < n_max; ++i, nr += 4 * Bi) {
+            while (req(Bi - 1).n_levels <= i) --Bi;
+            int* lr = nr + 2 * Bi;
+            for (int b = 0, k = 0; b < Bi; ++b) {
+                nr[b] = nr[Bi + b] = p.noise_idx ? p.noise_idx[(size_t)i * B + b] : i;
+                lr[b] = Tn + b;
+                lr[Bi + b] = req(b).has_negative ? Tn + B + 1 + k++ : Tn + B;     // the unconditional label: the zero row, or the request's own negative
+            }
+        }
+    }
+
+    // ---- conditioning tables for every request's whole trajectory, once
+    const size_t text = e->text;
+    HIP_TRY(hipMemcpyAsync(e->c_sigma, sigs, (size_t)Tn * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(e->c_label, p.labels, (size_t)B * text * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemsetAsync(e->c_label + (size_t)B * text, 0, text * sizeof(float), s));     // uncond = zeros (diffusion.py:61)
+    for (int b = 0, k = 0; b < B && n_neg; ) {                // negative labels, compacted: one copy per run of consecutive requests that have one
+        if (!req(b).has_negative) { ++b; continue; }
+        int b1 = b;
+        while (b1 < B && req(b1).has_negative) ++b1;
+        HIP_TRY(hipMemcpyAsync(e->c_label + (size_t)(B + 1 + k) * text, p.neg_labels + (size_t)b * text, (size_t)(b1 - b) * text * sizeof(float),
+                               hipMemcpyDeviceToDevice, s));
+        k += b1 - b; b = b1;
+    }
+    {
+        ProfScope ps(e, KC_COND, s);
+        cond_noise_rows(e, Tn, s);
+        cond_label_rows(e, Tn, B + 1 + n_neg, s);
+    }
+    if (int rc = cond_tables(e, T, s)) return rc;
+    HIP_TRY(hipMemcpyAsync(e->req_dev, tab, up_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(e->stage_ev, s));     // no stream sync: the staging buffer is the engine's, guarded by this event
+    e->dbg_batch = 2 * B; e->dbg_T = T;
+    const SamplerStepRow* tab_dev = static_cast<const SamplerStepRow*>(e->req_dev);
+    const float* mix_dev = reinterpret_cast<const float*>(tab_dev + (size_t)n_max * tabB);
+    const int* nr = reinterpret_cast<const int*>(mix_dev + tabB);
+
+    // ---- the start: pure noise at the schedule's first level (diffusion.py:52,59), else the forward process at the first remaining level (train.py:130)
+    const size_t tot = (size_t)B * e->img;
+    if (!any_mix) HIP_TRY(hipMemcpyAsync(e->xt, p.noise, tot * sizeof(float), hipMemcpyDeviceToDevice, s));
+    else launch_start_mix(p.noise, p.init_latent, mix_dev, p.stride, e->xt, B, e->img, p.path_start, s);
+    HIP_TRY(hipMemsetAsync(e->x0_prev, 0, tot * sizeof(float), s));
+    // ---- the steps over the shrinking prefix of requests that still run
+    for (int i = 0, Bi = B; i < n_max; ++i, nr += 4 * Bi) {
+        while (req(Bi - 1).n_levels <= i) --Bi;
+        const bool last = i == n_max - 1;
+        // At the debug step (tld_engine_set_debug_step; every step when it is negative) the body's stages are kept, and so are the step's inputs
+        // (x_t, x0_prev) and outputs (the 2B forward output, the x0 written, the next x_t).
+        if (p.keep_stages) e->dbg_keep = e->debug && (e->dbg_step < 0 || e->dbg_step == i);
+        SNAP("step.x_t", e->xt, ST_F32, s, B, e->img); SNAP("step.x0_prev", e->x0_prev, ST_F32, s, B, e->img);
+        // pred_image: model(cat[x_t, x_t], sigma_i, [labels; 0])   (diffusion.py:94-101)
+        if (int rc = run_body(e, e->xt, Bi, 2 * Bi, nr, nr + 2 * Bi, e->io_out, s, true)) return rc;
+        SamplerStepParams up{};
+        up.x0_2b = e->io_out; up.x_t = e->xt; up.x0_prev = e->x0_prev; up.out_latent = p.out_latent;
+        up.trace_x0 = (!last && p.trace_x0) ? p.trace_x0 + (size_t)i * tot : nullptr;
+        up.trace_xt = (!last && p.trace_xt) ? p.trace_xt + (size_t)i * tot : nullptr;
+        up.noise = p.noise; up.z0 = p.init_latent; up.mask = p.mask;
+        up.rows = tab_dev + (size_t)i * tabB; up.row_stride = p.stride; up.sharp = p.sharp; up.bright = p.bright;
+        up.active = Bi; up.img = e->img; up.chan_stride = e->cfg.image_size * e->cfg.image_size;
+        {
+            ProfScope ps(e, KC_UPDATE, s);
+            launch_sampler_step(up, p.path_step, s);
+        }
+        // (the uniform entries: every sample is at its last level together, and an inner step has just stored its prediction to x0_prev)
+        SNAP("step.out", e->io_out, ST_F32, s, 2 * B, e->img); SNAP("step.x0", last ? p.out_latent : e->x0_prev, ST_F32, s, B, e->img);
+        if (!last) SNAP("step.x_next", e->xt, ST_F32, s, B, e->img);
+        e->dbg_keep = false;
+    }
+    HIP_TRY(hipGetLastError());
+    return TLD_OK;
+}
+
+// tld_sample / tld_sample_from after their own checks: one record and one coefficient table for the whole batch; noise row i is level i
+int run_uniform(tld_engine* e, const void* noise, const void* init_latent, const void* mask, float start_mix, const void* labels, const float* coeffs,
+                int n_levels, float class_guidance, float sharp_f, float bright_f, void* out_latent, int batch, void* trace_x0, void* trace_xt,
+                int path_step, void* hip_stream) {
     if (!e->finalized) return fail(TLD_ERR_STATE, "weights not finalized");
     if (batch <= 0 || 2 * batch > e->cfg.max_batch)
         return fail(TLD_ERR_INVALID, "sampler batch %d needs max_batch >= %d (have %d)", batch, 2 * batch, e->cfg.max_batch);
     if (n_levels < 2) return fail(TLD_ERR_INVALID, "need at least two noise levels");
-    const int B = batch, B2 = 2 * batch, T = n_levels + B + 1;
-    if (int rc = ensure_cond_capacity(e, T)) return rc;
-    if (int rc = ensure_rows_capacity(e, (int64_t)(n_levels + 1) * B2)) return rc;
-
-    // ---- conditioning tables for the whole trajectory, once
-    const size_t n_rows = (size_t)(n_levels + 1) * B2;
-    if (int rc = debug_begin(e, T, n_levels, s)) return rc;
-    if (int rc = stage_acquire(e, (size_t)n_levels * sizeof(float) + n_rows * sizeof(int))) return rc;
-    float* sig = static_cast<float*>(e->stage_host);
-    int* rows = reinterpret_cast<int*>(sig + n_levels);
-    for (int i = 0; i < n_levels; ++i) sig[i] = coeffs[(size_t)i * 6 + 0];
-    HIP_TRY(hipMemcpyAsync(e->c_sigma, sig, (size_t)n_levels * sizeof(float), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(e->c_label, labels, (size_t)B * e->text * sizeof(float), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemsetAsync(e->c_label + (size_t)B * e->text, 0, e->text * sizeof(float), s));   // uncond = zeros (diffusion.py:61)
-    {
-        ProfScope ps(e, KC_COND, s);
-        cond_noise_rows(e, n_levels, s);
-        cond_label_rows(e, n_levels, B + 1, s);
-    }
-    if (int rc = cond_tables(e, T, s)) return rc;
-    // row tables: [step][B2] noise rows, then one [B2] label-row table
-    for (int i = 0; i < n_levels; ++i)
-        for (int b = 0; b < B2; ++b) rows[(size_t)i * B2 + b] = i;
-    for (int b = 0; b < B2; ++b) rows[(size_t)n_levels * B2 + b] = n_levels + (b < B ? b : B);
-    HIP_TRY(hipMemcpyAsync(e->rows_dev, rows, n_rows * sizeof(int), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipEventRecord(e->stage_ev, s));     // no stream sync: the staging buffer is the engine's, guarded by this event
-    *label_row_out = e->rows_dev + (size_t)n_levels * B2;
-    e->dbg_batch = B2; e->dbg_T = T;
-    return TLD_OK;
-}
-
-// one step's elementwise parameters (row i of the coefficient table)
-UpdateParams update_params(tld_engine* e, const float* coeffs, int n_levels, int i, float class_guidance, float sharp_f, float bright_f,
-                           void* out_latent, int B, void* trace_x0, void* trace_xt) {
-    const bool final_step = (i == n_levels - 1);
-    const size_t tot = (size_t)B * e->img;
-    UpdateParams up{};
-    const float* c = coeffs + (size_t)i * 6;
-    up.x0_2b = e->io_out; up.x_t = e->xt; up.x0_prev = e->x0_prev;
-    up.x0_out = final_step ? static_cast<float*>(out_latent) : e->x0_cfg;
-    up.trace_x0 = (!final_step && trace_x0) ? static_cast<float*>(trace_x0) + (size_t)i * tot : nullptr;
-    up.trace_xt = (!final_step && trace_xt) ? static_cast<float*>(trace_xt) + (size_t)i * tot : nullptr;
-    up.g = class_guidance; up.a = c[1]; up.b = c[2]; up.c = c[3]; up.c1 = c[4]; up.c2 = c[5];
-    up.sharp = sharp_f; up.bright = bright_f; up.final_step = final_step ? 1 : 0;
-    up.batch = B; up.img = e->img; up.chan_stride = e->cfg.image_size * e->cfg.image_size; up.C = e->cfg.n_channels;
-    return up;
-}
-
-// Stage hook around one sampler step: at the debug step (tld_engine_set_debug_step; every step when it is negative) the body's stages are kept, and so
-// are the step's inputs (x_t, x0_prev) and outputs (the 2B forward output, the x0 written, the next x_t).
-int step_begin(tld_engine* e, int i, int B, hipStream_t s) {
-    e->dbg_keep = e->debug && (e->dbg_step < 0 || e->dbg_step == i);
-    SNAP("step.x_t", e->xt, ST_F32, s, B, e->img); SNAP("step.x0_prev", e->x0_prev, ST_F32, s, B, e->img);
-    return TLD_OK;
-}
-int step_end(tld_engine* e, const UpdateParams& up, int B, hipStream_t s) {
-    SNAP("step.out", e->io_out, ST_F32, s, 2 * B, e->img); SNAP("step.x0", up.x0_out, ST_F32, s, B, e->img);
-    if (!up.final_step) SNAP("step.x_next", e->xt, ST_F32, s, B, e->img);
-    e->dbg_keep = false;
-    return TLD_OK;
+    DeviceGuard dg(e->cfg.device_id);
+    PathScope paths(e);
+    const tld_sample_request rec{n_levels, class_guidance, start_mix, 0};
+    SamplePlan p{};
+    p.B = batch; p.n_max = n_levels; p.stride = 0; p.requests = &rec; p.coeffs = coeffs; p.Tn = n_levels;
+    p.noise = static_cast<const float*>(noise); p.init_latent = static_cast<const float*>(init_latent); p.mask = static_cast<const float*>(mask);
+    p.labels = static_cast<const float*>(labels); p.sharp = sharp_f; p.bright = bright_f;
+    p.out_latent = static_cast<float*>(out_latent); p.trace_x0 = static_cast<float*>(trace_x0); p.trace_xt = static_cast<float*>(trace_xt);
+    p.path_step = path_step; p.path_start = EP_START_MIX; p.keep_stages = true;
+    return run_sampler(e, p, static_cast<hipStream_t>(hip_stream));
 }
 
 }  // namespace
@@ -1073,9 +1141,9 @@ int tld_engine_finalize_weights(tld_engine* e) {
     if (int rc = dev_alloc(e, &e->io_label, B2 * e->text)) return rc;
     if (int rc = dev_alloc(e, &e->xt, B2 * e->img)) return rc;
     if (int rc = dev_alloc(e, &e->x0_prev, B2 * e->img)) return rc;
-    if (int rc = dev_alloc(e, &e->x0_cfg, B2 * e->img)) return rc;
     if (int rc = ensure_cond_capacity(e, 2 * (int)B2)) return rc;
-    if (int rc = ensure_rows_capacity(e, 64 * (int64_t)B2)) return rc;
+    if (int rc = dev_alloc(e, &e->rows_dev, 2 * B2)) return rc;
+    if (int rc = ensure_req_capacity(e, 64 * (sizeof(SamplerStepRow) + 8 * B2))) return rc;      // a 64-level call at full batch; larger calls grow it
     e->finalized = true;
     return TLD_OK;
 }
@@ -1225,30 +1293,8 @@ int tld_sample(tld_engine* e, const void* x_T, const void* labels, const float* 
                float class_guidance, float sharp_f, float bright_f, void* out_latent, int32_t batch,
                void* trace_x0, void* trace_xt, void* hip_stream) {
     if (!e || !x_T || !labels || !coeffs || !out_latent) return fail(TLD_ERR_INVALID, "null argument");
-    DeviceGuard dg(e->cfg.device_id);
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    const int* label_row = nullptr;
-    PathScope paths(e);
-    if (int rc = sample_prepare(e, labels, coeffs, n_levels, batch, s, &label_row)) return rc;
-    const int B = batch, B2 = 2 * batch;
-
-    const size_t tot = (size_t)B * e->img;
-    HIP_TRY(hipMemcpyAsync(e->xt, x_T, tot * sizeof(float), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemsetAsync(e->x0_prev, 0, tot * sizeof(float), s));
-
-    for (int i = 0; i < n_levels; ++i) {
-        // pred_image: model(cat[x_t, x_t], sigma_i, [labels; 0])   (diffusion.py:94-101)
-        if (int rc = step_begin(e, i, B, s)) return rc;
-        if (int rc = run_body(e, e->xt, B, B2, e->rows_dev + (size_t)i * B2, label_row, e->io_out, s, true)) return rc;
-        const UpdateParams up = update_params(e, coeffs, n_levels, i, class_guidance, sharp_f, bright_f, out_latent, B, trace_x0, trace_xt);
-        {
-            ProfScope ps(e, KC_UPDATE, s);
-            launch_update(up, s);
-        }
-        if (int rc = step_end(e, up, B, s)) return rc;
-    }
-    HIP_TRY(hipGetLastError());
-    return TLD_OK;
+    return run_uniform(e, x_T, nullptr, nullptr, 1.0f, labels, coeffs, n_levels, class_guidance, sharp_f, bright_f, out_latent, batch, trace_x0, trace_xt,
+                       EP_UPDATE, hip_stream);
 }
 
 int tld_sample_from(tld_engine* e, const void* noise, const void* init_latent, const void* mask, float start_mix, const void* labels,
@@ -1257,34 +1303,8 @@ int tld_sample_from(tld_engine* e, const void* noise, const void* init_latent, c
     if (!e || !noise || !labels || !coeffs || !out_latent) return fail(TLD_ERR_INVALID, "null argument");
     if (!(start_mix > 0.0f && start_mix <= 1.0f)) return fail(TLD_ERR_INVALID, "start_mix %g outside (0, 1]", (double)start_mix);
     if (!init_latent && (mask || start_mix < 1.0f)) return fail(TLD_ERR_INVALID, "init_latent is required with a mask or with start_mix < 1");
-    DeviceGuard dg(e->cfg.device_id);
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    const int* label_row = nullptr;
-    PathScope paths(e);
-    if (int rc = sample_prepare(e, labels, coeffs, n_levels, batch, s, &label_row)) return rc;
-    const int B = batch, B2 = 2 * batch;
-
-    const size_t tot = (size_t)B * e->img;
-    // the start: pure noise at the schedule's first level (diffusion.py:52,59), else the forward process at the first remaining level (train.py:130)
-    if (start_mix == 1.0f) HIP_TRY(hipMemcpyAsync(e->xt, noise, tot * sizeof(float), hipMemcpyDeviceToDevice, s));
-    else launch_start_mix(static_cast<const float*>(noise), static_cast<const float*>(init_latent), start_mix, e->xt, (int)tot, s);
-    HIP_TRY(hipMemsetAsync(e->x0_prev, 0, tot * sizeof(float), s));
-
-    for (int i = 0; i < n_levels; ++i) {
-        if (int rc = step_begin(e, i, B, s)) return rc;
-        if (int rc = run_body(e, e->xt, B, B2, e->rows_dev + (size_t)i * B2, label_row, e->io_out, s, true)) return rc;
-        UpdateFromParams uf{};
-        uf.u = update_params(e, coeffs, n_levels, i, class_guidance, sharp_f, bright_f, out_latent, B, trace_x0, trace_xt);
-        uf.noise = static_cast<const float*>(noise); uf.z0 = static_cast<const float*>(init_latent); uf.mask = static_cast<const float*>(mask);
-        uf.s_next = (i + 1 < n_levels) ? coeffs[(size_t)(i + 1) * 6 + 0] : 0.0f;
-        {
-            ProfScope ps(e, KC_UPDATE, s);
-            launch_update_from(uf, s);
-        }
-        if (int rc = step_end(e, uf.u, B, s)) return rc;
-    }
-    HIP_TRY(hipGetLastError());
-    return TLD_OK;
+    return run_uniform(e, noise, init_latent, mask, start_mix, labels, coeffs, n_levels, class_guidance, sharp_f, bright_f, out_latent, batch, trace_x0,
+                       trace_xt, mask ? EP_UPDATE_FROM_MASK : EP_UPDATE_FROM, hip_stream);
 }
 
 // the most conditioning token rows one tld_sample_requests call may need (distinct sigmas + label rows): at the 100 M width a row of cond.wq + cond.kv is
@@ -1299,7 +1319,6 @@ int tld_sample_requests(tld_engine* e, const void* noise, const void* init_laten
     if (mask && !init_latent) return fail(TLD_ERR_INVALID, "init_latent is required with a mask");
     const int B = batch;
     int n_neg = 0;
-    bool any_mix = false;
     for (int b = 0; b < B; ++b) {
         const tld_sample_request& r = requests[b];
         if (r.n_levels < 2) return fail(TLD_ERR_INVALID, "request %d: need at least two noise levels (have %d)", b, r.n_levels);
@@ -1309,10 +1328,7 @@ int tld_sample_requests(tld_engine* e, const void* noise, const void* init_laten
                         r.n_levels, b - 1, requests[b - 1].n_levels);
         if (!(r.start_mix > 0.0f && r.start_mix <= 1.0f)) return fail(TLD_ERR_INVALID, "request %d: start_mix %g outside (0, 1]", b, (double)r.start_mix);
         if (!std::isfinite(r.class_guidance)) return fail(TLD_ERR_INVALID, "request %d: class_guidance is not finite", b);
-        if (r.start_mix < 1.0f) {
-            if (!init_latent) return fail(TLD_ERR_INVALID, "request %d: init_latent is required with start_mix < 1", b);
-            any_mix = true;
-        }
+        if (r.start_mix < 1.0f && !init_latent) return fail(TLD_ERR_INVALID, "request %d: init_latent is required with start_mix < 1", b);
         if (r.has_negative) {
             if (!neg_labels) return fail(TLD_ERR_INVALID, "request %d: has_negative without neg_labels", b);
             ++n_neg;
@@ -1324,115 +1340,31 @@ int tld_sample_requests(tld_engine* e, const void* noise, const void* init_laten
     if (2 * batch > e->cfg.max_batch)
         return fail(TLD_ERR_INVALID, "sampler batch %d needs max_batch >= %d (have %d)", batch, 2 * batch, e->cfg.max_batch);
 
-    // ---- host tables: the distinct float32 sigmas of every (request, step), and the per-step token-row tables over the active prefix
-    std::vector<float> sig;                                   // distinct sigmas, in order of first use
-    std::unordered_map<uint32_t, int> sig_row;                // by bit pattern: requests that share a schedule share rows
-    std::vector<int> noise_idx((size_t)n_max * B, 0), active(n_max, 0);
-    size_t row_ints = 0;
-    for (int i = 0; i < n_max; ++i) {
-        int Bi = 0;
-        while (Bi < B && requests[Bi].n_levels > i) ++Bi;
-        active[i] = Bi;
-        row_ints += (size_t)4 * Bi;
-        for (int b = 0; b < Bi; ++b) {
+    // ---- the distinct float32 sigmas of every (request, step): requests that share a schedule share conditioning rows
+    std::vector<float> sig;                                   // in order of first use
+    std::unordered_map<uint32_t, int> sig_row;                // by bit pattern
+    std::vector<int> noise_idx((size_t)n_max * B, 0);
+    for (int i = 0; i < n_max; ++i)
+        for (int b = 0; b < B && requests[b].n_levels > i; ++b) {
             const float sg = coeffs[((size_t)b * n_max + i) * 6 + 0];
             uint32_t bits; memcpy(&bits, &sg, 4);
             auto it = sig_row.find(bits);
             if (it == sig_row.end()) { it = sig_row.emplace(bits, (int)sig.size()).first; sig.push_back(sg); }
             noise_idx[(size_t)i * B + b] = it->second;
         }
-    }
     const int Tn = (int)sig.size(), T = Tn + B + 1 + n_neg;
     if (T > kMaxRequestCondRows)
         return fail(TLD_ERR_INVALID, "the call needs %d conditioning rows (%d distinct noise levels + %d labels + 1 + %d negative labels): at most %d", T, Tn,
                     B, n_neg, kMaxRequestCondRows);
     DeviceGuard dg(e->cfg.device_id);
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    PathScope paths(e);
-    if (int rc = ensure_cond_capacity(e, T)) return rc;
-    if (int rc = ensure_rows_capacity(e, (int64_t)row_ints)) return rc;
-    const size_t tab_bytes = (size_t)n_max * B * sizeof(UpdateRequestRow), mix_bytes = (size_t)B * sizeof(float);
-    if (int rc = ensure_req_capacity(e, tab_bytes + mix_bytes)) return rc;
-    if (int rc = debug_begin(e, T, Tn, s)) return rc;         // (debug: the launch paths are recorded; no stage of this entry is kept)
-    if (int rc = stage_acquire(e, tab_bytes + mix_bytes + (size_t)Tn * sizeof(float) + row_ints * sizeof(int))) return rc;
-    UpdateRequestRow* tab = static_cast<UpdateRequestRow*>(e->stage_host);
-    float* mix = reinterpret_cast<float*>(tab + (size_t)n_max * B);
-    float* sigs = mix + B;
-    int* rows = reinterpret_cast<int*>(sigs + Tn);
-    std::vector<int> neg_row(B, Tn + B);                      // the unconditional label row of each request: the zero row, or its own negative
-    for (int b = 0, k = 0; b < B; ++b) {
-        mix[b] = requests[b].start_mix;
-        if (requests[b].has_negative) neg_row[b] = Tn + B + 1 + k++;
-    }
-    memcpy(sigs, sig.data(), (size_t)Tn * sizeof(float));
-    std::vector<size_t> step_rows(n_max);                     // offset of step i's [noise rows 2 Bi | label rows 2 Bi] in the row table
-    for (size_t i = 0, at = 0; i < (size_t)n_max; ++i) {
-        const int Bi = active[i];
-        step_rows[i] = at;
-        int* nr = rows + at; int* lr = nr + 2 * Bi;
-        for (int b = 0; b < Bi; ++b) {
-            nr[b] = nr[Bi + b] = noise_idx[i * B + b];
-            lr[b] = Tn + b; lr[Bi + b] = neg_row[b];
-            const float* c = coeffs + ((size_t)b * n_max + i) * 6;
-            const int nl = requests[b].n_levels;
-            UpdateRequestRow& u = tab[i * B + b];
-            u.g = requests[b].class_guidance; u.a = c[1]; u.b = c[2]; u.c = c[3]; u.c1 = c[4]; u.c2 = c[5];
-            u.s_next = ((int)i + 1 < nl) ? c[6] : 0.0f;       // sigma of the request's next row
-            u.final_step = ((int)i == nl - 1) ? 1 : 0;
-        }
-        for (int b = Bi; b < B; ++b) tab[i * B + b] = UpdateRequestRow{};
-        at += (size_t)4 * Bi;
-    }
-
-    // ---- conditioning tables for every request's whole trajectory, once
-    const size_t text = e->text;
-    HIP_TRY(hipMemcpyAsync(e->c_sigma, sigs, (size_t)Tn * sizeof(float), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(e->c_label, labels, (size_t)B * text * sizeof(float), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemsetAsync(e->c_label + (size_t)B * text, 0, text * sizeof(float), s));     // uncond = zeros (diffusion.py:61)
-    for (int b = 0; b < B; ) {                                 // negative labels, compacted: one copy per run of consecutive requests that have one
-        if (!requests[b].has_negative) { ++b; continue; }
-        int b1 = b;
-        while (b1 < B && requests[b1].has_negative) ++b1;
-        HIP_TRY(hipMemcpyAsync(e->c_label + (size_t)(neg_row[b] - Tn) * text, static_cast<const float*>(neg_labels) + (size_t)b * text,
-                               (size_t)(b1 - b) * text * sizeof(float), hipMemcpyDeviceToDevice, s));
-        b = b1;
-    }
-    {
-        ProfScope ps(e, KC_COND, s);
-        cond_noise_rows(e, Tn, s);
-        cond_label_rows(e, Tn, B + 1 + n_neg, s);
-    }
-    if (int rc = cond_tables(e, T, s)) return rc;
-    HIP_TRY(hipMemcpyAsync(e->rows_dev, rows, row_ints * sizeof(int), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(e->req_dev, tab, tab_bytes + mix_bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipEventRecord(e->stage_ev, s));     // no stream sync: the staging buffer is the engine's, guarded by this event
-    e->dbg_batch = 2 * B; e->dbg_T = T;
-    const UpdateRequestRow* tab_dev = static_cast<const UpdateRequestRow*>(e->req_dev);
-    const float* mix_dev = reinterpret_cast<const float*>(tab_dev + (size_t)n_max * B);
-
-    // ---- the start of every request, then the steps over the shrinking prefix of requests that still run
-    const size_t tot = (size_t)B * e->img;
-    if (!any_mix) HIP_TRY(hipMemcpyAsync(e->xt, noise, tot * sizeof(float), hipMemcpyDeviceToDevice, s));
-    else launch_start_mix_requests(static_cast<const float*>(noise), static_cast<const float*>(init_latent), mix_dev, e->xt, B, e->img, s);
-    HIP_TRY(hipMemsetAsync(e->x0_prev, 0, tot * sizeof(float), s));
-    for (int i = 0; i < n_max; ++i) {
-        const int Bi = active[i];
-        const int* nr = e->rows_dev + step_rows[i];
-        if (int rc = run_body(e, e->xt, Bi, 2 * Bi, nr, nr + 2 * Bi, e->io_out, s, true)) return rc;
-        UpdateRequestsParams up{};
-        up.x0_2b = e->io_out; up.x_t = e->xt; up.x0_prev = e->x0_prev; up.out_latent = static_cast<float*>(out_latent);
-        up.trace_x0 = (i < n_max - 1 && trace_x0) ? static_cast<float*>(trace_x0) + (size_t)i * tot : nullptr;
-        up.trace_xt = (i < n_max - 1 && trace_xt) ? static_cast<float*>(trace_xt) + (size_t)i * tot : nullptr;
-        up.noise = static_cast<const float*>(noise); up.z0 = static_cast<const float*>(init_latent); up.mask = static_cast<const float*>(mask);
-        up.rows = tab_dev + (size_t)i * B; up.sharp = sharp_f; up.bright = bright_f;
-        up.active = Bi; up.img = e->img; up.chan_stride = e->cfg.image_size * e->cfg.image_size;
-        {
-            ProfScope ps(e, KC_UPDATE, s);
-            launch_update_requests(up, s);
-        }
-    }
-    HIP_TRY(hipGetLastError());
-    return TLD_OK;
+    PathScope paths(e);                                       // (debug: the launch paths are recorded; no stage of this entry is kept)
+    SamplePlan p{};
+    p.B = B; p.n_max = n_max; p.stride = 1; p.requests = requests; p.coeffs = coeffs; p.Tn = Tn; p.sig = sig.data(); p.noise_idx = noise_idx.data();
+    p.noise = static_cast<const float*>(noise); p.init_latent = static_cast<const float*>(init_latent); p.mask = static_cast<const float*>(mask);
+    p.labels = static_cast<const float*>(labels); p.neg_labels = static_cast<const float*>(neg_labels); p.sharp = sharp_f; p.bright = bright_f;
+    p.out_latent = static_cast<float*>(out_latent); p.trace_x0 = static_cast<float*>(trace_x0); p.trace_xt = static_cast<float*>(trace_xt);
+    p.path_step = mask ? EP_UPDATE_REQ_MASK : EP_UPDATE_REQ; p.path_start = EP_START_MIX_REQ; p.keep_stages = false;
+    return run_sampler(e, p, static_cast<hipStream_t>(hip_stream));
 }
 
 int tld_debug_gemm_bf16(const void* a, const void* w, float* c, int32_t M, int32_t N, int32_t K, void* hip_stream) {

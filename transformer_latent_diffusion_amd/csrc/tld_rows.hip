@@ -4,10 +4,9 @@
 //   layernorm_bf16      LayerNorm rows -> bf16 GEMM operand                           tld/transformer_blocks.py:131,136
 //   cross_row_kernel    SA residual add + whole cross-attention sub-block + LN3       tld/transformer_blocks.py:136-138, 62-72
 //   tail_kernel         out_proj Linear(d->pd) + unpatchify                           tld/denoiser.py:47-52,72,82
-//   update_kernel       CFG combine + DPM-Solver++(2M)/DDIM update + latent shifts    tld/diffusion.py:66-89,122-125
-//   update_from_kernel  the same step of a trajectory that starts from an image, + the inpainting blend
-//   start_mix_kernel    x_start = s0 eps + (1 - s0) z0, the forward process of tld/train.py:130
-//   update_requests_kernel / start_mix_requests_kernel   the same two with per-sample scalars from a device table
+//   sampler_step_kernel CFG combine + DPM-Solver++(2M)/DDIM update + latent shifts    tld/diffusion.py:66-89,122-125
+//                       (+ the inpainting blend), per-sample scalars from a device table: the one step of all three sampler entries
+//   start_mix_kernel    x_start = s0 eps + (1 - s0) z0, the forward process of tld/train.py:130, s0 per sample from a device table
 //   dwconv_gelu_kernel  depthwise 3x3 + bias + exact GELU, channels-last              tld/transformer_blocks.py:96-103
 //
 // Row layout: a wave owns one token row of d features; lane l holds features {2l, 2l+1} + 128*j
@@ -1017,121 +1016,20 @@ __global__ __launch_bounds__(256) void tail_mfma_kernel(TailParams p, const bf16
 #endif
 
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void update_kernel(UpdateParams p) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const int n = p.batch * p.img;
-    if (i >= n) return;
-    const float cond = p.x0_2b[i], unc = p.x0_2b[n + i];
-    float x0 = p.g * cond + (1.0f - p.g) * unc;                   // diffusion.py:124-125
-    if (p.final_step) {
-        const int ch = (i % p.img) / p.chan_stride;
-        if (ch == 3) x0 += p.sharp;                               // diffusion.py:88
-        if (ch == 0) x0 += p.bright;                              // diffusion.py:89
-        p.x0_out[i] = x0;
-        return;
-    }
-    p.x0_out[i] = x0;
-    if (p.trace_x0) p.trace_x0[i] = x0;
-    const float D = p.c1 * x0 - p.c2 * p.x0_prev[i];              // diffusion.py:76 (c1=1,c2=0: :72/:79)
-    const float xt = (p.a * D + p.b * p.x_t[i]) / p.c;            // diffusion.py:81
-    p.x_t[i] = xt;
-    p.x0_prev[i] = x0;
-    if (p.trace_xt) p.trace_xt[i] = xt;
-}
-
-// ------------------------------------------------------------------------------------------------
-// update_kernel's sibling for tld_sample_from (image-to-image / inpainting).  A thread owns V consecutive elements (V = 4: one 16-byte access
-// per stream; they share a channel and a mask quad because chan_stride % 4 == 0) and runs update_kernel's arithmetic on each, so that without a
-// mask the two kernels write the same bits.  Which products of those expressions the compiler fuses depends on how it vectorises a kernel, so
-// contraction is switched off here and the roundings update_kernel performs are spelled out:
+// The sampler's elementwise step, one launch per step for all three sampler entries: CFG combine, DPM-Solver++(2M)/DDIM update,
+// latent shifts, and with MASK the inpainting blend.  Sample b takes {g, a, b, c, c1, c2, s_next, final} from rows[b * row_stride]: a row per
+// request (tld_sample_requests), or one row for the whole batch.  The launch covers the `active` requests still running at this step; the
+// unconditional operand of sample b sits `active` samples after its conditional one.  A thread owns V consecutive elements (V = 4: one 16-byte
+// access per stream; they share a sample, a channel and a mask quad because img % 4 == 0 and chan_stride % 4 == 0).  Which products the compiler
+// fuses depends on how it vectorises a kernel, so contraction is off and the roundings are spelled out:
 //   x0 = fma(g, cond, (1 - g) unc)      D = fma(c1, x0, -(c2 x0_prev))      x_t = (a D + b x_t) / c   with both products rounded
-// (tests/test_gpu_img2img.py holds the two kernels to equal bits).  MASK adds, in the same launch:
+// MASK adds, in the same launch:
 //   after the update   x_t <- m x_t + (1 - m) (s_next eps + (1 - s_next) z0)     the known region rides the forward process of the same eps
 //   on the final step  x0  <- m x0  + (1 - m) z0                                  before the latent shifts
-// x0_prev, x0_out of the inner steps and trace_x0 keep the unblended prediction.  The blend is written m a + (1 - m) b: m = 1 gives a and m = 0
-// gives b exactly, and with no contraction it rounds as the fp32 reference loop does.
+// x0_prev and trace_x0 keep the unblended prediction.  The blend is written m a + (1 - m) b: m = 1 gives a and m = 0 gives b exactly, and with
+// no contraction it rounds as the fp32 reference loop does.
 template <bool MASK, int V>
-__global__ __launch_bounds__(256) void update_from_kernel(UpdateFromParams q) {
-#pragma clang fp contract(off)
-    const UpdateParams& p = q.u;
-    const int i = (blockIdx.x * 256 + threadIdx.x) * V;
-    const int n = p.batch * p.img;
-    if (i >= n) return;
-    float cond[V], unc[V], prev[V], xin[V], eps[V], z[V], m[V], x0o[V], xto[V];
-    auto load = [&](float* dst, const float* src) {
-        if constexpr (V == 4) *reinterpret_cast<float4*>(dst) = *reinterpret_cast<const float4*>(src);
-        else dst[0] = src[0];
-    };
-    auto store = [&](float* dst, const float* src) {
-        if constexpr (V == 4) *reinterpret_cast<float4*>(dst) = *reinterpret_cast<const float4*>(src);
-        else dst[0] = src[0];
-    };
-    const int b = i / p.img, r = i - b * p.img;
-    const int ch = r / p.chan_stride;
-    load(cond, p.x0_2b + i);
-    load(unc, p.x0_2b + n + i);
-    if constexpr (MASK) {
-        load(m, q.mask + (size_t)b * p.chan_stride + (r - ch * p.chan_stride));
-        load(z, q.z0 + i);
-    }
-    if (p.final_step) {
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-            float x0 = __builtin_fmaf(p.g, cond[v], (1.0f - p.g) * unc[v]);   // diffusion.py:124-125
-            if constexpr (MASK) x0 = m[v] * x0 + (1.0f - m[v]) * z[v];
-            if (ch == 3) x0 += p.sharp;                                   // diffusion.py:88
-            if (ch == 0) x0 += p.bright;                                  // diffusion.py:89
-            x0o[v] = x0;
-        }
-        store(p.x0_out + i, x0o);
-        return;
-    }
-    load(prev, p.x0_prev + i);
-    load(xin, p.x_t + i);
-    if constexpr (MASK) load(eps, q.noise + i);
-#pragma unroll
-    for (int v = 0; v < V; ++v) {
-        const float x0 = __builtin_fmaf(p.g, cond[v], (1.0f - p.g) * unc[v]);
-        const float D = __builtin_fmaf(p.c1, x0, -(p.c2 * prev[v]));      // diffusion.py:76 (c1=1,c2=0: :72/:79)
-        float xt = (p.a * D + p.b * xin[v]) / p.c;                        // diffusion.py:81
-        if constexpr (MASK) {
-            const float known = q.s_next * eps[v] + (1.0f - q.s_next) * z[v];
-            xt = m[v] * xt + (1.0f - m[v]) * known;
-        }
-        x0o[v] = x0;
-        xto[v] = xt;
-    }
-    store(p.x0_out + i, x0o);
-    if (p.trace_x0) store(p.trace_x0 + i, x0o);
-    store(p.x_t + i, xto);
-    store(p.x0_prev + i, x0o);
-    if (p.trace_xt) store(p.trace_xt + i, xto);
-}
-
-// x_start = s0 eps + (1 - s0) z0: the forward process at the first remaining level (tld/train.py:130)
-template <int V>
-__global__ __launch_bounds__(256) void start_mix_kernel(const float* __restrict__ noise, const float* __restrict__ z0, float s0,
-                                                        float* __restrict__ x_t, int n) {
-#pragma clang fp contract(off)
-    const int i = (blockIdx.x * 256 + threadIdx.x) * V;
-    if (i >= n) return;
-    if constexpr (V == 4) {
-        const float4 e = *reinterpret_cast<const float4*>(noise + i), z = *reinterpret_cast<const float4*>(z0 + i);
-        const float t = 1.0f - s0;
-        *reinterpret_cast<float4*>(x_t + i) = make_float4(s0 * e.x + t * z.x, s0 * e.y + t * z.y, s0 * e.z + t * z.z, s0 * e.w + t * z.w);
-    } else {
-        x_t[i] = s0 * noise[i] + (1.0f - s0) * z0[i];
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// update_from_kernel's sibling for tld_sample_requests: B independent requests in one launch, each with its own guidance,
-// coefficients and final step, read from rows[sample].  The arithmetic is update_from_kernel's, expression by expression (contraction off,
-// the same three spelled-out roundings, the same m a + (1 - m) b blends), so request b's elements carry the bits the batch-1 call of
-// update_kernel / update_from_kernel writes for it.  The launch covers the `active` requests still running at this step; the unconditional
-// operand of sample b sits `active` samples after its conditional one.  A thread's V elements share a sample (img % 4 == 0), hence a row.
-template <bool MASK, int V>
-__global__ __launch_bounds__(256) void update_requests_kernel(UpdateRequestsParams p) {
+__global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p) {
 #pragma clang fp contract(off)
     const int i = (blockIdx.x * 256 + threadIdx.x) * V;
     const int n = p.active * p.img;
@@ -1147,7 +1045,7 @@ __global__ __launch_bounds__(256) void update_requests_kernel(UpdateRequestsPara
     };
     const int b = i / p.img, r = i - b * p.img;
     const int ch = r / p.chan_stride;
-    const UpdateRequestRow q = p.rows[b];
+    const SamplerStepRow q = p.rows[b * p.row_stride];
     load(cond, p.x0_2b + i);
     load(unc, p.x0_2b + n + i);
     if constexpr (MASK) {
@@ -1187,14 +1085,15 @@ __global__ __launch_bounds__(256) void update_requests_kernel(UpdateRequestsPara
     if (p.trace_xt) store(p.trace_xt + i, xto);
 }
 
-// start_mix_kernel with the mix of each sample read from s0[sample]; a sample whose s0 is exactly 1 is copied, as tld_sample_from copies it
+// x_start = s0 eps + (1 - s0) z0: the forward process at the first remaining level (tld/train.py:130), s0 read per sample from s0v[sample * s0_stride];
+// a sample whose s0 is exactly 1 starts from eps itself and is copied
 template <int V>
-__global__ __launch_bounds__(256) void start_mix_requests_kernel(const float* __restrict__ noise, const float* __restrict__ z0,
-                                                                 const float* __restrict__ s0v, float* __restrict__ x_t, int n, int img) {
+__global__ __launch_bounds__(256) void start_mix_kernel(const float* __restrict__ noise, const float* __restrict__ z0, const float* __restrict__ s0v,
+                                                        int s0_stride, float* __restrict__ x_t, int n, int img) {
 #pragma clang fp contract(off)
     const int i = (blockIdx.x * 256 + threadIdx.x) * V;
     if (i >= n) return;
-    const float s0 = s0v[i / img];
+    const float s0 = s0v[(i / img) * s0_stride];
     if constexpr (V == 4) {
         const float4 e = *reinterpret_cast<const float4*>(noise + i);
         if (s0 == 1.0f) { *reinterpret_cast<float4*>(x_t + i) = e; return; }
@@ -1595,66 +1494,34 @@ void launch_tail(const TailParams& p, hipStream_t s) {
     TLD_DISPATCH_D(p.d, { TLD_LDS_OPT_IN((tail_kernel<NJ, HALF>), lds); hipLaunchKernelGGL((tail_kernel<NJ, HALF>), dim3((rows + rpb - 1) / rpb), dim3(256), lds, s, p, rpb); });
 }
 
-void launch_update(const UpdateParams& p, hipStream_t s) {
-    const int n = p.batch * p.img;
-    note_path(EP_UPDATE);
-    hipLaunchKernelGGL(update_kernel, dim3((n + 255) / 256), dim3(256), 0, s, p);
-}
-
 namespace {
 bool aligned16(const void* a) { return (reinterpret_cast<uintptr_t>(a) & 15) == 0; }
 }
 
-void launch_update_from(const UpdateFromParams& q, hipStream_t s) {
-    const UpdateParams& p = q.u;
-    const int n = p.batch * p.img;
-    // 16-byte accesses: four consecutive elements then share a sample, a channel and one aligned mask quad (null pointers count as aligned)
-    const bool vec = p.img % 4 == 0 && p.chan_stride % 4 == 0 && aligned16(p.x0_2b) && aligned16(p.x_t) && aligned16(p.x0_prev) && aligned16(p.x0_out) &&
-                     aligned16(p.trace_x0) && aligned16(p.trace_xt) && aligned16(q.noise) && aligned16(q.z0) && aligned16(q.mask);
-    const int threads = vec ? n / 4 : n;
-    const dim3 grid((threads + 255) / 256), block(256);
-    note_path(q.mask ? EP_UPDATE_FROM_MASK : EP_UPDATE_FROM);
-    if (q.mask) {
-        if (vec) hipLaunchKernelGGL((update_from_kernel<true, 4>), grid, block, 0, s, q);
-        else hipLaunchKernelGGL((update_from_kernel<true, 1>), grid, block, 0, s, q);
-    } else {
-        if (vec) hipLaunchKernelGGL((update_from_kernel<false, 4>), grid, block, 0, s, q);
-        else hipLaunchKernelGGL((update_from_kernel<false, 1>), grid, block, 0, s, q);
-    }
-}
-
-void launch_start_mix(const float* noise, const float* z0, float s0, float* x_t, int n, hipStream_t s) {
-    note_path(EP_START_MIX);
-    if (n % 4 == 0 && aligned16(noise) && aligned16(z0) && aligned16(x_t))
-        hipLaunchKernelGGL((start_mix_kernel<4>), dim3((n / 4 + 255) / 256), dim3(256), 0, s, noise, z0, s0, x_t, n);
-    else
-        hipLaunchKernelGGL((start_mix_kernel<1>), dim3((n + 255) / 256), dim3(256), 0, s, noise, z0, s0, x_t, n);
-}
-
-void launch_update_requests(const UpdateRequestsParams& p, hipStream_t s) {
+void launch_sampler_step(const SamplerStepParams& p, int path, hipStream_t s) {
     const int n = p.active * p.img;
-    // as launch_update_from: 16-byte accesses need four consecutive elements in one sample, one channel and one aligned mask quad
+    // 16-byte accesses: four consecutive elements then share a sample, a channel and one aligned mask quad (null pointers count as aligned)
     const bool vec = p.img % 4 == 0 && p.chan_stride % 4 == 0 && aligned16(p.x0_2b) && aligned16(p.x_t) && aligned16(p.x0_prev) && aligned16(p.out_latent) &&
                      aligned16(p.trace_x0) && aligned16(p.trace_xt) && aligned16(p.noise) && aligned16(p.z0) && aligned16(p.mask);
     const int threads = vec ? n / 4 : n;
     const dim3 grid((threads + 255) / 256), block(256);
-    note_path(p.mask ? EP_UPDATE_REQ_MASK : EP_UPDATE_REQ);
+    note_path(path);
     if (p.mask) {
-        if (vec) hipLaunchKernelGGL((update_requests_kernel<true, 4>), grid, block, 0, s, p);
-        else hipLaunchKernelGGL((update_requests_kernel<true, 1>), grid, block, 0, s, p);
+        if (vec) hipLaunchKernelGGL((sampler_step_kernel<true, 4>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((sampler_step_kernel<true, 1>), grid, block, 0, s, p);
     } else {
-        if (vec) hipLaunchKernelGGL((update_requests_kernel<false, 4>), grid, block, 0, s, p);
-        else hipLaunchKernelGGL((update_requests_kernel<false, 1>), grid, block, 0, s, p);
+        if (vec) hipLaunchKernelGGL((sampler_step_kernel<false, 4>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((sampler_step_kernel<false, 1>), grid, block, 0, s, p);
     }
 }
 
-void launch_start_mix_requests(const float* noise, const float* z0, const float* s0, float* x_t, int batch, int img, hipStream_t s) {
+void launch_start_mix(const float* noise, const float* z0, const float* s0v, int s0_stride, float* x_t, int batch, int img, int path, hipStream_t s) {
     const int n = batch * img;
-    note_path(EP_START_MIX_REQ);
+    note_path(path);
     if (img % 4 == 0 && aligned16(noise) && aligned16(z0) && aligned16(x_t))
-        hipLaunchKernelGGL((start_mix_requests_kernel<4>), dim3((n / 4 + 255) / 256), dim3(256), 0, s, noise, z0, s0, x_t, n, img);
+        hipLaunchKernelGGL((start_mix_kernel<4>), dim3((n / 4 + 255) / 256), dim3(256), 0, s, noise, z0, s0v, s0_stride, x_t, n, img);
     else
-        hipLaunchKernelGGL((start_mix_requests_kernel<1>), dim3((n + 255) / 256), dim3(256), 0, s, noise, z0, s0, x_t, n, img);
+        hipLaunchKernelGGL((start_mix_kernel<1>), dim3((n + 255) / 256), dim3(256), 0, s, noise, z0, s0v, s0_stride, x_t, n, img);
 }
 
 // Streaming form of the same computation for grids that are a multiple of 32 wide (512 / 1024 px latents; round 3): one workgroup =

@@ -240,18 +240,23 @@ class Denoiser:
         lab = labels.to(device=dev, dtype=torch.float32).contiguous()
         co = np.ascontiguousarray(coeffs, dtype=np.float32)
         n_levels = co.shape[0]
-        out = torch.empty_like(xT)
+        return self._run_sampler(xT, n_levels, trace, lambda out, tx0, txt, stream: _lib.check(_lib.lib().tld_sample(
+            h, xT.data_ptr(), lab.data_ptr(), co.ctypes.data_as(C.POINTER(C.c_float)), n_levels,
+            float(class_guidance), float(sharp_f), float(bright_f), out, B, tx0, txt, stream), "tld_sample"))
+
+    @staticmethod
+    def _run_sampler(noise: torch.Tensor, n_levels: int, trace: bool, call):
+        """What sample_latents and sample_latents_from share after their arguments: the result and trace tensors shaped after ``noise``
+        (fp32, on the engine's device), then ``call(out, trace_x0, trace_xt, stream)`` -- pointers -- on that device's current stream."""
+        dev = noise.device
+        out = torch.empty_like(noise)
         tx0 = txt = None
         if trace:
-            tx0 = torch.empty((n_levels - 1,) + tuple(xT.shape), device=dev, dtype=torch.float32)
+            tx0 = torch.empty((n_levels - 1,) + tuple(noise.shape), device=dev, dtype=torch.float32)
             txt = torch.empty_like(tx0)
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().tld_sample(
-                h, xT.data_ptr(), lab.data_ptr(), co.ctypes.data_as(C.POINTER(C.c_float)), n_levels,
-                float(class_guidance), float(sharp_f), float(bright_f), out.data_ptr(), B,
-                C.c_void_p(tx0.data_ptr() if trace else None), C.c_void_p(txt.data_ptr() if trace else None),
-                C.c_void_p(stream)), "tld_sample")
+            call(ptr(out), ptr(tx0), ptr(txt), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
         return (out, tx0, txt) if trace else out
 
     @torch.no_grad()
@@ -278,19 +283,10 @@ class Denoiser:
         lab = labels.to(device=dev, dtype=torch.float32).contiguous()
         co = np.ascontiguousarray(coeffs, dtype=np.float32)
         n_levels = co.shape[0]
-        out = torch.empty_like(eps)
-        tx0 = txt = None
-        if trace:
-            tx0 = torch.empty((n_levels - 1,) + tuple(eps.shape), device=dev, dtype=torch.float32)
-            txt = torch.empty_like(tx0)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().tld_sample_from(
-                h, eps.data_ptr(), z0.data_ptr(), C.c_void_p(m.data_ptr() if m is not None else None), float(start_mix), lab.data_ptr(),
-                co.ctypes.data_as(C.POINTER(C.c_float)), n_levels, float(class_guidance), float(sharp_f), float(bright_f), out.data_ptr(), B,
-                C.c_void_p(tx0.data_ptr() if trace else None), C.c_void_p(txt.data_ptr() if trace else None),
-                C.c_void_p(stream)), "tld_sample_from")
-        return (out, tx0, txt) if trace else out
+        return self._run_sampler(eps, n_levels, trace, lambda out, tx0, txt, stream: _lib.check(_lib.lib().tld_sample_from(
+            h, eps.data_ptr(), z0.data_ptr(), C.c_void_p(m.data_ptr() if m is not None else None), float(start_mix), lab.data_ptr(),
+            co.ctypes.data_as(C.POINTER(C.c_float)), n_levels, float(class_guidance), float(sharp_f), float(bright_f), out, B,
+            tx0, txt, stream), "tld_sample_from"))
 
     @torch.no_grad()
     def sample_latents_requests(self, noise: torch.Tensor, labels: torch.Tensor, coeff_list, guidance, *, neg_labels=None, init_latents=None,
