@@ -224,3 +224,56 @@ def test_images_to_latents_to_a_training_step():
     loss = tr.train_step((z / 8.0).cpu(), y)                           # (host batches, as the reference's loader yields them)
     torch.cuda.synchronize()
     assert torch.isfinite(loss).all()
+
+
+def test_two_engines_in_one_process_have_independent_cores():
+    """An AutoencoderKL's decoder and encoder engines alive together: interleaved calls, debug capture on the encoder only, and a rebuilt
+    encoder engine leave each half bitwise equal to a stand-alone object with the same weights, and each engine's weight bytes alone."""
+    from transformer_latent_diffusion_amd import AutoencoderKL
+    from transformer_latent_diffusion_amd.vae import AutoencoderKLDecoder, VaeDecoderConfig
+    from transformer_latent_diffusion_amd.vae_encoder import AutoencoderKLEncoder
+    ecfg, dcfg = _tiny_cfg(), VaeDecoderConfig(block_out_channels=(64, 128), layers_per_block=1)
+    vae = AutoencoderKL(ecfg, dcfg, init_seed=5, max_batch=2).to(_dev())
+    x = _image(76, (2, 3, 64, 64)).to(_dev())
+    z = torch.randn(2, 4, 16, 16, generator=torch.Generator().manual_seed(77)).to(_dev())
+    with pytest.warns(RuntimeWarning):
+        want_img = AutoencoderKLDecoder(dcfg, init_seed=5, max_batch=2).decode(z)[0]
+        want_mom = AutoencoderKLEncoder(ecfg, init_seed=5, max_batch=2).moments(x)
+        img0 = vae.decode(z)[0]
+        dec_bytes = vae.decoder.weight_bytes
+        vae.encoder._ensure_engine(x.device, 64)
+        vae.encoder.set_debug(True)
+        mom0 = vae.encoder.moments(x)
+    enc_bytes = vae.encoder.weight_bytes
+    img1 = vae.decode(z)[0]
+    assert dec_bytes > 0 and enc_bytes > 0 and vae.decoder.weight_bytes == dec_bytes and vae.encoder.weight_bytes == enc_bytes
+    assert vae.encoder.read_stage("mid.attn").shape == (2, 128, 32, 32)
+    for name in ("conv_in", "mid.res0", "mid.attn", "mid.res1", "up0.res0", "norm_out", "down0.res0"):
+        with pytest.raises(RuntimeError, match="no captured stage named"):
+            vae.decoder.read_stage(name)
+    vae.encoder._drop_engine()
+    assert vae.encoder._engine is None and vae.decoder._engine is not None
+    mom1 = vae.encoder.moments(x)
+    torch.cuda.synchronize()
+    assert vae.encoder.weight_bytes == enc_bytes and vae.decoder.weight_bytes == dec_bytes
+    assert torch.equal(img0, want_img) and torch.equal(img1, want_img)
+    assert torch.equal(mom0, want_mom) and torch.equal(mom1, want_mom)
+
+
+def test_conv_hooks_refuse_oversized_operands_with_a_status():
+    """Both debug convolution hooks run one body: a source image of 4 GiB or more is refused before anything is allocated or launched, with
+    a non-zero status, tld_last_error set and the output untouched.  (No argument of either hook reaches a refusal by launch_gemm itself:
+    its operand-reach check covers plain GEMMs only, EPI_F32 convolutions exist at both tile widths, and a hook sets cv_up or cv_down, never
+    both; the body passes that status on all the same.)"""
+    from transformer_latent_diffusion_amd import _lib
+    L = _lib.lib()
+    d = _dev()
+    x = torch.zeros(64, dtype=torch.bfloat16, device=d)
+    w = torch.zeros(8 * 9 * 64, dtype=torch.bfloat16, device=d)
+    out = torch.full((8,), float("nan"), device=d)
+    for call in (lambda: L.tld_debug_conv3x3(x.data_ptr(), w.data_ptr(), out.data_ptr(), 8, 4096, 4096, 64, 8, 0, _stream()),     # 16 GiB of source
+                 lambda: L.tld_debug_conv3x3_s2(x.data_ptr(), w.data_ptr(), out.data_ptr(), 8, 2048, 2048, 64, 8, _stream())):
+        rc = call()
+        assert rc != 0 and b"4 GiB" in L.tld_last_error(), (rc, L.tld_last_error())
+    torch.cuda.synchronize()
+    assert torch.isnan(out).all()

@@ -34,6 +34,35 @@ def test_synthetic_weights_are_deterministic():
     assert any(not np.array_equal(a[k], c[k]) for k in a)
 
 
+# sha1 over key names, shapes and bytes of the synthetic decoder / encoder weights, taken before the two fills were merged into one:
+# the golden fixtures under tests/golden/ were generated from these weights, so the Philox keys, the draw order and the gains must stay
+_SYNTH_DIGESTS = {
+    ("tiny", 0): ("081ca5f49dd02a2777647b2023802207fdba1be1", "6200d2c41d430c5bc0da07815985bbc3377de825"),
+    ("tiny", 3): ("97b3635cf51a7b2dbab71b96102ad905b241d904", "456188240e908722c4d4e05c07738e0cd2cf3df2"),
+    ("sdxl", 0): ("ce7930d8136662fa021fe964983e618ef5af485c", "bfbc26c3c6d4aff56a455f746429362e11525af1"),
+    ("sdxl", 3): ("bded6cbf1afead43201cb8e1702c7d139ff48f13", "bee1de529c383dcf724fc0f3786896c125af6dcf"),
+}
+
+
+def _sd_digest(sd):
+    import hashlib
+    h = hashlib.sha1()
+    for k, v in sd.items():
+        assert v.dtype == np.float32
+        h.update(k.encode())
+        h.update(repr(tuple(v.shape)).encode())
+        h.update(np.ascontiguousarray(v).tobytes())
+    return h.hexdigest()
+
+
+@pytest.mark.parametrize("geom,seed", sorted(_SYNTH_DIGESTS))
+def test_synthetic_weights_are_pinned(geom, seed):
+    from transformer_latent_diffusion_amd.vae_encoder import VaeEncoderConfig, synth_vae_encoder_state_dict
+    kw = dict(block_out_channels=(64, 128), layers_per_block=1) if geom == "tiny" else {}
+    got = (_sd_digest(synth_vae_state_dict(VaeDecoderConfig(**kw), seed)), _sd_digest(synth_vae_encoder_state_dict(VaeEncoderConfig(**kw), seed)))
+    assert got == _SYNTH_DIGESTS[(geom, seed)]
+
+
 # ---- an nn.Module decoder built from the published module graph, independent of the functional restatement ---------
 class _Res(nn.Module):
     def __init__(self, cin, cout, g):

@@ -2,6 +2,8 @@
 """Dump the g5 forward, a 70-sample forward, the g5 35-step CFG end latent and the tiny model's sampler outputs (end latent and both traces of a plain call, a
 strength-0.65 call, a masked call and the five-request call of tests/test_gpu_requests.py) of the engine library selected by TLD_LIB (same-box A/B of builds:
 outputs of two builds that only re-order work must be BITWISE equal).  One "part <name> <sha1>" line per tensor: equal lines are equal bits.
+Then the VAE: a tiny decoder (latent side 8: one sample per attention step, no fused GroupNorm statistics; side 16: batched attention, fused statistics)
+and a tiny encoder (64 px, fp32 and bf16 input), B = 2 -- the output and every captured stage as parts, plus a "vae <name> weight_bytes ... launches ..." line each.
     TLD_LIB=<lib.so> python tools/lib_ab_check.py out.npy"""
 import hashlib, os, sys
 from dataclasses import asdict
@@ -44,6 +46,28 @@ calls = {"tiny plain": lambda: gent.generate_latents(labels, num_imgs=5, img_siz
 for name, call in calls.items():
     for what, v in zip(("end latent", "trace_x0", "trace_xt"), call()):
         parts[f"{name} {what}"] = v.cpu().numpy()
+# the VAE engines: (64, 128), one layer per block, B = 2 -- the smallest shapes that reach every host path the two engines share
+import warnings
+from transformer_latent_diffusion_amd.vae import AutoencoderKLDecoder, VaeDecoderConfig
+from transformer_latent_diffusion_amd.vae_encoder import AutoencoderKLEncoder, VaeEncoderConfig
+warnings.simplefilter("ignore", RuntimeWarning)            # (the synthetic-weights notice)
+mid = ["mid.res0", "mid.attn", "mid.res1"]
+dec_stages = ["conv_in"] + mid + ["up0.res0", "up0.res1", "up0.upsample", "up1.res0", "up1.res1", "norm_out"]
+enc_stages = ["conv_in", "down0.res0", "down0.downsample", "down1.res0"] + mid + ["norm_out"]
+def vae_parts(name, eng, call, inp, stages):
+    call(inp)                                               # builds the engine
+    eng.set_debug(True); eng.set_profile(True)
+    parts[name] = call(inp).cpu().numpy()
+    for st in stages:
+        parts[f"{name} {st}"] = eng.read_stage(st).numpy()
+    print("vae", name, "weight_bytes", eng.weight_bytes, "launches", {k: n for k, (_, n) in eng.get_profile().items()})
+dec = AutoencoderKLDecoder(VaeDecoderConfig(block_out_channels=(64, 128), layers_per_block=1), init_seed=4, max_batch=2)
+for side in (8, 16):
+    vae_parts(f"vae decode {side}", dec, lambda z: dec.decode(z)[0], torch.randn(2, 4, side, side, generator=rg).to(dev), dec_stages)
+enc = AutoencoderKLEncoder(VaeEncoderConfig(block_out_channels=(64, 128), layers_per_block=1), init_seed=4, max_batch=2)
+img = (torch.randn(2, 3, 64, 64, generator=rg) * 0.6).clamp(-1, 1)
+for dt in (torch.float32, torch.bfloat16):
+    vae_parts(f"vae encode {dt}".replace("torch.", ""), enc, enc.moments, img.to(dt).to(dev), enc_stages)
 for name, v in parts.items():
     assert np.isfinite(v).all(), name
     print("part", name, tuple(v.shape), hashlib.sha1(np.ascontiguousarray(v).tobytes()).hexdigest())

@@ -263,31 +263,28 @@ enum VClass { VC_CONV = 0, VC_GEMM, VC_GN, VC_OTHER, VC_COUNT };
 
 struct Stage { std::string name; bf16* dev = nullptr; int B = 0, C = 0, H = 0, W = 0; };
 
-}  // namespace
-
-struct tld_vae {
-    tld_vae_config cfg{};
-    int G = 32, zc = 4, oc = 3, nb = 0, hl = 0;
-    std::vector<int> boc;                 // block_out_channels (encoder order)
+// What resnet() / attention() / group_norm() / conv3x3() and the weight packing work on: the state the decoder and the encoder have in
+// common.  Each engine owns one next to its own config and its own layers; nothing here knows which of the two it serves.
+struct VaeCore {
+    int device_id = 0, max_batch = 0, G = 32;
+    int C0 = 0, hl = 0;                   // the mid block's width and side
+    bool mid_attn = false;
     bool finalized = false;
     std::map<std::string, HostTensor> host;
     std::vector<void*> allocs;
     int64_t weight_bytes = 0;
 
-    // weights
-    float *pq_w = nullptr, *pq_b = nullptr, *cin_wt = nullptr, *cin_b = nullptr, *cout_b = nullptr, *zero_bias = nullptr;
-    int C0 = 0;
+    // weights of the part both halves have: mid block, its attention, the output norm and convolution
+    float* zero_bias = nullptr;
     Resnet mid0, mid1;
     GnW attn_gn;
     ConvW attn_qkv, attn_out;             // [3C][C] (q | k | v rows) and [C][C]
-    std::vector<UpBlock> ups;
     GnW norm_out;
     ConvW conv_out;
 
     // workspace: four activation buffers (each with a zero page in front) + small ones
     char* buf[4] = {nullptr, nullptr, nullptr, nullptr};
     size_t buf_elems = 0;                 // bf16 elements of data per buffer
-    float* io_z = nullptr;
     float2 *gn_partial = nullptr, *gn_stats = nullptr;
     int gn_max_chunks = 0;
     // mid-block attention scratch for att_nb samples at a time: scores fp32 [att_nb][HW][HW], probabilities bf16 (same shape),
@@ -309,10 +306,8 @@ struct tld_vae {
     bf16* data(int i) const { return reinterpret_cast<bf16*>(buf[i] + kHdr); }
 };
 
-namespace {
-
 template <typename T>
-int dev_alloc(tld_vae* v, T** out, size_t count, bool weight = false) {
+int dev_alloc(VaeCore* v, T** out, size_t count, bool weight = false) {
     void* p = nullptr;
     HIP_TRY(hipMalloc(&p, count * sizeof(T) > 0 ? count * sizeof(T) : 16));
     v->allocs.push_back(p);
@@ -321,12 +316,12 @@ int dev_alloc(tld_vae* v, T** out, size_t count, bool weight = false) {
     return TLD_OK;
 }
 
-int upload_f32(tld_vae* v, const std::vector<float>& h, float** out) {
+int upload_f32(VaeCore* v, const std::vector<float>& h, float** out) {
     if (int rc = dev_alloc(v, out, h.size(), true)) return rc;
     HIP_TRY(hipMemcpy(*out, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
     return TLD_OK;
 }
-int upload_bf16(tld_vae* v, const std::vector<float>& h, bf16** out) {
+int upload_bf16(VaeCore* v, const std::vector<float>& h, bf16** out) {
     std::vector<uint16_t> t(h.size());
     for (size_t i = 0; i < h.size(); ++i) t[i] = f32_to_bf16_rne(h[i]);
     if (int rc = dev_alloc(v, out, h.size(), true)) return rc;
@@ -334,12 +329,12 @@ int upload_bf16(tld_vae* v, const std::vector<float>& h, bf16** out) {
     return TLD_OK;
 }
 
-const HostTensor* find(const tld_vae* v, const std::string& key) {
+const HostTensor* find(const VaeCore* v, const std::string& key) {
     auto it = v->host.find(key);
     return it == v->host.end() ? nullptr : &it->second;
 }
 
-int need(const tld_vae* v, const std::string& key, std::initializer_list<int64_t> shape, const HostTensor** out) {
+int need(const VaeCore* v, const std::string& key, std::initializer_list<int64_t> shape, const HostTensor** out) {
     const HostTensor* t = find(v, key);
     if (!t) return fail(TLD_ERR_STATE, "missing state_dict entry '%s'", key.c_str());
     int64_t n = 1, m = 1;
@@ -361,7 +356,7 @@ int need(const tld_vae* v, const std::string& key, std::initializer_list<int64_t
 }
 
 // conv weight [cout][cin][k][k] -> bf16 [cout][k*k][cin]
-int pack_conv(tld_vae* v, const std::string& prefix, int cin, int cout, int k, ConvW* cw) {
+int pack_conv(VaeCore* v, const std::string& prefix, int cin, int cout, int k, ConvW* cw) {
     const HostTensor *w = nullptr, *b = nullptr;
     if (int rc = need(v, prefix + ".weight", {cout, cin, k, k}, &w)) return rc;
     if (int rc = need(v, prefix + ".bias", {cout}, &b)) return rc;
@@ -374,7 +369,7 @@ int pack_conv(tld_vae* v, const std::string& prefix, int cin, int cout, int k, C
     if (int rc = upload_bf16(v, t, &cw->w)) return rc;
     return upload_f32(v, b->data, &cw->b);
 }
-int pack_gn(tld_vae* v, const std::string& prefix, int c, GnW* g) {
+int pack_gn(VaeCore* v, const std::string& prefix, int c, GnW* g) {
     const HostTensor *w = nullptr, *b = nullptr;
     if (int rc = need(v, prefix + ".weight", {c}, &w)) return rc;
     if (int rc = need(v, prefix + ".bias", {c}, &b)) return rc;
@@ -382,7 +377,7 @@ int pack_gn(tld_vae* v, const std::string& prefix, int c, GnW* g) {
     if (int rc = upload_f32(v, w->data, &g->g)) return rc;
     return upload_f32(v, b->data, &g->b);
 }
-int pack_resnet(tld_vae* v, const std::string& prefix, int cin, int cout, Resnet* r) {
+int pack_resnet(VaeCore* v, const std::string& prefix, int cin, int cout, Resnet* r) {
     r->cin = cin; r->cout = cout; r->has_sc = cin != cout;
     if (int rc = pack_gn(v, prefix + ".norm1", cin, &r->n1)) return rc;
     if (int rc = pack_conv(v, prefix + ".conv1", cin, cout, 3, &r->c1)) return rc;
@@ -393,8 +388,8 @@ int pack_resnet(tld_vae* v, const std::string& prefix, int cin, int cout, Resnet
 }
 
 struct Timer {
-    tld_vae* v; int kc; hipStream_t s; bool on = false; size_t idx = 0;
-    Timer(tld_vae* v_, int kc_, hipStream_t s_) : v(v_), kc(kc_), s(s_) {
+    VaeCore* v; int kc; hipStream_t s; bool on = false; size_t idx = 0;
+    Timer(VaeCore* v_, int kc_, hipStream_t s_) : v(v_), kc(kc_), s(s_) {
         if (!v->profile) return;
         if (v->ev_used[kc] == v->ev[kc].size()) {
             hipEvent_t a, b;
@@ -426,7 +421,7 @@ int check_launch(const char* what) {
 }
 
 // GroupNorm (+ SiLU) of the [B, HW, C] image in buffer `src` into buffer `dst`
-int group_norm(tld_vae* v, int src, int dst, const GnW& gn, int B, int HW, int C, bool silu, hipStream_t s) {
+int group_norm(VaeCore* v, int src, int dst, const GnW& gn, int B, int HW, int C, bool silu, hipStream_t s) {
     Timer t(v, VC_GN, s);
     const int ppb = 256;
     const int nchunk = (HW + ppb - 1) / ppb;
@@ -445,7 +440,7 @@ int group_norm(tld_vae* v, int src, int dst, const GnW& gn, int B, int HW, int C
 // 3x3 convolution of buffer `src` ([B, H >> up, W >> up, cin]) into an [B, H, W, cout] image
 //   epi EPI_BIAS_BF16: written to buffer dst;  EPI_BIAS_RESID: added to buffer dst in place;  EPI_F32: fp32 [M][cout] to c_f32
 //   down = 1 (encoder Downsample2D): stride 2 with padding (0, 1, 0, 1) from a [B, 2H, 2W, cin] source instead (GemmParams::cv_down)
-int conv3x3(tld_vae* v, int src, int dst, const ConvW& cw, int B, int H, int W, int up, int epi, float* c_f32, hipStream_t s, int down = 0) {
+int conv3x3(VaeCore* v, int src, int dst, const ConvW& cw, int B, int H, int W, int up, int epi, float* c_f32, hipStream_t s, int down = 0) {
     Timer t(v, VC_CONV, s);
     GemmParams p{};
     p.A = reinterpret_cast<const bf16*>(v->buf[src]);
@@ -470,7 +465,7 @@ int conv3x3(tld_vae* v, int src, int dst, const ConvW& cw, int B, int H, int W, 
 }
 
 // plain GEMM C[M,N] = A[M,K] W[N,K]^T with one of the three epilogues
-int gemm(tld_vae* v, const bf16* A, int lda, const bf16* Wt, int ldw, int M, int N, int K, int epi, const float* bias, bf16* out, int ldo,
+int gemm(VaeCore* v, const bf16* A, int lda, const bf16* Wt, int ldw, int M, int N, int K, int epi, const float* bias, bf16* out, int ldo,
          float* c_f32, hipStream_t s, int w_batch_rows = 0, size_t w_batch_stride_bytes = 0) {
     Timer t(v, VC_GEMM, s);
     GemmParams p{};
@@ -484,7 +479,7 @@ int gemm(tld_vae* v, const bf16* A, int lda, const bf16* Wt, int ldw, int M, int
     return check_launch("gemm");
 }
 
-int snapshot(tld_vae* v, const char* name, int src, int B, int H, int W, int C, hipStream_t s) {
+int snapshot(VaeCore* v, const char* name, int src, int B, int H, int W, int C, hipStream_t s) {
     if (!v->debug) return TLD_OK;
     Stage st;
     st.name = name; st.B = B; st.C = C; st.H = H; st.W = W;
@@ -495,7 +490,7 @@ int snapshot(tld_vae* v, const char* name, int src, int B, int H, int W, int C, 
     return TLD_OK;
 }
 
-void clear_stages(tld_vae* v) {
+void clear_stages(VaeCore* v) {
     for (auto& st : v->stages) (void)hipFree(st.dev);
     v->stages.clear();
 }
@@ -503,7 +498,7 @@ void clear_stages(tld_vae* v) {
 // ResnetBlock2D (diffusers models/resnet.py; temb is None in the VAE, output_scale_factor 1):
 //   h = conv1(silu(norm1(x)));  h = conv2(silu(norm2(h)));  return shortcut(x) + h
 // x lives in buffer *xi; on return *xi names the buffer holding the result.  bufs: x, t (normalised), h, s (shortcut)
-int resnet(tld_vae* v, const Resnet& r, int* xi, int B, int H, int W, hipStream_t s) {
+int resnet(VaeCore* v, const Resnet& r, int* xi, int B, int H, int W, hipStream_t s) {
     int idx[4], n = 0;
     for (int i = 0; i < 4; ++i) if (i != *xi) idx[n++] = i;
     const int x = *xi, t = idx[0], h = idx[1], sc = idx[2];
@@ -523,7 +518,7 @@ int resnet(tld_vae* v, const Resnet& r, int* xi, int B, int H, int W, hipStream_
 
 // Attention block of the mid block (diffusers Attention with heads = 1, dim_head = C, residual_connection, bias):
 //   t = group_norm(x) as [B, HW, C] tokens;  q, k, v = linear(t);  o = softmax(q k^T / sqrt(C)) v;  x += to_out(o)
-int attention(tld_vae* v, int* xi, int B, int H, int W, int C, hipStream_t s) {
+int attention(VaeCore* v, int* xi, int B, int H, int W, int C, hipStream_t s) {
     int idx[4], n = 0;
     for (int i = 0; i < 4; ++i) if (i != *xi) idx[n++] = i;
     const int x = *xi, t = idx[0], qkv = idx[1];
@@ -566,93 +561,78 @@ int attention(tld_vae* v, int* xi, int B, int H, int W, int C, hipStream_t s) {
     return check_launch("attention");
 }
 
-size_t max_act_elems(const tld_vae* v) {                    // per sample, over all stages of the decoder
-    size_t mx = 0;
-    int H = v->hl;
-    int c = v->boc[v->nb - 1];
-    mx = std::max(mx, (size_t)H * H * c * 3);               // attention q|k|v
-    for (int i = 0; i < v->nb; ++i) {
-        const int cout = v->boc[v->nb - 1 - i];
-        mx = std::max(mx, (size_t)H * H * std::max(c, cout));
-        c = cout;
-        if (i != v->nb - 1) { H *= 2; mx = std::max(mx, (size_t)H * H * c); }
-    }
-    return mx;
-}
+// ---- what the two engines' ABI entries share -------------------------------------------------------------------------------
 
-}  // namespace
-
-// ---- C ABI -------------------------------------------------------------------------------------------------------------
-
-extern "C" {
-
-int tld_vae_create(const tld_vae_config* cfg, tld_vae** out) {
-    if (!cfg || !out) return fail(TLD_ERR_INVALID, "null argument");
-    *out = nullptr;
+// The config fields both engines have (tld_vae_config / tld_vae_enc_config name them alike); each create checks its own besides.
+template <typename Cfg>
+int check_common_config(const Cfg* cfg) {
     if (cfg->n_blocks < 1 || cfg->n_blocks > 4) return fail(TLD_ERR_INVALID, "n_blocks=%d: 1..4 supported", cfg->n_blocks);
     for (int i = 0; i < cfg->n_blocks; ++i)
         if (!chan_ok(cfg->block_out_channels[i]))
             return fail(TLD_ERR_INVALID, "block_out_channels[%d]=%d: must be one of 64, 128, 256, 512, 1024", i, cfg->block_out_channels[i]);
     if (cfg->latent_channels < 1 || cfg->latent_channels > 16) return fail(TLD_ERR_INVALID, "latent_channels=%d: 1..16 supported", cfg->latent_channels);
-    if (cfg->out_channels < 1 || cfg->out_channels > 8) return fail(TLD_ERR_INVALID, "out_channels=%d: 1..8 supported", cfg->out_channels);
     if (cfg->norm_num_groups < 1 || cfg->norm_num_groups > 64) return fail(TLD_ERR_INVALID, "norm_num_groups=%d: 1..64 supported", cfg->norm_num_groups);
     for (int i = 0; i < cfg->n_blocks; ++i)
         if (cfg->block_out_channels[i] % cfg->norm_num_groups)
             return fail(TLD_ERR_INVALID, "block_out_channels[%d]=%d is not a multiple of norm_num_groups=%d", i, cfg->block_out_channels[i], cfg->norm_num_groups);
     if (cfg->layers_per_block < 1 || cfg->layers_per_block > 8) return fail(TLD_ERR_INVALID, "layers_per_block=%d: 1..8 supported", cfg->layers_per_block);
-    if (cfg->latent_size < 4 || cfg->latent_size > 256) return fail(TLD_ERR_INVALID, "latent_size=%d: 4..256 supported", cfg->latent_size);
-    if (cfg->mid_block_attention && cfg->latent_size % 8)
-        return fail(TLD_ERR_INVALID, "latent_size=%d: the mid-block attention needs a multiple of 8 (h*w tokens in 64-wide K-steps)", cfg->latent_size);
     if (cfg->max_batch < 1) return fail(TLD_ERR_INVALID, "max_batch must be positive");
+    return TLD_OK;
+}
+int check_device(int device_id, const char* half) {          // half: "decoder" / "encoder"
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(TLD_ERR_HIP, "no HIP device available (the VAE decoder has no CPU path)");
-    if (cfg->device_id < 0 || cfg->device_id >= ndev) return fail(TLD_ERR_INVALID, "device_id=%d out of range (%d devices)", cfg->device_id, ndev);
-    DeviceGuard guard(cfg->device_id);
-
-    tld_vae* v = new tld_vae();
-    v->cfg = *cfg;
-    v->G = cfg->norm_num_groups; v->zc = cfg->latent_channels; v->oc = cfg->out_channels; v->nb = cfg->n_blocks; v->hl = cfg->latent_size;
-    v->boc.assign(cfg->block_out_channels, cfg->block_out_channels + cfg->n_blocks);
-    v->C0 = v->boc[v->nb - 1];
-    v->fuse_stats = fuse_stats_enabled();
-    v->buf_elems = max_act_elems(v) * (size_t)cfg->max_batch;
-    const size_t bytes = v->buf_elems * 2 + kHdr;
-    if (bytes >= (1ull << 32)) {
-        const size_t per = max_act_elems(v) * 2;
-        delete v;
-        return fail(TLD_ERR_INVALID, "max_batch=%d: an activation buffer (%zu bytes per sample) must stay below 4 GiB (32-bit DMA offsets); "
-                    "decode in chunks of at most %zu", cfg->max_batch, per, (size_t)(((1ull << 32) - kHdr - 1) / per));
-    }
-    auto bail = [&](int rc) { tld_vae_destroy(v); return rc; };
-    for (int i = 0; i < 4; ++i) {
-        if (int rc = dev_alloc(v, &v->buf[i], bytes)) return bail(rc);
-        if (hipMemset(v->buf[i], 0, kHdr) != hipSuccess) return bail(fail(TLD_ERR_HIP, "hipMemset failed"));
-    }
-    const int Hout = v->hl << (v->nb - 1);
-    const size_t lat = (size_t)cfg->max_batch * v->zc * v->hl * v->hl;
-    if (int rc = dev_alloc(v, &v->io_z, lat)) return bail(rc);
-    v->gn_max_chunks = (Hout * Hout + 255) / 256;
-    if (int rc = dev_alloc(v, &v->gn_partial, (size_t)cfg->max_batch * v->gn_max_chunks * v->G)) return bail(rc);
-    if (int rc = dev_alloc(v, &v->gn_stats, (size_t)cfg->max_batch * v->G)) return bail(rc);
-    if (cfg->mid_block_attention) {
-        const size_t hw = (size_t)v->hl * v->hl;
-        const size_t fit = ((size_t)256 << 20) / (hw * hw * 4);             // samples whose fp32 scores fit in 256 MB
-        v->att_nb = (int)std::max<size_t>(1, std::min<size_t>(fit, (size_t)cfg->max_batch));
-        if (int rc = dev_alloc(v, &v->scores, (size_t)v->att_nb * hw * hw)) return bail(rc);
-        if (int rc = dev_alloc(v, &v->probs, (size_t)v->att_nb * hw * hw)) return bail(rc);
-        if (int rc = dev_alloc(v, &v->vt, (size_t)v->att_nb * hw * v->C0)) return bail(rc);
-    }
-    if (int rc = dev_alloc(v, &v->out_f32, (size_t)cfg->max_batch * Hout * Hout * v->oc)) return bail(rc);
-    *out = v;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(TLD_ERR_HIP, "no HIP device available (the VAE %s has no CPU path)", half);
+    if (device_id < 0 || device_id >= ndev) return fail(TLD_ERR_INVALID, "device_id=%d out of range (%d devices)", device_id, ndev);
     return TLD_OK;
 }
 
-int tld_vae_load_tensor(tld_vae* v, const char* key, const void* host_ptr, const int64_t* shape, int32_t ndim, int32_t dtype) {
-    if (!v || !key || (!host_ptr && ndim > 0) || ndim < 0 || ndim > 8) return fail(TLD_ERR_INVALID, "bad argument");
-    if (v->finalized) return fail(TLD_ERR_STATE, "weights already finalized");
+// The core of a checked config (hl: side of the mid block) and its workspace for max_batch samples: `per` activation elements per sample
+// (the engine's largest stage), GroupNorm scratch for an image of side `side_max`, attention scratch for the mid block, `out_elems` fp32
+// per sample in front of the tail kernel.  On an error the caller destroys the engine, which frees what was allocated.
+template <typename Cfg>
+int core_create(VaeCore* c, const Cfg& cfg, int hl, size_t per, int side_max, size_t out_elems, const char* verb) {
+    c->device_id = cfg.device_id; c->max_batch = cfg.max_batch; c->G = cfg.norm_num_groups;
+    c->C0 = cfg.block_out_channels[cfg.n_blocks - 1]; c->hl = hl; c->mid_attn = cfg.mid_block_attention != 0;
+    c->fuse_stats = fuse_stats_enabled();
+    c->buf_elems = per * (size_t)c->max_batch;
+    const size_t bytes = c->buf_elems * 2 + kHdr;
+    if (bytes >= (1ull << 32))
+        return fail(TLD_ERR_INVALID, "max_batch=%d: an activation buffer (%zu bytes per sample) must stay below 4 GiB (32-bit DMA offsets); "
+                    "%s in chunks of at most %zu", c->max_batch, per * 2, verb, (size_t)(((1ull << 32) - kHdr - 1) / (per * 2)));
+    for (int i = 0; i < 4; ++i) {
+        if (int rc = dev_alloc(c, &c->buf[i], bytes)) return rc;
+        if (hipMemset(c->buf[i], 0, kHdr) != hipSuccess) return fail(TLD_ERR_HIP, "hipMemset failed");
+    }
+    c->gn_max_chunks = (side_max * side_max + 255) / 256;
+    if (int rc = dev_alloc(c, &c->gn_partial, (size_t)c->max_batch * c->gn_max_chunks * c->G)) return rc;
+    if (int rc = dev_alloc(c, &c->gn_stats, (size_t)c->max_batch * c->G)) return rc;
+    if (c->mid_attn) {
+        const size_t hw = (size_t)hl * hl;
+        const size_t fit = ((size_t)256 << 20) / (hw * hw * 4);             // samples whose fp32 scores fit in 256 MB
+        c->att_nb = (int)std::max<size_t>(1, std::min<size_t>(fit, (size_t)c->max_batch));
+        if (int rc = dev_alloc(c, &c->scores, (size_t)c->att_nb * hw * hw)) return rc;
+        if (int rc = dev_alloc(c, &c->probs, (size_t)c->att_nb * hw * hw)) return rc;
+        if (int rc = dev_alloc(c, &c->vt, (size_t)c->att_nb * hw * c->C0)) return rc;
+    }
+    return dev_alloc(c, &c->out_f32, (size_t)c->max_batch * out_elems);
+}
+
+void core_release(VaeCore* c) {
+    clear_stages(c);
+    for (int k = 0; k < VC_COUNT; ++k)
+        for (auto& e : c->ev[k]) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+    for (void* p : c->allocs) (void)hipFree(p);
+    c->allocs.clear();
+}
+
+// load_tensor of an engine that keeps the keys under own[0] / own[1] and passes over the other half's, under other[0] / other[1]
+int core_load_tensor(VaeCore* c, const char* key, const void* host_ptr, const int64_t* shape, int32_t ndim, int32_t dtype,
+                     const char* const (&own)[2], const char* const (&other)[2]) {
+    if (!key || (!host_ptr && ndim > 0) || ndim < 0 || ndim > 8) return fail(TLD_ERR_INVALID, "bad argument");
+    if (c->finalized) return fail(TLD_ERR_STATE, "weights already finalized");
     std::string k(key);
-    if (k.rfind("encoder.", 0) == 0 || k.rfind("quant_conv.", 0) == 0) return TLD_OK;      // the encoder half is not used by decode
-    if (k.rfind("decoder.", 0) != 0 && k.rfind("post_quant_conv.", 0) != 0) return fail(TLD_ERR_KEY, "unknown state_dict key '%s'", key);
+    if (k.rfind(other[0], 0) == 0 || k.rfind(other[1], 0) == 0) return TLD_OK;
+    if (k.rfind(own[0], 0) != 0 && k.rfind(own[1], 0) != 0) return fail(TLD_ERR_KEY, "unknown state_dict key '%s'", key);
     if (dtype != TLD_DTYPE_F32) return fail(TLD_ERR_INVALID, "'%s': host tensors must be fp32", key);
     // pre-0.19 diffusers spelling of the attention block
     static const char* const ren[][2] = {{".query.", ".to_q."}, {".key.", ".to_k."}, {".value.", ".to_v."}, {".proj_attn.", ".to_out.0."}};
@@ -664,162 +644,112 @@ int tld_vae_load_tensor(tld_vae* v, const char* key, const void* host_ptr, const
     int64_t n = 1;
     for (int i = 0; i < ndim; ++i) { if (shape[i] < 0) return fail(TLD_ERR_SHAPE, "'%s': negative dimension", key); t.shape.push_back(shape[i]); n *= shape[i]; }
     t.data.assign(reinterpret_cast<const float*>(host_ptr), reinterpret_cast<const float*>(host_ptr) + n);
-    v->host[k] = std::move(t);
+    c->host[k] = std::move(t);
     return TLD_OK;
 }
 
-int tld_vae_finalize_weights(tld_vae* v) {
-    if (!v) return fail(TLD_ERR_INVALID, "null vae");
-    if (v->finalized) return fail(TLD_ERR_STATE, "weights already finalized");
-    DeviceGuard guard(v->cfg.device_id);
-    const int zc = v->zc, C0 = v->C0;
+// <half>.conv_in: [c0][cin][3][3] -> fp32 [tap][cin][c0] (what both conv_in kernels read) and its bias
+int pack_conv_in(VaeCore* c, const std::string& half, int cin, int c0, float** wt_out, float** b_out) {
     const HostTensor* t = nullptr;
-    if (v->cfg.use_post_quant_conv) {
-        if (int rc = need(v, "post_quant_conv.weight", {zc, zc, 1, 1}, &t)) return rc;
-        if (int rc = upload_f32(v, t->data, &v->pq_w)) return rc;
-        if (int rc = need(v, "post_quant_conv.bias", {zc}, &t)) return rc;
-        if (int rc = upload_f32(v, t->data, &v->pq_b)) return rc;
-    }
-    {   // conv_in: [C0][zc][3][3] -> [tap][zc][C0]
-        if (int rc = need(v, "decoder.conv_in.weight", {C0, zc, 3, 3}, &t)) return rc;
-        std::vector<float> wt((size_t)9 * zc * C0);
-        for (int o = 0; o < C0; ++o)
-            for (int c = 0; c < zc; ++c)
-                for (int tap = 0; tap < 9; ++tap) wt[((size_t)tap * zc + c) * C0 + o] = t->data[((size_t)o * zc + c) * 9 + tap];
-        if (int rc = upload_f32(v, wt, &v->cin_wt)) return rc;
-        if (int rc = need(v, "decoder.conv_in.bias", {C0}, &t)) return rc;
-        if (int rc = upload_f32(v, t->data, &v->cin_b)) return rc;
-    }
-    if (int rc = pack_resnet(v, "decoder.mid_block.resnets.0", C0, C0, &v->mid0)) return rc;
-    if (int rc = pack_resnet(v, "decoder.mid_block.resnets.1", C0, C0, &v->mid1)) return rc;
-    if (v->cfg.mid_block_attention) {
-        const std::string a = "decoder.mid_block.attentions.0";
-        if (int rc = pack_gn(v, a + ".group_norm", C0, &v->attn_gn)) return rc;
-        std::vector<float> w((size_t)3 * C0 * C0), b((size_t)3 * C0);
+    if (int rc = need(c, half + ".conv_in.weight", {c0, cin, 3, 3}, &t)) return rc;
+    std::vector<float> wt((size_t)9 * cin * c0);
+    for (int o = 0; o < c0; ++o)
+        for (int ci = 0; ci < cin; ++ci)
+            for (int tap = 0; tap < 9; ++tap) wt[((size_t)tap * cin + ci) * c0 + o] = t->data[((size_t)o * cin + ci) * 9 + tap];
+    if (int rc = upload_f32(c, wt, wt_out)) return rc;
+    if (int rc = need(c, half + ".conv_in.bias", {c0}, &t)) return rc;
+    return upload_f32(c, t->data, b_out);
+}
+
+// <half>.mid_block: two resnets, the attention projections (q | k | v stacked into one [3C][C] matrix), and the zero bias of the P.V GEMM
+int pack_mid(VaeCore* c, const std::string& half) {
+    const int C = c->C0;
+    const HostTensor* t = nullptr;
+    if (int rc = pack_resnet(c, half + ".mid_block.resnets.0", C, C, &c->mid0)) return rc;
+    if (int rc = pack_resnet(c, half + ".mid_block.resnets.1", C, C, &c->mid1)) return rc;
+    if (c->mid_attn) {
+        const std::string a = half + ".mid_block.attentions.0";
+        if (int rc = pack_gn(c, a + ".group_norm", C, &c->attn_gn)) return rc;
+        std::vector<float> w((size_t)3 * C * C), b((size_t)3 * C);
         const char* names[3] = {".to_q", ".to_k", ".to_v"};
         for (int i = 0; i < 3; ++i) {
-            if (int rc = need(v, a + names[i] + ".weight", {C0, C0}, &t)) return rc;
-            memcpy(w.data() + (size_t)i * C0 * C0, t->data.data(), (size_t)C0 * C0 * 4);
-            if (int rc = need(v, a + names[i] + ".bias", {C0}, &t)) return rc;
-            memcpy(b.data() + (size_t)i * C0, t->data.data(), (size_t)C0 * 4);
+            if (int rc = need(c, a + names[i] + ".weight", {C, C}, &t)) return rc;
+            memcpy(w.data() + (size_t)i * C * C, t->data.data(), (size_t)C * C * 4);
+            if (int rc = need(c, a + names[i] + ".bias", {C}, &t)) return rc;
+            memcpy(b.data() + (size_t)i * C, t->data.data(), (size_t)C * 4);
         }
-        v->attn_qkv.cin = C0; v->attn_qkv.cout = 3 * C0; v->attn_qkv.k = 1;
-        if (int rc = upload_bf16(v, w, &v->attn_qkv.w)) return rc;
-        if (int rc = upload_f32(v, b, &v->attn_qkv.b)) return rc;
-        if (int rc = need(v, a + ".to_out.0.weight", {C0, C0}, &t)) return rc;
-        v->attn_out.cin = C0; v->attn_out.cout = C0; v->attn_out.k = 1;
-        if (int rc = upload_bf16(v, t->data, &v->attn_out.w)) return rc;
-        if (int rc = need(v, a + ".to_out.0.bias", {C0}, &t)) return rc;
-        if (int rc = upload_f32(v, t->data, &v->attn_out.b)) return rc;
+        c->attn_qkv.cin = C; c->attn_qkv.cout = 3 * C; c->attn_qkv.k = 1;
+        if (int rc = upload_bf16(c, w, &c->attn_qkv.w)) return rc;
+        if (int rc = upload_f32(c, b, &c->attn_qkv.b)) return rc;
+        if (int rc = need(c, a + ".to_out.0.weight", {C, C}, &t)) return rc;
+        c->attn_out.cin = C; c->attn_out.cout = C; c->attn_out.k = 1;
+        if (int rc = upload_bf16(c, t->data, &c->attn_out.w)) return rc;
+        if (int rc = need(c, a + ".to_out.0.bias", {C}, &t)) return rc;
+        if (int rc = upload_f32(c, t->data, &c->attn_out.b)) return rc;
     }
-    {
-        std::vector<float> z(1024, 0.f);
-        if (int rc = upload_f32(v, z, &v->zero_bias)) return rc;
-    }
-    v->ups.resize(v->nb);
-    int c = C0;
-    for (int i = 0; i < v->nb; ++i) {
-        UpBlock& ub = v->ups[i];
-        ub.cout = v->boc[v->nb - 1 - i];
-        ub.res.resize(v->cfg.layers_per_block + 1);
-        for (int j = 0; j <= v->cfg.layers_per_block; ++j) {
-            const std::string pre = "decoder.up_blocks." + std::to_string(i) + ".resnets." + std::to_string(j);
-            if (int rc = pack_resnet(v, pre, j == 0 ? c : ub.cout, ub.cout, &ub.res[j])) return rc;
-        }
-        c = ub.cout;
-        ub.has_up = i != v->nb - 1;
-        if (ub.has_up)
-            if (int rc = pack_conv(v, "decoder.up_blocks." + std::to_string(i) + ".upsamplers.0.conv", c, c, 3, &ub.up)) return rc;
-    }
-    if (int rc = pack_gn(v, "decoder.conv_norm_out", c, &v->norm_out)) return rc;
-    {   // conv_out: bf16 [oc][9][c]; its bias is added by the fp32 tail kernel
-        if (int rc = pack_conv(v, "decoder.conv_out", c, v->oc, 3, &v->conv_out)) return rc;
-        v->cout_b = v->conv_out.b;
-    }
-    v->host.clear();
+    std::vector<float> z(1024, 0.f);
+    return upload_f32(c, z, &c->zero_bias);
+}
+
+// <half>.conv_norm_out and conv_out (bf16 [oc][9][cin]; its bias is added by the engine's fp32 tail kernel)
+int pack_out(VaeCore* c, const std::string& half, int cin, int oc) {
+    if (int rc = pack_gn(c, half + ".conv_norm_out", cin, &c->norm_out)) return rc;
+    return pack_conv(c, half + ".conv_out", cin, oc, 3, &c->conv_out);
+}
+
+int core_finish_weights(VaeCore* c) {
+    c->host.clear();
     HIP_TRY(hipDeviceSynchronize());
-    v->finalized = true;
+    c->finalized = true;
     return TLD_OK;
 }
 
-int tld_vae_decode(tld_vae* v, const void* z, float* out, int32_t batch, int32_t io_dtype, void* hip_stream) {
-    if (!v || !z || !out) return fail(TLD_ERR_INVALID, "null argument");
-    if (!v->finalized) return fail(TLD_ERR_STATE, "weights not finalized");
-    if (batch < 1 || batch > v->cfg.max_batch) return fail(TLD_ERR_INVALID, "batch=%d outside 1..max_batch=%d", batch, v->cfg.max_batch);
+// the checks and resets every decode / encode call starts with (under the caller's DeviceGuard: stages are freed here)
+int core_begin_call(VaeCore* c, const void* in, const void* out, int32_t batch, int32_t io_dtype) {
+    if (!in || !out) return fail(TLD_ERR_INVALID, "null argument");
+    if (!c->finalized) return fail(TLD_ERR_STATE, "weights not finalized");
+    if (batch < 1 || batch > c->max_batch) return fail(TLD_ERR_INVALID, "batch=%d outside 1..max_batch=%d", batch, c->max_batch);
     if (io_dtype != TLD_DTYPE_F32 && io_dtype != TLD_DTYPE_BF16 && io_dtype != TLD_DTYPE_F16) return fail(TLD_ERR_INVALID, "io_dtype=%d", io_dtype);
-    DeviceGuard guard(v->cfg.device_id);
-    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-    const int B = batch;
-    if (v->debug) clear_stages(v);
-    for (int k = 0; k < VC_COUNT; ++k) if (!v->profile) v->ev_used[k] = 0;
+    if (c->debug) clear_stages(c);
+    for (int k = 0; k < VC_COUNT; ++k) if (!c->profile) c->ev_used[k] = 0;
+    c->have_partial = false;
+    return TLD_OK;
+}
 
-    int H = v->hl, W = v->hl;
-    v->have_partial = false;
-    const float* zf = reinterpret_cast<const float*>(z);
-    {
-        Timer t(v, VC_OTHER, s);
-        if (io_dtype != TLD_DTYPE_F32) {
-            const long n = (long)B * v->zc * H * W;
-            hipLaunchKernelGGL(vae_cast_in_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, z, io_dtype, v->io_z, n);
-            zf = v->io_z;
-        }
-        const int threads = ((std::max(v->C0, 9 * v->zc) + 63) / 64) * 64;
-        hipLaunchKernelGGL(vae_conv_in_kernel, dim3(B * H * W), dim3(threads), 0, s, zf, v->zc, H, W, v->pq_w, v->pq_b, v->cin_wt, v->cin_b, v->data(0), v->C0);
-        if (int rc = check_launch("conv_in")) return rc;
+// mid block on the [B, H, W, C0] image in buffer *xi: resnet, attention, resnet, each with its snapshot
+int mid_block(VaeCore* c, int* xi, int B, int H, int W, hipStream_t s) {
+    const int C = c->C0;
+    if (int rc = resnet(c, c->mid0, xi, B, H, W, s)) return rc;
+    if (int rc = snapshot(c, "mid.res0", *xi, B, H, W, C, s)) return rc;
+    if (c->mid_attn) {
+        if (int rc = attention(c, xi, B, H, W, C, s)) return rc;
+        if (int rc = snapshot(c, "mid.attn", *xi, B, H, W, C, s)) return rc;
     }
-    int x = 0;
-    int C = v->C0;
-    if (int rc = snapshot(v, "conv_in", x, B, H, W, C, s)) return rc;
-    if (int rc = resnet(v, v->mid0, &x, B, H, W, s)) return rc;
-    if (int rc = snapshot(v, "mid.res0", x, B, H, W, C, s)) return rc;
-    if (v->cfg.mid_block_attention) {
-        if (int rc = attention(v, &x, B, H, W, C, s)) return rc;
-        if (int rc = snapshot(v, "mid.attn", x, B, H, W, C, s)) return rc;
-    }
-    if (int rc = resnet(v, v->mid1, &x, B, H, W, s)) return rc;
-    if (int rc = snapshot(v, "mid.res1", x, B, H, W, C, s)) return rc;
-    for (int i = 0; i < v->nb; ++i) {
-        const UpBlock& ub = v->ups[i];
-        for (size_t j = 0; j < ub.res.size(); ++j) {
-            if (int rc = resnet(v, ub.res[j], &x, B, H, W, s)) return rc;
-            C = ub.cout;
-            const std::string nm = "up" + std::to_string(i) + ".res" + std::to_string(j);
-            if (int rc = snapshot(v, nm.c_str(), x, B, H, W, C, s)) return rc;
-        }
-        if (ub.has_up) {                      // Upsample2D: nearest 2x, then conv 3x3 -- one implicit GEMM over the small image
-            const int dst = (x + 1) & 3;
-            H *= 2; W *= 2;
-            if (int rc = conv3x3(v, x, dst, ub.up, B, H, W, 1, EPI_BIAS_BF16, nullptr, s)) return rc;
-            x = dst;
-            const std::string nm = "up" + std::to_string(i) + ".upsample";
-            if (int rc = snapshot(v, nm.c_str(), x, B, H, W, C, s)) return rc;
-        }
-    }
+    if (int rc = resnet(c, c->mid1, xi, B, H, W, s)) return rc;
+    return snapshot(c, "mid.res1", *xi, B, H, W, C, s);
+}
+
+// conv_norm_out + SiLU, then conv_out of buffer x into out_f32 (fp32 [B*H*W][oc], no bias yet): what each engine's tail kernel reads
+int norm_conv_out(VaeCore* c, int x, int B, int H, int W, int C, hipStream_t s) {
     const int t = (x + 1) & 3;
-    if (int rc = group_norm(v, x, t, v->norm_out, B, H * W, C, true, s)) return rc;
-    if (int rc = snapshot(v, "norm_out", t, B, H, W, C, s)) return rc;
-    if (int rc = conv3x3(v, t, -1, v->conv_out, B, H, W, 0, EPI_F32, v->out_f32, s)) return rc;
-    {
-        Timer tm(v, VC_OTHER, s);
-        const long total = (long)B * H * W;
-        hipLaunchKernelGGL(vae_out_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, v->out_f32, v->cout_b, out, H * W, v->oc, total);
-        if (int rc = check_launch("conv_out tail")) return rc;
-    }
+    if (int rc = group_norm(c, x, t, c->norm_out, B, H * W, C, true, s)) return rc;
+    if (int rc = snapshot(c, "norm_out", t, B, H, W, C, s)) return rc;
+    return conv3x3(c, t, -1, c->conv_out, B, H, W, 0, EPI_F32, c->out_f32, s);
+}
+
+// ---- test / measurement hooks of a core (the ABI entries check their own handle) -------------------------------------------
+
+int core_set_debug(VaeCore* c, int32_t enable) {
+    DeviceGuard guard(c->device_id);
+    c->debug = enable != 0;
+    if (!c->debug) clear_stages(c);
     return TLD_OK;
 }
 
-int tld_vae_set_debug(tld_vae* v, int32_t enable) {
-    if (!v) return fail(TLD_ERR_INVALID, "null vae");
-    DeviceGuard guard(v->cfg.device_id);
-    v->debug = enable != 0;
-    if (!v->debug) clear_stages(v);
-    return TLD_OK;
-}
-
-int tld_vae_read_stage(tld_vae* v, const char* name, float* host_out, int64_t numel, int64_t* shape4) {
-    if (!v || !name || !host_out) return fail(TLD_ERR_INVALID, "null argument");
-    DeviceGuard guard(v->cfg.device_id);
-    for (const Stage& st : v->stages) {
+int core_read_stage(VaeCore* c, const char* name, float* host_out, int64_t numel, int64_t* shape4) {
+    if (!name || !host_out) return fail(TLD_ERR_INVALID, "null argument");
+    DeviceGuard guard(c->device_id);
+    for (const Stage& st : c->stages) {
         if (st.name != name) continue;
         const size_t n = (size_t)st.B * st.C * st.H * st.W;
         if (shape4) { shape4[0] = st.B; shape4[1] = st.C; shape4[2] = st.H; shape4[3] = st.W; }
@@ -830,75 +760,243 @@ int tld_vae_read_stage(tld_vae* v, const char* name, float* host_out, int64_t nu
         const size_t HW = (size_t)st.H * st.W;
         for (int b = 0; b < st.B; ++b)
             for (size_t p = 0; p < HW; ++p)
-                for (int c = 0; c < st.C; ++c)
-                    host_out[((size_t)b * st.C + c) * HW + p] = bf16_to_f32(tmp[((size_t)b * HW + p) * st.C + c]);
+                for (int ch = 0; ch < st.C; ++ch)
+                    host_out[((size_t)b * st.C + ch) * HW + p] = bf16_to_f32(tmp[((size_t)b * HW + p) * st.C + ch]);
         return TLD_OK;
     }
     return fail(TLD_ERR_KEY, "no captured stage named '%s' (set_debug before decode?)", name);
 }
 
-int tld_vae_set_profile(tld_vae* v, int32_t enable) {
-    if (!v) return fail(TLD_ERR_INVALID, "null vae");
-    v->profile = enable != 0;
-    for (int k = 0; k < VC_COUNT; ++k) v->ev_used[k] = 0;
+int core_set_profile(VaeCore* c, int32_t enable) {
+    c->profile = enable != 0;
+    for (int k = 0; k < VC_COUNT; ++k) c->ev_used[k] = 0;
     return TLD_OK;
 }
 
-int tld_vae_get_profile(tld_vae* v, int32_t kclass, double* total_ms, int64_t* launches) {
-    if (!v || kclass < 0 || kclass >= VC_COUNT || !total_ms || !launches) return fail(TLD_ERR_INVALID, "bad argument");
-    DeviceGuard guard(v->cfg.device_id);
+int core_get_profile(VaeCore* c, int32_t kclass, double* total_ms, int64_t* launches) {
+    if (kclass < 0 || kclass >= VC_COUNT || !total_ms || !launches) return fail(TLD_ERR_INVALID, "bad argument");
+    DeviceGuard guard(c->device_id);
     HIP_TRY(hipDeviceSynchronize());
     double tot = 0.0;
-    for (size_t i = 0; i < v->ev_used[kclass]; ++i) {
+    for (size_t i = 0; i < c->ev_used[kclass]; ++i) {
         float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, v->ev[kclass][i].first, v->ev[kclass][i].second));
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev[kclass][i].first, c->ev[kclass][i].second));
         tot += ms;
     }
     *total_ms = tot;
-    *launches = (int64_t)v->ev_used[kclass];
+    *launches = (int64_t)c->ev_used[kclass];
     return TLD_OK;
 }
 
-int64_t tld_vae_weight_bytes(const tld_vae* v) { return v ? v->weight_bytes : 0; }
+// The implicit-GEMM 3x3 convolution alone, behind both debug hooks.  H x W is the OUTPUT size; the source is [B, H >> up, W >> up, cin]
+// (up = 1: nearest-2x folded in) or [B, 2H, 2W, cin] (down = 1: stride 2, pad (0, 1, 0, 1)).  Works on a scratch copy with the zero page.
+int debug_conv(const void* in_bf16, const void* w_bf16, float* out_f32, int B, int H, int W, int cin, int cout, int up, int down,
+               void* hip_stream, const char* what) {
+    if (!in_bf16 || !w_bf16 || !out_f32) return fail(TLD_ERR_INVALID, "null argument");
+    if (cin % 64 || cin < 64) return fail(TLD_ERR_INVALID, "cin=%d must be a multiple of 64", cin);
+    PtrDeviceGuard guard(in_bf16);
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    const size_t n = (size_t)B * (down ? 2 * H : H >> up) * (down ? 2 * W : W >> up) * cin * 2;
+    if (n + kHdr >= (1ull << 32)) return fail(TLD_ERR_INVALID, "operands must be smaller than 4 GiB");
+    char* buf = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf), n + kHdr));
+    int rc = TLD_OK;
+    if (hipMemsetAsync(buf, 0, kHdr, s) != hipSuccess || hipMemcpyAsync(buf + kHdr, in_bf16, n, hipMemcpyDeviceToDevice, s) != hipSuccess)
+        rc = fail(TLD_ERR_HIP, "%s: copying the input failed", what);
+    if (!rc) {
+        GemmParams p{};
+        p.A = reinterpret_cast<const bf16*>(buf);
+        p.conv = 1; p.cv_h = H; p.cv_w = W; p.cv_up = up; p.cv_down = down; p.cv_cin = cin; p.cv_data_off = kHdr; p.lda = cin;
+        p.W = reinterpret_cast<const bf16*>(w_bf16); p.ldw = 9 * cin;
+        p.M = B * H * W; p.N = cout; p.K = 9 * cin;
+        p.c_f32 = out_f32; p.ldc = cout;
+        rc = launch_gemm(p, EPI_F32, s);               // a refused plan: nothing launched, out_f32 untouched, tld_last_error says why
+        const hipError_t e = hipGetLastError();
+        if (!rc && e != hipSuccess) rc = fail(TLD_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
+    }
+    const hipError_t sync = hipStreamSynchronize(s);   // (buf is read until here, whatever the status)
+    (void)hipFree(buf);
+    if (!rc && sync != hipSuccess) rc = fail(TLD_ERR_HIP, "%s failed: %s", what, hipGetErrorString(sync));
+    return rc;
+}
+
+}  // namespace
+
+struct tld_vae {
+    tld_vae_config cfg{};
+    VaeCore core;
+    // decoder only
+    int zc = 4, oc = 3;
+    float *pq_w = nullptr, *pq_b = nullptr;      // post_quant_conv [zc][zc], [zc] (null: use_post_quant_conv = 0)
+    float *cin_wt = nullptr, *cin_b = nullptr;   // conv_in fp32 [9 zc][C0], [C0]
+    std::vector<UpBlock> ups;
+    float* io_z = nullptr;                       // fp32 copy of a bf16 / fp16 latent
+};
+
+namespace {
+
+size_t max_act_elems(const tld_vae_config& cfg) {           // per sample, over all stages of the decoder
+    size_t mx = 0;
+    const int nb = cfg.n_blocks;
+    int H = cfg.latent_size;
+    int c = cfg.block_out_channels[nb - 1];
+    mx = std::max(mx, (size_t)H * H * c * 3);               // attention q|k|v
+    for (int i = 0; i < nb; ++i) {
+        const int cout = cfg.block_out_channels[nb - 1 - i];
+        mx = std::max(mx, (size_t)H * H * std::max(c, cout));
+        c = cout;
+        if (i != nb - 1) { H *= 2; mx = std::max(mx, (size_t)H * H * c); }
+    }
+    return mx;
+}
+
+const char* const kDecoderKeys[2] = {"decoder.", "post_quant_conv."};
+const char* const kEncoderKeys[2] = {"encoder.", "quant_conv."};
+
+}  // namespace
+
+// ---- C ABI -------------------------------------------------------------------------------------------------------------
+
+extern "C" {
+
+int tld_vae_create(const tld_vae_config* cfg, tld_vae** out) {
+    if (!cfg || !out) return fail(TLD_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (int rc = check_common_config(cfg)) return rc;
+    if (cfg->out_channels < 1 || cfg->out_channels > 8) return fail(TLD_ERR_INVALID, "out_channels=%d: 1..8 supported", cfg->out_channels);
+    if (cfg->latent_size < 4 || cfg->latent_size > 256) return fail(TLD_ERR_INVALID, "latent_size=%d: 4..256 supported", cfg->latent_size);
+    if (cfg->mid_block_attention && cfg->latent_size % 8)
+        return fail(TLD_ERR_INVALID, "latent_size=%d: the mid-block attention needs a multiple of 8 (h*w tokens in 64-wide K-steps)", cfg->latent_size);
+    if (int rc = check_device(cfg->device_id, "decoder")) return rc;
+    DeviceGuard guard(cfg->device_id);
+
+    tld_vae* v = new tld_vae();
+    v->cfg = *cfg;
+    v->zc = cfg->latent_channels; v->oc = cfg->out_channels;
+    const int hl = cfg->latent_size, Hout = hl << (cfg->n_blocks - 1);
+    int rc = core_create(&v->core, *cfg, hl, max_act_elems(*cfg), Hout, (size_t)Hout * Hout * v->oc, "decode");
+    if (!rc) rc = dev_alloc(&v->core, &v->io_z, (size_t)cfg->max_batch * v->zc * hl * hl);
+    if (rc) { tld_vae_destroy(v); return rc; }
+    *out = v;
+    return TLD_OK;
+}
+
+int tld_vae_load_tensor(tld_vae* v, const char* key, const void* host_ptr, const int64_t* shape, int32_t ndim, int32_t dtype) {
+    if (!v) return fail(TLD_ERR_INVALID, "bad argument");
+    return core_load_tensor(&v->core, key, host_ptr, shape, ndim, dtype, kDecoderKeys, kEncoderKeys);      // the encoder half is not used by decode
+}
+
+int tld_vae_finalize_weights(tld_vae* v) {
+    if (!v) return fail(TLD_ERR_INVALID, "null vae");
+    VaeCore* c = &v->core;
+    if (c->finalized) return fail(TLD_ERR_STATE, "weights already finalized");
+    DeviceGuard guard(c->device_id);
+    const int zc = v->zc, nb = v->cfg.n_blocks;
+    const HostTensor* t = nullptr;
+    if (v->cfg.use_post_quant_conv) {
+        if (int rc = need(c, "post_quant_conv.weight", {zc, zc, 1, 1}, &t)) return rc;
+        if (int rc = upload_f32(c, t->data, &v->pq_w)) return rc;
+        if (int rc = need(c, "post_quant_conv.bias", {zc}, &t)) return rc;
+        if (int rc = upload_f32(c, t->data, &v->pq_b)) return rc;
+    }
+    if (int rc = pack_conv_in(c, "decoder", zc, c->C0, &v->cin_wt, &v->cin_b)) return rc;
+    if (int rc = pack_mid(c, "decoder")) return rc;
+    v->ups.resize(nb);
+    int ch = c->C0;
+    for (int i = 0; i < nb; ++i) {
+        UpBlock& ub = v->ups[i];
+        ub.cout = v->cfg.block_out_channels[nb - 1 - i];
+        ub.res.resize(v->cfg.layers_per_block + 1);
+        for (int j = 0; j <= v->cfg.layers_per_block; ++j) {
+            const std::string pre = "decoder.up_blocks." + std::to_string(i) + ".resnets." + std::to_string(j);
+            if (int rc = pack_resnet(c, pre, j == 0 ? ch : ub.cout, ub.cout, &ub.res[j])) return rc;
+        }
+        ch = ub.cout;
+        ub.has_up = i != nb - 1;
+        if (ub.has_up)
+            if (int rc = pack_conv(c, "decoder.up_blocks." + std::to_string(i) + ".upsamplers.0.conv", ch, ch, 3, &ub.up)) return rc;
+    }
+    if (int rc = pack_out(c, "decoder", ch, v->oc)) return rc;
+    return core_finish_weights(c);
+}
+
+int tld_vae_decode(tld_vae* v, const void* z, float* out, int32_t batch, int32_t io_dtype, void* hip_stream) {
+    if (!v) return fail(TLD_ERR_INVALID, "null argument");
+    VaeCore* c = &v->core;
+    DeviceGuard guard(c->device_id);
+    if (int rc = core_begin_call(c, z, out, batch, io_dtype)) return rc;
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    const int B = batch;
+
+    int H = c->hl, W = c->hl;
+    const float* zf = reinterpret_cast<const float*>(z);
+    {
+        Timer t(c, VC_OTHER, s);
+        if (io_dtype != TLD_DTYPE_F32) {
+            const long n = (long)B * v->zc * H * W;
+            hipLaunchKernelGGL(vae_cast_in_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, z, io_dtype, v->io_z, n);
+            zf = v->io_z;
+        }
+        const int threads = ((std::max(c->C0, 9 * v->zc) + 63) / 64) * 64;
+        hipLaunchKernelGGL(vae_conv_in_kernel, dim3(B * H * W), dim3(threads), 0, s, zf, v->zc, H, W, v->pq_w, v->pq_b, v->cin_wt, v->cin_b, c->data(0), c->C0);
+        if (int rc = check_launch("conv_in")) return rc;
+    }
+    int x = 0;
+    int C = c->C0;
+    if (int rc = snapshot(c, "conv_in", x, B, H, W, C, s)) return rc;
+    if (int rc = mid_block(c, &x, B, H, W, s)) return rc;
+    for (size_t i = 0; i < v->ups.size(); ++i) {
+        const UpBlock& ub = v->ups[i];
+        for (size_t j = 0; j < ub.res.size(); ++j) {
+            if (int rc = resnet(c, ub.res[j], &x, B, H, W, s)) return rc;
+            C = ub.cout;
+            const std::string nm = "up" + std::to_string(i) + ".res" + std::to_string(j);
+            if (int rc = snapshot(c, nm.c_str(), x, B, H, W, C, s)) return rc;
+        }
+        if (ub.has_up) {                      // Upsample2D: nearest 2x, then conv 3x3 -- one implicit GEMM over the small image
+            const int dst = (x + 1) & 3;
+            H *= 2; W *= 2;
+            if (int rc = conv3x3(c, x, dst, ub.up, B, H, W, 1, EPI_BIAS_BF16, nullptr, s)) return rc;
+            x = dst;
+            const std::string nm = "up" + std::to_string(i) + ".upsample";
+            if (int rc = snapshot(c, nm.c_str(), x, B, H, W, C, s)) return rc;
+        }
+    }
+    if (int rc = norm_conv_out(c, x, B, H, W, C, s)) return rc;
+    {
+        Timer tm(c, VC_OTHER, s);
+        const long total = (long)B * H * W;
+        hipLaunchKernelGGL(vae_out_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, c->out_f32, c->conv_out.b, out, H * W, v->oc, total);
+        if (int rc = check_launch("conv_out tail")) return rc;
+    }
+    return TLD_OK;
+}
+
+int tld_vae_set_debug(tld_vae* v, int32_t enable) { return v ? core_set_debug(&v->core, enable) : fail(TLD_ERR_INVALID, "null vae"); }
+int tld_vae_read_stage(tld_vae* v, const char* name, float* host_out, int64_t numel, int64_t* shape4) {
+    return v ? core_read_stage(&v->core, name, host_out, numel, shape4) : fail(TLD_ERR_INVALID, "null argument");
+}
+int tld_vae_set_profile(tld_vae* v, int32_t enable) { return v ? core_set_profile(&v->core, enable) : fail(TLD_ERR_INVALID, "null vae"); }
+int tld_vae_get_profile(tld_vae* v, int32_t kclass, double* total_ms, int64_t* launches) {
+    return v ? core_get_profile(&v->core, kclass, total_ms, launches) : fail(TLD_ERR_INVALID, "bad argument");
+}
+
+int64_t tld_vae_weight_bytes(const tld_vae* v) { return v ? v->core.weight_bytes : 0; }
 
 int tld_vae_destroy(tld_vae* v) {
     if (!v) return TLD_OK;
-    DeviceGuard guard(v->cfg.device_id);
-    clear_stages(v);
-    for (int k = 0; k < VC_COUNT; ++k)
-        for (auto& e : v->ev[k]) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-    for (void* p : v->allocs) (void)hipFree(p);
+    DeviceGuard guard(v->core.device_id);
+    core_release(&v->core);
     delete v;
     return TLD_OK;
 }
 
 // Test hook: the implicit-GEMM 3x3 convolution alone.  in: bf16 channels-last [B, H >> up, W >> up, cin] (device);
-// w: bf16 [cout][3][3][cin] (device); out: fp32 [B*H*W][cout] (device).  Allocates a scratch copy with the zero page.
+// w: bf16 [cout][3][3][cin] (device); out: fp32 [B*H*W][cout] (device).
 int tld_debug_conv3x3(const void* in_bf16, const void* w_bf16, float* out_f32, int32_t B, int32_t H, int32_t W, int32_t cin,
                       int32_t cout, int32_t up, void* hip_stream) {
-    if (!in_bf16 || !w_bf16 || !out_f32) return fail(TLD_ERR_INVALID, "null argument");
-    if (cin % 64 || cin < 64) return fail(TLD_ERR_INVALID, "cin=%d must be a multiple of 64", cin);
     if (up != 0 && up != 1) return fail(TLD_ERR_INVALID, "up must be 0 or 1");
-    PtrDeviceGuard guard(in_bf16);
-    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-    const size_t n = (size_t)B * (H >> up) * (W >> up) * cin * 2;
-    if (n + kHdr >= (1ull << 32)) return fail(TLD_ERR_INVALID, "operands must be smaller than 4 GiB");
-    char* buf = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf), n + kHdr));
-    HIP_TRY(hipMemsetAsync(buf, 0, kHdr, s));
-    HIP_TRY(hipMemcpyAsync(buf + kHdr, in_bf16, n, hipMemcpyDeviceToDevice, s));
-    GemmParams p{};
-    p.A = reinterpret_cast<const bf16*>(buf);
-    p.conv = 1; p.cv_h = H; p.cv_w = W; p.cv_up = up; p.cv_cin = cin; p.cv_data_off = kHdr; p.lda = cin;
-    p.W = reinterpret_cast<const bf16*>(w_bf16); p.ldw = 9 * cin;
-    p.M = B * H * W; p.N = cout; p.K = 9 * cin;
-    p.c_f32 = out_f32; p.ldc = cout;
-    launch_gemm(p, EPI_F32, s);
-    const hipError_t e = hipGetLastError();
-    HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipFree(buf));
-    if (e != hipSuccess) return fail(TLD_ERR_HIP, "conv3x3 launch failed: %s", hipGetErrorString(e));
-    return TLD_OK;
+    return debug_conv(in_bf16, w_bf16, out_f32, B, H, W, cin, cout, up, 0, hip_stream, "conv3x3");
 }
 
 }  // extern "C"
@@ -910,8 +1008,8 @@ int tld_debug_conv3x3(const void* in_bf16, const void* w_bf16, float* out_f32, i
 //   conv_in 3x3 (3 -> C0) -> down blocks (layers_per_block resnets, stride-2 3x3 conv with padding (0, 1, 0, 1) except in the
 //   last) -> mid block (resnet, single-head attention, resnet) -> GroupNorm, SiLU, conv_out 3x3 (-> 2 zc) -> quant_conv 1x1.
 // Output: the fp32 moments [B, 2 zc, S / 2^(n-1), S / 2^(n-1)] (mean | logvar); the Gaussian is sampled on the Python side.
-// Everything between conv_in and conv_out is the decoder's machinery (resnet / attention / group_norm / conv3x3 on a tld_vae
-// workspace); the downsampler is the implicit-GEMM convolution with its stride-2 addressing (GemmParams::cv_down).
+// Everything between conv_in and the tail kernel is the shared machinery above (resnet / attention / group_norm / conv3x3 on the
+// encoder's own VaeCore); the downsampler is the implicit-GEMM convolution with its stride-2 addressing (GemmParams::cv_down).
 
 namespace {
 
@@ -985,38 +1083,27 @@ struct DownBlock { std::vector<Resnet> res; bool has_down = false; ConvW down; i
 
 struct tld_vae_enc {
     tld_vae_enc_config cfg{};
-    // workspace, GroupNorm / attention scratch, mid-block and output weights, stage snapshots and profile events: a decoder object
-    // used as the engine state that resnet() / attention() / group_norm() / conv3x3() work on (its decoder-only fields stay unused)
-    tld_vae core;
+    VaeCore core;
+    // encoder only
     int S = 0, cin = 3, oc = 8;                  // image size, input channels, moments channels (2 zc)
-    float *cin_wt = nullptr, *cin_b = nullptr;   // conv_in fp32 [9 cin][C0], [C0]
+    float *cin_wt = nullptr, *cin_b = nullptr;   // conv_in fp32 [9 cin][c0], [c0]
     std::vector<DownBlock> downs;
     float *qc_w = nullptr, *qc_b = nullptr;      // quant_conv [oc][oc], [oc] (null: use_quant_conv = 0)
 };
 
 namespace {
 
-size_t enc_max_act_elems(const tld_vae_enc* e) {            // per sample, over all stages of the encoder
-    const tld_vae& v = e->core;
-    size_t H = (size_t)e->S, mx = H * H * v.boc[0];
-    int c = v.boc[0];
-    for (int i = 0; i < v.nb; ++i) {
-        const int cout = v.boc[i];
+size_t enc_max_act_elems(const tld_vae_enc_config& cfg) {   // per sample, over all stages of the encoder
+    size_t H = (size_t)cfg.image_size, mx = H * H * cfg.block_out_channels[0];
+    int c = cfg.block_out_channels[0];
+    for (int i = 0; i < cfg.n_blocks; ++i) {
+        const int cout = cfg.block_out_channels[i];
         mx = std::max(mx, H * H * std::max(c, cout));
         c = cout;
-        if (i != v.nb - 1) H /= 2;                            // (the downsampled image is smaller than its source)
+        if (i != cfg.n_blocks - 1) H /= 2;                    // (the downsampled image is smaller than its source)
     }
     mx = std::max(mx, H * H * c * 3);                        // attention q|k|v
     return mx;
-}
-
-void enc_release(tld_vae_enc* e) {
-    tld_vae* v = &e->core;
-    clear_stages(v);
-    for (int k = 0; k < VC_COUNT; ++k)
-        for (auto& ev : v->ev[k]) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
-    for (void* p : v->allocs) (void)hipFree(p);
-    v->allocs.clear();
 }
 
 }  // namespace
@@ -1027,249 +1114,131 @@ int tld_vae_enc_create(const tld_vae_enc_config* cfg, tld_vae_enc** out) {
     if (!cfg || !out) return fail(TLD_ERR_INVALID, "null argument");
     *out = nullptr;
     if (cfg->in_channels < 1 || cfg->in_channels > 4) return fail(TLD_ERR_INVALID, "in_channels=%d: 1..4 supported", cfg->in_channels);
-    if (cfg->n_blocks < 1 || cfg->n_blocks > 4) return fail(TLD_ERR_INVALID, "n_blocks=%d: 1..4 supported", cfg->n_blocks);
-    for (int i = 0; i < cfg->n_blocks; ++i)
-        if (!chan_ok(cfg->block_out_channels[i]))
-            return fail(TLD_ERR_INVALID, "block_out_channels[%d]=%d: must be one of 64, 128, 256, 512, 1024", i, cfg->block_out_channels[i]);
-    if (cfg->latent_channels < 1 || cfg->latent_channels > 16) return fail(TLD_ERR_INVALID, "latent_channels=%d: 1..16 supported", cfg->latent_channels);
-    if (cfg->norm_num_groups < 1 || cfg->norm_num_groups > 64) return fail(TLD_ERR_INVALID, "norm_num_groups=%d: 1..64 supported", cfg->norm_num_groups);
-    for (int i = 0; i < cfg->n_blocks; ++i)
-        if (cfg->block_out_channels[i] % cfg->norm_num_groups)
-            return fail(TLD_ERR_INVALID, "block_out_channels[%d]=%d is not a multiple of norm_num_groups=%d", i, cfg->block_out_channels[i], cfg->norm_num_groups);
-    if (cfg->layers_per_block < 1 || cfg->layers_per_block > 8) return fail(TLD_ERR_INVALID, "layers_per_block=%d: 1..8 supported", cfg->layers_per_block);
+    if (int rc = check_common_config(cfg)) return rc;
     const int down = 1 << (cfg->n_blocks - 1);
     if (cfg->image_size < 64 || cfg->image_size > 2048 || cfg->image_size % 64 || cfg->image_size % (8 * down))
         return fail(TLD_ERR_INVALID, "image_size=%d: a multiple of 64 and of 8 * 2^(n_blocks-1) = %d in 64..2048 (the mid-block attention needs "
                     "a multiple of 8 per side)", cfg->image_size, 8 * down);
-    if (cfg->max_batch < 1) return fail(TLD_ERR_INVALID, "max_batch must be positive");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(TLD_ERR_HIP, "no HIP device available (the VAE encoder has no CPU path)");
-    if (cfg->device_id < 0 || cfg->device_id >= ndev) return fail(TLD_ERR_INVALID, "device_id=%d out of range (%d devices)", cfg->device_id, ndev);
+    if (int rc = check_device(cfg->device_id, "encoder")) return rc;
     DeviceGuard guard(cfg->device_id);
 
     tld_vae_enc* e = new tld_vae_enc();
     e->cfg = *cfg;
     e->S = cfg->image_size; e->cin = cfg->in_channels; e->oc = 2 * cfg->latent_channels;
-    tld_vae* v = &e->core;
-    v->cfg.device_id = cfg->device_id; v->cfg.max_batch = cfg->max_batch; v->cfg.mid_block_attention = cfg->mid_block_attention;
-    v->G = cfg->norm_num_groups; v->zc = cfg->latent_channels; v->oc = e->oc; v->nb = cfg->n_blocks; v->hl = e->S / down;
-    v->boc.assign(cfg->block_out_channels, cfg->block_out_channels + cfg->n_blocks);
-    v->C0 = v->boc[v->nb - 1];                               // (the mid block's width, as in the decoder)
-    v->fuse_stats = fuse_stats_enabled();
-    const size_t per = enc_max_act_elems(e);
-    v->buf_elems = per * (size_t)cfg->max_batch;
-    const size_t bytes = v->buf_elems * 2 + kHdr;
-    if (bytes >= (1ull << 32)) {
-        delete e;
-        return fail(TLD_ERR_INVALID, "max_batch=%d: an activation buffer (%zu bytes per sample) must stay below 4 GiB (32-bit DMA offsets); "
-                    "encode in chunks of at most %zu", cfg->max_batch, per * 2, (size_t)(((1ull << 32) - kHdr - 1) / (per * 2)));
+    const int hl = e->S / down;
+    if (int rc = core_create(&e->core, *cfg, hl, enc_max_act_elems(*cfg), e->S, (size_t)hl * hl * e->oc, "encode")) {
+        tld_vae_enc_destroy(e);
+        return rc;
     }
-    auto bail = [&](int rc) { tld_vae_enc_destroy(e); return rc; };
-    for (int i = 0; i < 4; ++i) {
-        if (int rc = dev_alloc(v, &v->buf[i], bytes)) return bail(rc);
-        if (hipMemset(v->buf[i], 0, kHdr) != hipSuccess) return bail(fail(TLD_ERR_HIP, "hipMemset failed"));
-    }
-    v->gn_max_chunks = (e->S * e->S + 255) / 256;
-    if (int rc = dev_alloc(v, &v->gn_partial, (size_t)cfg->max_batch * v->gn_max_chunks * v->G)) return bail(rc);
-    if (int rc = dev_alloc(v, &v->gn_stats, (size_t)cfg->max_batch * v->G)) return bail(rc);
-    if (cfg->mid_block_attention) {
-        const size_t hw = (size_t)v->hl * v->hl;
-        const size_t fit = ((size_t)256 << 20) / (hw * hw * 4);             // samples whose fp32 scores fit in 256 MB
-        v->att_nb = (int)std::max<size_t>(1, std::min<size_t>(fit, (size_t)cfg->max_batch));
-        if (int rc = dev_alloc(v, &v->scores, (size_t)v->att_nb * hw * hw)) return bail(rc);
-        if (int rc = dev_alloc(v, &v->probs, (size_t)v->att_nb * hw * hw)) return bail(rc);
-        if (int rc = dev_alloc(v, &v->vt, (size_t)v->att_nb * hw * v->C0)) return bail(rc);
-    }
-    if (int rc = dev_alloc(v, &v->out_f32, (size_t)cfg->max_batch * v->hl * v->hl * e->oc)) return bail(rc);
     *out = e;
     return TLD_OK;
 }
 
 int tld_vae_enc_load_tensor(tld_vae_enc* e, const char* key, const void* host_ptr, const int64_t* shape, int32_t ndim, int32_t dtype) {
-    if (!e || !key || (!host_ptr && ndim > 0) || ndim < 0 || ndim > 8) return fail(TLD_ERR_INVALID, "bad argument");
-    tld_vae* v = &e->core;
-    if (v->finalized) return fail(TLD_ERR_STATE, "weights already finalized");
-    std::string k(key);
-    if (k.rfind("decoder.", 0) == 0 || k.rfind("post_quant_conv.", 0) == 0) return TLD_OK;      // the decoder half is not used by encode
-    if (k.rfind("encoder.", 0) != 0 && k.rfind("quant_conv.", 0) != 0) return fail(TLD_ERR_KEY, "unknown state_dict key '%s'", key);
-    if (dtype != TLD_DTYPE_F32) return fail(TLD_ERR_INVALID, "'%s': host tensors must be fp32", key);
-    static const char* const ren[][2] = {{".query.", ".to_q."}, {".key.", ".to_k."}, {".value.", ".to_v."}, {".proj_attn.", ".to_out.0."}};
-    for (auto& r : ren) {
-        const size_t pos = k.find(r[0]);
-        if (pos != std::string::npos && k.find(".attentions.") != std::string::npos) k.replace(pos, strlen(r[0]), r[1]);
-    }
-    HostTensor t;
-    int64_t n = 1;
-    for (int i = 0; i < ndim; ++i) { if (shape[i] < 0) return fail(TLD_ERR_SHAPE, "'%s': negative dimension", key); t.shape.push_back(shape[i]); n *= shape[i]; }
-    t.data.assign(reinterpret_cast<const float*>(host_ptr), reinterpret_cast<const float*>(host_ptr) + n);
-    v->host[k] = std::move(t);
-    return TLD_OK;
+    if (!e) return fail(TLD_ERR_INVALID, "bad argument");
+    return core_load_tensor(&e->core, key, host_ptr, shape, ndim, dtype, kEncoderKeys, kDecoderKeys);      // the decoder half is not used by encode
 }
 
 int tld_vae_enc_finalize_weights(tld_vae_enc* e) {
     if (!e) return fail(TLD_ERR_INVALID, "null encoder");
-    tld_vae* v = &e->core;
-    if (v->finalized) return fail(TLD_ERR_STATE, "weights already finalized");
-    DeviceGuard guard(e->cfg.device_id);
-    const int c0 = v->boc[0], C = v->C0, cin = e->cin, oc = e->oc;
+    VaeCore* c = &e->core;
+    if (c->finalized) return fail(TLD_ERR_STATE, "weights already finalized");
+    DeviceGuard guard(c->device_id);
+    const int nb = e->cfg.n_blocks, oc = e->oc;
     const HostTensor* t = nullptr;
-    {   // conv_in: [c0][cin][3][3] -> fp32 [tap][cin][c0]
-        if (int rc = need(v, "encoder.conv_in.weight", {c0, cin, 3, 3}, &t)) return rc;
-        std::vector<float> wt((size_t)9 * cin * c0);
-        for (int o = 0; o < c0; ++o)
-            for (int c = 0; c < cin; ++c)
-                for (int tap = 0; tap < 9; ++tap) wt[((size_t)tap * cin + c) * c0 + o] = t->data[((size_t)o * cin + c) * 9 + tap];
-        if (int rc = upload_f32(v, wt, &e->cin_wt)) return rc;
-        if (int rc = need(v, "encoder.conv_in.bias", {c0}, &t)) return rc;
-        if (int rc = upload_f32(v, t->data, &e->cin_b)) return rc;
-    }
-    e->downs.resize(v->nb);
-    int c = c0;
-    for (int i = 0; i < v->nb; ++i) {
+    int ch = e->cfg.block_out_channels[0];
+    if (int rc = pack_conv_in(c, "encoder", e->cin, ch, &e->cin_wt, &e->cin_b)) return rc;
+    e->downs.resize(nb);
+    for (int i = 0; i < nb; ++i) {
         DownBlock& db = e->downs[i];
-        db.cout = v->boc[i];
+        db.cout = e->cfg.block_out_channels[i];
         db.res.resize(e->cfg.layers_per_block);
         const std::string pre = "encoder.down_blocks." + std::to_string(i);
         for (int j = 0; j < e->cfg.layers_per_block; ++j)
-            if (int rc = pack_resnet(v, pre + ".resnets." + std::to_string(j), j == 0 ? c : db.cout, db.cout, &db.res[j])) return rc;
-        c = db.cout;
-        db.has_down = i != v->nb - 1;
+            if (int rc = pack_resnet(c, pre + ".resnets." + std::to_string(j), j == 0 ? ch : db.cout, db.cout, &db.res[j])) return rc;
+        ch = db.cout;
+        db.has_down = i != nb - 1;
         if (db.has_down)
-            if (int rc = pack_conv(v, pre + ".downsamplers.0.conv", c, c, 3, &db.down)) return rc;
+            if (int rc = pack_conv(c, pre + ".downsamplers.0.conv", ch, ch, 3, &db.down)) return rc;
     }
-    if (int rc = pack_resnet(v, "encoder.mid_block.resnets.0", C, C, &v->mid0)) return rc;
-    if (int rc = pack_resnet(v, "encoder.mid_block.resnets.1", C, C, &v->mid1)) return rc;
-    if (e->cfg.mid_block_attention) {
-        const std::string a = "encoder.mid_block.attentions.0";
-        if (int rc = pack_gn(v, a + ".group_norm", C, &v->attn_gn)) return rc;
-        std::vector<float> w((size_t)3 * C * C), b((size_t)3 * C);
-        const char* names[3] = {".to_q", ".to_k", ".to_v"};
-        for (int i = 0; i < 3; ++i) {
-            if (int rc = need(v, a + names[i] + ".weight", {C, C}, &t)) return rc;
-            memcpy(w.data() + (size_t)i * C * C, t->data.data(), (size_t)C * C * 4);
-            if (int rc = need(v, a + names[i] + ".bias", {C}, &t)) return rc;
-            memcpy(b.data() + (size_t)i * C, t->data.data(), (size_t)C * 4);
-        }
-        v->attn_qkv.cin = C; v->attn_qkv.cout = 3 * C; v->attn_qkv.k = 1;
-        if (int rc = upload_bf16(v, w, &v->attn_qkv.w)) return rc;
-        if (int rc = upload_f32(v, b, &v->attn_qkv.b)) return rc;
-        if (int rc = need(v, a + ".to_out.0.weight", {C, C}, &t)) return rc;
-        v->attn_out.cin = C; v->attn_out.cout = C; v->attn_out.k = 1;
-        if (int rc = upload_bf16(v, t->data, &v->attn_out.w)) return rc;
-        if (int rc = need(v, a + ".to_out.0.bias", {C}, &t)) return rc;
-        if (int rc = upload_f32(v, t->data, &v->attn_out.b)) return rc;
-    }
-    {
-        std::vector<float> z(1024, 0.f);
-        if (int rc = upload_f32(v, z, &v->zero_bias)) return rc;
-    }
-    if (int rc = pack_gn(v, "encoder.conv_norm_out", C, &v->norm_out)) return rc;
-    if (int rc = pack_conv(v, "encoder.conv_out", C, oc, 3, &v->conv_out)) return rc;      // bf16 [oc][9][C]; bias added by the tail kernel
+    if (int rc = pack_mid(c, "encoder")) return rc;
+    if (int rc = pack_out(c, "encoder", c->C0, oc)) return rc;
     if (e->cfg.use_quant_conv) {
-        if (int rc = need(v, "quant_conv.weight", {oc, oc, 1, 1}, &t)) return rc;
-        if (int rc = upload_f32(v, t->data, &e->qc_w)) return rc;
-        if (int rc = need(v, "quant_conv.bias", {oc}, &t)) return rc;
-        if (int rc = upload_f32(v, t->data, &e->qc_b)) return rc;
+        if (int rc = need(c, "quant_conv.weight", {oc, oc, 1, 1}, &t)) return rc;
+        if (int rc = upload_f32(c, t->data, &e->qc_w)) return rc;
+        if (int rc = need(c, "quant_conv.bias", {oc}, &t)) return rc;
+        if (int rc = upload_f32(c, t->data, &e->qc_b)) return rc;
     }
-    v->host.clear();
-    HIP_TRY(hipDeviceSynchronize());
-    v->finalized = true;
-    return TLD_OK;
+    return core_finish_weights(c);
 }
 
 int tld_vae_enc_encode(tld_vae_enc* e, const void* x, float* moments, int32_t batch, int32_t io_dtype, void* hip_stream) {
-    if (!e || !x || !moments) return fail(TLD_ERR_INVALID, "null argument");
-    tld_vae* v = &e->core;
-    if (!v->finalized) return fail(TLD_ERR_STATE, "weights not finalized");
-    if (batch < 1 || batch > e->cfg.max_batch) return fail(TLD_ERR_INVALID, "batch=%d outside 1..max_batch=%d", batch, e->cfg.max_batch);
-    if (io_dtype != TLD_DTYPE_F32 && io_dtype != TLD_DTYPE_BF16 && io_dtype != TLD_DTYPE_F16) return fail(TLD_ERR_INVALID, "io_dtype=%d", io_dtype);
-    DeviceGuard guard(e->cfg.device_id);
+    if (!e) return fail(TLD_ERR_INVALID, "null argument");
+    VaeCore* c = &e->core;
+    DeviceGuard guard(c->device_id);
+    if (int rc = core_begin_call(c, x, moments, batch, io_dtype)) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
     const int B = batch;
-    if (v->debug) clear_stages(v);
-    for (int k = 0; k < VC_COUNT; ++k) if (!v->profile) v->ev_used[k] = 0;
 
     int H = e->S, W = e->S;
-    int C = v->boc[0];
-    v->have_partial = false;
+    int C = e->cfg.block_out_channels[0];
     {
-        Timer t(v, VC_OTHER, s);
+        Timer t(c, VC_OTHER, s);
         const int ppb = 256;
         const long npix = (long)B * H * W;
         const size_t lds = ((size_t)9 * e->cin * C + C) * sizeof(float);          // <= 148 KiB (cin 4, C0 1024)
         if (lds > 65536)
             HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(vae_enc_conv_in_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(vae_enc_conv_in_kernel, dim3((unsigned)((npix + ppb - 1) / ppb)), dim3(256), lds, s, x, io_dtype, e->cin, e->S,
-                           e->cin_wt, e->cin_b, v->data(0), C, ppb, npix);
+                           e->cin_wt, e->cin_b, c->data(0), C, ppb, npix);
         if (int rc = check_launch("conv_in")) return rc;
     }
     int x0 = 0;
-    if (int rc = snapshot(v, "conv_in", x0, B, H, W, C, s)) return rc;
-    for (int i = 0; i < v->nb; ++i) {
+    if (int rc = snapshot(c, "conv_in", x0, B, H, W, C, s)) return rc;
+    for (size_t i = 0; i < e->downs.size(); ++i) {
         const DownBlock& db = e->downs[i];
         for (size_t j = 0; j < db.res.size(); ++j) {
-            if (int rc = resnet(v, db.res[j], &x0, B, H, W, s)) return rc;
+            if (int rc = resnet(c, db.res[j], &x0, B, H, W, s)) return rc;
             C = db.cout;
             const std::string nm = "down" + std::to_string(i) + ".res" + std::to_string(j);
-            if (int rc = snapshot(v, nm.c_str(), x0, B, H, W, C, s)) return rc;
+            if (int rc = snapshot(c, nm.c_str(), x0, B, H, W, C, s)) return rc;
         }
         if (db.has_down) {                    // Downsample2D: pad (0, 1, 0, 1), 3x3 conv with stride 2 -- one implicit GEMM over the small image
             const int dst = (x0 + 1) & 3;
             H /= 2; W /= 2;
-            if (int rc = conv3x3(v, x0, dst, db.down, B, H, W, 0, EPI_BIAS_BF16, nullptr, s, 1)) return rc;
+            if (int rc = conv3x3(c, x0, dst, db.down, B, H, W, 0, EPI_BIAS_BF16, nullptr, s, 1)) return rc;
             x0 = dst;
             const std::string nm = "down" + std::to_string(i) + ".downsample";
-            if (int rc = snapshot(v, nm.c_str(), x0, B, H, W, C, s)) return rc;
+            if (int rc = snapshot(c, nm.c_str(), x0, B, H, W, C, s)) return rc;
         }
     }
-    if (int rc = resnet(v, v->mid0, &x0, B, H, W, s)) return rc;
-    if (int rc = snapshot(v, "mid.res0", x0, B, H, W, C, s)) return rc;
-    if (e->cfg.mid_block_attention) {
-        if (int rc = attention(v, &x0, B, H, W, C, s)) return rc;
-        if (int rc = snapshot(v, "mid.attn", x0, B, H, W, C, s)) return rc;
-    }
-    if (int rc = resnet(v, v->mid1, &x0, B, H, W, s)) return rc;
-    if (int rc = snapshot(v, "mid.res1", x0, B, H, W, C, s)) return rc;
-    const int t = (x0 + 1) & 3;
-    if (int rc = group_norm(v, x0, t, v->norm_out, B, H * W, C, true, s)) return rc;
-    if (int rc = snapshot(v, "norm_out", t, B, H, W, C, s)) return rc;
-    if (int rc = conv3x3(v, t, -1, v->conv_out, B, H, W, 0, EPI_F32, v->out_f32, s)) return rc;
+    if (int rc = mid_block(c, &x0, B, H, W, s)) return rc;
+    if (int rc = norm_conv_out(c, x0, B, H, W, C, s)) return rc;
     {
-        Timer tm(v, VC_OTHER, s);
+        Timer tm(c, VC_OTHER, s);
         const long total = (long)B * H * W;
-        hipLaunchKernelGGL(vae_enc_out_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, v->out_f32, v->conv_out.b, e->qc_w, e->qc_b,
+        hipLaunchKernelGGL(vae_enc_out_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, c->out_f32, c->conv_out.b, e->qc_w, e->qc_b,
                            moments, H * W, e->oc, total);
         if (int rc = check_launch("conv_out / quant_conv tail")) return rc;
     }
     return TLD_OK;
 }
 
-int tld_vae_enc_set_debug(tld_vae_enc* e, int32_t enable) {
-    if (!e) return fail(TLD_ERR_INVALID, "null encoder");
-    return tld_vae_set_debug(&e->core, enable);
-}
-
+int tld_vae_enc_set_debug(tld_vae_enc* e, int32_t enable) { return e ? core_set_debug(&e->core, enable) : fail(TLD_ERR_INVALID, "null encoder"); }
 int tld_vae_enc_read_stage(tld_vae_enc* e, const char* name, float* host_out, int64_t numel, int64_t* shape4) {
-    if (!e) return fail(TLD_ERR_INVALID, "null encoder");
-    return tld_vae_read_stage(&e->core, name, host_out, numel, shape4);
+    return e ? core_read_stage(&e->core, name, host_out, numel, shape4) : fail(TLD_ERR_INVALID, "null encoder");
 }
-
-int tld_vae_enc_set_profile(tld_vae_enc* e, int32_t enable) {
-    if (!e) return fail(TLD_ERR_INVALID, "null encoder");
-    return tld_vae_set_profile(&e->core, enable);
-}
-
+int tld_vae_enc_set_profile(tld_vae_enc* e, int32_t enable) { return e ? core_set_profile(&e->core, enable) : fail(TLD_ERR_INVALID, "null encoder"); }
 int tld_vae_enc_get_profile(tld_vae_enc* e, int32_t kclass, double* total_ms, int64_t* launches) {
-    if (!e) return fail(TLD_ERR_INVALID, "null encoder");
-    return tld_vae_get_profile(&e->core, kclass, total_ms, launches);
+    return e ? core_get_profile(&e->core, kclass, total_ms, launches) : fail(TLD_ERR_INVALID, "null encoder");
 }
 
 int64_t tld_vae_enc_weight_bytes(const tld_vae_enc* e) { return e ? e->core.weight_bytes : 0; }
 
 int tld_vae_enc_destroy(tld_vae_enc* e) {
     if (!e) return TLD_OK;
-    DeviceGuard guard(e->cfg.device_id);
-    enc_release(e);
+    DeviceGuard guard(e->core.device_id);
+    core_release(&e->core);
     delete e;
     return TLD_OK;
 }
@@ -1278,29 +1247,8 @@ int tld_vae_enc_destroy(tld_vae_enc* e) {
 // in: bf16 channels-last [B, 2H, 2W, cin] (device); w: bf16 [cout][3][3][cin] (device); out: fp32 [B*H*W][cout] (device).
 int tld_debug_conv3x3_s2(const void* in_bf16, const void* w_bf16, float* out_f32, int32_t B, int32_t H, int32_t W, int32_t cin,
                          int32_t cout, void* hip_stream) {
-    if (!in_bf16 || !w_bf16 || !out_f32) return fail(TLD_ERR_INVALID, "null argument");
-    if (cin % 64 || cin < 64) return fail(TLD_ERR_INVALID, "cin=%d must be a multiple of 64", cin);
     if (B < 1 || H < 1 || W < 1 || cout < 1 || H > 8192 || W > 8192) return fail(TLD_ERR_INVALID, "bad shape");
-    PtrDeviceGuard guard(in_bf16);
-    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-    const size_t n = (size_t)B * (2 * H) * (2 * W) * cin * 2;
-    if (n + kHdr >= (1ull << 32)) return fail(TLD_ERR_INVALID, "operands must be smaller than 4 GiB");
-    char* buf = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf), n + kHdr));
-    HIP_TRY(hipMemsetAsync(buf, 0, kHdr, s));
-    HIP_TRY(hipMemcpyAsync(buf + kHdr, in_bf16, n, hipMemcpyDeviceToDevice, s));
-    GemmParams p{};
-    p.A = reinterpret_cast<const bf16*>(buf);
-    p.conv = 1; p.cv_h = H; p.cv_w = W; p.cv_down = 1; p.cv_cin = cin; p.cv_data_off = kHdr; p.lda = cin;
-    p.W = reinterpret_cast<const bf16*>(w_bf16); p.ldw = 9 * cin;
-    p.M = B * H * W; p.N = cout; p.K = 9 * cin;
-    p.c_f32 = out_f32; p.ldc = cout;
-    launch_gemm(p, EPI_F32, s);
-    const hipError_t e = hipGetLastError();
-    HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipFree(buf));
-    if (e != hipSuccess) return fail(TLD_ERR_HIP, "conv3x3_s2 launch failed: %s", hipGetErrorString(e));
-    return TLD_OK;
+    return debug_conv(in_bf16, w_bf16, out_f32, B, H, W, cin, cout, 0, 1, hip_stream, "conv3x3_s2");
 }
 
 }  // extern "C"
