@@ -230,33 +230,52 @@ class Denoiser:
                        sharp_f: float = 0.0, bright_f: float = 0.0, trace: bool = False):
         """On-device CFG sampler (tld_sample): x_T [B,C,S,S], labels [B,text] (conditional half only),
         coeffs = schedule.step_coefficients(...).  Returns fp32 latent [B,C,S,S] (+ traces)."""
-        dev = self._resolve_device(x_T)
-        B = x_T.shape[0]
+        co = np.ascontiguousarray(coeffs, dtype=np.float32)
+        return self._run_sampler(x_T, labels, co.shape[0], trace, lambda h, B, eps, z0, m, lab, neg, out, tx0, txt, stream: _lib.check(
+            _lib.lib().tld_sample(h, eps, lab, co.ctypes.data_as(C.POINTER(C.c_float)), co.shape[0], float(class_guidance), float(sharp_f),
+                                  float(bright_f), out, B, tx0, txt, stream), "tld_sample"))
+
+    def _run_sampler(self, noise, labels, n_levels: int, trace: bool, call, init_latents=None, mask=None, neg_labels=None, order=None,
+                     new_trace=torch.empty):
+        """What the three sampler entries share around their C call: the device, the ``init_latents`` / ``mask`` shape checks, the empty
+        batch, the engine for the CFG-doubled batch, the operands as contiguous fp32 on the device (rows gathered in ``order`` when the
+        engine wants its own), the result and -- with ``trace`` -- the [n_levels-1,B,C,S,S] trace tensors from ``new_trace``, then
+        ``call(engine, B, noise, init_latents, mask, labels, neg_labels, out, trace_x0, trace_xt, stream)`` -- pointers, NULL for an absent
+        operand -- under the device context on its current stream.  Results come back in the caller's order."""
+        dev = self._resolve_device(noise)
+        B = noise.shape[0]
+        if init_latents is not None and tuple(init_latents.shape) != tuple(noise.shape):
+            raise ValueError(f"init_latents {tuple(init_latents.shape)} != noise {tuple(noise.shape)}")
+        if mask is not None and tuple(mask.shape) != (B, 1) + tuple(noise.shape[2:]):
+            raise ValueError(f"mask {tuple(mask.shape)}: expected {(B, 1) + tuple(noise.shape[2:])}")
         if B == 0:
-            z = torch.empty_like(x_T, dtype=torch.float32)
+            z = torch.empty_like(noise, dtype=torch.float32)
             return (z, None, None) if trace else z
         h = self._ensure_engine(2 * B, dev)
-        xT = x_T.to(device=dev, dtype=torch.float32).contiguous()
-        lab = labels.to(device=dev, dtype=torch.float32).contiguous()
-        co = np.ascontiguousarray(coeffs, dtype=np.float32)
-        n_levels = co.shape[0]
-        return self._run_sampler(xT, n_levels, trace, lambda out, tx0, txt, stream: _lib.check(_lib.lib().tld_sample(
-            h, xT.data_ptr(), lab.data_ptr(), co.ctypes.data_as(C.POINTER(C.c_float)), n_levels,
-            float(class_guidance), float(sharp_f), float(bright_f), out, B, tx0, txt, stream), "tld_sample"))
+        idx = None if order is None else torch.tensor(order, device=dev)
 
-    @staticmethod
-    def _run_sampler(noise: torch.Tensor, n_levels: int, trace: bool, call):
-        """What sample_latents and sample_latents_from share after their arguments: the result and trace tensors shaped after ``noise``
-        (fp32, on the engine's device), then ``call(out, trace_x0, trace_xt, stream)`` -- pointers -- on that device's current stream."""
-        dev = noise.device
-        out = torch.empty_like(noise)
+        def operand(t):
+            if t is None:
+                return None
+            t = t.to(device=dev, dtype=torch.float32)
+            return (t if idx is None else t[idx]).contiguous()
+
+        eps, z0, m, lab, neg = operand(noise), operand(init_latents), operand(mask), operand(labels), operand(neg_labels)
+        out = torch.empty_like(eps)
         tx0 = txt = None
         if trace:
-            tx0 = torch.empty((n_levels - 1,) + tuple(noise.shape), device=dev, dtype=torch.float32)
-            txt = torch.empty_like(tx0)
+            tx0 = new_trace((n_levels - 1,) + tuple(eps.shape), device=dev, dtype=torch.float32)
+            txt = new_trace(tx0.shape, device=dev, dtype=torch.float32)
         ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
         with torch.cuda.device(dev):
-            call(ptr(out), ptr(tx0), ptr(txt), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            call(h, B, ptr(eps), ptr(z0), ptr(m), ptr(lab), ptr(neg), ptr(out), ptr(tx0), ptr(txt),
+                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        if idx is not None:
+            inv = torch.empty_like(idx)
+            inv[idx] = torch.arange(B, device=dev)
+            out = out[inv]
+            if trace:
+                tx0, txt = tx0[:, inv], txt[:, inv]
         return (out, tx0, txt) if trace else out
 
     @torch.no_grad()
@@ -267,26 +286,11 @@ class Denoiser:
         ``start_mix * noise + (1 - start_mix) * init_latents`` (``start_mix = 1.0``: at ``noise`` itself) and runs the levels of ``coeffs``
         (the remaining ones, ``schedule.truncate_levels``); with ``mask`` [B,1,S,S] in [0,1] (1 = regenerate) the kept region is re-imposed
         after every step and on the final prediction.  Returns fp32 latent [B,C,S,S] (+ traces)."""
-        dev = self._resolve_device(noise)
-        B = noise.shape[0]
-        if tuple(init_latents.shape) != tuple(noise.shape):
-            raise ValueError(f"init_latents {tuple(init_latents.shape)} != noise {tuple(noise.shape)}")
-        if mask is not None and tuple(mask.shape) != (B, 1) + tuple(noise.shape[2:]):
-            raise ValueError(f"mask {tuple(mask.shape)}: expected {(B, 1) + tuple(noise.shape[2:])}")
-        if B == 0:
-            z = torch.empty_like(noise, dtype=torch.float32)
-            return (z, None, None) if trace else z
-        h = self._ensure_engine(2 * B, dev)
-        eps = noise.to(device=dev, dtype=torch.float32).contiguous()
-        z0 = init_latents.to(device=dev, dtype=torch.float32).contiguous()
-        m = mask.to(device=dev, dtype=torch.float32).contiguous() if mask is not None else None
-        lab = labels.to(device=dev, dtype=torch.float32).contiguous()
         co = np.ascontiguousarray(coeffs, dtype=np.float32)
-        n_levels = co.shape[0]
-        return self._run_sampler(eps, n_levels, trace, lambda out, tx0, txt, stream: _lib.check(_lib.lib().tld_sample_from(
-            h, eps.data_ptr(), z0.data_ptr(), C.c_void_p(m.data_ptr() if m is not None else None), float(start_mix), lab.data_ptr(),
-            co.ctypes.data_as(C.POINTER(C.c_float)), n_levels, float(class_guidance), float(sharp_f), float(bright_f), out, B,
-            tx0, txt, stream), "tld_sample_from"))
+        return self._run_sampler(noise, labels, co.shape[0], trace, lambda h, B, eps, z0, m, lab, neg, out, tx0, txt, stream: _lib.check(
+            _lib.lib().tld_sample_from(h, eps, z0, m, float(start_mix), lab, co.ctypes.data_as(C.POINTER(C.c_float)), co.shape[0],
+                                       float(class_guidance), float(sharp_f), float(bright_f), out, B, tx0, txt, stream), "tld_sample_from"),
+            init_latents=init_latents, mask=mask)
 
     @torch.no_grad()
     def sample_latents_requests(self, noise: torch.Tensor, labels: torch.Tensor, coeff_list, guidance, *, neg_labels=None, init_latents=None,
@@ -298,9 +302,9 @@ class Denoiser:
         None (a request without one keeps the zero label).  ``init_latents`` [B,C,S,S] + ``start_mix`` (B values in (0, 1], default 1) +
         ``mask`` [B,1,S,S] as in ``sample_latents_from``; a text-to-image request in a call that carries masks takes an all-ones mask.
         Request b's result equals, bit for bit, ``sample_latents`` / ``sample_latents_from`` of that request alone.  Returns fp32 latents
-        [B,C,S,S] in the caller's order; with ``trace`` also [n_max-1,B,C,S,S] predictions and states, zero where a request had finished."""
+        [B,C,S,S] in the caller's order; with ``trace`` also [n_max-1,B,C,S,S] predictions and states, zero where a request had finished.
+        Its own here: the records' checks, the engine's order, the row cap and the negative labels as one tensor; the rest is ``_run_sampler``."""
         from . import schedule
-        dev = self._resolve_device(noise)
         B = noise.shape[0]
         if noise.dim() != 4 or tuple(noise.shape[1:]) != (self.n_channels, self.image_size, self.image_size):
             raise ValueError(f"noise {tuple(noise.shape)}: expected [B,{self.n_channels},{self.image_size},{self.image_size}]")
@@ -319,12 +323,8 @@ class Denoiser:
                 raise ValueError(f"guidance[{b}] = {guid[b]} is not finite")
             if not (0.0 < mix[b] <= 1.0):
                 raise ValueError(f"start_mix[{b}] = {mix[b]} outside (0, 1]")
-        if init_latents is not None and tuple(init_latents.shape) != tuple(noise.shape):
-            raise ValueError(f"init_latents {tuple(init_latents.shape)} != noise {tuple(noise.shape)}")
         if init_latents is None and (mask is not None or any(v < 1.0 for v in mix)):
             raise ValueError("init_latents is required with a mask or with a start_mix < 1")
-        if mask is not None and tuple(mask.shape) != (B, 1) + tuple(noise.shape[2:]):
-            raise ValueError(f"mask {tuple(mask.shape)}: expected {(B, 1) + tuple(noise.shape[2:])}")
         neg, has_neg = None, [False] * B
         if neg_labels is not None:
             if isinstance(neg_labels, torch.Tensor):
@@ -340,14 +340,12 @@ class Denoiser:
                         raise ValueError(f"neg_labels[{b}] {tuple(r.shape)}: expected {(self.text_emb_size,)}")
                 has_neg = [r is not None for r in rows]
                 if any(has_neg):
+                    dev = self._resolve_device(noise)
                     neg = torch.stack([torch.zeros(self.text_emb_size, device=dev) if r is None else r.detach().to(dev, torch.float32) for r in rows])
-        if B == 0:
-            z = torch.empty_like(noise, dtype=torch.float32)
-            return (z, None, None) if trace else z
         counts = [t.shape[0] for t in tabs]
-        order = schedule.request_order(counts)                  # the engine wants non-increasing level counts: sort here, un-sort the results
-        n_max = counts[order[0]]
-        rows_needed = schedule.request_cond_rows([tabs[b] for b in order], sum(has_neg))
+        order = schedule.request_order(counts)                  # the engine wants non-increasing level counts: _run_sampler gathers and un-sorts
+        n_max = counts[order[0]] if B else 0
+        rows_needed = schedule.request_cond_rows([tabs[b] for b in order], sum(has_neg)) if B else 0
         if rows_needed > schedule.REQUEST_ROW_CAP:
             raise ValueError(f"the call needs {rows_needed} conditioning rows (distinct noise levels + labels): at most {schedule.REQUEST_ROW_CAP}")
         table = np.zeros((B, n_max, 6), dtype=np.float32)
@@ -355,28 +353,11 @@ class Denoiser:
         for k, b in enumerate(order):
             table[k, :counts[b]] = tabs[b]
             recs[k] = _lib.TldSampleRequest(counts[b], guid[b], mix[b], int(has_neg[b]))
-        h = self._ensure_engine(2 * B, dev)
-        idx = torch.tensor(order, device=dev)
-
-        def take(t):
-            return None if t is None else t.to(device=dev, dtype=torch.float32)[idx].contiguous()
-
-        eps, lab, z0, m, ng = take(noise), take(labels), take(init_latents), take(mask), take(neg)
-        out = torch.empty_like(eps)
-        tx0 = txt = None
-        if trace:
-            tx0 = torch.zeros((n_max - 1,) + tuple(eps.shape), device=dev, dtype=torch.float32)
-            txt = torch.zeros_like(tx0)
-        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().tld_sample_requests(
-                h, ptr(eps), ptr(z0), ptr(m), ptr(lab), ptr(ng), recs, table.ctypes.data_as(C.POINTER(C.c_float)), n_max,
-                float(sharp_f), float(bright_f), ptr(out), B, ptr(tx0), ptr(txt), C.c_void_p(stream)), "tld_sample_requests")
-        inv = torch.empty_like(idx)
-        inv[idx] = torch.arange(B, device=dev)
-        out = out[inv]
-        return (out, tx0[:, inv], txt[:, inv]) if trace else out
+        # traces start as zeros: the engine leaves a finished request's slots alone
+        return self._run_sampler(noise, labels, n_max, trace, lambda h, B, eps, z0, m, lab, ng, out, tx0, txt, stream: _lib.check(
+            _lib.lib().tld_sample_requests(h, eps, z0, m, lab, ng, recs, table.ctypes.data_as(C.POINTER(C.c_float)), n_max, float(sharp_f),
+                                           float(bright_f), out, B, tx0, txt, stream), "tld_sample_requests"),
+            init_latents=init_latents, mask=mask, neg_labels=neg, order=order, new_trace=torch.zeros)
 
     # ---- test / bench hooks -----------------------------------------------------------------------------
     # launch paths of tld_engine_debug_paths, by bit number (include/tld_hip.h; None: unused bit)

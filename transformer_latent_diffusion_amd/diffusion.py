@@ -12,7 +12,7 @@ from __future__ import annotations
 import numbers
 import os
 from dataclasses import asdict, dataclass
-from typing import Any, Optional
+from typing import Any, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -23,6 +23,32 @@ from .configs import LTDConfig
 from .denoiser import Denoiser
 
 device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
+
+
+def check_mask_range(mask: Tensor, meaning: str = ""):
+    """An inpainting mask holds values in [0, 1]; ``meaning`` ends the message."""
+    if mask.numel():
+        lo, hi = float(mask.min()), float(mask.max())
+        if not (lo >= 0.0 and hi <= 1.0):
+            raise ValueError(f"mask values span [{lo}, {hi}]: expected [0, 1]{meaning}")
+
+
+def stack_optional(v, what: str, B: int, shape: tuple, fill: float):
+    """A per-request optional operand as one tensor: ``v`` is None, a tensor [B, *shape] (returned as it is) or a length-B sequence of
+    [*shape] tensors / None; returns None where no entry is given, else fp32 [B, *shape] on the host with ``fill`` for the None entries."""
+    if v is None or isinstance(v, Tensor):
+        if v is not None and tuple(v.shape) != (B,) + shape:
+            raise ValueError(f"{what} {tuple(v.shape)}: expected {(B,) + shape}")
+        return v
+    v = list(v)
+    if len(v) != B:
+        raise ValueError(f"{what}: {len(v)} entries for {B} requests")
+    if all(t is None for t in v):
+        return None
+    for b, t in enumerate(v):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{what}[{b}] {tuple(t.shape)}: expected {shape}")
+    return torch.stack([torch.full(shape, fill) if t is None else t.detach().to("cpu", torch.float32) for t in v])
 
 
 @dataclass
@@ -53,30 +79,46 @@ class DiffusionGenerator:
 
         ``use_ddpm_plus=True``: DPM-Solver++(2M); else DDIM with alpha = 1 - sigma (diffusion.py:45-48).
         """
-        latents = self.generate_latents(labels, n_iter, num_imgs, class_guidance, seed, img_size, sharp_f,
-                                        bright_f, exponent, seeds, noise_levels, use_ddpm_plus)
+        return self._decode(self.generate_latents(labels, n_iter, num_imgs, class_guidance, seed, img_size, sharp_f, bright_f, exponent,
+                                                  seeds, noise_levels, use_ddpm_plus), scale_factor)
+
+    def _decode(self, latents, scale_factor):
+        """The exit edge of the three ``generate*`` (diffusion.py:91): (decoded_images_on_cpu, latents); (None, latents) without a VAE."""
         if self.vae is None:
             return None, latents
-        img = self.vae.decode((latents * scale_factor).to(self.model_dtype))[0].cpu()   # diffusion.py:91
-        return img, latents
+        return self.vae.decode((latents * scale_factor).to(self.model_dtype))[0].cpu(), latents
+
+    def _in_model_dtype(self, out, trace):
+        """The sampler's fp32 latents in ``model_dtype``; with ``trace`` they come with the two fp32 trace tensors, which stay."""
+        if trace:
+            lat, tx0, txt = out
+            return lat.to(self.model_dtype), tx0, txt
+        return out.to(self.model_dtype)
+
+    @staticmethod
+    def _trajectory(n_iter, exponent, noise_levels, strength, use_ddpm_plus):
+        """One request's schedule as the sampler takes it: ``(coeffs, start_mix)``.  ``strength`` None: the whole schedule from pure noise;
+        else ``schedule.truncate_levels`` picks the entry level, and ``start_mix`` is that level in float32 (1.0 where nothing was cut:
+        pure noise at the first level, as the reference feeds it, diffusion.py:52,59).  Every ``generate_latents*`` builds its scalars
+        here, which is what makes a request of a batched call equal its solo call."""
+        levels = schedule.noise_schedule(n_iter, exponent, noise_levels)
+        k = 0
+        if strength is not None:
+            k, levels = schedule.truncate_levels(levels, strength)
+        return schedule.step_coefficients(levels, use_ddpm_plus), float(np.float32(levels[0])) if k > 0 else 1.0
 
     @torch.no_grad()
     def generate_latents(self, labels, n_iter=30, num_imgs=16, class_guidance=3, seed=10, img_size=32,
                          sharp_f=0.1, bright_f=0.1, exponent=1, seeds=None, noise_levels=None,
                          use_ddpm_plus=True, trace=False):
-        levels = schedule.noise_schedule(n_iter, exponent, noise_levels)
-        coeffs = schedule.step_coefficients(levels, use_ddpm_plus)
+        coeffs, _ = self._trajectory(n_iter, exponent, noise_levels, None, use_ddpm_plus)
         x_t = self.initialize_image(seeds, num_imgs, img_size, seed)
         if labels.size(0) != x_t.size(0):
             # the reference zips labels and noise by torch.cat (diffusion.py:61,98)
             raise RuntimeError(f"labels batch {labels.size(0)} != num_imgs {x_t.size(0)}")
         self.model.eval()
-        out = self.model.sample_latents(x_t, labels.to(self.device), coeffs, class_guidance, sharp_f, bright_f,
-                                        trace=trace)
-        if trace:
-            lat, tx0, txt = out
-            return lat.to(self.model_dtype), tx0, txt
-        return out.to(self.model_dtype)
+        return self._in_model_dtype(self.model.sample_latents(x_t, labels.to(self.device), coeffs, class_guidance, sharp_f, bright_f,
+                                                              trace=trace), trace)
 
     @torch.no_grad()
     def generate_from(self, init_latents: Tensor, labels: Tensor, strength: float = 0.6, mask: Optional[Tensor] = None, n_iter: int = 30,
@@ -84,12 +126,8 @@ class DiffusionGenerator:
                       img_size: Optional[int] = None, sharp_f: float = 0.1, bright_f: float = 0.1, exponent: float = 1,
                       seeds: Optional[Tensor] = None, noise_levels=None, use_ddpm_plus: bool = True):
         """``generate`` for image-to-image and inpainting (``generate_latents_from``); returns (decoded_images_on_cpu, latents)."""
-        latents = self.generate_latents_from(init_latents, labels, strength, mask, n_iter, num_imgs, class_guidance, seed, img_size,
-                                             sharp_f, bright_f, exponent, seeds, noise_levels, use_ddpm_plus)
-        if self.vae is None:
-            return None, latents
-        img = self.vae.decode((latents * scale_factor).to(self.model_dtype))[0].cpu()
-        return img, latents
+        return self._decode(self.generate_latents_from(init_latents, labels, strength, mask, n_iter, num_imgs, class_guidance, seed, img_size,
+                                                       sharp_f, bright_f, exponent, seeds, noise_levels, use_ddpm_plus), scale_factor)
 
     @torch.no_grad()
     def generate_latents_from(self, init_latents, labels, strength=0.6, mask=None, n_iter=30, num_imgs=None, class_guidance=3, seed=10,
@@ -106,7 +144,7 @@ class DiffusionGenerator:
         the mask is 0).  Shapes and ranges are checked on the host before anything is enqueued."""
         if init_latents.dim() != 4:
             raise ValueError(f"init_latents {tuple(init_latents.shape)}: expected [B,C,S,S]")
-        B, C_, S = init_latents.shape[0], init_latents.shape[1], init_latents.shape[-1]
+        B, S = init_latents.shape[0], init_latents.shape[-1]
         num_imgs = B if num_imgs is None else num_imgs
         img_size = S if img_size is None else img_size
         want = (num_imgs, self.model.n_channels, img_size, img_size) if seeds is None else tuple(seeds.shape)
@@ -117,23 +155,13 @@ class DiffusionGenerator:
         if mask is not None:
             if tuple(mask.shape) != (B, 1, img_size, img_size):
                 raise ValueError(f"mask {tuple(mask.shape)}: expected {(B, 1, img_size, img_size)} (latent resolution; see latent_mask)")
-            if mask.numel():
-                lo, hi = float(mask.min()), float(mask.max())
-                if not (lo >= 0.0 and hi <= 1.0):
-                    raise ValueError(f"mask values span [{lo}, {hi}]: expected [0, 1] (1 = regenerate, 0 = keep)")
-        full = schedule.noise_schedule(n_iter, exponent, noise_levels)
-        k, levels = schedule.truncate_levels(full, strength)
-        coeffs = schedule.step_coefficients(levels, use_ddpm_plus)
-        start_mix = float(np.float32(levels[0])) if k > 0 else 1.0      # k = 0: pure noise at the first level, as the reference feeds it (diffusion.py:52,59)
+            check_mask_range(mask, " (1 = regenerate, 0 = keep)")
+        coeffs, start_mix = self._trajectory(n_iter, exponent, noise_levels, strength, use_ddpm_plus)
         eps = self.initialize_image(seeds, num_imgs, img_size, seed)
         self.model.eval()
-        out = self.model.sample_latents_from(eps, init_latents.to(self.device), labels.to(self.device), coeffs, class_guidance, start_mix,
-                                             mask=None if mask is None else mask.to(self.device), sharp_f=sharp_f, bright_f=bright_f,
-                                             trace=trace)
-        if trace:
-            lat, tx0, txt = out
-            return lat.to(self.model_dtype), tx0, txt
-        return out.to(self.model_dtype)
+        return self._in_model_dtype(self.model.sample_latents_from(
+            eps, init_latents.to(self.device), labels.to(self.device), coeffs, class_guidance, start_mix,
+            mask=None if mask is None else mask.to(self.device), sharp_f=sharp_f, bright_f=bright_f, trace=trace), trace)
 
     @torch.no_grad()
     def generate_latents_requests(self, labels, *, n_iter=30, class_guidance=3, negative_labels=None, seed=10, seeds=None, img_size=None,
@@ -148,13 +176,13 @@ class DiffusionGenerator:
         (each request's own ``initialize_image(None, 1, size, seed)``, as ``generate_images_from_texts`` draws it); else ``seed`` draws the
         whole batch as ``generate_latents`` does.  ``init_latents`` [B,C,S,S] with ``strength`` (an entry None or 1.0: the text-to-image
         trajectory) and ``mask`` [B,1,S,S] as in ``generate_latents_from``; a sequence entry None stands for zeros (init) / all ones (mask).
-        Schedules are built per request with ``schedule.noise_schedule`` / ``truncate_levels`` / ``step_coefficients``, so the float64 scalars
-        are exactly those of the solo call.  Shapes and ranges are checked on the host before anything is enqueued."""
+        Each request's schedule comes from ``_trajectory``, the function the solo calls use, so its float64 scalars are exactly theirs.
+        Shapes and ranges are checked on the host before anything is enqueued."""
         B = labels.size(0)
         size = self.model.image_size if img_size is None else img_size
 
-        def per_request(v, what, scalar=(numbers.Number, bool, type(None))):
-            if isinstance(v, scalar) or (isinstance(v, Tensor) and v.dim() == 0):
+        def per_request(v, what):
+            if isinstance(v, (numbers.Number, bool, type(None))) or (isinstance(v, Tensor) and v.dim() == 0):
                 return [v] * B
             v = list(v)
             if len(v) != B:
@@ -166,63 +194,44 @@ class DiffusionGenerator:
         for b in range(B):
             if not np.isfinite(float(guid[b])):
                 raise ValueError(f"class_guidance[{b}] = {guid[b]} is not finite")
-
-        def stacked(v, what, shape, fill):
-            if v is None or isinstance(v, Tensor):
-                if v is not None and tuple(v.shape) != (B,) + shape:
-                    raise ValueError(f"{what} {tuple(v.shape)}: expected {(B,) + shape}")
-                return v
-            v = per_request(v, what, scalar=())
-            if all(t is None for t in v):
-                return None
-            for b, t in enumerate(v):
-                if t is not None and tuple(t.shape) != shape:
-                    raise ValueError(f"{what}[{b}] {tuple(t.shape)}: expected {shape}")
-            return torch.stack([torch.full(shape, fill) if t is None else t.detach().to("cpu", torch.float32) for t in v])
-
-        C_ = self.model.n_channels
-        z0 = stacked(init_latents, "init_latents", (C_, size, size), 0.0)
-        m = stacked(mask, "mask", (1, size, size), 1.0)
-        if m is not None and m.numel() and not (float(m.min()) >= 0.0 and float(m.max()) <= 1.0):
-            raise ValueError(f"mask values span [{float(m.min())}, {float(m.max())}]: expected [0, 1] (1 = regenerate, 0 = keep)")
+        z0 = stack_optional(init_latents, "init_latents", B, (self.model.n_channels, size, size), 0.0)
+        m = stack_optional(mask, "mask", B, (1, size, size), 1.0)
+        if m is not None:
+            check_mask_range(m, " (1 = regenerate, 0 = keep)")
         if z0 is None and (m is not None or any(v is not None and float(v) != 1.0 for v in stren)):
             raise ValueError("init_latents is required with a mask or a strength below 1")
         coeffs, mix = [], []
         for b in range(B):
             if int(n_it[b]) < 2 and noise_levels is None:
                 raise ValueError(f"n_iter[{b}] = {n_it[b]}: a trajectory needs at least two noise levels")
-            levels = schedule.noise_schedule(int(n_it[b]), expo[b], noise_levels)
-            k = 0
-            if stren[b] is not None:
-                k, levels = schedule.truncate_levels(levels, stren[b])
-            coeffs.append(schedule.step_coefficients(levels, bool(plus[b])))
-            mix.append(float(np.float32(levels[0])) if k > 0 else 1.0)
-        if seeds is None:
-            eps = self.initialize_image(None, B, size, seed)
-        elif isinstance(seeds, Tensor):
-            eps = self.initialize_image(seeds, B, size, seed)
-        else:
-            eps = torch.cat([self.initialize_image(None, 1, size, int(v)) for v in per_request(seeds, "seeds", scalar=())]) if B else \
-                self.initialize_image(None, 0, size, seed)
+            co, s0 = self._trajectory(int(n_it[b]), expo[b], noise_levels, stren[b], bool(plus[b]))
+            coeffs.append(co)
+            mix.append(s0)
+        eps = self._noise(seeds, B, size, seed)
         if eps.size(0) != B:
             raise RuntimeError(f"labels batch {B} != noise batch {eps.size(0)}")
         self.model.eval()
-        out = self.model.sample_latents_requests(eps, labels.to(self.device), coeffs, [float(g) for g in guid], neg_labels=negative_labels,
-                                                 init_latents=z0, start_mix=mix, mask=m, sharp_f=sharp_f, bright_f=bright_f, trace=trace)
-        if trace:
-            lat, tx0, txt = out
-            return lat.to(self.model_dtype), tx0, txt
-        return out.to(self.model_dtype)
+        return self._in_model_dtype(self.model.sample_latents_requests(
+            eps, labels.to(self.device), coeffs, [float(g) for g in guid], neg_labels=negative_labels, init_latents=z0, start_mix=mix,
+            mask=m, sharp_f=sharp_f, bright_f=bright_f, trace=trace), trace)
 
     @torch.no_grad()
     def generate_requests(self, labels, *, scale_factor: int = 8, **kw):
         """``generate_latents_requests`` plus the VAE decode; returns (decoded_images_on_cpu, latents)."""
         kw.pop("trace", None)
-        latents = self.generate_latents_requests(labels, **kw)
-        if self.vae is None:
-            return None, latents
-        img = self.vae.decode((latents * scale_factor).to(self.model_dtype))[0].cpu()
-        return img, latents
+        return self._decode(self.generate_latents_requests(labels, **kw), scale_factor)
+
+    def _noise(self, seeds, num_imgs, img_size, seed):
+        """``initialize_image`` where ``seeds`` may also be one int per image: image i then starts from its own
+        ``initialize_image(None, 1, img_size, seeds[i])``, the noise of a one-image call with that seed."""
+        if seeds is None or isinstance(seeds, Tensor):
+            return self.initialize_image(seeds, num_imgs, img_size, seed)
+        seeds = list(seeds)
+        if len(seeds) != num_imgs:
+            raise ValueError(f"seeds: {len(seeds)} entries for {num_imgs} requests")
+        if not seeds:
+            return self.initialize_image(None, 0, img_size, seed)
+        return torch.cat([self.initialize_image(None, 1, img_size, int(v)) for v in seeds])
 
     def initialize_image(self, seeds, num_imgs, img_size, seed):
         """Initial noise (diffusion.py:105-120): the caller's ``seeds`` tensor, or ``torch.randn`` from a
@@ -282,8 +291,7 @@ def latent_mask(mask, latent_size: int) -> Tensor:
     H = m.shape[0]
     if latent_size <= 0 or H % latent_size:
         raise ValueError(f"mask side {H} is not a multiple of the latent size {latent_size}")
-    if m.numel() and not (float(m.min()) >= 0.0 and float(m.max()) <= 1.0):
-        raise ValueError(f"mask values span [{float(m.min())}, {float(m.max())}]: expected [0, 1]")
+    check_mask_range(m)
     f = H // latent_size
     return m.reshape(latent_size, f, latent_size, f).mean(dim=(1, 3)).clamp_(0.0, 1.0).unsqueeze(0)
 
@@ -342,11 +350,15 @@ class DiffusionTransformer:
         import clip
         return clip.tokenize(prompts, truncate=True)
 
+    def _labels(self, texts) -> Tensor:
+        """The text encoder's labels of ``texts``, on the device it leaves them on: the injected ``text_encoder``, else CLIP over ``tokenize``."""
+        if self._text_encoder is not None:
+            return self._text_encoder(texts)
+        return self.clip_model.encode_text(self.tokenize(texts).to(self.device))
+
     @torch.no_grad()
     def encode_text(self, prompts):
-        if self._text_encoder is not None:
-            return self._text_encoder(prompts).cpu()
-        return self.clip_model.encode_text(self.tokenize(prompts).to(self.device)).cpu()
+        return self._labels(prompts).cpu()
 
     @torch.no_grad()
     def generate_images_from_texts(self, prompts, class_guidance=6, seeds=11, n_iter=15, negative_prompts=None):
@@ -356,8 +368,9 @@ class DiffusionTransformer:
         per prompt.  ``seeds``: an int (request i uses seeds + i) or one int per prompt.  Request i's picture is exactly
         what ``generate_image_from_text(prompts[i], seed=seeds[i])`` returns: samples never interact.
         ``class_guidance`` / ``n_iter`` may be one value per prompt and ``negative_prompts`` one string (or None) per prompt, or one string
-        for all: the call then goes through ``generate_latents_requests`` (still one sampler call), and a negative
-        prompt is encoded with the same text encoder in the same call as the prompts.  Scalars and no negatives take the path above."""
+        for all: the sampler call is then ``generate_latents_requests`` (still one call), and a negative
+        prompt is encoded with the same text encoder in the same call as the prompts.  Scalars and no negatives call ``generate_latents``;
+        the seeds and noise before the sampler call and the decode and pictures after it are the same code for both."""
         from .sharded import sharded_sample
         prompts = list(prompts)
         n = len(prompts)
@@ -366,22 +379,32 @@ class DiffusionTransformer:
         seed_list = [int(seeds) + i for i in range(n)] if isinstance(seeds, numbers.Integral) else [int(v) for v in seeds]
         if len(seed_list) != n:
             raise ValueError(f"{len(seed_list)} seeds for {n} prompts")
-        if not (isinstance(class_guidance, numbers.Number) and isinstance(n_iter, numbers.Number) and negative_prompts is None):
-            return self._generate_images_requests(prompts, class_guidance, seed_list, n_iter, negative_prompts)
-        if self._text_encoder is not None:
-            labels = self._text_encoder(prompts)
-        else:
-            labels = self.clip_model.encode_text(self.tokenize(prompts).to(self.device))
-        labels = labels.to(self.device, torch.float32)
         gen, size = self.diffuser, self.diffuser.model.image_size
-        x_T = torch.cat([gen.initialize_image(None, 1, size, s) for s in seed_list])     # each request's own noise
+        if isinstance(class_guidance, numbers.Number) and isinstance(n_iter, numbers.Number) and negative_prompts is None:
+            labels, extras = self._labels(prompts).to(self.device, torch.float32), ()
 
-        def one(xs, ls):
-            return gen.generate_latents(ls, n_iter=n_iter, num_imgs=xs.shape[0], class_guidance=class_guidance, img_size=size,
-                                        sharp_f=0, bright_f=0, exponent=1, seeds=xs)
+            def one(xs, ls):
+                return gen.generate_latents(ls, n_iter=n_iter, num_imgs=xs.shape[0], class_guidance=class_guidance, img_size=size,
+                                            sharp_f=0, bright_f=0, exponent=1, seeds=xs)
+        else:
+            def per_prompt(v, what):
+                v = [v] * n if isinstance(v, numbers.Number) else list(v)
+                if len(v) != n:
+                    raise ValueError(f"{len(v)} {what} values for {n} prompts")
+                return v
 
-        latents = sharded_sample(one, x_T, labels)
-        out = gen.vae.decode((latents * 8).to(gen.model_dtype))[0].cpu()                # scale_factor 8 (diffusion.py:180)
+            guid, n_it = [float(g) for g in per_prompt(class_guidance, "class_guidance")], [int(k) for k in per_prompt(n_iter, "n_iter")]
+            labels, neg_rows = self._encode_with_negatives(prompts, negative_prompts)
+            extras = (torch.arange(n),)
+
+            def one(xs, ls, which):           # the per-request scalars ride as the requests' indices, sliced like every per-sample tensor
+                w = [int(i) for i in which]
+                return gen.generate_latents_requests(ls, n_iter=[n_it[i] for i in w], class_guidance=[guid[i] for i in w],
+                                                     negative_labels=None if neg_rows is None else [neg_rows[i] for i in w], seeds=xs, img_size=size,
+                                                     sharp_f=0, bright_f=0, exponent=1)
+
+        x_T = gen._noise(seed_list, n, size, 0)                                          # each request's own noise
+        out = gen._decode(sharded_sample(one, x_T, labels, extras=extras), 8)[0]         # scale_factor 8 (diffusion.py:180)
         return [to_pil(((out[i] + 1) / 2).float().clip(0, 1)) for i in range(n)]
 
     def _encode_with_negatives(self, prompts, negative_prompts):
@@ -395,11 +418,7 @@ class DiffusionTransformer:
             if len(negs) != n:
                 raise ValueError(f"{len(negs)} negative prompts for {n} prompts")
         texts = list(prompts) + [str(p) for p in negs if p is not None]
-        if self._text_encoder is not None:
-            emb = self._text_encoder(texts)
-        else:
-            emb = self.clip_model.encode_text(self.tokenize(texts).to(self.device))
-        emb = emb.to(self.device, torch.float32)
+        emb = self._labels(texts).to(self.device, torch.float32)
         if len(texts) == n:
             return emb, None
         rows, k = [], n
@@ -408,48 +427,19 @@ class DiffusionTransformer:
             k += p is not None
         return emb[:n], rows
 
-    @torch.no_grad()
-    def _generate_images_requests(self, prompts, class_guidance, seed_list, n_iter, negative_prompts):
-        """``generate_images_from_texts`` with per-prompt sampler scalars and negative prompts: one encoder call, one sampler call."""
-        from .sharded import sharded_sample
-        n = len(prompts)
-
-        def per_prompt(v, what):
-            v = [v] * n if isinstance(v, numbers.Number) else list(v)
-            if len(v) != n:
-                raise ValueError(f"{len(v)} {what} values for {n} prompts")
-            return v
-
-        guid, n_it = [float(g) for g in per_prompt(class_guidance, "class_guidance")], [int(k) for k in per_prompt(n_iter, "n_iter")]
-        labels, neg_rows = self._encode_with_negatives(prompts, negative_prompts)
-        gen, size = self.diffuser, self.diffuser.model.image_size
-        x_T = torch.cat([gen.initialize_image(None, 1, size, s) for s in seed_list])     # each request's own noise
-
-        def one(xs, ls, which):               # the per-request scalars ride as the requests' indices, sliced like every per-sample tensor
-            w = [int(i) for i in which]
-            return gen.generate_latents_requests(ls, n_iter=[n_it[i] for i in w], class_guidance=[guid[i] for i in w],
-                                                 negative_labels=None if neg_rows is None else [neg_rows[i] for i in w], seeds=xs, img_size=size,
-                                                 sharp_f=0, bright_f=0, exponent=1)
-
-        latents = sharded_sample(one, x_T, labels, extras=(torch.arange(n),))
-        out = gen.vae.decode((latents * 8).to(gen.model_dtype))[0].cpu()                # scale_factor 8 (diffusion.py:180)
-        return [to_pil(((out[i] + 1) / 2).float().clip(0, 1)) for i in range(n)]
-
     def generate_image_from_text(self, prompt: str, class_guidance=6, seed=11, num_imgs=1, img_size=32, n_iter=15, *, negative_prompt=None):
         nrow = int(np.sqrt(num_imgs))
         if negative_prompt is not None:       # the unconditional half of the guidance pair reads the negative prompt's label instead of zeros
             labels, neg = self._encode_with_negatives([prompt] * num_imgs, [negative_prompt] + [None] * (num_imgs - 1))
             out, _ = self.diffuser.generate_requests(labels, negative_labels=[neg[0]] * num_imgs, n_iter=n_iter, class_guidance=class_guidance,
                                                      seed=seed, exponent=1, scale_factor=8, sharp_f=0, bright_f=0)
-            return to_pil(make_image_grid((out + 1) / 2, nrow=nrow, padding=4).float().clip(0, 1))
-        labels = self.encode_text([prompt] * num_imgs)
-        # NOTE: like the reference, ``img_size`` is ignored in favour of the model's own size (:175)
-        out, out_latent = self.diffuser.generate(
-            labels=labels, num_imgs=num_imgs, img_size=self.diffuser.model.image_size,
-            class_guidance=class_guidance, seed=seed, n_iter=n_iter, exponent=1, scale_factor=8, sharp_f=0,
-            bright_f=0)
+        else:
+            # NOTE: like the reference, ``img_size`` is ignored in favour of the model's own size (:175)
+            out, _ = self.diffuser.generate(
+                labels=self.encode_text([prompt] * num_imgs), num_imgs=num_imgs, img_size=self.diffuser.model.image_size,
+                class_guidance=class_guidance, seed=seed, n_iter=n_iter, exponent=1, scale_factor=8, sharp_f=0,
+                bright_f=0)
         return to_pil(make_image_grid((out + 1) / 2, nrow=nrow, padding=4).float().clip(0, 1))
-
 
     @torch.no_grad()
     def generate_image_from_image(self, image, prompt: str, strength=0.6, mask=None, class_guidance=6, seed=11, n_iter=15,
@@ -500,6 +490,16 @@ class DiffusionTransformer:
         pic = to_pil(((out[0] + 1) / 2).float().clip(0, 1))
         return (pic, latents) if return_latents else pic
 
+class _Request(NamedTuple):
+    """One queued request of ``RequestBatcher``."""
+    ticket: int
+    prompt: str
+    class_guidance: float
+    seed: int
+    n_iter: int
+    negative_prompt: Optional[str]
+
+
 class RequestBatcher:
     """Groups text-to-image requests into batched sampler calls (serving-side batching; the reference's FastAPI
     handler runs the blocking pipeline once per request, tld/app.py:48-65).
@@ -526,7 +526,8 @@ class RequestBatcher:
             raise ValueError("a negative prompt needs RequestBatcher(mixed=True)")
         ticket = self._next
         self._next += 1
-        self._queue.append((ticket, str(prompt), float(class_guidance), int(seed), int(n_iter), None if negative_prompt is None else str(negative_prompt)))
+        self._queue.append(_Request(ticket, str(prompt), float(class_guidance), int(seed), int(n_iter),
+                                    None if negative_prompt is None else str(negative_prompt)))
         return ticket
 
     def pending(self) -> int:
@@ -549,7 +550,7 @@ class RequestBatcher:
             calls, cur = [], []
             for q in self._queue:
                 if cur and (len(cur) == self.max_batch or
-                            self.call_rows([(r[4], r[5] is not None) for r in cur + [q]]) > schedule.REQUEST_ROW_CAP):
+                            self.call_rows([(r.n_iter, r.negative_prompt is not None) for r in cur + [q]]) > schedule.REQUEST_ROW_CAP):
                     calls.append(cur)
                     cur = []
                 cur.append(q)
@@ -557,8 +558,8 @@ class RequestBatcher:
                 calls.append(cur)
             return calls
         groups = {}
-        for t, p, g, s, n, _ in self._queue:
-            groups.setdefault((g, n), []).append((t, p, s))
+        for q in self._queue:
+            groups.setdefault((q.class_guidance, q.n_iter), []).append((q.ticket, q.prompt, q.seed))
         calls = []
         for (g, n), reqs in sorted(groups.items(), key=lambda kv: -len(kv[1])):
             for i in range(0, len(reqs), self.max_batch):
@@ -570,27 +571,21 @@ class RequestBatcher:
         (bad prompt, out of memory) loses nothing that was already computed: the exception carries ``partial`` = the finished images,
         and a retry only repeats the groups that did not run."""
         out = {}
-        if self.mixed:
-            for reqs in self.plan():
-                kw = {"negative_prompts": [r[5] for r in reqs]} if any(r[5] is not None for r in reqs) else {}
-                try:
-                    imgs = self.pipeline.generate_images_from_texts([r[1] for r in reqs], class_guidance=[r[2] for r in reqs],
-                                                                    seeds=[r[3] for r in reqs], n_iter=[r[4] for r in reqs], **kw)
-                except Exception as exc:
-                    exc.partial = out
-                    raise
-                out.update({r[0]: im for r, im in zip(reqs, imgs)})
-                done = {r[0] for r in reqs}
-                self._queue = [q for q in self._queue if q[0] not in done]
-            return out
-        for g, n, reqs in self.plan():
+        for call in self.plan():
+            if self.mixed:                    # a list of the queue's records
+                reqs = call
+                kw = dict(class_guidance=[r.class_guidance for r in reqs], seeds=[r.seed for r in reqs], n_iter=[r.n_iter for r in reqs])
+                if any(r.negative_prompt is not None for r in reqs):
+                    kw["negative_prompts"] = [r.negative_prompt for r in reqs]
+            else:                             # (class_guidance, n_iter, [(ticket, prompt, seed), ...])
+                g, n, reqs = call
+                kw = dict(class_guidance=g, seeds=[s for _, _, s in reqs], n_iter=n)
             try:
-                imgs = self.pipeline.generate_images_from_texts([p for _, p, _ in reqs], class_guidance=g,
-                                                                seeds=[s for _, _, s in reqs], n_iter=n)
+                imgs = self.pipeline.generate_images_from_texts([r[1] for r in reqs], **kw)
             except Exception as exc:
                 exc.partial = out
                 raise
-            out.update({t: im for (t, _, _), im in zip(reqs, imgs)})
-            done = {t for t, _, _ in reqs}
-            self._queue = [q for q in self._queue if q[0] not in done]
+            out.update({r[0]: im for r, im in zip(reqs, imgs)})
+            done = {r[0] for r in reqs}
+            self._queue = [q for q in self._queue if q.ticket not in done]
         return out

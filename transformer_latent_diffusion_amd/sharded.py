@@ -18,6 +18,8 @@ from typing import Callable, Optional, Sequence, Tuple
 import torch
 import torch.distributed as dist
 
+from .diffusion import stack_optional
+
 
 def shard_bounds(total: int, world: int, rank: int) -> Tuple[int, int]:
     """Contiguous, balanced split: the first ``total % world`` ranks get one extra item."""
@@ -74,10 +76,8 @@ def generate_latents_sharded(gen, labels: torch.Tensor, n_iter: int = 30, num_im
     x_T = gen.initialize_image(seeds, num_imgs, img_size, seed)     # full batch, same on every rank
 
     def one(x_shard, lab_shard):
-        return gen.generate_latents(lab_shard, n_iter=n_iter, num_imgs=x_shard.shape[0],
-                                    class_guidance=class_guidance, seed=seed, img_size=img_size, sharp_f=sharp_f,
-                                    bright_f=bright_f, exponent=exponent, seeds=x_shard, noise_levels=noise_levels,
-                                    use_ddpm_plus=use_ddpm_plus)
+        return gen.generate_latents(lab_shard, n_iter, x_shard.shape[0], class_guidance, seed, img_size, sharp_f, bright_f, exponent,
+                                    x_shard, noise_levels, use_ddpm_plus)
 
     return sharded_sample(one, x_T, labels.to(x_T.device), group)
 
@@ -94,10 +94,8 @@ def generate_latents_from_sharded(gen, init_latents: torch.Tensor, labels: torch
     eps = gen.initialize_image(seeds, num_imgs, img_size, seed)     # full batch, same on every rank
 
     def one(eps_shard, lab_shard, z0_shard, mask_shard):
-        return gen.generate_latents_from(z0_shard, lab_shard, strength=strength, mask=mask_shard, n_iter=n_iter,
-                                         num_imgs=eps_shard.shape[0], class_guidance=class_guidance, seed=seed, img_size=img_size,
-                                         sharp_f=sharp_f, bright_f=bright_f, exponent=exponent, seeds=eps_shard,
-                                         noise_levels=noise_levels, use_ddpm_plus=use_ddpm_plus)
+        return gen.generate_latents_from(z0_shard, lab_shard, strength, mask_shard, n_iter, eps_shard.shape[0], class_guidance, seed, img_size,
+                                         sharp_f, bright_f, exponent, eps_shard, noise_levels, use_ddpm_plus)
 
     return sharded_sample(one, eps, labels.to(eps.device), group, extras=(init_latents, mask))
 
@@ -108,27 +106,21 @@ def generate_latents_requests_sharded(gen, labels: torch.Tensor, *, group: Optio
     """``DiffusionGenerator.generate_latents_requests`` over all ranks of ``group`` (same arguments, without ``trace``).  The noise,
     labels, negative labels, initial latents and masks travel as per-sample tensors; the per-request sequences (``n_iter``,
     ``class_guidance``, ``exponent``, ``strength``, ``use_ddpm_plus``) ride as the requests' indices, one more ``extras`` tensor sliced
-    with the same bounds, and every rank picks its own entries."""
+    with the same bounds, and every rank picks its own entries.  The noise is drawn and the optional operands are stacked by the helpers
+    ``generate_latents_requests`` itself uses; a whole tensor travels as it is (``sharded_sample`` checks its batch)."""
     B = labels.shape[0]
     size = gen.model.image_size if img_size is None else img_size
-    if seeds is None or isinstance(seeds, torch.Tensor):
-        eps = gen.initialize_image(seeds, B, size, seed)            # full batch, same on every rank
-    else:
-        eps = torch.cat([gen.initialize_image(None, 1, size, int(v)) for v in seeds])
+    eps = gen._noise(seeds, B, size, seed)                           # full batch, same on every rank
 
-    def tensor_of(v, shape, fill):                                   # a sequence with None entries -> one [B, ...] tensor
-        if v is None or isinstance(v, torch.Tensor):
-            return v
-        if all(t is None for t in v):
-            return None
-        return torch.stack([torch.full(shape, fill) if t is None else t.detach().to("cpu", torch.float32) for t in v])
+    def tensor_of(v, what, shape, fill):
+        return v if isinstance(v, torch.Tensor) else stack_optional(v, what, B, shape, fill)
 
     has_neg = None
     if negative_labels is not None and not isinstance(negative_labels, torch.Tensor):
         has_neg = [t is not None for t in negative_labels]
-    neg = tensor_of(negative_labels, (labels.shape[1],), 0.0)
-    z0 = tensor_of(init_latents, tuple(eps.shape[1:]), 0.0)
-    m = tensor_of(mask, (1, size, size), 1.0)
+    neg = tensor_of(negative_labels, "neg_labels", (labels.shape[1],), 0.0)
+    z0 = tensor_of(init_latents, "init_latents", tuple(eps.shape[1:]), 0.0)
+    m = tensor_of(mask, "mask", (1, size, size), 1.0)
 
     def one(eps_shard, lab_shard, which, neg_shard, z0_shard, mask_shard):
         w = [int(i) for i in which]
