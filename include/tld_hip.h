@@ -166,6 +166,24 @@ TLD_API int tld_sample_requests(tld_engine* e, const void* noise, const void* in
                const tld_sample_request* requests, const float* coeffs, int32_t n_max, float sharp_f, float bright_f, void* out_latent,
                int32_t batch, void* trace_x0, void* trace_xt, void* hip_stream);
 
+/* tld_sample_requests with one guidance value per FORWARD: guidance is a HOST array [batch, n_max], row b holding g[b][i] for
+ * i = 0 .. requests[b].n_levels - 1 (the last entry belongs to the final prediction); entries past n_levels are ignored, every used entry must be
+ * finite, and requests[b].class_guidance is ignored.  A forward whose g is not bit-equal to 1.0f is today's step: x0 = fma(g, cond, (1 - g) unc).
+ * A forward whose g is 1.0f has NO unconditional model sample: x0 = cond, the value itself -- what the formula gives at g = 1 for finite unc, up to
+ * the sign of a zero.  The model batch of step i is [B_i conditional samples | U_i unconditional samples], U_i = #{b < B_i : g[b][i] != 1} compacted in
+ * request order, so the call makes sum(n_levels) + sum(U_i) model-sample forwards and needs max_i (B_i + U_i) <= max_batch (not 2 x batch).  Request
+ * b's results do not depend on the other requests, on their tables, or on whether its own unguided steps were skipped or computed.  Limited-interval
+ * guidance (guide only while sigma is inside [lo, hi]) is a table of g and 1.0 (schedule.guidance_table).  It records the launch-path bits 58-60 of
+ * the tld_sample_requests step it runs.  The record checks come first and need no device; every refusal happens before anything is enqueued; no
+ * stream synchronisation.  Test hook TLD_GUIDANCE_SKIP=0 (read at tld_engine_create): the full 2 B_i batch runs at every step and an unguided step
+ * combines with the fma as if guided at g = 1; the capacity rule follows the batch actually run. */
+TLD_API int tld_sample_requests_guided(tld_engine* e, const void* noise, const void* init_latent, const void* mask, const void* labels,
+               const void* neg_labels, const tld_sample_request* requests, const float* coeffs, const float* guidance, int32_t n_max, float sharp_f,
+               float bright_f, void* out_latent, int32_t batch, void* trace_x0, void* trace_xt, void* hip_stream);
+/* model samples the last sampler call on this engine enqueued: conditional and unconditional.  tld_sample / tld_sample_from / tld_sample_requests
+ * report sum(n_levels) twice; tld_sample_requests_guided reports (sum(n_levels), sum(U_i)) */
+TLD_API int tld_engine_sample_rows(tld_engine* e, int64_t* cond, int64_t* uncond);
+
 /* Test hook: stage capture of the inference forward (what tld_train_set_debug is to the training step).  With debug on, a forward
  * (tld_denoiser_forward, or every step of tld_sample / tld_sample_from)
  *   - first fills every engine-owned activation, statistics, seam and split-K buffer -- and, once per call, the conditioning tables -- with 0xFF bytes

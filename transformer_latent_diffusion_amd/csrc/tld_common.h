@@ -365,6 +365,7 @@ struct EmbedParams {
     resid_t* tok;                 // [B*N, d]
     float2* stats_out;            // optional [B*N][kLnSlots]: slot 0 <- (sum, sum of squares) of the rounded row, slot 1 <- 0
     int batch, src_batch;         // model sample b reads latent b % src_batch (CFG doubling without a copy)
+    const int* src_row;           // optional device table [batch]: model sample b reads latent src_row[b] instead
     int C, S, p, grid, pd, d, ntok;
 };
 void launch_embed(const EmbedParams& p, hipStream_t s);
@@ -385,6 +386,7 @@ struct CrossRowParams {
     const resid_t* x_in;          // optional separate input stream [src_batch*ntok, d] (CFG layer-0 sharing)
     const bf16* att;              // [M,d]  (or [src_batch*ntok, d] with x_in)
     int src_batch;                // with x_in: model sample b reads x_in / att of sample b % src_batch
+    const int* src_row;           // optional device table [batch]: with x_in, sample b reads those of sample src_row[b] instead
     const float* wq;              // [T, H, d]  gamma2 * (Wq_h^T k_t[h] / 8) for this layer (per token row)
     const float* bwq;             // [T, H]     sum_j beta2[j] * (Wq_h^T k_t[h] / 8)[j]
     const float* v; int v_ld;     // [T, v_ld]  cross-attention values (per token row) for this layer
@@ -422,6 +424,7 @@ struct SamplerStepRow {
     float g, a, b, c, c1, c2;     // class guidance and the step's coefficients of the request (schedule.py)
     float s_next;                 // noise level the updated x_t sits at (read with a mask only; unused on the request's final step)
     int final_step;               // 1: the request's last level -- combine (+ mask blend, + shifts on channels 3 and 0) into out_latent, no update
+                                  // (the slots flavour packs final | (slot + 1) << 1 here: see launch_sampler_step)
 };
 struct SamplerStepParams {
     const float* x0_2b;           // [2 active, img] model output of the step: cond rows of the active prefix, then their uncond rows
@@ -438,7 +441,9 @@ struct SamplerStepParams {
     int active, img, chan_stride; // requests still running at this step (a prefix: the records are ordered by non-increasing level count)
 };
 // path: the EP_UPDATE* bit that names the flavour of step the calling entry asked for
-void launch_sampler_step(const SamplerStepParams& p, int path, hipStream_t s);
+// slots (tld_sample_requests_guided): x0_2b is [active cond samples | the unconditional samples of the requests guided at this step], and a row's
+// final_step holds final | (slot + 1) << 1 -- the unconditional operand of the request is sample active + slot; slot + 1 == 0: none, x0 = cond itself
+void launch_sampler_step(const SamplerStepParams& p, int path, hipStream_t s, bool slots = false);
 // x_t[b] = s0 noise[b] + (1 - s0) z0[b] with s0 = s0v[b * s0_stride] read from a device table; s0 == 1 copies noise[b] (z0 may then be null).  path: EP_START_MIX*
 void launch_start_mix(const float* noise, const float* z0, const float* s0v, int s0_stride, float* x_t, int batch, int img, int path, hipStream_t s);
 

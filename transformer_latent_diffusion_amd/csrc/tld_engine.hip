@@ -134,6 +134,8 @@ struct tld_engine {
     resid_t* x = nullptr;
     resid_t* x_half = nullptr;         // patch embedding of the un-doubled batch (CFG layer-0 sharing)
     bool share_l0 = true;              // TLD_SHARE_L0=0 disables (A/B testing)
+    bool guidance_skip = true;         // TLD_GUIDANCE_SKIP=0: tld_sample_requests_guided runs the unconditional sample of an unguided step too (A/B testing)
+    int64_t rows_cond = 0, rows_uncond = 0;     // model samples the last sampler call enqueued (tld_engine_sample_rows)
     bool fold_ln1 = true;              // TLD_FOLD_LN1=0: separate LayerNorm-1 kernel (A/B testing)
     bool low_latency = false;          // tld_engine_set_low_latency: capacity class for small batches (round 5) -- the down projection runs as split-K (see run_body)
     float* splitk = nullptr;           // [ll_split][max rows][d] fp32 slices of it
@@ -450,14 +452,15 @@ void cond_label_rows(tld_engine* e, int row0, int Tl, hipStream_t s) {
                       e->text, e->d, 0, s);
 }
 
-// embed -> L decoder blocks -> tail, for `batch` model samples whose latents are x_src[b % src_batch].
+// embed -> L decoder blocks -> tail, for `batch` model samples whose latents are x_src[b % src_batch], or x_src[src_row[b]] with a device table
+// src_row [batch] whose first src_batch entries are the identity (src_batch <= batch <= 2 src_batch: the unconditional samples are a subset).
 // share_l0: the model batch is [x_src ; x_src] (CFG doubling), so everything before the first cross-attention --
 // patch embedding, LN1, the QKV GEMM and self-attention of block 0 -- is identical for both halves and is
 // computed for src_batch samples only; block 0's row kernel then fans it out to the 2*src_batch streams.
 int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const int* noise_row,
-             const int* label_row, float* out, hipStream_t s, bool share_l0 = false) {
+             const int* label_row, float* out, hipStream_t s, bool share_l0 = false, const int* src_row = nullptr) {
     const int d = e->d, M = batch * e->ntok;
-    share_l0 = share_l0 && e->share_l0 && batch == 2 * src_batch;
+    share_l0 = share_l0 && e->share_l0 && (src_row ? batch > src_batch && batch <= 2 * src_batch : batch == 2 * src_batch);
     if (int rc = debug_poison(e, s)) return rc;
     const int b0 = share_l0 ? src_batch : batch;            // samples processed up to block 0's attention
     resid_t* xe = share_l0 ? e->x_half : e->x;
@@ -469,6 +472,7 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
         ep.x = x_src; ep.conv_w = e->conv_w; ep.conv_b = e->conv_b; ep.ln1_w = e->pln1_w; ep.ln1_b = e->pln1_b;
         ep.lin_wt = e->plin_wt; ep.lin_w_hl = e->plin_w_hl; ep.lin_b = e->plin_b; ep.ln2_w = e->pln2_w; ep.ln2_b = e->pln2_b; ep.pos = e->pos;
         ep.tok = xe; ep.stats_out = fold1 ? e->ln_stats : nullptr; ep.batch = b0; ep.src_batch = src_batch; ep.C = e->cfg.n_channels;
+        ep.src_row = share_l0 ? nullptr : src_row;               // (shared: the first src_batch samples are the identity)
         ep.S = e->cfg.image_size; ep.p = e->cfg.patch_size; ep.grid = e->grid; ep.pd = e->pd; ep.d = d;
         ep.ntok = e->ntok;
         launch_embed(ep, s);
@@ -532,7 +536,7 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
             ProfScope ps(e, KC_CROSS, s);
             CrossRowParams cp{};
             cp.x = e->x; cp.att = e->att;
-            cp.x_in = half ? xe : nullptr; cp.src_batch = src_batch;
+            cp.x_in = half ? xe : nullptr; cp.src_batch = src_batch; cp.src_row = src_row;
             cp.wq = e->c_wq + (size_t)l * e->cond_cap * e->H * d;
             cp.bwq = e->c_bwq + (size_t)l * e->cond_cap * e->H;
             cp.v = e->c_kv + (size_t)l * e->cond_cap * 2 * d + d;     // V half of each [2d] row
@@ -643,6 +647,7 @@ struct SamplePlan {
     int B, n_max, stride;
     const tld_sample_request* requests;
     const float* coeffs;                 // HOST [B or 1][n_max][6]: (sigma, a, b, c, c1, c2) per level
+    const float* guidance;               // HOST [B][n_max] or null: the guidance of request b's forward i instead of its record's (tld_sample_requests_guided)
     // conditioning noise rows: Tn sigmas and, per (step, request), the row of its sigma; null: row i is level i of the one table (the uniform entries)
     int Tn; const float* sig; const int* noise_idx;       // sig [Tn], noise_idx [n_max][B]
     const float *noise, *init_latent, *mask, *labels, *neg_labels;      // device; init_latent / mask / neg_labels optional
@@ -652,15 +657,35 @@ struct SamplePlan {
     bool keep_stages;                    // step.* and the body's stages are kept at the debug step (the uniform entries)
 };
 
+// Unconditional slots of step i of a guided call, for the Bi requests still running: slot[b] is the place of request b's unconditional sample among the
+// step's (compacted in request order), or -1 where its guidance is 1.0f and none exists.  skip off: every request keeps one.  Returns their number U_i.
+int guided_slots(const float* guidance, int n_max, int Bi, int i, bool skip, int* slot) {
+    int U = 0;
+    for (int b = 0; b < Bi; ++b) slot[b] = (!skip || guidance[(size_t)b * n_max + i] != 1.0f) ? U++ : -1;
+    return U;
+}
+
 // The one sampler loop: conditioning tables of every request's whole trajectory, the start, then per step the model on the requests that still run
 // (a shrinking prefix, CFG-doubled, layer-0 sharing) and the elementwise step.  Host-built tables travel through the engine's pinned staging buffer
 // in two uploads behind stage_ev: no stream synchronisation.  Conditioning rows: Tn noise rows, B label rows, the zero row, one row per negative label.
+// With a guidance table (tld_sample_requests_guided) the model batch of step i is [Bi conditional | U_i unconditional] samples, U_i the requests guided at
+// that step: the step's rows then carry a third table, the request each model sample reads, and a request's step row its unconditional slot.
 int run_sampler(tld_engine* e, const SamplePlan& p, hipStream_t s) {
     const int B = p.B, n_max = p.n_max, Tn = p.Tn, tabB = p.stride ? B : 1;
     auto req = [&](int b) -> const tld_sample_request& { return p.requests[(size_t)b * p.stride]; };
+    const bool guided = p.guidance != nullptr;
+    const int per = guided ? 3 : 2;                           // int tables per step: noise rows, label rows (, source rows), one entry per model sample
     int n_neg = 0;
     size_t row_ints = 0;                                      // per step [noise rows 2 Bi | label rows 2 Bi] over the Bi requests still running
     for (int b = 0; b < B; ++b) { n_neg += req(b).has_negative ? 1 : 0; row_ints += (size_t)4 * req(b).n_levels; }
+    std::vector<int> slot((size_t)B), mbs((size_t)n_max);     // a step's unconditional slots; model samples per step
+    int64_t n_cond = 0, n_unc = 0;
+    for (int i = 0, Bi = B; i < n_max; ++i) {
+        while (req(Bi - 1).n_levels <= i) --Bi;
+        const int U = guided ? guided_slots(p.guidance, n_max, Bi, i, e->guidance_skip, slot.data()) : Bi;
+        mbs[(size_t)i] = Bi + U; n_cond += Bi; n_unc += U;
+    }
+    if (guided) row_ints = (size_t)3 * (size_t)(n_cond + n_unc);
     const int T = Tn + B + 1 + n_neg;
     const size_t tab_bytes = (size_t)n_max * tabB * sizeof(SamplerStepRow), mix_bytes = (size_t)tabB * sizeof(float);
     const size_t up_bytes = tab_bytes + mix_bytes + row_ints * sizeof(int);
@@ -681,7 +706,7 @@ int run_sampler(tld_engine* e, const SamplePlan& p, hipStream_t s) {
         for (int i = 0; i < n_max; ++i, c += 6) {
             SamplerStepRow& u = tab[(size_t)i * tabB + b];
             if (i >= r.n_levels) { u = SamplerStepRow{}; continue; }
-            u.g = r.class_guidance; u.a = c[1]; u.b = c[2]; u.c = c[3]; u.c1 = c[4]; u.c2 = c[5];
+            u.g = guided ? p.guidance[(size_t)b * n_max + i] : r.class_guidance; u.a = c[1]; u.b = c[2]; u.c = c[3]; u.c1 = c[4]; u.c2 = c[5];
             u.s_next = (i + 1 < r.n_levels) ? c[6] : 0.0f;    // sigma of the request's next row
             u.final_step = (i == r.n_levels - 1) ? 1 : 0;
         }
@@ -689,15 +714,24 @@ int run_sampler(tld_engine* e, const SamplePlan& p, hipStream_t s) {
     for (int t = 0; t < Tn; ++t) sigs[t] = p.sig ? p.sig[t] : p.coeffs[(size_t)t * 6];
     {
         int* nr = rows;
-        for (int i = 0, Bi = B; i < n_max; ++i, nr += 4 * Bi) {
+        for (int i = 0, Bi = B; i < n_max; nr += per * mbs[(size_t)i], ++i) {
             while (req(Bi - 1).n_levels <= i) --Bi;
-            int* lr = nr + 2 * Bi;
+            const int mb = mbs[(size_t)i];
+            int *lr = nr + mb, *sr = lr + mb;                 // (sr: guided only)
+            if (guided) guided_slots(p.guidance, n_max, Bi, i, e->guidance_skip, slot.data());
             for (int b = 0, k = 0; b < Bi; ++b) {
-                nr[b] = nr[Bi + b] = p.noise_idx ? p.noise_idx[(size_t)i * B + b] : i;
+                const int neg = req(b).has_negative ? Tn + B + 1 + k++ : Tn + B;  // the unconditional label: the zero row, or the request's own negative
+                const int sl = guided ? slot[(size_t)b] : b;
+                nr[b] = p.noise_idx ? p.noise_idx[(size_t)i * B + b] : i;
                 lr[b] = Tn + b;
-                lr[Bi + b] = req(b).has_negative ? Tn + B + 1 + k++ : Tn + B;     // the unconditional label: the zero row, or the request's own negative
+                if (guided) { sr[b] = b; tab[(size_t)i * tabB + b].final_step |= (sl + 1) << 1; }
+                if (sl < 0) continue;
+                nr[Bi + sl] = nr[b];
+                lr[Bi + sl] = neg;
+                if (guided) sr[Bi + sl] = b;
             }
         }
+        e->rows_cond = n_cond; e->rows_uncond = n_unc;
     }
 
     // ---- conditioning tables for every request's whole trajectory, once
@@ -732,15 +766,16 @@ int run_sampler(tld_engine* e, const SamplePlan& p, hipStream_t s) {
     else launch_start_mix(p.noise, p.init_latent, mix_dev, p.stride, e->xt, B, e->img, p.path_start, s);
     HIP_TRY(hipMemsetAsync(e->x0_prev, 0, tot * sizeof(float), s));
     // ---- the steps over the shrinking prefix of requests that still run
-    for (int i = 0, Bi = B; i < n_max; ++i, nr += 4 * Bi) {
+    for (int i = 0, Bi = B; i < n_max; nr += per * mbs[(size_t)i], ++i) {
         while (req(Bi - 1).n_levels <= i) --Bi;
         const bool last = i == n_max - 1;
+        const int mb = mbs[(size_t)i];
         // At the debug step (tld_engine_set_debug_step; every step when it is negative) the body's stages are kept, and so are the step's inputs
         // (x_t, x0_prev) and outputs (the 2B forward output, the x0 written, the next x_t).
         if (p.keep_stages) e->dbg_keep = e->debug && (e->dbg_step < 0 || e->dbg_step == i);
         SNAP("step.x_t", e->xt, ST_F32, s, B, e->img); SNAP("step.x0_prev", e->x0_prev, ST_F32, s, B, e->img);
         // pred_image: model(cat[x_t, x_t], sigma_i, [labels; 0])   (diffusion.py:94-101)
-        if (int rc = run_body(e, e->xt, Bi, 2 * Bi, nr, nr + 2 * Bi, e->io_out, s, true)) return rc;
+        if (int rc = run_body(e, e->xt, Bi, mb, nr, nr + mb, e->io_out, s, true, guided ? nr + 2 * mb : nullptr)) return rc;
         SamplerStepParams up{};
         up.x0_2b = e->io_out; up.x_t = e->xt; up.x0_prev = e->x0_prev; up.out_latent = p.out_latent;
         up.trace_x0 = (!last && p.trace_x0) ? p.trace_x0 + (size_t)i * tot : nullptr;
@@ -750,7 +785,7 @@ int run_sampler(tld_engine* e, const SamplePlan& p, hipStream_t s) {
         up.active = Bi; up.img = e->img; up.chan_stride = e->cfg.image_size * e->cfg.image_size;
         {
             ProfScope ps(e, KC_UPDATE, s);
-            launch_sampler_step(up, p.path_step, s);
+            launch_sampler_step(up, p.path_step, s, guided);
         }
         // (the uniform entries: every sample is at its last level together, and an inner step has just stored its prediction to x0_prev)
         SNAP("step.out", e->io_out, ST_F32, s, 2 * B, e->img); SNAP("step.x0", last ? p.out_latent : e->x0_prev, ST_F32, s, B, e->img);
@@ -840,6 +875,7 @@ int tld_engine_create(const tld_config* c, tld_engine** out) {
     e->layers.resize(e->L);
     if (const char* fd = getenv("TLD_FUSE_DWCONV")) e->fuse_dwconv = atoi(fd) != 0;
     if (const char* sl = getenv("TLD_SHARE_L0")) e->share_l0 = atoi(sl) != 0;
+    if (const char* gs = getenv("TLD_GUIDANCE_SKIP")) e->guidance_skip = atoi(gs) != 0;
     if (const char* f8 = getenv("TLD_FP8_FUSED")) e->fp8_fused = atoi(f8) != 0;
     if (const char* fl = getenv("TLD_FOLD_LN3")) e->fold_ln3 = atoi(fl) != 0;
     if (const char* fl = getenv("TLD_FOLD_LN1")) e->fold_ln1 = atoi(fl) != 0;
@@ -1112,7 +1148,7 @@ int tld_engine_finalize_weights(tld_engine* e) {
 
     const size_t B2 = (size_t)e->cfg.max_batch, M = B2 * e->ntok;
     if (int rc = dev_alloc(e, &e->x, M * d)) return rc;
-    if (int rc = dev_alloc(e, &e->x_half, (M + 1) / 2 * d)) return rc;
+    if (int rc = dev_alloc(e, &e->x_half, M * d)) return rc;      // (up to max_batch - 1 shared samples: a guided call's unconditional subset may be one sample)
     if (int rc = dev_alloc(e, &e->xn, M * d)) return rc;
     if (int rc = dev_alloc(e, &e->row_stats, M + 256)) return rc;
     if (int rc = dev_alloc(e, &e->ln_stats, (M + 256) * kLnSlots)) return rc;
@@ -1129,7 +1165,7 @@ int tld_engine_finalize_weights(tld_engine* e) {
     {   // what a debug forward poisons first: every activation / statistics / seam buffer above (the split-K slices and the fp8 operand: debug_poison)
         auto& P = e->poison;
         P.clear();
-        P.emplace_back(e->x, M * d * sizeof(resid_t)); P.emplace_back(e->x_half, (M + 1) / 2 * d * sizeof(resid_t)); P.emplace_back(e->xn, M * d * 2);
+        P.emplace_back(e->x, M * d * sizeof(resid_t)); P.emplace_back(e->x_half, M * d * sizeof(resid_t)); P.emplace_back(e->xn, M * d * 2);
         P.emplace_back(e->row_stats, (M + 256) * sizeof(float2)); P.emplace_back(e->ln_stats, (M + 256) * kLnSlots * sizeof(float2));
         P.emplace_back(e->qk, M * 2 * d * 2); P.emplace_back(e->vt, M * d * 2); P.emplace_back(e->att, M * d * 2);
         P.emplace_back(e->hid1, M * hid * 2); P.emplace_back(e->hid2, M * hid * 2);
@@ -1311,11 +1347,12 @@ int tld_sample_from(tld_engine* e, const void* noise, const void* init_latent, c
 // about 0.52 MB, so the grow-only tables stay near 0.5 GiB
 constexpr int kMaxRequestCondRows = 1024;
 
-int tld_sample_requests(tld_engine* e, const void* noise, const void* init_latent, const void* mask, const void* labels, const void* neg_labels,
-                        const tld_sample_request* requests, const float* coeffs, int32_t n_max, float sharp_f, float bright_f, void* out_latent,
-                        int32_t batch, void* trace_x0, void* trace_xt, void* hip_stream) {
+// tld_sample_requests, and with `guided` tld_sample_requests_guided: `guidance` is then the HOST table [batch][n_max] that replaces the records' class_guidance
+static int sample_requests(tld_engine* e, const void* noise, const void* init_latent, const void* mask, const void* labels, const void* neg_labels,
+                           const tld_sample_request* requests, const float* coeffs, const float* guidance, bool guided, int32_t n_max, float sharp_f,
+                           float bright_f, void* out_latent, int32_t batch, void* trace_x0, void* trace_xt, void* hip_stream) {
     // the records first: their checks need no engine and no device
-    if (!requests || !coeffs || batch <= 0) return fail(TLD_ERR_INVALID, "null argument");
+    if (!requests || !coeffs || batch <= 0 || (guided && !guidance)) return fail(TLD_ERR_INVALID, "null argument");
     if (mask && !init_latent) return fail(TLD_ERR_INVALID, "init_latent is required with a mask");
     const int B = batch;
     int n_neg = 0;
@@ -1327,7 +1364,9 @@ int tld_sample_requests(tld_engine* e, const void* noise, const void* init_laten
             return fail(TLD_ERR_INVALID, "request %d has %d levels after request %d with %d: the records must be ordered by non-increasing n_levels", b,
                         r.n_levels, b - 1, requests[b - 1].n_levels);
         if (!(r.start_mix > 0.0f && r.start_mix <= 1.0f)) return fail(TLD_ERR_INVALID, "request %d: start_mix %g outside (0, 1]", b, (double)r.start_mix);
-        if (!std::isfinite(r.class_guidance)) return fail(TLD_ERR_INVALID, "request %d: class_guidance is not finite", b);
+        if (!guided && !std::isfinite(r.class_guidance)) return fail(TLD_ERR_INVALID, "request %d: class_guidance is not finite", b);
+        for (int i = 0; guided && i < r.n_levels; ++i)
+            if (!std::isfinite(guidance[(size_t)b * n_max + i])) return fail(TLD_ERR_INVALID, "request %d: guidance of forward %d is not finite", b, i);
         if (r.start_mix < 1.0f && !init_latent) return fail(TLD_ERR_INVALID, "request %d: init_latent is required with start_mix < 1", b);
         if (r.has_negative) {
             if (!neg_labels) return fail(TLD_ERR_INVALID, "request %d: has_negative without neg_labels", b);
@@ -1337,8 +1376,18 @@ int tld_sample_requests(tld_engine* e, const void* noise, const void* init_laten
     if (requests[0].n_levels != n_max) return fail(TLD_ERR_INVALID, "n_max = %d, but the longest request has %d levels", n_max, requests[0].n_levels);
     if (!e || !noise || !labels || !out_latent) return fail(TLD_ERR_INVALID, "null argument");
     if (!e->finalized) return fail(TLD_ERR_STATE, "weights not finalized");
-    if (2 * batch > e->cfg.max_batch)
+    if (!guided && 2 * batch > e->cfg.max_batch)
         return fail(TLD_ERR_INVALID, "sampler batch %d needs max_batch >= %d (have %d)", batch, 2 * batch, e->cfg.max_batch);
+    if (guided) {     // the largest model batch of the call: the requests still running plus those of them guided at that step
+        std::vector<int> slot((size_t)B);
+        for (int i = 0, Bi = B; i < n_max; ++i) {
+            while (requests[Bi - 1].n_levels <= i) --Bi;
+            const int mb = Bi + guided_slots(guidance, n_max, Bi, i, e->guidance_skip, slot.data());
+            if (mb > e->cfg.max_batch)
+                return fail(TLD_ERR_INVALID, "step %d runs %d requests and %d unconditional samples: needs max_batch >= %d (have %d)", i, Bi, mb - Bi, mb,
+                            e->cfg.max_batch);
+        }
+    }
 
     // ---- the distinct float32 sigmas of every (request, step): requests that share a schedule share conditioning rows
     std::vector<float> sig;                                   // in order of first use
@@ -1359,12 +1408,32 @@ int tld_sample_requests(tld_engine* e, const void* noise, const void* init_laten
     DeviceGuard dg(e->cfg.device_id);
     PathScope paths(e);                                       // (debug: the launch paths are recorded; no stage of this entry is kept)
     SamplePlan p{};
-    p.B = B; p.n_max = n_max; p.stride = 1; p.requests = requests; p.coeffs = coeffs; p.Tn = Tn; p.sig = sig.data(); p.noise_idx = noise_idx.data();
+    p.B = B; p.n_max = n_max; p.stride = 1; p.requests = requests; p.coeffs = coeffs; p.guidance = guided ? guidance : nullptr; p.Tn = Tn; p.sig = sig.data(); p.noise_idx = noise_idx.data();
     p.noise = static_cast<const float*>(noise); p.init_latent = static_cast<const float*>(init_latent); p.mask = static_cast<const float*>(mask);
     p.labels = static_cast<const float*>(labels); p.neg_labels = static_cast<const float*>(neg_labels); p.sharp = sharp_f; p.bright = bright_f;
     p.out_latent = static_cast<float*>(out_latent); p.trace_x0 = static_cast<float*>(trace_x0); p.trace_xt = static_cast<float*>(trace_xt);
     p.path_step = mask ? EP_UPDATE_REQ_MASK : EP_UPDATE_REQ; p.path_start = EP_START_MIX_REQ; p.keep_stages = false;
     return run_sampler(e, p, static_cast<hipStream_t>(hip_stream));
+}
+
+int tld_sample_requests(tld_engine* e, const void* noise, const void* init_latent, const void* mask, const void* labels, const void* neg_labels,
+                        const tld_sample_request* requests, const float* coeffs, int32_t n_max, float sharp_f, float bright_f, void* out_latent,
+                        int32_t batch, void* trace_x0, void* trace_xt, void* hip_stream) {
+    return sample_requests(e, noise, init_latent, mask, labels, neg_labels, requests, coeffs, nullptr, false, n_max, sharp_f, bright_f, out_latent, batch,
+                           trace_x0, trace_xt, hip_stream);
+}
+
+int tld_sample_requests_guided(tld_engine* e, const void* noise, const void* init_latent, const void* mask, const void* labels, const void* neg_labels,
+                               const tld_sample_request* requests, const float* coeffs, const float* guidance, int32_t n_max, float sharp_f,
+                               float bright_f, void* out_latent, int32_t batch, void* trace_x0, void* trace_xt, void* hip_stream) {
+    return sample_requests(e, noise, init_latent, mask, labels, neg_labels, requests, coeffs, guidance, true, n_max, sharp_f, bright_f, out_latent, batch,
+                           trace_x0, trace_xt, hip_stream);
+}
+
+int tld_engine_sample_rows(tld_engine* e, int64_t* cond, int64_t* uncond) {
+    if (!e || !cond || !uncond) return fail(TLD_ERR_INVALID, "null argument");
+    *cond = e->rows_cond; *uncond = e->rows_uncond;
+    return TLD_OK;
 }
 
 int tld_debug_gemm_bf16(const void* a, const void* w, float* c, int32_t M, int32_t N, int32_t K, void* hip_stream) {

@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256) void embed_kernel(EmbedParams p) {
         if (row < total && lane < cpp) {
             const int b = row / p.ntok, t = row - b * p.ntok;
             const int ti = t / p.grid, tj = t - ti * p.grid;
-            xv = p.x[(((size_t)(b % p.src_batch) * p.C + ic) * p.S + (ti * p.p + iu)) * p.S + (tj * p.p + iv)];
+            xv = p.x[(((size_t)(p.src_row ? p.src_row[b] : b % p.src_batch) * p.C + ic) * p.S + (ti * p.p + iu)) * p.S + (tj * p.p + iv)];
         }
         return xv;
     };
@@ -301,7 +301,7 @@ __global__ __launch_bounds__(256, 3) void cross_row_kernel(CrossRowParams p, int
     // input rows: normally the same rows; with CFG layer-0 sharing the cond and uncond samples read the one copy
     const resid_t* xin = p.x_in ? p.x_in : p.x;
     const size_t obase = (size_t)b * p.ntok;
-    const size_t ibase = p.x_in ? (size_t)(b % p.src_batch) * p.ntok : obase;
+    const size_t ibase = p.x_in ? (size_t)(p.src_row ? p.src_row[b] : b % p.src_batch) * p.ntok : obase;
 
     // Two rows per wave at a time (independent reduction chains fill the DPP wait states), with the next
     // pair's HBM loads issued before the current pair is processed (the first pair's before the table fill).
@@ -498,7 +498,7 @@ __global__ __launch_bounds__(512) void cross_row_mfma_kernel(CrossRowParams p, i
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const resid_t* xin = p.x_in ? p.x_in : p.x;
     const size_t obase = (size_t)b * p.ntok;
-    const size_t ibase = p.x_in ? (size_t)(b % p.src_batch) * p.ntok : obase;
+    const size_t ibase = p.x_in ? (size_t)(p.src_row ? p.src_row[b] : b % p.src_batch) * p.ntok : obase;
 
     auto pair_row = [&](int g) { return 16 * (g0 + g) + 2 * wid; };   // this wave's row pair of group g (row inside the sample)
     // the next row pair's loads are in flight while the current one is processed (a second pair in flight measured 1 us SLOWER: 40.8 vs 39.7; round 4:
@@ -793,7 +793,7 @@ __global__ __launch_bounds__(256) void embed_mfma_kernel(EmbedParams p, const bf
     float xin[PD];
     {
         const int pp = p.p * p.p;
-        const float* xb = p.x + (size_t)(b % p.src_batch) * p.C * p.S * p.S;
+        const float* xb = p.x + (size_t)(p.src_row ? p.src_row[b] : b % p.src_batch) * p.C * p.S * p.S;
 #pragma unroll
         for (int k = 0; k < PD; ++k) {
             const int c = k / pp, uv = k - c * pp, u = uv / p.p, v = uv - u * p.p;
@@ -1028,7 +1028,9 @@ __global__ __launch_bounds__(256) void tail_mfma_kernel(TailParams p, const bf16
 //   on the final step  x0  <- m x0  + (1 - m) z0                                  before the latent shifts
 // x0_prev and trace_x0 keep the unblended prediction.  The blend is written m a + (1 - m) b: m = 1 gives a and m = 0 gives b exactly, and with
 // no contraction it rounds as the fp32 reference loop does.
-template <bool MASK, int V>
+// SLOT (tld_sample_requests_guided): a request has an unconditional sample only at the steps it is guided at.  Its row's `final_step` then holds
+// final | (slot + 1) << 1: the unconditional operand sits at sample active + slot of the model output, and a row without a slot takes x0 = cond itself.
+template <bool MASK, int V, bool SLOT = false>
 __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p) {
 #pragma clang fp contract(off)
     const int i = (blockIdx.x * 256 + threadIdx.x) * V;
@@ -1047,15 +1049,25 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p) 
     const int ch = r / p.chan_stride;
     const SamplerStepRow q = p.rows[b * p.row_stride];
     load(cond, p.x0_2b + i);
-    load(unc, p.x0_2b + n + i);
+    const int slot = SLOT ? (q.final_step >> 1) - 1 : 0;
+    const bool final_step = SLOT ? (q.final_step & 1) != 0 : q.final_step != 0;
+    if constexpr (SLOT) {
+        if (slot >= 0) load(unc, p.x0_2b + (size_t)(p.active + slot) * p.img + r);
+    } else {
+        load(unc, p.x0_2b + n + i);
+    }
+    auto combine = [&](float c, float u) {                                    // diffusion.py:124-125
+        if constexpr (SLOT) { if (slot < 0) return c; }
+        return __builtin_fmaf(q.g, c, (1.0f - q.g) * u);
+    };
     if constexpr (MASK) {
         load(m, p.mask + (size_t)b * p.chan_stride + (r - ch * p.chan_stride));
         load(z, p.z0 + i);
     }
-    if (q.final_step) {
+    if (final_step) {
 #pragma unroll
         for (int v = 0; v < V; ++v) {
-            float x0 = __builtin_fmaf(q.g, cond[v], (1.0f - q.g) * unc[v]);   // diffusion.py:124-125
+            float x0 = combine(cond[v], unc[v]);
             if constexpr (MASK) x0 = m[v] * x0 + (1.0f - m[v]) * z[v];
             if (ch == 3) x0 += p.sharp;                                   // diffusion.py:88
             if (ch == 0) x0 += p.bright;                                  // diffusion.py:89
@@ -1069,7 +1081,7 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p) 
     if constexpr (MASK) load(eps, p.noise + i);
 #pragma unroll
     for (int v = 0; v < V; ++v) {
-        const float x0 = __builtin_fmaf(q.g, cond[v], (1.0f - q.g) * unc[v]);
+        const float x0 = combine(cond[v], unc[v]);
         const float D = __builtin_fmaf(q.c1, x0, -(q.c2 * prev[v]));      // diffusion.py:76 (c1=1,c2=0: :72/:79)
         float xt = (q.a * D + q.b * xin[v]) / q.c;                        // diffusion.py:81
         if constexpr (MASK) {
@@ -1498,7 +1510,7 @@ namespace {
 bool aligned16(const void* a) { return (reinterpret_cast<uintptr_t>(a) & 15) == 0; }
 }
 
-void launch_sampler_step(const SamplerStepParams& p, int path, hipStream_t s) {
+void launch_sampler_step(const SamplerStepParams& p, int path, hipStream_t s, bool slots) {
     const int n = p.active * p.img;
     // 16-byte accesses: four consecutive elements then share a sample, a channel and one aligned mask quad (null pointers count as aligned)
     const bool vec = p.img % 4 == 0 && p.chan_stride % 4 == 0 && aligned16(p.x0_2b) && aligned16(p.x_t) && aligned16(p.x0_prev) && aligned16(p.out_latent) &&
@@ -1506,7 +1518,15 @@ void launch_sampler_step(const SamplerStepParams& p, int path, hipStream_t s) {
     const int threads = vec ? n / 4 : n;
     const dim3 grid((threads + 255) / 256), block(256);
     note_path(path);
-    if (p.mask) {
+    if (slots) {
+        if (p.mask) {
+            if (vec) hipLaunchKernelGGL((sampler_step_kernel<true, 4, true>), grid, block, 0, s, p);
+            else hipLaunchKernelGGL((sampler_step_kernel<true, 1, true>), grid, block, 0, s, p);
+        } else {
+            if (vec) hipLaunchKernelGGL((sampler_step_kernel<false, 4, true>), grid, block, 0, s, p);
+            else hipLaunchKernelGGL((sampler_step_kernel<false, 1, true>), grid, block, 0, s, p);
+        }
+    } else if (p.mask) {
         if (vec) hipLaunchKernelGGL((sampler_step_kernel<true, 4>), grid, block, 0, s, p);
         else hipLaunchKernelGGL((sampler_step_kernel<true, 1>), grid, block, 0, s, p);
     } else {

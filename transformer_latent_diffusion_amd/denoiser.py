@@ -18,6 +18,7 @@ CPU or eager-PyTorch fallback: calling the model without a HIP device raises.
 from __future__ import annotations
 
 import ctypes as C
+import os
 from collections import OrderedDict
 from typing import Dict, Iterator, Optional
 
@@ -55,6 +56,7 @@ class Denoiser:
         self._engine = None
         self._engine_batch = 0
         self._engine_device = None
+        self._engine_skip = True          # the engine's TLD_GUIDANCE_SKIP, as tld_engine_create read it
         self._gemm_dtype = 0              # 0: bf16 operands; 1: MX-fp8 QKV / MLP GEMMs (set_gemm_dtype)
         self._low_latency = 0             # capacity class for small batches (set_low_latency): 0 default, 1 / 2 = split-K down projection in four / eight splits
         self.training = False
@@ -143,6 +145,7 @@ class Denoiser:
                              self.text_emb_size, self.n_channels, self.mlp_multiplier, cap, dev.index)
         h = C.c_void_p()
         _lib.check(L.tld_engine_create(C.byref(cfg), C.byref(h)), "tld_engine_create")
+        self._engine_skip = self._env_guidance_skip()
         try:
             if self._gemm_dtype:
                 _lib.check(L.tld_engine_set_gemm_dtype(h, self._gemm_dtype), "tld_engine_set_gemm_dtype")
@@ -161,6 +164,17 @@ class Denoiser:
             raise
         self._engine, self._engine_batch, self._engine_device = h, cap, dev
         return h
+
+    @staticmethod
+    def _env_guidance_skip() -> bool:
+        """``TLD_GUIDANCE_SKIP`` as ``tld_engine_create`` reads it (atoi: unset = on, anything but a non-zero integer = off)."""
+        v = os.environ.get("TLD_GUIDANCE_SKIP")
+        if v is None:
+            return True
+        try:
+            return int(v.strip()) != 0
+        except ValueError:
+            return False
 
     def set_gemm_dtype(self, name: str) -> "Denoiser":
         """Operand type of the QKV / MLP GEMMs: ``"bf16"`` (default) or ``"fp8"`` (MX-fp8: e4m3 elements, E8M0 scale
@@ -236,9 +250,9 @@ class Denoiser:
                                   float(bright_f), out, B, tx0, txt, stream), "tld_sample"))
 
     def _run_sampler(self, noise, labels, n_levels: int, trace: bool, call, init_latents=None, mask=None, neg_labels=None, order=None,
-                     new_trace=torch.empty):
+                     new_trace=torch.empty, model_batch=None):
         """What the three sampler entries share around their C call: the device, the ``init_latents`` / ``mask`` shape checks, the empty
-        batch, the engine for the CFG-doubled batch, the operands as contiguous fp32 on the device (rows gathered in ``order`` when the
+        batch, the engine for the CFG-doubled batch (or ``model_batch(engine_skip)``, a guided call's own largest step), the operands as contiguous fp32 on the device (rows gathered in ``order`` when the
         engine wants its own), the result and -- with ``trace`` -- the [n_levels-1,B,C,S,S] trace tensors from ``new_trace``, then
         ``call(engine, B, noise, init_latents, mask, labels, neg_labels, out, trace_x0, trace_xt, stream)`` -- pointers, NULL for an absent
         operand -- under the device context on its current stream.  Results come back in the caller's order."""
@@ -251,7 +265,13 @@ class Denoiser:
         if B == 0:
             z = torch.empty_like(noise, dtype=torch.float32)
             return (z, None, None) if trace else z
-        h = self._ensure_engine(2 * B, dev)
+        if model_batch is None:
+            h = self._ensure_engine(2 * B, dev)
+        else:       # the engine at hand decides with its own TLD_GUIDANCE_SKIP where it is large enough; a new one reads the environment now
+            need = model_batch(self._engine_skip)
+            if self._engine is None or self._engine_batch < need or self._engine_device != dev:
+                need = model_batch(self._env_guidance_skip())
+            h = self._ensure_engine(need, dev)
         idx = None if order is None else torch.tensor(order, device=dev)
 
         def operand(t):
@@ -294,7 +314,7 @@ class Denoiser:
 
     @torch.no_grad()
     def sample_latents_requests(self, noise: torch.Tensor, labels: torch.Tensor, coeff_list, guidance, *, neg_labels=None, init_latents=None,
-                                start_mix=None, mask=None, sharp_f: float = 0.0, bright_f: float = 0.0, trace: bool = False):
+                                start_mix=None, mask=None, sharp_f: float = 0.0, bright_f: float = 0.0, trace: bool = False, guidance_steps=None):
         """B independent requests in one on-device sampler call (tld_sample_requests).
 
         ``noise`` [B,C,S,S], ``labels`` [B,text]; ``coeff_list``: B tables ``schedule.step_coefficients(...)`` (each request's own levels
@@ -303,6 +323,9 @@ class Denoiser:
         ``mask`` [B,1,S,S] as in ``sample_latents_from``; a text-to-image request in a call that carries masks takes an all-ones mask.
         Request b's result equals, bit for bit, ``sample_latents`` / ``sample_latents_from`` of that request alone.  Returns fp32 latents
         [B,C,S,S] in the caller's order; with ``trace`` also [n_max-1,B,C,S,S] predictions and states, zero where a request had finished.
+        ``guidance_steps``: B arrays, request b's guidance per forward (``coeff_list[b].shape[0]`` values, e.g. ``schedule.guidance_table``); the
+        call is then tld_sample_requests_guided: ``guidance`` is ignored (it may be None), a forward whose value is exactly
+        1.0 runs no unconditional sample, and the engine is reserved for the largest step, ``max_i (B_i + U_i)`` samples, instead of 2 B.
         Its own here: the records' checks, the engine's order, the row cap and the negative labels as one tensor; the rest is ``_run_sampler``."""
         from . import schedule
         B = noise.shape[0]
@@ -311,6 +334,12 @@ class Denoiser:
         if tuple(labels.shape) != (B, self.text_emb_size):
             raise ValueError(f"labels {tuple(labels.shape)}: expected {(B, self.text_emb_size)}")
         tabs = [np.ascontiguousarray(c, dtype=np.float32) for c in coeff_list]
+        steps = None
+        if guidance_steps is not None:
+            steps = [np.ascontiguousarray(t, dtype=np.float32) for t in guidance_steps]
+            if len(steps) != B:
+                raise ValueError(f"guidance_steps: {len(steps)} entries for {B} requests")
+            guidance = [1.0] * B
         guid = [float(g) for g in guidance]
         mix = [1.0] * B if start_mix is None else [float(v) for v in start_mix]
         for what, seq in (("coeff_list", tabs), ("guidance", guid), ("start_mix", mix)):
@@ -323,6 +352,10 @@ class Denoiser:
                 raise ValueError(f"guidance[{b}] = {guid[b]} is not finite")
             if not (0.0 < mix[b] <= 1.0):
                 raise ValueError(f"start_mix[{b}] = {mix[b]} outside (0, 1]")
+            if steps is not None and (steps[b].ndim != 1 or steps[b].shape[0] != t.shape[0]):
+                raise ValueError(f"guidance_steps[{b}] {steps[b].shape}: expected [{t.shape[0]}], one value per forward")
+            if steps is not None and not np.isfinite(steps[b]).all():
+                raise ValueError(f"guidance_steps[{b}] holds a value that is not finite")
         if init_latents is None and (mask is not None or any(v < 1.0 for v in mix)):
             raise ValueError("init_latents is required with a mask or with a start_mix < 1")
         neg, has_neg = None, [False] * B
@@ -353,6 +386,23 @@ class Denoiser:
         for k, b in enumerate(order):
             table[k, :counts[b]] = tabs[b]
             recs[k] = _lib.TldSampleRequest(counts[b], guid[b], mix[b], int(has_neg[b]))
+        if steps is not None:
+            gtab = np.zeros((B, n_max), dtype=np.float32)
+            for k, b in enumerate(order):
+                gtab[k, :counts[b]] = steps[b]
+
+            def model_batch(skip):       # the planning the engine repeats in C
+                if not B:
+                    return 0
+                sc = [counts[b] for b in order]
+                U = schedule.guided_rows(sc, [steps[b] for b in order], skip)[0]
+                return max(bi + u for bi, u in zip(schedule.active_prefix(sc), U))
+
+            return self._run_sampler(noise, labels, n_max, trace, lambda h, B, eps, z0, m, lab, ng, out, tx0, txt, stream: _lib.check(
+                _lib.lib().tld_sample_requests_guided(h, eps, z0, m, lab, ng, recs, table.ctypes.data_as(C.POINTER(C.c_float)),
+                                                      gtab.ctypes.data_as(C.POINTER(C.c_float)), n_max, float(sharp_f), float(bright_f), out, B, tx0,
+                                                      txt, stream), "tld_sample_requests_guided"),
+                init_latents=init_latents, mask=mask, neg_labels=neg, order=order, new_trace=torch.zeros, model_batch=model_batch)
         # traces start as zeros: the engine leaves a finished request's slots alone
         return self._run_sampler(noise, labels, n_max, trace, lambda h, B, eps, z0, m, lab, ng, out, tx0, txt, stream: _lib.check(
             _lib.lib().tld_sample_requests(h, eps, z0, m, lab, ng, recs, table.ctypes.data_as(C.POINTER(C.c_float)), n_max, float(sharp_f),
@@ -375,6 +425,13 @@ class Denoiser:
 
     # the launch paths of sample_latents_requests, by bit number
     SAMPLER_PATH_NAMES = {58: "update_requests", 59: "update_requests masked", 60: "start_mix per request"}
+
+    def sample_rows(self):
+        """``(cond, uncond)``: the model samples the last sampler call on this model's engine enqueued (``tld_engine_sample_rows``); the CFG-doubled
+        entries report ``sum(n_levels)`` twice, a guided call ``sum(n_levels)`` and the unconditional samples it did run."""
+        c, u = C.c_int64(), C.c_int64()
+        _lib.check(_lib.lib().tld_engine_sample_rows(self._engine, C.byref(c), C.byref(u)), "tld_engine_sample_rows")
+        return int(c.value), int(u.value)
 
     def set_debug(self, enable: bool = True):
         """Stage capture of the forward (``tld_engine_set_debug``): allocates (frees) the snapshot memory of the current engine."""

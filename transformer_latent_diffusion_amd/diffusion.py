@@ -51,6 +51,30 @@ def stack_optional(v, what: str, B: int, shape: tuple, fill: float):
     return torch.stack([torch.full(shape, fill) if t is None else t.detach().to("cpu", torch.float32) for t in v])
 
 
+def per_request_intervals(v, B: int):
+    """``guidance_interval`` as one entry per request: ``v`` is None, one ``(lo, hi)`` pair of numbers (for all), or a length-B sequence of
+    pairs / None (a request without one is guided throughout).  Returns a list of B ``(lo, hi)`` float pairs / None; ``lo > hi`` raises."""
+    if v is None:
+        return [None] * B
+    v = list(v)
+    if len(v) == 2 and all(isinstance(x, numbers.Number) for x in v):
+        v = [tuple(v)] * B
+    if len(v) != B:
+        raise ValueError(f"guidance_interval: {len(v)} entries for {B} requests")
+    out = []
+    for b, iv in enumerate(v):
+        if iv is None:
+            out.append(None)
+            continue
+        if not isinstance(iv, (tuple, list)) or len(iv) != 2 or not all(isinstance(x, numbers.Number) for x in iv):
+            raise ValueError(f"guidance_interval[{b}] = {iv!r}: expected (lo, hi)")
+        lo, hi = float(iv[0]), float(iv[1])
+        if not (lo <= hi):
+            raise ValueError(f"guidance_interval[{b}] = ({lo}, {hi}): expected lo <= hi")
+        out.append((lo, hi))
+    return out
+
+
 @dataclass
 class DiffusionGenerator:
     model: Denoiser
@@ -74,13 +98,15 @@ class DiffusionGenerator:
         seeds: Optional[Tensor] = None,
         noise_levels=None,
         use_ddpm_plus: bool = True,
+        guidance_interval=None,
     ):
         """Reverse diffusion with classifier-free guidance; returns (decoded_images_on_cpu, latents).
 
         ``use_ddpm_plus=True``: DPM-Solver++(2M); else DDIM with alpha = 1 - sigma (diffusion.py:45-48).
+        ``guidance_interval`` (not in the reference): see ``generate_latents``.
         """
         return self._decode(self.generate_latents(labels, n_iter, num_imgs, class_guidance, seed, img_size, sharp_f, bright_f, exponent,
-                                                  seeds, noise_levels, use_ddpm_plus), scale_factor)
+                                                  seeds, noise_levels, use_ddpm_plus, guidance_interval=guidance_interval), scale_factor)
 
     def _decode(self, latents, scale_factor):
         """The exit edge of the three ``generate*`` (diffusion.py:91): (decoded_images_on_cpu, latents); (None, latents) without a VAE."""
@@ -110,12 +136,19 @@ class DiffusionGenerator:
     @torch.no_grad()
     def generate_latents(self, labels, n_iter=30, num_imgs=16, class_guidance=3, seed=10, img_size=32,
                          sharp_f=0.1, bright_f=0.1, exponent=1, seeds=None, noise_levels=None,
-                         use_ddpm_plus=True, trace=False):
+                         use_ddpm_plus=True, trace=False, guidance_interval=None):
+        """``guidance_interval = (lo, hi)``: limited-interval guidance -- ``class_guidance`` only at the forwards whose noise level lies in
+        [lo, hi], the plain conditional prediction elsewhere, where no unconditional sample is run.  The call is then
+        ``generate_latents_requests`` with B equal requests; None keeps the path of the reference's sampler untouched."""
         coeffs, _ = self._trajectory(n_iter, exponent, noise_levels, None, use_ddpm_plus)
         x_t = self.initialize_image(seeds, num_imgs, img_size, seed)
         if labels.size(0) != x_t.size(0):
             # the reference zips labels and noise by torch.cat (diffusion.py:61,98)
             raise RuntimeError(f"labels batch {labels.size(0)} != num_imgs {x_t.size(0)}")
+        if guidance_interval is not None:
+            return self.generate_latents_requests(labels, n_iter=n_iter, class_guidance=class_guidance, seeds=x_t, img_size=img_size, sharp_f=sharp_f,
+                                                  bright_f=bright_f, exponent=exponent, noise_levels=noise_levels, use_ddpm_plus=use_ddpm_plus,
+                                                  trace=trace, guidance_interval=guidance_interval)
         self.model.eval()
         return self._in_model_dtype(self.model.sample_latents(x_t, labels.to(self.device), coeffs, class_guidance, sharp_f, bright_f,
                                                               trace=trace), trace)
@@ -132,7 +165,7 @@ class DiffusionGenerator:
     @torch.no_grad()
     def generate_latents_from(self, init_latents, labels, strength=0.6, mask=None, n_iter=30, num_imgs=None, class_guidance=3, seed=10,
                               img_size=None, sharp_f=0.1, bright_f=0.1, exponent=1, seeds=None, noise_levels=None, use_ddpm_plus=True,
-                              trace=False):
+                              trace=False, guidance_interval=None):
         """Reverse diffusion that starts from ``init_latents`` [B,C,S,S] (model space: VAE latent / scale_factor, tld/train.py:122)
         instead of pure noise; the other arguments are ``generate_latents``' (``num_imgs`` / ``img_size`` default to the latents' own).
 
@@ -141,7 +174,8 @@ class DiffusionGenerator:
         noise ``generate_latents`` would start from for the same ``seed`` / ``seeds``; 1.0 is the text-to-image trajectory, bit for bit.
         ``mask`` [B,1,S,S] in [0,1] at latent resolution (1 = regenerate, 0 = keep): after every step the kept region is set to the same
         forward process of ``init_latents`` at that step's level, and to ``init_latents`` itself in the final prediction (exactly, where
-        the mask is 0).  Shapes and ranges are checked on the host before anything is enqueued."""
+        the mask is 0).  Shapes and ranges are checked on the host before anything is enqueued.  ``guidance_interval = (lo, hi)``: as in
+        ``generate_latents``, through ``generate_latents_requests`` with B equal requests."""
         if init_latents.dim() != 4:
             raise ValueError(f"init_latents {tuple(init_latents.shape)}: expected [B,C,S,S]")
         B, S = init_latents.shape[0], init_latents.shape[-1]
@@ -158,6 +192,11 @@ class DiffusionGenerator:
             check_mask_range(mask, " (1 = regenerate, 0 = keep)")
         coeffs, start_mix = self._trajectory(n_iter, exponent, noise_levels, strength, use_ddpm_plus)
         eps = self.initialize_image(seeds, num_imgs, img_size, seed)
+        if guidance_interval is not None:
+            return self.generate_latents_requests(labels, n_iter=n_iter, class_guidance=class_guidance, seeds=eps, img_size=img_size, sharp_f=sharp_f,
+                                                  bright_f=bright_f, exponent=exponent, noise_levels=noise_levels, use_ddpm_plus=use_ddpm_plus,
+                                                  init_latents=init_latents, strength=strength, mask=mask, trace=trace,
+                                                  guidance_interval=guidance_interval)
         self.model.eval()
         return self._in_model_dtype(self.model.sample_latents_from(
             eps, init_latents.to(self.device), labels.to(self.device), coeffs, class_guidance, start_mix,
@@ -166,7 +205,7 @@ class DiffusionGenerator:
     @torch.no_grad()
     def generate_latents_requests(self, labels, *, n_iter=30, class_guidance=3, negative_labels=None, seed=10, seeds=None, img_size=None,
                                   sharp_f=0.1, bright_f=0.1, exponent=1, noise_levels=None, use_ddpm_plus=True, init_latents=None,
-                                  strength=None, mask=None, trace=False):
+                                  strength=None, mask=None, trace=False, guidance_interval=None, guidance_schedule=None):
         """B independent requests in ONE sampler call (``Denoiser.sample_latents_requests``): each of ``n_iter``,
         ``class_guidance``, ``exponent``, ``strength`` and ``use_ddpm_plus`` is a scalar (for all) or a length-B sequence.  Request b's latent
         is bit for bit what ``generate_latents`` / ``generate_latents_from`` return for that request alone with the same noise.
@@ -177,6 +216,11 @@ class DiffusionGenerator:
         whole batch as ``generate_latents`` does.  ``init_latents`` [B,C,S,S] with ``strength`` (an entry None or 1.0: the text-to-image
         trajectory) and ``mask`` [B,1,S,S] as in ``generate_latents_from``; a sequence entry None stands for zeros (init) / all ones (mask).
         Each request's schedule comes from ``_trajectory``, the function the solo calls use, so its float64 scalars are exactly theirs.
+        ``guidance_interval``: ``(lo, hi)`` for all, or one pair / None per request -- the request is guided at ``class_guidance`` only at the
+        forwards whose noise level lies in [lo, hi] (``schedule.guidance_table``).  ``guidance_schedule``: one array per request (or None),
+        its guidance per forward, one value per level it runs; it wins over the interval and the scalar.  With either, the call is
+        ``sample_latents_requests(..., guidance_steps=...)``: a forward whose guidance is exactly 1.0 runs no unconditional sample (DESIGN.md
+        section 7.8).
         Shapes and ranges are checked on the host before anything is enqueued."""
         B = labels.size(0)
         size = self.model.image_size if img_size is None else img_size
@@ -207,13 +251,31 @@ class DiffusionGenerator:
             co, s0 = self._trajectory(int(n_it[b]), expo[b], noise_levels, stren[b], bool(plus[b]))
             coeffs.append(co)
             mix.append(s0)
+        steps = None
+        if guidance_interval is not None or guidance_schedule is not None:
+            ivs = per_request_intervals(guidance_interval, B)
+            sched = [None] * B if guidance_schedule is None else list(guidance_schedule)
+            if len(sched) != B:
+                raise ValueError(f"guidance_schedule: {len(sched)} entries for {B} requests")
+            steps = []
+            for b in range(B):
+                if sched[b] is None:
+                    steps.append(schedule.guidance_table(coeffs[b], float(guid[b]), ivs[b]))
+                    continue
+                t = np.ascontiguousarray(torch.as_tensor(sched[b]).detach().cpu().numpy() if isinstance(sched[b], Tensor) else sched[b], dtype=np.float32)
+                if t.ndim != 1 or t.shape[0] != coeffs[b].shape[0]:
+                    raise ValueError(f"guidance_schedule[{b}] {t.shape}: expected [{coeffs[b].shape[0]}], one value per forward")
+                if not np.isfinite(t).all():
+                    raise ValueError(f"guidance_schedule[{b}] holds a value that is not finite")
+                steps.append(t)
         eps = self._noise(seeds, B, size, seed)
         if eps.size(0) != B:
             raise RuntimeError(f"labels batch {B} != noise batch {eps.size(0)}")
         self.model.eval()
+        kw = {} if steps is None else dict(guidance_steps=steps)
         return self._in_model_dtype(self.model.sample_latents_requests(
             eps, labels.to(self.device), coeffs, [float(g) for g in guid], neg_labels=negative_labels, init_latents=z0, start_mix=mix,
-            mask=m, sharp_f=sharp_f, bright_f=bright_f, trace=trace), trace)
+            mask=m, sharp_f=sharp_f, bright_f=bright_f, trace=trace, **kw), trace)
 
     @torch.no_grad()
     def generate_requests(self, labels, *, scale_factor: int = 8, **kw):
@@ -361,7 +423,7 @@ class DiffusionTransformer:
         return self._labels(prompts).cpu()
 
     @torch.no_grad()
-    def generate_images_from_texts(self, prompts, class_guidance=6, seeds=11, n_iter=15, negative_prompts=None):
+    def generate_images_from_texts(self, prompts, class_guidance=6, seeds=11, n_iter=15, negative_prompts=None, guidance_interval=None):
         """Batched front edge (the reference serves one prompt per call, tld/app.py:48-65):
         one text-encoder call for all prompts, labels stay on the device, ONE sampler call (sample-sharded over the
         ranks of the default process group when torch.distributed is initialised), one VAE decode; returns one PIL image
@@ -370,7 +432,9 @@ class DiffusionTransformer:
         ``class_guidance`` / ``n_iter`` may be one value per prompt and ``negative_prompts`` one string (or None) per prompt, or one string
         for all: the sampler call is then ``generate_latents_requests`` (still one call), and a negative
         prompt is encoded with the same text encoder in the same call as the prompts.  Scalars and no negatives call ``generate_latents``;
-        the seeds and noise before the sampler call and the decode and pictures after it are the same code for both."""
+        the seeds and noise before the sampler call and the decode and pictures after it are the same code for both.
+        ``guidance_interval``: ``(lo, hi)`` for all prompts or one pair / None per prompt -- limited-interval guidance
+        (``generate_latents_requests``); the call is then the requests one."""
         from .sharded import sharded_sample
         prompts = list(prompts)
         n = len(prompts)
@@ -380,7 +444,7 @@ class DiffusionTransformer:
         if len(seed_list) != n:
             raise ValueError(f"{len(seed_list)} seeds for {n} prompts")
         gen, size = self.diffuser, self.diffuser.model.image_size
-        if isinstance(class_guidance, numbers.Number) and isinstance(n_iter, numbers.Number) and negative_prompts is None:
+        if isinstance(class_guidance, numbers.Number) and isinstance(n_iter, numbers.Number) and negative_prompts is None and guidance_interval is None:
             labels, extras = self._labels(prompts).to(self.device, torch.float32), ()
 
             def one(xs, ls):
@@ -396,12 +460,14 @@ class DiffusionTransformer:
             guid, n_it = [float(g) for g in per_prompt(class_guidance, "class_guidance")], [int(k) for k in per_prompt(n_iter, "n_iter")]
             labels, neg_rows = self._encode_with_negatives(prompts, negative_prompts)
             extras = (torch.arange(n),)
+            ivs = None if guidance_interval is None else per_request_intervals(guidance_interval, n)
 
             def one(xs, ls, which):           # the per-request scalars ride as the requests' indices, sliced like every per-sample tensor
                 w = [int(i) for i in which]
+                kw = {} if ivs is None else dict(guidance_interval=[ivs[i] for i in w])
                 return gen.generate_latents_requests(ls, n_iter=[n_it[i] for i in w], class_guidance=[guid[i] for i in w],
                                                      negative_labels=None if neg_rows is None else [neg_rows[i] for i in w], seeds=xs, img_size=size,
-                                                     sharp_f=0, bright_f=0, exponent=1)
+                                                     sharp_f=0, bright_f=0, exponent=1, **kw)
 
         x_T = gen._noise(seed_list, n, size, 0)                                          # each request's own noise
         out = gen._decode(sharded_sample(one, x_T, labels, extras=extras), 8)[0]         # scale_factor 8 (diffusion.py:180)
@@ -427,12 +493,17 @@ class DiffusionTransformer:
             k += p is not None
         return emb[:n], rows
 
-    def generate_image_from_text(self, prompt: str, class_guidance=6, seed=11, num_imgs=1, img_size=32, n_iter=15, *, negative_prompt=None):
+    def generate_image_from_text(self, prompt: str, class_guidance=6, seed=11, num_imgs=1, img_size=32, n_iter=15, *, negative_prompt=None,
+                                 guidance_interval=None):
         nrow = int(np.sqrt(num_imgs))
+        giv = {} if guidance_interval is None else dict(guidance_interval=guidance_interval)      # limited-interval guidance
         if negative_prompt is not None:       # the unconditional half of the guidance pair reads the negative prompt's label instead of zeros
             labels, neg = self._encode_with_negatives([prompt] * num_imgs, [negative_prompt] + [None] * (num_imgs - 1))
             out, _ = self.diffuser.generate_requests(labels, negative_labels=[neg[0]] * num_imgs, n_iter=n_iter, class_guidance=class_guidance,
-                                                     seed=seed, exponent=1, scale_factor=8, sharp_f=0, bright_f=0)
+                                                     seed=seed, exponent=1, scale_factor=8, sharp_f=0, bright_f=0, **giv)
+        elif giv:
+            out, _ = self.diffuser.generate_requests(self.encode_text([prompt] * num_imgs), n_iter=n_iter, class_guidance=class_guidance, seed=seed,
+                                                     exponent=1, scale_factor=8, sharp_f=0, bright_f=0, **giv)
         else:
             # NOTE: like the reference, ``img_size`` is ignored in favour of the model's own size (:175)
             out, _ = self.diffuser.generate(
@@ -443,7 +514,7 @@ class DiffusionTransformer:
 
     @torch.no_grad()
     def generate_image_from_image(self, image, prompt: str, strength=0.6, mask=None, class_guidance=6, seed=11, n_iter=15,
-                                  sample_posterior=False, return_latents=False, *, negative_prompt=None):
+                                  sample_posterior=False, return_latents=False, *, negative_prompt=None, guidance_interval=None):
         """Image -> image: edit ``image`` towards ``prompt`` at ``strength``, or with ``mask`` regenerate only the masked region.
 
         ``image``: a PIL image or a [3,H,W] tensor in [0,1] with H = W = 8 x the model's latent size (no resizing here).  It is encoded
@@ -451,7 +522,8 @@ class DiffusionTransformer:
         when ``sample_posterior``) and divided by 8 (tld/train.py:122).  ``mask``: PIL "L" image or tensor [H,W] / [1,H,W] at pixel
         resolution, 1 = regenerate; it is area-averaged to the latent grid (``latent_mask``), so only latent cells whose 8 x 8 pixels are
         all 0 are kept exactly.  Sampler settings as in ``generate_image_from_text``; with ``negative_prompt`` the unconditional half of
-        the guidance pair reads that prompt's label (``generate_requests``).  Returns a PIL image (with ``return_latents``: (image, latents))."""
+        the guidance pair reads that prompt's label (``generate_requests``); ``guidance_interval = (lo, hi)`` guides only at the noise levels
+        inside it (the same entry).  Returns a PIL image (with ``return_latents``: (image, latents))."""
         gen = self.diffuser
         size = gen.model.image_size
         if not isinstance(image, Tensor):
@@ -481,9 +553,10 @@ class DiffusionTransformer:
         else:
             z = dist_.mode()
         z0 = z.to(torch.float32) / 8
-        if neg is not None:
+        if neg is not None or guidance_interval is not None:
+            giv = {} if guidance_interval is None else dict(guidance_interval=guidance_interval)
             out, latents = gen.generate_requests(labels, negative_labels=neg, init_latents=z0, strength=strength, mask=m, n_iter=n_iter,
-                                                 class_guidance=class_guidance, seed=seed, exponent=1, scale_factor=8, sharp_f=0, bright_f=0)
+                                                 class_guidance=class_guidance, seed=seed, exponent=1, scale_factor=8, sharp_f=0, bright_f=0, **giv)
         else:
             out, latents = gen.generate_from(z0, labels, strength=strength, mask=m, n_iter=n_iter, class_guidance=class_guidance, seed=seed,
                                              exponent=1, scale_factor=8, sharp_f=0, bright_f=0)
@@ -519,13 +592,20 @@ class RequestBatcher:
         self.max_batch = int(max_batch)
         self.mixed = bool(mixed)
         self._queue = []
+        self._intervals = {}               # ticket -> (lo, hi) of the requests that brought a guidance interval
         self._next = 0
 
-    def submit(self, prompt: str, class_guidance: float = 6, seed: int = 11, n_iter: int = 15, negative_prompt: Optional[str] = None) -> int:
+    def submit(self, prompt: str, class_guidance: float = 6, seed: int = 11, n_iter: int = 15, negative_prompt: Optional[str] = None,
+               guidance_interval=None) -> int:
         if negative_prompt is not None and not self.mixed:
             raise ValueError("a negative prompt needs RequestBatcher(mixed=True)")
+        if guidance_interval is not None and not self.mixed:
+            raise ValueError("a guidance interval needs RequestBatcher(mixed=True)")
+        interval = per_request_intervals(guidance_interval, 1)[0] if guidance_interval is not None else None
         ticket = self._next
         self._next += 1
+        if interval is not None:
+            self._intervals[ticket] = interval
         self._queue.append(_Request(ticket, str(prompt), float(class_guidance), int(seed), int(n_iter),
                                     None if negative_prompt is None else str(negative_prompt)))
         return ticket
@@ -577,6 +657,8 @@ class RequestBatcher:
                 kw = dict(class_guidance=[r.class_guidance for r in reqs], seeds=[r.seed for r in reqs], n_iter=[r.n_iter for r in reqs])
                 if any(r.negative_prompt is not None for r in reqs):
                     kw["negative_prompts"] = [r.negative_prompt for r in reqs]
+                if any(r.ticket in self._intervals for r in reqs):
+                    kw["guidance_interval"] = [self._intervals.get(r.ticket) for r in reqs]
             else:                             # (class_guidance, n_iter, [(ticket, prompt, seed), ...])
                 g, n, reqs = call
                 kw = dict(class_guidance=g, seeds=[s for _, _, s in reqs], n_iter=n)
@@ -587,5 +669,7 @@ class RequestBatcher:
                 raise
             out.update({r[0]: im for r, im in zip(reqs, imgs)})
             done = {r[0] for r in reqs}
+            for t in done:
+                self._intervals.pop(t, None)
             self._queue = [q for q in self._queue if q.ticket not in done]
         return out

@@ -179,3 +179,48 @@ def distinct_sigma_rows(coeff_list: Sequence[np.ndarray]) -> Tuple[np.ndarray, L
 def request_cond_rows(coeff_list: Sequence[np.ndarray], n_negative: int = 0) -> int:
     """Conditioning rows a call of these requests needs: distinct sigmas + one label row each + the zero row + one per negative label."""
     return len(distinct_sigma_rows(coeff_list)[0]) + len(coeff_list) + 1 + int(n_negative)
+
+
+# ---- one guidance value per forward (tld_sample_requests_guided; DESIGN.md section 7.8) ---------------------------------------------------------
+def guidance_table(coeffs: np.ndarray, class_guidance: float, interval: Optional[Tuple[float, float]] = None) -> np.ndarray:
+    """float32 [n_levels]: a request's guidance per forward under limited-interval guidance -- ``class_guidance`` where the forward's noise
+    level lies inside ``interval = (lo, hi)`` (both edges inclusive), else exactly 1.0, the value at which the engine runs no unconditional
+    sample.  The level of forward i is column 0 of ``step_coefficients``, the float32 sigma the model is conditioned on, and the comparison
+    is made in float32; the last entry belongs to the final prediction.  ``interval`` None: guided throughout."""
+    sig = np.ascontiguousarray(coeffs, dtype=np.float32)
+    if sig.ndim != 2 or sig.shape[1] != 6:
+        raise ValueError(f"coeffs {sig.shape}: expected [n_levels, 6]")
+    g = np.float32(class_guidance)
+    if not np.isfinite(g):
+        raise ValueError(f"class_guidance = {class_guidance} is not finite")
+    if interval is None:
+        return np.full(sig.shape[0], g, dtype=np.float32)
+    lo, hi = (np.float32(v) for v in interval)
+    if not (lo <= hi):
+        raise ValueError(f"guidance interval ({interval[0]}, {interval[1]}): expected lo <= hi")
+    inside = (sig[:, 0] >= lo) & (sig[:, 0] <= hi)
+    return np.where(inside, g, np.float32(1.0)).astype(np.float32)
+
+
+def guided_rows(sorted_counts: Sequence[int], tables: Sequence[np.ndarray], skip: bool = True):
+    """The model batches of a guided call, as the engine plans them: requests in the engine's order (``request_order``) with one guidance
+    table each.  Returns ``(U, slots, src)`` with, per step i over the ``B_i`` requests still running (``active_prefix``): ``U[i]`` the
+    number of unconditional samples, ``slots[i][b]`` the place of request b's among them (compacted in request order) or -1 where
+    ``tables[b][i]`` is exactly 1.0 and it has none, and ``src[i]`` the request each of the ``B_i + U[i]`` model samples reads -- the
+    identity, then the guided requests.  The call makes ``sum(counts) + sum(U)`` model-sample forwards and needs an engine of
+    ``max(B_i + U[i])`` samples.  ``skip`` False (the engine under ``TLD_GUIDANCE_SKIP=0``): every request keeps its unconditional sample."""
+    prefix = active_prefix(sorted_counts)
+    tabs = [np.ascontiguousarray(t, dtype=np.float32) for t in tables]
+    if len(tabs) != len(sorted_counts):
+        raise ValueError(f"{len(tabs)} guidance tables for {len(sorted_counts)} requests")
+    for b, t in enumerate(tabs):
+        if t.ndim != 1 or t.shape[0] != int(sorted_counts[b]):
+            raise ValueError(f"guidance table {b} {t.shape}: expected [{int(sorted_counts[b])}], one value per forward")
+    U, slots, src = [], [], []
+    for i, Bi in enumerate(prefix):
+        guided = [b for b in range(Bi) if not skip or tabs[b][i] != np.float32(1.0)]
+        place = {b: k for k, b in enumerate(guided)}
+        U.append(len(guided))
+        slots.append([place.get(b, -1) for b in range(Bi)])
+        src.append(list(range(Bi)) + guided)
+    return U, slots, src

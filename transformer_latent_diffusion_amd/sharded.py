@@ -18,7 +18,7 @@ from typing import Callable, Optional, Sequence, Tuple
 import torch
 import torch.distributed as dist
 
-from .diffusion import stack_optional
+from .diffusion import per_request_intervals, stack_optional
 
 
 def shard_bounds(total: int, world: int, rank: int) -> Tuple[int, int]:
@@ -111,6 +111,11 @@ def generate_latents_requests_sharded(gen, labels: torch.Tensor, *, group: Optio
     B = labels.shape[0]
     size = gen.model.image_size if img_size is None else img_size
     eps = gen._noise(seeds, B, size, seed)                           # full batch, same on every rank
+    # per-step guidance: one interval / one table per request, picked by index like the other per-request sequences (a single (lo, hi) is for all)
+    if per_request.get("guidance_interval") is not None:
+        per_request["guidance_interval"] = per_request_intervals(per_request["guidance_interval"], B)
+    if per_request.get("guidance_schedule") is not None:
+        per_request["guidance_schedule"] = list(per_request["guidance_schedule"])
 
     def tensor_of(v, what, shape, fill):
         return v if isinstance(v, torch.Tensor) else stack_optional(v, what, B, shape, fill)
