@@ -131,7 +131,7 @@ TLD_API int tld_sample_from(tld_engine* e, const void* noise, const void* init_l
                const float* coeffs, int32_t n_levels, float class_guidance, float sharp_f, float bright_f, void* out_latent,
                int32_t batch, void* trace_x0, void* trace_xt, void* hip_stream);
 
-/* B independent requests in ONE sampler call (DESIGN.md 7.7): every request brings its own guidance scale, its own schedule (levels and their number),
+/* B independent requests in ONE sampler call (DESIGN.md 7.9): every request brings its own guidance scale, its own schedule (levels and their number),
  * an optional negative label in place of the zero "uncond" label of tld/diffusion.py:61, and its own image-to-image start.  It replaces what a serving
  * loop around the reference does one call at a time (tld/app.py:48-65, one prompt, one guidance value, one n_iter per call) and cannot be done from
  * outside here because the loop runs on the device.  Request b's result is bit for bit what tld_sample / tld_sample_from return for that request alone.
@@ -456,9 +456,26 @@ TLD_API int tld_clip_finalize_weights(tld_clip* c);
 /* CLIP.encode_text(text):  tokens [batch, context_length] int32 (device), eot_index [batch] int32 (device) = text.argmax(-1)
  * (the EOT token has the largest id), out [batch, embed_dim] fp32 (device). */
 TLD_API int tld_clip_encode_text(tld_clip* c, const int32_t* tokens, const int32_t* eot_index, float* out, int32_t batch, void* hip_stream);
-/* Test hook: copy a workspace buffer of the LAST encode_text to host fp32 (synchronises): "x", "tmp" ([T, width] fp32), "pooled"
- * ([batch, width]), "h", "att" ([T, width]), "qkv" ([T, 3 width]), "f" ([T, 4 width]) -- the state after the last block. */
-TLD_API int tld_clip_read_buffer(tld_clip* c, const char* name, float* host_out, int64_t numel);
+/* Test hook: stage capture of the text tower, the contract of tld_engine_set_debug.  With debug on, tld_clip_encode_text
+ *   - first fills every workspace buffer (x, tmp, pooled, h, qkv, att, f; all max_batch prompts) with 0xFF bytes -- NaN in bf16 and fp32 -- so that a kernel
+ *     that stores nothing, or too few rows, shows as NaN instead of the previous call's values;
+ *   - keeps every stage of every block: device-to-device copies on the same stream, right after the kernel that completes the value, in the stored type
+ *     (converted to fp32 on read).  Snapshot memory (for max_batch prompts: about 44 width bytes per row per block) is allocated by set_debug(1), which fails
+ *     cleanly (TLD_ERR_HIP, debug stays off) if it cannot be had, and freed by set_debug(0) / destroy; an encode allocates nothing.
+ * With debug off nothing is launched, copied or allocated for the hook, and the output is bitwise the same.  A debug call on a capturing stream is refused
+ * (TLD_ERR_STATE).  Stages hold the LAST encode_text call (T = batch * context_length rows, W = width, E = embed_dim, i = block index):
+ *   x0 [T, W] fp32 (token + positional embedding);
+ *   blk<i>.h1 [T, W] bf16 (ln_1), blk<i>.qkv [T, 3 W] bf16, blk<i>.att [T, W] bf16, blk<i>.attn_out [T, W] fp32 (out_proj without its bias),
+ *   blk<i>.x1 [T, W] fp32 (the stream after the first residual add), blk<i>.h2 [T, W] bf16 (ln_2), blk<i>.f_pre [T, 4 W] bf16 (c_fc + bias, before the
+ *   in-place QuickGELU), blk<i>.f [T, 4 W] bf16, blk<i>.mlp_out [T, W] fp32 (c_proj without its bias), blk<i>.x2 [T, W] fp32 (the stream after the second
+ *   add; absent for the last block, where only the pooled rows are formed);
+ *   pooled [batch, W] fp32 (ln_final of the EOT rows), out [batch, E] fp32;
+ *   operands as the engine holds them, read in place, logical [N][K]: blk<i>.in_w [3 W, W], blk<i>.out_w [W, W], blk<i>.fc_w [4 W, W], blk<i>.proj_w
+ *   [W, 4 W] (bf16) and proj_t [E, W] (fp32, text_projection transposed); these need no debug call.
+ * read_stage: host_out fp32 [numel]; shape4 (may be null) receives (rows, columns, 1, 1) whenever the stage exists; numel must match (TLD_ERR_SHAPE
+ * otherwise); an unknown or uncaptured name is TLD_ERR_KEY.  Synchronises the device. */
+TLD_API int tld_clip_set_debug(tld_clip* c, int32_t enable);
+TLD_API int tld_clip_read_stage(tld_clip* c, const char* name, float* host_out, int64_t numel, int64_t* shape4);
 TLD_API int64_t tld_clip_weight_bytes(const tld_clip* c);
 TLD_API int tld_clip_destroy(tld_clip* c);
 

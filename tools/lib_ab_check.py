@@ -4,6 +4,8 @@ strength-0.65 call, a masked call and the five-request call of tests/test_gpu_re
 outputs of two builds that only re-order work must be BITWISE equal).  One "part <name> <sha1>" line per tensor: equal lines are equal bits.
 Then the VAE: a tiny decoder (latent side 8: one sample per attention step, no fused GroupNorm statistics; side 16: batched attention, fused statistics)
 and a tiny encoder (64 px, fp32 and bf16 input), B = 2 -- the output and every captured stage as parts, plus a "vae <name> weight_bytes ... launches ..." line each.
+Then the CLIP text tower with the stage hook off: encode_text of the cases of tests/test_gpu_clip.py (tiny chunked, ViT-L/14 at 4 prompts, both g13 geometries)
+and of 64 prompts on a two-layer ViT-L/14 tower.
     TLD_LIB=<lib.so> python tools/lib_ab_check.py out.npy"""
 import hashlib, os, sys
 from dataclasses import asdict
@@ -68,6 +70,21 @@ enc = AutoencoderKLEncoder(VaeEncoderConfig(block_out_channels=(64, 128), layers
 img = (torch.randn(2, 3, 64, 64, generator=rg) * 0.6).clamp(-1, 1)
 for dt in (torch.float32, torch.bfloat16):
     vae_parts(f"vae encode {dt}".replace("torch.", ""), enc, enc.moments, img.to(dt).to(dev), enc_stages)
+# the CLIP text tower, debug off: the cases of tests/test_gpu_clip.py and the shipped batch of 64 prompts
+from test_clip_host import TINY, _tokens, load_g13
+from transformer_latent_diffusion_amd.clip_text import ClipTextConfig, ClipTextEncoder, synth_clip_state_dict
+def clip_part(name, ccfg, csd, text, max_batch):
+    ce = ClipTextEncoder(ccfg, max_batch=max_batch)
+    ce.load_state_dict({k: torch.from_numpy(v) for k, v in csd.items()})
+    parts[name] = ce.to(dev).encode_text(text.to(dev)).cpu().numpy()
+    ce._drop_engine()
+clip_part("clip tiny 11 prompts", TINY, synth_clip_state_dict(TINY, 3), _tokens(TINY, 11, 1), 4)
+clip_part("clip l14 4 prompts", ClipTextConfig(), synth_clip_state_dict(ClipTextConfig(), 0), _tokens(ClipTextConfig(), 4, 2), 4)
+for tag in ("tiny", "l14"):
+    gcfg, gsd, gtext, _, _ = load_g13(tag)
+    clip_part(f"clip g13 {tag}", gcfg, gsd, gtext, 8)
+c2 = ClipTextConfig(layers=2)
+clip_part("clip l14 two layers 64 prompts", c2, synth_clip_state_dict(c2, 0), _tokens(c2, 64, 5), 64)
 for name, v in parts.items():
     assert np.isfinite(v).all(), name
     print("part", name, tuple(v.shape), hashlib.sha1(np.ascontiguousarray(v).tobytes()).hexdigest())

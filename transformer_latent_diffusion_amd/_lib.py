@@ -29,7 +29,7 @@ ABI_SYMBOLS = (
     "tld_vae_enc_create", "tld_vae_enc_load_tensor", "tld_vae_enc_finalize_weights", "tld_vae_enc_encode", "tld_vae_enc_set_debug",
     "tld_vae_enc_read_stage", "tld_vae_enc_set_profile", "tld_vae_enc_get_profile", "tld_vae_enc_weight_bytes", "tld_vae_enc_destroy",
     "tld_debug_conv3x3_s2",
-    "tld_clip_create", "tld_clip_load_tensor", "tld_clip_finalize_weights", "tld_clip_encode_text", "tld_clip_read_buffer", "tld_clip_weight_bytes",
+    "tld_clip_create", "tld_clip_load_tensor", "tld_clip_finalize_weights", "tld_clip_encode_text", "tld_clip_set_debug", "tld_clip_read_stage", "tld_clip_weight_bytes",
     "tld_clip_destroy",
     "tld_train_create", "tld_train_param_count", "tld_train_tensor_count", "tld_train_param_layout", "tld_train_set_angular_speeds", "tld_train_bind",
     "tld_train_refresh_weights", "tld_train_forward_backward", "tld_train_forward_backward_cb", "tld_train_adam_ema", "tld_debug_attention_bwd", "tld_debug_wgrad", "tld_debug_attention_fwd", "tld_debug_dwconv_gelu",
@@ -176,7 +176,9 @@ def lib() -> C.CDLL:
     L.tld_clip_load_tensor.argtypes = [vp, C.c_char_p, vp, i64p, i32, i32]
     L.tld_clip_finalize_weights.argtypes = [vp]
     L.tld_clip_encode_text.argtypes = [vp, vp, vp, vp, i32, vp]
-    L.tld_clip_read_buffer.argtypes = [vp, C.c_char_p, C.POINTER(C.c_float), C.c_int64]
+    if hasattr(L, "tld_clip_set_debug"):             # (absent from A/B builds that predate the text tower's stage hook)
+        L.tld_clip_set_debug.argtypes = [vp, i32]
+        L.tld_clip_read_stage.argtypes = [vp, C.c_char_p, C.POINTER(C.c_float), C.c_int64, i64p]
     L.tld_clip_weight_bytes.argtypes = [vp]
     L.tld_clip_weight_bytes.restype = C.c_int64
     L.tld_clip_destroy.argtypes = [vp]

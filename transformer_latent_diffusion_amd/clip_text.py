@@ -106,6 +106,7 @@ class ClipTextEncoder:
         self._device: Optional[torch.device] = None
         self._engine = None
         self._engine_key = None
+        self._debug = False
 
     # ---- nn.Module-like surface ----------------------------------------------------------------------------------
     def eval(self) -> "ClipTextEncoder":
@@ -184,6 +185,31 @@ class ClipTextEncoder:
             L.tld_clip_destroy(h)
             raise
         self._engine, self._engine_key = h, key
+        if self._debug:
+            self._debug = False                     # (a failed allocation leaves the hook off)
+            self.set_debug(True)
+
+    # ---- test hook: stage capture (include/tld_hip.h: tld_clip_set_debug) --------------------------------------------
+    def set_debug(self, on: bool = True):
+        """Keep every stage of every block of the following encode_text calls (snapshot memory for ``max_batch`` prompts is allocated
+        here; a failure raises and leaves the hook off).  Before the engine exists the request is remembered and applied when it is built."""
+        if self._engine is not None:
+            _lib.check(_lib.lib().tld_clip_set_debug(self._engine, int(bool(on))), "tld_clip_set_debug")
+        self._debug = bool(on)
+
+    def read_stage(self, name: str) -> torch.Tensor:
+        """One stage of the last ``tld_clip_encode_text`` call (the last chunk of a chunked encode), fp32 ``[rows, columns]`` on the host."""
+        if self._engine is None:
+            raise RuntimeError("read_stage: no engine yet (encode_text first)")
+        read = _lib.lib().tld_clip_read_stage
+        shape = (C.c_int64 * 4)()
+        probe = np.empty(1, dtype=np.float32)
+        rc = read(self._engine, name.encode(), probe.ctypes.data_as(C.POINTER(C.c_float)), -1, shape)
+        if shape[0] == 0:                           # no such stage: the probe's own status says why
+            _lib.check(rc or 1, f"tld_clip_read_stage({name})")
+        out = np.empty((shape[0], shape[1]), dtype=np.float32)
+        _lib.check(read(self._engine, name.encode(), out.ctypes.data_as(C.POINTER(C.c_float)), out.size, shape), f"tld_clip_read_stage({name})")
+        return torch.from_numpy(out)
 
     @torch.no_grad()
     def encode_text(self, text: torch.Tensor) -> torch.Tensor:

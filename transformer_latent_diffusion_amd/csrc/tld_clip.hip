@@ -19,6 +19,7 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <string>
@@ -191,6 +192,9 @@ __global__ void clip_quickgelu_kernel(bf16* __restrict__ f, long n8) {
 
 struct HostTensor { std::vector<float> data; std::vector<int64_t> shape; };
 
+// one kept stage: `cols` values per row in the stored type; per_prompt: [batch] rows instead of [batch * ctx]
+struct Snap { std::string name; void* dev = nullptr; int cols = 0; bool is_bf16 = false, per_prompt = false, valid = false; };
+
 struct Block {
     float *ln1_g = nullptr, *ln1_b = nullptr, *ln2_g = nullptr, *ln2_b = nullptr;
     bf16 *in_w = nullptr, *out_w = nullptr, *fc_w = nullptr, *proj_w = nullptr;
@@ -211,6 +215,10 @@ struct tld_clip {
     // workspace (max_batch * ctx rows)
     float *x = nullptr, *tmp = nullptr, *pooled = nullptr;
     bf16 *h = nullptr, *qkv = nullptr, *att = nullptr, *f = nullptr;
+    // stage capture (tld_clip_set_debug): snapshot memory for max_batch prompts, allocated by set_debug(1), freed by set_debug(0) / destroy
+    bool debug = false;
+    int dbg_batch = 0;                        // batch of the last debug encode (rows of the stages: dbg_batch * ctx, or dbg_batch)
+    std::vector<Snap> snaps;
 };
 
 namespace {
@@ -259,6 +267,27 @@ void gemm(const bf16* A, int lda, const bf16* Wt, int M, int N, int K, int epi, 
     if (epi == EPI_BIAS_BF16) { p.out_bf16 = out_bf16; p.ldo = N; }
     else { p.c_f32 = out_f32; p.ldc = N; }
     launch_gemm(p, epi, s);
+}
+
+
+void free_snaps(tld_clip* c) {
+    for (Snap& sn : c->snaps) (void)hipFree(sn.dev);
+    c->snaps.clear();
+    c->debug = false;
+    c->dbg_batch = 0;
+}
+Snap* find_snap(tld_clip* c, const std::string& name) {
+    for (Snap& sn : c->snaps) if (sn.name == name) return &sn;
+    return nullptr;
+}
+// same-stream copy of the rows of this call into the stage's snapshot (debug only)
+int keep(tld_clip* c, const std::string& name, const void* src, int batch, hipStream_t s) {
+    Snap* sn = find_snap(c, name);
+    if (!sn) return fail(TLD_ERR_STATE, "stage '%s' has no snapshot memory", name.c_str());
+    const size_t rows = sn->per_prompt ? (size_t)batch : (size_t)batch * c->ctx;
+    HIP_TRY(hipMemcpyAsync(sn->dev, src, rows * sn->cols * (sn->is_bf16 ? 2 : 4), hipMemcpyDeviceToDevice, s));
+    sn->valid = true;
+    return TLD_OK;
 }
 
 }  // namespace
@@ -363,6 +392,23 @@ int tld_clip_encode_text(tld_clip* c, const int32_t* tokens, const int32_t* eot_
     DeviceGuard guard(c->cfg.device_id);
     hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
     const int W = c->W, ctx = c->ctx, T = batch * ctx;
+    const bool dbg = c->debug;
+    if (dbg) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone)
+            return fail(TLD_ERR_STATE, "a debug encode (tld_clip_set_debug) cannot be captured into a graph");
+        for (Snap& sn : c->snaps) sn.valid = false;
+        c->dbg_batch = batch;
+        const size_t TW = (size_t)c->cfg.max_batch * ctx * W;        // the whole workspace: NaN in bf16 and fp32 wherever this call stores nothing
+        HIP_TRY(hipMemsetAsync(c->x, 0xFF, TW * 4, s));
+        HIP_TRY(hipMemsetAsync(c->tmp, 0xFF, TW * 4, s));
+        HIP_TRY(hipMemsetAsync(c->pooled, 0xFF, (size_t)c->cfg.max_batch * W * 4, s));
+        HIP_TRY(hipMemsetAsync(c->h, 0xFF, TW * 2, s));
+        HIP_TRY(hipMemsetAsync(c->qkv, 0xFF, TW * 3 * 2, s));
+        HIP_TRY(hipMemsetAsync(c->att, 0xFF, TW * 2, s));
+        HIP_TRY(hipMemsetAsync(c->f, 0xFF, TW * 4 * 2, s));
+    }
+#define KEEP(name, src) do { if (dbg) { if (int rc_ = keep(c, name, src, batch, s)) return rc_; } } while (0)
     {
         const long n = (long)T * W;
         hipLaunchKernelGGL(clip_embed_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, tokens, c->tok_emb, c->pos, c->x, T, W, ctx, c->V);
@@ -371,48 +417,109 @@ int tld_clip_encode_text(tld_clip* c, const int32_t* tokens, const int32_t* eot_
     const size_t attn_lds = (size_t)(ctx * 64 * 2 + ctx * 65 + 128) * sizeof(float);
     static PerDeviceOnce attr_set;
     attr_set.run([&] { hipFuncSetAttribute(reinterpret_cast<const void*>(clip_attn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * (64 * 2 + 65) * 4 + 512); });
+    KEEP("x0", c->x);
     hipLaunchKernelGGL(clip_add_ln_kernel, rows, dim3(256), 0, s, c->x, (const float*)nullptr, (const float*)nullptr, c->blocks[0].ln1_g, c->blocks[0].ln1_b, c->h, T, W);
     for (int l = 0; l < c->L; ++l) {
         const Block& b = c->blocks[l];
+        const std::string pre = dbg ? "blk" + std::to_string(l) + "." : std::string();
+        KEEP(pre + "h1", c->h);
         gemm(c->h, W, b.in_w, T, 3 * W, W, EPI_BIAS_BF16, b.in_b, c->qkv, nullptr, s);
+        KEEP(pre + "qkv", c->qkv);
         hipLaunchKernelGGL(clip_attn_kernel, dim3(c->H, batch), dim3(64), attn_lds, s, c->qkv, c->att, ctx, W);
+        KEEP(pre + "att", c->att);
         gemm(c->att, W, b.out_w, T, W, W, EPI_F32, nullptr, nullptr, c->tmp, s);
+        KEEP(pre + "attn_out", c->tmp);
         hipLaunchKernelGGL(clip_add_ln_kernel, rows, dim3(256), 0, s, c->x, c->tmp, b.out_b, b.ln2_g, b.ln2_b, c->h, T, W);
+        KEEP(pre + "x1", c->x);
+        KEEP(pre + "h2", c->h);
         gemm(c->h, W, b.fc_w, T, 4 * W, W, EPI_BIAS_BF16, b.fc_b, c->f, nullptr, s);
+        KEEP(pre + "f_pre", c->f);
         {
             const long n8 = (long)T * 4 * W / 8;
             hipLaunchKernelGGL(clip_quickgelu_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, c->f, n8);
         }
+        KEEP(pre + "f", c->f);
         gemm(c->f, 4 * W, b.proj_w, T, W, 4 * W, EPI_F32, nullptr, nullptr, c->tmp, s);
-        if (l + 1 < c->L)
+        KEEP(pre + "mlp_out", c->tmp);
+        if (l + 1 < c->L) {
             hipLaunchKernelGGL(clip_add_ln_kernel, rows, dim3(256), 0, s, c->x, c->tmp, b.proj_b, c->blocks[l + 1].ln1_g, c->blocks[l + 1].ln1_b, c->h, T, W);
-        else
+            KEEP(pre + "x2", c->x);
+        } else {
             hipLaunchKernelGGL(clip_final_ln_kernel, dim3(batch), dim3(64), 0, s, c->x, c->tmp, b.proj_b, eot_index, c->lnf_g, c->lnf_b, c->pooled, W, ctx);
+            KEEP("pooled", c->pooled);
+        }
     }
     launch_linear_f32(c->pooled, W, c->proj_t, nullptr, out, c->E, batch, W, c->E, 0, s);
+    KEEP("out", out);
+#undef KEEP
     return check_launch("encode_text");
 }
 
-int tld_clip_read_buffer(tld_clip* c, const char* name, float* host_out, int64_t numel) {
+int tld_clip_set_debug(tld_clip* c, int32_t enable) {
+    if (!c) return fail(TLD_ERR_INVALID, "null handle");
+    DeviceGuard guard(c->cfg.device_id);
+    if (!enable) { free_snaps(c); return TLD_OK; }
+    if (c->debug) return TLD_OK;
+    const size_t B = (size_t)c->cfg.max_batch, T = B * c->ctx;
+    auto add = [&](const std::string& name, int cols, bool is_bf16, bool per_prompt) {
+        Snap sn;
+        sn.name = name; sn.cols = cols; sn.is_bf16 = is_bf16; sn.per_prompt = per_prompt;
+        if (hipMalloc(&sn.dev, (per_prompt ? B : T) * cols * (is_bf16 ? 2 : 4)) != hipSuccess) { (void)hipGetLastError(); return false; }
+        c->snaps.push_back(sn);
+        return true;
+    };
+    const int W = c->W;
+    bool ok = add("x0", W, false, false);
+    for (int l = 0; ok && l < c->L; ++l) {
+        const std::string pre = "blk" + std::to_string(l) + ".";
+        ok = add(pre + "h1", W, true, false) && add(pre + "qkv", 3 * W, true, false) && add(pre + "att", W, true, false) &&
+             add(pre + "attn_out", W, false, false) && add(pre + "x1", W, false, false) && add(pre + "h2", W, true, false) &&
+             add(pre + "f_pre", 4 * W, true, false) && add(pre + "f", 4 * W, true, false) && add(pre + "mlp_out", W, false, false) &&
+             (l + 1 == c->L || add(pre + "x2", W, false, false));              // the last block forms only the pooled rows
+    }
+    ok = ok && add("pooled", W, false, true) && add("out", c->E, false, true);
+    if (!ok) {
+        free_snaps(c);
+        return fail(TLD_ERR_HIP, "tld_clip_set_debug: no memory for the stage snapshots of %d prompts x %d layers; debug stays off", c->cfg.max_batch, c->L);
+    }
+    c->debug = true;
+    return TLD_OK;
+}
+
+int tld_clip_read_stage(tld_clip* c, const char* name, float* host_out, int64_t numel, int64_t* shape4) {
     if (!c || !name || !host_out) return fail(TLD_ERR_INVALID, "null argument");
     DeviceGuard guard(c->cfg.device_id);
-    HIP_TRY(hipDeviceSynchronize());
     const std::string n(name);
-    {   // bound the read by the buffer's size (workspace is sized for max_batch * context_length rows)
-        const int64_t TW = (int64_t)c->cfg.max_batch * c->ctx * c->W;
-        const int64_t cap = n == "pooled" ? (int64_t)c->cfg.max_batch * c->W : n == "qkv" ? 3 * TW : n == "f" ? 4 * TW : TW;
-        if (numel <= 0 || numel > cap) return fail(TLD_ERR_INVALID, "numel %lld outside (0, %lld] for buffer '%s'", (long long)numel, (long long)cap, name);
+    const void* src = nullptr;
+    int64_t rows = 0, cols = 0;
+    bool is_bf16 = false;
+    if (n == "proj_t") { if (c->finalized) { src = c->proj_t; rows = c->E; cols = c->W; } }
+    else if (n.rfind("blk", 0) == 0 && n.size() > 2 && n.compare(n.size() - 2, 2, "_w") == 0) {      // operands as the engine holds them, logical [N][K]
+        const size_t dot = n.find('.');
+        const std::string idx = dot == std::string::npos ? "" : n.substr(3, dot - 3), w = dot == std::string::npos ? "" : n.substr(dot + 1);
+        int l = -1;
+        if (!idx.empty() && idx.size() <= 3 && idx.find_first_not_of("0123456789") == std::string::npos) l = atoi(idx.c_str());
+        if (c->finalized && l >= 0 && l < c->L && std::to_string(l) == idx) {
+            const Block& b = c->blocks[l];
+            const int64_t W = c->W;
+            is_bf16 = true;
+            if (w == "in_w") { src = b.in_w; rows = 3 * W; cols = W; }
+            else if (w == "out_w") { src = b.out_w; rows = W; cols = W; }
+            else if (w == "fc_w") { src = b.fc_w; rows = 4 * W; cols = W; }
+            else if (w == "proj_w") { src = b.proj_w; rows = W; cols = 4 * W; }
+        }
+    } else if (Snap* sn = find_snap(c, n)) {
+        if (sn->valid) { src = sn->dev; rows = sn->per_prompt ? c->dbg_batch : (int64_t)c->dbg_batch * c->ctx; cols = sn->cols; is_bf16 = sn->is_bf16; }
     }
-    const float* f32 = n == "x" ? c->x : n == "tmp" ? c->tmp : n == "pooled" ? c->pooled : nullptr;
-    const bf16* b16 = n == "h" ? c->h : n == "qkv" ? c->qkv : n == "att" ? c->att : n == "f" ? c->f : nullptr;
-    if (f32) { HIP_TRY(hipMemcpy(host_out, f32, (size_t)numel * 4, hipMemcpyDeviceToHost)); return TLD_OK; }
-    if (b16) {
-        std::vector<uint16_t> t((size_t)numel);
-        HIP_TRY(hipMemcpy(t.data(), b16, (size_t)numel * 2, hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < numel; ++i) { const uint32_t u = (uint32_t)t[i] << 16; memcpy(host_out + i, &u, 4); }
-        return TLD_OK;
-    }
-    return fail(TLD_ERR_KEY, "no buffer named '%s' (x, tmp, pooled, h, qkv, att, f)", name);
+    if (!src) return fail(TLD_ERR_KEY, "no captured stage named '%s' (set_debug before encode_text?)", name);
+    if (shape4) { shape4[0] = rows; shape4[1] = cols; shape4[2] = 1; shape4[3] = 1; }
+    if (rows * cols != numel) return fail(TLD_ERR_SHAPE, "stage '%s' has %lld elements, caller passed %lld", name, (long long)(rows * cols), (long long)numel);
+    HIP_TRY(hipDeviceSynchronize());
+    if (!is_bf16) { HIP_TRY(hipMemcpy(host_out, src, (size_t)numel * 4, hipMemcpyDeviceToHost)); return TLD_OK; }
+    std::vector<uint16_t> t((size_t)numel);
+    HIP_TRY(hipMemcpy(t.data(), src, (size_t)numel * 2, hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < numel; ++i) { const uint32_t u = (uint32_t)t[i] << 16; memcpy(host_out + i, &u, 4); }
+    return TLD_OK;
 }
 
 int64_t tld_clip_weight_bytes(const tld_clip* c) { return c ? c->weight_bytes : 0; }
@@ -420,6 +527,7 @@ int64_t tld_clip_weight_bytes(const tld_clip* c) { return c ? c->weight_bytes : 
 int tld_clip_destroy(tld_clip* c) {
     if (!c) return TLD_OK;
     DeviceGuard guard(c->cfg.device_id);
+    free_snaps(c);
     for (void* p : c->allocs) (void)hipFree(p);
     delete c;
     return TLD_OK;
