@@ -184,12 +184,36 @@ TLD_API int tld_sample_requests_guided(tld_engine* e, const void* noise, const v
  * report sum(n_levels) twice; tld_sample_requests_guided reports (sum(n_levels), sum(U_i)) */
 TLD_API int tld_engine_sample_rows(tld_engine* e, int64_t* cond, int64_t* uncond);
 
-/* Test hook: stage capture of the inference forward (what tld_train_set_debug is to the training step).  With debug on, a forward
+/* THE STAGE HOOK: one contract behind tld_engine_ / tld_vae_ / tld_vae_enc_ / tld_clip_ / tld_train_ set_debug and read_stage (one implementation:
+ * StageStore, csrc/tld_host.h).  set_debug(1) turns capture on, and twice is harmless; the engine's next calls keep named stages: the
+ * engine's own buffers read in place, or device-to-device copies taken on the call's stream right after the kernel that completed the value, in
+ * the stored type.  Every call forgets the copies of the call before it.  set_debug(0) and destroy free all of it.  read_stage converts a stage to
+ * fp32 in its logical shape on the host and synchronises the device:
+ *   TLD_ERR_KEY    the name is unknown or not captured (debug off, no debug call yet, a stage of another path);
+ *   TLD_ERR_SHAPE  numel differs from the stage's element count: host_out is untouched; shape4, where the entry has one and it is not null,
+ *                  holds the logical shape whenever the stage exists (unused trailing dimensions 1);
+ *   TLD_ERR_STATE  from the CALL, when a copy finds no reserved memory (set_debug(1) before the engine's mode was chosen).
+ * tld_debug_decode_stage is the store's decoder alone, for the CPU suite.  The blocks below list only what is each engine's own: its names, what it
+ * poisons and when its snapshot memory is taken. */
+#define TLD_STAGE_F32 0
+#define TLD_STAGE_BF16 1
+#define TLD_STAGE_U8 2        /* raw bytes */
+#define TLD_STAGE_MX8S 3      /* E8M0 scale bytes stored [cols / 4][rows][4], logical [rows, cols] */
+#define TLD_STAGE_MX8W 4      /* e4m3 codes [rows, cols] with scales `aux` [cols / 128][rows][4]: code x 2^(scale - 127) */
+#define TLD_STAGE_PLAIN 0
+#define TLD_STAGE_QKV_ROWS 1  /* 3 d rows in the fused QKV -> attention kernel's packed order -> [q; k; v] x [head][64] */
+#define TLD_STAGE_NHWC 2      /* logical (B, C, H, W) stored [B][H][W][C] */
+/* raw (host copy of the stored bytes; with outer_stride != 0: shape4[0] runs of shape4[1..3] elements, outer_stride elements apart) -> out fp32 [numel]
+ * in logical order.  aux: TLD_STAGE_MX8W only; d, heads: TLD_STAGE_QKV_ROWS only.  No device is touched.  TLD_ERR_INVALID: a null pointer or an
+ * impossible combination; TLD_ERR_SHAPE: numel is not the product of shape4. */
+TLD_API int tld_debug_decode_stage(const void* raw, const void* aux, int32_t dtype, int32_t layout, const int64_t* shape4, int64_t outer_stride,
+                                   int32_t d, int32_t heads, float* out, int64_t numel);
+
+/* The inference forward's stages.  With debug on, a forward
  * (tld_denoiser_forward, or every step of tld_sample / tld_sample_from)
  *   - first fills every engine-owned activation, statistics, seam and split-K buffer -- and, once per call, the conditioning tables -- with 0xFF bytes
  *     (NaN in bf16 and fp32), so that a kernel that stores nothing, or too few rows, shows as NaN instead of the previous call's values;
- *   - keeps every stage of every block: device-to-device copies on the same stream, right after the kernel that completes the value, in the stored
- *     type (bf16 or fp32; converted to fp32 on read).  Snapshot memory (for max_batch samples) is allocated by set_debug(1), which fails cleanly
+ *   - keeps every stage of every block.  Snapshot memory (for max_batch samples) is allocated by set_debug(1), which fails cleanly
  *     (TLD_ERR_HIP, debug stays off) if it cannot be had, and freed by set_debug(0) / destroy; a forward allocates nothing.  Call set_debug(1) after
  *     tld_engine_set_low_latency;
  *   - records which launch path every size-dependent dispatch took (tld_engine_debug_paths).
@@ -234,7 +258,6 @@ TLD_API int tld_engine_sample_rows(tld_engine* e, int64_t* cond, int64_t* uncond
  *   tld_sample_requests: 58 update_requests without a mask   59 update_requests with a mask   60 start_mix per request */
 #define TLD_ENGINE_PATH_BITS 61
 TLD_API int tld_engine_set_debug(tld_engine* e, int32_t enable);
-/* host_out fp32 [numel]; numel must match the stage (TLD_ERR_SHAPE otherwise).  Synchronises the device. */
 TLD_API int tld_engine_read_stage(tld_engine* e, const char* name, float* host_out, int64_t numel);
 /* logical shape of a captured stage: 4 int64, unused trailing dimensions 1 */
 TLD_API int tld_engine_stage_shape(tld_engine* e, const char* name, int64_t* shape4);
@@ -359,8 +382,8 @@ TLD_API int tld_vae_finalize_weights(tld_vae* v);
  *   out  [batch, out_channels, 8h, 8w]    device, fp32 (2^(n_blocks-1) x upsampling) */
 TLD_API int tld_vae_decode(tld_vae* v, const void* z, float* out, int32_t batch, int32_t io_dtype, void* hip_stream);
 
-/* Test hook: with debug enabled, decode keeps a copy of the activation after every stage; read_stage converts one to
- * host fp32 [batch, C, H, W].  names: "conv_in", "mid.res0", "mid.attn", "mid.res1", "up<i>.res<j>", "up<i>.upsample",
+/* The decoder's stages (the stage hook above): bf16 NHWC copies of the activation after every stage, read as fp32 [batch, C, H, W]; their memory is
+ * taken at capture, since the sizes follow the call's resolution.  names: "conv_in", "mid.res0", "mid.attn", "mid.res1", "up<i>.res<j>", "up<i>.upsample",
  * "norm_out".  shape4 (optional) receives batch, C, H, W. */
 TLD_API int tld_vae_set_debug(tld_vae* v, int32_t enable);
 TLD_API int tld_vae_read_stage(tld_vae* v, const char* name, float* host_out, int64_t numel, int64_t* shape4);
@@ -412,7 +435,7 @@ TLD_API int tld_vae_enc_finalize_weights(tld_vae_enc* e);
  *   x        [batch, in_channels, S, S]                 device, io_dtype (already mapped to [-1, 1] by the caller)
  *   moments  [batch, 2 latent_channels, S/2^(n-1), S/2^(n-1)]  device, fp32 (mean, then logvar before its clamp) */
 TLD_API int tld_vae_enc_encode(tld_vae_enc* e, const void* x, float* moments, int32_t batch, int32_t io_dtype, void* hip_stream);
-/* Test hook as tld_vae_set_debug / read_stage.  names: "conv_in", "down<i>.res<j>", "down<i>.downsample", "mid.res0", "mid.attn",
+/* The encoder's stages, as the decoder's.  names: "conv_in", "down<i>.res<j>", "down<i>.downsample", "mid.res0", "mid.attn",
  * "mid.res1", "norm_out" (after SiLU). */
 TLD_API int tld_vae_enc_set_debug(tld_vae_enc* e, int32_t enable);
 TLD_API int tld_vae_enc_read_stage(tld_vae_enc* e, const char* name, float* host_out, int64_t numel, int64_t* shape4);
@@ -456,11 +479,10 @@ TLD_API int tld_clip_finalize_weights(tld_clip* c);
 /* CLIP.encode_text(text):  tokens [batch, context_length] int32 (device), eot_index [batch] int32 (device) = text.argmax(-1)
  * (the EOT token has the largest id), out [batch, embed_dim] fp32 (device). */
 TLD_API int tld_clip_encode_text(tld_clip* c, const int32_t* tokens, const int32_t* eot_index, float* out, int32_t batch, void* hip_stream);
-/* Test hook: stage capture of the text tower, the contract of tld_engine_set_debug.  With debug on, tld_clip_encode_text
+/* The text tower's stages (the stage hook above).  With debug on, tld_clip_encode_text
  *   - first fills every workspace buffer (x, tmp, pooled, h, qkv, att, f; all max_batch prompts) with 0xFF bytes -- NaN in bf16 and fp32 -- so that a kernel
  *     that stores nothing, or too few rows, shows as NaN instead of the previous call's values;
- *   - keeps every stage of every block: device-to-device copies on the same stream, right after the kernel that completes the value, in the stored type
- *     (converted to fp32 on read).  Snapshot memory (for max_batch prompts: about 44 width bytes per row per block) is allocated by set_debug(1), which fails
+ *   - keeps every stage of every block.  Snapshot memory (for max_batch prompts: about 44 width bytes per row per block) is allocated by set_debug(1), which fails
  *     cleanly (TLD_ERR_HIP, debug stays off) if it cannot be had, and freed by set_debug(0) / destroy; an encode allocates nothing.
  * With debug off nothing is launched, copied or allocated for the hook, and the output is bitwise the same.  A debug call on a capturing stream is refused
  * (TLD_ERR_STATE).  Stages hold the LAST encode_text call (T = batch * context_length rows, W = width, E = embed_dim, i = block index):
@@ -471,9 +493,8 @@ TLD_API int tld_clip_encode_text(tld_clip* c, const int32_t* tokens, const int32
  *   add; absent for the last block, where only the pooled rows are formed);
  *   pooled [batch, W] fp32 (ln_final of the EOT rows), out [batch, E] fp32;
  *   operands as the engine holds them, read in place, logical [N][K]: blk<i>.in_w [3 W, W], blk<i>.out_w [W, W], blk<i>.fc_w [4 W, W], blk<i>.proj_w
- *   [W, 4 W] (bf16) and proj_t [E, W] (fp32, text_projection transposed); these need no debug call.
- * read_stage: host_out fp32 [numel]; shape4 (may be null) receives (rows, columns, 1, 1) whenever the stage exists; numel must match (TLD_ERR_SHAPE
- * otherwise); an unknown or uncaptured name is TLD_ERR_KEY.  Synchronises the device. */
+ *   [W, 4 W] (bf16) and proj_t [E, W] (fp32, text_projection transposed); these are named from finalize_weights on and need no debug call.
+ * shape4 receives (rows, columns, 1, 1). */
 TLD_API int tld_clip_set_debug(tld_clip* c, int32_t enable);
 TLD_API int tld_clip_read_stage(tld_clip* c, const char* name, float* host_out, int64_t numel, int64_t* shape4);
 TLD_API int64_t tld_clip_weight_bytes(const tld_clip* c);
@@ -541,11 +562,11 @@ TLD_API int tld_debug_attention_fwd(const void* qk, const void* vt, void* att, i
  * would pick for that grid (whole-image / tiled / row-streaming).  channels % 64 == 0; grid <= 16 or a multiple of 16. */
 TLD_API int tld_debug_dwconv_gelu(const void* in_bf16, const float* weight_host, const float* bias_host, void* out_bf16, int32_t batch,
                                   int32_t grid, int32_t channels, void* hip_stream);
-/* Test hook: stage capture of the training step (the training engine's tld_vae_set_debug / tld_vae_read_stage).  With debug on, one
+/* The training step's stages (the stage hook above).  With debug on, one
  * tld_train_forward_backward call
  *   - first fills every engine-owned activation / statistics / scratch / partial-sum buffer and the bound gradient vector with 0xFF bytes
  *     (NaN in bf16 and fp32), so that a kernel that stores nothing, or too few rows, shows as NaN instead of the previous call's values;
- *   - keeps what the backward overwrites: device-to-device copies on the same stream, right after the kernel that completes the value.
+ *   - keeps what the backward overwrites.
  *     Snapshot memory (for max_batch samples) is allocated by set_debug(1), which fails if it cannot be had, and freed by set_debug(0) / destroy;
  *     create allocates none, a step allocates none;
  *   - records which launch path every size-dependent dispatch took (tld_train_debug_paths).
@@ -567,7 +588,7 @@ TLD_API int tld_debug_dwconv_gelu(const void* in_bf16, const float* weight_host,
  *   28 attention backward one kernel   29 two kernels   30 masked (token count not a multiple of the block) */
 #define TLD_TRAIN_PATH_BITS 31
 TLD_API int tld_train_set_debug(tld_train* e, int32_t enable);
-/* host_out fp32 [numel] (numel must match the stage); shape_out: 4 int64, unused trailing dimensions 1; may be NULL.  host_out NULL: only the shape. */
+/* shape_out may be NULL; host_out NULL: only the shape. */
 TLD_API int tld_train_read_stage(tld_train* e, const char* name, float* host_out, int64_t numel, int64_t* shape_out);
 /* mask of the launch paths the last debug call took */
 TLD_API int tld_train_debug_paths(tld_train* e, uint64_t* mask);

@@ -6,6 +6,8 @@ Then the VAE: a tiny decoder (latent side 8: one sample per attention step, no f
 and a tiny encoder (64 px, fp32 and bf16 input), B = 2 -- the output and every captured stage as parts, plus a "vae <name> weight_bytes ... launches ..." line each.
 Then the CLIP text tower with the stage hook off: encode_text of the cases of tests/test_gpu_clip.py (tiny chunked, ViT-L/14 at 4 prompts, both g13 geometries)
 and of 64 prompts on a two-layer ViT-L/14 tower.
+Then the stage hooks ON: one forward of the tiny denoiser, one encode of the tiny text tower and one tiny training step (loss, gradient vector), each with
+every stage its header block names as a part ("absent <name>" where the engine's path has no such stage).
     TLD_LIB=<lib.so> python tools/lib_ab_check.py out.npy"""
 import hashlib, os, sys
 from dataclasses import asdict
@@ -85,7 +87,39 @@ for tag in ("tiny", "l14"):
     clip_part(f"clip g13 {tag}", gcfg, gsd, gtext, 8)
 c2 = ClipTextConfig(layers=2)
 clip_part("clip l14 two layers 64 prompts", c2, synth_clip_state_dict(c2, 0), _tokens(c2, 64, 5), 64)
+# the stage hooks on: every stage name of include/tld_hip.h is tried, so a stage that appears or disappears shows as a changed line
+staged = set()
+def stage_parts(tag, names, read):
+    for n in names:
+        try:
+            parts[f"{tag} {n}"] = np.asarray(read(n), np.float32)
+            staged.add(f"{tag} {n}")                         # (a stage may hold the poison where its kernel stores nothing: no finiteness check)
+        except RuntimeError:
+            print("absent", tag, n)
+mt.reserve(2); mt.set_debug(True)
+parts["tiny debug forward"] = mt(eps[:2].to(dev), torch.tensor([[0.3], [0.8]]).to(dev), labels[:2].to(dev)).cpu().numpy()
+blk = ("x_in ln1 xn1 qk vt att sa ca stats xn3 hid_pre hid splitk mlp wqkv wup wdown qkv_c1 qkv_b1 up_c1 up_b1").split()
+stage_parts("tiny stage", ["tokens0", "out"] + [f"cond.{n}" for n in "sin h1 pre y kv wq bwq".split()] + [f"blk{i}.{n}" for i in range(ct.n_layers) for n in blk],
+            mt.read_stage)
+mt.set_debug(False)
+ce = ClipTextEncoder(TINY, max_batch=4)
+ce.load_state_dict({k: torch.from_numpy(v) for k, v in synth_clip_state_dict(TINY, 3).items()})
+ce.to(dev).set_debug(True)
+parts["clip tiny debug encode"] = ce.encode_text(_tokens(TINY, 3, 1).to(dev)).cpu().numpy()
+cblk = "h1 qkv att attn_out x1 h2 f_pre f mlp_out x2 in_w out_w fc_w proj_w".split()
+stage_parts("clip stage", ["x0", "pooled", "out", "proj_t"] + [f"blk{i}.{n}" for i in range(TINY.layers) for n in cblk], lambda n: ce.read_stage(n).numpy())
+ce._drop_engine()
+from transformer_latent_diffusion_amd import Trainer
+tr = Trainer(ct, device=dev, state_dict={k: torch.from_numpy(np.array(v)) for k, v in sdt.items()}, max_batch=2).set_debug(True)
+loss, pred = tr.forward_backward((0.6 * z0[:2] + 0.4 * eps[:2]).contiguous(), torch.tensor([0.4, 0.7]), labels[:2], z0[:2])
+torch.cuda.synchronize()
+parts["train loss"] = loss.float().cpu().numpy().reshape(-1); parts["train prediction"] = pred.float().cpu().numpy(); parts["train gradients"] = tr.grads.cpu().numpy()
+tblk = ("x1 a1 qk vt att x2 a2 qc cr x3 a3 h hc o st1 st2 st3 p0 kvc wqkv wq wup wdown wqkv_t wq_t wup_t wdown_t gl gx.in dg dhc dh da3 gx.ln3 dqc dkv da2 gx.ln2 dqkv da1 "
+        "gx.ln1 gxb.ln1").split()
+stage_parts("train stage", "sinb h1 g1v ycat y yst p16 p16n est1 e est2 xfin dout row_loss gx.tail gxb.tail dy de dpn dp16 dycat dg1".split() +
+            [f"blk{i}.{n}" for i in range(ct.n_layers) for n in tblk], lambda n: tr.read_stage(n).numpy())
+tr.set_debug(False)
 for name, v in parts.items():
-    assert np.isfinite(v).all(), name
+    assert name in staged or np.isfinite(v).all(), name
     print("part", name, tuple(v.shape), hashlib.sha1(np.ascontiguousarray(v).tobytes()).hexdigest())
 np.save(sys.argv[1], np.concatenate([v.reshape(-1) for v in parts.values()]))

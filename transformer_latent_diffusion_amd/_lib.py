@@ -21,7 +21,7 @@ KERNEL_CLASSES = ("gemm_qkv", "gemm_up", "gemm_down", "attention", "cross_row", 
 ABI_SYMBOLS = (
     "tld_engine_create", "tld_engine_load_tensor", "tld_engine_finalize_weights", "tld_denoiser_forward",
     "tld_sample", "tld_sample_from", "tld_sample_requests", "tld_sample_requests_guided", "tld_engine_sample_rows", "tld_engine_set_gemm_dtype", "tld_engine_set_low_latency", "tld_debug_gemm_splitk", "tld_debug_quant_mx8", "tld_debug_quant_mx8_host", "tld_debug_gemm_mx8",
-    "tld_engine_set_debug", "tld_engine_read_stage", "tld_engine_stage_shape", "tld_engine_set_debug_step", "tld_engine_debug_paths", "tld_debug_gemm_bf16", "tld_debug_gemm_bench", "tld_debug_gemm_plan", "tld_debug_gemm_epilogue",
+    "tld_debug_decode_stage", "tld_engine_set_debug", "tld_engine_read_stage", "tld_engine_stage_shape", "tld_engine_set_debug_step", "tld_engine_debug_paths", "tld_debug_gemm_bf16", "tld_debug_gemm_bench", "tld_debug_gemm_plan", "tld_debug_gemm_epilogue",
     "tld_engine_set_profile", "tld_engine_profile_reserve", "tld_engine_get_profile", "tld_engine_weight_bytes", "tld_engine_destroy",
     "tld_vae_create", "tld_vae_load_tensor", "tld_vae_finalize_weights", "tld_vae_decode", "tld_vae_set_debug",
     "tld_vae_read_stage", "tld_vae_set_profile", "tld_vae_get_profile", "tld_debug_conv3x3", "tld_vae_weight_bytes",
@@ -129,6 +129,8 @@ def lib() -> C.CDLL:
     L.tld_debug_quant_mx8.argtypes = [vp, vp, vp, i32, i32, vp]
     L.tld_debug_quant_mx8_host.argtypes = [C.POINTER(C.c_float), i32, i32, vp, vp]
     L.tld_debug_gemm_mx8.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp]
+    if hasattr(L, "tld_debug_decode_stage"):         # (absent from A/B builds that predate the shared stage store)
+        L.tld_debug_decode_stage.argtypes = [vp, vp, i32, i32, i64p, C.c_int64, i32, i32, C.POINTER(C.c_float), C.c_int64]
     L.tld_engine_set_debug.argtypes = [vp, i32]
     L.tld_engine_read_stage.argtypes = [vp, C.c_char_p, C.POINTER(C.c_float), C.c_int64]
     if hasattr(L, "tld_engine_stage_shape"):         # (absent from A/B builds that predate the per-block stage hook)

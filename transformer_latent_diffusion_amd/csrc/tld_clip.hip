@@ -15,6 +15,7 @@
 // ~13 GFLOP per prompt: this path is about removing the host round trip, not about its own speed.
 #include "../../include/tld_hip.h"
 #include "tld_common.h"
+#include "tld_host.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -28,42 +29,6 @@
 using namespace tld;
 
 namespace {
-
-int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    set_last_error(buf);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t _e = (expr);                                                                    \
-        if (_e != hipSuccess)                                                                      \
-            return fail(TLD_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
-
-inline uint16_t f32_to_bf16_rne(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-
-struct DeviceGuard {
-    int prev = -1; bool switched = false;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
-        else if (prev < 0) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
-    DeviceGuard(const DeviceGuard&) = delete;
-    DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
 
 // ---- kernels -----------------------------------------------------------------------------------------------------------
 
@@ -190,11 +155,6 @@ __global__ void clip_quickgelu_kernel(bf16* __restrict__ f, long n8) {
     *reinterpret_cast<bf16x8*>(f + i * 8) = v;
 }
 
-struct HostTensor { std::vector<float> data; std::vector<int64_t> shape; };
-
-// one kept stage: `cols` values per row in the stored type; per_prompt: [batch] rows instead of [batch * ctx]
-struct Snap { std::string name; void* dev = nullptr; int cols = 0; bool is_bf16 = false, per_prompt = false, valid = false; };
-
 struct Block {
     float *ln1_g = nullptr, *ln1_b = nullptr, *ln2_g = nullptr, *ln2_b = nullptr;
     bf16 *in_w = nullptr, *out_w = nullptr, *fc_w = nullptr, *proj_w = nullptr;
@@ -203,13 +163,11 @@ struct Block {
 
 }  // namespace
 
-struct tld_clip {
+struct tld_clip : DeviceArena {
     tld_clip_config cfg{};
     int W = 0, L = 0, H = 0, ctx = 0, E = 0, V = 0;
     bool finalized = false;
     std::map<std::string, HostTensor> host;
-    std::vector<void*> allocs;
-    int64_t weight_bytes = 0;
     float *tok_emb = nullptr, *pos = nullptr, *lnf_g = nullptr, *lnf_b = nullptr, *proj_t = nullptr;     // proj_t: text_projection^T [E][W]
     std::vector<Block> blocks;
     // workspace (max_batch * ctx rows)
@@ -217,33 +175,11 @@ struct tld_clip {
     bf16 *h = nullptr, *qkv = nullptr, *att = nullptr, *f = nullptr;
     // stage capture (tld_clip_set_debug): snapshot memory for max_batch prompts, allocated by set_debug(1), freed by set_debug(0) / destroy
     bool debug = false;
-    int dbg_batch = 0;                        // batch of the last debug encode (rows of the stages: dbg_batch * ctx, or dbg_batch)
-    std::vector<Snap> snaps;
+    StageStore stages;                        // the stage hook (tld_host.h); the operands are named in it from finalize_weights on
 };
 
 namespace {
 
-template <typename T>
-int dev_alloc(tld_clip* c, T** out, size_t count, bool weight = false) {
-    void* p = nullptr;
-    HIP_TRY(hipMalloc(&p, count * sizeof(T) > 0 ? count * sizeof(T) : 16));
-    c->allocs.push_back(p);
-    if (weight) c->weight_bytes += (int64_t)(count * sizeof(T));
-    *out = reinterpret_cast<T*>(p);
-    return TLD_OK;
-}
-int upload_f32(tld_clip* c, const std::vector<float>& hv, float** out) {
-    if (int rc = dev_alloc(c, out, hv.size(), true)) return rc;
-    HIP_TRY(hipMemcpy(*out, hv.data(), hv.size() * sizeof(float), hipMemcpyHostToDevice));
-    return TLD_OK;
-}
-int upload_bf16(tld_clip* c, const std::vector<float>& hv, bf16** out) {
-    std::vector<uint16_t> t(hv.size());
-    for (size_t i = 0; i < hv.size(); ++i) t[i] = f32_to_bf16_rne(hv[i]);
-    if (int rc = dev_alloc(c, out, hv.size(), true)) return rc;
-    HIP_TRY(hipMemcpy(*out, t.data(), t.size() * 2, hipMemcpyHostToDevice));
-    return TLD_OK;
-}
 int need(const tld_clip* c, const std::string& key, const std::vector<int64_t>& shape, const HostTensor** out) {
     auto it = c->host.find(key);
     if (it == c->host.end()) return fail(TLD_ERR_STATE, "missing state_dict entry '%s'", key.c_str());
@@ -256,38 +192,30 @@ int need(const tld_clip* c, const std::string& key, const std::vector<int64_t>& 
     *out = &it->second;
     return TLD_OK;
 }
-int check_launch(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(TLD_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
-    return TLD_OK;
-}
-void gemm(const bf16* A, int lda, const bf16* Wt, int M, int N, int K, int epi, const float* bias, bf16* out_bf16, float* out_f32, hipStream_t s) {
+int gemm(const bf16* A, int lda, const bf16* Wt, int M, int N, int K, int epi, const float* bias, bf16* out_bf16, float* out_f32, hipStream_t s) {
     GemmParams p{};
     p.A = A; p.lda = lda; p.W = Wt; p.ldw = K; p.M = M; p.N = N; p.K = K; p.bias = bias;
     if (epi == EPI_BIAS_BF16) { p.out_bf16 = out_bf16; p.ldo = N; }
     else { p.c_f32 = out_f32; p.ldc = N; }
-    launch_gemm(p, epi, s);
+    return launch_gemm(p, epi, s);
 }
 
-
-void free_snaps(tld_clip* c) {
-    for (Snap& sn : c->snaps) (void)hipFree(sn.dev);
-    c->snaps.clear();
+// the GEMM operands as the engine holds them, logical [N][K], read in place: named once the weights exist, whether or not the hook is on
+void name_operands(tld_clip* c) {
+    const int64_t W = c->W;
+    c->stages.ref("proj_t", c->proj_t, ST_F32, c->E, W);
+    for (int l = 0; l < (int)c->blocks.size(); ++l) {
+        const Block& b = c->blocks[l];
+        const std::string pre = "blk" + std::to_string(l) + ".";
+        c->stages.ref(pre + "in_w", b.in_w, ST_BF16, 3 * W, W); c->stages.ref(pre + "out_w", b.out_w, ST_BF16, W, W);
+        c->stages.ref(pre + "fc_w", b.fc_w, ST_BF16, 4 * W, W); c->stages.ref(pre + "proj_w", b.proj_w, ST_BF16, W, 4 * W);
+    }
+}
+// set_debug(0) / destroy: the snapshots go, the operand names stay
+void drop_snapshots(tld_clip* c) {
+    c->stages.free_all();
     c->debug = false;
-    c->dbg_batch = 0;
-}
-Snap* find_snap(tld_clip* c, const std::string& name) {
-    for (Snap& sn : c->snaps) if (sn.name == name) return &sn;
-    return nullptr;
-}
-// same-stream copy of the rows of this call into the stage's snapshot (debug only)
-int keep(tld_clip* c, const std::string& name, const void* src, int batch, hipStream_t s) {
-    Snap* sn = find_snap(c, name);
-    if (!sn) return fail(TLD_ERR_STATE, "stage '%s' has no snapshot memory", name.c_str());
-    const size_t rows = sn->per_prompt ? (size_t)batch : (size_t)batch * c->ctx;
-    HIP_TRY(hipMemcpyAsync(sn->dev, src, rows * sn->cols * (sn->is_bf16 ? 2 : 4), hipMemcpyDeviceToDevice, s));
-    sn->valid = true;
-    return TLD_OK;
+    if (c->finalized) name_operands(c);
 }
 
 }  // namespace
@@ -382,6 +310,7 @@ int tld_clip_finalize_weights(tld_clip* c) {
     c->host.clear();
     HIP_TRY(hipDeviceSynchronize());
     c->finalized = true;
+    name_operands(c);
     return TLD_OK;
 }
 
@@ -397,8 +326,7 @@ int tld_clip_encode_text(tld_clip* c, const int32_t* tokens, const int32_t* eot_
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone)
             return fail(TLD_ERR_STATE, "a debug encode (tld_clip_set_debug) cannot be captured into a graph");
-        for (Snap& sn : c->snaps) sn.valid = false;
-        c->dbg_batch = batch;
+        c->stages.begin_call();
         const size_t TW = (size_t)c->cfg.max_batch * ctx * W;        // the whole workspace: NaN in bf16 and fp32 wherever this call stores nothing
         HIP_TRY(hipMemsetAsync(c->x, 0xFF, TW * 4, s));
         HIP_TRY(hipMemsetAsync(c->tmp, 0xFF, TW * 4, s));
@@ -408,7 +336,8 @@ int tld_clip_encode_text(tld_clip* c, const int32_t* tokens, const int32_t* eot_
         HIP_TRY(hipMemsetAsync(c->att, 0xFF, TW * 2, s));
         HIP_TRY(hipMemsetAsync(c->f, 0xFF, TW * 4 * 2, s));
     }
-#define KEEP(name, src) do { if (dbg) { if (int rc_ = keep(c, name, src, batch, s)) return rc_; } } while (0)
+#define KEEP(name, src, dtype, rows, cols) do { if (dbg) { if (int rc_ = c->stages.copy(name, src, dtype, s, rows, cols)) return rc_; } } while (0)
+#define GEMM(what, ...) GEMM_TRY("tld_clip_encode_text, block " + std::to_string(l) + " " what, gemm(__VA_ARGS__))
     {
         const long n = (long)T * W;
         hipLaunchKernelGGL(clip_embed_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, tokens, c->tok_emb, c->pos, c->x, T, W, ctx, c->V);
@@ -417,69 +346,65 @@ int tld_clip_encode_text(tld_clip* c, const int32_t* tokens, const int32_t* eot_
     const size_t attn_lds = (size_t)(ctx * 64 * 2 + ctx * 65 + 128) * sizeof(float);
     static PerDeviceOnce attr_set;
     attr_set.run([&] { hipFuncSetAttribute(reinterpret_cast<const void*>(clip_attn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * (64 * 2 + 65) * 4 + 512); });
-    KEEP("x0", c->x);
+    KEEP("x0", c->x, ST_F32, T, W);
     hipLaunchKernelGGL(clip_add_ln_kernel, rows, dim3(256), 0, s, c->x, (const float*)nullptr, (const float*)nullptr, c->blocks[0].ln1_g, c->blocks[0].ln1_b, c->h, T, W);
     for (int l = 0; l < c->L; ++l) {
         const Block& b = c->blocks[l];
         const std::string pre = dbg ? "blk" + std::to_string(l) + "." : std::string();
-        KEEP(pre + "h1", c->h);
-        gemm(c->h, W, b.in_w, T, 3 * W, W, EPI_BIAS_BF16, b.in_b, c->qkv, nullptr, s);
-        KEEP(pre + "qkv", c->qkv);
+        KEEP(pre + "h1", c->h, ST_BF16, T, W);
+        GEMM("in_proj", c->h, W, b.in_w, T, 3 * W, W, EPI_BIAS_BF16, b.in_b, c->qkv, nullptr, s);
+        KEEP(pre + "qkv", c->qkv, ST_BF16, T, 3 * W);
         hipLaunchKernelGGL(clip_attn_kernel, dim3(c->H, batch), dim3(64), attn_lds, s, c->qkv, c->att, ctx, W);
-        KEEP(pre + "att", c->att);
-        gemm(c->att, W, b.out_w, T, W, W, EPI_F32, nullptr, nullptr, c->tmp, s);
-        KEEP(pre + "attn_out", c->tmp);
+        KEEP(pre + "att", c->att, ST_BF16, T, W);
+        GEMM("out_proj", c->att, W, b.out_w, T, W, W, EPI_F32, nullptr, nullptr, c->tmp, s);
+        KEEP(pre + "attn_out", c->tmp, ST_F32, T, W);
         hipLaunchKernelGGL(clip_add_ln_kernel, rows, dim3(256), 0, s, c->x, c->tmp, b.out_b, b.ln2_g, b.ln2_b, c->h, T, W);
-        KEEP(pre + "x1", c->x);
-        KEEP(pre + "h2", c->h);
-        gemm(c->h, W, b.fc_w, T, 4 * W, W, EPI_BIAS_BF16, b.fc_b, c->f, nullptr, s);
-        KEEP(pre + "f_pre", c->f);
+        KEEP(pre + "x1", c->x, ST_F32, T, W);
+        KEEP(pre + "h2", c->h, ST_BF16, T, W);
+        GEMM("c_fc", c->h, W, b.fc_w, T, 4 * W, W, EPI_BIAS_BF16, b.fc_b, c->f, nullptr, s);
+        KEEP(pre + "f_pre", c->f, ST_BF16, T, 4 * W);
         {
             const long n8 = (long)T * 4 * W / 8;
             hipLaunchKernelGGL(clip_quickgelu_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, c->f, n8);
         }
-        KEEP(pre + "f", c->f);
-        gemm(c->f, 4 * W, b.proj_w, T, W, 4 * W, EPI_F32, nullptr, nullptr, c->tmp, s);
-        KEEP(pre + "mlp_out", c->tmp);
+        KEEP(pre + "f", c->f, ST_BF16, T, 4 * W);
+        GEMM("c_proj", c->f, 4 * W, b.proj_w, T, W, 4 * W, EPI_F32, nullptr, nullptr, c->tmp, s);
+        KEEP(pre + "mlp_out", c->tmp, ST_F32, T, W);
         if (l + 1 < c->L) {
             hipLaunchKernelGGL(clip_add_ln_kernel, rows, dim3(256), 0, s, c->x, c->tmp, b.proj_b, c->blocks[l + 1].ln1_g, c->blocks[l + 1].ln1_b, c->h, T, W);
-            KEEP(pre + "x2", c->x);
+            KEEP(pre + "x2", c->x, ST_F32, T, W);
         } else {
             hipLaunchKernelGGL(clip_final_ln_kernel, dim3(batch), dim3(64), 0, s, c->x, c->tmp, b.proj_b, eot_index, c->lnf_g, c->lnf_b, c->pooled, W, ctx);
-            KEEP("pooled", c->pooled);
+            KEEP("pooled", c->pooled, ST_F32, batch, W);
         }
     }
     launch_linear_f32(c->pooled, W, c->proj_t, nullptr, out, c->E, batch, W, c->E, 0, s);
-    KEEP("out", out);
+    KEEP("out", out, ST_F32, batch, c->E);
 #undef KEEP
+#undef GEMM
     return check_launch("encode_text");
 }
 
 int tld_clip_set_debug(tld_clip* c, int32_t enable) {
     if (!c) return fail(TLD_ERR_INVALID, "null handle");
     DeviceGuard guard(c->cfg.device_id);
-    if (!enable) { free_snaps(c); return TLD_OK; }
+    if (!enable) { drop_snapshots(c); return TLD_OK; }
     if (c->debug) return TLD_OK;
-    const size_t B = (size_t)c->cfg.max_batch, T = B * c->ctx;
-    auto add = [&](const std::string& name, int cols, bool is_bf16, bool per_prompt) {
-        Snap sn;
-        sn.name = name; sn.cols = cols; sn.is_bf16 = is_bf16; sn.per_prompt = per_prompt;
-        if (hipMalloc(&sn.dev, (per_prompt ? B : T) * cols * (is_bf16 ? 2 : 4)) != hipSuccess) { (void)hipGetLastError(); return false; }
-        c->snaps.push_back(sn);
-        return true;
-    };
-    const int W = c->W;
-    bool ok = add("x0", W, false, false);
-    for (int l = 0; ok && l < c->L; ++l) {
+    // memory for every stage of max_batch prompts: T rows per block stage, one row per prompt for the pooled row and the output
+    const size_t B = (size_t)c->cfg.max_batch, T = B * c->ctx, W = c->W;
+    int rc = c->stages.reserve("x0", T * W * 4);
+    for (int l = 0; !rc && l < c->L; ++l) {
         const std::string pre = "blk" + std::to_string(l) + ".";
-        ok = add(pre + "h1", W, true, false) && add(pre + "qkv", 3 * W, true, false) && add(pre + "att", W, true, false) &&
-             add(pre + "attn_out", W, false, false) && add(pre + "x1", W, false, false) && add(pre + "h2", W, true, false) &&
-             add(pre + "f_pre", 4 * W, true, false) && add(pre + "f", 4 * W, true, false) && add(pre + "mlp_out", W, false, false) &&
-             (l + 1 == c->L || add(pre + "x2", W, false, false));              // the last block forms only the pooled rows
+        for (const char* n : {"h1", "att", "h2"}) if (!rc) rc = c->stages.reserve(pre + n, T * W * 2);
+        for (const char* n : {"attn_out", "x1", "mlp_out"}) if (!rc) rc = c->stages.reserve(pre + n, T * W * 4);
+        if (!rc) rc = c->stages.reserve(pre + "qkv", T * 3 * W * 2);
+        for (const char* n : {"f_pre", "f"}) if (!rc) rc = c->stages.reserve(pre + n, T * 4 * W * 2);
+        if (!rc && l + 1 < c->L) rc = c->stages.reserve(pre + "x2", T * W * 4);              // the last block forms only the pooled rows
     }
-    ok = ok && add("pooled", W, false, true) && add("out", c->E, false, true);
-    if (!ok) {
-        free_snaps(c);
+    if (!rc) rc = c->stages.reserve("pooled", B * W * 4);
+    if (!rc) rc = c->stages.reserve("out", B * c->E * 4);
+    if (rc) {
+        drop_snapshots(c);
         return fail(TLD_ERR_HIP, "tld_clip_set_debug: no memory for the stage snapshots of %d prompts x %d layers; debug stays off", c->cfg.max_batch, c->L);
     }
     c->debug = true;
@@ -489,37 +414,7 @@ int tld_clip_set_debug(tld_clip* c, int32_t enable) {
 int tld_clip_read_stage(tld_clip* c, const char* name, float* host_out, int64_t numel, int64_t* shape4) {
     if (!c || !name || !host_out) return fail(TLD_ERR_INVALID, "null argument");
     DeviceGuard guard(c->cfg.device_id);
-    const std::string n(name);
-    const void* src = nullptr;
-    int64_t rows = 0, cols = 0;
-    bool is_bf16 = false;
-    if (n == "proj_t") { if (c->finalized) { src = c->proj_t; rows = c->E; cols = c->W; } }
-    else if (n.rfind("blk", 0) == 0 && n.size() > 2 && n.compare(n.size() - 2, 2, "_w") == 0) {      // operands as the engine holds them, logical [N][K]
-        const size_t dot = n.find('.');
-        const std::string idx = dot == std::string::npos ? "" : n.substr(3, dot - 3), w = dot == std::string::npos ? "" : n.substr(dot + 1);
-        int l = -1;
-        if (!idx.empty() && idx.size() <= 3 && idx.find_first_not_of("0123456789") == std::string::npos) l = atoi(idx.c_str());
-        if (c->finalized && l >= 0 && l < c->L && std::to_string(l) == idx) {
-            const Block& b = c->blocks[l];
-            const int64_t W = c->W;
-            is_bf16 = true;
-            if (w == "in_w") { src = b.in_w; rows = 3 * W; cols = W; }
-            else if (w == "out_w") { src = b.out_w; rows = W; cols = W; }
-            else if (w == "fc_w") { src = b.fc_w; rows = 4 * W; cols = W; }
-            else if (w == "proj_w") { src = b.proj_w; rows = W; cols = 4 * W; }
-        }
-    } else if (Snap* sn = find_snap(c, n)) {
-        if (sn->valid) { src = sn->dev; rows = sn->per_prompt ? c->dbg_batch : (int64_t)c->dbg_batch * c->ctx; cols = sn->cols; is_bf16 = sn->is_bf16; }
-    }
-    if (!src) return fail(TLD_ERR_KEY, "no captured stage named '%s' (set_debug before encode_text?)", name);
-    if (shape4) { shape4[0] = rows; shape4[1] = cols; shape4[2] = 1; shape4[3] = 1; }
-    if (rows * cols != numel) return fail(TLD_ERR_SHAPE, "stage '%s' has %lld elements, caller passed %lld", name, (long long)(rows * cols), (long long)numel);
-    HIP_TRY(hipDeviceSynchronize());
-    if (!is_bf16) { HIP_TRY(hipMemcpy(host_out, src, (size_t)numel * 4, hipMemcpyDeviceToHost)); return TLD_OK; }
-    std::vector<uint16_t> t((size_t)numel);
-    HIP_TRY(hipMemcpy(t.data(), src, (size_t)numel * 2, hipMemcpyDeviceToHost));
-    for (int64_t i = 0; i < numel; ++i) { const uint32_t u = (uint32_t)t[i] << 16; memcpy(host_out + i, &u, 4); }
-    return TLD_OK;
+    return c->stages.read(name, host_out, numel, shape4);
 }
 
 int64_t tld_clip_weight_bytes(const tld_clip* c) { return c ? c->weight_bytes : 0; }
@@ -527,7 +422,7 @@ int64_t tld_clip_weight_bytes(const tld_clip* c) { return c ? c->weight_bytes : 
 int tld_clip_destroy(tld_clip* c) {
     if (!c) return TLD_OK;
     DeviceGuard guard(c->cfg.device_id);
-    free_snaps(c);
+    drop_snapshots(c);
     for (void* p : c->allocs) (void)hipFree(p);
     delete c;
     return TLD_OK;

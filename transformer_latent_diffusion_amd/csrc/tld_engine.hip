@@ -6,6 +6,7 @@
 // with no host round trip.  See DESIGN.md for the data layout and per-kernel roofline notes.
 #include "../../include/tld_hip.h"
 #include "tld_common.h"
+#include "tld_host.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -20,57 +21,13 @@
 using namespace tld;
 
 namespace {
-
 thread_local char g_err[512] = "";
-
-int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
 }  // namespace
 namespace tld {
 void set_last_error(const char* msg) { snprintf(g_err, sizeof(g_err), "%s", msg); }
 thread_local uint64_t* g_path_sink = nullptr;
 }  // namespace tld
 namespace {
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t _e = (expr);                                                                    \
-        if (_e != hipSuccess)                                                                      \
-            return fail(TLD_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
-
-inline uint16_t f32_to_bf16_rne(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-
-// Every ABI entry point runs with the engine's device current and puts the caller's device back on exit: the
-// library never changes the calling thread's current HIP device (a model on cuda:1 used from a thread whose
-// current device is cuda:0 would otherwise silently redirect the caller's later allocations and launches).
-struct DeviceGuard {
-    int prev = -1; bool switched = false;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
-        else if (prev < 0) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
-    DeviceGuard(const DeviceGuard&) = delete;
-    DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
-
-struct HostTensor {
-    std::vector<float> data;
-    std::vector<int64_t> shape;
-};
 
 struct Layer {
     bf16 *qkv_w = nullptr, *up_w = nullptr, *down_w = nullptr;
@@ -89,25 +46,13 @@ struct Layer {
     float *kv_w = nullptr, *q_w = nullptr;   // fp32, conditioning path
 };
 
-// stage hook (tld_engine_set_debug): a named tensor in its stored type, read in place (the engine's own buffer) or from a copy the hook owns.
-// Tables with a per-layer pitch (the conditioning tables) are `outer` runs of shape[1..3] elements, `outer_stride` elements apart.
-// fp8 mode: ST_U8 = raw bytes (the e4m3 codes of an A operand), ST_MX8S = E8M0 scale bytes stored [K/128][rows][4], logical shape [rows, K/32] (the
-// layout is undone on read), ST_MX8W = an e4m3 weight [N, K] read in place with its scales (`aux`, [K/128][N][4]) and dequantised on the host
-enum { ST_F32 = 0, ST_BF16 = 1, ST_U8 = 2, ST_MX8S = 3, ST_MX8W = 4 };
-inline size_t st_bytes(int dtype) { return dtype == ST_F32 ? 4 : dtype == ST_BF16 ? 2 : 1; }
-enum { UNPACK_NONE = 0, UNPACK_QKV_ROWS = 1 };      // rows stored in the fused QKV -> attention kernel's [head][feature half][q | k | v][32] order
-struct DbgStage {
-    void* ptr = nullptr; const void* aux = nullptr; int dtype = ST_F32; int64_t shape[4] = {1, 1, 1, 1};
-    bool owned = false; size_t cap = 0; bool live = false;
-    int64_t outer_stride = 0; int unpack = UNPACK_NONE;
-};
-
 enum KClass { KC_GEMM_QKV = 0, KC_GEMM_UP, KC_GEMM_DOWN, KC_ATTN, KC_CROSS, KC_DWCONV, KC_LN, KC_EMBED,
               KC_TAIL, KC_UPDATE, KC_COND, KC_COUNT };
 
 }  // namespace
 
-struct tld_engine {
+struct tld_engine : DeviceArena {      // (pad = 256: every allocation of this engine carries 256 bytes of over-read margin)
+    tld_engine() { pad = 256; }
     tld_config cfg{};
     int d = 0, L = 0, H = 0, ntok = 0, grid = 0, pd = 0, hid = 0, img = 0, ne = 0, text = 0;
     bool finalized = false;
@@ -116,8 +61,6 @@ struct tld_engine {
     bool fp8_fused = true;              // TLD_FP8_FUSED=0: separate quantisation passes instead of quantising producers (A/B testing)
     uint8_t *a8 = nullptr, *as8 = nullptr;   // fp8 mode: quantised A operand [M, hid] and its block scales [hid/128][M][4]
     std::map<std::string, HostTensor> host;
-    std::vector<void*> allocs;
-    int64_t weight_bytes = 0;
 
     // fp32 parameters
     float *angular = nullptr, *ff1_w = nullptr, *ff1_b = nullptr, *ff3_w = nullptr, *ff3_b = nullptr;
@@ -167,9 +110,8 @@ struct tld_engine {
     bool debug = false;
     bool dbg_keep = false;             // the running body's stages are kept (debug on, and the sampler is at the debug step)
     int dbg_step = -1;                 // sampler step whose stages are kept (tld_engine_set_debug_step); < 0: every step, so the last one remains
-    int dbg_batch = 0, dbg_T = 0;
     uint64_t paths = 0;                // launch paths of the last debug call
-    std::map<std::string, DbgStage> stages;
+    StageStore stages;                 // the stage hook (tld_host.h)
     std::vector<std::pair<void*, size_t>> poison;      // activation / statistics / seam / split-K buffers a debug forward fills with 0xFF first
 
     // per-class event profiling
@@ -181,15 +123,6 @@ struct tld_engine {
 };
 
 namespace {
-
-template <typename T>
-int dev_alloc(tld_engine* e, T** p, size_t count) {
-    void* q = nullptr;
-    HIP_TRY(hipMalloc(&q, count * sizeof(T) + 256));
-    e->allocs.push_back(q);
-    *p = reinterpret_cast<T*>(q);
-    return TLD_OK;
-}
 
 int upload_f32(tld_engine* e, const char* key, float** dst, int64_t expect) {
     auto it = e->host.find(key);
@@ -284,47 +217,8 @@ struct ProfScope {
 constexpr int kLowLatMaxRows2 = 1024;
 constexpr int kLowLatMaxRows = 4096;        // capacity of the low-latency class (token rows = max_batch x tokens): beyond it the tiles fill the chip by themselves
 
-// ---- stage hook ---------------------------------------------------------------------------------------------------------------
-void free_stages(tld_engine* e) {
-    for (auto& kv : e->stages) if (kv.second.owned && kv.second.ptr) (void)hipFree(kv.second.ptr);
-    e->stages.clear();
-}
-DbgStage* stage_slot(tld_engine* e, const std::string& name, int dtype, int64_t s0, int64_t s1, int64_t s2, int64_t s3) {
-    DbgStage& st = e->stages[name];
-    st.dtype = dtype; st.shape[0] = s0; st.shape[1] = s1; st.shape[2] = s2; st.shape[3] = s3; st.live = true;
-    return &st;
-}
-// the engine's own buffer under a name (nothing is copied)
-void stage_ref(tld_engine* e, const std::string& name, const void* ptr, int dtype, int64_t s0, int64_t s1 = 1, int64_t s2 = 1, int64_t s3 = 1,
-               int64_t outer_stride = 0, int unpack = UNPACK_NONE) {
-    if (!e->debug || !ptr) return;
-    DbgStage* st = stage_slot(e, name, dtype, s0, s1, s2, s3);
-    st->owned = false; st->ptr = const_cast<void*>(ptr); st->outer_stride = outer_stride; st->unpack = unpack;
-}
-// a device-to-device copy on the stream, right after the kernel that completed the value, into memory tld_engine_set_debug(1) reserved
-int stage_copy(tld_engine* e, const std::string& name, const void* src, int dtype, hipStream_t s, int64_t s0, int64_t s1 = 1, int64_t s2 = 1, int64_t s3 = 1) {
-    if (!e->dbg_keep) return TLD_OK;
-    auto it = e->stages.find(name);
-    const size_t bytes = (size_t)(s0 * s1 * s2 * s3) * st_bytes(dtype);
-    if (it == e->stages.end() || !it->second.owned || it->second.cap < bytes)
-        return fail(TLD_ERR_STATE, "stage hook: no snapshot memory reserved for '%s' (%zu bytes): call tld_engine_set_debug(1) after the engine's "
-                    "mode (tld_engine_set_low_latency) is chosen", name.c_str(), bytes);
-    stage_slot(e, name, dtype, s0, s1, s2, s3);
-    HIP_TRY(hipMemcpyAsync(it->second.ptr, src, bytes, hipMemcpyDeviceToDevice, s));
-    return TLD_OK;
-}
-// a snapshot a kernel writes itself (cross_row's x + att dump): *out is the reserved memory, or null when nothing is kept
-int stage_sink(tld_engine* e, const std::string& name, int64_t s0, int64_t s1, float** out) {
-    *out = nullptr;
-    if (!e->dbg_keep) return TLD_OK;
-    auto it = e->stages.find(name);
-    if (it == e->stages.end() || !it->second.owned || it->second.cap < (size_t)(s0 * s1) * 4)
-        return fail(TLD_ERR_STATE, "stage hook: no snapshot memory reserved for '%s' (%zu bytes)", name.c_str(), (size_t)(s0 * s1) * 4);
-    stage_slot(e, name, ST_F32, s0, s1, 1, 1);
-    *out = static_cast<float*>(it->second.ptr);
-    return TLD_OK;
-}
-#define SNAP(...) do { if (e->dbg_keep) { if (int _r = stage_copy(e, __VA_ARGS__)) return _r; } } while (0)
+// ---- stage hook (StageStore, tld_host.h): this engine's names, sizes and poison step ---------------------------------------------------
+#define SNAP(...) do { if (e->dbg_keep) { if (int _r = e->stages.copy(__VA_ARGS__)) return _r; } } while (0)
 inline std::string blk_name(int l, const char* n) { return "blk" + std::to_string(l) + "." + n; }
 
 // which of the forward's size-independent branches this engine takes (run_body and the snapshot reservation agree through these)
@@ -335,19 +229,7 @@ inline bool eng_fuse_dw(const tld_engine* e) { return e->fuse_dwconv && (e->grid
 // and the names of what is read in place: the conditioning tables and the GEMM operands as the engine holds them
 int reserve_snapshots(tld_engine* e) {
     const size_t B = (size_t)e->cfg.max_batch, M = B * e->ntok, d = e->d, hid = e->hid;
-    auto one = [&](const std::string& name, size_t bytes) -> int {
-        DbgStage& st = e->stages[name];
-        if (st.owned && st.cap >= bytes) return TLD_OK;
-        if (st.owned && st.ptr) (void)hipFree(st.ptr);
-        st = DbgStage();
-        if (hipMalloc(&st.ptr, bytes) != hipSuccess) {
-            st.ptr = nullptr; (void)hipGetLastError();
-            return fail(TLD_ERR_HIP, "tld_engine_set_debug: hipMalloc of %zu bytes for the snapshot '%s' failed", bytes, name.c_str());
-        }
-        st.owned = true; st.cap = bytes;
-        return TLD_OK;
-    };
-#define RES(name, bytes) do { if (int _r = one(name, bytes)) return _r; } while (0)
+#define RES(name, bytes) do { if (int _r = e->stages.reserve(name, bytes)) return _r; } while (0)
     const size_t rs = sizeof(resid_t);
     RES("tokens0", M * d * rs); RES("out", B * e->img * 4);
     for (const char* n : {"step.x_t", "step.x0_prev", "step.x0", "step.x_next"}) RES(n, B * e->img * 4);
@@ -370,21 +252,22 @@ int reserve_snapshots(tld_engine* e) {
 #undef RES
     for (int l = 0; l < e->L; ++l) {
         const Layer& Ly = e->layers[l];
-        if (eng_fused_qa(e)) {
-            stage_ref(e, blk_name(l, "wqkv"), Ly.qkv_wp, ST_BF16, 3 * d, d, 1, 1, 0, UNPACK_QKV_ROWS);
-            stage_ref(e, blk_name(l, "qkv_c1"), Ly.qkv_c1p, ST_F32, 3 * d, 1, 1, 1, 0, UNPACK_QKV_ROWS);
-            stage_ref(e, blk_name(l, "qkv_b1"), Ly.qkv_b1p, ST_F32, 3 * d, 1, 1, 1, 0, UNPACK_QKV_ROWS);
+        StageStore& S = e->stages;
+        if (eng_fused_qa(e)) {      // rows in the fused kernel's packed order: the reader needs d and the head count to undo it
+            const struct { const char* n; const void* p; int dt; int64_t cols; } packed[] = {{"wqkv", Ly.qkv_wp, ST_BF16, (int64_t)d}, {"qkv_c1", Ly.qkv_c1p, ST_F32, 1}, {"qkv_b1", Ly.qkv_b1p, ST_F32, 1}};
+            for (const auto& q : packed)
+                if (Stage* st = S.ref(blk_name(l, q.n), q.p, q.dt, 3 * d, q.cols, 1, 1, 0, SL_QKV_ROWS)) { st->extra.d = e->d; st->extra.heads = e->H; }
         } else {
-            stage_ref(e, blk_name(l, "wqkv"), e->fold_ln1 ? Ly.qkv_wf : Ly.qkv_w, ST_BF16, 3 * d, d);
-            stage_ref(e, blk_name(l, "qkv_c1"), Ly.qkv_c1, ST_F32, 3 * d); stage_ref(e, blk_name(l, "qkv_b1"), Ly.qkv_b1, ST_F32, 3 * d);
+            S.ref(blk_name(l, "wqkv"), e->fold_ln1 ? Ly.qkv_wf : Ly.qkv_w, ST_BF16, 3 * d, d);
+            S.ref(blk_name(l, "qkv_c1"), Ly.qkv_c1, ST_F32, 3 * d); S.ref(blk_name(l, "qkv_b1"), Ly.qkv_b1, ST_F32, 3 * d);
         }
-        stage_ref(e, blk_name(l, "wup"), e->fold_ln3 ? Ly.up_wf : Ly.up_w, ST_BF16, hid, d);
-        stage_ref(e, blk_name(l, "up_c1"), Ly.up_c1, ST_F32, hid); stage_ref(e, blk_name(l, "up_b1"), Ly.up_b1, ST_F32, hid);
-        stage_ref(e, blk_name(l, "wdown"), Ly.down_w, ST_BF16, d, hid);
+        S.ref(blk_name(l, "wup"), e->fold_ln3 ? Ly.up_wf : Ly.up_w, ST_BF16, hid, d);
+        S.ref(blk_name(l, "up_c1"), Ly.up_c1, ST_F32, hid); S.ref(blk_name(l, "up_b1"), Ly.up_b1, ST_F32, hid);
+        S.ref(blk_name(l, "wdown"), Ly.down_w, ST_BF16, d, hid);
         if (e->fp8) {   // the weights as held: e4m3 + E8M0, dequantised on read
-            stage_ref(e, blk_name(l, "wqkv"), Ly.qkv_w8, ST_MX8W, 3 * d, d); e->stages[blk_name(l, "wqkv")].aux = Ly.qkv_s8;
-            stage_ref(e, blk_name(l, "wup"), Ly.up_w8, ST_MX8W, hid, d); e->stages[blk_name(l, "wup")].aux = Ly.up_s8;
-            stage_ref(e, blk_name(l, "wdown"), Ly.down_w8, ST_MX8W, d, hid); e->stages[blk_name(l, "wdown")].aux = Ly.down_s8;
+            if (Stage* st = S.ref(blk_name(l, "wqkv"), Ly.qkv_w8, ST_MX8W, 3 * d, d)) st->aux = Ly.qkv_s8;
+            if (Stage* st = S.ref(blk_name(l, "wup"), Ly.up_w8, ST_MX8W, hid, d)) st->aux = Ly.up_s8;
+            if (Stage* st = S.ref(blk_name(l, "wdown"), Ly.down_w8, ST_MX8W, d, hid)) st->aux = Ly.down_s8;
         }
     }
     return TLD_OK;
@@ -411,12 +294,13 @@ int debug_begin(tld_engine* e, int T, int Tn, hipStream_t s) {
     HIP_TRY(hipMemsetAsync(e->c_kv, 0xFF, L * cap * 2 * d * 4, s));
     HIP_TRY(hipMemsetAsync(e->c_wq, 0xFF, L * cap * H * d * 4, s));
     HIP_TRY(hipMemsetAsync(e->c_bwq, 0xFF, L * cap * H * 4, s));
-    for (auto& kv : e->stages) if (kv.second.owned) kv.second.live = false;      // every snapshot of an earlier call is forgotten (the operand names stay)
-    stage_ref(e, "cond.sin", e->c_sin, ST_F32, Tn, e->ne); stage_ref(e, "cond.h1", e->c_h1, ST_F32, Tn, d);      // (noise rows only)
-    stage_ref(e, "cond.pre", e->c_pre, ST_F32, T, d); stage_ref(e, "cond.y", e->c_y, ST_F32, T, d);
-    stage_ref(e, "cond.kv", e->c_kv, ST_F32, L, T, 2 * d, 1, (int64_t)(cap * 2 * d));
-    stage_ref(e, "cond.wq", e->c_wq, ST_F32, L, T, H, d, (int64_t)(cap * H * d));
-    stage_ref(e, "cond.bwq", e->c_bwq, ST_F32, L, T, H, 1, (int64_t)(cap * H));
+    StageStore& S = e->stages;
+    S.begin_call();      // every snapshot of an earlier call is forgotten (the operand names stay)
+    S.ref("cond.sin", e->c_sin, ST_F32, Tn, e->ne); S.ref("cond.h1", e->c_h1, ST_F32, Tn, d);      // (noise rows only)
+    S.ref("cond.pre", e->c_pre, ST_F32, T, d); S.ref("cond.y", e->c_y, ST_F32, T, d);
+    S.ref("cond.kv", e->c_kv, ST_F32, L, T, 2 * d, 1, (int64_t)(cap * 2 * d));
+    S.ref("cond.wq", e->c_wq, ST_F32, L, T, H, d, (int64_t)(cap * H * d));
+    S.ref("cond.bwq", e->c_bwq, ST_F32, L, T, H, 1, (int64_t)(cap * H));
     return TLD_OK;
 }
 struct PathScope {      // the launchers record their paths into this engine while one of its debug calls runs on this thread; no stage is kept after it, on any exit
@@ -500,7 +384,7 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
             g.A = half ? xe : e->x; g.lda = d; g.W = Ly.qkv_wp; g.ldw = d; g.M = Ml; g.N = 3 * d; g.K = d;
             g.out_bf16 = e->att; g.ldo = d; g.ntok = e->ntok; g.d = d;
             g.ln_stats = e->ln_stats; g.ln_slots = l == 0 ? 2 : ln_slots; g.ln_c1 = Ly.qkv_c1p; g.ln_b1 = Ly.qkv_b1p;
-            launch_gemm(g, EPI_QKV_ATTN, s);
+            GEMM_TRY(blk_name(l, "QKV + attention"), launch_gemm(g, EPI_QKV_ATTN, s));
         } else {   // q|k, v^T = LN1(x) Wqkv^T
             ProfScope ps(e, KC_GEMM_QKV, s);
             GemmParams g{};
@@ -518,7 +402,7 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
                 g.ln_c1 = Ly.qkv_c1; g.ln_b1 = Ly.qkv_b1;
             }
 #endif
-            launch_gemm(g, fold1 ? EPI_QKV_LN : EPI_QKV, s);
+            GEMM_TRY(blk_name(l, "QKV projection"), launch_gemm(g, fold1 ? EPI_QKV_LN : EPI_QKV, s));
             SNAP(blk_name(l, "qk"), e->qk, ST_BF16, s, Ml, 2 * d); SNAP(blk_name(l, "vt"), e->vt, ST_BF16, s, bl, d, e->ntok);
         }
         if (!fused_qa) {
@@ -544,7 +428,7 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
             cp.noise_row = noise_row; cp.label_row = label_row;
             cp.ln2_w = Ly.n2_w; cp.ln2_b = Ly.n2_b; cp.ln3_w = Ly.n3_w; cp.ln3_b = Ly.n3_b;
             cp.xn3 = fold3 ? nullptr : e->xn; cp.ln3_stats = fold3 ? e->row_stats : nullptr; cp.batch = batch; cp.ntok = e->ntok; cp.d = d; cp.heads = e->H;
-            if (e->dbg_keep) { if (int rc = stage_sink(e, blk_name(l, "sa"), M, d, &cp.sa_out)) return rc; }
+            if (e->dbg_keep) { if (int rc = e->stages.sink(blk_name(l, "sa"), M, d, &cp.sa_out)) return rc; }
             const bool cross8 = fuse8 && cross_row_supports_ln3_stats(d);      // (= the 4-features-per-lane kernel is in use)
             if (cross8) { cp.xn3_f8 = e->a8; cp.xn3_s8 = e->as8; }
             launch_cross_row(cp, s);
@@ -564,7 +448,7 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
             }
 #endif
             g.dw_seam = e->seam;
-            launch_gemm(g, e->grid == 32 ? EPI_UP_DWCONV32 : EPI_UP_DWCONV2, s);
+            GEMM_TRY(blk_name(l, "fused up-projection"), launch_gemm(g, e->grid == 32 ? EPI_UP_DWCONV32 : EPI_UP_DWCONV2, s));
             if (e->grid == 32) {
                 ProfScope ps2(e, KC_DWCONV, s);
                 launch_dwconv_seam(e->seam, Ly.dw_wpk, Ly.dw_b_half, e->hid2, e->hid, batch, e->hid, s);
@@ -586,7 +470,7 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
                     g.A = e->x; g.W = Ly.up_wf; g.bias = Ly.up_b1; g.ln_c1 = Ly.up_c1; g.row_stats = e->row_stats;
                 }
 #endif
-                launch_gemm(g, EPI_BIAS_BF16, s);
+                GEMM_TRY(blk_name(l, "up-projection"), launch_gemm(g, EPI_BIAS_BF16, s));
             }
             SNAP(blk_name(l, "hid_pre"), e->hid1, ST_BF16, s, M, e->hid);
             {
@@ -607,7 +491,7 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
             GemmParams g{};
             g.A = e->hid2; g.lda = e->hid; g.W = Ly.down_w; g.ldw = e->hid; g.M = M; g.N = d; g.K = e->hid / e->ll_split; g.ksplit = e->ll_split;
             g.c_f32 = e->splitk; g.ldc = d;
-            launch_gemm(g, EPI_F32, s);
+            GEMM_TRY(blk_name(l, "split-K down projection"), launch_gemm(g, EPI_F32, s));
             SNAP(blk_name(l, "splitk"), e->splitk, ST_F32, s, e->ll_split, M, d);
             launch_splitk_resid(e->splitk, e->ll_split, (size_t)M * d, Ly.down_b, e->x, (fold1 && l + 1 < e->L) ? e->ln_stats : nullptr, M, d, s);
         } else
@@ -623,7 +507,7 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
                 g.f8 = 1; g.A = reinterpret_cast<const bf16*>(e->a8); g.W = reinterpret_cast<const bf16*>(Ly.down_w8);
                 g.a_scale = e->as8; g.w_scale = Ly.down_s8;
             }
-            launch_gemm(g, EPI_BIAS_RESID, s);
+            GEMM_TRY(blk_name(l, "down projection"), launch_gemm(g, EPI_BIAS_RESID, s));
         }
         SNAP(blk_name(l, "mlp"), e->x, rdt, s, M, d);
     }
@@ -755,7 +639,6 @@ int run_sampler(tld_engine* e, const SamplePlan& p, hipStream_t s) {
     if (int rc = cond_tables(e, T, s)) return rc;
     HIP_TRY(hipMemcpyAsync(e->req_dev, tab, up_bytes, hipMemcpyHostToDevice, s));
     HIP_TRY(hipEventRecord(e->stage_ev, s));     // no stream sync: the staging buffer is the engine's, guarded by this event
-    e->dbg_batch = 2 * B; e->dbg_T = T;
     const SamplerStepRow* tab_dev = static_cast<const SamplerStepRow*>(e->req_dev);
     const float* mix_dev = reinterpret_cast<const float*>(tab_dev + (size_t)n_max * tabB);
     const int* nr = reinterpret_cast<const int*>(mix_dev + tabB);
@@ -939,7 +822,7 @@ int tld_engine_finalize_weights(tld_engine* e) {
         std::vector<uint16_t> hl((size_t)(2 * pd * d));
         for (int64_t i = 0; i < pd * d; ++i) {
             const uint16_t hi = f32_to_bf16_rne(W[(size_t)i]);
-            uint32_t u = (uint32_t)hi << 16; float hf; memcpy(&hf, &u, 4);
+            const float hf = bf16_to_f32(hi);
             hl[(size_t)i] = hi; hl[(size_t)(pd * d + i)] = f32_to_bf16_rne(W[(size_t)i] - hf);
         }
         if (int rc = dev_alloc(e, &e->out_w_hl, hl.size())) return rc;
@@ -952,7 +835,7 @@ int tld_engine_finalize_weights(tld_engine* e) {
             std::vector<uint16_t> hl((size_t)(2 * pd * d));
             for (int64_t i = 0; i < pd * d; ++i) {
                 const uint16_t hi = f32_to_bf16_rne(W[(size_t)i]);
-                uint32_t u = (uint32_t)hi << 16; float hf; memcpy(&hf, &u, 4);
+                const float hf = bf16_to_f32(hi);
                 hl[(size_t)i] = hi; hl[(size_t)(pd * d + i)] = f32_to_bf16_rne(W[(size_t)i] - hf);
             }
             if (int rc = dev_alloc(e, &e->plin_w_hl, hl.size())) return rc;
@@ -1015,7 +898,7 @@ int tld_engine_finalize_weights(tld_engine* e) {
                     const float w = W[(size_t)(n * d + k2)];
                     const uint16_t q = f32_to_bf16_rne(g1[(size_t)k2] * w);
                     wf[(size_t)(n * d + k2)] = q;
-                    uint32_t u = (uint32_t)q << 16; float qf; memcpy(&qf, &u, 4);
+                    const float qf = bf16_to_f32(q);
                     sc += qf; sb += (double)be[(size_t)k2] * w;
                 }
                 c1[(size_t)n] = (float)sc; b1[(size_t)n] = (float)sb;
@@ -1081,7 +964,7 @@ int tld_engine_finalize_weights(tld_engine* e) {
                     const float w = W[(size_t)(n * d + k2)];
                     const uint16_t q = f32_to_bf16_rne(g3[(size_t)k2] * w);
                     wf[(size_t)(n * d + k2)] = q;
-                    uint32_t u = (uint32_t)q << 16; float qf; memcpy(&qf, &u, 4);
+                    const float qf = bf16_to_f32(q);
                     sc += qf; sb += (double)b3[(size_t)k2] * w;
                 }
                 c1[(size_t)n] = (float)sc; b1[(size_t)n] = (float)(sb + ub[(size_t)n]);
@@ -1190,10 +1073,10 @@ int tld_engine_set_debug(tld_engine* e, int32_t enable) {
     if (enable) {
         if (!e->finalized) return fail(TLD_ERR_STATE, "tld_engine_set_debug: weights not finalized");
         e->debug = true;
-        if (int rc = reserve_snapshots(e)) { (void)hipDeviceSynchronize(); free_stages(e); e->debug = false; return rc; }
+        if (int rc = reserve_snapshots(e)) { (void)hipDeviceSynchronize(); e->stages.free_all(); e->debug = false; return rc; }
     } else {
         (void)hipDeviceSynchronize();
-        free_stages(e);
+        e->stages.free_all();
         e->debug = false; e->dbg_keep = false;
     }
     return TLD_OK;
@@ -1220,75 +1103,26 @@ std::string stage_alias(const tld_engine* e, const char* name) {
     if (!strcmp(name, "tokens_final")) return blk_name(e->L - 1, "mlp");
     return name;
 }
-const DbgStage* find_stage(tld_engine* e, const char* name) {
-    auto it = e->stages.find(stage_alias(e, name));
-    return (it != e->stages.end() && it->second.live && it->second.ptr) ? &it->second : nullptr;
-}
 }  // namespace
+
+int tld_debug_decode_stage(const void* raw, const void* aux, int32_t dtype, int32_t layout, const int64_t* shape4, int64_t outer_stride, int32_t d,
+                           int32_t heads, float* out, int64_t numel) {
+    if (!raw || !shape4 || !out) return fail(TLD_ERR_INVALID, "tld_debug_decode_stage: null argument");
+    if (numel != stage_numel(shape4)) return fail(TLD_ERR_SHAPE, "tld_debug_decode_stage: the shape has %lld elements, the caller's buffer %lld", (long long)stage_numel(shape4), (long long)numel);
+    StageExtra x;
+    x.outer_stride = outer_stride; x.d = d; x.heads = heads;
+    return decode_stage(raw, aux, dtype, layout, shape4, x, out);
+}
 
 int tld_engine_stage_shape(tld_engine* e, const char* name, int64_t* shape4) {
     if (!e || !name || !shape4) return fail(TLD_ERR_INVALID, "null argument");
-    const DbgStage* st = find_stage(e, name);
-    if (!st) return fail(TLD_ERR_KEY, "no captured stage named %s (was debug enabled before the forward? a stage of another path?)", name);
-    for (int i = 0; i < 4; ++i) shape4[i] = st->shape[i];
-    return TLD_OK;
+    return e->stages.read(stage_alias(e, name), nullptr, 0, shape4);
 }
 
 int tld_engine_read_stage(tld_engine* e, const char* name, float* host_out, int64_t numel) {
     if (!e || !name || !host_out) return fail(TLD_ERR_INVALID, "null argument");
     DeviceGuard dg(e->cfg.device_id);
-    HIP_TRY(hipDeviceSynchronize());
-    const DbgStage* st = find_stage(e, name);
-    if (!st) return fail(TLD_ERR_KEY, "no captured stage named %s (was debug enabled before the forward? a stage of another path?)", name);
-    const int64_t outer = st->outer_stride ? st->shape[0] : 1;
-    const int64_t inner = (st->outer_stride ? 1 : st->shape[0]) * st->shape[1] * st->shape[2] * st->shape[3];
-    if (numel != outer * inner)
-        return fail(TLD_ERR_SHAPE, "stage %s has %lld elements [%lld, %lld, %lld, %lld], the caller's buffer %lld", name, (long long)(outer * inner),
-                    (long long)st->shape[0], (long long)st->shape[1], (long long)st->shape[2], (long long)st->shape[3], (long long)numel);
-    if (st->dtype == ST_U8 || st->dtype == ST_MX8S || st->dtype == ST_MX8W) {
-        const int64_t rows = st->shape[0], cols = st->shape[1];
-        std::vector<uint8_t> raw((size_t)numel);
-        HIP_TRY(hipMemcpy(raw.data(), st->ptr, (size_t)numel, hipMemcpyDeviceToHost));
-        if (st->dtype == ST_U8) {
-            for (int64_t i = 0; i < numel; ++i) host_out[i] = (float)raw[(size_t)i];
-        } else if (st->dtype == ST_MX8S) {      // [cols / 4][rows][4] -> [rows][cols]
-            for (int64_t r = 0; r < rows; ++r)
-                for (int64_t c = 0; c < cols; ++c) host_out[r * cols + c] = (float)raw[(size_t)(((c >> 2) * rows + r) * 4 + (c & 3))];
-        } else {                                // e4m3 code x 2^(E8M0 - 127), scales [cols / 128][rows][4]
-            std::vector<uint8_t> sc((size_t)(numel / 32));
-            HIP_TRY(hipMemcpy(sc.data(), st->aux, sc.size(), hipMemcpyDeviceToHost));
-            for (int64_t r = 0; r < rows; ++r)
-                for (int64_t c = 0; c < cols; ++c) {
-                    const uint8_t q = raw[(size_t)(r * cols + c)];
-                    const int ex = (q >> 3) & 15, man = q & 7;
-                    const float mag = ex ? ldexpf((float)(8 + man), ex - 10) : ldexpf((float)man, -9);      // (the quantiser saturates: no NaN code is stored)
-                    const int e8 = sc[(size_t)(((c >> 7) * rows + r) * 4 + ((c >> 5) & 3))];
-                    host_out[r * cols + c] = ldexpf((q & 0x80) ? -mag : mag, e8 - 127);
-                }
-        }
-        return TLD_OK;
-    }
-    const size_t esz = st->dtype == ST_BF16 ? 2 : 4;
-    std::vector<uint16_t> half;
-    if (st->dtype == ST_BF16) half.resize((size_t)numel);
-    for (int64_t o = 0; o < outer; ++o) {
-        const char* src = static_cast<const char*>(st->ptr) + (size_t)o * st->outer_stride * esz;
-        void* dst = st->dtype == ST_BF16 ? static_cast<void*>(half.data() + o * inner) : static_cast<void*>(host_out + o * inner);
-        HIP_TRY(hipMemcpy(dst, src, (size_t)inner * esz, hipMemcpyDeviceToHost));
-    }
-    if (st->dtype == ST_BF16)
-        for (int64_t i = 0; i < numel; ++i) { const uint32_t u = (uint32_t)half[(size_t)i] << 16; memcpy(host_out + i, &u, 4); }
-    if (st->unpack == UNPACK_QKV_ROWS) {      // back to the logical [q; k; v] x [head][64] row order (the inverse of the packing in finalize_weights)
-        const int64_t d = e->d, row = st->shape[1];
-        std::vector<float> tmp(host_out, host_out + numel);
-        for (int64_t h = 0; h < e->H; ++h)
-            for (int part = 0; part < 3; ++part)
-                for (int64_t c = 0; c < 64; ++c) {
-                    const int64_t logical = part * d + h * 64 + c, packed = h * 192 + (c >> 5) * 96 + part * 32 + (c & 31);
-                    memcpy(host_out + logical * row, tmp.data() + packed * row, (size_t)row * 4);
-                }
-    }
-    return TLD_OK;
+    return e->stages.read(stage_alias(e, name), host_out, numel, nullptr);
 }
 
 int tld_denoiser_forward(tld_engine* e, const void* x, const void* noise, const void* label, void* out,
@@ -1318,7 +1152,6 @@ int tld_denoiser_forward(tld_engine* e, const void* x, const void* noise, const 
     }
     if (int rc = cond_tables(e, 2 * batch, s)) return rc;
     launch_iota(e->rows_dev, 2 * batch, 0, s);
-    e->dbg_batch = batch; e->dbg_T = 2 * batch;
     if (int rc = run_body(e, xin, batch, batch, e->rows_dev, e->rows_dev + batch, o, s)) return rc;
     if (io_dtype != TLD_DTYPE_F32) launch_cast_from_f32(e->io_out, out, io_dtype, (int64_t)batch * e->img, s);
     HIP_TRY(hipGetLastError());
@@ -1494,10 +1327,15 @@ int tld_debug_gemm_bench(int32_t M, int32_t N, int32_t K, int32_t epilogue, int3
     }
     hipEvent_t a, b;
     HIP_TRY(hipEventCreate(&a)); HIP_TRY(hipEventCreate(&b));
-    auto run = [&]() { launch_gemm(g, epilogue, nullptr); };
-    for (int i = 0; i < 3; ++i) run();
+    auto run = [&]() { return launch_gemm(g, epilogue, nullptr); };
+    if (const int rc = run()) {      // a refused plan (the reason is in tld_last_error): every later launch would be refused alike, nothing to time
+        hipEventDestroy(a); hipEventDestroy(b);
+        hipFree(A); hipFree(W); hipFree(out); hipFree(vt); hipFree(bias); hipFree(res); hipFree(dww);
+        return rc;
+    }
+    for (int i = 1; i < 3; ++i) (void)run();
     HIP_TRY(hipEventRecord(a, nullptr));
-    for (int i = 0; i < iters; ++i) run();
+    for (int i = 0; i < iters; ++i) (void)run();
     HIP_TRY(hipEventRecord(b, nullptr));
     HIP_TRY(hipEventSynchronize(b));
     float ms = 0.f;
@@ -1743,7 +1581,7 @@ int tld_engine_destroy(tld_engine* e) {
     (void)hipDeviceSynchronize();
     for (int k = 0; k < KC_COUNT; ++k)
         for (auto& ev : e->prof_ev[k]) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
-    free_stages(e);
+    e->stages.free_all();
     for (void* p : e->allocs) (void)hipFree(p);
     if (e->stage_host) (void)hipHostFree(e->stage_host);
     if (e->stage_ev) (void)hipEventDestroy(e->stage_ev);

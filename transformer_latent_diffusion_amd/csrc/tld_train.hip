@@ -13,6 +13,7 @@
 // graph (none of the inference path's algebraic folds), so every saved tensor is the one autograd would save.
 #include "../../include/tld_hip.h"
 #include "tld_train_kernels.h"
+#include "tld_host.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -33,29 +34,6 @@ int launch_attention_bwd(const bf16* qk, const bf16* vt, const bf16* o, const bf
 
 namespace {
 
-int tfail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    tld::set_last_error(buf);
-    return code;
-}
-#define HIP_TRY(expr)                                                                                                            \
-    do {                                                                                                                         \
-        hipError_t _e = (expr);                                                                                                  \
-        if (_e != hipSuccess) return tfail(TLD_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
-
-struct DevGuard {
-    int prev = -1; bool switched = false;
-    explicit DevGuard(int dev) {
-        if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DevGuard() { if (switched) (void)hipSetDevice(prev); }
-};
-
 struct Tensor { std::string key; int64_t off, numel; };
 
 struct LayerP {          // offsets into the flat parameter / gradient vectors
@@ -72,9 +50,6 @@ struct LayerB {          // engine-owned per-layer buffers
 
 inline dim3 g1(size_t n, int bs = 256) { return dim3((unsigned)((n + bs - 1) / bs)); }
 
-// stage hook (tld_train_set_debug): a named tensor, read in place (the engine's own buffer) or from a copy the hook owns
-enum { ST_F32 = 0, ST_BF16 = 1 };
-struct Stage { void* ptr = nullptr; int dtype = ST_F32; int64_t shape[4] = {1, 1, 1, 1}; bool owned = false; size_t cap = 0; bool live = false; };
 // launch-path bits (the table in include/tld_hip.h)
 enum : int {
     PB_RESID_Q4 = 0, PB_RESID_GEN = 4, PB_LNB_Q4 = 5, PB_LNB_GEN = 8, PB_EMB_LDS = 9, PB_EMB_PLAIN = 13, PB_TAIL4_16 = 14, PB_TAIL4_32 = 15, PB_TAIL4_64 = 16,
@@ -98,7 +73,7 @@ struct tld_train {
     std::vector<size_t> alloc_bytes;     // size of each entry of allocs (the stage hook poisons them)
     bool debug = false;                  // stage hook (tld_train_set_debug)
     uint64_t paths = 0;                  // launch paths of the last debug call
-    std::map<std::string, Stage> stages;
+    StageStore stages;                   // the stage hook (tld_host.h)
     float* angular = nullptr;            // sinusoid buffer (not a parameter; tld/transformer_blocks.py:11-15)
     float* zero_bias = nullptr;
     // conditioning path
@@ -135,7 +110,7 @@ void add_t(tld_train* e, const std::string& k, int64_t n, int64_t* off) {
 template <typename T>
 int dalloc(tld_train* e, T** p, size_t n) {
     void* q = nullptr;
-    if (hipMalloc(&q, n * sizeof(T)) != hipSuccess) return tfail(TLD_ERR_HIP, "hipMalloc of %zu bytes failed", n * sizeof(T));
+    if (hipMalloc(&q, n * sizeof(T)) != hipSuccess) return fail(TLD_ERR_HIP, "hipMalloc of %zu bytes failed", n * sizeof(T));
     e->allocs.push_back(q);
     e->alloc_bytes.push_back(n * sizeof(T));
     *p = reinterpret_cast<T*>(q);
@@ -182,46 +157,14 @@ int gemm_bf16(const bf16* A, int lda, const bf16* W, int ldw, const float* bias,
     g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.M = Mr; g.N = Nc; g.K = K; g.out_bf16 = out; g.ldo = Nc; g.bias = bias;
     return launch_gemm(g, EPI_BIAS_BF16, s);
 }
-// a refused GEMM plan launches nothing: the step fails with launch_gemm's text instead of going on with the previous call's buffers
-#define GEMM_TRY(expr)                                                                                                           \
-    do {                                                                                                                         \
-        if (int _g = (expr)) { const std::string _m = tld_last_error(); return tfail(_g, "training step: %s refused: %s", #expr, _m.c_str()); } \
-    } while (0)
-
-// ---- stage hook ---------------------------------------------------------------------------------------------------------------
-void free_stages(tld_train* e) {
-    for (auto& kv : e->stages) if (kv.second.owned && kv.second.ptr) hipFree(kv.second.ptr);
-    e->stages.clear();
-}
-Stage* stage_slot(tld_train* e, const std::string& name, int dtype, int64_t s0, int64_t s1, int64_t s2, int64_t s3) {
-    Stage& st = e->stages[name];
-    st.dtype = dtype; st.shape[0] = s0; st.shape[1] = s1; st.shape[2] = s2; st.shape[3] = s3; st.live = true;
-    return &st;
-}
-// the engine's own buffer under a name (nothing is copied)
-void stage_ref(tld_train* e, const std::string& name, const void* ptr, int dtype, int64_t s0, int64_t s1 = 1, int64_t s2 = 1, int64_t s3 = 1) {
-    if (!e->debug) return;
-    Stage* st = stage_slot(e, name, dtype, s0, s1, s2, s3);
-    if (st->owned && st->ptr) { hipFree(st->ptr); st->cap = 0; }
-    st->owned = false; st->ptr = const_cast<void*>(ptr);
-}
-// a device-to-device copy on the stream, taken right after the kernel that completed the value
-int stage_copy(tld_train* e, const std::string& name, const void* src, int dtype, hipStream_t s, int64_t s0, int64_t s1 = 1, int64_t s2 = 1, int64_t s3 = 1) {
-    if (!e->debug) return TLD_OK;
-    Stage* st = stage_slot(e, name, dtype, s0, s1, s2, s3);
-    const size_t bytes = (size_t)(s0 * s1 * s2 * s3) * (dtype == ST_BF16 ? 2 : 4);
-    if (!st->owned || st->cap < bytes) {      // (tld_train_set_debug reserved every snapshot at max_batch: a name it does not know is a bug here)
-        st->live = false;
-        return tfail(TLD_ERR_STATE, "stage hook: no snapshot memory reserved for '%s' (%zu bytes)", name.c_str(), bytes);
-    }
-    if (hipMemcpyAsync(st->ptr, src, bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) return tfail(TLD_ERR_HIP, "stage hook: copy of '%s' failed", name.c_str());
-    return TLD_OK;
-}
+// ---- stage hook (StageStore, tld_host.h): this engine's names, sizes and poison step.  The names debug_begin references and the names
+// reserve_snapshots reserves are disjoint (forward tensors saved for the backward vs copies of the backward's transient buffers) -----------------
 // start of a debug call: poison what the kernels are to write, forget the last call's stages, name the saved forward tensors
 int debug_begin(tld_train* e, int B, hipStream_t s) {
     const int d = e->d, hid = e->hid, pd = e->pd, N = e->N, H = e->H, M = B * N;
     e->paths = 0;
-    for (auto& kv : e->stages) kv.second.live = false;
+    StageStore& S = e->stages;
+    S.begin_call();
     auto keep = [&](const void* p) {       // constants and the weight operand copies (refreshed before this point) stay
         if (p == e->angular || p == e->zero_bias) return true;
         for (const LayerB& b : e->lb)
@@ -231,40 +174,31 @@ int debug_begin(tld_train* e, int B, hipStream_t s) {
     for (size_t i = 0; i < e->allocs.size(); ++i)
         if (!keep(e->allocs[i])) HIP_TRY(hipMemsetAsync(e->allocs[i], 0xFF, e->alloc_bytes[i], s));
     HIP_TRY(hipMemsetAsync(e->grads, 0xFF, (size_t)e->nparam * 4, s));
-    stage_ref(e, "sinb", e->sinb, ST_F32, B, e->ne); stage_ref(e, "h1", e->h1, ST_F32, B, d); stage_ref(e, "g1v", e->g1v, ST_F32, B, d);
-    stage_ref(e, "ycat", e->ycat, ST_F32, 2 * B, d); stage_ref(e, "y", e->y, ST_F32, 2 * B, d); stage_ref(e, "yst", e->yst, ST_F32, 2 * B, 2);
-    stage_ref(e, "p16", e->p16, ST_F32, M, pd); stage_ref(e, "p16n", e->p16n, ST_F32, M, pd); stage_ref(e, "est1", e->est1, ST_F32, M, 2);
-    stage_ref(e, "e", e->e, ST_F32, M, d); stage_ref(e, "est2", e->est2, ST_F32, M, 2); stage_ref(e, "xfin", e->xfin, ST_BF16, M, d);
-    stage_ref(e, "dout", e->dout, ST_F32, M, pd); stage_ref(e, "row_loss", e->row_loss, ST_F32, M);
+    S.ref("sinb", e->sinb, ST_F32, B, e->ne); S.ref("h1", e->h1, ST_F32, B, d); S.ref("g1v", e->g1v, ST_F32, B, d);
+    S.ref("ycat", e->ycat, ST_F32, 2 * B, d); S.ref("y", e->y, ST_F32, 2 * B, d); S.ref("yst", e->yst, ST_F32, 2 * B, 2);
+    S.ref("p16", e->p16, ST_F32, M, pd); S.ref("p16n", e->p16n, ST_F32, M, pd); S.ref("est1", e->est1, ST_F32, M, 2);
+    S.ref("e", e->e, ST_F32, M, d); S.ref("est2", e->est2, ST_F32, M, 2); S.ref("xfin", e->xfin, ST_BF16, M, d);
+    S.ref("dout", e->dout, ST_F32, M, pd); S.ref("row_loss", e->row_loss, ST_F32, M);
     for (int i = 0; i < e->L; ++i) {
         const LayerB& b = e->lb[i];
         const std::string p = "blk" + std::to_string(i) + ".";
         const struct { const char* n; const bf16* q; int w; } acts[] = {{"x1", b.x1, d}, {"a1", b.a1, d}, {"qk", b.qk, 2 * d}, {"att", b.att, d}, {"x2", b.x2, d}, {"a2", b.a2, d},
             {"qc", b.qc, d}, {"cr", b.cr, d}, {"x3", b.x3, d}, {"a3", b.a3, d}, {"h", b.h, hid}, {"hc", b.hc, hid}, {"o", b.o, d}};
-        for (const auto& a : acts) stage_ref(e, p + a.n, a.q, ST_BF16, M, a.w);
-        stage_ref(e, p + "vt", b.vt, ST_BF16, B, H, 64, N);
-        stage_ref(e, p + "st1", b.st1, ST_F32, M, 2); stage_ref(e, p + "st2", b.st2, ST_F32, M, 2); stage_ref(e, p + "st3", b.st3, ST_F32, M, 2);
-        stage_ref(e, p + "p0", b.p0, ST_F32, M, H); stage_ref(e, p + "kvc", b.kvc, ST_F32, 2 * B, 2 * d);
-        stage_ref(e, p + "wqkv", b.wqkv, ST_BF16, 3 * d, d); stage_ref(e, p + "wqkv_t", b.wqkv_t, ST_BF16, d, 3 * d);
-        stage_ref(e, p + "wq", b.wq, ST_BF16, d, d); stage_ref(e, p + "wq_t", b.wq_t, ST_BF16, d, d);
-        stage_ref(e, p + "wup", b.wup, ST_BF16, hid, d); stage_ref(e, p + "wup_t", b.wup_t, ST_BF16, d, hid);
-        stage_ref(e, p + "wdown", b.wdown, ST_BF16, d, hid); stage_ref(e, p + "wdown_t", b.wdown_t, ST_BF16, hid, d);
+        for (const auto& a : acts) S.ref(p + a.n, a.q, ST_BF16, M, a.w);
+        S.ref(p + "vt", b.vt, ST_BF16, B, H, 64, N);
+        S.ref(p + "st1", b.st1, ST_F32, M, 2); S.ref(p + "st2", b.st2, ST_F32, M, 2); S.ref(p + "st3", b.st3, ST_F32, M, 2);
+        S.ref(p + "p0", b.p0, ST_F32, M, H); S.ref(p + "kvc", b.kvc, ST_F32, 2 * B, 2 * d);
+        S.ref(p + "wqkv", b.wqkv, ST_BF16, 3 * d, d); S.ref(p + "wqkv_t", b.wqkv_t, ST_BF16, d, 3 * d);
+        S.ref(p + "wq", b.wq, ST_BF16, d, d); S.ref(p + "wq_t", b.wq_t, ST_BF16, d, d);
+        S.ref(p + "wup", b.wup, ST_BF16, hid, d); S.ref(p + "wup_t", b.wup_t, ST_BF16, d, hid);
+        S.ref(p + "wdown", b.wdown, ST_BF16, d, hid); S.ref(p + "wdown_t", b.wdown_t, ST_BF16, hid, d);
     }
     return TLD_OK;
 }
 // set_debug(1): memory for every snapshot a step of max_batch samples takes (the names of the SNAP calls in tld_train_forward_backward_cb)
 int reserve_snapshots(tld_train* e) {
     const size_t M = (size_t)e->B * e->N, d = e->d, hid = e->hid, pd = e->pd, B2 = 2 * (size_t)e->B;
-    auto one = [&](const std::string& name, size_t bytes) -> int {
-        Stage& st = e->stages[name];
-        if (st.owned && st.cap >= bytes) return TLD_OK;
-        if (st.owned && st.ptr) hipFree(st.ptr);
-        st = Stage();
-        if (hipMalloc(&st.ptr, bytes) != hipSuccess) { st.ptr = nullptr; return tfail(TLD_ERR_HIP, "tld_train_set_debug: hipMalloc of %zu bytes for the snapshot '%s' failed", bytes, name.c_str()); }
-        st.owned = true; st.cap = bytes;
-        return TLD_OK;
-    };
-#define RES(name, bytes) do { if (int _r = one(name, bytes)) return _r; } while (0)
+#define RES(name, bytes) do { if (int _r = e->stages.reserve(name, bytes)) return _r; } while (0)
     RES("gx.tail", M * d * 4); RES("gxb.tail", M * d * 2);
     const bool dw_fused = e->G <= 16 && e->N >= 176 && e->hid % 64 == 0;
     for (int i = 0; i < e->L; ++i) {
@@ -281,27 +215,27 @@ int reserve_snapshots(tld_train* e) {
     return TLD_OK;
 }
 #define PATH(b) do { if (e->debug) e->paths |= 1ull << (b); } while (0)
-#define SNAP(...) do { if (e->debug) { if (int _r = stage_copy(e, __VA_ARGS__)) return _r; } } while (0)
+#define SNAP(...) do { if (e->debug) { if (int _r = e->stages.copy(__VA_ARGS__)) return _r; } } while (0)
 
 }  // namespace
 
 extern "C" {
 
 int tld_train_create(const tld_config* cfg, tld_train** out) {
-    if (!cfg || !out) return tfail(TLD_ERR_INVALID, "null argument");
+    if (!cfg || !out) return fail(TLD_ERR_INVALID, "null argument");
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return tfail(TLD_ERR_HIP, "no HIP device: the training engine has no CPU path");
-    if (cfg->device_id < 0 || cfg->device_id >= ndev) return tfail(TLD_ERR_INVALID, "device_id %d out of range", cfg->device_id);
-    if (cfg->embed_dim % 64 || cfg->embed_dim > 1024 || cfg->embed_dim <= 0) return tfail(TLD_ERR_INVALID, "embed_dim must be a multiple of 64 (the head width), <= 1024");
-    if (cfg->patch_size <= 0 || cfg->image_size % cfg->patch_size) return tfail(TLD_ERR_INVALID, "image_size must be a multiple of patch_size");
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(TLD_ERR_HIP, "no HIP device: the training engine has no CPU path");
+    if (cfg->device_id < 0 || cfg->device_id >= ndev) return fail(TLD_ERR_INVALID, "device_id %d out of range", cfg->device_id);
+    if (cfg->embed_dim % 64 || cfg->embed_dim > 1024 || cfg->embed_dim <= 0) return fail(TLD_ERR_INVALID, "embed_dim must be a multiple of 64 (the head width), <= 1024");
+    if (cfg->patch_size <= 0 || cfg->image_size % cfg->patch_size) return fail(TLD_ERR_INVALID, "image_size must be a multiple of patch_size");
     const int G = cfg->image_size / cfg->patch_size;
     // the inference engine's grids (square, side a multiple of 4: token counts that are multiples of 16, which the attention forward and
     // backward take), up to 64 x 64; the reference trains at whatever image_size it is given (tld/train.py:83)
     if (G % 4 || G < 4 || G > 64)
-        return tfail(TLD_ERR_INVALID, "the training step supports image_size / patch_size = G with G a multiple of 4, 4 <= G <= 64 (16 .. 4096 tokens); got G = %d", G);
-    if (cfg->n_channels * cfg->patch_size * cfg->patch_size > 64) return tfail(TLD_ERR_INVALID, "patch_dim must be <= 64");
-    if (cfg->noise_embed_dims % 2 || cfg->max_batch <= 0 || cfg->n_layers <= 0) return tfail(TLD_ERR_INVALID, "bad configuration");
-    DevGuard dg(cfg->device_id);
+        return fail(TLD_ERR_INVALID, "the training step supports image_size / patch_size = G with G a multiple of 4, 4 <= G <= 64 (16 .. 4096 tokens); got G = %d", G);
+    if (cfg->n_channels * cfg->patch_size * cfg->patch_size > 64) return fail(TLD_ERR_INVALID, "patch_dim must be <= 64");
+    if (cfg->noise_embed_dims % 2 || cfg->max_batch <= 0 || cfg->n_layers <= 0) return fail(TLD_ERR_INVALID, "bad configuration");
+    DeviceGuard dg(cfg->device_id);
     tld_train* e = new tld_train();
     e->cfg = *cfg;
     e->d = cfg->embed_dim; e->L = cfg->n_layers; e->H = e->d / 64; e->G = G; e->N = G * G; e->S = cfg->image_size; e->C = cfg->n_channels;
@@ -337,7 +271,7 @@ int tld_train_create(const tld_config* cfg, tld_train** out) {
     add_t(e, "label_proj.weight", (int64_t)d * e->text, &e->lbw); add_t(e, "label_proj.bias", d, &e->lbb);
 
     const size_t B = e->B, M = B * e->N;
-    if (M * (size_t)hid * 2 >= ((size_t)1 << 32)) { delete e; return tfail(TLD_ERR_INVALID, "max_batch too large: the MLP hidden activation must stay below 4 GiB"); }
+    if (M * (size_t)hid * 2 >= ((size_t)1 << 32)) { delete e; return fail(TLD_ERR_INVALID, "max_batch too large: the MLP hidden activation must stay below 4 GiB"); }
     auto cleanup = [&](int rc) { for (void* p : e->allocs) hipFree(p); delete e; return rc; };
     auto alloc_all = [&]() -> int {
         DALLOC(e->angular, e->ne / 2); DALLOC(e->zero_bias, 3 * hid > 4096 ? 3 * hid : 4096);
@@ -373,7 +307,7 @@ int tld_train_create(const tld_config* cfg, tld_train** out) {
         return 0;
     };
     if (int rc = alloc_all()) return cleanup(rc);
-    if (hipMemset(e->zero_bias, 0, (size_t)(3 * hid > 4096 ? 3 * hid : 4096) * 4) != hipSuccess) return cleanup(tfail(TLD_ERR_HIP, "hipMemset failed"));
+    if (hipMemset(e->zero_bias, 0, (size_t)(3 * hid > 4096 ? 3 * hid : 4096) * 4) != hipSuccess) return cleanup(fail(TLD_ERR_HIP, "hipMemset failed"));
     // angular_speeds = 2 pi exp(linspace(log 1, log 1000, ne / 2))   (tld/transformer_blocks.py:11-15; float32 arithmetic as torch does it)
     {
         const int half = e->ne / 2;
@@ -385,7 +319,7 @@ int tld_train_create(const tld_config* cfg, tld_train** out) {
             const float v = k < half / 2 ? lo + step * (float)k : hiv - step * (float)(half - 1 - k);
             a[k] = 2.0f * 3.14159265358979323846f * expf(v);
         }
-        if (hipMemcpy(e->angular, a.data(), half * 4, hipMemcpyHostToDevice) != hipSuccess) return cleanup(tfail(TLD_ERR_HIP, "hipMemcpy failed"));
+        if (hipMemcpy(e->angular, a.data(), half * 4, hipMemcpyHostToDevice) != hipSuccess) return cleanup(fail(TLD_ERR_HIP, "hipMemcpy failed"));
     }
     *out = e;
     return TLD_OK;
@@ -395,7 +329,7 @@ int64_t tld_train_param_count(const tld_train* e) { return e ? e->nparam : 0; }
 int32_t tld_train_tensor_count(const tld_train* e) { return e ? (int32_t)e->layout.size() : 0; }
 
 int tld_train_param_layout(const tld_train* e, int32_t index, char* key_out, int32_t key_cap, int64_t* offset, int64_t* numel) {
-    if (!e || index < 0 || index >= (int32_t)e->layout.size() || !key_out || key_cap <= 0) return tfail(TLD_ERR_INVALID, "bad argument");
+    if (!e || index < 0 || index >= (int32_t)e->layout.size() || !key_out || key_cap <= 0) return fail(TLD_ERR_INVALID, "bad argument");
     const Tensor& t = e->layout[index];
     snprintf(key_out, (size_t)key_cap, "%s", t.key.c_str());
     if (offset) *offset = t.off;
@@ -406,21 +340,21 @@ int tld_train_param_layout(const tld_train* e, int32_t index, char* key_out, int
 /* The sinusoid buffer "fourier_feats.0.angular_speeds" is a registered buffer of the reference, not a parameter; a checkpoint's
  * values can be installed here (host fp32 [noise_embed_dims / 2]); the default is the constructor's formula. */
 int tld_train_set_angular_speeds(tld_train* e, const float* host, int32_t n) {
-    if (!e || !host || n != e->ne / 2) return tfail(TLD_ERR_SHAPE, "angular_speeds must have %d entries", e ? e->ne / 2 : 0);
-    DevGuard dg(e->cfg.device_id);
+    if (!e || !host || n != e->ne / 2) return fail(TLD_ERR_SHAPE, "angular_speeds must have %d entries", e ? e->ne / 2 : 0);
+    DeviceGuard dg(e->cfg.device_id);
     HIP_TRY(hipMemcpy(e->angular, host, (size_t)n * 4, hipMemcpyHostToDevice));
     return TLD_OK;
 }
 
 int tld_train_bind(tld_train* e, float* params, float* grads) {
-    if (!e || !params || !grads) return tfail(TLD_ERR_INVALID, "null argument");
+    if (!e || !params || !grads) return fail(TLD_ERR_INVALID, "null argument");
     e->params = params; e->grads = grads; e->weights_fresh = false;
     return TLD_OK;
 }
 
 int tld_train_refresh_weights(tld_train* e, void* hip_stream) {
-    if (!e || !e->params) return tfail(TLD_ERR_STATE, "tld_train_bind first");
-    DevGuard dg(e->cfg.device_id);
+    if (!e || !e->params) return fail(TLD_ERR_STATE, "tld_train_bind first");
+    DeviceGuard dg(e->cfg.device_id);
     hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
     const int d = e->d, hid = e->hid;
     auto both = [&](int64_t off, int R, int Cc, bf16* w, bf16* wt) {       // [R, C] fp32 -> bf16 copy and bf16 transpose [C, R]
@@ -445,10 +379,10 @@ int tld_train_forward_backward(tld_train* e, const float* x_noisy, const float* 
 
 int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const float* noise_level, const float* label, const float* target,
                                   int32_t batch, float* loss_out, float* pred_out, void* hip_stream, tld_grad_ready_fn grad_ready, void* user) {
-    if (!e || !x_noisy || !noise_level || !label || !target || !loss_out || !pred_out) return tfail(TLD_ERR_INVALID, "null argument");
-    if (!e->params) return tfail(TLD_ERR_STATE, "tld_train_bind first");
-    if (batch <= 0 || batch > e->B) return tfail(TLD_ERR_INVALID, "batch %d outside [1, max_batch = %d]", batch, e->B);
-    DevGuard dg(e->cfg.device_id);
+    if (!e || !x_noisy || !noise_level || !label || !target || !loss_out || !pred_out) return fail(TLD_ERR_INVALID, "null argument");
+    if (!e->params) return fail(TLD_ERR_STATE, "tld_train_bind first");
+    if (batch <= 0 || batch > e->B) return fail(TLD_ERR_INVALID, "batch %d outside [1, max_batch = %d]", batch, e->B);
+    DeviceGuard dg(e->cfg.device_id);
     hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
     if (!e->weights_fresh) { if (int rc = tld_train_refresh_weights(e, hip_stream)) return rc; }
     const int d = e->d, hid = e->hid, pd = e->pd, N = e->N, H = e->H, B = batch, M = B * N, G = e->G;
@@ -466,7 +400,7 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
     if (e->debug) {
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)
-            return tfail(TLD_ERR_STATE, "a debug step (tld_train_set_debug) cannot be captured into a graph");
+            return fail(TLD_ERR_STATE, "a debug step (tld_train_set_debug) cannot be captured into a graph");
         if (int rc = debug_begin(e, B, s)) return rc;
     }
     // the three small fp32 products on the tiled kernel (see tld_train_kernels.h)
@@ -532,18 +466,18 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
         {
             GemmParams g{};
             g.A = b.a1; g.lda = d; g.W = b.wqkv; g.ldw = d; g.M = M; g.N = 3 * d; g.K = d; g.out_bf16 = b.qk; g.ldo = 2 * d; g.vt = b.vt; g.ntok = N; g.d = d;
-            GEMM_TRY(launch_gemm(g, EPI_QKV, s));
+            GEMM_TRY("training step", launch_gemm(g, EPI_QKV, s));
         }
         launch_attention(b.qk, b.vt, b.att, B, N, H, s);
         resid_ln(b.x1, b.att, b.x2, P + p.n2w, P + p.n2b, b.a2, b.st2);
         // x = x + CA(LN2 x, y)   (:62-72,137)
-        GEMM_TRY(gemm_bf16(b.a2, d, b.wq, d, e->zero_bias, b.qc, M, d, d, s));
+        GEMM_TRY("training step", gemm_bf16(b.a2, d, b.wq, d, e->zero_bias, b.qc, M, d, d, s));
         hipLaunchKernelGGL(cross_fwd_kernel, dim3(B * H), blk, 0, s, b.qc, b.kvc, b.cr, b.p0, N, d);
         resid_ln(b.x2, b.cr, b.x3, P + p.n3w, P + p.n3b, b.a3, b.st3);
         // x = x + MLPSepConv(LN3 x)   (:89-113,138)
-        GEMM_TRY(gemm_bf16(b.a3, d, b.wup, d, P + p.up_b, b.h, M, hid, d, s));
+        GEMM_TRY("training step", gemm_bf16(b.a3, d, b.wup, d, P + p.up_b, b.h, M, hid, d, s));
         hipLaunchKernelGGL(dwconv_kernel, dw_grid, blk, dw_lds, s, b.h, b.dww_t, P + p.dw_b, b.hc, b.gl, B, G, hid, 0, dw_rows);
-        GEMM_TRY(gemm_bf16(b.gl, hid, b.wdown, hid, P + p.down_b, b.o, M, d, hid, s));
+        GEMM_TRY("training step", gemm_bf16(b.gl, hid, b.wdown, hid, P + p.down_b, b.o, M, d, hid, s));
         bf16* xnext = i + 1 < e->L ? e->lb[i + 1].x1 : e->xfin;
         if (i + 1 < e->L) resid_ln(b.x3, b.o, xnext, P + e->lp[i + 1].n1w, P + e->lp[i + 1].n1b, e->lb[i + 1].a1, e->lb[i + 1].st1);      // + the next block's LN1
         else resid_ln(b.x3, b.o, xnext, (const float*)nullptr, (const float*)nullptr, (bf16*)nullptr, (float2*)nullptr);
@@ -676,8 +610,8 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
         // ---- MLP: o = g Wdown^T + b;  g = GELU(hc);  hc = dwconv(h);  h = a3 Wup^T + b;  a3 = LN3(x3)
         // (e->gxb = bf16(e->gx): written by whoever completed gx -- tail_dx_kernel for the top block, the LayerNorm-1 backward of the block above otherwise)
         colsum(e->gxb, M, d, Gd + p.down_b);
-        GEMM_TRY(weight_grad(e->gxb, d, b.gl, hid, Gd + p.down_w));
-        GEMM_TRY(gemm_bf16(e->gxb, d, b.wdown_t, d, e->zero_bias, e->dbig, M, hid, d, s));                         // dg = go Wdown
+        GEMM_TRY("training step", weight_grad(e->gxb, d, b.gl, hid, Gd + p.down_w));
+        GEMM_TRY("training step", gemm_bf16(e->gxb, d, b.wdown_t, d, e->zero_bias, e->dbig, M, hid, d, s));                         // dg = go Wdown
         SNAP(sn + "dg", e->dbig, ST_BF16, s, M, hid);
         const bool dw_fused = G <= 16 && N >= 176 && hid % 64 == 0;
         if (dw_fused) {      PATH(PB_DW_FUSED);      // GELU' multiply, depthwise weight-gradient partials and input gradient in one pass (both images of a (sample, 64-channel chunk) in LDS)
@@ -693,8 +627,8 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
         }
         SNAP(sn + "dh", b.gl, ST_BF16, s, M, hid);
         if (!dw_fused) colsum(b.gl, M, hid, Gd + p.up_b);
-        GEMM_TRY(weight_grad(b.gl, hid, b.a3, d, Gd + p.up_w));
-        GEMM_TRY(gemm_bf16(b.gl, hid, b.wup_t, hid, e->zero_bias, e->dsmall2, M, d, hid, s));                     // da3 = dh Wup
+        GEMM_TRY("training step", weight_grad(b.gl, hid, b.a3, d, Gd + p.up_w));
+        GEMM_TRY("training step", gemm_bf16(b.gl, hid, b.wup_t, hid, e->zero_bias, e->dsmall2, M, d, hid, s));                     // da3 = dh Wup
         SNAP(sn + "da3", e->dsmall2, ST_BF16, s, M, d);
         ln_bwd_rows(e->dsmall2, b.x3, b.st3, P + p.n3w, e->gx, 1, Gd + p.n3w, Gd + p.n3b, M, d);
         SNAP(sn + "gx.ln3", e->gx, ST_F32, s, M, d);
@@ -703,21 +637,21 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
         hipLaunchKernelGGL(cross_bwd_kernel, dim3(B * H), blk, 0, s, e->gx, b.qc, b.kvc, b.p0, e->dsmall2, dkv, N, d);   // dqc -> dsmall2
         SNAP(sn + "dqc", e->dsmall2, ST_BF16, s, M, d); SNAP(sn + "dkv", dkv, ST_F32, s, 2 * B, 2 * d);
         lin_dw(dkv, 2 * d, e->y, d, Gd + p.kv, nullptr, 2 * B, 2 * d, d);       // (per block: its gradient range must be complete at the grad_ready call below)
-        GEMM_TRY(weight_grad(e->dsmall2, d, b.a2, d, Gd + p.q));
-        GEMM_TRY(gemm_bf16(e->dsmall2, d, b.wq_t, d, e->zero_bias, e->dsmall, M, d, d, s));                       // da2 = dqc Wq
+        GEMM_TRY("training step", weight_grad(e->dsmall2, d, b.a2, d, Gd + p.q));
+        GEMM_TRY("training step", gemm_bf16(e->dsmall2, d, b.wq_t, d, e->zero_bias, e->dsmall, M, d, d, s));                       // da2 = dqc Wq
         SNAP(sn + "da2", e->dsmall, ST_BF16, s, M, d);
         ln_bwd_rows(e->dsmall, b.x2, b.st2, P + p.n2w, e->gx, 1, Gd + p.n2w, Gd + p.n2b, M, d);
         SNAP(sn + "gx.ln2", e->gx, ST_F32, s, M, d);
         // ---- self-attention: att = SDPA(q, k, v);  qkv = a1 Wqkv^T;  a1 = LN1(x1)
         int attn_path = 0;
-        if (launch_attention_bwd(b.qk, b.vt, b.att, e->gx, e->dsmall, e->attn_stats, B, N, H, s, &attn_path)) return tfail(TLD_ERR_INVALID, "attention backward: unsupported token count %d", N);
+        if (launch_attention_bwd(b.qk, b.vt, b.att, e->gx, e->dsmall, e->attn_stats, B, N, H, s, &attn_path)) return fail(TLD_ERR_INVALID, "attention backward: unsupported token count %d", N);
         if (attn_path & 1) PATH(PB_ATT_ONE);
         if (attn_path & 2) PATH(PB_ATT_TWO);
         if (attn_path & 4) PATH(PB_ATT_MASKED);
         SNAP(sn + "dqkv", e->dsmall, ST_BF16, s, M, 3 * d);
         // (dO as a bf16 copy from the LayerNorm-2 backward: 192 -> 189 us, but delta = dO . O from rounded dO moves the worst g15 gradient from 1.86e-2 to 1.92e-2 of a 2e-2 bound: not taken)
-        GEMM_TRY(weight_grad(e->dsmall, 3 * d, b.a1, d, Gd + p.qkv));
-        GEMM_TRY(gemm_bf16(e->dsmall, 3 * d, b.wqkv_t, 3 * d, e->zero_bias, e->dsmall2, M, d, 3 * d, s));         // da1 = dqkv Wqkv
+        GEMM_TRY("training step", weight_grad(e->dsmall, 3 * d, b.a1, d, Gd + p.qkv));
+        GEMM_TRY("training step", gemm_bf16(e->dsmall, 3 * d, b.wqkv_t, 3 * d, e->zero_bias, e->dsmall2, M, d, 3 * d, s));         // da1 = dqkv Wqkv
         SNAP(sn + "da1", e->dsmall2, ST_BF16, s, M, d);
         ln_bwd_rows(e->dsmall2, b.x1, b.st1, P + p.n1w, e->gx, 1, Gd + p.n1w, Gd + p.n1b, M, d, i > 0 ? e->gxb : nullptr);
         SNAP(sn + "gx.ln1", e->gx, ST_F32, s, M, d);
@@ -769,8 +703,8 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
  * grad_scale multiplies the gradient first (1 / world_size after a SUM all-reduce). */
 int tld_train_adam_ema(tld_train* e, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t numel, float lr,
                        float beta1, float beta2, float eps, int32_t step, float ema_alpha, float grad_scale, void* hip_stream) {
-    if (!params || !grads || !exp_avg || !exp_avg_sq || numel <= 0 || step <= 0) return tfail(TLD_ERR_INVALID, "bad argument");
-    DevGuard dg(e ? e->cfg.device_id : 0);
+    if (!params || !grads || !exp_avg || !exp_avg_sq || numel <= 0 || step <= 0) return fail(TLD_ERR_INVALID, "bad argument");
+    DeviceGuard dg(e ? e->cfg.device_id : 0);
     hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
     const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
     hipLaunchKernelGGL(adam_ema_kernel, g1((size_t)numel), dim3(256), 0, s, params, grads, exp_avg, exp_avg_sq, ema, (size_t)numel, lr, beta1, beta2, eps, bc1, bc2,
@@ -785,11 +719,11 @@ int tld_train_adam_ema(tld_train* e, float* params, const float* grads, float* e
  * (dq | dk | dv); scratch: 2 * batch * heads * ntok floats (used when ntok > 256).  Device pointers. */
 int tld_debug_attention_bwd(const void* qk, const void* vt, const void* o, const float* g, void* dqkv, float* scratch, int32_t batch, int32_t ntok,
                             int32_t heads, void* hip_stream) {
-    if (!qk || !vt || !o || !g || !dqkv || batch <= 0 || heads <= 0 || ntok <= 0) return tfail(TLD_ERR_INVALID, "bad argument");
+    if (!qk || !vt || !o || !g || !dqkv || batch <= 0 || heads <= 0 || ntok <= 0) return fail(TLD_ERR_INVALID, "bad argument");
     PtrDeviceGuard guard(qk);
     if (launch_attention_bwd(reinterpret_cast<const bf16*>(qk), reinterpret_cast<const bf16*>(vt), reinterpret_cast<const bf16*>(o), g,
                              reinterpret_cast<bf16*>(dqkv), scratch, batch, ntok, heads, reinterpret_cast<hipStream_t>(hip_stream)))
-        return tfail(TLD_ERR_INVALID, "attention backward: unsupported token count %d (or no scratch)", ntok);
+        return fail(TLD_ERR_INVALID, "attention backward: unsupported token count %d (or no scratch)", ntok);
     HIP_TRY(hipGetLastError());
     return TLD_OK;
 }
@@ -797,62 +731,46 @@ int tld_debug_attention_bwd(const void* qk, const void* vt, const void* o, const
 /* Test hook: the weight-gradient product dW[n_out, k_in] = dY^T X of the training step (dY [rows, n_out], X [rows, k_in] bf16 row-major, fp32 out)
  * on the transposed-operand GEMM; `slices`: fp32 workspace of slice_floats elements for the split-K partial sums.  Device pointers. */
 int tld_debug_wgrad(const void* dy, const void* x, float* dw, float* slices, int64_t slice_floats, int32_t rows, int32_t n_out, int32_t k_in, void* hip_stream) {
-    if (!dy || !x || !dw || !slices || rows <= 0) return tfail(TLD_ERR_INVALID, "bad argument");
+    if (!dy || !x || !dw || !slices || rows <= 0) return fail(TLD_ERR_INVALID, "bad argument");
     PtrDeviceGuard guard(dy);
     if (!wgrad_tn(reinterpret_cast<const bf16*>(dy), n_out, reinterpret_cast<const bf16*>(x), k_in, rows, dw, slices, (size_t)slice_floats,
                   reinterpret_cast<hipStream_t>(hip_stream)))
-        return tfail(TLD_ERR_SHAPE, "n_out and k_in must be multiples of 256, rows a multiple of 64");
+        return fail(TLD_ERR_SHAPE, "n_out and k_in must be multiples of 256, rows a multiple of 64");
     HIP_TRY(hipGetLastError());
     return TLD_OK;
 }
 
 int tld_train_set_debug(tld_train* e, int32_t enable) {
-    if (!e) return tfail(TLD_ERR_INVALID, "null engine");
-    DevGuard dg(e->cfg.device_id);
+    if (!e) return fail(TLD_ERR_INVALID, "null engine");
+    DeviceGuard dg(e->cfg.device_id);
     e->paths = 0;
     if (enable) {
-        if (int rc = reserve_snapshots(e)) { free_stages(e); e->debug = false; return rc; }
+        if (int rc = reserve_snapshots(e)) { e->stages.free_all(); e->debug = false; return rc; }
         e->debug = true;
     } else {
         e->debug = false;
         (void)hipDeviceSynchronize();
-        free_stages(e);
+        e->stages.free_all();
     }
     return TLD_OK;
 }
 
 int tld_train_read_stage(tld_train* e, const char* name, float* host_out, int64_t numel, int64_t* shape_out) {
-    if (!e || !name) return tfail(TLD_ERR_INVALID, "null argument");
-    DevGuard dg(e->cfg.device_id);
-    auto it = e->stages.find(name);
-    if (it == e->stages.end() || !it->second.live || !it->second.ptr)
-        return tfail(TLD_ERR_KEY, "no captured stage named '%s' (tld_train_set_debug before the step? a stage of the other depthwise form?)", name);
-    const Stage& st = it->second;
-    const int64_t n = st.shape[0] * st.shape[1] * st.shape[2] * st.shape[3];
-    if (shape_out) for (int k = 0; k < 4; ++k) shape_out[k] = st.shape[k];
-    if (!host_out) return TLD_OK;
-    if (numel != n) return tfail(TLD_ERR_SHAPE, "stage '%s' has %lld elements, caller gave %lld", name, (long long)n, (long long)numel);
-    HIP_TRY(hipDeviceSynchronize());
-    if (st.dtype == ST_F32) {
-        HIP_TRY(hipMemcpy(host_out, st.ptr, (size_t)n * 4, hipMemcpyDeviceToHost));
-    } else {       // bf16 -> fp32 on the host: the upper half of the word
-        std::vector<uint16_t> tmp((size_t)n);
-        HIP_TRY(hipMemcpy(tmp.data(), st.ptr, (size_t)n * 2, hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < n; ++i) { const uint32_t u = (uint32_t)tmp[(size_t)i] << 16; memcpy(host_out + i, &u, 4); }
-    }
-    return TLD_OK;
+    if (!e || !name) return fail(TLD_ERR_INVALID, "null argument");
+    DeviceGuard dg(e->cfg.device_id);
+    return e->stages.read(name, host_out, numel, shape_out);      // (host_out null: the shape only)
 }
 
 int tld_train_debug_paths(tld_train* e, uint64_t* mask) {
-    if (!e || !mask) return tfail(TLD_ERR_INVALID, "null argument");
+    if (!e || !mask) return fail(TLD_ERR_INVALID, "null argument");
     *mask = e->paths;
     return TLD_OK;
 }
 
 int tld_train_destroy(tld_train* e) {
     if (!e) return TLD_OK;
-    DevGuard dg(e->cfg.device_id);
-    free_stages(e);
+    DeviceGuard dg(e->cfg.device_id);
+    e->stages.free_all();
     for (void* p : e->allocs) hipFree(p);
     delete e;
     return TLD_OK;

@@ -15,6 +15,7 @@
 // two-stage fp32 / fp64 reduction and its affine + SiLU one elementwise pass.
 #include "../../include/tld_hip.h"
 #include "tld_common.h"
+#include "tld_host.h"
 
 #include <algorithm>
 #include <cmath>
@@ -32,48 +33,6 @@ namespace {
 
 constexpr unsigned kHdr = 2048;       // zero page in front of every activation buffer (bytes): one pixel of up to 1024 channels
 constexpr float kGnEps = 1e-6f;       // AutoencoderKL: every GroupNorm is built with eps = 1e-6
-
-int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    set_last_error(buf);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t _e = (expr);                                                                    \
-        if (_e != hipSuccess)                                                                      \
-            return fail(TLD_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
-
-inline uint16_t f32_to_bf16_rne(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-inline float bf16_to_f32(uint16_t h) {
-    uint32_t u = (uint32_t)h << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-
-struct DeviceGuard {
-    int prev = -1; bool switched = false;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
-        else if (prev < 0) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
-    DeviceGuard(const DeviceGuard&) = delete;
-    DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
 
 // ---- kernels -----------------------------------------------------------------------------------------------------------
 
@@ -252,8 +211,6 @@ __global__ void vae_cast_in_kernel(const void* __restrict__ src, int dtype, floa
 
 // ---- host structures ---------------------------------------------------------------------------------------------------
 
-struct HostTensor { std::vector<float> data; std::vector<int64_t> shape; };
-
 struct ConvW { bf16* w = nullptr; float* b = nullptr; int cin = 0, cout = 0, k = 0; };     // [cout][k*k*cin] (tap-major), fp32 bias
 struct GnW { float* g = nullptr; float* b = nullptr; int c = 0; };
 struct Resnet { GnW n1, n2; ConvW c1, c2, sc; bool has_sc = false; int cin = 0, cout = 0; };
@@ -261,18 +218,14 @@ struct UpBlock { std::vector<Resnet> res; bool has_up = false; ConvW up; int cou
 
 enum VClass { VC_CONV = 0, VC_GEMM, VC_GN, VC_OTHER, VC_COUNT };
 
-struct Stage { std::string name; bf16* dev = nullptr; int B = 0, C = 0, H = 0, W = 0; };
-
 // What resnet() / attention() / group_norm() / conv3x3() and the weight packing work on: the state the decoder and the encoder have in
 // common.  Each engine owns one next to its own config and its own layers; nothing here knows which of the two it serves.
-struct VaeCore {
+struct VaeCore : DeviceArena {
     int device_id = 0, max_batch = 0, G = 32;
     int C0 = 0, hl = 0;                   // the mid block's width and side
     bool mid_attn = false;
     bool finalized = false;
     std::map<std::string, HostTensor> host;
-    std::vector<void*> allocs;
-    int64_t weight_bytes = 0;
 
     // weights of the part both halves have: mid block, its attention, the output norm and convolution
     float* zero_bias = nullptr;
@@ -298,36 +251,13 @@ struct VaeCore {
     bool have_partial = false;
     bool fuse_stats = true;               // GroupNorm statistics in the producing conv epilogue wherever the shapes allow
     bool debug = false;
-    std::vector<Stage> stages;
+    StageStore stages;                    // the stage hook (tld_host.h): bf16 NHWC copies, their memory taken at capture (sizes follow the call)
     bool profile = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[VC_COUNT];
     size_t ev_used[VC_COUNT] = {0, 0, 0, 0};
 
     bf16* data(int i) const { return reinterpret_cast<bf16*>(buf[i] + kHdr); }
 };
-
-template <typename T>
-int dev_alloc(VaeCore* v, T** out, size_t count, bool weight = false) {
-    void* p = nullptr;
-    HIP_TRY(hipMalloc(&p, count * sizeof(T) > 0 ? count * sizeof(T) : 16));
-    v->allocs.push_back(p);
-    if (weight) v->weight_bytes += (int64_t)(count * sizeof(T));
-    *out = reinterpret_cast<T*>(p);
-    return TLD_OK;
-}
-
-int upload_f32(VaeCore* v, const std::vector<float>& h, float** out) {
-    if (int rc = dev_alloc(v, out, h.size(), true)) return rc;
-    HIP_TRY(hipMemcpy(*out, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-    return TLD_OK;
-}
-int upload_bf16(VaeCore* v, const std::vector<float>& h, bf16** out) {
-    std::vector<uint16_t> t(h.size());
-    for (size_t i = 0; i < h.size(); ++i) t[i] = f32_to_bf16_rne(h[i]);
-    if (int rc = dev_alloc(v, out, h.size(), true)) return rc;
-    HIP_TRY(hipMemcpy(*out, t.data(), t.size() * 2, hipMemcpyHostToDevice));
-    return TLD_OK;
-}
 
 const HostTensor* find(const VaeCore* v, const std::string& key) {
     auto it = v->host.find(key);
@@ -414,12 +344,6 @@ bool chan_ok(int c) { return c == 64 || c == 128 || c == 256 || c == 512 || c ==
 
 // ---- op sequencing ---------------------------------------------------------------------------------------------------
 
-int check_launch(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(TLD_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
-    return TLD_OK;
-}
-
 // GroupNorm (+ SiLU) of the [B, HW, C] image in buffer `src` into buffer `dst`
 int group_norm(VaeCore* v, int src, int dst, const GnW& gn, int B, int HW, int C, bool silu, hipStream_t s) {
     Timer t(v, VC_GN, s);
@@ -481,18 +405,7 @@ int gemm(VaeCore* v, const bf16* A, int lda, const bf16* Wt, int ldw, int M, int
 
 int snapshot(VaeCore* v, const char* name, int src, int B, int H, int W, int C, hipStream_t s) {
     if (!v->debug) return TLD_OK;
-    Stage st;
-    st.name = name; st.B = B; st.C = C; st.H = H; st.W = W;
-    const size_t n = (size_t)B * H * W * C;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&st.dev), n * 2));
-    HIP_TRY(hipMemcpyAsync(st.dev, v->data(src), n * 2, hipMemcpyDeviceToDevice, s));
-    v->stages.push_back(st);
-    return TLD_OK;
-}
-
-void clear_stages(VaeCore* v) {
-    for (auto& st : v->stages) (void)hipFree(st.dev);
-    v->stages.clear();
+    return v->stages.copy(name, v->data(src), ST_BF16, s, B, C, H, W, SL_NHWC, /*grow=*/true);
 }
 
 // ResnetBlock2D (diffusers models/resnet.py; temb is None in the VAE, output_scale_factor 1):
@@ -618,7 +531,7 @@ int core_create(VaeCore* c, const Cfg& cfg, int hl, size_t per, int side_max, si
 }
 
 void core_release(VaeCore* c) {
-    clear_stages(c);
+    c->stages.free_all();
     for (int k = 0; k < VC_COUNT; ++k)
         for (auto& e : c->ev[k]) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     for (void* p : c->allocs) (void)hipFree(p);
@@ -704,13 +617,13 @@ int core_finish_weights(VaeCore* c) {
     return TLD_OK;
 }
 
-// the checks and resets every decode / encode call starts with (under the caller's DeviceGuard: stages are freed here)
+// the checks and resets every decode / encode call starts with
 int core_begin_call(VaeCore* c, const void* in, const void* out, int32_t batch, int32_t io_dtype) {
     if (!in || !out) return fail(TLD_ERR_INVALID, "null argument");
     if (!c->finalized) return fail(TLD_ERR_STATE, "weights not finalized");
     if (batch < 1 || batch > c->max_batch) return fail(TLD_ERR_INVALID, "batch=%d outside 1..max_batch=%d", batch, c->max_batch);
     if (io_dtype != TLD_DTYPE_F32 && io_dtype != TLD_DTYPE_BF16 && io_dtype != TLD_DTYPE_F16) return fail(TLD_ERR_INVALID, "io_dtype=%d", io_dtype);
-    if (c->debug) clear_stages(c);
+    if (c->debug) c->stages.begin_call();
     for (int k = 0; k < VC_COUNT; ++k) if (!c->profile) c->ev_used[k] = 0;
     c->have_partial = false;
     return TLD_OK;
@@ -742,29 +655,14 @@ int norm_conv_out(VaeCore* c, int x, int B, int H, int W, int C, hipStream_t s) 
 int core_set_debug(VaeCore* c, int32_t enable) {
     DeviceGuard guard(c->device_id);
     c->debug = enable != 0;
-    if (!c->debug) clear_stages(c);
+    if (!c->debug) c->stages.free_all();
     return TLD_OK;
 }
 
 int core_read_stage(VaeCore* c, const char* name, float* host_out, int64_t numel, int64_t* shape4) {
     if (!name || !host_out) return fail(TLD_ERR_INVALID, "null argument");
     DeviceGuard guard(c->device_id);
-    for (const Stage& st : c->stages) {
-        if (st.name != name) continue;
-        const size_t n = (size_t)st.B * st.C * st.H * st.W;
-        if (shape4) { shape4[0] = st.B; shape4[1] = st.C; shape4[2] = st.H; shape4[3] = st.W; }
-        if ((int64_t)n != numel) return fail(TLD_ERR_SHAPE, "stage '%s' has %zu elements, caller passed %lld", name, n, (long long)numel);
-        HIP_TRY(hipDeviceSynchronize());
-        std::vector<uint16_t> tmp(n);
-        HIP_TRY(hipMemcpy(tmp.data(), st.dev, n * 2, hipMemcpyDeviceToHost));
-        const size_t HW = (size_t)st.H * st.W;
-        for (int b = 0; b < st.B; ++b)
-            for (size_t p = 0; p < HW; ++p)
-                for (int ch = 0; ch < st.C; ++ch)
-                    host_out[((size_t)b * st.C + ch) * HW + p] = bf16_to_f32(tmp[((size_t)b * HW + p) * st.C + ch]);
-        return TLD_OK;
-    }
-    return fail(TLD_ERR_KEY, "no captured stage named '%s' (set_debug before decode?)", name);
+    return c->stages.read(name, host_out, numel, shape4);
 }
 
 int core_set_profile(VaeCore* c, int32_t enable) {
