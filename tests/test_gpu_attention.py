@@ -40,7 +40,8 @@ def _ref(q, k, v):
 @pytest.mark.parametrize("N,B,H,scale", [(64, 3, 2, 1.0), (128, 2, 4, 1.0), (256, 3, 12, 1.0), (512, 2, 12, 1.0), (768, 1, 3, 1.0), (1024, 2, 12, 1.0), (1280, 1, 2, 2.0),
                                          (1024, 1, 4, 3.0), (2048, 1, 2, 6.0), (4096, 1, 2, 1.0),
                                          (1024, 1, 1, 1.0), (512, 3, 3, 1.0), (768, 5, 2, 1.0),      # (sample, head) pair counts that are not multiples of the 8 XCDs: attn2's padded 1-D grid (round 6)
-                                         (16, 5, 2, 1.0), (144, 3, 4, 1.0), (400, 2, 6, 2.0), (576, 2, 12, 1.0), (2008, 1, 2, 1.0)])   # masked chunked kernel: partial last chunk / query block
+                                         (16, 5, 2, 1.0), (144, 3, 4, 1.0), (400, 2, 6, 2.0), (576, 2, 12, 1.0), (2008, 1, 2, 1.0),    # masked chunked kernel: partial last chunk / query block
+                                         (1296, 2, 3, 1.0), (2304, 1, 3, 1.0), (3600, 1, 3, 1.0)])      # grids 36, 48 (nine chunks of attn2_kernel), 60 (28 x 128 + 16: the thinnest partial chunk)
 def test_attention_forward_vs_fp32(N, B, H, scale):
     g = torch.Generator().manual_seed(N + 7 * B + H)
     q = (torch.randn(B, N, H, 64, generator=g) * scale).to(torch.bfloat16)
@@ -72,3 +73,20 @@ def test_attention_rising_scores_advance_the_running_max():
     r = float((got - ref).pow(2).mean().sqrt() / ref.pow(2).mean().sqrt())
     print(f"rising scores: rel-rms {r:.2e}")
     assert torch.isfinite(got).all() and r <= ATT_TOL, r
+
+
+@pytest.mark.parametrize("N", [144, 400])
+@pytest.mark.parametrize("positive", [False, True])
+def test_attention_masked_kernel_with_every_score_strongly_signed(N, positive):
+    """The masked forward kernel on the all-negative-score input of tests/test_gpu_attn_bwd_classes.py (family 5: every q.k / 8 inside
+    -300 ... -150 log2 units, so a key past N, whose score would be 0, must stay out of the running max) and its mirror: finite, same bounds."""
+    from test_gpu_attn_bwd_classes import _bh, inputs
+    B, H = _bh(N)
+    q, k, v, _ = (t.view(B, N, H, 64).to(torch.bfloat16) for t in inputs(5, N, int(positive)))
+    got = _run(B, N, H, q, k, v).float().reshape(B, N, H, 64)
+    ref = _ref(q, k, v)
+    assert torch.isfinite(got).all()
+    r = float((got - ref).pow(2).mean().sqrt() / ref.pow(2).mean().sqrt())
+    row = ((got - ref).pow(2).sum(-1).sqrt() / ref.pow(2).sum(-1).sqrt().clamp_min(1e-6)).max().item()
+    print(f"attention N={N} scores {'above 150' if positive else 'below -150'} log2 units: rel-rms {r:.2e}, worst row {row:.2e}")
+    assert r <= ATT_TOL and row <= ATT_ROW_TOL, (r, row)

@@ -2,7 +2,7 @@
 counts whose attention backward tiles exactly (64, 256, 1024, 2304, 4096).
 
 The attention backward alone against torch autograd at token counts that are not multiples of its block (partial last block, and at
-N % 32 == 16 a half-empty 32 x 32 tile); whole training steps against autograd over the pinned restatement at G = 4, 12, 20, 24 and the
+N % 32 == 16 a half-empty 32 x 32 tile); whole training steps against autograd over the pinned restatement at G = 4, 12, 20, 24, 36, 44, 60 and the
 100 M width; graph replay against eager steps; the fine-tuning workflow from a 32-latent model to 48; the edges of the domain.
 Tolerances are those of tests/test_gpu_train.py: loss 5e-3 relative, prediction FWD_TOL rel-rms, gradients GRAD_TOL relative L2."""
 import ctypes as C
@@ -87,7 +87,8 @@ def _step_vs_oracle(cfg, B, seed, tag):
 # image_size 8: G = 4, 16 tokens (one 32-token block, half of it masked); 24: G = 12, 144 tokens (single-workgroup attention backward, the
 # three-kernel depthwise backward); 40: G = 20, 400 tokens (two-kernel path, a half-empty 32-token tile); 48: G = 24, 576 tokens (384 px).
 # The batches leave B N off a multiple of 64 rows at G = 4, 12 and 20 (the padded weight-gradient contraction).
-@pytest.mark.parametrize("image_size,B", [(8, 7), (24, 5), (40, 3), (48, 2)])
+# 72, 88, 120: G = 36, 44, 60 (1296, 1936, 3600 tokens): the 6- and 8-wave masked kernel pairs of the attention backward.
+@pytest.mark.parametrize("image_size,B", [(8, 7), (24, 5), (40, 3), (48, 2), (72, 2), (88, 1), (120, 1)])
 def test_new_grid_step_vs_oracle_autograd(image_size, B):
     from transformer_latent_diffusion_amd import DenoiserConfig
     cfg = DenoiserConfig(image_size=image_size, n_channels=4, n_layers=1)

@@ -20,8 +20,15 @@ pile up, so the bounds are per element, or per class where a kernel has intermed
   256-row tile, each sample, corner / edge / interior / band-seam pixels, each (sample, head), dropped-label samples.  Bounds are at most
   twice the worst value measured on an MI355X over all cases (profiles/r10_train_stage_errors.txt), written beside each constant.
 
+* MODELLED (the attention backward, beside its MEASURED bound): dq, dk and dv per class of tests/test_gpu_attn_bwd_classes.py -- each (sample, head),
+  full / partial blocks, the half-outside tile, each owning wave -- against twice the error of the float64 rounding model
+  (train_stage_refs.attn_bwd_model, fp32-gradient form: the step passes its fp32 residual gradient) over the same member.  On an MI355X measured equals
+  the yardstick to three digits at every case (profiles/r11_attn_bwd_classes.txt, section 3).
+
 Every compared tensor is first checked for NaN / Inf (the poison), with the count in the message.
-CASES reach every launch path: test_cases_reach_every_launch_path holds the union of tld_train_debug_paths against the full mask.
+CASES reach every launch path: test_cases_reach_every_launch_path holds the union of tld_train_debug_paths against the full mask, and -- the one
+"masked" bit standing for several kernel pairs -- the (mode, waves, masked) instantiation of the attention backward of every product grid.
+Cases G4 ... G60 (d = 128, one block) run every grid the other cases leave out; they came after the mutation table below.
 
 The checks bite.  Eight numeric, in-bounds mutations of the kernels, one build each, each run once on an MI355X: this file, then the end-to-end
 gradient tests of tests/test_gpu_train.py (test_forward_backward_vs_reference_step g15 / g17, test_64_token_step..., test_wide_model_gradients...: "old 4").
@@ -61,6 +68,7 @@ import pytest
 import torch
 
 import train_stage_refs as R
+from test_gpu_attn_bwd_classes import GRIDS, compare as attn_bwd_compare, dispatch as attn_bwd_dispatch
 from test_gpu_parity import _dev
 
 pytestmark = pytest.mark.gpu
@@ -99,6 +107,11 @@ CASES = {
     "G": (_cfg(256, 128, 1), 2, 2),               # four depthwise bands, 16 key blocks
     "I": (_cfg(192, 16, 1), 2, 2),                # M = 128 with a width the untransposed weight gradient refuses: the transposing form, one run
 }
+# every other product grid G x G at the narrowest width (d = 128, one block): with B (144), C (1024), A (256), F (400), G (4096) and E (64) the
+# attention backward runs the instantiation of every grid the trainer accepts (test_cases_reach_every_launch_path), and the depthwise bands,
+# the position table and the tail run at those grids too
+for _G in (4, 24, 28, 36, 40, 44, 48, 52, 56, 60):
+    CASES[f"G{_G}"] = (_cfg(128, 2 * _G, 1), 1 if _G >= 52 else 2, 1 if _G >= 52 else 2)
 TN_OFF_CASES = ("A", "C")                         # case H: the transposing weight gradient with split runs (TLD_TRAIN_TN_WGRAD=0, fresh process)
 
 
@@ -395,6 +408,12 @@ def backward_block(r, i, weights_only=False):
     r.meas(s + "attention backward dqkv", "attn_bwd", S("dqkv"), dqkv, heads=True)
     for j, nm in enumerate(("dq", "dk", "dv")):
         r.meas(s + "attention backward " + nm, "attn_bwd", S("dqkv")[:, j * d:(j + 1) * d], dqkv[:, j * d:(j + 1) * d], heads=True)
+    # MODELLED: per class of tests/test_gpu_attn_bwd_classes.py against the rounding model, in the form of the instantiation the step runs
+    # (TG = float: the engine passes its fp32 residual gradient, so delta = dO . O takes dO unrounded)
+    model = torch.stack(R.attn_bwd_model(qk[:, :d].view(B, N, d), qk[:, d:].view(B, N, d), v3, S("att").view(B, N, d), S("gx.ln2").view(B, N, d), H, False))
+    r.fail += attn_bwd_compare(f"case {r.name} {s}attention backward", S("dqkv").view(B, N, 3 * d), dqkv.view(B, N, 3, d).permute(2, 0, 1, 3).contiguous(), model, H,
+                               attn_bwd_dispatch(N)[1], N)
+    del model
     r.round(s + "da1 = dqkv Wqkv", S("da1"), S("dqkv") @ S("wqkv"), K=3 * d)
     if i > 0:
         r.round(s + "gxb = bf16(gx)", S("gxb.ln1"), S("gx.ln1"))
@@ -531,6 +550,17 @@ def test_cases_reach_every_launch_path():
     for case in TN_OFF_CASES:
         mask |= (_TN_OFF[case] if case in _TN_OFF else _tn_off(case))["paths"]
     names = Trainer.PATH_NAMES
+    # the one "masked" bit stands for several kernel pairs: split it by the dispatch's (mode, NW, masked) at each case's token count, hold the
+    # three attention bits of every case against that, and require the instantiation of every product grid
+    reached = set()
+    for case, (kw, _, _) in CASES.items():
+        n = (kw["image_size"] // kw["patch_size"]) ** 2
+        mode, nw, masked = attn_bwd_dispatch(n)
+        bits = _PATHS[case] >> names.index("attn_bwd_one_kernel") & 7
+        assert bits == (1 if mode == "fused" else 2) | (4 if masked else 0), (case, n, bits, mode, nw, masked)
+        reached.add((mode, nw, masked))
+    unreached = sorted(n for n in GRIDS if attn_bwd_dispatch(n) not in reached)
+    assert not unreached, f"product grids whose attention-backward instantiation no case runs: {unreached}"
     missing = [names[b] for b in range(len(names)) if not mask >> b & 1]
     print(f"launch paths reached: {bin(mask).count('1')} of {len(names)} (mask {mask:#x})")
     assert not missing, "launch paths no case reaches: " + ", ".join(missing)

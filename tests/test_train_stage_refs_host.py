@@ -103,6 +103,37 @@ def test_attention_backward_alone(N):
         assert _rel(a, r) <= TOL
 
 
+@pytest.mark.parametrize("N", [48, 144])
+@pytest.mark.parametrize("g_is_bf16", [False, True])
+def test_attention_backward_rounding_model(N, g_is_bf16):
+    """attn_bwd_model, the yardstick of the attention-backward class tests: with every rounding off it is attn_bwd (itself held against
+    autograd here and in test_attention_backward_alone); with them on it differs from the exact result by a relative rms of the order of one
+    bf16 rounding -- above 2^-10 (the final rounding alone gives 2^-9 / sqrt(3) = 1.1e-3) and below 2^-6 -- in dq, dk and dv."""
+    gen = torch.Generator().manual_seed(8 + N)
+    B, H, d = 2, 3, 192
+    bf = R.bf16_round
+    q, k, v = bf(_rand(gen, B, N, d, scale=1.5)), bf(_rand(gen, B, N, d)), bf(_rand(gen, B, N, d))
+    g = _rand(gen, B, N, d, scale=0.1).float().double()
+    if g_is_bf16:
+        g = bf(g)
+    o = R.attn_fwd(q, k, v, H)
+    exact = R.attn_bwd(q, k, v, g, H)
+    sp = lambda t: t.view(B, N, H, 64).transpose(1, 2)
+    sdpa = lambda q_, k_, v_: torch.nn.functional.scaled_dot_product_attention(sp(q_), sp(k_), sp(v_)).transpose(1, 2).reshape(B, N, d)
+    for a, r in zip(exact, _vjp(sdpa, (q, k, v), g)):
+        assert _rel(a, r) <= TOL
+    for a, r in zip(R.attn_bwd_model(q, k, v, o, g, H, g_is_bf16, rounded=False), exact):
+        assert _rel(a, r) <= TOL
+    model = R.attn_bwd_model(q, k, v, bf(o), g, H, g_is_bf16)
+    for name, a, r in zip(("dq", "dk", "dv"), model, exact):
+        e = _rel(a, r)
+        print(f"N = {N}, bf16 g {g_is_bf16}: model vs exact {name} {e:.2e}")
+        assert torch.equal(a, bf(a)) and 2.0 ** -10 < e < 2.0 ** -6, (name, e)
+    if not g_is_bf16:           # the two forms differ only in delta: the fp32-g form keeps dO unrounded there
+        other = R.attn_bwd_model(q, k, v, bf(o), g, H, True)
+        assert not torch.equal(other[0], model[0]) and torch.equal(other[2], model[2])
+
+
 def test_cross_attention_alone():
     gen = torch.Generator().manual_seed(4)
     B, N, H, d = 3, 20, 2, 128

@@ -78,6 +78,28 @@ def attn_bwd(q, k, v, do, H):
     return _merge(ds @ kh), _merge(ds.transpose(-1, -2) @ qh), _merge(dv)
 
 
+def bf16_round(t):
+    """The bf16 rounding of an fp32 value, as a float64 tensor (the kernels round fp32 accumulators)."""
+    return t.float().bfloat16().to(t.dtype)
+
+
+def attn_bwd_model(q, k, v, o, g, H, g_is_bf16, rounded=True):
+    """Rounding model of csrc/tld_train_attn.hip: attn_bwd in float64 with the roundings the kernel documents and no others.  q, k, v, g
+    [B, N, d]; o [B, N, d] is the forward's output as the kernel reads it (bf16).  dO is rounded to bf16 for the dP, dV and dK products;
+    delta = dO . O takes dO unrounded when the kernel gets an fp32 gradient and the bf16 dO when it gets a bf16 one; P stays unrounded
+    inside dS = P o (dP - delta); dS is rounded to bf16 before dS K and dS^T Q, P before P^T dO; each output is scaled (1/8 for dq and dk)
+    and rounded once to bf16.  rounded=False switches every rounding off: attn_bwd again, with delta from o."""
+    r = bf16_round if rounded else (lambda t: t)
+    qh, kh, vh, oh, gh = (_heads(t, H) for t in (q, k, v, o, g))
+    sc = 1.0 / math.sqrt(qh.shape[-1])
+    gb = r(gh)
+    p = torch.softmax(qh @ kh.transpose(-1, -2) * sc, dim=-1)
+    delta = ((gb if g_is_bf16 else gh) * oh).sum(-1, keepdim=True)
+    ds = r(p * (gb @ vh.transpose(-1, -2) - delta))
+    dv = r(p).transpose(-1, -2) @ gb
+    return r(_merge(ds @ kh * sc)), r(_merge(ds.transpose(-1, -2) @ qh * sc)), r(_merge(dv))
+
+
 def cross_fwd(qc, kv, H):
     """Attention of every token over the two conditioning tokens: qc [B, N, d], kv [B, 2, 2 d] = (k | v) -> (out [B, N, d], p0 [B, N, H])."""
     d = qc.shape[-1]

@@ -223,8 +223,9 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_kernel(const bf16* __restric
                     st[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(sK, kt * 32 + l31, kc * 2 + hi), qf[kc], st[kt], 0, 0, 0);
             }
         };
-        // MASKED, last key block kb: scores of keys >= N become -inf before the row statistics, so P = 0 there.  (The dQ sweep needs no mask:
-        // a key past N has a zero K row, so its dS^T entry, finite, adds exactly nothing to dQ.)
+        // MASKED, last key block kb: scores of keys >= N become -inf before the row statistics and before P in the dQ sweep, so P = 0 there.
+        // (A key past N has a zero K row, so a finite dS^T entry would add exactly nothing to dQ -- but its score is 0 and its P = 2^-Lq, which
+        // is +inf for a query row whose real scores all lie below -128 in log2 units, and inf x 0 in the dQ product is NaN.)
         auto mask_keys = [&](int kb) {
 #pragma unroll
             for (int kt = 0; kt < NW; ++kt) {
@@ -309,6 +310,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_kernel(const bf16* __restric
                 stage_v(kb);
                 __syncthreads();
                 scores();
+                if (MASKED && kb == NB - 1) mask_keys(kb);   // P = 0 for keys >= N: their score is 0, and 2^-Lq overflows once Lq < -128
 #pragma unroll
                 for (int kt = 0; kt < NW; ++kt)
 #pragma unroll
