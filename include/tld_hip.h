@@ -540,6 +540,28 @@ TLD_API int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, co
  * ema may be NULL; grad_scale multiplies the gradient first (1 / world_size after a SUM all-reduce). */
 TLD_API int tld_train_adam_ema(tld_train* e, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t numel,
                                float lr, float beta1, float beta2, float eps, int32_t step, float ema_alpha, float grad_scale, void* hip_stream);
+/* The guarded optimizer step: clip_grad_norm_ (tld has none; torch.nn.utils.clip_grad_norm_ semantics) and the non-finite step skip of
+ * accelerate's GradScaler (Accelerator(mixed_precision="fp16"), tld/train.py:69), decided ON THE DEVICE: neither call makes the host wait.
+ * opt_state: caller-owned device fp64 [TLD_TRAIN_OPT_STATE_DOUBLES], all zeros = a fresh optimizer:
+ *   [0] t: optimizer steps applied     [1] steps skipped in total     [2] last_skipped (0 or 1)
+ *   [3] gradient norm of this step (of grads * grad_scale, before clipping; Inf or NaN when an element is non-finite)
+ *   [4] clip coefficient     [5] bc1 = 1 - beta1^t     [6] bc2 = 1 - beta2^t     [7] 0     [8 ..] 1024 partial sums of squares
+ * tld_train_grad_guard sums (grads[i] * grad_scale)^2 in double (fixed order, no atomics: bitwise repeatable; non-finite exactly when an
+ * element is) and applies, in double:
+ *   norm = sqrt(sum);  nonfinite = !isfinite(sum)
+ *   if (skip_nonfinite && nonfinite)  skipped += 1; last_skipped = 1; coef = 0;  t, bc1, bc2 unchanged
+ *   else  last_skipped = 0; t += 1; c = max_norm / (norm + 1e-6); coef = clip ? (c > 1 ? 1 : c) : 1;  bc1, bc2 from the new t
+ * (clip = max_norm > 0 and finite; the bias corrections use the float-rounded betas; a NaN norm with the skip off gives a NaN coefficient,
+ * as clip_grad_norm_(error_if_nonfinite=False) does).  TLD_ERR_INVALID before any HIP call: grads or opt_state NULL, numel <= 0, max_norm
+ * NaN, grads not 16-byte or opt_state not 8-byte aligned.  e may be NULL.
+ * tld_train_adam_ema_guarded is tld_train_adam_ema on gi = (grads[i] * grad_scale) * (float)coef with bc1 / bc2 read from opt_state; when
+ * last_skipped is set it touches nothing.  e and ema may be NULL. */
+#define TLD_TRAIN_OPT_STATE_DOUBLES (8 + 1024)
+TLD_API int tld_train_grad_guard(tld_train* e, const float* grads, int64_t numel, float grad_scale, double max_norm, int32_t skip_nonfinite,
+                                 float beta1, float beta2, double* opt_state, void* hip_stream);
+TLD_API int tld_train_adam_ema_guarded(tld_train* e, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t numel,
+                                       float lr, float beta1, float beta2, float eps, float ema_alpha, float grad_scale, const double* opt_state,
+                                       void* hip_stream);
 /* Test hook: self-attention backward alone (head_dim 64; ntok a multiple of 16): qk [M, 2d] bf16 (q | k), vt [B, H, 64, ntok]
  * bf16, o [M, d] bf16 (forward output), g [M, d] fp32 (dL/dO) -> dqkv [M, 3d] bf16 (dq | dk | dv).  scratch: 2 * batch * heads * ntok floats
  * (row statistics between the two kernels of the ntok > 256 path; may be NULL otherwise).  Device pointers. */

@@ -2,7 +2,8 @@
 """Time the native training step (tld/train.py:118-175): 100 M-parameter denoiser, 32x32x4 latents, the reference's
 TrainConfig (batch 128, Adam lr 3e-4, EMA 0.999).  One step = make_batch (host RNG, as the reference) + forward + backward + Adam + EMA.
 Prints one JSON line in bench.py's vocabulary.   tools/train_bench.py [--batch 128] [--steps 10] [--warmup 2] [--layers 12] [--image-size 32]
-[--patch-size 2] [--no-cpu-baseline]   (--image-size: the latent side, e.g. 48 = 576 tokens, the 384 px fine-tuning grid; the TFLOP/s figures
+[--patch-size 2] [--no-cpu-baseline] [--max-grad-norm X] [--skip-nonfinite]   (the last two: the guarded optimizer step, to time beside the plain one;
+--image-size: the latent side, e.g. 48 = 576 tokens, the 384 px fine-tuning grid; the TFLOP/s figures
 are quoted at the default 32 only, where the op count below applies)"""
 import argparse
 import json
@@ -24,6 +25,8 @@ ap.add_argument("--layers", type=int, default=12)
 ap.add_argument("--image-size", type=int, default=32)
 ap.add_argument("--patch-size", type=int, default=2)
 ap.add_argument("--no-cpu-baseline", action="store_true")
+ap.add_argument("--max-grad-norm", type=float, default=None)
+ap.add_argument("--skip-nonfinite", action="store_true")
 args = ap.parse_args()
 
 dev = torch.device("cuda", 0)
@@ -32,7 +35,7 @@ cfg = config_100m(S)
 cfg.patch_size = args.patch_size
 cfg.n_layers = args.layers
 tc = TrainConfig(batch_size=args.batch)
-tr = Trainer(cfg, tc, device=dev, init_seed=5, max_batch=args.batch)
+tr = Trainer(cfg, tc, device=dev, init_seed=5, max_batch=args.batch, max_grad_norm=args.max_grad_norm, skip_nonfinite=args.skip_nonfinite)
 g = torch.Generator().manual_seed(1)
 x = torch.randn(args.batch, 4, S, S, generator=g) * 0.8
 y = torch.randn(args.batch, 768, generator=g) * 0.5
@@ -71,6 +74,8 @@ line = {"metric": f"training samples/sec (100M denoiser, {S}x{S}x4 latents, fwd 
         "loss": float(loss), "algorithmic_tflops": step_tflop / ddt, "frac_of_bf16_mfma_peak": step_tflop / ddt / 2500.0,
         "roofline": {"bound": "mfma", "achieved": step_tflop / ddt, "peak": 2500.0, "unit": "TFLOP/s", "frac": step_tflop / ddt / 2500.0,
                      "note": "whole step (3 x the reference forward op count) over the device-only step time; per-kernel times: profiles/r05_train_kernel_stats.csv (rocprofv3 --kernel-trace --stats of this tool)"}}
+if tr.guarded:
+    line["optimizer_guard"] = dict(tr.optimizer_stats(), max_grad_norm=args.max_grad_norm, skip_nonfinite=args.skip_nonfinite)
 if not args.no_cpu_baseline:
     from oracle.torch_ref import train_step_reference
     from transformer_latent_diffusion_amd.weights import synth_state_dict

@@ -14,6 +14,8 @@ LIB_PATH = os.environ.get("TLD_LIB", os.path.join(_HERE, "libtld_hip.so"))   # T
 
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
 
+TRAIN_OPT_STATE_DOUBLES = 8 + 1024         # TLD_TRAIN_OPT_STATE_DOUBLES (include/tld_hip.h): the guarded optimizer step's fp64 state vector
+
 KERNEL_CLASSES = ("gemm_qkv", "gemm_up", "gemm_down", "attention", "cross_row", "dwconv_gelu", "layernorm",
                   "embed", "tail", "update", "conditioning")
 
@@ -32,7 +34,7 @@ ABI_SYMBOLS = (
     "tld_clip_create", "tld_clip_load_tensor", "tld_clip_finalize_weights", "tld_clip_encode_text", "tld_clip_set_debug", "tld_clip_read_stage", "tld_clip_weight_bytes",
     "tld_clip_destroy",
     "tld_train_create", "tld_train_param_count", "tld_train_tensor_count", "tld_train_param_layout", "tld_train_set_angular_speeds", "tld_train_bind",
-    "tld_train_refresh_weights", "tld_train_forward_backward", "tld_train_forward_backward_cb", "tld_train_adam_ema", "tld_debug_attention_bwd", "tld_debug_wgrad", "tld_debug_attention_fwd", "tld_debug_dwconv_gelu",
+    "tld_train_refresh_weights", "tld_train_forward_backward", "tld_train_forward_backward_cb", "tld_train_adam_ema", "tld_train_grad_guard", "tld_train_adam_ema_guarded", "tld_debug_attention_bwd", "tld_debug_wgrad", "tld_debug_attention_fwd", "tld_debug_dwconv_gelu",
     "tld_train_set_debug", "tld_train_read_stage", "tld_train_debug_paths", "tld_train_destroy",
     "tld_last_error",
 )
@@ -197,6 +199,9 @@ def lib() -> C.CDLL:
     L.tld_train_forward_backward.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp]
     L.tld_train_forward_backward_cb.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, GRAD_READY_FN, vp]
     L.tld_train_adam_ema.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64, f32, f32, f32, f32, i32, f32, f32, vp]
+    if hasattr(L, "tld_train_grad_guard"):           # (absent from A/B builds that predate the guarded optimizer step)
+        L.tld_train_grad_guard.argtypes = [vp, vp, C.c_int64, f32, C.c_double, i32, f32, f32, vp, vp]
+        L.tld_train_adam_ema_guarded.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64, f32, f32, f32, f32, f32, f32, vp, vp]
     L.tld_debug_attention_bwd.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     L.tld_debug_wgrad.argtypes = [vp, vp, vp, vp, C.c_int64, i32, i32, i32, vp]
     L.tld_debug_dwconv_gelu.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, i32, i32, i32, vp]

@@ -714,6 +714,49 @@ int tld_train_adam_ema(tld_train* e, float* params, const float* grads, float* e
     return TLD_OK;
 }
 
+static_assert(TLD_TRAIN_OPT_STATE_DOUBLES == GUARD_STATE_HEAD + GUARD_PARTS, "state layout of include/tld_hip.h");
+
+/* The guard in front of tld_train_adam_ema_guarded (state layout and finalize rule: include/tld_hip.h): the global norm of grads * grad_scale
+ * from 1024 fixed-order double partials (no atomics: bitwise repeatable), then clip coefficient / skip decision / Adam's step count and bias
+ * corrections into opt_state, all on the stream -- the host never waits. */
+int tld_train_grad_guard(tld_train* e, const float* grads, int64_t numel, float grad_scale, double max_norm, int32_t skip_nonfinite, float beta1,
+                         float beta2, double* opt_state, void* hip_stream) {
+    if (!grads || !opt_state) return fail(TLD_ERR_INVALID, "grad guard: null gradient or state pointer");
+    if (numel <= 0) return fail(TLD_ERR_INVALID, "grad guard: numel %lld", (long long)numel);
+    if (std::isnan(max_norm)) return fail(TLD_ERR_INVALID, "grad guard: max_norm is NaN (<= 0 or +inf: no clipping)");
+    if (((uintptr_t)grads & 15) || ((uintptr_t)opt_state & 7))
+        return fail(TLD_ERR_INVALID, "grad guard: grads must be 16-byte and opt_state 8-byte aligned");
+    DeviceGuard dg(e ? e->cfg.device_id : std::max(0, ptr_device(grads)));
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    const size_t n = (size_t)numel, chunk = ((n + GUARD_PARTS - 1) / GUARD_PARTS + 3) / 4 * 4;
+    const int clip = max_norm > 0.0 && !std::isinf(max_norm);
+    hipLaunchKernelGGL(grad_sqsum_kernel, dim3(GUARD_PARTS), dim3(256), 0, s, grads, n, chunk, grad_scale, opt_state + GUARD_STATE_HEAD);
+    hipLaunchKernelGGL(grad_guard_finalize_kernel, dim3(1), dim3(256), 0, s, opt_state, max_norm, clip, skip_nonfinite ? 1 : 0, beta1, beta2);
+    HIP_TRY(hipGetLastError());
+    return TLD_OK;
+}
+
+/* tld_train_adam_ema with the clip coefficient and the bias corrections read from opt_state on the device; a step the guard marked skipped
+ * leaves every vector as it was. */
+int tld_train_adam_ema_guarded(tld_train* e, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t numel, float lr,
+                               float beta1, float beta2, float eps, float ema_alpha, float grad_scale, const double* opt_state, void* hip_stream) {
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !opt_state || numel <= 0) return fail(TLD_ERR_INVALID, "bad argument");
+    if ((uintptr_t)opt_state & 7) return fail(TLD_ERR_INVALID, "opt_state must be 8-byte aligned");
+    DeviceGuard dg(e ? e->cfg.device_id : std::max(0, ptr_device(params)));
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    const size_t n = (size_t)numel;
+    const bool vec = !(((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)ema) & 15);
+    if (vec)
+        hipLaunchKernelGGL((adam_ema_guarded_kernel<true>), g1((n + 3) / 4), dim3(256), 0, s, params, grads, exp_avg, exp_avg_sq, ema, n, lr, beta1, beta2, eps,
+                           ema_alpha, grad_scale, opt_state);
+    else
+        hipLaunchKernelGGL((adam_ema_guarded_kernel<false>), g1(n), dim3(256), 0, s, params, grads, exp_avg, exp_avg_sq, ema, n, lr, beta1, beta2, eps, ema_alpha,
+                           grad_scale, opt_state);
+    HIP_TRY(hipGetLastError());
+    if (e && params == e->params) e->weights_fresh = false;          // the bf16 operand copies are stale now (a skipped step rebuilds the same ones)
+    return TLD_OK;
+}
+
 /* Test hook: backward of softmax(Q K^T / 8) V for `batch` samples x `heads` heads over `ntok` tokens (a multiple of 16).
  * qk [M, 2 d] bf16 (q | k), vt [B, H, 64, ntok] bf16, o [M, d] bf16 (the forward output), g [M, d] fp32 (dL/dO); dqkv [M, 3 d] bf16 out
  * (dq | dk | dv); scratch: 2 * batch * heads * ntok floats (used when ntok > 256).  Device pointers. */

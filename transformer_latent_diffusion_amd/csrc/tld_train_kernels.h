@@ -1141,5 +1141,117 @@ __global__ void adam_ema_kernel(float* __restrict__ p, const float* __restrict__
     if (ema) ema[i] = ema[i] * alpha + pi * (1.0f - alpha);   // ema.mul_(alpha).add_(param, alpha = 1 - alpha)
 }
 
+// ---- guarded optimizer step: global gradient norm, clip_grad_norm_ coefficient, GradScaler's non-finite skip (include/tld_hip.h) ---------
+// The state vector (fp64, caller-owned): [0] t  [1] skipped  [2] last_skipped  [3] norm  [4] coef  [5] bc1  [6] bc2  [7] 0  [8 ..] partials.
+constexpr int GUARD_PARTS = 1024;             // workgroups of grad_sqsum_kernel = partial sums: FIXED, so that the sum does not depend on the CU count
+constexpr int GUARD_STATE_HEAD = 8;
+
+// fixed-order tree over one double per thread of a 256-thread workgroup; the total is returned to every thread
+__device__ inline double block_sum_256(double a, double* sh) {
+    const int t = threadIdx.x;
+    sh[t] = a;
+    __syncthreads();
+#pragma unroll
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) sh[t] += sh[t + s];
+        __syncthreads();
+    }
+    return sh[0];
+}
+
+// part[b] = sum over workgroup b's chunk of (g[i] * grad_scale)^2.  Product, square and sum in double: the product of two fp32 values is exact
+// there and no finite fp32 input overflows the sum, so the sum is non-finite exactly when an element is.  g 16-byte aligned; chunk % 4 == 0.
+__global__ __launch_bounds__(256) void grad_sqsum_kernel(const float* __restrict__ g, size_t n, size_t chunk, float grad_scale, double* __restrict__ part) {
+    __shared__ double sh[256];
+    const size_t begin = (size_t)blockIdx.x * chunk;
+    const size_t end = begin < n ? (n - begin < chunk ? n : begin + chunk) : begin;
+    const size_t len = end - begin, nvec = len / 4;
+    const double sc = (double)grad_scale;
+    const float4* g4 = reinterpret_cast<const float4*>(g + begin);
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+#pragma unroll 4
+    for (size_t v = threadIdx.x; v < nvec; v += 256) {
+        const float4 q = g4[v];
+        const double x = (double)q.x * sc, y = (double)q.y * sc, z = (double)q.z * sc, w = (double)q.w * sc;
+        a0 = fma(x, x, a0); a1 = fma(y, y, a1); a2 = fma(z, z, a2); a3 = fma(w, w, a3);
+    }
+    const size_t ti = begin + nvec * 4 + threadIdx.x;           // scalar tail: the last chunk's len % 4 elements
+    if (ti < end) { const double x = (double)g[ti] * sc; a0 = fma(x, x, a0); }
+    const double tot = block_sum_256((a0 + a1) + (a2 + a3), sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = tot;
+}
+
+// One workgroup: the partials in a fixed order, then one lane applies the finalize rule of include/tld_hip.h to the state.  b1 / b2: the
+// float-rounded betas the optimizer kernel multiplies with; the bias corrections follow the steps APPLIED, not the steps attempted.
+__global__ __launch_bounds__(256) void grad_guard_finalize_kernel(double* __restrict__ st, double max_norm, int clip, int skip_nonfinite, float b1, float b2) {
+    __shared__ double sh[256];
+    const double* part = st + GUARD_STATE_HEAD;
+    const int t = threadIdx.x;
+    double a = 0.0;
+#pragma unroll
+    for (int k = 0; k < GUARD_PARTS / 256; ++k) a += part[t + 256 * k];
+    const double sum = block_sum_256(a, sh);
+    if (t != 0) return;
+    const double norm = sqrt(sum);
+    st[3] = norm;
+    st[7] = 0.0;
+    if (skip_nonfinite && !isfinite(sum)) {
+        st[1] += 1.0; st[2] = 1.0; st[4] = 0.0;
+        return;
+    }
+    const double steps = st[0] + 1.0;
+    const double c = max_norm / (norm + 1e-6);
+    st[0] = steps; st[2] = 0.0;
+    st[4] = clip ? (c > 1.0 ? 1.0 : c) : 1.0;
+    st[5] = 1.0 - pow((double)b1, steps);
+    st[6] = 1.0 - pow((double)b2, steps);
+}
+
+// adam_ema_kernel's arithmetic for one element with the clip coefficient folded into the gradient (e: the EMA value, used when has_ema)
+__device__ inline void adam_ema_guarded_one(float& p, float g, float& m, float& v, float& e, bool has_ema, float lr, float b1, float b2, float eps, float bc1,
+                                            float bc2, float alpha, float grad_scale, float coef) {
+    const float gi = (g * grad_scale) * coef;
+    const float mi = b1 * m + (1.0f - b1) * gi;
+    const float vi = b2 * v + (1.0f - b2) * gi * gi;
+    m = mi; v = vi;
+    const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
+    const float pi = p - (lr / bc1) * (mi / denom);
+    p = pi;
+    if (has_ema) e = e * alpha + pi * (1.0f - alpha);
+}
+
+// adam_ema_kernel behind the guard: coef, bc1, bc2 come from the state vector; a skipped step (st[2] != 0) touches nothing.  VEC: four elements
+// per thread with 16-byte accesses (every vector 16-byte aligned), the last thread takes the numel % 4 tail one element at a time.
+template <bool VEC>
+__global__ __launch_bounds__(256) void adam_ema_guarded_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                               float* __restrict__ ema, size_t n, float lr, float b1, float b2, float eps, float alpha,
+                                                               float grad_scale, const double* __restrict__ st) {
+    if (st[2] != 0.0) return;
+    const float coef = (float)st[4], bc1 = (float)st[5], bc2 = (float)st[6];
+    const bool has_ema = ema != nullptr;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t first = VEC ? i * 4 : i;
+    if (first >= n) return;
+    if (VEC && n - first >= 4) {
+        float4 p4 = *reinterpret_cast<float4*>(p + first), m4 = *reinterpret_cast<float4*>(m + first), v4 = *reinterpret_cast<float4*>(v + first);
+        const float4 g4 = *reinterpret_cast<const float4*>(g + first);
+        float4 e4 = has_ema ? *reinterpret_cast<float4*>(ema + first) : make_float4(0.f, 0.f, 0.f, 0.f);
+        adam_ema_guarded_one(p4.x, g4.x, m4.x, v4.x, e4.x, has_ema, lr, b1, b2, eps, bc1, bc2, alpha, grad_scale, coef);
+        adam_ema_guarded_one(p4.y, g4.y, m4.y, v4.y, e4.y, has_ema, lr, b1, b2, eps, bc1, bc2, alpha, grad_scale, coef);
+        adam_ema_guarded_one(p4.z, g4.z, m4.z, v4.z, e4.z, has_ema, lr, b1, b2, eps, bc1, bc2, alpha, grad_scale, coef);
+        adam_ema_guarded_one(p4.w, g4.w, m4.w, v4.w, e4.w, has_ema, lr, b1, b2, eps, bc1, bc2, alpha, grad_scale, coef);
+        *reinterpret_cast<float4*>(p + first) = p4; *reinterpret_cast<float4*>(m + first) = m4; *reinterpret_cast<float4*>(v + first) = v4;
+        if (has_ema) *reinterpret_cast<float4*>(ema + first) = e4;
+        return;
+    }
+    const size_t last = VEC ? n : first + 1;                  // VEC: the numel % 4 tail, one element at a time
+    for (size_t j = first; j < last; ++j) {
+        float pj = p[j], mj = m[j], vj = v[j], ej = has_ema ? ema[j] : 0.f;
+        adam_ema_guarded_one(pj, g[j], mj, vj, ej, has_ema, lr, b1, b2, eps, bc1, bc2, alpha, grad_scale, coef);
+        p[j] = pj; m[j] = mj; v[j] = vj;
+        if (has_ema) ema[j] = ej;
+    }
+}
+
 }  // namespace train
 }  // namespace tld

@@ -96,7 +96,8 @@ class Trainer:
     def __init__(self, denoiser_cfg: DenoiserConfig, train_cfg: Optional[TrainConfig] = None, device="cuda",
                  state_dict: Optional[Mapping[str, torch.Tensor]] = None, init_seed: int = 0, max_batch: Optional[int] = None,
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, keep_ema: bool = True, process_group=None,
-                 overlap_allreduce: bool = True, use_graph: Optional[bool] = None):
+                 overlap_allreduce: bool = True, use_graph: Optional[bool] = None, max_grad_norm: Optional[float] = None,
+                 skip_nonfinite: bool = False):
         self.cfg = denoiser_cfg
         self.tc = train_cfg if train_cfg is not None else TrainConfig()
         dev = torch.device(device)
@@ -110,6 +111,13 @@ class Trainer:
             # training forward has no dropout; training a different model silently is worse than refusing (every published config has dropout = 0)
             raise NotImplementedError(f"DenoiserConfig.dropout = {denoiser_cfg.dropout}: the training engine implements dropout = 0 only")
         self.betas, self.eps = betas, eps
+        if max_grad_norm is not None and np.isnan(float(max_grad_norm)):
+            raise ValueError("max_grad_norm is NaN")
+        # the guarded optimizer step (optimizer_step): either option makes the trainer own the guard's fp64 device state vector
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.guarded = self.max_grad_norm is not None or self.skip_nonfinite
+        self._opt_state = None
         self.group = process_group
         self.layout = param_layout(denoiser_cfg)
         self.numel = sum(int(np.prod(s)) for _, s in self.layout.values())
@@ -127,6 +135,8 @@ class Trainer:
             self.params, self.grads, self.exp_avg, self.exp_avg_sq = z(), z(), z(), z()
             self.ema = z() if keep_ema else None
             self.step = 0
+            if self.guarded:              # all zeros = a fresh optimizer (include/tld_hip.h); a step allocates nothing
+                self._opt_state = torch.zeros(_lib.TRAIN_OPT_STATE_DOUBLES, dtype=torch.float64, device=self.device)
             sd = state_dict if state_dict is not None else {k: torch.from_numpy(np.array(v)) for k, v in synth_state_dict(denoiser_cfg, init_seed).items()}
             self.load_state_dict(sd)
             _lib.check(L.tld_train_bind(self._h, C.c_void_p(self.params.data_ptr()), C.c_void_p(self.grads.data_ptr())), "tld_train_bind")
@@ -432,7 +442,14 @@ class Trainer:
 
     def optimizer_step(self) -> None:
         """DDP gradient mean + Adam + EMA (tld/train.py:168-172).  The gradient sum over the ranks is either already in flight (per-block slices
-        started during the backward, ``overlap_allreduce``) or one all-reduce of the flat vector here."""
+        started during the backward, ``overlap_allreduce``) or one all-reduce of the flat vector here.
+
+        With ``max_grad_norm`` and / or ``skip_nonfinite`` the step is guarded on the device (``tld_train_grad_guard`` +
+        ``tld_train_adam_ema_guarded``, no host synchronisation): the global norm is that of the MEAN gradient of the whole step -- taken
+        after the all-reduce and after the accumulation over micro-batches, with the same 1 / world x 1 / micro-batches factor the optimizer
+        applies -- so it is the same on every rank, and every rank clips (``torch.nn.utils.clip_grad_norm_`` semantics) or skips (a
+        non-finite norm, as accelerate's ``GradScaler`` does) alike.  A skipped step changes nothing and does not advance Adam's bias
+        correction: ``self.step`` keeps counting the calls, the device's count of APPLIED steps (``optimizer_stats()``) is what Adam uses."""
         if self._acc_n:
             raise RuntimeError(f"optimizer_step in the middle of a gradient accumulation ({self._acc_n} micro-batches folded, none marked last); "
                                "finish it with a forward_backward(last_micro_batch=True) or drop it with reset_accumulation()")
@@ -450,10 +467,45 @@ class Trainer:
         self.step += 1
         stream = torch.cuda.current_stream(self.device).cuda_stream
         p = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None
+        if self.guarded:
+            L = _lib.lib()
+            b1, b2 = float(self.betas[0]), float(self.betas[1])
+            with torch.cuda.device(self.device):
+                _lib.check(L.tld_train_grad_guard(self._h, p(self.grads), self.numel, float(scale), self.max_grad_norm if self.max_grad_norm is not None else 0.0,
+                                                  int(self.skip_nonfinite), b1, b2, p(self._opt_state), C.c_void_p(stream)), "tld_train_grad_guard")
+                _lib.check(L.tld_train_adam_ema_guarded(self._h, p(self.params), p(self.grads), p(self.exp_avg), p(self.exp_avg_sq), p(self.ema), self.numel,
+                                                        float(self.tc.lr), b1, b2, float(self.eps), float(self.tc.alpha), float(scale), p(self._opt_state),
+                                                        C.c_void_p(stream)), "tld_train_adam_ema_guarded")
+            return
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().tld_train_adam_ema(self._h, p(self.params), p(self.grads), p(self.exp_avg), p(self.exp_avg_sq), p(self.ema), self.numel,
                                                      float(self.tc.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), self.step,
                                                      float(self.tc.alpha), float(scale), C.c_void_p(stream)), "tld_train_adam_ema")
+
+    # ---- the guard's readouts ----------------------------------------------------------------------------------------------------
+    def _need_guard(self) -> None:
+        if self._opt_state is None:
+            raise RuntimeError("this Trainer's optimizer step is not guarded (construct it with max_grad_norm= and / or skip_nonfinite=True)")
+
+    @property
+    def grad_norm(self) -> torch.Tensor:
+        """Global norm of the last step's mean gradient (before clipping; Inf or NaN when non-finite): a 0-d fp64 view of the device state --
+        reading the attribute does not synchronise, ``float()`` of it does."""
+        self._need_guard()
+        return self._opt_state[3]
+
+    def optimizer_stats(self) -> Dict[str, object]:
+        """Synchronises and returns the guard's state: ``grad_norm``, ``clip_coef``, ``applied_steps``, ``skipped_steps``, ``last_skipped``."""
+        self._need_guard()
+        t, skipped, last, norm, coef = self._opt_state[:5].cpu().tolist()
+        return {"grad_norm": norm, "clip_coef": coef, "applied_steps": int(t), "skipped_steps": int(skipped), "last_skipped": bool(last)}
+
+    def _set_applied_steps(self, t: int) -> None:
+        """The guard's state for an optimizer that has applied ``t`` steps (tld_train_grad_guard's formula, float-rounded betas in double)."""
+        st = torch.zeros(_lib.TRAIN_OPT_STATE_DOUBLES, dtype=torch.float64)
+        b1, b2 = (float(np.float32(b)) for b in self.betas)
+        st[0], st[5], st[6] = float(t), 1.0 - b1 ** t, 1.0 - b2 ** t
+        self._opt_state.copy_(st)
 
     def train_step(self, x: torch.Tensor, y: torch.Tensor, np_rng: Optional[np.random.Generator] = None,
                    generator: Optional[torch.Generator] = None) -> torch.Tensor:
@@ -512,10 +564,11 @@ class Trainer:
         """``torch.optim.Adam(model.parameters(), lr).state_dict()`` as the reference saves it (tld/train.py:86,152): per-parameter
         ``{step, exp_avg, exp_avg_sq}`` in ``named_parameters()`` order + one param group.  (Before the first step torch's ``state`` is empty.)"""
         state = {}
-        if self.step > 0:
+        step = self.optimizer_stats()["applied_steps"] if self.guarded else self.step      # (a checkpoint copies everything to the host anyway)
+        if step > 0:
             for i, (k, (o, s)) in enumerate(self.layout.items()):
                 n = int(np.prod(s))
-                state[i] = {"step": torch.tensor(float(self.step)), "exp_avg": self.exp_avg[o:o + n].view(*s).clone(),
+                state[i] = {"step": torch.tensor(float(step)), "exp_avg": self.exp_avg[o:o + n].view(*s).clone(),
                             "exp_avg_sq": self.exp_avg_sq[o:o + n].view(*s).clone()}
         group = {"lr": self.tc.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": 0, "amsgrad": False, "maximize": False,
                  "foreach": None, "capturable": False, "differentiable": False, "fused": None, "params": list(range(len(self.layout)))}
@@ -544,6 +597,8 @@ class Trainer:
         if groups:
             self.tc.lr = float(groups[0].get("lr", self.tc.lr))
             self.betas = tuple(groups[0].get("betas", self.betas)); self.eps = float(groups[0].get("eps", self.eps))
+        if self.guarded:                      # the device's count restarts from the checkpoint's applied steps; skips are not carried
+            self._set_applied_steps(self.step)
 
     def checkpoint(self) -> Dict[str, object]:
         """The dict the reference saves (tld/train.py:150-156): EMA weights, ``optimizer.state_dict()``, global step."""
