@@ -69,6 +69,23 @@ TLD_API int tld_engine_load_tensor(tld_engine* e, const char* key, const void* h
  * fails with TLD_ERR_STATE and names the first missing key if the state_dict was incomplete. */
 TLD_API int tld_engine_finalize_weights(tld_engine* e);
 
+/* Weights from a flat fp32 DEVICE vector, in place.  The vector is in tld_train_param_layout order -- the reference's
+ * Denoiser.named_parameters() order, i.e. the state_dict order without the two registered buffers -- so a training engine's `params` or EMA vector of the
+ * same configuration is one.  tld_engine_param_count is its length (= tld_train_param_count of a training engine with the same config; known from create on).
+ * tld_engine_refresh_weights rebuilds, with kernels enqueued on hip_stream, every weight image this engine holds in its mode (fp32 copies, bf16 casts,
+ * hi / lo splits, transposes, depthwise tap packings, the LayerNorm-1 / LayerNorm-3 folds with their column sums and packed rows, the e4m3 images with
+ * their E8M0 scales), each with exactly the bits tld_engine_finalize_weights computes from the same values on the host.  It allocates nothing, frees
+ * nothing, stages nothing through the host and synchronises neither the stream nor the device; flat_device is read until the stream has passed the
+ * call, and calls on this engine enqueued on the same stream afterwards see the new weights.  The pointer tables built at finalize, the activation
+ * buffers, the capacity, the GEMM mode, the low-latency class and the debug / profile state stay; angular_speeds is not a parameter and keeps its
+ * value; tld_engine_weight_bytes is unchanged.  A capturing stream is not refused (the call only launches kernels), but capture is not part of the tests.
+ * Refusals enqueue nothing and leave the weights as they were:
+ *   TLD_ERR_STATE  before tld_engine_finalize_weights (the first load goes through tld_engine_load_tensor);
+ *   TLD_ERR_SHAPE  numel differs from tld_engine_param_count;
+ *   TLD_ERR_INVALID  a null engine or vector. */
+TLD_API int64_t tld_engine_param_count(const tld_engine* e);
+TLD_API int tld_engine_refresh_weights(tld_engine* e, const float* flat_device, int64_t numel, void* hip_stream);
+
 /* Operand type of the QKV / MLP GEMMs: 0 = bf16 (default), 1 = MX-fp8 (OCP e4m3 elements with one E8M0 scale per 32
  * K-elements, v_mfma_scale_f32_32x32x64_f8f6f4).  Call between tld_engine_create and tld_engine_finalize_weights.
  * Not in the reference (its model_dtype is fp32 / fp16 / bf16, tld/configs.py:33-37): BASELINE config C4. */
@@ -281,6 +298,9 @@ TLD_API int tld_debug_gemm_splitk(const void* a_bf16, const void* w_bf16, float*
  * gemm_mx8: C[M,N] = dequant(A) . dequant(W)^T in fp32 from such operands (device).  K % 128 == 0, M % 4 == N % 4 == 0. */
 TLD_API int tld_debug_quant_mx8(const void* in_bf16, void* out_e4m3, void* out_scale, int32_t M, int32_t K, void* hip_stream);
 TLD_API int tld_debug_quant_mx8_host(const float* w, int32_t rows, int32_t K, void* out_e4m3, void* out_scale);
+/* quant_mx8_f32: the weight-side quantiser on the device (fp32 device matrix [rows,K] -> device outputs laid out as above), the kernel
+ * tld_engine_refresh_weights runs in the fp8 mode; its codes and scale bytes equal quant_mx8_host's on every input.  K % 128 == 0. */
+TLD_API int tld_debug_quant_mx8_f32(const float* in_device, void* out_e4m3, void* out_scale, int32_t rows, int32_t K, void* hip_stream);
 TLD_API int tld_debug_gemm_mx8(const void* a_e4m3, const void* a_scale, const void* w_e4m3, const void* w_scale, float* c_f32,
                                int32_t M, int32_t N, int32_t K, void* hip_stream);
 

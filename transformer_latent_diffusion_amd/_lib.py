@@ -23,6 +23,7 @@ KERNEL_CLASSES = ("gemm_qkv", "gemm_up", "gemm_down", "attention", "cross_row", 
 ABI_SYMBOLS = (
     "tld_engine_create", "tld_engine_load_tensor", "tld_engine_finalize_weights", "tld_denoiser_forward",
     "tld_sample", "tld_sample_from", "tld_sample_requests", "tld_sample_requests_guided", "tld_engine_sample_rows", "tld_engine_set_gemm_dtype", "tld_engine_set_low_latency", "tld_debug_gemm_splitk", "tld_debug_quant_mx8", "tld_debug_quant_mx8_host", "tld_debug_gemm_mx8",
+    "tld_engine_param_count", "tld_engine_refresh_weights", "tld_debug_quant_mx8_f32",
     "tld_debug_decode_stage", "tld_engine_set_debug", "tld_engine_read_stage", "tld_engine_stage_shape", "tld_engine_set_debug_step", "tld_engine_debug_paths", "tld_debug_gemm_bf16", "tld_debug_gemm_bench", "tld_debug_gemm_plan", "tld_debug_gemm_epilogue",
     "tld_engine_set_profile", "tld_engine_profile_reserve", "tld_engine_get_profile", "tld_engine_weight_bytes", "tld_engine_destroy",
     "tld_vae_create", "tld_vae_load_tensor", "tld_vae_finalize_weights", "tld_vae_decode", "tld_vae_set_debug",
@@ -131,6 +132,11 @@ def lib() -> C.CDLL:
     L.tld_debug_quant_mx8.argtypes = [vp, vp, vp, i32, i32, vp]
     L.tld_debug_quant_mx8_host.argtypes = [C.POINTER(C.c_float), i32, i32, vp, vp]
     L.tld_debug_gemm_mx8.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp]
+    if hasattr(L, "tld_engine_refresh_weights"):     # (absent from A/B builds that predate the device weight refresh)
+        L.tld_engine_param_count.argtypes = [vp]
+        L.tld_engine_param_count.restype = C.c_int64
+        L.tld_engine_refresh_weights.argtypes = [vp, vp, C.c_int64, vp]
+        L.tld_debug_quant_mx8_f32.argtypes = [vp, vp, vp, i32, i32, vp]
     if hasattr(L, "tld_debug_decode_stage"):         # (absent from A/B builds that predate the shared stage store)
         L.tld_debug_decode_stage.argtypes = [vp, vp, i32, i32, i64p, C.c_int64, i32, i32, C.POINTER(C.c_float), C.c_int64]
     L.tld_engine_set_debug.argtypes = [vp, i32]
@@ -215,7 +221,7 @@ def lib() -> C.CDLL:
         if "TLD_LIB" in os.environ and not hasattr(L, name):     # an older A/B build: symbols added since are simply absent (tests/test_abi.py checks the real library)
             continue
         if name not in ("tld_last_error", "tld_engine_weight_bytes", "tld_vae_weight_bytes", "tld_vae_enc_weight_bytes", "tld_clip_weight_bytes", "tld_train_param_count",
-                        "tld_train_tensor_count"):
+                        "tld_train_tensor_count", "tld_engine_param_count"):
             getattr(L, name).restype = C.c_int
     _lib = L
     return L

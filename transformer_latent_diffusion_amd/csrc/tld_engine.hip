@@ -7,6 +7,7 @@
 #include "../../include/tld_hip.h"
 #include "tld_common.h"
 #include "tld_host.h"
+#include "tld_refresh.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -28,23 +29,6 @@ void set_last_error(const char* msg) { snprintf(g_err, sizeof(g_err), "%s", msg)
 thread_local uint64_t* g_path_sink = nullptr;
 }  // namespace tld
 namespace {
-
-struct Layer {
-    bf16 *qkv_w = nullptr, *up_w = nullptr, *down_w = nullptr;
-    bf16 *qkv_wf = nullptr;                               // bf16(gamma1 (.) Wqkv): LayerNorm-1 folded into the QKV GEMM
-    float *qkv_c1 = nullptr, *qkv_b1 = nullptr;           // [3d] column sums of qkv_wf; beta1 . Wqkv^T
-    bf16 *qkv_wp = nullptr;                               // qkv_wf with its rows permuted to [head][q_h | k_h | v_h] (fused QKV -> attention kernel)
-    float *qkv_c1p = nullptr, *qkv_b1p = nullptr;         // the same permutation of qkv_c1 / qkv_b1
-    float *up_b = nullptr, *dw_w9c = nullptr, *dw_b = nullptr, *down_b = nullptr;
-    float *dw_w9c_half = nullptr, *dw_b_half = nullptr;   // 0.5 x (exact): operands of the fused up-projection epilogue
-    uint32_t* dw_wpk = nullptr;                           // the halved taps as packed bf16 pairs [3][4][hid] (EPI_UP_DWCONV2)
-    // MX-fp8 GEMM mode (tld_engine_set_gemm_dtype): e4m3 weights + E8M0 block scales [K/128][N][4]
-    uint8_t *qkv_w8 = nullptr, *qkv_s8 = nullptr, *up_w8 = nullptr, *up_s8 = nullptr, *down_w8 = nullptr, *down_s8 = nullptr;
-    bf16 *up_wf = nullptr;                                // bf16(gamma3 (.) Wup): LayerNorm-3 folded into the up-projection
-    float *up_c1 = nullptr, *up_b1 = nullptr;             // [hid] column sums of up_wf; up_b + beta3 . Wup^T
-    float *n1_w = nullptr, *n1_b = nullptr, *n2_w = nullptr, *n2_b = nullptr, *n3_w = nullptr, *n3_b = nullptr;
-    float *kv_w = nullptr, *q_w = nullptr;   // fp32, conditioning path
-};
 
 enum KClass { KC_GEMM_QKV = 0, KC_GEMM_UP, KC_GEMM_DOWN, KC_ATTN, KC_CROSS, KC_DWCONV, KC_LN, KC_EMBED,
               KC_TAIL, KC_UPDATE, KC_COND, KC_COUNT };
@@ -72,6 +56,8 @@ struct tld_engine : DeviceArena {      // (pad = 256: every allocation of this e
     bf16* plin_w_hl = nullptr;          // patch-embedding Linear weight as a split bf16 pair [2][d][pd] (embed_mfma_kernel)
     std::vector<Layer> layers;
     const float **tab_kv_w = nullptr, **tab_q_w = nullptr, **tab_n2_w = nullptr, **tab_n2_b = nullptr;   // [L] device tables
+    RefreshPlan refresh;                // tld_engine_refresh_weights: where every weight image above comes from in a flat parameter vector (built at finalize)
+    int64_t nparam = 0;                 // length of that vector (tld_engine_param_count)
 
     // activations (sized for cfg.max_batch)
     resid_t* x = nullptr;
@@ -756,6 +742,7 @@ int tld_engine_create(const tld_config* c, tld_engine** out) {
     e->pd = pd; e->hid = c->mlp_multiplier * c->embed_dim; e->img = c->n_channels * c->image_size * c->image_size;
     e->ne = c->noise_embed_dims; e->text = c->text_emb_size;
     e->layers.resize(e->L);
+    e->nparam = make_param_layout(e->d, e->L, e->ne, e->pd, e->hid, e->ntok, e->text).count;
     if (const char* fd = getenv("TLD_FUSE_DWCONV")) e->fuse_dwconv = atoi(fd) != 0;
     if (const char* sl = getenv("TLD_SHARE_L0")) e->share_l0 = atoi(sl) != 0;
     if (const char* gs = getenv("TLD_GUIDANCE_SKIP")) e->guidance_skip = atoi(gs) != 0;
@@ -1028,6 +1015,26 @@ int tld_engine_finalize_weights(tld_engine* e) {
         HIP_TRY(hipMemcpy(e->tab_n2_w, hg.data(), L * sizeof(float*), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(e->tab_n2_b, hb.data(), L * sizeof(float*), hipMemcpyHostToDevice));
     }
+    {   // tld_engine_refresh_weights: the blocks' image pointers as a device table, and the images outside the blocks with their places in the flat vector
+        const ParamLayout pl = make_param_layout(e->d, e->L, e->ne, e->pd, e->hid, e->ntok, e->text);
+        RefreshPlan& R = e->refresh;
+        R = RefreshPlan();
+        R.d = e->d; R.hid = e->hid; R.L = e->L; R.l0 = pl.layers[0]; R.layer_stride = pl.layer_stride();
+        R.fold = e->fold_ln1 || e->fold_ln3; R.fp8 = e->fp8;
+        Layer* ld = nullptr;
+        if (int rc = dev_alloc(e, &ld, (size_t)e->L)) return rc;
+        HIP_TRY(hipMemcpy(ld, e->layers.data(), (size_t)e->L * sizeof(Layer), hipMemcpyHostToDevice));
+        R.layers_dev = ld;
+        auto job = [&R](void* dst, int64_t src, int64_t n, int kind = RJ_COPY, int cols = 0) { if (dst) R.jobs[R.njobs++] = RefreshJob{dst, src, n, kind, cols}; };
+        job(e->ff1_w, pl.ff1w, d * ne); job(e->ff1_b, pl.ff1b, d); job(e->ff3_w, pl.ff3w, d * d); job(e->ff3_b, pl.ff3b, d);
+        job(e->label_w, pl.lbw, d * text); job(e->label_b, pl.lbb, d); job(e->norm_w, pl.nw, d); job(e->norm_b, pl.nb, d);
+        job(e->conv_w, pl.cvw, pd * cpp); job(e->conv_b, pl.cvb, pd); job(e->pln1_w, pl.l1w, pd); job(e->pln1_b, pl.l1b, pd);
+        job(e->plin_b, pl.lib, d); job(e->pln2_w, pl.l2w, d); job(e->pln2_b, pl.l2b, d); job(e->pos, pl.pos, N * d);
+        job(e->out_w, pl.outw, pd * d); job(e->out_b, pl.outb, pd);
+        job(e->out_w_hl, pl.outw, pd * d, RJ_SPLIT_HL); job(e->plin_w_hl, pl.liw, d * pd, RJ_SPLIT_HL);
+        job(e->plin_wt, pl.liw, d * pd, RJ_TRANSPOSE, (int)pd);
+        static_assert(kRefreshMaxJobs >= 21, "the images outside the blocks");
+    }
 
     const size_t B2 = (size_t)e->cfg.max_batch, M = B2 * e->ntok;
     if (int rc = dev_alloc(e, &e->x, M * d)) return rc;
@@ -1065,6 +1072,17 @@ int tld_engine_finalize_weights(tld_engine* e) {
     if (int rc = ensure_req_capacity(e, 64 * (sizeof(SamplerStepRow) + 8 * B2))) return rc;      // a 64-level call at full batch; larger calls grow it
     e->finalized = true;
     return TLD_OK;
+}
+
+int64_t tld_engine_param_count(const tld_engine* e) { return e ? e->nparam : 0; }
+
+int tld_engine_refresh_weights(tld_engine* e, const float* flat_device, int64_t numel, void* hip_stream) {
+    if (!e || !flat_device) return fail(TLD_ERR_INVALID, "null argument");
+    if (!e->finalized) return fail(TLD_ERR_STATE, "tld_engine_refresh_weights: weights not finalized (the first load goes through tld_engine_load_tensor)");
+    if (numel != e->nparam)
+        return fail(TLD_ERR_SHAPE, "tld_engine_refresh_weights: the flat vector has %lld elements, this configuration %lld", (long long)numel, (long long)e->nparam);
+    DeviceGuard dg(e->cfg.device_id);
+    return launch_refresh_weights(e->refresh, flat_device, static_cast<hipStream_t>(hip_stream));
 }
 
 int tld_engine_set_debug(tld_engine* e, int32_t enable) {
@@ -1399,6 +1417,14 @@ int tld_debug_quant_mx8(const void* in_bf16, void* out_e4m3, void* out_scale, in
     PtrDeviceGuard guard(in_bf16);
     launch_quant_mx8(static_cast<const bf16*>(in_bf16), static_cast<uint8_t*>(out_e4m3), static_cast<uint8_t*>(out_scale), M, K,
                      static_cast<hipStream_t>(hip_stream));
+    HIP_TRY(hipGetLastError());
+    return TLD_OK;
+}
+
+int tld_debug_quant_mx8_f32(const float* in_device, void* out_e4m3, void* out_scale, int32_t rows, int32_t K, void* hip_stream) {
+    if (!in_device || !out_e4m3 || !out_scale || rows <= 0 || K <= 0 || K % 128) return fail(TLD_ERR_INVALID, "bad argument (K %% 128 == 0)");
+    PtrDeviceGuard guard(in_device);
+    launch_quant_mx8_f32(in_device, static_cast<uint8_t*>(out_e4m3), static_cast<uint8_t*>(out_scale), rows, K, static_cast<hipStream_t>(hip_stream));
     HIP_TRY(hipGetLastError());
     return TLD_OK;
 }

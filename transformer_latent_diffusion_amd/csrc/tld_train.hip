@@ -14,6 +14,7 @@
 #include "../../include/tld_hip.h"
 #include "tld_train_kernels.h"
 #include "tld_host.h"
+#include "tld_param_layout.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -34,11 +35,8 @@ int launch_attention_bwd(const bf16* qk, const bf16* vt, const bf16* o, const bf
 
 namespace {
 
-struct Tensor { std::string key; int64_t off, numel; };
-
-struct LayerP {          // offsets into the flat parameter / gradient vectors
-    int64_t qkv, kv, q, up_w, up_b, dw_w, dw_b, down_w, down_b, n1w, n1b, n2w, n2b, n3w, n3b;
-};
+using Tensor = ParamTensor;      // the flat parameter / gradient vectors: tld_param_layout.h
+using LayerP = LayerOffsets;
 struct LayerB {          // engine-owned per-layer buffers
     bf16 *wqkv, *wqkv_t, *wq, *wq_t, *wup, *wup_t, *wdown, *wdown_t;          // bf16 GEMM operands and their transposes
     bf16 *x1, *x2, *x3;                                                      // residual stream at the input of the three sub-blocks
@@ -100,12 +98,6 @@ struct tld_train {
 };
 
 namespace {
-
-void add_t(tld_train* e, const std::string& k, int64_t n, int64_t* off) {
-    *off = e->nparam;
-    e->layout.push_back({k, e->nparam, n});
-    e->nparam += n;
-}
 
 template <typename T>
 int dalloc(tld_train* e, T** p, size_t n) {
@@ -243,32 +235,13 @@ int tld_train_create(const tld_config* cfg, tld_train** out) {
     e->B = cfg->max_batch;
     e->tn_wgrad = !(getenv("TLD_TRAIN_TN_WGRAD") && atoi(getenv("TLD_TRAIN_TN_WGRAD")) == 0);
     const int d = e->d, hid = e->hid, pd = e->pd;
-    // canonical order: Denoiser.named_parameters() of the reference (tld/denoiser.py:85-114; pinned by tests/test_train_host.py)
-    add_t(e, "fourier_feats.1.weight", (int64_t)d * e->ne, &e->ff1w); add_t(e, "fourier_feats.1.bias", d, &e->ff1b);
-    add_t(e, "fourier_feats.3.weight", (int64_t)d * d, &e->ff3w); add_t(e, "fourier_feats.3.bias", d, &e->ff3b);
-    const std::string blk = "denoiser_trans_block.";
-    add_t(e, blk + "patchify_and_embed.0.weight", (int64_t)pd * pd, &e->cvw); add_t(e, blk + "patchify_and_embed.0.bias", pd, &e->cvb);
-    add_t(e, blk + "patchify_and_embed.2.weight", pd, &e->l1w); add_t(e, blk + "patchify_and_embed.2.bias", pd, &e->l1b);
-    add_t(e, blk + "patchify_and_embed.3.weight", (int64_t)d * pd, &e->liw); add_t(e, blk + "patchify_and_embed.3.bias", d, &e->lib);
-    add_t(e, blk + "patchify_and_embed.4.weight", d, &e->l2w); add_t(e, blk + "patchify_and_embed.4.bias", d, &e->l2b);
-    add_t(e, blk + "pos_embed.weight", (int64_t)e->N * d, &e->pos);
-    e->lp.resize(e->L);
-    for (int i = 0; i < e->L; ++i) {
-        const std::string p = blk + "decoder_blocks." + std::to_string(i) + ".";
-        LayerP& q = e->lp[i];
-        add_t(e, p + "self_attention.qkv_linear.weight", (int64_t)3 * d * d, &q.qkv);
-        add_t(e, p + "cross_attention.kv_linear.weight", (int64_t)2 * d * d, &q.kv);
-        add_t(e, p + "cross_attention.q_linear.weight", (int64_t)d * d, &q.q);
-        add_t(e, p + "mlp.mlp.0.weight", (int64_t)hid * d, &q.up_w); add_t(e, p + "mlp.mlp.0.bias", hid, &q.up_b);
-        add_t(e, p + "mlp.mlp.1.weight", (int64_t)hid * 9, &q.dw_w); add_t(e, p + "mlp.mlp.1.bias", hid, &q.dw_b);
-        add_t(e, p + "mlp.mlp.3.weight", (int64_t)d * hid, &q.down_w); add_t(e, p + "mlp.mlp.3.bias", d, &q.down_b);
-        add_t(e, p + "norm1.weight", d, &q.n1w); add_t(e, p + "norm1.bias", d, &q.n1b);
-        add_t(e, p + "norm2.weight", d, &q.n2w); add_t(e, p + "norm2.bias", d, &q.n2b);
-        add_t(e, p + "norm3.weight", d, &q.n3w); add_t(e, p + "norm3.bias", d, &q.n3b);
+    {   // canonical order: Denoiser.named_parameters() of the reference (tld_param_layout.h; pinned by tests/test_train_host.py)
+        const ParamLayout pl = make_param_layout(d, e->L, e->ne, pd, hid, e->N, e->text);
+        e->layout = pl.tensors; e->nparam = pl.count; e->lp = pl.layers;
+        e->ff1w = pl.ff1w; e->ff1b = pl.ff1b; e->ff3w = pl.ff3w; e->ff3b = pl.ff3b; e->cvw = pl.cvw; e->cvb = pl.cvb; e->l1w = pl.l1w; e->l1b = pl.l1b;
+        e->liw = pl.liw; e->lib = pl.lib; e->l2w = pl.l2w; e->l2b = pl.l2b; e->pos = pl.pos; e->outw = pl.outw; e->outb = pl.outb; e->nw = pl.nw; e->nb = pl.nb;
+        e->lbw = pl.lbw; e->lbb = pl.lbb;
     }
-    add_t(e, blk + "out_proj.0.weight", (int64_t)pd * d, &e->outw); add_t(e, blk + "out_proj.0.bias", pd, &e->outb);
-    add_t(e, "norm.weight", d, &e->nw); add_t(e, "norm.bias", d, &e->nb);
-    add_t(e, "label_proj.weight", (int64_t)d * e->text, &e->lbw); add_t(e, "label_proj.bias", d, &e->lbb);
 
     const size_t B = e->B, M = B * e->N;
     if (M * (size_t)hid * 2 >= ((size_t)1 << 32)) { delete e; return fail(TLD_ERR_INVALID, "max_batch too large: the MLP hidden activation must stay below 4 GiB"); }

@@ -7,6 +7,7 @@ Keeps the constructor and call contract the reference's sampler, pipeline and te
     model(x, noise_level, label) -> x0_pred         [B,C,S,S], [B,1], [B,text] -> [B,C,S,S]
     model.eval() / .to(dtype) / .to(device)         chainable
     model.load_state_dict(sd) / .state_dict()       reference key names and shapes
+    model.load_flat(flat)                           the parameters as one fp32 vector (``weights.param_layout`` order); a live engine is refreshed in place
     model.parameters()                              fp32 tensors (count matches the reference)
     model.n_channels, model.image_size              ints
 
@@ -26,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .weights import state_dict_spec, synth_state_dict
+from .weights import param_count, param_layout, state_dict_spec, synth_state_dict
 
 _IO_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16}
 
@@ -48,9 +49,13 @@ class Denoiser:
                          embed_dim=embed_dim, dropout=dropout, n_layers=n_layers, text_emb_size=text_emb_size,
                          n_channels=n_channels, mlp_multiplier=mlp_multiplier)
         self._spec = state_dict_spec(self._cfg)
+        self.param_count = param_count(self._cfg)     # length of the flat parameter vector (load_flat)
+        # the engine's weights when they came through load_flat: a private device copy of the vector.  While _flat_stale is set the host state below is
+        # behind it, and the first reader of self._state brings it up to date (one device-to-host copy)
+        self._flat: Optional[torch.Tensor] = None
+        self._flat_stale = False
         # like nn.Module construction, a fresh model holds (deterministic) random weights
-        self._state: "OrderedDict[str, torch.Tensor]" = OrderedDict(
-            (k, torch.from_numpy(np.array(v))) for k, v in synth_state_dict(self._cfg, init_seed).items())
+        self._state = OrderedDict((k, torch.from_numpy(np.array(v))) for k, v in synth_state_dict(self._cfg, init_seed).items())
         self._device: Optional[torch.device] = None
         self._dtype = torch.float32
         self._engine = None
@@ -112,6 +117,61 @@ class Denoiser:
             new[k] = t.to(torch.int64 if kind == "arange" else torch.float32).contiguous().clone()
         self._state = new
         self._drop_engine()
+        return self
+
+    # the host state: {key: fp32 tensor} under the reference's keys.  Assigning it (load_state_dict, the constructor) makes it current; after a
+    # load_flat into a live engine it is materialised from the device copy on first use -- by state_dict(), parameters() or an engine rebuild
+    @property
+    def _state(self) -> "OrderedDict[str, torch.Tensor]":
+        if self._flat_stale:
+            self._host_state = self._state_from_flat(self._flat.cpu())
+            self._flat_stale = False
+        return self._host_state
+
+    @_state.setter
+    def _state(self, value):
+        self._host_state = value
+        self._flat_stale = False
+
+    def _state_from_flat(self, host_flat: torch.Tensor) -> "OrderedDict[str, torch.Tensor]":
+        """The host state with its parameters taken from ``host_flat``; the two registered buffers keep their values."""
+        new = OrderedDict(self._host_state)
+        for k, (o, shape) in param_layout(self._cfg).items():
+            new[k] = host_flat[o:o + int(np.prod(shape))].view(*shape).clone()
+        return new
+
+    def load_flat(self, flat: torch.Tensor) -> "Denoiser":
+        """The parameters from ONE fp32 vector of ``param_count`` elements in ``weights.param_layout`` order (``weights.flatten_state_dict``;
+        a ``Trainer``'s ``params`` / ``ema``), on the CPU or on the engine's device.  ``angular_speeds`` is not a parameter and keeps its value.
+
+        With a live engine its weight images are rebuilt in place by kernels on the current stream (``tld_engine_refresh_weights``: bit-equal to
+        a load of the same values through ``load_state_dict``): the engine, its capacity, GEMM dtype, low-latency class and debug / profile state
+        stay, nothing is rebuilt and nothing waits for the device (a CPU vector is copied up first).  The object keeps a private device copy of
+        the vector; ``state_dict()``, ``parameters()`` and a later engine rebuild (a larger batch, ``set_gemm_dtype``, ``set_low_latency``,
+        ``to``) read the new weights from it.  Without a live engine the values go into the host state and the engine is built on first use.
+        Refused before anything is enqueued: a vector of another length, dtype or rank, or on another device than the engine's."""
+        if not isinstance(flat, torch.Tensor):
+            raise TypeError(f"load_flat: a torch tensor is expected, got {type(flat).__name__}")
+        if flat.dim() != 1 or flat.numel() != self.param_count:
+            raise ValueError(f"load_flat: a vector of shape {tuple(flat.shape)}; this model's parameters are ({self.param_count},)")
+        if flat.dtype != torch.float32:
+            raise TypeError(f"load_flat: dtype {flat.dtype}; the flat parameter vector is float32")
+        flat = flat.detach()
+        if self._engine is None:
+            self._state = self._state_from_flat(flat.cpu())
+            self._flat = None
+            return self
+        dev = self._engine_device
+        if flat.device.type != "cpu" and (flat.device.type != "cuda" or flat.device.index != dev.index):
+            raise ValueError(f"load_flat: the vector is on {flat.device}, the engine on {dev}")
+        with torch.cuda.device(dev):
+            if self._flat is None or self._flat.device != dev:
+                self._flat = torch.empty(self.param_count, dtype=torch.float32, device=dev)
+            self._flat.copy_(flat)                  # (stream-ordered: the caller may overwrite its vector right after this call)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(_lib.lib().tld_engine_refresh_weights(self._engine, C.c_void_p(self._flat.data_ptr()), self.param_count, C.c_void_p(stream)),
+                       "tld_engine_refresh_weights")
+        self._flat_stale = True
         return self
 
     # ---- engine management ---------------------------------------------------------------------------

@@ -25,7 +25,7 @@ import torch
 
 from . import _lib
 from .configs import DenoiserConfig
-from .weights import state_dict_spec, synth_state_dict
+from .weights import param_layout, state_dict_spec, synth_state_dict, unflatten  # noqa: F401  (param_layout: this module's name for it stays)
 
 LABEL_DROPOUT = 0.15                 # tld/train.py:135
 
@@ -46,19 +46,6 @@ class TrainConfig:
     compile: bool = True
     save_model: bool = True
     use_wandb: bool = True
-
-
-def param_layout(cfg) -> "OrderedDict[str, Tuple[int, Tuple[int, ...]]]":
-    """{key: (offset, shape)} of the flat parameter vector: ``Denoiser.named_parameters()`` order = the state_dict order without the two
-    registered buffers (``angular_speeds``, ``precomputed_pos_enc``).  The engine reports the same table (``tld_train_param_layout``)."""
-    out: "OrderedDict[str, Tuple[int, Tuple[int, ...]]]" = OrderedDict()
-    off = 0
-    for k, (shape, kind) in state_dict_spec(cfg).items():
-        if kind in ("angular", "arange"):
-            continue
-        out[k] = (off, tuple(shape))
-        off += int(np.prod(shape))
-    return out
 
 
 def mix_noise(x: torch.Tensor, noise_level: torch.Tensor, noise: torch.Tensor) -> torch.Tensor:
@@ -176,6 +163,7 @@ class Trainer:
         self._stage = [None, None]
         self._stage_i = 0
         self._copy_stream = None
+        self._eval_den = None             # eval_generate's denoiser (built on the first call, synced on every one)
 
     def _check_layout(self):
         L = _lib.lib()
@@ -199,10 +187,7 @@ class Trainer:
 
     # ---- state ----------------------------------------------------------------------------------------------------------------
     def _unflatten(self, flat: torch.Tensor) -> "OrderedDict[str, torch.Tensor]":
-        out = OrderedDict()
-        for k, (o, s) in self.layout.items():
-            out[k] = flat[o:o + int(np.prod(s))].view(*s)
-        return out
+        return unflatten(flat, self.cfg)
 
     def state_dict(self) -> "OrderedDict[str, torch.Tensor]":
         """Views into the live flat parameter vector, reference keys (+ the two registered buffers)."""
@@ -558,6 +543,56 @@ class Trainer:
         if st is not None:
             st["free"] = torch.cuda.Event()
             st["free"].record(torch.cuda.current_stream(self.device))
+
+    # ---- evaluation while training (tld/train.py:23-40,140-147) --------------------------------------------------------------------
+    def _weights_vector(self, weights: str) -> torch.Tensor:
+        if weights == "ema":
+            if self.ema is None:
+                raise RuntimeError("this Trainer keeps no EMA copy (keep_ema=False): evaluate weights='live'")
+            return self.ema
+        if weights == "live":
+            return self.params
+        raise ValueError(f"weights = {weights!r}: 'ema' or 'live'")
+
+    def make_denoiser(self, model_batch: int = 32, weights: str = "ema"):
+        """An inference ``Denoiser`` of this trainer's config on its device, reserved for ``model_batch`` samples per forward (the CFG-doubled
+        count: 32 = the 16 images of the reference's ``eval_gen``), holding the EMA (``"ema"``) or the live (``"live"``) weights and this
+        trainer's ``angular_speeds``.  ``sync_denoiser`` brings it up to date later without rebuilding it."""
+        from .denoiser import Denoiser
+        src = self._weights_vector(weights)
+        den = Denoiser(**asdict(self.cfg)).to(self.device)
+        den.load_state_dict({"fourier_feats.0.angular_speeds": self._angular.clone()}, strict=False)
+        den.load_flat(src)
+        return den.reserve(model_batch)
+
+    def sync_denoiser(self, den, weights: str = "ema"):
+        """``den.load_flat(self.ema or self.params)``: the denoiser's engine takes the trainer's current weights in place, by kernels on the current
+        stream -- ordered behind the optimizer kernel that wrote them, with no device-to-host copy, no engine rebuild and no host wait."""
+        den.load_flat(self._weights_vector(weights))
+        return den
+
+    @torch.no_grad()
+    def eval_generate(self, labels: torch.Tensor, vae=None, *, num_imgs: int = 16, class_guidance: float = 4.5, seed: int = 10, n_iter: int = 40,
+                      exponent: float = 1, sharp_f: float = 0.1, bright_f: float = 0.1, weights: str = "ema", model_batch: Optional[int] = None):
+        """The reference's ``eval_gen`` (tld/train.py:23-35; defaults as there) from the weights this trainer holds NOW: a cached denoiser is synced
+        (``sync_denoiser``) and samples ``num_imgs`` latents for ``repeat_interleave(labels, 2, dim=0)`` through
+        ``DiffusionGenerator.generate_latents``.  Returns the latents, or ``(latents, images)`` with the decoded images of ``vae`` (an object
+        with ``.decode``) when one is given.  Runs on the calling rank only, issues no collective, and touches nothing of the training step's
+        state (gradients, accumulation, ``global_step``, the captured graph)."""
+        from .diffusion import DiffusionGenerator
+        need = int(model_batch) if model_batch is not None else 2 * int(num_imgs)
+        key = str(weights)
+        self._weights_vector(key)                 # (refusals before anything is built)
+        if self._eval_den is None:
+            self._eval_den = self.make_denoiser(need, key)
+        else:
+            self.sync_denoiser(self._eval_den.reserve(need), key)
+        gen = DiffusionGenerator(self._eval_den, vae, self.device, torch.float32)
+        latents = gen.generate_latents(labels=torch.repeat_interleave(labels, 2, dim=0), n_iter=n_iter, num_imgs=num_imgs, class_guidance=class_guidance,
+                                       seed=seed, img_size=self.cfg.image_size, sharp_f=sharp_f, bright_f=bright_f, exponent=exponent)
+        if vae is None:
+            return latents
+        return latents, gen._decode(latents, 8)[0]
 
     # ---- checkpoint / resume ----------------------------------------------------------------------------------------------------
     def optimizer_state_dict(self) -> Dict[str, object]:

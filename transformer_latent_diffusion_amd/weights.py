@@ -95,6 +95,51 @@ def param_count(cfg) -> int:
     return tot
 
 
+def param_layout(cfg) -> "OrderedDict[str, Tuple[int, Tuple[int, ...]]]":
+    """{key: (offset, shape)} of the flat parameter vector: ``Denoiser.named_parameters()`` order = the state_dict order without the two
+    registered buffers (``angular_speeds``, ``precomputed_pos_enc``).  The engines report the same table (``tld_train_param_layout``;
+    ``csrc/tld_param_layout.h``)."""
+    out: "OrderedDict[str, Tuple[int, Tuple[int, ...]]]" = OrderedDict()
+    off = 0
+    for k, (shape, kind) in state_dict_spec(cfg).items():
+        if kind in ("angular", "arange"):
+            continue
+        out[k] = (off, tuple(shape))
+        off += int(np.prod(shape))
+    return out
+
+
+def flatten_state_dict(sd, cfg):
+    """The parameters of ``sd`` (tensors or arrays under the reference's keys) as ONE fp32 host tensor in ``param_layout`` order -- what
+    ``Denoiser.load_flat`` and ``tld_engine_refresh_weights`` take, and what ``Trainer.params`` / ``Trainer.ema`` are on the device.  The two
+    registered buffers are not in it; keys the layout does not know are ignored."""
+    import torch
+    lay = param_layout(cfg)
+    missing = [k for k in lay if k not in sd]
+    if missing:
+        raise KeyError(f"missing keys in state_dict: {missing[:4]}{' ...' if len(missing) > 4 else ''}")
+    flat = torch.empty(param_count(cfg), dtype=torch.float32)
+    for k, (o, shape) in lay.items():
+        t = (sd[k] if isinstance(sd[k], torch.Tensor) else torch.as_tensor(np.asarray(sd[k]))).detach().to(torch.float32).cpu()
+        if tuple(t.shape) != shape:
+            raise ValueError(f"size mismatch for {k}: {tuple(t.shape)}, the layout has {shape}")
+        flat[o:o + t.numel()] = t.reshape(-1)
+    return flat
+
+
+def unflatten(flat, cfg):
+    """Inverse of ``flatten_state_dict``: {key: view of ``flat`` in the parameter's shape}, in ``param_layout`` order (a 1-D tensor on any
+    device; nothing is copied)."""
+    lay = param_layout(cfg)
+    n = param_count(cfg)
+    if flat.dim() != 1 or flat.numel() != n:
+        raise ValueError(f"flat vector of shape {tuple(flat.shape)}: expected ({n},)")
+    out = OrderedDict()
+    for k, (o, shape) in lay.items():
+        out[k] = flat[o:o + int(np.prod(shape))].view(*shape)
+    return out
+
+
 def angular_speeds(noise_embed_dims: int) -> np.ndarray:
     """2*pi*exp(linspace(ln 1, ln 1000, dims/2)) (tld/transformer_blocks.py:11-15).
 
