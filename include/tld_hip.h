@@ -582,6 +582,40 @@ TLD_API int tld_train_grad_guard(tld_train* e, const float* grads, int64_t numel
 TLD_API int tld_train_adam_ema_guarded(tld_train* e, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t numel,
                                        float lr, float beta1, float beta2, float eps, float ema_alpha, float grad_scale, const double* opt_state,
                                        void* hip_stream);
+/* The training batch of one step, built on the device from a resident dataset (tld/train.py:121-138 without the host):
+ * gather rows idx[b] of the source, draw noise, noise level and label mask from Philox4x32-10 and mix.  One kernel on hip_stream; nothing is
+ * allocated, nothing synchronises.  e may be NULL (the device is that of x_noisy).
+ *   src        latents [rows, latent_elems] (latent_elems = C S S) as TLD_DTYPE_U8 / F16 / F32, labels [rows, text_emb] as F16 / F32, both device;
+ *              TLD_DTYPE_U8: target = dequant_table[code] (device float[256], already divided by the VAE scale factor);
+ *              F16 / F32: target = float(latent) / vae_scale, a correctly rounded fp32 division (tld/train.py:122)
+ *   idx        device int64 [batch]; an index outside [0, rows) is never dereferenced: the position takes row 0 and *bad_index_count
+ *              (device int32, never reset here) is incremented
+ *   seed, step, replica   Philox key (seed_lo, seed_hi), counter (c0, 4 replica + stream, step_lo, step_hi); every draw is a function of
+ *              (seed, replica, step, position) alone
+ *     stream 0 noise: c0 = e / 4 of the flat element e of [batch, latent_elems]; words (r0, r1) and (r2, r3) give two Box-Muller pairs
+ *              sqrt(-2 ln u0) (cos, sin)(2 pi u1), u = ((r >> 8) + 0.5) 2^-24 (ln u0 from log1p of the exact 1 - u0 where fp32 cannot hold u0)
+ *     stream 1 noise level: one Beta(beta_a, beta_b) draw per sample in double, c0 = 64 b + j (the method and its loop bound: DESIGN.md 7.11)
+ *     stream 2 label mask: c0 = b / 4, word b % 4, u = float(r >> 8) 2^-24; the label row is all zeros when u < label_dropout
+ *   x_noisy = float(nl noise + (1 - nl) target) with every product and sum rounded in double, no FMA (= train.mix_noise bit for bit);
+ *   noise_level = float(nl); label [batch, text_emb]; target [batch, latent_elems]: device fp32.
+ *   noise (fp32 [batch, latent_elems]), noise_level64 (fp64 [batch]), mask (uint8 [batch]): what was drawn, for tests; each may be NULL.
+ * TLD_ERR_INVALID before any HIP call: a NULL src, source pointer, idx, required output or bad_index_count; batch, rows, latent_elems or
+ * text_emb <= 0; batch > 2^26 or batch * latent_elems > 2^34 (the 32-bit c0); an unknown dtype; TLD_DTYPE_U8 without a table; a float source
+ * whose vae_scale is not a finite non-zero number; beta_a or beta_b not > 0 (NaN included); label_dropout outside [0, 1]. */
+enum { TLD_DTYPE_U8 = 3 };
+typedef struct tld_batch_source {
+    const void* latents;
+    const void* labels;
+    const float* dequant_table;
+    int64_t rows;
+    int32_t latent_dtype, label_dtype;
+    int32_t latent_elems, text_emb;
+    float vae_scale;
+} tld_batch_source;
+TLD_API int tld_train_prepare_batch(tld_train* e, const tld_batch_source* src, const int64_t* idx, int32_t batch, uint64_t seed, uint64_t step,
+                                    uint32_t replica, double beta_a, double beta_b, float label_dropout, float* x_noisy, float* noise_level,
+                                    float* label, float* target, float* noise, double* noise_level64, uint8_t* mask, int32_t* bad_index_count,
+                                    void* hip_stream);
 /* Test hook: self-attention backward alone (head_dim 64; ntok a multiple of 16): qk [M, 2d] bf16 (q | k), vt [B, H, 64, ntok]
  * bf16, o [M, d] bf16 (forward output), g [M, d] fp32 (dL/dO) -> dqkv [M, 3d] bf16 (dq | dk | dv).  scratch: 2 * batch * heads * ntok floats
  * (row statistics between the two kernels of the ntok > 256 path; may be NULL otherwise).  Device pointers. */

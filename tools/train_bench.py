@@ -4,7 +4,9 @@ TrainConfig (batch 128, Adam lr 3e-4, EMA 0.999).  One step = make_batch (host R
 Prints one JSON line in bench.py's vocabulary.   tools/train_bench.py [--batch 128] [--steps 10] [--warmup 2] [--layers 12] [--image-size 32]
 [--patch-size 2] [--no-cpu-baseline] [--max-grad-norm X] [--skip-nonfinite]   (the last two: the guarded optimizer step, to time beside the plain one;
 --image-size: the latent side, e.g. 48 = 576 tokens, the 384 px fine-tuning grid; the TFLOP/s figures
-are quoted at the default 32 only, where the op count below applies)"""
+are quoted at the default 32 only, where the op count below applies)
+--device-data [--latent-dtype uint8|float16|float32]: the same model and batch size through train_step (host make_batch + pinned staging) and through
+train_step_from (a device-resident dataset, one preparation kernel: DESIGN.md section 7.11) in one process; one JSON line with both."""
 import argparse
 import json
 import os
@@ -27,6 +29,8 @@ ap.add_argument("--patch-size", type=int, default=2)
 ap.add_argument("--no-cpu-baseline", action="store_true")
 ap.add_argument("--max-grad-norm", type=float, default=None)
 ap.add_argument("--skip-nonfinite", action="store_true")
+ap.add_argument("--device-data", action="store_true")
+ap.add_argument("--latent-dtype", choices=("uint8", "float16", "float32"), default="uint8")
 args = ap.parse_args()
 
 dev = torch.device("cuda", 0)
@@ -40,6 +44,61 @@ g = torch.Generator().manual_seed(1)
 x = torch.randn(args.batch, 4, S, S, generator=g) * 0.8
 y = torch.randn(args.batch, 768, generator=g) * 0.5
 rng, tg = np.random.default_rng(0), torch.Generator().manual_seed(0)
+
+
+def timed_steps(step_fn):
+    """warmup + steps calls of step_fn(i): (wall ms per step, median HIP-event ms per step, last loss)."""
+    for i in range(args.warmup):
+        step_fn(i)
+    torch.cuda.synchronize()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+    t_start = time.perf_counter()
+    for i in range(args.steps):
+        ev[i].record()
+        out = step_fn(args.warmup + i)
+    ev[args.steps].record()
+    torch.cuda.synchronize()
+    wall = (time.perf_counter() - t_start) / args.steps * 1e3
+    each = sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(args.steps))
+    return wall, each[len(each) // 2], float(out)
+
+
+if args.device_data:
+    from transformer_latent_diffusion_amd import DeviceLatentDataset, quantize_latents
+    rows = 16 * args.batch
+    gd = torch.Generator().manual_seed(2)
+    lat = torch.randn(rows, 4, S, S, generator=gd) * 0.8 * 8             # unscaled latents, as the reference stores them
+    lat = {"uint8": quantize_latents, "float16": lambda t: t.half(), "float32": lambda t: t}[args.latent_dtype](lat)
+    ds = DeviceLatentDataset(lat, (torch.randn(rows, 768, generator=gd) * 0.5).half(), device=dev)
+    idx = [b for b in ds.batches(args.batch, seed=0, epoch=0) if len(b) == args.batch]
+    # the host path: what the loader would hand over (fp32 latents / scale, fp32 embeddings) -> make_batch on the host -> pinned staging
+    t_h = time.perf_counter()
+    for _ in range(5):
+        tr.make_batch(x, y, rng, tg)
+    host_prepare_ms = (time.perf_counter() - t_h) / 5 * 1e3
+    host = timed_steps(lambda i: tr.train_step(x, y, rng, tg))
+    device = timed_steps(lambda i: tr.train_step_from(ds, idx[i % len(idx)]))
+    # the preparation kernel alone, HIP events around single launches; a matrix product is queued first so that the host has enqueued the launch and
+    # both events before the device reaches them (otherwise the interval is the host's launch path, not the kernel)
+    times, w = [], torch.randn(4096, 4096, device=dev)
+    for i in range(30):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        w @ w
+        a.record(); tr.prepare_batch(ds, idx[i % len(idx)]); b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b))
+    kernel_ms = sorted(times[5:])[len(times[5:]) // 2]
+    E = 4 * S * S
+    nbytes = args.batch * (E * ds.latents.element_size() + 768 * 2 + 8 + 2 * E * 4 + 768 * 4 + 4)
+    side = lambda t, extra: dict({"ms_per_step": t[0], "ms_per_step_median_events": t[1], "samples_per_s": args.batch / t[0] * 1e3, "loss": t[2]}, **extra)
+    print(json.dumps({"metric": f"training step, host batch against device batch (100M denoiser, {S}x{S}x4 latents, batch {args.batch})", "unit": "ms/step",
+                      "steps": args.steps, "warmup": args.warmup, "cpu_threads": torch.get_num_threads(), "graph": tr.use_graph,
+                      "host_data": side(host, {"path": "train_step: make_batch on the host, pinned staging, 4 copies", "make_batch_host_ms": host_prepare_ms}),
+                      "device_data": side(device, {"path": f"train_step_from: resident {args.latent_dtype} latents + fp16 embeddings, one kernel",
+                                                   "prepare_kernel_ms": kernel_ms, "prepare_bytes": nbytes, "prepare_GB_per_s": nbytes / kernel_ms / 1e6}),
+                      "device_over_host": device[0] / host[0]}))
+    sys.exit(0)
+
 # device-resident batch (the loader's job); the per-step host work of tld/train.py:118-138 (Beta draw, randn, mask) is timed with the step
 for _ in range(args.warmup):
     loss = tr.train_step(x, y, rng, tg)

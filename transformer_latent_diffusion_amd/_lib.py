@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TLD_LIB", os.path.join(_HERE, "libtld_hip.so"))   # TLD_LIB: A/B-testing builds only
 
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
+DTYPE_U8 = 3                             # TLD_DTYPE_U8: quantised latents of a tld_batch_source
 
 TRAIN_OPT_STATE_DOUBLES = 8 + 1024         # TLD_TRAIN_OPT_STATE_DOUBLES (include/tld_hip.h): the guarded optimizer step's fp64 state vector
 
@@ -35,7 +36,7 @@ ABI_SYMBOLS = (
     "tld_clip_create", "tld_clip_load_tensor", "tld_clip_finalize_weights", "tld_clip_encode_text", "tld_clip_set_debug", "tld_clip_read_stage", "tld_clip_weight_bytes",
     "tld_clip_destroy",
     "tld_train_create", "tld_train_param_count", "tld_train_tensor_count", "tld_train_param_layout", "tld_train_set_angular_speeds", "tld_train_bind",
-    "tld_train_refresh_weights", "tld_train_forward_backward", "tld_train_forward_backward_cb", "tld_train_adam_ema", "tld_train_grad_guard", "tld_train_adam_ema_guarded", "tld_debug_attention_bwd", "tld_debug_wgrad", "tld_debug_attention_fwd", "tld_debug_dwconv_gelu",
+    "tld_train_refresh_weights", "tld_train_forward_backward", "tld_train_forward_backward_cb", "tld_train_adam_ema", "tld_train_grad_guard", "tld_train_adam_ema_guarded", "tld_train_prepare_batch", "tld_debug_attention_bwd", "tld_debug_wgrad", "tld_debug_attention_fwd", "tld_debug_dwconv_gelu",
     "tld_train_set_debug", "tld_train_read_stage", "tld_train_debug_paths", "tld_train_destroy",
     "tld_last_error",
 )
@@ -70,6 +71,13 @@ class TldVaeEncConfig(C.Structure):
                 ("block_out_channels", C.c_int32 * 4), ("layers_per_block", C.c_int32), ("norm_num_groups", C.c_int32),
                 ("mid_block_attention", C.c_int32), ("use_quant_conv", C.c_int32), ("image_size", C.c_int32),
                 ("max_batch", C.c_int32), ("device_id", C.c_int32)]
+
+
+class TldBatchSource(C.Structure):
+    """tld_batch_source (include/tld_hip.h): the resident dataset a tld_train_prepare_batch call gathers from."""
+    _fields_ = [("latents", C.c_void_p), ("labels", C.c_void_p), ("dequant_table", C.c_void_p), ("rows", C.c_int64),
+                ("latent_dtype", C.c_int32), ("label_dtype", C.c_int32), ("latent_elems", C.c_int32), ("text_emb", C.c_int32),
+                ("vae_scale", C.c_float)]
 
 
 class TldClipConfig(C.Structure):
@@ -208,6 +216,9 @@ def lib() -> C.CDLL:
     if hasattr(L, "tld_train_grad_guard"):           # (absent from A/B builds that predate the guarded optimizer step)
         L.tld_train_grad_guard.argtypes = [vp, vp, C.c_int64, f32, C.c_double, i32, f32, f32, vp, vp]
         L.tld_train_adam_ema_guarded.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64, f32, f32, f32, f32, f32, f32, vp, vp]
+    if hasattr(L, "tld_train_prepare_batch"):        # (absent from A/B builds that predate the device batch preparation)
+        L.tld_train_prepare_batch.argtypes = [vp, C.POINTER(TldBatchSource), vp, i32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_double, C.c_double, f32,
+                                              vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.tld_debug_attention_bwd.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     L.tld_debug_wgrad.argtypes = [vp, vp, vp, vp, C.c_int64, i32, i32, i32, vp]
     L.tld_debug_dwconv_gelu.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, i32, i32, i32, vp]

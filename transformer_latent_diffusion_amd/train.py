@@ -84,7 +84,7 @@ class Trainer:
                  state_dict: Optional[Mapping[str, torch.Tensor]] = None, init_seed: int = 0, max_batch: Optional[int] = None,
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, keep_ema: bool = True, process_group=None,
                  overlap_allreduce: bool = True, use_graph: Optional[bool] = None, max_grad_norm: Optional[float] = None,
-                 skip_nonfinite: bool = False):
+                 skip_nonfinite: bool = False, data_seed: int = 0):
         self.cfg = denoiser_cfg
         self.tc = train_cfg if train_cfg is not None else TrainConfig()
         dev = torch.device(device)
@@ -164,6 +164,9 @@ class Trainer:
         self._stage_i = 0
         self._copy_stream = None
         self._eval_den = None             # eval_generate's denoiser (built on the first call, synced on every one)
+        # the device data path (prepare_batch / train_step_from): the Philox key of every draw, and the kernel's count of refused row indices
+        self.data_seed = int(data_seed) & (2 ** 64 - 1)
+        self._bad = torch.zeros(1, dtype=torch.int32, device=self.device)
 
     def _check_layout(self):
         L = _lib.lib()
@@ -500,6 +503,61 @@ class Trainer:
         staged = self._stage_batch((x_noisy, noise_level, label, x))
         loss, _ = self.forward_backward(*staged)
         self._release_stage()
+        self.optimizer_step()
+        return loss
+
+    # ---- the device data path --------------------------------------------------------------------------
+    @property
+    def bad_indices(self) -> torch.Tensor:
+        """How many row indices ``prepare_batch``'s kernel has refused since this trainer was built (each such position trained on row 0): a 0-d
+        int32 view of the device counter -- reading the attribute does not synchronise, ``int()`` of it does."""
+        return self._bad[0]
+
+    def _rank(self) -> int:
+        import torch.distributed as dist
+        return dist.get_rank(self.group) if dist.is_available() and dist.is_initialized() else 0
+
+    def prepare_batch(self, dataset, idx, *, step: Optional[int] = None, debug: bool = False):
+        """``make_batch`` on the device (tld/train.py:121-138): rows ``idx`` of a ``data.DeviceLatentDataset`` -> ``(x_noisy, noise_level, label,
+        target)``, fp32 device tensors ready for ``forward_backward``; one kernel on the current stream, no host wait.  The noise, the Beta noise
+        level and the label mask are Philox draws keyed by ``data_seed`` and addressed by (rank, ``step``, position): ``step`` defaults to
+        ``global_step``, which a checkpoint carries, so a resumed run continues the stream of the uninterrupted one.  A host ``idx`` (list, array,
+        CPU tensor) is range-checked here; a device ``idx`` is left to the kernel's guard (``bad_indices``).  ``debug=True`` appends
+        ``(noise, noise_level64, mask)``, what was drawn."""
+        dev = self.device
+        if dataset.device.type != "cuda" or (dataset.device.index if dataset.device.index is not None else torch.cuda.current_device()) != dev.index:
+            raise ValueError(f"the dataset lives on {dataset.device}, this trainer on {dev}")
+        shape = (self.cfg.n_channels, self.cfg.image_size, self.cfg.image_size)
+        if tuple(dataset.sample_shape) != shape or dataset.text_emb.shape[1] != self.cfg.text_emb_size:
+            raise ValueError(f"dataset rows are {tuple(dataset.sample_shape)} with {dataset.text_emb.shape[1]} text features; the model takes {shape} and "
+                             f"{self.cfg.text_emb_size}")
+        if not (isinstance(idx, torch.Tensor) and idx.device.type == "cuda"):
+            host = torch.as_tensor(idx).reshape(-1)
+            if host.numel() and (host.dtype.is_floating_point or int(host.min()) < 0 or int(host.max()) >= len(dataset)):
+                raise IndexError(f"batch indices outside [0, {len(dataset)}) (or not integers)")
+            idx = host
+        idx = idx.reshape(-1).to(dev, torch.int64).contiguous()
+        B = int(idx.numel())
+        if B == 0:
+            raise ValueError("an empty batch")
+        f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+        x_noisy, noise_level, label, target = f(B, *shape), f(B), f(B, self.cfg.text_emb_size), f(B, *shape)
+        extra = (f(B, *shape), torch.empty(B, dtype=torch.float64, device=dev), torch.empty(B, dtype=torch.uint8, device=dev)) if debug else (None, None, None)
+        src = dataset.source()
+        p = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().tld_train_prepare_batch(self._h, C.byref(src), p(idx), B, self.data_seed, int(self.global_step if step is None else step),
+                                                          self._rank(), float(self.tc.beta_a), float(self.tc.beta_b), LABEL_DROPOUT, p(x_noisy),
+                                                          p(noise_level), p(label), p(target), p(extra[0]), p(extra[1]), p(extra[2]), p(self._bad),
+                                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "tld_train_prepare_batch")
+        out = (x_noisy, noise_level, label, target)
+        return out + (extra[0], extra[1], extra[2].bool()) if debug else out
+
+    def train_step_from(self, dataset, idx) -> torch.Tensor:
+        """``train_step`` without the host: ``prepare_batch`` + ``forward_backward`` + ``optimizer_step`` on rows ``idx`` of a device-resident
+        dataset.  Returns the loss tensor (device, not synchronised).  With graph replay on, the prepared tensors go through the captured step's
+        fixed input buffers like any other device batch."""
+        loss, _ = self.forward_backward(*self.prepare_batch(dataset, idx))
         self.optimizer_step()
         return loss
 
