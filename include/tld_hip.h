@@ -616,6 +616,45 @@ TLD_API int tld_train_prepare_batch(tld_train* e, const tld_batch_source* src, c
                                     uint32_t replica, double beta_a, double beta_b, float label_dropout, float* x_noisy, float* noise_level,
                                     float* label, float* target, float* noise, double* noise_level64, uint8_t* mask, int32_t* bad_index_count,
                                     void* hip_stream);
+/* tld_train_prepare_batch with the noise levels GIVEN (held-out evaluation at fixed levels).  noise_level_in: device fp64
+ * [batch], 8-byte aligned: nl = noise_level_in[b], used as it is (a NaN propagates; the Python layer validates), the two Gamma draws of stream 1
+ * are skipped and everything else is the plain entry's -- gather, Philox noise on stream 0, mask on stream 2 at label_dropout, the double mix,
+ * noise_level = float(nl), the optional outputs (noise_level64 echoes the input).  NULL: exactly tld_train_prepare_batch, which is this call with
+ * NULL.  The same refusals. */
+TLD_API int tld_train_prepare_batch_at(tld_train* e, const tld_batch_source* src, const int64_t* idx, int32_t batch, uint64_t seed, uint64_t step,
+                                       uint32_t replica, double beta_a, double beta_b, float label_dropout, float* x_noisy, float* noise_level,
+                                       float* label, float* target, float* noise, double* noise_level64, uint8_t* mask, int32_t* bad_index_count,
+                                       void* hip_stream, const double* noise_level_in);
+/* ---- Held-out loss, per sample and by noise level ------------------------------------------------------------------
+ * tld_train_forward_loss is the forward half of tld_train_forward_backward and nothing else: the same kernels in the same order (one internal
+ * function under both entries) up to the per-row squared errors and the scalar loss, then tld_train_sample_loss on them.
+ *   weights    flat fp32 device vector of tld_train_param_count elements (the EMA vector is the intended one): every parameter the forward reads
+ *              comes from it, the bf16 / transposed operand copies included, which are rebuilt from it at the start of the call and marked stale
+ *              at its end (the next training step rebuilds them from the bound parameters).  NULL or the bound params pointer: the bound parameters
+ *   loss_out   device fp32 [1];  sample_loss_out  device fp64 [batch], may be NULL;  pred_out  device fp32 [batch, C, S, S], may be NULL (an
+ *              engine-owned image of max_batch samples takes the prediction)
+ * It never writes the bound gradient vector, invokes no callback and advances nothing; kernel launches only (a capturing stream is not refused).
+ * TLD_ERR_INVALID: a NULL engine or required pointer, batch outside [1, max_batch]; TLD_ERR_STATE: before tld_train_bind, or with the stage hook
+ * on (a debug call poisons the gradient vector).
+ *
+ * tld_train_sample_loss: out[b] = (sum_t row_sq[b rows_per_sample + t]) / elems_per_sample, summed in double in a fixed order (no atomics: bitwise
+ * repeatable, and a sample's value does not depend on its position in the batch); a sample is non-finite exactly when one of its rows is.  out:
+ * device fp64 [batch].  row_sq NULL: the engine's own row errors of its last forward, from either entry -- batch must be that call's batch (or that
+ * of a forward captured into a graph, which replays out of the engine's sight), rows_per_sample / elems_per_sample are the engine's (tokens,
+ * C S S) and the arguments are ignored; otherwise TLD_ERR_STATE.  row_sq non-NULL: any device fp32 array [batch, rows_per_sample]; e may be NULL.
+ *
+ * tld_train_loss_buckets accumulates into the caller-owned device fp64 vector state[2 n_buckets + 2] (all zeros = empty):
+ *   [0, n) sum of the losses per bucket   [n, 2n) counts   [2n] sum of every accepted loss   [2n + 1] rejected samples
+ * Sample b goes to bucket min(n - 1, floor((double)noise_level[b] * n)); a level outside [0, 1], NaN included, only increments the rejected
+ * count; a non-finite loss is added as it is.  One workgroup, the owner of a cell adds b = 0 .. batch - 1 in order: after any sequence of calls the
+ * state is what the serial loop gives on the host, bit for bit.  sample_loss device fp64 [batch], noise_level device fp32 [batch].
+ * TLD_ERR_INVALID before any HIP call: a NULL pointer, state or sample_loss not 8-byte aligned, n_buckets outside [1, 256], batch < 1. */
+TLD_API int tld_train_forward_loss(tld_train* e, const float* weights, const float* x_noisy, const float* noise_level, const float* label,
+                                   const float* target, int32_t batch, float* loss_out, double* sample_loss_out, float* pred_out, void* hip_stream);
+TLD_API int tld_train_sample_loss(tld_train* e, const float* row_sq, int32_t batch, int32_t rows_per_sample, int64_t elems_per_sample, double* out,
+                                  void* hip_stream);
+TLD_API int tld_train_loss_buckets(const double* sample_loss, const float* noise_level, int32_t batch, int32_t n_buckets, double* state,
+                                   void* hip_stream);
 /* Test hook: self-attention backward alone (head_dim 64; ntok a multiple of 16): qk [M, 2d] bf16 (q | k), vt [B, H, 64, ntok]
  * bf16, o [M, d] bf16 (forward output), g [M, d] fp32 (dL/dO) -> dqkv [M, 3d] bf16 (dq | dk | dv).  scratch: 2 * batch * heads * ntok floats
  * (row statistics between the two kernels of the ntok > 256 path; may be NULL otherwise).  Device pointers. */

@@ -36,7 +36,8 @@ ABI_SYMBOLS = (
     "tld_clip_create", "tld_clip_load_tensor", "tld_clip_finalize_weights", "tld_clip_encode_text", "tld_clip_set_debug", "tld_clip_read_stage", "tld_clip_weight_bytes",
     "tld_clip_destroy",
     "tld_train_create", "tld_train_param_count", "tld_train_tensor_count", "tld_train_param_layout", "tld_train_set_angular_speeds", "tld_train_bind",
-    "tld_train_refresh_weights", "tld_train_forward_backward", "tld_train_forward_backward_cb", "tld_train_adam_ema", "tld_train_grad_guard", "tld_train_adam_ema_guarded", "tld_train_prepare_batch", "tld_debug_attention_bwd", "tld_debug_wgrad", "tld_debug_attention_fwd", "tld_debug_dwconv_gelu",
+    "tld_train_refresh_weights", "tld_train_forward_backward", "tld_train_forward_backward_cb", "tld_train_adam_ema", "tld_train_grad_guard", "tld_train_adam_ema_guarded", "tld_train_prepare_batch", "tld_train_prepare_batch_at",
+    "tld_train_forward_loss", "tld_train_sample_loss", "tld_train_loss_buckets", "tld_debug_attention_bwd", "tld_debug_wgrad", "tld_debug_attention_fwd", "tld_debug_dwconv_gelu",
     "tld_train_set_debug", "tld_train_read_stage", "tld_train_debug_paths", "tld_train_destroy",
     "tld_last_error",
 )
@@ -219,6 +220,11 @@ def lib() -> C.CDLL:
     if hasattr(L, "tld_train_prepare_batch"):        # (absent from A/B builds that predate the device batch preparation)
         L.tld_train_prepare_batch.argtypes = [vp, C.POINTER(TldBatchSource), vp, i32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_double, C.c_double, f32,
                                               vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "tld_train_forward_loss"):         # (absent from A/B builds that predate the held-out loss)
+        L.tld_train_prepare_batch_at.argtypes = L.tld_train_prepare_batch.argtypes + [vp]
+        L.tld_train_forward_loss.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+        L.tld_train_sample_loss.argtypes = [vp, vp, i32, i32, C.c_int64, vp, vp]
+        L.tld_train_loss_buckets.argtypes = [vp, vp, i32, i32, vp, vp]
     L.tld_debug_attention_bwd.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     L.tld_debug_wgrad.argtypes = [vp, vp, vp, vp, C.c_int64, i32, i32, i32, vp]
     L.tld_debug_dwconv_gelu.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, i32, i32, i32, vp]

@@ -27,6 +27,7 @@ struct BatchArgs {
     const void* latents; const void* labels; const float* table; const int64_t* idx;
     float *x_noisy, *noise_level, *label, *target, *noise;
     double* noise_level64; uint8_t* mask; int32_t* bad;
+    const double* level_in;                               // given noise levels [batch] (tld_train_prepare_batch_at); null: the Beta draw
     int64_t rows; uint64_t seed, step;
     double beta_a, beta_b;
     float vae_scale, label_dropout;
@@ -87,8 +88,10 @@ __global__ __launch_bounds__(kBatchLanes) void prepare_batch_kernel(BatchArgs A)
     const uint32_t b = blockIdx.x / (uint32_t)A.chunks, chunk = blockIdx.x % (uint32_t)A.chunks;
 
     if (A.lat_dtype == TLD_DTYPE_U8) tab[tid] = A.table[tid];
-    if (tid == 0) sh_lg[0] = log_gamma_draw(A.beta_a, 0, A, b);
-    if (tid == 64) sh_lg[1] = log_gamma_draw(A.beta_b, BATCH_LEVEL_SLOTS / 2, A, b);
+    if (!A.level_in) {
+        if (tid == 0) sh_lg[0] = log_gamma_draw(A.beta_a, 0, A, b);
+        if (tid == 64) sh_lg[1] = log_gamma_draw(A.beta_b, BATCH_LEVEL_SLOTS / 2, A, b);
+    }
     if (tid == 128) {
         int64_t r = A.idx[b];
         if (r < 0 || r >= A.rows) {                       // never dereferenced: the position takes row 0, and the call says so
@@ -101,7 +104,10 @@ __global__ __launch_bounds__(kBatchLanes) void prepare_batch_kernel(BatchArgs A)
         sh_drop = uniform24(w) < A.label_dropout ? 1 : 0;
     }
     __syncthreads();
-    const double nl = 1.0 / (1.0 + exp(sh_lg[1] - sh_lg[0])), sl = __dsub_rn(1.0, nl);
+    double nl;
+    if (A.level_in) nl = A.level_in[b];                   // used as given: a NaN propagates
+    else nl = 1.0 / (1.0 + exp(sh_lg[1] - sh_lg[0]));
+    const double sl = __dsub_rn(1.0, nl);
     const int64_t row = sh_row;
     const int drop = sh_drop;
     if (chunk == 0 && tid == 0) {
@@ -178,6 +184,13 @@ extern "C" {
 int tld_train_prepare_batch(tld_train* e, const tld_batch_source* src, const int64_t* idx, int32_t batch, uint64_t seed, uint64_t step, uint32_t replica,
                             double beta_a, double beta_b, float label_dropout, float* x_noisy, float* noise_level, float* label, float* target, float* noise,
                             double* noise_level64, uint8_t* mask, int32_t* bad_index_count, void* hip_stream) {
+    return tld_train_prepare_batch_at(e, src, idx, batch, seed, step, replica, beta_a, beta_b, label_dropout, x_noisy, noise_level, label, target, noise, noise_level64,
+                                      mask, bad_index_count, hip_stream, nullptr);
+}
+
+int tld_train_prepare_batch_at(tld_train* e, const tld_batch_source* src, const int64_t* idx, int32_t batch, uint64_t seed, uint64_t step, uint32_t replica,
+                               double beta_a, double beta_b, float label_dropout, float* x_noisy, float* noise_level, float* label, float* target, float* noise,
+                               double* noise_level64, uint8_t* mask, int32_t* bad_index_count, void* hip_stream, const double* noise_level_in) {
     (void)e;                                              // no engine state is read: the handle is accepted for symmetry with the other tld_train_* entries
     if (!src || !src->latents || !src->labels || !idx) return fail(TLD_ERR_INVALID, "prepare batch: null source or index pointer");
     if (!x_noisy || !noise_level || !label || !target || !bad_index_count) return fail(TLD_ERR_INVALID, "prepare batch: null output pointer");
@@ -195,11 +208,12 @@ int tld_train_prepare_batch(tld_train* e, const tld_batch_source* src, const int
     if (!(beta_a > 0.0) || !(beta_b > 0.0) || std::isinf(beta_a) || std::isinf(beta_b))
         return fail(TLD_ERR_INVALID, "prepare batch: Beta(%g, %g) needs finite shapes > 0", beta_a, beta_b);
     if (!(label_dropout >= 0.f && label_dropout <= 1.f)) return fail(TLD_ERR_INVALID, "prepare batch: label_dropout %g outside [0, 1]", (double)label_dropout);
+    if ((uintptr_t)noise_level_in & 7) return fail(TLD_ERR_INVALID, "prepare batch: noise_level_in must be 8-byte aligned");
 
     BatchArgs A{};
     A.latents = src->latents; A.labels = src->labels; A.table = src->dequant_table; A.idx = idx;
     A.x_noisy = x_noisy; A.noise_level = noise_level; A.label = label; A.target = target; A.noise = noise;
-    A.noise_level64 = noise_level64; A.mask = mask; A.bad = bad_index_count;
+    A.noise_level64 = noise_level64; A.mask = mask; A.bad = bad_index_count; A.level_in = noise_level_in;
     A.rows = src->rows; A.seed = seed; A.step = step; A.beta_a = beta_a; A.beta_b = beta_b;
     A.vae_scale = src->vae_scale; A.label_dropout = label_dropout; A.replica = replica;
     A.lat_dtype = lt; A.lab_dtype = bt; A.E = src->latent_elems; A.text = src->text_emb;

@@ -16,6 +16,7 @@
 #include "tld_host.h"
 #include "tld_param_layout.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -84,6 +85,9 @@ struct tld_train {
     bf16* xfin;
     // tail / loss
     float *dout, *row_loss, *io;
+    float* pred_scratch = nullptr;       // tld_train_forward_loss with pred_out NULL: [max_batch, C, S, S]
+    int last_batch = 0;                  // batch of the last forward (either entry): what row_loss holds for tld_train_sample_loss
+    int captured_batch = 0;              // batch of the last forward enqueued on a capturing stream: a graph replays it out of the engine's sight
     // backward scratch
     float* gx;                           // dL/d(residual stream) fp32 [M, d]
     bf16 *gxb, *T1, *T2, *dbig, *dsmall, *dsmall2;
@@ -209,6 +213,121 @@ int reserve_snapshots(tld_train* e) {
 #define PATH(b) do { if (e->debug) e->paths |= 1ull << (b); } while (0)
 #define SNAP(...) do { if (e->debug) { if (int _r = e->stages.copy(__VA_ARGS__)) return _r; } } while (0)
 
+// the bf16 GEMM operands, their transposes and the tap-major depthwise taps of the flat parameter vector `src` (the bound parameters for the training
+// step; any other vector for tld_train_forward_loss, which clears weights_fresh afterwards)
+int refresh_operands(tld_train* e, const float* src, hipStream_t s) {
+    const int d = e->d, hid = e->hid;
+    auto both = [&](int64_t off, int R, int Cc, bf16* w, bf16* wt) {       // [R, C] fp32 -> bf16 copy and bf16 transpose [C, R]
+        hipLaunchKernelGGL((transpose_to_bf16<float>), dim3((Cc + 31) / 32, (R + 31) / 32), dim3(256), 0, s, src + off, Cc, wt, R, R, Cc, 1, w);
+    };
+    for (int i = 0; i < e->L; ++i) {
+        both(e->lp[i].qkv, 3 * d, d, e->lb[i].wqkv, e->lb[i].wqkv_t);
+        both(e->lp[i].q, d, d, e->lb[i].wq, e->lb[i].wq_t);
+        both(e->lp[i].up_w, hid, d, e->lb[i].wup, e->lb[i].wup_t);
+        both(e->lp[i].down_w, d, hid, e->lb[i].wdown, e->lb[i].wdown_t);
+        hipLaunchKernelGGL(dw_tapmajor_kernel, g1((size_t)hid * 9), dim3(256), 0, s, src + e->lp[i].dw_w, e->lb[i].dww_t, hid);
+    }
+    HIP_TRY(hipGetLastError());
+    return TLD_OK;
+}
+
+// The training forward (the plain module graph of tld/denoiser.py, every tensor the backward needs saved in the engine's buffers) on the flat
+// parameter vector P, whose operand copies the caller has refreshed; ends in the per-row squared errors (row_loss) and the scalar loss.  Kernel
+// launches only.  Shared by tld_train_forward_backward_cb and tld_train_forward_loss.
+int train_forward(tld_train* e, const float* P, const float* x_noisy, const float* noise_level, const float* label, const float* target, int B,
+                  float* loss_out, float* pred_out, hipStream_t s) {
+    const int d = e->d, hid = e->hid, pd = e->pd, N = e->N, H = e->H, M = B * N, G = e->G;
+    const dim3 blk(256);
+    const int dw_rows = dwconv_band_rows(G);
+    const dim3 dw_grid(B * (hid / 64) * ((G + dw_rows - 1) / dw_rows));
+    const size_t dw_lds = dwconv_lds_bytes(G);
+    {
+        static PerDeviceOnce once;
+        once.run([&] { hipFuncSetAttribute(reinterpret_cast<const void*>(dwconv_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
+    }
+    const float inv_numel = 1.0f / (float)((size_t)B * e->C * e->S * e->S);
+    e->last_batch = B;
+    {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cap) != hipSuccess) (void)hipGetLastError();       // (a query that fails says nothing about this call's launches)
+        else if (cap != hipStreamCaptureStatusNone) e->captured_batch = B;
+    }
+    // the small fp32 products on the tiled kernel (see tld_train_kernels.h)
+    auto lin_fwd = [&](const float* in, int ldi, const float* W, const float* bias, float* out, int ldo, int R, int Nn, int K, float* pre, int gelu) {
+        hipLaunchKernelGGL(tiled_f32_kernel, dim3((Nn + 31) / 32, (R + 31) / 32), dim3(256), 0, s, in, (long)ldi, 1L, W, (long)K, 1L, bias, out, ldo, R, Nn, K, pre, gelu, 0);
+    };
+
+    // conditioning (tld/denoiser.py:105-122): sinusoid -> Linear -> GELU -> Linear | label_proj -> stack -> LayerNorm
+    hipLaunchKernelGGL(sinusoid_kernel, g1((size_t)B * e->ne / 2), blk, 0, s, noise_level, e->angular, e->sinb, B, e->ne / 2);
+    lin_fwd(e->sinb, e->ne, P + e->ff1w, P + e->ff1b, e->g1v, d, B, d, e->ne, e->h1, 1);
+    lin_fwd(e->g1v, d, P + e->ff3w, P + e->ff3b, e->ycat, 2 * d, B, d, d, nullptr, 0);
+    lin_fwd(label, e->text, P + e->lbw, P + e->lbb, e->ycat + d, 2 * d, B, d, e->text, nullptr, 0);
+    hipLaunchKernelGGL((ln_fwd_kernel<float>), dim3((2 * B + 3) / 4), blk, 0, s, e->ycat, P + e->nw, P + e->nb, (bf16*)nullptr, e->y, e->yst,
+                       (const float*)nullptr, 1, 2 * B, d);
+    // patch embedding (tld/denoiser.py:34-45,75-77)
+    {
+        EmbedTrain q{};
+        q.x = x_noisy; q.conv_w = P + e->cvw; q.conv_b = P + e->cvb; q.ln1_w = P + e->l1w; q.ln1_b = P + e->l1b; q.lin_w = P + e->liw; q.lin_b = P + e->lib;
+        q.ln2_w = P + e->l2w; q.ln2_b = P + e->l2b; q.pos = P + e->pos; q.p = e->p16; q.pn = e->p16n; q.st1 = e->est1; q.e = e->e; q.st2 = e->est2;
+        q.x0 = e->lb[0].x1; q.B = B; q.C = e->C; q.S = e->S; q.patch = e->cfg.patch_size; q.grid = G; q.pd = pd; q.d = d;
+        const size_t lwb = (size_t)pd * d * 4;
+        if (lwb <= 65536) {
+            const int nwg = (M + 3) / 4 < 4 * device_cu_count() ? (M + 3) / 4 : 4 * device_cu_count();
+            if (d <= 256) { PATH(PB_EMB_LDS); hipLaunchKernelGGL((embed_fwd_lds_kernel<1>), dim3(nwg), blk, lwb, s, q); }
+            else if (d <= 512) { PATH(PB_EMB_LDS + 1); hipLaunchKernelGGL((embed_fwd_lds_kernel<2>), dim3(nwg), blk, lwb, s, q); }
+            else if (d <= 768) { PATH(PB_EMB_LDS + 2); hipLaunchKernelGGL((embed_fwd_lds_kernel<3>), dim3(nwg), blk, lwb, s, q); }
+            else { PATH(PB_EMB_LDS + 3); hipLaunchKernelGGL((embed_fwd_lds_kernel<4>), dim3(nwg), blk, lwb, s, q); }
+        } else {
+            PATH(PB_EMB_PLAIN);
+            hipLaunchKernelGGL(embed_fwd_kernel, dim3((M + 3) / 4), blk, 0, s, q);
+        }
+    }
+    // x_out = x_in + delta [; a_out = LN(x_out), stats]   (delta == nullptr: LayerNorm of x_in alone)
+    auto resid_ln = [&](const bf16* x_in, const bf16* delta, bf16* x_out, const float* gamma, const float* beta, bf16* a_out, float2* st) {
+        const dim3 grid((M + 3) / 4);
+        if (d == 768) { PATH(PB_RESID_Q4 + 2); hipLaunchKernelGGL((resid_add_ln_q4_kernel<3>), grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M); }
+        else if (d == 512) { PATH(PB_RESID_Q4 + 1); hipLaunchKernelGGL((resid_add_ln_q4_kernel<2>), grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M); }
+        else if (d == 256) { PATH(PB_RESID_Q4); hipLaunchKernelGGL((resid_add_ln_q4_kernel<1>), grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M); }
+        else if (d == 1024) { PATH(PB_RESID_Q4 + 3); hipLaunchKernelGGL((resid_add_ln_q4_kernel<4>), grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M); }
+        else if (delta) { PATH(PB_RESID_GEN); hipLaunchKernelGGL(resid_add_ln_kernel, grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M, d); }
+        else { PATH(PB_RESID_GEN); hipLaunchKernelGGL((ln_fwd_kernel<bf16>), grid, blk, 0, s, x_in, gamma, beta, a_out, (float*)nullptr, st, (const float*)nullptr, 1, M, d); }
+    };
+    // (k | v) of the two conditioning tokens for every block in one launch (tld/transformer_blocks.py:66-68): the blocks' parameters are laid out
+    // identically, so block i's kv_linear.weight sits i block-strides after block 0's
+    const long blk_stride = e->L > 1 ? (long)(e->lp[1].kv - e->lp[0].kv) : 0;
+    const long kv_stride = (long)e->B * 2 * 2 * d;
+    hipLaunchKernelGGL(tiled_f32_kernel, dim3((2 * d + 31) / 32, (2 * B + 31) / 32, e->L), dim3(256), 0, s, e->y, (long)d, 1L, P + e->lp[0].kv, (long)d, 1L,
+                       (const float*)nullptr, e->kvc_all, 2 * d, 2 * B, 2 * d, d, (float*)nullptr, 0, 0, 0L, blk_stride, kv_stride);
+    for (int i = 0; i < e->L; ++i) {
+        LayerB& b = e->lb[i]; const LayerP& p = e->lp[i];
+        // x = x + SA(LN1 x)   (tld/transformer_blocks.py:51-59,136)
+        if (i == 0) resid_ln(b.x1, (const bf16*)nullptr, (bf16*)nullptr, P + p.n1w, P + p.n1b, b.a1, b.st1);      // (blocks > 0: LN1 rides on the previous block's last residual add)
+        {
+            GemmParams g{};
+            g.A = b.a1; g.lda = d; g.W = b.wqkv; g.ldw = d; g.M = M; g.N = 3 * d; g.K = d; g.out_bf16 = b.qk; g.ldo = 2 * d; g.vt = b.vt; g.ntok = N; g.d = d;
+            GEMM_TRY("training step", launch_gemm(g, EPI_QKV, s));
+        }
+        launch_attention(b.qk, b.vt, b.att, B, N, H, s);
+        resid_ln(b.x1, b.att, b.x2, P + p.n2w, P + p.n2b, b.a2, b.st2);
+        // x = x + CA(LN2 x, y)   (:62-72,137)
+        GEMM_TRY("training step", gemm_bf16(b.a2, d, b.wq, d, e->zero_bias, b.qc, M, d, d, s));
+        hipLaunchKernelGGL(cross_fwd_kernel, dim3(B * H), blk, 0, s, b.qc, b.kvc, b.cr, b.p0, N, d);
+        resid_ln(b.x2, b.cr, b.x3, P + p.n3w, P + p.n3b, b.a3, b.st3);
+        // x = x + MLPSepConv(LN3 x)   (:89-113,138)
+        GEMM_TRY("training step", gemm_bf16(b.a3, d, b.wup, d, P + p.up_b, b.h, M, hid, d, s));
+        hipLaunchKernelGGL(dwconv_kernel, dw_grid, blk, dw_lds, s, b.h, b.dww_t, P + p.dw_b, b.hc, b.gl, B, G, hid, 0, dw_rows);
+        GEMM_TRY("training step", gemm_bf16(b.gl, hid, b.wdown, hid, P + p.down_b, b.o, M, d, hid, s));
+        bf16* xnext = i + 1 < e->L ? e->lb[i + 1].x1 : e->xfin;
+        if (i + 1 < e->L) resid_ln(b.x3, b.o, xnext, P + e->lp[i + 1].n1w, P + e->lp[i + 1].n1b, e->lb[i + 1].a1, e->lb[i + 1].st1);      // + the next block's LN1
+        else resid_ln(b.x3, b.o, xnext, (const float*)nullptr, (const float*)nullptr, (bf16*)nullptr, (float2*)nullptr);
+    }
+    // out_proj + unpatchify + MSE (tld/denoiser.py:47-52,72,82; tld/train.py:167)
+    hipLaunchKernelGGL(tail_fwd_kernel, dim3((M + 3) / 4), blk, 0, s, e->xfin, P + e->outw, P + e->outb, target, pred_out, e->dout, e->row_loss, B, e->C, e->S,
+                       e->cfg.patch_size, G, pd, d, inv_numel);
+    hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), blk, 0, s, e->row_loss, M, inv_numel, loss_out);
+    return TLD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -253,7 +372,7 @@ int tld_train_create(const tld_config* cfg, tld_train** out) {
         DALLOC(e->dy_parts, (size_t)e->L * B * 2 * d); DALLOC(e->yst, B * 2);
         DALLOC(e->p16, M * pd); DALLOC(e->p16n, M * pd); DALLOC(e->e, M * d); DALLOC(e->patches, M * pd); DALLOC(e->de, M * d);
         DALLOC(e->dpn, M * pd); DALLOC(e->dp16, M * pd); DALLOC(e->est1, M); DALLOC(e->est2, M); DALLOC(e->xfin, M * d);
-        DALLOC(e->dout, M * pd); DALLOC(e->row_loss, M); DALLOC(e->io, 4);
+        DALLOC(e->dout, M * pd); DALLOC(e->row_loss, M); DALLOC(e->io, 4); DALLOC(e->pred_scratch, B * e->C * e->S * e->S);
         const size_t wide = hid > 3 * d ? hid : 3 * d;
         DALLOC(e->gx, M * d); DALLOC(e->gxb, M * d); e->tr_rows = M + 4096; DALLOC(e->T1, e->tr_rows * wide); DALLOC(e->T2, e->tr_rows * wide); DALLOC(e->dbig, M * hid);
         DALLOC(e->dsmall, M * 3 * d); DALLOC(e->dsmall2, M * d); DALLOC(e->attn_stats, 2 * M * e->H); DALLOC(e->scr, (size_t)pd * d + 64);
@@ -328,19 +447,7 @@ int tld_train_bind(tld_train* e, float* params, float* grads) {
 int tld_train_refresh_weights(tld_train* e, void* hip_stream) {
     if (!e || !e->params) return fail(TLD_ERR_STATE, "tld_train_bind first");
     DeviceGuard dg(e->cfg.device_id);
-    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-    const int d = e->d, hid = e->hid;
-    auto both = [&](int64_t off, int R, int Cc, bf16* w, bf16* wt) {       // [R, C] fp32 -> bf16 copy and bf16 transpose [C, R]
-        hipLaunchKernelGGL((transpose_to_bf16<float>), dim3((Cc + 31) / 32, (R + 31) / 32), dim3(256), 0, s, e->params + off, Cc, wt, R, R, Cc, 1, w);
-    };
-    for (int i = 0; i < e->L; ++i) {
-        both(e->lp[i].qkv, 3 * d, d, e->lb[i].wqkv, e->lb[i].wqkv_t);
-        both(e->lp[i].q, d, d, e->lb[i].wq, e->lb[i].wq_t);
-        both(e->lp[i].up_w, hid, d, e->lb[i].wup, e->lb[i].wup_t);
-        both(e->lp[i].down_w, d, hid, e->lb[i].wdown, e->lb[i].wdown_t);
-        hipLaunchKernelGGL(dw_tapmajor_kernel, g1((size_t)hid * 9), dim3(256), 0, s, e->params + e->lp[i].dw_w, e->lb[i].dww_t, hid);
-    }
-    HIP_TRY(hipGetLastError());
+    if (int rc = refresh_operands(e, e->params, reinterpret_cast<hipStream_t>(hip_stream))) return rc;
     e->weights_fresh = true;
     return TLD_OK;
 }
@@ -365,21 +472,13 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
     const int dw_rows = dwconv_band_rows(G);
     const dim3 dw_grid(B * (hid / 64) * ((G + dw_rows - 1) / dw_rows));
     const size_t dw_lds = dwconv_lds_bytes(G);
-    {
-        static PerDeviceOnce once;
-        once.run([&] { hipFuncSetAttribute(reinterpret_cast<const void*>(dwconv_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-    }
-    const float inv_numel = 1.0f / (float)((size_t)B * e->C * e->S * e->S);
     if (e->debug) {
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)
             return fail(TLD_ERR_STATE, "a debug step (tld_train_set_debug) cannot be captured into a graph");
         if (int rc = debug_begin(e, B, s)) return rc;
     }
-    // the three small fp32 products on the tiled kernel (see tld_train_kernels.h)
-    auto lin_fwd = [&](const float* in, int ldi, const float* W, const float* bias, float* out, int ldo, int R, int Nn, int K, float* pre, int gelu) {
-        hipLaunchKernelGGL(tiled_f32_kernel, dim3((Nn + 31) / 32, (R + 31) / 32), dim3(256), 0, s, in, (long)ldi, 1L, W, (long)K, 1L, bias, out, ldo, R, Nn, K, pre, gelu, 0);
-    };
+    // the two small fp32 products of the backward on the tiled kernel (see tld_train_kernels.h)
     auto lin_dx = [&](const float* dyp, int ldy, const float* W, float* dx, int ldx, int R, int Nn, int K, int acc) {      // dx[r, k] (+)= sum_n dy[r, n] W[n, k]
         hipLaunchKernelGGL(tiled_f32_kernel, dim3((K + 31) / 32, (R + 31) / 32), dim3(256), 0, s, dyp, (long)ldy, 1L, W, 1L, (long)K, (const float*)nullptr, dx, ldx, R, K, Nn,
                            (float*)nullptr, 0, acc);
@@ -389,76 +488,11 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
                            (float*)nullptr, 0, 0);
         if (db) hipLaunchKernelGGL(small_colsum, g1(Nn), dim3(256), 0, s, dyp, ldy, db, R, Nn, 0);
     };
+    const long blk_stride = e->L > 1 ? (long)(e->lp[1].kv - e->lp[0].kv) : 0;       // (as in train_forward: block i's kv_linear.weight and its (k | v) rows)
+    const long kv_stride = (long)e->B * 2 * 2 * d;
 
     // ================================================ forward ================================================
-    // conditioning (tld/denoiser.py:105-122): sinusoid -> Linear -> GELU -> Linear | label_proj -> stack -> LayerNorm
-    hipLaunchKernelGGL(sinusoid_kernel, g1((size_t)B * e->ne / 2), blk, 0, s, noise_level, e->angular, e->sinb, B, e->ne / 2);
-    lin_fwd(e->sinb, e->ne, P + e->ff1w, P + e->ff1b, e->g1v, d, B, d, e->ne, e->h1, 1);
-    lin_fwd(e->g1v, d, P + e->ff3w, P + e->ff3b, e->ycat, 2 * d, B, d, d, nullptr, 0);
-    lin_fwd(label, e->text, P + e->lbw, P + e->lbb, e->ycat + d, 2 * d, B, d, e->text, nullptr, 0);
-    hipLaunchKernelGGL((ln_fwd_kernel<float>), dim3((2 * B + 3) / 4), blk, 0, s, e->ycat, P + e->nw, P + e->nb, (bf16*)nullptr, e->y, e->yst,
-                       (const float*)nullptr, 1, 2 * B, d);
-    // patch embedding (tld/denoiser.py:34-45,75-77)
-    {
-        EmbedTrain q{};
-        q.x = x_noisy; q.conv_w = P + e->cvw; q.conv_b = P + e->cvb; q.ln1_w = P + e->l1w; q.ln1_b = P + e->l1b; q.lin_w = P + e->liw; q.lin_b = P + e->lib;
-        q.ln2_w = P + e->l2w; q.ln2_b = P + e->l2b; q.pos = P + e->pos; q.p = e->p16; q.pn = e->p16n; q.st1 = e->est1; q.e = e->e; q.st2 = e->est2;
-        q.x0 = e->lb[0].x1; q.B = B; q.C = e->C; q.S = e->S; q.patch = e->cfg.patch_size; q.grid = G; q.pd = pd; q.d = d;
-        const size_t lwb = (size_t)pd * d * 4;
-        if (lwb <= 65536) {
-            const int nwg = (M + 3) / 4 < 4 * device_cu_count() ? (M + 3) / 4 : 4 * device_cu_count();
-            if (d <= 256) { PATH(PB_EMB_LDS); hipLaunchKernelGGL((embed_fwd_lds_kernel<1>), dim3(nwg), blk, lwb, s, q); }
-            else if (d <= 512) { PATH(PB_EMB_LDS + 1); hipLaunchKernelGGL((embed_fwd_lds_kernel<2>), dim3(nwg), blk, lwb, s, q); }
-            else if (d <= 768) { PATH(PB_EMB_LDS + 2); hipLaunchKernelGGL((embed_fwd_lds_kernel<3>), dim3(nwg), blk, lwb, s, q); }
-            else { PATH(PB_EMB_LDS + 3); hipLaunchKernelGGL((embed_fwd_lds_kernel<4>), dim3(nwg), blk, lwb, s, q); }
-        } else {
-            PATH(PB_EMB_PLAIN);
-            hipLaunchKernelGGL(embed_fwd_kernel, dim3((M + 3) / 4), blk, 0, s, q);
-        }
-    }
-    // x_out = x_in + delta [; a_out = LN(x_out), stats]   (delta == nullptr: LayerNorm of x_in alone)
-    auto resid_ln = [&](const bf16* x_in, const bf16* delta, bf16* x_out, const float* gamma, const float* beta, bf16* a_out, float2* st) {
-        const dim3 grid((M + 3) / 4);
-        if (d == 768) { PATH(PB_RESID_Q4 + 2); hipLaunchKernelGGL((resid_add_ln_q4_kernel<3>), grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M); }
-        else if (d == 512) { PATH(PB_RESID_Q4 + 1); hipLaunchKernelGGL((resid_add_ln_q4_kernel<2>), grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M); }
-        else if (d == 256) { PATH(PB_RESID_Q4); hipLaunchKernelGGL((resid_add_ln_q4_kernel<1>), grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M); }
-        else if (d == 1024) { PATH(PB_RESID_Q4 + 3); hipLaunchKernelGGL((resid_add_ln_q4_kernel<4>), grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M); }
-        else if (delta) { PATH(PB_RESID_GEN); hipLaunchKernelGGL(resid_add_ln_kernel, grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M, d); }
-        else { PATH(PB_RESID_GEN); hipLaunchKernelGGL((ln_fwd_kernel<bf16>), grid, blk, 0, s, x_in, gamma, beta, a_out, (float*)nullptr, st, (const float*)nullptr, 1, M, d); }
-    };
-    // (k | v) of the two conditioning tokens for every block in one launch (tld/transformer_blocks.py:66-68): the blocks' parameters are laid out
-    // identically, so block i's kv_linear.weight sits i block-strides after block 0's
-    const long blk_stride = e->L > 1 ? (long)(e->lp[1].kv - e->lp[0].kv) : 0;
-    const long kv_stride = (long)e->B * 2 * 2 * d;
-    hipLaunchKernelGGL(tiled_f32_kernel, dim3((2 * d + 31) / 32, (2 * B + 31) / 32, e->L), dim3(256), 0, s, e->y, (long)d, 1L, P + e->lp[0].kv, (long)d, 1L,
-                       (const float*)nullptr, e->kvc_all, 2 * d, 2 * B, 2 * d, d, (float*)nullptr, 0, 0, 0L, blk_stride, kv_stride);
-    for (int i = 0; i < e->L; ++i) {
-        LayerB& b = e->lb[i]; const LayerP& p = e->lp[i];
-        // x = x + SA(LN1 x)   (tld/transformer_blocks.py:51-59,136)
-        if (i == 0) resid_ln(b.x1, (const bf16*)nullptr, (bf16*)nullptr, P + p.n1w, P + p.n1b, b.a1, b.st1);      // (blocks > 0: LN1 rides on the previous block's last residual add)
-        {
-            GemmParams g{};
-            g.A = b.a1; g.lda = d; g.W = b.wqkv; g.ldw = d; g.M = M; g.N = 3 * d; g.K = d; g.out_bf16 = b.qk; g.ldo = 2 * d; g.vt = b.vt; g.ntok = N; g.d = d;
-            GEMM_TRY("training step", launch_gemm(g, EPI_QKV, s));
-        }
-        launch_attention(b.qk, b.vt, b.att, B, N, H, s);
-        resid_ln(b.x1, b.att, b.x2, P + p.n2w, P + p.n2b, b.a2, b.st2);
-        // x = x + CA(LN2 x, y)   (:62-72,137)
-        GEMM_TRY("training step", gemm_bf16(b.a2, d, b.wq, d, e->zero_bias, b.qc, M, d, d, s));
-        hipLaunchKernelGGL(cross_fwd_kernel, dim3(B * H), blk, 0, s, b.qc, b.kvc, b.cr, b.p0, N, d);
-        resid_ln(b.x2, b.cr, b.x3, P + p.n3w, P + p.n3b, b.a3, b.st3);
-        // x = x + MLPSepConv(LN3 x)   (:89-113,138)
-        GEMM_TRY("training step", gemm_bf16(b.a3, d, b.wup, d, P + p.up_b, b.h, M, hid, d, s));
-        hipLaunchKernelGGL(dwconv_kernel, dw_grid, blk, dw_lds, s, b.h, b.dww_t, P + p.dw_b, b.hc, b.gl, B, G, hid, 0, dw_rows);
-        GEMM_TRY("training step", gemm_bf16(b.gl, hid, b.wdown, hid, P + p.down_b, b.o, M, d, hid, s));
-        bf16* xnext = i + 1 < e->L ? e->lb[i + 1].x1 : e->xfin;
-        if (i + 1 < e->L) resid_ln(b.x3, b.o, xnext, P + e->lp[i + 1].n1w, P + e->lp[i + 1].n1b, e->lb[i + 1].a1, e->lb[i + 1].st1);      // + the next block's LN1
-        else resid_ln(b.x3, b.o, xnext, (const float*)nullptr, (const float*)nullptr, (bf16*)nullptr, (float2*)nullptr);
-    }
-    // out_proj + unpatchify + MSE (tld/denoiser.py:47-52,72,82; tld/train.py:167)
-    hipLaunchKernelGGL(tail_fwd_kernel, dim3((M + 3) / 4), blk, 0, s, e->xfin, P + e->outw, P + e->outb, target, pred_out, e->dout, e->row_loss, B, e->C, e->S,
-                       e->cfg.patch_size, G, pd, d, inv_numel);
-    hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), blk, 0, s, e->row_loss, M, inv_numel, loss_out);
+    if (int rc = train_forward(e, P, x_noisy, noise_level, label, target, B, loss_out, pred_out, s)) return rc;
 
     // ================================================ backward ===============================================
     if (e->debug) for (int i = 0; i < e->L; ++i) SNAP("blk" + std::to_string(i) + ".gl", e->lb[i].gl, ST_BF16, s, M, hid);       // (the backward writes dh there)
@@ -667,6 +701,70 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
         grad_ready(user, 0, e->lp[0].qkv);
         grad_ready(user, e->outw, e->nparam - e->outw);
     }
+    HIP_TRY(hipGetLastError());
+    return TLD_OK;
+}
+
+/* The forward half of tld_train_forward_backward on any flat weight vector (include/tld_hip.h): train_forward, then the per-sample reduction.
+ * Writes no gradient, calls nothing back, advances nothing. */
+int tld_train_forward_loss(tld_train* e, const float* weights, const float* x_noisy, const float* noise_level, const float* label, const float* target,
+                           int32_t batch, float* loss_out, double* sample_loss_out, float* pred_out, void* hip_stream) {
+    if (!e || !x_noisy || !noise_level || !label || !target || !loss_out) return fail(TLD_ERR_INVALID, "forward loss: null argument");
+    if (batch <= 0 || batch > e->B) return fail(TLD_ERR_INVALID, "forward loss: batch %d outside [1, max_batch = %d]", batch, e->B);
+    if (sample_loss_out && ((uintptr_t)sample_loss_out & 7)) return fail(TLD_ERR_INVALID, "forward loss: sample_loss_out must be 8-byte aligned");
+    if (!e->params) return fail(TLD_ERR_STATE, "tld_train_bind first");
+    if (e->debug) return fail(TLD_ERR_STATE, "forward loss: the stage hook is on (tld_train_set_debug): a debug call poisons the gradient vector, which this entry never writes");
+    DeviceGuard dg(e->cfg.device_id);
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    const bool bound = !weights || weights == e->params;
+    const float* P = bound ? e->params : weights;
+    if (!bound) {
+        e->weights_fresh = false;                                        // (first: an error below must not leave foreign operand copies marked fresh)
+        if (int rc = refresh_operands(e, P, s)) return rc;
+    } else if (!e->weights_fresh) {
+        if (int rc = refresh_operands(e, P, s)) return rc;
+        e->weights_fresh = true;
+    }
+    if (int rc = train_forward(e, P, x_noisy, noise_level, label, target, batch, loss_out, pred_out ? pred_out : e->pred_scratch, s)) return rc;
+    if (sample_loss_out) {
+        if (int rc = tld_train_sample_loss(e, nullptr, batch, 0, 0, sample_loss_out, hip_stream)) return rc;
+    }
+    HIP_TRY(hipGetLastError());
+    return TLD_OK;
+}
+
+/* out[b] = (sum of the rows of sample b) / elems_per_sample in double, fixed order (sample_loss_kernel). */
+int tld_train_sample_loss(tld_train* e, const float* row_sq, int32_t batch, int32_t rows_per_sample, int64_t elems_per_sample, double* out, void* hip_stream) {
+    if (!out || ((uintptr_t)out & 7)) return fail(TLD_ERR_INVALID, "sample loss: out is null or not 8-byte aligned");
+    if (batch <= 0) return fail(TLD_ERR_INVALID, "sample loss: batch %d", batch);
+    if (!row_sq) {
+        if (!e) return fail(TLD_ERR_INVALID, "sample loss: neither rows nor an engine");
+        if (e->last_batch == 0) return fail(TLD_ERR_STATE, "sample loss: the engine has run no forward yet");
+        if (batch != e->last_batch && batch != e->captured_batch)
+            return fail(TLD_ERR_STATE, "sample loss: batch %d, but the engine's last forward had %d samples", batch, e->last_batch);
+        row_sq = e->row_loss; rows_per_sample = e->N; elems_per_sample = (int64_t)e->C * e->S * e->S;
+    } else if (rows_per_sample <= 0 || elems_per_sample <= 0) {
+        return fail(TLD_ERR_INVALID, "sample loss: rows_per_sample %d, elems_per_sample %lld", rows_per_sample, (long long)elems_per_sample);
+    }
+    DeviceGuard dg(e ? e->cfg.device_id : std::max(0, ptr_device(out)));
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    if (rows_per_sample <= 1024)
+        hipLaunchKernelGGL((sample_loss_kernel<true>), dim3(((unsigned)batch + 3) / 4), dim3(256), 0, s, row_sq, batch, rows_per_sample, (double)elems_per_sample, out);
+    else
+        hipLaunchKernelGGL((sample_loss_kernel<false>), dim3((unsigned)batch), dim3(256), 0, s, row_sq, batch, rows_per_sample, (double)elems_per_sample, out);
+    HIP_TRY(hipGetLastError());
+    return TLD_OK;
+}
+
+/* The accumulator by noise level (state layout: include/tld_hip.h); one workgroup, serial per bucket (loss_buckets_kernel). */
+int tld_train_loss_buckets(const double* sample_loss, const float* noise_level, int32_t batch, int32_t n_buckets, double* state, void* hip_stream) {
+    if (!sample_loss || !noise_level || !state) return fail(TLD_ERR_INVALID, "loss buckets: null pointer");
+    if (((uintptr_t)state & 7) || ((uintptr_t)sample_loss & 7)) return fail(TLD_ERR_INVALID, "loss buckets: state and sample_loss must be 8-byte aligned");
+    if (n_buckets < 1 || n_buckets > LOSS_BUCKETS_MAX) return fail(TLD_ERR_INVALID, "loss buckets: n_buckets %d outside [1, %d]", n_buckets, LOSS_BUCKETS_MAX);
+    if (batch < 1) return fail(TLD_ERR_INVALID, "loss buckets: batch %d", batch);
+    DeviceGuard dg(std::max(0, ptr_device(state)));
+    hipLaunchKernelGGL(loss_buckets_kernel, dim3(1), dim3(LOSS_BUCKETS_THREADS), 0, reinterpret_cast<hipStream_t>(hip_stream), sample_loss, noise_level, batch, n_buckets,
+                       state);
     HIP_TRY(hipGetLastError());
     return TLD_OK;
 }

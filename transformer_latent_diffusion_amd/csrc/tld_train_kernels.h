@@ -1253,5 +1253,64 @@ __global__ __launch_bounds__(256) void adam_ema_guarded_kernel(float* __restrict
     }
 }
 
+// ---- held-out loss: per-sample reduction of the row errors and the accumulator by noise level (include/tld_hip.h) --------
+// fixed xor butterfly over the 64 lanes of a wave: every lane ends with the same bits (each level adds the same two values in both lanes)
+__device__ inline double wave_sum_f64(double a) {
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) a += __shfl_xor(a, m, 64);
+    return a;
+}
+// out[b] = (sum_t row_sq[b R + t]) / elems in double.  WAVE: one wave per sample (four samples per workgroup), lane l adds rows l, l + 64, ... in
+// order; otherwise one workgroup per sample, thread t adds rows t, t + 256, ..., and the four wave totals are added as (w0 + w1) + (w2 + w3).
+// Either order depends on R alone, never on b or the batch: the same rows give the same bits at any position.  No atomics.
+template <bool WAVE>
+__global__ __launch_bounds__(256) void sample_loss_kernel(const float* __restrict__ row_sq, int batch, int R, double elems, double* __restrict__ out) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (WAVE) {
+        const int64_t b = (int64_t)blockIdx.x * 4 + wave;
+        if (b >= batch) return;
+        const float* r = row_sq + b * (int64_t)R;
+        double a = 0.0;
+        for (int t = lane; t < R; t += 64) a += (double)r[t];
+        a = wave_sum_f64(a);
+        if (lane == 0) out[b] = a / elems;
+    } else {
+        __shared__ double sh[4];
+        const int64_t b = blockIdx.x;
+        const float* r = row_sq + b * (int64_t)R;
+        double a = 0.0;
+        for (int t = threadIdx.x; t < R; t += 256) a += (double)r[t];
+        a = wave_sum_f64(a);
+        if (lane == 0) sh[wave] = a;
+        __syncthreads();
+        if (threadIdx.x == 0) out[b] = ((sh[0] + sh[1]) + (sh[2] + sh[3])) / elems;
+    }
+}
+
+constexpr int LOSS_BUCKETS_MAX = 256;
+constexpr int LOSS_BUCKETS_THREADS = 320;      // five waves: one thread per bucket and one for the total
+// state[0, n) += losses by bucket, [n, 2n) += counts, [2n] += every accepted loss, [2n + 1] += rejected samples (level outside [0, 1], NaN included).
+// One workgroup; thread k < n owns bucket k and walks b = 0 .. batch - 1 in order, thread n owns the total and the rejected count: the state after
+// any sequence of calls is what the serial loop over the samples gives, bit for bit.  A non-finite loss is added as it is.
+__global__ __launch_bounds__(LOSS_BUCKETS_THREADS) void loss_buckets_kernel(const double* __restrict__ sample_loss, const float* __restrict__ level, int batch,
+                                                                            int n, double* __restrict__ state) {
+#pragma clang fp contract(off)
+    const int k = threadIdx.x;
+    if (k > n) return;
+    double sum = state[k < n ? k : 2 * n], cnt = state[k < n ? n + k : 2 * n + 1];
+    for (int b = 0; b < batch; ++b) {
+        const double l = (double)level[b];
+        const bool ok = l >= 0.0 && l <= 1.0;
+        int q = ok ? (int)floor(l * (double)n) : -1;
+        if (q > n - 1) q = n - 1;
+        if (k < n) {
+            if (q == k) { sum += sample_loss[b]; cnt += 1.0; }
+        } else if (ok) sum += sample_loss[b];
+        else cnt += 1.0;
+    }
+    state[k < n ? k : 2 * n] = sum;
+    state[k < n ? n + k : 2 * n + 1] = cnt;
+}
+
 }  // namespace train
 }  // namespace tld

@@ -76,6 +76,77 @@ def update_ema_(ema: torch.Tensor, params: torch.Tensor, alpha: float = 0.999) -
     ema.mul_(alpha).add_(params, alpha=1 - alpha)
 
 
+EVAL_SEED_XOR = 0x5851F42D4C957F2D     # eval_loss's default Philox key is data_seed ^ this: the evaluation never meets the training stream
+
+
+def bucket_midpoints(n_buckets: int) -> np.ndarray:
+    """The default evaluation levels: the midpoints (k + 0.5) / n of the n noise-level bins, float64."""
+    return (np.arange(int(n_buckets), dtype=np.float64) + 0.5) / float(n_buckets)
+
+
+def eval_plan(n: int, batch_size: int, world: int, rank: int, levels):
+    """The batch / level plan of ``Trainer.eval_loss``, a pure host function: the ``n`` positions of the evaluation are cut into batches
+    ``[j * batch_size, (j + 1) * batch_size)`` (the last one may be short), rank ``r`` of ``world`` takes the batches ``j = r (mod world)``, and
+    global position ``p`` is evaluated at ``levels[p % len(levels)]`` whatever the world size.  Returns ``[(j, start, stop, levels float64
+    [stop - start]), ...]`` for this rank, in the order it runs them."""
+    n, batch_size, world, rank = int(n), int(batch_size), int(world), int(rank)
+    lv = np.asarray(levels, dtype=np.float64).reshape(-1)
+    if n < 0 or batch_size < 1 or world < 1 or not 0 <= rank < world:
+        raise ValueError(f"eval_plan(n={n}, batch_size={batch_size}, world={world}, rank={rank})")
+    if lv.size == 0 or not bool(np.all((lv >= 0.0) & (lv <= 1.0))):          # (NaN fails the comparison)
+        raise ValueError("noise levels must be a non-empty sequence inside [0, 1]")
+    plan = []
+    for j in range(rank, (n + batch_size - 1) // batch_size, world):
+        start, stop = j * batch_size, min(n, (j + 1) * batch_size)
+        plan.append((j, start, stop, lv[np.arange(start, stop) % lv.size]))
+    return plan
+
+
+class EvalLoss:
+    """Loss by noise level: the device state vector of ``tld_train_loss_buckets`` (fp64 ``[2 n + 2]``: sums per bucket, counts, total sum, rejected
+    count) and its readouts.  Every property is a device tensor computed without a host wait; ``cpu()`` synchronises and returns a dict."""
+
+    def __init__(self, n_buckets: int, device=None, state: Optional[torch.Tensor] = None):
+        self.n_buckets = int(n_buckets)
+        if not 1 <= self.n_buckets <= 256:
+            raise ValueError(f"n_buckets = {n_buckets}: 1 .. 256")
+        self.state = state if state is not None else torch.zeros(2 * self.n_buckets + 2, dtype=torch.float64, device=device)
+        if self.state.dtype != torch.float64 or self.state.numel() != 2 * self.n_buckets + 2:
+            raise ValueError("state must be float64 [2 n_buckets + 2]")
+
+    def zero_(self) -> "EvalLoss":
+        self.state.zero_()
+        return self
+
+    @property
+    def bucket_count(self) -> torch.Tensor:
+        return self.state[self.n_buckets:2 * self.n_buckets]
+
+    @property
+    def bucket_loss(self) -> torch.Tensor:
+        """Mean loss per bucket; NaN where the bucket is empty."""
+        c = self.bucket_count
+        return torch.where(c > 0, self.state[:self.n_buckets] / c, torch.full_like(c, float("nan")))
+
+    @property
+    def loss(self) -> torch.Tensor:
+        """Mean loss over every accepted sample (NaN when there is none)."""
+        return self.state[2 * self.n_buckets] / self.bucket_count.sum()
+
+    @property
+    def rejected(self) -> torch.Tensor:
+        return self.state[2 * self.n_buckets + 1]
+
+    def cpu(self) -> Dict[str, object]:
+        st = self.state.detach().cpu().numpy()
+        n = self.n_buckets
+        cnt = st[n:2 * n]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return {"loss": float(st[2 * n] / cnt.sum()) if cnt.sum() > 0 else float("nan"),
+                    "bucket_loss": np.where(cnt > 0, st[:n] / np.where(cnt > 0, cnt, 1.0), np.nan), "bucket_count": cnt.astype(np.int64),
+                    "rejected": int(st[2 * n + 1]), "n_buckets": n}
+
+
 class Trainer:
     """One model replica + optimizer state on one device.  With ``torch.distributed`` initialised (backend ``nccl`` = RCCL) every rank
     holds a replica, gradients are summed with one all-reduce of the flat vector per step and divided by the world size."""
@@ -84,7 +155,7 @@ class Trainer:
                  state_dict: Optional[Mapping[str, torch.Tensor]] = None, init_seed: int = 0, max_batch: Optional[int] = None,
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, keep_ema: bool = True, process_group=None,
                  overlap_allreduce: bool = True, use_graph: Optional[bool] = None, max_grad_norm: Optional[float] = None,
-                 skip_nonfinite: bool = False, data_seed: int = 0):
+                 skip_nonfinite: bool = False, data_seed: int = 0, loss_buckets: Optional[int] = None):
         self.cfg = denoiser_cfg
         self.tc = train_cfg if train_cfg is not None else TrainConfig()
         dev = torch.device(device)
@@ -167,6 +238,9 @@ class Trainer:
         # the device data path (prepare_batch / train_step_from): the Philox key of every draw, and the kernel's count of refused row indices
         self.data_seed = int(data_seed) & (2 ** 64 - 1)
         self._bad = torch.zeros(1, dtype=torch.int32, device=self.device)
+        # loss by noise level: the batch of the engine's last forward (sample_loss), and with loss_buckets=n the running accumulator of the training loss
+        self._last_batch = 0
+        self.train_loss_levels = EvalLoss(loss_buckets, self.device) if loss_buckets is not None else None
 
     def _check_layout(self):
         L = _lib.lib()
@@ -364,10 +438,19 @@ class Trainer:
                     for dst, src in zip(self._static[:4], (xn, nl, lab, tgt)):
                         dst.copy_(src)
                 self._graph.replay()
+                self._note_forward(B, self._static[1])
                 return self._fold_micro_batch(last_micro_batch), self._static[4].clone()         # (a copy: the static buffer is overwritten by the next replay)
         pred = torch.empty_like(xn)
         launch(xn, nl, lab, tgt, pred)
+        self._note_forward(B, nl)
         return self._fold_micro_batch(last_micro_batch), pred
+
+    def _note_forward(self, B: int, nl: torch.Tensor) -> None:
+        """After a forward_backward: remember its batch for ``sample_loss`` and, with ``loss_buckets``, add the step's per-sample losses to
+        ``train_loss_levels`` at the step's own noise levels (two launches, outside the captured region)."""
+        self._last_batch = B
+        if self.train_loss_levels is not None:
+            self._accumulate_levels(self.sample_loss(), nl, self.train_loss_levels)
 
     def _fold_micro_batch(self, last: bool) -> torch.Tensor:
         """Gradient accumulation bookkeeping after a forward_backward; returns the loss tensor to hand out (a copy while accumulating: the engine
@@ -601,6 +684,128 @@ class Trainer:
         if st is not None:
             st["free"] = torch.cuda.Event()
             st["free"].record(torch.cuda.current_stream(self.device))
+
+    # ---- held-out loss, per sample and by noise level ----------------------------------------------------
+    def _loss_weights(self, weights) -> Optional[torch.Tensor]:
+        """``"model"`` -> None (the bound parameters), ``"ema"`` -> the EMA vector, or a flat fp32 device vector of ``numel`` elements."""
+        if isinstance(weights, str):
+            if weights in ("model", "live"):
+                return None
+            if weights == "ema":
+                return self._weights_vector("ema")
+            raise ValueError(f"weights = {weights!r}: 'model', 'ema' or a flat tensor")
+        if not isinstance(weights, torch.Tensor):
+            raise TypeError("weights: 'model', 'ema' or a flat float32 tensor on the trainer's device")
+        if weights.dtype != torch.float32 or weights.device != self.device or weights.numel() != self.numel or not weights.is_contiguous():
+            raise ValueError(f"a weight vector must be contiguous float32 [{self.numel}] on {self.device}")
+        return weights
+
+    def _forward_loss(self, xn, nl, lab, tgt, wvec, loss, sample, pred) -> None:
+        B = int(xn.shape[0])
+        p = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().tld_train_forward_loss(self._h, p(wvec), p(xn), p(nl), p(lab), p(tgt), B, p(loss), p(sample), p(pred),
+                                                         C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "tld_train_forward_loss")
+        self._last_batch = B
+
+    def forward_loss(self, x_noisy: torch.Tensor, noise_level: torch.Tensor, label: torch.Tensor, target: torch.Tensor, *, weights="model"):
+        """The forward half of ``forward_backward`` on the live parameters (``"model"``), the EMA copy (``"ema"``) or any flat weight vector:
+        returns ``(loss [1], sample_loss fp64 [B], pred)`` on the device.  Same kernels, same bits as the training forward; it writes no gradient,
+        advances no counter and leaves an accumulation in progress alone.  The loss is a tensor of its own (not the training step's cell)."""
+        dev = self.device
+        t = lambda a: a.detach().to(dev, torch.float32).contiguous()
+        xn, nl, lab, tgt = t(x_noisy), t(noise_level).view(-1), t(label), t(target)
+        B = xn.shape[0]
+        if not (nl.numel() == B and lab.shape[0] == B and tgt.shape == xn.shape):
+            raise ValueError("inconsistent batch shapes")
+        if B > self.max_batch:
+            raise ValueError(f"batch {B} exceeds max_batch {self.max_batch}")
+        wvec = self._loss_weights(weights)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        sample = torch.empty(B, dtype=torch.float64, device=dev)
+        pred = torch.empty_like(xn)
+        self._forward_loss(xn, nl, lab, tgt, wvec, loss, sample, pred)
+        return loss, sample, pred
+
+    def sample_loss(self) -> torch.Tensor:
+        """Per-sample MSE (fp64 ``[B]``, summed in double in a fixed order) of the last ``forward_backward`` or ``forward_loss``, from the row errors
+        the engine still holds -- after a graph replay too, which fills the same buffer."""
+        if self._last_batch <= 0:
+            raise RuntimeError("sample_loss: no forward has run yet")
+        out = torch.empty(self._last_batch, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().tld_train_sample_loss(self._h, None, self._last_batch, 0, 0, C.c_void_p(out.data_ptr()),
+                                                        C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "tld_train_sample_loss")
+        return out
+
+    def _accumulate_levels(self, sample: torch.Tensor, nl: torch.Tensor, acc: EvalLoss) -> None:
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().tld_train_loss_buckets(C.c_void_p(sample.data_ptr()), C.c_void_p(nl.data_ptr()), int(sample.numel()), acc.n_buckets,
+                                                         C.c_void_p(acc.state.data_ptr()), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
+                       "tld_train_loss_buckets")
+
+    def reset_loss_levels(self) -> None:
+        """Zero ``train_loss_levels`` (``Trainer(loss_buckets=n)``)."""
+        if self.train_loss_levels is None:
+            raise RuntimeError("this Trainer keeps no training loss by noise level (construct it with loss_buckets=n)")
+        self.train_loss_levels.zero_()
+
+    def eval_loss(self, dataset, idx, *, weights="ema", noise_levels=None, n_buckets: int = 10, batch_size: Optional[int] = None,
+                  seed: Optional[int] = None, reduce: bool = True) -> EvalLoss:
+        """Held-out loss of rows ``idx`` of a ``data.DeviceLatentDataset`` by noise level, on the device and without a host wait.  The evaluation
+        is a fixed sequence of batches ``idx[j B : (j + 1) B]`` (``B = batch_size or max_batch``, the last one may be short); position ``p``
+        gets the level ``noise_levels[p % L]`` (default: the ``n_buckets`` bin midpoints); batch ``j`` is built by ``tld_train_prepare_batch_at`` with
+        key ``seed`` (default ``data_seed ^ EVAL_SEED_XOR``), replica 0, step ``j`` and no label dropout, run through ``forward_loss`` on
+        ``weights`` and added to the accumulator.  With more than one rank, rank ``r`` takes the batches ``j = r (mod world)`` and ``reduce=True``
+        sums the state with one all-reduce: the result is a function of (weights, dataset, idx, B, levels, seed) and not of the world size, up to
+        the order of a few double additions.  Nothing of the training step moves: ``global_step``, ``step``, gradients, an accumulation in
+        progress and pending reductions stay as they are, and the launches are eager (never captured)."""
+        dev = self.device
+        if dataset.device.type != "cuda" or (dataset.device.index if dataset.device.index is not None else torch.cuda.current_device()) != dev.index:
+            raise ValueError(f"the dataset lives on {dataset.device}, this trainer on {dev}")
+        shape = (self.cfg.n_channels, self.cfg.image_size, self.cfg.image_size)
+        if tuple(dataset.sample_shape) != shape or dataset.text_emb.shape[1] != self.cfg.text_emb_size:
+            raise ValueError(f"dataset rows are {tuple(dataset.sample_shape)} with {dataset.text_emb.shape[1]} text features; the model takes {shape} and "
+                             f"{self.cfg.text_emb_size}")
+        if not (isinstance(idx, torch.Tensor) and idx.device.type == "cuda"):
+            host = torch.as_tensor(idx).reshape(-1)
+            if host.numel() and (host.dtype.is_floating_point or int(host.min()) < 0 or int(host.max()) >= len(dataset)):
+                raise IndexError(f"evaluation indices outside [0, {len(dataset)}) (or not integers)")
+            idx = host
+        idx = idx.reshape(-1).to(dev, torch.int64).contiguous()
+        n = int(idx.numel())
+        if n == 0:
+            raise ValueError("an empty evaluation set")
+        B = int(batch_size) if batch_size is not None else self.max_batch
+        if not 1 <= B <= self.max_batch:
+            raise ValueError(f"batch_size {B} outside [1, max_batch = {self.max_batch}]")
+        out = EvalLoss(n_buckets, dev)
+        levels = np.asarray(noise_levels, dtype=np.float64).reshape(-1) if noise_levels is not None else bucket_midpoints(out.n_buckets)
+        plan = eval_plan(n, B, self._world(), self._rank(), levels)          # (refuses levels outside [0, 1])
+        wvec = self._loss_weights(weights)
+        key = (self.data_seed ^ EVAL_SEED_XOR if seed is None else int(seed)) & (2 ** 64 - 1)
+        # the level table goes up once, from pinned memory: the copy is ordered on the stream and the host does not wait for it
+        table = torch.from_numpy(np.ascontiguousarray(levels)).pin_memory().to(dev, non_blocking=True)
+        level_at = table[torch.arange(n, device=dev) % table.numel()]
+        f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+        x_noisy, noise_level, label, target = f(B, *shape), f(B), f(B, self.cfg.text_emb_size), f(B, *shape)
+        loss, sample = f(1), torch.empty(B, dtype=torch.float64, device=dev)
+        src = dataset.source()
+        p = lambda a: C.c_void_p(a.data_ptr())
+        L = _lib.lib()
+        for j, start, stop, _ in plan:
+            b = stop - start
+            with torch.cuda.device(dev):
+                _lib.check(L.tld_train_prepare_batch_at(self._h, C.byref(src), p(idx[start:stop]), b, key, j, 0, float(self.tc.beta_a), float(self.tc.beta_b),
+                                                        0.0, p(x_noisy), p(noise_level), p(label), p(target), None, None, None, p(self._bad),
+                                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), p(level_at[start:stop])),
+                           "tld_train_prepare_batch_at")
+            self._forward_loss(x_noisy[:b], noise_level[:b], label[:b], target[:b], wvec, loss, sample[:b], None)
+            self._accumulate_levels(sample[:b], noise_level[:b], out)
+        if reduce and self._world() > 1:
+            import torch.distributed as dist
+            dist.all_reduce(out.state, op=dist.ReduceOp.SUM, group=self.group)
+        return out
 
     # ---- evaluation while training (tld/train.py:23-40,140-147) --------------------------------------------------------------------
     def _weights_vector(self, weights: str) -> torch.Tensor:
