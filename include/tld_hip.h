@@ -243,6 +243,9 @@ TLD_API int tld_debug_decode_stage(const void* raw, const void* aux, int32_t dty
  *   blk<i>.qk [Mi, 2 d] and blk<i>.vt [samples, d, tokens] on the two-kernel path, blk<i>.att [Mi, d], blk<i>.sa [M, d] (x + att, fp32), blk<i>.ca
  *   [M, d], blk<i>.stats [M, 2] ((mean, rstd) of the stored row) or blk<i>.xn3 [M, d] without the LayerNorm-3 fold, blk<i>.hid_pre [M, hid] where
  *   the up-projection's output exists in HBM, blk<i>.hid [M, hid], blk<i>.splitk [splits, M, d] in the low-latency classes, blk<i>.mlp [M, d];
+ *   the LAST block's blk<i>.mlp, where out_proj is folded into its down projection (default class, bf16 operands; TLD_FOLD_TAIL=0 turns the fold off): the
+ *   product path never forms that row, so the stage is an fp32 evaluation x2 + hid Wd^T + bd made for the hook alone, in the hook's own memory
+ *   (an fp32-output GEMM plus a row add; no product buffer is touched, no launch path recorded) -- `out` is the folded tail of blk<i>.ca and blk<i>.hid;
  *   out [batch, C S S] (the forward's output before any I/O cast); of a sampler's debug step: step.x_t, step.x0_prev (its inputs), step.out
  *   [2 B, C S S], step.x0, step.x_next (absent at the last step);
  *   conditioning, read in place: cond.sin [Tn, noise_embed_dims], cond.h1 [Tn, d] (the Tn noise rows: sinusoid features, GELU(ff1)), cond.pre, cond.y [T, d] (T token rows: noise rows, then label rows), cond.kv [L, T, 2 d], cond.wq [L, T, H, d],
@@ -261,13 +264,14 @@ TLD_API int tld_debug_decode_stage(const void* raw, const void* aux, int32_t dty
  * Launch-path bits of tld_engine_debug_paths (bit number : path):
  *    0 embed plain   1-4 embed_mfma<2 | 4 | 6 | 8>   5-8 layernorm q4<1..4>   9 layernorm generic   10 layernorm mx8 (fp8 mode)
  *   11 QKV fused with attention   12 QKV with the LayerNorm-1 fold   13 QKV plain
- *   14 attention 256 tokens   15 chunked (k 256 tokens)   17 64 tokens   19 masked (any other count)   (16, 18 unused: no square token grid has 128 / 32 tokens)
+ *   14 attention 256 tokens   15 chunked (k 256 tokens)   17 64 tokens   19 masked (any other count)   (18 unused: no square token grid has 32 tokens)
+ *   16 out_proj folded into the last block's down projection (tail_fold_kernel; set together with the tail_mfma<NT> bit of its patch-feature tiles)
  *   20-23 cross_row_mfma<1..4>   24 ... with one 16-row group per workgroup   25 ... with more   26 cross_row VALU   27 the x_in fan-out (layer-0 sharing)
  *   28 up-projection fused with the depthwise conv, 16 x 16   29 ... 32 x 32 plus the seam kernel   30 ... 16 x 16, the 4-wave small-launch form
  *   31 up-projection alone   32 depthwise whole image   33 tiled   34 streaming
  *   35 down projection writing LayerNorm-1 partial sums   36 ... not writing them (last block, or no fold)   37 down projection, 8-wave kernel
  *   38 4-wave form, 64-row tiles   39 4-wave form, 128-row tiles   40 split-K x 4   41 split-K x 8   42 split-K 4-wave form
- *   43 split-K finisher <12> (d 768)   44 <6> (d 384)   45-48 tail_mfma<1..4>   49 tail plain
+ *   43 split-K finisher <12> (d 768)   44 <6> (d 384)   45-48 tail_mfma<1..4>   49 tail plain (widths that are no multiple of 128, unfolded only)
  *   the sampler's step and start kernels, named by the entry that launched them: tld_sample 50 update; tld_sample_from 51 update_from without a mask
  *   52 update_from with a mask   53 start_mix
  *   writers of the MX-fp8 A operand (with bit 10): 54 separate quantisation pass   55 cross_row_mfma writing e4m3   56 depthwise tiled writing e4m3

@@ -307,7 +307,7 @@ inline int device_cu_count() {
 enum : int {
     EP_EMBED_PLAIN = 0, EP_EMBED_MFMA = 1 /* +0..3: TPW 2, 4, 6, 8 */, EP_LN_Q4 = 5 /* +0..3: q4<1..4> */, EP_LN_GENERIC = 9, EP_LN_MX8 = 10,
     EP_QKV_ATTN = 11, EP_QKV_LN = 12, EP_QKV_PLAIN = 13,
-    EP_ATT_256 = 14, EP_ATT_CHUNKED = 15, EP_ATT_64 = 17 /* 16, 18: unused (128 / 32 tokens: no square grid) */, EP_ATT_MASKED = 19,
+    EP_ATT_256 = 14, EP_ATT_CHUNKED = 15, EP_ATT_64 = 17 /* 18: unused (32 tokens: no square grid); 16: EP_TAIL_FOLD below */, EP_ATT_MASKED = 19,
     EP_CROSS_MFMA = 20 /* +0..3: NQ 1..4 */, EP_CROSS_GPW1 = 24, EP_CROSS_GPWN = 25, EP_CROSS_VALU = 26, EP_CROSS_FANOUT = 27,
     EP_UP_FUSED16 = 28, EP_UP_FUSED32_SEAM = 29, EP_UP_FUSED16_SMALL = 30, EP_UP_PLAIN = 31, EP_DW_WHOLE = 32, EP_DW_TILED = 33, EP_DW_STREAM = 34,
     EP_DOWN_STATS = 35, EP_DOWN_NOSTATS = 36, EP_DOWN_MAIN = 37, EP_DOWN_SMALL64 = 38, EP_DOWN_SMALL128 = 39,
@@ -317,6 +317,8 @@ enum : int {
     EP_QUANT_MX8 = 54, EP_CROSS_F8 = 55, EP_DW_TILED_F8 = 56, EP_DW_STREAM_F8 = 57,
     // tld_sample_requests
     EP_UPDATE_REQ = 58, EP_UPDATE_REQ_MASK = 59, EP_START_MIX_REQ = 60,
+    // out_proj folded into the last block's down projection (bit 16 was unused): set next to the EP_TAIL_MFMA bit of the launch's patch-feature tiles
+    EP_TAIL_FOLD = 16,
     EP_COUNT = 61
 };
 extern thread_local uint64_t* g_path_sink;
@@ -415,8 +417,18 @@ struct TailParams {
     const float* b;               // [pd]
     float* out;                   // [B,C,S,S] fp32
     int batch, C, S, p, grid, pd, d, ntok;
+    // folded form (hid non-null; bf16 residual stream): tok is the residual row BEFORE the last block's down projection and
+    // out = [tok | hid] . [Wout | Wout Wd]^T + (Wout bd + bo)  (tld_tail_fold_math.h); w / w_hl / b are not read
+    const bf16* hid;              // [B*N, hidn] the last block's hidden rows
+    const bf16* wf_hl;            // [2][pdp][d + hidn] split bf16 image of [Wout | Wout Wd], pdp = pd rounded up to 16 (pad rows zero)
+    const float* bf;              // [pd]
+    int hidn;
 };
 void launch_tail(const TailParams& p, hipStream_t s);
+#ifdef TLD_RESID_BF16
+// stage hook only: row [M, d] fp32 <- x + row + bias per element (the unrounded residual row the folded tail stands for)
+void launch_tail_fold_debug_row(float* row, const resid_t* x, const float* bias, int M, int d, hipStream_t s);
+#endif
 
 // sampler elementwise: CFG combine + multistep update (see schedule.py).  One kernel serves tld_sample, tld_sample_from and
 // tld_sample_requests: what differs per sample is read from a device table, one row per (step, request), or one per step shared by every sample

@@ -8,6 +8,7 @@
 #include "tld_common.h"
 #include "tld_host.h"
 #include "tld_refresh.h"
+#include "tld_tail_fold_math.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -53,6 +54,9 @@ struct tld_engine : DeviceArena {      // (pad = 256: every allocation of this e
           *plin_b = nullptr, *pln2_w = nullptr, *pln2_b = nullptr, *pos = nullptr, *out_w = nullptr,
           *out_b = nullptr;
     bf16* out_w_hl = nullptr;           // out_proj weight as a split bf16 pair [2][pd][d] (tail_mfma_kernel)
+    bool fold_tail = true;              // TLD_FOLD_TAIL=0: the last block's down projection and out_proj stay two kernels (A/B testing)
+    bf16* out_fold_hl = nullptr;        // out_proj folded into the last block's down projection: [Wout | Wout Wd] as a split bf16 pair [2][pdp][d + hid] ...
+    float* out_fold_b = nullptr;        // ... and Wout bd + bo [pd] (tld_tail_fold_math.h; null: no fold in this engine's mode)
     bf16* plin_w_hl = nullptr;          // patch-embedding Linear weight as a split bf16 pair [2][d][pd] (embed_mfma_kernel)
     std::vector<Layer> layers;
     const float **tab_kv_w = nullptr, **tab_q_w = nullptr, **tab_n2_w = nullptr, **tab_n2_b = nullptr;   // [L] device tables
@@ -221,7 +225,8 @@ int reserve_snapshots(tld_engine* e) {
     for (const char* n : {"step.x_t", "step.x0_prev", "step.x0", "step.x_next"}) RES(n, B * e->img * 4);
     RES("step.out", B * e->img * 4);
     for (int l = 0; l < e->L; ++l) {
-        for (const char* n : {"x_in", "ca", "mlp"}) RES(blk_name(l, n), M * d * rs);
+        for (const char* n : {"x_in", "ca"}) RES(blk_name(l, n), M * d * rs);
+        RES(blk_name(l, "mlp"), M * d * ((l + 1 == e->L && e->out_fold_hl) ? 4 : rs));      // (the folded tail: the last block's row is an fp32 debug evaluation)
         RES(blk_name(l, "att"), M * d * 2); RES(blk_name(l, "sa"), M * d * 4);
         if (e->fold_ln1) RES(blk_name(l, "ln1"), M * kLnSlots * 8); else RES(blk_name(l, "xn1"), M * d * 2);
         if (!eng_fused_qa(e)) { RES(blk_name(l, "qk"), M * 2 * d * 2); RES(blk_name(l, "vt"), M * d * 2); }
@@ -467,7 +472,28 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
             }
         }
         if (!(fuse8 && e->grid > 16)) SNAP(blk_name(l, "hid"), e->hid2, ST_BF16, s, M, e->hid);      // (the quantising depthwise kernels write no bf16 copy)
-        if (e->low_latency && !e->fp8) {
+        // The last block, default class, bf16 operands: its down projection is folded into out_proj.  The 768-wide row
+        // x3 = x2 + hid2 Wd^T + bd is read by out_proj alone, so the tail below takes [x2 | hid2] against [Wout | Wout Wd] and the GEMM is not launched.
+        const bool fold_tail = l + 1 == e->L && e->out_fold_hl && !e->fp8 && !e->low_latency;
+#ifdef TLD_RESID_BF16
+        if (fold_tail && e->dbg_keep) {
+            // stage hook only: the row the folded tail stands for, unrounded, as an fp32 stage in the hook's own memory (like cross_row's sa dump: no
+            // product buffer is touched and no launch path is recorded) -- hid2 Wd^T by the fp32-output GEMM, then x2 and the bias per element
+            float* row = nullptr;
+            if (int rc = e->stages.sink(blk_name(l, "mlp"), M, d, &row)) return rc;
+            GemmParams g{};
+            g.A = e->hid2; g.lda = e->hid; g.W = Ly.down_w; g.ldw = e->hid; g.M = M; g.N = d; g.K = e->hid; g.c_f32 = row; g.ldc = d;
+            uint64_t* const sink = g_path_sink;
+            g_path_sink = nullptr;
+            const int rc = launch_gemm(g, EPI_F32, s);
+            g_path_sink = sink;
+            if (rc) { const std::string m = tld_last_error(); return fail(rc, "%s (debug row of the folded tail): %s", blk_name(l, "mlp").c_str(), m.c_str()); }
+            launch_tail_fold_debug_row(row, e->x, Ly.down_b, M, d, s);
+        }
+#endif
+        if (fold_tail) {
+            // (nothing here: launch_tail after the loop)
+        } else if (e->low_latency && !e->fp8) {
             // Low-latency class: a handful of samples are a handful of 256-row tiles, and the down projection's 48 K-steps per tile (K = 4 d) were
             // half of a layer's time however empty the chip was.  Four K-splits quadruple the work items (fp32 slices, summed in a fixed order by
             // the finishing kernel together with bias, residual add and the LayerNorm-1 partial sums).  Results differ from the default class in the
@@ -495,7 +521,7 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
             }
             GEMM_TRY(blk_name(l, "down projection"), launch_gemm(g, EPI_BIAS_RESID, s));
         }
-        SNAP(blk_name(l, "mlp"), e->x, rdt, s, M, d);
+        if (!fold_tail) SNAP(blk_name(l, "mlp"), e->x, rdt, s, M, d);
     }
     {
         ProfScope ps(e, KC_TAIL, s);
@@ -503,6 +529,9 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
         tp.tok = e->x; tp.w = e->out_w; tp.w_hl = e->out_w_hl; tp.b = e->out_b; tp.out = out; tp.batch = batch;
         tp.C = e->cfg.n_channels; tp.S = e->cfg.image_size; tp.p = e->cfg.patch_size; tp.grid = e->grid;
         tp.pd = e->pd; tp.d = d; tp.ntok = e->ntok;
+        if (e->out_fold_hl && !e->fp8 && !e->low_latency) {      // (= fold_tail of the last block: e->x is x2, the row before the down projection)
+            tp.hid = e->hid2; tp.hidn = e->hid; tp.wf_hl = e->out_fold_hl; tp.bf = e->out_fold_b;
+        }
         launch_tail(tp, s);
     }
     SNAP("out", out, ST_F32, s, batch, e->img);
@@ -749,7 +778,9 @@ int tld_engine_create(const tld_config* c, tld_engine** out) {
     if (const char* f8 = getenv("TLD_FP8_FUSED")) e->fp8_fused = atoi(f8) != 0;
     if (const char* fl = getenv("TLD_FOLD_LN3")) e->fold_ln3 = atoi(fl) != 0;
     if (const char* fl = getenv("TLD_FOLD_LN1")) e->fold_ln1 = atoi(fl) != 0;
+    if (const char* ft = getenv("TLD_FOLD_TAIL")) e->fold_tail = atoi(ft) != 0;
 #ifndef TLD_RESID_BF16
+    e->fold_tail = false;              // the folded tail reads the bf16 residual row as an MFMA operand
     e->fold_ln3 = false;               // the folds feed the bf16 residual stream straight to the MFMA
     e->fold_ln1 = false;
 #endif
@@ -1002,6 +1033,30 @@ int tld_engine_finalize_weights(tld_engine* e) {
         }
 #undef LK
     }
+    if (e->fold_tail && !e->fp8) {   // out_proj folded into the last block's down projection (tld_tail_fold_math.h; the refresh kernel computes the same bits)
+        snprintf(key, sizeof(key), "denoiser_trans_block.decoder_blocks.%d.mlp.mlp.3.weight", e->L - 1);
+        const std::vector<float>& Wd = e->host[key].data;                                                   // [d][hid]
+        snprintf(key, sizeof(key), "denoiser_trans_block.decoder_blocks.%d.mlp.mlp.3.bias", e->L - 1);
+        const std::vector<float>& bd = e->host[key].data;
+        const std::vector<float>& Wo = e->host["denoiser_trans_block.out_proj.0.weight"].data;              // [pd][d]
+        const std::vector<float>& bo = e->host["denoiser_trans_block.out_proj.0.bias"].data;
+        const int64_t pdp = tail_fold_padded_rows((int)pd), K = d + hid;
+        std::vector<uint16_t> img((size_t)(2 * pdp * K), 0);
+        std::vector<float> wf((size_t)hid), bf((size_t)pd);
+        std::vector<double> acc((size_t)hid);
+        for (int64_t f = 0; f < pd; ++f) {
+            const float* wo = &Wo[(size_t)(f * d)];
+            tail_fold_weight_row(wo, Wd.data(), (int)d, (int)hid, acc.data(), wf.data());
+            bf[(size_t)f] = tail_fold_bias(wo, bd.data(), bo[(size_t)f], (int)d);
+            for (int64_t k2 = 0; k2 < K; ++k2)
+                tail_fold_split(k2 < d ? wo[k2] : wf[(size_t)(k2 - d)], &img[(size_t)(f * K + k2)], &img[(size_t)((pdp + f) * K + k2)]);
+        }
+        if (int rc = dev_alloc(e, &e->out_fold_hl, img.size())) return rc;
+        if (int rc = dev_alloc(e, &e->out_fold_b, bf.size())) return rc;
+        HIP_TRY(hipMemcpy(e->out_fold_hl, img.data(), img.size() * 2, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(e->out_fold_b, bf.data(), bf.size() * 4, hipMemcpyHostToDevice));
+        e->weight_bytes += (int64_t)img.size() * 2 + (int64_t)bf.size() * 4;
+    }
     e->host.clear();
     {   // per-layer pointer tables for the layer-batched conditioning launches
         const size_t L = (size_t)e->L;
@@ -1034,6 +1089,7 @@ int tld_engine_finalize_weights(tld_engine* e) {
         job(e->out_w_hl, pl.outw, pd * d, RJ_SPLIT_HL); job(e->plin_w_hl, pl.liw, d * pd, RJ_SPLIT_HL);
         job(e->plin_wt, pl.liw, d * pd, RJ_TRANSPOSE, (int)pd);
         static_assert(kRefreshMaxJobs >= 21, "the images outside the blocks");
+        R.tail_fold_hl = e->out_fold_hl; R.tail_fold_b = e->out_fold_b; R.outw = pl.outw; R.outb = pl.outb; R.pd = e->pd;
     }
 
     const size_t B2 = (size_t)e->cfg.max_batch, M = B2 * e->ntok;

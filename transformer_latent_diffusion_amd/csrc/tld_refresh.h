@@ -40,6 +40,11 @@ struct RefreshPlan {
     bool fold = false, fp8 = false;          // any block holds a folded image / the e4m3 images (all blocks of an engine are alike)
     RefreshJob jobs[kRefreshMaxJobs];
     int njobs = 0;
+    // out_proj folded into the last block's down projection (tld_tail_fold_math.h); tail_fold_hl null: the engine holds no folded operand
+    bf16* tail_fold_hl = nullptr;            // [2][pdp][d + hid] split bf16 image of [Wout | Wout Wd]
+    float* tail_fold_b = nullptr;            // [pd] Wout bd + bo
+    int64_t outw = 0, outb = 0;              // out_proj weight [pd][d] and bias [pd] in the flat vector
+    int pd = 0;
 };
 
 // every weight image of the plan from `flat` (fp32, device), enqueued on s: kernels only, no allocation, no synchronisation

@@ -7,12 +7,13 @@
 //   * the two double-precision sums of a LayerNorm fold are taken per output row in the host's order, k = 0 .. d - 1, one add per element: one lane
 //     walks one row (refresh_fold_kernel).  A tree would change the last bit of float(sum) once in some tens of millions of elements;
 //   * contraction is off in every kernel here (a product of two fp32 values is exact in double, so it could not change the sums; pinned anyway).
-// Four launches per refresh: the images outside the blocks, the blocks' elementwise images, the folds, the e4m3 images; the blocks sit a constant
+// Up to five launches per refresh: the images outside the blocks, the blocks' elementwise images, the folds, the folded out_proj operand, the e4m3 images; the blocks sit a constant
 // stride apart in the flat vector, so the last three take the block index from blockIdx.z.  All stores are ordinary vector stores.
 #include "tld_common.h"
 #include "tld_stages.h"      // fail
 #include "tld_refresh.h"
 #include "tld_refresh_math.h"
+#include "tld_tail_fold_math.h"
 
 namespace tld {
 
@@ -186,6 +187,33 @@ __global__ __launch_bounds__(64) void refresh_fold_kernel(const Layer* __restric
     if (wp) { Ly.qkv_c1p[packed_row(lane)] = c1; Ly.qkv_b1p[packed_row(lane)] = b1; }      // (the 64 pad entries behind them are not touched)
 }
 
+// ---- out_proj folded into the last block's down projection: the split bf16 image of [Wout | Wout Wd] and b' = Wout bd + bo -----------------------
+// One thread per element, each walking its own sum in the host's order (tld_tail_fold_math.h is the one spelling of both).  Consecutive threads take
+// consecutive columns j, so the reads of Wd[k][j] are coalesced and Wout[f][k] is a broadcast.  Items: pd hid folded weights | pd d copies of Wout | pd biases.
+__global__ __launch_bounds__(256) void refresh_tail_fold_kernel(bf16* __restrict__ img_, float* __restrict__ bias, const float* __restrict__ wout,
+                                                                const float* __restrict__ bo, const float* __restrict__ wd, const float* __restrict__ bd,
+                                                                int pd, int d, int hid) {
+#pragma clang fp contract(off)
+    uint16_t* img = reinterpret_cast<uint16_t*>(img_);
+    const int K = d + hid;
+    const int64_t lo = (int64_t)tail_fold_padded_rows(pd) * K;
+    const int64_t nf = (int64_t)pd * hid, nw = (int64_t)pd * d;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < nf + nw) {
+        int f, k;
+        float w;
+        if (i < nf) { f = (int)(i / hid); const int j = (int)(i - (int64_t)f * hid); k = d + j; w = tail_fold_weight(wout + (int64_t)f * d, wd, d, hid, j); }
+        else { const int64_t r = i - nf; f = (int)(r / d); k = (int)(r - (int64_t)f * d); w = wout[r]; }
+        uint16_t h, l;
+        tail_fold_split(w, &h, &l);
+        img[(int64_t)f * K + k] = h;
+        img[lo + (int64_t)f * K + k] = l;
+    } else if (i < nf + nw + pd) {
+        const int f = (int)(i - nf - nw);
+        bias[f] = tail_fold_bias(wout + (int64_t)f * d, bd, bo[f], d);
+    }
+}
+
 // ---- MX-fp8 from fp32 (quant_mx8_host, tld_quant.hip): per row and block of 32 K-elements X = 2^(floor(log2 amax) - 8), q = e4m3_rne(clamp(v / X)) ----
 // a thread owns 8 consecutive elements, four adjacent lanes one block (K % 32 == 0: a quad never straddles two rows, and the group count is a multiple of 4,
 // so a quad is whole or absent)
@@ -252,6 +280,12 @@ int launch_refresh_weights(const RefreshPlan& p, const float* flat, hipStream_t 
     if (p.fold) {
         const int rows = p.hid > 3 * p.d ? p.hid : 3 * p.d;
         hipLaunchKernelGGL(refresh_fold_kernel, dim3((unsigned)(rows / 64), 2, (unsigned)p.L), dim3(64), 0, s, p.layers_dev, flat, p.l0, p.layer_stride, p.d, p.hid);
+    }
+    if (p.tail_fold_hl) {
+        const float* last = flat + (int64_t)(p.L - 1) * p.layer_stride;
+        const int64_t items = (int64_t)p.pd * (p.hid + p.d + 1);
+        hipLaunchKernelGGL(refresh_tail_fold_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p.tail_fold_hl, p.tail_fold_b, flat + p.outw, flat + p.outb,
+                           last + p.l0.down_w, last + p.l0.down_b, p.pd, p.d, p.hid);
     }
     if (p.fp8) hipLaunchKernelGGL(refresh_fp8_kernel, dim3(64, 3, (unsigned)p.L), dim3(256), 0, s, p.layers_dev, flat, p.l0, p.layer_stride, p.d, p.hid);
     const hipError_t e = hipGetLastError();

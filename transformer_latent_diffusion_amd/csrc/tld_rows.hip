@@ -1013,6 +1013,130 @@ __global__ __launch_bounds__(256) void tail_mfma_kernel(TailParams p, const bf16
             }
         }
 }
+
+// ------------------------------------------------------------------------------------------------
+// The folded tail: out_proj applied to the last block's down projection without the 768-wide row in between,
+//   out[row][f] = [x2 | hid2][row] . [Wout | W'][f]^T + b'[f],   W' = Wout Wd, b' = Wout bd + bo  (tld_tail_fold_math.h),
+// one skinny product over K = d + hid per token row, bound by the hid2 rows it streams from HBM.  Same MFMA roles as tail_mfma_kernel (weights = A,
+// 16 token rows = B, split bf16 weights hi + lo, fp32 accumulation, the same pixel-shuffle store), but:
+//   * K does not fit LDS as a split pair, so a lane takes its weight fragments from L2 into registers, and one fragment serves the RT 16-row tiles
+//     of the workgroup: weight bytes per workgroup = 2 pdp / (16 RT) of the activation bytes;
+//   * the K-blocks of 32 are dealt to the workgroup's 8 waves in contiguous runs of ceil(nkb / 8) and the 8 partial sums meet in LDS in the fixed
+//     order ((0 + 1) + (2 + 3)) + ((4 + 5) + (6 + 7)): the summation order is a function of d and hid alone, never of the batch or of RT -- a row's
+//     result is the same bits in every launch.  Each wave runs RT x NT independent accumulator chains.
+// RT follows the launch size (launch_tail): 1 for small launches -- one image, 256 rows, is 16 workgroups of 8 short chains.
+template <int NT, int RT>
+__global__ __launch_bounds__(512) void tail_fold_kernel(TailParams p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];       // [8 waves][RT x NT][64 lanes] f32x4
+    f32x4* red = reinterpret_cast<f32x4*>(smem);
+    const int d = p.d, K = d + p.hidn, pdp = NT * 16;
+    // (wid through readfirstlane: the K-block guards below must be SCALAR branches -- as lane predicates the compiler drops the branch, and an MFMA does not
+    // honour EXEC: the guarded product would be accumulated anyway)
+    const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int tok = lane & 15, kq = lane >> 4;
+    const int total = p.batch * p.ntok;
+    const int row0 = blockIdx.x * (RT * 16);
+    const int nkb = K >> 5, dkb = d >> 5;                             // d % 64 == 0: a K-block lies in x2 or in hid2, never across
+    const int per = (nkb + 7) >> 3;
+    const int kb_lo = wid * per, kb_hi = kb_lo + per < nkb ? kb_lo + per : nkb;
+    unsigned xoff[RT], hoff[RT];                                      // element offsets of this lane's rows (M hid 2 < 4 GiB: tld_engine_create)
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+        const int r = row0 + rt * 16 + tok;
+        const unsigned row = (unsigned)(r < total ? r : total - 1);
+        xoff[rt] = row * (unsigned)d + kq * 8; hoff[rt] = row * (unsigned)p.hidn + kq * 8;
+    }
+    const bf16* wbase = p.wf_hl + (size_t)tok * K + kq * 8;
+    const size_t lo_plane = (size_t)pdp * K;
+    f32x4 acc[RT][NT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) acc[rt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // Two register buffers of G K-blocks each: the loads of one group are all in flight while the other group's MFMAs run.  The loads are unconditional
+    // (past the wave's run they repeat a valid address and the value is dropped), only the MFMAs are guarded, by a wave-uniform branch: the loop has no
+    // load behind a condition, which keeps the waits counted.  G from the registers a lane can spare: the small-launch forms (RT 1) run few waves per CU
+    // and need the deeper prefetch, the large-launch forms hide latency by occupancy (two workgroups per CU at <= 128 registers).
+    constexpr int G = RT == 1 ? (NT == 1 ? 4 : NT == 2 ? 2 : 1) : 1;
+    bf16x8 xa[2][G][RT], wh[2][G][NT], wl[2][G][NT];
+    auto fetch = [&](int buf, int kb0) {
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            int kb = kb0 + g;
+            kb = kb < nkb ? kb : nkb - 1;
+            const bool in_x = kb < dkb;                               // wave-uniform
+            const int ko = (in_x ? kb : kb - dkb) * 32;
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt)
+                xa[buf][g][rt] = *reinterpret_cast<const bf16x8*>(in_x ? p.tok + xoff[rt] + ko : p.hid + hoff[rt] + ko);
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const bf16* w = wbase + (size_t)t * 16 * K + kb * 32;
+                wh[buf][g][t] = *reinterpret_cast<const bf16x8*>(w);
+                wl[buf][g][t] = *reinterpret_cast<const bf16x8*>(w + lo_plane);
+            }
+        }
+    };
+    auto mma = [&](int buf, int kb0) {                                // K-blocks in ascending order, hi then lo: the one summation order of a chain
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            if (kb0 + g < kb_hi) {
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) acc[rt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[buf][g][t], xa[buf][g][rt], acc[rt][t], 0, 0, 0);
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) acc[rt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[buf][g][t], xa[buf][g][rt], acc[rt][t], 0, 0, 0);
+            }
+        }
+    };
+    fetch(0, kb_lo);
+    for (int kb0 = kb_lo; kb0 < kb_hi; kb0 += 2 * G) {
+        fetch(1, kb0 + G);
+        __builtin_amdgcn_sched_barrier(0);                            // (the loads stay ahead of the other buffer's MFMAs: sunk behind them they wait uncounted)
+        mma(0, kb0);
+        __builtin_amdgcn_sched_barrier(0);
+        fetch(0, kb0 + 2 * G);
+        __builtin_amdgcn_sched_barrier(0);
+        mma(1, kb0 + G);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) red[(wid * (RT * NT) + rt * NT + t) * 64 + lane] = acc[rt][t];
+    __syncthreads();
+    const int pp = p.p * p.p;
+    for (int it = wid; it < RT * NT; it += 8) {
+        const int rt = it / NT, t = it - rt * NT;
+        f32x4 s[8];
+#pragma unroll
+        for (int w = 0; w < 8; ++w) s[w] = red[(w * (RT * NT) + it) * 64 + lane];
+        const f32x4 sum = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
+        const int row = row0 + rt * 16 + tok;
+        if (row >= total) continue;
+        const int b = row / p.ntok, tk = row - b * p.ntok;
+        const int ti = tk / p.grid, tj = tk - ti * p.grid;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int f = t * 16 + 4 * kq + r;              // feature f = (c, u, v) of token (ti, tj) -> out[b, c, ti*p+u, tj*p+v]
+            if (f < p.pd) {
+                const int c = f / pp, uv = f - c * pp;
+                const int u = uv / p.p, vv = uv - u * p.p;
+                p.out[(((size_t)b * p.C + c) * p.S + (ti * p.p + u)) * p.S + (tj * p.p + vv)] = sum[r] + p.bf[f];
+            }
+        }
+    }
+}
+
+// debug stage of the folded tail's input row (stage hook only, never on the product path): row[i][c] = x2[i][c] + row[i][c] + bias[c], row holding
+// hid2 Wd^T in fp32 (an EPI_F32 GEMM) on entry -- the unrounded residual row the folded tail's result stands for
+__global__ __launch_bounds__(256) void tail_fold_debug_row_kernel(float* __restrict__ row, const bf16* __restrict__ x, const float* __restrict__ bias, int64_t n, int d) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) row[i] = ((float)x[i] + row[i]) + bias[(int)(i % d)];
+}
 #endif
 
 // ------------------------------------------------------------------------------------------------
@@ -1487,6 +1611,22 @@ void launch_splitk_resid(const float* parts, int nsplit, size_t slice_stride, co
 
 void launch_tail(const TailParams& p, hipStream_t s) {
 #ifdef TLD_RESID_BF16
+    if (p.hid) {      // folded form: tok = x2, hid = hid2 of the last block (any d, any hid: both are multiples of 64)
+        const int nt = (p.pd + 15) / 16, rows = p.batch * p.ntok;
+        // row tiles per workgroup: as many as keep a fragment's re-use high while every CU still has a workgroup; LDS 8 RT NT KiB <= 64 KiB
+        const int big = nt <= 2 ? 4 : 2;
+        const int rt = rows >= 16 * big * device_cu_count() ? big : 1;
+        const int lds = 8 * rt * nt * 1024;
+        dim3 grid((unsigned)((rows + 16 * rt - 1) / (16 * rt)));
+#define TLD_TF(NT, RT) hipLaunchKernelGGL((tail_fold_kernel<NT, RT>), grid, dim3(512), lds, s, p)
+        note_path(EP_TAIL_MFMA + nt - 1); note_path(EP_TAIL_FOLD);
+        if (nt == 1) { if (rt == 1) TLD_TF(1, 1); else TLD_TF(1, 4); }
+        else if (nt == 2) { if (rt == 1) TLD_TF(2, 1); else TLD_TF(2, 4); }
+        else if (nt == 3) { if (rt == 1) TLD_TF(3, 1); else TLD_TF(3, 2); }
+        else { if (rt == 1) TLD_TF(4, 1); else TLD_TF(4, 2); }
+#undef TLD_TF
+        return;
+    }
     if (p.w_hl && p.d % 128 == 0 && (long)p.pd * p.d <= 40960) {      // matrix-pipe form: split-bf16 weights [2][pd][d] in <= 160 KiB of LDS (the XOR swizzle of its
                                                                       // weight image permutes 16-byte chunks within aligned groups of 16: rows of d / 8 = 16 k chunks)
         const int nt = (p.pd + 15) / 16, rows = p.batch * p.ntok;
@@ -1505,6 +1645,13 @@ void launch_tail(const TailParams& p, hipStream_t s) {
     note_path(EP_TAIL_PLAIN);
     TLD_DISPATCH_D(p.d, { TLD_LDS_OPT_IN((tail_kernel<NJ, HALF>), lds); hipLaunchKernelGGL((tail_kernel<NJ, HALF>), dim3((rows + rpb - 1) / rpb), dim3(256), lds, s, p, rpb); });
 }
+
+#ifdef TLD_RESID_BF16
+void launch_tail_fold_debug_row(float* row, const resid_t* x, const float* bias, int M, int d, hipStream_t s) {
+    const int64_t n = (int64_t)M * d;
+    hipLaunchKernelGGL(tail_fold_debug_row_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, row, x, bias, n, d);
+}
+#endif
 
 namespace {
 bool aligned16(const void* a) { return (reinterpret_cast<uintptr_t>(a) & 15) == 0; }

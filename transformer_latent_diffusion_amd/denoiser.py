@@ -470,14 +470,16 @@ class Denoiser:
             init_latents=init_latents, mask=mask, neg_labels=neg, order=order, new_trace=torch.zeros)
 
     # ---- test / bench hooks -----------------------------------------------------------------------------
-    # launch paths of tld_engine_debug_paths, by bit number (include/tld_hip.h; None: unused bit)
+    # launch paths of tld_engine_debug_paths, by bit number (include/tld_hip.h; None: a bit no default engine sets).  "tail folded" (out_proj folded into
+    # the last block's down projection) comes with the tail_mfma<NT> bit of its patch-feature tiles.  Bit 49, the VALU tail of widths that are no multiple
+    # of 128, is set only with TLD_FOLD_TAIL=0 since the fold (tests/test_gpu_tail_fold.py holds it there): the folded tail takes every width.
     PATH_NAMES = ("embed plain", "embed_mfma<2>", "embed_mfma<4>", "embed_mfma<6>", "embed_mfma<8>", "layernorm q4<1>", "layernorm q4<2>", "layernorm q4<3>",
                   "layernorm q4<4>", "layernorm generic", "layernorm mx8", "QKV fused with attention", "QKV LayerNorm-1 fold", "QKV plain", "attention 256",
-                  "attention chunked", None, "attention 64", None, "attention masked", "cross_row_mfma<1>", "cross_row_mfma<2>",
+                  "attention chunked", "tail folded", "attention 64", None, "attention masked", "cross_row_mfma<1>", "cross_row_mfma<2>",
                   "cross_row_mfma<3>", "cross_row_mfma<4>", "cross_row gpw 1", "cross_row gpw > 1", "cross_row VALU", "cross_row x_in fan-out",
                   "up fused 16", "up fused 32 + seam", "up fused 16 4-wave", "up alone", "depthwise whole image", "depthwise tiled", "depthwise streaming",
                   "down with stats_out", "down without stats_out", "down 8-wave", "down 4-wave 64", "down 4-wave 128", "split-K x4", "split-K x8",
-                  "split-K 4-wave", "split-K finisher<12>", "split-K finisher<6>", "tail_mfma<1>", "tail_mfma<2>", "tail_mfma<3>", "tail_mfma<4>", "tail plain",
+                  "split-K 4-wave", "split-K finisher<12>", "split-K finisher<6>", "tail_mfma<1>", "tail_mfma<2>", "tail_mfma<3>", "tail_mfma<4>", None,
                   "update", "update_from", "update_from masked", "start_mix")
     # the writers of the MX-fp8 A operand, by bit number (bit 10 is in PATH_NAMES too): held by tests/test_gpu_fp8_stages.py
     FP8_PATH_NAMES = {10: "layernorm mx8", 54: "fp8 separate quantisation pass", 55: "fp8 cross_row writer", 56: "fp8 depthwise tiled",
