@@ -524,6 +524,52 @@ TLD_API int tld_clip_read_stage(tld_clip* c, const char* name, float* host_out, 
 TLD_API int64_t tld_clip_weight_bytes(const tld_clip* c);
 TLD_API int tld_clip_destroy(tld_clip* c);
 
+/* ---- CLIP image tower: image embeddings in the labels' joint space ------------------------------------------------
+ * Restated: VisionTransformer.forward of openai/CLIP clip/model.py, what `model.encode_image(preprocess(img))` runs: conv1 (patch x patch,
+ * stride patch, no bias), class token + positional embedding, ln_pre, pre-LN residual blocks with unmasked nn.MultiheadAttention and a
+ * QuickGELU MLP, ln_post of the class token's row times proj.  Resizing, cropping and normalising the picture stay in Python (clip_preprocess).
+ * Limits, checked by tld_clip_vis_create before any HIP call (TLD_ERR_INVALID, the reason in tld_last_error()):
+ *   width a multiple of 64 in 64..1024;  heads * 64 == width;  layers 1..64;  patch_size 1..32;  image_size a positive multiple of patch_size;
+ *   g = image_size / patch_size in 1..16, i.e. at most 257 tokens (the 336 px towers, 577 tokens, are out of scope);  embed_dim, max_batch >= 1. */
+typedef struct tld_clip_vis tld_clip_vis;
+
+typedef struct tld_clip_vis_config {
+    int32_t image_size;         /* 224: input_resolution */
+    int32_t patch_size;         /* 14 */
+    int32_t width;              /* 1024: vision_width, multiple of 64 */
+    int32_t heads;              /* width / 64 */
+    int32_t layers;             /* 24 */
+    int32_t embed_dim;          /* 768: columns of visual.proj */
+    int32_t max_batch;
+    int32_t device_id;
+} tld_clip_vis_config;
+
+TLD_API int tld_clip_vis_create(const tld_clip_vis_config* cfg, tld_clip_vis** out);
+/* CLIP.state_dict() entries, one at a time (host fp32): "visual.class_embedding" [W], "visual.positional_embedding" [g*g + 1, W], "visual.proj" [W, E],
+ * "visual.conv1.weight" [W, 3, p, p], "visual.ln_pre.*", "visual.ln_post.*", "visual.transformer.resblocks.<i>.{ln_1,ln_2}.*",
+ * ".attn.in_proj_{weight,bias}", ".attn.out_proj.*", ".mlp.c_fc.*", ".mlp.c_proj.*".  The text side of the archive, "logit_scale" and the
+ * metadata entries are accepted and ignored. */
+TLD_API int tld_clip_vis_load_tensor(tld_clip_vis* c, const char* key, const void* host_ptr, const int64_t* shape, int32_t ndim, int32_t dtype);
+TLD_API int tld_clip_vis_finalize_weights(tld_clip_vis* c);
+/* VisionTransformer.forward(pixels):  pixels [batch, 3, image_size, image_size] (device; io_dtype TLD_DTYPE_F32 / BF16 / F16), already normalised;
+ * out [batch, embed_dim] fp32 (device).  Launches only: allocates nothing, does not synchronise. */
+TLD_API int tld_clip_vis_encode_image(tld_clip_vis* c, const void* pixels, float* out, int32_t batch, int32_t io_dtype, void* hip_stream);
+/* The image tower's stages (the stage hook above): the contract of tld_clip_set_debug -- every workspace buffer of all max_batch images
+ * is filled with 0xFF bytes first, a capturing stream is refused (TLD_ERR_STATE), nothing is launched or allocated with the hook off and the output keeps
+ * its bits.  Stages of the LAST encode_image call (P = batch * g*g patch rows, T = batch * (g*g + 1) token rows, Kp = 3 p*p rounded up to a multiple of 64):
+ *   patches [P, Kp] bf16 (im2col rows, zero beyond 3 p*p), emb [P, W] fp32 (conv1), x0 [T, W] fp32 (after ln_pre);
+ *   blk<i>.{h1, qkv, att, attn_out, x1, h2, f_pre, f, mlp_out, x2} as in the text tower (x2 absent for the last block);
+ *   pooled [batch, W] fp32 (ln_post of the class rows), out [batch, E] fp32;
+ *   operands as held, from finalize_weights on: conv_w [W, Kp] bf16, blk<i>.in_w / out_w / fc_w / proj_w (bf16), proj_t [E, W] fp32. */
+TLD_API int tld_clip_vis_set_debug(tld_clip_vis* c, int32_t enable);
+TLD_API int tld_clip_vis_read_stage(tld_clip_vis* c, const char* name, float* host_out, int64_t numel, int64_t* shape4);
+/* The image tower's attention kernel alone (no engine): qkv_bf16 [batch * n, 3 * 64 heads] bf16 device rows as the in_proj GEMM leaves them (q | k | v,
+ * head h at columns h * 64), out_bf16 [batch * n, 64 heads] bf16; unmasked softmax(q k^T / 8) v per (sample, head).  Reads rows 0 .. batch n - 1 of qkv and
+ * stores rows 0 .. batch n - 1 of out, nothing else.  TLD_ERR_INVALID before any HIP call: a NULL pointer, batch < 1, n outside 2..257, heads outside 1..16. */
+TLD_API int tld_debug_clip_vis_attention(const void* qkv_bf16, void* out_bf16, int32_t batch, int32_t n, int32_t heads, void* hip_stream);
+TLD_API int64_t tld_clip_vis_weight_bytes(const tld_clip_vis* c);
+TLD_API int tld_clip_vis_destroy(tld_clip_vis* c);
+
 TLD_API const char* tld_last_error(void);
 
 /* ---- Training step: tld/train.py:162-173 for one batch on one device -------------------------------------------

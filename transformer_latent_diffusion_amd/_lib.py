@@ -35,6 +35,8 @@ ABI_SYMBOLS = (
     "tld_debug_conv3x3_s2",
     "tld_clip_create", "tld_clip_load_tensor", "tld_clip_finalize_weights", "tld_clip_encode_text", "tld_clip_set_debug", "tld_clip_read_stage", "tld_clip_weight_bytes",
     "tld_clip_destroy",
+    "tld_clip_vis_create", "tld_clip_vis_load_tensor", "tld_clip_vis_finalize_weights", "tld_clip_vis_encode_image", "tld_clip_vis_set_debug", "tld_clip_vis_read_stage",
+    "tld_clip_vis_weight_bytes", "tld_clip_vis_destroy", "tld_debug_clip_vis_attention",
     "tld_train_create", "tld_train_param_count", "tld_train_tensor_count", "tld_train_param_layout", "tld_train_set_angular_speeds", "tld_train_bind",
     "tld_train_refresh_weights", "tld_train_forward_backward", "tld_train_forward_backward_cb", "tld_train_adam_ema", "tld_train_grad_guard", "tld_train_adam_ema_guarded", "tld_train_prepare_batch", "tld_train_prepare_batch_at",
     "tld_train_forward_loss", "tld_train_sample_loss", "tld_train_loss_buckets", "tld_debug_attention_bwd", "tld_debug_wgrad", "tld_debug_attention_fwd", "tld_debug_dwconv_gelu",
@@ -84,6 +86,10 @@ class TldBatchSource(C.Structure):
 class TldClipConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("vocab_size", "context_length", "width", "heads", "layers", "embed_dim", "max_batch",
                                          "device_id")]
+
+
+class TldClipVisConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("image_size", "patch_size", "width", "heads", "layers", "embed_dim", "max_batch", "device_id")]
 
 
 class TldGemmEpilogueArgs(C.Structure):
@@ -201,6 +207,17 @@ def lib() -> C.CDLL:
     L.tld_clip_weight_bytes.argtypes = [vp]
     L.tld_clip_weight_bytes.restype = C.c_int64
     L.tld_clip_destroy.argtypes = [vp]
+    if hasattr(L, "tld_clip_vis_create"):            # (absent from A/B builds that predate the image tower)
+        L.tld_clip_vis_create.argtypes = [C.POINTER(TldClipVisConfig), C.POINTER(vp)]
+        L.tld_clip_vis_load_tensor.argtypes = [vp, C.c_char_p, vp, i64p, i32, i32]
+        L.tld_clip_vis_finalize_weights.argtypes = [vp]
+        L.tld_clip_vis_encode_image.argtypes = [vp, vp, vp, i32, i32, vp]
+        L.tld_clip_vis_set_debug.argtypes = [vp, i32]
+        L.tld_clip_vis_read_stage.argtypes = [vp, C.c_char_p, C.POINTER(C.c_float), C.c_int64, i64p]
+        L.tld_clip_vis_weight_bytes.argtypes = [vp]
+        L.tld_clip_vis_weight_bytes.restype = C.c_int64
+        L.tld_clip_vis_destroy.argtypes = [vp]
+        L.tld_debug_clip_vis_attention.argtypes = [vp, vp, i32, i32, i32, vp]
     f32 = C.c_float
     L.tld_train_create.argtypes = [C.POINTER(TldConfig), C.POINTER(vp)]
     L.tld_train_param_count.argtypes = [vp]
@@ -237,7 +254,7 @@ def lib() -> C.CDLL:
     for name in ABI_SYMBOLS:
         if "TLD_LIB" in os.environ and not hasattr(L, name):     # an older A/B build: symbols added since are simply absent (tests/test_abi.py checks the real library)
             continue
-        if name not in ("tld_last_error", "tld_engine_weight_bytes", "tld_vae_weight_bytes", "tld_vae_enc_weight_bytes", "tld_clip_weight_bytes", "tld_train_param_count",
+        if name not in ("tld_last_error", "tld_engine_weight_bytes", "tld_vae_weight_bytes", "tld_vae_enc_weight_bytes", "tld_clip_weight_bytes", "tld_clip_vis_weight_bytes", "tld_train_param_count",
                         "tld_train_tensor_count", "tld_engine_param_count"):
             getattr(L, name).restype = C.c_int
     _lib = L

@@ -16,6 +16,7 @@
 #include "../../include/tld_hip.h"
 #include "tld_common.h"
 #include "tld_host.h"
+#include "tld_clip_kernels.h"      // clip_add_ln_kernel, clip_final_ln_kernel, clip_quickgelu_kernel, gemm: shared with tld_clip_vision.hip
 
 #include <cmath>
 #include <cstdarg>
@@ -41,60 +42,6 @@ __global__ void clip_embed_kernel(const int* __restrict__ tokens, const float* _
     int id = tokens[t];
     id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
     x[i] = tok_emb[(size_t)id * W + c] + pos[(size_t)(t % ctx) * W + c];
-}
-
-// One wave per row:  if add: x[row] += add[row] + bias (the residual add of the block that just finished);  out = bf16(LayerNorm(x[row])).
-// fp32 statistics, two passes over the row held in registers (W <= 64 * 16).
-__global__ __launch_bounds__(256) void clip_add_ln_kernel(float* __restrict__ x, const float* __restrict__ add, const float* __restrict__ bias,
-                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                          bf16* __restrict__ out, int T, int W) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= T) return;
-    float v[16];
-    const int n = W / 64;                          // elements per lane (W % 64 == 0, n <= 16)
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        if (j < n) {
-            const int c = j * 64 + lane;
-            float f = x[(size_t)row * W + c];
-            if (add) { f += add[(size_t)row * W + c] + bias[c]; x[(size_t)row * W + c] = f; }
-            v[j] = f; s += f;
-        }
-    }
-    const float mean = wave_sum(s) / (float)W;
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) if (j < n) { const float c = v[j] - mean; q = fmaf(c, c, q); }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)W + kLnEps);
-#pragma unroll
-    for (int j = 0; j < 16; ++j)
-        if (j < n) { const int c = j * 64 + lane; out[(size_t)row * W + c] = (bf16)((v[j] - mean) * rstd * gamma[c] + beta[c]); }
-}
-
-// The same for the B pooled rows only (row = b * ctx + eot[b]): residual add of the last block, ln_final, fp32 out [B, W]
-__global__ __launch_bounds__(64) void clip_final_ln_kernel(const float* __restrict__ x, const float* __restrict__ add, const float* __restrict__ bias,
-                                                           const int* __restrict__ eot, const float* __restrict__ gamma,
-                                                           const float* __restrict__ beta, float* __restrict__ out, int W, int ctx) {
-    const int b = blockIdx.x, lane = threadIdx.x;
-    int e = eot[b];
-    e = e < 0 ? 0 : (e >= ctx ? ctx - 1 : e);
-    const size_t row = (size_t)b * ctx + e;
-    float v[16];
-    const int n = W / 64;
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j)
-        if (j < n) { const int c = j * 64 + lane; v[j] = x[row * W + c] + add[row * W + c] + bias[c]; s += v[j]; }
-    const float mean = wave_sum(s) / (float)W;
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) if (j < n) { const float c = v[j] - mean; q = fmaf(c, c, q); }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)W + kLnEps);
-#pragma unroll
-    for (int j = 0; j < 16; ++j)
-        if (j < n) { const int c = j * 64 + lane; out[(size_t)b * W + c] = (v[j] - mean) * rstd * gamma[c] + beta[c]; }
 }
 
 // Causal multi-head attention, head_dim 64, ctx <= 128 tokens: one wave per (head, sample).  q | k | v are the bf16 rows of the
@@ -142,19 +89,6 @@ __global__ __launch_bounds__(64) void clip_attn_kernel(const bf16* __restrict__ 
     }
 }
 
-// QuickGELU in place: x * sigmoid(1.702 x)      (clip/model.py QuickGELU)
-__global__ void clip_quickgelu_kernel(bf16* __restrict__ f, long n8) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n8) return;
-    bf16x8 v = *reinterpret_cast<bf16x8*>(f + i * 8);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const float x = (float)v[e];
-        v[e] = (bf16)(x * __builtin_amdgcn_rcpf(1.0f + __expf(-1.702f * x)));
-    }
-    *reinterpret_cast<bf16x8*>(f + i * 8) = v;
-}
-
 struct Block {
     float *ln1_g = nullptr, *ln1_b = nullptr, *ln2_g = nullptr, *ln2_b = nullptr;
     bf16 *in_w = nullptr, *out_w = nullptr, *fc_w = nullptr, *proj_w = nullptr;
@@ -192,14 +126,6 @@ int need(const tld_clip* c, const std::string& key, const std::vector<int64_t>& 
     *out = &it->second;
     return TLD_OK;
 }
-int gemm(const bf16* A, int lda, const bf16* Wt, int M, int N, int K, int epi, const float* bias, bf16* out_bf16, float* out_f32, hipStream_t s) {
-    GemmParams p{};
-    p.A = A; p.lda = lda; p.W = Wt; p.ldw = K; p.M = M; p.N = N; p.K = K; p.bias = bias;
-    if (epi == EPI_BIAS_BF16) { p.out_bf16 = out_bf16; p.ldo = N; }
-    else { p.c_f32 = out_f32; p.ldc = N; }
-    return launch_gemm(p, epi, s);
-}
-
 // the GEMM operands as the engine holds them, logical [N][K], read in place: named once the weights exist, whether or not the hook is on
 void name_operands(tld_clip* c) {
     const int64_t W = c->W;

@@ -423,6 +423,21 @@ class DiffusionTransformer:
         return self._labels(prompts).cpu()
 
     @torch.no_grad()
+    def clip_scores(self, images, prompts) -> Tensor:
+        """CLIP score of each picture against its prompt: cosine of ``clip_model.encode_image(clip_preprocess(images))`` with the prompt's label.
+        ``images``: PIL images or a float tensor ``[B, 3, H, W]`` in [0, 1]; ``prompts``: one string per image.  Returns ``[B]`` fp32 on the device.
+        Needs a ``clip_model`` with an image tower (``Clip(text, visual)`` or what ``clip.load`` returns)."""
+        from .clip_image import clip_preprocess, clip_score
+        if self.clip_model is None or not hasattr(self.clip_model, "encode_image"):
+            raise RuntimeError("clip_scores needs a clip_model with encode_image (the image tower): pass clip_model=Clip(text=..., visual=...); "
+                               f"this pipeline holds {type(self.clip_model).__name__}")
+        prompts = [prompts] if isinstance(prompts, str) else list(prompts)
+        pixels = clip_preprocess(images, self.clip_model.visual.input_resolution).to(self.device)
+        if pixels.shape[0] != len(prompts):
+            raise ValueError(f"clip_scores: {pixels.shape[0]} images but {len(prompts)} prompts")
+        return clip_score(self.clip_model.encode_image(pixels).float(), self._labels(prompts).to(self.device).float())
+
+    @torch.no_grad()
     def generate_images_from_texts(self, prompts, class_guidance=6, seeds=11, n_iter=15, negative_prompts=None, guidance_interval=None):
         """Batched front edge (the reference serves one prompt per call, tld/app.py:48-65):
         one text-encoder call for all prompts, labels stay on the device, ONE sampler call (sample-sharded over the

@@ -857,6 +857,23 @@ class Trainer:
             return latents
         return latents, gen._decode(latents, 8)[0]
 
+    @torch.no_grad()
+    def eval_clip_score(self, labels: torch.Tensor, vae, clip_image, **eval_generate_kwargs):
+        """``eval_generate`` plus the CLIP score of every sample against the label it was generated from: the decoded images go from [-1, 1] to
+        [0, 1], through ``clip_preprocess`` and ``clip_image.encode_image`` (a ``ClipImageEncoder`` or a ``Clip``), and ``clip_score`` takes the cosine
+        with ``repeat_interleave(labels, 2, dim=0)[i]`` -- the labels are CLIP text embeddings, so no text tower runs.  Returns
+        ``(latents, images, scores)``; ``scores`` is a ``[num_imgs]`` fp32 tensor on the trainer's device and is not synchronised here.  Touches
+        nothing of the training step's state, like ``eval_generate``."""
+        from .clip_image import clip_preprocess, clip_score
+        if vae is None:
+            raise ValueError("eval_clip_score needs a vae: the score is taken on decoded images")
+        latents, images = self.eval_generate(labels, vae, **eval_generate_kwargs)
+        size = getattr(clip_image, "visual", clip_image).input_resolution
+        pixels = clip_preprocess((images.to(self.device, torch.float32) * 0.5 + 0.5).clamp(0.0, 1.0), size)
+        emb = clip_image.encode_image(pixels)
+        used = torch.repeat_interleave(labels, 2, dim=0)[:emb.shape[0]].to(self.device)
+        return latents, images, clip_score(emb, used)
+
     # ---- checkpoint / resume ----------------------------------------------------------------------------------------------------
     def optimizer_state_dict(self) -> Dict[str, object]:
         """``torch.optim.Adam(model.parameters(), lr).state_dict()`` as the reference saves it (tld/train.py:86,152): per-parameter
