@@ -65,8 +65,9 @@ TLD_API int tld_engine_create(const tld_config* cfg, tld_engine** out);
 TLD_API int tld_engine_load_tensor(tld_engine* e, const char* key, const void* host_ptr, const int64_t* shape,
                            int32_t ndim, int32_t dtype);
 
-/* Packs weights into device layouts (bf16 GEMM operands, folded tables).  Must follow the loads;
- * fails with TLD_ERR_STATE and names the first missing key if the state_dict was incomplete. */
+/* Builds the weight images on the device (bf16 GEMM operands, folded tables): the loaded tensors go up as one temporary fp32 vector and the kernels of
+ * tld_engine_refresh_weights fill the images.  Must follow the loads; fails with TLD_ERR_STATE and names a missing key if the state_dict was
+ * incomplete, with TLD_ERR_SHAPE where a tensor's element count is not the configuration's. */
 TLD_API int tld_engine_finalize_weights(tld_engine* e);
 
 /* Weights from a flat fp32 DEVICE vector, in place.  The vector is in tld_train_param_layout order -- the reference's
@@ -74,7 +75,7 @@ TLD_API int tld_engine_finalize_weights(tld_engine* e);
  * same configuration is one.  tld_engine_param_count is its length (= tld_train_param_count of a training engine with the same config; known from create on).
  * tld_engine_refresh_weights rebuilds, with kernels enqueued on hip_stream, every weight image this engine holds in its mode (fp32 copies, bf16 casts,
  * hi / lo splits, transposes, depthwise tap packings, the LayerNorm-1 / LayerNorm-3 folds with their column sums and packed rows, the e4m3 images with
- * their E8M0 scales), each with exactly the bits tld_engine_finalize_weights computes from the same values on the host.  It allocates nothing, frees
+ * their E8M0 scales), each with exactly the bits tld_engine_finalize_weights builds from the same values (it runs the same kernels).  It allocates nothing, frees
  * nothing, stages nothing through the host and synchronises neither the stream nor the device; flat_device is read until the stream has passed the
  * call, and calls on this engine enqueued on the same stream afterwards see the new weights.  The pointer tables built at finalize, the activation
  * buffers, the capacity, the GEMM mode, the low-latency class and the debug / profile state stay; angular_speeds is not a parameter and keeps its
@@ -253,6 +254,15 @@ TLD_API int tld_debug_decode_stage(const void* raw, const void* aux, int32_t dty
  *   operands as the engine holds them, read in place, in logical [N][K] order (the fused QKV -> attention kernel's row packing is undone on read):
  *   blk<i>.wqkv [3 d, d], blk<i>.wup [hid, d] (gamma-scaled under the LayerNorm folds), blk<i>.wdown [d, hid], and the folds' vectors
  *   blk<i>.qkv_c1, blk<i>.qkv_b1 [3 d], blk<i>.up_c1, blk<i>.up_b1 [hid].
+ *   every other weight image, read in place in STORAGE order under img.<field> (an image the engine's mode does not hold: no such stage):
+ *   the fp32 copies img.{angular [noise_embed_dims / 2], ff1_w [d, noise_embed_dims], ff1_b, ff3_w [d, d], ff3_b, label_w [d, text], label_b, norm_w, norm_b,
+ *   conv_w [pd, pd], conv_b, pln1_w, pln1_b [pd], plin_b, pln2_w, pln2_b [d], pos [tokens, d], out_w [pd, d], out_b [pd]} (pd = patch_dim) and
+ *   blk<i>.img.{kv_w [2 d, d], q_w [d, d], up_b, dw_b [hid], down_b, n1_w, n1_b, n2_w, n2_b, n3_w, n3_b [d]}; the split bf16 pairs img.out_w_hl
+ *   [2, pd, d], img.plin_w_hl [2, d, pd], img.out_fold_hl [2, pd rounded up to 16, d + hid] with img.out_fold_b [pd]; img.plin_wt [pd, d];
+ *   blk<i>.img.{qkv_wf [3 d, d], qkv_c1, qkv_b1 [3 d]} (the LayerNorm-1 fold in [q; k; v] row order) and blk<i>.img.{qkv_wp, qkv_c1p, qkv_b1p}, the same in
+ *   the fused kernel's PACKED row order; blk<i>.img.{dw_w9c, dw_w9c_half [9, hid], dw_b_half [hid]} and blk<i>.img.dw_wpk [3, 4, hid, 2], the packed tap
+ *   pairs as bf16 (low half first); fp8 mode: blk<i>.img.{qkv_w8 [3 d, d], up_w8 [hid, d], down_w8 [d, hid]}, the raw e4m3 codes, and
+ *   blk<i>.img.{qkv_s8, up_s8, down_s8} [N, K / 32], the E8M0 scale bytes in logical order, both as the byte values 0 ... 255.
  *   fp8 GEMM mode (tld_engine_set_gemm_dtype; no folds, two-kernel QKV, up-projection alone): the three A operands as the GEMMs read them, copied after
  *   the producer or quantisation pass and before the GEMM: blk<i>.a8_qkv [Mi, d], blk<i>.a8_up [M, d], blk<i>.a8_down [M, hid], each as two stages:
  *   <name>.q, the e4m3 codes, and <name>.s [rows, K / 32], the E8M0 scale bytes in logical order (the GEMM's [K / 128][rows][4] layout, with the rows

@@ -1,4 +1,4 @@
-// Host driver for csrc/tld_tail_fold_math.h: the folded out_proj operand as tld_engine_finalize_weights builds it.
+// Host driver for csrc/tld_tail_fold_math.h: the folded out_proj operand, element by element as refresh_tail_fold_kernel builds it.
 //   tail_fold_main pd d hid in.bin out.bin
 // in.bin:  fp32 Wout [pd][d] | Wd [d][hid] | bd [d] | bo [pd]
 // out.bin: fp32 W' [pd][hid] | b' [pd] | uint16 image [2][pdp][d + hid] (hi plane, lo plane; rows >= pd zero)
@@ -23,14 +23,8 @@ int main(int argc, char** argv) {
     const int pdp = tld::tail_fold_padded_rows(pd), K = d + hid;
     std::vector<float> wf((size_t)pd * hid), bf((size_t)pd);
     std::vector<uint16_t> img((size_t)2 * pdp * K, 0);
-    std::vector<double> acc((size_t)hid);
     for (int r = 0; r < pd; ++r) {
-        // the row form (what tld_engine_finalize_weights calls) and the element form (what the refresh kernel calls) must agree bit for bit
-        tld::tail_fold_weight_row(wout + (size_t)r * d, wd, d, hid, acc.data(), &wf[(size_t)r * hid]);
-        for (int j = 0; j < hid; ++j) {
-            const float e = tld::tail_fold_weight(wout + (size_t)r * d, wd, d, hid, j);
-            if (memcmp(&e, &wf[(size_t)r * hid + j], 4) != 0) { fprintf(stderr, "row form and element form differ at [%d][%d]\n", r, j); return 1; }
-        }
+        for (int j = 0; j < hid; ++j) wf[(size_t)r * hid + j] = tld::tail_fold_weight(wout + (size_t)r * d, wd, d, hid, j);
         bf[(size_t)r] = tld::tail_fold_bias(wout + (size_t)r * d, bd, bo[r], d);
         for (int k = 0; k < K; ++k) {
             const float w = k < d ? wout[(size_t)r * d + k] : wf[(size_t)r * hid + (k - d)];

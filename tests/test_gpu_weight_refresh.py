@@ -1,9 +1,11 @@
 """GPU: the device weight refresh (tld_engine_refresh_weights, Denoiser.load_flat, Trainer.sync_denoiser / eval_generate).
 
-The refresh must produce exactly the bits tld_engine_finalize_weights computes on the host, so every comparison here is an equality: engine H is
-a fresh Denoiser with load_state_dict(B) (the host path), engine D held weights A, ran a forward, and took B through load_flat.  With the stage
-hook on, EVERY stage of a forward -- the weight operands the engine holds included -- must have the same bits in both, poison and all; with it
-off, the forward and a CFG sampler must return equal tensors.  Weights: synth_state_dict, seed 0 = "A", seed 1 = "B"; two blocks, model batch 3."""
+A refresh must leave exactly the engine a fresh load of the same values builds, so every comparison here is an equality: engine H is a fresh
+Denoiser with load_state_dict(B) (tld_engine_load_tensor + tld_engine_finalize_weights), engine D held weights A, ran a forward, and took B
+through load_flat.  Both run the refresh kernels, so what those compute is held against an independent statement: every weight image of either
+engine, read through the stage hook, must have the bits of the numpy restatement in weight_image_refs.py.  With the stage hook on, EVERY stage
+of a forward -- the weight images included -- must have the same bits in both engines, poison and all; with it off, the forward and a CFG
+sampler must return equal tensors.  Weights: synth_state_dict, seed 0 = "A", seed 1 = "B"; two blocks, model batch 3."""
 import ctypes as C
 import os
 from dataclasses import asdict
@@ -13,6 +15,7 @@ import pytest
 import torch
 
 from test_gpu_parity import _dev
+from weight_image_refs import BLOCK_IMAGES, GLOBAL_IMAGES, as_read, engine_mode, weight_images
 from transformer_latent_diffusion_amd import Denoiser, DenoiserConfig, DiffusionGenerator, TrainConfig, Trainer, _lib, flatten_state_dict, schedule, weights
 
 pytestmark = pytest.mark.gpu
@@ -64,7 +67,7 @@ def _with_env(env, fn):
 
 
 def _model(case, seed, batch=BATCH):
-    """A Denoiser of the case holding the weights of `seed` through the HOST path, its engine built (the switches are read at tld_engine_create)."""
+    """A Denoiser of the case holding the weights of `seed` through load_state_dict, its engine built (the switches are read at tld_engine_create)."""
     cfg, env, dtype, lowlat = CASES[case]
     m = Denoiser(**asdict(cfg)).to(_dev())
     m.load_state_dict(_sd(cfg, seed)[0])
@@ -87,9 +90,9 @@ def _inputs(cfg, B=BATCH, seed=5):
 
 def _stage_names(cfg):
     """Every name the stage hook of a forward can hold (include/tld_hip.h); which of them exist depends on the engine's mode."""
-    names = ["tokens0", "out", "cond.sin", "cond.h1", "cond.pre", "cond.y", "cond.kv", "cond.wq", "cond.bwq"]
+    names = ["tokens0", "out", "cond.sin", "cond.h1", "cond.pre", "cond.y", "cond.kv", "cond.wq", "cond.bwq"] + GLOBAL_IMAGES
     per_block = ["x_in", "ln1", "xn1", "qk", "vt", "att", "sa", "ca", "stats", "xn3", "hid_pre", "hid", "splitk", "mlp", "a8_qkv.q", "a8_qkv.s", "a8_up.q",
-                 "a8_up.s", "a8_down.q", "a8_down.s", "wqkv", "wup", "wdown", "qkv_c1", "qkv_b1", "up_c1", "up_b1"]
+                 "a8_up.s", "a8_down.q", "a8_down.s", "wqkv", "wup", "wdown", "qkv_c1", "qkv_b1", "up_c1", "up_b1"] + BLOCK_IMAGES
     return names + [f"blk{i}.{n}" for i in range(cfg.n_layers) for n in per_block]
 
 
@@ -108,13 +111,30 @@ def _stages(m, cfg, inputs):
     return got, out
 
 
-def _assert_same_engine_state(h, d, cfg, what):
+_REF = {}
+
+
+def _images(case, seed):
+    """{stage name: bits} of every weight image an engine of the case holds with the weights of `seed`, from the numpy restatement."""
+    if (case, seed) not in _REF:
+        cfg, env, dtype, _ = CASES[case]
+        ref = weight_images(_sd(cfg, seed)[0], cfg, engine_mode(cfg, env, dtype))
+        _REF[case, seed] = {n: as_read(a).view(np.uint32) for n, a in ref.items()}
+    return _REF[case, seed]
+
+
+def _assert_same_engine_state(h, d, cfg, what, ref):
     """Requirements 2 and 3: every stage of a debug forward has the same bits in both engines; with debug off the forward and the end latent of a
-    4-level CFG sampler are equal."""
+    4-level CFG sampler are equal.  `ref` (_images): every weight image either engine holds has the bits of the restatement, and no other exists."""
     inputs = _inputs(cfg)
     sh, oh = _stages(h, cfg, inputs)
     sd_, od = _stages(d, cfg, inputs)
     assert set(sh) == set(sd_), (what, set(sh) ^ set(sd_))
+    for who, got in (("load_state_dict", sh), ("load_flat", sd_)):
+        held = {n for n in got if "img." in n or n.split(".")[-1] in ("wqkv", "wup", "wdown", "qkv_c1", "qkv_b1", "up_c1", "up_b1")}
+        assert held == set(ref), (what, who, held ^ set(ref))
+        wrong = [n for n in ref if got[n].shape != ref[n].shape or not np.array_equal(got[n], ref[n])]
+        assert not wrong, (what, who, wrong)
     operands = [n for n in sh if n.split(".")[-1] in ("wqkv", "wup", "wdown")]
     assert len(operands) == 3 * cfg.n_layers and "tokens0" in sh and "out" in sh, (what, sorted(sh))
     differ = [n for n in sh if sh[n].shape != sd_[n].shape or not np.array_equal(sh[n], sd_[n])]
@@ -148,12 +168,12 @@ def test_refreshed_engine_equals_host_loaded_engine(case):
     assert L.tld_engine_param_count(d._engine) == weights.param_count(cfg) == d.param_count
     wb = L.tld_engine_weight_bytes(d._engine)
     assert wb == L.tld_engine_weight_bytes(h._engine)
-    _assert_same_engine_state(h, d, cfg, case)
+    _assert_same_engine_state(h, d, cfg, case, _images(case, 1))
     if case == "d768_256tok":       # no residue: back to A on the refreshed engine (from a HOST vector this time) = a fresh host-loaded A
         handle = d._engine.value
         d.load_flat(_sd(cfg, 0)[1])
         assert d._engine.value == handle and L.tld_engine_weight_bytes(d._engine) == wb
-        _assert_same_engine_state(_model(case, 0), d, cfg, case + " back to A")
+        _assert_same_engine_state(_model(case, 0), d, cfg, case + " back to A", _images(case, 0))
 
 
 def test_state_dict_and_rebuild_after_load_flat():

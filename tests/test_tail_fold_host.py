@@ -11,6 +11,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from weight_image_refs import _bf16_value, _reference      # (the restatement lives with those of the other weight images)
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = [(16, 768, 3072), (4, 64, 128), (64, 192, 384)]      # (patch_dim, d, hid): the 100M model, the smallest, the widest patch
 
@@ -28,16 +30,6 @@ def _build(tmp_path, name, flags):
     return exe
 
 
-def _bf16_bits(x):
-    """Round-to-nearest-even to bf16, as uint16 (finite inputs)."""
-    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
-    return ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
-
-
-def _bf16_value(bits):
-    return (bits.astype(np.uint32) << 16).view(np.float32)
-
-
 def _inputs(pd, d, hid, seed):
     rng = np.random.default_rng(seed)
     wout = (rng.standard_normal((pd, d)) / np.sqrt(d)).astype(np.float32)
@@ -45,27 +37,6 @@ def _inputs(pd, d, hid, seed):
     bd = (rng.standard_normal(d) * 0.1).astype(np.float32)
     bo = (rng.standard_normal(pd) * 0.1).astype(np.float32)
     return wout, wd, bd, bo
-
-
-def _reference(wout, wd, bd, bo):
-    pd, d = wout.shape
-    hid = wd.shape[1]
-    q = _bf16_value(_bf16_bits(wd)).astype(np.float64)
-    w64 = wout.astype(np.float64)
-    s = np.zeros((pd, hid), np.float64)
-    sb = np.zeros(pd, np.float64)
-    for k in range(d):                                   # the sequential sum: one product (exact in float64) and one add per k
-        s += w64[:, k:k + 1] * q[k][None, :]
-        sb += w64[:, k] * np.float64(bd[k])
-    wf = s.astype(np.float32)
-    bf = (sb + bo.astype(np.float64)).astype(np.float32)
-    pdp, K = (pd + 15) // 16 * 16, d + hid
-    row = np.concatenate([wout, wf], axis=1)
-    hi = _bf16_bits(row)
-    lo = _bf16_bits(row - _bf16_value(hi))               # fp32 subtraction, exact or rounded once as in the header
-    img = np.zeros((2, pdp, K), np.uint16)
-    img[0, :pd], img[1, :pd] = hi, lo
-    return wf, bf, img
 
 
 def _run(exe, tmp_path, pd, d, hid, seed):

@@ -101,6 +101,8 @@ parts["tiny debug forward"] = mt(eps[:2].to(dev), torch.tensor([[0.3], [0.8]]).t
 blk = ("x_in ln1 xn1 qk vt att sa ca stats xn3 hid_pre hid splitk mlp wqkv wup wdown qkv_c1 qkv_b1 up_c1 up_b1").split()
 stage_parts("tiny stage", ["tokens0", "out"] + [f"cond.{n}" for n in "sin h1 pre y kv wq bwq".split()] + [f"blk{i}.{n}" for i in range(ct.n_layers) for n in blk],
             mt.read_stage)
+from weight_image_refs import BLOCK_IMAGES, GLOBAL_IMAGES      # the weight images in storage order
+stage_parts("tiny stage", GLOBAL_IMAGES + [f"blk{i}.{n}" for i in range(ct.n_layers) for n in BLOCK_IMAGES], mt.read_stage)
 mt.set_debug(False)
 ce = ClipTextEncoder(TINY, max_batch=4)
 ce.load_state_dict({k: torch.from_numpy(v) for k, v in synth_clip_state_dict(TINY, 3).items()})

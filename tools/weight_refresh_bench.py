@@ -2,8 +2,8 @@
 """Cost of bringing an inference engine up to date with a live Trainer's EMA weights, at the C1 model (100 M parameters,
 max_batch 128), in one process:
 
-  (a) the host path, the only one before the device refresh:   den.load_state_dict(tr.ema_state_dict()); den.reserve(128)
-      -- a device-to-host copy of the vector, the host's weight transformations and an engine rebuild.  Wall time, ending in a synchronise.
+  (a) a fresh load, the only way before the device refresh:    den.load_state_dict(tr.ema_state_dict()); den.reserve(128)
+      -- a device-to-host copy of the vector and an engine rebuild (upload + the refresh kernels).  Wall time, ending in a synchronise.
   (b) the device path:                                          den.load_flat(tr.ema)
       -- one device-to-device copy and the refresh kernels, in place.  Wall time ending in a synchronise, and device time from HIP events.
 
@@ -69,7 +69,7 @@ lines = [
     "Bringing an inference engine (100 M model, d = 768, %d blocks, 256 tokens, max_batch %d) up to date with a Trainer's EMA weights," % (args.layers, args.batch),
     "one MI355X, one process (tools/weight_refresh_bench.py).  %d parameters = %.1f MB as fp32.  Not gated anywhere: a record." % (n, n * 4 / 1e6),
     "",
-    "(a) host path   den.load_state_dict(tr.ema_state_dict()); den.reserve(%d)   wall ms, synchronised:   %s" % (args.batch, "  ".join("%.1f" % v for v in host)),
+    "(a) fresh load  den.load_state_dict(tr.ema_state_dict()); den.reserve(%d)   wall ms, synchronised:   %s" % (args.batch, "  ".join("%.1f" % v for v in host)),
     "(b) device path den.load_flat(tr.ema)                                        wall ms, synchronised:   median %.3f  (min %.3f, max %.3f; %d calls)"
     % (med(wall), min(wall), max(wall), len(wall)),
     "                (the private device-to-device copy of the vector + 4 kernels) device ms, HIP events:   median %.3f  (min %.3f, max %.3f)"

@@ -1,4 +1,4 @@
-// tld_engine.hip -- host side of libtld_hip.so: weight packing, workspace, kernel sequencing, C ABI.
+// tld_engine.hip -- host side of libtld_hip.so: weight image allocation (tld_refresh.hip builds them), workspace, kernel sequencing, C ABI.
 //
 // One engine = one device + one model.  The forward is a fixed sequence of hand-written kernels
 // (7 per decoder block) enqueued on the caller's stream; the sampler prepares every conditioning
@@ -113,33 +113,6 @@ struct tld_engine : DeviceArena {      // (pad = 256: every allocation of this e
 };
 
 namespace {
-
-int upload_f32(tld_engine* e, const char* key, float** dst, int64_t expect) {
-    auto it = e->host.find(key);
-    if (it == e->host.end()) return fail(TLD_ERR_STATE, "state_dict entry missing: %s", key);
-    if ((int64_t)it->second.data.size() != expect)
-        return fail(TLD_ERR_SHAPE, "%s: expected %lld elements, got %lld", key, (long long)expect,
-                    (long long)it->second.data.size());
-    if (int rc = dev_alloc(e, dst, (size_t)expect)) return rc;
-    HIP_TRY(hipMemcpy(*dst, it->second.data.data(), expect * sizeof(float), hipMemcpyHostToDevice));
-    e->weight_bytes += expect * sizeof(float);
-    return TLD_OK;
-}
-
-int upload_bf16(tld_engine* e, const char* key, bf16** dst, int64_t expect) {
-    auto it = e->host.find(key);
-    if (it == e->host.end()) return fail(TLD_ERR_STATE, "state_dict entry missing: %s", key);
-    if ((int64_t)it->second.data.size() != expect)
-        return fail(TLD_ERR_SHAPE, "%s: expected %lld elements, got %lld", key, (long long)expect,
-                    (long long)it->second.data.size());
-    std::vector<uint16_t> tmp((size_t)expect);
-    const float* src = it->second.data.data();
-    for (int64_t i = 0; i < expect; ++i) tmp[(size_t)i] = f32_to_bf16_rne(src[i]);
-    if (int rc = dev_alloc(e, dst, (size_t)expect)) return rc;
-    HIP_TRY(hipMemcpy(*dst, tmp.data(), expect * 2, hipMemcpyHostToDevice));
-    e->weight_bytes += expect * 2;
-    return TLD_OK;
-}
 
 int ensure_cond_capacity(tld_engine* e, int T) {
     if (T <= e->cond_cap) return TLD_OK;
@@ -260,6 +233,34 @@ int reserve_snapshots(tld_engine* e) {
             if (Stage* st = S.ref(blk_name(l, "wup"), Ly.up_w8, ST_MX8W, hid, d)) st->aux = Ly.up_s8;
             if (Stage* st = S.ref(blk_name(l, "wdown"), Ly.down_w8, ST_MX8W, d, hid)) st->aux = Ly.down_s8;
         }
+        // every other image of the block, in storage order (a null pointer -- an image this mode does not hold -- gets no name)
+        const struct { const char* n; const void* p; int dt; int64_t s0, s1, s2, s3; } imgs[] = {
+            {"kv_w", Ly.kv_w, ST_F32, 2 * e->d, e->d, 1, 1}, {"q_w", Ly.q_w, ST_F32, e->d, e->d, 1, 1}, {"up_b", Ly.up_b, ST_F32, e->hid, 1, 1, 1},
+            {"dw_b", Ly.dw_b, ST_F32, e->hid, 1, 1, 1}, {"down_b", Ly.down_b, ST_F32, e->d, 1, 1, 1}, {"n1_w", Ly.n1_w, ST_F32, e->d, 1, 1, 1},
+            {"n1_b", Ly.n1_b, ST_F32, e->d, 1, 1, 1}, {"n2_w", Ly.n2_w, ST_F32, e->d, 1, 1, 1}, {"n2_b", Ly.n2_b, ST_F32, e->d, 1, 1, 1},
+            {"n3_w", Ly.n3_w, ST_F32, e->d, 1, 1, 1}, {"n3_b", Ly.n3_b, ST_F32, e->d, 1, 1, 1},
+            {"qkv_wf", Ly.qkv_wf, ST_BF16, 3 * e->d, e->d, 1, 1}, {"qkv_c1", Ly.qkv_c1, ST_F32, 3 * e->d, 1, 1, 1}, {"qkv_b1", Ly.qkv_b1, ST_F32, 3 * e->d, 1, 1, 1},
+            {"qkv_wp", Ly.qkv_wp, ST_BF16, 3 * e->d, e->d, 1, 1}, {"qkv_c1p", Ly.qkv_c1p, ST_F32, 3 * e->d, 1, 1, 1}, {"qkv_b1p", Ly.qkv_b1p, ST_F32, 3 * e->d, 1, 1, 1},
+            {"dw_w9c", Ly.dw_w9c, ST_F32, 9, e->hid, 1, 1}, {"dw_w9c_half", Ly.dw_w9c_half, ST_F32, 9, e->hid, 1, 1}, {"dw_b_half", Ly.dw_b_half, ST_F32, e->hid, 1, 1, 1},
+            {"dw_wpk", Ly.dw_wpk, ST_BF16, 3, 4, e->hid, 2},
+            {"qkv_w8", Ly.qkv_w8, ST_U8, 3 * e->d, e->d, 1, 1}, {"qkv_s8", Ly.qkv_s8, ST_MX8S, 3 * e->d, e->d / 32, 1, 1},
+            {"up_w8", Ly.up_w8, ST_U8, e->hid, e->d, 1, 1}, {"up_s8", Ly.up_s8, ST_MX8S, e->hid, e->d / 32, 1, 1},
+            {"down_w8", Ly.down_w8, ST_U8, e->d, e->hid, 1, 1}, {"down_s8", Ly.down_s8, ST_MX8S, e->d, e->hid / 32, 1, 1}};
+        for (const auto& q : imgs) S.ref(blk_name(l, "img.") + q.n, q.p, q.dt, q.s0, q.s1, q.s2, q.s3);
+    }
+    {   // ... and of those outside the blocks
+        StageStore& S = e->stages;
+        const int64_t dd = e->d, ne = e->ne, pd = e->pd, K = e->d + e->hid;
+        S.ref("img.angular", e->angular, ST_F32, ne / 2); S.ref("img.ff1_w", e->ff1_w, ST_F32, dd, ne); S.ref("img.ff1_b", e->ff1_b, ST_F32, dd);
+        S.ref("img.ff3_w", e->ff3_w, ST_F32, dd, dd); S.ref("img.ff3_b", e->ff3_b, ST_F32, dd);
+        S.ref("img.label_w", e->label_w, ST_F32, dd, e->text); S.ref("img.label_b", e->label_b, ST_F32, dd);
+        S.ref("img.norm_w", e->norm_w, ST_F32, dd); S.ref("img.norm_b", e->norm_b, ST_F32, dd);
+        S.ref("img.conv_w", e->conv_w, ST_F32, pd, pd); S.ref("img.conv_b", e->conv_b, ST_F32, pd);
+        S.ref("img.pln1_w", e->pln1_w, ST_F32, pd); S.ref("img.pln1_b", e->pln1_b, ST_F32, pd); S.ref("img.plin_b", e->plin_b, ST_F32, dd);
+        S.ref("img.pln2_w", e->pln2_w, ST_F32, dd); S.ref("img.pln2_b", e->pln2_b, ST_F32, dd); S.ref("img.pos", e->pos, ST_F32, e->ntok, dd);
+        S.ref("img.out_w", e->out_w, ST_F32, pd, dd); S.ref("img.out_b", e->out_b, ST_F32, pd);
+        S.ref("img.out_w_hl", e->out_w_hl, ST_BF16, 2, pd, dd); S.ref("img.plin_w_hl", e->plin_w_hl, ST_BF16, 2, dd, pd); S.ref("img.plin_wt", e->plin_wt, ST_F32, pd, dd);
+        S.ref("img.out_fold_hl", e->out_fold_hl, ST_BF16, 2, tail_fold_padded_rows(e->pd), K); S.ref("img.out_fold_b", e->out_fold_b, ST_F32, pd);
     }
     return TLD_OK;
 }
@@ -812,284 +813,101 @@ int tld_engine_load_tensor(tld_engine* e, const char* key, const void* host_ptr,
     return TLD_OK;
 }
 
+// Allocates every weight image this engine's mode holds, uploads the loaded fp32 tensors as ONE temporary flat vector in ParamLayout order and lets the
+// refresh kernels (tld_refresh.hip: the one builder of every image) fill them; then the activation buffers.  No arithmetic on weight values happens here.
 int tld_engine_finalize_weights(tld_engine* e) {
     if (!e) return fail(TLD_ERR_INVALID, "null engine");
     if (e->finalized) return TLD_OK;
     DeviceGuard dg(e->cfg.device_id);
     const int64_t d = e->d, ne = e->ne, pd = e->pd, hid = e->hid, N = e->ntok, text = e->text;
-    const int64_t cpp = pd;   // C*p*p
-#define UP32(key, field, n) if (int rc = upload_f32(e, key, &e->field, (n))) return rc;
-    UP32("fourier_feats.0.angular_speeds", angular, ne / 2)
-    UP32("fourier_feats.1.weight", ff1_w, d * ne) UP32("fourier_feats.1.bias", ff1_b, d)
-    UP32("fourier_feats.3.weight", ff3_w, d * d) UP32("fourier_feats.3.bias", ff3_b, d)
-    UP32("label_proj.weight", label_w, d * text) UP32("label_proj.bias", label_b, d)
-    UP32("norm.weight", norm_w, d) UP32("norm.bias", norm_b, d)
-    UP32("denoiser_trans_block.patchify_and_embed.0.weight", conv_w, pd * cpp)
-    UP32("denoiser_trans_block.patchify_and_embed.0.bias", conv_b, pd)
-    UP32("denoiser_trans_block.patchify_and_embed.2.weight", pln1_w, pd)
-    UP32("denoiser_trans_block.patchify_and_embed.2.bias", pln1_b, pd)
-    UP32("denoiser_trans_block.patchify_and_embed.3.bias", plin_b, d)
-    UP32("denoiser_trans_block.patchify_and_embed.4.weight", pln2_w, d)
-    UP32("denoiser_trans_block.patchify_and_embed.4.bias", pln2_b, d)
-    UP32("denoiser_trans_block.pos_embed.weight", pos, N * d)
-    UP32("denoiser_trans_block.out_proj.0.weight", out_w, pd * d)
-    UP32("denoiser_trans_block.out_proj.0.bias", out_b, pd)
-#undef UP32
-    {   // out_proj weight as hi + lo bf16 halves for the matrix-pipe tail kernel (hi = bf16(w), lo = bf16(w - hi): 16 significant bits)
-        const std::vector<float>& W = e->host["denoiser_trans_block.out_proj.0.weight"].data;
-        std::vector<uint16_t> hl((size_t)(2 * pd * d));
-        for (int64_t i = 0; i < pd * d; ++i) {
-            const uint16_t hi = f32_to_bf16_rne(W[(size_t)i]);
-            const float hf = bf16_to_f32(hi);
-            hl[(size_t)i] = hi; hl[(size_t)(pd * d + i)] = f32_to_bf16_rne(W[(size_t)i] - hf);
-        }
-        if (int rc = dev_alloc(e, &e->out_w_hl, hl.size())) return rc;
-        HIP_TRY(hipMemcpy(e->out_w_hl, hl.data(), hl.size() * 2, hipMemcpyHostToDevice));
-        e->weight_bytes += (int64_t)hl.size() * 2;
-    }
-    {   // the same split for the patch-embedding Linear weight [d, pd] (embed_mfma_kernel)
-        const std::vector<float>& W = e->host["denoiser_trans_block.patchify_and_embed.3.weight"].data;
-        if ((int64_t)W.size() == d * pd) {
-            std::vector<uint16_t> hl((size_t)(2 * pd * d));
-            for (int64_t i = 0; i < pd * d; ++i) {
-                const uint16_t hi = f32_to_bf16_rne(W[(size_t)i]);
-                const float hf = bf16_to_f32(hi);
-                hl[(size_t)i] = hi; hl[(size_t)(pd * d + i)] = f32_to_bf16_rne(W[(size_t)i] - hf);
-            }
-            if (int rc = dev_alloc(e, &e->plin_w_hl, hl.size())) return rc;
-            HIP_TRY(hipMemcpy(e->plin_w_hl, hl.data(), hl.size() * 2, hipMemcpyHostToDevice));
-            e->weight_bytes += (int64_t)hl.size() * 2;
-        }
-    }
-    {   // Linear(pd -> d) weight [d, pd] -> transposed [pd, d] for coalesced per-feature reads
-        const char* key = "denoiser_trans_block.patchify_and_embed.3.weight";
+    const ParamLayout pl = make_param_layout(e->d, e->L, e->ne, e->pd, e->hid, e->ntok, e->text);
+    // the loaded state dict: every parameter present, with its element count (keys outside the layout are ignored)
+    const auto loaded = [e](const std::string& key, int64_t numel, const HostTensor** out) -> int {
         auto it = e->host.find(key);
-        if (it == e->host.end()) return fail(TLD_ERR_STATE, "state_dict entry missing: %s", key);
-        if ((int64_t)it->second.data.size() != d * pd) return fail(TLD_ERR_SHAPE, "%s: bad size", key);
-        std::vector<float> tr((size_t)(d * pd));
-        for (int64_t n = 0; n < d; ++n)
-            for (int64_t o = 0; o < pd; ++o) tr[(size_t)(o * d + n)] = it->second.data[(size_t)(n * pd + o)];
-        if (int rc = dev_alloc(e, &e->plin_wt, (size_t)(d * pd))) return rc;
-        HIP_TRY(hipMemcpy(e->plin_wt, tr.data(), tr.size() * sizeof(float), hipMemcpyHostToDevice));
-        e->weight_bytes += (int64_t)tr.size() * 4;
-    }
-    char key[256];
-    for (int l = 0; l < e->L; ++l) {
-        Layer& Ly = e->layers[l];
-#define LK(suffix) (snprintf(key, sizeof(key), "denoiser_trans_block.decoder_blocks.%d.%s", l, suffix), key)
-        // bf16 GEMM operands: only the copies this engine's paths read are made resident (the LayerNorm folds use gamma-scaled
-        // copies built below, the fp8 mode its own e4m3 ones); presence and size of the three matrices are checked either way
-        {
-            const struct { const char* suffix; int64_t n; } need[3] = {{"self_attention.qkv_linear.weight", 3 * d * d},
-                                                                       {"mlp.mlp.0.weight", hid * d}, {"mlp.mlp.3.weight", d * hid}};
-            for (const auto& nd : need) {
-                auto it = e->host.find(LK(nd.suffix));
-                if (it == e->host.end()) return fail(TLD_ERR_STATE, "state_dict entry missing: %s", key);
-                if ((int64_t)it->second.data.size() != nd.n)
-                    return fail(TLD_ERR_SHAPE, "%s: expected %lld elements, got %lld", key, (long long)nd.n, (long long)it->second.data.size());
-            }
-            for (const char* sfx : {"norm1.weight", "norm1.bias", "norm3.weight", "norm3.bias", "mlp.mlp.0.bias", "mlp.mlp.1.bias"})
-                if (e->host.find(LK(sfx)) == e->host.end()) return fail(TLD_ERR_STATE, "state_dict entry missing: %s", key);
-        }
-        if (!e->fold_ln1 && !e->fp8)
-            if (int rc = upload_bf16(e, LK("self_attention.qkv_linear.weight"), &Ly.qkv_w, 3 * d * d)) return rc;
-        if (int rc = upload_f32(e, LK("cross_attention.kv_linear.weight"), &Ly.kv_w, 2 * d * d)) return rc;
-        if (int rc = upload_f32(e, LK("cross_attention.q_linear.weight"), &Ly.q_w, d * d)) return rc;
-        if (!e->fold_ln3 && !e->fp8)
-            if (int rc = upload_bf16(e, LK("mlp.mlp.0.weight"), &Ly.up_w, hid * d)) return rc;
-        if (int rc = upload_f32(e, LK("mlp.mlp.0.bias"), &Ly.up_b, hid)) return rc;
-        if (int rc = upload_f32(e, LK("mlp.mlp.1.bias"), &Ly.dw_b, hid)) return rc;
-        if (!e->fp8)
-            if (int rc = upload_bf16(e, LK("mlp.mlp.3.weight"), &Ly.down_w, d * hid)) return rc;
-        if (int rc = upload_f32(e, LK("mlp.mlp.3.bias"), &Ly.down_b, d)) return rc;
-        if (int rc = upload_f32(e, LK("norm1.weight"), &Ly.n1_w, d)) return rc;
-        if (int rc = upload_f32(e, LK("norm1.bias"), &Ly.n1_b, d)) return rc;
+        if (it == e->host.end()) return fail(TLD_ERR_STATE, "state_dict entry missing: %s", key.c_str());
+        if ((int64_t)it->second.data.size() != numel)
+            return fail(TLD_ERR_SHAPE, "%s: expected %lld elements, got %lld", key.c_str(), (long long)numel, (long long)it->second.data.size());
+        *out = &it->second;
+        return TLD_OK;
+    };
+    const HostTensor* t = nullptr;
+    for (const ParamTensor& q : pl.tensors) if (int rc = loaded(q.key, q.numel, &t)) return rc;
+    if (int rc = loaded("fourier_feats.0.angular_speeds", ne / 2, &t)) return rc;      // a buffer, not a parameter: not in the flat vector
+#define IMG(ptr, n) if (int rc = dev_alloc(e, &(ptr), (size_t)(n), true)) return rc;
+    IMG(e->angular, ne / 2)
+    HIP_TRY(hipMemcpy(e->angular, t->data.data(), (size_t)(ne / 2) * sizeof(float), hipMemcpyHostToDevice));
+    // the images outside the blocks, each with its place in the flat vector
+    RefreshPlan& R = e->refresh;
+    R = RefreshPlan();
+    R.d = e->d; R.hid = e->hid; R.L = e->L; R.pd = e->pd; R.l0 = pl.layers[0]; R.layer_stride = pl.layer_stride(); R.outw = pl.outw; R.outb = pl.outb;
+    R.fold = e->fold_ln1 || e->fold_ln3; R.fp8 = e->fp8;
+#define JOB(ptr, src, n, kind, cols) IMG(ptr, (kind) == RJ_SPLIT_HL ? 2 * (n) : (n)) R.jobs[R.njobs++] = RefreshJob{ptr, src, n, kind, cols};
+#define COPY(ptr, src, n) JOB(e->ptr, pl.src, n, RJ_COPY, 0)
+    COPY(ff1_w, ff1w, d * ne) COPY(ff1_b, ff1b, d) COPY(ff3_w, ff3w, d * d) COPY(ff3_b, ff3b, d) COPY(label_w, lbw, d * text) COPY(label_b, lbb, d)
+    COPY(norm_w, nw, d) COPY(norm_b, nb, d) COPY(conv_w, cvw, pd * pd) COPY(conv_b, cvb, pd) COPY(pln1_w, l1w, pd) COPY(pln1_b, l1b, pd)
+    COPY(plin_b, lib, d) COPY(pln2_w, l2w, d) COPY(pln2_b, l2b, d) COPY(pos, pos, N * d) COPY(out_w, outw, pd * d) COPY(out_b, outb, pd)
+    JOB(e->out_w_hl, pl.outw, pd * d, RJ_SPLIT_HL, 0)        // hi + lo bf16 halves for the matrix-pipe tail kernel (16 significant bits)
+    JOB(e->plin_w_hl, pl.liw, d * pd, RJ_SPLIT_HL, 0)        // the same split of the patch-embedding Linear weight [d, pd] (embed_mfma_kernel)
+    JOB(e->plin_wt, pl.liw, d * pd, RJ_TRANSPOSE, (int)pd)   // ... and its transpose [pd, d] for coalesced per-feature reads
+#undef COPY
+#undef JOB
+    static_assert(kRefreshMaxJobs >= 21, "the images outside the blocks");
+    for (Layer& Ly : e->layers) {
+        // bf16 GEMM operands: only the copies this engine's paths read are made resident (the LayerNorm folds use gamma-scaled copies, the fp8 mode
+        // its own e4m3 ones)
+        if (!e->fold_ln1 && !e->fp8) IMG(Ly.qkv_w, 3 * d * d)
+        if (!e->fold_ln3 && !e->fp8) IMG(Ly.up_w, hid * d)
+        if (!e->fp8) IMG(Ly.down_w, d * hid)
+        IMG(Ly.kv_w, 2 * d * d) IMG(Ly.q_w, d * d) IMG(Ly.up_b, hid) IMG(Ly.dw_b, hid) IMG(Ly.down_b, d)
+        IMG(Ly.n1_w, d) IMG(Ly.n1_b, d) IMG(Ly.n2_w, d) IMG(Ly.n2_b, d) IMG(Ly.n3_w, d) IMG(Ly.n3_b, d)
         if (e->fold_ln1) {
-            const std::vector<float>& W = e->host[LK("self_attention.qkv_linear.weight")].data;   // [3d][d]
-            const std::vector<float>& g1 = e->host[LK("norm1.weight")].data;
-            const std::vector<float>& be = e->host[LK("norm1.bias")].data;
-            std::vector<uint16_t> wf((size_t)(3 * d * d));
-            std::vector<float> c1((size_t)(3 * d)), b1((size_t)(3 * d));
-            for (int64_t n = 0; n < 3 * d; ++n) {
-                double sc = 0.0, sb = 0.0;
-                for (int64_t k2 = 0; k2 < d; ++k2) {
-                    const float w = W[(size_t)(n * d + k2)];
-                    const uint16_t q = f32_to_bf16_rne(g1[(size_t)k2] * w);
-                    wf[(size_t)(n * d + k2)] = q;
-                    const float qf = bf16_to_f32(q);
-                    sc += qf; sb += (double)be[(size_t)k2] * w;
-                }
-                c1[(size_t)n] = (float)sc; b1[(size_t)n] = (float)sb;
-            }
-            if (int rc = dev_alloc(e, &Ly.qkv_wf, wf.size())) return rc;
-            if (int rc = dev_alloc(e, &Ly.qkv_c1, c1.size())) return rc;
-            if (int rc = dev_alloc(e, &Ly.qkv_b1, b1.size())) return rc;
-            HIP_TRY(hipMemcpy(Ly.qkv_wf, wf.data(), wf.size() * 2, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(Ly.qkv_c1, c1.data(), c1.size() * 4, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(Ly.qkv_b1, b1.data(), b1.size() * 4, hipMemcpyHostToDevice));
-            e->weight_bytes += (int64_t)wf.size() * 2 + (int64_t)c1.size() * 8;
+            IMG(Ly.qkv_wf, 3 * d * d) IMG(Ly.qkv_c1, 3 * d) IMG(Ly.qkv_b1, 3 * d)
             if (e->fuse_qkv_attn) {     // rows [q; k; v] x [head][64]  ->  [head][feature half][q | k | v][32]: tile-column h of the fused kernel is head h, and each of
                 // its two 96-column wave columns holds 32 features of q, of k AND of v -- so the slow part of the image write (V^T: 2-byte scattered LDS writes) is
                 // shared by all eight waves instead of falling on the four that held v (round 5; the values and their accumulation order do not change)
-                std::vector<uint16_t> wp(wf.size());
-                std::vector<float> c1p(c1.size()), b1p(b1.size());
-                for (int64_t h = 0; h < e->H; ++h)
-                    for (int part = 0; part < 3; ++part)
-                        for (int64_t c = 0; c < 64; ++c) {
-                            const int64_t src = part * d + h * 64 + c, dst = h * 192 + (c >> 5) * 96 + part * 32 + (c & 31);
-                            memcpy(&wp[(size_t)(dst * d)], &wf[(size_t)(src * d)], (size_t)d * 2);
-                            c1p[(size_t)dst] = c1[(size_t)src]; b1p[(size_t)dst] = b1[(size_t)src];
-                        }
-                if (int rc = dev_alloc(e, &Ly.qkv_wp, wp.size())) return rc;
-                if (int rc = dev_alloc(e, &Ly.qkv_c1p, c1p.size() + 64)) return rc;      // (+64: the side-table DMA of the last head reads a 256-column window)
-                if (int rc = dev_alloc(e, &Ly.qkv_b1p, b1p.size() + 64)) return rc;
-                HIP_TRY(hipMemcpy(Ly.qkv_wp, wp.data(), wp.size() * 2, hipMemcpyHostToDevice));
-                HIP_TRY(hipMemcpy(Ly.qkv_c1p, c1p.data(), c1p.size() * 4, hipMemcpyHostToDevice));
-                HIP_TRY(hipMemcpy(Ly.qkv_b1p, b1p.data(), b1p.size() * 4, hipMemcpyHostToDevice));
-                e->weight_bytes += (int64_t)wp.size() * 2 + (int64_t)c1p.size() * 8;
+                IMG(Ly.qkv_wp, 3 * d * d)
+                if (int rc = dev_alloc(e, &Ly.qkv_c1p, (size_t)(3 * d + 64))) return rc;      // (+64: the side-table DMA of the last head reads a 256-column window;
+                if (int rc = dev_alloc(e, &Ly.qkv_b1p, (size_t)(3 * d + 64))) return rc;      // that margin is no weight)
+                e->weight_bytes += 2 * 3 * d * (int64_t)sizeof(float);
             }
         }
         if (e->fp8) {
-            struct Q { const char* key; int64_t rows, K; uint8_t** w; uint8_t** sc; };
-            const Q qs[3] = {{"self_attention.qkv_linear.weight", 3 * d, d, &Ly.qkv_w8, &Ly.qkv_s8},
-                             {"mlp.mlp.0.weight", hid, d, &Ly.up_w8, &Ly.up_s8},
-                             {"mlp.mlp.3.weight", d, hid, &Ly.down_w8, &Ly.down_s8}};
-            for (const Q& q : qs) {
-                const std::vector<float>& W = e->host[LK(q.key)].data;
-                std::vector<uint8_t> w8((size_t)(q.rows * q.K)), s8((size_t)(q.rows * q.K / 32));
-                quant_mx8_host(W.data(), (int)q.rows, (int)q.K, w8.data(), s8.data());
-                if (int rc = dev_alloc(e, q.w, w8.size())) return rc;
-                if (int rc = dev_alloc(e, q.sc, s8.size())) return rc;
-                HIP_TRY(hipMemcpy(*q.w, w8.data(), w8.size(), hipMemcpyHostToDevice));
-                HIP_TRY(hipMemcpy(*q.sc, s8.data(), s8.size(), hipMemcpyHostToDevice));
-                e->weight_bytes += (int64_t)(w8.size() + s8.size());
-            }
+            IMG(Ly.qkv_w8, 3 * d * d) IMG(Ly.qkv_s8, 3 * d * d / 32) IMG(Ly.up_w8, hid * d) IMG(Ly.up_s8, hid * d / 32)
+            IMG(Ly.down_w8, d * hid) IMG(Ly.down_s8, d * hid / 32)
         }
-        if (int rc = upload_f32(e, LK("norm2.weight"), &Ly.n2_w, d)) return rc;
-        if (int rc = upload_f32(e, LK("norm2.bias"), &Ly.n2_b, d)) return rc;
-        if (int rc = upload_f32(e, LK("norm3.weight"), &Ly.n3_w, d)) return rc;
-        if (int rc = upload_f32(e, LK("norm3.bias"), &Ly.n3_b, d)) return rc;
-        if (e->fold_ln3) {
-            const std::vector<float>& W = e->host[LK("mlp.mlp.0.weight")].data;      // [hid][d]  (1x1 conv = Linear)
-            const std::vector<float>& ub = e->host[LK("mlp.mlp.0.bias")].data;
-            const std::vector<float>& g3 = e->host[LK("norm3.weight")].data;
-            const std::vector<float>& b3 = e->host[LK("norm3.bias")].data;
-            std::vector<uint16_t> wf((size_t)(hid * d));
-            std::vector<float> c1((size_t)hid), b1((size_t)hid);
-            for (int64_t n = 0; n < hid; ++n) {
-                double sc = 0.0, sb = 0.0;
-                for (int64_t k2 = 0; k2 < d; ++k2) {
-                    const float w = W[(size_t)(n * d + k2)];
-                    const uint16_t q = f32_to_bf16_rne(g3[(size_t)k2] * w);
-                    wf[(size_t)(n * d + k2)] = q;
-                    const float qf = bf16_to_f32(q);
-                    sc += qf; sb += (double)b3[(size_t)k2] * w;
-                }
-                c1[(size_t)n] = (float)sc; b1[(size_t)n] = (float)(sb + ub[(size_t)n]);
-            }
-            if (int rc = dev_alloc(e, &Ly.up_wf, wf.size())) return rc;
-            if (int rc = dev_alloc(e, &Ly.up_c1, c1.size())) return rc;
-            if (int rc = dev_alloc(e, &Ly.up_b1, b1.size())) return rc;
-            HIP_TRY(hipMemcpy(Ly.up_wf, wf.data(), wf.size() * 2, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(Ly.up_c1, c1.data(), c1.size() * 4, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(Ly.up_b1, b1.data(), b1.size() * 4, hipMemcpyHostToDevice));
-            e->weight_bytes += (int64_t)wf.size() * 2 + (int64_t)c1.size() * 8;
-        }
-        {   // depthwise weight [hid,1,3,3] -> [9][hid]
-            auto it = e->host.find(LK("mlp.mlp.1.weight"));
-            if (it == e->host.end()) return fail(TLD_ERR_STATE, "state_dict entry missing: %s", key);
-            if ((int64_t)it->second.data.size() != hid * 9) return fail(TLD_ERR_SHAPE, "%s: bad size", key);
-            std::vector<float> tr((size_t)(hid * 9));
-            for (int64_t c = 0; c < hid; ++c)
-                for (int k = 0; k < 9; ++k) tr[(size_t)(k * hid + c)] = it->second.data[(size_t)(c * 9 + k)];
-            if (int rc = dev_alloc(e, &Ly.dw_w9c, (size_t)(hid * 9))) return rc;
-            HIP_TRY(hipMemcpy(Ly.dw_w9c, tr.data(), tr.size() * sizeof(float), hipMemcpyHostToDevice));
-            e->weight_bytes += (int64_t)tr.size() * 4;
-            // halved copies for the fused epilogue (its GELU is written for x / 2; scaling by 0.5 is exact)
-            std::vector<float> hb(e->host[LK("mlp.mlp.1.bias")].data);
-            for (float& v : tr) v *= 0.5f;
-            for (float& v : hb) v *= 0.5f;
-            if (int rc = dev_alloc(e, &Ly.dw_w9c_half, tr.size())) return rc;
-            if (int rc = dev_alloc(e, &Ly.dw_b_half, hb.size())) return rc;
-            HIP_TRY(hipMemcpy(Ly.dw_w9c_half, tr.data(), tr.size() * sizeof(float), hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(Ly.dw_b_half, hb.data(), hb.size() * sizeof(float), hipMemcpyHostToDevice));
-            e->weight_bytes += (int64_t)(tr.size() + hb.size()) * 4;
-            // packed bf16 tap pairs for the v_dot2c form: per window row du and channel c, with (w0, w1, w2) the halved
-            // taps of that row:  kind 0 = (lo 0, hi w0), 1 = (w1, w2), 2 = (w0, w1), 3 = (w2, 0)
-            std::vector<uint32_t> pk((size_t)(12 * hid));
-            for (int du = 0; du < 3; ++du)
-                for (int64_t c = 0; c < hid; ++c) {
-                    const uint32_t w0 = f32_to_bf16_rne(tr[(size_t)((du * 3 + 0) * hid + c)]);
-                    const uint32_t w1 = f32_to_bf16_rne(tr[(size_t)((du * 3 + 1) * hid + c)]);
-                    const uint32_t w2 = f32_to_bf16_rne(tr[(size_t)((du * 3 + 2) * hid + c)]);
-                    pk[(size_t)((du * 4 + 0) * hid + c)] = w0 << 16;
-                    pk[(size_t)((du * 4 + 1) * hid + c)] = w1 | (w2 << 16);
-                    pk[(size_t)((du * 4 + 2) * hid + c)] = w0 | (w1 << 16);
-                    pk[(size_t)((du * 4 + 3) * hid + c)] = w2;
-                }
-            if (int rc = dev_alloc(e, &Ly.dw_wpk, pk.size())) return rc;
-            HIP_TRY(hipMemcpy(Ly.dw_wpk, pk.data(), pk.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-            e->weight_bytes += (int64_t)pk.size() * 4;
-        }
-#undef LK
+        if (e->fold_ln3) { IMG(Ly.up_wf, hid * d) IMG(Ly.up_c1, hid) IMG(Ly.up_b1, hid) }
+        // depthwise taps [hid,1,3,3] -> [9][hid]; halved copies for the fused epilogue (its GELU is written for x / 2; scaling by 0.5 is exact); packed bf16
+        // tap pairs for the v_dot2c form
+        IMG(Ly.dw_w9c, 9 * hid) IMG(Ly.dw_w9c_half, 9 * hid) IMG(Ly.dw_b_half, hid) IMG(Ly.dw_wpk, 12 * hid)
     }
-    if (e->fold_tail && !e->fp8) {   // out_proj folded into the last block's down projection (tld_tail_fold_math.h; the refresh kernel computes the same bits)
-        snprintf(key, sizeof(key), "denoiser_trans_block.decoder_blocks.%d.mlp.mlp.3.weight", e->L - 1);
-        const std::vector<float>& Wd = e->host[key].data;                                                   // [d][hid]
-        snprintf(key, sizeof(key), "denoiser_trans_block.decoder_blocks.%d.mlp.mlp.3.bias", e->L - 1);
-        const std::vector<float>& bd = e->host[key].data;
-        const std::vector<float>& Wo = e->host["denoiser_trans_block.out_proj.0.weight"].data;              // [pd][d]
-        const std::vector<float>& bo = e->host["denoiser_trans_block.out_proj.0.bias"].data;
-        const int64_t pdp = tail_fold_padded_rows((int)pd), K = d + hid;
-        std::vector<uint16_t> img((size_t)(2 * pdp * K), 0);
-        std::vector<float> wf((size_t)hid), bf((size_t)pd);
-        std::vector<double> acc((size_t)hid);
-        for (int64_t f = 0; f < pd; ++f) {
-            const float* wo = &Wo[(size_t)(f * d)];
-            tail_fold_weight_row(wo, Wd.data(), (int)d, (int)hid, acc.data(), wf.data());
-            bf[(size_t)f] = tail_fold_bias(wo, bd.data(), bo[(size_t)f], (int)d);
-            for (int64_t k2 = 0; k2 < K; ++k2)
-                tail_fold_split(k2 < d ? wo[k2] : wf[(size_t)(k2 - d)], &img[(size_t)(f * K + k2)], &img[(size_t)((pdp + f) * K + k2)]);
-        }
-        if (int rc = dev_alloc(e, &e->out_fold_hl, img.size())) return rc;
-        if (int rc = dev_alloc(e, &e->out_fold_b, bf.size())) return rc;
-        HIP_TRY(hipMemcpy(e->out_fold_hl, img.data(), img.size() * 2, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(e->out_fold_b, bf.data(), bf.size() * 4, hipMemcpyHostToDevice));
-        e->weight_bytes += (int64_t)img.size() * 2 + (int64_t)bf.size() * 4;
+    if (e->fold_tail && !e->fp8) {   // out_proj folded into the last block's down projection (tld_tail_fold_math.h); rows pd .. pdp - 1 of the image stay zero
+        const size_t n = (size_t)(2 * tail_fold_padded_rows((int)pd) * (d + hid));
+        IMG(e->out_fold_hl, n) IMG(e->out_fold_b, pd)
+        HIP_TRY(hipMemsetAsync(e->out_fold_hl, 0, n * sizeof(bf16), nullptr));
+        R.tail_fold_hl = e->out_fold_hl; R.tail_fold_b = e->out_fold_b;
     }
-    e->host.clear();
+#undef IMG
     {   // per-layer pointer tables for the layer-batched conditioning launches
         const size_t L = (size_t)e->L;
-        std::vector<const float*> hk(L), hq(L), hg(L), hb(L);
-        for (size_t l = 0; l < L; ++l) { hk[l] = e->layers[l].kv_w; hq[l] = e->layers[l].q_w; hg[l] = e->layers[l].n2_w; hb[l] = e->layers[l].n2_b; }
+        std::vector<const float*> tab(4 * L);
+        for (size_t l = 0; l < L; ++l) { tab[l] = e->layers[l].kv_w; tab[L + l] = e->layers[l].q_w; tab[2 * L + l] = e->layers[l].n2_w; tab[3 * L + l] = e->layers[l].n2_b; }
         const float** tabs = nullptr;
         if (int rc = dev_alloc(e, &tabs, 4 * L)) return rc;
         e->tab_kv_w = tabs; e->tab_q_w = tabs + L; e->tab_n2_w = tabs + 2 * L; e->tab_n2_b = tabs + 3 * L;
-        HIP_TRY(hipMemcpy(e->tab_kv_w, hk.data(), L * sizeof(float*), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(e->tab_q_w, hq.data(), L * sizeof(float*), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(e->tab_n2_w, hg.data(), L * sizeof(float*), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(e->tab_n2_b, hb.data(), L * sizeof(float*), hipMemcpyHostToDevice));
-    }
-    {   // tld_engine_refresh_weights: the blocks' image pointers as a device table, and the images outside the blocks with their places in the flat vector
-        const ParamLayout pl = make_param_layout(e->d, e->L, e->ne, e->pd, e->hid, e->ntok, e->text);
-        RefreshPlan& R = e->refresh;
-        R = RefreshPlan();
-        R.d = e->d; R.hid = e->hid; R.L = e->L; R.l0 = pl.layers[0]; R.layer_stride = pl.layer_stride();
-        R.fold = e->fold_ln1 || e->fold_ln3; R.fp8 = e->fp8;
-        Layer* ld = nullptr;
-        if (int rc = dev_alloc(e, &ld, (size_t)e->L)) return rc;
-        HIP_TRY(hipMemcpy(ld, e->layers.data(), (size_t)e->L * sizeof(Layer), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(tabs, tab.data(), 4 * L * sizeof(float*), hipMemcpyHostToDevice));
+        Layer* ld = nullptr;      // the blocks' image pointers as a device table (the refresh kernels index it by blockIdx.z)
+        if (int rc = dev_alloc(e, &ld, L)) return rc;
+        HIP_TRY(hipMemcpy(ld, e->layers.data(), L * sizeof(Layer), hipMemcpyHostToDevice));
         R.layers_dev = ld;
-        auto job = [&R](void* dst, int64_t src, int64_t n, int kind = RJ_COPY, int cols = 0) { if (dst) R.jobs[R.njobs++] = RefreshJob{dst, src, n, kind, cols}; };
-        job(e->ff1_w, pl.ff1w, d * ne); job(e->ff1_b, pl.ff1b, d); job(e->ff3_w, pl.ff3w, d * d); job(e->ff3_b, pl.ff3b, d);
-        job(e->label_w, pl.lbw, d * text); job(e->label_b, pl.lbb, d); job(e->norm_w, pl.nw, d); job(e->norm_b, pl.nb, d);
-        job(e->conv_w, pl.cvw, pd * cpp); job(e->conv_b, pl.cvb, pd); job(e->pln1_w, pl.l1w, pd); job(e->pln1_b, pl.l1b, pd);
-        job(e->plin_b, pl.lib, d); job(e->pln2_w, pl.l2w, d); job(e->pln2_b, pl.l2b, d); job(e->pos, pl.pos, N * d);
-        job(e->out_w, pl.outw, pd * d); job(e->out_b, pl.outb, pd);
-        job(e->out_w_hl, pl.outw, pd * d, RJ_SPLIT_HL); job(e->plin_w_hl, pl.liw, d * pd, RJ_SPLIT_HL);
-        job(e->plin_wt, pl.liw, d * pd, RJ_TRANSPOSE, (int)pd);
-        static_assert(kRefreshMaxJobs >= 21, "the images outside the blocks");
-        R.tail_fold_hl = e->out_fold_hl; R.tail_fold_b = e->out_fold_b; R.outw = pl.outw; R.outb = pl.outb; R.pd = e->pd;
+    }
+    {   // the loaded values as a temporary flat vector (outside the arena: freed before the activations are allocated), and the one refresh
+        struct Flat { float* p = nullptr; ~Flat() { if (p) (void)hipFree(p); } } flat;
+        HIP_TRY(hipMalloc(&flat.p, (size_t)pl.count * sizeof(float)));
+        for (const ParamTensor& q : pl.tensors)
+            HIP_TRY(hipMemcpy(flat.p + q.off, e->host[q.key].data.data(), (size_t)q.numel * sizeof(float), hipMemcpyHostToDevice));
+        e->host.clear();
+        if (int rc = launch_refresh_weights(R, flat.p, nullptr)) return rc;
+        HIP_TRY(hipStreamSynchronize(nullptr));
     }
 
     const size_t B2 = (size_t)e->cfg.max_batch, M = B2 * e->ntok;

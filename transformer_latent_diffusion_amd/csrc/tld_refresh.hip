@@ -1,12 +1,15 @@
-// tld_refresh.hip -- every weight image of a finalized inference engine, rebuilt on the device from a flat fp32 parameter vector
-// (tld_engine_refresh_weights).
+// tld_refresh.hip -- every weight image of the inference engine, built on the device from a flat fp32 parameter vector: THE one builder, run by
+// tld_engine_finalize_weights on the loaded state dict and by tld_engine_refresh_weights on a caller's vector.
 //
-// One device counterpart per branch of tld_engine_finalize_weights, writing into the buffers finalize allocated, and BIT-EQUAL to what the host
-// loops there compute -- the tests compare the engine's operands with ==.  What that takes:
-//   * one bf16 and one e4m3 rounding for host and device, in integer arithmetic (tld_refresh_math.h), no hardware convert;
-//   * the two double-precision sums of a LayerNorm fold are taken per output row in the host's order, k = 0 .. d - 1, one add per element: one lane
-//     walks one row (refresh_fold_kernel).  A tree would change the last bit of float(sum) once in some tens of millions of elements;
+// The kernels write into the buffers finalize allocated (a null pointer: an image this engine's mode does not hold).  Every image is DEFINED to the bit,
+// and tests/weight_image_refs.py restates each definition in numpy; tests/test_gpu_weight_refresh.py compares the engine's images with it using ==.
+// What the definitions fix:
+//   * one bf16 and one e4m3 rounding, in integer arithmetic (tld_refresh_math.h; the host's f32_to_bf16_rne and quant_mx8_host round alike), no hardware
+//     convert;
+//   * the two double-precision sums of a LayerNorm fold are sequential per output row, k = 0 .. d - 1, one add per element: one lane walks one row
+//     (refresh_fold_kernel).  A tree would change the last bit of float(sum) once in some tens of millions of elements;
 //   * contraction is off in every kernel here (a product of two fp32 values is exact in double, so it could not change the sums; pinned anyway).
+// No kernel reads the vector past its last parameter: 16-byte loads are taken only where the element count and both addresses allow them.
 // Up to five launches per refresh: the images outside the blocks, the blocks' elementwise images, the folds, the folded out_proj operand, the e4m3 images; the blocks sit a constant
 // stride apart in the flat vector, so the last three take the block index from blockIdx.z.  All stores are ordinary vector stores.
 #include "tld_common.h"
@@ -131,7 +134,7 @@ __global__ __launch_bounds__(256) void refresh_layer_kernel(const Layer* __restr
 //   c1[n]    = (float) sum_k double(float(wf[n][k]))
 //   b1[n]    = (float) (sum_k double(be[k]) * double(W[n][k])  [+ double(up_b[n]) for LayerNorm-3])
 // One wave owns 64 rows.  Per 64-column tile: lane j loads column j of the 64 rows (256-byte coalesced runs), stores wf (and its packed copy) and parks
-// W in LDS; then lane r walks row r of the tile in k order, re-deriving wf from g (an LDS broadcast) -- so both sums are the host's sequential sums.
+// W in LDS; then lane r walks row r of the tile in k order, re-deriving wf from g (an LDS broadcast) -- so both sums are the sequential sums of the definition.
 // The pitch of 65 floats keeps the walk (lane r at word 65 r + k) off bank conflicts.
 __global__ __launch_bounds__(64) void refresh_fold_kernel(const Layer* __restrict__ layers, const float* __restrict__ flat, LayerOffsets o, int64_t stride, int d,
                                                           int hid) {
@@ -188,7 +191,7 @@ __global__ __launch_bounds__(64) void refresh_fold_kernel(const Layer* __restric
 }
 
 // ---- out_proj folded into the last block's down projection: the split bf16 image of [Wout | Wout Wd] and b' = Wout bd + bo -----------------------
-// One thread per element, each walking its own sum in the host's order (tld_tail_fold_math.h is the one spelling of both).  Consecutive threads take
+// One thread per element, each walking its own sum k-ascending (tld_tail_fold_math.h spells the arithmetic).  Consecutive threads take
 // consecutive columns j, so the reads of Wd[k][j] are coalesced and Wout[f][k] is a broadcast.  Items: pd hid folded weights | pd d copies of Wout | pd biases.
 __global__ __launch_bounds__(256) void refresh_tail_fold_kernel(bf16* __restrict__ img_, float* __restrict__ bias, const float* __restrict__ wout,
                                                                 const float* __restrict__ bo, const float* __restrict__ wd, const float* __restrict__ bd,
@@ -245,7 +248,7 @@ __device__ __forceinline__ void quant_mx8_f32_rows(const float* __restrict__ in,
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             float v = f[e] * inv;
-            v = v < -448.f ? -448.f : (v > 448.f ? 448.f : v);                    // (a NaN passes, as on the host)
+            v = v < -448.f ? -448.f : (v > 448.f ? 448.f : v);                    // (a NaN passes, as in quant_mx8_host)
             w[e >> 2] |= (uint32_t)e4m3_rne_bits(__float_as_uint(v)) << ((e & 3) * 8);
         }
         *reinterpret_cast<uint2*>(out + (int64_t)row * K + k0) = make_uint2(w[0], w[1]);

@@ -92,7 +92,7 @@ inline int decode_stage(const void* raw, const void* aux_raw, int dtype, int lay
         for (int64_t b = 0; b < B; ++b)
             for (int64_t p = 0; p < HW; ++p)
                 for (int64_t c = 0; c < C; ++c) out[(b * C + c) * HW + p] = load((b * HW + p) * C + c);
-    } else if (layout == SL_QKV_ROWS && !x.outer_stride) {      // the inverse of the packing in finalize_weights
+    } else if (layout == SL_QKV_ROWS && !x.outer_stride) {      // the inverse of the packing in refresh_fold_kernel
         const int64_t d = x.d, row = shape4[0] ? n / shape4[0] : 0;
         if (d <= 0 || d != (int64_t)x.heads * 64 || shape4[0] != 3 * d) return fail(TLD_ERR_INVALID, "decode_stage: packed QKV rows need shape[0] = 3 d and d = 64 heads");
         for (int64_t h = 0; h < x.heads; ++h)

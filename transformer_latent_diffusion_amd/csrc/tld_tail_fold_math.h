@@ -1,5 +1,5 @@
 // tld_tail_fold_math.h -- out_proj folded into the last block's down projection: the arithmetic of the folded
-// operand, one spelling for tld_engine_finalize_weights (host) and the device weight refresh (tld_refresh.hip), which must give the same bits.
+// operand, as refresh_tail_fold_kernel (tld_refresh.hip) builds it; tests/test_tail_fold_host.py holds it on the host against a float64 restatement.
 //   W'[f][j] = (float) sum_k double(Wout[f][k]) * double(float(bf16(Wd[k][j])))          [pd x hid]
 //   b'[f]    = (float) (sum_k double(Wout[f][k]) * double(bd[k]) + double(bo[f]))
 // Sums in double, k = 0 .. d - 1 ascending, one add per element.  A product of two fp32 values is exact in double, so contraction could not change
@@ -55,21 +55,6 @@ TLD_HD float tail_fold_weight(const float* wout_row, const float* wd, int d, int
         s += (double)wout_row[k] * (double)q;
     }
     return (float)s;
-}
-
-// Row f of W' in one pass over Wd (host): acc [hid] doubles of scratch.  Element j sees the same products in the same order as tail_fold_weight(.., j)
-// -- k ascending, one add per k -- so the bits are the same; the walk is along the rows of Wd instead of down its columns.
-inline void tail_fold_weight_row(const float* wout_row, const float* wd, int d, int hid, double* acc, float* out) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
-    for (int j = 0; j < hid; ++j) acc[j] = 0.0;
-    for (int k = 0; k < d; ++k) {
-        const double w = (double)wout_row[k];
-        const float* row = wd + (int64_t)k * hid;
-        for (int j = 0; j < hid; ++j) acc[j] += w * (double)tail_fold_f32_from_bits((uint32_t)bf16_rne_bits(tail_fold_bits(row[j])) << 16);
-    }
-    for (int j = 0; j < hid; ++j) out[j] = (float)acc[j];
 }
 
 // b'[f]
