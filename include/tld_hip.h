@@ -642,6 +642,44 @@ TLD_API int tld_train_grad_guard(tld_train* e, const float* grads, int64_t numel
 TLD_API int tld_train_adam_ema_guarded(tld_train* e, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t numel,
                                        float lr, float beta1, float beta2, float eps, float ema_alpha, float grad_scale, const double* opt_state,
                                        void* hip_stream);
+/* The grouped optimizer step: torch.optim.AdamW (decoupled weight decay) with parameter groups, a learning-rate schedule that follows the steps
+ * APPLIED (LambdaLR behind accelerate's scheduler wrapper: no advance on a skipped step) and frozen tensors, behind the same guard.  A plan
+ * describes the flat vector once: segment s (a tensor) has seg_numel[s] >= 1 elements -- the segments tile [0, numel) in order, any length, also not
+ * a multiple of 4 -- and belongs to groups[seg_group[s]] = (lr_scale, weight_decay, frozen).  tld_opt_plan_create cuts every segment from its first
+ * element into chunks of at most 8192 elements (a constant: not a function of the CU count; no chunk spans two segments), uploads the tables once
+ * and owns the partial sums; a step allocates nothing and synchronises nothing.  lr_factors[n_factors] (may be NULL with n_factors = 0: factor 1):
+ * applied step t = 1, 2, ... runs at factor lr_factors[min(t, n_factors) - 1].
+ * opt_state is tld_train_grad_guard's vector with the same head; [7] holds the schedule factor, [8 ..] is not used by these calls.
+ * tld_train_grad_guard_grouped, in double, fixed order, no atomics (bitwise repeatable on any CU count):
+ *   partial[c] = sum over chunk c of (grads[i] * grad_scale)^2       (per thread as tld_train_grad_guard, then the fixed 256-lane tree)
+ *   seg[s]     = partial[c] added in chunk order over the chunks of segment s       -> tld_opt_plan_segment_sqsums (frozen segments included)
+ *   sum        = seg[s] added in segment order over the segments whose group is NOT frozen;  norm = sqrt(sum);  nonfinite = !isfinite(sum)
+ *   if (skip_nonfinite && nonfinite)  skipped += 1; last_skipped = 1; coef = 0;  t, bc1, bc2 and [7] unchanged
+ *   else  last_skipped = 0; t += 1; c = max_norm / (norm + 1e-6); coef = clip ? (c > 1 ? 1 : c) : 1;  bc1, bc2 from the new t;
+ *         [7] = (double)lr_factors[min(t, n_factors) - 1] with the new t, or 1.0 without a table
+ * tld_train_adamw_ema_grouped: a skipped step touches nothing; an element of a frozen group is neither read nor written (params, moments, EMA);
+ * every other element i of group q, with bc1 / bc2 / coef read from opt_state:
+ *   lr_q = (float)((double)lr * (double)lr_scale_q * [7]);   gi = (grads[i] * grad_scale) * (float)coef;   m, v as tld_train_adam_ema_guarded
+ *   p = p * (1.0f - lr_q * wd_q)                  (AdamW: param.mul_(1 - lr * weight_decay); a product of its own, exact when wd_q = 0)
+ *   p = p - (lr_q / bc1) * (m / (sqrtf(v) / sqrtf(bc2) + eps));   ema = ema * alpha + p * (1 - alpha)   (ema may be NULL)
+ * so one group (1, 0, not frozen) without a table gives tld_train_adam_ema_guarded's bits.  A plan whose groups are all frozen is legal: norm 0,
+ * the step counts and nothing else changes.
+ * TLD_ERR_INVALID with a text naming the offending index, before any HIP call in tld_opt_plan_create: a null pointer, n_seg < 1, a segment length
+ * < 1, n_groups outside 1 .. 256, a seg_group out of range, an lr_scale / weight_decay / factor that is negative or not finite, frozen not 0 / 1,
+ * n_factors < 0 or > 0 with a null table, a total length over 2^40, more than 2^30 chunks; in the two step calls: a null pointer, numel !=
+ * tld_opt_plan_numel, NaN max_norm, vectors not 16-byte or opt_state not 8-byte aligned.  A refusal enqueues nothing. */
+typedef struct tld_opt_group { float lr_scale; float weight_decay; int32_t frozen; int32_t reserved; } tld_opt_group;
+typedef struct tld_opt_plan tld_opt_plan;
+TLD_API int tld_opt_plan_create(int32_t device, const int64_t* seg_numel, const int32_t* seg_group, int32_t n_seg, const tld_opt_group* groups,
+                                int32_t n_groups, const float* lr_factors, int64_t n_factors, tld_opt_plan** out);
+TLD_API void tld_opt_plan_destroy(tld_opt_plan* p);
+TLD_API int64_t tld_opt_plan_numel(const tld_opt_plan* p);
+TLD_API int tld_opt_plan_segment_sqsums(const tld_opt_plan* p, const double** device_ptr);        /* device double [n_seg], of the last guard call */
+TLD_API int tld_train_grad_guard_grouped(tld_opt_plan* p, const float* grads, int64_t numel, float grad_scale, double max_norm, int32_t skip_nonfinite,
+                                         float beta1, float beta2, double* opt_state, void* hip_stream);
+TLD_API int tld_train_adamw_ema_grouped(tld_opt_plan* p, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t numel,
+                                        float lr, float beta1, float beta2, float eps, float ema_alpha, float grad_scale, const double* opt_state,
+                                        void* hip_stream);
 /* The training batch of one step, built on the device from a resident dataset (tld/train.py:121-138 without the host):
  * gather rows idx[b] of the source, draw noise, noise level and label mask from Philox4x32-10 and mix.  One kernel on hip_stream; nothing is
  * allocated, nothing synchronises.  e may be NULL (the device is that of x_noisy).

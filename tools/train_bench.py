@@ -5,6 +5,8 @@ Prints one JSON line in bench.py's vocabulary.   tools/train_bench.py [--batch 1
 [--patch-size 2] [--no-cpu-baseline] [--max-grad-norm X] [--skip-nonfinite]   (the last two: the guarded optimizer step, to time beside the plain one;
 --image-size: the latent side, e.g. 48 = 576 tokens, the 384 px fine-tuning grid; the TFLOP/s figures
 are quoted at the default 32 only, where the op count below applies)
+--weight-decay W / --freeze GLOB (repeatable) / --lr-warmup N: the grouped optimizer step (AdamW with the usual no-decay exemptions, frozen tensors, a
+warm-up on the applied steps: DESIGN.md section 7.3); every run also reports the optimizer part alone in HIP-event time ("optimizer_ms_events")
 --device-data [--latent-dtype uint8|float16|float32]: the same model and batch size through train_step (host make_batch + pinned staging) and through
 train_step_from (a device-resident dataset, one preparation kernel: DESIGN.md section 7.11) in one process; one JSON line with both."""
 import argparse
@@ -29,6 +31,9 @@ ap.add_argument("--patch-size", type=int, default=2)
 ap.add_argument("--no-cpu-baseline", action="store_true")
 ap.add_argument("--max-grad-norm", type=float, default=None)
 ap.add_argument("--skip-nonfinite", action="store_true")
+ap.add_argument("--weight-decay", type=float, default=0.0)
+ap.add_argument("--freeze", action="append", default=[])
+ap.add_argument("--lr-warmup", type=int, default=0)
 ap.add_argument("--device-data", action="store_true")
 ap.add_argument("--latent-dtype", choices=("uint8", "float16", "float32"), default="uint8")
 args = ap.parse_args()
@@ -39,7 +44,14 @@ cfg = config_100m(S)
 cfg.patch_size = args.patch_size
 cfg.n_layers = args.layers
 tc = TrainConfig(batch_size=args.batch)
-tr = Trainer(cfg, tc, device=dev, init_seed=5, max_batch=args.batch, max_grad_norm=args.max_grad_norm, skip_nonfinite=args.skip_nonfinite)
+grouped = {}
+if args.weight_decay or args.freeze or args.lr_warmup:
+    from transformer_latent_diffusion_amd import opt_groups, param_layout
+    specs = [dict(match=args.freeze, frozen=True)] if args.freeze else []
+    grouped = dict(weight_decay=args.weight_decay, param_groups=specs + (opt_groups.no_decay(param_layout(cfg)) if args.weight_decay else []))
+    if args.lr_warmup:
+        grouped.update(lr_schedule=opt_groups.warmup_constant(args.lr_warmup), schedule_steps=args.lr_warmup)
+tr = Trainer(cfg, tc, device=dev, init_seed=5, max_batch=args.batch, max_grad_norm=args.max_grad_norm, skip_nonfinite=args.skip_nonfinite, **grouped)
 g = torch.Generator().manual_seed(1)
 x = torch.randn(args.batch, 4, S, S, generator=g) * 0.8
 y = torch.randn(args.batch, 768, generator=g) * 0.5
@@ -133,7 +145,21 @@ line = {"metric": f"training samples/sec (100M denoiser, {S}x{S}x4 latents, fwd 
         "loss": float(loss), "algorithmic_tflops": step_tflop / ddt, "frac_of_bf16_mfma_peak": step_tflop / ddt / 2500.0,
         "roofline": {"bound": "mfma", "achieved": step_tflop / ddt, "peak": 2500.0, "unit": "TFLOP/s", "frac": step_tflop / ddt / 2500.0,
                      "note": "whole step (3 x the reference forward op count) over the device-only step time; per-kernel times: profiles/r05_train_kernel_stats.csv (rocprofv3 --kernel-trace --stats of this tool)"}}
-if tr.guarded:
+# the optimizer part alone on the last step's gradients, HIP events around single calls; a matrix product is queued first so that the host has
+# enqueued the launches and both events before the device reaches them
+opt_times, wm = [], torch.randn(4096, 4096, device=dev)
+for i in range(25):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    wm @ wm
+    a.record(); tr.optimizer_step(); b.record()
+    b.synchronize()
+    opt_times.append(a.elapsed_time(b))
+line["optimizer_ms_events"] = sorted(opt_times[5:])[len(opt_times[5:]) // 2]
+if getattr(tr, "grouped", False):
+    frozen = sum(n for n, q in zip(tr._seg_numel, tr._seg_group) if tr._groups[q][2])
+    line["optimizer_groups"] = {"weight_decay": args.weight_decay, "freeze": args.freeze, "lr_warmup": args.lr_warmup, "groups": len(tr._groups),
+                                "frozen_fraction": frozen / tr.numel}
+if tr.guarded or getattr(tr, "grouped", False):
     line["optimizer_guard"] = dict(tr.optimizer_stats(), max_grad_norm=args.max_grad_norm, skip_nonfinite=args.skip_nonfinite)
 if not args.no_cpu_baseline:
     from oracle.torch_ref import train_step_reference

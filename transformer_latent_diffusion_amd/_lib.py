@@ -38,7 +38,9 @@ ABI_SYMBOLS = (
     "tld_clip_vis_create", "tld_clip_vis_load_tensor", "tld_clip_vis_finalize_weights", "tld_clip_vis_encode_image", "tld_clip_vis_set_debug", "tld_clip_vis_read_stage",
     "tld_clip_vis_weight_bytes", "tld_clip_vis_destroy", "tld_debug_clip_vis_attention",
     "tld_train_create", "tld_train_param_count", "tld_train_tensor_count", "tld_train_param_layout", "tld_train_set_angular_speeds", "tld_train_bind",
-    "tld_train_refresh_weights", "tld_train_forward_backward", "tld_train_forward_backward_cb", "tld_train_adam_ema", "tld_train_grad_guard", "tld_train_adam_ema_guarded", "tld_train_prepare_batch", "tld_train_prepare_batch_at",
+    "tld_train_refresh_weights", "tld_train_forward_backward", "tld_train_forward_backward_cb", "tld_train_adam_ema", "tld_train_grad_guard", "tld_train_adam_ema_guarded",
+    "tld_opt_plan_create", "tld_opt_plan_destroy", "tld_opt_plan_numel", "tld_opt_plan_segment_sqsums", "tld_train_grad_guard_grouped", "tld_train_adamw_ema_grouped",
+    "tld_train_prepare_batch", "tld_train_prepare_batch_at",
     "tld_train_forward_loss", "tld_train_sample_loss", "tld_train_loss_buckets", "tld_debug_attention_bwd", "tld_debug_wgrad", "tld_debug_attention_fwd", "tld_debug_dwconv_gelu",
     "tld_train_set_debug", "tld_train_read_stage", "tld_train_debug_paths", "tld_train_destroy",
     "tld_last_error",
@@ -81,6 +83,11 @@ class TldBatchSource(C.Structure):
     _fields_ = [("latents", C.c_void_p), ("labels", C.c_void_p), ("dequant_table", C.c_void_p), ("rows", C.c_int64),
                 ("latent_dtype", C.c_int32), ("label_dtype", C.c_int32), ("latent_elems", C.c_int32), ("text_emb", C.c_int32),
                 ("vae_scale", C.c_float)]
+
+
+class TldOptGroup(C.Structure):
+    """tld_opt_group (include/tld_hip.h): one parameter group of a tld_opt_plan."""
+    _fields_ = [("lr_scale", C.c_float), ("weight_decay", C.c_float), ("frozen", C.c_int32), ("reserved", C.c_int32)]
 
 
 class TldClipConfig(C.Structure):
@@ -234,6 +241,15 @@ def lib() -> C.CDLL:
     if hasattr(L, "tld_train_grad_guard"):           # (absent from A/B builds that predate the guarded optimizer step)
         L.tld_train_grad_guard.argtypes = [vp, vp, C.c_int64, f32, C.c_double, i32, f32, f32, vp, vp]
         L.tld_train_adam_ema_guarded.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64, f32, f32, f32, f32, f32, f32, vp, vp]
+    if hasattr(L, "tld_opt_plan_create"):            # (absent from A/B builds that predate the grouped optimizer step)
+        L.tld_opt_plan_create.argtypes = [i32, i64p, C.POINTER(i32), i32, C.POINTER(TldOptGroup), i32, C.POINTER(f32), C.c_int64, C.POINTER(vp)]
+        L.tld_opt_plan_destroy.argtypes = [vp]
+        L.tld_opt_plan_destroy.restype = None
+        L.tld_opt_plan_numel.argtypes = [vp]
+        L.tld_opt_plan_numel.restype = C.c_int64
+        L.tld_opt_plan_segment_sqsums.argtypes = [vp, C.POINTER(vp)]
+        L.tld_train_grad_guard_grouped.argtypes = [vp, vp, C.c_int64, f32, C.c_double, i32, f32, f32, vp, vp]
+        L.tld_train_adamw_ema_grouped.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64, f32, f32, f32, f32, f32, f32, vp, vp]
     if hasattr(L, "tld_train_prepare_batch"):        # (absent from A/B builds that predate the device batch preparation)
         L.tld_train_prepare_batch.argtypes = [vp, C.POINTER(TldBatchSource), vp, i32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_double, C.c_double, f32,
                                               vp, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -255,7 +271,7 @@ def lib() -> C.CDLL:
         if "TLD_LIB" in os.environ and not hasattr(L, name):     # an older A/B build: symbols added since are simply absent (tests/test_abi.py checks the real library)
             continue
         if name not in ("tld_last_error", "tld_engine_weight_bytes", "tld_vae_weight_bytes", "tld_vae_enc_weight_bytes", "tld_clip_weight_bytes", "tld_clip_vis_weight_bytes", "tld_train_param_count",
-                        "tld_train_tensor_count", "tld_engine_param_count"):
+                        "tld_train_tensor_count", "tld_engine_param_count", "tld_opt_plan_numel", "tld_opt_plan_destroy"):
             getattr(L, name).restype = C.c_int
     _lib = L
     return L

@@ -15,6 +15,7 @@
 #include "tld_train_kernels.h"
 #include "tld_host.h"
 #include "tld_param_layout.h"
+#include "tld_opt_plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -825,6 +826,113 @@ int tld_train_adam_ema_guarded(tld_train* e, float* params, const float* grads, 
                            grad_scale, opt_state);
     HIP_TRY(hipGetLastError());
     if (e && params == e->params) e->weights_fresh = false;          // the bf16 operand copies are stale now (a skipped step rebuilds the same ones)
+    return TLD_OK;
+}
+
+/* ---- the grouped optimizer step (contract: include/tld_hip.h; the cut: tld_opt_plan.h) ------------------------------------------------- */
+struct tld_opt_plan {
+    int device = 0;
+    int64_t numel = 0, n_factors = 0;
+    int32_t n_seg = 0, n_chunks = 0;
+    OptChunkDev* chunks = nullptr;         // [n_chunks]
+    double* part = nullptr;                // [n_chunks] partial sums of squares of the last guard call
+    int32_t* seg_chunk0 = nullptr;         // [n_seg + 1]
+    unsigned char* seg_frozen = nullptr;   // [n_seg]
+    double* seg_sq = nullptr;              // [n_seg] per-segment sums of the last guard call
+    float* lr_factors = nullptr;           // [n_factors]
+};
+
+static_assert(sizeof(tld_opt_group) == sizeof(OptGroup), "tld_opt_group of include/tld_hip.h and OptGroup of tld_opt_plan.h are one layout");
+
+void tld_opt_plan_destroy(tld_opt_plan* p) {
+    if (!p) return;
+    DeviceGuard dg(p->device);
+    for (void* q : {(void*)p->chunks, (void*)p->part, (void*)p->seg_chunk0, (void*)p->seg_frozen, (void*)p->seg_sq, (void*)p->lr_factors})
+        if (q) (void)hipFree(q);
+    delete p;
+}
+
+int tld_opt_plan_create(int32_t device, const int64_t* seg_numel, const int32_t* seg_group, int32_t n_seg, const tld_opt_group* groups, int32_t n_groups,
+                        const float* lr_factors, int64_t n_factors, tld_opt_plan** out) {
+    const std::string why = opt_plan_check(seg_numel, seg_group, n_seg, reinterpret_cast<const OptGroup*>(groups), n_groups, lr_factors, n_factors, out);
+    if (!why.empty()) return fail(TLD_ERR_INVALID, "opt plan: %s", why.c_str());
+    *out = nullptr;
+    if (device < 0) return fail(TLD_ERR_INVALID, "opt plan: device %d", device);
+    if (opt_chunk_count(seg_numel, n_seg) > (int64_t)1 << 30)
+        return fail(TLD_ERR_INVALID, "opt plan: %lld chunks (at most 2^30)", (long long)opt_chunk_count(seg_numel, n_seg));
+    const OptCut cut = opt_cut(seg_numel, n_seg);
+    std::vector<OptChunkDev> rec(cut.chunks.size());
+    for (size_t c = 0; c < rec.size(); ++c) {
+        const OptChunk& k = cut.chunks[c];
+        const tld_opt_group& q = groups[seg_group[k.seg]];
+        rec[c] = OptChunkDev{(long long)k.first, k.len, k.seg, q.lr_scale, q.weight_decay, q.frozen, 0};
+    }
+    std::vector<int32_t> c0(cut.seg_chunk0.begin(), cut.seg_chunk0.end());
+    std::vector<unsigned char> frozen((size_t)n_seg);
+    for (int32_t s = 0; s < n_seg; ++s) frozen[(size_t)s] = (unsigned char)groups[seg_group[s]].frozen;
+    tld_opt_plan* p = new tld_opt_plan();
+    p->device = device; p->numel = cut.numel; p->n_factors = n_factors; p->n_seg = n_seg; p->n_chunks = (int32_t)rec.size();
+    DeviceGuard dg(device);
+    auto up = [](auto** dst, const void* src, size_t bytes) {
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(dst), bytes ? bytes : 16);
+        if (e == hipSuccess && src && bytes) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess && !src) e = hipMemset(*dst, 0, bytes ? bytes : 16);
+        return e;
+    };
+    hipError_t e = up(&p->chunks, rec.data(), rec.size() * sizeof(OptChunkDev));
+    if (e == hipSuccess) e = up(&p->part, nullptr, rec.size() * sizeof(double));
+    if (e == hipSuccess) e = up(&p->seg_chunk0, c0.data(), c0.size() * sizeof(int32_t));
+    if (e == hipSuccess) e = up(&p->seg_frozen, frozen.data(), frozen.size());
+    if (e == hipSuccess) e = up(&p->seg_sq, nullptr, (size_t)n_seg * sizeof(double));
+    if (e == hipSuccess && n_factors > 0) e = up(&p->lr_factors, lr_factors, (size_t)n_factors * sizeof(float));
+    if (e != hipSuccess) {
+        tld_opt_plan_destroy(p);
+        return fail(TLD_ERR_HIP, "opt plan: uploading the tables failed: %s", hipGetErrorString(e));
+    }
+    *out = p;
+    return TLD_OK;
+}
+
+int64_t tld_opt_plan_numel(const tld_opt_plan* p) { return p ? p->numel : 0; }
+
+int tld_opt_plan_segment_sqsums(const tld_opt_plan* p, const double** device_ptr) {
+    if (!p || !device_ptr) return fail(TLD_ERR_INVALID, "opt plan: null plan or result pointer");
+    *device_ptr = p->seg_sq;
+    return TLD_OK;
+}
+
+/* tld_train_grad_guard over the plan's chunks: one partial per chunk, per-segment sums in chunk order, the global sum over the segments that
+ * are not frozen in segment order, then the finalize rule and the schedule factor -- two launches on the stream, nothing allocated. */
+int tld_train_grad_guard_grouped(tld_opt_plan* p, const float* grads, int64_t numel, float grad_scale, double max_norm, int32_t skip_nonfinite,
+                                 float beta1, float beta2, double* opt_state, void* hip_stream) {
+    if (!p || !grads || !opt_state) return fail(TLD_ERR_INVALID, "grouped grad guard: null plan, gradient or state pointer");
+    if (numel != p->numel) return fail(TLD_ERR_INVALID, "grouped grad guard: numel %lld, the plan covers %lld", (long long)numel, (long long)p->numel);
+    if (std::isnan(max_norm)) return fail(TLD_ERR_INVALID, "grouped grad guard: max_norm is NaN (<= 0 or +inf: no clipping)");
+    if (((uintptr_t)grads & 15) || ((uintptr_t)opt_state & 7))
+        return fail(TLD_ERR_INVALID, "grouped grad guard: grads must be 16-byte and opt_state 8-byte aligned");
+    DeviceGuard dg(p->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    const int clip = max_norm > 0.0 && !std::isinf(max_norm);
+    hipLaunchKernelGGL(seg_sqsum_kernel, dim3((unsigned)p->n_chunks), dim3(256), 0, s, grads, p->chunks, grad_scale, p->part);
+    hipLaunchKernelGGL(grouped_guard_finalize_kernel, dim3(1), dim3(OPT_FIN_THREADS), 0, s, opt_state, p->part, p->seg_chunk0, p->seg_frozen, p->seg_sq, p->n_seg,
+                       p->lr_factors, (long long)p->n_factors, max_norm, clip, skip_nonfinite ? 1 : 0, beta1, beta2);
+    HIP_TRY(hipGetLastError());
+    return TLD_OK;
+}
+
+/* AdamW + EMA by group behind the grouped guard: one workgroup per chunk of the plan. */
+int tld_train_adamw_ema_grouped(tld_opt_plan* p, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t numel, float lr,
+                                float beta1, float beta2, float eps, float ema_alpha, float grad_scale, const double* opt_state, void* hip_stream) {
+    if (!p || !params || !grads || !exp_avg || !exp_avg_sq || !opt_state) return fail(TLD_ERR_INVALID, "grouped adamw: null plan, vector or state pointer");
+    if (numel != p->numel) return fail(TLD_ERR_INVALID, "grouped adamw: numel %lld, the plan covers %lld", (long long)numel, (long long)p->numel);
+    if (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)ema) & 15)
+        return fail(TLD_ERR_INVALID, "grouped adamw: params, grads, exp_avg, exp_avg_sq and ema must be 16-byte aligned");
+    if ((uintptr_t)opt_state & 7) return fail(TLD_ERR_INVALID, "grouped adamw: opt_state must be 8-byte aligned");
+    DeviceGuard dg(p->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    hipLaunchKernelGGL(adamw_ema_grouped_kernel, dim3((unsigned)p->n_chunks), dim3(256), 0, s, params, grads, exp_avg, exp_avg_sq, ema, p->chunks, lr, beta1, beta2,
+                       eps, ema_alpha, grad_scale, opt_state);
+    HIP_TRY(hipGetLastError());
     return TLD_OK;
 }
 

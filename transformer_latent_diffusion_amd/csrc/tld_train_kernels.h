@@ -1253,6 +1253,166 @@ __global__ __launch_bounds__(256) void adam_ema_guarded_kernel(float* __restrict
     }
 }
 
+// ---- grouped optimizer step: AdamW with per-tensor groups, an lr schedule on the APPLIED steps, frozen tensors (include/tld_hip.h) ---------------
+// One record per chunk of tld_opt_plan.h's cut with its group's parameters folded in, so a workgroup learns all it needs from ONE 32-byte read.
+struct OptChunkDev { long long first; int len; int seg; float lr_scale; float weight_decay; int frozen; int pad; };
+static_assert(sizeof(OptChunkDev) == 32, "one 32-byte record per chunk");
+
+// elements [first, first + len) of a 16-byte aligned vector: head scalars up to the next 16-byte boundary, nvec float4, tail scalars
+__device__ inline void opt_chunk_split(long long first, int len, int& head, int& nvec, int& tail) {
+    head = (int)((4 - (first & 3)) & 3);
+    if (head > len) head = len;
+    nvec = (len - head) >> 2;
+    tail = len - head - 4 * nvec;
+}
+
+// part[c] = sum over chunk c of (g[i] * grad_scale)^2: grad_sqsum_kernel's arithmetic (double products, four accumulators by vector component,
+// the scalar head and tail into the first, the fixed 256-lane tree), one workgroup per chunk.  Frozen segments are summed too: their norms are read out.
+__global__ __launch_bounds__(256) void seg_sqsum_kernel(const float* __restrict__ g, const OptChunkDev* __restrict__ chunks, float grad_scale,
+                                                        double* __restrict__ part) {
+    __shared__ double sh[256];
+    const OptChunkDev c = chunks[blockIdx.x];
+    int head, nvec, tail;
+    opt_chunk_split(c.first, c.len, head, nvec, tail);
+    const double sc = (double)grad_scale;
+    const float* gc = g + c.first;
+    const float4* g4 = reinterpret_cast<const float4*>(gc + head);
+    const int t = threadIdx.x;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+#pragma unroll 4
+    for (int k = t; k < nvec; k += 256) {
+        const float4 q = g4[k];
+        const double x = (double)q.x * sc, y = (double)q.y * sc, z = (double)q.z * sc, w = (double)q.w * sc;
+        a0 = fma(x, x, a0); a1 = fma(y, y, a1); a2 = fma(z, z, a2); a3 = fma(w, w, a3);
+    }
+    if (t < head) { const double x = (double)gc[t] * sc; a0 = fma(x, x, a0); }
+    if (t < tail) { const double x = (double)gc[head + 4 * nvec + t] * sc; a0 = fma(x, x, a0); }
+    const double tot = block_sum_256((a0 + a1) + (a2 + a3), sh);
+    if (t == 0) part[blockIdx.x] = tot;
+}
+
+// One workgroup of 16 waves.  A wave owns a segment at a time: its chunk partials are added IN CHUNK ORDER (384 at a time through the wave's LDS slot,
+// every lane adding the same values) into seg_sq[s]; one thread then adds the sums of the segments whose group is not frozen IN SEGMENT ORDER (a frozen one enters
+// as + 0.0, which changes no bit of a sum of squares) and applies grad_guard_finalize_kernel's rule.  st[7]: the schedule factor of the step count
+// just reached, lr_factors[min(t, n_factors) - 1] (1 without a table); a skipped step keeps it.  No atomics: bitwise repeatable on any CU count.
+constexpr int OPT_FIN_THREADS = 1024;
+constexpr int OPT_FIN_ROUNDS = 6;              // partials of one segment a wave loads at once: 6 x 64 (a 768 x 3072 weight is 288 chunks)
+// acc + sh[0] + sh[1] + ... + sh[m - 1], added strictly in that order; eight LDS reads are in flight ahead of the dependent additions
+__device__ inline double ordered_sum_lds(const double* sh, int m, double acc) {
+#pragma clang fp contract(off)
+    int k = 0;
+    for (; k + 8 <= m; k += 8) {
+        const double t0 = sh[k], t1 = sh[k + 1], t2 = sh[k + 2], t3 = sh[k + 3], t4 = sh[k + 4], t5 = sh[k + 5], t6 = sh[k + 6], t7 = sh[k + 7];
+        acc += t0; acc += t1; acc += t2; acc += t3; acc += t4; acc += t5; acc += t6; acc += t7;
+    }
+    for (; k < m; ++k) acc += sh[k];
+    return acc;
+}
+__global__ __launch_bounds__(OPT_FIN_THREADS) void grouped_guard_finalize_kernel(double* __restrict__ st, const double* __restrict__ part,
+                                                                                 const int* __restrict__ seg_chunk0, const unsigned char* __restrict__ seg_frozen,
+                                                                                 double* __restrict__ seg_sq, int n_seg, const float* __restrict__ lr_factors,
+                                                                                 long long n_factors, double max_norm, int clip, int skip_nonfinite, float b1,
+                                                                                 float b2) {
+#pragma clang fp contract(off)
+    __shared__ double tile[OPT_FIN_THREADS];
+    constexpr int SLOT = 64 * OPT_FIN_ROUNDS;
+    __shared__ double stage[OPT_FIN_THREADS / 64 * SLOT];     // SLOT partials per wave, private to it
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double* mine = stage + SLOT * wave;
+    double sum = 0.0;                                         // thread 0's
+    for (int base = 0; base < n_seg; base += OPT_FIN_THREADS) {
+        const int cnt = n_seg - base < OPT_FIN_THREADS ? n_seg - base : OPT_FIN_THREADS;
+        int n0 = 0, n1 = 0;                                   // the chunk range of the wave's next segment, loaded one segment ahead
+        if (wave < cnt) { n0 = seg_chunk0[base + wave]; n1 = seg_chunk0[base + wave + 1]; }
+        for (int j = wave; j < cnt; j += OPT_FIN_THREADS / 64) {
+            const int s = base + j, c0 = n0, c1 = n1;
+            if (j + OPT_FIN_THREADS / 64 < cnt) { n0 = seg_chunk0[s + OPT_FIN_THREADS / 64]; n1 = seg_chunk0[s + OPT_FIN_THREADS / 64 + 1]; }
+            double acc = 0.0;
+            for (int c = c0; c < c1; c += SLOT) {
+                const int m = c1 - c < SLOT ? c1 - c : SLOT;
+                double x[OPT_FIN_ROUNDS];
+#pragma unroll
+                for (int r = 0; r < OPT_FIN_ROUNDS; ++r) x[r] = lane + 64 * r < m ? part[c + lane + 64 * r] : 0.0;
+                // a wave's LDS operations execute in order; the wavefront fences keep the compiler from moving them across each other
+#pragma unroll
+                for (int r = 0; r < OPT_FIN_ROUNDS; ++r)
+                    if (lane + 64 * r < m) mine[lane + 64 * r] = x[r];
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                acc = ordered_sum_lds(mine, m, acc);          // every lane adds the same values in the same order
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            }
+            if (lane == 0) { seg_sq[s] = acc; tile[j] = seg_frozen[s] ? 0.0 : acc; }
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) sum = ordered_sum_lds(tile, cnt, sum);
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    const double norm = sqrt(sum);
+    st[3] = norm;
+    if (skip_nonfinite && !isfinite(sum)) {
+        st[1] += 1.0; st[2] = 1.0; st[4] = 0.0;
+        return;
+    }
+    const double steps = st[0] + 1.0;
+    const double c = max_norm / (norm + 1e-6);
+    st[0] = steps; st[2] = 0.0;
+    st[4] = clip ? (c > 1.0 ? 1.0 : c) : 1.0;
+    st[5] = 1.0 - pow((double)b1, steps);
+    st[6] = 1.0 - pow((double)b2, steps);
+    const long long at = steps < (double)n_factors ? (long long)steps : n_factors;
+    st[7] = n_factors > 0 ? (double)lr_factors[at - 1] : 1.0;
+}
+
+// torch.optim.AdamW's param.mul_(1 - lr * weight_decay) as a product of its own: never contracted into the update that follows, so that a group
+// without decay (factor exactly 1) gives adam_ema_guarded_kernel's bits.
+__device__ inline float opt_decay_mul(float p, float decay) {
+#pragma clang fp contract(off)
+    return p * decay;
+}
+
+// One workgroup per chunk: adam_ema_guarded_one with the group's learning rate lr_q = lr * lr_scale * st[7] on the decayed parameter.  A skipped
+// step touches nothing; a chunk of a frozen group returns before it loads anything.  16-byte accesses on the aligned interior of the chunk (every
+// vector is 16-byte aligned, so the four share the split), scalars at the ragged head and tail.
+__global__ __launch_bounds__(256) void adamw_ema_grouped_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                                float* __restrict__ ema, const OptChunkDev* __restrict__ chunks, float lr, float b1, float b2,
+                                                                float eps, float alpha, float grad_scale, const double* __restrict__ st) {
+    if (st[2] != 0.0) return;
+    const OptChunkDev c = chunks[blockIdx.x];
+    if (c.frozen) return;
+    const float coef = (float)st[4], bc1 = (float)st[5], bc2 = (float)st[6];
+    const float lr_q = (float)((double)lr * (double)c.lr_scale * st[7]);
+    const float decay = 1.0f - lr_q * c.weight_decay;
+    const bool has_ema = ema != nullptr;
+    int head, nvec, tail;
+    opt_chunk_split(c.first, c.len, head, nvec, tail);
+    const size_t v0 = (size_t)c.first + head;
+    const int t = threadIdx.x;
+#pragma unroll 2
+    for (int k = t; k < nvec; k += 256) {
+        const size_t i = v0 + 4 * (size_t)k;
+        float4 p4 = *reinterpret_cast<float4*>(p + i), m4 = *reinterpret_cast<float4*>(m + i), v4 = *reinterpret_cast<float4*>(v + i);
+        const float4 g4 = *reinterpret_cast<const float4*>(g + i);
+        float4 e4 = has_ema ? *reinterpret_cast<float4*>(ema + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+        p4.x = opt_decay_mul(p4.x, decay); p4.y = opt_decay_mul(p4.y, decay); p4.z = opt_decay_mul(p4.z, decay); p4.w = opt_decay_mul(p4.w, decay);
+        adam_ema_guarded_one(p4.x, g4.x, m4.x, v4.x, e4.x, has_ema, lr_q, b1, b2, eps, bc1, bc2, alpha, grad_scale, coef);
+        adam_ema_guarded_one(p4.y, g4.y, m4.y, v4.y, e4.y, has_ema, lr_q, b1, b2, eps, bc1, bc2, alpha, grad_scale, coef);
+        adam_ema_guarded_one(p4.z, g4.z, m4.z, v4.z, e4.z, has_ema, lr_q, b1, b2, eps, bc1, bc2, alpha, grad_scale, coef);
+        adam_ema_guarded_one(p4.w, g4.w, m4.w, v4.w, e4.w, has_ema, lr_q, b1, b2, eps, bc1, bc2, alpha, grad_scale, coef);
+        *reinterpret_cast<float4*>(p + i) = p4; *reinterpret_cast<float4*>(m + i) = m4; *reinterpret_cast<float4*>(v + i) = v4;
+        if (has_ema) *reinterpret_cast<float4*>(ema + i) = e4;
+    }
+    // the ragged ends: thread t takes head element t and / or tail element t (at most three of each)
+    for (int side = 0; side < 2; ++side) {
+        if (t >= (side ? tail : head)) continue;
+        const size_t j = side ? v0 + 4 * (size_t)nvec + t : (size_t)c.first + t;
+        float pj = opt_decay_mul(p[j], decay), mj = m[j], vj = v[j], ej = has_ema ? ema[j] : 0.f;
+        adam_ema_guarded_one(pj, g[j], mj, vj, ej, has_ema, lr_q, b1, b2, eps, bc1, bc2, alpha, grad_scale, coef);
+        p[j] = pj; m[j] = mj; v[j] = vj;
+        if (has_ema) ema[j] = ej;
+    }
+}
+
 // ---- held-out loss: per-sample reduction of the row errors and the accumulator by noise level (include/tld_hip.h) --------
 // fixed xor butterfly over the 64 lanes of a wave: every lane ends with the same bits (each level adds the same two values in both lanes)
 __device__ inline double wave_sum_f64(double a) {

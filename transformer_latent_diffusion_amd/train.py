@@ -23,7 +23,7 @@ from typing import Dict, Mapping, Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, opt_groups
 from .configs import DenoiserConfig
 from .weights import param_layout, state_dict_spec, synth_state_dict, unflatten  # noqa: F401  (param_layout: this module's name for it stays)
 
@@ -155,7 +155,8 @@ class Trainer:
                  state_dict: Optional[Mapping[str, torch.Tensor]] = None, init_seed: int = 0, max_batch: Optional[int] = None,
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, keep_ema: bool = True, process_group=None,
                  overlap_allreduce: bool = True, use_graph: Optional[bool] = None, max_grad_norm: Optional[float] = None,
-                 skip_nonfinite: bool = False, data_seed: int = 0, loss_buckets: Optional[int] = None):
+                 skip_nonfinite: bool = False, data_seed: int = 0, loss_buckets: Optional[int] = None, weight_decay: float = 0.0,
+                 param_groups=None, lr_schedule=None, schedule_steps: Optional[int] = None):
         self.cfg = denoiser_cfg
         self.tc = train_cfg if train_cfg is not None else TrainConfig()
         dev = torch.device(device)
@@ -178,6 +179,16 @@ class Trainer:
         self._opt_state = None
         self.group = process_group
         self.layout = param_layout(denoiser_cfg)
+        # the grouped optimizer step (opt_groups): any of weight_decay / param_groups / lr_schedule makes the trainer own a
+        # tld_opt_plan and the fp64 state; with all three at their defaults nothing is built and the three step paths below run as they always did
+        self.weight_decay = float(weight_decay)
+        self.grouped = self.weight_decay != 0.0 or bool(param_groups) or lr_schedule is not None
+        self._plan = None
+        self._lr_table = None
+        if self.grouped:
+            self._seg_numel, self._seg_group, self._groups = opt_groups.resolve(self.layout, param_groups, self.weight_decay)
+            if lr_schedule is not None:
+                self._lr_table = opt_groups.lr_table(lr_schedule, schedule_steps)
         self.numel = sum(int(np.prod(s)) for _, s in self.layout.values())
         c = asdict(denoiser_cfg)
         L = _lib.lib()
@@ -193,12 +204,15 @@ class Trainer:
             self.params, self.grads, self.exp_avg, self.exp_avg_sq = z(), z(), z(), z()
             self.ema = z() if keep_ema else None
             self.step = 0
-            if self.guarded:              # all zeros = a fresh optimizer (include/tld_hip.h); a step allocates nothing
+            if self.grouped:
+                self._build_plan()
+            if self.guarded or self.grouped:              # all zeros = a fresh optimizer (include/tld_hip.h); a step allocates nothing
                 self._opt_state = torch.zeros(_lib.TRAIN_OPT_STATE_DOUBLES, dtype=torch.float64, device=self.device)
             sd = state_dict if state_dict is not None else {k: torch.from_numpy(np.array(v)) for k, v in synth_state_dict(denoiser_cfg, init_seed).items()}
             self.load_state_dict(sd)
             _lib.check(L.tld_train_bind(self._h, C.c_void_p(self.params.data_ptr()), C.c_void_p(self.grads.data_ptr())), "tld_train_bind")
         except Exception:
+            self._destroy_plan()
             L.tld_train_destroy(self._h)
             self._h = None
             raise
@@ -254,8 +268,38 @@ class Trainer:
             if buf.value.decode() != k or off.value != o or num.value != int(np.prod(s)):
                 raise RuntimeError(f"parameter layout mismatch at {i}: engine {buf.value.decode()}@{off.value}+{num.value}, host {k}@{o}")
 
+    def _build_plan(self) -> None:
+        """``tld_opt_plan_create`` from the resolved groups: the tables go up once, here."""
+        n, ng = len(self._seg_numel), len(self._groups)
+        numel = (C.c_int64 * n)(*self._seg_numel)
+        group = (C.c_int32 * n)(*self._seg_group)
+        gs = (_lib.TldOptGroup * ng)(*[_lib.TldOptGroup(s, w, int(f), 0) for s, w, f in self._groups])
+        tab = self._lr_table
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().tld_opt_plan_create(self.device.index, numel, group, n, gs, ng,
+                                                      tab.ctypes.data_as(C.POINTER(C.c_float)) if tab is not None else None,
+                                                      int(tab.size) if tab is not None else 0, C.byref(h)), "tld_opt_plan_create")
+        self._plan = h
+        if _lib.lib().tld_opt_plan_numel(h) != self.numel:
+            raise RuntimeError("the optimizer plan and the parameter layout disagree on the vector's length")
+        ptr = C.c_void_p()
+        _lib.check(_lib.lib().tld_opt_plan_segment_sqsums(h, C.byref(ptr)), "tld_opt_plan_segment_sqsums")
+
+        class _View:                      # the plan's device double [n_tensors], handed to torch without a copy
+            __cuda_array_interface__ = {"shape": (n,), "typestr": "<f8", "data": (int(ptr.value), False), "version": 2, "strides": None}
+        with torch.cuda.device(self.device):
+            self._seg_sq = torch.as_tensor(_View(), device=self.device)
+
+    def _destroy_plan(self) -> None:
+        if getattr(self, "_plan", None) is not None:
+            self._seg_sq = None
+            _lib.lib().tld_opt_plan_destroy(self._plan)
+            self._plan = None
+
     def __del__(self):
         try:
+            self._destroy_plan()
             if getattr(self, "_h", None) is not None:
                 _lib.lib().tld_train_destroy(self._h)
                 self._h = None
@@ -538,6 +582,19 @@ class Trainer:
         self.step += 1
         stream = torch.cuda.current_stream(self.device).cuda_stream
         p = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None
+        if self.grouped:
+            L = _lib.lib()
+            b1, b2 = float(self.betas[0]), float(self.betas[1])
+            with torch.cuda.device(self.device):
+                _lib.check(L.tld_train_grad_guard_grouped(self._plan, p(self.grads), self.numel, float(scale),
+                                                          self.max_grad_norm if self.max_grad_norm is not None else 0.0, int(self.skip_nonfinite), b1, b2,
+                                                          p(self._opt_state), C.c_void_p(stream)), "tld_train_grad_guard_grouped")
+                _lib.check(L.tld_train_adamw_ema_grouped(self._plan, p(self.params), p(self.grads), p(self.exp_avg), p(self.exp_avg_sq), p(self.ema),
+                                                         self.numel, float(self.tc.lr), b1, b2, float(self.eps), float(self.tc.alpha), float(scale),
+                                                         p(self._opt_state), C.c_void_p(stream)), "tld_train_adamw_ema_grouped")
+                # the grouped entries take no engine: binding the same vectors again marks its bf16 operand copies stale
+                _lib.check(L.tld_train_bind(self._h, p(self.params), p(self.grads)), "tld_train_bind")
+            return
         if self.guarded:
             L = _lib.lib()
             b1, b2 = float(self.betas[0]), float(self.betas[1])
@@ -559,6 +616,14 @@ class Trainer:
             raise RuntimeError("this Trainer's optimizer step is not guarded (construct it with max_grad_norm= and / or skip_nonfinite=True)")
 
     @property
+    def tensor_grad_norms(self) -> torch.Tensor:
+        """Per-tensor norms of the last step's mean gradient, fp64 ``[n_tensors]`` on the device in ``param_layout`` order (frozen tensors
+        included; before clipping): the square roots of the plan's per-segment sums -- reading it does not synchronise.  Grouped trainers only."""
+        if self._plan is None:
+            raise RuntimeError("this Trainer's optimizer step is not grouped (construct it with weight_decay=, param_groups= or lr_schedule=)")
+        return self._seg_sq.sqrt()
+
+    @property
     def grad_norm(self) -> torch.Tensor:
         """Global norm of the last step's mean gradient (before clipping; Inf or NaN when non-finite): a 0-d fp64 view of the device state --
         reading the attribute does not synchronise, ``float()`` of it does."""
@@ -568,14 +633,23 @@ class Trainer:
     def optimizer_stats(self) -> Dict[str, object]:
         """Synchronises and returns the guard's state: ``grad_norm``, ``clip_coef``, ``applied_steps``, ``skipped_steps``, ``last_skipped``."""
         self._need_guard()
-        t, skipped, last, norm, coef = self._opt_state[:5].cpu().tolist()
-        return {"grad_norm": norm, "clip_coef": coef, "applied_steps": int(t), "skipped_steps": int(skipped), "last_skipped": bool(last)}
+        t, skipped, last, norm, coef, _, _, factor = self._opt_state[:8].cpu().tolist()
+        out = {"grad_norm": norm, "clip_coef": coef, "applied_steps": int(t), "skipped_steps": int(skipped), "last_skipped": bool(last)}
+        if self.grouped:                  # the schedule factor of the last applied step (1 without a schedule, 0 before the first step)
+            out["lr_factor"] = factor
+        return out
+
+    def _factor_at(self, t: int) -> float:
+        """The schedule factor applied step ``t`` >= 1 runs at: ``table[min(t, n) - 1]``, or 1 without a table."""
+        return 1.0 if self._lr_table is None else float(self._lr_table[min(int(t), self._lr_table.size) - 1])
 
     def _set_applied_steps(self, t: int) -> None:
         """The guard's state for an optimizer that has applied ``t`` steps (tld_train_grad_guard's formula, float-rounded betas in double)."""
         st = torch.zeros(_lib.TRAIN_OPT_STATE_DOUBLES, dtype=torch.float64)
         b1, b2 = (float(np.float32(b)) for b in self.betas)
         st[0], st[5], st[6] = float(t), 1.0 - b1 ** t, 1.0 - b2 ** t
+        if self.grouped and t > 0:
+            st[7] = self._factor_at(t)
         self._opt_state.copy_(st)
 
     def train_step(self, x: torch.Tensor, y: torch.Tensor, np_rng: Optional[np.random.Generator] = None,
@@ -879,12 +953,17 @@ class Trainer:
         """``torch.optim.Adam(model.parameters(), lr).state_dict()`` as the reference saves it (tld/train.py:86,152): per-parameter
         ``{step, exp_avg, exp_avg_sq}`` in ``named_parameters()`` order + one param group.  (Before the first step torch's ``state`` is empty.)"""
         state = {}
-        step = self.optimizer_stats()["applied_steps"] if self.guarded else self.step      # (a checkpoint copies everything to the host anyway)
+        step = self.optimizer_stats()["applied_steps"] if self.guarded or self.grouped else self.step      # (a checkpoint copies everything to the host anyway)
         if step > 0:
             for i, (k, (o, s)) in enumerate(self.layout.items()):
+                if self.grouped and self._groups[self._seg_group[i]][2]:
+                    continue              # a frozen tensor has no Adam state, as a parameter with requires_grad = False has none in torch
                 n = int(np.prod(s))
                 state[i] = {"step": torch.tensor(float(step)), "exp_avg": self.exp_avg[o:o + n].view(*s).clone(),
                             "exp_avg_sq": self.exp_avg_sq[o:o + n].view(*s).clone()}
+        if self.grouped:                  # torch.optim.AdamW's groups; lr as LambdaLR leaves it after `step` steps: that of the NEXT step
+            return {"state": state, "param_groups": opt_groups.torch_param_groups(self._seg_group, self._groups, self.tc.lr, self.betas, self.eps,
+                                                                                  self._factor_at(step + 1), self._lr_table is not None)}
         group = {"lr": self.tc.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": 0, "amsgrad": False, "maximize": False,
                  "foreach": None, "capturable": False, "differentiable": False, "fused": None, "params": list(range(len(self.layout)))}
         return {"state": state, "param_groups": [group]}
@@ -892,6 +971,13 @@ class Trainer:
     def load_optimizer_state_dict(self, osd: Mapping[str, object]) -> None:
         """Inverse of ``optimizer_state_dict`` (``optimizer.load_state_dict`` of tld/train.py:100): also accepts a reference checkpoint's Adam state."""
         state = osd.get("state", {})
+        groups = osd.get("param_groups") or []
+        if self.grouped:                  # refused before anything is touched
+            mine = [[i for i, q in enumerate(self._seg_group) if q == k] for k in range(len(self._groups))]
+            theirs = [[int(i) for i in g.get("params", [])] for g in groups]
+            if theirs != mine:
+                raise RuntimeError(f"the checkpoint's optimizer has {len(theirs)} param groups over another partition of the parameters than this "
+                                   f"trainer's {len(mine)} groups")
         self.exp_avg.zero_(); self.exp_avg_sq.zero_()
         steps = set()
         for i, (k, (o, s)) in enumerate(self.layout.items()):
@@ -908,11 +994,10 @@ class Trainer:
         if len(steps) > 1:
             raise RuntimeError(f"per-parameter Adam step counts differ ({sorted(steps)}): the fused optimizer kernel keeps one count")
         self.step = steps.pop() if steps else 0
-        groups = osd.get("param_groups") or []
         if groups:
-            self.tc.lr = float(groups[0].get("lr", self.tc.lr))
+            self.tc.lr = float(groups[0].get("initial_lr", groups[0].get("lr", self.tc.lr)) if self.grouped else groups[0].get("lr", self.tc.lr))
             self.betas = tuple(groups[0].get("betas", self.betas)); self.eps = float(groups[0].get("eps", self.eps))
-        if self.guarded:                      # the device's count restarts from the checkpoint's applied steps; skips are not carried
+        if self.guarded or self.grouped:      # the device's count restarts from the checkpoint's applied steps; skips are not carried
             self._set_applied_steps(self.step)
 
     def checkpoint(self) -> Dict[str, object]:
