@@ -286,7 +286,8 @@ TLD_API int tld_debug_decode_stage(const void* raw, const void* aux, int32_t dty
  *   52 update_from with a mask   53 start_mix
  *   writers of the MX-fp8 A operand (with bit 10): 54 separate quantisation pass   55 cross_row_mfma writing e4m3   56 depthwise tiled writing e4m3
  *   57 depthwise streaming writing e4m3
- *   tld_sample_requests: 58 update_requests without a mask   59 update_requests with a mask   60 start_mix per request */
+ *   tld_sample_requests: 58 update_requests without a mask   59 update_requests with a mask   60 start_mix per request
+ *   61 fused QKV + attention on two-head tiles (set instead of bit 11 by such a launch) */
 #define TLD_ENGINE_PATH_BITS 61
 TLD_API int tld_engine_set_debug(tld_engine* e, int32_t enable);
 TLD_API int tld_engine_read_stage(tld_engine* e, const char* name, float* host_out, int64_t numel);
@@ -363,6 +364,10 @@ TLD_API int tld_debug_gemm_epilogue(const tld_gemm_epilogue_args* args, void* hi
 #define TLD_GEMM_PLAN_QUERY_INTS 24
 #define TLD_GEMM_PLAN_INTS 9
 TLD_API int tld_debug_gemm_plan(const int32_t* queries, int32_t n, int32_t* plans);
+/* Which form of the fused QKV + attention kernel a launch gets (tld_qkv_pair_plan.h: plan_qkv_pair): `queries` holds n rows of
+ * (samples, heads, CU count), pair[i] receives 1 for two-head tiles and 0 for one-head tiles.  cost_ratio (may be null) receives numerator and
+ * denominator of t_pair / t_item, the measured cost of a two-head tile in one-head items, which the rule compares whole rounds with. */
+TLD_API int tld_debug_qkv_pair_plan(const int32_t* queries, int32_t n, int32_t* pair, int32_t* cost_ratio);
 
 /* Live per-kernel-class timing with HIP events recorded on the launch stream around every launch
  * of the selected classes (bit k of class_mask).  Classes: 0 gemm_qkv, 1 gemm_up, 2 gemm_down,

@@ -25,7 +25,7 @@ ABI_SYMBOLS = (
     "tld_engine_create", "tld_engine_load_tensor", "tld_engine_finalize_weights", "tld_denoiser_forward",
     "tld_sample", "tld_sample_from", "tld_sample_requests", "tld_sample_requests_guided", "tld_engine_sample_rows", "tld_engine_set_gemm_dtype", "tld_engine_set_low_latency", "tld_debug_gemm_splitk", "tld_debug_quant_mx8", "tld_debug_quant_mx8_host", "tld_debug_gemm_mx8",
     "tld_engine_param_count", "tld_engine_refresh_weights", "tld_debug_quant_mx8_f32",
-    "tld_debug_decode_stage", "tld_engine_set_debug", "tld_engine_read_stage", "tld_engine_stage_shape", "tld_engine_set_debug_step", "tld_engine_debug_paths", "tld_debug_gemm_bf16", "tld_debug_gemm_bench", "tld_debug_gemm_plan", "tld_debug_gemm_epilogue",
+    "tld_debug_decode_stage", "tld_engine_set_debug", "tld_engine_read_stage", "tld_engine_stage_shape", "tld_engine_set_debug_step", "tld_engine_debug_paths", "tld_debug_gemm_bf16", "tld_debug_gemm_bench", "tld_debug_gemm_plan", "tld_debug_qkv_pair_plan", "tld_debug_gemm_epilogue",
     "tld_engine_set_profile", "tld_engine_profile_reserve", "tld_engine_get_profile", "tld_engine_weight_bytes", "tld_engine_destroy",
     "tld_vae_create", "tld_vae_load_tensor", "tld_vae_finalize_weights", "tld_vae_decode", "tld_vae_set_debug",
     "tld_vae_read_stage", "tld_vae_set_profile", "tld_vae_get_profile", "tld_debug_conv3x3", "tld_vae_weight_bytes",
@@ -171,6 +171,8 @@ def lib() -> C.CDLL:
     L.tld_debug_gemm_bench.argtypes = [i32, i32, i32, i32, i32, i32, C.POINTER(C.c_double)]
     if hasattr(L, "tld_debug_gemm_plan"):            # (absent from A/B builds that predate it)
         L.tld_debug_gemm_plan.argtypes = [vp, i32, vp]
+    if hasattr(L, "tld_debug_qkv_pair_plan"):
+        L.tld_debug_qkv_pair_plan.argtypes = [vp, i32, vp, vp]
     if hasattr(L, "tld_debug_gemm_epilogue"):
         L.tld_debug_gemm_epilogue.argtypes = [C.POINTER(TldGemmEpilogueArgs), vp]
     L.tld_engine_set_profile.argtypes = [vp, C.c_uint32]

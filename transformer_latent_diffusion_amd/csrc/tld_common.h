@@ -4,6 +4,7 @@
 #include <atomic>
 #include <mutex>
 #include <stdint.h>
+#include "tld_qkv_pair_plan.h"    // plan_qkv_pair: one or two heads per tile of the fused QKV + attention kernel
 #include "tld_gemm_plan.h"        // GemmParams, GemmEpilogue, bf16, resid_t, kLnSlots (tld_gemm_params.h); GemmPlan, gemm_resid_stat_slots
 
 namespace tld {
@@ -319,7 +320,9 @@ enum : int {
     EP_UPDATE_REQ = 58, EP_UPDATE_REQ_MASK = 59, EP_START_MIX_REQ = 60,
     // out_proj folded into the last block's down projection (bit 16 was unused): set next to the EP_TAIL_MFMA bit of the launch's patch-feature tiles
     EP_TAIL_FOLD = 16,
-    EP_COUNT = 61
+    // fused QKV + attention on two-head tiles (EPI_QKV_ATTN2); a launch sets this bit INSTEAD of EP_QKV_ATTN
+    EP_QKV_ATTN_PAIR = 61,
+    EP_COUNT = 62
 };
 extern thread_local uint64_t* g_path_sink;
 inline void note_path(int bit) { if (g_path_sink) *g_path_sink |= 1ull << bit; }

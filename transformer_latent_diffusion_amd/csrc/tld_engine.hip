@@ -74,6 +74,8 @@ struct tld_engine : DeviceArena {      // (pad = 256: every allocation of this e
     float* splitk = nullptr;           // [ll_split][max rows][d] fp32 slices of it
     int ll_split = 0;                  // K-splits of the low-latency down projection (4 or 8, from the engine's capacity: lowlat_split)
     bool fuse_qkv_attn = true;         // 256-token grids with the LayerNorm-1 fold: QKV GEMM + self-attention as ONE kernel per (sample, head) (TLD_FUSE_QKV_ATTN=0: two kernels)
+    int qkv_pair = 1;                  // TLD_QKV_ATTN_PAIR: that kernel on two-head tiles (EPI_QKV_ATTN2): 0 never, 1 where plan_qkv_pair says so, 2 wherever the shape permits (test hook)
+    uint32_t* pair_park = nullptr;     // one slot of kPairSlotDwords per workgroup such a launch can have (min(head pairs of max_batch, CUs)); null: no pair form in this engine
     float2* ln_stats = nullptr;        // [M][kLnSlots] row partial sums of the residual stream (embed / down GEMM -> QKV GEMM)
     bool fold_ln3 = true;              // TLD_FOLD_LN3=0: cross_row writes LN3(x) and the up-projection reads it (A/B testing)
     float2* row_stats = nullptr;       // [M] (mean, rstd) of the residual rows, cross_row -> up-projection epilogue
@@ -186,6 +188,12 @@ inline std::string blk_name(int l, const char* n) { return "blk" + std::to_strin
 
 // which of the forward's size-independent branches this engine takes (run_body and the snapshot reservation agree through these)
 inline bool eng_fused_qa(const tld_engine* e) { return e->fuse_qkv_attn && e->fold_ln1 && !e->fp8; }
+// ... on two-head tiles for a launch of `samples` samples: the engine holds the pair-ordered images and the slots (finalize: heads even, not fp8, a batch <= max_batch
+// that takes them), is not a low-latency class, and the switch and plan_qkv_pair (tld_qkv_pair_plan.h) agree
+inline bool eng_qkv_pair(const tld_engine* e, int samples) {
+    if (!eng_fused_qa(e) || !e->pair_park || e->low_latency) return false;
+    return e->qkv_pair == 2 || (e->qkv_pair == 1 && plan_qkv_pair(samples, e->H, device_cu_count()));
+}
 inline bool eng_fuse_dw(const tld_engine* e) { return e->fuse_dwconv && (e->grid == 16 || (e->grid == 32 && e->seam)) && e->hid % 256 == 0; }
 
 // set_debug(1): memory for every snapshot a forward of max_batch samples takes (the names of the SNAP calls in run_body and the samplers),
@@ -373,10 +381,12 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
         if (fused_qa) {
             ProfScope ps(e, KC_GEMM_QKV, s);
             GemmParams g{};
-            g.A = half ? xe : e->x; g.lda = d; g.W = Ly.qkv_wp; g.ldw = d; g.M = Ml; g.N = 3 * d; g.K = d;
+            const bool pair = eng_qkv_pair(e, bl);          // two heads per tile where that is the faster cut of this launch (the same bits either way)
+            g.A = half ? xe : e->x; g.lda = d; g.W = pair ? Ly.qkv_wp2 : Ly.qkv_wp; g.ldw = d; g.M = Ml; g.N = 3 * d; g.K = d;
             g.out_bf16 = e->att; g.ldo = d; g.ntok = e->ntok; g.d = d;
-            g.ln_stats = e->ln_stats; g.ln_slots = l == 0 ? 2 : ln_slots; g.ln_c1 = Ly.qkv_c1p; g.ln_b1 = Ly.qkv_b1p;
-            GEMM_TRY(blk_name(l, "QKV + attention"), launch_gemm(g, EPI_QKV_ATTN, s));
+            g.ln_stats = e->ln_stats; g.ln_slots = l == 0 ? 2 : ln_slots; g.ln_c1 = pair ? Ly.qkv_c1p2 : Ly.qkv_c1p; g.ln_b1 = pair ? Ly.qkv_b1p2 : Ly.qkv_b1p;
+            g.park = pair ? e->pair_park : nullptr;
+            GEMM_TRY(blk_name(l, "QKV + attention"), launch_gemm(g, pair ? EPI_QKV_ATTN2 : EPI_QKV_ATTN, s));
         } else {   // q|k, v^T = LN1(x) Wqkv^T
             ProfScope ps(e, KC_GEMM_QKV, s);
             GemmParams g{};
@@ -795,6 +805,7 @@ int tld_engine_create(const tld_config* c, tld_engine** out) {
     // residual stream) and an even number of 64-wide K-steps (its LDS map relies on which stage a tile consumes last)
     if (const char* fq = getenv("TLD_FUSE_QKV_ATTN")) e->fuse_qkv_attn = atoi(fq) != 0;
     e->fuse_qkv_attn = e->fuse_qkv_attn && e->fold_ln1 && ntok == 256 && e->d % 128 == 0;
+    if (const char* qp = getenv("TLD_QKV_ATTN_PAIR")) { const int v = atoi(qp); e->qkv_pair = v < 0 ? 0 : v > 2 ? 2 : v; }
     *out = e;
     return TLD_OK;
 }
@@ -852,6 +863,12 @@ int tld_engine_finalize_weights(tld_engine* e) {
 #undef COPY
 #undef JOB
     static_assert(kRefreshMaxJobs >= 21, "the images outside the blocks");
+    // the two-head form of the fused QKV + attention kernel: only engines that can run it hold its images and slots
+    bool pair_form = false;
+    if (e->fuse_qkv_attn && !e->fp8 && !e->low_latency && e->H % 2 == 0 && e->qkv_pair != 0) {
+        pair_form = e->qkv_pair == 2;
+        for (int b = 1; b <= e->cfg.max_batch && !pair_form; ++b) pair_form = plan_qkv_pair(b, e->H, device_cu_count());
+    }
     for (Layer& Ly : e->layers) {
         // bf16 GEMM operands: only the copies this engine's paths read are made resident (the LayerNorm folds use gamma-scaled copies, the fp8 mode
         // its own e4m3 ones)
@@ -869,6 +886,9 @@ int tld_engine_finalize_weights(tld_engine* e) {
                 if (int rc = dev_alloc(e, &Ly.qkv_c1p, (size_t)(3 * d + 64))) return rc;      // (+64: the side-table DMA of the last head reads a 256-column window;
                 if (int rc = dev_alloc(e, &Ly.qkv_b1p, (size_t)(3 * d + 64))) return rc;      // that margin is no weight)
                 e->weight_bytes += 2 * 3 * d * (int64_t)sizeof(float);
+                if (pair_form) {    // the same rows in head-pair order (EPI_QKV_ATTN2): 3 d^2 bf16 more per block
+                    IMG(Ly.qkv_wp2, 3 * d * d) IMG(Ly.qkv_c1p2, 3 * d) IMG(Ly.qkv_b1p2, 3 * d)
+                }
             }
         }
         if (e->fp8) {
@@ -919,6 +939,10 @@ int tld_engine_finalize_weights(tld_engine* e) {
     if (int rc = dev_alloc(e, &e->qk, M * 2 * d)) return rc;
     if (int rc = dev_alloc(e, &e->vt, M * d)) return rc;
     if (int rc = dev_alloc(e, &e->att, M * d)) return rc;
+    if (pair_form) {
+        const size_t pairs = B2 * (size_t)(e->H / 2), cus = (size_t)device_cu_count();
+        if (int rc = dev_alloc(e, &e->pair_park, (pairs < cus ? pairs : cus) * (size_t)kPairSlotDwords)) return rc;
+    }
     if (int rc = dev_alloc(e, &e->hid1, M * hid)) return rc;
     if (e->grid == 32 && e->fuse_dwconv && hid % 256 == 0) { if (int rc = dev_alloc(e, &e->seam, M * hid / 4)) return rc; }
     if (int rc = dev_alloc(e, &e->hid2, M * hid)) return rc;

@@ -95,6 +95,11 @@ struct G256P : G256<BN> {
     // images live behind it (stage 1, which a tile of an even number of K-steps consumes last, the LayerNorm side tables -- dead once the
     // accumulators are normalised -- and the rest of the CU's 160 KiB)
     static constexpr int AT_K = STAGE_BYTES, AT_V = AT_K + 256 * 128, AT_Q = AT_V + 64 * kAttnVPitch, ATTN_LDS = AT_Q + 256 * 128;
+    // EPI_QKV_ATTN2 (BN = 384): the two stages are all of the CU's 160 KiB, so nothing is prefetched under the epilogue (tiles start cold, always in
+    // stage 0) and the LayerNorm side tables arrive by DMA during the tile's LAST K-step, at the bottom of stage 0, which that step no longer reads
+    // (K-steps per tile are even).  The three images of ONE head follow them: they overlay no table, so the second head's pass needs no table again.
+    static constexpr int P2_RAW = 0, P2_ST = P2_RAW + 256 * 8 * kLnSlots, P2_CB = P2_ST + 256 * 8;       // row partial sums | (mean, rstd) | c1[384], b1[384]
+    static constexpr int P2_K = P2_CB + 2 * 384 * 4 + 3072, P2_V = P2_K + 256 * 128, P2_Q = P2_V + 64 * kAttnVPitch, PAIR_LDS_END = P2_Q + 256 * 128;
 };
 
 // F8 = true: both operands are OCP e4m3 bytes with MX block scales (one E8M0 byte per 32 K-elements), multiplied by
@@ -124,6 +129,10 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, int nblocks
     constexpr bool UPDW = EPI == EPI_UP_DWCONV2 || EPI == EPI_UP_DWCONV32;       // fused depthwise epilogues (16 x 16 / 32 x 32 token grids)
     static_assert(EPI != EPI_QKV_ATTN || (BN == 192 && !F8 && !CONV && !RING), "the fused attention epilogue is written for 256 x 192 tiles");
     static_assert(EPI != EPI_QKV_ATTN || G::ATTN_LDS <= 160 * 1024, "LDS");
+    constexpr bool PAIR = EPI == EPI_QKV_ATTN2;                       // two heads per 256 x 384 tile (see the epilogue)
+    static_assert(!PAIR || (BN == 384 && !F8 && !CONV && !RING && !TN), "the two-head attention epilogue is written for 256 x 384 tiles");
+    static_assert(!PAIR || G::PAIR_LDS_END <= G::LDS_BYTES, "LDS");
+    constexpr bool COLD = UPDW || PAIR;                               // the epilogue owns all of LDS: no prefetch of the next tile under it
     static_assert(8 * G::SCRATCH <= G::STAGE_BYTES, "epilogue scratch must fit in one stage");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
@@ -301,6 +310,17 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, int nblocks
                                    : reinterpret_cast<const char*>(p.W) + tnW + (size_t)(kbyte >> 7) * 64 * p.ldw * 2;
             const unsigned vo = isA ? voffA[q2] : voffB[q2 - G::A_PIECES];
             __builtin_amdgcn_global_load_lds((gptr_t)(base + vo), (lptr_t)(st + (isA ? 0 : G::A_BYTES) + (wid * G::A_PIECES + (isA ? q2 : q2 - G::A_PIECES)) * 1024), 16, 0, 0);
+            return;
+        }
+        if constexpr (PAIR) {
+            // 192 accumulators leave this K loop no register to spare: a uniform base in SGPRs + the 32-bit lane offset (the compiler otherwise carried every
+            // offset as a 64-bit pair with a zero upper half and spilled)
+            const bool isA = q2 < G::A_PIECES;
+            const char* base = reinterpret_cast<const char*>(isA ? (const void*)p.A : (const void*)p.W) + kbyte;
+            asm volatile("" : "+s"(base));
+            unsigned vo = isA ? voffA[q2] : voffB[q2 - G::A_PIECES];
+            asm volatile("" : "+v"(vo));
+            __builtin_amdgcn_global_load_lds((gptr_t)(base + vo), (lptr_t)(st + (isA ? (wid * G::A_PIECES + q2) : G::A_BYTES / 1024 + wid * G::B_PIECES + (q2 - G::A_PIECES)) * 1024), 16, 0, 0);
             return;
         }
         if (q2 < G::A_PIECES) {
@@ -561,6 +581,23 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, int nblocks
                     __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(smem + G::LN_CB + wid * 1024), 16, 0, 0);
                 }
             }
+            if constexpr (PAIR) {
+                // into the bottom of stage 0 during the tile's last K-step (which reads stage 1): 16 KiB of row partial sums, then c1 | b1 of the
+                // tile's 384 columns -- waves 0 / 1 columns 0 - 255 of c1 / b1, the lower halves of waves 2 / 3 columns 256 - 383
+                int ln = lane;
+                asm volatile("" : "+v"(ln));          // (lane-only address parts must not become K-loop invariants: the loop has no register to hold them)
+#pragma unroll
+                for (int q2 = 0; q2 < 2; ++q2) {
+                    const int piece = wid * 2 + q2;
+                    const int row = m0 + piece * 16 + (ln >> 2);
+                    const char* src = reinterpret_cast<const char*>(p.ln_stats) + (size_t)row * 64 + (ln & 3) * 16;
+                    __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(smem + G::P2_RAW + piece * 1024), 16, 0, 0);
+                }
+                if (wid < 4 && (wid < 2 || ln < 32)) {
+                    const float* src = ((wid & 1) ? p.ln_b1 : p.ln_c1) + n0 + (wid >> 1) * 256 + ln * 4;
+                    __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(smem + G::P2_CB + (wid & 1) * 1536 + (wid >> 1) * 1024), 16, 0, 0);
+                }
+            }
             if constexpr (EPI == EPI_BIAS_BF16) {      // folded LayerNorm-3 of the plain up-projection (grids other than 16 x 16)
                 if (BN != 384 && p.row_stats && wid < 2) {                   // (384-wide: no fold and no LDS behind the stages to stage it in)
                     int r0s = m0 + wid * 128 + lane * 2;                     // 2 rows (16 B) per lane, clamped at the matrix end
@@ -627,10 +664,10 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, int nblocks
             __builtin_amdgcn_s_barrier();          // ... everybody's; also: the previous epilogue's scratch reads are done
             if (grp) __builtin_amdgcn_s_barrier(); // stagger in
             for (int k = 0; k < nkt; ++k, ++g) {
-                if (k == (nkt > 1 ? 1 : 0)) aux_dma();        // (K = 64: the tile's only K-step; every wave is past the previous epilogue since the barrier above)
+                if (k == (PAIR ? nkt - 1 : nkt > 1 ? 1 : 0)) aux_dma();        // (K = 64: the tile's only K-step; every wave is past the previous epilogue since the barrier above)
                 const char* st = smem + (g & 1) * G::STAGE_BYTES;
                 char* nst = smem + ((g + 1) & 1) * G::STAGE_BYTES;
-                const bool more = (k + 1 < nkt) || (has_next && !UPDW);
+                const bool more = (k + 1 < nkt) || (has_next && !COLD);
                 const int pkb = (k + 1 < nkt) ? (KSPLIT_OK ? kb0 : 0) + (k + 1) * G::BK * 2 : (KSPLIT_OK ? kbn : 0);
                 if constexpr (CONV) {
                     if (k + 1 < nkt) {
@@ -1367,6 +1404,157 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, int nblocks
                     }
                 }
                 // (the next tile's K loop opens with a barrier: every wave is out of the images before stage 1 is written again)
+            } else if constexpr (PAIR) {
+                // ---- fused self-attention of (sample m0 / 256, heads 2 n0 / 384 and 2 n0 / 384 + 1): the 384-wide K loop is balanced between LDS reads and
+                // MFMAs where the 192-wide one is LDS-bound, but 160 KiB of LDS and 256 registers hold ONE head's attention state.  So the
+                // epilogue of EPI_QKV_ATTN runs twice over the same three images, and while head A is worked on, head B's q | k | v wait as packed bf16 in
+                // the workgroup's slot of GemmParams::park (96 KB, L2-resident).
+                // Tile column c = [wave column wn = c / 96][part (c % 96) / 32: q | k | v][side (c % 32) / 16: head A | B][16 features]: feature 16 wn + c % 16 of
+                // the head.  In the swapped accumulators (lane = token row, register quad rq = columns 8 rq + 4 hi .. + 3 of a 32-column block) quads 0, 1 are
+                // head A's and quads 2, 3 head B's: every wave holds a share of both heads, nothing moves between waves.
+                // The arithmetic of every output element -- K order, LayerNorm correction, the rounding of q, k, v to bf16, attn256_wave -- is EPI_QKV_ATTN's.
+                int e_lane = lane, e_l31 = l31, e_hi = hi;
+                asm volatile("" : "+v"(e_lane), "+v"(e_l31), "+v"(e_hi));
+                const int tid = wid * 64 + e_lane;
+                {
+                    const int s0 = (tid & 1) * 4;
+                    const float4* raw = reinterpret_cast<const float4*>(smem + G::P2_RAW + (tid >> 1) * 64 + s0 * 8);
+                    float su = 0.f, sq = 0.f;
+#pragma unroll
+                    for (int q2 = 0; q2 < 2; ++q2)
+                        if (s0 + 2 * q2 < p.ln_slots) {
+                            const float4 v = raw[q2];
+                            su += v.x + v.z; sq += v.y + v.w;
+                        }
+                    su = dpp_add<0xB1>(su); sq = dpp_add<0xB1>(sq);
+                    int kdim = p.K;
+                    asm volatile("" : "+s"(kdim));           // (1 / K stays here: hoisted out of the tile loop it cost the K loop a register)
+                    const float inv_k = 1.0f / (float)kdim;
+                    const float mu = su * inv_k;
+                    const float var = fmaxf(fmaf(sq, inv_k, -mu * mu), 0.f);
+                    if (!(tid & 1))
+                        reinterpret_cast<float2*>(smem + G::P2_ST)[tid >> 1] = make_float2(mu, __builtin_amdgcn_rsqf(var + kLnEps));
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_s_barrier();
+                }
+                // The slot is written and read lane-linearly, 16 bytes per lane and access (one contiguous KiB per wave), and each lane reads back exactly the
+                // bytes it stored: program order of ONE thread on its own addresses, which the memory path keeps per wave -- no other wave, workgroup or agent
+                // ever touches these bytes, so no fence and no cache maintenance is involved.  The s_waitcnt vmcnt(0) before the reload only makes the stores'
+                // completion explicit (and keeps the compiler from forwarding the stored registers to the loads, which would keep head B live).
+                u32x4* slot = reinterpret_cast<u32x4*>(p.park) + (size_t)blockIdx.x * (kPairSlotDwords / 4) + tid;
+                bf16x8 pk[G::TM][G::TN];              // one head's values of this lane: [32-row block][q | k | v][quad (0, 1) x 4 columns]
+                {
+                    float rs[G::TM], nm[G::TM];
+#pragma unroll
+                    for (int i = 0; i < G::TM; ++i) {
+                        const float2 st = reinterpret_cast<const float2*>(smem + G::P2_ST)[wm * G::WROWS + i * 32 + e_l31];
+                        rs[i] = st.y; nm[i] = -st.y * st.x;
+                    }
+#pragma unroll
+                    for (int j = 0; j < G::TN; ++j) {
+#pragma unroll
+                        for (int rq = 0; rq < 4; ++rq) {
+                            const int cl = wn * G::WCOLS + j * 32 + 8 * rq + 4 * e_hi;         // column inside the tile
+                            const float4 c4 = *reinterpret_cast<const float4*>(smem + G::P2_CB + cl * 4);
+                            const float4 b4 = *reinterpret_cast<const float4*>(smem + G::P2_CB + 1536 + cl * 4);
+#pragma unroll
+                            for (int i = 0; i < G::TM; ++i) {
+                                acc[i][j][rq * 4 + 0] = fmaf(rs[i], acc[i][j][rq * 4 + 0], fmaf(nm[i], c4.x, b4.x));
+                                acc[i][j][rq * 4 + 1] = fmaf(rs[i], acc[i][j][rq * 4 + 1], fmaf(nm[i], c4.y, b4.y));
+                                acc[i][j][rq * 4 + 2] = fmaf(rs[i], acc[i][j][rq * 4 + 2], fmaf(nm[i], c4.z, b4.z));
+                                acc[i][j][rq * 4 + 3] = fmaf(rs[i], acc[i][j][rq * 4 + 3], fmaf(nm[i], c4.w, b4.w));
+                            }
+                        }
+                        // head B of this part: rounded as the image write rounds, parked, dead
+#pragma unroll
+                        for (int i = 0; i < G::TM; ++i) {
+                            bf16x8 b;
+#pragma unroll
+                            for (int e2 = 0; e2 < 8; ++e2) b[e2] = (bf16)acc[i][j][8 + e2];
+                            slot[(j * G::TM + i) * 512] = __builtin_bit_cast(u32x4, b);
+                        }
+                    }
+#pragma unroll
+                    for (int j = 0; j < G::TN; ++j)
+#pragma unroll
+                        for (int i = 0; i < G::TM; ++i)
+#pragma unroll
+                            for (int e2 = 0; e2 < 8; ++e2) pk[i][j][e2] = (bf16)acc[i][j][e2];
+                }
+                char* Kimg = smem + G::P2_K;
+                char* Vimg = smem + G::P2_V;
+                char* Qimg = smem + G::P2_Q;
+                // one head from pk: images, attention of this wave's 32 query rows, transposed store -- the body of EPI_QKV_ATTN with 16 features per wave column
+                auto head = [&](int side) {
+#pragma unroll
+                    for (int j = 0; j < G::TN; ++j) {
+#pragma unroll
+                        for (int i = 0; i < G::TM; ++i) {
+                            const int row = wm * G::WROWS + i * 32 + e_l31;
+#pragma unroll
+                            for (int rq = 0; rq < 2; ++rq) {
+                                const bf16x4 q4 = {pk[i][j][rq * 4 + 0], pk[i][j][rq * 4 + 1], pk[i][j][rq * 4 + 2], pk[i][j][rq * 4 + 3]};
+                                const int f = wn * 16 + 8 * rq + 4 * e_hi;                 // feature inside q, k or v
+                                if (j < 2) {
+                                    char* img = j == 0 ? Qimg : Kimg;
+                                    *reinterpret_cast<bf16x4*>(img + row * 128 + ((((f >> 3) ^ ((row >> 1) & 7)) << 4) | ((f & 7) << 1))) = q4;
+                                } else {
+#pragma unroll
+                                    for (int e2 = 0; e2 < 4; ++e2)
+                                        *reinterpret_cast<bf16*>(Vimg + (f + e2) * kAttnVPitch + row * 2) = q4[e2];
+                                }
+                            }
+                        }
+                    }
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_s_barrier();
+                    const int q0 = wid * 32;                     // this wave's query rows
+                    bf16x8 qf[4];
+                    {
+                        const int row = q0 + e_l31;
+#pragma unroll
+                        for (int ks = 0; ks < 4; ++ks)
+                            qf[ks] = *reinterpret_cast<const bf16x8*>(Qimg + row * 128 + (((ks * 2 + e_hi) ^ ((row >> 1) & 7)) << 4));
+                    }
+                    f32x16 o[2];
+                    const float inv = attn256_wave(Kimg, Vimg, qf, o, e_l31, e_hi);
+                    // the transpose patch overlays the wave's OWN query rows of the Q image, as in EPI_QKV_ATTN
+                    char* T = Qimg + wid * 4096;
+                    bf16* dst0 = p.out_bf16 + (size_t)(m0 + q0) * p.ldo + ((n0 / BN) * 2 + side) * 64;
+#pragma unroll
+                    for (int half = 0; half < 2; ++half) {
+                        if ((e_l31 >> 4) == half) {
+#pragma unroll
+                            for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+                                for (int rq = 0; rq < 4; ++rq) {
+                                    bf16x4 o4;
+#pragma unroll
+                                    for (int e2 = 0; e2 < 4; ++e2) o4[e2] = (bf16)(o[ct][rq * 4 + e2] * inv);
+                                    *reinterpret_cast<bf16x4*>(T + (e_l31 & 15) * 144 + ct * 64 + rq * 16 + e_hi * 8) = o4;
+                                }
+                        }
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+#pragma unroll
+                        for (int it2 = 0; it2 < 2; ++it2) {
+                            const int r = it2 * 8 + (e_lane >> 3), c16 = e_lane & 7;
+                            const u32x4 w = *reinterpret_cast<const u32x4*>(T + r * 144 + c16 * 16);
+                            __builtin_nontemporal_store(w, reinterpret_cast<u32x4*>(dst0 + (size_t)(half * 16 + r) * p.ldo + c16 * 8));
+                        }
+                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    }
+                };
+                head(0);
+                wait_vmcnt<0>();                           // this wave's park stores are complete (they were long ago: the wait is head A's output stores)
+#pragma unroll
+                for (int j = 0; j < G::TN; ++j)
+#pragma unroll
+                    for (int i = 0; i < G::TM; ++i) pk[i][j] = __builtin_bit_cast(bf16x8, slot[(j * G::TM + i) * 512]);
+                __builtin_amdgcn_s_barrier();              // every wave is out of head A's images (the reload's latency runs under this wait)
+                head(1);
+                // the next tile starts cold: its first K-step lands in stage 0, under the images
+                __builtin_amdgcn_s_barrier();
+                if (has_next) issue(m0n, n0n, g);
             } else if constexpr (EPI == EPI_BIAS_BF16 && G::WCOLS == 96) {
                 // 256 x 384 tiles, bias -> bf16 (no LayerNorm-3 fold: all of LDS is operand stages).  The 64-column epilogue below moves one 32 x 64 slab
                 // per pass; a wave tile here is 96 columns wide, so it goes one 32 x 32 MFMA tile at a time: swapped accumulators (lane = token row, four
@@ -1635,6 +1823,8 @@ bool dispatch_main(const GemmParams& pg, int epilogue, const GemmPlan& plan, hip
         case main_key(256, EPI_BIAS_RESID, false, false): launch_main<256, EPI_BIAS_RESID, false, false>(pg, plan, s); return true;
         case main_key(256, EPI_UP_DWCONV2, false, false): launch_main<256, EPI_UP_DWCONV2, false, false>(pg, plan, s); return true;
         case main_key(256, EPI_UP_DWCONV32, false, false): launch_main<256, EPI_UP_DWCONV32, false, false>(pg, plan, s); return true;
+        // 256 x 384, two heads of QKV + attention (the newest case: at the end, see above)
+        case main_key(384, EPI_QKV_ATTN2, false, false): launch_main<384, EPI_QKV_ATTN2, false, false>(pg, plan, s); return true;
         default: return false;
     }
 }
@@ -1686,6 +1876,7 @@ int launch_gemm(const GemmParams& p_in, int epilogue, hipStream_t s) {
     auto note_main = [&]() {      // launch-path record of the engine's stage hook (the engine's epilogues only)
         switch (epilogue) {
             case EPI_QKV_ATTN: note_path(EP_QKV_ATTN); break;
+            case EPI_QKV_ATTN2: note_path(EP_QKV_ATTN_PAIR); break;
             case EPI_QKV_LN: note_path(EP_QKV_LN); break;
             case EPI_QKV: note_path(EP_QKV_PLAIN); break;
             case EPI_UP_DWCONV2: note_path(EP_UP_FUSED16); break;
@@ -1749,5 +1940,13 @@ extern "C" TLD_API int tld_debug_gemm_plan(const int32_t* queries, int32_t n, in
         int32_t* o = plans + (size_t)i * TLD_GEMM_PLAN_INTS;
         o[0] = g.family; o[1] = g.bn; o[2] = g.bm; o[3] = g.ring; o[4] = g.xcd_ngroups; o[5] = g.half_tail; o[6] = g.nblocks; o[7] = g.block; o[8] = g.refusal;
     }
+    return TLD_OK;
+}
+
+// Test hook: plan_qkv_pair of each (samples, heads, CU count) row, and the cost ratio it compares with; no device involved
+extern "C" TLD_API int tld_debug_qkv_pair_plan(const int32_t* queries, int32_t n, int32_t* pair, int32_t* cost_ratio) {
+    if (!queries || !pair || n < 0) { tld::set_last_error("tld_debug_qkv_pair_plan: null argument"); return TLD_ERR_INVALID; }
+    for (int32_t i = 0; i < n; ++i) pair[i] = tld::plan_qkv_pair(queries[3 * (size_t)i], queries[3 * (size_t)i + 1], queries[3 * (size_t)i + 2]) ? 1 : 0;
+    if (cost_ratio) { cost_ratio[0] = (int32_t)tld::kQkvPairCostNum; cost_ratio[1] = (int32_t)tld::kQkvPairCostDen; }
     return TLD_OK;
 }

@@ -38,6 +38,9 @@ enum GemmEpilogue {
                          // [head][q_h | k_h | v_h] so that a 256 x 192 tile = everything (sample, head) needs; q, k, v^T go from the
                          // accumulators to LDS, softmax(q k^T / 8) v runs there, and only att[256 x 64] is written (out_bf16, ldo = d).
                          // Needs ntok == 256, N = 3 d = heads x 192, K % 128 == 0.  (tld/transformer_blocks.py:51-59 + 24-48)
+    EPI_QKV_ATTN2 = 9,   // the same on 256 x 384 tiles, TWO heads per tile: W rows in pair order (tld_refresh_math.h: qkv_pair_row), the second head's
+                         // q | k | v parked in GemmParams::park while the first head's attention runs.  Bitwise the results of EPI_QKV_ATTN.  Heads even.
+                         // (8 is not used: kernel names with template argument 8 are read as an up-projection form by the benchmark's trace reader)
 };
 
 struct GemmParams {
@@ -109,6 +112,9 @@ struct GemmParams {
     int cv_down;                  // conv: stride-2 3x3 convolution with padding (0, 1, 0, 1) (diffusers Downsample2D, VAE encoder): output pixel (y, x)
                                   //   and tap (ky, kx) read source pixel (2y + ky, 2x + kx) of a 2 cv_h x 2 cv_w image -- a tap is outside only on the
                                   //   bottom / right pad, which reads the zero page.  Excludes cv_up (launch_gemm refuses both).
+    uint32_t* park;               // EPI_QKV_ATTN2: one slot of kPairSlotDwords per workgroup of the launch (min(tiles, CUs) slots)
 };
+
+constexpr int kPairSlotDwords = 512 * 48;     // EPI_QKV_ATTN2: 512 lanes x 48 packed bf16 pairs = the second head's q | k | v of one 256 x 384 tile (96 KB)
 
 }  // namespace tld

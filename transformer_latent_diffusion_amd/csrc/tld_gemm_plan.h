@@ -60,7 +60,7 @@ constexpr bool gemm_main_instantiated(int bn, int epilogue, bool f8, bool conv) 
     if (conv) return !f8 && plain && (bn == 256 || bn == 128);             // implicit 3x3 convolution (VAE): three epilogues
     if (f8) return (bn == 256 || bn == 128) ? (plain || epilogue == EPI_QKV) : (bn == 192 && epilogue == EPI_BIAS_RESID);      // MX-fp8: four epilogues, 192-wide for the residual add
     switch (bn) {
-        case 384: return epilogue == EPI_BIAS_BF16 || epilogue == EPI_BIAS_RESID;       // residual add (the down projection) and, for the training step's N = 768 linears, bias -> bf16
+        case 384: return epilogue == EPI_BIAS_BF16 || epilogue == EPI_BIAS_RESID || epilogue == EPI_QKV_ATTN2;       // two heads of QKV + attention; residual add (the down projection) and, for the training step's N = 768 linears, bias -> bf16
         case 192: return epilogue == EPI_QKV_ATTN || epilogue == EPI_BIAS_RESID;
         case 256: return plain || epilogue == EPI_QKV || epilogue == EPI_QKV_LN || epilogue == EPI_UP_DWCONV2 || epilogue == EPI_UP_DWCONV32;
         case 128: return plain || epilogue == EPI_QKV || epilogue == EPI_QKV_LN;
@@ -99,6 +99,7 @@ inline int bf16_tile_width(long M, long N, long K, int epilogue) {
     const long ntm = (M + 255) / 256;
     auto whole_rounds = [&](long bn) { return N % bn == 0 && (ntm * (N / bn)) % kPlanCus == 0; };       // the workgroups of bn-wide tiles fill every round of the chip
     if (epilogue == EPI_QKV_ATTN) return 192;          // one tile = one (sample, head): caller guarantees N = heads x 192, ntok == 256
+    if (epilogue == EPI_QKV_ATTN2) return 384;         // one tile = one (sample, head pair): the caller asked plan_qkv_pair first
     if (epilogue == EPI_UP_DWCONV2 || epilogue == EPI_UP_DWCONV32) return 256;          // caller guarantees N % 256 == 0 and one 16x16 image (8 rows of a 32x32 one) per 256 rows
     // INVARIANT (gemm_resid_stat_slots below relies on it): the residual-add epilogue at N % 192 == 0 uses 192- or 384-wide tiles for EVERY batch size, never
     // 128 / 256 -- both give 96-column wave tiles, which is what the LayerNorm-1 partial sums are defined on (results must not depend on the batch size).

@@ -14,6 +14,8 @@ struct Layer {
     float *qkv_c1 = nullptr, *qkv_b1 = nullptr;           // [3d] column sums of qkv_wf; beta1 . Wqkv^T
     bf16 *qkv_wp = nullptr;                               // qkv_wf with its rows permuted to [head][q_h | k_h | v_h] (fused QKV -> attention kernel)
     float *qkv_c1p = nullptr, *qkv_b1p = nullptr;         // the same permutation of qkv_c1 / qkv_b1
+    bf16 *qkv_wp2 = nullptr;                              // qkv_wf in head-pair order (tld_refresh_math.h: qkv_pair_row; the two-head form of that kernel, EPI_QKV_ATTN2)
+    float *qkv_c1p2 = nullptr, *qkv_b1p2 = nullptr;       // the same permutation of qkv_c1 / qkv_b1
     float *up_b = nullptr, *dw_w9c = nullptr, *dw_b = nullptr, *down_b = nullptr;
     float *dw_w9c_half = nullptr, *dw_b_half = nullptr;   // 0.5 x (exact): operands of the fused up-projection epilogue
     uint32_t* dw_wpk = nullptr;                           // the halved taps as packed bf16 pairs [3][4][hid] (EPI_UP_DWCONV2)

@@ -156,6 +156,7 @@ __global__ __launch_bounds__(64) void refresh_fold_kernel(const Layer* __restric
     uint16_t* wp = ln3 ? nullptr : reinterpret_cast<uint16_t*>(Ly.qkv_wp);
     const int part = row0 / d, head = (row0 - part * d) >> 6;
     auto packed_row = [&](int r) { return head * 192 + (r >> 5) * 96 + part * 32 + (r & 31); };
+    uint16_t* wp2 = ln3 ? nullptr : reinterpret_cast<uint16_t*>(Ly.qkv_wp2);      // ... and the two-head form's, where the engine holds it
     double sc = 0.0, sb = 0.0;
     for (int k0 = 0; k0 < d; k0 += 64) {
         const float gk = g[k0 + lane];
@@ -171,6 +172,7 @@ __global__ __launch_bounds__(64) void refresh_fold_kernel(const Layer* __restric
                 const uint16_t q = bf16_bits(gk * w[i]);
                 wf[(int64_t)(row0 + r) * d + k0 + lane] = q;
                 if (wp) wp[(int64_t)packed_row(r) * d + k0 + lane] = q;
+                if (wp2) wp2[(int64_t)qkv_pair_row(part, head, r) * d + k0 + lane] = q;
             }
         }
         __syncthreads();
@@ -188,6 +190,7 @@ __global__ __launch_bounds__(64) void refresh_fold_kernel(const Layer* __restric
     (ln3 ? Ly.up_c1 : Ly.qkv_c1)[n] = c1;
     (ln3 ? Ly.up_b1 : Ly.qkv_b1)[n] = b1;
     if (wp) { Ly.qkv_c1p[packed_row(lane)] = c1; Ly.qkv_b1p[packed_row(lane)] = b1; }      // (the 64 pad entries behind them are not touched)
+    if (wp2) { Ly.qkv_c1p2[qkv_pair_row(part, head, lane)] = c1; Ly.qkv_b1p2[qkv_pair_row(part, head, lane)] = b1; }
 }
 
 // ---- out_proj folded into the last block's down projection: the split bf16 image of [Wout | Wout Wd] and b' = Wout bd + bo -----------------------

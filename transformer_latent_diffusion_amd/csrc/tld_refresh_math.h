@@ -40,4 +40,10 @@ TLD_HD uint8_t e4m3_rne_bits(uint32_t u) {
     return sign | (uint8_t)(q + ((rem > half || (rem == half && (q & 1u))) ? 1u : 0u));
 }
 
+// Row of the pair-ordered QKV weight image (qkv_wp2, EPI_QKV_ATTN2) that holds row r (0 .. 63) of (part = q | k | v, head): a 256 x 384 tile is the head pair
+// head >> 1, its columns [wave column = feature / 16][part][side = head & 1][16 features] -- every 96-column wave tile holds 16 features of q, k and v of both heads
+TLD_HD int qkv_pair_row(int part, int head, int r) {
+    return (head >> 1) * 384 + (r >> 4) * 96 + part * 32 + (head & 1) * 16 + (r & 15);
+}
+
 }  // namespace tld

@@ -485,6 +485,10 @@ class Denoiser:
     FP8_PATH_NAMES = {10: "layernorm mx8", 54: "fp8 separate quantisation pass", 55: "fp8 cross_row writer", 56: "fp8 depthwise tiled",
                       57: "fp8 depthwise streaming"}
 
+    # the two-head form of the fused QKV + attention kernel (taken where whole rounds of head pairs fill the device, or under TLD_QKV_ATTN_PAIR=2): not in
+    # PATH_NAMES, whose cases are small batches; held by tests/test_gpu_qkv_pair.py
+    QKV_PAIR_PATH_NAMES = {61: "QKV + attention, two heads per tile"}
+
     # the launch paths of sample_latents_requests, by bit number
     SAMPLER_PATH_NAMES = {58: "update_requests", 59: "update_requests masked", 60: "start_mix per request"}
 
