@@ -812,6 +812,32 @@ TLD_API int tld_train_read_stage(tld_train* e, const char* name, float* host_out
 TLD_API int tld_train_debug_paths(tld_train* e, uint64_t* mask);
 TLD_API int tld_train_destroy(tld_train* e);
 
+/* ---- Distribution metrics on embedding banks ---------------------------------------------------------------------------
+ * The reference leaves its FID script as a TODO (README.md:237).  These three kernels give the two statistics such a script takes -- the moments of a
+ * Frechet distance and the pair sums of a kernel MMD (CMMD: Jayasumana et al. 2024) -- over embeddings that stay on the device.
+ *
+ * A bank is a plain device fp32 matrix [capacity, pitch]; pitch = dim rounded up to a multiple of 32, pad columns zero; dim in [1, 4096].  Every
+ * entry point takes device pointers, enqueues on hip_stream without synchronising, uses no atomic on a value and repeats bitwise.
+ *
+ * tld_feat_append: rows [used, used + rows) of the bank from src [rows, dim] (contiguous; fp32, bf16 or fp16 by src_dtype).  normalize = 1: each row is
+ * divided by its L2 norm; the squares are added in double in ascending column order, the quotient is formed in double and rounded to fp32 once.  A row
+ * with a non-finite value (or, with normalize = 1, norm 0) is stored as zeros and adds one to *bad_count (device int32; the caller zeroes it).
+ * Refused (TLD_ERR_INVALID, before any HIP call): null pointers, dim, pitch, src_dtype, rows < 1, rows that do not fit [used, capacity). */
+TLD_API int tld_feat_append(float* bank, int64_t capacity, int64_t used, int32_t dim, int32_t pitch, const void* src, int32_t src_dtype, int64_t rows,
+                            int32_t normalize, int32_t* bad_count, void* hip_stream);
+/* mean [dim] and cov [dim, dim] (double, device) of rows [0, n) of the bank: numpy.mean(axis=0) and numpy.cov(rowvar=False) -- ddof = 1, two passes,
+ * centred in double, every sum in a fixed order; cov is symmetric bit for bit.  Refused: null pointers, dim, pitch, n < 2. */
+TLD_API int tld_feat_moments(const float* bank, int64_t n, int32_t dim, int32_t pitch, double* mean, double* cov, void* hip_stream);
+/* Doubles of `partials` a tld_feat_kernel_sum call of these sizes needs (one per 128 x 128 tile of its plan); 0 for sizes it refuses.  Needs no GPU. */
+TLD_API int64_t tld_feat_kernel_sum_partials(int64_t na, int64_t nb, int32_t same);
+/* out[0] = sum_{i < na, j < nb} expm1(-gamma d2_ij), d2_ij = max(0, |a_i|^2 + |b_j|^2 - 2 a_i . b_j), over rows [0, na) of a and [0, nb) of b (banks of one
+ * dim and pitch; 16-byte aligned).  k - 1, not k: the ones cancel exactly in every MMD estimator.  same = 1: b is a, the terms i == j are the constant
+ * 0, and only tiles on or above the diagonal run.  Dot products on the fp32 MFMA, row norms from an fp32 fmaf chain in the same order, expm1f, then
+ * double.  partials [n_partials >= tld_feat_kernel_sum_partials(na, nb, same)] is workspace; nothing outside rows < na / < nb is read.
+ * Refused: null pointers, dim, pitch, na or nb < 1, same = 1 with na != nb or a != b, a negative or non-finite gamma, too few partials. */
+TLD_API int tld_feat_kernel_sum(const float* a, int64_t na, const float* b, int64_t nb, int32_t dim, int32_t pitch, double gamma, int32_t same,
+                                double* partials, int64_t n_partials, double* out, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,7 @@ ABI_SYMBOLS = (
     "tld_train_prepare_batch", "tld_train_prepare_batch_at",
     "tld_train_forward_loss", "tld_train_sample_loss", "tld_train_loss_buckets", "tld_debug_attention_bwd", "tld_debug_wgrad", "tld_debug_attention_fwd", "tld_debug_dwconv_gelu",
     "tld_train_set_debug", "tld_train_read_stage", "tld_train_debug_paths", "tld_train_destroy",
+    "tld_feat_append", "tld_feat_moments", "tld_feat_kernel_sum_partials", "tld_feat_kernel_sum",
     "tld_last_error",
 )
 
@@ -269,11 +270,17 @@ def lib() -> C.CDLL:
         L.tld_train_read_stage.argtypes = [vp, C.c_char_p, C.POINTER(C.c_float), C.c_int64, i64p]
         L.tld_train_debug_paths.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.tld_train_destroy.argtypes = [vp]
+    if hasattr(L, "tld_feat_append"):                # (absent from A/B builds that predate the distribution metrics)
+        L.tld_feat_append.argtypes = [vp, C.c_int64, C.c_int64, i32, i32, vp, i32, C.c_int64, i32, vp, vp]
+        L.tld_feat_moments.argtypes = [vp, C.c_int64, i32, i32, vp, vp, vp]
+        L.tld_feat_kernel_sum_partials.argtypes = [C.c_int64, C.c_int64, i32]
+        L.tld_feat_kernel_sum_partials.restype = C.c_int64
+        L.tld_feat_kernel_sum.argtypes = [vp, C.c_int64, vp, C.c_int64, i32, i32, C.c_double, i32, vp, C.c_int64, vp, vp]
     for name in ABI_SYMBOLS:
         if "TLD_LIB" in os.environ and not hasattr(L, name):     # an older A/B build: symbols added since are simply absent (tests/test_abi.py checks the real library)
             continue
         if name not in ("tld_last_error", "tld_engine_weight_bytes", "tld_vae_weight_bytes", "tld_vae_enc_weight_bytes", "tld_clip_weight_bytes", "tld_clip_vis_weight_bytes", "tld_train_param_count",
-                        "tld_train_tensor_count", "tld_engine_param_count", "tld_opt_plan_numel", "tld_opt_plan_destroy"):
+                        "tld_train_tensor_count", "tld_engine_param_count", "tld_opt_plan_numel", "tld_opt_plan_destroy", "tld_feat_kernel_sum_partials"):
             getattr(L, name).restype = C.c_int
     _lib = L
     return L

@@ -438,6 +438,21 @@ class DiffusionTransformer:
         return clip_score(self.clip_model.encode_image(pixels).float(), self._labels(prompts).to(self.device).float())
 
     @torch.no_grad()
+    def image_features(self, images, bank=None) -> Tensor:
+        """CLIP image embeddings of arbitrary pictures, ``clip_model.encode_image(clip_preprocess(images))``: PIL images or a float tensor
+        ``[B, 3, H, W]`` in [0, 1] -> ``[B, embed_dim]`` fp32 on the device; with ``bank`` (a ``metrics.FeatureBank``) they are appended to it as
+        well.  This builds the reference bank of real images that ``metrics.cmmd`` / ``metrics.frechet_distance`` compare generated samples with
+        (``Trainer.eval_features`` fills the other one).  Needs a ``clip_model`` with an image tower, like ``clip_scores``."""
+        from .metrics import image_embeddings
+        if self.clip_model is None or not hasattr(self.clip_model, "encode_image"):
+            raise RuntimeError("image_features needs a clip_model with encode_image (the image tower): pass clip_model=Clip(text=..., visual=...); "
+                               f"this pipeline holds {type(self.clip_model).__name__}")
+        emb = image_embeddings(self.clip_model, images, self.device)
+        if bank is not None:
+            bank.add(emb)
+        return emb
+
+    @torch.no_grad()
     def generate_images_from_texts(self, prompts, class_guidance=6, seeds=11, n_iter=15, negative_prompts=None, guidance_interval=None):
         """Batched front edge (the reference serves one prompt per call, tld/app.py:48-65):
         one text-encoder call for all prompts, labels stay on the device, ONE sampler call (sample-sharded over the

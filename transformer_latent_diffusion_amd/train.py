@@ -948,6 +948,21 @@ class Trainer:
         used = torch.repeat_interleave(labels, 2, dim=0)[:emb.shape[0]].to(self.device)
         return latents, images, clip_score(emb, used)
 
+    @torch.no_grad()
+    def eval_features(self, labels: torch.Tensor, vae, clip_image, bank, **eval_generate_kwargs):
+        """``eval_generate`` plus the CLIP image embedding of every sample, appended to ``bank`` (a ``metrics.FeatureBank``): the decoded images go
+        from [-1, 1] to [0, 1], through ``clip_preprocess`` and ``clip_image.encode_image`` -- the chain of ``eval_clip_score`` -- and ``bank.add``
+        stores them (L2-normalised if the bank says so) with no host synchronisation.  Returns ``(latents, images)``.  Call it in a loop over label
+        batches and seeds to fill a bank, then ``metrics.cmmd`` / ``metrics.frechet_distance`` against a bank of real images
+        (``DiffusionTransformer.image_features``).  This rank's samples only: gathering banks across ranks is left to the caller.  Touches nothing
+        of the training step's state, like ``eval_generate``."""
+        from .metrics import image_embeddings
+        if vae is None:
+            raise ValueError("eval_features needs a vae: the embeddings are taken on decoded images")
+        latents, images = self.eval_generate(labels, vae, **eval_generate_kwargs)
+        bank.add(image_embeddings(clip_image, (images.to(self.device, torch.float32) * 0.5 + 0.5).clamp(0.0, 1.0), self.device))
+        return latents, images
+
     # ---- checkpoint / resume ----------------------------------------------------------------------------------------------------
     def optimizer_state_dict(self) -> Dict[str, object]:
         """``torch.optim.Adam(model.parameters(), lr).state_dict()`` as the reference saves it (tld/train.py:86,152): per-parameter
