@@ -1,21 +1,24 @@
-// tld_attn_core.h -- one wave's share of a 256-key self-attention head with q, k, v^T already resident in LDS.
+// tld_attn_core.h -- one wave's share of a 256-key self-attention head with q, k, v already resident in LDS.
 //
 // softmax(q k^T / sqrt(64)) v for 32 query rows against 256 keys, head_dim 64 (tld/transformer_blocks.py:37-44: non-causal, no mask,
-// no dropout in eval).  Used by the fused QKV -> attention epilogue of the GEMM (tld_gemm.hip, EPI_QKV_ATTN), where the operands come
-// straight from the accumulators of the head's 256 x 192 (q_h | k_h | v_h) tile and never travel through HBM.  Same arithmetic as
+// no dropout in eval).  Used by the fused QKV -> attention epilogues of the GEMM (tld_gemm.hip, EPI_QKV_ATTN and EPI_QKV_ATTN2), where the
+// operands come straight from the accumulators of the head's q | k | v columns and never travel through HBM.  Same arithmetic as
 // attn1_kernel (tld_attn.hip): scores TRANSPOSED (S^T = K Q^T, a lane owns one query column), row max / row sum lane-local plus one
 // lane^32 exchange, exp2 output converted in place into the B operand of O^T = V^T P^T, V^T gathered with the P operand's key order.
 //
-// LDS images (written by the caller):
-//   K   [256 keys][64 features] bf16, 128-byte rows, 16-byte chunk c of row r at chunk c ^ ((r >> 1) & 7)
-//   Q   [256 queries][64]       bf16, same image
-//   V^T [64 features][256 keys] bf16, row pitch 520 bytes (512 + 8: the 32 lanes of an 8-byte read hit 32 distinct bank pairs)
+// LDS images (written by the caller, all three [256 rows][64 features] bf16 in 128-byte rows, one 8-byte store per accumulator quad):
+//   K   16-byte chunk c of row r at chunk c ^ ((r >> 1) & 7); read by rows, 16 bytes per lane
+//   Q   the same image
+//   V   row-major too, with a swizzle of its own (tld_attn_vimage.h).  The A operand of O^T = V^T P^T -- 8 keys of one feature per lane -- is
+//       read out of it with the transposing LDS read ds_read_b64_tr_b16, two reads per fragment: the instruction count of the two 8-byte
+//       reads a transposed image V^T [64][256 + pad] took, without the 32 two-byte stores per lane and head that writing V^T cost.
+// The transposing read gathers across lanes: EXEC must be all ones, so attn256_wave is called by whole waves outside any divergent region.
 #pragma once
 #include "tld_common.h"
+#include "tld_attn_vimage.h"
 
 namespace tld {
 
-constexpr int kAttnVPitch = 256 * 2 + 8;
 constexpr float kAttnScaleLog2e = 0.125f * 1.44269504088896340736f;   // (1 / sqrt(64)) * log2(e)
 
 // o[ct][r]: O^T accumulators (feature tile ct, lane = query l31); returns 1 / (softmax denominator) of the lane's query
@@ -68,13 +71,19 @@ __device__ __forceinline__ float attn256_wave(const char* Ks, const char* Vs, co
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[ct][r] = 0.f;
     float l_run = 0.f;
-    auto vfrag = [&](int s2, int ct) {                 // step s2 = 2 t + hf: keys s2 * 16 + hi * 4 .. (+3, +8 .. +11)
-        const char* vp = Vs + (ct * 32 + l31) * kAttnVPitch + (s2 * 16 + hi * 4) * 2;
-        const uint2 v0 = *reinterpret_cast<const uint2*>(vp);
-        const uint2 v1 = *reinterpret_cast<const uint2*>(vp + 16);
-        union { uint4 u; bf16x8 v; } cvt;
-        cvt.u = make_uint4(v0.x, v0.y, v1.x, v1.y);
-        return cvt.v;
+    const int vbase = attn_v_tr_addr(hi * 32 + l31, 0, 0, 0);
+    static_assert(attn_v_tr_step(0, 0, 1, 0) == 64 && attn_v_tr_step(64, 0, 1, 0) == 0, "feature tile 1 is the base with bit 6 flipped");
+    auto vfrag = [&](int s2, int ct) {                 // step s2 = 2 t + hf: feature 32 ct + l31 of keys s2 * 16 + hi * 4 .. (+3, +8 .. +11)
+        typedef short s16x4 __attribute__((ext_vector_type(4)));
+        typedef short s16x8 __attribute__((ext_vector_type(8)));
+        // feature tile 1: the XOR is made where it is used (volatile: not hoisted into a second base register that would live through the whole phase --
+        // the two-head kernel has none to spare); key step and read are immediates of the instruction
+        int vb = vbase;
+        if (ct) asm volatile("v_xor_b32 %0, 64, %1" : "=v"(vb) : "v"(vbase));
+        const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(Vs + attn_v_tr_step(vb, s2, 0, 0)));
+        const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(Vs + attn_v_tr_step(vb, s2, 0, 1)));
+        const s16x8 v = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+        return __builtin_bit_cast(bf16x8, v);
     };
     auto probs = [&](int s2) {
         bf16x8 pf;

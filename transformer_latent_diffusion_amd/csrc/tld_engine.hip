@@ -376,7 +376,7 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
             else { launch_layernorm_bf16(half ? xe : e->x, Ly.n1_w, Ly.n1_b, e->xn, Ml, d, s); SNAP(blk_name(l, "xn1"), e->xn, ST_BF16, s, Ml, d); }
         }
         // 256-token grids with the LayerNorm-1 fold: the QKV projection and the whole self-attention of a (sample, head) are one 256 x 192
-        // GEMM tile + epilogue; q | k, v^T never reach HBM and `att` is written directly.  (the fp8 mode keeps the two kernels)
+        // GEMM tile + epilogue; q, k, v never reach HBM and `att` is written directly.  (the fp8 mode keeps the two kernels)
         const bool fused_qa = eng_fused_qa(e);
         if (fused_qa) {
             ProfScope ps(e, KC_GEMM_QKV, s);

@@ -91,15 +91,16 @@ struct G256P : G256<BN> {
     static constexpr int PLAINCB_OFF = PLAINRS_OFF + 256 * 8;       // ... and c1 | bias of the tile's columns (fp32; bf16 operands, no conv)
     static constexpr int PLAINLN_LDS = PLAINCB_OFF + 2048;
     static constexpr int SCRATCH = 4608;             // per-wave epilogue scratch (8 x 4608 <= one stage)
-    // EPI_QKV_ATTN (BN = 192): stage 0 keeps receiving the next tile's first K-step while the epilogue runs; the head's K, V^T and Q
+    // EPI_QKV_ATTN (BN = 192): stage 0 keeps receiving the next tile's first K-step while the epilogue runs; the head's K, V and Q
     // images live behind it (stage 1, which a tile of an even number of K-steps consumes last, the LayerNorm side tables -- dead once the
     // accumulators are normalised -- and the rest of the CU's 160 KiB)
-    static constexpr int AT_K = STAGE_BYTES, AT_V = AT_K + 256 * 128, AT_Q = AT_V + 64 * kAttnVPitch, ATTN_LDS = AT_Q + 256 * 128;
+    static constexpr int AT_K = STAGE_BYTES, AT_V = AT_K + 256 * 128, AT_Q = AT_V + kAttnVImageBytes, ATTN_LDS = AT_Q + 256 * 128;
     // EPI_QKV_ATTN2 (BN = 384): the two stages are all of the CU's 160 KiB, so nothing is prefetched under the epilogue (tiles start cold, always in
     // stage 0) and the LayerNorm side tables arrive by DMA during the tile's LAST K-step, at the bottom of stage 0, which that step no longer reads
-    // (K-steps per tile are even).  The three images of ONE head follow them: they overlay no table, so the second head's pass needs no table again.
+    // (K-steps per tile are even).  Five 32-KiB images -- k, v of both heads and one q -- are the 160 KiB to the byte (tld_attn_vimage.h: the map; the one
+    // that overlays the tables is written behind the barrier that ends the table reads).
     static constexpr int P2_RAW = 0, P2_ST = P2_RAW + 256 * 8 * kLnSlots, P2_CB = P2_ST + 256 * 8;       // row partial sums | (mean, rstd) | c1[384], b1[384]
-    static constexpr int P2_K = P2_CB + 2 * 384 * 4 + 3072, P2_V = P2_K + 256 * 128, P2_Q = P2_V + 64 * kAttnVPitch, PAIR_LDS_END = P2_Q + 256 * 128;
+    static_assert(BN != 384 || P2_CB + 2 * 384 * 4 == kPairTabBytes, "the image map of tld_attn_vimage.h is laid around these tables");
 };
 
 // F8 = true: both operands are OCP e4m3 bytes with MX block scales (one E8M0 byte per 32 K-elements), multiplied by
@@ -131,7 +132,7 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, int nblocks
     static_assert(EPI != EPI_QKV_ATTN || G::ATTN_LDS <= 160 * 1024, "LDS");
     constexpr bool PAIR = EPI == EPI_QKV_ATTN2;                       // two heads per 256 x 384 tile (see the epilogue)
     static_assert(!PAIR || (BN == 384 && !F8 && !CONV && !RING && !TN), "the two-head attention epilogue is written for 256 x 384 tiles");
-    static_assert(!PAIR || G::PAIR_LDS_END <= G::LDS_BYTES, "LDS");
+    static_assert(!PAIR || G::LDS_BYTES == kPairLdsBytes, "LDS");
     constexpr bool COLD = UPDW || PAIR;                               // the epilogue owns all of LDS: no prefetch of the next tile under it
     static_assert(8 * G::SCRATCH <= G::STAGE_BYTES, "epilogue scratch must fit in one stage");
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1279,7 +1280,7 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, int nblocks
             } else if constexpr (EPI == EPI_QKV_ATTN) {
                 // ---- fused self-attention of (sample m0 / 256, head n0 / 192).  The accumulators hold x W'^T for the head's q | k | v columns
                 // (swapped order: lane = token row, registers = 4 consecutive columns per quad).  LayerNorm-1 is applied in place exactly as
-                // in EPI_QKV_LN, then q, k (row images, the GEMM's 128-byte rows + XOR swizzle) and v^T go to LDS and every wave runs the
+                // in EPI_QKV_LN, then q, k (row images, the GEMM's 128-byte rows + XOR swizzle) and v (row-major too, tld_attn_vimage.h) go to LDS and every wave runs the
                 // head's attention for 32 query rows (tld_attn_core.h).  Only att[256 x 64] is stored.
                 int e_lane = lane, e_l31 = l31, e_hi = hi;
                 asm volatile("" : "+v"(e_lane), "+v"(e_l31), "+v"(e_hi));
@@ -1348,9 +1349,7 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, int nblocks
                                 char* img = j == 0 ? Qimg : Kimg;
                                 *reinterpret_cast<bf16x4*>(img + row * 128 + ((((f >> 3) ^ ((row >> 1) & 7)) << 4) | ((f & 7) << 1))) = pk;
                             } else {
-#pragma unroll
-                                for (int e2 = 0; e2 < 4; ++e2)
-                                    *reinterpret_cast<bf16*>(Vimg + (f + e2) * kAttnVPitch + row * 2) = pk[e2];
+                                *reinterpret_cast<bf16x4*>(Vimg + attn_v_off(row, f)) = pk;
                             }
                         }
                     }
@@ -1407,8 +1406,8 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, int nblocks
             } else if constexpr (PAIR) {
                 // ---- fused self-attention of (sample m0 / 256, heads 2 n0 / 384 and 2 n0 / 384 + 1): the 384-wide K loop is balanced between LDS reads and
                 // MFMAs where the 192-wide one is LDS-bound, but 160 KiB of LDS and 256 registers hold ONE head's attention state.  So the
-                // epilogue of EPI_QKV_ATTN runs twice over the same three images, and while head A is worked on, head B's q | k | v wait as packed bf16 in
-                // the workgroup's slot of GemmParams::park (96 KB, L2-resident).
+                // attention of EPI_QKV_ATTN runs twice: head B's k and v wait in LDS images of their own (V row-major is 32 KiB, so five images fit), and
+                // while head A is worked on only head B's q waits as packed bf16 in the workgroup's slot of GemmParams::park (32 KB, L2-resident).
                 // Tile column c = [wave column wn = c / 96][part (c % 96) / 32: q | k | v][side (c % 32) / 16: head A | B][16 features]: feature 16 wn + c % 16 of
                 // the head.  In the swapped accumulators (lane = token row, register quad rq = columns 8 rq + 4 hi .. + 3 of a 32-column block) quads 0, 1 are
                 // head A's and quads 2, 3 head B's: every wave holds a share of both heads, nothing moves between waves.
@@ -1437,12 +1436,25 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, int nblocks
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                     __builtin_amdgcn_s_barrier();
                 }
-                // The slot is written and read lane-linearly, 16 bytes per lane and access (one contiguous KiB per wave), and each lane reads back exactly the
-                // bytes it stored: program order of ONE thread on its own addresses, which the memory path keeps per wave -- no other wave, workgroup or agent
-                // ever touches these bytes, so no fence and no cache maintenance is involved.  The s_waitcnt vmcnt(0) before the reload only makes the stores'
-                // completion explicit (and keeps the compiler from forwarding the stored registers to the loads, which would keep head B live).
+                // Head A's k, v, q and head B's k go from the corrected accumulators straight to four images that overlay no table (tld_attn_vimage.h: the
+                // map); head B's v follows into the fifth, over the tables, behind the barrier that ends the table reads; only head B's q has to wait, in the
+                // workgroup's slot of GemmParams::park.  The slot is written and read lane-linearly, 16 bytes per lane and access (one contiguous KiB per
+                // wave), and each lane reads back exactly the bytes it stored: program order of ONE thread on its own addresses, which the memory path keeps
+                // per wave -- no other wave, workgroup or agent ever touches these bytes, so no fence and no cache maintenance is involved.  The s_waitcnt
+                // vmcnt(0) before the reload only makes the stores' completion explicit (and keeps the compiler from forwarding the stored registers to the
+                // loads, which would keep q_B live through head A's attention).
                 u32x4* slot = reinterpret_cast<u32x4*>(p.park) + (size_t)blockIdx.x * (kPairSlotDwords / 4) + tid;
-                bf16x8 pk[G::TM][G::TN];              // one head's values of this lane: [32-row block][q | k | v][quad (0, 1) x 4 columns]
+                char* KAimg = smem + kPairKA;
+                char* VAimg = smem + kPairVA;
+                char* Qimg = smem + kPairQ;
+                char* KBimg = smem + kPairKB;
+                char* VBimg = smem + kPairVB;
+                // one register quad of the lane's token row: 4 consecutive features f .. f + 3 of q, k (the GEMM's row image) or v (tld_attn_vimage.h)
+                auto put = [&](char* img, bool v, int row, int f, const bf16x4 q4) {
+                    *reinterpret_cast<bf16x4*>(img + (v ? attn_v_off(row, f) : row * 128 + ((((f >> 3) ^ ((row >> 1) & 7)) << 4) | ((f & 7) << 1)))) = q4;
+                };
+                bf16x8 pk[G::TM][G::TN];              // head A's values of this lane: [32-row block][q | k | v][quad (0, 1) x 4 columns]
+                bf16x8 kvb[2][G::TM];                 // head B's k and v: [k | v][32-row block][quad (2, 3) x 4 columns]
                 {
                     float rs[G::TM], nm[G::TM];
 #pragma unroll
@@ -1465,13 +1477,14 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, int nblocks
                                 acc[i][j][rq * 4 + 3] = fmaf(rs[i], acc[i][j][rq * 4 + 3], fmaf(nm[i], c4.w, b4.w));
                             }
                         }
-                        // head B of this part: rounded as the image write rounds, parked, dead
+                        // head B of this part, rounded as the image write rounds: q is parked and dead, k and v shrink to packed pairs
 #pragma unroll
                         for (int i = 0; i < G::TM; ++i) {
                             bf16x8 b;
 #pragma unroll
                             for (int e2 = 0; e2 < 8; ++e2) b[e2] = (bf16)acc[i][j][8 + e2];
-                            slot[(j * G::TM + i) * 512] = __builtin_bit_cast(u32x4, b);
+                            if (j == 0) slot[i * 512] = __builtin_bit_cast(u32x4, b);
+                            else kvb[j - 1][i] = b;
                         }
                     }
 #pragma unroll
@@ -1481,33 +1494,20 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, int nblocks
 #pragma unroll
                             for (int e2 = 0; e2 < 8; ++e2) pk[i][j][e2] = (bf16)acc[i][j][e2];
                 }
-                char* Kimg = smem + G::P2_K;
-                char* Vimg = smem + G::P2_V;
-                char* Qimg = smem + G::P2_Q;
-                // one head from pk: images, attention of this wave's 32 query rows, transposed store -- the body of EPI_QKV_ATTN with 16 features per wave column
-                auto head = [&](int side) {
+                // (the accumulators are dead: the image addresses below cost the correction no register)
+                auto put8 = [&](char* img, bool v, int i, const bf16x8 b) {      // a lane's two quads of one 32-row block
 #pragma unroll
-                    for (int j = 0; j < G::TN; ++j) {
+                    for (int rq = 0; rq < 2; ++rq)
+                        put(img, v, wm * G::WROWS + i * 32 + e_l31, wn * 16 + 8 * rq + 4 * e_hi, bf16x4{b[rq * 4 + 0], b[rq * 4 + 1], b[rq * 4 + 2], b[rq * 4 + 3]});
+                };
 #pragma unroll
-                        for (int i = 0; i < G::TM; ++i) {
-                            const int row = wm * G::WROWS + i * 32 + e_l31;
+                for (int i = 0; i < G::TM; ++i) { put8(Qimg, false, i, pk[i][0]); put8(KAimg, false, i, pk[i][1]); put8(VAimg, true, i, pk[i][2]); put8(KBimg, false, i, kvb[0][i]); }
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();              // the four images are complete, and every wave is done with the tables: V_B overlays them
 #pragma unroll
-                            for (int rq = 0; rq < 2; ++rq) {
-                                const bf16x4 q4 = {pk[i][j][rq * 4 + 0], pk[i][j][rq * 4 + 1], pk[i][j][rq * 4 + 2], pk[i][j][rq * 4 + 3]};
-                                const int f = wn * 16 + 8 * rq + 4 * e_hi;                 // feature inside q, k or v
-                                if (j < 2) {
-                                    char* img = j == 0 ? Qimg : Kimg;
-                                    *reinterpret_cast<bf16x4*>(img + row * 128 + ((((f >> 3) ^ ((row >> 1) & 7)) << 4) | ((f & 7) << 1))) = q4;
-                                } else {
-#pragma unroll
-                                    for (int e2 = 0; e2 < 4; ++e2)
-                                        *reinterpret_cast<bf16*>(Vimg + (f + e2) * kAttnVPitch + row * 2) = q4[e2];
-                                }
-                            }
-                        }
-                    }
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_s_barrier();
+                for (int i = 0; i < G::TM; ++i) put8(VBimg, true, i, kvb[1][i]);
+                // one head from its images: attention of this wave's 32 query rows, transposed store -- the body of EPI_QKV_ATTN
+                auto head = [&](const char* Kimg, const char* Vimg, int side) {
                     const int q0 = wid * 32;                     // this wave's query rows
                     bf16x8 qf[4];
                     {
@@ -1544,15 +1544,18 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, int nblocks
                         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
                     }
                 };
-                head(0);
+                head(KAimg, VAimg, 0);                     // (V_B's writes retire under it: the barriers below stand between them and head B's reads)
                 wait_vmcnt<0>();                           // this wave's park stores are complete (they were long ago: the wait is head A's output stores)
+                u32x4 qb[G::TM];
 #pragma unroll
-                for (int j = 0; j < G::TN; ++j)
+                for (int i = 0; i < G::TM; ++i) qb[i] = slot[i * 512];
+                __builtin_amdgcn_s_barrier();              // every wave is out of head A's Q rows and transpose patches (the reload's latency runs under this wait)
 #pragma unroll
-                    for (int i = 0; i < G::TM; ++i) pk[i][j] = __builtin_bit_cast(bf16x8, slot[(j * G::TM + i) * 512]);
-                __builtin_amdgcn_s_barrier();              // every wave is out of head A's images (the reload's latency runs under this wait)
-                head(1);
-                // the next tile starts cold: its first K-step lands in stage 0, under the images
+                for (int i = 0; i < G::TM; ++i) put8(Qimg, false, i, __builtin_bit_cast(bf16x8, qb[i]));
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                head(KBimg, VBimg, 1);
+                // the next tile starts cold: its first K-step lands in stage 0, under the images (every byte of LDS is an image until this barrier)
                 __builtin_amdgcn_s_barrier();
                 if (has_next) issue(m0n, n0n, g);
             } else if constexpr (EPI == EPI_BIAS_BF16 && G::WCOLS == 96) {

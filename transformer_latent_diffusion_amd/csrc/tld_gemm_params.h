@@ -35,11 +35,11 @@ enum GemmEpilogue {
                          // the depthwise conv: token-pair image in LDS, packed-bf16 taps on v_dot2c_f32_bf16; needs ntok == 256, BN == 256.
                          // Value 4 was the first form of this epilogue, retired in round 4.)
     EPI_QKV_ATTN = 7,    // QKV GEMM (LayerNorm-1 folded in) + the head's whole self-attention in the epilogue: W rows are permuted to
-                         // [head][q_h | k_h | v_h] so that a 256 x 192 tile = everything (sample, head) needs; q, k, v^T go from the
+                         // [head][q_h | k_h | v_h] so that a 256 x 192 tile = everything (sample, head) needs; q, k, v go from the
                          // accumulators to LDS, softmax(q k^T / 8) v runs there, and only att[256 x 64] is written (out_bf16, ldo = d).
                          // Needs ntok == 256, N = 3 d = heads x 192, K % 128 == 0.  (tld/transformer_blocks.py:51-59 + 24-48)
     EPI_QKV_ATTN2 = 9,   // the same on 256 x 384 tiles, TWO heads per tile: W rows in pair order (tld_refresh_math.h: qkv_pair_row), the second head's
-                         // q | k | v parked in GemmParams::park while the first head's attention runs.  Bitwise the results of EPI_QKV_ATTN.  Heads even.
+                         // k and v in LDS images of their own and its q parked in GemmParams::park while the first head's attention runs.  Bitwise the results of EPI_QKV_ATTN.  Heads even.
                          // (8 is not used: kernel names with template argument 8 are read as an up-projection form by the benchmark's trace reader)
 };
 
@@ -115,6 +115,6 @@ struct GemmParams {
     uint32_t* park;               // EPI_QKV_ATTN2: one slot of kPairSlotDwords per workgroup of the launch (min(tiles, CUs) slots)
 };
 
-constexpr int kPairSlotDwords = 512 * 48;     // EPI_QKV_ATTN2: 512 lanes x 48 packed bf16 pairs = the second head's q | k | v of one 256 x 384 tile (96 KB)
+constexpr int kPairSlotDwords = 512 * 16;     // EPI_QKV_ATTN2: 512 lanes x 16 packed bf16 pairs = the second head's q of one 256 x 384 tile (32 KB); its k and v stay in LDS
 
 }  // namespace tld
