@@ -121,6 +121,23 @@ def test_spec_and_synth_agree():
     assert ClipVisionConfig().tokens == 257 and dict(clip_visual_spec(ClipVisionConfig()))["visual.conv1.weight"] == (1024, 3, 14, 14)
 
 
+@pytest.mark.parametrize("which", ["text TINY seed 3", "visual 14 2 64 seed 0", "visual 14 2 128 embed 768 seed 0"])
+def test_synthetic_weights_are_pinned(which):
+    """sha1 of every tensor (shape and fp32 bytes) of both towers' deterministic initialisation, as recorded in tests/golden/clip_synth_digests.json
+    before the towers shared their spec and draw helpers: the draw order, dtypes and scales are part of every pinned GPU result."""
+    import hashlib
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "clip_synth_digests.json")) as f:
+        want = json.load(f)[which]
+    sd = {"text TINY seed 3": lambda: synth_clip_state_dict(TEXT_TINY, 3), "visual 14 2 64 seed 0": lambda: synth_clip_visual_state_dict(vcfg(14, 2, 64), 0),
+          "visual 14 2 128 embed 768 seed 0": lambda: synth_clip_visual_state_dict(vcfg(14, 2, 128, embed_dim=768), 0)}[which]()
+    assert list(sd) == list(want)                                   # the same keys in the same order
+    for k, v in sd.items():
+        assert v.dtype == np.float32
+        assert hashlib.sha1(repr(tuple(v.shape)).encode() + np.ascontiguousarray(v).tobytes()).hexdigest() == want[k], k
+
+
 def test_full_clip_dict_loads_into_both_towers():
     cfg = vcfg(14, 2, 64)
     sd = _full_clip_dict(cfg)

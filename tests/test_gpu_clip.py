@@ -103,6 +103,7 @@ def test_clip_abi_error_paths():
     a = np.zeros((3, 3), np.float32)
     shp = (C.c_int64 * 2)(3, 3)
     assert L.tld_clip_load_tensor(h, b"nonsense", a.ctypes.data_as(C.c_void_p), shp, 2, 0) == 2
+    assert L.tld_clip_load_tensor(h, b"text_projection", a.ctypes.data_as(C.c_void_p), None, 2, 0) == 1 and b"bad argument" in L.tld_last_error()   # null shape
     assert L.tld_clip_load_tensor(h, b"visual.proj", a.ctypes.data_as(C.c_void_p), shp, 2, 0) == 0           # ignored
     assert L.tld_clip_load_tensor(h, b"token_embedding.weight", a.ctypes.data_as(C.c_void_p), shp, 2, 0) == 0
     assert L.tld_clip_finalize_weights(h) == 3 and b"token_embedding.weight" in L.tld_last_error()

@@ -1,4 +1,4 @@
-"""The ONE contract of the stage hook (StageStore, csrc/tld_host.h; the block in include/tld_hip.h), asserted through the C ABI on each of the five
+"""The ONE contract of the stage hook (StageStore, csrc/tld_host.h; the block in include/tld_hip.h), asserted through the C ABI on each of the six
 handles at its smallest test configuration: shapes and status codes only."""
 import ctypes as C
 import warnings
@@ -72,6 +72,19 @@ def _clip():
                   b"blk1.qkv", lambda B: [B * TINY.context_length, 3 * TINY.width, 1, 1], enc._drop_engine)
 
 
+def _clip_vis():
+    from test_clip_vision_host import vcfg
+    from transformer_latent_diffusion_amd.clip_image import ClipImageEncoder, synth_clip_visual_state_dict
+    cfg = vcfg(14, 2, 64)                                        # 5 tokens, width 64, two layers
+    enc = ClipImageEncoder(cfg, max_batch=2)
+    enc.load_state_dict({k: torch.from_numpy(v) for k, v in synth_clip_visual_state_dict(cfg, 6).items()})
+    enc.to(_dev())
+    enc._ensure_engine(_dev())
+    pix = torch.randn(2, 3, 28, 28, generator=torch.Generator().manual_seed(9)).to(_dev())
+    return Handle(enc.set_debug, lambda B: enc.encode_image(pix[:B]), lambda name, buf, numel, shape4: _lib.lib().tld_clip_vis_read_stage(enc._engine, name, buf, numel, shape4),
+                  b"blk1.qkv", lambda B: [B * 5, 192, 1, 1], enc._drop_engine)
+
+
 def _training():
     from transformer_latent_diffusion_amd import DenoiserConfig, Trainer
     cfg = DenoiserConfig(image_size=8, n_channels=4, n_layers=1)          # G = 4, 16 tokens: the smallest grid of tests/test_gpu_train_grids.py
@@ -83,7 +96,7 @@ def _training():
                   lambda B: [B * 16, 3 * cfg.embed_dim, 1, 1])
 
 
-HANDLES = {"denoiser": _denoiser, "vae_decoder": lambda: _vae(False), "vae_encoder": lambda: _vae(True), "clip": _clip, "training": _training}
+HANDLES = {"denoiser": _denoiser, "vae_decoder": lambda: _vae(False), "vae_encoder": lambda: _vae(True), "clip": _clip, "clip_vis": _clip_vis, "training": _training}
 
 
 @pytest.mark.gpu

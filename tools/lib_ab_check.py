@@ -5,8 +5,8 @@ outputs of two builds that only re-order work must be BITWISE equal).  One "part
 Then the VAE: a tiny decoder (latent side 8: one sample per attention step, no fused GroupNorm statistics; side 16: batched attention, fused statistics)
 and a tiny encoder (64 px, fp32 and bf16 input), B = 2 -- the output and every captured stage as parts, plus a "vae <name> weight_bytes ... launches ..." line each.
 Then the CLIP text tower with the stage hook off: encode_text of the cases of tests/test_gpu_clip.py (tiny chunked, ViT-L/14 at 4 prompts, both g13 geometries)
-and of 64 prompts on a two-layer ViT-L/14 tower.
-Then the stage hooks ON: one forward of the tiny denoiser, one encode of the tiny text tower and one tiny training step (loss, gradient vector), each with
+and of 64 prompts on a two-layer ViT-L/14 tower; and the CLIP image tower: a 5-token tower chunked (5 images, 2 per call; fp32 and bf16 pixels) and a 257-token case.
+Then the stage hooks ON: one forward of the tiny denoiser, one encode of the tiny text tower and of the tiny image tower and one tiny training step (loss, gradient vector), each with
 every stage its header block names as a part ("absent <name>" where the engine's path has no such stage).
     TLD_LIB=<lib.so> python tools/lib_ab_check.py out.npy"""
 import hashlib, os, sys
@@ -87,6 +87,20 @@ for tag in ("tiny", "l14"):
     clip_part(f"clip g13 {tag}", gcfg, gsd, gtext, 8)
 c2 = ClipTextConfig(layers=2)
 clip_part("clip l14 two layers 64 prompts", c2, synth_clip_state_dict(c2, 0), _tokens(c2, 64, 5), 64)
+# the CLIP image tower, debug off: the tiny tower chunked (5 images, 2 per call) in fp32 and bf16 pixels, and the 257-token case of tests/test_gpu_clip_vision.py
+from test_clip_vision_host import CASES, case_pixels, case_weights, vcfg
+from transformer_latent_diffusion_amd.clip_image import ClipImageEncoder, synth_clip_visual_state_dict
+def clip_vis_part(name, vc, vsd, pix, max_batch):
+    ve = ClipImageEncoder(vc, max_batch=max_batch)
+    ve.load_state_dict(vsd)
+    parts[name] = ve.to(dev).encode_image(pix.to(dev)).cpu().numpy()
+    ve._drop_engine()
+vtiny = vcfg(14, 2, 64)
+vtiny_sd = {k: torch.from_numpy(v) for k, v in synth_clip_visual_state_dict(vtiny, 3).items()}
+vpix = torch.randn(5, 3, 28, 28, generator=rg)
+for dt in (torch.float32, torch.bfloat16):
+    clip_vis_part(f"clip_vis tiny 5 images {dt}".replace("torch.", ""), vtiny, vtiny_sd, vpix.to(dt), 2)
+clip_vis_part("clip_vis T257W128", CASES["T257W128"][0], case_weights("T257W128"), case_pixels("T257W128"), CASES["T257W128"][2])
 # the stage hooks on: every stage name of include/tld_hip.h is tried, so a stage that appears or disappears shows as a changed line
 staged = set()
 def stage_parts(tag, names, read):
@@ -111,6 +125,13 @@ parts["clip tiny debug encode"] = ce.encode_text(_tokens(TINY, 3, 1).to(dev)).cp
 cblk = "h1 qkv att attn_out x1 h2 f_pre f mlp_out x2 in_w out_w fc_w proj_w".split()
 stage_parts("clip stage", ["x0", "pooled", "out", "proj_t"] + [f"blk{i}.{n}" for i in range(TINY.layers) for n in cblk], lambda n: ce.read_stage(n).numpy())
 ce._drop_engine()
+ve = ClipImageEncoder(vtiny, max_batch=4)
+ve.load_state_dict(vtiny_sd)
+ve.to(dev).set_debug(True)
+parts["clip_vis tiny debug encode"] = ve.encode_image(vpix[:3].to(dev)).cpu().numpy()
+stage_parts("clip_vis stage", ["patches", "emb", "x0", "pooled", "out", "conv_w", "proj_t"] + [f"blk{i}.{n}" for i in range(vtiny.layers) for n in cblk],
+            lambda n: ve.read_stage(n).numpy())
+ve._drop_engine()
 from transformer_latent_diffusion_amd import Trainer
 tr = Trainer(ct, device=dev, state_dict={k: torch.from_numpy(np.array(v)) for k, v in sdt.items()}, max_batch=2).set_debug(True)
 loss, pred = tr.forward_backward((0.6 * z0[:2] + 0.4 * eps[:2]).contiguous(), torch.tensor([0.4, 0.7]), labels[:2], z0[:2])

@@ -15,8 +15,6 @@ deterministic random weights (no checkpoint can be downloaded here).
 """
 from __future__ import annotations
 
-import ctypes as C
-import warnings
 from collections import OrderedDict
 from dataclasses import dataclass
 from typing import Mapping, Optional, Tuple
@@ -26,11 +24,10 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .clip_text import ClipTextEncoder, clip_text_spec
+from .clip_text import (_METADATA_KEYS, ClipTextEncoder, _block_spec, _ClipEngine, _ptr, _synth_transformer_entry, clip_text_spec)
 
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)        # clip/clip.py _transform
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
-_METADATA_KEYS = ("logit_scale", "input_resolution", "context_length", "vocab_size")
 
 
 @dataclass
@@ -62,20 +59,7 @@ def clip_visual_spec(cfg: ClipVisionConfig) -> "OrderedDict[str, Tuple[int, ...]
     s["visual.conv1.weight"] = (w, 3, cfg.patch_size, cfg.patch_size)
     s["visual.ln_pre.weight"] = (w,)
     s["visual.ln_pre.bias"] = (w,)
-    for i in range(cfg.layers):
-        p = f"visual.transformer.resblocks.{i}."
-        s[p + "attn.in_proj_weight"] = (3 * w, w)
-        s[p + "attn.in_proj_bias"] = (3 * w,)
-        s[p + "attn.out_proj.weight"] = (w, w)
-        s[p + "attn.out_proj.bias"] = (w,)
-        s[p + "ln_1.weight"] = (w,)
-        s[p + "ln_1.bias"] = (w,)
-        s[p + "mlp.c_fc.weight"] = (4 * w, w)
-        s[p + "mlp.c_fc.bias"] = (4 * w,)
-        s[p + "mlp.c_proj.weight"] = (w, 4 * w)
-        s[p + "mlp.c_proj.bias"] = (w,)
-        s[p + "ln_2.weight"] = (w,)
-        s[p + "ln_2.bias"] = (w,)
+    _block_spec(s, "visual.transformer.resblocks.", cfg.layers, w)
     s["visual.ln_post.weight"] = (w,)
     s["visual.ln_post.bias"] = (w,)
     return s
@@ -86,25 +70,15 @@ def synth_clip_visual_state_dict(cfg: ClipVisionConfig, seed: int = 0) -> "Order
     initialize_parameters) with non-trivial LayerNorm affines and biases and an in_proj that gives a peaked, not degenerate, softmax -- the recipe
     of ``synth_clip_state_dict``."""
     rng = np.random.Generator(np.random.Philox(key=seed + 0xC11F + 0x1000))
-    w, L = cfg.width, cfg.layers
-    scale = w ** -0.5
-    proj_std, attn_std, fc_std = (w ** -0.5) * ((2 * L) ** -0.5), w ** -0.5, (2 * w) ** -0.5
+    w = cfg.width
     out: "OrderedDict[str, np.ndarray]" = OrderedDict()
     for k, shape in clip_visual_spec(cfg).items():
         if k in ("visual.class_embedding", "visual.positional_embedding", "visual.proj"):
-            v = scale * rng.standard_normal(shape)
+            v = w ** -0.5 * rng.standard_normal(shape)
         elif k == "visual.conv1.weight":
             v = (3 * cfg.patch_size ** 2) ** -0.5 * rng.standard_normal(shape)          # unit-variance patch features from unit-variance pixels
-        elif ".ln_" in k:
-            v = (1.0 + 0.2 * rng.standard_normal(shape)) if k.endswith("weight") else 0.1 * rng.standard_normal(shape)
-        elif k.endswith("bias"):
-            v = 0.05 * rng.standard_normal(shape)
-        elif "in_proj_weight" in k:
-            v = 1.5 * attn_std * rng.standard_normal(shape)
-        elif "out_proj.weight" in k or "c_proj.weight" in k:
-            v = 4.0 * proj_std * rng.standard_normal(shape)
         else:
-            v = fc_std * rng.standard_normal(shape)
+            v = _synth_transformer_entry(rng, k, shape, w, cfg.layers)
         out[k] = np.asarray(v, dtype=np.float32)
     return out
 
@@ -189,132 +163,25 @@ def clip_score(image_emb: torch.Tensor, text_emb: torch.Tensor) -> torch.Tensor:
 _IO_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16}
 
 
-class ClipImageEncoder:
+class ClipImageEncoder(_ClipEngine):
+    _ABI, _CALL, _INPUT = "tld_clip_vis", "encode_image", "pixels"
+
     def __init__(self, cfg: Optional[ClipVisionConfig] = None, init_seed: int = 0, max_batch: int = 16):
-        self.config = cfg if cfg is not None else ClipVisionConfig()
-        if self.config.heads * 64 != self.config.width:
-            raise ValueError("head_dim must be 64 (width // heads)")
-        self._spec = clip_visual_spec(self.config)
-        self._state: "OrderedDict[str, torch.Tensor]" = OrderedDict(
-            (k, torch.from_numpy(v)) for k, v in synth_clip_visual_state_dict(self.config, init_seed).items())
-        self._weights_loaded = False     # still on the deterministic random initialisation (no checkpoint can be downloaded here)
-        self.max_batch = int(max_batch)
-        self._device: Optional[torch.device] = None
-        self._engine = None
-        self._engine_key = None
-        self._debug = False
+        super().__init__(cfg if cfg is not None else ClipVisionConfig(), clip_visual_spec, synth_clip_visual_state_dict, init_seed, max_batch)
 
     @property
     def input_resolution(self) -> int:
         """``model.visual.input_resolution`` of openai/CLIP."""
         return self.config.image_size
 
-    # ---- nn.Module-like surface ----------------------------------------------------------------------------------
-    def eval(self) -> "ClipImageEncoder":
-        return self
-
-    def to(self, *args, **kwargs) -> "ClipImageEncoder":
-        for a in list(args) + list(kwargs.values()):
-            if isinstance(a, (torch.device, str)) and not isinstance(a, torch.dtype):
-                dev = torch.device(a)
-                if dev != self._device:
-                    self._drop_engine()
-                self._device = dev
-        return self
-
-    def state_dict(self) -> "OrderedDict[str, torch.Tensor]":
-        return OrderedDict(self._state)
-
     @staticmethod
-    def _is_text_key(k: str) -> bool:
+    def _is_foreign(k: str) -> bool:
         return (k in ("token_embedding.weight", "positional_embedding", "text_projection") or k.startswith("ln_final.") or
                 k.startswith("transformer.resblocks."))
 
-    def load_state_dict(self, sd: Mapping[str, torch.Tensor], strict: bool = True) -> "ClipImageEncoder":
-        new, seen = OrderedDict(), set()
-        for k, v in sd.items():
-            k = str(k)
-            if self._is_text_key(k) or k in _METADATA_KEYS:
-                continue
-            if k not in self._spec:
-                if strict:
-                    raise RuntimeError(f"unexpected key {k!r} in CLIP state_dict")
-                continue
-            t = (v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))).detach().cpu().to(torch.float32)
-            if tuple(t.shape) != tuple(self._spec[k]):
-                raise RuntimeError(f"size mismatch for {k}: checkpoint {tuple(t.shape)}, model {tuple(self._spec[k])}")
-            new[k] = t.contiguous()
-            seen.add(k)
-        missing = [k for k in self._spec if k not in seen]
-        if strict and missing:
-            raise RuntimeError(f"missing keys in CLIP state_dict: {missing[:4]}{' ...' if len(missing) > 4 else ''}")
-        self._state.update(new)
-        self._weights_loaded = True
-        self._drop_engine()
-        return self
-
-    def parameters(self):
-        return iter(self._state.values())
-
-    # ---- engine ---------------------------------------------------------------------------------------------------
-    def _drop_engine(self):
-        if self._engine is not None:
-            _lib.lib().tld_clip_vis_destroy(self._engine)
-            self._engine, self._engine_key = None, None
-
-    def __del__(self):
-        try:
-            self._drop_engine()
-        except Exception:
-            pass
-
-    def _ensure_engine(self, device: torch.device):
-        if device.type != "cuda":
-            raise RuntimeError("ClipImageEncoder.encode_image needs a HIP device (pixels on 'cuda'); there is no CPU path")
-        key = (device.index or 0, self.max_batch)
-        if self._engine is not None and self._engine_key == key:
-            return
-        self._drop_engine()
-        L, c = _lib.lib(), self.config
-        cc = _lib.TldClipVisConfig(c.image_size, c.patch_size, c.width, c.heads, c.layers, c.embed_dim, self.max_batch, device.index or 0)
-        h = C.c_void_p()
-        _lib.check(L.tld_clip_vis_create(C.byref(cc), C.byref(h)), "tld_clip_vis_create")
-        try:
-            for k, t in self._state.items():
-                a = np.ascontiguousarray(t.numpy(), dtype=np.float32)
-                shape = (C.c_int64 * a.ndim)(*a.shape)
-                _lib.check(L.tld_clip_vis_load_tensor(h, k.encode(), a.ctypes.data_as(C.c_void_p), shape, a.ndim, _lib.DTYPE_F32),
-                           f"tld_clip_vis_load_tensor({k})")
-            _lib.check(L.tld_clip_vis_finalize_weights(h), "tld_clip_vis_finalize_weights")
-        except Exception:
-            L.tld_clip_vis_destroy(h)
-            raise
-        self._engine, self._engine_key = h, key
-        if self._debug:
-            self._debug = False                     # (a failed allocation leaves the hook off)
-            self.set_debug(True)
-
-    # ---- test hook: stage capture (include/tld_hip.h: tld_clip_vis_set_debug) ----------------------------------------
-    def set_debug(self, on: bool = True):
-        """Keep every stage of every block of the following encode_image calls (snapshot memory for ``max_batch`` images is allocated here; a
-        failure raises and leaves the hook off).  Before the engine exists the request is remembered and applied when it is built."""
-        if self._engine is not None:
-            _lib.check(_lib.lib().tld_clip_vis_set_debug(self._engine, int(bool(on))), "tld_clip_vis_set_debug")
-        self._debug = bool(on)
-
-    def read_stage(self, name: str) -> torch.Tensor:
-        """One stage of the last ``tld_clip_vis_encode_image`` call (the last chunk of a chunked encode), fp32 ``[rows, columns]`` on the host."""
-        if self._engine is None:
-            raise RuntimeError("read_stage: no engine yet (encode_image first)")
-        read = _lib.lib().tld_clip_vis_read_stage
-        shape = (C.c_int64 * 4)()
-        probe = np.empty(1, dtype=np.float32)
-        rc = read(self._engine, name.encode(), probe.ctypes.data_as(C.POINTER(C.c_float)), -1, shape)
-        if shape[0] == 0:                           # no such stage: the probe's own status says why
-            _lib.check(rc or 1, f"tld_clip_vis_read_stage({name})")
-        out = np.empty((shape[0], shape[1]), dtype=np.float32)
-        _lib.check(read(self._engine, name.encode(), out.ctypes.data_as(C.POINTER(C.c_float)), out.size, shape), f"tld_clip_vis_read_stage({name})")
-        return torch.from_numpy(out)
+    def _config(self, device_id: int):
+        c = self.config
+        return _lib.TldClipVisConfig(c.image_size, c.patch_size, c.width, c.heads, c.layers, c.embed_dim, self.max_batch, device_id)
 
     @torch.no_grad()
     def encode_image(self, pixel_values: torch.Tensor) -> torch.Tensor:
@@ -325,29 +192,11 @@ class ClipImageEncoder:
             raise ValueError(f"expected pixels [B, 3, {R}, {R}], got {tuple(pixel_values.shape)}")
         if pixel_values.dtype not in _IO_DTYPES:
             raise ValueError(f"expected fp32, fp16 or bf16 pixels, got {pixel_values.dtype}")
-        dev = pixel_values.device if pixel_values.device.type == "cuda" else (self._device or pixel_values.device)
-        if dev.type != "cuda":
-            raise RuntimeError("ClipImageEncoder.encode_image needs a HIP device (pixels on 'cuda'); there is no CPU path")
-        if not self._weights_loaded:
-            self._weights_loaded = True             # (warn once per object)
-            warnings.warn("ClipImageEncoder is encoding with its deterministic RANDOM initialisation: no CLIP state_dict was loaded "
-                          "(load_state_dict); the embeddings carry no meaning", RuntimeWarning, stacklevel=2)
-        self._ensure_engine(dev)
+        dev = self._engine_for(pixel_values)
         pix = pixel_values.to(dev).contiguous()
-        B = pix.shape[0]
-        out = torch.empty(B, self.config.embed_dim, dtype=torch.float32, device=dev)
-        L = _lib.lib()
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        with torch.cuda.device(dev):
-            for b0 in range(0, B, self.max_batch):
-                b1 = min(B, b0 + self.max_batch)
-                _lib.check(L.tld_clip_vis_encode_image(self._engine, C.c_void_p(pix[b0:b1].data_ptr()), C.c_void_p(out[b0:b1].data_ptr()), b1 - b0,
-                                                       _IO_DTYPES[pix.dtype], C.c_void_p(stream)), "tld_clip_vis_encode_image")
+        out = torch.empty(pix.shape[0], self.config.embed_dim, dtype=torch.float32, device=dev)
+        self._run(dev, pix.shape[0], lambda entry, eng, b0, b1, stream: entry(eng, _ptr(pix[b0:b1]), _ptr(out[b0:b1]), b1 - b0, _IO_DTYPES[pix.dtype], stream))
         return out
-
-    @property
-    def weight_bytes(self) -> int:
-        return int(_lib.lib().tld_clip_vis_weight_bytes(self._engine)) if self._engine is not None else 0
 
 
 class Clip:

@@ -15,6 +15,7 @@
 #include "tld_common.h"
 #include "tld_host.h"
 #include "tld_clip_kernels.h"      // clip_add_ln_kernel, clip_final_ln_kernel, clip_quickgelu_kernel, gemm: shared with tld_clip.hip
+#include "tld_clip_core.h"         // ClipCore: the engine's state, weights, stage hook and block runner, shared with tld_clip.hip
 
 #include <cmath>
 #include <cstdio>
@@ -213,61 +214,6 @@ __global__ __launch_bounds__(256) void clip_vis_attn_kernel(const bf16* __restri
     }
 }
 
-struct Block {
-    float *ln1_g = nullptr, *ln1_b = nullptr, *ln2_g = nullptr, *ln2_b = nullptr;
-    bf16 *in_w = nullptr, *out_w = nullptr, *fc_w = nullptr, *proj_w = nullptr;
-    float *in_b = nullptr, *out_b = nullptr, *fc_b = nullptr, *proj_b = nullptr;
-};
-
-}  // namespace
-
-struct tld_clip_vis : DeviceArena {
-    tld_clip_vis_config cfg{};
-    int W = 0, L = 0, H = 0, E = 0, g = 0, p = 0, n = 0, Kp = 0;       // n = g*g + 1 tokens; Kp = 3 p*p rounded up to a multiple of 64
-    bool finalized = false;
-    std::map<std::string, HostTensor> host;
-    float *cls = nullptr, *pos = nullptr, *pre_g = nullptr, *pre_b = nullptr, *post_g = nullptr, *post_b = nullptr, *proj_t = nullptr;    // proj_t: proj^T [E][W]
-    bf16* conv_w = nullptr;                                             // conv1.weight packed [W][Kp], zero beyond 3 p*p
-    std::vector<Block> blocks;
-    // workspace (max_batch * n rows; patches: max_batch * g*g rows of Kp)
-    float *x = nullptr, *tmp = nullptr, *pooled = nullptr;
-    bf16 *patches = nullptr, *h = nullptr, *qkv = nullptr, *att = nullptr, *f = nullptr;
-    bool debug = false;
-    StageStore stages;
-};
-
-namespace {
-
-int need(const tld_clip_vis* c, const std::string& key, const std::vector<int64_t>& shape, const HostTensor** out) {
-    auto it = c->host.find(key);
-    if (it == c->host.end()) return fail(TLD_ERR_STATE, "missing state_dict entry '%s'", key.c_str());
-    if (it->second.shape != shape) {
-        std::string got, want;
-        for (int64_t s : it->second.shape) got += std::to_string(s) + ",";
-        for (int64_t s : shape) want += std::to_string(s) + ",";
-        return fail(TLD_ERR_SHAPE, "'%s' has shape [%s], expected [%s]", key.c_str(), got.c_str(), want.c_str());
-    }
-    *out = &it->second;
-    return TLD_OK;
-}
-
-void name_operands(tld_clip_vis* c) {
-    const int64_t W = c->W;
-    c->stages.ref("conv_w", c->conv_w, ST_BF16, W, c->Kp);
-    c->stages.ref("proj_t", c->proj_t, ST_F32, c->E, W);
-    for (int l = 0; l < (int)c->blocks.size(); ++l) {
-        const Block& b = c->blocks[l];
-        const std::string pre = "blk" + std::to_string(l) + ".";
-        c->stages.ref(pre + "in_w", b.in_w, ST_BF16, 3 * W, W); c->stages.ref(pre + "out_w", b.out_w, ST_BF16, W, W);
-        c->stages.ref(pre + "fc_w", b.fc_w, ST_BF16, 4 * W, W); c->stages.ref(pre + "proj_w", b.proj_w, ST_BF16, W, 4 * W);
-    }
-}
-void drop_snapshots(tld_clip_vis* c) {
-    c->stages.free_all();
-    c->debug = false;
-    if (c->finalized) name_operands(c);
-}
-
 size_t attn_lds_bytes(int NT) { return ((size_t)NT * 32 * kKPitch + (size_t)64 * v_pitch(NT * 32)) * sizeof(bf16); }
 
 // one workgroup per (head, sample); the dynamic LDS follows the sample's own tile count
@@ -287,14 +233,26 @@ void launch_im2col(const void* pix, bf16* rows, long total, int g, int p, int Kp
 
 }  // namespace
 
+struct tld_clip_vis : ClipCore {              // the transformer, its workspace and the stage hook: tld_clip_core.h
+    int g = 0, p = 0, n = 0, Kp = 0;          // n = g*g + 1 tokens; Kp = 3 p*p rounded up to a multiple of 64
+    float *cls = nullptr, *pos = nullptr, *pre_g = nullptr, *pre_b = nullptr, *post_g = nullptr, *post_b = nullptr;
+    bf16* conv_w = nullptr;                   // conv1.weight packed [W][Kp], zero beyond 3 p*p
+    bf16* patches = nullptr;                  // workspace: max_batch * g*g rows of Kp
+};
+
+namespace {
+
+// the tower's own GEMM operand beside the core's (name_operands): nothing before the weights exist
+void name_conv_w(tld_clip_vis* c) { c->stages.ref("conv_w", c->conv_w, ST_BF16, c->W, c->Kp); }
+
+}  // namespace
+
 extern "C" {
 
 int tld_clip_vis_create(const tld_clip_vis_config* cfg, tld_clip_vis** out) {
     if (!cfg || !out) return fail(TLD_ERR_INVALID, "null argument");
     *out = nullptr;
-    if (cfg->width < 64 || cfg->width > 1024 || cfg->width % 64) return fail(TLD_ERR_INVALID, "width=%d: a multiple of 64 in 64..1024", cfg->width);
-    if (cfg->heads * 64 != cfg->width) return fail(TLD_ERR_INVALID, "heads=%d: head_dim must be 64 (width / heads)", cfg->heads);
-    if (cfg->layers < 1 || cfg->layers > 64) return fail(TLD_ERR_INVALID, "layers=%d: 1..64", cfg->layers);
+    if (int rc = check_transformer(cfg->width, cfg->heads, cfg->layers)) return rc;
     if (cfg->patch_size < 1 || cfg->patch_size > 32) return fail(TLD_ERR_INVALID, "patch_size=%d: 1..32", cfg->patch_size);
     if (cfg->image_size < 1 || cfg->image_size % cfg->patch_size)
         return fail(TLD_ERR_INVALID, "image_size=%d: a positive multiple of patch_size=%d", cfg->image_size, cfg->patch_size);
@@ -303,74 +261,34 @@ int tld_clip_vis_create(const tld_clip_vis_config* cfg, tld_clip_vis** out) {
         return fail(TLD_ERR_INVALID, "image_size / patch_size = %d: the grid side must be 1..%d (at most %d tokens); the 336 px towers (577 tokens) are out of scope",
                     g, kMaxGrid, kMaxGrid * kMaxGrid + 1);
     if (cfg->embed_dim < 1 || cfg->max_batch < 1) return fail(TLD_ERR_INVALID, "embed_dim / max_batch must be positive");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(TLD_ERR_HIP, "no HIP device available (the image tower has no CPU path)");
-    if (cfg->device_id < 0 || cfg->device_id >= ndev) return fail(TLD_ERR_INVALID, "device_id=%d out of range (%d devices)", cfg->device_id, ndev);
+    if (int rc = check_device(cfg->device_id, "image")) return rc;
     DeviceGuard guard(cfg->device_id);
     tld_clip_vis* c = new tld_clip_vis();
-    c->cfg = *cfg;
-    c->W = cfg->width; c->L = cfg->layers; c->H = cfg->heads; c->E = cfg->embed_dim; c->g = g; c->p = cfg->patch_size; c->n = g * g + 1;
+    c->W = cfg->width; c->L = cfg->layers; c->H = cfg->heads; c->E = cfg->embed_dim; c->max_batch = cfg->max_batch; c->device_id = cfg->device_id;
+    c->g = g; c->p = cfg->patch_size; c->n = g * g + 1;
     c->Kp = (3 * c->p * c->p + 63) / 64 * 64;
-    const size_t B = (size_t)cfg->max_batch, T = B * c->n, W = c->W;
-    auto bail = [&](int rc) { tld_clip_vis_destroy(c); return rc; };
-    if (int rc = dev_alloc(c, &c->x, T * W)) return bail(rc);
-    if (int rc = dev_alloc(c, &c->tmp, T * W)) return bail(rc);
-    if (int rc = dev_alloc(c, &c->pooled, B * W)) return bail(rc);
-    if (int rc = dev_alloc(c, &c->patches, B * g * g * c->Kp)) return bail(rc);
-    if (int rc = dev_alloc(c, &c->h, T * W)) return bail(rc);
-    if (int rc = dev_alloc(c, &c->qkv, T * 3 * W)) return bail(rc);
-    if (int rc = dev_alloc(c, &c->att, T * W)) return bail(rc);
-    if (int rc = dev_alloc(c, &c->f, T * 4 * W)) return bail(rc);
+    if (int rc = alloc_workspace(c, c->n, &c->patches, (size_t)cfg->max_batch * g * g * c->Kp)) { tld_clip_vis_destroy(c); return rc; }
     *out = c;
     return TLD_OK;
 }
 
 int tld_clip_vis_load_tensor(tld_clip_vis* c, const char* key, const void* host_ptr, const int64_t* shape, int32_t ndim, int32_t dtype) {
-    if (!c || !key || (!host_ptr && ndim > 0) || (!shape && ndim > 0) || ndim < 0 || ndim > 8) return fail(TLD_ERR_INVALID, "bad argument");
-    if (c->finalized) return fail(TLD_ERR_STATE, "weights already finalized");
-    std::string k(key);
-    if (k.rfind("visual.", 0) != 0) {
-        // the text side and the archive's metadata are not used by encode_image (the text engine does the same with visual.*)
-        const bool other = k == "logit_scale" || k == "input_resolution" || k == "context_length" || k == "vocab_size" || k == "token_embedding.weight" ||
-                           k == "positional_embedding" || k == "text_projection" || k.rfind("ln_final.", 0) == 0 || k.rfind("transformer.resblocks.", 0) == 0;
-        return other ? TLD_OK : fail(TLD_ERR_KEY, "unknown state_dict key '%s'", key);
-    }
-    const bool known = k == "visual.class_embedding" || k == "visual.positional_embedding" || k == "visual.proj" || k == "visual.conv1.weight" ||
-                       k.rfind("visual.ln_pre.", 0) == 0 || k.rfind("visual.ln_post.", 0) == 0 || k.rfind("visual.transformer.resblocks.", 0) == 0;
-    if (!known) return fail(TLD_ERR_KEY, "unknown state_dict key '%s'", key);
-    if (dtype != TLD_DTYPE_F32) return fail(TLD_ERR_INVALID, "'%s': host tensors must be fp32", key);
-    HostTensor t;
-    int64_t n = 1;
-    for (int i = 0; i < ndim; ++i) { if (shape[i] < 0) return fail(TLD_ERR_SHAPE, "'%s': negative dimension", key); t.shape.push_back(shape[i]); n *= shape[i]; }
-    t.data.assign(reinterpret_cast<const float*>(host_ptr), reinterpret_cast<const float*>(host_ptr) + n);
-    c->host[k] = std::move(t);
-    return TLD_OK;
+    return load_tensor(c, CLIP_IMAGE, key, host_ptr, shape, ndim, dtype);
 }
 
 int tld_clip_vis_finalize_weights(tld_clip_vis* c) {
     if (!c) return fail(TLD_ERR_INVALID, "null handle");
     if (c->finalized) return fail(TLD_ERR_STATE, "weights already finalized");
-    DeviceGuard guard(c->cfg.device_id);
-    const int W = c->W, E = c->E, p = c->p, Kp = c->Kp;
+    DeviceGuard guard(c->device_id);
+    const int W = c->W, p = c->p, Kp = c->Kp;
+    if (int rc = upload_entry(c, "visual.class_embedding", {W}, &c->cls)) return rc;
+    if (int rc = upload_entry(c, "visual.positional_embedding", {c->n, W}, &c->pos)) return rc;
+    if (int rc = upload_entry(c, "visual.ln_pre.weight", {W}, &c->pre_g)) return rc;
+    if (int rc = upload_entry(c, "visual.ln_pre.bias", {W}, &c->pre_b)) return rc;
+    if (int rc = upload_entry(c, "visual.ln_post.weight", {W}, &c->post_g)) return rc;
+    if (int rc = upload_entry(c, "visual.ln_post.bias", {W}, &c->post_b)) return rc;
+    if (int rc = upload_proj_t(c, "visual.proj")) return rc;
     const HostTensor* t = nullptr;
-    if (int rc = need(c, "visual.class_embedding", {W}, &t)) return rc;
-    if (int rc = upload_f32(c, t->data, &c->cls)) return rc;
-    if (int rc = need(c, "visual.positional_embedding", {c->n, W}, &t)) return rc;
-    if (int rc = upload_f32(c, t->data, &c->pos)) return rc;
-    if (int rc = need(c, "visual.ln_pre.weight", {W}, &t)) return rc;
-    if (int rc = upload_f32(c, t->data, &c->pre_g)) return rc;
-    if (int rc = need(c, "visual.ln_pre.bias", {W}, &t)) return rc;
-    if (int rc = upload_f32(c, t->data, &c->pre_b)) return rc;
-    if (int rc = need(c, "visual.ln_post.weight", {W}, &t)) return rc;
-    if (int rc = upload_f32(c, t->data, &c->post_g)) return rc;
-    if (int rc = need(c, "visual.ln_post.bias", {W}, &t)) return rc;
-    if (int rc = upload_f32(c, t->data, &c->post_b)) return rc;
-    if (int rc = need(c, "visual.proj", {W, E}, &t)) return rc;
-    {
-        std::vector<float> pt((size_t)E * W);
-        for (int k = 0; k < W; ++k) for (int n = 0; n < E; ++n) pt[(size_t)n * W + k] = t->data[(size_t)k * E + n];
-        if (int rc = upload_f32(c, pt, &c->proj_t)) return rc;
-    }
     if (int rc = need(c, "visual.conv1.weight", {W, 3, p, p}, &t)) return rc;
     {
         const int K0 = 3 * p * p;
@@ -378,143 +296,55 @@ int tld_clip_vis_finalize_weights(tld_clip_vis* c) {
         for (int o = 0; o < W; ++o) for (int k = 0; k < K0; ++k) cw[(size_t)o * Kp + k] = t->data[(size_t)o * K0 + k];
         if (int rc = upload_bf16(c, cw, &c->conv_w)) return rc;
     }
-    c->blocks.resize(c->L);
-    for (int l = 0; l < c->L; ++l) {
-        Block& b = c->blocks[l];
-        const std::string pfx = "visual.transformer.resblocks." + std::to_string(l) + ".";
-        struct Item { const char* key; std::vector<int64_t> shape; float** f32; bf16** b16; };
-        const std::vector<Item> items = {
-            {"ln_1.weight", {W}, &b.ln1_g, nullptr}, {"ln_1.bias", {W}, &b.ln1_b, nullptr},
-            {"attn.in_proj_weight", {3 * W, W}, nullptr, &b.in_w}, {"attn.in_proj_bias", {3 * W}, &b.in_b, nullptr},
-            {"attn.out_proj.weight", {W, W}, nullptr, &b.out_w}, {"attn.out_proj.bias", {W}, &b.out_b, nullptr},
-            {"ln_2.weight", {W}, &b.ln2_g, nullptr}, {"ln_2.bias", {W}, &b.ln2_b, nullptr},
-            {"mlp.c_fc.weight", {4 * W, W}, nullptr, &b.fc_w}, {"mlp.c_fc.bias", {4 * W}, &b.fc_b, nullptr},
-            {"mlp.c_proj.weight", {W, 4 * W}, nullptr, &b.proj_w}, {"mlp.c_proj.bias", {W}, &b.proj_b, nullptr},
-        };
-        for (auto& it : items) {
-            if (int rc = need(c, pfx + it.key, it.shape, &t)) return rc;
-            if (it.f32) { if (int rc = upload_f32(c, t->data, it.f32)) return rc; }
-            else { if (int rc = upload_bf16(c, t->data, it.b16)) return rc; }
-        }
-    }
-    c->host.clear();
-    HIP_TRY(hipDeviceSynchronize());
-    c->finalized = true;
-    name_operands(c);
+    if (int rc = upload_blocks(c, CLIP_IMAGE)) return rc;
+    if (int rc = finish_weights(c)) return rc;
+    name_conv_w(c);
     return TLD_OK;
 }
 
 int tld_clip_vis_encode_image(tld_clip_vis* c, const void* pixels, float* out, int32_t batch, int32_t io_dtype, void* hip_stream) {
     if (!c || !pixels || !out) return fail(TLD_ERR_INVALID, "null argument");
-    if (!c->finalized) return fail(TLD_ERR_STATE, "weights not finalized");
-    if (batch < 1 || batch > c->cfg.max_batch) return fail(TLD_ERR_INVALID, "batch=%d outside 1..max_batch=%d", batch, c->cfg.max_batch);
+    if (int rc = check_encode(c, batch)) return rc;
     if (io_dtype != TLD_DTYPE_F32 && io_dtype != TLD_DTYPE_BF16 && io_dtype != TLD_DTYPE_F16) return fail(TLD_ERR_INVALID, "io_dtype=%d: fp32, bf16 or fp16", io_dtype);
-    DeviceGuard guard(c->cfg.device_id);
+    DeviceGuard guard(c->device_id);
     hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
     const int W = c->W, n = c->n, g = c->g, Kp = c->Kp, T = batch * n, P = batch * g * g;
-    const bool dbg = c->debug;
-    if (dbg) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone)
-            return fail(TLD_ERR_STATE, "a debug encode (tld_clip_vis_set_debug) cannot be captured into a graph");
-        c->stages.begin_call();
-        const size_t B = (size_t)c->cfg.max_batch, TW = B * n * W;      // the whole workspace of max_batch samples: NaN in bf16 and fp32 wherever this call stores nothing
-        HIP_TRY(hipMemsetAsync(c->x, 0xFF, TW * 4, s));
-        HIP_TRY(hipMemsetAsync(c->tmp, 0xFF, TW * 4, s));
-        HIP_TRY(hipMemsetAsync(c->pooled, 0xFF, B * W * 4, s));
-        HIP_TRY(hipMemsetAsync(c->patches, 0xFF, B * g * g * Kp * 2, s));
-        HIP_TRY(hipMemsetAsync(c->h, 0xFF, TW * 2, s));
-        HIP_TRY(hipMemsetAsync(c->qkv, 0xFF, TW * 3 * 2, s));
-        HIP_TRY(hipMemsetAsync(c->att, 0xFF, TW * 2, s));
-        HIP_TRY(hipMemsetAsync(c->f, 0xFF, TW * 4 * 2, s));
-    }
-#define KEEP(name, src, dtype, rows, cols) do { if (dbg) { if (int rc_ = c->stages.copy(name, src, dtype, s, rows, cols)) return rc_; } } while (0)
-#define GEMM(where, what, ...) GEMM_TRY(std::string("tld_clip_vis_encode_image, ") + where + " " what, gemm(__VA_ARGS__))
+    if (c->debug) { if (int rc = begin_debug_call(c, n, "tld_clip_vis_set_debug", s, c->patches, (size_t)c->max_batch * g * g * Kp)) return rc; }
     {
         const long total = (long)P * Kp;
         if (io_dtype == TLD_DTYPE_F32) launch_im2col<float>(pixels, c->patches, total, g, c->p, Kp, s);
         else if (io_dtype == TLD_DTYPE_BF16) launch_im2col<bf16>(pixels, c->patches, total, g, c->p, Kp, s);
         else launch_im2col<_Float16>(pixels, c->patches, total, g, c->p, Kp, s);
     }
-    KEEP("patches", c->patches, ST_BF16, P, Kp);
-    GEMM("patch embedding", "conv1", c->patches, Kp, c->conv_w, P, W, Kp, EPI_F32, nullptr, nullptr, c->tmp, s);
-    KEEP("emb", c->tmp, ST_F32, P, W);
-    const dim3 rows((T + 3) / 4);
-    hipLaunchKernelGGL(clip_vis_embed_ln_kernel, rows, dim3(256), 0, s, c->tmp, c->cls, c->pos, c->pre_g, c->pre_b, c->x, T, W, n);
-    KEEP("x0", c->x, ST_F32, T, W);
-    hipLaunchKernelGGL(clip_add_ln_kernel, rows, dim3(256), 0, s, c->x, (const float*)nullptr, (const float*)nullptr, c->blocks[0].ln1_g, c->blocks[0].ln1_b, c->h, T, W);
-
-    for (int l = 0; l < c->L; ++l) {
-        const Block& b = c->blocks[l];
-        const std::string pre = dbg ? "blk" + std::to_string(l) + "." : std::string();
-        const std::string where = "block " + std::to_string(l);
-        KEEP(pre + "h1", c->h, ST_BF16, T, W);
-        GEMM(where, "in_proj", c->h, W, b.in_w, T, 3 * W, W, EPI_BIAS_BF16, b.in_b, c->qkv, nullptr, s);
-        KEEP(pre + "qkv", c->qkv, ST_BF16, T, 3 * W);
-        launch_attention(c->qkv, c->att, batch, n, c->H, s);
-        KEEP(pre + "att", c->att, ST_BF16, T, W);
-        GEMM(where, "out_proj", c->att, W, b.out_w, T, W, W, EPI_F32, nullptr, nullptr, c->tmp, s);
-        KEEP(pre + "attn_out", c->tmp, ST_F32, T, W);
-        hipLaunchKernelGGL(clip_add_ln_kernel, rows, dim3(256), 0, s, c->x, c->tmp, b.out_b, b.ln2_g, b.ln2_b, c->h, T, W);
-        KEEP(pre + "x1", c->x, ST_F32, T, W);
-        KEEP(pre + "h2", c->h, ST_BF16, T, W);
-        GEMM(where, "c_fc", c->h, W, b.fc_w, T, 4 * W, W, EPI_BIAS_BF16, b.fc_b, c->f, nullptr, s);
-        KEEP(pre + "f_pre", c->f, ST_BF16, T, 4 * W);
-        {
-            const long n8 = (long)T * 4 * W / 8;
-            hipLaunchKernelGGL(clip_quickgelu_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, c->f, n8);
-        }
-        KEEP(pre + "f", c->f, ST_BF16, T, 4 * W);
-        GEMM(where, "c_proj", c->f, 4 * W, b.proj_w, T, W, 4 * W, EPI_F32, nullptr, nullptr, c->tmp, s);
-        KEEP(pre + "mlp_out", c->tmp, ST_F32, T, W);
-        if (l + 1 < c->L) {
-            hipLaunchKernelGGL(clip_add_ln_kernel, rows, dim3(256), 0, s, c->x, c->tmp, b.proj_b, c->blocks[l + 1].ln1_g, c->blocks[l + 1].ln1_b, c->h, T, W);
-            KEEP(pre + "x2", c->x, ST_F32, T, W);
-        } else {
-            // the class token's row of each sample only: residual add of the last block + ln_post
-            hipLaunchKernelGGL(clip_final_ln_kernel, dim3(batch), dim3(64), 0, s, c->x, c->tmp, b.proj_b, (const int*)nullptr, c->post_g, c->post_b, c->pooled, W, n);
-            KEEP("pooled", c->pooled, ST_F32, batch, W);
-        }
-    }
-    launch_linear_f32(c->pooled, W, c->proj_t, nullptr, out, c->E, batch, W, c->E, 0, s);
-    KEEP("out", out, ST_F32, batch, c->E);
-#undef KEEP
-#undef GEMM
+    CLIP_KEEP("patches", c->patches, ST_BF16, P, Kp);
+    GEMM_TRY("tld_clip_vis_encode_image, patch embedding conv1", gemm(c->patches, Kp, c->conv_w, P, W, Kp, EPI_F32, nullptr, nullptr, c->tmp, s));
+    CLIP_KEEP("emb", c->tmp, ST_F32, P, W);
+    hipLaunchKernelGGL(clip_vis_embed_ln_kernel, dim3((T + 3) / 4), dim3(256), 0, s, c->tmp, c->cls, c->pos, c->pre_g, c->pre_b, c->x, T, W, n);
+    // the class token's row of each sample is the pooled one (no EOT index), through ln_post
+    auto attention = [&] { launch_attention(c->qkv, c->att, batch, n, c->H, s); };
+    if (int rc = run_blocks(c, batch, n, attention, nullptr, c->post_g, c->post_b, "tld_clip_vis_encode_image", out, s)) return rc;
     return check_launch("encode_image");
 }
 
 int tld_clip_vis_set_debug(tld_clip_vis* c, int32_t enable) {
     if (!c) return fail(TLD_ERR_INVALID, "null handle");
-    DeviceGuard guard(c->cfg.device_id);
-    if (!enable) { drop_snapshots(c); return TLD_OK; }
+    DeviceGuard guard(c->device_id);
+    if (!enable) { drop_snapshots(c); name_conv_w(c); return TLD_OK; }
     if (c->debug) return TLD_OK;
-    const size_t B = (size_t)c->cfg.max_batch, T = B * c->n, P = B * c->g * c->g, W = c->W;
+    const size_t P = (size_t)c->max_batch * c->g * c->g;
     int rc = c->stages.reserve("patches", P * c->Kp * 2);
-    if (!rc) rc = c->stages.reserve("emb", P * W * 4);
-    if (!rc) rc = c->stages.reserve("x0", T * W * 4);
-    for (int l = 0; !rc && l < c->L; ++l) {
-        const std::string pre = "blk" + std::to_string(l) + ".";
-        for (const char* nm : {"h1", "att", "h2"}) if (!rc) rc = c->stages.reserve(pre + nm, T * W * 2);
-        for (const char* nm : {"attn_out", "x1", "mlp_out"}) if (!rc) rc = c->stages.reserve(pre + nm, T * W * 4);
-        if (!rc) rc = c->stages.reserve(pre + "qkv", T * 3 * W * 2);
-        for (const char* nm : {"f_pre", "f"}) if (!rc) rc = c->stages.reserve(pre + nm, T * 4 * W * 2);
-        if (!rc && l + 1 < c->L) rc = c->stages.reserve(pre + "x2", T * W * 4);              // the last block forms only the pooled rows
-    }
-    if (!rc) rc = c->stages.reserve("pooled", B * W * 4);
-    if (!rc) rc = c->stages.reserve("out", B * c->E * 4);
+    if (!rc) rc = c->stages.reserve("emb", P * c->W * 4);
+    if (!rc) rc = reserve_stages(c, c->n);
     if (rc) {
         drop_snapshots(c);
-        return fail(TLD_ERR_HIP, "tld_clip_vis_set_debug: no memory for the stage snapshots of %d images x %d layers; debug stays off", c->cfg.max_batch, c->L);
+        name_conv_w(c);
+        return fail(TLD_ERR_HIP, "tld_clip_vis_set_debug: no memory for the stage snapshots of %d images x %d layers; debug stays off", c->max_batch, c->L);
     }
     c->debug = true;
     return TLD_OK;
 }
 
-int tld_clip_vis_read_stage(tld_clip_vis* c, const char* name, float* host_out, int64_t numel, int64_t* shape4) {
-    if (!c || !name || !host_out) return fail(TLD_ERR_INVALID, "null argument");
-    DeviceGuard guard(c->cfg.device_id);
-    return c->stages.read(name, host_out, numel, shape4);
-}
+int tld_clip_vis_read_stage(tld_clip_vis* c, const char* name, float* host_out, int64_t numel, int64_t* shape4) { return read_stage(c, name, host_out, numel, shape4); }
 
 int tld_debug_clip_vis_attention(const void* qkv_bf16, void* out_bf16, int32_t batch, int32_t n, int32_t heads, void* hip_stream) {
     if (!qkv_bf16 || !out_bf16) return fail(TLD_ERR_INVALID, "null argument");
@@ -526,13 +356,11 @@ int tld_debug_clip_vis_attention(const void* qkv_bf16, void* out_bf16, int32_t b
     return check_launch("tld_debug_clip_vis_attention");
 }
 
-int64_t tld_clip_vis_weight_bytes(const tld_clip_vis* c) { return c ? c->weight_bytes : 0; }
+int64_t tld_clip_vis_weight_bytes(const tld_clip_vis* c) { return weight_bytes(c); }
 
 int tld_clip_vis_destroy(tld_clip_vis* c) {
     if (!c) return TLD_OK;
-    DeviceGuard guard(c->cfg.device_id);
-    drop_snapshots(c);
-    for (void* p : c->allocs) (void)hipFree(p);
+    release(c);
     delete c;
     return TLD_OK;
 }
