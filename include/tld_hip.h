@@ -198,6 +198,32 @@ TLD_API int tld_sample_requests(tld_engine* e, const void* noise, const void* in
 TLD_API int tld_sample_requests_guided(tld_engine* e, const void* noise, const void* init_latent, const void* mask, const void* labels,
                const void* neg_labels, const tld_sample_request* requests, const float* coeffs, const float* guidance, int32_t n_max, float sharp_f,
                float bright_f, void* out_latent, int32_t batch, void* trace_x0, void* trace_xt, void* hip_stream);
+/* tld_sample_requests_guided with noise injected inside the step: SDE DPM-Solver++(2M) and DDIM with eta, per request.  Two more
+ * HOST arrays:
+ *   noise_coeff [batch, n_max] fp32: e of request b's forward i (schedule.step_coefficients(..., eta) returns it beside the table whose a, b, c it
+ *               belongs to).  Every used entry must be finite and >= 0, and the entry of a request's final forward must be 0; entries past n_levels
+ *               are ignored
+ *   noise_keys  [batch] uint64: the request's noise key
+ * After x_t = (a D + b x_t) / c of an inner step, and before the mask blend, the step adds x_t <- x_t + e z: the product is rounded, then the sum.
+ * z are standard normals from Philox4x32-10 under the request's key at the counter (quad, i, tag, 0), quad = (element index inside the request's own
+ * [C, S, S] image) / 4 and i the forward index of the request's own trajectory (csrc/tld_sampler_noise.h), through the Box-Muller functions of the
+ * batch preparation.  Neither the request's place in the call nor the other requests enter the counter: request b's result is bit for bit that of
+ * the request alone with the same key.  A forward whose e is 0.0f draws nothing and adds nothing, so an all-zero noise_coeff gives the result of
+ * tld_sample_requests_guided -- or, with guidance NULL, of tld_sample_requests -- bit for bit.  With a mask the known region still rides the forward
+ * process of the start eps; x0_prev, trace_x0 and trace_xt are written as before, trace_xt after the noise.
+ *   guidance    as in tld_sample_requests_guided, or NULL: every forward of request b then takes requests[b].class_guidance and no unconditional
+ *               sample is skipped -- the 2 B_i batch and the capacity rule (batch*2 <= max_batch) of tld_sample_requests
+ * Still one elementwise launch per step; the second table (e and the key per (step, request)) travels in the same pinned staging upload as the rows,
+ * no stream synchronisation.  tld_engine_sample_rows and the launch-path bits are those of the entry it generalises (58-60).  All record checks,
+ * these arrays' included, come first and need no device; every refusal happens before anything is enqueued. */
+TLD_API int tld_sample_requests_stochastic(tld_engine* e, const void* noise, const void* init_latent, const void* mask, const void* labels,
+               const void* neg_labels, const tld_sample_request* requests, const float* coeffs, const float* guidance, const float* noise_coeff,
+               const uint64_t* noise_keys, int32_t n_max, float sharp_f, float bright_f, void* out_latent, int32_t batch, void* trace_x0,
+               void* trace_xt, void* hip_stream);
+/* engine-free: out_device [batch, img] fp32 <- the normals the stochastic step draws for request key keys_device[b] (uint64, device) at forward
+ * steps_device[b] (uint32, device) over an image of img elements, from the device function the step kernel calls.  img need not be a multiple of 4 */
+TLD_API int tld_debug_sampler_noise(const uint64_t* keys_device, const uint32_t* steps_device, int32_t batch, int32_t img, float* out_device,
+               void* hip_stream);
 /* model samples the last sampler call on this engine enqueued: conditional and unconditional.  tld_sample / tld_sample_from / tld_sample_requests
  * report sum(n_levels) twice; tld_sample_requests_guided reports (sum(n_levels), sum(U_i)) */
 TLD_API int tld_engine_sample_rows(tld_engine* e, int64_t* cond, int64_t* uncond);

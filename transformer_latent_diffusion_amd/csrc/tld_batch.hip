@@ -11,6 +11,7 @@
 #include "tld_common.h"
 #include "tld_host.h"        // fail, DeviceGuard, HIP_TRY
 #include "tld_batch_math.h"
+#include "tld_normal_device.h"     // log_uniform24_open
 #include "../../include/tld_hip.h"
 
 #include <algorithm>
@@ -71,11 +72,6 @@ __device__ __forceinline__ float scaled(float v, float scale) { return __fdiv_rn
 
 __device__ __forceinline__ float mix(double nl, double sl, float noise, float target) {
     return (float)__dadd_rn(__dmul_rn(nl, (double)noise), __dmul_rn(sl, (double)target));
-}
-
-// ln of the unrounded u = ((r >> 8) + 0.5) 2^-24: u is exact in fp32 below one half, 1 - u is exact from there on
-__device__ __forceinline__ float log_uniform24_open(uint32_t r) {
-    return (r >> 8) < 0x800000u ? logf(uniform24_open(r)) : log1pf(-uniform24_open_complement(r));
 }
 
 __global__ __launch_bounds__(kBatchLanes) void prepare_batch_kernel(BatchArgs A) {

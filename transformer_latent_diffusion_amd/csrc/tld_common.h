@@ -441,6 +441,13 @@ struct SamplerStepRow {
     int final_step;               // 1: the request's last level -- combine (+ mask blend, + shifts on channels 3 and 0) into out_latent, no update
                                   // (the slots flavour packs final | (slot + 1) << 1 here: see launch_sampler_step)
 };
+// second table of the stochastic entry, one row per (step, request) beside SamplerStepRow: x_t += e z after the update, z the standard normals of
+// (key, step, quad) (tld_sampler_noise.h).  e == 0.0f: nothing is drawn and nothing is added
+struct alignas(16) SamplerNoiseRow {
+    float e;                      // sigma_t sqrt(1 - exp(-2 eta h)) of the request's step (schedule.py); 0 on its final forward
+    uint32_t key_lo, key_hi;      // the request's 64-bit noise key
+    uint32_t reserved;
+};
 struct SamplerStepParams {
     const float* x0_2b;           // [2 active, img] model output of the step: cond rows of the active prefix, then their uncond rows
     float* x_t;                   // [B, img]  in/out
@@ -454,11 +461,17 @@ struct SamplerStepParams {
     int row_stride;               // 1: a row per request; 0: one row for every sample
     float sharp, bright;
     int active, img, chan_stride; // requests still running at this step (a prefix: the records are ordered by non-increasing level count)
+    // the NOISE flavour only (tld_sample_requests_stochastic): this step's rows of the second device table and the forward index
+    const SamplerNoiseRow* noise_rows;            // sample b reads noise_rows[b * row_stride]; null: no flavour of the kernel reads it
+    uint32_t noise_step;
 };
 // path: the EP_UPDATE* bit that names the flavour of step the calling entry asked for
 // slots (tld_sample_requests_guided): x0_2b is [active cond samples | the unconditional samples of the requests guided at this step], and a row's
 // final_step holds final | (slot + 1) << 1 -- the unconditional operand of the request is sample active + slot; slot + 1 == 0: none, x0 = cond itself
+// p.noise_rows non-null (slots only): the NOISE flavour
 void launch_sampler_step(const SamplerStepParams& p, int path, hipStream_t s, bool slots = false);
+// z [batch, img] fp32 <- the normals sampler_step_kernel<.., NOISE> draws for (keys[b], steps[b]): the same device function (tld_debug_sampler_noise)
+void launch_sampler_noise_debug(const uint64_t* keys, const uint32_t* steps, int batch, int img, float* z, hipStream_t s);
 // x_t[b] = s0 noise[b] + (1 - s0) z0[b] with s0 = s0v[b * s0_stride] read from a device table; s0 == 1 copies noise[b] (z0 may then be null).  path: EP_START_MIX*
 void launch_start_mix(const float* noise, const float* z0, const float* s0v, int s0_stride, float* x_t, int batch, int img, int path, hipStream_t s);
 

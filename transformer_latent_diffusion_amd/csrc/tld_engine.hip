@@ -558,6 +558,9 @@ struct SamplePlan {
     const tld_sample_request* requests;
     const float* coeffs;                 // HOST [B or 1][n_max][6]: (sigma, a, b, c, c1, c2) per level
     const float* guidance;               // HOST [B][n_max] or null: the guidance of request b's forward i instead of its record's (tld_sample_requests_guided)
+    bool skip;                           // with guidance: a forward guided at exactly 1.0f runs no unconditional sample (the engine's TLD_GUIDANCE_SKIP)
+    // tld_sample_requests_stochastic (with guidance only): HOST [B][n_max] e of request b's forward i and HOST [B] keys; null: no noise, the kernels without the NOISE flag
+    const float* noise_coeff; const uint64_t* noise_keys;
     // conditioning noise rows: Tn sigmas and, per (step, request), the row of its sigma; null: row i is level i of the one table (the uniform entries)
     int Tn; const float* sig; const int* noise_idx;       // sig [Tn], noise_idx [n_max][B]
     const float *noise, *init_latent, *mask, *labels, *neg_labels;      // device; init_latent / mask / neg_labels optional
@@ -592,13 +595,16 @@ int run_sampler(tld_engine* e, const SamplePlan& p, hipStream_t s) {
     int64_t n_cond = 0, n_unc = 0;
     for (int i = 0, Bi = B; i < n_max; ++i) {
         while (req(Bi - 1).n_levels <= i) --Bi;
-        const int U = guided ? guided_slots(p.guidance, n_max, Bi, i, e->guidance_skip, slot.data()) : Bi;
+        const int U = guided ? guided_slots(p.guidance, n_max, Bi, i, p.skip, slot.data()) : Bi;
         mbs[(size_t)i] = Bi + U; n_cond += Bi; n_unc += U;
     }
     if (guided) row_ints = (size_t)3 * (size_t)(n_cond + n_unc);
     const int T = Tn + B + 1 + n_neg;
     const size_t tab_bytes = (size_t)n_max * tabB * sizeof(SamplerStepRow), mix_bytes = (size_t)tabB * sizeof(float);
-    const size_t up_bytes = tab_bytes + mix_bytes + row_ints * sizeof(int);
+    // (the stochastic entry's second table, 16-byte rows [n_max][tabB], rides behind the int tables in the same upload)
+    const bool noisy = p.noise_coeff != nullptr;
+    const size_t noise_off = (tab_bytes + mix_bytes + row_ints * sizeof(int) + 15) & ~(size_t)15;
+    const size_t up_bytes = noisy ? noise_off + (size_t)n_max * tabB * sizeof(SamplerNoiseRow) : tab_bytes + mix_bytes + row_ints * sizeof(int);
     if (int rc = ensure_cond_capacity(e, T)) return rc;
     if (int rc = ensure_req_capacity(e, up_bytes)) return rc;
     if (int rc = debug_begin(e, T, Tn, s)) return rc;
@@ -606,7 +612,16 @@ int run_sampler(tld_engine* e, const SamplePlan& p, hipStream_t s) {
     SamplerStepRow* tab = static_cast<SamplerStepRow*>(e->stage_host);
     float* mix = reinterpret_cast<float*>(tab + (size_t)n_max * tabB);
     int* rows = reinterpret_cast<int*>(mix + tabB);
-    float* sigs = reinterpret_cast<float*>(rows + row_ints);
+    float* sigs = reinterpret_cast<float*>(static_cast<char*>(e->stage_host) + up_bytes);
+    if (noisy) {
+        SamplerNoiseRow* nt = reinterpret_cast<SamplerNoiseRow*>(static_cast<char*>(e->stage_host) + noise_off);
+        for (int b = 0; b < tabB; ++b)
+            for (int i = 0; i < n_max; ++i) {
+                const bool on = i < req(b).n_levels - 1;          // (the final forward adds none: its entry was checked to be 0)
+                nt[(size_t)i * tabB + b] = SamplerNoiseRow{on ? p.noise_coeff[(size_t)b * n_max + i] : 0.0f, (uint32_t)p.noise_keys[b],
+                                                           (uint32_t)(p.noise_keys[b] >> 32), 0u};
+            }
+    }
     bool any_mix = false;
     for (int b = 0; b < tabB; ++b) {
         const tld_sample_request& r = req(b);
@@ -628,7 +643,7 @@ int run_sampler(tld_engine* e, const SamplePlan& p, hipStream_t s) {
             while (req(Bi - 1).n_levels <= i) --Bi;
             const int mb = mbs[(size_t)i];
             int *lr = nr + mb, *sr = lr + mb;                 // (sr: guided only)
-            if (guided) guided_slots(p.guidance, n_max, Bi, i, e->guidance_skip, slot.data());
+            if (guided) guided_slots(p.guidance, n_max, Bi, i, p.skip, slot.data());
             for (int b = 0, k = 0; b < Bi; ++b) {
                 const int neg = req(b).has_negative ? Tn + B + 1 + k++ : Tn + B;  // the unconditional label: the zero row, or the request's own negative
                 const int sl = guided ? slot[(size_t)b] : b;
@@ -668,6 +683,7 @@ int run_sampler(tld_engine* e, const SamplePlan& p, hipStream_t s) {
     const SamplerStepRow* tab_dev = static_cast<const SamplerStepRow*>(e->req_dev);
     const float* mix_dev = reinterpret_cast<const float*>(tab_dev + (size_t)n_max * tabB);
     const int* nr = reinterpret_cast<const int*>(mix_dev + tabB);
+    const SamplerNoiseRow* noise_dev = noisy ? reinterpret_cast<const SamplerNoiseRow*>(static_cast<const char*>(e->req_dev) + noise_off) : nullptr;
 
     // ---- the start: pure noise at the schedule's first level (diffusion.py:52,59), else the forward process at the first remaining level (train.py:130)
     const size_t tot = (size_t)B * e->img;
@@ -692,6 +708,7 @@ int run_sampler(tld_engine* e, const SamplePlan& p, hipStream_t s) {
         up.noise = p.noise; up.z0 = p.init_latent; up.mask = p.mask;
         up.rows = tab_dev + (size_t)i * tabB; up.row_stride = p.stride; up.sharp = p.sharp; up.bright = p.bright;
         up.active = Bi; up.img = e->img; up.chan_stride = e->cfg.image_size * e->cfg.image_size;
+        if (noisy) { up.noise_rows = noise_dev + (size_t)i * tabB; up.noise_step = (uint32_t)i; }
         {
             ProfScope ps(e, KC_UPDATE, s);
             launch_sampler_step(up, p.path_step, s, guided);
@@ -1096,12 +1113,17 @@ int tld_sample_from(tld_engine* e, const void* noise, const void* init_latent, c
 // about 0.52 MB, so the grow-only tables stay near 0.5 GiB
 constexpr int kMaxRequestCondRows = 1024;
 
-// tld_sample_requests, and with `guided` tld_sample_requests_guided: `guidance` is then the HOST table [batch][n_max] that replaces the records' class_guidance
+// tld_sample_requests, and with `guided` tld_sample_requests_guided: `guidance` is then the HOST table [batch][n_max] that replaces the records' class_guidance.
+// `stochastic` (tld_sample_requests_stochastic): the guided call plus noise_coeff [batch][n_max] and noise_keys [batch]; a null `guidance` there stands for
+// the table of the records' class_guidance with no skipping, the 2 B_i batch of tld_sample_requests
 static int sample_requests(tld_engine* e, const void* noise, const void* init_latent, const void* mask, const void* labels, const void* neg_labels,
                            const tld_sample_request* requests, const float* coeffs, const float* guidance, bool guided, int32_t n_max, float sharp_f,
-                           float bright_f, void* out_latent, int32_t batch, void* trace_x0, void* trace_xt, void* hip_stream) {
+                           float bright_f, void* out_latent, int32_t batch, void* trace_x0, void* trace_xt, void* hip_stream,
+                           bool stochastic = false, const float* noise_coeff = nullptr, const uint64_t* noise_keys = nullptr) {
     // the records first: their checks need no engine and no device
     if (!requests || !coeffs || batch <= 0 || (guided && !guidance)) return fail(TLD_ERR_INVALID, "null argument");
+    if (stochastic && !noise_coeff) return fail(TLD_ERR_INVALID, "null argument: noise_coeff");
+    if (stochastic && !noise_keys) return fail(TLD_ERR_INVALID, "null argument: noise_keys");
     if (mask && !init_latent) return fail(TLD_ERR_INVALID, "init_latent is required with a mask");
     const int B = batch;
     int n_neg = 0;
@@ -1121,17 +1143,32 @@ static int sample_requests(tld_engine* e, const void* noise, const void* init_la
             if (!neg_labels) return fail(TLD_ERR_INVALID, "request %d: has_negative without neg_labels", b);
             ++n_neg;
         }
+        for (int i = 0; stochastic && i < r.n_levels; ++i) {
+            const float en = noise_coeff[(size_t)b * n_max + i];
+            if (!(std::isfinite(en) && en >= 0.0f)) return fail(TLD_ERR_INVALID, "request %d: noise_coeff of forward %d is %g: expected finite and >= 0", b, i, (double)en);
+            if (i == r.n_levels - 1 && en != 0.0f)
+                return fail(TLD_ERR_INVALID, "request %d: noise_coeff of its final forward %d is %g: the final prediction takes no noise, expected 0", b, i, (double)en);
+        }
     }
     if (requests[0].n_levels != n_max) return fail(TLD_ERR_INVALID, "n_max = %d, but the longest request has %d levels", n_max, requests[0].n_levels);
     if (!e || !noise || !labels || !out_latent) return fail(TLD_ERR_INVALID, "null argument");
     if (!e->finalized) return fail(TLD_ERR_STATE, "weights not finalized");
     if (!guided && 2 * batch > e->cfg.max_batch)
         return fail(TLD_ERR_INVALID, "sampler batch %d needs max_batch >= %d (have %d)", batch, 2 * batch, e->cfg.max_batch);
+    // the stochastic entry always runs the slots flavour of the step: without a table it gets the records' guidance at every forward, no sample skipped
+    std::vector<float> own_guidance;
+    const bool skip = e->guidance_skip && !(stochastic && !guided);
+    if (stochastic && !guided) {
+        own_guidance.assign((size_t)B * n_max, 0.0f);
+        for (int b = 0; b < B; ++b)
+            for (int i = 0; i < requests[b].n_levels; ++i) own_guidance[(size_t)b * n_max + i] = requests[b].class_guidance;
+        guidance = own_guidance.data();
+    }
     if (guided) {     // the largest model batch of the call: the requests still running plus those of them guided at that step
         std::vector<int> slot((size_t)B);
         for (int i = 0, Bi = B; i < n_max; ++i) {
             while (requests[Bi - 1].n_levels <= i) --Bi;
-            const int mb = Bi + guided_slots(guidance, n_max, Bi, i, e->guidance_skip, slot.data());
+            const int mb = Bi + guided_slots(guidance, n_max, Bi, i, skip, slot.data());
             if (mb > e->cfg.max_batch)
                 return fail(TLD_ERR_INVALID, "step %d runs %d requests and %d unconditional samples: needs max_batch >= %d (have %d)", i, Bi, mb - Bi, mb,
                             e->cfg.max_batch);
@@ -1157,11 +1194,12 @@ static int sample_requests(tld_engine* e, const void* noise, const void* init_la
     DeviceGuard dg(e->cfg.device_id);
     PathScope paths(e);                                       // (debug: the launch paths are recorded; no stage of this entry is kept)
     SamplePlan p{};
-    p.B = B; p.n_max = n_max; p.stride = 1; p.requests = requests; p.coeffs = coeffs; p.guidance = guided ? guidance : nullptr; p.Tn = Tn; p.sig = sig.data(); p.noise_idx = noise_idx.data();
+    p.B = B; p.n_max = n_max; p.stride = 1; p.requests = requests; p.coeffs = coeffs; p.guidance = (guided || stochastic) ? guidance : nullptr; p.skip = skip; p.Tn = Tn; p.sig = sig.data(); p.noise_idx = noise_idx.data();
     p.noise = static_cast<const float*>(noise); p.init_latent = static_cast<const float*>(init_latent); p.mask = static_cast<const float*>(mask);
     p.labels = static_cast<const float*>(labels); p.neg_labels = static_cast<const float*>(neg_labels); p.sharp = sharp_f; p.bright = bright_f;
     p.out_latent = static_cast<float*>(out_latent); p.trace_x0 = static_cast<float*>(trace_x0); p.trace_xt = static_cast<float*>(trace_xt);
     p.path_step = mask ? EP_UPDATE_REQ_MASK : EP_UPDATE_REQ; p.path_start = EP_START_MIX_REQ; p.keep_stages = false;
+    if (stochastic) { p.noise_coeff = noise_coeff; p.noise_keys = noise_keys; }
     return run_sampler(e, p, static_cast<hipStream_t>(hip_stream));
 }
 
@@ -1177,6 +1215,22 @@ int tld_sample_requests_guided(tld_engine* e, const void* noise, const void* ini
                                float bright_f, void* out_latent, int32_t batch, void* trace_x0, void* trace_xt, void* hip_stream) {
     return sample_requests(e, noise, init_latent, mask, labels, neg_labels, requests, coeffs, guidance, true, n_max, sharp_f, bright_f, out_latent, batch,
                            trace_x0, trace_xt, hip_stream);
+}
+
+int tld_sample_requests_stochastic(tld_engine* e, const void* noise, const void* init_latent, const void* mask, const void* labels, const void* neg_labels,
+                                   const tld_sample_request* requests, const float* coeffs, const float* guidance, const float* noise_coeff,
+                                   const uint64_t* noise_keys, int32_t n_max, float sharp_f, float bright_f, void* out_latent, int32_t batch,
+                                   void* trace_x0, void* trace_xt, void* hip_stream) {
+    return sample_requests(e, noise, init_latent, mask, labels, neg_labels, requests, coeffs, guidance, guidance != nullptr, n_max, sharp_f, bright_f,
+                           out_latent, batch, trace_x0, trace_xt, hip_stream, true, noise_coeff, noise_keys);
+}
+
+int tld_debug_sampler_noise(const uint64_t* keys_device, const uint32_t* steps_device, int32_t batch, int32_t img, float* out_device, void* hip_stream) {
+    if (!keys_device || !steps_device || !out_device) return fail(TLD_ERR_INVALID, "null argument");
+    if (batch <= 0 || img <= 0) return fail(TLD_ERR_INVALID, "need positive sizes (batch %d, img %d)", batch, img);
+    launch_sampler_noise_debug(keys_device, steps_device, batch, img, out_device, static_cast<hipStream_t>(hip_stream));
+    HIP_TRY(hipGetLastError());
+    return TLD_OK;
 }
 
 int tld_engine_sample_rows(tld_engine* e, int64_t* cond, int64_t* uncond) {

@@ -14,6 +14,8 @@
 // multiple of the head width 64, transformer_blocks.py:126-128): the last group then holds 64 features in lanes 0-31
 // and lanes 32-63 carry zeros through every sum and skip their loads / stores (`live`).
 #include "tld_common.h"
+#include "tld_sampler_noise.h"    // the counter of the stochastic sampler's noise
+#include "tld_normal_device.h"    // philox_normals4
 #include <cstdlib>
 
 namespace tld {
@@ -1139,6 +1141,12 @@ __global__ __launch_bounds__(256) void tail_fold_debug_row_kernel(float* __restr
 }
 #endif
 
+// the four normals of elements 4 quad .. 4 quad + 3 of a request's image at forward `step` (tld_sampler_noise.h): the one function behind the NOISE flavour of the
+// step kernel and tld_debug_sampler_noise
+__device__ __forceinline__ void sampler_noise4(uint32_t key_lo, uint32_t key_hi, uint32_t step, uint32_t quad, float n[4]) {
+    philox_normals4(sampler_noise_philox(((uint64_t)key_hi << 32) | key_lo, step, quad), n);
+}
+
 // ------------------------------------------------------------------------------------------------
 // The sampler's elementwise step, one launch per step for all three sampler entries: CFG combine, DPM-Solver++(2M)/DDIM update,
 // latent shifts, and with MASK the inpainting blend.  Sample b takes {g, a, b, c, c1, c2, s_next, final} from rows[b * row_stride]: a row per
@@ -1154,7 +1162,10 @@ __global__ __launch_bounds__(256) void tail_fold_debug_row_kernel(float* __restr
 // no contraction it rounds as the fp32 reference loop does.
 // SLOT (tld_sample_requests_guided): a request has an unconditional sample only at the steps it is guided at.  Its row's `final_step` then holds
 // final | (slot + 1) << 1: the unconditional operand sits at sample active + slot of the model output, and a row without a slot takes x0 = cond itself.
-template <bool MASK, int V, bool SLOT = false>
+// NOISE (tld_sample_requests_stochastic): after the update and before the blend, x_t <- x_t + e z with the product rounded, then the sum;
+// e and the key come from noise_rows[b * row_stride], z from the counter (quad of the element inside the request's own image, noise_step) under that key
+// (sampler_noise4).  A row with e == 0.0f draws nothing and adds nothing: the arithmetic above exactly.  The final step returns before it.
+template <bool MASK, int V, bool SLOT = false, bool NOISE = false>
 __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p) {
 #pragma clang fp contract(off)
     const int i = (blockIdx.x * 256 + threadIdx.x) * V;
@@ -1203,11 +1214,28 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p) 
     load(prev, p.x0_prev + i);
     load(xin, p.x_t + i);
     if constexpr (MASK) load(eps, p.noise + i);
+    float en = 0.0f, nz[V];
+    if constexpr (NOISE) {
+        const SamplerNoiseRow nq = p.noise_rows[b * p.row_stride];
+        en = nq.e;
+        if (en != 0.0f) {
+            float n4[4];
+            sampler_noise4(nq.key_lo, nq.key_hi, p.noise_step, (uint32_t)r >> 2, n4);
+            if constexpr (V == 4) {
+#pragma unroll
+                for (int v = 0; v < 4; ++v) nz[v] = n4[v];
+            } else {                                                          // the quad's counter, this thread's own element
+                const int k = r & 3;
+                nz[0] = (k & 2) ? ((k & 1) ? n4[3] : n4[2]) : ((k & 1) ? n4[1] : n4[0]);
+            }
+        }
+    }
 #pragma unroll
     for (int v = 0; v < V; ++v) {
         const float x0 = combine(cond[v], unc[v]);
         const float D = __builtin_fmaf(q.c1, x0, -(q.c2 * prev[v]));      // diffusion.py:76 (c1=1,c2=0: :72/:79)
         float xt = (q.a * D + q.b * xin[v]) / q.c;                        // diffusion.py:81
+        if constexpr (NOISE) { if (en != 0.0f) xt = xt + en * nz[v]; }
         if constexpr (MASK) {
             const float known = q.s_next * eps[v] + (1.0f - q.s_next) * z[v];
             xt = m[v] * xt + (1.0f - m[v]) * known;
@@ -1239,6 +1267,23 @@ __global__ __launch_bounds__(256) void start_mix_kernel(const float* __restrict_
     } else {
         x_t[i] = s0 == 1.0f ? noise[i] : s0 * noise[i] + (1.0f - s0) * z0[i];
     }
+}
+
+// tld_debug_sampler_noise: z[b, 4 quad + k] = element k of sampler_noise4(keys[b], steps[b], quad); a thread owns one quad, scalar stores (img need
+// not be a multiple of 4: the last quad of an image is cut)
+__global__ __launch_bounds__(256) void sampler_noise_debug_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ steps, int batch, int img,
+                                                                  float* __restrict__ z) {
+    const int quads = (img + 3) >> 2;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (int64_t)batch * quads) return;
+    const int b = (int)(t / quads), quad = (int)(t - (int64_t)b * quads);
+    const uint64_t key = keys[b];
+    float n4[4];
+    sampler_noise4((uint32_t)key, (uint32_t)(key >> 32), steps[b], (uint32_t)quad, n4);
+    float* dst = z + (int64_t)b * img + 4 * quad;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (4 * quad + k < img) dst[k] = n4[k];
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1665,7 +1710,15 @@ void launch_sampler_step(const SamplerStepParams& p, int path, hipStream_t s, bo
     const int threads = vec ? n / 4 : n;
     const dim3 grid((threads + 255) / 256), block(256);
     note_path(path);
-    if (slots) {
+    if (slots && p.noise_rows) {
+        if (p.mask) {
+            if (vec) hipLaunchKernelGGL((sampler_step_kernel<true, 4, true, true>), grid, block, 0, s, p);
+            else hipLaunchKernelGGL((sampler_step_kernel<true, 1, true, true>), grid, block, 0, s, p);
+        } else {
+            if (vec) hipLaunchKernelGGL((sampler_step_kernel<false, 4, true, true>), grid, block, 0, s, p);
+            else hipLaunchKernelGGL((sampler_step_kernel<false, 1, true, true>), grid, block, 0, s, p);
+        }
+    } else if (slots) {
         if (p.mask) {
             if (vec) hipLaunchKernelGGL((sampler_step_kernel<true, 4, true>), grid, block, 0, s, p);
             else hipLaunchKernelGGL((sampler_step_kernel<true, 1, true>), grid, block, 0, s, p);
@@ -1680,6 +1733,11 @@ void launch_sampler_step(const SamplerStepParams& p, int path, hipStream_t s, bo
         if (vec) hipLaunchKernelGGL((sampler_step_kernel<false, 4>), grid, block, 0, s, p);
         else hipLaunchKernelGGL((sampler_step_kernel<false, 1>), grid, block, 0, s, p);
     }
+}
+
+void launch_sampler_noise_debug(const uint64_t* keys, const uint32_t* steps, int batch, int img, float* z, hipStream_t s) {
+    const int64_t threads = (int64_t)batch * ((img + 3) / 4);
+    hipLaunchKernelGGL(sampler_noise_debug_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, keys, steps, batch, img, z);
 }
 
 void launch_start_mix(const float* noise, const float* z0, const float* s0v, int s0_stride, float* x_t, int batch, int img, int path, hipStream_t s) {

@@ -374,7 +374,8 @@ class Denoiser:
 
     @torch.no_grad()
     def sample_latents_requests(self, noise: torch.Tensor, labels: torch.Tensor, coeff_list, guidance, *, neg_labels=None, init_latents=None,
-                                start_mix=None, mask=None, sharp_f: float = 0.0, bright_f: float = 0.0, trace: bool = False, guidance_steps=None):
+                                start_mix=None, mask=None, sharp_f: float = 0.0, bright_f: float = 0.0, trace: bool = False, guidance_steps=None,
+                                noise_coeffs=None, noise_keys=None):
         """B independent requests in one on-device sampler call (tld_sample_requests).
 
         ``noise`` [B,C,S,S], ``labels`` [B,text]; ``coeff_list``: B tables ``schedule.step_coefficients(...)`` (each request's own levels
@@ -386,6 +387,12 @@ class Denoiser:
         ``guidance_steps``: B arrays, request b's guidance per forward (``coeff_list[b].shape[0]`` values, e.g. ``schedule.guidance_table``); the
         call is then tld_sample_requests_guided: ``guidance`` is ignored (it may be None), a forward whose value is exactly
         1.0 runs no unconditional sample, and the engine is reserved for the largest step, ``max_i (B_i + U_i)`` samples, instead of 2 B.
+        ``noise_coeffs`` + ``noise_keys`` (both or neither): the call is tld_sample_requests_stochastic.  ``noise_coeffs``: B
+        arrays, request b's ``e`` per forward (``coeff_list[b].shape[0]`` values, finite, >= 0, the last one 0 -- the second result of
+        ``schedule.step_coefficients(..., eta)``, whose table belongs in ``coeff_list``); ``noise_keys``: B ints, each request's 64-bit noise key
+        (``schedule.noise_key``).  After an inner step's update the kernel adds ``e z``, z the normals of (key, forward, element): request b's
+        result is bit for bit that of the request alone with the same key, and all-zero arrays give the call without them.  With
+        ``guidance_steps`` the model batches are the guided call's; without, the CFG-doubled ones.
         Its own here: the records' checks, the engine's order, the row cap and the negative labels as one tensor; the rest is ``_run_sampler``."""
         from . import schedule
         B = noise.shape[0]
@@ -418,6 +425,24 @@ class Denoiser:
                 raise ValueError(f"guidance_steps[{b}] holds a value that is not finite")
         if init_latents is None and (mask is not None or any(v < 1.0 for v in mix)):
             raise ValueError("init_latents is required with a mask or with a start_mix < 1")
+        if (noise_coeffs is None) != (noise_keys is None):
+            raise ValueError("noise_coeffs and noise_keys come together")
+        ecs = keys = None
+        if noise_coeffs is not None:
+            ecs = [np.ascontiguousarray(t, dtype=np.float32) for t in noise_coeffs]
+            keys = [int(k) for k in noise_keys]
+            for what, seq in (("noise_coeffs", ecs), ("noise_keys", keys)):
+                if len(seq) != B:
+                    raise ValueError(f"{what}: {len(seq)} entries for {B} requests")
+            for b, t in enumerate(ecs):
+                if t.ndim != 1 or t.shape[0] != tabs[b].shape[0]:
+                    raise ValueError(f"noise_coeffs[{b}] {t.shape}: expected [{tabs[b].shape[0]}], one value per forward")
+                if not (np.isfinite(t).all() and (t >= 0).all()):
+                    raise ValueError(f"noise_coeffs[{b}] holds a value that is not finite and >= 0")
+                if t[-1] != 0:
+                    raise ValueError(f"noise_coeffs[{b}][-1] = {t[-1]}: the final prediction takes no noise, expected 0")
+                if not 0 <= keys[b] < 1 << 64:
+                    raise ValueError(f"noise_keys[{b}] = {keys[b]}: expected a 64-bit unsigned value")
         neg, has_neg = None, [False] * B
         if neg_labels is not None:
             if isinstance(neg_labels, torch.Tensor):
@@ -446,6 +471,7 @@ class Denoiser:
         for k, b in enumerate(order):
             table[k, :counts[b]] = tabs[b]
             recs[k] = _lib.TldSampleRequest(counts[b], guid[b], mix[b], int(has_neg[b]))
+        gtab, model_batch = None, None
         if steps is not None:
             gtab = np.zeros((B, n_max), dtype=np.float32)
             for k, b in enumerate(order):
@@ -458,16 +484,28 @@ class Denoiser:
                 U = schedule.guided_rows(sc, [steps[b] for b in order], skip)[0]
                 return max(bi + u for bi, u in zip(schedule.active_prefix(sc), U))
 
-            return self._run_sampler(noise, labels, n_max, trace, lambda h, B, eps, z0, m, lab, ng, out, tx0, txt, stream: _lib.check(
-                _lib.lib().tld_sample_requests_guided(h, eps, z0, m, lab, ng, recs, table.ctypes.data_as(C.POINTER(C.c_float)),
-                                                      gtab.ctypes.data_as(C.POINTER(C.c_float)), n_max, float(sharp_f), float(bright_f), out, B, tx0,
-                                                      txt, stream), "tld_sample_requests_guided"),
-                init_latents=init_latents, mask=mask, neg_labels=neg, order=order, new_trace=torch.zeros, model_batch=model_batch)
+        fp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
         # traces start as zeros: the engine leaves a finished request's slots alone
+        common = dict(init_latents=init_latents, mask=mask, neg_labels=neg, order=order, new_trace=torch.zeros)
+        if ecs is not None:              # (guidance NULL: the records' scales on the CFG-doubled batch)
+            etab = np.zeros((B, n_max), dtype=np.float32)
+            ktab = np.zeros(B, dtype=np.uint64)
+            for k, b in enumerate(order):
+                etab[k, :counts[b]] = ecs[b]
+                ktab[k] = keys[b]
+            return self._run_sampler(noise, labels, n_max, trace, lambda h, B, eps, z0, m, lab, ng, out, tx0, txt, stream: _lib.check(
+                _lib.lib().tld_sample_requests_stochastic(h, eps, z0, m, lab, ng, recs, fp(table), fp(gtab), fp(etab),
+                                                          ktab.ctypes.data_as(C.POINTER(C.c_uint64)), n_max, float(sharp_f), float(bright_f), out, B,
+                                                          tx0, txt, stream), "tld_sample_requests_stochastic"),
+                model_batch=model_batch, **common)
+        if steps is not None:
+            return self._run_sampler(noise, labels, n_max, trace, lambda h, B, eps, z0, m, lab, ng, out, tx0, txt, stream: _lib.check(
+                _lib.lib().tld_sample_requests_guided(h, eps, z0, m, lab, ng, recs, fp(table), fp(gtab), n_max, float(sharp_f), float(bright_f), out, B,
+                                                      tx0, txt, stream), "tld_sample_requests_guided"),
+                model_batch=model_batch, **common)
         return self._run_sampler(noise, labels, n_max, trace, lambda h, B, eps, z0, m, lab, ng, out, tx0, txt, stream: _lib.check(
-            _lib.lib().tld_sample_requests(h, eps, z0, m, lab, ng, recs, table.ctypes.data_as(C.POINTER(C.c_float)), n_max, float(sharp_f),
-                                           float(bright_f), out, B, tx0, txt, stream), "tld_sample_requests"),
-            init_latents=init_latents, mask=mask, neg_labels=neg, order=order, new_trace=torch.zeros)
+            _lib.lib().tld_sample_requests(h, eps, z0, m, lab, ng, recs, fp(table), n_max, float(sharp_f), float(bright_f), out, B, tx0, txt, stream),
+            "tld_sample_requests"), **common)
 
     # ---- test / bench hooks -----------------------------------------------------------------------------
     # launch paths of tld_engine_debug_paths, by bit number (include/tld_hip.h; None: a bit no default engine sets).  "tail folded" (out_proj folded into

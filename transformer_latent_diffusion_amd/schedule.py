@@ -116,12 +116,72 @@ def multistep_ratios(noise_levels: Sequence[float]) -> List[float]:
     return [hs[i - 1] / hs[i] for i in range(1, len(hs))]
 
 
-def step_coefficients(noise_levels: Sequence[float], use_ddpm_plus: bool = True) -> np.ndarray:
+def check_eta(eta) -> float:
+    """``eta`` of the stochastic sampler as a float: finite and >= 0, else ValueError."""
+    try:
+        v = float(eta)
+    except (TypeError, ValueError):
+        raise ValueError(f"eta = {eta!r}: expected a number")
+    if not math.isfinite(v) or v < 0.0:
+        raise ValueError(f"eta = {eta!r}: expected a finite value >= 0")
+    return v
+
+
+def stochastic_step_coefficients_f64(noise_levels: Sequence[float], use_ddpm_plus: bool, eta: float) -> Tuple[np.ndarray, np.ndarray]:
+    """The float64 table and noise coefficients ``step_coefficients(..., eta > 0)`` rounds to float32.
+
+    With alpha = 1 - sigma, lambda = log(alpha / sigma), a step from level s to t, h = lambda_t - lambda_s > 0 and D = c1 x0 - c2 x0_prev:
+
+        x_t = (sigma_t / sigma_s) e^{-eta h} x_s + alpha_t (1 - e^{-(1 + eta) h}) D + sigma_t sqrt(1 - e^{-2 eta h}) z,   z ~ N(0, I)
+
+    the eta form of k-diffusion's ``sample_dpmpp_2m_sde`` ("midpoint") written for a general alpha; c1 = c2 + 1 = 1 + 1 / (2 r) are the
+    deterministic solver's (first order on the first step, and throughout with ``use_ddpm_plus=False``: DDIM with that eta).  In the kernel's
+    spelling ``x_t = (a D + b x_s) / c``: c = sigma_s, b = sigma_t e^{-eta h}, a = sigma_s alpha_t (1 - e^{-(1 + eta) h}), and the new
+    e = sigma_t sqrt(1 - e^{-2 eta h}).  Both 1 - e^{-x} are evaluated as -expm1(-x).  Returns ``(table [n, 6], e [n])``; the last row is the
+    final prediction's (e = 0).  Raises ValueError unless eta is finite and > 0 and the levels lie in (0, 1) and strictly decrease."""
+    eta = check_eta(eta)
+    nl = [float(v) for v in noise_levels]
+    n = len(nl)
+    if not eta > 0.0:
+        raise ValueError("eta = 0 is the deterministic table: step_coefficients(levels, use_ddpm_plus)")
+    if n < 2:
+        raise ValueError("a trajectory needs at least two noise levels")
+    if not all(math.isfinite(v) and 0.0 < v < 1.0 for v in nl):
+        raise ValueError(f"eta > 0 needs every noise level inside (0, 1) (lambda = log((1 - sigma) / sigma)); have {nl}")
+    if any(nl[i + 1] >= nl[i] for i in range(n - 1)):
+        raise ValueError(f"eta > 0 needs strictly decreasing noise levels (h = lambda_t - lambda_s > 0); have {nl}")
+    lam = [math.log((1.0 - s) / s) for s in nl]
+    rs = multistep_ratios(nl) if use_ddpm_plus else None
+    tab = np.zeros((n, 6), dtype=np.float64)
+    e = np.zeros(n, dtype=np.float64)
+    for i in range(n - 1):
+        s, t = nl[i], nl[i + 1]
+        h = lam[i + 1] - lam[i]
+        c1, c2 = 1.0, 0.0
+        if i > 0 and use_ddpm_plus:
+            c1 = 1 + 1 / (2 * rs[i - 1])
+            c2 = 1 / (2 * rs[i - 1])
+        tab[i] = (s, s * (1.0 - t) * -math.expm1(-(1.0 + eta) * h), t * math.exp(-eta * h), s, c1, c2)
+        e[i] = t * math.sqrt(-math.expm1(-2.0 * eta * h))
+    tab[n - 1] = (nl[n - 1], 0.0, 0.0, 1.0, 1.0, 0.0)
+    return tab, e
+
+
+def step_coefficients(noise_levels: Sequence[float], use_ddpm_plus: bool = True, eta: float = 0.0):
     """float32 table [n_levels, 6] = (sigma, a, b, c, c1, c2) per forward.
 
     Row i < n_levels-1 drives loop iteration i (diffusion.py:66-83); the last row is the final
     prediction at ``next_noise`` of the last iteration (:85), for which only sigma is meaningful.
+
+    ``eta`` (not in the reference): 0 returns this table, from this code.  ``eta > 0`` returns ``(table, e)``: the
+    table of the SDE solver (``stochastic_step_coefficients_f64``) and the float32 vector ``e`` [n_levels] of the noise added after each
+    step's update, 0 for the final prediction.  A negative or non-finite eta, or with eta > 0 levels that do not strictly decrease inside
+    (0, 1), raise ValueError before anything else.
     """
+    eta = check_eta(eta)
+    if eta > 0.0:
+        tab64, e64 = stochastic_step_coefficients_f64(noise_levels, use_ddpm_plus, eta)
+        return tab64.astype(np.float32), e64.astype(np.float32)
     nl = [float(v) for v in noise_levels]
     n = len(nl)
     if n < 2:
@@ -200,6 +260,14 @@ def guidance_table(coeffs: np.ndarray, class_guidance: float, interval: Optional
         raise ValueError(f"guidance interval ({interval[0]}, {interval[1]}): expected lo <= hi")
     inside = (sig[:, 0] >= lo) & (sig[:, 0] <= hi)
     return np.where(inside, g, np.float32(1.0)).astype(np.float32)
+
+
+# ---- noise inside the step (tld_sample_requests_stochastic) ---------------------------------------------------------------
+def noise_key(seed: int, index: int = 0) -> int:
+    """A request's default 64-bit noise key: ``(seed & 0xffffffff) | (index << 32)``, ``index`` the image's place inside the ``torch.randn`` draw
+    that made its start noise -- b under one batch seed, 0 where each request has its own seed.  A one-image call with seed s and the request
+    "seed s" of a batched call then share the key, as they share the start noise."""
+    return (int(seed) & 0xFFFFFFFF) | ((int(index) & 0xFFFFFFFF) << 32)
 
 
 def guided_rows(sorted_counts: Sequence[int], tables: Sequence[np.ndarray], skip: bool = True):

@@ -105,7 +105,7 @@ def generate_latents_requests_sharded(gen, labels: torch.Tensor, *, group: Optio
                                       **per_request) -> torch.Tensor:
     """``DiffusionGenerator.generate_latents_requests`` over all ranks of ``group`` (same arguments, without ``trace``).  The noise,
     labels, negative labels, initial latents and masks travel as per-sample tensors; the per-request sequences (``n_iter``,
-    ``class_guidance``, ``exponent``, ``strength``, ``use_ddpm_plus``) ride as the requests' indices, one more ``extras`` tensor sliced
+    ``class_guidance``, ``exponent``, ``strength``, ``use_ddpm_plus``, ``eta``, ``noise_seeds``) ride as the requests' indices, one more ``extras`` tensor sliced
     with the same bounds, and every rank picks its own entries.  The noise is drawn and the optional operands are stacked by the helpers
     ``generate_latents_requests`` itself uses; a whole tensor travels as it is (``sharded_sample`` checks its batch)."""
     B = labels.shape[0]
@@ -116,6 +116,10 @@ def generate_latents_requests_sharded(gen, labels: torch.Tensor, *, group: Optio
         per_request["guidance_interval"] = per_request_intervals(per_request["guidance_interval"], B)
     if per_request.get("guidance_schedule") is not None:
         per_request["guidance_schedule"] = list(per_request["guidance_schedule"])
+    # the stochastic sampler: a request's noise key belongs to the request, so the default keys are made here, from the whole batch's seeds, and sliced
+    eta = per_request.get("eta", 0.0)
+    if any(float(v) > 0.0 for v in ([eta] if not isinstance(eta, (list, tuple)) else eta)):
+        per_request["noise_seeds"] = gen._noise_keys(seeds, per_request.get("noise_seeds"), B, seed)
 
     def tensor_of(v, what, shape, fill):
         return v if isinstance(v, torch.Tensor) else stack_optional(v, what, B, shape, fill)
