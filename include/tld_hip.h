@@ -224,6 +224,32 @@ TLD_API int tld_sample_requests_stochastic(tld_engine* e, const void* noise, con
  * steps_device[b] (uint32, device) over an image of img elements, from the device function the step kernel calls.  img need not be a multiple of 4 */
 TLD_API int tld_debug_sampler_noise(const uint64_t* keys_device, const uint32_t* steps_device, int32_t batch, int32_t img, float* out_device,
                void* hip_stream);
+/* tld_sample_requests_stochastic with a shape for the guidance update: guidance rescale and adaptive projected guidance, per request.
+ * One more HOST array:
+ *   shape [batch][4] fp32: (eta_par, norm_r, beta, phi) of request b.  eta_par: weight of the part of the update cond - unc parallel to cond (1: off);
+ *         norm_r: the update's norm over the request's image is clipped to it (0: off); beta: momentum over the updates, d + beta m with m the
+ *         previous guided forward's update, zero at the call's start (0: off; APG uses negative values); phi: guidance rescale, the standard deviation
+ *         of the prediction over the request's image is pulled towards that of cond (0: off).  Refused: non-finite values, eta_par < 0, norm_r < 0,
+ *         |beta| >= 1, phi outside [0, 1]
+ * A request whose row is (1, 0, 0, 0) takes fma(g, cond, (1 - g) unc) as every other entry does, the same bits; so does every request at a forward
+ * that runs no unconditional sample (x0 = cond) or is guided at exactly 1.0f, which neither reads nor writes the momentum.  Otherwise a launch of one workgroup per running
+ * request sums cond, dbar, cond^2, dbar cond, dbar^2 over the request's whole image (a masked-out known region included) in double, in an order
+ * that depends on the image size alone, makes two fp32 weights (csrc/tld_guidance_shape.h), and the step takes x0 = fma(P, cond, fl32(Q dbar)).
+ * Request b's result is bit for bit that of the request alone.  A step in which no running request needs that launch does not make it.
+ *   noise_coeff, noise_keys  as in tld_sample_requests_stochastic, or both NULL: no noise
+ *   guidance                 as there, or NULL
+ * tld_engine_sample_rows and the launch-path bits are those of the entry it generalises; the statistics launch is timed in the `update` class.
+ * Every refusal happens before anything is enqueued; no stream synchronisation. */
+TLD_API int tld_sample_requests_shaped(tld_engine* e, const void* noise, const void* init_latent, const void* mask, const void* labels,
+               const void* neg_labels, const tld_sample_request* requests, const float* coeffs, const float* guidance, const float* noise_coeff,
+               const uint64_t* noise_keys, const float* shape, int32_t n_max, float sharp_f, float bright_f, void* out_latent, int32_t batch,
+               void* trace_x0, void* trace_xt, void* hip_stream);
+/* engine-free: the statistics kernel and the combine of the shaped step on cond_device, unc_device [batch, img] fp32 under the HOST arrays g [batch]
+ * and shape [batch][4]: x0_device [batch, img] fp32, pq_device [batch][2] fp32 (P, Q), sums_device [batch][5] double (sum c, sum dbar, sum c^2,
+ * sum dbar c, sum dbar^2); zeros for a neutral row, whose x0 is plain CFG.  mom_device [batch, img] fp32 or NULL: read, and overwritten with dbar, for the
+ * entries with beta != 0 (NULL: every beta must be 0).  img need not be a multiple of 4.  Returns after the stream has finished */
+TLD_API int tld_debug_guidance_shape(const float* cond_device, const float* unc_device, float* mom_device, const float* g, const float* shape,
+               int32_t batch, int32_t img, float* x0_device, float* pq_device, double* sums_device, void* hip_stream);
 /* model samples the last sampler call on this engine enqueued: conditional and unconditional.  tld_sample / tld_sample_from / tld_sample_requests
  * report sum(n_levels) twice; tld_sample_requests_guided reports (sum(n_levels), sum(U_i)) */
 TLD_API int tld_engine_sample_rows(tld_engine* e, int64_t* cond, int64_t* uncond);

@@ -23,7 +23,7 @@ KERNEL_CLASSES = ("gemm_qkv", "gemm_up", "gemm_down", "attention", "cross_row", 
 # every symbol include/tld_hip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = (
     "tld_engine_create", "tld_engine_load_tensor", "tld_engine_finalize_weights", "tld_denoiser_forward",
-    "tld_sample", "tld_sample_from", "tld_sample_requests", "tld_sample_requests_guided", "tld_sample_requests_stochastic", "tld_debug_sampler_noise", "tld_engine_sample_rows", "tld_engine_set_gemm_dtype", "tld_engine_set_low_latency", "tld_debug_gemm_splitk", "tld_debug_quant_mx8", "tld_debug_quant_mx8_host", "tld_debug_gemm_mx8",
+    "tld_sample", "tld_sample_from", "tld_sample_requests", "tld_sample_requests_guided", "tld_sample_requests_stochastic", "tld_debug_sampler_noise", "tld_sample_requests_shaped", "tld_debug_guidance_shape", "tld_engine_sample_rows", "tld_engine_set_gemm_dtype", "tld_engine_set_low_latency", "tld_debug_gemm_splitk", "tld_debug_quant_mx8", "tld_debug_quant_mx8_host", "tld_debug_gemm_mx8",
     "tld_engine_param_count", "tld_engine_refresh_weights", "tld_debug_quant_mx8_f32",
     "tld_debug_decode_stage", "tld_engine_set_debug", "tld_engine_read_stage", "tld_engine_stage_shape", "tld_engine_set_debug_step", "tld_engine_debug_paths", "tld_debug_gemm_bf16", "tld_debug_gemm_bench", "tld_debug_gemm_plan", "tld_debug_qkv_pair_plan", "tld_debug_gemm_epilogue",
     "tld_engine_set_profile", "tld_engine_profile_reserve", "tld_engine_get_profile", "tld_engine_weight_bytes", "tld_engine_destroy",
@@ -153,6 +153,11 @@ def lib() -> C.CDLL:
         L.tld_sample_requests_stochastic.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(TldSampleRequest), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                                      C.POINTER(C.c_float), C.POINTER(C.c_uint64), i32, C.c_float, C.c_float, vp, i32, vp, vp, vp]
         L.tld_debug_sampler_noise.argtypes = [vp, vp, i32, i32, vp, vp]
+    if hasattr(L, "tld_sample_requests_shaped"):         # (absent from A/B builds that predate the shaped guidance update)
+        L.tld_sample_requests_shaped.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(TldSampleRequest), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                                 C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_float), i32, C.c_float, C.c_float, vp, i32,
+                                                 vp, vp, vp]
+        L.tld_debug_guidance_shape.argtypes = [vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), i32, i32, vp, vp, vp, vp]
     L.tld_engine_set_gemm_dtype.argtypes = [vp, i32]
     L.tld_engine_set_low_latency.argtypes = [vp, i32]
     L.tld_debug_gemm_splitk.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]

@@ -4,6 +4,7 @@
 #include <atomic>
 #include <mutex>
 #include <stdint.h>
+#include "tld_guidance_shape.h"   // GuidanceShape, guidance_shape_finalize
 #include "tld_qkv_pair_plan.h"    // plan_qkv_pair: one or two heads per tile of the fused QKV + attention kernel
 #include "tld_gemm_plan.h"        // GemmParams, GemmEpilogue, bf16, resid_t, kLnSlots (tld_gemm_params.h); GemmPlan, gemm_resid_stat_slots
 
@@ -464,12 +465,33 @@ struct SamplerStepParams {
     // the NOISE flavour only (tld_sample_requests_stochastic): this step's rows of the second device table and the forward index
     const SamplerNoiseRow* noise_rows;            // sample b reads noise_rows[b * row_stride]; null: no flavour of the kernel reads it
     uint32_t noise_step;
+    // the SHAPE flavour only (tld_sample_requests_shaped), on top of NOISE: the requests' shape rows, this step's (P, Q) of
+    // guidance_stats_kernel and the momentum buffer
+    const GuidanceShape* shape_rows;              // sample b reads shape_rows[b * row_stride]; null: no flavour of the kernel reads it
+    const float2* shape_pq;                       // [B] written by the stats launch of this step for the rows that are shaped and have a slot
+    float* shape_mom;                             // [B, img] read and written where the row's beta != 0
 };
 // path: the EP_UPDATE* bit that names the flavour of step the calling entry asked for
 // slots (tld_sample_requests_guided): x0_2b is [active cond samples | the unconditional samples of the requests guided at this step], and a row's
 // final_step holds final | (slot + 1) << 1 -- the unconditional operand of the request is sample active + slot; slot + 1 == 0: none, x0 = cond itself
-// p.noise_rows non-null (slots only): the NOISE flavour
+// p.noise_rows non-null (slots only): the NOISE flavour; p.shape_rows non-null as well: the SHAPE flavour
 void launch_sampler_step(const SamplerStepParams& p, int path, hipStream_t s, bool slots = false);
+// The statistics of the shaped guidance update (tld_guidance_shape.h), one workgroup per request b < active: over cond + b img, the unconditional
+// sample unc_base + slot img (slot from rows[b * row_stride].final_step as the slots flavour of the step packs it) and, where the row's beta != 0,
+// mom + b img, the five sums in double -> sums[5 b ..] and (P, Q) of rows[..].g -> pq[b].  A neutral row or a row without a slot writes nothing.
+struct GuidanceStatsParams {
+    const float *cond, *unc_base, *mom;
+    const SamplerStepRow* rows;
+    const GuidanceShape* shape_rows;
+    int row_stride, active, img;
+    float2* pq;
+    double* sums;
+};
+void launch_guidance_stats(const GuidanceStatsParams& p, hipStream_t s);
+// tld_debug_guidance_shape: x0[b] <- the SHAPE flavour's combine of (cond[b], unc[b], mom[b]) under pq[b], through the same device functions (a
+// neutral row: plain CFG at rows[b].g); mom (may be null) <- dbar where beta != 0
+void launch_guidance_shape_debug(const float* cond, const float* unc, float* mom, const SamplerStepRow* rows, const GuidanceShape* shape_rows,
+                                 const float2* pq, int batch, int img, float* x0, hipStream_t s);
 // z [batch, img] fp32 <- the normals sampler_step_kernel<.., NOISE> draws for (keys[b], steps[b]): the same device function (tld_debug_sampler_noise)
 void launch_sampler_noise_debug(const uint64_t* keys, const uint32_t* steps, int batch, int img, float* z, hipStream_t s);
 // x_t[b] = s0 noise[b] + (1 - s0) z0[b] with s0 = s0v[b * s0_stride] read from a device table; s0 == 1 copies noise[b] (z0 may then be null).  path: EP_START_MIX*

@@ -89,6 +89,11 @@ struct tld_engine : DeviceArena {      // (pad = 256: every allocation of this e
     hipEvent_t stage_ev = nullptr;     // recorded after the last copy out of stage_host
     void* req_dev = nullptr;           // the samplers' tables of one call (run_sampler): step rows, start mixes, token-row indices
     size_t req_cap = 0;
+    // the shaped guidance update (tld_sample_requests_shaped), allocated by the first call that needs them: the momentum buffer [max_batch, img], and
+    // per request (P, Q) and the five sums of the step's guidance_stats_kernel launch
+    float* shape_mom = nullptr;
+    float2* shape_pq = nullptr;
+    double* shape_sums = nullptr;
 
     // conditioning tables (sized for cond_cap token rows)
     int cond_cap = 0;
@@ -561,6 +566,8 @@ struct SamplePlan {
     bool skip;                           // with guidance: a forward guided at exactly 1.0f runs no unconditional sample (the engine's TLD_GUIDANCE_SKIP)
     // tld_sample_requests_stochastic (with guidance only): HOST [B][n_max] e of request b's forward i and HOST [B] keys; null: no noise, the kernels without the NOISE flag
     const float* noise_coeff; const uint64_t* noise_keys;
+    // tld_sample_requests_shaped (with noise_coeff only): HOST [B] shape rows; null: the kernels without the SHAPE flag
+    const GuidanceShape* shape;
     // conditioning noise rows: Tn sigmas and, per (step, request), the row of its sigma; null: row i is level i of the one table (the uniform entries)
     int Tn; const float* sig; const int* noise_idx;       // sig [Tn], noise_idx [n_max][B]
     const float *noise, *init_latent, *mask, *labels, *neg_labels;      // device; init_latent / mask / neg_labels optional
@@ -604,9 +611,31 @@ int run_sampler(tld_engine* e, const SamplePlan& p, hipStream_t s) {
     // (the stochastic entry's second table, 16-byte rows [n_max][tabB], rides behind the int tables in the same upload)
     const bool noisy = p.noise_coeff != nullptr;
     const size_t noise_off = (tab_bytes + mix_bytes + row_ints * sizeof(int) + 15) & ~(size_t)15;
-    const size_t up_bytes = noisy ? noise_off + (size_t)n_max * tabB * sizeof(SamplerNoiseRow) : tab_bytes + mix_bytes + row_ints * sizeof(int);
+    // (and the shaped entry's third table, one 16-byte row per request, behind that)
+    const bool shaped = noisy && p.shape != nullptr;
+    const size_t shape_off = noise_off + (size_t)n_max * tabB * sizeof(SamplerNoiseRow);
+    const size_t up_bytes = shaped ? shape_off + (size_t)tabB * sizeof(GuidanceShape)
+                            : noisy ? shape_off : tab_bytes + mix_bytes + row_ints * sizeof(int);
+    // the steps at which a running request is shaped, has an unconditional sample and is guided at other than 1.0f: only they launch the statistics kernel
+    // (a forward at exactly 1.0f is x0 = cond with the momentum left alone, with the engine's guidance skip on or off)
+    std::vector<char> stats_step((size_t)n_max, 0);
+    bool any_shape = false, any_mom = false;
+    if (shaped) {
+        for (int i = 0, Bi = B; i < n_max; ++i) {
+            while (req(Bi - 1).n_levels <= i) --Bi;
+            guided_slots(p.guidance, n_max, Bi, i, p.skip, slot.data());
+            for (int b = 0; b < Bi; ++b)
+                if (slot[(size_t)b] >= 0 && !p.shape[b].neutral() && p.guidance[(size_t)b * n_max + i] != 1.0f) { stats_step[(size_t)i] = 1; any_shape = true; any_mom |= p.shape[b].beta != 0.0f; }
+        }
+    }
     if (int rc = ensure_cond_capacity(e, T)) return rc;
     if (int rc = ensure_req_capacity(e, up_bytes)) return rc;
+    if (any_shape && !e->shape_pq)
+        if (int rc = dev_alloc(e, &e->shape_pq, (size_t)e->cfg.max_batch)) return rc;
+    if (any_shape && !e->shape_sums)
+        if (int rc = dev_alloc(e, &e->shape_sums, (size_t)e->cfg.max_batch * GS_SUMS)) return rc;
+    if (any_mom && !e->shape_mom)
+        if (int rc = dev_alloc(e, &e->shape_mom, (size_t)e->cfg.max_batch * e->img)) return rc;
     if (int rc = debug_begin(e, T, Tn, s)) return rc;
     if (int rc = stage_acquire(e, up_bytes + (size_t)Tn * sizeof(float))) return rc;
     SamplerStepRow* tab = static_cast<SamplerStepRow*>(e->stage_host);
@@ -621,6 +650,10 @@ int run_sampler(tld_engine* e, const SamplePlan& p, hipStream_t s) {
                 nt[(size_t)i * tabB + b] = SamplerNoiseRow{on ? p.noise_coeff[(size_t)b * n_max + i] : 0.0f, (uint32_t)p.noise_keys[b],
                                                            (uint32_t)(p.noise_keys[b] >> 32), 0u};
             }
+    }
+    if (shaped) {
+        GuidanceShape* st = reinterpret_cast<GuidanceShape*>(static_cast<char*>(e->stage_host) + shape_off);
+        for (int b = 0; b < tabB; ++b) st[b] = p.shape[b];
     }
     bool any_mix = false;
     for (int b = 0; b < tabB; ++b) {
@@ -684,12 +717,14 @@ int run_sampler(tld_engine* e, const SamplePlan& p, hipStream_t s) {
     const float* mix_dev = reinterpret_cast<const float*>(tab_dev + (size_t)n_max * tabB);
     const int* nr = reinterpret_cast<const int*>(mix_dev + tabB);
     const SamplerNoiseRow* noise_dev = noisy ? reinterpret_cast<const SamplerNoiseRow*>(static_cast<const char*>(e->req_dev) + noise_off) : nullptr;
+    const GuidanceShape* shape_dev = shaped ? reinterpret_cast<const GuidanceShape*>(static_cast<const char*>(e->req_dev) + shape_off) : nullptr;
 
     // ---- the start: pure noise at the schedule's first level (diffusion.py:52,59), else the forward process at the first remaining level (train.py:130)
     const size_t tot = (size_t)B * e->img;
     if (!any_mix) HIP_TRY(hipMemcpyAsync(e->xt, p.noise, tot * sizeof(float), hipMemcpyDeviceToDevice, s));
     else launch_start_mix(p.noise, p.init_latent, mix_dev, p.stride, e->xt, B, e->img, p.path_start, s);
     HIP_TRY(hipMemsetAsync(e->x0_prev, 0, tot * sizeof(float), s));
+    if (any_mom) HIP_TRY(hipMemsetAsync(e->shape_mom, 0, tot * sizeof(float), s));      // the momentum starts every call at zero
     // ---- the steps over the shrinking prefix of requests that still run
     for (int i = 0, Bi = B; i < n_max; nr += per * mbs[(size_t)i], ++i) {
         while (req(Bi - 1).n_levels <= i) --Bi;
@@ -709,6 +744,16 @@ int run_sampler(tld_engine* e, const SamplePlan& p, hipStream_t s) {
         up.rows = tab_dev + (size_t)i * tabB; up.row_stride = p.stride; up.sharp = p.sharp; up.bright = p.bright;
         up.active = Bi; up.img = e->img; up.chan_stride = e->cfg.image_size * e->cfg.image_size;
         if (noisy) { up.noise_rows = noise_dev + (size_t)i * tabB; up.noise_step = (uint32_t)i; }
+        // a step at which no running request is shaped and guided needs neither the statistics nor the SHAPE flavour: it would take `combine` for every
+        // request, which the NOISE flavour does with one table less to read
+        if (stats_step[(size_t)i]) {       // (P, Q) of the requests shaped at this step, before the step reads them
+            up.shape_rows = shape_dev; up.shape_pq = e->shape_pq; up.shape_mom = any_mom ? e->shape_mom : nullptr;
+            GuidanceStatsParams gp{};
+            gp.cond = e->io_out; gp.unc_base = e->io_out + (size_t)Bi * e->img; gp.mom = up.shape_mom; gp.rows = up.rows; gp.shape_rows = shape_dev;
+            gp.row_stride = p.stride; gp.active = Bi; gp.img = e->img; gp.pq = e->shape_pq; gp.sums = e->shape_sums;
+            ProfScope ps(e, KC_UPDATE, s);
+            launch_guidance_stats(gp, s);
+        }
         {
             ProfScope ps(e, KC_UPDATE, s);
             launch_sampler_step(up, p.path_step, s, guided);
@@ -1119,11 +1164,16 @@ constexpr int kMaxRequestCondRows = 1024;
 static int sample_requests(tld_engine* e, const void* noise, const void* init_latent, const void* mask, const void* labels, const void* neg_labels,
                            const tld_sample_request* requests, const float* coeffs, const float* guidance, bool guided, int32_t n_max, float sharp_f,
                            float bright_f, void* out_latent, int32_t batch, void* trace_x0, void* trace_xt, void* hip_stream,
-                           bool stochastic = false, const float* noise_coeff = nullptr, const uint64_t* noise_keys = nullptr) {
+                           bool stochastic = false, const float* noise_coeff = nullptr, const uint64_t* noise_keys = nullptr,
+                           const GuidanceShape* shape = nullptr) {
     // the records first: their checks need no engine and no device
     if (!requests || !coeffs || batch <= 0 || (guided && !guidance)) return fail(TLD_ERR_INVALID, "null argument");
     if (stochastic && !noise_coeff) return fail(TLD_ERR_INVALID, "null argument: noise_coeff");
     if (stochastic && !noise_keys) return fail(TLD_ERR_INVALID, "null argument: noise_keys");
+    for (int b = 0; shape && b < batch; ++b)
+        if (const char* bad = guidance_shape_invalid(shape[b]))
+            return fail(TLD_ERR_INVALID, "request %d: shape (%g, %g, %g, %g): bad %s", b, (double)shape[b].eta_par, (double)shape[b].norm_r,
+                        (double)shape[b].beta, (double)shape[b].phi, bad);
     if (mask && !init_latent) return fail(TLD_ERR_INVALID, "init_latent is required with a mask");
     const int B = batch;
     int n_neg = 0;
@@ -1199,7 +1249,7 @@ static int sample_requests(tld_engine* e, const void* noise, const void* init_la
     p.labels = static_cast<const float*>(labels); p.neg_labels = static_cast<const float*>(neg_labels); p.sharp = sharp_f; p.bright = bright_f;
     p.out_latent = static_cast<float*>(out_latent); p.trace_x0 = static_cast<float*>(trace_x0); p.trace_xt = static_cast<float*>(trace_xt);
     p.path_step = mask ? EP_UPDATE_REQ_MASK : EP_UPDATE_REQ; p.path_start = EP_START_MIX_REQ; p.keep_stages = false;
-    if (stochastic) { p.noise_coeff = noise_coeff; p.noise_keys = noise_keys; }
+    if (stochastic) { p.noise_coeff = noise_coeff; p.noise_keys = noise_keys; p.shape = shape; }
     return run_sampler(e, p, static_cast<hipStream_t>(hip_stream));
 }
 
@@ -1223,6 +1273,69 @@ int tld_sample_requests_stochastic(tld_engine* e, const void* noise, const void*
                                    void* trace_x0, void* trace_xt, void* hip_stream) {
     return sample_requests(e, noise, init_latent, mask, labels, neg_labels, requests, coeffs, guidance, guidance != nullptr, n_max, sharp_f, bright_f,
                            out_latent, batch, trace_x0, trace_xt, hip_stream, true, noise_coeff, noise_keys);
+}
+
+int tld_sample_requests_shaped(tld_engine* e, const void* noise, const void* init_latent, const void* mask, const void* labels, const void* neg_labels,
+                               const tld_sample_request* requests, const float* coeffs, const float* guidance, const float* noise_coeff,
+                               const uint64_t* noise_keys, const float* shape, int32_t n_max, float sharp_f, float bright_f, void* out_latent, int32_t batch,
+                               void* trace_x0, void* trace_xt, void* hip_stream) {
+    if (!shape) return fail(TLD_ERR_INVALID, "null argument: shape");
+    if ((noise_coeff == nullptr) != (noise_keys == nullptr)) return fail(TLD_ERR_INVALID, "noise_coeff and noise_keys come together (both NULL: no noise)");
+    if (batch <= 0 || n_max <= 0) return fail(TLD_ERR_INVALID, "need positive sizes (batch %d, n_max %d)", batch, n_max);
+    // without noise the step still runs the NOISE flavour (under the SHAPE flag where a request is shaped), on a table of zeros: nothing is drawn, nothing added
+    std::vector<float> no_coeff;
+    std::vector<uint64_t> no_keys;
+    if (!noise_coeff) {
+        no_coeff.assign((size_t)batch * n_max, 0.0f); no_keys.assign((size_t)batch, 0);
+        noise_coeff = no_coeff.data(); noise_keys = no_keys.data();
+    }
+    std::vector<GuidanceShape> rows((size_t)batch);
+    for (int b = 0; b < batch; ++b) rows[(size_t)b] = GuidanceShape{shape[4 * b], shape[4 * b + 1], shape[4 * b + 2], shape[4 * b + 3]};
+    return sample_requests(e, noise, init_latent, mask, labels, neg_labels, requests, coeffs, guidance, guidance != nullptr, n_max, sharp_f, bright_f,
+                           out_latent, batch, trace_x0, trace_xt, hip_stream, true, noise_coeff, noise_keys, rows.data());
+}
+
+int tld_debug_guidance_shape(const float* cond_device, const float* unc_device, float* mom_device, const float* g, const float* shape, int32_t batch,
+                             int32_t img, float* x0_device, float* pq_device, double* sums_device, void* hip_stream) {
+    if (!cond_device || !unc_device || !g || !shape || !x0_device || !pq_device || !sums_device) return fail(TLD_ERR_INVALID, "null argument");
+    if (batch <= 0 || img <= 0) return fail(TLD_ERR_INVALID, "need positive sizes (batch %d, img %d)", batch, img);
+    std::vector<SamplerStepRow> steps((size_t)batch);
+    std::vector<GuidanceShape> rows((size_t)batch);
+    for (int b = 0; b < batch; ++b) {
+        rows[(size_t)b] = GuidanceShape{shape[4 * b], shape[4 * b + 1], shape[4 * b + 2], shape[4 * b + 3]};
+        if (const char* bad = guidance_shape_invalid(rows[(size_t)b]))
+            return fail(TLD_ERR_INVALID, "entry %d: shape (%g, %g, %g, %g): bad %s", b, (double)shape[4 * b], (double)shape[4 * b + 1], (double)shape[4 * b + 2],
+                        (double)shape[4 * b + 3], bad);
+        if (!std::isfinite(g[b])) return fail(TLD_ERR_INVALID, "entry %d: guidance %g is not finite", b, (double)g[b]);
+        if (!mom_device && rows[(size_t)b].beta != 0.0f)
+            return fail(TLD_ERR_INVALID, "entry %d: beta = %g needs the momentum buffer", b, (double)rows[(size_t)b].beta);
+        steps[(size_t)b] = SamplerStepRow{};
+        steps[(size_t)b].g = g[b];
+        steps[(size_t)b].final_step = (b + 1) << 1;           // (entry b's unconditional operand is unc[b]: slot b, as the step kernel packs it)
+    }
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    const size_t step_bytes = (size_t)batch * sizeof(SamplerStepRow), shape_bytes = (size_t)batch * sizeof(GuidanceShape);
+    char* tab = nullptr;
+    HIP_TRY(hipMalloc(&tab, step_bytes + shape_bytes));
+    int rc = TLD_OK;
+    auto run = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(tab, steps.data(), step_bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(tab + step_bytes, rows.data(), shape_bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(pq_device, 0, (size_t)batch * sizeof(float2), s));
+        HIP_TRY(hipMemsetAsync(sums_device, 0, (size_t)batch * GS_SUMS * sizeof(double), s));
+        GuidanceStatsParams gp{};
+        gp.cond = cond_device; gp.unc_base = unc_device; gp.mom = mom_device; gp.rows = reinterpret_cast<const SamplerStepRow*>(tab);
+        gp.shape_rows = reinterpret_cast<const GuidanceShape*>(tab + step_bytes);
+        gp.row_stride = 1; gp.active = batch; gp.img = img; gp.pq = reinterpret_cast<float2*>(pq_device); gp.sums = sums_device;
+        launch_guidance_stats(gp, s);
+        launch_guidance_shape_debug(cond_device, unc_device, mom_device, gp.rows, gp.shape_rows, gp.pq, batch, img, x0_device, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(s));                      // (the tables are this call's own)
+        return TLD_OK;
+    };
+    rc = run();
+    hipFree(tab);
+    return rc;
 }
 
 int tld_debug_sampler_noise(const uint64_t* keys_device, const uint32_t* steps_device, int32_t batch, int32_t img, float* out_device, void* hip_stream) {

@@ -1147,6 +1147,103 @@ __device__ __forceinline__ void sampler_noise4(uint32_t key_lo, uint32_t key_hi,
     philox_normals4(sampler_noise_philox(((uint64_t)key_hi << 32) | key_lo, step, quad), n);
 }
 
+// The shaped guidance update (tld_guidance_shape.h), the two device functions behind guidance_stats_kernel, the SHAPE flavour of the
+// step kernel and tld_debug_guidance_shape: the update after the momentum, and the prediction under the request's weights
+__device__ __forceinline__ float guidance_dbar(float c, float u, float m, float beta) {
+#pragma clang fp contract(off)
+    const float d = c - u;
+    return beta != 0.0f ? d + beta * m : d;
+}
+__device__ __forceinline__ float guidance_shaped_x0(float P, float Q, float c, float dbar) {
+#pragma clang fp contract(off)
+    return __builtin_fmaf(P, c, Q * dbar);
+}
+
+// One workgroup of 256 threads per request still running: no atomics, no partial sums in memory, no second pass.  Thread t owns quads t, t + 256, ...
+// of the request's image, in that order, and within a quad its elements in order; it forms dbar as the step kernel will and adds to five double sums.
+// The workgroup's 256 partial sums meet in LDS in a fixed halving tree (128, 64, ..., 1), and thread 0 runs guidance_shape_finalize.  The order of
+// every addition depends on img alone: a request's sums, P and Q do not depend on the other requests or on where it stands in the call.  V = 4 reads a
+// quad as one 16-byte load per operand; V = 1 reads the same elements in the same order one by one (img no multiple of 4, or an operand not 16-byte
+// aligned) and gives the same bits.  Products of two fp32 values are exact in double, so only the additions round.
+template <int V>
+__global__ __launch_bounds__(256) void guidance_stats_kernel(GuidanceStatsParams p) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.x, t = threadIdx.x;
+    const GuidanceShape h = p.shape_rows[b * p.row_stride];
+    const SamplerStepRow q = p.rows[b * p.row_stride];
+    const int slot = (q.final_step >> 1) - 1;
+    // (the whole workgroup, before any barrier.  g == 1.0f: the forward is unguided -- x0 = cond and the momentum stays, whether or not the engine
+    // skipped its unconditional sample)
+    if (h.neutral() || slot < 0 || q.g == 1.0f) return;
+    const float* c = p.cond + (size_t)b * p.img;
+    const float* u = p.unc_base + (size_t)slot * p.img;
+    const bool mom = h.beta != 0.0f;
+    const float* m = mom ? p.mom + (size_t)b * p.img : nullptr;
+    double acc[GS_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    const int quads = (p.img + 3) >> 2;
+    for (int qd = t; qd < quads; qd += 256) {
+        const int e0 = 4 * qd;
+        float cv[4], uv[4], mv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        int cnt = 4;
+        if constexpr (V == 4) {
+            *reinterpret_cast<float4*>(cv) = *reinterpret_cast<const float4*>(c + e0);
+            *reinterpret_cast<float4*>(uv) = *reinterpret_cast<const float4*>(u + e0);
+            if (mom) *reinterpret_cast<float4*>(mv) = *reinterpret_cast<const float4*>(m + e0);
+        } else {
+            cnt = p.img - e0 < 4 ? p.img - e0 : 4;
+            for (int k = 0; k < cnt; ++k) {
+                cv[k] = c[e0 + k];
+                uv[k] = u[e0 + k];
+                if (mom) mv[k] = m[e0 + k];
+            }
+        }
+        for (int k = 0; k < cnt; ++k) {
+            const double cd = (double)cv[k], dd = (double)guidance_dbar(cv[k], uv[k], mv[k], h.beta);
+            acc[GS_SC] = acc[GS_SC] + cd;
+            acc[GS_SD] = acc[GS_SD] + dd;
+            acc[GS_SCC] = acc[GS_SCC] + cd * cd;
+            acc[GS_SDC] = acc[GS_SDC] + dd * cd;
+            acc[GS_SDD] = acc[GS_SDD] + dd * dd;
+        }
+    }
+    __shared__ double red[GS_SUMS][256];
+#pragma unroll
+    for (int j = 0; j < GS_SUMS; ++j) red[j][t] = acc[j];
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (t < w) {
+#pragma unroll
+            for (int j = 0; j < GS_SUMS; ++j) red[j][t] = red[j][t] + red[j][t + w];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        double sums[GS_SUMS];
+#pragma unroll
+        for (int j = 0; j < GS_SUMS; ++j) { sums[j] = red[j][0]; p.sums[(size_t)b * GS_SUMS + j] = sums[j]; }
+        const GuidanceWeights w = guidance_shape_finalize(sums, p.img, q.g, h);
+        p.pq[b] = make_float2(w.P, w.Q);
+    }
+}
+
+// tld_debug_guidance_shape: element by element what the SHAPE flavour of the step kernel computes for x0 and stores to the momentum buffer
+__global__ __launch_bounds__(256) void guidance_shape_debug_kernel(const float* __restrict__ cond, const float* __restrict__ unc, float* __restrict__ mom,
+                                                                   const SamplerStepRow* __restrict__ rows, const GuidanceShape* __restrict__ shape_rows,
+                                                                   const float2* __restrict__ pq, int batch, int img, float* __restrict__ x0) {
+#pragma clang fp contract(off)
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)batch * img) return;
+    const int b = (int)(i / img);
+    const GuidanceShape h = shape_rows[b];
+    const float c = cond[i], u = unc[i];
+    if (h.neutral() || rows[b].g == 1.0f) { x0[i] = __builtin_fmaf(rows[b].g, c, (1.0f - rows[b].g) * u); return; }
+    const bool keep = h.beta != 0.0f && mom != nullptr;
+    const float db = guidance_dbar(c, u, keep ? mom[i] : 0.0f, keep ? h.beta : 0.0f);
+    const float2 w = pq[b];
+    x0[i] = guidance_shaped_x0(w.x, w.y, c, db);
+    if (keep) mom[i] = db;
+}
+
 // ------------------------------------------------------------------------------------------------
 // The sampler's elementwise step, one launch per step for all three sampler entries: CFG combine, DPM-Solver++(2M)/DDIM update,
 // latent shifts, and with MASK the inpainting blend.  Sample b takes {g, a, b, c, c1, c2, s_next, final} from rows[b * row_stride]: a row per
@@ -1165,7 +1262,10 @@ __device__ __forceinline__ void sampler_noise4(uint32_t key_lo, uint32_t key_hi,
 // NOISE (tld_sample_requests_stochastic): after the update and before the blend, x_t <- x_t + e z with the product rounded, then the sum;
 // e and the key come from noise_rows[b * row_stride], z from the counter (quad of the element inside the request's own image, noise_step) under that key
 // (sampler_noise4).  A row with e == 0.0f draws nothing and adds nothing: the arithmetic above exactly.  The final step returns before it.
-template <bool MASK, int V, bool SLOT = false, bool NOISE = false>
+// SHAPE (tld_sample_requests_shaped), on top of SLOT and NOISE: a request whose shape row is not neutral and which has an unconditional
+// slot at this step and a guidance other than 1.0f takes x0 = fma(P, cond, Q dbar), dbar = cond - unc (+ beta m), with (P, Q) from this step's guidance_stats_kernel launch, and where
+// beta != 0 an inner step stores m <- dbar.  Every other request takes `combine` as it stands and touches neither table nor buffer.
+template <bool MASK, int V, bool SLOT = false, bool NOISE = false, bool SHAPE = false>
 __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p) {
 #pragma clang fp contract(off)
     const int i = (blockIdx.x * 256 + threadIdx.x) * V;
@@ -1195,6 +1295,27 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p) 
         if constexpr (SLOT) { if (slot < 0) return c; }
         return __builtin_fmaf(q.g, c, (1.0f - q.g) * u);
     };
+    bool shaped = false;
+    float sP = 0.0f, sQ = 0.0f, sbeta = 0.0f, mom[V], dbo[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) mom[v] = 0.0f;
+    if constexpr (SHAPE) {
+        const GuidanceShape h = p.shape_rows[b * p.row_stride];
+        if (slot >= 0 && !h.neutral() && q.g != 1.0f) {
+            const float2 w = p.shape_pq[b];
+            shaped = true; sP = w.x; sQ = w.y; sbeta = h.beta;
+            if (sbeta != 0.0f) load(mom, p.shape_mom + i);
+        }
+    }
+    auto predict = [&](int v) {
+        if constexpr (SHAPE) {
+            if (shaped) {
+                dbo[v] = guidance_dbar(cond[v], unc[v], mom[v], sbeta);
+                return guidance_shaped_x0(sP, sQ, cond[v], dbo[v]);
+            }
+        }
+        return combine(cond[v], unc[v]);
+    };
     if constexpr (MASK) {
         load(m, p.mask + (size_t)b * p.chan_stride + (r - ch * p.chan_stride));
         load(z, p.z0 + i);
@@ -1202,7 +1323,7 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p) 
     if (final_step) {
 #pragma unroll
         for (int v = 0; v < V; ++v) {
-            float x0 = combine(cond[v], unc[v]);
+            float x0 = predict(v);
             if constexpr (MASK) x0 = m[v] * x0 + (1.0f - m[v]) * z[v];
             if (ch == 3) x0 += p.sharp;                                   // diffusion.py:88
             if (ch == 0) x0 += p.bright;                                  // diffusion.py:89
@@ -1232,7 +1353,7 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p) 
     }
 #pragma unroll
     for (int v = 0; v < V; ++v) {
-        const float x0 = combine(cond[v], unc[v]);
+        const float x0 = predict(v);
         const float D = __builtin_fmaf(q.c1, x0, -(q.c2 * prev[v]));      // diffusion.py:76 (c1=1,c2=0: :72/:79)
         float xt = (q.a * D + q.b * xin[v]) / q.c;                        // diffusion.py:81
         if constexpr (NOISE) { if (en != 0.0f) xt = xt + en * nz[v]; }
@@ -1247,6 +1368,7 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p) 
     store(p.x_t + i, xto);
     store(p.x0_prev + i, x0o);
     if (p.trace_xt) store(p.trace_xt + i, xto);
+    if constexpr (SHAPE) { if (shaped && sbeta != 0.0f) store(p.shape_mom + i, dbo); }
 }
 
 // x_start = s0 eps + (1 - s0) z0: the forward process at the first remaining level (tld/train.py:130), s0 read per sample from s0v[sample * s0_stride];
@@ -1706,11 +1828,19 @@ void launch_sampler_step(const SamplerStepParams& p, int path, hipStream_t s, bo
     const int n = p.active * p.img;
     // 16-byte accesses: four consecutive elements then share a sample, a channel and one aligned mask quad (null pointers count as aligned)
     const bool vec = p.img % 4 == 0 && p.chan_stride % 4 == 0 && aligned16(p.x0_2b) && aligned16(p.x_t) && aligned16(p.x0_prev) && aligned16(p.out_latent) &&
-                     aligned16(p.trace_x0) && aligned16(p.trace_xt) && aligned16(p.noise) && aligned16(p.z0) && aligned16(p.mask);
+                     aligned16(p.trace_x0) && aligned16(p.trace_xt) && aligned16(p.noise) && aligned16(p.z0) && aligned16(p.mask) && aligned16(p.shape_mom);
     const int threads = vec ? n / 4 : n;
     const dim3 grid((threads + 255) / 256), block(256);
     note_path(path);
-    if (slots && p.noise_rows) {
+    if (slots && p.noise_rows && p.shape_rows) {
+        if (p.mask) {
+            if (vec) hipLaunchKernelGGL((sampler_step_kernel<true, 4, true, true, true>), grid, block, 0, s, p);
+            else hipLaunchKernelGGL((sampler_step_kernel<true, 1, true, true, true>), grid, block, 0, s, p);
+        } else {
+            if (vec) hipLaunchKernelGGL((sampler_step_kernel<false, 4, true, true, true>), grid, block, 0, s, p);
+            else hipLaunchKernelGGL((sampler_step_kernel<false, 1, true, true, true>), grid, block, 0, s, p);
+        }
+    } else if (slots && p.noise_rows) {
         if (p.mask) {
             if (vec) hipLaunchKernelGGL((sampler_step_kernel<true, 4, true, true>), grid, block, 0, s, p);
             else hipLaunchKernelGGL((sampler_step_kernel<true, 1, true, true>), grid, block, 0, s, p);
@@ -1733,6 +1863,18 @@ void launch_sampler_step(const SamplerStepParams& p, int path, hipStream_t s, bo
         if (vec) hipLaunchKernelGGL((sampler_step_kernel<false, 4>), grid, block, 0, s, p);
         else hipLaunchKernelGGL((sampler_step_kernel<false, 1>), grid, block, 0, s, p);
     }
+}
+
+void launch_guidance_stats(const GuidanceStatsParams& p, hipStream_t s) {
+    const bool vec = p.img % 4 == 0 && aligned16(p.cond) && aligned16(p.unc_base) && aligned16(p.mom);
+    if (vec) hipLaunchKernelGGL((guidance_stats_kernel<4>), dim3((unsigned)p.active), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((guidance_stats_kernel<1>), dim3((unsigned)p.active), dim3(256), 0, s, p);
+}
+
+void launch_guidance_shape_debug(const float* cond, const float* unc, float* mom, const SamplerStepRow* rows, const GuidanceShape* shape_rows,
+                                 const float2* pq, int batch, int img, float* x0, hipStream_t s) {
+    const int64_t n = (int64_t)batch * img;
+    hipLaunchKernelGGL(guidance_shape_debug_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, cond, unc, mom, rows, shape_rows, pq, batch, img, x0);
 }
 
 void launch_sampler_noise_debug(const uint64_t* keys, const uint32_t* steps, int batch, int img, float* z, hipStream_t s) {

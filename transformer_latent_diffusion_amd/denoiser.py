@@ -375,7 +375,7 @@ class Denoiser:
     @torch.no_grad()
     def sample_latents_requests(self, noise: torch.Tensor, labels: torch.Tensor, coeff_list, guidance, *, neg_labels=None, init_latents=None,
                                 start_mix=None, mask=None, sharp_f: float = 0.0, bright_f: float = 0.0, trace: bool = False, guidance_steps=None,
-                                noise_coeffs=None, noise_keys=None):
+                                noise_coeffs=None, noise_keys=None, shape=None):
         """B independent requests in one on-device sampler call (tld_sample_requests).
 
         ``noise`` [B,C,S,S], ``labels`` [B,text]; ``coeff_list``: B tables ``schedule.step_coefficients(...)`` (each request's own levels
@@ -393,6 +393,10 @@ class Denoiser:
         (``schedule.noise_key``).  After an inner step's update the kernel adds ``e z``, z the normals of (key, forward, element): request b's
         result is bit for bit that of the request alone with the same key, and all-zero arrays give the call without them.  With
         ``guidance_steps`` the model batches are the guided call's; without, the CFG-doubled ones.
+        ``shape``: B rows ``(eta_par, norm_r, beta, phi)`` (``schedule.check_guidance_shape``); the call is then tld_sample_requests_shaped
+        (DESIGN.md section 7.16), with or without any of the above: guidance rescale and adaptive projected guidance on the requests whose row is
+        not ``schedule.GUIDANCE_SHAPE_NEUTRAL``.  A neutral row is the request without ``shape``, bit for bit, and request b still equals the
+        request alone.
         Its own here: the records' checks, the engine's order, the row cap and the negative labels as one tensor; the rest is ``_run_sampler``."""
         from . import schedule
         B = noise.shape[0]
@@ -443,6 +447,15 @@ class Denoiser:
                     raise ValueError(f"noise_coeffs[{b}][-1] = {t[-1]}: the final prediction takes no noise, expected 0")
                 if not 0 <= keys[b] < 1 << 64:
                     raise ValueError(f"noise_keys[{b}] = {keys[b]}: expected a 64-bit unsigned value")
+        shp = None
+        if shape is not None:
+            rows = [tuple(r) for r in shape]
+            if len(rows) != B:
+                raise ValueError(f"shape: {len(rows)} entries for {B} requests")
+            for b, r in enumerate(rows):
+                if len(r) != 4:
+                    raise ValueError(f"shape[{b}] has {len(r)} values: expected (eta_par, norm_r, beta, phi)")
+            shp = [schedule.check_guidance_shape(r[3], r[0], r[1], r[2]) for r in rows]
         neg, has_neg = None, [False] * B
         if neg_labels is not None:
             if isinstance(neg_labels, torch.Tensor):
@@ -487,12 +500,21 @@ class Denoiser:
         fp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
         # traces start as zeros: the engine leaves a finished request's slots alone
         common = dict(init_latents=init_latents, mask=mask, neg_labels=neg, order=order, new_trace=torch.zeros)
-        if ecs is not None:              # (guidance NULL: the records' scales on the CFG-doubled batch)
+        etab = ktab = None
+        if ecs is not None:
             etab = np.zeros((B, n_max), dtype=np.float32)
             ktab = np.zeros(B, dtype=np.uint64)
             for k, b in enumerate(order):
                 etab[k, :counts[b]] = ecs[b]
                 ktab[k] = keys[b]
+        if shp is not None:              # (noise_coeff / noise_keys NULL: no noise; guidance NULL: as in the stochastic entry)
+            stab = np.ascontiguousarray([shp[b] for b in order], dtype=np.float32).reshape(B, 4)
+            kp = None if ktab is None else ktab.ctypes.data_as(C.POINTER(C.c_uint64))
+            return self._run_sampler(noise, labels, n_max, trace, lambda h, B, eps, z0, m, lab, ng, out, tx0, txt, stream: _lib.check(
+                _lib.lib().tld_sample_requests_shaped(h, eps, z0, m, lab, ng, recs, fp(table), fp(gtab), fp(etab), kp, fp(stab), n_max, float(sharp_f),
+                                                      float(bright_f), out, B, tx0, txt, stream), "tld_sample_requests_shaped"),
+                model_batch=model_batch, **common)
+        if ecs is not None:              # (guidance NULL: the records' scales on the CFG-doubled batch)
             return self._run_sampler(noise, labels, n_max, trace, lambda h, B, eps, z0, m, lab, ng, out, tx0, txt, stream: _lib.check(
                 _lib.lib().tld_sample_requests_stochastic(h, eps, z0, m, lab, ng, recs, fp(table), fp(gtab), fp(etab),
                                                           ktab.ctypes.data_as(C.POINTER(C.c_uint64)), n_max, float(sharp_f), float(bright_f), out, B,

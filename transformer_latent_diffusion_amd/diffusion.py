@@ -101,15 +101,19 @@ class DiffusionGenerator:
         guidance_interval=None,
         eta: float = 0.0,
         noise_seeds=None,
+        guidance_rescale: float = 0.0,
+        apg_eta: float = 1.0,
+        apg_norm: float = 0.0,
+        apg_momentum: float = 0.0,
     ):
         """Reverse diffusion with classifier-free guidance; returns (decoded_images_on_cpu, latents).
 
         ``use_ddpm_plus=True``: DPM-Solver++(2M); else DDIM with alpha = 1 - sigma (diffusion.py:45-48).
-        ``guidance_interval``, ``eta``, ``noise_seeds`` (not in the reference): see ``generate_latents``.
+        ``guidance_interval``, ``eta``, ``noise_seeds``, ``guidance_rescale`` and ``apg_*`` (not in the reference): see ``generate_latents``.
         """
         return self._decode(self.generate_latents(labels, n_iter, num_imgs, class_guidance, seed, img_size, sharp_f, bright_f, exponent,
                                                   seeds, noise_levels, use_ddpm_plus, guidance_interval=guidance_interval, eta=eta,
-                                                  noise_seeds=noise_seeds), scale_factor)
+                                                  noise_seeds=noise_seeds, guidance_rescale=guidance_rescale, apg_eta=apg_eta, apg_norm=apg_norm, apg_momentum=apg_momentum), scale_factor)
 
     def _decode(self, latents, scale_factor):
         """The exit edge of the three ``generate*`` (diffusion.py:91): (decoded_images_on_cpu, latents); (None, latents) without a VAE."""
@@ -170,25 +174,34 @@ class DiffusionGenerator:
     @torch.no_grad()
     def generate_latents(self, labels, n_iter=30, num_imgs=16, class_guidance=3, seed=10, img_size=32,
                          sharp_f=0.1, bright_f=0.1, exponent=1, seeds=None, noise_levels=None,
-                         use_ddpm_plus=True, trace=False, guidance_interval=None, eta=0.0, noise_seeds=None):
+                         use_ddpm_plus=True, trace=False, guidance_interval=None, eta=0.0, noise_seeds=None, guidance_rescale=0.0, apg_eta=1.0, apg_norm=0.0, apg_momentum=0.0):
         """``guidance_interval = (lo, hi)``: limited-interval guidance -- ``class_guidance`` only at the forwards whose noise level lies in
         [lo, hi], the plain conditional prediction elsewhere, where no unconditional sample is run.  The call is then
         ``generate_latents_requests`` with B equal requests; None keeps the path of the reference's sampler untouched.
         ``eta > 0``: the stochastic sampler -- SDE DPM-Solver++(2M), or with ``use_ddpm_plus=False`` DDIM with that eta
         (1: the first-order SDE solver) -- through ``generate_latents_requests`` too; the noise of image b comes from the key
-        ``schedule.noise_key(seed, b)``, or ``noise_seeds[b]`` (required when ``seeds`` is a tensor).  0 is the deterministic path, untouched."""
+        ``schedule.noise_key(seed, b)``, or ``noise_seeds[b]`` (required when ``seeds`` is a tensor).  0 is the deterministic path, untouched.
+        ``guidance_rescale`` (phi in [0, 1]; Lin et al. 2023) and ``apg_eta`` / ``apg_norm`` / ``apg_momentum`` (adaptive projected guidance, Sadat
+        et al. 2024: the weight of the update's part parallel to the conditional prediction, the norm the update is clipped to, the momentum over
+        the updates) shape the guidance update on the device (``schedule.check_guidance_shape``).  The statistics run over
+        each image's whole latent, a masked-out known region included.  Any value other than the defaults takes ``generate_latents_requests``
+        too; the defaults are plain CFG on the old path, untouched."""
         eta = schedule.check_eta(eta)
+        shape = dict(zip(("apg_eta", "apg_norm", "apg_momentum", "guidance_rescale"),
+                         schedule.check_guidance_shape(guidance_rescale, apg_eta, apg_norm, apg_momentum)))
+        if schedule.guidance_shape_neutral(shape.values()):
+            shape = {}
         keys = self._noise_keys(seeds, noise_seeds, num_imgs if seeds is None else len(seeds), seed) if eta > 0.0 else None
         coeffs, _ = self._trajectory(n_iter, exponent, noise_levels, None, use_ddpm_plus)
         x_t = self.initialize_image(seeds, num_imgs, img_size, seed)
         if labels.size(0) != x_t.size(0):
             # the reference zips labels and noise by torch.cat (diffusion.py:61,98)
             raise RuntimeError(f"labels batch {labels.size(0)} != num_imgs {x_t.size(0)}")
-        if guidance_interval is not None or keys is not None:
+        if guidance_interval is not None or keys is not None or shape:
             sde = {} if keys is None else dict(eta=eta, noise_seeds=keys)
             return self.generate_latents_requests(labels, n_iter=n_iter, class_guidance=class_guidance, seeds=x_t, img_size=img_size, sharp_f=sharp_f,
                                                   bright_f=bright_f, exponent=exponent, noise_levels=noise_levels, use_ddpm_plus=use_ddpm_plus,
-                                                  trace=trace, guidance_interval=guidance_interval, **sde)
+                                                  trace=trace, guidance_interval=guidance_interval, **sde, **shape)
         self.model.eval()
         return self._in_model_dtype(self.model.sample_latents(x_t, labels.to(self.device), coeffs, class_guidance, sharp_f, bright_f,
                                                               trace=trace), trace)
@@ -197,16 +210,17 @@ class DiffusionGenerator:
     def generate_from(self, init_latents: Tensor, labels: Tensor, strength: float = 0.6, mask: Optional[Tensor] = None, n_iter: int = 30,
                       num_imgs: Optional[int] = None, class_guidance: float = 3, seed: int = 10, scale_factor: int = 8,
                       img_size: Optional[int] = None, sharp_f: float = 0.1, bright_f: float = 0.1, exponent: float = 1,
-                      seeds: Optional[Tensor] = None, noise_levels=None, use_ddpm_plus: bool = True, eta: float = 0.0, noise_seeds=None):
+                      seeds: Optional[Tensor] = None, noise_levels=None, use_ddpm_plus: bool = True, eta: float = 0.0, noise_seeds=None,
+                      guidance_rescale: float = 0.0, apg_eta: float = 1.0, apg_norm: float = 0.0, apg_momentum: float = 0.0):
         """``generate`` for image-to-image and inpainting (``generate_latents_from``); returns (decoded_images_on_cpu, latents)."""
         return self._decode(self.generate_latents_from(init_latents, labels, strength, mask, n_iter, num_imgs, class_guidance, seed, img_size,
                                                        sharp_f, bright_f, exponent, seeds, noise_levels, use_ddpm_plus, eta=eta,
-                                                       noise_seeds=noise_seeds), scale_factor)
+                                                       noise_seeds=noise_seeds, guidance_rescale=guidance_rescale, apg_eta=apg_eta, apg_norm=apg_norm, apg_momentum=apg_momentum), scale_factor)
 
     @torch.no_grad()
     def generate_latents_from(self, init_latents, labels, strength=0.6, mask=None, n_iter=30, num_imgs=None, class_guidance=3, seed=10,
                               img_size=None, sharp_f=0.1, bright_f=0.1, exponent=1, seeds=None, noise_levels=None, use_ddpm_plus=True,
-                              trace=False, guidance_interval=None, eta=0.0, noise_seeds=None):
+                              trace=False, guidance_interval=None, eta=0.0, noise_seeds=None, guidance_rescale=0.0, apg_eta=1.0, apg_norm=0.0, apg_momentum=0.0):
         """Reverse diffusion that starts from ``init_latents`` [B,C,S,S] (model space: VAE latent / scale_factor, tld/train.py:122)
         instead of pure noise; the other arguments are ``generate_latents``' (``num_imgs`` / ``img_size`` default to the latents' own).
 
@@ -217,8 +231,13 @@ class DiffusionGenerator:
         forward process of ``init_latents`` at that step's level, and to ``init_latents`` itself in the final prediction (exactly, where
         the mask is 0).  Shapes and ranges are checked on the host before anything is enqueued.  ``guidance_interval = (lo, hi)``: as in
         ``generate_latents``, through ``generate_latents_requests`` with B equal requests; so are ``eta`` and ``noise_seeds`` (with a mask the
-        noise is added before the blend: the kept region still rides the forward process of the start noise)."""
+        noise is added before the blend: the kept region still rides the forward process of the start noise), and ``guidance_rescale`` and the
+        ``apg_*`` controls (their statistics run over the whole latent, the kept region included)."""
         eta = schedule.check_eta(eta)
+        shape = dict(zip(("apg_eta", "apg_norm", "apg_momentum", "guidance_rescale"),
+                         schedule.check_guidance_shape(guidance_rescale, apg_eta, apg_norm, apg_momentum)))
+        if schedule.guidance_shape_neutral(shape.values()):
+            shape = {}
         if init_latents.dim() != 4:
             raise ValueError(f"init_latents {tuple(init_latents.shape)}: expected [B,C,S,S]")
         B, S = init_latents.shape[0], init_latents.shape[-1]
@@ -236,12 +255,12 @@ class DiffusionGenerator:
         coeffs, start_mix = self._trajectory(n_iter, exponent, noise_levels, strength, use_ddpm_plus)
         keys = self._noise_keys(seeds, noise_seeds, B, seed) if eta > 0.0 else None
         eps = self.initialize_image(seeds, num_imgs, img_size, seed)
-        if guidance_interval is not None or keys is not None:
+        if guidance_interval is not None or keys is not None or shape:
             sde = {} if keys is None else dict(eta=eta, noise_seeds=keys)
             return self.generate_latents_requests(labels, n_iter=n_iter, class_guidance=class_guidance, seeds=eps, img_size=img_size, sharp_f=sharp_f,
                                                   bright_f=bright_f, exponent=exponent, noise_levels=noise_levels, use_ddpm_plus=use_ddpm_plus,
                                                   init_latents=init_latents, strength=strength, mask=mask, trace=trace,
-                                                  guidance_interval=guidance_interval, **sde)
+                                                  guidance_interval=guidance_interval, **sde, **shape)
         self.model.eval()
         return self._in_model_dtype(self.model.sample_latents_from(
             eps, init_latents.to(self.device), labels.to(self.device), coeffs, class_guidance, start_mix,
@@ -251,7 +270,7 @@ class DiffusionGenerator:
     def generate_latents_requests(self, labels, *, n_iter=30, class_guidance=3, negative_labels=None, seed=10, seeds=None, img_size=None,
                                   sharp_f=0.1, bright_f=0.1, exponent=1, noise_levels=None, use_ddpm_plus=True, init_latents=None,
                                   strength=None, mask=None, trace=False, guidance_interval=None, guidance_schedule=None, eta=0.0,
-                                  noise_seeds=None):
+                                  noise_seeds=None, guidance_rescale=0.0, apg_eta=1.0, apg_norm=0.0, apg_momentum=0.0):
         """B independent requests in ONE sampler call (``Denoiser.sample_latents_requests``): each of ``n_iter``,
         ``class_guidance``, ``exponent``, ``strength`` and ``use_ddpm_plus`` is a scalar (for all) or a length-B sequence.  Request b's latent
         is bit for bit what ``generate_latents`` / ``generate_latents_from`` return for that request alone with the same noise.
@@ -272,6 +291,9 @@ class DiffusionGenerator:
         own eta, and its noise comes from the key ``noise_seeds[b]`` -- by default ``schedule.noise_key`` of the seed that drew its start noise
         (``(seed, b)``, or ``(seeds[b], 0)`` with one int seed per request; ``seeds`` as a tensor needs ``noise_seeds``).  Request b still equals
         the request alone with the same noise and key, bit for bit.
+        ``guidance_rescale``, ``apg_eta``, ``apg_norm``, ``apg_momentum``: each a scalar or one value per request (``generate_latents``;
+        DESIGN.md section 7.16).  With any value other than the defaults the call is ``sample_latents_requests(..., shape=...)``; a request at
+        the defaults runs plain CFG inside it, and request b still equals the request alone, bit for bit.
         Shapes and ranges are checked on the host before anything is enqueued."""
         B = labels.size(0)
         size = self.model.image_size if img_size is None else img_size
@@ -288,6 +310,7 @@ class DiffusionGenerator:
         expo, plus, stren = per_request(exponent, "exponent"), per_request(use_ddpm_plus, "use_ddpm_plus"), per_request(strength, "strength")
         etas = [schedule.check_eta(v) for v in per_request(eta, "eta")]
         keys = self._noise_keys(seeds, noise_seeds, B, seed) if any(v > 0.0 for v in etas) else None
+        shape_rows = schedule.guidance_shape_rows(B, guidance_rescale, apg_eta, apg_norm, apg_momentum)
         for b in range(B):
             if not np.isfinite(float(guid[b])):
                 raise ValueError(f"class_guidance[{b}] = {guid[b]} is not finite")
@@ -332,6 +355,8 @@ class DiffusionGenerator:
         kw = {} if steps is None else dict(guidance_steps=steps)
         if keys is not None:
             kw.update(noise_coeffs=ecs, noise_keys=keys)
+        if shape_rows is not None:
+            kw.update(shape=shape_rows)
         return self._in_model_dtype(self.model.sample_latents_requests(
             eps, labels.to(self.device), coeffs, [float(g) for g in guid], neg_labels=negative_labels, init_latents=z0, start_mix=mix,
             mask=m, sharp_f=sharp_f, bright_f=bright_f, trace=trace, **kw), trace)
@@ -512,7 +537,8 @@ class DiffusionTransformer:
         return emb
 
     @torch.no_grad()
-    def generate_images_from_texts(self, prompts, class_guidance=6, seeds=11, n_iter=15, negative_prompts=None, guidance_interval=None, eta=0.0):
+    def generate_images_from_texts(self, prompts, class_guidance=6, seeds=11, n_iter=15, negative_prompts=None, guidance_interval=None, eta=0.0,
+                                   guidance_rescale=0.0, apg_eta=1.0, apg_norm=0.0, apg_momentum=0.0):
         """Batched front edge (the reference serves one prompt per call, tld/app.py:48-65):
         one text-encoder call for all prompts, labels stay on the device, ONE sampler call (sample-sharded over the
         ranks of the default process group when torch.distributed is initialised), one VAE decode; returns one PIL image
@@ -525,7 +551,9 @@ class DiffusionTransformer:
         ``guidance_interval``: ``(lo, hi)`` for all prompts or one pair / None per prompt -- limited-interval guidance
         (``generate_latents_requests``); the call is then the requests one.
         ``eta``: one value or one per prompt; any ``eta > 0`` makes it the requests call with the stochastic sampler.
-        Request i's noise key is ``schedule.noise_key(seeds[i])``, that of the one-prompt call with its seed, so the pictures still agree."""
+        Request i's noise key is ``schedule.noise_key(seeds[i])``, that of the one-prompt call with its seed, so the pictures still agree.
+        ``guidance_rescale``, ``apg_eta``, ``apg_norm``, ``apg_momentum``: one value or one per prompt (``DiffusionGenerator.generate_latents``,
+        DESIGN.md section 7.16); any value other than the defaults makes it the requests call."""
         from .sharded import sharded_sample
         prompts = list(prompts)
         n = len(prompts)
@@ -539,8 +567,9 @@ class DiffusionTransformer:
         if len(etas) != n:
             raise ValueError(f"{len(etas)} eta values for {n} prompts")
         noisy = any(v > 0.0 for v in etas)
+        shape_rows = schedule.guidance_shape_rows(n, guidance_rescale, apg_eta, apg_norm, apg_momentum)     # (eta_par, norm_r, beta, phi) per prompt, or None
         if (isinstance(class_guidance, numbers.Number) and isinstance(n_iter, numbers.Number) and negative_prompts is None and guidance_interval is None
-                and not noisy):
+                and not noisy and shape_rows is None):
             labels, extras = self._labels(prompts).to(self.device, torch.float32), ()
 
             def one(xs, ls):
@@ -563,6 +592,9 @@ class DiffusionTransformer:
                 kw = {} if ivs is None else dict(guidance_interval=[ivs[i] for i in w])
                 if noisy:
                     kw.update(eta=[etas[i] for i in w], noise_seeds=[schedule.noise_key(seed_list[i]) for i in w])
+                if shape_rows is not None:
+                    kw.update(apg_eta=[shape_rows[i][0] for i in w], apg_norm=[shape_rows[i][1] for i in w],
+                              apg_momentum=[shape_rows[i][2] for i in w], guidance_rescale=[shape_rows[i][3] for i in w])
                 return gen.generate_latents_requests(ls, n_iter=[n_it[i] for i in w], class_guidance=[guid[i] for i in w],
                                                      negative_labels=None if neg_rows is None else [neg_rows[i] for i in w], seeds=xs, img_size=size,
                                                      sharp_f=0, bright_f=0, exponent=1, **kw)
@@ -592,11 +624,14 @@ class DiffusionTransformer:
         return emb[:n], rows
 
     def generate_image_from_text(self, prompt: str, class_guidance=6, seed=11, num_imgs=1, img_size=32, n_iter=15, *, negative_prompt=None,
-                                 guidance_interval=None, eta=0.0):
+                                 guidance_interval=None, eta=0.0, guidance_rescale=0.0, apg_eta=1.0, apg_norm=0.0, apg_momentum=0.0):
         nrow = int(np.sqrt(num_imgs))
         giv = {} if guidance_interval is None else dict(guidance_interval=guidance_interval)      # limited-interval guidance
         if schedule.check_eta(eta) > 0.0:     # the stochastic sampler: image b's noise key is schedule.noise_key(seed, b)
             giv["eta"] = eta
+        row = schedule.check_guidance_shape(guidance_rescale, apg_eta, apg_norm, apg_momentum)
+        if not schedule.guidance_shape_neutral(row):      # guidance rescale / APG
+            giv.update(apg_eta=row[0], apg_norm=row[1], apg_momentum=row[2], guidance_rescale=row[3])
         if negative_prompt is not None:       # the unconditional half of the guidance pair reads the negative prompt's label instead of zeros
             labels, neg = self._encode_with_negatives([prompt] * num_imgs, [negative_prompt] + [None] * (num_imgs - 1))
             out, _ = self.diffuser.generate_requests(labels, negative_labels=[neg[0]] * num_imgs, n_iter=n_iter, class_guidance=class_guidance,
@@ -614,7 +649,8 @@ class DiffusionTransformer:
 
     @torch.no_grad()
     def generate_image_from_image(self, image, prompt: str, strength=0.6, mask=None, class_guidance=6, seed=11, n_iter=15,
-                                  sample_posterior=False, return_latents=False, *, negative_prompt=None, guidance_interval=None, eta=0.0):
+                                  sample_posterior=False, return_latents=False, *, negative_prompt=None, guidance_interval=None, eta=0.0,
+                                  guidance_rescale=0.0, apg_eta=1.0, apg_norm=0.0, apg_momentum=0.0):
         """Image -> image: edit ``image`` towards ``prompt`` at ``strength``, or with ``mask`` regenerate only the masked region.
 
         ``image``: a PIL image or a [3,H,W] tensor in [0,1] with H = W = 8 x the model's latent size (no resizing here).  It is encoded
@@ -623,8 +659,9 @@ class DiffusionTransformer:
         resolution, 1 = regenerate; it is area-averaged to the latent grid (``latent_mask``), so only latent cells whose 8 x 8 pixels are
         all 0 are kept exactly.  Sampler settings as in ``generate_image_from_text``; with ``negative_prompt`` the unconditional half of
         the guidance pair reads that prompt's label (``generate_requests``); ``guidance_interval = (lo, hi)`` guides only at the noise levels
-        inside it (the same entry); ``eta > 0`` takes the stochastic sampler (the same entry; noise key ``schedule.noise_key(seed)``).  Returns a PIL
-        image (with ``return_latents``: (image, latents))."""
+        inside it (the same entry); ``eta > 0`` takes the stochastic sampler (the same entry; noise key ``schedule.noise_key(seed)``);
+        so do ``guidance_rescale`` and the ``apg_*`` controls (their statistics run over the whole latent, the kept region of
+        a mask included).  Returns a PIL image (with ``return_latents``: (image, latents))."""
         gen = self.diffuser
         size = gen.model.image_size
         if not isinstance(image, Tensor):
@@ -654,10 +691,14 @@ class DiffusionTransformer:
         else:
             z = dist_.mode()
         z0 = z.to(torch.float32) / 8
-        if neg is not None or guidance_interval is not None or schedule.check_eta(eta) > 0.0:
+        row = schedule.check_guidance_shape(guidance_rescale, apg_eta, apg_norm, apg_momentum)
+        shaped = not schedule.guidance_shape_neutral(row)
+        if neg is not None or guidance_interval is not None or schedule.check_eta(eta) > 0.0 or shaped:
             giv = {} if guidance_interval is None else dict(guidance_interval=guidance_interval)
             if eta > 0.0:
                 giv["eta"] = eta
+            if shaped:
+                giv.update(apg_eta=row[0], apg_norm=row[1], apg_momentum=row[2], guidance_rescale=row[3])
             out, latents = gen.generate_requests(labels, negative_labels=neg, init_latents=z0, strength=strength, mask=m, n_iter=n_iter,
                                                  class_guidance=class_guidance, seed=seed, exponent=1, scale_factor=8, sharp_f=0, bright_f=0, **giv)
         else:
@@ -697,11 +738,14 @@ class RequestBatcher:
         self._queue = []
         self._intervals = {}               # ticket -> (lo, hi) of the requests that brought a guidance interval
         self._etas = {}                    # ticket -> eta of the requests that asked for the stochastic sampler
+        self._shapes = {}                  # ticket -> (eta_par, norm_r, beta, phi) of the requests that shape their guidance update
         self._next = 0
 
     def submit(self, prompt: str, class_guidance: float = 6, seed: int = 11, n_iter: int = 15, negative_prompt: Optional[str] = None,
-               guidance_interval=None, eta: float = 0.0) -> int:
+               guidance_interval=None, eta: float = 0.0, guidance_rescale: float = 0.0, apg_eta: float = 1.0, apg_norm: float = 0.0,
+               apg_momentum: float = 0.0) -> int:
         eta = schedule.check_eta(eta)
+        row = schedule.check_guidance_shape(guidance_rescale, apg_eta, apg_norm, apg_momentum)
         if negative_prompt is not None and not self.mixed:
             raise ValueError("a negative prompt needs RequestBatcher(mixed=True)")
         if guidance_interval is not None and not self.mixed:
@@ -713,12 +757,20 @@ class RequestBatcher:
             self._intervals[ticket] = interval
         if eta > 0.0:
             self._etas[ticket] = eta
+        if not schedule.guidance_shape_neutral(row):
+            self._shapes[ticket] = row
         self._queue.append(_Request(ticket, str(prompt), float(class_guidance), int(seed), int(n_iter),
                                     None if negative_prompt is None else str(negative_prompt)))
         return ticket
 
     def pending(self) -> int:
         return len(self._queue)
+
+    @staticmethod
+    def _shape_kwargs(rows):
+        """Rows ``(eta_par, norm_r, beta, phi)``, one per request of a call, as ``generate_images_from_texts``' per-prompt keyword lists."""
+        return dict(apg_eta=[r[0] for r in rows], apg_norm=[r[1] for r in rows], apg_momentum=[r[2] for r in rows],
+                    guidance_rescale=[r[3] for r in rows])
 
     @staticmethod
     def call_rows(requests) -> int:
@@ -746,9 +798,10 @@ class RequestBatcher:
             return calls
         groups = {}
         for q in self._queue:
-            groups.setdefault((q.class_guidance, q.n_iter, self._etas.get(q.ticket, 0.0)), []).append((q.ticket, q.prompt, q.seed))
+            key = (q.class_guidance, q.n_iter, self._etas.get(q.ticket, 0.0), self._shapes.get(q.ticket, schedule.GUIDANCE_SHAPE_NEUTRAL))
+            groups.setdefault(key, []).append((q.ticket, q.prompt, q.seed))
         calls = []
-        for (g, n, _), reqs in sorted(groups.items(), key=lambda kv: -len(kv[1])):      # (a group's eta is that of any of its tickets)
+        for (g, n, _, _), reqs in sorted(groups.items(), key=lambda kv: -len(kv[1])):   # (a group's eta and shape are those of any of its tickets)
             for i in range(0, len(reqs), self.max_batch):
                 calls.append((g, n, reqs[i:i + self.max_batch]))
         return calls
@@ -768,11 +821,15 @@ class RequestBatcher:
                     kw["guidance_interval"] = [self._intervals.get(r.ticket) for r in reqs]
                 if any(r.ticket in self._etas for r in reqs):
                     kw["eta"] = [self._etas.get(r.ticket, 0.0) for r in reqs]
+                if any(r.ticket in self._shapes for r in reqs):
+                    kw.update(self._shape_kwargs([self._shapes.get(r.ticket, schedule.GUIDANCE_SHAPE_NEUTRAL) for r in reqs]))
             else:                             # (class_guidance, n_iter, [(ticket, prompt, seed), ...])
                 g, n, reqs = call
                 kw = dict(class_guidance=g, seeds=[s for _, _, s in reqs], n_iter=n)
                 if reqs[0][0] in self._etas:
                     kw["eta"] = self._etas[reqs[0][0]]
+                if reqs[0][0] in self._shapes:
+                    kw.update(self._shape_kwargs([self._shapes[reqs[0][0]]] * len(reqs)))
             try:
                 imgs = self.pipeline.generate_images_from_texts([r[1] for r in reqs], **kw)
             except Exception as exc:
@@ -783,5 +840,6 @@ class RequestBatcher:
             for t in done:
                 self._intervals.pop(t, None)
                 self._etas.pop(t, None)
+                self._shapes.pop(t, None)
             self._queue = [q for q in self._queue if q.ticket not in done]
         return out

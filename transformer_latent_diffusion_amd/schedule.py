@@ -270,6 +270,56 @@ def noise_key(seed: int, index: int = 0) -> int:
     return (int(seed) & 0xFFFFFFFF) | ((int(index) & 0xFFFFFFFF) << 32)
 
 
+# ---- the shape of the guidance update (tld_sample_requests_shaped) ----------------------------------------------------------
+GUIDANCE_SHAPE_NEUTRAL = (1.0, 0.0, 0.0, 0.0)       # (eta_par, norm_r, beta, phi): plain classifier-free guidance
+
+
+def check_guidance_shape(guidance_rescale=0.0, apg_eta=1.0, apg_norm=0.0, apg_momentum=0.0) -> Tuple[float, float, float, float]:
+    """The four controls of the guidance update as the engine's row ``(eta_par, norm_r, beta, phi)`` of float32 values held as floats:
+    ``guidance_rescale`` = phi in [0, 1] (Lin et al. 2023; 0 off), ``apg_eta`` = eta_par >= 0 (weight of the update's part parallel to the
+    conditional prediction; 1 off), ``apg_norm`` = norm_r >= 0 (the update's norm is clipped to it; 0 off), ``apg_momentum`` = beta with
+    |beta| < 1 (Sadat et al. 2024 use negative values; 0 off).  Anything else, a non-finite value included, raises ValueError.  The checks
+    run on the float32 values, which are what the engine checks again."""
+    out = []
+    for name, v in (("apg_eta", apg_eta), ("apg_norm", apg_norm), ("apg_momentum", apg_momentum), ("guidance_rescale", guidance_rescale)):
+        try:
+            with np.errstate(over="ignore"):
+                f = float(np.float32(float(v)))
+        except (TypeError, ValueError, OverflowError):
+            raise ValueError(f"{name} = {v!r}: expected a number")
+        if not math.isfinite(f):
+            raise ValueError(f"{name} = {v!r}: expected a finite value")
+        out.append(f)
+    eta_par, norm_r, beta, phi = out
+    if eta_par < 0.0:
+        raise ValueError(f"apg_eta = {apg_eta!r}: expected >= 0")
+    if norm_r < 0.0:
+        raise ValueError(f"apg_norm = {apg_norm!r}: expected >= 0 (0: no clipping)")
+    if not abs(beta) < 1.0:
+        raise ValueError(f"apg_momentum = {apg_momentum!r}: expected |beta| < 1")
+    if not 0.0 <= phi <= 1.0:
+        raise ValueError(f"guidance_rescale = {guidance_rescale!r}: expected inside [0, 1]")
+    return eta_par, norm_r, beta, phi
+
+
+def guidance_shape_neutral(row) -> bool:
+    """True where the row asks for none of the four controls: the request takes plain CFG, the arithmetic of every other entry."""
+    return tuple(float(v) for v in row) == GUIDANCE_SHAPE_NEUTRAL
+
+
+def guidance_shape_rows(B: int, guidance_rescale=0.0, apg_eta=1.0, apg_norm=0.0, apg_momentum=0.0):
+    """Each control a scalar (for all) or a length-B sequence -> B checked rows, or None where every row is neutral (the call without ``shape``)."""
+    def seq(v, name):
+        if isinstance(v, (list, tuple, np.ndarray)):
+            if len(v) != B:
+                raise ValueError(f"{name}: {len(v)} entries for {B} requests")
+            return list(v)
+        return [v] * B
+    cols = [seq(guidance_rescale, "guidance_rescale"), seq(apg_eta, "apg_eta"), seq(apg_norm, "apg_norm"), seq(apg_momentum, "apg_momentum")]
+    rows = [check_guidance_shape(cols[0][b], cols[1][b], cols[2][b], cols[3][b]) for b in range(B)]
+    return None if all(guidance_shape_neutral(r) for r in rows) else rows
+
+
 def guided_rows(sorted_counts: Sequence[int], tables: Sequence[np.ndarray], skip: bool = True):
     """The model batches of a guided call, as the engine plans them: requests in the engine's order (``request_order``) with one guidance
     table each.  Returns ``(U, slots, src)`` with, per step i over the ``B_i`` requests still running (``active_prefix``): ``U[i]`` the

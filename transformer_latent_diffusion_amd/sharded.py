@@ -105,7 +105,7 @@ def generate_latents_requests_sharded(gen, labels: torch.Tensor, *, group: Optio
                                       **per_request) -> torch.Tensor:
     """``DiffusionGenerator.generate_latents_requests`` over all ranks of ``group`` (same arguments, without ``trace``).  The noise,
     labels, negative labels, initial latents and masks travel as per-sample tensors; the per-request sequences (``n_iter``,
-    ``class_guidance``, ``exponent``, ``strength``, ``use_ddpm_plus``, ``eta``, ``noise_seeds``) ride as the requests' indices, one more ``extras`` tensor sliced
+    ``class_guidance``, ``exponent``, ``strength``, ``use_ddpm_plus``, ``eta``, ``noise_seeds``, ``guidance_rescale``, ``apg_eta``, ``apg_norm``, ``apg_momentum``) ride as the requests' indices, one more ``extras`` tensor sliced
     with the same bounds, and every rank picks its own entries.  The noise is drawn and the optional operands are stacked by the helpers
     ``generate_latents_requests`` itself uses; a whole tensor travels as it is (``sharded_sample`` checks its batch)."""
     B = labels.shape[0]
