@@ -1,7 +1,7 @@
 """CPU: the call transcript of the Python sampler surface (denoiser.py, diffusion.py, sharded.py).
 
 Every public entry is driven through a fixed list of calls around a stand-in for libtld_hip.so that records what ``tld_sample``,
-``tld_sample_from`` and ``tld_sample_requests`` receive: the entry, the batch, the level count and every scalar, each request record, which
+``tld_sample_from`` and the four ``tld_sample_requests*`` entries receive: the entry, the batch, the level count and every scalar, each request record, which
 optional pointers were null, and every tensor operand BY NAME -- a bitwise match against a table of tensors this file builds itself (the
 ``torch.randn`` draws from the same seeds, ``schedule.step_coefficients`` tables, stacked and filled optionals, ...), so the transcript holds
 no hash of a random draw and does not depend on the torch or numpy build.  The stand-in reads its operands through host pointers and writes a
@@ -143,14 +143,45 @@ class Lib:
         return self._run("tld_sample_from", B, eps, lab, z0, m, None, [(n_levels, g, start_mix, 0)] * B, self.names.of(tab),
                          dict(n_levels=n_levels, class_guidance=g, start_mix=start_mix, sharp_f=sharp, bright_f=bright), out, tx0, txt, stream)
 
-    def tld_sample_requests(self, h, eps, z0, m, lab, neg, recs, table, n_max, sharp, bright, out, B, tx0, txt, stream):
+    def _requests(self, entry, eps, z0, m, lab, neg, recs, table, n_max, sharp, bright, out, B, tx0, txt, stream, **host):
+        """The four requests entries.  ``host``: the entry's further HOST arrays by parameter name (a pointer or None) -- a guidance table is
+        recorded as its values per request, the noise coefficients by name, the keys and the shape rows as values; a NULL as None."""
         recs = [(r.n_levels, r.class_guidance, r.start_mix, r.has_negative) for r in recs]
         tab = np.ctypeslib.as_array(table, shape=(B, n_max, 6))
         coeffs = [self.names.of(tab[k, : r[0]]) for k, r in enumerate(recs)]
         pad = all(not tab[k, r[0]:].any() for k, r in enumerate(recs))
-        return self._run("tld_sample_requests", B, eps, lab, z0, m, neg, recs, coeffs,
-                         dict(n_max=n_max, sharp_f=sharp, bright_f=bright, records=[list(r) for r in recs], table_padding_zero=pad),
+        extra = {}
+        for what, p in host.items():
+            if p is None:
+                extra[what] = None
+            elif what == "noise_keys":
+                extra[what] = [int(v) for v in np.ctypeslib.as_array(p, shape=(B,))]
+            elif what == "shape":
+                extra[what] = np.ctypeslib.as_array(p, shape=(B, 4)).astype(np.float64).tolist()
+            else:
+                t = np.ctypeslib.as_array(p, shape=(B, n_max))
+                rows = [t[k, : r[0]] for k, r in enumerate(recs)]
+                extra[what] = [self.names.of(v) for v in rows] if what == "noise_coeff" else [v.astype(np.float64).tolist() for v in rows]
+                extra[what + "_padding_zero"] = all(not t[k, r[0]:].any() for k, r in enumerate(recs))
+        return self._run(entry, B, eps, lab, z0, m, neg, recs, coeffs,
+                         dict(n_max=n_max, sharp_f=sharp, bright_f=bright, records=[list(r) for r in recs], table_padding_zero=pad, **extra),
                          out, tx0, txt, stream)
+
+    def tld_sample_requests(self, h, eps, z0, m, lab, neg, recs, table, n_max, sharp, bright, out, B, tx0, txt, stream):
+        return self._requests("tld_sample_requests", eps, z0, m, lab, neg, recs, table, n_max, sharp, bright, out, B, tx0, txt, stream)
+
+    def tld_sample_requests_guided(self, h, eps, z0, m, lab, neg, recs, table, guidance, n_max, sharp, bright, out, B, tx0, txt, stream):
+        return self._requests("tld_sample_requests_guided", eps, z0, m, lab, neg, recs, table, n_max, sharp, bright, out, B, tx0, txt, stream, guidance=guidance)
+
+    def tld_sample_requests_stochastic(self, h, eps, z0, m, lab, neg, recs, table, guidance, noise_coeff, noise_keys, n_max, sharp, bright, out, B, tx0, txt,
+                                       stream):
+        return self._requests("tld_sample_requests_stochastic", eps, z0, m, lab, neg, recs, table, n_max, sharp, bright, out, B, tx0, txt, stream,
+                              guidance=guidance, noise_coeff=noise_coeff, noise_keys=noise_keys)
+
+    def tld_sample_requests_shaped(self, h, eps, z0, m, lab, neg, recs, table, guidance, noise_coeff, noise_keys, shape, n_max, sharp, bright, out, B, tx0,
+                                   txt, stream):
+        return self._requests("tld_sample_requests_shaped", eps, z0, m, lab, neg, recs, table, n_max, sharp, bright, out, B, tx0, txt, stream,
+                              guidance=guidance, noise_coeff=noise_coeff, noise_keys=noise_keys, shape=shape)
 
 
 def _label(text):
@@ -276,6 +307,17 @@ def build_transcript(mp):
     for s in (None, 0.65):
         lv = schedule.noise_schedule(99, 1, LEVELS)
         names.add(f"coef(LEVELS{'' if s is None else f', s {s}'})", schedule.step_coefficients(lv if s is None else schedule.truncate_levels(lv, s)[1], True))
+    for n in (3, 4, 5, 6, 8):                           # the stochastic solvers: the table and the noise coefficient per forward
+        names.add(f"ecoef zeros {n}", np.zeros(n, np.float32))
+        for plus in (True, False):
+            for eta in (0.5, 1.0):
+                co, e = schedule.step_coefficients(schedule.noise_schedule(n, 1), plus, eta)
+                names.add(f"coef(n {n}, e 1, {'dpm' if plus else 'ddim'}, eta {eta})", co)
+                names.add(f"ecoef(n {n}, e 1, {'dpm' if plus else 'ddim'}, eta {eta})", e)
+    co, e = schedule.step_coefficients(schedule.truncate_levels(schedule.noise_schedule(8, 1), 0.65)[1], True, 1.0)
+    names.add("coef(n 8, e 1, dpm, s 0.65, eta 1.0)", co)
+    names.add("ecoef(n 8, e 1, dpm, s 0.65, eta 1.0)", e)
+    names.add(f"ecoef zeros {co.shape[0]}", np.zeros(co.shape[0], np.float32))
     rg = torch.Generator().manual_seed(61)
     eps5, z5 = torch.randn(5, CH, S, S, generator=rg), torch.randn(5, CH, S, S, generator=rg) * 0.5
     lab5, neg5 = torch.randn(5, TXT, generator=rg) * 0.5, torch.randn(5, TXT, generator=rg) * 0.5
@@ -429,6 +471,7 @@ def build_transcript(mp):
     # ---- refusals: type and message --------------------------------------------------------------------------------------------------------
     z3, l3, e3, k3 = z5[:3], lab5[:3], eps5[:3], mask5[:3]
     ok = dict(n_iter=[4, 5, 6], class_guidance=3.0, seed=1)
+    co4n = schedule.step_coefficients(schedule.noise_schedule(4, 1)).shape[0]
     refusals = {
         "generate_latents labels batch": lambda: gen.generate_latents(l3, num_imgs=5, img_size=S),
         "generate labels batch": lambda: gen.generate(l3, seeds=eps5),
@@ -490,6 +533,30 @@ def build_transcript(mp):
         "sample_requests neg count": lambda: m.sample_latents_requests(e3, l3, [co5] * 3, [1.0] * 3, neg_labels=[None]),
         "sample_requests neg row": lambda: m.sample_latents_requests(e3, l3, [co5] * 3, [1.0] * 3, neg_labels=[None, torch.zeros(5), None]),
         "sample_requests bad neg row, empty batch": lambda: m.sample_latents_requests(e3[:0], l3[:0], [], [], neg_labels=torch.zeros(1, TXT)),
+        "requests guidance_interval order": lambda: gen.generate_latents_requests(l3, **dict(ok, guidance_interval=(0.8, 0.3))),
+        "requests guidance_interval count": lambda: gen.generate_latents_requests(l3, **dict(ok, guidance_interval=[None, (0.2, 0.9)])),
+        "requests guidance_schedule count": lambda: gen.generate_latents_requests(l3, **dict(ok, guidance_schedule=[None, None])),
+        "requests guidance_schedule length": lambda: gen.generate_latents_requests(l3, **dict(ok, guidance_schedule=[None, np.ones(2), None])),
+        "requests guidance_schedule nan": lambda: gen.generate_latents_requests(l3, **dict(ok, n_iter=4, guidance_schedule=[None, np.full(co4n, float("nan")), None])),
+        "requests eta negative": lambda: gen.generate_latents_requests(l3, **dict(ok, eta=[0.0, -0.5, 0.0])),
+        "requests eta count": lambda: gen.generate_latents_requests(l3, **dict(ok, eta=[0.5, 0.5])),
+        "requests eta with a seeds tensor": lambda: gen.generate_latents_requests(l3, **dict(ok, eta=0.5, seeds=e3)),
+        "requests noise_seeds count": lambda: gen.generate_latents_requests(l3, **dict(ok, eta=0.5, noise_seeds=[1, 2])),
+        "requests guidance_rescale range": lambda: gen.generate_latents_requests(l3, **dict(ok, guidance_rescale=1.5)),
+        "requests apg_momentum range": lambda: gen.generate_latents_requests(l3, **dict(ok, apg_momentum=[0.0, 1.0, 0.0])),
+        "requests apg_norm count": lambda: gen.generate_latents_requests(l3, **dict(ok, apg_norm=[1.0, 2.0])),
+        "generate_latents eta nan": lambda: gen.generate_latents(l3, num_imgs=3, img_size=S, eta=float("nan")),
+        "generate_latents_from apg_eta negative": lambda: gen.generate_latents_from(z3, l3, apg_eta=-1.0),
+        "sample_requests guidance_steps count": lambda: m.sample_latents_requests(e3, l3, [co5] * 3, None, guidance_steps=[np.ones(5)] * 2),
+        "sample_requests guidance_steps length": lambda: m.sample_latents_requests(e3, l3, [co5] * 3, None, guidance_steps=[np.ones(co5.shape[0] + 1)] * 3),
+        "sample_requests guidance_steps inf": lambda: m.sample_latents_requests(e3, l3, [co5] * 3, None, guidance_steps=[np.full(co5.shape[0], float("inf"))] * 3),
+        "sample_requests noise_coeffs without keys": lambda: m.sample_latents_requests(e3, l3, [co5] * 3, [1.0] * 3, noise_coeffs=[np.zeros(co5.shape[0])] * 3),
+        "sample_requests noise_keys count": lambda: m.sample_latents_requests(e3, l3, [co5] * 3, [1.0] * 3, noise_coeffs=[np.zeros(co5.shape[0])] * 3, noise_keys=[1]),
+        "sample_requests noise_coeffs final": lambda: m.sample_latents_requests(e3, l3, [co5] * 3, [1.0] * 3, noise_coeffs=[np.ones(co5.shape[0])] * 3, noise_keys=[1, 2, 3]),
+        "sample_requests noise_keys range": lambda: m.sample_latents_requests(e3, l3, [co5] * 3, [1.0] * 3, noise_coeffs=[np.zeros(co5.shape[0])] * 3, noise_keys=[1, -2, 3]),
+        "sample_requests shape count": lambda: m.sample_latents_requests(e3, l3, [co5] * 3, [1.0] * 3, shape=[(1.0, 0.0, 0.0, 0.0)] * 2),
+        "sample_requests shape row": lambda: m.sample_latents_requests(e3, l3, [co5] * 3, [1.0] * 3, shape=[(1.0, 0.0, 0.0)] * 3),
+        "sample_requests shape phi": lambda: m.sample_latents_requests(e3, l3, [co5] * 3, [1.0] * 3, shape=[(1.0, 0.0, 0.0, 2.0)] * 3),
         "latent_mask not square": lambda: latent_mask(torch.zeros(32, 16), 16),
         "latent_mask dims": lambda: latent_mask(torch.zeros(2, 32, 32), 16),
         "latent_mask multiple": lambda: latent_mask(torch.zeros(1, 40, 40), 16),
@@ -526,6 +593,47 @@ def build_transcript(mp):
     }
     for label, fn in refusals.items():
         call("refusal: " + label, fn)
+    # ---- the guided, stochastic and shaped entries through the public API (after every older call: the stand-in numbers what it writes) --------------------------------------------------------------------
+    ge = dict(n_iter=[8, 5, 8, 3, 5], class_guidance=[1.0, 3.0, 4.5, 6.0, 3.0], seeds=[11, 12, 13, 14, 11])
+    n8, n5 = co8.shape[0], co5.shape[0]
+    call("requests guidance_interval for all, trace", lambda: gen.generate_latents_requests(lab5, guidance_interval=(0.3, 0.8), trace=True, **ge))
+    call("requests guidance_interval per request", lambda: gen.generate_latents_requests(lab5, guidance_interval=[None, (0.2, 0.9), (0.5, 0.5), None, (0.0, 1.0)],
+                                                                                         negative_labels=neg_list, **ge))
+    call("requests guidance_schedule", lambda: gen.generate_latents_requests(
+        lab5[:3], n_iter=[8, 5, 8], class_guidance=2.0, seeds=[11, 12, 13], guidance_schedule=[np.linspace(4.0, 1.0, n8), None, np.ones(n8)]))
+    call("requests guidance_schedule and interval", lambda: gen.generate_latents_requests(
+        lab5[:3], n_iter=[5, 8, 5], class_guidance=2.0, seed=4, guidance_schedule=[None, np.full(n8, 1.5), None], guidance_interval=[(0.3, 0.8), None, None]))
+    call("requests eta per request", lambda: gen.generate_latents_requests(lab5, eta=[0.0, 1.0, 0.5, 0.0, 1.0], use_ddpm_plus=[True, True, False, True, False], **ge))
+    call("requests eta, batch seed", lambda: gen.generate_latents_requests(lab5[:3], n_iter=[4, 6, 4], eta=0.5, seed=4))
+    call("requests eta, seeds tensor and noise_seeds", lambda: gen.generate_latents_requests(lab5, n_iter=5, eta=1.0, seeds=eps5, img_size=S,
+                                                                                             noise_seeds=[1, 2, 1 << 40, (1 << 64) - 1, 5]))
+    call("requests eta, init and mask", lambda: gen.generate_latents_requests(lab5, init_latents=z5, strength=0.65, mask=mask5, n_iter=8, eta=1.0, seed=4, trace=True))
+    call("requests guidance_rescale", lambda: gen.generate_latents_requests(lab5, guidance_rescale=0.75, **ge))
+    call("requests apg per request", lambda: gen.generate_latents_requests(lab5, apg_eta=[1.0, 0.0, 0.5, 1.0, 0.0], apg_norm=[0.0, 2.5, 0.0, 0.0, 15.0],
+                                                                           apg_momentum=[0.0, -0.5, 0.0, 0.0, -0.75], guidance_rescale=[0.0, 0.0, 0.5, 0.0, 0.25], **ge))
+    call("requests interval and eta", lambda: gen.generate_latents_requests(lab5, guidance_interval=(0.3, 0.8), eta=[1.0, 0.0, 0.5, 1.0, 0.0], **ge))
+    call("requests interval and shape", lambda: gen.generate_latents_requests(lab5, guidance_interval=[None, (0.2, 0.9), None, None, (0.3, 0.8)], guidance_rescale=0.5,
+                                                                              apg_norm=2.5, **ge))
+    call("requests eta and shape", lambda: gen.generate_latents_requests(lab5, eta=0.5, apg_eta=0.0, apg_momentum=-0.5, negative_labels=neg5, **ge))
+    call("requests interval, eta and shape, trace", lambda: gen.generate_latents_requests(lab5, guidance_interval=(0.3, 0.8), eta=[1.0, 0.0, 0.5, 1.0, 0.0],
+                                                                                          guidance_rescale=[0.5, 0.0, 0.0, 0.25, 0.0], trace=True, **ge))
+    call("generate_latents guidance_interval", lambda: gen.generate_latents(lab5, n_iter=8, num_imgs=5, class_guidance=3.0, seed=4, img_size=S, guidance_interval=(0.3, 0.8)))
+    call("generate_latents eta", lambda: gen.generate_latents(lab5[:3], n_iter=5, num_imgs=3, seed=4, img_size=S, eta=1.0, use_ddpm_plus=False))
+    call("generate_latents apg, trace", lambda: gen.generate_latents(lab5[:3], n_iter=5, num_imgs=3, seed=4, img_size=S, apg_eta=0.0, apg_norm=2.5, trace=True))
+    call("generate eta and rescale", lambda: gen.generate(lab5[:3], n_iter=5, num_imgs=3, seed=4, img_size=S, eta=0.5, guidance_rescale=0.75))
+    call("generate_latents_from interval, eta, rescale, mask", lambda: gen.generate_latents_from(z5, lab5, strength=0.65, mask=mask5, n_iter=8, seed=4,
+                                                                                                guidance_interval=(0.1, 0.5), eta=1.0, guidance_rescale=0.5))
+    call("generate_from apg", lambda: gen.generate_from(z5[:3], lab5[:3], strength=1.0, n_iter=5, seed=4, apg_momentum=-0.5))
+    g3s, e3s = [np.full(n5, 2.0), np.r_[np.ones(n8 - 1), 3.0], np.ones(n5)], [np.zeros(n5), np.r_[np.full(n8 - 1, 0.25), 0.0], np.zeros(n5)]
+    names.add("e3s[1]", e3s[1])
+    call("sample_latents_requests guidance_steps", lambda: m.sample_latents_requests(eps5[:3], lab5[:3], [co5, co8, co5], None, guidance_steps=g3s, trace=True))
+    call("sample_latents_requests noise", lambda: m.sample_latents_requests(eps5[:3], lab5[:3], [co5, co8, co5], [1, 2, 3], noise_coeffs=e3s, noise_keys=[7, 8, 9]))
+    call("sample_latents_requests shape alone", lambda: m.sample_latents_requests(eps5[:3], lab5[:3], [co5, co8, co5], [1, 2, 3],
+                                                                                  shape=[(1.0, 0.0, 0.0, 0.0), (0.0, 2.5, -0.5, 0.0), (1.0, 0.0, 0.0, 0.5)]))
+    call("sample_latents_requests steps, noise and shape", lambda: m.sample_latents_requests(
+        eps5[:3], lab5[:3], [co5, co8, co5], None, guidance_steps=g3s, noise_coeffs=e3s, noise_keys=[7, 8, (1 << 64) - 1], shape=[(1.0, 0.0, 0.0, 0.5)] * 3,
+        neg_labels=neg_list[:3], init_latents=z5[:3], start_mix=[1, 0.5, 1], mask=mask5[:3]))
+    call("sample_latents_requests steps and shape, empty batch", lambda: m.sample_latents_requests(eps5[:0], lab5[:0], [], None, guidance_steps=[], shape=[], trace=True))
     text = json.dumps(out)
     assert '"?"' not in text, "a tensor the table does not name: " + next(json.dumps(c) for c in out if '"?"' in json.dumps(c))[:2000]
     bad = [c["call"] for c in out if ("raises" in c) != c["call"].startswith("refusal: ")]

@@ -5,6 +5,7 @@
 #include <mutex>
 #include <stdint.h>
 #include "tld_guidance_shape.h"   // GuidanceShape, guidance_shape_finalize
+#include "tld_sampler_rows.h"     // SamplerStepRow, SamplerNoiseRow: the rows of the sampler's staged upload
 #include "tld_qkv_pair_plan.h"    // plan_qkv_pair: one or two heads per tile of the fused QKV + attention kernel
 #include "tld_gemm_plan.h"        // GemmParams, GemmEpilogue, bf16, resid_t, kLnSlots (tld_gemm_params.h); GemmPlan, gemm_resid_stat_slots
 
@@ -436,19 +437,6 @@ void launch_tail_fold_debug_row(float* row, const resid_t* x, const float* bias,
 
 // sampler elementwise: CFG combine + multistep update (see schedule.py).  One kernel serves tld_sample, tld_sample_from and
 // tld_sample_requests: what differs per sample is read from a device table, one row per (step, request), or one per step shared by every sample
-struct SamplerStepRow {
-    float g, a, b, c, c1, c2;     // class guidance and the step's coefficients of the request (schedule.py)
-    float s_next;                 // noise level the updated x_t sits at (read with a mask only; unused on the request's final step)
-    int final_step;               // 1: the request's last level -- combine (+ mask blend, + shifts on channels 3 and 0) into out_latent, no update
-                                  // (the slots flavour packs final | (slot + 1) << 1 here: see launch_sampler_step)
-};
-// second table of the stochastic entry, one row per (step, request) beside SamplerStepRow: x_t += e z after the update, z the standard normals of
-// (key, step, quad) (tld_sampler_noise.h).  e == 0.0f: nothing is drawn and nothing is added
-struct alignas(16) SamplerNoiseRow {
-    float e;                      // sigma_t sqrt(1 - exp(-2 eta h)) of the request's step (schedule.py); 0 on its final forward
-    uint32_t key_lo, key_hi;      // the request's 64-bit noise key
-    uint32_t reserved;
-};
 struct SamplerStepParams {
     const float* x0_2b;           // [2 active, img] model output of the step: cond rows of the active prefix, then their uncond rows
     float* x_t;                   // [B, img]  in/out

@@ -8,6 +8,7 @@
 #include "tld_common.h"
 #include "tld_host.h"
 #include "tld_refresh.h"
+#include "tld_sample_plan.h"
 #include "tld_tail_fold_math.h"
 
 #include <cmath>
@@ -17,7 +18,6 @@
 #include <cstdlib>
 #include <map>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 using namespace tld;
@@ -89,6 +89,7 @@ struct tld_engine : DeviceArena {      // (pad = 256: every allocation of this e
     hipEvent_t stage_ev = nullptr;     // recorded after the last copy out of stage_host
     void* req_dev = nullptr;           // the samplers' tables of one call (run_sampler): step rows, start mixes, token-row indices
     size_t req_cap = 0;
+    SamplePlan plan;                   // of the last sampler call: kept for its vectors, so a steady state plans without allocating them
     // the shaped guidance update (tld_sample_requests_shaped), allocated by the first call that needs them: the momentum buffer [max_batch, img], and
     // per request (P, Q) and the five sums of the step's guidance_stats_kernel launch
     float* shape_mom = nullptr;
@@ -555,142 +556,37 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
     return TLD_OK;
 }
 
-// What a sampler entry asks of run_sampler, after its own argument checks.  Request b is requests[b * stride] with the coefficient table
-// coeffs + b * stride * n_max * 6: stride 1 for tld_sample_requests, 0 for the uniform entries (one record and one table for the whole batch, one
-// row per step in the device table).  The records are ordered by non-increasing n_levels, and requests[0].n_levels == n_max.
-struct SamplePlan {
-    int B, n_max, stride;
-    const tld_sample_request* requests;
-    const float* coeffs;                 // HOST [B or 1][n_max][6]: (sigma, a, b, c, c1, c2) per level
-    const float* guidance;               // HOST [B][n_max] or null: the guidance of request b's forward i instead of its record's (tld_sample_requests_guided)
-    bool skip;                           // with guidance: a forward guided at exactly 1.0f runs no unconditional sample (the engine's TLD_GUIDANCE_SKIP)
-    // tld_sample_requests_stochastic (with guidance only): HOST [B][n_max] e of request b's forward i and HOST [B] keys; null: no noise, the kernels without the NOISE flag
-    const float* noise_coeff; const uint64_t* noise_keys;
-    // tld_sample_requests_shaped (with noise_coeff only): HOST [B] shape rows; null: the kernels without the SHAPE flag
-    const GuidanceShape* shape;
-    // conditioning noise rows: Tn sigmas and, per (step, request), the row of its sigma; null: row i is level i of the one table (the uniform entries)
-    int Tn; const float* sig; const int* noise_idx;       // sig [Tn], noise_idx [n_max][B]
-    const float *noise, *init_latent, *mask, *labels, *neg_labels;      // device; init_latent / mask / neg_labels optional
+// The device side of a sampler call, beside its SampleCall (tld_sample_plan.h)
+struct SampleOperands {
+    const float *noise, *init_latent, *mask, *labels, *neg_labels;      // init_latent / mask / neg_labels optional
     float sharp, bright;
     float *out_latent, *trace_x0, *trace_xt;
     int path_step, path_start;           // the EP_UPDATE* / EP_START_MIX* bits of the calling entry
     bool keep_stages;                    // step.* and the body's stages are kept at the debug step (the uniform entries)
 };
 
-// Unconditional slots of step i of a guided call, for the Bi requests still running: slot[b] is the place of request b's unconditional sample among the
-// step's (compacted in request order), or -1 where its guidance is 1.0f and none exists.  skip off: every request keeps one.  Returns their number U_i.
-int guided_slots(const float* guidance, int n_max, int Bi, int i, bool skip, int* slot) {
-    int U = 0;
-    for (int b = 0; b < Bi; ++b) slot[b] = (!skip || guidance[(size_t)b * n_max + i] != 1.0f) ? U++ : -1;
-    return U;
-}
-
-// The one sampler loop: conditioning tables of every request's whole trajectory, the start, then per step the model on the requests that still run
-// (a shrinking prefix, CFG-doubled, layer-0 sharing) and the elementwise step.  Host-built tables travel through the engine's pinned staging buffer
-// in two uploads behind stage_ev: no stream synchronisation.  Conditioning rows: Tn noise rows, B label rows, the zero row, one row per negative label.
-// With a guidance table (tld_sample_requests_guided) the model batch of step i is [Bi conditional | U_i unconditional] samples, U_i the requests guided at
-// that step: the step's rows then carry a third table, the request each model sample reads, and a request's step row its unconditional slot.
-int run_sampler(tld_engine* e, const SamplePlan& p, hipStream_t s) {
-    const int B = p.B, n_max = p.n_max, Tn = p.Tn, tabB = p.stride ? B : 1;
-    auto req = [&](int b) -> const tld_sample_request& { return p.requests[(size_t)b * p.stride]; };
-    const bool guided = p.guidance != nullptr;
-    const int per = guided ? 3 : 2;                           // int tables per step: noise rows, label rows (, source rows), one entry per model sample
-    int n_neg = 0;
-    size_t row_ints = 0;                                      // per step [noise rows 2 Bi | label rows 2 Bi] over the Bi requests still running
-    for (int b = 0; b < B; ++b) { n_neg += req(b).has_negative ? 1 : 0; row_ints += (size_t)4 * req(b).n_levels; }
-    std::vector<int> slot((size_t)B), mbs((size_t)n_max);     // a step's unconditional slots; model samples per step
-    int64_t n_cond = 0, n_unc = 0;
-    for (int i = 0, Bi = B; i < n_max; ++i) {
-        while (req(Bi - 1).n_levels <= i) --Bi;
-        const int U = guided ? guided_slots(p.guidance, n_max, Bi, i, p.skip, slot.data()) : Bi;
-        mbs[(size_t)i] = Bi + U; n_cond += Bi; n_unc += U;
-    }
-    if (guided) row_ints = (size_t)3 * (size_t)(n_cond + n_unc);
-    const int T = Tn + B + 1 + n_neg;
-    const size_t tab_bytes = (size_t)n_max * tabB * sizeof(SamplerStepRow), mix_bytes = (size_t)tabB * sizeof(float);
-    // (the stochastic entry's second table, 16-byte rows [n_max][tabB], rides behind the int tables in the same upload)
-    const bool noisy = p.noise_coeff != nullptr;
-    const size_t noise_off = (tab_bytes + mix_bytes + row_ints * sizeof(int) + 15) & ~(size_t)15;
-    // (and the shaped entry's third table, one 16-byte row per request, behind that)
-    const bool shaped = noisy && p.shape != nullptr;
-    const size_t shape_off = noise_off + (size_t)n_max * tabB * sizeof(SamplerNoiseRow);
-    const size_t up_bytes = shaped ? shape_off + (size_t)tabB * sizeof(GuidanceShape)
-                            : noisy ? shape_off : tab_bytes + mix_bytes + row_ints * sizeof(int);
-    // the steps at which a running request is shaped, has an unconditional sample and is guided at other than 1.0f: only they launch the statistics kernel
-    // (a forward at exactly 1.0f is x0 = cond with the momentum left alone, with the engine's guidance skip on or off)
-    std::vector<char> stats_step((size_t)n_max, 0);
-    bool any_shape = false, any_mom = false;
-    if (shaped) {
-        for (int i = 0, Bi = B; i < n_max; ++i) {
-            while (req(Bi - 1).n_levels <= i) --Bi;
-            guided_slots(p.guidance, n_max, Bi, i, p.skip, slot.data());
-            for (int b = 0; b < Bi; ++b)
-                if (slot[(size_t)b] >= 0 && !p.shape[b].neutral() && p.guidance[(size_t)b * n_max + i] != 1.0f) { stats_step[(size_t)i] = 1; any_shape = true; any_mom |= p.shape[b].beta != 0.0f; }
-        }
-    }
+// The one sampler loop: conditioning tables of every request's whole trajectory, the start, then per step of the plan the model on the requests that
+// still run (a shrinking prefix, CFG-doubled, layer-0 sharing) and the elementwise step.  Host-built tables travel through the engine's pinned staging
+// buffer in two uploads behind stage_ev: no stream synchronisation.  Conditioning rows: Tn noise rows, B label rows, the zero row, one row per negative label.
+// In the slots flavour the model batch of step i is [Bi conditional | U_i unconditional] samples, U_i the requests guided at that step: the step's
+// rows then carry a third table, the request each model sample reads, and a request's step row its unconditional slot.
+int run_sampler(tld_engine* e, const SamplePlan& plan, const SampleCall& call, const SampleOperands& p, hipStream_t s) {
+    const int B = plan.B, n_max = plan.n_max, Tn = plan.Tn, T = plan.T, tabB = plan.tabB;
+    const bool any_mom = plan.any_mom;
     if (int rc = ensure_cond_capacity(e, T)) return rc;
-    if (int rc = ensure_req_capacity(e, up_bytes)) return rc;
-    if (any_shape && !e->shape_pq)
+    if (int rc = ensure_req_capacity(e, plan.up_bytes)) return rc;
+    if (plan.any_shape && !e->shape_pq)
         if (int rc = dev_alloc(e, &e->shape_pq, (size_t)e->cfg.max_batch)) return rc;
-    if (any_shape && !e->shape_sums)
+    if (plan.any_shape && !e->shape_sums)
         if (int rc = dev_alloc(e, &e->shape_sums, (size_t)e->cfg.max_batch * GS_SUMS)) return rc;
     if (any_mom && !e->shape_mom)
         if (int rc = dev_alloc(e, &e->shape_mom, (size_t)e->cfg.max_batch * e->img)) return rc;
     if (int rc = debug_begin(e, T, Tn, s)) return rc;
-    if (int rc = stage_acquire(e, up_bytes + (size_t)Tn * sizeof(float))) return rc;
-    SamplerStepRow* tab = static_cast<SamplerStepRow*>(e->stage_host);
-    float* mix = reinterpret_cast<float*>(tab + (size_t)n_max * tabB);
-    int* rows = reinterpret_cast<int*>(mix + tabB);
-    float* sigs = reinterpret_cast<float*>(static_cast<char*>(e->stage_host) + up_bytes);
-    if (noisy) {
-        SamplerNoiseRow* nt = reinterpret_cast<SamplerNoiseRow*>(static_cast<char*>(e->stage_host) + noise_off);
-        for (int b = 0; b < tabB; ++b)
-            for (int i = 0; i < n_max; ++i) {
-                const bool on = i < req(b).n_levels - 1;          // (the final forward adds none: its entry was checked to be 0)
-                nt[(size_t)i * tabB + b] = SamplerNoiseRow{on ? p.noise_coeff[(size_t)b * n_max + i] : 0.0f, (uint32_t)p.noise_keys[b],
-                                                           (uint32_t)(p.noise_keys[b] >> 32), 0u};
-            }
-    }
-    if (shaped) {
-        GuidanceShape* st = reinterpret_cast<GuidanceShape*>(static_cast<char*>(e->stage_host) + shape_off);
-        for (int b = 0; b < tabB; ++b) st[b] = p.shape[b];
-    }
-    bool any_mix = false;
-    for (int b = 0; b < tabB; ++b) {
-        const tld_sample_request& r = req(b);
-        const float* c = p.coeffs + (size_t)b * n_max * 6;
-        mix[b] = r.start_mix;
-        any_mix |= r.start_mix < 1.0f;
-        for (int i = 0; i < n_max; ++i, c += 6) {
-            SamplerStepRow& u = tab[(size_t)i * tabB + b];
-            if (i >= r.n_levels) { u = SamplerStepRow{}; continue; }
-            u.g = guided ? p.guidance[(size_t)b * n_max + i] : r.class_guidance; u.a = c[1]; u.b = c[2]; u.c = c[3]; u.c1 = c[4]; u.c2 = c[5];
-            u.s_next = (i + 1 < r.n_levels) ? c[6] : 0.0f;    // sigma of the request's next row
-            u.final_step = (i == r.n_levels - 1) ? 1 : 0;
-        }
-    }
-    for (int t = 0; t < Tn; ++t) sigs[t] = p.sig ? p.sig[t] : p.coeffs[(size_t)t * 6];
-    {
-        int* nr = rows;
-        for (int i = 0, Bi = B; i < n_max; nr += per * mbs[(size_t)i], ++i) {
-            while (req(Bi - 1).n_levels <= i) --Bi;
-            const int mb = mbs[(size_t)i];
-            int *lr = nr + mb, *sr = lr + mb;                 // (sr: guided only)
-            if (guided) guided_slots(p.guidance, n_max, Bi, i, p.skip, slot.data());
-            for (int b = 0, k = 0; b < Bi; ++b) {
-                const int neg = req(b).has_negative ? Tn + B + 1 + k++ : Tn + B;  // the unconditional label: the zero row, or the request's own negative
-                const int sl = guided ? slot[(size_t)b] : b;
-                nr[b] = p.noise_idx ? p.noise_idx[(size_t)i * B + b] : i;
-                lr[b] = Tn + b;
-                if (guided) { sr[b] = b; tab[(size_t)i * tabB + b].final_step |= (sl + 1) << 1; }
-                if (sl < 0) continue;
-                nr[Bi + sl] = nr[b];
-                lr[Bi + sl] = neg;
-                if (guided) sr[Bi + sl] = b;
-            }
-        }
-        e->rows_cond = n_cond; e->rows_uncond = n_unc;
-    }
+    if (int rc = stage_acquire(e, plan.stage_bytes)) return rc;
+    sample_plan_fill(plan, call, e->stage_host);
+    e->rows_cond = plan.rows_cond; e->rows_uncond = plan.rows_uncond;
+    const float* sigs = reinterpret_cast<const float*>(static_cast<const char*>(e->stage_host) + plan.up_bytes);
+    const int n_neg = plan.n_neg;
 
     // ---- conditioning tables for every request's whole trajectory, once
     const size_t text = e->text;
@@ -698,9 +594,9 @@ int run_sampler(tld_engine* e, const SamplePlan& p, hipStream_t s) {
     HIP_TRY(hipMemcpyAsync(e->c_label, p.labels, (size_t)B * text * sizeof(float), hipMemcpyDeviceToDevice, s));
     HIP_TRY(hipMemsetAsync(e->c_label + (size_t)B * text, 0, text * sizeof(float), s));     // uncond = zeros (diffusion.py:61)
     for (int b = 0, k = 0; b < B && n_neg; ) {                // negative labels, compacted: one copy per run of consecutive requests that have one
-        if (!req(b).has_negative) { ++b; continue; }
+        if (!call.req(b).has_negative) { ++b; continue; }
         int b1 = b;
-        while (b1 < B && req(b1).has_negative) ++b1;
+        while (b1 < B && call.req(b1).has_negative) ++b1;
         HIP_TRY(hipMemcpyAsync(e->c_label + (size_t)(B + 1 + k) * text, p.neg_labels + (size_t)b * text, (size_t)(b1 - b) * text * sizeof(float),
                                hipMemcpyDeviceToDevice, s));
         k += b1 - b; b = b1;
@@ -711,52 +607,54 @@ int run_sampler(tld_engine* e, const SamplePlan& p, hipStream_t s) {
         cond_label_rows(e, Tn, B + 1 + n_neg, s);
     }
     if (int rc = cond_tables(e, T, s)) return rc;
-    HIP_TRY(hipMemcpyAsync(e->req_dev, tab, up_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(e->req_dev, e->stage_host, plan.up_bytes, hipMemcpyHostToDevice, s));
     HIP_TRY(hipEventRecord(e->stage_ev, s));     // no stream sync: the staging buffer is the engine's, guarded by this event
-    const SamplerStepRow* tab_dev = static_cast<const SamplerStepRow*>(e->req_dev);
-    const float* mix_dev = reinterpret_cast<const float*>(tab_dev + (size_t)n_max * tabB);
-    const int* nr = reinterpret_cast<const int*>(mix_dev + tabB);
-    const SamplerNoiseRow* noise_dev = noisy ? reinterpret_cast<const SamplerNoiseRow*>(static_cast<const char*>(e->req_dev) + noise_off) : nullptr;
-    const GuidanceShape* shape_dev = shaped ? reinterpret_cast<const GuidanceShape*>(static_cast<const char*>(e->req_dev) + shape_off) : nullptr;
+    const char* dev = static_cast<const char*>(e->req_dev);
+    const SamplerStepRow* tab_dev = reinterpret_cast<const SamplerStepRow*>(dev);
+    const float* mix_dev = reinterpret_cast<const float*>(dev + plan.mix_off);
+    const int* rows_dev = reinterpret_cast<const int*>(dev + plan.rows_off);
+    const SamplerNoiseRow* noise_dev = plan.noise ? reinterpret_cast<const SamplerNoiseRow*>(dev + plan.noise_off) : nullptr;
+    const GuidanceShape* shape_dev = plan.shape ? reinterpret_cast<const GuidanceShape*>(dev + plan.shape_off) : nullptr;
 
     // ---- the start: pure noise at the schedule's first level (diffusion.py:52,59), else the forward process at the first remaining level (train.py:130)
     const size_t tot = (size_t)B * e->img;
-    if (!any_mix) HIP_TRY(hipMemcpyAsync(e->xt, p.noise, tot * sizeof(float), hipMemcpyDeviceToDevice, s));
-    else launch_start_mix(p.noise, p.init_latent, mix_dev, p.stride, e->xt, B, e->img, p.path_start, s);
+    if (!plan.any_mix) HIP_TRY(hipMemcpyAsync(e->xt, p.noise, tot * sizeof(float), hipMemcpyDeviceToDevice, s));
+    else launch_start_mix(p.noise, p.init_latent, mix_dev, plan.stride, e->xt, B, e->img, p.path_start, s);
     HIP_TRY(hipMemsetAsync(e->x0_prev, 0, tot * sizeof(float), s));
     if (any_mom) HIP_TRY(hipMemsetAsync(e->shape_mom, 0, tot * sizeof(float), s));      // the momentum starts every call at zero
     // ---- the steps over the shrinking prefix of requests that still run
-    for (int i = 0, Bi = B; i < n_max; nr += per * mbs[(size_t)i], ++i) {
-        while (req(Bi - 1).n_levels <= i) --Bi;
+    for (int i = 0; i < n_max; ++i) {
+        const SampleStep& st = plan.steps[(size_t)i];
         const bool last = i == n_max - 1;
-        const int mb = mbs[(size_t)i];
+        const int Bi = st.Bi, mb = st.mb;
+        const int* nr = rows_dev + st.rows_off;
         // At the debug step (tld_engine_set_debug_step; every step when it is negative) the body's stages are kept, and so are the step's inputs
         // (x_t, x0_prev) and outputs (the 2B forward output, the x0 written, the next x_t).
         if (p.keep_stages) e->dbg_keep = e->debug && (e->dbg_step < 0 || e->dbg_step == i);
         SNAP("step.x_t", e->xt, ST_F32, s, B, e->img); SNAP("step.x0_prev", e->x0_prev, ST_F32, s, B, e->img);
         // pred_image: model(cat[x_t, x_t], sigma_i, [labels; 0])   (diffusion.py:94-101)
-        if (int rc = run_body(e, e->xt, Bi, mb, nr, nr + mb, e->io_out, s, true, guided ? nr + 2 * mb : nullptr)) return rc;
+        if (int rc = run_body(e, e->xt, Bi, mb, nr, nr + mb, e->io_out, s, true, plan.slots ? nr + 2 * mb : nullptr)) return rc;
         SamplerStepParams up{};
         up.x0_2b = e->io_out; up.x_t = e->xt; up.x0_prev = e->x0_prev; up.out_latent = p.out_latent;
         up.trace_x0 = (!last && p.trace_x0) ? p.trace_x0 + (size_t)i * tot : nullptr;
         up.trace_xt = (!last && p.trace_xt) ? p.trace_xt + (size_t)i * tot : nullptr;
         up.noise = p.noise; up.z0 = p.init_latent; up.mask = p.mask;
-        up.rows = tab_dev + (size_t)i * tabB; up.row_stride = p.stride; up.sharp = p.sharp; up.bright = p.bright;
+        up.rows = tab_dev + (size_t)i * tabB; up.row_stride = plan.stride; up.sharp = p.sharp; up.bright = p.bright;
         up.active = Bi; up.img = e->img; up.chan_stride = e->cfg.image_size * e->cfg.image_size;
-        if (noisy) { up.noise_rows = noise_dev + (size_t)i * tabB; up.noise_step = (uint32_t)i; }
+        if (plan.noise) { up.noise_rows = noise_dev + (size_t)i * tabB; up.noise_step = (uint32_t)i; }
         // a step at which no running request is shaped and guided needs neither the statistics nor the SHAPE flavour: it would take `combine` for every
         // request, which the NOISE flavour does with one table less to read
-        if (stats_step[(size_t)i]) {       // (P, Q) of the requests shaped at this step, before the step reads them
+        if (st.stats) {       // (P, Q) of the requests shaped at this step, before the step reads them
             up.shape_rows = shape_dev; up.shape_pq = e->shape_pq; up.shape_mom = any_mom ? e->shape_mom : nullptr;
             GuidanceStatsParams gp{};
             gp.cond = e->io_out; gp.unc_base = e->io_out + (size_t)Bi * e->img; gp.mom = up.shape_mom; gp.rows = up.rows; gp.shape_rows = shape_dev;
-            gp.row_stride = p.stride; gp.active = Bi; gp.img = e->img; gp.pq = e->shape_pq; gp.sums = e->shape_sums;
+            gp.row_stride = plan.stride; gp.active = Bi; gp.img = e->img; gp.pq = e->shape_pq; gp.sums = e->shape_sums;
             ProfScope ps(e, KC_UPDATE, s);
             launch_guidance_stats(gp, s);
         }
         {
             ProfScope ps(e, KC_UPDATE, s);
-            launch_sampler_step(up, p.path_step, s, guided);
+            launch_sampler_step(up, p.path_step, s, plan.slots);
         }
         // (the uniform entries: every sample is at its last level together, and an inner step has just stored its prediction to x0_prev)
         SNAP("step.out", e->io_out, ST_F32, s, 2 * B, e->img); SNAP("step.x0", last ? p.out_latent : e->x0_prev, ST_F32, s, B, e->img);
@@ -767,24 +665,49 @@ int run_sampler(tld_engine* e, const SamplePlan& p, hipStream_t s) {
     return TLD_OK;
 }
 
-// tld_sample / tld_sample_from after their own checks: one record and one coefficient table for the whole batch; noise row i is level i
+// Every sampler entry: check, the engine's state, plan, run.  The uniform entries have tested their pointers before the checks, the others test them here.
+int sample_requests(tld_engine* e, SampleCall& call, const SampleOperands& ops, void* hip_stream) {
+    // the records first: their checks need no engine and no device
+    if (SampleRefusal r = sample_call_check(call)) return fail(r.code, "%s", r.msg.c_str());
+    if (!e || !ops.noise || !ops.labels || !ops.out_latent) return fail(TLD_ERR_INVALID, "null argument");
+    if (!e->finalized) return fail(TLD_ERR_STATE, "weights not finalized");
+    call.guidance_skip = e->guidance_skip; call.max_batch = e->cfg.max_batch;
+    if (SampleRefusal r = sample_plan(call, e->plan)) return fail(r.code, "%s", r.msg.c_str());
+    DeviceGuard dg(e->cfg.device_id);
+    PathScope paths(e);                                       // (debug: the launch paths are recorded; the requests entries keep no stage)
+    return run_sampler(e, e->plan, call, ops, static_cast<hipStream_t>(hip_stream));
+}
+
+SampleOperands sample_operands(const void* noise, const void* init_latent, const void* mask, const void* labels, const void* neg_labels, float sharp_f,
+                               float bright_f, void* out_latent, void* trace_x0, void* trace_xt, int path_step, int path_start, bool keep_stages) {
+    return SampleOperands{static_cast<const float*>(noise), static_cast<const float*>(init_latent), static_cast<const float*>(mask),
+                          static_cast<const float*>(labels), static_cast<const float*>(neg_labels), sharp_f, bright_f, static_cast<float*>(out_latent),
+                          static_cast<float*>(trace_x0), static_cast<float*>(trace_xt), path_step, path_start, keep_stages};
+}
+
+// tld_sample / tld_sample_from after their pointer tests: one record and one coefficient table for the whole batch; noise row i is level i
 int run_uniform(tld_engine* e, const void* noise, const void* init_latent, const void* mask, float start_mix, const void* labels, const float* coeffs,
                 int n_levels, float class_guidance, float sharp_f, float bright_f, void* out_latent, int batch, void* trace_x0, void* trace_xt,
                 int path_step, void* hip_stream) {
-    if (!e->finalized) return fail(TLD_ERR_STATE, "weights not finalized");
-    if (batch <= 0 || 2 * batch > e->cfg.max_batch)
-        return fail(TLD_ERR_INVALID, "sampler batch %d needs max_batch >= %d (have %d)", batch, 2 * batch, e->cfg.max_batch);
-    if (n_levels < 2) return fail(TLD_ERR_INVALID, "need at least two noise levels");
-    DeviceGuard dg(e->cfg.device_id);
-    PathScope paths(e);
     const tld_sample_request rec{n_levels, class_guidance, start_mix, 0};
-    SamplePlan p{};
-    p.B = batch; p.n_max = n_levels; p.stride = 0; p.requests = &rec; p.coeffs = coeffs; p.Tn = n_levels;
-    p.noise = static_cast<const float*>(noise); p.init_latent = static_cast<const float*>(init_latent); p.mask = static_cast<const float*>(mask);
-    p.labels = static_cast<const float*>(labels); p.sharp = sharp_f; p.bright = bright_f;
-    p.out_latent = static_cast<float*>(out_latent); p.trace_x0 = static_cast<float*>(trace_x0); p.trace_xt = static_cast<float*>(trace_xt);
-    p.path_step = path_step; p.path_start = EP_START_MIX; p.keep_stages = true;
-    return run_sampler(e, p, static_cast<hipStream_t>(hip_stream));
+    SampleCall call{};
+    call.entry = SE_UNIFORM; call.B = batch; call.n_max = n_levels; call.stride = 0; call.requests = &rec; call.coeffs = coeffs;
+    call.has_mask = mask != nullptr; call.has_init = init_latent != nullptr;
+    SampleOperands ops = sample_operands(noise, init_latent, mask, labels, nullptr, sharp_f, bright_f, out_latent, trace_x0, trace_xt, path_step, EP_START_MIX, true);
+    return sample_requests(e, call, ops, hip_stream);
+}
+
+// the four tld_sample_requests* entries: a record and a coefficient table per request; guidance, noise_coeff + noise_keys and shape as the entry has them
+int run_requests(SampleEntry entry, tld_engine* e, const void* noise, const void* init_latent, const void* mask, const void* labels, const void* neg_labels,
+                 const tld_sample_request* requests, const float* coeffs, const float* guidance, const float* noise_coeff, const uint64_t* noise_keys,
+                 const float* shape, int n_max, float sharp_f, float bright_f, void* out_latent, int batch, void* trace_x0, void* trace_xt, void* hip_stream) {
+    SampleCall call{};
+    call.entry = entry; call.B = batch; call.n_max = n_max; call.stride = 1; call.requests = requests; call.coeffs = coeffs;
+    call.guidance = guidance; call.noise_coeff = noise_coeff; call.noise_keys = noise_keys; call.shape = shape;
+    call.has_mask = mask != nullptr; call.has_init = init_latent != nullptr; call.has_neg_labels = neg_labels != nullptr;
+    SampleOperands ops = sample_operands(noise, init_latent, mask, labels, neg_labels, sharp_f, bright_f, out_latent, trace_x0, trace_xt,
+                                         mask ? EP_UPDATE_REQ_MASK : EP_UPDATE_REQ, EP_START_MIX_REQ, false);
+    return sample_requests(e, call, ops, hip_stream);
 }
 
 }  // namespace
@@ -1154,145 +1077,34 @@ int tld_sample_from(tld_engine* e, const void* noise, const void* init_latent, c
                        trace_xt, mask ? EP_UPDATE_FROM_MASK : EP_UPDATE_FROM, hip_stream);
 }
 
-// the most conditioning token rows one tld_sample_requests call may need (distinct sigmas + label rows): at the 100 M width a row of cond.wq + cond.kv is
-// about 0.52 MB, so the grow-only tables stay near 0.5 GiB
-constexpr int kMaxRequestCondRows = 1024;
-
-// tld_sample_requests, and with `guided` tld_sample_requests_guided: `guidance` is then the HOST table [batch][n_max] that replaces the records' class_guidance.
-// `stochastic` (tld_sample_requests_stochastic): the guided call plus noise_coeff [batch][n_max] and noise_keys [batch]; a null `guidance` there stands for
-// the table of the records' class_guidance with no skipping, the 2 B_i batch of tld_sample_requests
-static int sample_requests(tld_engine* e, const void* noise, const void* init_latent, const void* mask, const void* labels, const void* neg_labels,
-                           const tld_sample_request* requests, const float* coeffs, const float* guidance, bool guided, int32_t n_max, float sharp_f,
-                           float bright_f, void* out_latent, int32_t batch, void* trace_x0, void* trace_xt, void* hip_stream,
-                           bool stochastic = false, const float* noise_coeff = nullptr, const uint64_t* noise_keys = nullptr,
-                           const GuidanceShape* shape = nullptr) {
-    // the records first: their checks need no engine and no device
-    if (!requests || !coeffs || batch <= 0 || (guided && !guidance)) return fail(TLD_ERR_INVALID, "null argument");
-    if (stochastic && !noise_coeff) return fail(TLD_ERR_INVALID, "null argument: noise_coeff");
-    if (stochastic && !noise_keys) return fail(TLD_ERR_INVALID, "null argument: noise_keys");
-    for (int b = 0; shape && b < batch; ++b)
-        if (const char* bad = guidance_shape_invalid(shape[b]))
-            return fail(TLD_ERR_INVALID, "request %d: shape (%g, %g, %g, %g): bad %s", b, (double)shape[b].eta_par, (double)shape[b].norm_r,
-                        (double)shape[b].beta, (double)shape[b].phi, bad);
-    if (mask && !init_latent) return fail(TLD_ERR_INVALID, "init_latent is required with a mask");
-    const int B = batch;
-    int n_neg = 0;
-    for (int b = 0; b < B; ++b) {
-        const tld_sample_request& r = requests[b];
-        if (r.n_levels < 2) return fail(TLD_ERR_INVALID, "request %d: need at least two noise levels (have %d)", b, r.n_levels);
-        if (r.n_levels > n_max) return fail(TLD_ERR_INVALID, "request %d: %d levels beside a coefficient table of n_max = %d", b, r.n_levels, n_max);
-        if (b > 0 && r.n_levels > requests[b - 1].n_levels)
-            return fail(TLD_ERR_INVALID, "request %d has %d levels after request %d with %d: the records must be ordered by non-increasing n_levels", b,
-                        r.n_levels, b - 1, requests[b - 1].n_levels);
-        if (!(r.start_mix > 0.0f && r.start_mix <= 1.0f)) return fail(TLD_ERR_INVALID, "request %d: start_mix %g outside (0, 1]", b, (double)r.start_mix);
-        if (!guided && !std::isfinite(r.class_guidance)) return fail(TLD_ERR_INVALID, "request %d: class_guidance is not finite", b);
-        for (int i = 0; guided && i < r.n_levels; ++i)
-            if (!std::isfinite(guidance[(size_t)b * n_max + i])) return fail(TLD_ERR_INVALID, "request %d: guidance of forward %d is not finite", b, i);
-        if (r.start_mix < 1.0f && !init_latent) return fail(TLD_ERR_INVALID, "request %d: init_latent is required with start_mix < 1", b);
-        if (r.has_negative) {
-            if (!neg_labels) return fail(TLD_ERR_INVALID, "request %d: has_negative without neg_labels", b);
-            ++n_neg;
-        }
-        for (int i = 0; stochastic && i < r.n_levels; ++i) {
-            const float en = noise_coeff[(size_t)b * n_max + i];
-            if (!(std::isfinite(en) && en >= 0.0f)) return fail(TLD_ERR_INVALID, "request %d: noise_coeff of forward %d is %g: expected finite and >= 0", b, i, (double)en);
-            if (i == r.n_levels - 1 && en != 0.0f)
-                return fail(TLD_ERR_INVALID, "request %d: noise_coeff of its final forward %d is %g: the final prediction takes no noise, expected 0", b, i, (double)en);
-        }
-    }
-    if (requests[0].n_levels != n_max) return fail(TLD_ERR_INVALID, "n_max = %d, but the longest request has %d levels", n_max, requests[0].n_levels);
-    if (!e || !noise || !labels || !out_latent) return fail(TLD_ERR_INVALID, "null argument");
-    if (!e->finalized) return fail(TLD_ERR_STATE, "weights not finalized");
-    if (!guided && 2 * batch > e->cfg.max_batch)
-        return fail(TLD_ERR_INVALID, "sampler batch %d needs max_batch >= %d (have %d)", batch, 2 * batch, e->cfg.max_batch);
-    // the stochastic entry always runs the slots flavour of the step: without a table it gets the records' guidance at every forward, no sample skipped
-    std::vector<float> own_guidance;
-    const bool skip = e->guidance_skip && !(stochastic && !guided);
-    if (stochastic && !guided) {
-        own_guidance.assign((size_t)B * n_max, 0.0f);
-        for (int b = 0; b < B; ++b)
-            for (int i = 0; i < requests[b].n_levels; ++i) own_guidance[(size_t)b * n_max + i] = requests[b].class_guidance;
-        guidance = own_guidance.data();
-    }
-    if (guided) {     // the largest model batch of the call: the requests still running plus those of them guided at that step
-        std::vector<int> slot((size_t)B);
-        for (int i = 0, Bi = B; i < n_max; ++i) {
-            while (requests[Bi - 1].n_levels <= i) --Bi;
-            const int mb = Bi + guided_slots(guidance, n_max, Bi, i, skip, slot.data());
-            if (mb > e->cfg.max_batch)
-                return fail(TLD_ERR_INVALID, "step %d runs %d requests and %d unconditional samples: needs max_batch >= %d (have %d)", i, Bi, mb - Bi, mb,
-                            e->cfg.max_batch);
-        }
-    }
-
-    // ---- the distinct float32 sigmas of every (request, step): requests that share a schedule share conditioning rows
-    std::vector<float> sig;                                   // in order of first use
-    std::unordered_map<uint32_t, int> sig_row;                // by bit pattern
-    std::vector<int> noise_idx((size_t)n_max * B, 0);
-    for (int i = 0; i < n_max; ++i)
-        for (int b = 0; b < B && requests[b].n_levels > i; ++b) {
-            const float sg = coeffs[((size_t)b * n_max + i) * 6 + 0];
-            uint32_t bits; memcpy(&bits, &sg, 4);
-            auto it = sig_row.find(bits);
-            if (it == sig_row.end()) { it = sig_row.emplace(bits, (int)sig.size()).first; sig.push_back(sg); }
-            noise_idx[(size_t)i * B + b] = it->second;
-        }
-    const int Tn = (int)sig.size(), T = Tn + B + 1 + n_neg;
-    if (T > kMaxRequestCondRows)
-        return fail(TLD_ERR_INVALID, "the call needs %d conditioning rows (%d distinct noise levels + %d labels + 1 + %d negative labels): at most %d", T, Tn,
-                    B, n_neg, kMaxRequestCondRows);
-    DeviceGuard dg(e->cfg.device_id);
-    PathScope paths(e);                                       // (debug: the launch paths are recorded; no stage of this entry is kept)
-    SamplePlan p{};
-    p.B = B; p.n_max = n_max; p.stride = 1; p.requests = requests; p.coeffs = coeffs; p.guidance = (guided || stochastic) ? guidance : nullptr; p.skip = skip; p.Tn = Tn; p.sig = sig.data(); p.noise_idx = noise_idx.data();
-    p.noise = static_cast<const float*>(noise); p.init_latent = static_cast<const float*>(init_latent); p.mask = static_cast<const float*>(mask);
-    p.labels = static_cast<const float*>(labels); p.neg_labels = static_cast<const float*>(neg_labels); p.sharp = sharp_f; p.bright = bright_f;
-    p.out_latent = static_cast<float*>(out_latent); p.trace_x0 = static_cast<float*>(trace_x0); p.trace_xt = static_cast<float*>(trace_xt);
-    p.path_step = mask ? EP_UPDATE_REQ_MASK : EP_UPDATE_REQ; p.path_start = EP_START_MIX_REQ; p.keep_stages = false;
-    if (stochastic) { p.noise_coeff = noise_coeff; p.noise_keys = noise_keys; p.shape = shape; }
-    return run_sampler(e, p, static_cast<hipStream_t>(hip_stream));
-}
-
 int tld_sample_requests(tld_engine* e, const void* noise, const void* init_latent, const void* mask, const void* labels, const void* neg_labels,
                         const tld_sample_request* requests, const float* coeffs, int32_t n_max, float sharp_f, float bright_f, void* out_latent,
                         int32_t batch, void* trace_x0, void* trace_xt, void* hip_stream) {
-    return sample_requests(e, noise, init_latent, mask, labels, neg_labels, requests, coeffs, nullptr, false, n_max, sharp_f, bright_f, out_latent, batch,
-                           trace_x0, trace_xt, hip_stream);
+    return run_requests(SE_REQUESTS, e, noise, init_latent, mask, labels, neg_labels, requests, coeffs, nullptr, nullptr, nullptr, nullptr, n_max, sharp_f,
+                        bright_f, out_latent, batch, trace_x0, trace_xt, hip_stream);
 }
 
 int tld_sample_requests_guided(tld_engine* e, const void* noise, const void* init_latent, const void* mask, const void* labels, const void* neg_labels,
                                const tld_sample_request* requests, const float* coeffs, const float* guidance, int32_t n_max, float sharp_f,
                                float bright_f, void* out_latent, int32_t batch, void* trace_x0, void* trace_xt, void* hip_stream) {
-    return sample_requests(e, noise, init_latent, mask, labels, neg_labels, requests, coeffs, guidance, true, n_max, sharp_f, bright_f, out_latent, batch,
-                           trace_x0, trace_xt, hip_stream);
+    return run_requests(SE_GUIDED, e, noise, init_latent, mask, labels, neg_labels, requests, coeffs, guidance, nullptr, nullptr, nullptr, n_max, sharp_f,
+                        bright_f, out_latent, batch, trace_x0, trace_xt, hip_stream);
 }
 
 int tld_sample_requests_stochastic(tld_engine* e, const void* noise, const void* init_latent, const void* mask, const void* labels, const void* neg_labels,
                                    const tld_sample_request* requests, const float* coeffs, const float* guidance, const float* noise_coeff,
                                    const uint64_t* noise_keys, int32_t n_max, float sharp_f, float bright_f, void* out_latent, int32_t batch,
                                    void* trace_x0, void* trace_xt, void* hip_stream) {
-    return sample_requests(e, noise, init_latent, mask, labels, neg_labels, requests, coeffs, guidance, guidance != nullptr, n_max, sharp_f, bright_f,
-                           out_latent, batch, trace_x0, trace_xt, hip_stream, true, noise_coeff, noise_keys);
+    return run_requests(SE_STOCHASTIC, e, noise, init_latent, mask, labels, neg_labels, requests, coeffs, guidance, noise_coeff, noise_keys, nullptr, n_max,
+                        sharp_f, bright_f, out_latent, batch, trace_x0, trace_xt, hip_stream);
 }
 
 int tld_sample_requests_shaped(tld_engine* e, const void* noise, const void* init_latent, const void* mask, const void* labels, const void* neg_labels,
                                const tld_sample_request* requests, const float* coeffs, const float* guidance, const float* noise_coeff,
                                const uint64_t* noise_keys, const float* shape, int32_t n_max, float sharp_f, float bright_f, void* out_latent, int32_t batch,
                                void* trace_x0, void* trace_xt, void* hip_stream) {
-    if (!shape) return fail(TLD_ERR_INVALID, "null argument: shape");
-    if ((noise_coeff == nullptr) != (noise_keys == nullptr)) return fail(TLD_ERR_INVALID, "noise_coeff and noise_keys come together (both NULL: no noise)");
-    if (batch <= 0 || n_max <= 0) return fail(TLD_ERR_INVALID, "need positive sizes (batch %d, n_max %d)", batch, n_max);
-    // without noise the step still runs the NOISE flavour (under the SHAPE flag where a request is shaped), on a table of zeros: nothing is drawn, nothing added
-    std::vector<float> no_coeff;
-    std::vector<uint64_t> no_keys;
-    if (!noise_coeff) {
-        no_coeff.assign((size_t)batch * n_max, 0.0f); no_keys.assign((size_t)batch, 0);
-        noise_coeff = no_coeff.data(); noise_keys = no_keys.data();
-    }
-    std::vector<GuidanceShape> rows((size_t)batch);
-    for (int b = 0; b < batch; ++b) rows[(size_t)b] = GuidanceShape{shape[4 * b], shape[4 * b + 1], shape[4 * b + 2], shape[4 * b + 3]};
-    return sample_requests(e, noise, init_latent, mask, labels, neg_labels, requests, coeffs, guidance, guidance != nullptr, n_max, sharp_f, bright_f,
-                           out_latent, batch, trace_x0, trace_xt, hip_stream, true, noise_coeff, noise_keys, rows.data());
+    return run_requests(SE_SHAPED, e, noise, init_latent, mask, labels, neg_labels, requests, coeffs, guidance, noise_coeff, noise_keys, shape, n_max,
+                        sharp_f, bright_f, out_latent, batch, trace_x0, trace_xt, hip_stream);
 }
 
 int tld_debug_guidance_shape(const float* cond_device, const float* unc_device, float* mom_device, const float* g, const float* shape, int32_t batch,

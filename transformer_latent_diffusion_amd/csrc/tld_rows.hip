@@ -17,6 +17,7 @@
 #include "tld_sampler_noise.h"    // the counter of the stochastic sampler's noise
 #include "tld_normal_device.h"    // philox_normals4
 #include <cstdlib>
+#include <type_traits>
 
 namespace tld {
 
@@ -1822,6 +1823,16 @@ void launch_tail_fold_debug_row(float* row, const resid_t* x, const float* bias,
 
 namespace {
 bool aligned16(const void* a) { return (reinterpret_cast<uintptr_t>(a) & 15) == 0; }
+// a runtime boolean, or an index below 4, as a compile-time constant: f(std::bool_constant<b>{}), f(std::integral_constant<int, i>{})
+template <class F> void with_bool(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <class F> void with_index4(int i, F&& f) {
+    switch (i) {
+        case 0: f(std::integral_constant<int, 0>{}); break;
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        default: f(std::integral_constant<int, 3>{}); break;
+    }
+}
 }
 
 void launch_sampler_step(const SamplerStepParams& p, int path, hipStream_t s, bool slots) {
@@ -1832,37 +1843,16 @@ void launch_sampler_step(const SamplerStepParams& p, int path, hipStream_t s, bo
     const int threads = vec ? n / 4 : n;
     const dim3 grid((threads + 255) / 256), block(256);
     note_path(path);
-    if (slots && p.noise_rows && p.shape_rows) {
-        if (p.mask) {
-            if (vec) hipLaunchKernelGGL((sampler_step_kernel<true, 4, true, true, true>), grid, block, 0, s, p);
-            else hipLaunchKernelGGL((sampler_step_kernel<true, 1, true, true, true>), grid, block, 0, s, p);
-        } else {
-            if (vec) hipLaunchKernelGGL((sampler_step_kernel<false, 4, true, true, true>), grid, block, 0, s, p);
-            else hipLaunchKernelGGL((sampler_step_kernel<false, 1, true, true, true>), grid, block, 0, s, p);
-        }
-    } else if (slots && p.noise_rows) {
-        if (p.mask) {
-            if (vec) hipLaunchKernelGGL((sampler_step_kernel<true, 4, true, true>), grid, block, 0, s, p);
-            else hipLaunchKernelGGL((sampler_step_kernel<true, 1, true, true>), grid, block, 0, s, p);
-        } else {
-            if (vec) hipLaunchKernelGGL((sampler_step_kernel<false, 4, true, true>), grid, block, 0, s, p);
-            else hipLaunchKernelGGL((sampler_step_kernel<false, 1, true, true>), grid, block, 0, s, p);
-        }
-    } else if (slots) {
-        if (p.mask) {
-            if (vec) hipLaunchKernelGGL((sampler_step_kernel<true, 4, true>), grid, block, 0, s, p);
-            else hipLaunchKernelGGL((sampler_step_kernel<true, 1, true>), grid, block, 0, s, p);
-        } else {
-            if (vec) hipLaunchKernelGGL((sampler_step_kernel<false, 4, true>), grid, block, 0, s, p);
-            else hipLaunchKernelGGL((sampler_step_kernel<false, 1, true>), grid, block, 0, s, p);
-        }
-    } else if (p.mask) {
-        if (vec) hipLaunchKernelGGL((sampler_step_kernel<true, 4>), grid, block, 0, s, p);
-        else hipLaunchKernelGGL((sampler_step_kernel<true, 1>), grid, block, 0, s, p);
-    } else {
-        if (vec) hipLaunchKernelGGL((sampler_step_kernel<false, 4>), grid, block, 0, s, p);
-        else hipLaunchKernelGGL((sampler_step_kernel<false, 1>), grid, block, 0, s, p);
-    }
+    // the flavours nest: plain, SLOT, SLOT + NOISE, SLOT + NOISE + SHAPE
+    const int flavour = !slots ? 0 : !p.noise_rows ? 1 : !p.shape_rows ? 2 : 3;
+    with_bool(p.mask != nullptr, [&](auto mask) {
+        with_bool(vec, [&](auto v4) {
+            with_index4(flavour, [&](auto f) {
+                constexpr int F = decltype(f)::value;
+                hipLaunchKernelGGL((sampler_step_kernel<decltype(mask)::value, decltype(v4)::value ? 4 : 1, (F >= 1), (F >= 2), (F >= 3)>), grid, block, 0, s, p);
+            });
+        });
+    });
 }
 
 void launch_guidance_stats(const GuidanceStatsParams& p, hipStream_t s) {

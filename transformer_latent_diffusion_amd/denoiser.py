@@ -490,7 +490,7 @@ class Denoiser:
             for k, b in enumerate(order):
                 gtab[k, :counts[b]] = steps[b]
 
-            def model_batch(skip):       # the planning the engine repeats in C
+            def model_batch(skip):       # the largest step of the plan the engine makes (csrc/tld_sample_plan.h; held against it on the CPU)
                 if not B:
                     return 0
                 sc = [counts[b] for b in order]
@@ -507,27 +507,20 @@ class Denoiser:
             for k, b in enumerate(order):
                 etab[k, :counts[b]] = ecs[b]
                 ktab[k] = keys[b]
+        kp = None if ktab is None else ktab.ctypes.data_as(C.POINTER(C.c_uint64))
+        # the entry and what it takes between the coefficient table and n_max
         if shp is not None:              # (noise_coeff / noise_keys NULL: no noise; guidance NULL: as in the stochastic entry)
             stab = np.ascontiguousarray([shp[b] for b in order], dtype=np.float32).reshape(B, 4)
-            kp = None if ktab is None else ktab.ctypes.data_as(C.POINTER(C.c_uint64))
-            return self._run_sampler(noise, labels, n_max, trace, lambda h, B, eps, z0, m, lab, ng, out, tx0, txt, stream: _lib.check(
-                _lib.lib().tld_sample_requests_shaped(h, eps, z0, m, lab, ng, recs, fp(table), fp(gtab), fp(etab), kp, fp(stab), n_max, float(sharp_f),
-                                                      float(bright_f), out, B, tx0, txt, stream), "tld_sample_requests_shaped"),
-                model_batch=model_batch, **common)
-        if ecs is not None:              # (guidance NULL: the records' scales on the CFG-doubled batch)
-            return self._run_sampler(noise, labels, n_max, trace, lambda h, B, eps, z0, m, lab, ng, out, tx0, txt, stream: _lib.check(
-                _lib.lib().tld_sample_requests_stochastic(h, eps, z0, m, lab, ng, recs, fp(table), fp(gtab), fp(etab),
-                                                          ktab.ctypes.data_as(C.POINTER(C.c_uint64)), n_max, float(sharp_f), float(bright_f), out, B,
-                                                          tx0, txt, stream), "tld_sample_requests_stochastic"),
-                model_batch=model_batch, **common)
-        if steps is not None:
-            return self._run_sampler(noise, labels, n_max, trace, lambda h, B, eps, z0, m, lab, ng, out, tx0, txt, stream: _lib.check(
-                _lib.lib().tld_sample_requests_guided(h, eps, z0, m, lab, ng, recs, fp(table), fp(gtab), n_max, float(sharp_f), float(bright_f), out, B,
-                                                      tx0, txt, stream), "tld_sample_requests_guided"),
-                model_batch=model_batch, **common)
+            entry, extra = "tld_sample_requests_shaped", (fp(gtab), fp(etab), kp, fp(stab))
+        elif ecs is not None:            # (guidance NULL: the records' scales on the CFG-doubled batch)
+            entry, extra = "tld_sample_requests_stochastic", (fp(gtab), fp(etab), kp)
+        elif steps is not None:
+            entry, extra = "tld_sample_requests_guided", (fp(gtab),)
+        else:
+            entry, extra = "tld_sample_requests", ()
         return self._run_sampler(noise, labels, n_max, trace, lambda h, B, eps, z0, m, lab, ng, out, tx0, txt, stream: _lib.check(
-            _lib.lib().tld_sample_requests(h, eps, z0, m, lab, ng, recs, fp(table), n_max, float(sharp_f), float(bright_f), out, B, tx0, txt, stream),
-            "tld_sample_requests"), **common)
+            getattr(_lib.lib(), entry)(h, eps, z0, m, lab, ng, recs, fp(table), *extra, n_max, float(sharp_f), float(bright_f), out, B, tx0, txt, stream),
+            entry), model_batch=model_batch, **common)
 
     # ---- test / bench hooks -----------------------------------------------------------------------------
     # launch paths of tld_engine_debug_paths, by bit number (include/tld_hip.h; None: a bit no default engine sets).  "tail folded" (out_proj folded into

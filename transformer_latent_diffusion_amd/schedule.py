@@ -200,8 +200,8 @@ def step_coefficients(noise_levels: Sequence[float], use_ddpm_plus: bool = True,
     return tab.astype(np.float32)
 
 
-# ---- B requests in one sampler call (tld_sample_requests): the host planning the engine repeats in C ------------------
-REQUEST_ROW_CAP = 1024      # most conditioning rows one call may need: kMaxRequestCondRows in csrc/tld_engine.hip
+# ---- B requests in one sampler call (tld_sample_requests): the host planning, held against the engine's (csrc/tld_sample_plan.h) by tests/test_sample_plan_host.py ----
+REQUEST_ROW_CAP = 1024      # most conditioning rows one call may need: kMaxRequestCondRows in csrc/tld_sample_plan.h
 
 
 def request_order(level_counts: Sequence[int]) -> List[int]:
