@@ -5,8 +5,8 @@ tests/test_gpu_weight_refresh.py reads every image through the stage hook and co
 
 ``weight_images(state_dict, cfg, mode)`` returns {stage name: array} for the images an engine of that mode holds, under the names of
 include/tld_hip.h: fp32 images as float32, bf16 images as their uint16 bit patterns, e4m3 codes and E8M0 scales as uint8 (scales in logical
-[rows, K / 32] order).  ``as_read`` turns one into the float32 array the stage hook returns for it.  ``engine_mode`` restates which images
-tld_engine_create / tld_engine_set_gemm_dtype choose for a configuration.
+[rows, K / 32] order).  ``as_read`` turns one into the float32 array the stage hook returns for it.  ``engine_mode`` says which images
+tld_engine_create / tld_engine_set_gemm_dtype choose for a configuration (the restatement lives in tests/body_plan_ref.py).
 """
 import ctypes as C
 
@@ -102,16 +102,11 @@ def dequant_mx8(q, s):
 
 
 def engine_mode(cfg, env=None, gemm_dtype="bf16"):
-    """Which images an engine holds (tld_engine_create with the switches in ``env``, then tld_engine_set_gemm_dtype)."""
-    env = env or {}
-    on = lambda k: int(env.get(k, "1")) != 0
-    d, hid = cfg.embed_dim, cfg.mlp_multiplier * cfg.embed_dim
-    ntok = (cfg.image_size // cfg.patch_size) ** 2
+    """Which images an engine holds (tld_engine_create with the switches in ``env``, then tld_engine_set_gemm_dtype): the plan of body_plan_ref.py."""
+    import body_plan_ref as B
     fp8 = gemm_dtype == "fp8"
-    fold_ln1 = on("TLD_FOLD_LN1") and d % 192 == 0 and d // 96 <= 8 and (3 * d) % 256 == 0 and not fp8
-    fold_ln3 = on("TLD_FOLD_LN3") and hid % 256 == 0 and d in (768, 512, 256) and not fp8
-    return dict(fp8=fp8, fold_ln1=fold_ln1, fold_ln3=fold_ln3, fold_tail=on("TLD_FOLD_TAIL") and not fp8,
-                packed_qkv=on("TLD_FUSE_QKV_ATTN") and fold_ln1 and ntok == 256 and d % 128 == 0)
+    p = B.plan(B.shape(cfg), B.switches(env), fp8, 0, 1, 256)
+    return dict(fp8=fp8, fold_ln1=p.fold_ln1, fold_ln3=p.fold_ln3, fold_tail=p.fold_tail_held, packed_qkv=p.fused_qa)
 
 
 # stage name of an fp32 copy outside the blocks -> state_dict key

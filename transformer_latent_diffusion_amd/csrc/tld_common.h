@@ -381,7 +381,7 @@ void launch_embed(const EmbedParams& p, hipStream_t s);
 void launch_layernorm_bf16(const resid_t* x, const float* g, const float* b, bf16* out, int M, int d,
                            hipStream_t s);
 // the same rows straight into the fp8 GEMM's operand format: e4m3 [M,d] + E8M0 scales [d/128][M][4]  (d % 256 == 0)
-bool layernorm_mx8_supported(int d);
+// (widths: layernorm_mx8_supported, tld_body_plan.h)
 void launch_layernorm_mx8(const resid_t* x, const float* g, const float* b, uint8_t* out8, uint8_t* scale8, int M, int d,
                           hipStream_t s);
 
@@ -410,9 +410,8 @@ struct CrossRowParams {
     int batch, ntok, d, heads;
 };
 void launch_cross_row(const CrossRowParams& p, hipStream_t s);
-bool cross_row_supports_ln3_stats(int d);
-// split-K finish of the low-latency down projection: x += bias + sum of the fp32 slices (+ LayerNorm-1 partial sums); d = 768 / 384
-bool splitk_resid_supported(int d);
+// (which widths write LN3 statistics: cross_row_supports_ln3_stats, tld_body_plan.h)
+// split-K finish of the low-latency down projection: x += bias + sum of the fp32 slices (+ LayerNorm-1 partial sums); d = 768 / 384 (splitk_resid_supported, tld_body_plan.h)
 void launch_splitk_resid(const float* parts, int nsplit, size_t slice_stride, const float* bias, resid_t* x, float2* stats_out, int M, int d, hipStream_t s);
 
 struct TailParams {

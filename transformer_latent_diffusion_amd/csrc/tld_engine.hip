@@ -6,6 +6,7 @@
 // with no host round trip.  See DESIGN.md for the data layout and per-kernel roofline notes.
 #include "../../include/tld_hip.h"
 #include "tld_common.h"
+#include "tld_body_plan.h"
 #include "tld_host.h"
 #include "tld_refresh.h"
 #include "tld_sample_plan.h"
@@ -36,14 +37,21 @@ enum KClass { KC_GEMM_QKV = 0, KC_GEMM_UP, KC_GEMM_DOWN, KC_ATTN, KC_CROSS, KC_D
 
 }  // namespace
 
-struct tld_engine : DeviceArena {      // (pad = 256: every allocation of this engine carries 256 bytes of over-read margin)
-    tld_engine() { pad = 256; }
+struct tld_engine : DeviceArena, BodyShape {      // (pad = 256: every allocation of this engine carries 256 bytes of over-read margin; d, L, H, grid, ntok, ...: body_shape(cfg))
+    tld_engine() : BodyShape{} { pad = 256; }
     tld_config cfg{};
-    int d = 0, L = 0, H = 0, ntok = 0, grid = 0, pd = 0, hid = 0, img = 0, ne = 0, text = 0;
+    BodySwitches sw;                    // the environment, read once at create (tld_engine_set_gemm_dtype(1) writes three of them: body_switches_set_dtype)
+    BodyPlan mode;                      // this engine's mode (tld_body_plan.h): computed at create, again when a setter changes an input; what is HELD is frozen at finalize
     bool finalized = false;
-    bool fuse_dwconv = true;            // TLD_FUSE_DWCONV=0 selects the two-kernel path (A/B testing)
-    bool fp8 = false;                   // QKV / MLP GEMMs on MX-fp8 operands (BASELINE config C4); set before finalize
-    bool fp8_fused = true;              // TLD_FP8_FUSED=0: separate quantisation passes instead of quantising producers (A/B testing)
+    // the buffers whose existence the plan decides (finalize; split-K: tld_engine_set_low_latency).  Nothing below asks whether one is null: the plan says what runs.
+    struct ModeBuffers {
+        uint32_t* seam = nullptr;       // 32 x 32 grids: the seam rows of the hidden tensor between the fused up-projection and launch_dwconv_seam
+        uint32_t* pair_park = nullptr;  // one slot of kPairSlotDwords per workgroup a two-head QKV + attention launch can have (plan.pair_slots)
+        bf16* out_fold_hl = nullptr;    // out_proj folded into the last block's down projection: [Wout | Wout Wd] as a split bf16 pair [2][pdp][d + hid] ...
+        float* out_fold_b = nullptr;    // ... and Wout bd + bo [pd] (tld_tail_fold_math.h)
+        float* splitk = nullptr;        // [slices][max rows][d] fp32 slices of the low-latency down projection (it outlives its class: clearing the class frees nothing)
+        int splitk_slices = 0;          // ... of the class set last (the buffer has room for at least that many)
+    } mb;
     uint8_t *a8 = nullptr, *as8 = nullptr;   // fp8 mode: quantised A operand [M, hid] and its block scales [hid/128][M][4]
     std::map<std::string, HostTensor> host;
 
@@ -54,9 +62,6 @@ struct tld_engine : DeviceArena {      // (pad = 256: every allocation of this e
           *plin_b = nullptr, *pln2_w = nullptr, *pln2_b = nullptr, *pos = nullptr, *out_w = nullptr,
           *out_b = nullptr;
     bf16* out_w_hl = nullptr;           // out_proj weight as a split bf16 pair [2][pd][d] (tail_mfma_kernel)
-    bool fold_tail = true;              // TLD_FOLD_TAIL=0: the last block's down projection and out_proj stay two kernels (A/B testing)
-    bf16* out_fold_hl = nullptr;        // out_proj folded into the last block's down projection: [Wout | Wout Wd] as a split bf16 pair [2][pdp][d + hid] ...
-    float* out_fold_b = nullptr;        // ... and Wout bd + bo [pd] (tld_tail_fold_math.h; null: no fold in this engine's mode)
     bf16* plin_w_hl = nullptr;          // patch-embedding Linear weight as a split bf16 pair [2][d][pd] (embed_mfma_kernel)
     std::vector<Layer> layers;
     const float **tab_kv_w = nullptr, **tab_q_w = nullptr, **tab_n2_w = nullptr, **tab_n2_b = nullptr;   // [L] device tables
@@ -66,21 +71,10 @@ struct tld_engine : DeviceArena {      // (pad = 256: every allocation of this e
     // activations (sized for cfg.max_batch)
     resid_t* x = nullptr;
     resid_t* x_half = nullptr;         // patch embedding of the un-doubled batch (CFG layer-0 sharing)
-    bool share_l0 = true;              // TLD_SHARE_L0=0 disables (A/B testing)
-    bool guidance_skip = true;         // TLD_GUIDANCE_SKIP=0: tld_sample_requests_guided runs the unconditional sample of an unguided step too (A/B testing)
     int64_t rows_cond = 0, rows_uncond = 0;     // model samples the last sampler call enqueued (tld_engine_sample_rows)
-    bool fold_ln1 = true;              // TLD_FOLD_LN1=0: separate LayerNorm-1 kernel (A/B testing)
-    bool low_latency = false;          // tld_engine_set_low_latency: capacity class for small batches (round 5) -- the down projection runs as split-K (see run_body)
-    float* splitk = nullptr;           // [ll_split][max rows][d] fp32 slices of it
-    int ll_split = 0;                  // K-splits of the low-latency down projection (4 or 8, from the engine's capacity: lowlat_split)
-    bool fuse_qkv_attn = true;         // 256-token grids with the LayerNorm-1 fold: QKV GEMM + self-attention as ONE kernel per (sample, head) (TLD_FUSE_QKV_ATTN=0: two kernels)
-    int qkv_pair = 1;                  // TLD_QKV_ATTN_PAIR: that kernel on two-head tiles (EPI_QKV_ATTN2): 0 never, 1 where plan_qkv_pair says so, 2 wherever the shape permits (test hook)
-    uint32_t* pair_park = nullptr;     // one slot of kPairSlotDwords per workgroup such a launch can have (min(head pairs of max_batch, CUs)); null: no pair form in this engine
     float2* ln_stats = nullptr;        // [M][kLnSlots] row partial sums of the residual stream (embed / down GEMM -> QKV GEMM)
-    bool fold_ln3 = true;              // TLD_FOLD_LN3=0: cross_row writes LN3(x) and the up-projection reads it (A/B testing)
     float2* row_stats = nullptr;       // [M] (mean, rstd) of the residual rows, cross_row -> up-projection epilogue
     bf16 *xn = nullptr, *qk = nullptr, *vt = nullptr, *att = nullptr, *hid1 = nullptr, *hid2 = nullptr;
-    uint32_t* seam = nullptr;            // 32 x 32 grids: the seam rows of the hidden tensor between the fused up-projection and launch_dwconv_seam
     float *io_x = nullptr, *io_sigma = nullptr, *io_label = nullptr, *io_out = nullptr;
     float *xt = nullptr, *x0_prev = nullptr;
     int* rows_dev = nullptr;           // tld_denoiser_forward's noise_row / label_row tables [2 max_batch]
@@ -179,88 +173,45 @@ struct ProfScope {
     ~ProfScope() { if (on) hipEventRecord(b, s); }
 };
 
-// block 0's MLP hidden tensors (bf16 [M, hid]; debug only, own buffers: they are mlp_multiplier times a residual-stream stage): "blk0_hid" = after the
-// depthwise conv + GELU on whichever path ran, "blk0_hid_pre" = the up-projection's output where it exists in HBM (the two-kernel path)
-// K-splits of the low-latency down projection: class 1 = four (engines of at most 4096 token rows), class 2 = eight (at most 1024 token rows: one or two images per CFG call, the
-// one-prompt-per-call pattern).  Round 6: eight splits take a one-image generate from 36.4 to 33.4 ms, but cost 6-8 ms at four or five images (twice the work items of 6 K-steps each
-// no longer fit one round of workgroups, and the finishing kernel reads twice the slices) -- hence two classes, each chosen by the CALLER for the engine and each with its own fp32
-// summation order: inside a class results are bit-identical across batch sizes.
-constexpr int kLowLatMaxRows2 = 1024;
-constexpr int kLowLatMaxRows = 4096;        // capacity of the low-latency class (token rows = max_batch x tokens): beyond it the tiles fill the chip by themselves
-
 // ---- stage hook (StageStore, tld_host.h): this engine's names, sizes and poison step ---------------------------------------------------
 #define SNAP(...) do { if (e->dbg_keep) { if (int _r = e->stages.copy(__VA_ARGS__)) return _r; } } while (0)
 inline std::string blk_name(int l, const char* n) { return "blk" + std::to_string(l) + "." + n; }
 
-// which of the forward's size-independent branches this engine takes (run_body and the snapshot reservation agree through these)
-inline bool eng_fused_qa(const tld_engine* e) { return e->fuse_qkv_attn && e->fold_ln1 && !e->fp8; }
-// ... on two-head tiles for a launch of `samples` samples: the engine holds the pair-ordered images and the slots (finalize: heads even, not fp8, a batch <= max_batch
-// that takes them), is not a low-latency class, and the switch and plan_qkv_pair (tld_qkv_pair_plan.h) agree
-inline bool eng_qkv_pair(const tld_engine* e, int samples) {
-    if (!eng_fused_qa(e) || !e->pair_park || e->low_latency) return false;
-    return e->qkv_pair == 2 || (e->qkv_pair == 1 && plan_qkv_pair(samples, e->H, device_cu_count()));
+// the engine's mode from its inputs (create, the two setters); after finalize what is held stays
+inline void replan(tld_engine* e, bool fp8, int cls) {
+    e->mode = plan_body(*e, e->sw, fp8, cls, e->cfg.max_batch, device_cu_count(), e->finalized ? &e->mode : nullptr);
 }
-inline bool eng_fuse_dw(const tld_engine* e) { return e->fuse_dwconv && (e->grid == 16 || (e->grid == 32 && e->seam)) && e->hid % 256 == 0; }
 
 // set_debug(1): memory for every snapshot a forward of max_batch samples takes (the names of the SNAP calls in run_body and the samplers),
 // and the names of what is read in place: the conditioning tables and the GEMM operands as the engine holds them
 int reserve_snapshots(tld_engine* e) {
-    const size_t B = (size_t)e->cfg.max_batch, M = B * e->ntok, d = e->d, hid = e->hid;
-#define RES(name, bytes) do { if (int _r = e->stages.reserve(name, bytes)) return _r; } while (0)
-    const size_t rs = sizeof(resid_t);
-    RES("tokens0", M * d * rs); RES("out", B * e->img * 4);
-    for (const char* n : {"step.x_t", "step.x0_prev", "step.x0", "step.x_next"}) RES(n, B * e->img * 4);
-    RES("step.out", B * e->img * 4);
-    for (int l = 0; l < e->L; ++l) {
-        for (const char* n : {"x_in", "ca"}) RES(blk_name(l, n), M * d * rs);
-        RES(blk_name(l, "mlp"), M * d * ((l + 1 == e->L && e->out_fold_hl) ? 4 : rs));      // (the folded tail: the last block's row is an fp32 debug evaluation)
-        RES(blk_name(l, "att"), M * d * 2); RES(blk_name(l, "sa"), M * d * 4);
-        if (e->fold_ln1) RES(blk_name(l, "ln1"), M * kLnSlots * 8); else RES(blk_name(l, "xn1"), M * d * 2);
-        if (!eng_fused_qa(e)) { RES(blk_name(l, "qk"), M * 2 * d * 2); RES(blk_name(l, "vt"), M * d * 2); }
-        if (e->fold_ln3) RES(blk_name(l, "stats"), M * 8); else RES(blk_name(l, "xn3"), M * d * 2);
-        if (!eng_fuse_dw(e)) RES(blk_name(l, "hid_pre"), M * hid * 2);
-        if (e->fp8) {   // the three A operands as the GEMMs read them: e4m3 codes, and the E8M0 scales of the call's rows
-            RES(blk_name(l, "a8_qkv.q"), M * d); RES(blk_name(l, "a8_qkv.s"), M * d / 32);
-            RES(blk_name(l, "a8_up.q"), M * d); RES(blk_name(l, "a8_up.s"), M * d / 32);
-            RES(blk_name(l, "a8_down.q"), M * hid); RES(blk_name(l, "a8_down.s"), M * hid / 32);
-        }
-        RES(blk_name(l, "hid"), M * hid * 2);
-        if (e->splitk) RES(blk_name(l, "splitk"), (size_t)e->ll_split * M * d * 4);
-    }
-#undef RES
+    const BodyPlan& P = e->mode;
+    const size_t d = e->d, hid = e->hid;
+    for (const BodyStage& st : body_stages(*e, P, e->cfg.max_batch, e->mb.splitk_slices))
+        if (int rc = e->stages.reserve(st.name, st.bytes)) return rc;
+    const std::vector<BodyImage> images = body_block_images(*e, P);
     for (int l = 0; l < e->L; ++l) {
         const Layer& Ly = e->layers[l];
         StageStore& S = e->stages;
-        if (eng_fused_qa(e)) {      // rows in the fused kernel's packed order: the reader needs d and the head count to undo it
+        if (P.fused_qa) {      // rows in the fused kernel's packed order: the reader needs d and the head count to undo it
             const struct { const char* n; const void* p; int dt; int64_t cols; } packed[] = {{"wqkv", Ly.qkv_wp, ST_BF16, (int64_t)d}, {"qkv_c1", Ly.qkv_c1p, ST_F32, 1}, {"qkv_b1", Ly.qkv_b1p, ST_F32, 1}};
             for (const auto& q : packed)
                 if (Stage* st = S.ref(blk_name(l, q.n), q.p, q.dt, 3 * d, q.cols, 1, 1, 0, SL_QKV_ROWS)) { st->extra.d = e->d; st->extra.heads = e->H; }
         } else {
-            S.ref(blk_name(l, "wqkv"), e->fold_ln1 ? Ly.qkv_wf : Ly.qkv_w, ST_BF16, 3 * d, d);
+            S.ref(blk_name(l, "wqkv"), P.fold_ln1 ? Ly.qkv_wf : Ly.qkv_w, ST_BF16, 3 * d, d);
             S.ref(blk_name(l, "qkv_c1"), Ly.qkv_c1, ST_F32, 3 * d); S.ref(blk_name(l, "qkv_b1"), Ly.qkv_b1, ST_F32, 3 * d);
         }
-        S.ref(blk_name(l, "wup"), e->fold_ln3 ? Ly.up_wf : Ly.up_w, ST_BF16, hid, d);
+        S.ref(blk_name(l, "wup"), P.fold_ln3 ? Ly.up_wf : Ly.up_w, ST_BF16, hid, d);
         S.ref(blk_name(l, "up_c1"), Ly.up_c1, ST_F32, hid); S.ref(blk_name(l, "up_b1"), Ly.up_b1, ST_F32, hid);
         S.ref(blk_name(l, "wdown"), Ly.down_w, ST_BF16, d, hid);
-        if (e->fp8) {   // the weights as held: e4m3 + E8M0, dequantised on read
+        if (P.fp8) {   // the weights as held: e4m3 + E8M0, dequantised on read
             if (Stage* st = S.ref(blk_name(l, "wqkv"), Ly.qkv_w8, ST_MX8W, 3 * d, d)) st->aux = Ly.qkv_s8;
             if (Stage* st = S.ref(blk_name(l, "wup"), Ly.up_w8, ST_MX8W, hid, d)) st->aux = Ly.up_s8;
             if (Stage* st = S.ref(blk_name(l, "wdown"), Ly.down_w8, ST_MX8W, d, hid)) st->aux = Ly.down_s8;
         }
-        // every other image of the block, in storage order (a null pointer -- an image this mode does not hold -- gets no name)
-        const struct { const char* n; const void* p; int dt; int64_t s0, s1, s2, s3; } imgs[] = {
-            {"kv_w", Ly.kv_w, ST_F32, 2 * e->d, e->d, 1, 1}, {"q_w", Ly.q_w, ST_F32, e->d, e->d, 1, 1}, {"up_b", Ly.up_b, ST_F32, e->hid, 1, 1, 1},
-            {"dw_b", Ly.dw_b, ST_F32, e->hid, 1, 1, 1}, {"down_b", Ly.down_b, ST_F32, e->d, 1, 1, 1}, {"n1_w", Ly.n1_w, ST_F32, e->d, 1, 1, 1},
-            {"n1_b", Ly.n1_b, ST_F32, e->d, 1, 1, 1}, {"n2_w", Ly.n2_w, ST_F32, e->d, 1, 1, 1}, {"n2_b", Ly.n2_b, ST_F32, e->d, 1, 1, 1},
-            {"n3_w", Ly.n3_w, ST_F32, e->d, 1, 1, 1}, {"n3_b", Ly.n3_b, ST_F32, e->d, 1, 1, 1},
-            {"qkv_wf", Ly.qkv_wf, ST_BF16, 3 * e->d, e->d, 1, 1}, {"qkv_c1", Ly.qkv_c1, ST_F32, 3 * e->d, 1, 1, 1}, {"qkv_b1", Ly.qkv_b1, ST_F32, 3 * e->d, 1, 1, 1},
-            {"qkv_wp", Ly.qkv_wp, ST_BF16, 3 * e->d, e->d, 1, 1}, {"qkv_c1p", Ly.qkv_c1p, ST_F32, 3 * e->d, 1, 1, 1}, {"qkv_b1p", Ly.qkv_b1p, ST_F32, 3 * e->d, 1, 1, 1},
-            {"dw_w9c", Ly.dw_w9c, ST_F32, 9, e->hid, 1, 1}, {"dw_w9c_half", Ly.dw_w9c_half, ST_F32, 9, e->hid, 1, 1}, {"dw_b_half", Ly.dw_b_half, ST_F32, e->hid, 1, 1, 1},
-            {"dw_wpk", Ly.dw_wpk, ST_BF16, 3, 4, e->hid, 2},
-            {"qkv_w8", Ly.qkv_w8, ST_U8, 3 * e->d, e->d, 1, 1}, {"qkv_s8", Ly.qkv_s8, ST_MX8S, 3 * e->d, e->d / 32, 1, 1},
-            {"up_w8", Ly.up_w8, ST_U8, e->hid, e->d, 1, 1}, {"up_s8", Ly.up_s8, ST_MX8S, e->hid, e->d / 32, 1, 1},
-            {"down_w8", Ly.down_w8, ST_U8, e->d, e->hid, 1, 1}, {"down_s8", Ly.down_s8, ST_MX8S, e->d, e->hid / 32, 1, 1}};
-        for (const auto& q : imgs) S.ref(blk_name(l, "img.") + q.n, q.p, q.dt, q.s0, q.s1, q.s2, q.s3);
+        // every other image of the block, in storage order (an image this mode does not hold -- a null pointer -- gets no name)
+        for (const BodyImage& q : images)
+            if (q.name) S.ref(blk_name(l, "img.") + q.name, q.get(Ly), q.dtype, q.shape[0], q.shape[1], q.shape[2], q.shape[3]);
     }
     {   // ... and of those outside the blocks
         StageStore& S = e->stages;
@@ -274,7 +225,7 @@ int reserve_snapshots(tld_engine* e) {
         S.ref("img.pln2_w", e->pln2_w, ST_F32, dd); S.ref("img.pln2_b", e->pln2_b, ST_F32, dd); S.ref("img.pos", e->pos, ST_F32, e->ntok, dd);
         S.ref("img.out_w", e->out_w, ST_F32, pd, dd); S.ref("img.out_b", e->out_b, ST_F32, pd);
         S.ref("img.out_w_hl", e->out_w_hl, ST_BF16, 2, pd, dd); S.ref("img.plin_w_hl", e->plin_w_hl, ST_BF16, 2, dd, pd); S.ref("img.plin_wt", e->plin_wt, ST_F32, pd, dd);
-        S.ref("img.out_fold_hl", e->out_fold_hl, ST_BF16, 2, tail_fold_padded_rows(e->pd), K); S.ref("img.out_fold_b", e->out_fold_b, ST_F32, pd);
+        S.ref("img.out_fold_hl", e->mb.out_fold_hl, ST_BF16, 2, tail_fold_padded_rows(e->pd), K); S.ref("img.out_fold_b", e->mb.out_fold_b, ST_F32, pd);
     }
     return TLD_OK;
 }
@@ -284,8 +235,8 @@ int debug_poison(tld_engine* e, hipStream_t s) {
     if (!e->debug) return TLD_OK;
     for (const auto& pb : e->poison) HIP_TRY(hipMemsetAsync(pb.first, 0xFF, pb.second, s));
     const size_t M = (size_t)e->cfg.max_batch * e->ntok;
-    if (e->splitk) HIP_TRY(hipMemsetAsync(e->splitk, 0xFF, (size_t)e->ll_split * M * e->d * 4, s));
-    if (e->a8) { HIP_TRY(hipMemsetAsync(e->a8, 0xFF, M * e->hid, s)); HIP_TRY(hipMemsetAsync(e->as8, 0xFF, M * e->hid / 32 + 1024, s)); }
+    if (e->mb.splitk_slices) HIP_TRY(hipMemsetAsync(e->mb.splitk, 0xFF, (size_t)e->mb.splitk_slices * M * e->d * 4, s));
+    if (e->mode.fp8) { HIP_TRY(hipMemsetAsync(e->a8, 0xFF, M * e->hid, s)); HIP_TRY(hipMemsetAsync(e->as8, 0xFF, M * e->hid / 32 + 1024, s)); }
     return TLD_OK;
 }
 // ... and of a debug call: the conditioning tables too; the launch-path record starts empty; the tables get their names for this call's T rows
@@ -350,11 +301,12 @@ void cond_label_rows(tld_engine* e, int row0, int Tl, hipStream_t s) {
 int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const int* noise_row,
              const int* label_row, float* out, hipStream_t s, bool share_l0 = false, const int* src_row = nullptr) {
     const int d = e->d, M = batch * e->ntok;
-    share_l0 = share_l0 && e->share_l0 && (src_row ? batch > src_batch && batch <= 2 * src_batch : batch == 2 * src_batch);
+    share_l0 = share_l0 && e->mode.share_l0 && (src_row ? batch > src_batch && batch <= 2 * src_batch : batch == 2 * src_batch);
     if (int rc = debug_poison(e, s)) return rc;
     const int b0 = share_l0 ? src_batch : batch;            // samples processed up to block 0's attention
     resid_t* xe = share_l0 ? e->x_half : e->x;
-    const bool fold1 = e->fold_ln1;                          // LayerNorm-1 applied inside the QKV GEMM's epilogue
+    const BodyPlan& P = e->mode;                             // which path every stage below takes: decided once (tld_body_plan.h), read here
+    const bool fold1 = P.fold_ln1;                           // LayerNorm-1 applied inside the QKV GEMM's epilogue
     const int ln_slots = gemm_resid_stat_slots(d);
     {
         ProfScope ps(e, KC_EMBED, s);
@@ -373,33 +325,32 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
         const Layer& Ly = e->layers[l];
         const bool half = share_l0 && l == 0;
         const int bl = half ? b0 : batch, Ml = bl * e->ntok;
-        const bool fuse8 = e->fp8 && e->fp8_fused;      // fp8 mode: producers write the MX-fp8 operand themselves
         SNAP(blk_name(l, "x_in"), half ? xe : e->x, rdt, s, Ml, d);
         if (fold1) SNAP(blk_name(l, "ln1"), e->ln_stats, ST_F32, s, Ml, kLnSlots, 2);
         if (!fold1) {   // xn = LN1(x)
             ProfScope ps(e, KC_LN, s);
-            if (fuse8 && layernorm_mx8_supported(d)) launch_layernorm_mx8(half ? xe : e->x, Ly.n1_w, Ly.n1_b, e->a8, e->as8, Ml, d, s);
+            if (P.ln_mx8) launch_layernorm_mx8(half ? xe : e->x, Ly.n1_w, Ly.n1_b, e->a8, e->as8, Ml, d, s);
             else { launch_layernorm_bf16(half ? xe : e->x, Ly.n1_w, Ly.n1_b, e->xn, Ml, d, s); SNAP(blk_name(l, "xn1"), e->xn, ST_BF16, s, Ml, d); }
         }
         // 256-token grids with the LayerNorm-1 fold: the QKV projection and the whole self-attention of a (sample, head) are one 256 x 192
         // GEMM tile + epilogue; q, k, v never reach HBM and `att` is written directly.  (the fp8 mode keeps the two kernels)
-        const bool fused_qa = eng_fused_qa(e);
+        const bool fused_qa = P.fused_qa;
         if (fused_qa) {
             ProfScope ps(e, KC_GEMM_QKV, s);
             GemmParams g{};
-            const bool pair = eng_qkv_pair(e, bl);          // two heads per tile where that is the faster cut of this launch (the same bits either way)
+            const bool pair = body_pair_launch(P, bl);      // two heads per tile where that is the faster cut of this launch (the same bits either way)
             g.A = half ? xe : e->x; g.lda = d; g.W = pair ? Ly.qkv_wp2 : Ly.qkv_wp; g.ldw = d; g.M = Ml; g.N = 3 * d; g.K = d;
             g.out_bf16 = e->att; g.ldo = d; g.ntok = e->ntok; g.d = d;
             g.ln_stats = e->ln_stats; g.ln_slots = l == 0 ? 2 : ln_slots; g.ln_c1 = pair ? Ly.qkv_c1p2 : Ly.qkv_c1p; g.ln_b1 = pair ? Ly.qkv_b1p2 : Ly.qkv_b1p;
-            g.park = pair ? e->pair_park : nullptr;
+            g.park = pair ? e->mb.pair_park : nullptr;
             GEMM_TRY(blk_name(l, "QKV + attention"), launch_gemm(g, pair ? EPI_QKV_ATTN2 : EPI_QKV_ATTN, s));
         } else {   // q|k, v^T = LN1(x) Wqkv^T
             ProfScope ps(e, KC_GEMM_QKV, s);
             GemmParams g{};
             g.A = e->xn; g.lda = d; g.W = Ly.qkv_w; g.ldw = d; g.M = Ml; g.N = 3 * d; g.K = d;
             g.out_bf16 = e->qk; g.ldo = 2 * d; g.vt = e->vt; g.ntok = e->ntok; g.d = d;
-            if (e->fp8) {   // MX-fp8: quantise LN1(x) (one pass over [M, d]; fused into the LayerNorm kernel when possible), then the e4m3 GEMM
-                if (!(fuse8 && layernorm_mx8_supported(d))) launch_quant_mx8(e->xn, e->a8, e->as8, Ml, d, s);
+            if (P.fp8) {   // MX-fp8: quantise LN1(x) (one pass over [M, d]; fused into the LayerNorm kernel when possible), then the e4m3 GEMM
+                if (P.quant_qkv) launch_quant_mx8(e->xn, e->a8, e->as8, Ml, d, s);
                 SNAP(blk_name(l, "a8_qkv.q"), e->a8, ST_U8, s, Ml, d); SNAP(blk_name(l, "a8_qkv.s"), e->as8, ST_MX8S, s, Ml, d / 32);
                 g.f8 = 1; g.A = reinterpret_cast<const bf16*>(e->a8); g.W = reinterpret_cast<const bf16*>(Ly.qkv_w8);
                 g.a_scale = e->as8; g.w_scale = Ly.qkv_s8;
@@ -422,8 +373,8 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
         // up-projection's epilogue and the pre-conv hidden never reaches HBM.  Other grids: separate kernels.
         // 512 px (32x32 tokens, round 4): a tile row-block is 8 image rows; the epilogue finishes the interior rows and a thin second kernel the two rows at
         // every tile seam from the hidden rows the epilogue leaves for it (half of the hidden tensor instead of a write + read of all of it).
-        const bool fuse_dw = eng_fuse_dw(e);
-        const bool fold3 = e->fold_ln3;                 // LN3 applied in the up-projection's epilogue: cross_row writes row statistics, not xn
+        const bool fuse_dw = P.fuse_dw;
+        const bool fold3 = P.fold_ln3;                  // LN3 applied in the up-projection's epilogue: cross_row writes row statistics, not xn
         {   // x += att; x += CA(LN2 x, y); xn = LN3(x) (or its row statistics)
             ProfScope ps(e, KC_CROSS, s);
             CrossRowParams cp{};
@@ -437,7 +388,7 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
             cp.ln2_w = Ly.n2_w; cp.ln2_b = Ly.n2_b; cp.ln3_w = Ly.n3_w; cp.ln3_b = Ly.n3_b;
             cp.xn3 = fold3 ? nullptr : e->xn; cp.ln3_stats = fold3 ? e->row_stats : nullptr; cp.batch = batch; cp.ntok = e->ntok; cp.d = d; cp.heads = e->H;
             if (e->dbg_keep) { if (int rc = e->stages.sink(blk_name(l, "sa"), M, d, &cp.sa_out)) return rc; }
-            const bool cross8 = fuse8 && cross_row_supports_ln3_stats(d);      // (= the 4-features-per-lane kernel is in use)
+            const bool cross8 = P.cross_mx8;
             if (cross8) { cp.xn3_f8 = e->a8; cp.xn3_s8 = e->as8; }
             launch_cross_row(cp, s);
             if (!fold3 && !cross8) SNAP(blk_name(l, "xn3"), e->xn, ST_BF16, s, M, d);
@@ -455,11 +406,11 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
                 g.A = e->x; g.W = Ly.up_wf; g.bias = Ly.up_b1; g.ln_c1 = Ly.up_c1; g.row_stats = e->row_stats;
             }
 #endif
-            g.dw_seam = e->seam;
-            GEMM_TRY(blk_name(l, "fused up-projection"), launch_gemm(g, e->grid == 32 ? EPI_UP_DWCONV32 : EPI_UP_DWCONV2, s));
-            if (e->grid == 32) {
+            g.dw_seam = e->mb.seam;
+            GEMM_TRY(blk_name(l, "fused up-projection"), launch_gemm(g, P.seam ? EPI_UP_DWCONV32 : EPI_UP_DWCONV2, s));
+            if (P.seam) {
                 ProfScope ps2(e, KC_DWCONV, s);
-                launch_dwconv_seam(e->seam, Ly.dw_wpk, Ly.dw_b_half, e->hid2, e->hid, batch, e->hid, s);
+                launch_dwconv_seam(e->mb.seam, Ly.dw_wpk, Ly.dw_b_half, e->hid2, e->hid, batch, e->hid, s);
             }
         } else {
             {   // hid1 = xn Wup^T + b
@@ -467,8 +418,8 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
                 GemmParams g{};
                 g.A = e->xn; g.lda = d; g.W = Ly.up_w; g.ldw = d; g.M = M; g.N = e->hid; g.K = d;
                 g.out_bf16 = e->hid1; g.ldo = e->hid; g.bias = Ly.up_b;
-                if (e->fp8) {
-                    if (!(fuse8 && cross_row_supports_ln3_stats(d))) launch_quant_mx8(e->xn, e->a8, e->as8, M, d, s);
+                if (P.fp8) {
+                    if (P.quant_up) launch_quant_mx8(e->xn, e->a8, e->as8, M, d, s);
                     SNAP(blk_name(l, "a8_up.q"), e->a8, ST_U8, s, M, d); SNAP(blk_name(l, "a8_up.s"), e->as8, ST_MX8S, s, M, d / 32);
                     g.f8 = 1; g.A = reinterpret_cast<const bf16*>(e->a8); g.W = reinterpret_cast<const bf16*>(Ly.up_w8);
                     g.a_scale = e->as8; g.w_scale = Ly.up_s8;
@@ -483,15 +434,15 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
             SNAP(blk_name(l, "hid_pre"), e->hid1, ST_BF16, s, M, e->hid);
             {
                 ProfScope ps(e, KC_DWCONV, s);
-                const bool dw8 = fuse8 && e->grid > 16;       // the tiled kernel writes the fp8 operand of the down projection itself
+                const bool dw8 = P.dw_mx8;                    // the tiled kernel writes the fp8 operand of the down projection itself
                 launch_dwconv_gelu(e->hid1, e->hid2, Ly.dw_w9c, Ly.dw_b, Ly.dw_w9c_half, Ly.dw_b_half, batch, e->grid, e->hid, s,
                                    dw8 ? e->a8 : nullptr, dw8 ? e->as8 : nullptr);
             }
         }
-        if (!(fuse8 && e->grid > 16)) SNAP(blk_name(l, "hid"), e->hid2, ST_BF16, s, M, e->hid);      // (the quantising depthwise kernels write no bf16 copy)
+        if (!P.dw_mx8) SNAP(blk_name(l, "hid"), e->hid2, ST_BF16, s, M, e->hid);      // (the quantising depthwise kernels write no bf16 copy)
         // The last block, default class, bf16 operands: its down projection is folded into out_proj.  The 768-wide row
         // x3 = x2 + hid2 Wd^T + bd is read by out_proj alone, so the tail below takes [x2 | hid2] against [Wout | Wout Wd] and the GEMM is not launched.
-        const bool fold_tail = l + 1 == e->L && e->out_fold_hl && !e->fp8 && !e->low_latency;
+        const bool fold_tail = l + 1 == e->L && P.fold_tail;
 #ifdef TLD_RESID_BF16
         if (fold_tail && e->dbg_keep) {
             // stage hook only: the row the folded tail stands for, unrounded, as an fp32 stage in the hook's own memory (like cross_row's sa dump: no
@@ -510,7 +461,7 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
 #endif
         if (fold_tail) {
             // (nothing here: launch_tail after the loop)
-        } else if (e->low_latency && !e->fp8) {
+        } else if (P.ll_split) {
             // Low-latency class: a handful of samples are a handful of 256-row tiles, and the down projection's 48 K-steps per tile (K = 4 d) were
             // half of a layer's time however empty the chip was.  Four K-splits quadruple the work items (fp32 slices, summed in a fixed order by
             // the finishing kernel together with bias, residual add and the LayerNorm-1 partial sums).  Results differ from the default class in the
@@ -518,11 +469,11 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
             // its capacity), never of the batch a call happens to carry: inside a class results stay bit-identical across batch sizes.
             ProfScope ps(e, KC_GEMM_DOWN, s);
             GemmParams g{};
-            g.A = e->hid2; g.lda = e->hid; g.W = Ly.down_w; g.ldw = e->hid; g.M = M; g.N = d; g.K = e->hid / e->ll_split; g.ksplit = e->ll_split;
-            g.c_f32 = e->splitk; g.ldc = d;
+            g.A = e->hid2; g.lda = e->hid; g.W = Ly.down_w; g.ldw = e->hid; g.M = M; g.N = d; g.K = e->hid / P.ll_split; g.ksplit = P.ll_split;
+            g.c_f32 = e->mb.splitk; g.ldc = d;
             GEMM_TRY(blk_name(l, "split-K down projection"), launch_gemm(g, EPI_F32, s));
-            SNAP(blk_name(l, "splitk"), e->splitk, ST_F32, s, e->ll_split, M, d);
-            launch_splitk_resid(e->splitk, e->ll_split, (size_t)M * d, Ly.down_b, e->x, (fold1 && l + 1 < e->L) ? e->ln_stats : nullptr, M, d, s);
+            SNAP(blk_name(l, "splitk"), e->mb.splitk, ST_F32, s, P.ll_split, M, d);
+            launch_splitk_resid(e->mb.splitk, P.ll_split, (size_t)M * d, Ly.down_b, e->x, (fold1 && l + 1 < e->L) ? e->ln_stats : nullptr, M, d, s);
         } else
         {   // x += hid2 Wdown^T + b
             ProfScope ps(e, KC_GEMM_DOWN, s);
@@ -530,8 +481,8 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
             g.A = e->hid2; g.lda = e->hid; g.W = Ly.down_w; g.ldw = e->hid; g.M = M; g.N = d; g.K = e->hid;
             g.bias = Ly.down_b; g.resid = e->x; g.ldr = d;
             g.stats_out = (fold1 && l + 1 < e->L) ? e->ln_stats : nullptr;
-            if (e->fp8) {
-                if (!(fuse8 && e->grid > 16)) launch_quant_mx8(e->hid2, e->a8, e->as8, M, e->hid, s);
+            if (P.fp8) {
+                if (P.quant_down) launch_quant_mx8(e->hid2, e->a8, e->as8, M, e->hid, s);
                 SNAP(blk_name(l, "a8_down.q"), e->a8, ST_U8, s, M, e->hid); SNAP(blk_name(l, "a8_down.s"), e->as8, ST_MX8S, s, M, e->hid / 32);
                 g.f8 = 1; g.A = reinterpret_cast<const bf16*>(e->a8); g.W = reinterpret_cast<const bf16*>(Ly.down_w8);
                 g.a_scale = e->as8; g.w_scale = Ly.down_s8;
@@ -546,8 +497,8 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
         tp.tok = e->x; tp.w = e->out_w; tp.w_hl = e->out_w_hl; tp.b = e->out_b; tp.out = out; tp.batch = batch;
         tp.C = e->cfg.n_channels; tp.S = e->cfg.image_size; tp.p = e->cfg.patch_size; tp.grid = e->grid;
         tp.pd = e->pd; tp.d = d; tp.ntok = e->ntok;
-        if (e->out_fold_hl && !e->fp8 && !e->low_latency) {      // (= fold_tail of the last block: e->x is x2, the row before the down projection)
-            tp.hid = e->hid2; tp.hidn = e->hid; tp.wf_hl = e->out_fold_hl; tp.bf = e->out_fold_b;
+        if (P.fold_tail) {      // (the last block's down projection was not launched: e->x is x2, the row before it)
+            tp.hid = e->hid2; tp.hidn = e->hid; tp.wf_hl = e->mb.out_fold_hl; tp.bf = e->mb.out_fold_b;
         }
         launch_tail(tp, s);
     }
@@ -671,7 +622,7 @@ int sample_requests(tld_engine* e, SampleCall& call, const SampleOperands& ops, 
     if (SampleRefusal r = sample_call_check(call)) return fail(r.code, "%s", r.msg.c_str());
     if (!e || !ops.noise || !ops.labels || !ops.out_latent) return fail(TLD_ERR_INVALID, "null argument");
     if (!e->finalized) return fail(TLD_ERR_STATE, "weights not finalized");
-    call.guidance_skip = e->guidance_skip; call.max_batch = e->cfg.max_batch;
+    call.guidance_skip = e->mode.guidance_skip; call.max_batch = e->cfg.max_batch;
     if (SampleRefusal r = sample_plan(call, e->plan)) return fail(r.code, "%s", r.msg.c_str());
     DeviceGuard dg(e->cfg.device_id);
     PathScope paths(e);                                       // (debug: the launch paths are recorded; the requests entries keep no stage)
@@ -721,41 +672,11 @@ const char* tld_last_error(void) { return g_err; }
 int tld_engine_create(const tld_config* c, tld_engine** out) {
     if (!c || !out) return fail(TLD_ERR_INVALID, "null argument");
     *out = nullptr;
-    if (c->embed_dim <= 0 || c->embed_dim % 64 != 0 || c->embed_dim > 1024)
-        return fail(TLD_ERR_INVALID, "embed_dim=%d unsupported: must be a multiple of the head width 64 (n_heads = embed_dim // 64, "
-                    "tld/transformer_blocks.py:126-128) and <= 1024 (the row kernels hold a token row in 8 x 128-feature register groups)", c->embed_dim);
-    if (c->patch_size <= 0 || c->image_size % c->patch_size != 0)
-        return fail(TLD_ERR_INVALID, "image_size=%d must be divisible by patch_size=%d", c->image_size, c->patch_size);
-    const int grid = c->image_size / c->patch_size, ntok = grid * grid;
-    // round 4: any grid whose side is a multiple of 4 (token count a multiple of 16: the 16-row groups of the cross-attention row kernel, 16-byte V^T
-    // rows); 64 / 128 / k 256 tokens have shape-specialised attention kernels, everything else takes the masked chunked one
-    if (ntok % 16 != 0)
-        return fail(TLD_ERR_INVALID, "token count %d unsupported: image_size / patch_size must be a multiple of 4", ntok);
-    const int pd = c->n_channels * c->patch_size * c->patch_size;
-    if (pd > 64) return fail(TLD_ERR_INVALID, "patch_dim=%d > 64 unsupported", pd);
-    if (c->noise_embed_dims % 2 || c->noise_embed_dims <= 0) return fail(TLD_ERR_INVALID, "noise_embed_dims must be even");
-    if (c->max_batch <= 0 || c->n_layers <= 0 || c->mlp_multiplier <= 0 || c->text_emb_size <= 0)
-        return fail(TLD_ERR_INVALID, "non-positive size in config");
-    if ((c->mlp_multiplier * c->embed_dim) % 64) return fail(TLD_ERR_INVALID, "hidden width must be a multiple of 64");
-    {   // the GEMM tile DMA addresses operands with 32-bit byte offsets
-        const int64_t g = c->image_size / c->patch_size;
-        const int64_t hid_bytes = (int64_t)c->max_batch * g * g * c->mlp_multiplier * c->embed_dim * 2;
-        if (hid_bytes >= (int64_t)1 << 32)
-            return fail(TLD_ERR_INVALID, "max_batch=%d: the hidden activation (%lld bytes) must stay below 4 GiB; "
-                        "run larger batches as several calls", c->max_batch, (long long)hid_bytes);
-    }
+    // (the runtime is asked for the device count only once the configuration has passed every refusal in front of the device_id one)
+    if (const std::string bad = body_config_check(*c, -1); !bad.empty()) return fail(TLD_ERR_INVALID, "%s", bad.c_str());
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
-    if (c->device_id < 0 || c->device_id >= ndev) return fail(TLD_ERR_INVALID, "device_id %d out of range (%d devices)", c->device_id, ndev);
-    {   // the row kernels keep per-workgroup tables in dynamic LDS (opted in above the 64-KiB default; a CU has 160 KiB)
-        const long d = c->embed_dim, H = d / 64;
-        const long embed_lds = (pd * d + (long)pd * pd) * 4, tail_lds = pd * d * 4, cross_lds = (H * d + 2 * d + H) * 4;
-        const long lim = 160 * 1024;
-        if (embed_lds > lim || tail_lds > lim || cross_lds > lim)
-            return fail(TLD_ERR_INVALID, "embed_dim=%d with patch_dim=%d needs %ld / %ld / %ld bytes of LDS in the embed / "
-                        "out-proj / cross-attention row kernels (limit %ld each): reduce patch_size*patch_size*n_channels "
-                        "or embed_dim", c->embed_dim, pd, embed_lds, tail_lds, cross_lds, lim);
-    }
+    if (const std::string bad = body_config_check(*c, ndev); !bad.empty()) return fail(TLD_ERR_INVALID, "%s", bad.c_str());
     DeviceGuard dg(c->device_id);
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, c->device_id));
@@ -763,34 +684,11 @@ int tld_engine_create(const tld_config* c, tld_engine** out) {
         return fail(TLD_ERR_INVALID, "device %d is %s; this engine is built for gfx950 only", c->device_id, prop.gcnArchName);
     tld_engine* e = new tld_engine();
     e->cfg = *c;
-    e->d = c->embed_dim; e->L = c->n_layers; e->H = c->embed_dim / 64; e->grid = grid; e->ntok = ntok;
-    e->pd = pd; e->hid = c->mlp_multiplier * c->embed_dim; e->img = c->n_channels * c->image_size * c->image_size;
-    e->ne = c->noise_embed_dims; e->text = c->text_emb_size;
+    static_cast<BodyShape&>(*e) = body_shape(*c);
     e->layers.resize(e->L);
     e->nparam = make_param_layout(e->d, e->L, e->ne, e->pd, e->hid, e->ntok, e->text).count;
-    if (const char* fd = getenv("TLD_FUSE_DWCONV")) e->fuse_dwconv = atoi(fd) != 0;
-    if (const char* sl = getenv("TLD_SHARE_L0")) e->share_l0 = atoi(sl) != 0;
-    if (const char* gs = getenv("TLD_GUIDANCE_SKIP")) e->guidance_skip = atoi(gs) != 0;
-    if (const char* f8 = getenv("TLD_FP8_FUSED")) e->fp8_fused = atoi(f8) != 0;
-    if (const char* fl = getenv("TLD_FOLD_LN3")) e->fold_ln3 = atoi(fl) != 0;
-    if (const char* fl = getenv("TLD_FOLD_LN1")) e->fold_ln1 = atoi(fl) != 0;
-    if (const char* ft = getenv("TLD_FOLD_TAIL")) e->fold_tail = atoi(ft) != 0;
-#ifndef TLD_RESID_BF16
-    e->fold_tail = false;              // the folded tail reads the bf16 residual row as an MFMA operand
-    e->fold_ln3 = false;               // the folds feed the bf16 residual stream straight to the MFMA
-    e->fold_ln1 = false;
-#endif
-    // LayerNorm-1 fold: needs the down projection's 96-column partial sums (d % 192 == 0, at most 8 groups) and a QKV
-    // width the 256-wide kernel takes for every batch size
-    e->fold_ln1 = e->fold_ln1 && gemm_resid_stat_slots(e->d) > 0 && (3 * e->d) % 256 == 0;
-    // needs the statistics-writing row kernel; both up-projection epilogues (fused depthwise at 16 x 16 tokens, plain
-    // bias + bf16 otherwise) apply the fold
-    e->fold_ln3 = e->fold_ln3 && e->hid % 256 == 0 && cross_row_supports_ln3_stats(e->d);
-    // fused QKV -> attention: one 256 x 192 tile per (sample, head) needs 256-token samples, the LayerNorm-1 fold (the kernel reads the raw
-    // residual stream) and an even number of 64-wide K-steps (its LDS map relies on which stage a tile consumes last)
-    if (const char* fq = getenv("TLD_FUSE_QKV_ATTN")) e->fuse_qkv_attn = atoi(fq) != 0;
-    e->fuse_qkv_attn = e->fuse_qkv_attn && e->fold_ln1 && ntok == 256 && e->d % 128 == 0;
-    if (const char* qp = getenv("TLD_QKV_ATTN_PAIR")) { const int v = atoi(qp); e->qkv_pair = v < 0 ? 0 : v > 2 ? 2 : v; }
+    e->sw = body_switches(getenv);
+    replan(e, false, 0);
     *out = e;
     return TLD_OK;
 }
@@ -836,7 +734,8 @@ int tld_engine_finalize_weights(tld_engine* e) {
     RefreshPlan& R = e->refresh;
     R = RefreshPlan();
     R.d = e->d; R.hid = e->hid; R.L = e->L; R.pd = e->pd; R.l0 = pl.layers[0]; R.layer_stride = pl.layer_stride(); R.outw = pl.outw; R.outb = pl.outb;
-    R.fold = e->fold_ln1 || e->fold_ln3; R.fp8 = e->fp8;
+    const BodyPlan& P = e->mode;
+    R.fold = P.fold_ln1 || P.fold_ln3; R.fp8 = P.fp8;
 #define JOB(ptr, src, n, kind, cols) IMG(ptr, (kind) == RJ_SPLIT_HL ? 2 * (n) : (n)) R.jobs[R.njobs++] = RefreshJob{ptr, src, n, kind, cols};
 #define COPY(ptr, src, n) JOB(e->ptr, pl.src, n, RJ_COPY, 0)
     COPY(ff1_w, ff1w, d * ne) COPY(ff1_b, ff1b, d) COPY(ff3_w, ff3w, d * d) COPY(ff3_b, ff3b, d) COPY(label_w, lbw, d * text) COPY(label_b, lbb, d)
@@ -848,48 +747,21 @@ int tld_engine_finalize_weights(tld_engine* e) {
 #undef COPY
 #undef JOB
     static_assert(kRefreshMaxJobs >= 21, "the images outside the blocks");
-    // the two-head form of the fused QKV + attention kernel: only engines that can run it hold its images and slots
-    bool pair_form = false;
-    if (e->fuse_qkv_attn && !e->fp8 && !e->low_latency && e->H % 2 == 0 && e->qkv_pair != 0) {
-        pair_form = e->qkv_pair == 2;
-        for (int b = 1; b <= e->cfg.max_batch && !pair_form; ++b) pair_form = plan_qkv_pair(b, e->H, device_cu_count());
-    }
-    for (Layer& Ly : e->layers) {
-        // bf16 GEMM operands: only the copies this engine's paths read are made resident (the LayerNorm folds use gamma-scaled copies, the fp8 mode
-        // its own e4m3 ones)
-        if (!e->fold_ln1 && !e->fp8) IMG(Ly.qkv_w, 3 * d * d)
-        if (!e->fold_ln3 && !e->fp8) IMG(Ly.up_w, hid * d)
-        if (!e->fp8) IMG(Ly.down_w, d * hid)
-        IMG(Ly.kv_w, 2 * d * d) IMG(Ly.q_w, d * d) IMG(Ly.up_b, hid) IMG(Ly.dw_b, hid) IMG(Ly.down_b, d)
-        IMG(Ly.n1_w, d) IMG(Ly.n1_b, d) IMG(Ly.n2_w, d) IMG(Ly.n2_b, d) IMG(Ly.n3_w, d) IMG(Ly.n3_b, d)
-        if (e->fold_ln1) {
-            IMG(Ly.qkv_wf, 3 * d * d) IMG(Ly.qkv_c1, 3 * d) IMG(Ly.qkv_b1, 3 * d)
-            if (e->fuse_qkv_attn) {     // rows [q; k; v] x [head][64]  ->  [head][feature half][q | k | v][32]: tile-column h of the fused kernel is head h, and each of
-                // its two 96-column wave columns holds 32 features of q, of k AND of v -- so the slow part of the image write (V^T: 2-byte scattered LDS writes) is
-                // shared by all eight waves instead of falling on the four that held v (round 5; the values and their accumulation order do not change)
-                IMG(Ly.qkv_wp, 3 * d * d)
-                if (int rc = dev_alloc(e, &Ly.qkv_c1p, (size_t)(3 * d + 64))) return rc;      // (+64: the side-table DMA of the last head reads a 256-column window;
-                if (int rc = dev_alloc(e, &Ly.qkv_b1p, (size_t)(3 * d + 64))) return rc;      // that margin is no weight)
-                e->weight_bytes += 2 * 3 * d * (int64_t)sizeof(float);
-                if (pair_form) {    // the same rows in head-pair order (EPI_QKV_ATTN2): 3 d^2 bf16 more per block
-                    IMG(Ly.qkv_wp2, 3 * d * d) IMG(Ly.qkv_c1p2, 3 * d) IMG(Ly.qkv_b1p2, 3 * d)
-                }
-            }
+    // the blocks' images this mode holds (body_block_images: the table the stage hook names them from too)
+    const std::vector<BodyImage> images = body_block_images(*e, P);
+    for (Layer& Ly : e->layers)
+        for (const BodyImage& q : images) {
+            if (!q.held) continue;
+            char* p = nullptr;
+            if (int rc = dev_alloc(e, &p, (size_t)(q.numel() + q.margin) * st_bytes(q.dtype))) return rc;
+            q.set(Ly, p);
+            e->weight_bytes += q.numel() * (int64_t)st_bytes(q.dtype);
         }
-        if (e->fp8) {
-            IMG(Ly.qkv_w8, 3 * d * d) IMG(Ly.qkv_s8, 3 * d * d / 32) IMG(Ly.up_w8, hid * d) IMG(Ly.up_s8, hid * d / 32)
-            IMG(Ly.down_w8, d * hid) IMG(Ly.down_s8, d * hid / 32)
-        }
-        if (e->fold_ln3) { IMG(Ly.up_wf, hid * d) IMG(Ly.up_c1, hid) IMG(Ly.up_b1, hid) }
-        // depthwise taps [hid,1,3,3] -> [9][hid]; halved copies for the fused epilogue (its GELU is written for x / 2; scaling by 0.5 is exact); packed bf16
-        // tap pairs for the v_dot2c form
-        IMG(Ly.dw_w9c, 9 * hid) IMG(Ly.dw_w9c_half, 9 * hid) IMG(Ly.dw_b_half, hid) IMG(Ly.dw_wpk, 12 * hid)
-    }
-    if (e->fold_tail && !e->fp8) {   // out_proj folded into the last block's down projection (tld_tail_fold_math.h); rows pd .. pdp - 1 of the image stay zero
+    if (P.fold_tail_held) {   // out_proj folded into the last block's down projection (tld_tail_fold_math.h); rows pd .. pdp - 1 of the image stay zero
         const size_t n = (size_t)(2 * tail_fold_padded_rows((int)pd) * (d + hid));
-        IMG(e->out_fold_hl, n) IMG(e->out_fold_b, pd)
-        HIP_TRY(hipMemsetAsync(e->out_fold_hl, 0, n * sizeof(bf16), nullptr));
-        R.tail_fold_hl = e->out_fold_hl; R.tail_fold_b = e->out_fold_b;
+        IMG(e->mb.out_fold_hl, n) IMG(e->mb.out_fold_b, pd)
+        HIP_TRY(hipMemsetAsync(e->mb.out_fold_hl, 0, n * sizeof(bf16), nullptr));
+        R.tail_fold_hl = e->mb.out_fold_hl; R.tail_fold_b = e->mb.out_fold_b;
     }
 #undef IMG
     {   // per-layer pointer tables for the layer-batched conditioning launches
@@ -924,25 +796,22 @@ int tld_engine_finalize_weights(tld_engine* e) {
     if (int rc = dev_alloc(e, &e->qk, M * 2 * d)) return rc;
     if (int rc = dev_alloc(e, &e->vt, M * d)) return rc;
     if (int rc = dev_alloc(e, &e->att, M * d)) return rc;
-    if (pair_form) {
-        const size_t pairs = B2 * (size_t)(e->H / 2), cus = (size_t)device_cu_count();
-        if (int rc = dev_alloc(e, &e->pair_park, (pairs < cus ? pairs : cus) * (size_t)kPairSlotDwords)) return rc;
-    }
+    if (P.pair_held) { if (int rc = dev_alloc(e, &e->mb.pair_park, (size_t)P.pair_slots * kPairSlotDwords)) return rc; }
     if (int rc = dev_alloc(e, &e->hid1, M * hid)) return rc;
-    if (e->grid == 32 && e->fuse_dwconv && hid % 256 == 0) { if (int rc = dev_alloc(e, &e->seam, M * hid / 4)) return rc; }
+    if (P.seam) { if (int rc = dev_alloc(e, &e->mb.seam, M * hid / 4)) return rc; }
     if (int rc = dev_alloc(e, &e->hid2, M * hid)) return rc;
-    if (e->fp8) {
+    if (P.fp8) {
         if (int rc = dev_alloc(e, &e->a8, M * hid)) return rc;
         if (int rc = dev_alloc(e, &e->as8, M * hid / 32 + 1024)) return rc;
     }
     {   // what a debug forward poisons first: every activation / statistics / seam buffer above (the split-K slices and the fp8 operand: debug_poison)
-        auto& P = e->poison;
-        P.clear();
-        P.emplace_back(e->x, M * d * sizeof(resid_t)); P.emplace_back(e->x_half, M * d * sizeof(resid_t)); P.emplace_back(e->xn, M * d * 2);
-        P.emplace_back(e->row_stats, (M + 256) * sizeof(float2)); P.emplace_back(e->ln_stats, (M + 256) * kLnSlots * sizeof(float2));
-        P.emplace_back(e->qk, M * 2 * d * 2); P.emplace_back(e->vt, M * d * 2); P.emplace_back(e->att, M * d * 2);
-        P.emplace_back(e->hid1, M * hid * 2); P.emplace_back(e->hid2, M * hid * 2);
-        if (e->seam) P.emplace_back(e->seam, M * hid / 4 * sizeof(uint32_t));
+        auto& Q = e->poison;
+        Q.clear();
+        Q.emplace_back(e->x, M * d * sizeof(resid_t)); Q.emplace_back(e->x_half, M * d * sizeof(resid_t)); Q.emplace_back(e->xn, M * d * 2);
+        Q.emplace_back(e->row_stats, (M + 256) * sizeof(float2)); Q.emplace_back(e->ln_stats, (M + 256) * kLnSlots * sizeof(float2));
+        Q.emplace_back(e->qk, M * 2 * d * 2); Q.emplace_back(e->vt, M * d * 2); Q.emplace_back(e->att, M * d * 2);
+        Q.emplace_back(e->hid1, M * hid * 2); Q.emplace_back(e->hid2, M * hid * 2);
+        if (P.seam) Q.emplace_back(e->mb.seam, M * hid / 4 * sizeof(uint32_t));
     }
     if (int rc = dev_alloc(e, &e->io_x, B2 * e->img)) return rc;
     if (int rc = dev_alloc(e, &e->io_out, B2 * e->img)) return rc;
@@ -1245,41 +1114,23 @@ int tld_debug_gemm_bench(int32_t M, int32_t N, int32_t K, int32_t epilogue, int3
 int tld_engine_set_low_latency(tld_engine* e, int32_t on) {
     if (!e) return fail(TLD_ERR_INVALID, "null engine");
     DeviceGuard dg(e->cfg.device_id);
-    if (!on) { e->low_latency = false; return TLD_OK; }
-    if (on != 1 && on != 2) return fail(TLD_ERR_INVALID, "low-latency class %d: 0 = off, 1 = four K-splits (engines up to %d token rows), 2 = eight (up to %d)", on, kLowLatMaxRows, kLowLatMaxRows2);
-    if (e->fp8)
-        return fail(TLD_ERR_INVALID, "low-latency class: bf16 GEMM operands only -- this engine runs MX-fp8 GEMMs (tld_engine_set_gemm_dtype), whose down projection has no split-K form");
-    const int64_t rows = (int64_t)e->cfg.max_batch * e->ntok;
-    const int max_rows = on == 2 ? kLowLatMaxRows2 : kLowLatMaxRows;
-    if (rows > max_rows)
-        return fail(TLD_ERR_INVALID, "low-latency class %d: engine capacity %lld token rows (max_batch %d x %d tokens) exceeds %d -- at that size %s",
-                    on, (long long)rows, e->cfg.max_batch, e->ntok, max_rows, on == 2 ? "class 1 (four K-splits) is the faster one" : "the default tiles fill the chip");
-    const int split = on == 2 ? 8 : 4;
-    if (!splitk_resid_supported(e->d) || e->hid % (64 * split) != 0)
-        return fail(TLD_ERR_INVALID, "low-latency class: needs embed_dim 384 or 768 (got %d) and a hidden width that splits into %d multiples of 64 (got %d)", e->d, split, e->hid);
-    if (e->splitk && e->ll_split < split) e->splitk = nullptr;      // (a class-1 buffer is too small for eight slices: allocate anew; the old one is released with the engine)
-    if (!e->splitk) { if (int rc = dev_alloc(e, &e->splitk, (size_t)split * rows * e->d)) return rc; }
-    e->ll_split = split;
-    e->low_latency = true;
+    if (const std::string bad = body_class_refusal(*e, e->cfg.max_batch, on, e->mode.fp8); !bad.empty()) return fail(TLD_ERR_INVALID, "%s", bad.c_str());
+    if (const int split = lowlat_split(on)) {
+        // (a class-1 buffer is too small for eight slices: allocate anew; the old one is released with the engine)
+        if (e->mb.splitk_slices < split) { if (int rc = dev_alloc(e, &e->mb.splitk, (size_t)split * e->cfg.max_batch * e->ntok * e->d)) return rc; }
+        e->mb.splitk_slices = split;
+    }
+    replan(e, e->mode.fp8, on);
     return TLD_OK;
 }
 
 int tld_engine_set_gemm_dtype(tld_engine* e, int32_t dtype) {
     if (!e) return fail(TLD_ERR_INVALID, "null engine");
     if (e->finalized) return fail(TLD_ERR_STATE, "the GEMM operand type must be chosen before tld_engine_finalize_weights");
-    if (dtype != 0 && dtype != 1) return fail(TLD_ERR_INVALID, "gemm dtype %d: 0 = bf16, 1 = MX-fp8 (e4m3 + E8M0 block scales)", dtype);
-    if (dtype == 1) {
-        if (e->low_latency) return fail(TLD_ERR_INVALID, "fp8 GEMMs and the low-latency class exclude each other (the split-K down projection is bf16 only): clear tld_engine_set_low_latency first");
-#ifndef TLD_RESID_BF16
-        return fail(TLD_ERR_INVALID, "the fp8 GEMM mode exists in the bf16-residual build only");
-#endif
-        if (e->d % 128 || e->hid % 128) return fail(TLD_ERR_INVALID, "fp8 GEMMs need embed_dim and hidden width multiples of 128");
-        e->fp8 = true;
-        // activations are quantised from the separately written LayerNorm / GELU outputs: no folds, no fused depthwise epilogue
-        e->fold_ln1 = false; e->fold_ln3 = false; e->fuse_dwconv = false;
-    } else {
-        e->fp8 = false;
-    }
+    DeviceGuard dg(e->cfg.device_id);
+    if (const std::string bad = body_dtype_refusal(*e, dtype, e->mode.cls); !bad.empty()) return fail(TLD_ERR_INVALID, "%s", bad.c_str());
+    body_switches_set_dtype(e->sw, dtype);      // ((1) writes three switches off and (0) does not put them back: kept as it was, see there)
+    replan(e, dtype == 1, e->mode.cls);
     return TLD_OK;
 }
 

@@ -8,7 +8,12 @@ struct float2;      // HIP's vector type, which a plain C++ translation unit onl
 
 namespace tld {
 
+#if defined(__clang__) || (defined(__GNUC__) && __GNUC__ >= 13)
 typedef __bf16 bf16;
+#else
+struct __bf16 { uint16_t bits; };      // a host compiler without the type (tests/host/body_plan_main.cpp) only meets it behind pointers and in sizeof
+typedef __bf16 bf16;
+#endif
 
 // Residual stream dtype: bf16, as in the reference's own bf16 mode (x never leaves bf16 there either).  All
 // statistics, softmax and residual ADDS are computed in fp32 and rounded once on store.  Measured vs the fp32

@@ -2,30 +2,10 @@
 // an engine and the description of one refresh.  Include after tld_common.h.
 #pragma once
 
+#include "tld_body_plan.h"        // Layer: one decoder block's weight images
 #include "tld_param_layout.h"
 
 namespace tld {
-
-// One decoder block's weight images, as tld_engine_finalize_weights allocates them for the engine's mode (a null pointer: not held in this mode).
-// Plain pointers only: finalize keeps a device copy of the engine's array of these, and the refresh kernels index it by blockIdx.z.
-struct Layer {
-    bf16 *qkv_w = nullptr, *up_w = nullptr, *down_w = nullptr;
-    bf16 *qkv_wf = nullptr;                               // bf16(gamma1 (.) Wqkv): LayerNorm-1 folded into the QKV GEMM
-    float *qkv_c1 = nullptr, *qkv_b1 = nullptr;           // [3d] column sums of qkv_wf; beta1 . Wqkv^T
-    bf16 *qkv_wp = nullptr;                               // qkv_wf with its rows permuted to [head][q_h | k_h | v_h] (fused QKV -> attention kernel)
-    float *qkv_c1p = nullptr, *qkv_b1p = nullptr;         // the same permutation of qkv_c1 / qkv_b1
-    bf16 *qkv_wp2 = nullptr;                              // qkv_wf in head-pair order (tld_refresh_math.h: qkv_pair_row; the two-head form of that kernel, EPI_QKV_ATTN2)
-    float *qkv_c1p2 = nullptr, *qkv_b1p2 = nullptr;       // the same permutation of qkv_c1 / qkv_b1
-    float *up_b = nullptr, *dw_w9c = nullptr, *dw_b = nullptr, *down_b = nullptr;
-    float *dw_w9c_half = nullptr, *dw_b_half = nullptr;   // 0.5 x (exact): operands of the fused up-projection epilogue
-    uint32_t* dw_wpk = nullptr;                           // the halved taps as packed bf16 pairs [3][4][hid] (EPI_UP_DWCONV2)
-    // MX-fp8 GEMM mode (tld_engine_set_gemm_dtype): e4m3 weights + E8M0 block scales [K/128][N][4]
-    uint8_t *qkv_w8 = nullptr, *qkv_s8 = nullptr, *up_w8 = nullptr, *up_s8 = nullptr, *down_w8 = nullptr, *down_s8 = nullptr;
-    bf16 *up_wf = nullptr;                                // bf16(gamma3 (.) Wup): LayerNorm-3 folded into the up-projection
-    float *up_c1 = nullptr, *up_b1 = nullptr;             // [hid] column sums of up_wf; up_b + beta3 . Wup^T
-    float *n1_w = nullptr, *n1_b = nullptr, *n2_w = nullptr, *n2_b = nullptr, *n3_w = nullptr, *n3_b = nullptr;
-    float *kv_w = nullptr, *q_w = nullptr;   // fp32, conditioning path
-};
 
 // An image outside the blocks: `n` source elements at flat[src] -> dst
 enum { RJ_COPY = 0,          // fp32 [n]

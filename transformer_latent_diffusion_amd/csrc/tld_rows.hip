@@ -1672,8 +1672,6 @@ void launch_layernorm_bf16(const resid_t* x, const float* g, const float* b, bf1
     TLD_DISPATCH_D(d, hipLaunchKernelGGL((layernorm_bf16_kernel<NJ, HALF>), dim3((M + 3) / 4), dim3(256), 0, s, x, g, b, out, M, d));
 }
 
-bool layernorm_mx8_supported(int d) { return d == 256 || d == 512 || d == 768; }      // (the fp8 mode stops at embed_dim 896: d % 128 == 0 below the engine's 1024)
-
 void launch_layernorm_mx8(const resid_t* x, const float* g, const float* b, uint8_t* out8, uint8_t* scale8, int M, int d,
                           hipStream_t s) {
     const dim3 gr((M + 3) / 4), bl(256);
@@ -1682,9 +1680,6 @@ void launch_layernorm_mx8(const resid_t* x, const float* g, const float* b, uint
     else if (d == 512) hipLaunchKernelGGL(layernorm_mx8_kernel<2>, gr, bl, 0, s, x, g, b, out8, scale8, M, d);
     else if (d == 256) hipLaunchKernelGGL(layernorm_mx8_kernel<1>, gr, bl, 0, s, x, g, b, out8, scale8, M, d);
 }
-
-// the LN3-statistics output (CrossRowParams::ln3_stats) exists in the matrix-pipe kernel only
-bool cross_row_supports_ln3_stats(int d) { return d == 768 || d == 512 || d == 256; }
 
 void launch_cross_row(const CrossRowParams& p, hipStream_t s) {
     if (p.d % 256 == 0 && p.d <= 1024 && p.ntok % 16 == 0) {
@@ -1768,8 +1763,6 @@ __global__ __launch_bounds__(256) void splitk_resid_kernel(const float* __restri
         if ((lane & (GL - 1)) == 0 && slot < kLnSlots) stats_out[(size_t)row * kLnSlots + slot] = make_float2(su, sq);
     }
 }
-
-bool splitk_resid_supported(int d) { return d == 768 || d == 384; }
 
 void launch_splitk_resid(const float* parts, int nsplit, size_t slice_stride, const float* bias, resid_t* x, float2* stats_out, int M, int d, hipStream_t s) {
     const dim3 grid((unsigned)((M + 3) / 4)), block(256);
