@@ -389,7 +389,10 @@ TLD_API int tld_debug_gemm_bench(int32_t M, int32_t N, int32_t K, int32_t epilog
  * K % 64 (fp8: K % 128, M % 4, N % 4), 16-byte rows and pointers, N % 8 for the bf16-storing epilogues (N % 4 for the residual add), pitches, the QKV
  * geometry (N = 3 d, d % 64, ntok % 8, M % ntok), ln_slots even in 2 .. 8, an even M under row_stats, row_stats only without fp8 and where no 384-wide
  * tile can be chosen, stats_out only at the widths that have slots (N % 192 == 0, N <= 768, bf16).  Convolution mode, the fused depthwise epilogues
- * (4, 6) and fused attention (7) are refused: their layouts are engine-internal. */
+ * (4, 6) and fused attention (7) are refused: their layouts are engine-internal.
+ * Sizes: the tile DMA reaches an operand row through a 32-bit byte offset -- (rows - 1) x pitch + 128 bytes <= 2^32 for A and for W (with the last group's
+ * w_batch_stride_bytes offset), at most 2^24 rows, a pitch below 2^24 bytes -- refused with TLD_ERR_INVALID before the device is touched; the epilogues store
+ * through 64-bit addresses, so outputs beyond 4 GiB are accepted. */
 typedef struct tld_gemm_epilogue_args {
     const void* A; const void* W;                    /* bf16 [M][lda] / [N][ldw], K contiguous (fp8: bytes) */
     const void* a_scale; const void* w_scale;        /* fp8: E8M0 block scales [K / 128][rows][4] */
@@ -812,24 +815,34 @@ TLD_API int tld_train_loss_buckets(const double* sample_loss, const float* noise
                                    void* hip_stream);
 /* Test hook: self-attention backward alone (head_dim 64; ntok a multiple of 16): qk [M, 2d] bf16 (q | k), vt [B, H, 64, ntok]
  * bf16, o [M, d] bf16 (forward output), g [M, d] fp32 (dL/dO) -> dqkv [M, 3d] bf16 (dq | dk | dv).  scratch: 2 * batch * heads * ntok floats
- * (row statistics between the two kernels of the ntok > 256 path; may be NULL otherwise).  Device pointers. */
+ * (row statistics between the two kernels of the ntok > 256 path; may be NULL otherwise).  Device pointers.
+ * Sizes: every address is formed in 64 bits, so buffers beyond 4 GiB are accepted; TLD_ERR_INVALID before any launch only when
+ * batch x heads x ceil(ntok / 32) workgroups pass 2^31 - 1. */
 TLD_API int tld_debug_attention_bwd(const void* qk, const void* vt, const void* o, const float* g, void* dqkv, float* scratch, int32_t batch,
                                     int32_t ntok, int32_t heads, void* hip_stream);
 /* Test hook: a weight gradient of the training step, dW[n_out, k_in] = dY^T X (dY [rows, n_out], X [rows, k_in] bf16 row-major; fp32 out):
  * both operands are read as they are (the contraction index is the row), split-K partial sums go through `slices` (slice_floats fp32).
- * n_out, k_in multiples of 256, rows a multiple of 64.  Device pointers. */
+ * n_out, k_in multiples of 256, rows a multiple of 64.  Device pointers.
+ * Sizes: any number of rows (a 64-bit base per K-step); TLD_ERR_INVALID before any launch when n_out or k_in reaches 2^23 (a row of
+ * either operand must stay below 2^24 bytes: the 24-bit multiply of the tile DMA). */
 TLD_API int tld_debug_wgrad(const void* dy, const void* x, float* dw, float* slices, int64_t slice_floats, int32_t rows, int32_t n_out, int32_t k_in,
                             void* hip_stream);
 /* Test / measurement hook: self-attention forward alone, softmax(q k^T / 8) v per head (head_dim 64; MHAttention.forward,
  * tld/transformer_blocks.py:31-48).  qk [batch * ntok, 2 d] bf16 (q | k), vt [batch, heads * 64, ntok] bf16 (V transposed per head),
  * att [batch * ntok, d] bf16 out, d = 64 heads.  iters launches back to back; *ms_per_launch (host pointer, may be NULL) receives the
- * HIP-event average.  Device pointers. */
+ * HIP-event average.  Device pointers.
+ * Sizes: every address is formed in 64 bits, so q | k beyond 4 GiB is accepted; TLD_ERR_INVALID before any launch when batch or heads
+ * pass 65 535 at a token count whose kernel puts them on the grid's z and y axes (all but the multiples of 256 above 256), or when the
+ * chunked kernel's workgroup count passes 2^31 - 1. */
 TLD_API int tld_debug_attention_fwd(const void* qk, const void* vt, void* att, int32_t batch, int32_t ntok, int32_t heads, int32_t iters,
                                     float* ms_per_launch, void* hip_stream);
 /* Test hook: the MLP's depthwise 3x3 convolution + GELU alone (nn.Conv2d(hid, hid, 3, padding=1, groups=hid) then nn.GELU() on the
  * "b (h w) c -> b c h w" view, tld/transformer_blocks.py:95-103) on channels-last tokens: in / out [batch, grid * grid, channels] bf16
  * (device), weight [channels, 9] and bias [channels] fp32 (HOST, the reference's conv.weight / conv.bias).  Runs the kernel the engine
- * would pick for that grid (whole-image / tiled / row-streaming).  channels % 64 == 0; grid <= 16 or a multiple of 16. */
+ * would pick for that grid (whole-image / tiled / row-streaming).  channels % 64 == 0; grid <= 16 or a multiple of 16.
+ * Sizes: the row-streaming kernel (grids that are multiples of 32) writes through 32-bit byte offsets: batch x grid^2 x channels x 2 B
+ * must stay below 4 GiB, else TLD_ERR_INVALID before any allocation or launch, with the largest batch that fits.  The whole-image and
+ * tiled kernels address in 64 bits and accept larger buffers (up to 2^31 - 1 workgroups). */
 TLD_API int tld_debug_dwconv_gelu(const void* in_bf16, const float* weight_host, const float* bias_host, void* out_bf16, int32_t batch,
                                   int32_t grid, int32_t channels, void* hip_stream);
 /* The training step's stages (the stage hook above).  With debug on, one

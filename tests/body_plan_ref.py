@@ -67,6 +67,14 @@ def config_check(cfg, max_batch, device_id=0, ndev=1):
     hid_bytes = max_batch * ntok * cfg.mlp_multiplier * d * 2
     if hid_bytes >= 1 << 32:
         return f"max_batch={max_batch}: the hidden activation ({hid_bytes} bytes) must stay below 4 GiB; run larger batches as several calls"
+    # what the hidden-activation rule alone does not hold (csrc/tld_reach.h: body_reach_check)
+    qk_bytes = max_batch * ntok * 2 * d * 2
+    if qk_bytes >= 1 << 32:
+        return (f"max_batch={max_batch}: the q|k activation (max_batch x tokens x 2 embed_dim x 2 B = {qk_bytes} bytes) must stay below 4 GiB, the reach of the 32-bit "
+                f"offsets it is addressed through; the largest max_batch that fits is {((1 << 32) - 1) // (ntok * 2 * d * 2)}; run larger batches as several calls")
+    if max_batch > 65535:
+        return (f"max_batch={max_batch}: the self-attention kernels put one sample on each block of the grid's z axis (at most 65535); the largest max_batch that fits "
+                "is 65535; run larger batches as several calls")
     if device_id < 0 or device_id >= ndev:
         return f"device_id {device_id} out of range ({ndev} devices)"
     H = d // 64

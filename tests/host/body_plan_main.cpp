@@ -9,7 +9,8 @@
 // c<N> (tld_engine_set_low_latency) and F (tld_engine_finalize_weights), or "-" for none.  NAME=value: the environment at create.
 // The driver goes through the calls as the engine does -- a refused setter changes nothing -- and prints one JSON object per line: the refusal of create; if there
 // is none the refusal of every op ("" where it passed), the shape, the switches after the ops, every field of the plan, every row of the image table
-// [member, stage name, dtype, numel, margin, held] and every reserved stage [name, bytes].
+// [member, stage name, dtype, numel, margin, held], every reserved stage [name, bytes], and every GEMM launch of a forward of max_batch samples against
+// launch_gemm's own reach check [name, fits with bf16 operands, fits with fp8 operands].
 #include "tld_body_plan.h"
 
 #include <fstream>
@@ -98,6 +99,12 @@ int main(int argc, char** argv) {
         std::printf("], \"stages\": [");
         k = 0;
         for (const BodyStage& st : body_stages(s, p, c.max_batch, splitk_slices)) std::printf("%s[%s, %zu]", k++ ? ", " : "", quoted(st.name).c_str(), st.bytes);
+        // every launch_gemm call of a forward of max_batch samples against the launch's own reach check, bf16 and fp8 operands: [name, fits, fits in fp8 mode]
+        std::printf("], \"gemm_reach\": [");
+        BodyGemm gb[3], g8[3];
+        const int ng = body_gemms(c, s.grid, c.max_batch, false, gb);
+        body_gemms(c, s.grid, c.max_batch, true, g8);
+        for (k = 0; k < ng; ++k) std::printf("%s[%s, %d, %d]", k ? ", " : "", quoted(gb[k].name).c_str(), (int)body_gemm_fits(gb[k]), (int)body_gemm_fits(g8[k]));
         std::printf("]}\n");
     }
     return 0;

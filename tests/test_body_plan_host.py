@@ -231,6 +231,75 @@ def test_create_refusals(driver):
         assert KEYS[k + 1] in B.config_check(NS(**fixed), mb2, dev2, 1), (k, mend)
 
 
+# ---- the 32-bit reach: the exact boundary of max_batch, and no accepted engine whose forward launch_gemm would refuse -------------------
+# (config, the largest max_batch create accepts, the words of the refusal one beyond it).  The hidden activation binds from mlp_multiplier 2 on (at 2 q|k is as
+# large); at 1 q|k [M, 2 d] is twice the hidden activation and binds.  The last two: narrow rows, where the hidden-activation rule alone would admit 2^25 rows
+# -- beyond the 24-bit row factor of the GEMM tile DMA -- and 524 288 samples of 16 tokens, beyond the z axis of the attention kernels' grid.
+REACH = [
+    (_cfg(d=768, image=32, mult=4), 2730, "the hidden activation (4295491584 bytes)"),
+    (_cfg(d=768, image=64, mult=4), 682, "the hidden activation (4297064448 bytes)"),
+    (_cfg(d=768, image=128, mult=4), 170, "the hidden activation (4303355904 bytes)"),
+    (_cfg(d=256, image=32, mult=4), 8191, "the hidden activation (4294967296 bytes)"),
+    (_cfg(d=384, image=32, patch=1, C=8, mult=2), 2730, "the hidden activation (4295491584 bytes)"),
+    (_cfg(d=768, image=32, mult=2), 5461, "the hidden activation (4295491584 bytes)"),
+    (_cfg(d=768, image=32, mult=1), 5461, "the q|k activation (max_batch x tokens x 2 embed_dim x 2 B = 4295491584 bytes)"),
+    (_cfg(d=512, image=64, mult=1), 2047, "the q|k activation (max_batch x tokens x 2 embed_dim x 2 B = 4294967296 bytes)"),
+    (_cfg(d=64, image=32, mult=1), 65535, "the q|k activation (max_batch x tokens x 2 embed_dim x 2 B = 4294967296 bytes)"),
+    (_cfg(d=64, image=8, mult=1), 65535, "the self-attention kernels put one sample on each block of the grid's z axis (at most 65535)"),
+]
+
+
+def _fp8_ok(cfg):
+    return cfg.embed_dim % 128 == 0 and (cfg.embed_dim * cfg.mlp_multiplier) % 128 == 0
+
+
+def test_reach_boundary_of_max_batch(driver):
+    """The largest accepted max_batch and one more, mlp_multiplier 1, 2 and 4: the refusal names the buffer and, for the rules of section 7.19, the largest max_batch
+    that fits; the accepted engine takes the fp8 mode where its widths allow (a8 [M, hid] bytes, its scales and the seam buffer are smaller than the hidden activation:
+    no rule of their own), and launch_gemm's reach check passes for every GEMM of its forward with bf16 and with fp8 operands."""
+    lines = []
+    for k, (cfg, mb, _) in enumerate(REACH):
+        lines += [_line(f"reach{k} in", cfg, mb, "d1" if _fp8_ok(cfg) else "-"), _line(f"reach{k} out", cfg, mb + 1)]
+    outs = driver(lines)
+    for k, (cfg, mb, words) in enumerate(REACH):
+        good, bad = outs[2 * k], outs[2 * k + 1]
+        assert good["create"] == "" == B.config_check(cfg, mb), (k, good["create"])
+        assert good["ops"] == ([""] if _fp8_ok(cfg) else []) and good["plan"]["fp8"] == int(_fp8_ok(cfg))
+        assert [g[0] for g in good["gemm_reach"]] == ["QKV projection", "up-projection", "down projection"]
+        assert all(g[1] == 1 and g[2] == 1 for g in good["gemm_reach"]), (k, good["gemm_reach"])
+        assert mb * good["shape"]["ntok"] <= 1 << 24
+        assert bad["create"] == B.config_check(cfg, mb + 1) and words in bad["create"], (k, bad["create"])
+        assert bad["create"].startswith(f"max_batch={mb + 1}: ") and "run larger batches as several calls" in bad["create"]
+        if "hidden activation" not in words:
+            assert f"the largest max_batch that fits is {mb};" in bad["create"], bad["create"]
+    # the figures of the issue's table: 2730 / 682 / 170 at d 768, 8190 < 8191 at d 256
+    assert [r[1] for r in REACH[:4]] == [2730, 682, 170, 8191]
+
+
+def test_no_accepted_engine_is_refused_by_launch_gemm(driver):
+    """At the largest max_batch create accepts, for every width, grid and multiplier the engine takes: every GEMM of the forward is inside launch_gemm's reach (a
+    create that accepts must not be followed by a refusal in the middle of a forward)."""
+    cases = []
+    for d in range(64, 1025, 64):
+        for image, patch in ((8, 2), (32, 2), (64, 2), (128, 2), (24, 2)):
+            for mult in (1, 2, 3, 4, 8):
+                cfg = _cfg(d=d, image=image, patch=patch, mult=mult)
+                lo, hi = 1, 1 << 21                      # bisect the boundary on the restatement (monotone in max_batch)
+                while lo < hi:
+                    mid = (lo + hi + 1) // 2
+                    lo, hi = (mid, hi) if "max_batch=" not in B.config_check(cfg, mid) else (lo, mid - 1)
+                cases.append((cfg, lo))
+    outs = driver([_line(f"fit{k}", cfg, mb) for k, (cfg, mb) in enumerate(cases)] + [_line(f"over{k}", cfg, mb + 1) for k, (cfg, mb) in enumerate(cases)])
+    n = len(cases)
+    for k, (cfg, mb) in enumerate(cases):
+        o, over = outs[k], outs[n + k]
+        if o["create"]:                                  # (refused for another reason -- the LDS of the row kernels at d = 1024 -- at every max_batch)
+            assert "max_batch=" not in o["create"]
+            continue
+        assert all(g[1] == 1 and g[2] == 1 for g in o["gemm_reach"]), (vars(cfg), mb, o["gemm_reach"])
+        assert over["create"].startswith(f"max_batch={mb + 1}: "), (vars(cfg), mb, over["create"])
+
+
 # (config, max_batch, ops, the refusal of each op).  Of two faults the upper one is reported.
 SETTERS = [
     (_cfg(), 4, "c3", ["low-latency class 3: 0 = off, 1 = four K-splits (engines up to 4096 token rows), 2 = eight (up to 1024)"]),

@@ -17,6 +17,7 @@
 #include "../../include/tld_hip.h"
 #include "tld_gemm_plan.h"            // gemm_resid_stat_slots, kLnSlots, bf16, resid_t
 #include "tld_qkv_pair_plan.h"        // plan_qkv_pair
+#include "tld_reach.h"                // body_reach_check: the sizes the kernels' 32-bit offsets and 16-bit grid axes end at
 #include "tld_stages.h"               // ST_*: the element types of the stage hook
 #include "tld_tail_fold_math.h"       // tail_fold_padded_rows
 
@@ -73,6 +74,8 @@ inline std::string body_config_check(const tld_config& c, int ndev) {
     const int64_t hid_bytes = (int64_t)c.max_batch * grid * grid * c.mlp_multiplier * c.embed_dim * 2;
     if (hid_bytes >= (int64_t)1 << 32)
         return body_say("max_batch=%d: the hidden activation (%lld bytes) must stay below 4 GiB; run larger batches as several calls", c.max_batch, (long long)hid_bytes);
+    // ... and what that rule alone does not hold: q|k at mlp_multiplier 1, the samples on the attention kernels' z axis
+    if (std::string bad = body_reach_check(c, grid); !bad.empty()) return bad;
     if (ndev < 0) return std::string();
     if (c.device_id < 0 || c.device_id >= ndev) return body_say("device_id %d out of range (%d devices)", c.device_id, ndev);
     // the row kernels keep per-workgroup tables in dynamic LDS (opted in above the 64-KiB default; a CU has 160 KiB)

@@ -105,6 +105,7 @@ int tld_clip_create(const tld_clip_config* cfg, tld_clip** out) {
     if (int rc = check_transformer(cfg->width, cfg->heads, cfg->layers)) return rc;
     if (cfg->context_length < 1 || cfg->context_length > 128) return fail(TLD_ERR_INVALID, "context_length=%d: 1..128", cfg->context_length);
     if (cfg->embed_dim < 1 || cfg->vocab_size < 1 || cfg->max_batch < 1) return fail(TLD_ERR_INVALID, "embed_dim / vocab_size / max_batch must be positive");
+    if (const std::string bad = clip_reach_check(cfg->max_batch, cfg->context_length, cfg->width); !bad.empty()) return fail(TLD_ERR_INVALID, "%s", bad.c_str());
     if (int rc = check_device(cfg->device_id, "text")) return rc;
     DeviceGuard guard(cfg->device_id);
     tld_clip* c = new tld_clip();

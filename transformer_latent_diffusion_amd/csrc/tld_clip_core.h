@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "tld_clip_keys.h"
+#include "tld_reach.h"             // clip_reach_check: the sizes the GEMM DMA's 32-bit offsets and the attention grid end at
 
 namespace tld {
 namespace {

@@ -261,6 +261,8 @@ int tld_clip_vis_create(const tld_clip_vis_config* cfg, tld_clip_vis** out) {
         return fail(TLD_ERR_INVALID, "image_size / patch_size = %d: the grid side must be 1..%d (at most %d tokens); the 336 px towers (577 tokens) are out of scope",
                     g, kMaxGrid, kMaxGrid * kMaxGrid + 1);
     if (cfg->embed_dim < 1 || cfg->max_batch < 1) return fail(TLD_ERR_INVALID, "embed_dim / max_batch must be positive");
+    if (const std::string bad = clip_reach_check(cfg->max_batch, g * g + 1, cfg->width, g * g, (3 * cfg->patch_size * cfg->patch_size + 63) / 64 * 64); !bad.empty())
+        return fail(TLD_ERR_INVALID, "%s", bad.c_str());
     if (int rc = check_device(cfg->device_id, "image")) return rc;
     DeviceGuard guard(cfg->device_id);
     tld_clip_vis* c = new tld_clip_vis();

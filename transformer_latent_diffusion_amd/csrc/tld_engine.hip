@@ -1227,7 +1227,6 @@ int tld_debug_gemm_epilogue(const tld_gemm_epilogue_args* a, void* hip_stream) {
             }
         }
     }
-    PtrDeviceGuard guard(a->A);
     GemmParams g{};
     g.A = static_cast<const bf16*>(a->A); g.lda = a->lda; g.W = static_cast<const bf16*>(a->W); g.ldw = a->ldw;
     g.M = a->M; g.N = a->N; g.K = a->K;
@@ -1240,6 +1239,8 @@ int tld_debug_gemm_epilogue(const tld_gemm_epilogue_args* a, void* hip_stream) {
     g.row_stats = static_cast<const float2*>(a->row_stats);
     g.c_f32 = a->c_f32; g.ldc = a->ldc;
     g.w_batch_rows = a->w_batch_rows; g.w_batch_stride_bytes = a->w_batch_stride_bytes;
+    if (const std::string reach = gemm_hook_refusal(g); !reach.empty()) return fail(TLD_ERR_INVALID, "%s", reach.c_str());      // (before the device is touched)
+    PtrDeviceGuard guard(a->A);
     if (launch_gemm(g, epi, static_cast<hipStream_t>(hip_stream))) return TLD_ERR_INVALID;     // (refused: reason in tld_last_error)
     HIP_TRY(hipGetLastError());
     return TLD_OK;
@@ -1287,6 +1288,7 @@ int tld_debug_dwconv_gelu(const void* in, const float* weight, const float* bias
                           void* hip_stream) {
     if (!in || !weight || !bias || !out || batch <= 0 || grid <= 0 || channels <= 0 || channels % 64) return fail(TLD_ERR_INVALID, "bad argument");
     if (grid > 16 && grid % 16) return fail(TLD_ERR_INVALID, "grids wider than 16 tokens must be a multiple of 16 (the engine's token counts are multiples of 256)");
+    if (const std::string bad = dwconv_hook_refusal(batch, grid, channels); !bad.empty()) return fail(TLD_ERR_INVALID, "%s", bad.c_str());
     PtrDeviceGuard guard(in);
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     const size_t nc = (size_t)channels;
@@ -1311,6 +1313,7 @@ int tld_debug_attention_fwd(const void* qk, const void* vt, void* att, int32_t b
     if (!qk || !vt || !att || batch <= 0 || heads <= 0 || iters <= 0) return fail(TLD_ERR_INVALID, "bad argument");
     if (ntok <= 0 || ntok % 8 != 0)
         return fail(TLD_ERR_INVALID, "attention supports token counts that are multiples of 8 (got %d)", ntok);
+    if (const std::string bad = attention_fwd_hook_refusal(batch, ntok, heads); !bad.empty()) return fail(TLD_ERR_INVALID, "%s", bad.c_str());
     PtrDeviceGuard guard(qk);
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     hipEvent_t e0 = nullptr, e1 = nullptr;

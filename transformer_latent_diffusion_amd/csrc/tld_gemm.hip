@@ -1849,23 +1849,10 @@ static const GemmSwitches& gemm_switches() {
     return sw;
 }
 
-// The DMA of a plain (non-conv, non-TN) launch forms each operand row's address as a uniform 64-bit base plus a 32-bit
-// byte offset  row * pitch (__umul24: both factors < 2^24)  + the 16-byte piece inside the row's first 128 bytes (+ the
-// block-diagonal group's W offset).  The largest such offset must not wrap: (M - 1) lda ESZ + 128 <= 2^32 for A, and
-// (N - 1) ldw ESZ + 128 + the last group's offset for W.  Host arithmetic only; the kernels are unchanged.
-static int gemm_offsets_fit(const GemmParams& p) {
-    const uint64_t esz = p.f8 ? 1 : 2, lim = 1ull << 32;
-    const uint64_t pa = (uint64_t)p.lda * esz, pw = (uint64_t)p.ldw * esz;
-    if (p.M < 1 || p.N < 1 || p.M > (1 << 24) || p.N > (1 << 24) || pa >= (1u << 24) || pw >= (1u << 24)) return 0;
-    if ((uint64_t)(p.M - 1) * pa + 128 > lim) return 0;
-    const uint64_t wgrp = p.w_batch_rows ? (uint64_t)((p.M - 1) / p.w_batch_rows) * p.w_batch_stride_bytes : 0;
-    return (uint64_t)(p.N - 1) * pw + 128 + wgrp <= lim;
-}
-
+// (the reach of the tile DMA's 32-bit offsets: gemm_offsets_fit, tld_gemm_plan.h)
 int launch_gemm(const GemmParams& p_in, int epilogue, hipStream_t s) {
     if (!p_in.conv && !gemm_offsets_fit(p_in)) {      // launch nothing, report it to the caller
-        set_last_error("launch_gemm: an operand row lies beyond the 4 GiB reach of the 32-bit DMA offsets (row * pitch + 128 bytes must stay "
-                       "<= 2^32 for A and for W); split the launch by rows");
+        set_last_error(kGemmReachRefusal);
         return TLD_ERR_INVALID;
     }
 #ifdef TLD_DBG_EPI

@@ -73,6 +73,24 @@ constexpr bool gemm_ring_instantiated(int bn, int epilogue, bool f8, bool conv) 
     return TLD_KLOOP_RING && bn == 256 && !(f8 && (conv || epilogue == EPI_BIAS_RESID)) && gemm_main_instantiated(bn, epilogue, f8, conv);
 }
 
+// ---- the reach of the tile DMA ---------------------------------------------------------------------------------------------------------------------------------
+// The DMA of a plain (non-conv, non-TN) launch forms each operand row's address as a uniform 64-bit base plus a 32-bit
+// byte offset  row * pitch (__umul24: both factors < 2^24)  + the 16-byte piece inside the row's first 128 bytes (+ the
+// block-diagonal group's W offset).  The largest such offset must not wrap: (M - 1) lda ESZ + 128 <= 2^32 for A, and
+// (N - 1) ldw ESZ + 128 + the last group's offset for W.  Host arithmetic only: launch_gemm asks it before every launch, and the engines' create
+// (tld_reach.h) keep every launch of theirs inside it.
+constexpr const char* kGemmReachRefusal =
+    "launch_gemm: an operand row lies beyond the 4 GiB reach of the 32-bit DMA offsets (row * pitch + 128 bytes must stay "
+    "<= 2^32 for A and for W); split the launch by rows";
+inline int gemm_offsets_fit(const GemmParams& p) {
+    const uint64_t esz = p.f8 ? 1 : 2, lim = 1ull << 32;
+    const uint64_t pa = (uint64_t)p.lda * esz, pw = (uint64_t)p.ldw * esz;
+    if (p.M < 1 || p.N < 1 || p.M > (1 << 24) || p.N > (1 << 24) || pa >= (1u << 24) || pw >= (1u << 24)) return 0;
+    if ((uint64_t)(p.M - 1) * pa + 128 > lim) return 0;
+    const uint64_t wgrp = p.w_batch_rows ? (uint64_t)((p.M - 1) / p.w_batch_rows) * p.w_batch_stride_bytes : 0;
+    return (uint64_t)(p.N - 1) * pw + 128 + wgrp <= lim;
+}
+
 // ---- the 4-wave small-batch forms (tld_updw.hip): shapes their kernels are written for ------------------------------------------------------------------------
 // (all three: bf16 operands whose byte offsets fit the kernels' 32-bit DMA offsets and 24-bit multiplies)
 inline bool pp_operands_fit(const GemmParams& p) {

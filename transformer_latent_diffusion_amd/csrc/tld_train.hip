@@ -16,6 +16,7 @@
 #include "tld_host.h"
 #include "tld_param_layout.h"
 #include "tld_opt_plan.h"
+#include "tld_reach.h"          // train_config_check, the hooks' refusals
 
 #include <algorithm>
 #include <cmath>
@@ -197,7 +198,7 @@ int reserve_snapshots(tld_train* e) {
     const size_t M = (size_t)e->B * e->N, d = e->d, hid = e->hid, pd = e->pd, B2 = 2 * (size_t)e->B;
 #define RES(name, bytes) do { if (int _r = e->stages.reserve(name, bytes)) return _r; } while (0)
     RES("gx.tail", M * d * 4); RES("gxb.tail", M * d * 2);
-    const bool dw_fused = e->G <= 16 && e->N >= 176 && e->hid % 64 == 0;
+    const bool dw_fused = train_dw_fused(e->G, e->N, e->hid);
     for (int i = 0; i < e->L; ++i) {
         const std::string p = "blk" + std::to_string(i) + ".";
         for (const char* n : {"gl", "dg", "dh"}) RES(p + n, M * hid * 2);
@@ -335,18 +336,12 @@ extern "C" {
 
 int tld_train_create(const tld_config* cfg, tld_train** out) {
     if (!cfg || !out) return fail(TLD_ERR_INVALID, "null argument");
+    // every refusal that is arithmetic on the configuration, the 32-bit reach of the step's kernels among them (tld_reach.h): before any HIP call
+    if (const std::string bad = train_config_check(*cfg); !bad.empty()) return fail(TLD_ERR_INVALID, "%s", bad.c_str());
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(TLD_ERR_HIP, "no HIP device: the training engine has no CPU path");
     if (cfg->device_id < 0 || cfg->device_id >= ndev) return fail(TLD_ERR_INVALID, "device_id %d out of range", cfg->device_id);
-    if (cfg->embed_dim % 64 || cfg->embed_dim > 1024 || cfg->embed_dim <= 0) return fail(TLD_ERR_INVALID, "embed_dim must be a multiple of 64 (the head width), <= 1024");
-    if (cfg->patch_size <= 0 || cfg->image_size % cfg->patch_size) return fail(TLD_ERR_INVALID, "image_size must be a multiple of patch_size");
     const int G = cfg->image_size / cfg->patch_size;
-    // the inference engine's grids (square, side a multiple of 4: token counts that are multiples of 16, which the attention forward and
-    // backward take), up to 64 x 64; the reference trains at whatever image_size it is given (tld/train.py:83)
-    if (G % 4 || G < 4 || G > 64)
-        return fail(TLD_ERR_INVALID, "the training step supports image_size / patch_size = G with G a multiple of 4, 4 <= G <= 64 (16 .. 4096 tokens); got G = %d", G);
-    if (cfg->n_channels * cfg->patch_size * cfg->patch_size > 64) return fail(TLD_ERR_INVALID, "patch_dim must be <= 64");
-    if (cfg->noise_embed_dims % 2 || cfg->max_batch <= 0 || cfg->n_layers <= 0) return fail(TLD_ERR_INVALID, "bad configuration");
     DeviceGuard dg(cfg->device_id);
     tld_train* e = new tld_train();
     e->cfg = *cfg;
@@ -363,8 +358,7 @@ int tld_train_create(const tld_config* cfg, tld_train** out) {
         e->lbw = pl.lbw; e->lbb = pl.lbb;
     }
 
-    const size_t B = e->B, M = B * e->N;
-    if (M * (size_t)hid * 2 >= ((size_t)1 << 32)) { delete e; return fail(TLD_ERR_INVALID, "max_batch too large: the MLP hidden activation must stay below 4 GiB"); }
+    const size_t B = e->B, M = B * e->N;      // (M hid 2 < 4 GiB and (M + 4096) max(hid, 3 d) 2 < 4 GiB: train_config_check above)
     auto cleanup = [&](int rc) { for (void* p : e->allocs) hipFree(p); delete e; return rc; };
     auto alloc_all = [&]() -> int {
         DALLOC(e->angular, e->ne / 2); DALLOC(e->zero_bias, 3 * hid > 4096 ? 3 * hid : 4096);
@@ -375,7 +369,7 @@ int tld_train_create(const tld_config* cfg, tld_train** out) {
         DALLOC(e->dpn, M * pd); DALLOC(e->dp16, M * pd); DALLOC(e->est1, M); DALLOC(e->est2, M); DALLOC(e->xfin, M * d);
         DALLOC(e->dout, M * pd); DALLOC(e->row_loss, M); DALLOC(e->io, 4); DALLOC(e->pred_scratch, B * e->C * e->S * e->S);
         const size_t wide = hid > 3 * d ? hid : 3 * d;
-        DALLOC(e->gx, M * d); DALLOC(e->gxb, M * d); e->tr_rows = M + 4096; DALLOC(e->T1, e->tr_rows * wide); DALLOC(e->T2, e->tr_rows * wide); DALLOC(e->dbig, M * hid);
+        DALLOC(e->gx, M * d); DALLOC(e->gxb, M * d); e->tr_rows = M + kTrainTransposeMargin; DALLOC(e->T1, e->tr_rows * wide); DALLOC(e->T2, e->tr_rows * wide); DALLOC(e->dbig, M * hid);
         DALLOC(e->dsmall, M * 3 * d); DALLOC(e->dsmall2, M * d); DALLOC(e->attn_stats, 2 * M * e->H); DALLOC(e->scr, (size_t)pd * d + 64);
         const size_t nchunk = (M + 255) / 256;
         size_t need = nchunk * 2 * (size_t)wide;                              // LN / colsum partials
@@ -621,7 +615,7 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
         GEMM_TRY("training step", weight_grad(e->gxb, d, b.gl, hid, Gd + p.down_w));
         GEMM_TRY("training step", gemm_bf16(e->gxb, d, b.wdown_t, d, e->zero_bias, e->dbig, M, hid, d, s));                         // dg = go Wdown
         SNAP(sn + "dg", e->dbig, ST_BF16, s, M, hid);
-        const bool dw_fused = G <= 16 && N >= 176 && hid % 64 == 0;
+        const bool dw_fused = train_dw_fused(G, N, hid);
         if (dw_fused) {      PATH(PB_DW_FUSED);      // GELU' multiply, depthwise weight-gradient partials and input gradient in one pass (both images of a (sample, 64-channel chunk) in LDS)
             hipLaunchKernelGGL(dwconv_bwd_img_kernel, dim3(B * (hid / 64)), blk, (size_t)2 * N * 128, s, e->dbig, b.hc, b.h, b.dww_t, b.gl, e->part, G, hid);   // dh -> b.gl (its forward value is consumed)
             hipLaunchKernelGGL(dwconv_wgrad_reduce, dim3((hid * 11 + 63) / 64), dim3(1024), 0, s, e->part, Gd + p.dw_w, Gd + p.dw_b, B, hid, 11, Gd + p.up_b);   // + the up-projection's bias gradient
@@ -942,6 +936,7 @@ int tld_train_adamw_ema_grouped(tld_opt_plan* p, float* params, const float* gra
 int tld_debug_attention_bwd(const void* qk, const void* vt, const void* o, const float* g, void* dqkv, float* scratch, int32_t batch, int32_t ntok,
                             int32_t heads, void* hip_stream) {
     if (!qk || !vt || !o || !g || !dqkv || batch <= 0 || heads <= 0 || ntok <= 0) return fail(TLD_ERR_INVALID, "bad argument");
+    if (const std::string bad = attention_bwd_hook_refusal(batch, ntok, heads); !bad.empty()) return fail(TLD_ERR_INVALID, "%s", bad.c_str());
     PtrDeviceGuard guard(qk);
     if (launch_attention_bwd(reinterpret_cast<const bf16*>(qk), reinterpret_cast<const bf16*>(vt), reinterpret_cast<const bf16*>(o), g,
                              reinterpret_cast<bf16*>(dqkv), scratch, batch, ntok, heads, reinterpret_cast<hipStream_t>(hip_stream)))
@@ -954,6 +949,7 @@ int tld_debug_attention_bwd(const void* qk, const void* vt, const void* o, const
  * on the transposed-operand GEMM; `slices`: fp32 workspace of slice_floats elements for the split-K partial sums.  Device pointers. */
 int tld_debug_wgrad(const void* dy, const void* x, float* dw, float* slices, int64_t slice_floats, int32_t rows, int32_t n_out, int32_t k_in, void* hip_stream) {
     if (!dy || !x || !dw || !slices || rows <= 0) return fail(TLD_ERR_INVALID, "bad argument");
+    if (const std::string bad = wgrad_hook_refusal(rows, n_out, k_in); !bad.empty()) return fail(TLD_ERR_INVALID, "%s", bad.c_str());
     PtrDeviceGuard guard(dy);
     if (!wgrad_tn(reinterpret_cast<const bf16*>(dy), n_out, reinterpret_cast<const bf16*>(x), k_in, rows, dw, slices, (size_t)slice_floats,
                   reinterpret_cast<hipStream_t>(hip_stream)))
