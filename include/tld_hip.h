@@ -254,6 +254,56 @@ TLD_API int tld_debug_guidance_shape(const float* cond_device, const float* unc_
  * report sum(n_levels) twice; tld_sample_requests_guided reports (sum(n_levels), sum(U_i)) */
 TLD_API int tld_engine_sample_rows(tld_engine* e, int64_t* cond, int64_t* uncond);
 
+/* SAMPLER SESSIONS: a sampler whose membership changes between steps.  A session holds `slots` slots of per-request state on one
+ * engine; tld_session_admit puts a request into a free slot, tld_session_step runs ONE model forward for every live request, each at its own level,
+ * and one elementwise update; a request leaves at its final forward.  A request's result is bit for bit that of tld_sample_requests (or _guided /
+ * _stochastic) with that request alone: nothing of its arithmetic depends on its slot, its neighbours or the step it was admitted at.
+ *   one session per engine; while it is open it owns the engine's conditioning tables and sampler buffers, and tld_denoiser_forward, the six
+ *   tld_sample* entries and tld_engine_refresh_weights return TLD_ERR_STATE.  After tld_session_close they behave, and produce bits, as before.
+ * A request: device noise [C, S, S], device label [text_emb], optional device negative label, n_levels with a HOST table [n_levels][6] as in
+ * tld_sample_requests, a scalar class_guidance or a HOST table guidance [n_levels] (a forward guided at exactly 1.0f then runs no unconditional
+ * sample, the engine's guidance-skip rule), and optionally HOST noise_coeff [n_levels] with a 64-bit key (HOST, one value) as in
+ * tld_sample_requests_stochastic.  Every host array is copied by admit.  sharp_f / bright_f are per session.  Not part of a session, and without a
+ * field here: init_latent, start_mix < 1, masks, the guidance shape (rescale / APG) and traces; `reserved` must be 0.
+ * tld_session_open   TLD_ERR_STATE: weights not finalized, a session already open, a capturing stream.  TLD_ERR_INVALID: slots < 1,
+ *                    2 slots > max_batch (every step then fits: no step is refused for its batch), cond_rows outside 3 .. 1024.  cond_rows is the
+ *                    session's conditioning-row table: row 0 the zero label, per live request one label row (two with a negative label) and a shared,
+ *                    reference-counted row per distinct float32 sigma.  The stream is the session's: admit and step take the stream again and are
+ *                    refused on any other (TLD_ERR_INVALID), or while it is capturing (TLD_ERR_STATE).
+ * tld_session_admit  *slot_out = the slot, or -1 with TLD_OK when there is no room NOW (no free slot, or too few free rows): ask again after a step.
+ *                    TLD_ERR_INVALID: a bad record (the wording of tld_sample_requests where the rule is the same), or a request that could never
+ *                    fit (its rows exceed cond_rows - 1).  Copies the noise into the slot, computes only the NEW conditioning rows in place.
+ * tld_session_step   finished_slots [cap] <- the slots whose request ran its final forward in this step (ascending), *n_finished their number;
+ *                    cap < slots is refused.  A step with no live request enqueues nothing.  Never synchronises the stream: the tables travel
+ *                    through a ring of pinned staging buffers, each behind its own event.  With tld_engine_set_debug(1) the launch paths are
+ *                    recorded (bit 62 for the session step) and no stage is kept.
+ * tld_session_latent the [C, S, S] fp32 device result of a finished slot; it stays valid until a later admit reuses the slot, so a copy enqueued on
+ *                    the session's stream before that admit reads the finished latent.
+ * tld_session_stats  out[5] <- live requests, steps made, conditional and unconditional model samples so far, conditioning rows in use.
+ * tld_session_close  frees the session (its three [slots, C, S, S] buffers stay with the engine's arena) and gives the engine back. */
+typedef struct tld_session tld_session;
+typedef struct tld_session_request {
+    int32_t n_levels;             /* >= 2 */
+    float class_guidance;         /* finite; read when guidance is NULL */
+    int32_t has_negative;         /* != 0: the unconditional sample reads neg_label */
+    int32_t reserved;             /* 0 */
+    const float* coeffs;          /* HOST [n_levels][6] */
+    const float* guidance;        /* HOST [n_levels] or NULL */
+    const float* noise_coeff;     /* HOST [n_levels] or NULL */
+    const uint64_t* noise_key;    /* HOST, one value; NULL exactly when noise_coeff is */
+    const float* noise;           /* device [C, S, S] */
+    const float* label;           /* device [text_emb] */
+    const float* neg_label;       /* device [text_emb] or NULL */
+} tld_session_request;
+TLD_API int tld_session_open(tld_engine* e, int32_t slots, int32_t cond_rows, float sharp_f, float bright_f, void* hip_stream, tld_session** out);
+TLD_API int tld_session_admit(tld_session* s, const tld_session_request* request, void* hip_stream, int32_t* slot_out);
+TLD_API int tld_session_step(tld_session* s, void* hip_stream, int32_t* finished_slots, int32_t cap, int32_t* n_finished);
+TLD_API int tld_session_latent(tld_session* s, int32_t slot, const float** device_ptr);
+/* dst_device [C, S, S] fp32 <- the slot's result, a device copy enqueued on the session's stream (hip_stream: as in tld_session_step) */
+TLD_API int tld_session_copy_latent(tld_session* s, int32_t slot, void* dst_device, void* hip_stream);
+TLD_API int tld_session_stats(const tld_session* s, int64_t* out);
+TLD_API int tld_session_close(tld_session* s);
+
 /* THE STAGE HOOK: one contract behind tld_engine_ / tld_vae_ / tld_vae_enc_ / tld_clip_ / tld_train_ set_debug and read_stage (one implementation:
  * StageStore, csrc/tld_host.h).  set_debug(1) turns capture on, and twice is harmless; the engine's next calls keep named stages: the
  * engine's own buffers read in place, or device-to-device copies taken on the call's stream right after the kernel that completed the value, in
@@ -339,8 +389,10 @@ TLD_API int tld_debug_decode_stage(const void* raw, const void* aux, int32_t dty
  *   writers of the MX-fp8 A operand (with bit 10): 54 separate quantisation pass   55 cross_row_mfma writing e4m3   56 depthwise tiled writing e4m3
  *   57 depthwise streaming writing e4m3
  *   tld_sample_requests: 58 update_requests without a mask   59 update_requests with a mask   60 start_mix per request
- *   61 fused QKV + attention on two-head tiles (set instead of bit 11 by such a launch) */
+ *   61 fused QKV + attention on two-head tiles (set instead of bit 11 by such a launch)
+ *   tld_session_step: 62 update_session (TLD_SESSION_PATH_BIT; the bits above are those of the closed sampler calls and the forward) */
 #define TLD_ENGINE_PATH_BITS 61
+#define TLD_SESSION_PATH_BIT 62
 TLD_API int tld_engine_set_debug(tld_engine* e, int32_t enable);
 TLD_API int tld_engine_read_stage(tld_engine* e, const char* name, float* host_out, int64_t numel);
 /* logical shape of a captured stage: 4 int64, unused trailing dimensions 1 */

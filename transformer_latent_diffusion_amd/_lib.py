@@ -25,6 +25,7 @@ ABI_SYMBOLS = (
     "tld_engine_create", "tld_engine_load_tensor", "tld_engine_finalize_weights", "tld_denoiser_forward",
     "tld_sample", "tld_sample_from", "tld_sample_requests", "tld_sample_requests_guided", "tld_sample_requests_stochastic", "tld_debug_sampler_noise", "tld_sample_requests_shaped", "tld_debug_guidance_shape", "tld_engine_sample_rows", "tld_engine_set_gemm_dtype", "tld_engine_set_low_latency", "tld_debug_gemm_splitk", "tld_debug_quant_mx8", "tld_debug_quant_mx8_host", "tld_debug_gemm_mx8",
     "tld_engine_param_count", "tld_engine_refresh_weights", "tld_debug_quant_mx8_f32",
+    "tld_session_open", "tld_session_admit", "tld_session_step", "tld_session_latent", "tld_session_copy_latent", "tld_session_stats", "tld_session_close",
     "tld_debug_decode_stage", "tld_engine_set_debug", "tld_engine_read_stage", "tld_engine_stage_shape", "tld_engine_set_debug_step", "tld_engine_debug_paths", "tld_debug_gemm_bf16", "tld_debug_gemm_bench", "tld_debug_gemm_plan", "tld_debug_qkv_pair_plan", "tld_debug_gemm_epilogue",
     "tld_engine_set_profile", "tld_engine_profile_reserve", "tld_engine_get_profile", "tld_engine_weight_bytes", "tld_engine_destroy",
     "tld_vae_create", "tld_vae_load_tensor", "tld_vae_finalize_weights", "tld_vae_decode", "tld_vae_set_debug",
@@ -63,6 +64,13 @@ class TldConfig(C.Structure):
 class TldSampleRequest(C.Structure):
     """tld_sample_request (include/tld_hip.h): one request's scalars of a tld_sample_requests call."""
     _fields_ = [("n_levels", C.c_int32), ("class_guidance", C.c_float), ("start_mix", C.c_float), ("has_negative", C.c_int32)]
+
+
+class TldSessionRequest(C.Structure):
+    """tld_session_request (include/tld_hip.h): one request of tld_session_admit; host arrays, then device pointers."""
+    _fields_ = [("n_levels", C.c_int32), ("class_guidance", C.c_float), ("has_negative", C.c_int32), ("reserved", C.c_int32),
+                ("coeffs", C.POINTER(C.c_float)), ("guidance", C.POINTER(C.c_float)), ("noise_coeff", C.POINTER(C.c_float)),
+                ("noise_key", C.POINTER(C.c_uint64)), ("noise", C.c_void_p), ("label", C.c_void_p), ("neg_label", C.c_void_p)]
 
 
 class TldVaeConfig(C.Structure):
@@ -158,6 +166,14 @@ def lib() -> C.CDLL:
                                                  C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_float), i32, C.c_float, C.c_float, vp, i32,
                                                  vp, vp, vp]
         L.tld_debug_guidance_shape.argtypes = [vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), i32, i32, vp, vp, vp, vp]
+    if hasattr(L, "tld_session_open"):               # (absent from A/B builds that predate sampler sessions)
+        L.tld_session_open.argtypes = [vp, i32, i32, C.c_float, C.c_float, vp, C.POINTER(vp)]
+        L.tld_session_admit.argtypes = [vp, C.POINTER(TldSessionRequest), vp, C.POINTER(i32)]
+        L.tld_session_step.argtypes = [vp, vp, C.POINTER(i32), i32, C.POINTER(i32)]
+        L.tld_session_latent.argtypes = [vp, i32, C.POINTER(vp)]
+        L.tld_session_copy_latent.argtypes = [vp, i32, vp, vp]
+        L.tld_session_stats.argtypes = [vp, i64p]
+        L.tld_session_close.argtypes = [vp]
     L.tld_engine_set_gemm_dtype.argtypes = [vp, i32]
     L.tld_engine_set_low_latency.argtypes = [vp, i32]
     L.tld_debug_gemm_splitk.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]

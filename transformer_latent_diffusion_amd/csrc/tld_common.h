@@ -324,7 +324,9 @@ enum : int {
     EP_TAIL_FOLD = 16,
     // fused QKV + attention on two-head tiles (EPI_QKV_ATTN2); a launch sets this bit INSTEAD of EP_QKV_ATTN
     EP_QKV_ATTN_PAIR = 61,
-    EP_COUNT = 62
+    // the step of a sampler session (tld_session_step)
+    EP_UPDATE_SESSION = 62,
+    EP_COUNT = 63
 };
 extern thread_local uint64_t* g_path_sink;
 inline void note_path(int bit) { if (g_path_sink) *g_path_sink |= 1ull << bit; }
@@ -457,11 +459,15 @@ struct SamplerStepParams {
     const GuidanceShape* shape_rows;              // sample b reads shape_rows[b * row_stride]; null: no flavour of the kernel reads it
     const float2* shape_pq;                       // [B] written by the stats launch of this step for the rows that are shaped and have a slot
     float* shape_mom;                             // [B, img] read and written where the row's beta != 0
+    // the session flavour only (tld_session_step), on top of SLOT (and NOISE): x_t, x0_prev and out_latent are the session's slot-major
+    // buffers and sample b of the step lives at req_slot[b] * img in them; the Philox counter's step is the row's `reserved`, not noise_step
+    const int* req_slot;                          // [active] device; null: no flavour of the kernel reads it
 };
 // path: the EP_UPDATE* bit that names the flavour of step the calling entry asked for
 // slots (tld_sample_requests_guided): x0_2b is [active cond samples | the unconditional samples of the requests guided at this step], and a row's
 // final_step holds final | (slot + 1) << 1 -- the unconditional operand of the request is sample active + slot; slot + 1 == 0: none, x0 = cond itself
 // p.noise_rows non-null (slots only): the NOISE flavour; p.shape_rows non-null as well: the SHAPE flavour
+// p.req_slot non-null (slots only; no mask, no shape rows, no traces): the session flavour
 void launch_sampler_step(const SamplerStepParams& p, int path, hipStream_t s, bool slots = false);
 // The statistics of the shaped guidance update (tld_guidance_shape.h), one workgroup per request b < active: over cond + b img, the unconditional
 // sample unc_base + slot img (slot from rows[b * row_stride].final_step as the slots flavour of the step packs it) and, where the row's beta != 0,

@@ -10,6 +10,7 @@
 #include "tld_host.h"
 #include "tld_refresh.h"
 #include "tld_sample_plan.h"
+#include "tld_session_plan.h"
 #include "tld_tail_fold_math.h"
 
 #include <cmath>
@@ -89,6 +90,10 @@ struct tld_engine : DeviceArena, BodyShape {      // (pad = 256: every allocatio
     float* shape_mom = nullptr;
     float2* shape_pq = nullptr;
     double* shape_sums = nullptr;
+    // the sampler session open on this engine (tld_session_open), or null; its slot-major buffers [3][sess_slots][img] are kept for the next one
+    tld_session* session = nullptr;
+    float* sess_buf = nullptr;
+    int sess_slots = 0;
 
     // conditioning tables (sized for cond_cap token rows)
     int cond_cap = 0;
@@ -298,8 +303,10 @@ void cond_label_rows(tld_engine* e, int row0, int Tl, hipStream_t s) {
 // share_l0: the model batch is [x_src ; x_src] (CFG doubling), so everything before the first cross-attention --
 // patch embedding, LN1, the QKV GEMM and self-attention of block 0 -- is identical for both halves and is
 // computed for src_batch samples only; block 0's row kernel then fans it out to the 2*src_batch streams.
+// embed_slot (a session step): a device table [batch] for the embed alone -- compact model sample k reads the latent x_src[embed_slot[k]], the
+// slot of its request in the session's slot-major x_t; shared, the embed takes the first src_batch entries.  The fan-out keeps the compact src_row.
 int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const int* noise_row,
-             const int* label_row, float* out, hipStream_t s, bool share_l0 = false, const int* src_row = nullptr) {
+             const int* label_row, float* out, hipStream_t s, bool share_l0 = false, const int* src_row = nullptr, const int* embed_slot = nullptr) {
     const int d = e->d, M = batch * e->ntok;
     share_l0 = share_l0 && e->mode.share_l0 && (src_row ? batch > src_batch && batch <= 2 * src_batch : batch == 2 * src_batch);
     if (int rc = debug_poison(e, s)) return rc;
@@ -314,7 +321,7 @@ int run_body(tld_engine* e, const float* x_src, int src_batch, int batch, const 
         ep.x = x_src; ep.conv_w = e->conv_w; ep.conv_b = e->conv_b; ep.ln1_w = e->pln1_w; ep.ln1_b = e->pln1_b;
         ep.lin_wt = e->plin_wt; ep.lin_w_hl = e->plin_w_hl; ep.lin_b = e->plin_b; ep.ln2_w = e->pln2_w; ep.ln2_b = e->pln2_b; ep.pos = e->pos;
         ep.tok = xe; ep.stats_out = fold1 ? e->ln_stats : nullptr; ep.batch = b0; ep.src_batch = src_batch; ep.C = e->cfg.n_channels;
-        ep.src_row = share_l0 ? nullptr : src_row;               // (shared: the first src_batch samples are the identity)
+        ep.src_row = embed_slot ? embed_slot : share_l0 ? nullptr : src_row;      // (shared: the first src_batch samples are the identity)
         ep.S = e->cfg.image_size; ep.p = e->cfg.patch_size; ep.grid = e->grid; ep.pd = e->pd; ep.d = d;
         ep.ntok = e->ntok;
         launch_embed(ep, s);
@@ -622,6 +629,7 @@ int sample_requests(tld_engine* e, SampleCall& call, const SampleOperands& ops, 
     if (SampleRefusal r = sample_call_check(call)) return fail(r.code, "%s", r.msg.c_str());
     if (!e || !ops.noise || !ops.labels || !ops.out_latent) return fail(TLD_ERR_INVALID, "null argument");
     if (!e->finalized) return fail(TLD_ERR_STATE, "weights not finalized");
+    if (e->session) return fail(TLD_ERR_STATE, "a sampler session is open on this engine: it owns the conditioning tables and the sampler buffers (tld_session_close first)");
     call.guidance_skip = e->mode.guidance_skip; call.max_batch = e->cfg.max_batch;
     if (SampleRefusal r = sample_plan(call, e->plan)) return fail(r.code, "%s", r.msg.c_str());
     DeviceGuard dg(e->cfg.device_id);
@@ -833,6 +841,7 @@ int tld_engine_refresh_weights(tld_engine* e, const float* flat_device, int64_t 
     if (!e->finalized) return fail(TLD_ERR_STATE, "tld_engine_refresh_weights: weights not finalized (the first load goes through tld_engine_load_tensor)");
     if (numel != e->nparam)
         return fail(TLD_ERR_SHAPE, "tld_engine_refresh_weights: the flat vector has %lld elements, this configuration %lld", (long long)numel, (long long)e->nparam);
+    if (e->session) return fail(TLD_ERR_STATE, "tld_engine_refresh_weights: a sampler session is open on this engine: its conditioning rows were made from the weights it opened with (tld_session_close first)");
     DeviceGuard dg(e->cfg.device_id);
     return launch_refresh_weights(e->refresh, flat_device, static_cast<hipStream_t>(hip_stream));
 }
@@ -899,6 +908,7 @@ int tld_denoiser_forward(tld_engine* e, const void* x, const void* noise, const 
                          int32_t batch, int32_t io_dtype, void* hip_stream) {
     if (!e || !x || !noise || !label || !out) return fail(TLD_ERR_INVALID, "null argument");
     if (!e->finalized) return fail(TLD_ERR_STATE, "weights not finalized");
+    if (e->session) return fail(TLD_ERR_STATE, "a sampler session is open on this engine: it owns the conditioning tables (tld_session_close first)");
     if (batch <= 0 || batch > e->cfg.max_batch) return fail(TLD_ERR_INVALID, "batch %d outside (0, max_batch=%d]", batch, e->cfg.max_batch);
     if (io_dtype < 0 || io_dtype > 2) return fail(TLD_ERR_INVALID, "bad io_dtype %d", io_dtype);
     DeviceGuard dg(e->cfg.device_id);
@@ -1114,6 +1124,7 @@ int tld_debug_gemm_bench(int32_t M, int32_t N, int32_t K, int32_t epilogue, int3
 int tld_engine_set_low_latency(tld_engine* e, int32_t on) {
     if (!e) return fail(TLD_ERR_INVALID, "null engine");
     DeviceGuard dg(e->cfg.device_id);
+    if (e->session) return fail(TLD_ERR_STATE, "tld_engine_set_low_latency: a sampler session is open on this engine (tld_session_close first)");
     if (const std::string bad = body_class_refusal(*e, e->cfg.max_batch, on, e->mode.fp8); !bad.empty()) return fail(TLD_ERR_INVALID, "%s", bad.c_str());
     if (const int split = lowlat_split(on)) {
         // (a class-1 buffer is too small for eight slices: allocate anew; the old one is released with the engine)
@@ -1332,8 +1343,247 @@ int tld_debug_attention_fwd(const void* qk, const void* vt, void* att, int32_t b
     return TLD_OK;
 }
 
+}  // extern "C"
+
+// ================================================================================================
+// Sampler sessions: the host state is tld_session_plan.h; here the buffers, the new conditioning rows of an admit and the step
+struct tld_session {
+    tld_engine* e = nullptr;
+    hipStream_t stream = nullptr;
+    float sharp = 0.0f, bright = 0.0f;
+    SessionPlan plan;
+    SessionStep st;
+    SessionAdmit ad;
+    float *xt = nullptr, *x0_prev = nullptr, *out = nullptr;      // [slots, img] each, slot-major
+    // a ring of pinned staging buffers, each behind its own event: the host waits only when it laps the ring
+    static constexpr int kRing = 4;
+    void* stage[kRing] = {};
+    hipEvent_t ev[kRing] = {};
+    bool used[kRing] = {};
+    int head = 0;
+    size_t stage_bytes = 0;
+};
+
+namespace {
+
+// the next staging buffer of the ring; session_staged after the last copy out of it
+int session_stage(tld_session* S, int* k_out) {
+    const int k = S->head;
+    S->head = (k + 1) % tld_session::kRing;
+    if (S->used[k]) HIP_TRY(hipEventSynchronize(S->ev[k]));
+    *k_out = k;
+    return TLD_OK;
+}
+int session_staged(tld_session* S, int k) {
+    HIP_TRY(hipEventRecord(S->ev[k], S->stream));
+    S->used[k] = true;
+    return TLD_OK;
+}
+
+// admit and step: the session's own stream, not capturing
+int session_stream_check(tld_session* S, void* hip_stream) {
+    if (static_cast<hipStream_t>(hip_stream) != S->stream) return fail(TLD_ERR_INVALID, "a session runs on the stream it was opened with: this call names another");
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(S->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+        return fail(TLD_ERR_STATE, "a sampler session cannot be captured into a graph: its membership changes between steps");
+    return TLD_OK;
+}
+
+// Conditioning of rows r0 .. r0 + n - 1 in place: the launchers of run_sampler pointed at a row range (a row's values depend neither on where it sits nor on
+// how many rows the launch carries).  kind: SR_SIGMA from c_sigma, SR_LABEL / SR_ZERO from c_label; then LayerNorm, per-layer K|V and the folded query vectors
+void session_cond_rows(tld_engine* e, int kind, int r0, int n, hipStream_t s) {
+    const size_t d = e->d, cap = (size_t)e->cond_cap, H = e->H, ne = e->ne, text = e->text;
+    float* pre = e->c_pre + (size_t)r0 * d;
+    if (kind == SR_SIGMA) {
+        launch_sinusoid(e->c_sigma + r0, e->angular, e->c_sin + (size_t)r0 * ne, n, e->ne / 2, s);
+        launch_linear_f32(e->c_sin + (size_t)r0 * ne, e->ne, e->ff1_w, e->ff1_b, e->c_h1 + (size_t)r0 * d, e->d, n, e->ne, e->d, 1, s);
+        launch_linear_f32(e->c_h1 + (size_t)r0 * d, e->d, e->ff3_w, e->ff3_b, pre, e->d, n, e->d, e->d, 0, s);
+    } else {
+        launch_linear_f32(e->c_label + (size_t)r0 * text, e->text, e->label_w, e->label_b, pre, e->d, n, e->text, e->d, 0, s);
+    }
+    launch_layernorm_f32(pre, e->norm_w, e->norm_b, e->c_y + (size_t)r0 * d, n, e->d, s);
+    launch_linear_f32_layers(e->c_y + (size_t)r0 * d, e->d, e->tab_kv_w, e->c_kv + (size_t)r0 * 2 * d, cap * 2 * d, 2 * e->d, n, e->d, 2 * e->d, e->L, s);
+    launch_wq_layers(e->c_kv + (size_t)r0 * 2 * d, cap * 2 * d, 2 * e->d, e->tab_q_w, e->tab_n2_w, e->tab_n2_b, e->c_wq + (size_t)r0 * H * d, cap * H * d,
+                     e->c_bwq + (size_t)r0 * H, cap * H, n, e->H, e->d, e->L, s);
+}
+
+void session_free(tld_session* S) {
+    for (int k = 0; k < tld_session::kRing; ++k) {
+        if (S->ev[k]) (void)hipEventDestroy(S->ev[k]);
+        if (S->stage[k]) (void)hipHostFree(S->stage[k]);
+    }
+    delete S;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tld_session_open(tld_engine* e, int32_t slots, int32_t cond_rows, float sharp_f, float bright_f, void* hip_stream, tld_session** out) {
+    if (!e || !out) return fail(TLD_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (!e->finalized) return fail(TLD_ERR_STATE, "weights not finalized");
+    if (e->session) return fail(TLD_ERR_STATE, "a sampler session is already open on this engine: one session per engine");
+    if (SampleRefusal r = session_open_check(slots, cond_rows, e->cfg.max_batch)) return fail(r.code, "%s", r.msg.c_str());
+    DeviceGuard dg(e->cfg.device_id);
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+        return fail(TLD_ERR_STATE, "a sampler session cannot be captured into a graph: its membership changes between steps");
+    tld_session* S = new tld_session();
+    S->e = e; S->stream = s; S->sharp = sharp_f; S->bright = bright_f;
+    S->plan.open(slots, cond_rows, e->mode.guidance_skip);
+    auto setup = [&]() -> int {
+        if (int rc = ensure_cond_capacity(e, cond_rows)) return rc;
+        if (int rc = ensure_req_capacity(e, S->plan.max_up_bytes())) return rc;
+        if (slots > e->sess_slots) {      // (grow-only, like every buffer of the arena)
+            if (int rc = dev_alloc(e, &e->sess_buf, (size_t)3 * slots * e->img)) return rc;
+            e->sess_slots = slots;
+        }
+        S->xt = e->sess_buf; S->x0_prev = S->xt + (size_t)slots * e->img; S->out = S->x0_prev + (size_t)slots * e->img;
+        S->stage_bytes = (std::max(S->plan.max_up_bytes(), (size_t)cond_rows * sizeof(float)) + 4095) & ~(size_t)4095;
+        for (int k = 0; k < tld_session::kRing; ++k) {
+            HIP_TRY(hipHostMalloc(&S->stage[k], S->stage_bytes, hipHostMallocDefault));
+            HIP_TRY(hipEventCreateWithFlags(&S->ev[k], hipEventDisableTiming));
+        }
+        // row 0: the zero label (diffusion.py:61)
+        HIP_TRY(hipMemsetAsync(e->c_label, 0, (size_t)e->text * sizeof(float), s));
+        {
+            ProfScope ps(e, KC_COND, s);
+            session_cond_rows(e, SR_ZERO, 0, 1, s);
+        }
+        HIP_TRY(hipGetLastError());
+        return TLD_OK;
+    };
+    if (int rc = setup()) { session_free(S); return rc; }
+    e->session = S;
+    *out = S;
+    return TLD_OK;
+}
+
+int tld_session_admit(tld_session* S, const tld_session_request* r, void* hip_stream, int32_t* slot_out) {
+    // the record first: its checks need no session and no device
+    if (SampleRefusal bad = session_request_check(r)) return fail(bad.code, "%s", bad.msg.c_str());
+    if (!S || !slot_out || !r->noise || !r->label) return fail(TLD_ERR_INVALID, "null argument");
+    *slot_out = -1;
+    tld_engine* e = S->e;
+    DeviceGuard dg(e->cfg.device_id);
+    if (int rc = session_stream_check(S, hip_stream)) return rc;
+    if (SampleRefusal bad = session_admit(S->plan, *r, S->ad)) return fail(bad.code, "%s", bad.msg.c_str());
+    const SessionAdmit& ad = S->ad;
+    if (ad.slot < 0) return TLD_OK;      // no room now
+    hipStream_t s = S->stream;
+    const size_t img = (size_t)e->img, text = (size_t)e->text;
+    HIP_TRY(hipMemcpyAsync(S->xt + (size_t)ad.slot * img, r->noise, img * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemsetAsync(S->x0_prev + (size_t)ad.slot * img, 0, img * sizeof(float), s));
+    HIP_TRY(hipMemcpyAsync(e->c_label + (size_t)ad.label_row * text, r->label, text * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (ad.neg_row >= 0) HIP_TRY(hipMemcpyAsync(e->c_label + (size_t)ad.neg_row * text, r->neg_label, text * sizeof(float), hipMemcpyDeviceToDevice, s));
+    const size_t ns = ad.new_sigma.size();
+    if (ns) {      // the new sigmas through a staging buffer of the ring, one copy and one set of launches per contiguous run of rows
+        int k = 0;
+        if (int rc = session_stage(S, &k)) return rc;
+        float* sig = static_cast<float*>(S->stage[k]);
+        for (size_t j = 0; j < ns; ++j) sig[j] = ad.new_sigma[j].second;
+        for (size_t j = 0; j < ns; ) {
+            size_t j1 = j + 1;
+            while (j1 < ns && ad.new_sigma[j1].first == ad.new_sigma[j1 - 1].first + 1) ++j1;
+            HIP_TRY(hipMemcpyAsync(e->c_sigma + ad.new_sigma[j].first, sig + j, (j1 - j) * sizeof(float), hipMemcpyHostToDevice, s));
+            j = j1;
+        }
+        if (int rc = session_staged(S, k)) return rc;
+    }
+    {
+        ProfScope ps(e, KC_COND, s);
+        for (size_t j = 0; j < ns; ) {
+            size_t j1 = j + 1;
+            while (j1 < ns && ad.new_sigma[j1].first == ad.new_sigma[j1 - 1].first + 1) ++j1;
+            session_cond_rows(e, SR_SIGMA, ad.new_sigma[j].first, (int)(j1 - j), s);
+            j = j1;
+        }
+        if (ad.neg_row == ad.label_row + 1) session_cond_rows(e, SR_LABEL, ad.label_row, 2, s);
+        else {
+            session_cond_rows(e, SR_LABEL, ad.label_row, 1, s);
+            if (ad.neg_row >= 0) session_cond_rows(e, SR_LABEL, ad.neg_row, 1, s);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    *slot_out = ad.slot;
+    return TLD_OK;
+}
+
+int tld_session_step(tld_session* S, void* hip_stream, int32_t* finished_slots, int32_t cap, int32_t* n_finished) {
+    if (!S || !finished_slots || !n_finished) return fail(TLD_ERR_INVALID, "null argument");
+    *n_finished = 0;
+    if (cap < S->plan.slots) return fail(TLD_ERR_INVALID, "finished_slots has room for %d slots: a step of this session may finish %d", cap, S->plan.slots);
+    tld_engine* e = S->e;
+    DeviceGuard dg(e->cfg.device_id);
+    if (int rc = session_stream_check(S, hip_stream)) return rc;
+    if (!S->plan.live) return TLD_OK;      // nothing to run: nothing is enqueued
+    hipStream_t s = S->stream;
+    int k = 0;
+    if (int rc = session_stage(S, &k)) return rc;
+    SessionStep& st = S->st;
+    session_step(S->plan, st, S->stage[k]);
+    for (size_t j = 0; j < st.finished.size(); ++j) finished_slots[j] = st.finished[j];
+    *n_finished = (int32_t)st.finished.size();
+    HIP_TRY(hipMemcpyAsync(e->req_dev, S->stage[k], st.up_bytes, hipMemcpyHostToDevice, s));      // the one upload of the step
+    if (int rc = session_staged(S, k)) return rc;
+    const char* dev = static_cast<const char*>(e->req_dev);
+    const int Bi = st.Bi, mb = st.mb;
+    const int *rs = reinterpret_cast<const int*>(dev + st.ints_off), *nr = rs + Bi, *lr = nr + mb, *sr = lr + mb, *es = sr + mb;
+    PathScope paths(e);                      // (debug: the launch paths are recorded and no stage is kept, as for the requests entries)
+    if (e->debug) e->paths = 0;
+    if (int rc = run_body(e, S->xt, Bi, mb, nr, lr, e->io_out, s, true, sr, es)) return rc;
+    SamplerStepParams up{};
+    up.x0_2b = e->io_out; up.x_t = S->xt; up.x0_prev = S->x0_prev; up.out_latent = S->out;
+    up.rows = reinterpret_cast<const SamplerStepRow*>(dev); up.row_stride = 1; up.sharp = S->sharp; up.bright = S->bright;
+    up.active = Bi; up.img = e->img; up.chan_stride = e->cfg.image_size * e->cfg.image_size;
+    if (st.noise) up.noise_rows = reinterpret_cast<const SamplerNoiseRow*>(dev + st.noise_off);
+    up.req_slot = rs;
+    {
+        ProfScope ps(e, KC_UPDATE, s);
+        launch_sampler_step(up, EP_UPDATE_SESSION, s, true);
+    }
+    HIP_TRY(hipGetLastError());
+    return TLD_OK;
+}
+
+int tld_session_latent(tld_session* S, int32_t slot, const float** device_ptr) {
+    if (!S || !device_ptr) return fail(TLD_ERR_INVALID, "null argument");
+    if (slot < 0 || slot >= S->plan.slots) return fail(TLD_ERR_INVALID, "slot %d outside [0, %d)", slot, S->plan.slots);
+    *device_ptr = S->out + (size_t)slot * S->e->img;
+    return TLD_OK;
+}
+
+int tld_session_copy_latent(tld_session* S, int32_t slot, void* dst_device, void* hip_stream) {
+    if (!S || !dst_device) return fail(TLD_ERR_INVALID, "null argument");
+    if (slot < 0 || slot >= S->plan.slots) return fail(TLD_ERR_INVALID, "slot %d outside [0, %d)", slot, S->plan.slots);
+    DeviceGuard dg(S->e->cfg.device_id);
+    if (int rc = session_stream_check(S, hip_stream)) return rc;
+    HIP_TRY(hipMemcpyAsync(dst_device, S->out + (size_t)slot * S->e->img, (size_t)S->e->img * sizeof(float), hipMemcpyDeviceToDevice, S->stream));
+    return TLD_OK;
+}
+
+int tld_session_stats(const tld_session* S, int64_t* out) {
+    if (!S || !out) return fail(TLD_ERR_INVALID, "null argument");
+    out[0] = S->plan.live; out[1] = S->plan.steps; out[2] = S->plan.rows_cond; out[3] = S->plan.rows_uncond; out[4] = S->plan.rows_used;
+    return TLD_OK;
+}
+
+int tld_session_close(tld_session* S) {
+    if (!S) return TLD_OK;
+    tld_engine* e = S->e;
+    DeviceGuard dg(e->cfg.device_id);
+    for (int k = 0; k < tld_session::kRing; ++k)
+        if (S->used[k]) (void)hipEventSynchronize(S->ev[k]);      // (the copies out of the pinned buffers have run before they are freed)
+    e->session = nullptr;
+    session_free(S);
+    return TLD_OK;
+}
+
 int tld_engine_destroy(tld_engine* e) {
     if (!e) return TLD_OK;
+    if (e->session) (void)tld_session_close(e->session);
     DeviceGuard dg(e->cfg.device_id);
     (void)hipDeviceSynchronize();
     for (int k = 0; k < KC_COUNT; ++k)

@@ -1266,7 +1266,11 @@ __global__ __launch_bounds__(256) void guidance_shape_debug_kernel(const float* 
 // SHAPE (tld_sample_requests_shaped), on top of SLOT and NOISE: a request whose shape row is not neutral and which has an unconditional
 // slot at this step and a guidance other than 1.0f takes x0 = fma(P, cond, Q dbar), dbar = cond - unc (+ beta m), with (P, Q) from this step's guidance_stats_kernel launch, and where
 // beta != 0 an inner step stores m <- dbar.  Every other request takes `combine` as it stands and touches neither table nor buffer.
-template <bool MASK, int V, bool SLOT = false, bool NOISE = false, bool SHAPE = false>
+// SESS (tld_session_step), on top of SLOT: the step's model output is compact (request b of the step's live set at b img, its
+// unconditional sample at (active + slot) img) while x_t, x0_prev and out_latent are the session's slot-major buffers, read and written at
+// req_slot[b] img; and a request's forward index -- the step of its noise counter -- comes from its noise row's `reserved`, since every live request sits at its own level.
+// The arithmetic is the code above and below, untouched.
+template <bool MASK, int V, bool SLOT = false, bool NOISE = false, bool SHAPE = false, bool SESS = false>
 __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p) {
 #pragma clang fp contract(off)
     const int i = (blockIdx.x * 256 + threadIdx.x) * V;
@@ -1285,6 +1289,7 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p) 
     const int ch = r / p.chan_stride;
     const SamplerStepRow q = p.rows[b * p.row_stride];
     load(cond, p.x0_2b + i);
+    const size_t si = SESS ? (size_t)p.req_slot[b] * p.img + r : (size_t)i;      // where the sample's state lives
     const int slot = SLOT ? (q.final_step >> 1) - 1 : 0;
     const bool final_step = SLOT ? (q.final_step & 1) != 0 : q.final_step != 0;
     if constexpr (SLOT) {
@@ -1330,11 +1335,11 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p) 
             if (ch == 0) x0 += p.bright;                                  // diffusion.py:89
             x0o[v] = x0;
         }
-        store(p.out_latent + i, x0o);
+        store(p.out_latent + si, x0o);
         return;
     }
-    load(prev, p.x0_prev + i);
-    load(xin, p.x_t + i);
+    load(prev, p.x0_prev + si);
+    load(xin, p.x_t + si);
     if constexpr (MASK) load(eps, p.noise + i);
     float en = 0.0f, nz[V];
     if constexpr (NOISE) {
@@ -1342,7 +1347,7 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p) 
         en = nq.e;
         if (en != 0.0f) {
             float n4[4];
-            sampler_noise4(nq.key_lo, nq.key_hi, p.noise_step, (uint32_t)r >> 2, n4);
+            sampler_noise4(nq.key_lo, nq.key_hi, SESS ? nq.reserved : p.noise_step, (uint32_t)r >> 2, n4);
             if constexpr (V == 4) {
 #pragma unroll
                 for (int v = 0; v < 4; ++v) nz[v] = n4[v];
@@ -1366,8 +1371,8 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepParams p) 
         xto[v] = xt;
     }
     if (p.trace_x0) store(p.trace_x0 + i, x0o);
-    store(p.x_t + i, xto);
-    store(p.x0_prev + i, x0o);
+    store(p.x_t + si, xto);
+    store(p.x0_prev + si, x0o);
     if (p.trace_xt) store(p.trace_xt + i, xto);
     if constexpr (SHAPE) { if (shaped && sbeta != 0.0f) store(p.shape_mom + i, dbo); }
 }
@@ -1836,6 +1841,14 @@ void launch_sampler_step(const SamplerStepParams& p, int path, hipStream_t s, bo
     const int threads = vec ? n / 4 : n;
     const dim3 grid((threads + 255) / 256), block(256);
     note_path(path);
+    if (p.req_slot) {       // the session flavour: SLOT, with or without NOISE; no mask, no shape, no traces (tld_session_step passes none)
+        with_bool(vec, [&](auto v4) {
+            with_bool(p.noise_rows != nullptr, [&](auto nz) {
+                hipLaunchKernelGGL((sampler_step_kernel<false, decltype(v4)::value ? 4 : 1, true, decltype(nz)::value, false, true>), grid, block, 0, s, p);
+            });
+        });
+        return;
+    }
     // the flavours nest: plain, SLOT, SLOT + NOISE, SLOT + NOISE + SHAPE
     const int flavour = !slots ? 0 : !p.noise_rows ? 1 : !p.shape_rows ? 2 : 3;
     with_bool(p.mask != nullptr, [&](auto mask) {

@@ -64,6 +64,7 @@ class Denoiser:
         self._engine_skip = True          # the engine's TLD_GUIDANCE_SKIP, as tld_engine_create read it
         self._gemm_dtype = 0              # 0: bf16 operands; 1: MX-fp8 QKV / MLP GEMMs (set_gemm_dtype)
         self._low_latency = 0             # capacity class for small batches (set_low_latency): 0 default, 1 / 2 = split-K down projection in four / eight splits
+        self._session = None              # the sampler session open on the engine (open_session), or None
         self.training = False
 
     # ---- nn.Module-like surface ------------------------------------------------------------------
@@ -176,6 +177,8 @@ class Denoiser:
 
     # ---- engine management ---------------------------------------------------------------------------
     def _drop_engine(self):
+        if self._session is not None:                        # (the engine goes, and its session with it)
+            self._session.close()
         if self._engine is not None:
             _lib.lib().tld_engine_destroy(self._engine)       # (the C ABI restores the caller's current device)
         self._engine = None
@@ -198,6 +201,9 @@ class Denoiser:
     def _ensure_engine(self, model_batch: int, dev: torch.device):
         if self._engine is not None and self._engine_batch >= model_batch and self._engine_device == dev:
             return self._engine
+        if self._session is not None and not self._session.closed:
+            raise RuntimeError(f"a sampler session is open on this model's engine (capacity {self._engine_batch} model samples): a call that needs a new "
+                               f"engine ({model_batch} on {dev}) would destroy it; close the session first")
         self._drop_engine()
         L = _lib.lib()
         cap = model_batch if self._low_latency else max(model_batch, 8)       # (the low-latency class is bounded by capacity: no head-room there)
@@ -522,6 +528,30 @@ class Denoiser:
             getattr(_lib.lib(), entry)(h, eps, z0, m, lab, ng, recs, fp(table), *extra, n_max, float(sharp_f), float(bright_f), out, B, tx0, txt, stream),
             entry), model_batch=model_batch, **common)
 
+    def open_session(self, slots: int, cond_rows: Optional[int] = None, sharp_f: float = 0.0, bright_f: float = 0.0, device=None) -> "DenoiserSession":
+        """A sampler session on this model's engine (``tld_session_open``), the raw form: ``slots`` requests run at once, each
+        at its own level, and requests are admitted between steps.  ``cond_rows``: the session's conditioning-row table (the zero row, one or
+        two label rows per live request and one shared row per distinct noise level); default ``min(1024, 1 + slots * 66)``, room for ``slots``
+        requests of 64 levels on distinct schedules.  The engine is reserved for ``2 * slots`` model samples.  One session per model at a time; while
+        it is open the other calls of this model raise (``TLD_ERR_STATE``)."""
+        if self._session is not None and not self._session.closed:
+            raise RuntimeError("a sampler session is already open on this model: one session per engine")
+        slots = int(slots)
+        if slots < 1:
+            raise ValueError(f"open_session: slots = {slots}: at least one")
+        if device is not None:
+            self.to(device)
+        dev = self._resolve_device()
+        rows = min(1024, 1 + slots * 66) if cond_rows is None else int(cond_rows)
+        h = self._ensure_engine(2 * slots, dev)
+        out = C.c_void_p()
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            _lib.check(_lib.lib().tld_session_open(h, slots, rows, float(sharp_f), float(bright_f), C.c_void_p(stream.cuda_stream), C.byref(out)),
+                       "tld_session_open")
+        self._session = DenoiserSession(self, out, slots, rows, dev)
+        return self._session
+
     # ---- test / bench hooks -----------------------------------------------------------------------------
     # launch paths of tld_engine_debug_paths, by bit number (include/tld_hip.h; None: a bit no default engine sets).  "tail folded" (out_proj folded into
     # the last block's down projection) comes with the tail_mfma<NT> bit of its patch-feature tiles.  Bit 49, the VALU tail of widths that are no multiple
@@ -544,6 +574,8 @@ class Denoiser:
 
     # the launch paths of sample_latents_requests, by bit number
     SAMPLER_PATH_NAMES = {58: "update_requests", 59: "update_requests masked", 60: "start_mix per request"}
+    # ... and of a sampler session's step
+    SESSION_PATH_NAMES = {62: "update_session"}
 
     def sample_rows(self):
         """``(cond, uncond)``: the model samples the last sampler call on this model's engine enqueued (``tld_engine_sample_rows``); the CFG-doubled
@@ -597,3 +629,120 @@ class Denoiser:
         _lib.check(_lib.lib().tld_engine_get_profile(self._engine, _lib.KERNEL_CLASSES.index(cls), C.byref(ms),
                                                      C.byref(n)), "tld_engine_get_profile")
         return ms.value, n.value
+
+
+class DenoiserSession:
+    """A sampler session on a ``Denoiser``'s engine (``Denoiser.open_session``; ``tld_session_*``), the raw form: slots,
+    tables and device tensors.  ``DiffusionGenerator.open_session`` builds requests the way the ``generate_latents*`` calls do.  A context manager;
+    every call runs on the stream that was current at ``open_session`` and raises on another one."""
+
+    def __init__(self, model: Denoiser, handle, slots: int, cond_rows: int, dev: torch.device):
+        self.model, self._h, self.slots, self.cond_rows, self.device = model, handle, slots, cond_rows, dev
+        self.closed = False
+        self._keep = {}                   # slot -> the device tensors of the request in it (they must outlive the copies admit enqueues)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _open(self):
+        if self.closed:
+            raise RuntimeError("the sampler session is closed")
+
+    @torch.no_grad()
+    def admit(self, noise: torch.Tensor, label: torch.Tensor, coeffs, guidance: float = 3.0, *, neg_label=None, guidance_steps=None, noise_coeff=None,
+              noise_key=None):
+        """One request into a free slot (``tld_session_admit``): ``noise`` [C,S,S] (or [1,C,S,S]), ``label`` [text], ``coeffs`` its table
+        ``schedule.step_coefficients(...)``, ``guidance`` its scale or ``guidance_steps`` one value per forward, ``neg_label`` [text] or None,
+        ``noise_coeff`` + ``noise_key`` (both or neither) as in ``sample_latents_requests``.  Returns the slot, or None when the session has no
+        room now (no free slot, or too few free conditioning rows): ask again after a ``step``."""
+        self._open()
+        m = self.model
+        want = (m.n_channels, m.image_size, m.image_size)
+        if tuple(noise.shape) == (1,) + want:
+            noise = noise[0]
+        if tuple(noise.shape) != want:
+            raise ValueError(f"noise {tuple(noise.shape)}: expected {want}")
+        if tuple(label.shape) == (1, m.text_emb_size):
+            label = label[0]
+        if tuple(label.shape) != (m.text_emb_size,):
+            raise ValueError(f"label {tuple(label.shape)}: expected {(m.text_emb_size,)}")
+        if neg_label is not None and tuple(neg_label.shape) != (m.text_emb_size,):
+            raise ValueError(f"neg_label {tuple(neg_label.shape)}: expected {(m.text_emb_size,)}")
+        co = np.ascontiguousarray(coeffs, dtype=np.float32)
+        if co.ndim != 2 or co.shape[1] != 6 or co.shape[0] < 2:
+            raise ValueError(f"coeffs {co.shape}: expected [n_levels >= 2, 6]")
+        n = co.shape[0]
+        if (noise_coeff is None) != (noise_key is None):
+            raise ValueError("noise_coeff and noise_key come together")
+        fp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
+        gs = ec = None
+        if guidance_steps is not None:
+            gs = np.ascontiguousarray(guidance_steps, dtype=np.float32)
+            if gs.shape != (n,):
+                raise ValueError(f"guidance_steps {gs.shape}: expected [{n}], one value per forward")
+        if noise_coeff is not None:
+            ec = np.ascontiguousarray(noise_coeff, dtype=np.float32)
+            if ec.shape != (n,):
+                raise ValueError(f"noise_coeff {ec.shape}: expected [{n}], one value per forward")
+            if not 0 <= int(noise_key) < 1 << 64:
+                raise ValueError(f"noise_key = {noise_key}: expected a 64-bit unsigned value")
+        key = None if noise_key is None else C.c_uint64(int(noise_key))
+        dev = self.device
+        t = lambda x: None if x is None else x.detach().to(device=dev, dtype=torch.float32).contiguous()
+        eps, lab, neg = t(noise), t(label), t(neg_label)
+        ptr = lambda x: C.c_void_p(None if x is None else x.data_ptr())
+        rq = _lib.TldSessionRequest(n, float(1.0 if gs is not None else guidance), int(neg is not None), 0, fp(co), fp(gs), fp(ec),
+                                    None if key is None else C.pointer(key), ptr(eps), ptr(lab), ptr(neg))
+        slot = C.c_int32(-1)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().tld_session_admit(self._h, C.byref(rq), self._stream(), C.byref(slot)), "tld_session_admit")
+        if slot.value < 0:
+            return None
+        self._keep[slot.value] = (eps, lab, neg)
+        return int(slot.value)
+
+    @torch.no_grad()
+    def step(self):
+        """One model forward for every live request, each at its own level, and one elementwise update (``tld_session_step``); returns the slots
+        whose request ran its final forward (ascending).  With no live request nothing is enqueued."""
+        self._open()
+        done, n = (C.c_int32 * self.slots)(), C.c_int32(0)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().tld_session_step(self._h, self._stream(), done, self.slots, C.byref(n)), "tld_session_step")
+        return [int(done[k]) for k in range(n.value)]
+
+    @torch.no_grad()
+    def latent(self, slot: int) -> torch.Tensor:
+        """A copy [C,S,S] of the slot's result, enqueued on the session's stream: the latent of the request that last finished in it."""
+        self._open()
+        m = self.model
+        out = torch.empty(m.n_channels, m.image_size, m.image_size, device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().tld_session_copy_latent(self._h, int(slot), C.c_void_p(out.data_ptr()), self._stream()), "tld_session_copy_latent")
+        return out
+
+    def stats(self) -> dict:
+        self._open()
+        v = (C.c_int64 * 5)()
+        _lib.check(_lib.lib().tld_session_stats(self._h, v), "tld_session_stats")
+        return dict(live=int(v[0]), steps=int(v[1]), rows_cond=int(v[2]), rows_uncond=int(v[3]), cond_rows_used=int(v[4]))
+
+    @property
+    def live(self) -> int:
+        return self.stats()["live"]
+
+    def close(self):
+        if self.closed:
+            return
+        self.closed = True
+        _lib.lib().tld_session_close(self._h)
+        self._keep.clear()
+        if self.model._session is self:
+            self.model._session = None

@@ -367,6 +367,19 @@ class DiffusionGenerator:
         kw.pop("trace", None)
         return self._decode(self.generate_latents_requests(labels, **kw), scale_factor)
 
+    def open_session(self, slots: int, img_size: Optional[int] = None, sharp_f: float = 0.1, bright_f: float = 0.1, cond_rows: Optional[int] = None) -> "SamplerSession":
+        """A sampler session: up to ``slots`` requests run at once, each at its own level; ``SamplerSession.admit`` puts a
+        request in between steps, ``step`` runs one model forward for every live request, and a request leaves at its final forward with, bit for
+        bit, the latent ``generate_latents_requests`` returns for it alone.  ``sharp_f`` / ``bright_f`` are per session.  Use it as a context manager."""
+        size = self.model.image_size if img_size is None else int(img_size)
+        if size != self.model.image_size:
+            raise ValueError(f"img_size {size}: a session runs at the model's own size {self.model.image_size}")
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise ValueError("sharded sampling is not part of a sampler session: open one session per rank's own requests")
+        self.model.eval()
+        return SamplerSession(self, self.model.open_session(slots, cond_rows, sharp_f, bright_f, device=self.device))
+
     def _noise(self, seeds, num_imgs, img_size, seed):
         """``initialize_image`` where ``seeds`` may also be one int per image: image i then starts from its own
         ``initialize_image(None, 1, img_size, seeds[i])``, the noise of a one-image call with that seed."""
@@ -706,6 +719,162 @@ class DiffusionTransformer:
                                              exponent=1, scale_factor=8, sharp_f=0, bright_f=0)
         pic = to_pil(((out[0] + 1) / 2).float().clip(0, 1))
         return (pic, latents) if return_latents else pic
+
+class SamplerSession:
+    """A sampler session of a ``DiffusionGenerator`` (``open_session``).  Requests are built by the helpers the
+    ``generate_latents*`` calls use (``_trajectory``, ``schedule.guidance_table``, ``schedule.noise_key``), so a request's tables are the solo call's
+    tables and its latent the solo call's latent, bit for bit."""
+
+    # what a request of the other sampler entries may bring and a session does not take
+    OUT_OF_SCOPE = {"init_latents": "init_latents (image-to-image)", "strength": "strength (start_mix < 1)", "mask": "mask (inpainting)",
+                    "guidance_rescale": "guidance_rescale (the guidance shape)", "apg_eta": "apg_eta (the guidance shape)",
+                    "apg_norm": "apg_norm (the guidance shape)", "apg_momentum": "apg_momentum (the guidance shape)", "trace": "trace"}
+
+    def __init__(self, generator: "DiffusionGenerator", raw):
+        self.generator, self.raw = generator, raw
+        self._ticket_of = {}              # slot -> ticket of the request in it
+        self._next = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    @torch.no_grad()
+    def admit(self, label: Tensor, *, n_iter=30, class_guidance=3, negative_label=None, seed=10, noise=None, exponent=1, use_ddpm_plus=True,
+              noise_levels=None, guidance_interval=None, guidance_schedule=None, eta=0.0, noise_seed=None, **other):
+        """One request: ``label`` [text] (or [1,text]) and the scalars of ``generate_latents_requests`` for one request.  ``noise``: its start noise
+        [C,S,S], else ``initialize_image(None, 1, size, seed)``.  ``eta > 0``: its noise key is ``noise_seed``, else ``schedule.noise_key(seed)``
+        (a ``noise`` tensor carries no seed: ``noise_seed`` is then required).  Returns a ticket, or None when the session has no room now."""
+        for k in other:
+            if k in self.OUT_OF_SCOPE:
+                raise ValueError(f"{self.OUT_OF_SCOPE[k]} is not part of a sampler session")
+            raise TypeError(f"admit() got an unexpected keyword argument {k!r}")
+        gen = self.generator
+        eta = schedule.check_eta(eta)
+        if not np.isfinite(float(class_guidance)):
+            raise ValueError(f"class_guidance = {class_guidance} is not finite")
+        if int(n_iter) < 2 and noise_levels is None:
+            raise ValueError(f"n_iter = {n_iter}: a trajectory needs at least two noise levels")
+        key = ecs = None
+        if eta > 0.0:
+            if noise_seed is None and noise is not None:
+                raise ValueError("eta > 0 with the start noise given as a tensor needs noise_seed: a tensor carries no seed to derive the noise key from")
+            key = schedule.noise_key(seed, 0) if noise_seed is None else int(noise_seed) & 0xFFFFFFFFFFFFFFFF
+            coeffs, _, ecs = gen._trajectory_noise(int(n_iter), exponent, noise_levels, None, bool(use_ddpm_plus), eta)
+        else:
+            coeffs, _ = gen._trajectory(int(n_iter), exponent, noise_levels, None, bool(use_ddpm_plus))
+        steps = None
+        if guidance_schedule is not None:
+            steps = np.ascontiguousarray(torch.as_tensor(guidance_schedule).detach().cpu().numpy() if isinstance(guidance_schedule, Tensor) else guidance_schedule,
+                                         dtype=np.float32)
+            if steps.ndim != 1 or steps.shape[0] != coeffs.shape[0]:
+                raise ValueError(f"guidance_schedule {steps.shape}: expected [{coeffs.shape[0]}], one value per forward")
+            if not np.isfinite(steps).all():
+                raise ValueError("guidance_schedule holds a value that is not finite")
+        elif guidance_interval is not None:
+            steps = schedule.guidance_table(coeffs, float(class_guidance), per_request_intervals(guidance_interval, 1)[0])
+        size = gen.model.image_size
+        eps = gen.initialize_image(None, 1, size, int(seed)) if noise is None else noise.to(gen.device, gen.model_dtype)
+        slot = self.raw.admit(eps, label.to(gen.device), coeffs, float(class_guidance), neg_label=negative_label, guidance_steps=steps, noise_coeff=ecs,
+                              noise_key=key)
+        if slot is None:
+            return None
+        ticket = self._next
+        self._next += 1
+        self._ticket_of[slot] = ticket
+        return ticket
+
+    @torch.no_grad()
+    def step(self):
+        """One step of every live request; returns ``{ticket: latent [C,S,S]}`` of the requests that finished in it (copies, in ``model_dtype``)."""
+        return {self._ticket_of.pop(slot): self.raw.latent(slot).to(self.generator.model_dtype) for slot in self.raw.step()}
+
+    @property
+    def live(self) -> int:
+        return self.raw.live
+
+    def stats(self) -> dict:
+        return self.raw.stats()
+
+    def close(self):
+        self.raw.close()
+
+
+class ContinuousBatcher:
+    """Serving-side batching with admission between steps (beside ``RequestBatcher``): one sampler session of ``slots``
+    slots over the pipeline's denoiser.  ``submit`` encodes the text and queues the request; ``step`` admits queued requests in submission order
+    while the session has room, runs one step and returns ``{ticket: PIL.Image}`` for the requests that finished; ``drain`` steps until nothing is
+    queued or live.  A request's picture is what ``generate_images_from_texts`` returns for that prompt alone."""
+
+    def __init__(self, pipeline: "DiffusionTransformer", slots: int = 8):
+        self.pipeline = pipeline
+        self.session = pipeline.diffuser.open_session(slots, sharp_f=0, bright_f=0)
+        self._queue = []                  # (ticket, label, negative label, admit keywords)
+        self._ticket_of = {}              # the session's ticket -> ours
+        self._next = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def close(self):
+        self.session.close()
+
+    @torch.no_grad()
+    def submit(self, prompt: str, class_guidance: float = 6, seed: int = 11, n_iter: int = 15, negative_prompt: Optional[str] = None,
+               guidance_interval=None, eta: float = 0.0, guidance_rescale: float = 0.0, apg_eta: float = 1.0, apg_norm: float = 0.0,
+               apg_momentum: float = 0.0) -> int:
+        eta = schedule.check_eta(eta)
+        if not schedule.guidance_shape_neutral(schedule.check_guidance_shape(guidance_rescale, apg_eta, apg_norm, apg_momentum)):
+            raise ValueError("the guidance shape (guidance_rescale / apg_*) is not part of a sampler session: use RequestBatcher(mixed=True)")
+        interval = per_request_intervals(guidance_interval, 1)[0] if guidance_interval is not None else None
+        if int(n_iter) < 2:
+            raise ValueError(f"n_iter = {n_iter}: a trajectory needs at least two noise levels")
+        labels, neg = self.pipeline._encode_with_negatives([str(prompt)], None if negative_prompt is None else [str(negative_prompt)])
+        kw = dict(n_iter=int(n_iter), class_guidance=float(class_guidance), seed=int(seed), exponent=1, guidance_interval=interval)
+        if eta > 0.0:
+            kw.update(eta=eta, noise_seed=schedule.noise_key(int(seed)))
+        ticket = self._next
+        self._next += 1
+        self._queue.append((ticket, labels[0], None if neg is None else neg[0], kw))
+        return ticket
+
+    def pending(self) -> int:
+        return len(self._queue)
+
+    @property
+    def live(self) -> int:
+        return self.session.live
+
+    @torch.no_grad()
+    def step(self):
+        while self._queue:
+            ticket, label, neg, kw = self._queue[0]
+            t = self.session.admit(label, negative_label=neg, **kw)
+            if t is None:
+                break
+            self._ticket_of[t] = ticket
+            self._queue.pop(0)
+        done = self.session.step()
+        if not done:
+            return {}
+        order = sorted(done)
+        out = self.pipeline.diffuser._decode(torch.stack([done[t] for t in order]), 8)[0]      # scale_factor 8 (diffusion.py:180)
+        return {self._ticket_of.pop(t): to_pil(((out[i] + 1) / 2).float().clip(0, 1)) for i, t in enumerate(order)}
+
+    def drain(self):
+        """Steps until nothing is queued or live; returns every picture of those steps."""
+        out = {}
+        while self._queue or self.session.live:      # (an empty session takes any request that can fit at all; one that cannot makes admit raise)
+            out.update(self.step())
+        return out
+
 
 class _Request(NamedTuple):
     """One queued request of ``RequestBatcher``."""
