@@ -891,7 +891,8 @@ TLD_API int tld_debug_attention_fwd(const void* qk, const void* vt, void* att, i
 /* Test hook: the MLP's depthwise 3x3 convolution + GELU alone (nn.Conv2d(hid, hid, 3, padding=1, groups=hid) then nn.GELU() on the
  * "b (h w) c -> b c h w" view, tld/transformer_blocks.py:95-103) on channels-last tokens: in / out [batch, grid * grid, channels] bf16
  * (device), weight [channels, 9] and bias [channels] fp32 (HOST, the reference's conv.weight / conv.bias).  Runs the kernel the engine
- * would pick for that grid (whole-image / tiled / row-streaming).  channels % 64 == 0; grid <= 16 or a multiple of 16.
+ * would pick for that grid (whole-image / tiled / row-streaming).  channels % 64 == 0; grid a multiple of 4, as tld_engine_create has it
+ * (any other side is refused with the engine's words, "token count ... unsupported"): the partial last 16 x 16 tiles of 20, 24, 28 ... included.
  * Sizes: the row-streaming kernel (grids that are multiples of 32) writes through 32-bit byte offsets: batch x grid^2 x channels x 2 B
  * must stay below 4 GiB, else TLD_ERR_INVALID before any allocation or launch, with the largest batch that fits.  The whole-image and
  * tiled kernels address in 64 bits and accept larger buffers (up to 2^31 - 1 workgroups). */

@@ -135,9 +135,9 @@ def _bf(t):
     return t.bfloat16().float()
 
 
-def inputs(family, N, variant=0):
-    """(q, k, v, g) fp32 host tensors [B, N, d]; q, k, v bf16-exact."""
-    B, H = _bh(N)
+def inputs(family, N, variant=0, bh=None):
+    """(q, k, v, g) fp32 host tensors [B, N, d]; q, k, v bf16-exact.  bh: another (samples, heads) than this file's (the forward's grid tests)."""
+    B, H = bh or _bh(N)
     d = 64 * H
     gen = torch.Generator().manual_seed(1000 * family + N + 7 * variant)
     rn = lambda *s: torch.randn(*s, generator=gen)

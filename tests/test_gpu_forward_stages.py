@@ -251,7 +251,7 @@ def report(c, start=0):
 class Body:
     """The stages of one body run (a forward, or the debug step of a sampler) and what the checks need to know about it."""
 
-    def __init__(self, m, kw, tag, B, src, noise_row, label_row, zero_label=()):
+    def __init__(self, m, kw, tag, B, src, noise_row, label_row, zero_label=(), checks=None):
         self.m, self.kw, self.dev = m, kw, _dev()
         self.d, self.L, self.patch, self.C = kw["embed_dim"], kw["n_layers"], kw["patch_size"], kw["n_channels"]
         self.H, self.G = self.d // 64, kw["image_size"] // kw["patch_size"]
@@ -264,7 +264,7 @@ class Body:
         while gpw < 16 and gps % (gpw * 2) == 0 and B * (gps // (gpw * 2)) >= cus:      # launch_cross_row's partition, CU count from the device
             gpw *= 2
         self.gpw = gpw if self.d % 256 == 0 else 1
-        self.c = Checks(tag, B, self.N, self.G, self.H, self.gpw, uncond_from=src if src < B else None, zero_label=zero_label)
+        self.c = (checks or Checks)(tag, B, self.N, self.G, self.H, self.gpw, uncond_from=src if src < B else None, zero_label=zero_label)      # checks: a subclass with further classes
         self.w = {k: v.to(self.dev).double() for k, v in m.state_dict().items() if v.dtype != torch.int64}
 
     def has(self, name):
@@ -444,8 +444,11 @@ def _with_env(env, fn):
                 os.environ[k] = v
 
 
-def run_forward_case(name, io_dtype=torch.float32, blocks=None):
-    kw, batches, max_batch, env, lowlat = CASES[name]
+def run_forward_case(name, io_dtype=torch.float32, blocks=None, case=None, checks=None, paths=None):
+    """case: a row like those of CASES, run under the tag `name` (tests/test_gpu_forward_grids.py); checks: the Checks class; paths: where the launch-path
+    masks go (this file's record otherwise)."""
+    kw, batches, max_batch, env, lowlat = CASES[name] if case is None else case
+    paths = _PATHS if paths is None else paths
     dev = _dev()
     m = _model(kw)
     if lowlat:
@@ -461,8 +464,8 @@ def run_forward_case(name, io_dtype=torch.float32, blocks=None):
             tag = name if len(batches) == 1 else f"{name}/{B}"
             if io_dtype != torch.float32:
                 tag += "/" + str(io_dtype).split(".")[-1]
-            b = Body(m, kw, tag, B, B, torch.arange(B), torch.arange(B) + B, zero)
-            _PATHS[tag] = b.paths
+            b = Body(m, kw, tag, B, B, torch.arange(B), torch.arange(B) + B, zero, checks=checks)
+            paths[tag] = b.paths
             check_cond(b, sd_.float().reshape(-1), ld.float())
             check_ends(b, xd.float(), out if io_dtype == torch.float32 else None)
             if io_dtype != torch.float32:      # the casts: inputs rounded by the caller, the output rounded once from the fp32 stage
@@ -505,9 +508,10 @@ def _check_trace_updates(c, what, x_start, tx0, txt, co, eps=None, z0=None, mask
         xt = txt[i].double()
 
 
-def _sampler(name, plus, from_image, masked=True):
+def _sampler(name, plus, from_image, masked=True, case=None, checks=None, paths=None):
     from transformer_latent_diffusion_amd import schedule
-    kw, B, n_levels, steps = SAMPLERS[name]
+    kw, B, n_levels, steps = SAMPLERS[name] if case is None else case
+    paths = _PATHS if paths is None else paths
     dev = _dev()
     m = _model(kw, seed=33)
     m.reserve(2 * B)
@@ -540,8 +544,8 @@ def _sampler(name, plus, from_image, masked=True):
             torch.cuda.synchronize()
             nrow = torch.full((2 * B,), step)
             lrow = n + torch.cat([torch.arange(B), torch.full((B,), B)])
-            b = Body(m, kw, f"{tag}/step{step}", 2 * B, B, nrow, lrow, zero_label=tuple(range(B, 2 * B)))
-            _PATHS[b.c.name] = b.paths
+            b = Body(m, kw, f"{tag}/step{step}", 2 * B, B, nrow, lrow, zero_label=tuple(range(B, 2 * B)), checks=checks)
+            paths[b.c.name] = b.paths
             c = b.c
             sig = torch.tensor([co[i][0] for i in range(n)], device=dev)
             check_cond(b, sig, torch.cat([lab, torch.zeros(1, 768, device=dev)]))

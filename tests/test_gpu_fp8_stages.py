@@ -85,11 +85,8 @@ class Checks8(FS.Checks):
         return out
 
 
-def _body(m, kw, tag, B, src, nrow, lrow, zero):
-    b = FS.Body(m, kw, tag, B, src, nrow, lrow, zero)
-    o = b.c
-    b.c = Checks8(o.name, o.B, o.N, o.G, o.H, o.gpw, uncond_from=o.uncond_from, zero_label=o.zero_label)
-    return b
+def _body(m, kw, tag, B, src, nrow, lrow, zero, checks=None):
+    return FS.Body(m, kw, tag, B, src, nrow, lrow, zero, checks=checks or Checks8)
 
 
 def check_block(b, i, fused, ops, ref_ops):
@@ -184,8 +181,11 @@ def _release(m):
     gc.collect(); torch.cuda.empty_cache()
 
 
-def run_forward_case(name, blocks=None):
-    kw, B, max_batch, engines = CASES[name]
+def run_forward_case(name, blocks=None, case=None, checks=None, paths=None):
+    """case: a row like those of CASES, run under the tag `name` (tests/test_gpu_forward_grids.py); checks: a subclass of Checks8; paths: where the
+    launch-path masks go (this file's record otherwise)."""
+    kw, B, max_batch, engines = CASES[name] if case is None else case
+    paths = _PATHS if paths is None else paths
     dev = _dev()
     x, sigma, lab, zero = FS._inputs(kw, B, 60 + B)
     xd, sd_, ld = x.to(dev), sigma.to(dev), lab.to(dev)
@@ -196,8 +196,8 @@ def run_forward_case(name, blocks=None):
             try:
                 out = m(xd, sd_, ld)
                 torch.cuda.synchronize()
-                b = _body(m, kw, f"{name}/{'fused' if fused == '1' else 'unfused'}", B, B, torch.arange(B), torch.arange(B) + B, zero)
-                _PATHS[b.c.name] = b.paths
+                b = _body(m, kw, f"{name}/{'fused' if fused == '1' else 'unfused'}", B, B, torch.arange(B), torch.arange(B) + B, zero, checks)
+                paths[b.c.name] = b.paths
                 FS.check_cond(b, sd_.reshape(-1), ld)
                 FS.check_ends(b, xd, out)
                 ops = {}

@@ -1298,7 +1298,7 @@ int64_t tld_engine_weight_bytes(const tld_engine* e) { return e ? e->weight_byte
 int tld_debug_dwconv_gelu(const void* in, const float* weight, const float* bias, void* out, int32_t batch, int32_t grid, int32_t channels,
                           void* hip_stream) {
     if (!in || !weight || !bias || !out || batch <= 0 || grid <= 0 || channels <= 0 || channels % 64) return fail(TLD_ERR_INVALID, "bad argument");
-    if (grid > 16 && grid % 16) return fail(TLD_ERR_INVALID, "grids wider than 16 tokens must be a multiple of 16 (the engine's token counts are multiples of 256)");
+    if (grid % 4) return fail(TLD_ERR_INVALID, "token count %lld unsupported: image_size / patch_size must be a multiple of 4", (long long)grid * grid);     // (body_config_check's rule and words)
     if (const std::string bad = dwconv_hook_refusal(batch, grid, channels); !bad.empty()) return fail(TLD_ERR_INVALID, "%s", bad.c_str());
     PtrDeviceGuard guard(in);
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
