@@ -907,7 +907,9 @@ TLD_API int tld_debug_dwconv_gelu(const void* in_bf16, const float* weight_host,
  *     create allocates none, a step allocates none;
  *   - records which launch path every size-dependent dispatch took (tld_train_debug_paths).
  * With debug off nothing is launched, copied or allocated for the hook.  A debug call on a capturing stream is refused (TLD_ERR_STATE).
- * Each path bit is set inside the branch that launches the kernel (the attention bits by launch_attention_bwd itself).
+ * Each path bit is set inside the branch that launches the kernel (the attention bits by launch_attention_bwd itself): the launch sites RECORD the
+ * mask.  The plan of the step (csrc/tld_train_plan.h: train_step_plan(...).paths, a pure host function of the configuration, the batch, the CU count and
+ * TLD_TRAIN_TN_WGRAD) PREDICTS it; tests hold the recorded mask of every case against the prediction.
  *
  * Stage names (i = block index; M = batch * tokens; every stage is read back as fp32 with its logical shape):
  *   saved forward tensors, read in place:  blk<i>.{x1 a1 qk vt att x2 a2 qc cr x3 a3 h hc o} (bf16; hc = GELU'(pre-activation) as stored),

@@ -5,7 +5,8 @@
 //
 // One query per line, whitespace-separated; one JSON object per line comes back, {"refusal": "..."} ("" where the size is accepted):
 //     train  image_size noise_embed_dims patch_size embed_dim n_layers text_emb_size n_channels mlp_multiplier max_batch      tld_train_create's arithmetic
-//            + "gemms": launches of the step checked against launch_gemm's reach, "unfit": how many of them it would refuse (accepted configurations only)
+//            + "gemms": launches of the step checked against launch_gemm's reach, "unfit": how many of them it would refuse, "untested": weight-gradient
+//              splits the step's plan chooses that are not among them (accepted configurations only)
 //     clip   max_batch rows width patch_rows patch_k            tld_clip_create (patch_rows 0) / tld_clip_vis_create
 //     dwconv batch grid channels                                tld_debug_dwconv_gelu
 //     attn_fwd batch ntok heads | attn_bwd batch ntok heads     tld_debug_attention_fwd / _bwd
@@ -16,6 +17,7 @@
 #include <fstream>
 #include <iostream>
 #include <sstream>
+#include <vector>
 
 using namespace tld;
 
@@ -25,32 +27,29 @@ static std::string quoted(const std::string& s) {
     return o + "\"";
 }
 
-static bool fits(long M, long N, long K, long lda, long ldw, long wbr = 0, unsigned long long wbs = 0) {
+static bool fits(const TrainGemm& g) {
     GemmParams p{};
-    p.M = (int)M; p.N = (int)N; p.K = (int)K; p.lda = (int)lda; p.ldw = (int)ldw; p.w_batch_rows = (int)wbr; p.w_batch_stride_bytes = (unsigned)wbs;
-    return M <= 2147483647L && wbs < (1ull << 32) && gemm_offsets_fit(p) != 0;
+    p.M = (int)g.M; p.N = (int)g.N; p.K = (int)g.K; p.lda = (int)g.lda; p.ldw = (int)g.ldw; p.w_batch_rows = (int)g.w_batch_rows; p.w_batch_stride_bytes = (unsigned)g.w_batch_stride_bytes;
+    return g.M <= 2147483647L && g.w_batch_stride_bytes < (1ull << 32) && gemm_offsets_fit(p) != 0;
 }
 
-// Every launch_gemm call a training step of max_batch samples can make, by shape: the linears of the forward and of the input gradients (A = an activation of M
-// rows), and the transposing weight gradient dW[Nout, Kin] = dY^T X for EVERY split count its workspace admits (tld_train.hip: weight_grad -- the step picks
-// one of them by the CU count; all are checked here): A = T1 [sk Nout, ms], W = T2 with the block-diagonal offset of split sk - 1.
-static void train_gemms(const tld_config& c, long* total, long* unfit) {
-    const long G = c.image_size / c.patch_size, M = (long)c.max_batch * G * G, d = c.embed_dim, hid = d * c.mlp_multiplier;
-    const long tr_rows = M + kTrainTransposeMargin;
-    auto count = [&](bool ok) { ++*total; if (!ok) ++*unfit; };
-    const long widths[4] = {d, 2 * d, 3 * d, hid};
-    for (long k : widths) for (long n : widths) count(fits(M, n, k, k, k));
-    const long pairs[5][2] = {{d, hid}, {hid, d}, {3 * d, d}, {d, d}, {2 * d, d}};
-    for (const auto& pr : pairs) {
-        const long Nout = pr[0], Kin = pr[1];
-        const long ms1 = (M + 63) / 64 * 64;
-        count(fits(Nout, Kin, ms1, ms1, ms1));
-        for (long sk = 2; sk <= 32; ++sk) {
-            const long mp = ((M + sk - 1) / sk + 127) / 128 * 128;
-            if (sk * mp > tr_rows) continue;
-            count(fits(sk * Nout, Kin, mp, mp, mp, Nout, (unsigned long long)Kin * mp * 2));
+// Every launch_gemm call a training step of max_batch samples can make (train_gemms, csrc/tld_train_plan.h: the linears, and the transposing weight gradient at
+// EVERY split count its workspace admits) against launch_gemm's reach; and that the split the step's plan chooses -- at 256 and at 304 CUs, with
+// TLD_TRAIN_TN_WGRAD=0 -- is one of the shapes just tested.
+static void train_gemm_reach(const tld_config& c, long* total, long* unfit, long* untested) {
+    const TrainShape s = train_shape(c);
+    const TrainWorkspace w = train_workspace(s);
+    const std::vector<TrainGemm> all = train_gemms(s, w, c.max_batch);
+    for (const TrainGemm& g : all) { ++*total; if (!fits(g)) ++*unfit; }
+    const int shape[4][2] = {{s.d, s.hid}, {s.hid, s.d}, {s.d, s.d}, {3 * s.d, s.d}};      // (Nout, Kin) of plan.wg[]
+    for (int cus : {256, 304}) {
+        const TrainStepPlan p = train_step_plan(s, w, c.max_batch, cus, false);
+        for (int k = 0; k < 4; ++k) {
+            bool found = false;
+            for (const TrainGemm& g : all)
+                found = found || (g.sk == p.wg[k].sk && g.M == (long)g.sk * shape[k][0] && g.N == shape[k][1] && g.K == p.wg[k].run_rows);
+            if (!found) ++*untested;
         }
-        for (long sk = 2; sk <= 8; sk *= 2) if (M % sk == 0) count(fits(sk * Nout, Kin, M / sk, M / sk, M / sk, Nout, (unsigned long long)Kin * (M / sk) * 2));
     }
 }
 
@@ -69,9 +68,9 @@ int main(int argc, char** argv) {
             in >> c.image_size >> c.noise_embed_dims >> c.patch_size >> c.embed_dim >> c.n_layers >> c.text_emb_size >> c.n_channels >> c.mlp_multiplier >> c.max_batch;
             r = train_config_check(c);
             if (r.empty()) {
-                long total = 0, unfit = 0;
-                train_gemms(c, &total, &unfit);
-                extra = ", \"gemms\": " + std::to_string(total) + ", \"unfit\": " + std::to_string(unfit);
+                long total = 0, unfit = 0, untested = 0;
+                train_gemm_reach(c, &total, &unfit, &untested);
+                extra = ", \"gemms\": " + std::to_string(total) + ", \"unfit\": " + std::to_string(unfit) + ", \"untested\": " + std::to_string(untested);
             }
         } else if (what == "clip") {
             int mb, rows, width, pr, pk;

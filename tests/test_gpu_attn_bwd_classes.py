@@ -1,7 +1,8 @@
 """The self-attention backward (csrc/tld_train_attn.hip) through tld_debug_attention_bwd: every instantiation of attn_bwd_kernel<NW, MODE, TG = float,
 MASKED> that the dispatch can select, and every product grid, class by class against float64.
 
-attn_bwd_block_waves and the branch order of launch_bwd are restated here (block_waves, dispatch); CPU tests hold the restatement against the
+attn_bwd_block_waves and attn_bwd_dispatch are restated in tests/train_plan_ref.py (block_waves, dispatch; held against the C++ on the CPU by
+tests/test_train_plan_host.py); CPU tests here hold the restatement against the
 padded-work figures of the kernel file's header comment and the case table against everything the dispatch can select for N a multiple of 16 up
 to 4096.  Each GPU case fills the output with NaN (every element must be written), keeps sentinels behind row B N and statistic 2 B H N, and
 compares dq, dk and dv separately with the exact float64 backward (train_stage_refs.attn_bwd) of the same bf16-exact operands, over the whole
@@ -54,29 +55,8 @@ gpu = pytest.mark.gpu
 LOG2E = 1.44269504088896340736
 
 
-# ---- the dispatch, restated -----------------------------------------------------------------------------------------------------------------
-def block_waves(n):
-    """attn_bwd_block_waves: waves per workgroup (block width 32 nw) at n tokens."""
-    if n <= 256:
-        return (n + 31) // 32
-    best, pad = 8, 1 << 30
-    for nw in (8, 7, 6, 5, 4):
-        npad = -(-n // (32 * nw)) * 32 * nw
-        if nw == 7 and npad != n:
-            continue
-        if npad < pad:
-            pad, best = npad, nw
-    return best
-
-
-def dispatch(n):
-    """launch_bwd: (mode, NW, masked) at n tokens, mode "fused" (one workgroup per (sample, head)) or "two" (dQ kernel + dK / dV kernel)."""
-    if n in (64, 128, 256):
-        return "fused", n // 32, False
-    if n > 256 and n % 256 == 0:
-        return "two", 8, False
-    nw = block_waves(n)
-    return ("fused" if n < 256 else "two"), nw, n % (32 * nw) != 0
+# ---- the dispatch, restated: tests/train_plan_ref.py (held against csrc/tld_train_plan.h on the CPU by tests/test_train_plan_host.py) -----------------
+from train_plan_ref import block_waves, dispatch  # noqa: E402,F401
 
 
 def padded_work(n):

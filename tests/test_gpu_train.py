@@ -24,6 +24,28 @@ GRAD_TOL = 2e-2
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+# Every configuration a test of this file creates a trainer at: name -> (DenoiserConfig arguments, the batch the test steps with, max_batch).  The two golden
+# steps (g15 / g17) bring their own configuration.  tests/test_train_plan_host.py sweeps the training step's host plan over this table, on the CPU.
+_WIDE = dict(noise_embed_dims=256, patch_size=2, dropout=0, text_emb_size=768, mlp_multiplier=4)
+TRAINER_SHAPES = {
+    "64 tokens": (dict(image_size=16, n_channels=4, n_layers=1), 16, 16),
+    "d192": (dict(image_size=32, n_channels=4, n_layers=2, embed_dim=192), 4, 4),
+    "d320": (dict(image_size=32, n_channels=4, n_layers=2, embed_dim=320), 4, 4),
+    "4096 tokens": (dict(image_size=128, n_channels=4, n_layers=1), 2, 2),
+    "wide": (dict(image_size=32, embed_dim=768, n_layers=2, n_channels=4, **_WIDE), 3, 4),
+    "default 2": (dict(image_size=32, n_channels=4), 2, 2),
+    "default 4": (dict(image_size=32, n_channels=4), 4, 4),
+    "default 8": (dict(image_size=32, n_channels=4), 8, 8),
+    "graph d256": (dict(image_size=32, embed_dim=256, n_layers=2, n_channels=4, **_WIDE), 8, 8),
+}
+GOLDEN_STEPS = ("g15_train_step.npz", "g17_train_step_1024tok.npz")          # (max_batch 4)
+
+
+def _shape(name):
+    from transformer_latent_diffusion_amd import DenoiserConfig
+    return DenoiserConfig(**TRAINER_SHAPES[name][0])
+
+
 def _trainer(cfg, sd, **kw):
     from transformer_latent_diffusion_amd import Trainer
     return Trainer(cfg, device=_dev(), state_dict={k: torch.from_numpy(np.array(v)) for k, v in sd.items()}, **kw)
@@ -48,7 +70,7 @@ def _g15(name="g15_train_step.npz"):
     return g, cfg, synth_weights(cfg, g["weight_seed"], g["weight_checksum"])
 
 
-@pytest.mark.parametrize("name", ["g15_train_step.npz", "g17_train_step_1024tok.npz"])
+@pytest.mark.parametrize("name", list(GOLDEN_STEPS))
 def test_forward_backward_vs_reference_step(name):
     """The reference's own training step (loss.backward() on its Denoiser, captured by import): g15 at 256 tokens, g17 at the 512 px
     fine-tuning geometry (image_size 64 = 1024 tokens: two-kernel attention backward, banded depthwise convolution)."""
@@ -166,7 +188,7 @@ def test_64_token_step_vs_oracle_autograd():
     from transformer_latent_diffusion_amd import DenoiserConfig
     from transformer_latent_diffusion_amd.train import drop_labels, mix_noise
     from transformer_latent_diffusion_amd.weights import synth_state_dict
-    cfg = DenoiserConfig(image_size=16, n_channels=4, n_layers=1)
+    cfg = _shape("64 tokens")
     sd = synth_state_dict(cfg, 41)
     gen = torch.Generator().manual_seed(42)
     B = 16                                   # 1024 token rows, as g15: the tolerance is the one the 256-token goldens hold
@@ -192,7 +214,7 @@ def test_odd_width_step_vs_oracle_autograd(d):
     from transformer_latent_diffusion_amd import DenoiserConfig
     from transformer_latent_diffusion_amd.train import drop_labels, mix_noise
     from transformer_latent_diffusion_amd.weights import synth_state_dict
-    cfg = DenoiserConfig(image_size=32, n_channels=4, n_layers=2, embed_dim=d)
+    cfg = _shape(f"d{d}")
     sd = synth_state_dict(cfg, 45 + d)
     gen = torch.Generator().manual_seed(46)
     B = 4
@@ -217,7 +239,7 @@ def test_4096_token_step_vs_oracle_autograd():
     from transformer_latent_diffusion_amd import DenoiserConfig
     from transformer_latent_diffusion_amd.train import drop_labels, mix_noise
     from transformer_latent_diffusion_amd.weights import synth_state_dict
-    cfg = DenoiserConfig(image_size=128, n_channels=4, n_layers=1)
+    cfg = _shape("4096 tokens")
     sd = synth_state_dict(cfg, 43)
     gen = torch.Generator().manual_seed(44)
     B = 2
@@ -241,8 +263,7 @@ def test_wide_model_gradients_vs_oracle_autograd():
     from transformer_latent_diffusion_amd import DenoiserConfig
     from transformer_latent_diffusion_amd.train import drop_labels, mix_noise
     from transformer_latent_diffusion_amd.weights import synth_state_dict
-    cfg = DenoiserConfig(image_size=32, noise_embed_dims=256, patch_size=2, embed_dim=768, dropout=0, n_layers=2, text_emb_size=768, n_channels=4,
-                         mlp_multiplier=4)
+    cfg = _shape("wide")
     sd = synth_state_dict(cfg, 31)
     gen = torch.Generator().manual_seed(32)
     B = 3
@@ -263,7 +284,7 @@ def test_wide_model_gradients_vs_oracle_autograd():
 def test_training_reduces_the_loss_and_ema_loads_into_the_inference_engine():
     """A few steps of Trainer.train_step on a fixed batch: the loss goes down; the EMA state_dict loads into the inference Denoiser."""
     from transformer_latent_diffusion_amd import Denoiser, DenoiserConfig, TrainConfig, Trainer
-    cfg = DenoiserConfig(image_size=32, n_channels=4)
+    cfg = _shape("default 4")
     tr = Trainer(cfg, TrainConfig(lr=1e-3, alpha=0.9), device=_dev(), init_seed=2, max_batch=8)
     gen = torch.Generator().manual_seed(1)
     x = torch.randn(8, 4, 32, 32, generator=gen) * 0.8
@@ -381,8 +402,7 @@ def test_graph_replay_equals_eager_steps(monkeypatch):
     Five optimizer steps give bit-identical losses and parameters to the eager path."""
     from transformer_latent_diffusion_amd import DenoiserConfig, Trainer
     from transformer_latent_diffusion_amd.train import TrainConfig
-    cfg = DenoiserConfig(image_size=32, noise_embed_dims=256, patch_size=2, embed_dim=256, dropout=0, n_layers=2, text_emb_size=768, n_channels=4,
-                         mlp_multiplier=4)
+    cfg = _shape("graph d256")
 
     def run(graph):
         monkeypatch.setenv("TLD_TRAIN_GRAPH", "1" if graph else "0")
@@ -409,8 +429,7 @@ def test_graph_capture_refreshes_weights_and_pred_is_not_aliased(monkeypatch):
     Sequence fb, fb (captures), step, fb, step, fb in graph mode == the same sequence eagerly, bit for bit; returned predictions are copies."""
     from transformer_latent_diffusion_amd import DenoiserConfig, Trainer
     from transformer_latent_diffusion_amd.train import TrainConfig
-    cfg = DenoiserConfig(image_size=32, noise_embed_dims=256, patch_size=2, embed_dim=256, dropout=0, n_layers=2, text_emb_size=768, n_channels=4,
-                         mlp_multiplier=4)
+    cfg = _shape("graph d256")
 
     def run(graph):
         monkeypatch.setenv("TLD_TRAIN_GRAPH", "1" if graph else "0")
@@ -442,7 +461,7 @@ def test_checkpoint_is_reference_format_and_resumes(tmp_path):
     Trainer.load_checkpoint resumes from it (tld/train.py:92-104): a run continued from the checkpoint takes the same steps as the original."""
     from transformer_latent_diffusion_amd import DenoiserConfig, Trainer
     from transformer_latent_diffusion_amd.train import TrainConfig
-    cfg = DenoiserConfig(image_size=32, n_channels=4)
+    cfg = _shape("default 4")
     tr = Trainer(cfg, TrainConfig(batch_size=4), device="cuda:0", init_seed=1, max_batch=4)
     g = torch.Generator().manual_seed(2); rng = np.random.default_rng(3)
     for _ in range(3):
@@ -481,7 +500,7 @@ def test_gradient_accumulation_equals_one_large_batch():
     summation order of the weight-gradient reductions), and the optimizer lands on the same parameters."""
     from transformer_latent_diffusion_amd import DenoiserConfig, Trainer
     from transformer_latent_diffusion_amd.train import TrainConfig
-    cfg = DenoiserConfig(image_size=32, n_channels=4)
+    cfg = _shape("default 4")
     g = torch.Generator().manual_seed(4)
     x = torch.randn(8, 4, 32, 32, generator=g) * 0.8; y = torch.randn(8, 768, generator=g) * 0.5
     nl = torch.rand(8, generator=g) * 0.9 + 0.05; noise = torch.randn(8, 4, 32, 32, generator=g)
@@ -512,7 +531,7 @@ def test_abandoned_accumulation_can_be_reset_and_explicit_use_graph_beats_the_en
     gradients (load_state_dict does it too); (b) an explicit use_graph= argument wins over TLD_TRAIN_GRAPH."""
     from transformer_latent_diffusion_amd import DenoiserConfig, Trainer
     from transformer_latent_diffusion_amd.train import TrainConfig
-    cfg = DenoiserConfig(image_size=32, n_channels=4)
+    cfg = _shape("default 4")
     g = torch.Generator().manual_seed(8)
     x = torch.randn(4, 4, 32, 32, generator=g) * 0.8; y = torch.randn(4, 768, generator=g) * 0.5
     nl = torch.rand(4, generator=g) * 0.9 + 0.05; noise = torch.randn(4, 4, 32, 32, generator=g)
@@ -543,7 +562,7 @@ def test_gradient_accumulation_under_graph_replay_and_ragged_staging():
     and train_step's pinned staging follows a batch whose size changes (the last, smaller batch of an epoch) and changes back."""
     from transformer_latent_diffusion_amd import DenoiserConfig, Trainer
     from transformer_latent_diffusion_amd.train import TrainConfig
-    cfg = DenoiserConfig(image_size=32, n_channels=4)
+    cfg = _shape("default 4")
     g = torch.Generator().manual_seed(12)
     mk = lambda n: (torch.randn(n, 4, 32, 32, generator=g) * 0.8, torch.rand(n, generator=g) * 0.9 + 0.05, torch.randn(n, 768, generator=g) * 0.5,
                     torch.randn(n, 4, 32, 32, generator=g))
@@ -577,7 +596,7 @@ def test_train_step_stages_host_batches_without_blocking_and_matches_device_batc
     on the same batch handed over as device tensors, step after step (graph replay on and off)."""
     from transformer_latent_diffusion_amd import DenoiserConfig, Trainer
     from transformer_latent_diffusion_amd.train import TrainConfig
-    cfg = DenoiserConfig(image_size=32, n_channels=4)
+    cfg = _shape("default 4")
     g = torch.Generator().manual_seed(8)
     x = torch.randn(4, 4, 32, 32, generator=g) * 0.8; y = torch.randn(4, 768, generator=g) * 0.5
     for graph in (True, False):

@@ -26,7 +26,8 @@ pile up, so the bounds are per element, or per class where a kernel has intermed
   the yardstick to three digits at every case (profiles/r11_attn_bwd_classes.txt, section 3).
 
 Every compared tensor is first checked for NaN / Inf (the poison), with the count in the message.
-CASES reach every launch path: test_cases_reach_every_launch_path holds the union of tld_train_debug_paths against the full mask, and -- the one
+Every case holds its whole mask of tld_train_debug_paths against the plan's prediction (train_plan_ref.expected_mask: test_forward_stages and the TN-off
+test).  CASES reach every launch path: test_cases_reach_every_launch_path holds the union of the masks against the full mask, and -- the one
 "masked" bit standing for several kernel pairs -- the (mode, waves, masked) instantiation of the attention backward of every product grid.
 Cases G4 ... G60 (d = 128, one block) run every grid the other cases leave out; they came after the mutation table below.
 
@@ -67,6 +68,7 @@ import numpy as np
 import pytest
 import torch
 
+import train_plan_ref
 import train_stage_refs as R
 from test_gpu_attn_bwd_classes import GRIDS, compare as attn_bwd_compare, dispatch as attn_bwd_dispatch
 from test_gpu_parity import _dev
@@ -115,6 +117,13 @@ for _G in (4, 24, 28, 36, 40, 44, 48, 52, 56, 60):
 TN_OFF_CASES = ("A", "C")                         # case H: the transposing weight gradient with split runs (TLD_TRAIN_TN_WGRAD=0, fresh process)
 
 
+def _atoi(text):
+    """C's atoi, as tld_train_create reads TLD_TRAIN_TN_WGRAD: leading blanks, a sign, digits; anything else ends the number (none: 0)."""
+    import re
+    m = re.match(r"\s*([+-]?\d+)", text)
+    return int(m.group(1)) if m else 0
+
+
 class _Tracked(dict):
     def __init__(self, *a):
         super().__init__(*a)
@@ -155,6 +164,9 @@ class Run:
         self.loss, self.pred = self.tr.forward_backward(*self.inputs)
         torch.cuda.synchronize()
         self.paths = self.tr.debug_paths()
+        # the plan's prediction of that mask (csrc/tld_train_plan.h through its restatement), for this device and this process's TLD_TRAIN_TN_WGRAD
+        self.expected_paths = train_plan_ref.expected_mask(kw, self.B, max_batch, torch.cuda.get_device_properties(self.dev).multi_processor_count,
+                                                           _atoi(os.environ.get("TLD_TRAIN_TN_WGRAD", "1")) != 0)
         self.w = {k: v.double() for k, v in self.tr.state_dict().items()}
         self.grads = _Tracked({k: v.double() for k, v in self.tr.grad_dict().items()})      # remembers which tensors a check has read
         self.backward_done = False
@@ -484,6 +496,7 @@ def run(request):
 
 def test_forward_stages(run):
     r = run
+    assert r.paths == r.expected_paths, f"case {r.name}: launch paths {r.paths:#x}, the plan predicts {r.expected_paths:#x}"
     n = len(r.rows); r.fail = []
     forward_ends(r)
     for i in range(r.L):
@@ -522,7 +535,7 @@ def test_every_parameter_gradient_is_checked_and_finite(run):
 def _tn_off(case):
     code = ("import sys, json; sys.path.insert(0, %r); import test_gpu_train_stages as T; r = T.Run(%r)\n"
             "for i in reversed(range(r.L)): T.backward_block(r, i, weights_only=True)\n"
-            "print('RESULT ' + json.dumps({'paths': r.paths, 'fail': r.fail, 'rows': [[a, b, c] for a, b, c, _ in r.rows]}))" % (os.path.join(REPO, "tests"), case))
+            "print('RESULT ' + json.dumps({'paths': r.paths, 'expected_paths': r.expected_paths, 'fail': r.fail, 'rows': [[a, b, c] for a, b, c, _ in r.rows]}))" % (os.path.join(REPO, "tests"), case))
     env = dict(os.environ, TLD_TRAIN_TN_WGRAD="0", PYTHONPATH=REPO + os.pathsep + os.environ.get("PYTHONPATH", ""))
     out = subprocess.run([sys.executable, "-c", code], env=env, cwd=REPO, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
@@ -540,6 +553,7 @@ def test_transposing_weight_gradient_with_split_runs(case):
         print(f"case {case} (TN off) {a:48s} {b:22s} {c:.3e}")
     assert not res["fail"], "\n".join(res["fail"])
     assert res["paths"] >> 26 & 1 and not res["paths"] >> 24 & 1, hex(res["paths"])
+    assert res["paths"] == res["expected_paths"], f"case {case} (TN off): launch paths {res['paths']:#x}, the plan predicts {res['expected_paths']:#x}"
 
 
 def test_cases_reach_every_launch_path():

@@ -87,7 +87,7 @@ def test_train_create_boundary(driver):
     outs = driver([_train_line(cfg, mb + k) for cfg, mb, _ in TRAIN for k in (0, 1)])
     for k, (cfg, mb, words) in enumerate(TRAIN):
         good, bad = outs[2 * k], outs[2 * k + 1]
-        assert good["refusal"] == "" and good["unfit"] == 0 and good["gemms"] > 16, (k, good)
+        assert good["refusal"] == "" and good["unfit"] == 0 and good["untested"] == 0 and good["gemms"] > 16, (k, good)
         assert bad["refusal"].startswith(f"max_batch={mb + 1}: ") and words in bad["refusal"], (k, bad)
         assert f"the largest max_batch that fits is {mb};" in bad["refusal"] and "run larger batches as several calls" in bad["refusal"], bad
 
@@ -99,7 +99,7 @@ def test_no_accepted_trainer_is_refused_by_launch_gemm(driver):
     best = [train_largest(c)[0] for c in cases]
     outs = driver([_train_line(c, b) for c, b in zip(cases, best)] + [_train_line(c, b + 1) for c, b in zip(cases, best)])
     for k, (c, b) in enumerate(zip(cases, best)):
-        assert outs[k]["refusal"] == "" and outs[k]["unfit"] == 0, (vars(c), b, outs[k])
+        assert outs[k]["refusal"] == "" and outs[k]["unfit"] == 0 and outs[k]["untested"] == 0, (vars(c), b, outs[k])
         assert outs[len(cases) + k]["refusal"].startswith(f"max_batch={b + 1}: "), (vars(c), b)
 
 

@@ -8,6 +8,8 @@ Then the CLIP text tower with the stage hook off: encode_text of the cases of te
 and of 64 prompts on a two-layer ViT-L/14 tower; and the CLIP image tower: a 5-token tower chunked (5 images, 2 per call; fp32 and bf16 pixels) and a 257-token case.
 Then the stage hooks ON: one forward of the tiny denoiser, one encode of the tiny text tower and of the tiny image tower and one tiny training step (loss, gradient vector), each with
 every stage its header block names as a part ("absent <name>" where the engine's path has no such stage).
+Then three more training steps with the hook off (loss and gradient vector): d 256, image 64, one block, batch 5 with the untransposed and, under TLD_TRAIN_TN_WGRAD=0, the
+transposing weight-gradient split; d 192, image 24, two blocks, batch 3: the zero-padded form.
     TLD_LIB=<lib.so> python tools/lib_ab_check.py out.npy"""
 import hashlib, os, sys
 from dataclasses import asdict
@@ -142,6 +144,32 @@ tblk = ("x1 a1 qk vt att x2 a2 qc cr x3 a3 h hc o st1 st2 st3 p0 kvc wqkv wq wup
 stage_parts("train stage", "sinb h1 g1v ycat y yst p16 p16n est1 e est2 xfin dout row_loss gx.tail gxb.tail dy de dpn dp16 dycat dg1".split() +
             [f"blk{i}.{n}" for i in range(ct.n_layers) for n in tblk], lambda n: tr.read_stage(n).numpy())
 tr.set_debug(False)
+# three more training steps, stage hook off: the smallest shapes that reach each weight-gradient form (csrc/tld_train_plan.h) -- the untransposed split (sk 5 at
+# 256 CUs), the transposing split (TLD_TRAIN_TN_WGRAD=0, read when the trainer is created) and the zero-padded form (M = 432)
+from transformer_latent_diffusion_amd import DenoiserConfig
+from transformer_latent_diffusion_amd.weights import synth_state_dict
+def train_part(name, d, image, blocks, batch, tn_off=False):
+    c = DenoiserConfig(image_size=image, noise_embed_dims=256, patch_size=2, embed_dim=d, dropout=0, n_layers=blocks, text_emb_size=768, n_channels=4, mlp_multiplier=4)
+    old = os.environ.get("TLD_TRAIN_TN_WGRAD")
+    if tn_off:
+        os.environ["TLD_TRAIN_TN_WGRAD"] = "0"
+    try:
+        t2 = Trainer(c, device=dev, state_dict={k: torch.from_numpy(np.array(v)) for k, v in synth_state_dict(c, 31).items()}, max_batch=batch, keep_ema=False, use_graph=False)
+    finally:
+        if tn_off:
+            os.environ.pop("TLD_TRAIN_TN_WGRAD") if old is None else os.environ.__setitem__("TLD_TRAIN_TN_WGRAD", old)
+    gg = torch.Generator().manual_seed(32 + batch)
+    x0 = torch.randn(batch, 4, image, image, generator=gg) * 0.8
+    nz = torch.randn(batch, 4, image, image, generator=gg)
+    lv = torch.rand(batch, generator=gg) * 0.9 + 0.05
+    lb = torch.randn(batch, 768, generator=gg) * 0.5
+    xn = (1 - lv).view(-1, 1, 1, 1) * x0 + lv.view(-1, 1, 1, 1) * nz
+    ls, _ = t2.forward_backward(xn.contiguous(), lv, lb, x0)
+    torch.cuda.synchronize()
+    parts[f"{name} loss"] = ls.float().cpu().numpy().reshape(-1); parts[f"{name} gradients"] = t2.grads.cpu().numpy()
+train_part("train d256 g32 untransposed split", 256, 64, 1, 5)
+train_part("train d256 g32 transposing split", 256, 64, 1, 5, tn_off=True)
+train_part("train d192 g12 zero-padded", 192, 24, 2, 3)
 for name, v in parts.items():
     assert name in staged or np.isfinite(v).all(), name
     print("part", name, tuple(v.shape), hashlib.sha1(np.ascontiguousarray(v).tobytes()).hexdigest())

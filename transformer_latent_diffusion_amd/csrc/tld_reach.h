@@ -13,6 +13,7 @@
 
 #include "../../include/tld_hip.h"
 #include "tld_gemm_plan.h"            // gemm_offsets_fit
+#include "tld_train_plan.h"           // kTrainTransposeMargin, train_dw_fused: the training step's workspace and forms
 
 namespace tld {
 
@@ -81,8 +82,6 @@ inline bool body_gemm_fits(const BodyGemm& g) {
 // below 4 GiB keeps every such launch inside the GEMM DMA's reach.  The rule implies the two GEMM A operands of M rows: the hidden activation [M, hid] and
 // dqkv [M, 3 d].  Row chunks on a grid's y axis: the column sums (64-row chunks), the transposes (32-row tiles when M is no multiple of 64) and the depthwise
 // weight gradient of the grids its fused backward does not take (one block per sample and image row).
-constexpr int kTrainTransposeMargin = 4096;       // rows T1 / T2 hold beyond M: split-K runs padded to a multiple of 128 rows
-inline bool train_dw_fused(int G, int N, int hid) { return G <= 16 && N >= 176 && hid % 64 == 0; }
 inline std::string train_config_check(const tld_config& c) {
     if (c.embed_dim % 64 || c.embed_dim > 1024 || c.embed_dim <= 0) return "embed_dim must be a multiple of 64 (the head width), <= 1024";
     if (c.patch_size <= 0 || c.image_size % c.patch_size) return "image_size must be a multiple of patch_size";

@@ -16,7 +16,7 @@
 #include "tld_host.h"
 #include "tld_param_layout.h"
 #include "tld_opt_plan.h"
-#include "tld_reach.h"          // train_config_check, the hooks' refusals
+#include "tld_reach.h"          // train_config_check, the hooks' refusals; tld_train_plan.h: the plan every dispatch below follows
 
 #include <algorithm>
 #include <cmath>
@@ -51,18 +51,13 @@ struct LayerB {          // engine-owned per-layer buffers
 
 inline dim3 g1(size_t n, int bs = 256) { return dim3((unsigned)((n + bs - 1) / bs)); }
 
-// launch-path bits (the table in include/tld_hip.h)
-enum : int {
-    PB_RESID_Q4 = 0, PB_RESID_GEN = 4, PB_LNB_Q4 = 5, PB_LNB_GEN = 8, PB_EMB_LDS = 9, PB_EMB_PLAIN = 13, PB_TAIL4_16 = 14, PB_TAIL4_32 = 15, PB_TAIL4_64 = 16,
-    PB_TAIL_GEN = 17, PB_TALL_COLS = 18, PB_TALL_PART = 19, PB_COLSUM4 = 20, PB_COLSUM = 21, PB_DW_FUSED = 22, PB_DW_UNFUSED = 23, PB_WG_TN = 24,
-    PB_WG_TR1 = 25, PB_WG_TRSK = 26, PB_WG_PAD = 27, PB_ATT_ONE = 28, PB_ATT_TWO = 29, PB_ATT_MASKED = 30
-};
-
 }  // namespace
 
-struct tld_train {
+struct tld_train : TrainShape {        // (the derived shape: tld_train_plan.h)
     tld_config cfg{};
-    int d = 0, L = 0, H = 0, N = 0, G = 0, pd = 0, hid = 0, S = 0, C = 0, ne = 0, text = 0, B = 0;
+    TrainWorkspace ws{};                 // the capacities create allocated
+    int cus = 0;                         // compute units of the engine's device
+    TrainStepPlan plan_max, plan_last;   // the plan of a step of max_batch samples, and of the last other batch size (step_plan)
     std::vector<Tensor> layout;
     int64_t nparam = 0;
     // offsets of the non-layer tensors
@@ -97,8 +92,6 @@ struct tld_train {
     float* attn_stats;                   // attention backward at > 256 tokens: [B, H, 2, N] (log-sum-exp | delta)
     float* splitk;                       // split-K partials of the weight-gradient GEMMs [8][max(hid, 3d)][d]
     float* part;                         // reduction partials
-    size_t part_floats = 0;
-    size_t tr_rows = 0, splitk_floats = 0;      // capacity of the transposed split-K operands (rows) and of the slice buffer
     bool weights_fresh = false;
     bool tn_wgrad = true;                // weight gradients without transposed copies (TLD_TRAIN_TN_WGRAD=0: the transposing form, a test hook)
 };
@@ -116,35 +109,28 @@ int dalloc(tld_train* e, T** p, size_t n) {
 }
 #define DALLOC(ptr, n) do { int _r = dalloc(e, &(ptr), (size_t)(n)); if (_r) return _r; } while (0)
 
-// C[Mr, Nc] = A[Mr, K] . W[Nc, K]^T on the engine's MFMA GEMM
-// dW[Nout, Kin] = dY^T X (dY [M, Nout], X [M, Kin], bf16 row-major) with both operands as they are -- the contraction index is the row, the MFMA
-// fragments come through the transposing LDS read (launch_gemm_tn): no transposed copies (8 transposes per block were 8.4 % of the step).
-// The output is small and the contraction long, so the rows are cut into `sk` runs of a multiple of 64 rows (split-K into fp32 slices
-// [sk][Nout][Kin], summed in a fixed order: bit-reproducible); sk = the count whose last round of 256 x 256 tiles is fullest.
-// Returns false (nothing launched) for shapes the kernel does not take.  (256 x 384 tiles -- 768-byte W rows with a rotating block swizzle, 240 tiles of
-// 10 splits instead of 252 of 7 -- measured 30.80 vs 30.88 ms per step, with 17 spilled registers: not kept.)
-bool wgrad_tn(const bf16* dY, int Nout, const bf16* X, int Kin, int M, float* dW, float* slices, size_t slice_floats, hipStream_t s) {
-    if (Nout % 256 || Kin % 256 || M % 64 || M <= 0) return false;
-    const int ncu = device_cu_count();
-    const long per = (long)(Nout / 256) * (Kin / 256);
-    double best = 0.0; int bsk = 1, bms = M;
-    for (int c = 1; c <= 32; ++c) {
-        const int mp = ((M + c - 1) / c + 63) / 64 * 64;
-        if ((c > 1 && mp < 1024) || (long)(c - 1) * mp >= M) continue;                            // runs too short / last run empty
-        if (c > 1 && (size_t)c * Nout * Kin > slice_floats) continue;                            // slice workspace
-        const long tiles = per * c, rounds = (tiles + ncu - 1) / ncu;
-        const double eff = (double)tiles / (double)(rounds * ncu) * ((double)M / ((double)c * mp));
-        if (eff > best + 1e-9) { best = eff; bsk = c; bms = mp; }
-    }
-    GemmParams g{};
-    g.A = dY; g.lda = Nout; g.W = X; g.ldw = Kin; g.M = bsk * Nout; g.N = Kin; g.K = bms; g.tn_ktotal = M; g.ldc = Kin;
-    g.c_f32 = bsk == 1 ? dW : slices;
-    g.w_batch_rows = bsk == 1 ? 0 : Nout;
-    launch_gemm_tn(g, s);
-    if (bsk > 1) hipLaunchKernelGGL(sum_slices, dim3((unsigned)(((size_t)Nout * Kin / 4 + 255) / 256)), dim3(256), 0, s, slices, bsk, (size_t)Nout * Kin, dW, (size_t)Nout * Kin / 4);
-    return true;
+// the plan of a step of `batch` samples: made once per batch size
+const TrainStepPlan& step_plan(tld_train* e, int batch) {
+    if (batch == e->plan_max.batch) return e->plan_max;
+    if (batch != e->plan_last.batch) e->plan_last = train_step_plan(*e, e->ws, batch, e->cus, e->tn_wgrad);
+    return e->plan_last;
 }
 
+// dW[Nout, Kin] = dY^T X (dY [M, Nout], X [M, Kin], bf16 row-major) with both operands as they are -- the contraction index is the row, the MFMA
+// fragments come through the transposing LDS read (launch_gemm_tn): no transposed copies (8 transposes per block were 8.4 % of the step).
+// The rows are cut into sp.sk runs of sp.run_rows rows (wgrad_split, tld_train_plan.h: split-K into fp32 slices [sk][Nout][Kin], summed in a fixed order).
+// (256 x 384 tiles -- 768-byte W rows with a rotating block swizzle, 240 tiles of 10 splits instead of 252 of 7 -- measured 30.80 vs 30.88 ms per step, with
+// 17 spilled registers: not kept.)
+void wgrad_tn(const bf16* dY, int Nout, const bf16* X, int Kin, int M, WgradSplit sp, float* dW, float* slices, hipStream_t s) {
+    GemmParams g{};
+    g.A = dY; g.lda = Nout; g.W = X; g.ldw = Kin; g.M = sp.sk * Nout; g.N = Kin; g.K = sp.run_rows; g.tn_ktotal = M; g.ldc = Kin;
+    g.c_f32 = sp.sk == 1 ? dW : slices;
+    g.w_batch_rows = sp.sk == 1 ? 0 : Nout;
+    launch_gemm_tn(g, s);
+    if (sp.sk > 1) hipLaunchKernelGGL(sum_slices, dim3((unsigned)(((size_t)Nout * Kin / 4 + 255) / 256)), dim3(256), 0, s, slices, sp.sk, (size_t)Nout * Kin, dW, (size_t)Nout * Kin / 4);
+}
+
+// C[Mr, Nc] = A[Mr, K] . W[Nc, K]^T on the engine's MFMA GEMM
 int gemm_f32(const bf16* A, int lda, const bf16* W, int ldw, float* C, int Mr, int Nc, int K, hipStream_t s) {
     GemmParams g{};
     g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.M = Mr; g.N = Nc; g.K = K; g.c_f32 = C; g.ldc = Nc;
@@ -195,10 +181,10 @@ int debug_begin(tld_train* e, int B, hipStream_t s) {
 }
 // set_debug(1): memory for every snapshot a step of max_batch samples takes (the names of the SNAP calls in tld_train_forward_backward_cb)
 int reserve_snapshots(tld_train* e) {
-    const size_t M = (size_t)e->B * e->N, d = e->d, hid = e->hid, pd = e->pd, B2 = 2 * (size_t)e->B;
+    const size_t M = (size_t)e->max_batch * e->N, d = e->d, hid = e->hid, pd = e->pd, B2 = 2 * (size_t)e->max_batch;
 #define RES(name, bytes) do { if (int _r = e->stages.reserve(name, bytes)) return _r; } while (0)
     RES("gx.tail", M * d * 4); RES("gxb.tail", M * d * 2);
-    const bool dw_fused = train_dw_fused(e->G, e->N, e->hid);
+    const bool dw_fused = e->plan_max.dw_fused;
     for (int i = 0; i < e->L; ++i) {
         const std::string p = "blk" + std::to_string(i) + ".";
         for (const char* n : {"gl", "dg", "dh"}) RES(p + n, M * hid * 2);
@@ -208,7 +194,7 @@ int reserve_snapshots(tld_train* e) {
         RES(p + "dqkv", M * 3 * d * 2); RES(p + "dkv", B2 * 2 * d * 4);
         if (i > 0) RES(p + "gxb.ln1", M * d * 2);
     }
-    RES("dy", B2 * d * 4); RES("dycat", B2 * d * 4); RES("dg1", (size_t)e->B * d * 4); RES("de", M * d * 4); RES("dpn", M * pd * 4); RES("dp16", M * pd * 4);
+    RES("dy", B2 * d * 4); RES("dycat", B2 * d * 4); RES("dg1", (size_t)e->max_batch * d * 4); RES("de", M * d * 4); RES("dpn", M * pd * 4); RES("dp16", M * pd * 4);
 #undef RES
     return TLD_OK;
 }
@@ -240,9 +226,7 @@ int train_forward(tld_train* e, const float* P, const float* x_noisy, const floa
                   float* loss_out, float* pred_out, hipStream_t s) {
     const int d = e->d, hid = e->hid, pd = e->pd, N = e->N, H = e->H, M = B * N, G = e->G;
     const dim3 blk(256);
-    const int dw_rows = dwconv_band_rows(G);
-    const dim3 dw_grid(B * (hid / 64) * ((G + dw_rows - 1) / dw_rows));
-    const size_t dw_lds = dwconv_lds_bytes(G);
+    const TrainStepPlan& plan = step_plan(e, B);
     {
         static PerDeviceOnce once;
         once.run([&] { hipFuncSetAttribute(reinterpret_cast<const void*>(dwconv_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
@@ -273,31 +257,34 @@ int train_forward(tld_train* e, const float* P, const float* x_noisy, const floa
         q.ln2_w = P + e->l2w; q.ln2_b = P + e->l2b; q.pos = P + e->pos; q.p = e->p16; q.pn = e->p16n; q.st1 = e->est1; q.e = e->e; q.st2 = e->est2;
         q.x0 = e->lb[0].x1; q.B = B; q.C = e->C; q.S = e->S; q.patch = e->cfg.patch_size; q.grid = G; q.pd = pd; q.d = d;
         const size_t lwb = (size_t)pd * d * 4;
-        if (lwb <= 65536) {
-            const int nwg = (M + 3) / 4 < 4 * device_cu_count() ? (M + 3) / 4 : 4 * device_cu_count();
-            if (d <= 256) { PATH(PB_EMB_LDS); hipLaunchKernelGGL((embed_fwd_lds_kernel<1>), dim3(nwg), blk, lwb, s, q); }
-            else if (d <= 512) { PATH(PB_EMB_LDS + 1); hipLaunchKernelGGL((embed_fwd_lds_kernel<2>), dim3(nwg), blk, lwb, s, q); }
-            else if (d <= 768) { PATH(PB_EMB_LDS + 2); hipLaunchKernelGGL((embed_fwd_lds_kernel<3>), dim3(nwg), blk, lwb, s, q); }
-            else { PATH(PB_EMB_LDS + 3); hipLaunchKernelGGL((embed_fwd_lds_kernel<4>), dim3(nwg), blk, lwb, s, q); }
-        } else {
-            PATH(PB_EMB_PLAIN);
-            hipLaunchKernelGGL(embed_fwd_kernel, dim3((M + 3) / 4), blk, 0, s, q);
+        const dim3 grid(plan.embed_wgs);
+        switch (plan.embed_lds) {
+        case 1: PATH(PB_EMB_LDS); hipLaunchKernelGGL((embed_fwd_lds_kernel<1>), grid, blk, lwb, s, q); break;
+        case 2: PATH(PB_EMB_LDS + 1); hipLaunchKernelGGL((embed_fwd_lds_kernel<2>), grid, blk, lwb, s, q); break;
+        case 3: PATH(PB_EMB_LDS + 2); hipLaunchKernelGGL((embed_fwd_lds_kernel<3>), grid, blk, lwb, s, q); break;
+        case 4: PATH(PB_EMB_LDS + 3); hipLaunchKernelGGL((embed_fwd_lds_kernel<4>), grid, blk, lwb, s, q); break;
+        default: PATH(PB_EMB_PLAIN); hipLaunchKernelGGL(embed_fwd_kernel, grid, blk, 0, s, q); break;
         }
     }
     // x_out = x_in + delta [; a_out = LN(x_out), stats]   (delta == nullptr: LayerNorm of x_in alone)
     auto resid_ln = [&](const bf16* x_in, const bf16* delta, bf16* x_out, const float* gamma, const float* beta, bf16* a_out, float2* st) {
         const dim3 grid((M + 3) / 4);
-        if (d == 768) { PATH(PB_RESID_Q4 + 2); hipLaunchKernelGGL((resid_add_ln_q4_kernel<3>), grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M); }
-        else if (d == 512) { PATH(PB_RESID_Q4 + 1); hipLaunchKernelGGL((resid_add_ln_q4_kernel<2>), grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M); }
-        else if (d == 256) { PATH(PB_RESID_Q4); hipLaunchKernelGGL((resid_add_ln_q4_kernel<1>), grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M); }
-        else if (d == 1024) { PATH(PB_RESID_Q4 + 3); hipLaunchKernelGGL((resid_add_ln_q4_kernel<4>), grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M); }
-        else if (delta) { PATH(PB_RESID_GEN); hipLaunchKernelGGL(resid_add_ln_kernel, grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M, d); }
-        else { PATH(PB_RESID_GEN); hipLaunchKernelGGL((ln_fwd_kernel<bf16>), grid, blk, 0, s, x_in, gamma, beta, a_out, (float*)nullptr, st, (const float*)nullptr, 1, M, d); }
+        switch (plan.resid_q4) {
+        case 3: PATH(PB_RESID_Q4 + 2); hipLaunchKernelGGL((resid_add_ln_q4_kernel<3>), grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M); break;
+        case 2: PATH(PB_RESID_Q4 + 1); hipLaunchKernelGGL((resid_add_ln_q4_kernel<2>), grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M); break;
+        case 1: PATH(PB_RESID_Q4); hipLaunchKernelGGL((resid_add_ln_q4_kernel<1>), grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M); break;
+        case 4: PATH(PB_RESID_Q4 + 3); hipLaunchKernelGGL((resid_add_ln_q4_kernel<4>), grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M); break;
+        default:
+            PATH(PB_RESID_GEN);
+            if (delta) hipLaunchKernelGGL(resid_add_ln_kernel, grid, blk, 0, s, x_in, delta, x_out, gamma, beta, a_out, st, M, d);
+            else hipLaunchKernelGGL((ln_fwd_kernel<bf16>), grid, blk, 0, s, x_in, gamma, beta, a_out, (float*)nullptr, st, (const float*)nullptr, 1, M, d);
+            break;
+        }
     };
     // (k | v) of the two conditioning tokens for every block in one launch (tld/transformer_blocks.py:66-68): the blocks' parameters are laid out
     // identically, so block i's kv_linear.weight sits i block-strides after block 0's
     const long blk_stride = e->L > 1 ? (long)(e->lp[1].kv - e->lp[0].kv) : 0;
-    const long kv_stride = (long)e->B * 2 * 2 * d;
+    const long kv_stride = (long)e->max_batch * 2 * 2 * d;
     hipLaunchKernelGGL(tiled_f32_kernel, dim3((2 * d + 31) / 32, (2 * B + 31) / 32, e->L), dim3(256), 0, s, e->y, (long)d, 1L, P + e->lp[0].kv, (long)d, 1L,
                        (const float*)nullptr, e->kvc_all, 2 * d, 2 * B, 2 * d, d, (float*)nullptr, 0, 0, 0L, blk_stride, kv_stride);
     for (int i = 0; i < e->L; ++i) {
@@ -317,7 +304,7 @@ int train_forward(tld_train* e, const float* P, const float* x_noisy, const floa
         resid_ln(b.x2, b.cr, b.x3, P + p.n3w, P + p.n3b, b.a3, b.st3);
         // x = x + MLPSepConv(LN3 x)   (:89-113,138)
         GEMM_TRY("training step", gemm_bf16(b.a3, d, b.wup, d, P + p.up_b, b.h, M, hid, d, s));
-        hipLaunchKernelGGL(dwconv_kernel, dw_grid, blk, dw_lds, s, b.h, b.dww_t, P + p.dw_b, b.hc, b.gl, B, G, hid, 0, dw_rows);
+        hipLaunchKernelGGL(dwconv_kernel, dim3(plan.dw_grid), blk, plan.dw_lds, s, b.h, b.dww_t, P + p.dw_b, b.hc, b.gl, B, G, hid, 0, plan.dw_rows);
         GEMM_TRY("training step", gemm_bf16(b.gl, hid, b.wdown, hid, P + p.down_b, b.o, M, d, hid, s));
         bf16* xnext = i + 1 < e->L ? e->lb[i + 1].x1 : e->xfin;
         if (i + 1 < e->L) resid_ln(b.x3, b.o, xnext, P + e->lp[i + 1].n1w, P + e->lp[i + 1].n1b, e->lb[i + 1].a1, e->lb[i + 1].st1);      // + the next block's LN1
@@ -341,14 +328,14 @@ int tld_train_create(const tld_config* cfg, tld_train** out) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(TLD_ERR_HIP, "no HIP device: the training engine has no CPU path");
     if (cfg->device_id < 0 || cfg->device_id >= ndev) return fail(TLD_ERR_INVALID, "device_id %d out of range", cfg->device_id);
-    const int G = cfg->image_size / cfg->patch_size;
     DeviceGuard dg(cfg->device_id);
     tld_train* e = new tld_train();
     e->cfg = *cfg;
-    e->d = cfg->embed_dim; e->L = cfg->n_layers; e->H = e->d / 64; e->G = G; e->N = G * G; e->S = cfg->image_size; e->C = cfg->n_channels;
-    e->pd = e->C * cfg->patch_size * cfg->patch_size; e->hid = e->d * cfg->mlp_multiplier; e->ne = cfg->noise_embed_dims; e->text = cfg->text_emb_size;
-    e->B = cfg->max_batch;
+    static_cast<TrainShape&>(*e) = train_shape(*cfg);
+    e->ws = train_workspace(*e);
+    e->cus = device_cu_count();
     e->tn_wgrad = !(getenv("TLD_TRAIN_TN_WGRAD") && atoi(getenv("TLD_TRAIN_TN_WGRAD")) == 0);
+    e->plan_max = train_step_plan(*e, e->ws, e->max_batch, e->cus, e->tn_wgrad);
     const int d = e->d, hid = e->hid, pd = e->pd;
     {   // canonical order: Denoiser.named_parameters() of the reference (tld_param_layout.h; pinned by tests/test_train_host.py)
         const ParamLayout pl = make_param_layout(d, e->L, e->ne, pd, hid, e->N, e->text);
@@ -358,10 +345,10 @@ int tld_train_create(const tld_config* cfg, tld_train** out) {
         e->lbw = pl.lbw; e->lbb = pl.lbb;
     }
 
-    const size_t B = e->B, M = B * e->N;      // (M hid 2 < 4 GiB and (M + 4096) max(hid, 3 d) 2 < 4 GiB: train_config_check above)
+    const size_t B = e->max_batch, M = B * e->N;      // (M hid 2 < 4 GiB and (M + 4096) max(hid, 3 d) 2 < 4 GiB: train_config_check above)
     auto cleanup = [&](int rc) { for (void* p : e->allocs) hipFree(p); delete e; return rc; };
     auto alloc_all = [&]() -> int {
-        DALLOC(e->angular, e->ne / 2); DALLOC(e->zero_bias, 3 * hid > 4096 ? 3 * hid : 4096);
+        DALLOC(e->angular, e->ne / 2); DALLOC(e->zero_bias, e->ws.zero_bias);
         DALLOC(e->sinb, B * e->ne); DALLOC(e->h1, B * d); DALLOC(e->g1v, B * d); DALLOC(e->ycat, B * 2 * d); DALLOC(e->y, B * 2 * d);
         DALLOC(e->dy, B * 2 * d); DALLOC(e->dycat, B * 2 * d); DALLOC(e->dg1, B * d); DALLOC(e->dkv_all, (size_t)e->L * B * 2 * 2 * d); DALLOC(e->kvc_all, (size_t)e->L * B * 2 * 2 * d);
         DALLOC(e->dy_parts, (size_t)e->L * B * 2 * d); DALLOC(e->yst, B * 2);
@@ -369,18 +356,10 @@ int tld_train_create(const tld_config* cfg, tld_train** out) {
         DALLOC(e->dpn, M * pd); DALLOC(e->dp16, M * pd); DALLOC(e->est1, M); DALLOC(e->est2, M); DALLOC(e->xfin, M * d);
         DALLOC(e->dout, M * pd); DALLOC(e->row_loss, M); DALLOC(e->io, 4); DALLOC(e->pred_scratch, B * e->C * e->S * e->S);
         const size_t wide = hid > 3 * d ? hid : 3 * d;
-        DALLOC(e->gx, M * d); DALLOC(e->gxb, M * d); e->tr_rows = M + kTrainTransposeMargin; DALLOC(e->T1, e->tr_rows * wide); DALLOC(e->T2, e->tr_rows * wide); DALLOC(e->dbig, M * hid);
-        DALLOC(e->dsmall, M * 3 * d); DALLOC(e->dsmall2, M * d); DALLOC(e->attn_stats, 2 * M * e->H); DALLOC(e->scr, (size_t)pd * d + 64);
-        const size_t nchunk = (M + 255) / 256;
-        size_t need = nchunk * 2 * (size_t)wide;                              // LN / colsum partials
-        if (((M + 31) / 32) * 2 * (size_t)d > need) need = ((M + 31) / 32) * 2 * (size_t)d;   // LayerNorm-backward partials (32-row workgroups)
-        if (B * e->G * 10 * (size_t)hid > need) need = B * e->G * 10 * (size_t)hid;          // depthwise weight-gradient partials (per sample and image row)
-        if (((M + 63) / 64) * (size_t)wide > need) need = ((M + 63) / 64) * (size_t)wide;     // column-sum partials (64-row chunks)
-        e->splitk_floats = 8 * (size_t)wide * d;
-        DALLOC(e->splitk, e->splitk_floats);
-        if (((M + 63) / 64) * (size_t)pd * d > need) need = ((M + 63) / 64) * (size_t)pd * d;    // tall weight-gradient partials (64-row chunks)
-        e->part_floats = need;
-        DALLOC(e->part, need);
+        DALLOC(e->gx, M * d); DALLOC(e->gxb, M * d); DALLOC(e->T1, e->ws.tr_rows * wide); DALLOC(e->T2, e->ws.tr_rows * wide); DALLOC(e->dbig, M * hid);
+        DALLOC(e->dsmall, M * 3 * d); DALLOC(e->dsmall2, M * d); DALLOC(e->attn_stats, e->ws.attn_stats); DALLOC(e->scr, e->ws.scr);
+        DALLOC(e->splitk, e->ws.splitk_floats);
+        DALLOC(e->part, e->ws.part_floats);
         e->lb.resize(e->L);
         for (int i = 0; i < e->L; ++i) {
             LayerB& q = e->lb[i];
@@ -394,7 +373,7 @@ int tld_train_create(const tld_config* cfg, tld_train** out) {
         return 0;
     };
     if (int rc = alloc_all()) return cleanup(rc);
-    if (hipMemset(e->zero_bias, 0, (size_t)(3 * hid > 4096 ? 3 * hid : 4096) * 4) != hipSuccess) return cleanup(fail(TLD_ERR_HIP, "hipMemset failed"));
+    if (hipMemset(e->zero_bias, 0, e->ws.zero_bias * 4) != hipSuccess) return cleanup(fail(TLD_ERR_HIP, "hipMemset failed"));
     // angular_speeds = 2 pi exp(linspace(log 1, log 1000, ne / 2))   (tld/transformer_blocks.py:11-15; float32 arithmetic as torch does it)
     {
         const int half = e->ne / 2;
@@ -456,7 +435,7 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
                                   int32_t batch, float* loss_out, float* pred_out, void* hip_stream, tld_grad_ready_fn grad_ready, void* user) {
     if (!e || !x_noisy || !noise_level || !label || !target || !loss_out || !pred_out) return fail(TLD_ERR_INVALID, "null argument");
     if (!e->params) return fail(TLD_ERR_STATE, "tld_train_bind first");
-    if (batch <= 0 || batch > e->B) return fail(TLD_ERR_INVALID, "batch %d outside [1, max_batch = %d]", batch, e->B);
+    if (batch <= 0 || batch > e->max_batch) return fail(TLD_ERR_INVALID, "batch %d outside [1, max_batch = %d]", batch, e->max_batch);
     DeviceGuard dg(e->cfg.device_id);
     hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
     if (!e->weights_fresh) { if (int rc = tld_train_refresh_weights(e, hip_stream)) return rc; }
@@ -464,9 +443,7 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
     float* P = e->params; float* Gd = e->grads;
     const dim3 blk(256);
     const int nchunk = (M + 255) / 256;
-    const int dw_rows = dwconv_band_rows(G);
-    const dim3 dw_grid(B * (hid / 64) * ((G + dw_rows - 1) / dw_rows));
-    const size_t dw_lds = dwconv_lds_bytes(G);
+    const TrainStepPlan& plan = step_plan(e, B);
     if (e->debug) {
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)
@@ -484,7 +461,7 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
         if (db) hipLaunchKernelGGL(small_colsum, g1(Nn), dim3(256), 0, s, dyp, ldy, db, R, Nn, 0);
     };
     const long blk_stride = e->L > 1 ? (long)(e->lp[1].kv - e->lp[0].kv) : 0;       // (as in train_forward: block i's kv_linear.weight and its (k | v) rows)
-    const long kv_stride = (long)e->B * 2 * 2 * d;
+    const long kv_stride = (long)e->max_batch * 2 * 2 * d;
 
     // ================================================ forward ================================================
     if (int rc = train_forward(e, P, x_noisy, noise_level, label, target, B, loss_out, pred_out, s)) return rc;
@@ -494,116 +471,102 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
     auto reduce = [&](int nparts, size_t stride, size_t part_off, float* dst, int n, int acc) {
         hipLaunchKernelGGL(reduce_partials, dim3((n + 15) / 16), dim3(1024), 0, s, e->part + part_off, nparts, stride, dst, n, acc);
     };
-    // dW[Nn, K] = dy^T x over the M rows (dy fp32 [M, Nn], Nn = patch_dim or smaller; x [M, K]) -> dst (fixed-order sum of per-chunk partials)
-    auto tall_dw = [&](const float* dyp, int Nn, auto xp, int K, float* dst) {
+    // dW[Nn, K] = dy^T x over the M rows (dy fp32 [M, Nn], Nn = patch_dim; x [M, K]) -> dst (fixed-order sum of per-chunk partials)
+    auto tall_dw = [&](const TallDwPlan& t, const float* dyp, auto xp, float* dst) {
         using TX = std::remove_cv_t<std::remove_pointer_t<decltype(xp)>>;
-        const int nc64 = (M + 63) / 64;
-        if ((Nn == 16 || Nn == 32 || Nn == 64) && (size_t)nc64 * Nn * K <= e->part_floats) {
-            PATH(PB_TALL_COLS);
-            const dim3 grid((K + 255) / 256, nc64);
-            if (Nn == 16) hipLaunchKernelGGL((tall_dw_cols_partial<TX, 16>), grid, blk, 0, s, dyp, xp, K, M, 64, e->part);
-            else if (Nn == 32) hipLaunchKernelGGL((tall_dw_cols_partial<TX, 32>), grid, blk, 0, s, dyp, xp, K, M, 64, e->part);
-            else hipLaunchKernelGGL((tall_dw_cols_partial<TX, 64>), grid, blk, 0, s, dyp, xp, K, M, 64, e->part);
-            reduce(nc64, (size_t)Nn * K, 0, dst, Nn * K, 0);
-        } else {
+        const int K = t.K, nc64 = (M + 63) / 64;
+        const dim3 grid((K + 255) / 256, nc64);
+        switch (t.nn) {
+        case 16: PATH(PB_TALL_COLS); hipLaunchKernelGGL((tall_dw_cols_partial<TX, 16>), grid, blk, 0, s, dyp, xp, K, M, 64, e->part); reduce(nc64, (size_t)16 * K, 0, dst, 16 * K, 0); break;
+        case 32: PATH(PB_TALL_COLS); hipLaunchKernelGGL((tall_dw_cols_partial<TX, 32>), grid, blk, 0, s, dyp, xp, K, M, 64, e->part); reduce(nc64, (size_t)32 * K, 0, dst, 32 * K, 0); break;
+        case 64: PATH(PB_TALL_COLS); hipLaunchKernelGGL((tall_dw_cols_partial<TX, 64>), grid, blk, 0, s, dyp, xp, K, M, 64, e->part); reduce(nc64, (size_t)64 * K, 0, dst, 64 * K, 0); break;
+        default:
             PATH(PB_TALL_PART);
-            hipLaunchKernelGGL((tall_dw_partial<TX>), dim3((Nn * K + 255) / 256, nchunk), blk, 0, s, dyp, Nn, xp, K, M, 256, e->part);
-            reduce(nchunk, (size_t)Nn * K, 0, dst, Nn * K, 0);
+            hipLaunchKernelGGL((tall_dw_partial<TX>), dim3((pd * K + 255) / 256, nchunk), blk, 0, s, dyp, pd, xp, K, M, 256, e->part);
+            reduce(nchunk, (size_t)pd * K, 0, dst, pd * K, 0);
+            break;
         }
     };
-    auto ln_bwd_rows = [&](auto dyp, auto xp, const float2* st, const float* gamma, float* dx, int acc, float* dgamma, float* dbeta, int rows, int width,
-                           bf16* dxb = nullptr) {
+    // LayerNorm backward over `rows` rows of width d
+    auto ln_bwd_rows = [&](auto dyp, auto xp, const float2* st, const float* gamma, float* dx, int acc, float* dgamma, float* dbeta, int rows, bf16* dxb = nullptr) {
         using TDY = std::remove_cv_t<std::remove_pointer_t<decltype(dyp)>>;
         using TX = std::remove_cv_t<std::remove_pointer_t<decltype(xp)>>;
-        const int nb = (rows + 31) / 32;                                  // 32 rows per workgroup: >= 1024 workgroups at the training batch
-        if (width == 768) { PATH(PB_LNB_Q4 + 2); hipLaunchKernelGGL((ln_bwd_q4_kernel<TDY, TX, 3>), dim3(nb), blk, 0, s, dyp, xp, st, gamma, dx, acc, e->part, 32, rows, dxb); }
-        else if (width == 512) { PATH(PB_LNB_Q4 + 1); hipLaunchKernelGGL((ln_bwd_q4_kernel<TDY, TX, 2>), dim3(nb), blk, 0, s, dyp, xp, st, gamma, dx, acc, e->part, 32, rows, dxb); }
-        else if (width == 256) { PATH(PB_LNB_Q4); hipLaunchKernelGGL((ln_bwd_q4_kernel<TDY, TX, 1>), dim3(nb), blk, 0, s, dyp, xp, st, gamma, dx, acc, e->part, 32, rows, dxb); }
-        else { PATH(PB_LNB_GEN); hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX>), dim3(nb), blk, 0, s, dyp, xp, st, gamma, dx, acc, e->part, 32, rows, width, dxb); }
+        const int width = d, nb = (rows + 31) / 32;                       // 32 rows per workgroup: >= 1024 workgroups at the training batch
+        switch (plan.lnb_q4) {
+        case 3: PATH(PB_LNB_Q4 + 2); hipLaunchKernelGGL((ln_bwd_q4_kernel<TDY, TX, 3>), dim3(nb), blk, 0, s, dyp, xp, st, gamma, dx, acc, e->part, 32, rows, dxb); break;
+        case 2: PATH(PB_LNB_Q4 + 1); hipLaunchKernelGGL((ln_bwd_q4_kernel<TDY, TX, 2>), dim3(nb), blk, 0, s, dyp, xp, st, gamma, dx, acc, e->part, 32, rows, dxb); break;
+        case 1: PATH(PB_LNB_Q4); hipLaunchKernelGGL((ln_bwd_q4_kernel<TDY, TX, 1>), dim3(nb), blk, 0, s, dyp, xp, st, gamma, dx, acc, e->part, 32, rows, dxb); break;
+        default: PATH(PB_LNB_GEN); hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX>), dim3(nb), blk, 0, s, dyp, xp, st, gamma, dx, acc, e->part, 32, rows, width, dxb); break;
+        }
         if (dbeta == dgamma + width) reduce(nb, 2 * (size_t)width, 0, dgamma, 2 * width, 0);       // (weight, bias) are neighbours in the flat vector: one launch
         else {
             reduce(nb, 2 * (size_t)width, 0, dgamma, width, 0);
             reduce(nb, 2 * (size_t)width, width, dbeta, width, 0);
         }
     };
-    auto colsum = [&](auto ap, int rows, int cols, float* dst) {
+    // column sums of the M rows of a [M, c.cols] matrix
+    auto colsum = [&](const ColsumPlan& c, auto ap, float* dst) {
         using T = std::remove_cv_t<std::remove_pointer_t<decltype(ap)>>;
-        if (cols % 4 == 0 && rows >= 4096) {        // four columns per thread, 64-row chunks (the chunk count feeds the 64 part-lanes of the reduction)
+        const int rows = M, cols = c.cols;
+        if (c.four) {
             const int nb = (rows + 63) / 64;
             PATH(PB_COLSUM4);
             hipLaunchKernelGGL((colsum4_partial<T>), dim3((cols / 4 + 255) / 256, nb), blk, 0, s, ap, rows, cols, 64, e->part);
             reduce(nb, (size_t)cols, 0, dst, cols, 0);
-            return;
+        } else {
+            const int nb = (rows + 255) / 256;
+            PATH(PB_COLSUM);
+            hipLaunchKernelGGL((colsum_partial<T>), dim3((cols + 255) / 256, nb), blk, 0, s, ap, rows, cols, 256, e->part);
+            reduce(nb, (size_t)cols, 0, dst, cols, 0);
         }
-        const int nb = (rows + 255) / 256;
-        PATH(PB_COLSUM);
-        hipLaunchKernelGGL((colsum_partial<T>), dim3((cols + 255) / 256, nb), blk, 0, s, ap, rows, cols, 256, e->part);
-        reduce(nb, (size_t)cols, 0, dst, cols, 0);
     };
-    auto transpose = [&](auto inp, int rows, int cols, bf16* outp) {        // [rows, cols] -> [cols, rows]
-        using T = std::remove_cv_t<std::remove_pointer_t<decltype(inp)>>;
-        hipLaunchKernelGGL((transpose_to_bf16<T>), dim3((cols + 31) / 32, (rows + 31) / 32), blk, 0, s, inp, cols, outp, rows, rows, cols);
-    };
-    // dW[Nout, Kin] = dY^T X with dY [M, Nout], X [M, Kin] (bf16): both operands transposed so that the contraction (M) is contiguous.
-    // The output is small and the contraction long, so the rows are cut into `sk` runs (split-K): the transposes write the stacked
-    // operands [split][Nout | Kin][M / sk], ONE GEMM launch multiplies every split with its own W block (GemmParams::w_batch_rows)
-    // into fp32 partials [split][Nout][Kin], and a fixed-order sum finishes (bit-reproducible).
-    auto weight_grad = [&](const bf16* dY, int Nout, const bf16* X, int Kin, float* dW) -> int {
-        int sk = 1;
-        if (Nout % 256 == 0) while (sk < 8 && (M / (sk * 2)) % 128 == 0 && M / (sk * 2) >= 1024) sk *= 2;
-        int ms = M / sk;
-        // Round 3: any split count, runs padded to a multiple of 128 rows (zero rows contribute nothing).  With 256 x 256 tiles the launch has
-        // sk (Nout / 256) (Kin / 256) workgroups; pick the sk whose last round is fullest (e.g. 7 x 12 x 3 = 252 of 256 CUs for the
-        // up-projection weight instead of 8 x 12 x 6 = 576 128-wide tiles = 2.25 rounds), discounted by the padding.
-        if (Nout % 256 == 0 && Kin % 256 == 0 && M % 64 == 0 && M >= 4096) {
-            const int ncu = device_cu_count();
-            const long per = (long)(Nout / 256) * (Kin / 256);
-            double best = 0.0; int bsk = 0, bms = 0;
-            for (int c = 2; c <= 32; ++c) {
-                const int mp = ((M + c - 1) / c + 127) / 128 * 128;
-                if (mp < 1024 || (long)(c - 1) * mp >= M) continue;                                     // runs too short / last run empty
-                if ((size_t)c * Nout * Kin > e->splitk_floats || (size_t)c * mp > e->tr_rows) continue;   // workspace
-                const long tiles = per * c, rounds = (tiles + ncu - 1) / ncu;
-                const double eff = (double)tiles / (double)(rounds * ncu) * ((double)M / ((double)c * mp));
-                if (eff > best + 1e-9) { best = eff; bsk = c; bms = mp; }
-            }
-            if (bsk) { sk = bsk; ms = bms; }
-        }
-        if (e->tn_wgrad && wgrad_tn(dY, Nout, X, Kin, M, dW, e->splitk, e->splitk_floats, s)) { PATH(PB_WG_TN); return 0; }
-        if (M % 64) {      // (token counts that are not multiples of 64, e.g. 144 x 3 rows): the GEMM's K loop takes whole 64-row steps, so the
-            ms = (M + 63) / 64 * 64;       // transposed operands get zero columns up to the next multiple of 64 (sk == 1 here)
+    // dW[Nout, Kin] = dY^T X with dY [M, Nout], X [M, Kin] (bf16), in the form and with the split the plan chose (wgrad_plan, tld_train_plan.h).  The
+    // transposing forms write both operands transposed so that the contraction (M) is contiguous: the stacked operands [split][Nout | Kin][run_rows], ONE GEMM
+    // launch multiplies every split with its own W block (GemmParams::w_batch_rows) into fp32 partials [split][Nout][Kin], and a fixed-order sum finishes
+    // (bit-reproducible).
+    auto weight_grad = [&](const WgradPlan& w, const bf16* dY, int Nout, const bf16* X, int Kin, float* dW) -> int {
+        const int sk = w.sk, ms = w.run_rows;
+        auto tr64 = [&](const bf16* src, int cols, bf16* dst) { hipLaunchKernelGGL(transpose_bf16_64, dim3(cols / 64, sk * ms / 64), blk, 0, s, src, cols, dst, ms, M, cols, sk); };
+        switch (w.form) {
+        case WG_TN:
+            PATH(PB_WG_TN);
+            wgrad_tn(dY, Nout, X, Kin, M, WgradSplit{sk, ms}, dW, e->splitk, s);
+            return 0;
+        case WG_PAD:       // the GEMM's K loop takes whole 64-row steps: the transposed operands get zero columns up to the next multiple of 64 (one run)
             PATH(PB_WG_PAD);
             hipMemsetAsync(e->T1, 0, (size_t)Nout * ms * 2, s);
             hipMemsetAsync(e->T2, 0, (size_t)Kin * ms * 2, s);
+            hipLaunchKernelGGL((transpose_to_bf16<bf16>), dim3((Nout + 31) / 32, (M + 31) / 32), blk, 0, s, dY, Nout, e->T1, ms, M, Nout, sk);
+            hipLaunchKernelGGL((transpose_to_bf16<bf16>), dim3((Kin + 31) / 32, (M + 31) / 32), blk, 0, s, X, Kin, e->T2, ms, M, Kin, sk);
+            return gemm_f32(e->T1, ms, e->T2, ms, dW, Nout, Kin, ms, s);
+        case WG_TR1:
+            PATH(PB_WG_TR1);
+            tr64(dY, Nout, e->T1); tr64(X, Kin, e->T2);
+            return gemm_f32(e->T1, ms, e->T2, ms, dW, Nout, Kin, ms, s);
+        default: {
+            PATH(PB_WG_TRSK);
+            tr64(dY, Nout, e->T1); tr64(X, Kin, e->T2);
+            GemmParams g{};
+            g.A = e->T1; g.lda = ms; g.W = e->T2; g.ldw = ms; g.M = sk * Nout; g.N = Kin; g.K = ms; g.c_f32 = e->splitk; g.ldc = Kin;
+            g.w_batch_rows = Nout; g.w_batch_stride_bytes = (unsigned)((size_t)Kin * ms * 2);
+            if (int rc = launch_gemm(g, EPI_F32, s)) return rc;
+            hipLaunchKernelGGL(sum_slices, dim3((unsigned)(((size_t)Nout * Kin / 4 + 255) / 256)), blk, 0, s, e->splitk, sk, (size_t)Nout * Kin, dW, (size_t)Nout * Kin / 4);
+            return 0;
         }
-        auto tr = [&](const bf16* src, int cols, bf16* dst) {
-            if (M % 64 == 0 && cols % 64 == 0 && ms % 64 == 0)
-                hipLaunchKernelGGL(transpose_bf16_64, dim3(cols / 64, sk * ms / 64), blk, 0, s, src, cols, dst, ms, M, cols, sk);
-            else
-                hipLaunchKernelGGL((transpose_to_bf16<bf16>), dim3((cols + 31) / 32, (M + 31) / 32), blk, 0, s, src, cols, dst, ms, M, cols, sk);
-        };
-        tr(dY, Nout, e->T1);
-        tr(X, Kin, e->T2);
-        if (sk == 1) { if (M % 64 == 0) PATH(PB_WG_TR1); return gemm_f32(e->T1, ms, e->T2, ms, dW, Nout, Kin, ms, s); }      // (ms == M, or M rounded up to 64)
-        PATH(PB_WG_TRSK);
-        GemmParams g{};
-        g.A = e->T1; g.lda = ms; g.W = e->T2; g.ldw = ms; g.M = sk * Nout; g.N = Kin; g.K = ms; g.c_f32 = e->splitk; g.ldc = Kin;
-        g.w_batch_rows = Nout; g.w_batch_stride_bytes = (unsigned)((size_t)Kin * ms * 2);
-        if (int rc = launch_gemm(g, EPI_F32, s)) return rc;
-        if ((Nout * Kin) % 4 == 0) hipLaunchKernelGGL(sum_slices, dim3((unsigned)(((size_t)Nout * Kin / 4 + 255) / 256)), blk, 0, s, e->splitk, sk, (size_t)Nout * Kin, dW, (size_t)Nout * Kin / 4);
-        else hipLaunchKernelGGL(reduce_partials, dim3((Nout * Kin + 15) / 16), dim3(1024), 0, s, e->splitk, sk, (size_t)Nout * Kin, dW, Nout * Kin, 0);
-        return 0;
+        }
     };
 
     // out_proj: gx = dout Wout;  dWout = dout^T x_final;  dbout
     // gx and its bf16 copy (the top block's GEMM operand)
-    if (pd == 16) { PATH(PB_TAIL4_16); hipLaunchKernelGGL((tail_dx4_kernel<16>), g1((size_t)M * d / 4), blk, 0, s, e->dout, P + e->outw, e->gx, e->gxb, M, d); }
-    else if (pd == 32) { PATH(PB_TAIL4_32); hipLaunchKernelGGL((tail_dx4_kernel<32>), g1((size_t)M * d / 4), blk, 0, s, e->dout, P + e->outw, e->gx, e->gxb, M, d); }
-    else if (pd == 64) { PATH(PB_TAIL4_64); hipLaunchKernelGGL((tail_dx4_kernel<64>), g1((size_t)M * d / 4), blk, 0, s, e->dout, P + e->outw, e->gx, e->gxb, M, d); }
-    else { PATH(PB_TAIL_GEN); hipLaunchKernelGGL(tail_dx_kernel, g1((size_t)M * d), blk, 0, s, e->dout, P + e->outw, e->gx, e->gxb, M, pd, d); }
+    switch (plan.tail4) {
+    case 16: PATH(PB_TAIL4_16); hipLaunchKernelGGL((tail_dx4_kernel<16>), g1((size_t)M * d / 4), blk, 0, s, e->dout, P + e->outw, e->gx, e->gxb, M, d); break;
+    case 32: PATH(PB_TAIL4_32); hipLaunchKernelGGL((tail_dx4_kernel<32>), g1((size_t)M * d / 4), blk, 0, s, e->dout, P + e->outw, e->gx, e->gxb, M, d); break;
+    case 64: PATH(PB_TAIL4_64); hipLaunchKernelGGL((tail_dx4_kernel<64>), g1((size_t)M * d / 4), blk, 0, s, e->dout, P + e->outw, e->gx, e->gxb, M, d); break;
+    default: PATH(PB_TAIL_GEN); hipLaunchKernelGGL(tail_dx_kernel, g1((size_t)M * d), blk, 0, s, e->dout, P + e->outw, e->gx, e->gxb, M, pd, d); break;
+    }
     SNAP("gx.tail", e->gx, ST_F32, s, M, d); SNAP("gxb.tail", e->gxb, ST_BF16, s, M, d);
-    tall_dw(e->dout, pd, (const bf16*)e->xfin, d, Gd + e->outw);
-    colsum(e->dout, M, pd, Gd + e->outb);
+    tall_dw(plan.tall[TALL_OUT], e->dout, (const bf16*)e->xfin, Gd + e->outw);
+    colsum(plan.colsum[CS_PD], e->dout, Gd + e->outb);
 
     for (int i = e->L - 1; i >= 0; --i) {
         LayerB& b = e->lb[i]; const LayerP& p = e->lp[i];
@@ -611,13 +574,12 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
         SNAP(sn + "gx.in", e->gx, ST_F32, s, M, d);
         // ---- MLP: o = g Wdown^T + b;  g = GELU(hc);  hc = dwconv(h);  h = a3 Wup^T + b;  a3 = LN3(x3)
         // (e->gxb = bf16(e->gx): written by whoever completed gx -- tail_dx_kernel for the top block, the LayerNorm-1 backward of the block above otherwise)
-        colsum(e->gxb, M, d, Gd + p.down_b);
-        GEMM_TRY("training step", weight_grad(e->gxb, d, b.gl, hid, Gd + p.down_w));
+        colsum(plan.colsum[CS_D], e->gxb, Gd + p.down_b);
+        GEMM_TRY("training step", weight_grad(plan.wg[WGP_DOWN], e->gxb, d, b.gl, hid, Gd + p.down_w));
         GEMM_TRY("training step", gemm_bf16(e->gxb, d, b.wdown_t, d, e->zero_bias, e->dbig, M, hid, d, s));                         // dg = go Wdown
         SNAP(sn + "dg", e->dbig, ST_BF16, s, M, hid);
-        const bool dw_fused = train_dw_fused(G, N, hid);
-        if (dw_fused) {      PATH(PB_DW_FUSED);      // GELU' multiply, depthwise weight-gradient partials and input gradient in one pass (both images of a (sample, 64-channel chunk) in LDS)
-            hipLaunchKernelGGL(dwconv_bwd_img_kernel, dim3(B * (hid / 64)), blk, (size_t)2 * N * 128, s, e->dbig, b.hc, b.h, b.dww_t, b.gl, e->part, G, hid);   // dh -> b.gl (its forward value is consumed)
+        if (plan.dw_fused) {      PATH(PB_DW_FUSED);      // GELU' multiply, depthwise weight-gradient partials and input gradient in one pass (both images of a (sample, 64-channel chunk) in LDS)
+            hipLaunchKernelGGL(dwconv_bwd_img_kernel, dim3(plan.dw_bwd_grid), blk, plan.dw_bwd_lds, s, e->dbig, b.hc, b.h, b.dww_t, b.gl, e->part, G, hid);   // dh -> b.gl (its forward value is consumed)
             hipLaunchKernelGGL(dwconv_wgrad_reduce, dim3((hid * 11 + 63) / 64), dim3(1024), 0, s, e->part, Gd + p.dw_w, Gd + p.dw_b, B, hid, 11, Gd + p.up_b);   // + the up-projection's bias gradient
         } else {
             PATH(PB_DW_UNFUSED);
@@ -625,24 +587,24 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
             SNAP(sn + "dhc", e->dbig, ST_BF16, s, M, hid);
             hipLaunchKernelGGL(dwconv_wgrad_kernel, dim3((hid + 255) / 256, B * G), blk, 0, s, e->dbig, b.h, e->part, G, hid);
             hipLaunchKernelGGL(dwconv_wgrad_reduce, dim3((hid * 10 + 63) / 64), dim3(1024), 0, s, e->part, Gd + p.dw_w, Gd + p.dw_b, B * G, hid);
-            hipLaunchKernelGGL(dwconv_kernel, dw_grid, blk, dw_lds, s, e->dbig, b.dww_t, (const float*)nullptr, b.gl, (bf16*)nullptr, B, G, hid, 1, dw_rows);   // dh -> b.gl
+            hipLaunchKernelGGL(dwconv_kernel, dim3(plan.dw_grid), blk, plan.dw_lds, s, e->dbig, b.dww_t, (const float*)nullptr, b.gl, (bf16*)nullptr, B, G, hid, 1, plan.dw_rows);   // dh -> b.gl
         }
         SNAP(sn + "dh", b.gl, ST_BF16, s, M, hid);
-        if (!dw_fused) colsum(b.gl, M, hid, Gd + p.up_b);
-        GEMM_TRY("training step", weight_grad(b.gl, hid, b.a3, d, Gd + p.up_w));
+        if (plan.colsum[CS_HID].used) colsum(plan.colsum[CS_HID], b.gl, Gd + p.up_b);
+        GEMM_TRY("training step", weight_grad(plan.wg[WGP_UP], b.gl, hid, b.a3, d, Gd + p.up_w));
         GEMM_TRY("training step", gemm_bf16(b.gl, hid, b.wup_t, hid, e->zero_bias, e->dsmall2, M, d, hid, s));                     // da3 = dh Wup
         SNAP(sn + "da3", e->dsmall2, ST_BF16, s, M, d);
-        ln_bwd_rows(e->dsmall2, b.x3, b.st3, P + p.n3w, e->gx, 1, Gd + p.n3w, Gd + p.n3b, M, d);
+        ln_bwd_rows(e->dsmall2, b.x3, b.st3, P + p.n3w, e->gx, 1, Gd + p.n3w, Gd + p.n3b, M);
         SNAP(sn + "gx.ln3", e->gx, ST_F32, s, M, d);
         // ---- cross-attention: cr = CA(qc, kv);  qc = a2 Wq^T;  kv = y Wkv^T;  a2 = LN2(x2)
         float* dkv = e->dkv_all + (size_t)i * kv_stride;
         hipLaunchKernelGGL(cross_bwd_kernel, dim3(B * H), blk, 0, s, e->gx, b.qc, b.kvc, b.p0, e->dsmall2, dkv, N, d);   // dqc -> dsmall2
         SNAP(sn + "dqc", e->dsmall2, ST_BF16, s, M, d); SNAP(sn + "dkv", dkv, ST_F32, s, 2 * B, 2 * d);
         lin_dw(dkv, 2 * d, e->y, d, Gd + p.kv, nullptr, 2 * B, 2 * d, d);       // (per block: its gradient range must be complete at the grad_ready call below)
-        GEMM_TRY("training step", weight_grad(e->dsmall2, d, b.a2, d, Gd + p.q));
+        GEMM_TRY("training step", weight_grad(plan.wg[WGP_Q], e->dsmall2, d, b.a2, d, Gd + p.q));
         GEMM_TRY("training step", gemm_bf16(e->dsmall2, d, b.wq_t, d, e->zero_bias, e->dsmall, M, d, d, s));                       // da2 = dqc Wq
         SNAP(sn + "da2", e->dsmall, ST_BF16, s, M, d);
-        ln_bwd_rows(e->dsmall, b.x2, b.st2, P + p.n2w, e->gx, 1, Gd + p.n2w, Gd + p.n2b, M, d);
+        ln_bwd_rows(e->dsmall, b.x2, b.st2, P + p.n2w, e->gx, 1, Gd + p.n2w, Gd + p.n2b, M);
         SNAP(sn + "gx.ln2", e->gx, ST_F32, s, M, d);
         // ---- self-attention: att = SDPA(q, k, v);  qkv = a1 Wqkv^T;  a1 = LN1(x1)
         int attn_path = 0;
@@ -652,10 +614,10 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
         if (attn_path & 4) PATH(PB_ATT_MASKED);
         SNAP(sn + "dqkv", e->dsmall, ST_BF16, s, M, 3 * d);
         // (dO as a bf16 copy from the LayerNorm-2 backward: 192 -> 189 us, but delta = dO . O from rounded dO moves the worst g15 gradient from 1.86e-2 to 1.92e-2 of a 2e-2 bound: not taken)
-        GEMM_TRY("training step", weight_grad(e->dsmall, 3 * d, b.a1, d, Gd + p.qkv));
+        GEMM_TRY("training step", weight_grad(plan.wg[WGP_QKV], e->dsmall, 3 * d, b.a1, d, Gd + p.qkv));
         GEMM_TRY("training step", gemm_bf16(e->dsmall, 3 * d, b.wqkv_t, 3 * d, e->zero_bias, e->dsmall2, M, d, 3 * d, s));         // da1 = dqkv Wqkv
         SNAP(sn + "da1", e->dsmall2, ST_BF16, s, M, d);
-        ln_bwd_rows(e->dsmall2, b.x1, b.st1, P + p.n1w, e->gx, 1, Gd + p.n1w, Gd + p.n1b, M, d, i > 0 ? e->gxb : nullptr);
+        ln_bwd_rows(e->dsmall2, b.x1, b.st1, P + p.n1w, e->gx, 1, Gd + p.n1w, Gd + p.n1b, M, i > 0 ? e->gxb : nullptr);
         SNAP(sn + "gx.ln1", e->gx, ST_F32, s, M, d);
         if (i > 0) SNAP(sn + "gxb.ln1", e->gxb, ST_BF16, s, M, d);
         // every gradient of this block is enqueued (its 15 tensors are one contiguous range of the flat vector): the data-parallel
@@ -664,27 +626,27 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
     }
     // dL/dy = sum over blocks of dkv_i Wkv_i: one batched launch into per-block parts, then a fixed-order sum
     hipLaunchKernelGGL(tiled_f32_kernel, dim3((d + 31) / 32, (2 * B + 31) / 32, e->L), dim3(256), 0, s, e->dkv_all, (long)(2 * d), 1L, P + e->lp[0].kv, 1L, (long)d,
-                       (const float*)nullptr, e->dy_parts, d, 2 * B, d, 2 * d, (float*)nullptr, 0, 0, kv_stride, blk_stride, (long)e->B * 2 * d);
-    hipLaunchKernelGGL(reduce_partials, dim3((2 * B * d + 15) / 16), dim3(1024), 0, s, e->dy_parts, e->L, (size_t)e->B * 2 * d, e->dy, 2 * B * d, 0);
+                       (const float*)nullptr, e->dy_parts, d, 2 * B, d, 2 * d, (float*)nullptr, 0, 0, kv_stride, blk_stride, (long)e->max_batch * 2 * d);
+    hipLaunchKernelGGL(reduce_partials, dim3((2 * B * d + 15) / 16), dim3(1024), 0, s, e->dy_parts, e->L, (size_t)e->max_batch * 2 * d, e->dy, 2 * B * d, 0);
     // ---- patch embedding: x0 = LN2(e) + pos;  e = pn Wlin^T + b;  pn = LN1(p);  p = conv(x)     (tld/denoiser.py:34-45,75-77)
     SNAP("dy", e->dy, ST_F32, s, 2 * B, d);
     hipLaunchKernelGGL(pos_grad_kernel, g1((size_t)N * d), blk, 0, s, e->gx, Gd + e->pos, B, N, d);
-    ln_bwd_rows(e->gx, e->e, e->est2, P + e->l2w, e->de, 0, Gd + e->l2w, Gd + e->l2b, M, d);
+    ln_bwd_rows(e->gx, e->e, e->est2, P + e->l2w, e->de, 0, Gd + e->l2w, Gd + e->l2b, M);
     SNAP("de", e->de, ST_F32, s, M, d);
-    colsum(e->de, M, d, Gd + e->lib);
+    colsum(plan.colsum[CS_D], e->de, Gd + e->lib);
     lin_dx(e->de, d, P + e->liw, e->dpn, pd, M, d, pd, 0);               // dpn = de Wlin
     SNAP("dpn", e->dpn, ST_F32, s, M, pd);
-    tall_dw(e->p16n, pd, (const float*)e->de, d, e->scr);                                                                              // dWlin^T [pd, d]
+    tall_dw(plan.tall[TALL_LIN], e->p16n, (const float*)e->de, e->scr);                                                                              // dWlin^T [pd, d]
     hipLaunchKernelGGL(transpose_f32_small, g1((size_t)pd * d), blk, 0, s, e->scr, Gd + e->liw, pd, d);
     hipLaunchKernelGGL(ln_small_bwd_kernel, dim3(nchunk), blk, 0, s, e->dpn, e->p16, e->est1, P + e->l1w, e->dp16, e->part, M, pd);
     SNAP("dp16", e->dp16, ST_F32, s, M, pd);
     reduce(nchunk, 2 * (size_t)pd, 0, Gd + e->l1w, pd, 0);
     reduce(nchunk, 2 * (size_t)pd, pd, Gd + e->l1b, pd, 0);
     hipLaunchKernelGGL(patches_kernel, g1((size_t)M * pd), blk, 0, s, x_noisy, e->patches, B, e->C, e->S, e->cfg.patch_size, G);
-    tall_dw(e->dp16, pd, (const float*)e->patches, pd, Gd + e->cvw);
-    colsum(e->dp16, M, pd, Gd + e->cvb);
+    tall_dw(plan.tall[TALL_CONV], e->dp16, (const float*)e->patches, Gd + e->cvw);
+    colsum(plan.colsum[CS_PD], e->dp16, Gd + e->cvb);
     // ---- conditioning: y = LN(stack[nz, lb]);  nz = W3 GELU(W1 sin + b1) + b3;  lb = label_proj(label)     (tld/denoiser.py:105-122)
-    ln_bwd_rows(e->dy, e->ycat, e->yst, P + e->nw, e->dycat, 0, Gd + e->nw, Gd + e->nb, 2 * B, d);
+    ln_bwd_rows(e->dy, e->ycat, e->yst, P + e->nw, e->dycat, 0, Gd + e->nw, Gd + e->nb, 2 * B);
     SNAP("dycat", e->dycat, ST_F32, s, 2 * B, d);
     lin_dw(e->dycat + d, 2 * d, label, e->text, Gd + e->lbw, Gd + e->lbb, B, d, e->text);
     lin_dw(e->dycat, 2 * d, e->g1v, d, Gd + e->ff3w, Gd + e->ff3b, B, d, d);
@@ -705,7 +667,7 @@ int tld_train_forward_backward_cb(tld_train* e, const float* x_noisy, const floa
 int tld_train_forward_loss(tld_train* e, const float* weights, const float* x_noisy, const float* noise_level, const float* label, const float* target,
                            int32_t batch, float* loss_out, double* sample_loss_out, float* pred_out, void* hip_stream) {
     if (!e || !x_noisy || !noise_level || !label || !target || !loss_out) return fail(TLD_ERR_INVALID, "forward loss: null argument");
-    if (batch <= 0 || batch > e->B) return fail(TLD_ERR_INVALID, "forward loss: batch %d outside [1, max_batch = %d]", batch, e->B);
+    if (batch <= 0 || batch > e->max_batch) return fail(TLD_ERR_INVALID, "forward loss: batch %d outside [1, max_batch = %d]", batch, e->max_batch);
     if (sample_loss_out && ((uintptr_t)sample_loss_out & 7)) return fail(TLD_ERR_INVALID, "forward loss: sample_loss_out must be 8-byte aligned");
     if (!e->params) return fail(TLD_ERR_STATE, "tld_train_bind first");
     if (e->debug) return fail(TLD_ERR_STATE, "forward loss: the stage hook is on (tld_train_set_debug): a debug call poisons the gradient vector, which this entry never writes");
@@ -950,10 +912,10 @@ int tld_debug_attention_bwd(const void* qk, const void* vt, const void* o, const
 int tld_debug_wgrad(const void* dy, const void* x, float* dw, float* slices, int64_t slice_floats, int32_t rows, int32_t n_out, int32_t k_in, void* hip_stream) {
     if (!dy || !x || !dw || !slices || rows <= 0) return fail(TLD_ERR_INVALID, "bad argument");
     if (const std::string bad = wgrad_hook_refusal(rows, n_out, k_in); !bad.empty()) return fail(TLD_ERR_INVALID, "%s", bad.c_str());
+    if (!wgrad_untransposed_takes(rows, n_out, k_in)) return fail(TLD_ERR_SHAPE, "n_out and k_in must be multiples of 256, rows a multiple of 64");
     PtrDeviceGuard guard(dy);
-    if (!wgrad_tn(reinterpret_cast<const bf16*>(dy), n_out, reinterpret_cast<const bf16*>(x), k_in, rows, dw, slices, (size_t)slice_floats,
-                  reinterpret_cast<hipStream_t>(hip_stream)))
-        return fail(TLD_ERR_SHAPE, "n_out and k_in must be multiples of 256, rows a multiple of 64");
+    wgrad_tn(reinterpret_cast<const bf16*>(dy), n_out, reinterpret_cast<const bf16*>(x), k_in, rows,
+             wgrad_split(rows, n_out, k_in, device_cu_count(), kWgradUntransposed, (size_t)slice_floats, 0), dw, slices, reinterpret_cast<hipStream_t>(hip_stream));
     HIP_TRY(hipGetLastError());
     return TLD_OK;
 }

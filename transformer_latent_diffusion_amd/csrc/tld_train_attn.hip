@@ -25,6 +25,7 @@
 // 256 keep the unmasked kernels at BT = N (<= 256) or 256.
 // Outputs are row-major bf16 [M, 3 d] (dq | dk | dv), the layout the weight- and input-gradient GEMMs consume.
 #include "tld_common.h"
+#include "tld_train_plan.h"      // attn_bwd_dispatch, attn_bwd_block_waves: which instantiation a token count takes
 
 // attribution builds (tools/attn_bwd_bench.py): -DTLD_AB_DBG=<bits>: 1 no staging loads, 2 no pass 1, 4 no pass 2, 8 no output stores
 #ifndef TLD_AB_DBG
@@ -95,22 +96,6 @@ __device__ __forceinline__ void store_tile(bf16* dst /* row of token l31, first 
             for (int e = 0; e < 4; ++e) v[e] = (bf16)(t[dh][rq * 4 + e] * scale);
             *reinterpret_cast<bf16x4*>(dst + dh * 32 + 8 * rq + 4 * hi) = v;
         }
-}
-
-// Waves per workgroup (block width BT = 32 nw tokens) of the attention backward at N tokens (N a multiple of 16).  N <= 256: one block
-// holds the sample, nw = ceil(N / 32) (64 / 128 / 256 tokens: 2 / 4 / 8, exact).  N > 256: the nw in 4 .. 8 with the least padded length
-// ceil(N / BT) BT, the wider on a tie (a multiple of 256: 8); 7 only where it leaves no padding -- the masked 7-wave dQ kernel spills.
-// Padded work (Np / N)^2 at the square grids: 16 tokens 4.0 (one 32-token tile), 144: 1.23, 400: 1.44, 784: 1.04, 1296: 1.08,
-// 1936: 1.12, 2704: 1.01, 3600: 1.03; 576, 1600, 3136 and the multiples of 256 none.
-int attn_bwd_block_waves(int ntok) {
-    if (ntok <= 256) return (ntok + 31) / 32;
-    int best = 8, pad = 1 << 30;
-    for (int nw = 8; nw >= 4; --nw) {
-        const int bt = 32 * nw, np = (ntok + bt - 1) / bt * bt;
-        if (nw == 7 && np != ntok) continue;
-        if (np < pad) { pad = np; best = nw; }
-    }
-    return best;
 }
 
 // TG: dL/dO as fp32 (the test hook) or bf16 (the training step: the LayerNorm-2 backward leaves a bf16 copy of the residual gradient).
@@ -388,46 +373,40 @@ void launch_one(const bf16* qk, const bf16* vt, const bf16* o, const TG* g, bf16
                        stats, heads, ntok);
 }
 
-// a block width chosen at run time: the masked kernel when N is not a multiple of BT = 32 nw
+// the instantiation the dispatch chose: returns 4 from the branch that launches a masked kernel, else 0
 template <int MODE, typename TG>
-int launch_nw(int nw, const bf16* qk, const bf16* vt, const bf16* o, const TG* g, bf16* dqkv, float* stats, int batch, int ntok, int heads, hipStream_t s) {
-    const bool masked = ntok % (32 * nw) != 0;
+int launch_nw(const AttnBwdDispatch& a, const bf16* qk, const bf16* vt, const bf16* o, const TG* g, bf16* dqkv, float* stats, int batch, int ntok, int heads, hipStream_t s) {
+    int path = 0;
 #define TLD_ATTN_BWD_NW(W) \
     case W: \
-        if (masked) launch_one<W, MODE, TG, true>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s); \
+        if (a.masked) { path = 4; launch_one<W, MODE, TG, true>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s); } \
         else launch_one<W, MODE, TG, false>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s); \
         break;
     if constexpr (MODE == ATTN_FUSED) {
-        switch (nw) { TLD_ATTN_BWD_NW(1) TLD_ATTN_BWD_NW(2) TLD_ATTN_BWD_NW(3) TLD_ATTN_BWD_NW(4) TLD_ATTN_BWD_NW(5) TLD_ATTN_BWD_NW(6) TLD_ATTN_BWD_NW(7)
-                      TLD_ATTN_BWD_NW(8) }
+        switch (a.waves) { TLD_ATTN_BWD_NW(1) TLD_ATTN_BWD_NW(2) TLD_ATTN_BWD_NW(3) TLD_ATTN_BWD_NW(4) TLD_ATTN_BWD_NW(5) TLD_ATTN_BWD_NW(6) TLD_ATTN_BWD_NW(7)
+                           TLD_ATTN_BWD_NW(8) }
     } else {
-        switch (nw) {
+        switch (a.waves) {
             TLD_ATTN_BWD_NW(4) TLD_ATTN_BWD_NW(5) TLD_ATTN_BWD_NW(6) TLD_ATTN_BWD_NW(8)
-            case 7: launch_one<7, MODE, TG, false>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s); break;      // (exact only: see attn_bwd_block_waves)
+            case 7: launch_one<7, MODE, TG, false>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s); break;      // (exact only: attn_bwd_block_waves picks 7 only where nothing is masked)
         }
     }
 #undef TLD_ATTN_BWD_NW
-    return masked ? 4 : 0;      // (MODE != ATTN_FUSED at 7 waves is exact only: attn_bwd_block_waves picks 7 only where masked is false)
+    return path;
 }
 
 template <typename TG>
 int launch_bwd(const bf16* qk, const bf16* vt, const bf16* o, const TG* g, bf16* dqkv, float* stats, int batch, int ntok, int heads, hipStream_t s, int* path_out) {
+    const AttnBwdDispatch a = attn_bwd_dispatch(ntok, stats != nullptr);      // (64, 128 and 256 tokens: 2, 4 and 8 waves, exact -- the kernels of the first training engine)
     int path = 0;      // for the stage hook of tld_train.hip: 1 one kernel, 2 two kernels, | 4 masked -- set in the branch that launches
-    // the token counts of the first training engine keep their kernels (unmasked, same block widths)
-    if (ntok == 256) { path = 1; launch_one<8, ATTN_FUSED, TG, false>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s); }
-    else if (ntok == 128) { path = 1; launch_one<4, ATTN_FUSED, TG, false>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s); }
-    else if (ntok == 64) { path = 1; launch_one<2, ATTN_FUSED, TG, false>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s); }
-    else if (ntok > 256 && ntok % 256 == 0 && stats) {
-        path = 2;
-        launch_one<8, ATTN_DQ, TG, false>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
-        launch_one<8, ATTN_DKV, TG, false>(qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
-    } else if (ntok % 16 || ntok <= 0) return 1;
-    else if (ntok < 256) path = 1 | launch_nw<ATTN_FUSED>(attn_bwd_block_waves(ntok), qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
-    else if (stats) {
-        const int nw = attn_bwd_block_waves(ntok);
-        path = 2 | launch_nw<ATTN_DQ>(nw, qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
-        launch_nw<ATTN_DKV>(nw, qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
-    } else return 1;
+    switch (a.mode) {
+    case ATTN_BWD_ONE: path = 1 | launch_nw<ATTN_FUSED>(a, qk, vt, o, g, dqkv, stats, batch, ntok, heads, s); break;
+    case ATTN_BWD_TWO:
+        path = 2 | launch_nw<ATTN_DQ>(a, qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
+        launch_nw<ATTN_DKV>(a, qk, vt, o, g, dqkv, stats, batch, ntok, heads, s);
+        break;
+    default: return 1;
+    }
     if (path_out) *path_out = path;
     return 0;
 }

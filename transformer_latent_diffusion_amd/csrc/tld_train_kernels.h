@@ -742,8 +742,6 @@ __global__ __launch_bounds__(256) void cross_bwd_kernel(const float* __restrict_
 // LDS with 16-byte copies (the whole 16 x 16 image, 32 KB, at the training shape; 18 rows of 32 / 64 tokens at the fine-tuning
 // sizes), then a thread (channel quad, image row) slides a rotating 3 x 3 fp32 register window along the row (the inference path's
 // dwconv_gelu_kernel recipe): every input value is read from HBM once (halo rows twice).
-inline int dwconv_band_rows(int G) { return G < 16 ? G : 16; }
-inline size_t dwconv_lds_bytes(int G) { const int R = dwconv_band_rows(G); return (size_t)(R + 2 < G ? R + 2 : G) * G * 128; }
 __global__ __launch_bounds__(256) void dwconv_kernel(const bf16* __restrict__ in, const float* __restrict__ w, const float* __restrict__ bias, bf16* __restrict__ out,
                                                      bf16* __restrict__ gelu_out, int B, int G, int C, int flip, int R) {
     extern __shared__ __attribute__((aligned(16))) char smem_[];   // [rows ylo .. yhi][G tokens][64 ch] bf16
