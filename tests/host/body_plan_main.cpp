@@ -10,7 +10,9 @@
 // The driver goes through the calls as the engine does -- a refused setter changes nothing -- and prints one JSON object per line: the refusal of create; if there
 // is none the refusal of every op ("" where it passed), the shape, the switches after the ops, every field of the plan, every row of the image table
 // [member, stage name, dtype, numel, margin, held], every reserved stage [name, bytes], and every GEMM launch of a forward of max_batch samples against
-// launch_gemm's own reach check [name, fits with bf16 operands, fits with fp8 operands].
+// launch_gemm's own reach check [name, fits with bf16 operands, fits with fp8 operands]; and "launch", what the plan meets in csrc/tld_launch_plan.h: the form of the
+// quantising LayerNorm where ln_mx8 is set, whether cross_row has the outputs fold_ln3 / cross_mx8 ask for, the form of the split-K finish where ll_split is set (-1
+// each where the plan does not ask), and the launch-path bits of the row and attention launches of a forward of max_batch samples, plain and with a shared layer 0.
 #include "tld_body_plan.h"
 
 #include <fstream>
@@ -24,6 +26,23 @@ static std::string quoted(const std::string& s) {
     std::string o = "\"";
     for (char ch : s) { if (ch == '"' || ch == '\\') o += '\\'; o += ch; }
     return o + "\"";
+}
+
+// The row and attention launches run_body (csrc/tld_engine.hip) makes under a plan, each site's `paths` or-ed together.  shared: the CFG-doubled batch with layer-0
+// sharing -- embed, LayerNorm-1 and attention of block 0 on half the samples, block 0's cross_row fanning out.  (The split-bf16 images outside the blocks are always held.)
+static uint64_t forward_paths(const BodyShape& s, const BodyPlan& P, int batch, bool shared) {
+    const int b0 = shared ? batch / 2 : batch;
+    uint64_t m = plan_embed(b0, s.ntok, s.pd, s.pd, s.d, true).paths;
+    for (int l = 0; l < s.L; ++l) {
+        const bool half = shared && l == 0;
+        const int bl = half ? b0 : batch;
+        if (!P.fold_ln1) m |= plan_layernorm(bl * s.ntok, s.d, P.ln_mx8).paths;
+        if (!P.fused_qa) m |= plan_attention(bl, s.ntok, s.H).paths;
+        m |= plan_cross_row(batch, s.ntok, s.d, s.H, half, P.cross_mx8, P.cus).paths;
+        if (!P.fuse_dw) m |= plan_dwconv(batch, s.grid, s.hid, P.dw_mx8).paths;
+        if (P.ll_split && !(l + 1 == s.L && P.fold_tail)) m |= plan_splitk_finish(batch * s.ntok, s.d).paths;
+    }
+    return m | plan_tail(batch, s.ntok, s.pd, s.d, P.fold_tail, true, P.cus).paths;
 }
 
 int main(int argc, char** argv) {
@@ -105,7 +124,10 @@ int main(int argc, char** argv) {
         const int ng = body_gemms(c, s.grid, c.max_batch, false, gb);
         body_gemms(c, s.grid, c.max_batch, true, g8);
         for (k = 0; k < ng; ++k) std::printf("%s[%s, %d, %d]", k ? ", " : "", quoted(gb[k].name).c_str(), (int)body_gemm_fits(gb[k]), (int)body_gemm_fits(g8[k]));
-        std::printf("]}\n");
+        std::printf("], \"launch\": [%d, %d, %d, %llu, %llu]}\n", p.ln_mx8 ? (int)plan_layernorm(c.max_batch * s.ntok, s.d, true).form : -1,
+                    p.fold_ln3 || p.cross_mx8 ? (int)plan_cross_row(c.max_batch, s.ntok, s.d, s.H, false, p.cross_mx8, cus).mode_outputs : -1,
+                    p.ll_split ? (int)plan_splitk_finish(c.max_batch * s.ntok, s.d).form : -1, (unsigned long long)forward_paths(s, p, c.max_batch, false),
+                    (unsigned long long)forward_paths(s, p, c.max_batch, true));
     }
     return 0;
 }

@@ -4,14 +4,16 @@ the pixel / query-row class masks of that file, and the input families whose bit
 tld_engine_create accepts any square token grid whose side G is a multiple of 4; what a forward launches at a grid follows from a handful of rules:
 
 | dispatch                          | depends on              | restated as          | source                                         |
-| attention form, N % 128           | token count             | attention_class      | launch_attention, launch_masked (tld_attn.hip) |
-| depthwise form, G % 16 / G % 3 /  | G                       | depthwise_class      | launch_dwconv_gelu (tld_rows.hip)              |
+| attention form, N % 128           | token count             | attention_class      | plan_attention (tld_launch_plan.h)             |
+| depthwise form, G % 16 / G % 3 /  | G                       | depthwise_class      | plan_dwconv (tld_launch_plan.h)                |
 |   strip count                     |                         |                      |                                                |
-| cross_row form and gpw            | d, ntok, batch, CUs     | cross_row_form       | launch_cross_row (tld_rows.hip)                |
+| cross_row form and gpw            | d, ntok, batch, CUs     | cross_row_form       | plan_cross_row (tld_launch_plan.h)             |
+| embed, LayerNorm-1, tail forms    | d, patch, operand type  | expected_paths       | plan_embed, plan_layernorm, plan_tail          |
 | fused up-projection               | G, hid (bf16 only)      | fused_up             | plan (tld_body_plan.h)                         |
 | fused QKV + attention             | ntok, d, LayerNorm-1    | fused_qkv_attention  | plan (tld_body_plan.h)                         |
 |                                   | fold                    |                      |                                                |
 
+The first three are restated in tests/launch_plan_ref.py, which tests/test_launch_plan_host.py holds against the compiled header field by field.
 expected_paths turns them into the bits of tld_engine_debug_paths a forward must and must not set; the GPU file asserts them case by case, so a grid
 that silently takes another kernel fails there.  The tests here hold: the two plan rules against tests/body_plan_ref.py; that the case tables reach
 every value of every class (whole-image depthwise with G % 3 = 0, 1, 2; tiled with G % 16 = 0, 4, 8, 12; streaming with 1, 2, 3 strips; attention at
@@ -28,6 +30,7 @@ import torch
 import body_plan_ref as BP
 import infer_stage_refs as F
 import train_stage_refs as R
+from launch_plan_ref import attention_class, cross_row_form, depthwise_class
 
 CUS_MI355X = 256
 
@@ -35,46 +38,17 @@ CUS_MI355X = 256
 BIT_QKV_ATTN, BIT_ATT_256, BIT_ATT_CHUNKED, BIT_ATT_64, BIT_ATT_MASKED = 11, 14, 15, 17, 19
 BIT_CROSS_MFMA1, BIT_GPW1, BIT_GPWN, BIT_CROSS_VALU, BIT_FANOUT = 20, 24, 25, 26, 27
 BIT_UP_16, BIT_UP_32, BIT_UP_16_4W, BIT_UP_ALONE, BIT_DW_WHOLE, BIT_DW_TILED, BIT_DW_STREAM = 28, 29, 30, 31, 32, 33, 34
-BIT_F8_PASS, BIT_F8_DW_TILED, BIT_F8_DW_STREAM = 54, 56, 57
+BIT_F8_PASS, BIT_F8_CROSS, BIT_F8_DW_TILED, BIT_F8_DW_STREAM = 54, 55, 56, 57
+BIT_EMBED_PLAIN, BIT_EMBED_MFMA1, BIT_LN_Q4_1, BIT_LN_GENERIC, BIT_LN_MX8, BIT_TAIL_FOLD, BIT_TAIL_MFMA1, BIT_TAIL_PLAIN = 0, 1, 5, 9, 10, 16, 45, 49
+BIT_SPLITK_FINISH12, BIT_SPLITK_FINISH6 = 43, 44
+EMBED_BITS = {BIT_EMBED_PLAIN} | {BIT_EMBED_MFMA1 + k for k in range(4)}
+LN_BITS = {BIT_LN_GENERIC, BIT_LN_MX8} | {BIT_LN_Q4_1 + k for k in range(4)}
+TAIL_BITS = {BIT_TAIL_PLAIN, BIT_TAIL_FOLD} | {BIT_TAIL_MFMA1 + k for k in range(4)}
 ATT_BITS = {"256": BIT_ATT_256, "chunked": BIT_ATT_CHUNKED, "64": BIT_ATT_64, "masked": BIT_ATT_MASKED}
 DW_BITS = {"whole": BIT_DW_WHOLE, "tiled": BIT_DW_TILED, "streaming": BIT_DW_STREAM}
 
 
-# ---- the dispatch, restated ----------------------------------------------------------------------------------------------------------------------
-def attention_class(n):
-    """launch_attention: (form, N % 128, single partial chunk) -- the last two for the masked kernel (attn_kernel<4, 4, true>: 128-key chunks,
-    128-query blocks, one K / V buffer when there is one chunk), else (form, 0, False).  128 and 32 tokens are no square grid's count."""
-    if n == 256:
-        return "256", 0, False
-    if n % 256 == 0:
-        return "chunked", 0, False
-    if n == 64:
-        return "64", 0, False
-    assert n not in (128, 32) and n % 16 == 0, n
-    return "masked", n % 128, n <= 128
-
-
-def depthwise_class(G):
-    """launch_dwconv_gelu: (form, what the form's loop ends on) -- whole image: G % 3 (the three-buffer column rotation); tiled: G % 16 (the width
-    of the partial last tile, 0: none); streaming: the number of 32-column strips."""
-    if G > 16 and G % 32 == 0:
-        return "streaming", G // 32
-    if G > 16:
-        return "tiled", G % 16
-    return "whole", G % 3
-
-
-def cross_row_form(d, ntok, batch, cus):
-    """launch_cross_row: ("mfma", gpw) -- groups of 16 rows per workgroup: the largest power of two (<= 16) that divides a sample's groups and
-    leaves a workgroup per CU -- or ("valu", 1)."""
-    if d % 256 or d > 1024 or ntok % 16:
-        return "valu", 1
-    gps, gpw = ntok // 16, 1
-    while gpw < 16 and gps % (gpw * 2) == 0 and batch * (gps // (gpw * 2)) >= cus:
-        gpw *= 2
-    return "mfma", gpw
-
-
+# ---- the dispatch, restated: the three launch classes are in tests/launch_plan_ref.py, held against csrc/tld_launch_plan.h by tests/test_launch_plan_host.py ----
 def fold_ln1(d, fp8=False):
     return not fp8 and d % 192 == 0 and d // 96 <= 8 and (3 * d) % 256 == 0
 
@@ -88,8 +62,9 @@ def fused_qkv_attention(ntok, d, fp8=False):
     return fold_ln1(d, fp8) and ntok == 256 and d % 128 == 0
 
 
-def expected_paths(d, G, batch, cus, mult=4, fp8=False, fp8_fused=True, sampler=False):
-    """(bits a forward of `batch` samples must set, bits it must not set).  batch: the samples cross_row sees (both halves of a CFG step)."""
+def expected_paths(d, G, batch, cus, mult=4, fp8=False, fp8_fused=True, sampler=False, pd=16):
+    """(bits a forward of `batch` samples must set, bits it must not set).  batch: the samples cross_row sees (both halves of a CFG step).  pd: the patch's
+    elements (every case here: 4 channels, 2 x 2 pixels)."""
     n, hid = G * G, d * mult
     on, off = set(), set()
     form = attention_class(n)[0]
@@ -112,9 +87,24 @@ def expected_paths(d, G, batch, cus, mult=4, fp8=False, fp8_fused=True, sampler=
         on.add(BIT_CROSS_VALU); off |= {BIT_CROSS_MFMA1 + k for k in range(4)} | {BIT_GPW1, BIT_GPWN}
     (on if sampler else off).add(BIT_FANOUT)
     f8 = {BIT_F8_DW_TILED: fp8 and fp8_fused and dw == "tiled", BIT_F8_DW_STREAM: fp8 and fp8_fused and dw == "streaming",
+          BIT_F8_CROSS: fp8 and fp8_fused and d in (256, 512, 768),
           BIT_F8_PASS: fp8 and (not fp8_fused or dw == "whole" or d not in (256, 512, 768))}
     for b, v in f8.items():
         (on if v else off).add(b)
+    # embed: the matrix-pipe kernel at a 16-element patch and d = 256 k (the engine always holds its split-bf16 weight), else the plain one
+    embed = BIT_EMBED_MFMA1 + d // 256 - 1 if pd == 16 and d % 256 == 0 and d <= 1024 else BIT_EMBED_PLAIN
+    on.add(embed); off |= EMBED_BITS - {embed}
+    # LayerNorm-1: no kernel of its own where it is folded into the QKV GEMM; the quantising one in the fused fp8 mode at 256, 512, 768; four features per lane at 256 k
+    if fold_ln1(d, fp8):
+        off |= LN_BITS
+    else:
+        ln = BIT_LN_MX8 if fp8 and fp8_fused and d in (256, 512, 768) else BIT_LN_Q4_1 + d // 256 - 1 if d in (256, 512, 768, 1024) else BIT_LN_GENERIC
+        on.add(ln); off |= LN_BITS - {ln}
+    # the tail: bf16 operands fold the last down projection into it (any width); fp8 takes the matrix-pipe kernel where its weight image fits, else the plain one
+    nt = BIT_TAIL_MFMA1 + (pd + 15) // 16 - 1
+    tail = {nt, BIT_TAIL_FOLD} if not fp8 else {nt} if d % 128 == 0 and pd * d <= 40960 else {BIT_TAIL_PLAIN}
+    on |= tail; off |= TAIL_BITS - tail
+    off |= {BIT_SPLITK_FINISH12, BIT_SPLITK_FINISH6}                  # (no case here runs a low-latency class)
     return on, off
 
 

@@ -10,6 +10,10 @@ Then the stage hooks ON: one forward of the tiny denoiser, one encode of the tin
 every stage its header block names as a part ("absent <name>" where the engine's path has no such stage).
 Then three more training steps with the hook off (loss and gradient vector): d 256, image 64, one block, batch 5 with the untransposed and, under TLD_TRAIN_TN_WGRAD=0, the
 transposing weight-gradient split; d 192, image 24, two blocks, batch 3: the zero-padded form.
+Then five forwards with the hook off, the smallest shapes that reach the row and attention launch forms (csrc/tld_launch_plan.h) the cases above do not: d 192 at 12 x 12
+tokens (plain embed, generic LayerNorm, masked attention, the VALU cross_row, whole-image depthwise); d 256 at 20 x 20 (four-features-per-lane LayerNorm, the tiled depthwise);
+d 256 at 32 x 32 under TLD_FUSE_DWCONV=0 (chunked attention, streaming depthwise); the same 20 x 20 model with fp8 operands (quantising LayerNorm, cross_row and depthwise, the
+unfolded matrix-pipe tail); d 384 at 8 x 8 in low-latency class 1 (one-chunk attention at 64 tokens, the split-K finish).
     TLD_LIB=<lib.so> python tools/lib_ab_check.py out.npy"""
 import hashlib, os, sys
 from dataclasses import asdict
@@ -170,6 +174,27 @@ def train_part(name, d, image, blocks, batch, tn_off=False):
 train_part("train d256 g32 untransposed split", 256, 64, 1, 5)
 train_part("train d256 g32 transposing split", 256, 64, 1, 5, tn_off=True)
 train_part("train d192 g12 zero-padded", 192, 24, 2, 3)
+# forwards of the launch forms not reached above (csrc/tld_launch_plan.h), stage hook off
+def forward_part(name, d, image, batch, env=None, setup=None):
+    c = DenoiserConfig(image_size=image, noise_embed_dims=256, patch_size=2, embed_dim=d, dropout=0, n_layers=2, text_emb_size=768, n_channels=4, mlp_multiplier=4)
+    old = {k: os.environ.get(k) for k in (env or {})}
+    os.environ.update(env or {})
+    try:
+        fm = Denoiser(**asdict(c)).to(dev)
+        fm.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in synth_state_dict(c, 41).items()})
+        if setup:
+            setup(fm)
+        gg = torch.Generator().manual_seed(43 + d + image)
+        xs, sg, lb = torch.randn(batch, 4, image, image, generator=gg), torch.rand(batch, 1, generator=gg) * 0.9 + 0.05, torch.randn(batch, 768, generator=gg) * 0.5
+        parts[name] = fm(xs.to(dev), sg.to(dev), lb.to(dev)).float().cpu().numpy()      # (the switches are read when the engine is created: at this first forward)
+    finally:
+        for k, v in old.items():
+            os.environ.pop(k) if v is None else os.environ.__setitem__(k, v)
+forward_part("forward d192 g12", 192, 24, 3)
+forward_part("forward d256 g20", 256, 40, 3)
+forward_part("forward d256 g32 unfused depthwise", 256, 64, 3, env={"TLD_FUSE_DWCONV": "0"})
+forward_part("forward d256 g20 fp8", 256, 40, 3, setup=lambda fm: fm.set_gemm_dtype("fp8"))
+forward_part("forward d384 g8 low latency", 384, 16, 2, setup=lambda fm: fm.set_low_latency(1))
 for name, v in parts.items():
     assert name in staged or np.isfinite(v).all(), name
     print("part", name, tuple(v.shape), hashlib.sha1(np.ascontiguousarray(v).tobytes()).hexdigest())

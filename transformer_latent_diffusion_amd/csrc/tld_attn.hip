@@ -38,9 +38,7 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 #ifndef TLD_ATTN_DBG
 #define TLD_ATTN_DBG 0
 #endif
-#ifndef TLD_ATTN_ST16
-#define TLD_ATTN_ST16 2       // 256-token kernel's output stores: 2 = whole 128-byte rows via an LDS transpose, 1 = 16-byte stores after a lane-pair exchange, 0 = 8-byte stores
-#endif
+// (TLD_ATTN_ST16, the 256-token kernel's output stores: tld_launch_plan.h, where the kernel's LDS bytes depend on it)
 
 constexpr float kScaleLog2e = 0.125f * 1.44269504088896340736f;   // (1/sqrt(64)) * log2(e)
 
@@ -793,63 +791,35 @@ __global__ __launch_bounds__(256, 2) void attn2_kernel(const bf16* __restrict__ 
 #endif
 }
 
-template <int KT, int NW, int QT, bool PIPE>
-void launch_attn1(const bf16* qk, const bf16* vt, bf16* att, int batch, int ntok, int heads, hipStream_t s) {
-    constexpr int KC = KT * 32;
-    const int lds = KC * 128 + 64 * (KC * 2 + 8) + (TLD_ATTN_ST16 == 2 ? NW * 16 * 144 : 0);
-    static PerDeviceOnce attr_set;
-    attr_set.run([&] { hipFuncSetAttribute(reinterpret_cast<const void*>(attn1_kernel<KT, NW, QT, PIPE>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds); });
-    hipLaunchKernelGGL((attn1_kernel<KT, NW, QT, PIPE>), dim3(1, heads, batch), dim3(NW * 64), lds, s, qk, vt, att, ntok,
-                       heads * 64);
+// the launch plan_attention (tld_launch_plan.h) made, with the opt-in to its dynamic LDS
+template <class K, class... Args>
+void launch_planned(K kernel, PerDeviceMax& optin, const AttentionPlan& a, hipStream_t s, Args... args) {
+    optin.run(a.lds, [&] { hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, a.lds); });
+    hipLaunchKernelGGL(kernel, dim3(a.gx, a.gy, a.gz), dim3(a.block), a.lds, s, args...);
 }
-
-template <int KT, int NW>
-void launch_kt(const bf16* qk, const bf16* vt, bf16* att, int batch, int ntok, int heads, hipStream_t s) {
-    constexpr int KC = KT * 32;
-    const int nbuf = (ntok > KC && 2 * (KC * 128 + 64 * (KC * 2 + 8)) <= 160 * 1024) ? 2 : 1;       // (the engine's shapes are all single-chunk here: ntok == KC)
-    const int lds = nbuf * (KC * 128 + 64 * (KC * 2 + 8));
-    static PerDeviceMax attr_lds;
-    attr_lds.run(lds, [&] { hipFuncSetAttribute(reinterpret_cast<const void*>(attn_kernel<KT, NW>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, lds); });
-    dim3 grid(ntok / (NW * 32), heads, batch), block(NW * 64);
-    hipLaunchKernelGGL((attn_kernel<KT, NW>), grid, block, lds, s, qk, vt, att, ntok, heads * 64, nbuf);
-}
-
-// any token count (multiple of 8): 128-key chunks, 4-wave workgroups of 128 queries, partial last chunk / block masked
-void launch_masked(const bf16* qk, const bf16* vt, bf16* att, int batch, int ntok, int heads, hipStream_t s) {
-    constexpr int KT = 4, NW = 4, KC = KT * 32;
-    const int nbuf = ntok > KC ? 2 : 1;
-    const int lds = nbuf * (KC * 128 + 64 * (KC * 2 + 8));
-    static PerDeviceMax attr_lds;
-    attr_lds.run(lds, [&] { hipFuncSetAttribute(reinterpret_cast<const void*>(attn_kernel<KT, NW, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds); });
-    dim3 grid((ntok + NW * 32 - 1) / (NW * 32), heads, batch), block(NW * 64);
-    hipLaunchKernelGGL((attn_kernel<KT, NW, true>), grid, block, lds, s, qk, vt, att, ntok, heads * 64, nbuf);
-}
-
-void launch_attn2(const bf16* qk, const bf16* vt, bf16* att, int batch, int ntok, int heads, hipStream_t s) {
-    constexpr int lds = 2 * 128 * 128 + 2 * 64 * 256 + 4 * 16 * 144;
-    static PerDeviceOnce attr_set;
-    attr_set.run([&] { hipFuncSetAttribute(reinterpret_cast<const void*>(attn2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds); });
-    const int npairs = batch * heads;
-    const int nblocks = ((npairs + 7) / 8) * 8 * (ntok / 256);         // pairs padded to whole rounds of the 8 XCDs (the surplus workgroups return at once)
-    hipLaunchKernelGGL(attn2_kernel, dim3(nblocks), dim3(256), lds, s, qk, vt, att, ntok, heads * 64, heads, npairs);
+template <int KT, int NW, bool MASKED>
+void launch_chunks(const AttentionPlan& a, const bf16* qk, const bf16* vt, bf16* att, int ntok, int heads, hipStream_t s) {
+    static PerDeviceMax optin;
+    launch_planned(attn_kernel<KT, NW, MASKED>, optin, a, s, qk, vt, att, ntok, heads * 64, a.nbuf);
 }
 
 }  // namespace
 
 void launch_attention(const bf16* qk, const bf16* vt, bf16* att, int batch, int ntok, int heads,
                       hipStream_t s) {
-    // 256 tokens: two unsynchronised 4-wave workgroups per CU, each staging its (sample, head)'s K / V^T once (attn1_kernel; the single
-    // 8-wave workgroup it replaced took 60 us against 44 at C1).  512+ tokens: the chunked two-query-tile kernel (attn2_kernel).
-    // (At the C1 shape the inference engine no longer comes here: its self-attention runs in the QKV GEMM's epilogue, EPI_QKV_ATTN.)
-    // (128 and 32 tokens carry no launch-path bit: no square token grid has them, only tld_debug_attention_fwd comes here with those counts)
-    if (ntok == 256) { note_path(EP_ATT_256); launch_attn1<8, 4, 2, true>(qk, vt, att, batch, ntok, heads, s); }
-    else if (ntok % 256 == 0) { note_path(EP_ATT_CHUNKED); launch_attn2(qk, vt, att, batch, ntok, heads, s); }
-    else if (ntok == 128) { launch_kt<4, 4>(qk, vt, att, batch, ntok, heads, s); }
-    else if (ntok == 64) { note_path(EP_ATT_64); launch_kt<2, 2>(qk, vt, att, batch, ntok, heads, s); }
-    else if (ntok == 32) { launch_kt<1, 1>(qk, vt, att, batch, ntok, heads, s); }
-    else { note_path(EP_ATT_MASKED); launch_masked(qk, vt, att, batch, ntok, heads, s); }      // any other multiple of 8 (tld_engine_create checks)
+    const AttentionPlan a = plan_attention(batch, ntok, heads);
+    note_paths(a.paths);
+    static PerDeviceMax optin1, optin2;
+    switch (a.form) {
+        case ATT_256: launch_planned(attn1_kernel<8, 4, 2, true>, optin1, a, s, qk, vt, att, ntok, heads * 64); break;
+        case ATT_CHUNKED: launch_planned(attn2_kernel, optin2, a, s, qk, vt, att, ntok, heads * 64, heads, (int)a.npairs); break;
+        case ATT_ONE_CHUNK:
+            if (a.kt == 4) launch_chunks<4, 4, false>(a, qk, vt, att, ntok, heads, s);
+            else if (a.kt == 2) launch_chunks<2, 2, false>(a, qk, vt, att, ntok, heads, s);
+            else launch_chunks<1, 1, false>(a, qk, vt, att, ntok, heads, s);
+            break;
+        case ATT_MASKED: launch_chunks<4, 4, true>(a, qk, vt, att, ntok, heads, s); break;
+    }
 }
 
 }  // namespace tld

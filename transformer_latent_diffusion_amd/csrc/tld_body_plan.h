@@ -16,23 +16,13 @@
 
 #include "../../include/tld_hip.h"
 #include "tld_gemm_plan.h"            // gemm_resid_stat_slots, kLnSlots, bf16, resid_t
+#include "tld_launch_plan.h"          // kResidBf16; which widths the row kernels have (layernorm_mx8_supported, cross_row_supports_ln3_stats, splitk_resid_supported) and their LDS
 #include "tld_qkv_pair_plan.h"        // plan_qkv_pair
 #include "tld_reach.h"                // body_reach_check: the sizes the kernels' 32-bit offsets and 16-bit grid axes end at
 #include "tld_stages.h"               // ST_*: the element types of the stage hook
 #include "tld_tail_fold_math.h"       // tail_fold_padded_rows
 
 namespace tld {
-
-#ifdef TLD_RESID_BF16
-constexpr bool kResidBf16 = true;
-#else
-constexpr bool kResidBf16 = false;    // the folds and the fp8 mode feed the bf16 residual stream straight to the MFMA: none of them in the fp32-residual build
-#endif
-
-// ---- shape predicates of the row kernels (tld_rows.hip) the mode depends on --------------------------------------------------------------------------------
-inline bool layernorm_mx8_supported(int d) { return d == 256 || d == 512 || d == 768; }      // (the fp8 mode stops at embed_dim 896: d % 128 == 0 below the engine's 1024)
-inline bool cross_row_supports_ln3_stats(int d) { return d == 768 || d == 512 || d == 256; } // the LN3-statistics output (CrossRowParams::ln3_stats) exists in the matrix-pipe kernel only
-inline bool splitk_resid_supported(int d) { return d == 768 || d == 384; }
 
 // ---- the derived shape of a configuration (after body_config_check) ------------------------------------------------------------------------------------------
 struct BodyShape { int d, L, H, grid, ntok, pd, hid, img, ne, text; };
@@ -79,8 +69,8 @@ inline std::string body_config_check(const tld_config& c, int ndev) {
     if (ndev < 0) return std::string();
     if (c.device_id < 0 || c.device_id >= ndev) return body_say("device_id %d out of range (%d devices)", c.device_id, ndev);
     // the row kernels keep per-workgroup tables in dynamic LDS (opted in above the 64-KiB default; a CU has 160 KiB)
-    const long d = c.embed_dim, H = d / 64;
-    const long embed_lds = (pd * d + (long)pd * pd) * 4, tail_lds = pd * d * 4, cross_lds = (H * d + 2 * d + H) * 4, lim = 160 * 1024;
+    const int d = c.embed_dim;
+    const long embed_lds = embed_plain_lds(pd, pd, d), tail_lds = tail_plain_lds(pd, d), cross_lds = cross_row_valu_lds(d, d / 64), lim = kLdsLimit;      // the plain forms'
     if (embed_lds > lim || tail_lds > lim || cross_lds > lim)
         return body_say("embed_dim=%d with patch_dim=%d needs %ld / %ld / %ld bytes of LDS in the embed / out-proj / cross-attention row kernels (limit %ld each): "
                         "reduce patch_size*patch_size*n_channels or embed_dim", c.embed_dim, pd, embed_lds, tail_lds, cross_lds, lim);

@@ -8,6 +8,7 @@
 #include "tld_sampler_rows.h"     // SamplerStepRow, SamplerNoiseRow: the rows of the sampler's staged upload
 #include "tld_qkv_pair_plan.h"    // plan_qkv_pair: one or two heads per tile of the fused QKV + attention kernel
 #include "tld_gemm_plan.h"        // GemmParams, GemmEpilogue, bf16, resid_t, kLnSlots (tld_gemm_params.h); GemmPlan, gemm_resid_stat_slots
+#include "tld_launch_plan.h"      // EP_*: the launch-path bits; plan_embed .. plan_attention: the row and attention launches
 
 namespace tld {
 
@@ -304,32 +305,10 @@ inline int device_cu_count() {
     return c;
 }
 
-// ---- launch-path record of the engine's stage hook (tld_engine_debug_paths; the table in include/tld_hip.h) -------------------------------
-// Each bit is set inside the branch that launches the kernel.  The sink is null unless a debug forward of an engine runs on this thread: with
-// debug off a launch costs one thread-local load and a not-taken branch.
-enum : int {
-    EP_EMBED_PLAIN = 0, EP_EMBED_MFMA = 1 /* +0..3: TPW 2, 4, 6, 8 */, EP_LN_Q4 = 5 /* +0..3: q4<1..4> */, EP_LN_GENERIC = 9, EP_LN_MX8 = 10,
-    EP_QKV_ATTN = 11, EP_QKV_LN = 12, EP_QKV_PLAIN = 13,
-    EP_ATT_256 = 14, EP_ATT_CHUNKED = 15, EP_ATT_64 = 17 /* 18: unused (32 tokens: no square grid); 16: EP_TAIL_FOLD below */, EP_ATT_MASKED = 19,
-    EP_CROSS_MFMA = 20 /* +0..3: NQ 1..4 */, EP_CROSS_GPW1 = 24, EP_CROSS_GPWN = 25, EP_CROSS_VALU = 26, EP_CROSS_FANOUT = 27,
-    EP_UP_FUSED16 = 28, EP_UP_FUSED32_SEAM = 29, EP_UP_FUSED16_SMALL = 30, EP_UP_PLAIN = 31, EP_DW_WHOLE = 32, EP_DW_TILED = 33, EP_DW_STREAM = 34,
-    EP_DOWN_STATS = 35, EP_DOWN_NOSTATS = 36, EP_DOWN_MAIN = 37, EP_DOWN_SMALL64 = 38, EP_DOWN_SMALL128 = 39,
-    EP_SPLITK4 = 40, EP_SPLITK8 = 41, EP_SPLITK_SMALL = 42, EP_SPLITK_FINISH12 = 43, EP_SPLITK_FINISH6 = 44,
-    EP_TAIL_MFMA = 45 /* +0..3: NT 1..4 */, EP_TAIL_PLAIN = 49, EP_UPDATE = 50, EP_UPDATE_FROM = 51, EP_UPDATE_FROM_MASK = 52, EP_START_MIX = 53,
-    // fp8 GEMM mode, the writers of the MX-fp8 A operand (bit 10 is the quantising LayerNorm)
-    EP_QUANT_MX8 = 54, EP_CROSS_F8 = 55, EP_DW_TILED_F8 = 56, EP_DW_STREAM_F8 = 57,
-    // tld_sample_requests
-    EP_UPDATE_REQ = 58, EP_UPDATE_REQ_MASK = 59, EP_START_MIX_REQ = 60,
-    // out_proj folded into the last block's down projection (bit 16 was unused): set next to the EP_TAIL_MFMA bit of the launch's patch-feature tiles
-    EP_TAIL_FOLD = 16,
-    // fused QKV + attention on two-head tiles (EPI_QKV_ATTN2); a launch sets this bit INSTEAD of EP_QKV_ATTN
-    EP_QKV_ATTN_PAIR = 61,
-    // the step of a sampler session (tld_session_step)
-    EP_UPDATE_SESSION = 62,
-    EP_COUNT = 63
-};
+// ---- launch-path record of the engine's stage hook: the EP_* bits are in tld_launch_plan.h, beside the plans that predict them ---------------------
 extern thread_local uint64_t* g_path_sink;
 inline void note_path(int bit) { if (g_path_sink) *g_path_sink |= 1ull << bit; }
+inline void note_paths(uint64_t bits) { if (g_path_sink) *g_path_sink |= bits; }      // a plan's `paths`
 
 // Executes plan_gemm's answer (tld_gemm_plan.h) for this device and the process's switches.  TLD_OK, or TLD_ERR_INVALID with the reason in tld_last_error() when
 // nothing was launched: a plain launch whose operand rows lie beyond the reach of the kernels' 32-bit DMA offsets, or a refused plan
@@ -383,7 +362,7 @@ void launch_embed(const EmbedParams& p, hipStream_t s);
 void launch_layernorm_bf16(const resid_t* x, const float* g, const float* b, bf16* out, int M, int d,
                            hipStream_t s);
 // the same rows straight into the fp8 GEMM's operand format: e4m3 [M,d] + E8M0 scales [d/128][M][4]  (d % 256 == 0)
-// (widths: layernorm_mx8_supported, tld_body_plan.h)
+// (widths: layernorm_mx8_supported, tld_launch_plan.h)
 void launch_layernorm_mx8(const resid_t* x, const float* g, const float* b, uint8_t* out8, uint8_t* scale8, int M, int d,
                           hipStream_t s);
 
@@ -412,8 +391,8 @@ struct CrossRowParams {
     int batch, ntok, d, heads;
 };
 void launch_cross_row(const CrossRowParams& p, hipStream_t s);
-// (which widths write LN3 statistics: cross_row_supports_ln3_stats, tld_body_plan.h)
-// split-K finish of the low-latency down projection: x += bias + sum of the fp32 slices (+ LayerNorm-1 partial sums); d = 768 / 384 (splitk_resid_supported, tld_body_plan.h)
+// (which widths write LN3 statistics: cross_row_supports_ln3_stats, tld_launch_plan.h)
+// split-K finish of the low-latency down projection: x += bias + sum of the fp32 slices (+ LayerNorm-1 partial sums); d = 768 / 384 (splitk_resid_supported, tld_launch_plan.h)
 void launch_splitk_resid(const float* parts, int nsplit, size_t slice_stride, const float* bias, resid_t* x, float2* stats_out, int M, int d, hipStream_t s);
 
 struct TailParams {

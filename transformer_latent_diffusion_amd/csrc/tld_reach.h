@@ -13,6 +13,7 @@
 
 #include "../../include/tld_hip.h"
 #include "tld_gemm_plan.h"            // gemm_offsets_fit
+#include "tld_launch_plan.h"          // plan_dwconv, plan_attention: the form and the workgroup count of the two hooks' launches
 #include "tld_train_plan.h"           // kTrainTransposeMargin, train_dw_fused: the training step's workspace and forms
 
 namespace tld {
@@ -120,31 +121,25 @@ inline std::string clip_reach_check(int max_batch, int rows, int width, int patc
 // tld_debug_dwconv_gelu.  The row-streaming kernel (grid a multiple of 32) writes through 32-bit byte offsets from the buffer's base: batch x grid^2 x channels
 // x 2 B must stay below 4 GiB.  The whole-image kernel (grid <= 16) and the tiled one (other grids) address in 64 bits and keep accepting; all three compute
 // their workgroup count in an int.
-inline int64_t dwconv_hook_blocks(int batch, int grid, int channels) {
-    const int64_t chunks = channels / 64;
-    if (grid > 16 && grid % 32 == 0) return (int64_t)batch * (grid / 32) * chunks;
-    if (grid > 16) { const int64_t t = (grid + 15) / 16; return (int64_t)batch * t * t * chunks; }
-    return (int64_t)batch * chunks;
-}
 inline std::string dwconv_hook_refusal(int batch, int grid, int channels) {
+    const DwconvPlan w = plan_dwconv(batch, grid, channels, false);
     const uint64_t bytes = (uint64_t)batch * grid * grid * channels * 2;
-    if (grid > 16 && grid % 32 == 0 && bytes >= kReach32)
+    if (w.form == DW_STREAM && bytes >= kReach32)
         return reach_say("tld_debug_dwconv_gelu: batch %d x %d x %d tokens x %d channels = %llu bytes: the row-streaming kernel (grids that are multiples of 32) writes through "
                          "32-bit byte offsets and needs the buffer below 4 GiB; the largest batch that fits is %lld", batch, grid, grid, channels, (unsigned long long)bytes,
                          (long long)((kReach32 - 1) / ((uint64_t)grid * grid * channels * 2)));
-    if (dwconv_hook_blocks(batch, grid, channels) > kGridX)
-        return reach_say("tld_debug_dwconv_gelu: %lld workgroups (batch %d, grid %d, %d channels) do not fit the launch's 32-bit count", (long long)dwconv_hook_blocks(batch, grid, channels),
-                         batch, grid, channels);
+    if (w.groups > kGridX)
+        return reach_say("tld_debug_dwconv_gelu: %lld workgroups (batch %d, grid %d, %d channels) do not fit the launch's 32-bit count", (long long)w.groups, batch, grid, channels);
     return std::string();
 }
 // tld_debug_attention_fwd.  Every kernel addresses qk, vt and att in 64 bits: no size is refused for its bytes.  All but the chunked kernel (token counts that
 // are multiples of 256 above 256) put the sample on the grid's z axis and the head on y.
 inline std::string attention_fwd_hook_refusal(int batch, int ntok, int heads) {
-    const bool chunked = ntok > 256 && ntok % 256 == 0;
-    if (!chunked && (batch > kGridYZ || heads > kGridYZ))
+    const AttentionPlan a = plan_attention(batch, ntok, heads);
+    if (a.form != ATT_CHUNKED && (a.gz > kGridYZ || a.gy > kGridYZ))
         return reach_say("tld_debug_attention_fwd: batch %d, heads %d: at %d tokens the kernel puts heads and samples on the grid's y and z axes (at most %lld each)", batch, heads, ntok,
                          (long long)kGridYZ);
-    if (chunked && (((int64_t)batch * heads + 7) / 8) * 8 * (ntok / 256) > kGridX)
+    if (a.form == ATT_CHUNKED && a.groups > kGridX)
         return reach_say("tld_debug_attention_fwd: batch %d x heads %d x %d query tiles do not fit the launch's 32-bit workgroup count", batch, heads, ntok / 256);
     return std::string();
 }

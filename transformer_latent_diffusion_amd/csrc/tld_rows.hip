@@ -1420,7 +1420,7 @@ __global__ __launch_bounds__(256) void sampler_noise_debug_kernel(const uint64_t
 // exactly once (the register-window version re-read each row three times through L2).  Thread (row i,
 // channel quad) then slides a 3x3 fp32 window along j: 3 ds_read_b64 + 36 FMAs + 4 GELUs + one 8-B
 // store per position; weights stay in registers.  GELU uses the Abramowitz-Stegun erf (1.5e-7).
-constexpr int DW_CB = 64;                       // channels per workgroup
+constexpr int DW_CB = kDwChannels;              // channels per workgroup (tld_launch_plan.h: the launch's grid counts them)
 __global__ __launch_bounds__(256) void dwconv_gelu_kernel(const bf16* __restrict__ in, bf16* __restrict__ out,
                                                           const float* __restrict__ w9c,
                                                           const float* __restrict__ bias, int batch,
@@ -1648,79 +1648,55 @@ __global__ __launch_bounds__(256) void dwconv_gelu_tiled_kernel(const bf16* __re
             optin.run((bytes), [&] { hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (bytes)); }); \
     } while (0)
 
+// The launchers below: make the plan (tld_launch_plan.h: every size-dependent decision), note its paths, switch on its form, launch.
 void launch_embed(const EmbedParams& p, hipStream_t s) {
+    const EmbedPlan e = plan_embed(p.batch, p.ntok, p.pd, p.C * p.p * p.p, p.d, p.lin_w_hl != nullptr);
+    const dim3 grid(e.gx), block(e.block);
+    note_paths(e.paths);
 #ifdef TLD_RESID_BF16
-    if (p.lin_w_hl && p.pd == 16 && p.C * p.p * p.p == 16 && p.d % 256 == 0 && p.d <= 1024) {       // matrix-pipe form
-        const int rows = p.batch * p.ntok;
-        const int lds = 16 * 16 * 4 + 4 * 4 * 32 * 4 + 3 * p.d * 4 + 4 * 32 * 144;      // conv weight, row partials, bias / LayerNorm vectors, transpose patches
-        dim3 grid((unsigned)((rows + 31) / 32));
-#define TLD_EM(TPW) do { TLD_LDS_OPT_IN((embed_mfma_kernel<TPW>), lds); hipLaunchKernelGGL((embed_mfma_kernel<TPW>), grid, dim3(256), lds, s, p, p.lin_w_hl); } while (0)
-        note_path(EP_EMBED_MFMA + p.d / 256 - 1);
-        if (p.d == 256) TLD_EM(2); else if (p.d == 512) TLD_EM(4); else if (p.d == 768) TLD_EM(6); else TLD_EM(8);
+    if (e.form == EMBED_MFMA) {
+#define TLD_EM(TPW) do { TLD_LDS_OPT_IN((embed_mfma_kernel<TPW>), e.lds); hipLaunchKernelGGL((embed_mfma_kernel<TPW>), grid, block, e.lds, s, p, p.lin_w_hl); } while (0)
+        switch (e.tpw) { case 2: TLD_EM(2); break; case 4: TLD_EM(4); break; case 6: TLD_EM(6); break; default: TLD_EM(8); break; }
 #undef TLD_EM
         return;
     }
 #endif
-    const int rows = p.batch * p.ntok;
-    const int lds = (p.pd * p.d + p.pd * p.C * p.p * p.p) * (int)sizeof(float);
-    note_path(EP_EMBED_PLAIN);
-    TLD_DISPATCH_D(p.d, { TLD_LDS_OPT_IN((embed_kernel<NJ, HALF>), lds); hipLaunchKernelGGL((embed_kernel<NJ, HALF>), dim3((rows + 31) / 32), dim3(256), lds, s, p); });
+    TLD_DISPATCH_D(p.d, { TLD_LDS_OPT_IN((embed_kernel<NJ, HALF>), e.lds); hipLaunchKernelGGL((embed_kernel<NJ, HALF>), grid, block, e.lds, s, p); });
 }
 
 void launch_layernorm_bf16(const resid_t* x, const float* g, const float* b, bf16* out, int M, int d,
                            hipStream_t s) {
-    if (d == 768 || d == 512 || d == 256 || d == 1024) note_path(EP_LN_Q4 + d / 256 - 1); else note_path(EP_LN_GENERIC);
-    if (d == 768) { hipLaunchKernelGGL(layernorm_bf16_q4_kernel<3>, dim3((M + 3) / 4), dim3(256), 0, s, x, g, b, out, M, d); return; }
-    if (d == 512) { hipLaunchKernelGGL(layernorm_bf16_q4_kernel<2>, dim3((M + 3) / 4), dim3(256), 0, s, x, g, b, out, M, d); return; }
-    if (d == 256) { hipLaunchKernelGGL(layernorm_bf16_q4_kernel<1>, dim3((M + 3) / 4), dim3(256), 0, s, x, g, b, out, M, d); return; }
-    if (d == 1024) { hipLaunchKernelGGL(layernorm_bf16_q4_kernel<4>, dim3((M + 3) / 4), dim3(256), 0, s, x, g, b, out, M, d); return; }
-    TLD_DISPATCH_D(d, hipLaunchKernelGGL((layernorm_bf16_kernel<NJ, HALF>), dim3((M + 3) / 4), dim3(256), 0, s, x, g, b, out, M, d));
+    const LayerNormPlan n = plan_layernorm(M, d, false);
+    const dim3 grid(n.gx), block(n.block);
+    note_paths(n.paths);
+#define TLD_LNQ(NQ) hipLaunchKernelGGL(layernorm_bf16_q4_kernel<NQ>, grid, block, 0, s, x, g, b, out, M, d)
+    if (n.form == LN_Q4) switch (n.nq) { case 1: TLD_LNQ(1); break; case 2: TLD_LNQ(2); break; case 3: TLD_LNQ(3); break; default: TLD_LNQ(4); break; }
+    else TLD_DISPATCH_D(d, hipLaunchKernelGGL((layernorm_bf16_kernel<NJ, HALF>), grid, block, 0, s, x, g, b, out, M, d));
+#undef TLD_LNQ
 }
 
 void launch_layernorm_mx8(const resid_t* x, const float* g, const float* b, uint8_t* out8, uint8_t* scale8, int M, int d,
                           hipStream_t s) {
-    const dim3 gr((M + 3) / 4), bl(256);
-    note_path(EP_LN_MX8);
-    if (d == 768) hipLaunchKernelGGL(layernorm_mx8_kernel<3>, gr, bl, 0, s, x, g, b, out8, scale8, M, d);
-    else if (d == 512) hipLaunchKernelGGL(layernorm_mx8_kernel<2>, gr, bl, 0, s, x, g, b, out8, scale8, M, d);
-    else if (d == 256) hipLaunchKernelGGL(layernorm_mx8_kernel<1>, gr, bl, 0, s, x, g, b, out8, scale8, M, d);
+    const LayerNormPlan n = plan_layernorm(M, d, true);
+    const dim3 grid(n.gx), block(n.block);
+    note_paths(n.paths);
+    if (n.form != LN_MX8) return;      // LN_NONE: no such kernel at this width (unreachable: the engine's mode asks layernorm_mx8_supported first)
+#define TLD_LN8(NQ) hipLaunchKernelGGL(layernorm_mx8_kernel<NQ>, grid, block, 0, s, x, g, b, out8, scale8, M, d)
+    switch (n.nq) { case 1: TLD_LN8(1); break; case 2: TLD_LN8(2); break; default: TLD_LN8(3); break; }
+#undef TLD_LN8
 }
 
 void launch_cross_row(const CrossRowParams& p, hipStream_t s) {
-    if (p.d % 256 == 0 && p.d <= 1024 && p.ntok % 16 == 0) {
-        // 512-thread workgroups over 16-row groups of one sample, ONE per CU (the kernel holds ~170 registers at d = 768: the split-bf16 slices of
-        // the query-difference vectors and the prefetched row pair live in registers; two workgroups per CU at 128 registers spilled and ran
-        // 43.7 us against 38.0).  Groups per workgroup: the largest power of two (<= 16) that divides a sample's groups and still leaves >= 1
-        // workgroup per CU (at C1: 128 samples x 16 groups / 8 = 256 workgroups = one resident round)
-        const int gps = p.ntok / 16;
-        const long want = device_cu_count();
-        int gpw = 1;
-        while (gpw < 16 && gps % (gpw * 2) == 0 && (long)p.batch * (gps / (gpw * 2)) >= want) gpw *= 2;
-        const int ldsm = 2 * 16 * p.d * 2 + 8 * 256 * 4 + 2 * p.d * 4;     // split-bf16 tile, partial logits, the two value rows
-        dim3 gridm((unsigned)(p.batch * (gps / gpw)));
-#define TLD_CRM(NQ) do { TLD_LDS_OPT_IN((cross_row_mfma_kernel<NQ>), ldsm); hipLaunchKernelGGL((cross_row_mfma_kernel<NQ>), gridm, dim3(512), ldsm, s, p, gpw); } while (0)
-        note_path(EP_CROSS_MFMA + p.d / 256 - 1); note_path(gpw > 1 ? EP_CROSS_GPWN : EP_CROSS_GPW1);
-        if (p.x_in) note_path(EP_CROSS_FANOUT);
-        if (p.xn3_f8) note_path(EP_CROSS_F8);
-        if (p.d == 256) TLD_CRM(1); else if (p.d == 512) TLD_CRM(2); else if (p.d == 768) TLD_CRM(3); else TLD_CRM(4);
+    const CrossRowPlan c = plan_cross_row(p.batch, p.ntok, p.d, p.heads, p.x_in != nullptr, p.xn3_f8 != nullptr, device_cu_count());
+    const dim3 grid(c.gx), block(c.block);
+    note_paths(c.paths);
+    if (c.form == CROSS_MFMA) {
+#define TLD_CRM(NQ) do { TLD_LDS_OPT_IN((cross_row_mfma_kernel<NQ>), c.lds); hipLaunchKernelGGL((cross_row_mfma_kernel<NQ>), grid, block, c.lds, s, p, c.gpw); } while (0)
+        switch (c.nq) { case 1: TLD_CRM(1); break; case 2: TLD_CRM(2); break; case 3: TLD_CRM(3); break; default: TLD_CRM(4); break; }
 #undef TLD_CRM
         return;
     }
-    // other widths (any multiple of 64): the 2-features-per-lane VALU kernel.  ~43 KB of LDS per workgroup -> 3 workgroups per CU.  Split each
-    // sample's row pairs into the number of chunks that makes the grid ONE full resident round (768 workgroups on 256 CUs) when the batch
-    // allows, else k rounds of <= ~48 rows per workgroup; a partial extra round costs as much as a full one.
-    const int slots = 3 * device_cu_count();
-    const long rows = (long)p.batch * p.ntok;
-    const long k = (rows + (long)slots * 48 - 1) / ((long)slots * 48);
-    long cps = slots * k / p.batch;
-    const long max_cps = p.ntok / 8 > 0 ? p.ntok / 8 : 1;          // at least one row pair per wave
-    if (cps > max_cps) cps = max_cps;
-    if (cps < 1) cps = 1;
-    const int lds = (p.heads * p.d + 2 * p.d + p.heads) * (int)sizeof(float);
-    dim3 grid((unsigned)(p.batch * cps));
-    note_path(EP_CROSS_VALU);
-    if (p.x_in) note_path(EP_CROSS_FANOUT);
-    TLD_DISPATCH_D(p.d, { TLD_LDS_OPT_IN((cross_row_kernel<NJ, HALF>), lds); hipLaunchKernelGGL((cross_row_kernel<NJ, HALF>), grid, dim3(256), lds, s, p, (int)cps); });
+    TLD_DISPATCH_D(p.d, { TLD_LDS_OPT_IN((cross_row_kernel<NJ, HALF>), c.lds); hipLaunchKernelGGL((cross_row_kernel<NJ, HALF>), grid, block, c.lds, s, p, c.cps); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1770,46 +1746,37 @@ __global__ __launch_bounds__(256) void splitk_resid_kernel(const float* __restri
 }
 
 void launch_splitk_resid(const float* parts, int nsplit, size_t slice_stride, const float* bias, resid_t* x, float2* stats_out, int M, int d, hipStream_t s) {
-    const dim3 grid((unsigned)((M + 3) / 4)), block(256);
-    if (d == 768) { note_path(EP_SPLITK_FINISH12); hipLaunchKernelGGL(splitk_resid_kernel<12>, grid, block, 0, s, parts, nsplit, slice_stride, bias, x, stats_out, M); }
-    else if (d == 384) { note_path(EP_SPLITK_FINISH6); hipLaunchKernelGGL(splitk_resid_kernel<6>, grid, block, 0, s, parts, nsplit, slice_stride, bias, x, stats_out, M); }
+    const SplitkFinishPlan f = plan_splitk_finish(M, d);
+    const dim3 grid(f.gx), block(f.block);
+    note_paths(f.paths);
+    if (f.form == SKF_CPL12) hipLaunchKernelGGL(splitk_resid_kernel<12>, grid, block, 0, s, parts, nsplit, slice_stride, bias, x, stats_out, M);
+    else if (f.form == SKF_CPL6) hipLaunchKernelGGL(splitk_resid_kernel<6>, grid, block, 0, s, parts, nsplit, slice_stride, bias, x, stats_out, M);
 }
 
 void launch_tail(const TailParams& p, hipStream_t s) {
+    const TailPlan t = plan_tail(p.batch, p.ntok, p.pd, p.d, p.hid != nullptr, p.w_hl != nullptr, device_cu_count());
+    const dim3 grid(t.gx), block(t.block);
+    note_paths(t.paths);
 #ifdef TLD_RESID_BF16
-    if (p.hid) {      // folded form: tok = x2, hid = hid2 of the last block (any d, any hid: both are multiples of 64)
-        const int nt = (p.pd + 15) / 16, rows = p.batch * p.ntok;
-        // row tiles per workgroup: as many as keep a fragment's re-use high while every CU still has a workgroup; LDS 8 RT NT KiB <= 64 KiB
-        const int big = nt <= 2 ? 4 : 2;
-        const int rt = rows >= 16 * big * device_cu_count() ? big : 1;
-        const int lds = 8 * rt * nt * 1024;
-        dim3 grid((unsigned)((rows + 16 * rt - 1) / (16 * rt)));
-#define TLD_TF(NT, RT) hipLaunchKernelGGL((tail_fold_kernel<NT, RT>), grid, dim3(512), lds, s, p)
-        note_path(EP_TAIL_MFMA + nt - 1); note_path(EP_TAIL_FOLD);
-        if (nt == 1) { if (rt == 1) TLD_TF(1, 1); else TLD_TF(1, 4); }
-        else if (nt == 2) { if (rt == 1) TLD_TF(2, 1); else TLD_TF(2, 4); }
-        else if (nt == 3) { if (rt == 1) TLD_TF(3, 1); else TLD_TF(3, 2); }
-        else { if (rt == 1) TLD_TF(4, 1); else TLD_TF(4, 2); }
+    if (t.form == TAIL_FOLD) {
+#define TLD_TF(NT, RT) hipLaunchKernelGGL((tail_fold_kernel<NT, RT>), grid, block, t.lds, s, p)
+        switch (t.nt) {
+            case 1: if (t.rt == 1) TLD_TF(1, 1); else TLD_TF(1, 4); break;
+            case 2: if (t.rt == 1) TLD_TF(2, 1); else TLD_TF(2, 4); break;
+            case 3: if (t.rt == 1) TLD_TF(3, 1); else TLD_TF(3, 2); break;
+            default: if (t.rt == 1) TLD_TF(4, 1); else TLD_TF(4, 2); break;
+        }
 #undef TLD_TF
         return;
     }
-    if (p.w_hl && p.d % 128 == 0 && (long)p.pd * p.d <= 40960) {      // matrix-pipe form: split-bf16 weights [2][pd][d] in <= 160 KiB of LDS (the XOR swizzle of its
-                                                                      // weight image permutes 16-byte chunks within aligned groups of 16: rows of d / 8 = 16 k chunks)
-        const int nt = (p.pd + 15) / 16, rows = p.batch * p.ntok;
-        const int lds = 2 * nt * 16 * p.d * 2;
-        dim3 grid((unsigned)((rows + 63) / 64));
-#define TLD_TM(NT) do { TLD_LDS_OPT_IN((tail_mfma_kernel<NT>), lds); hipLaunchKernelGGL((tail_mfma_kernel<NT>), grid, dim3(256), lds, s, p, p.w_hl); } while (0)
-        note_path(EP_TAIL_MFMA + (nt < 4 ? nt : 4) - 1);
-        if (nt == 1) TLD_TM(1); else if (nt == 2) TLD_TM(2); else if (nt == 3) TLD_TM(3); else TLD_TM(4);
+    if (t.form == TAIL_MFMA) {
+#define TLD_TM(NT) do { TLD_LDS_OPT_IN((tail_mfma_kernel<NT>), t.lds); hipLaunchKernelGGL((tail_mfma_kernel<NT>), grid, block, t.lds, s, p, p.w_hl); } while (0)
+        switch (t.nt) { case 1: TLD_TM(1); break; case 2: TLD_TM(2); break; case 3: TLD_TM(3); break; default: TLD_TM(4); break; }
 #undef TLD_TM
         return;
     }
 #endif
-    const int rpb = 64;
-    const int rows = p.batch * p.ntok;
-    const int lds = p.pd * p.d * (int)sizeof(float);
-    note_path(EP_TAIL_PLAIN);
-    TLD_DISPATCH_D(p.d, { TLD_LDS_OPT_IN((tail_kernel<NJ, HALF>), lds); hipLaunchKernelGGL((tail_kernel<NJ, HALF>), dim3((rows + rpb - 1) / rpb), dim3(256), lds, s, p, rpb); });
+    TLD_DISPATCH_D(p.d, { TLD_LDS_OPT_IN((tail_kernel<NJ, HALF>), t.lds); hipLaunchKernelGGL((tail_kernel<NJ, HALF>), grid, block, t.lds, s, p, t.rows_per_block); });
 }
 
 #ifdef TLD_RESID_BF16
@@ -2112,29 +2079,20 @@ void launch_dwconv_seam(const uint32_t* seam, const uint32_t* dw_wpk, const floa
 void launch_dwconv_gelu(const bf16* in, bf16* out, const float* w9c, const float* bias, const float* w9c_half,
                         const float* bias_half, int batch, int grid, int channels, hipStream_t s, uint8_t* out8,
                         uint8_t* scale8) {
-    if (grid > 16 && grid % 32 == 0) {       // row-streaming variant (ring of image rows in LDS, a DMA wave); halved tables
-        const dim3 gr((unsigned)(batch * (grid / 32) * (channels / DW_CB)));
-        note_path(EP_DW_STREAM);
-        if (out8) note_path(EP_DW_STREAM_F8);
-        if (out8) hipLaunchKernelGGL(dwconv_gelu_stream_kernel<true>, gr, dim3(320), 0, s, in, out, w9c_half, bias_half, batch, grid, channels, out8, scale8);
-        else hipLaunchKernelGGL(dwconv_gelu_stream_kernel<false>, gr, dim3(320), 0, s, in, out, w9c_half, bias_half, batch, grid, channels, out8, scale8);
-        return;
+    const DwconvPlan w = plan_dwconv(batch, grid, channels, out8 != nullptr);
+    const dim3 gr(w.gx), block(w.block);
+    note_paths(w.paths);
+    switch (w.form) {       // the streaming and the tiled kernel take the halved tables
+        case DW_STREAM:
+            if (w.f8) hipLaunchKernelGGL(dwconv_gelu_stream_kernel<true>, gr, block, 0, s, in, out, w9c_half, bias_half, batch, grid, channels, out8, scale8);
+            else hipLaunchKernelGGL(dwconv_gelu_stream_kernel<false>, gr, block, 0, s, in, out, w9c_half, bias_half, batch, grid, channels, out8, scale8);
+            break;
+        case DW_TILED:
+            if (w.f8) hipLaunchKernelGGL(dwconv_gelu_tiled_kernel<true>, gr, block, 0, s, in, out, w9c_half, bias_half, batch, grid, channels, out8, scale8);
+            else hipLaunchKernelGGL(dwconv_gelu_tiled_kernel<false>, gr, block, 0, s, in, out, w9c_half, bias_half, batch, grid, channels, out8, scale8);
+            break;
+        case DW_WHOLE: hipLaunchKernelGGL(dwconv_gelu_kernel, gr, block, w.lds, s, in, out, w9c, bias, batch, grid, channels); break;
     }
-    if (grid > 16) {        // spatially tiled variant (halo in LDS); takes the halved tables
-        const int tiles = (grid + 15) / 16;
-        const dim3 gr((unsigned)(batch * tiles * tiles * (channels / DW_CB)));
-        note_path(EP_DW_TILED);
-        if (out8) note_path(EP_DW_TILED_F8);
-        if (out8) hipLaunchKernelGGL(dwconv_gelu_tiled_kernel<true>, gr, dim3(256), 0, s, in, out, w9c_half, bias_half, batch, grid,
-                                     channels, out8, scale8);
-        else hipLaunchKernelGGL(dwconv_gelu_tiled_kernel<false>, gr, dim3(256), 0, s, in, out, w9c_half, bias_half, batch, grid,
-                                channels, out8, scale8);
-        return;
-    }
-    const int lds = grid * grid * 128;
-    note_path(EP_DW_WHOLE);
-    hipLaunchKernelGGL(dwconv_gelu_kernel, dim3((unsigned)(batch * (channels / DW_CB))), dim3(256), lds, s, in, out,
-                       w9c, bias, batch, grid, channels);
 }
 
 }  // namespace tld
